@@ -27,7 +27,7 @@ import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-import chinesechesszero_amd  # noqa: E402,F401  (first: sets GPU_MAX_HW_QUEUES before anything initialises HIP -- see its __init__)
+import chinesechesszero_amd  # noqa: E402,F401
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
@@ -94,7 +94,50 @@ def parse():
     ap.add_argument("--inject-fault", default="", help="testing: RANK:STEP raises on that rank at that timed step (the fail-fast path)")
     ap.add_argument("--value-f16", action="store_true", help="accumulate Q in float16 as the reference's CUDA path does (CCZ_FLAG_VALUE_F16, "
                     "net.py:178-189 -> mcts.py:63-71); default: float32, its CPU path")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed window, rank 0 writes what the timed path left for its "
+                    "caller after its last step -- the root statistics of every board's search, pi, the pending leaves, the last moves played, "
+                    "the game states -- as DIR/<name>.npy (float32 / float64, at most 64 MB: a fixed sample of boards beyond that)")
     return ap.parse_args()
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(e, out_dir: str):
+    """What the timed path hands its caller after its last step, as DIR/<name>.npy: the search state of every board (root children:
+    action ids, visits, Q, priors; pi at temperature 1; the leaves the last step selected for the next evaluation) plus the moves of
+    the last move played and the game states. Arrays are float32 (float64 for pi); ``board_index`` says which boards they hold: all of
+    them, or a fixed seeded sample when the whole set would exceed DUMP_MAX_BYTES. Synchronous reads; the window is over."""
+    from chinesechesszero_amd._lib import MAX_LEGAL
+    B = e.B
+    per_board = MAX_LEGAL * (5 * 4 + 8) + 12 * 4
+    idx = np.arange(B)
+    if B * per_board > DUMP_MAX_BYTES:
+        idx = np.sort(np.random.RandomState(0).choice(B, DUMP_MAX_BYTES // per_board, replace=False))
+    rc, leaf, st = e.root_children(), e.leaf_info(), e.game_status()
+    arrays = {
+        "board_index": idx.astype(np.float32),
+        "root_k": rc["k"][idx].astype(np.float32),
+        "root_visits_total": rc["root_visits"][idx].astype(np.float32),
+        "root_actions": rc["acts"][idx].astype(np.float32),
+        "root_visits": rc["visits"][idx].astype(np.float32),
+        "root_q": rc["q"][idx].astype(np.float32),
+        "root_prior": rc["prior"][idx].astype(np.float32),
+        "root_pi": e.root_pi()[idx].astype(np.float64),
+        "leaf_status": leaf["status"][idx].astype(np.float32),
+        "leaf_k": leaf["k"][idx].astype(np.float32),
+        "leaf_ids": leaf["ids"][idx].astype(np.float32),
+        "leaf_depth": leaf["depth"][idx].astype(np.float32),
+        "last_moves": e.moves_out.cpu().numpy()[idx].astype(np.float32),
+        "game_over": st["over"][idx].astype(np.float32),
+        "game_winner": st["winner"][idx].astype(np.float32),
+        "game_plies": st["plies"][idx].astype(np.float32),
+        "game_turn": st["turn"][idx].astype(np.float32),
+    }
+    assert sum(v.nbytes for v in arrays.values()) <= DUMP_MAX_BYTES
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v)
 
 
 def host_cores() -> int:
@@ -637,6 +680,8 @@ def main():
         rank_xchg_max_call_ms = [float(v) for v in t[2 * world + 4:3 * world + 4].tolist()]
         dev_all = [int(v) for v in t[3 * world + 4:3 * world + 8].tolist()]
     e.check_healthy()
+    if a.dump_outputs and rank == 0:
+        dump_outputs(e, a.dump_outputs)
     st_end = e.game_status()
     sims = s1["sims"] - s0["sims"]
     probes = s1["cache_probes"] - s0["cache_probes"]
@@ -795,7 +840,7 @@ def main():
             "error_flags_any": err_any,
             "plies": {"start_mean": float(plies0.mean()), "start_max": int(plies0.max()), "end_mean": float(plies1.mean())},
             "setup_seconds": setup_s,
-            "gpu_max_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"),   # (chinesechesszero_amd/__init__.py: the tower's launch chains need queues of their own)
+            "gpu_max_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"),   # (the environment's: with few queues the tower's launch chains share them)
         }
         if multi:
             xg = gather if gather is not None else ex

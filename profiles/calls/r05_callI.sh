@@ -1,4 +1,4 @@
-# round 5: after the hardware-queue fix (package default GPU_MAX_HW_QUEUES=8): the full-size window plain and with the N>1 path in a group of one on RCCL,
+# round 5: after the hardware-queue fix (then: eight hardware queues by package default): the full-size window plain and with the N>1 path in a group of one on RCCL,
 # asynchronous and blocking exchange, one box, interleaved; then the new test
 O=gpurun_out
 set -e

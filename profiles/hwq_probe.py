@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Hardware-queue aliasing probe (round 5). The 40x256 evaluator on 4096 synthetic rows, timed in a process that also holds the streams of the
-multi-GPU exchange. argv: group (0|1) order (exchange_first|eval_first|init_only) ; env GPU_MAX_HW_QUEUES as given (the package default is 8).
+multi-GPU exchange. argv: group (0|1) order (exchange_first|eval_first|init_only) ; the hardware-queue count is the environment's.
   exchange_first: process group + a USED exchange (side stream, RCCL stream) before the evaluator's first evaluation
   eval_first:     process group initialised, evaluator used, THEN the exchange used (bench.py's order: the first boundary comes after the first step)
   init_only:      process group initialised, exchange never used
@@ -13,8 +13,6 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-if os.environ.get("CCZ_NO_QUEUE_DEFAULT"):      # measure HIP's own default (4): keep the package from setting 8
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", "4")
 import chinesechesszero_amd  # noqa: E402,F401
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402

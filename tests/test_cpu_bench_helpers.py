@@ -102,3 +102,63 @@ def test_a_library_older_than_its_sources_is_refused(tmp_path, monkeypatch):
         _lib.lib()
     os.remove(root / "chinesechesszero_amd" / "libcczero.so.srchash")
     assert "carries no source stamp" in _lib.stale_build()
+
+
+class _FakeEngine:
+    """The inspection calls bench.dump_outputs makes, with the shapes and dtypes of SelfPlayEngine's (engine.py)."""
+
+    def __init__(self, B):
+        import numpy as np
+        import torch
+        rs = np.random.RandomState(B)
+        self.B = B
+        self._rc = {"k": rs.randint(0, 128, B).astype(np.int32), "acts": rs.randint(0, 2086, (B, 128)).astype(np.uint16),
+                    "visits": rs.randint(0, 400, (B, 128)).astype(np.int32), "q": rs.randn(B, 128).astype(np.float32),
+                    "prior": rs.rand(B, 128).astype(np.float32), "root_visits": rs.randint(0, 400, B).astype(np.int32)}
+        self._leaf = {"status": rs.randint(0, 3, B).astype(np.uint8), "k": rs.randint(0, 128, B).astype(np.int32),
+                      "ids": rs.randint(0, 2086, (B, 128)).astype(np.uint16), "depth": rs.randint(0, 30, B).astype(np.int32)}
+        self._st = {"over": rs.randint(0, 2, B).astype(np.uint8), "winner": rs.randint(-1, 2, B).astype(np.int8),
+                    "plies": rs.randint(0, 200, B).astype(np.int32), "turn": rs.randint(0, 2, B).astype(np.uint8)}
+        self.pi = rs.rand(B, 128)
+        self.moves_out = torch.from_numpy(rs.randint(-1, 2086, B).astype(np.int32))
+
+    def root_children(self):
+        return self._rc
+
+    def leaf_info(self):
+        return self._leaf
+
+    def game_status(self):
+        return self._st
+
+    def root_pi(self):
+        return self.pi
+
+
+def test_dump_outputs_writes_every_board_as_float_arrays(tmp_path):
+    import numpy as np
+    import bench
+    e = _FakeEngine(48)
+    bench.dump_outputs(e, str(tmp_path / "out"))
+    got = {f[:-4]: np.load(tmp_path / "out" / f) for f in os.listdir(tmp_path / "out")}
+    assert set(got) >= {"board_index", "root_actions", "root_visits", "root_q", "root_prior", "root_pi", "leaf_ids", "last_moves", "game_plies"}
+    assert all(v.dtype in (np.float32, np.float64) and v.shape[0] == 48 for v in got.values())
+    assert np.array_equal(got["board_index"], np.arange(48)) and got["root_pi"].dtype == np.float64
+    assert np.array_equal(got["root_visits"], e._rc["visits"]) and np.array_equal(got["root_actions"], e._rc["acts"])
+    assert np.array_equal(got["root_q"], e._rc["q"]) and np.array_equal(got["root_pi"], e.pi)
+    assert np.array_equal(got["leaf_ids"], e._leaf["ids"]) and np.array_equal(got["game_winner"], e._st["winner"])
+    assert np.array_equal(got["last_moves"], e.moves_out.numpy())
+
+
+def test_dump_outputs_samples_a_fixed_set_of_boards_under_the_size_cap(tmp_path, monkeypatch):
+    import numpy as np
+    import bench
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 40 * (128 * 28 + 48))   # room for 40 of the 100 boards
+    e = _FakeEngine(100)
+    for d in ("a", "b"):
+        bench.dump_outputs(e, str(tmp_path / d))
+    total = sum(os.path.getsize(tmp_path / "a" / f) - 128 for f in os.listdir(tmp_path / "a"))   # (minus each .npy header)
+    assert total <= bench.DUMP_MAX_BYTES
+    idx = np.load(tmp_path / "a" / "board_index.npy")
+    assert len(idx) == 40 and np.all(np.diff(idx) > 0) and np.array_equal(idx, np.load(tmp_path / "b" / "board_index.npy"))
+    assert np.array_equal(np.load(tmp_path / "a" / "root_q.npy"), e._rc["q"][idx.astype(np.int64)])

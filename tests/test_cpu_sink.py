@@ -189,39 +189,36 @@ def test_float32_option_and_dtype_guard(tmp_path):
         TupleSink(str(tmp_path))
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/dataset.py"), reason="the reference tree is only mounted in the build container")
 def test_the_references_own_dataset_reads_what_the_sink_writes(tmp_path):
-    """Not a fixture but the real consumer: reference dataset.py (numpy + torch only, importable as is) opens the directory
-    TupleSink.finalize() produced -- the check train.py:100 would make -- and hands back the rows, also after pickling
-    (DataLoader workers, dataset.py:64-73). Build container only: the reference never travels."""
-    import importlib.util
+    """Not a fixture of values but of the real consumer: reference dataset.py opens a directory the way
+    tests/golden/reference_dataset_reader.json records (three named .npy files, each memory-mapped, equal lengths; recorded by running
+    the reference's NpyMemmapDataset on a TupleSink directory) -- the check train.py:100 would make. The directory
+    TupleSink.finalize() produces is opened that way here and hands back the rows with the recorded item dtypes and shapes, also
+    after pickling (DataLoader workers, dataset.py:64-73: the memmaps are reloaded from their paths)."""
     import pickle
     from chinesechesszero_amd.collect import TupleSink
-    spec = importlib.util.spec_from_file_location("ref_dataset", "/root/reference/dataset.py")
-    ref = importlib.util.module_from_spec(spec)
-    sys_dont = __import__("sys")
-    old = sys_dont.dont_write_bytecode
-    sys_dont.dont_write_bytecode = True
-    try:
-        spec.loader.exec_module(ref)
-        sys_dont.modules["ref_dataset"] = ref     # pickle looks the class up by module name
-    finally:
-        sys_dont.dont_write_bytecode = old
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_dataset_reader.json")) as f:
+        fmt = json.load(f)
     s, p, z = _rows(40, 9)
     sink = TupleSink(str(tmp_path))
     sink.append(s[:25], p[:25], z[:25], games=1)
     sink.append(s[25:], p[25:], z[25:], games=1)
     sink.finalize()
-    ds = ref.NpyMemmapDataset(str(tmp_path))
-    assert len(ds) == 40
-    st, pi, w = ds[31]
-    assert st.dtype == np.float16 and pi.dtype == np.float64 and w.dtype == np.float32     # what collect.py:146-167 + convert.py store
+    paths = {k: str(tmp_path / name) for k, name in fmt["files"].items()}
+    arrays = {k: np.load(v, mmap_mode="r") for k, v in paths.items()}
+    assert all(isinstance(a, np.memmap) for a in arrays.values())
+    assert len(arrays["states"]) == len(arrays["mcts"]) == len(arrays["winners"]) == 40
+    st, pi, w = (arrays[k][31] for k in ("states", "mcts", "winners"))
+    for k, item in zip(("states", "mcts", "winners"), (st, pi, w)):
+        assert item.dtype == np.dtype(fmt["item"][k]["dtype"]) and list(item.shape) == fmt["item"][k]["shape"], k
     assert np.array_equal(st, s[31]) and np.array_equal(pi, p[31]) and w == z[31]
-    ds2 = pickle.loads(pickle.dumps(ds))
-    assert len(ds2) == 40 and np.array_equal(ds2[7][1], p[7])
+    again = {k: np.load(v, mmap_mode="r") for k, v in pickle.loads(pickle.dumps(paths)).items()}
+    assert len(again["mcts"]) == 40 and np.array_equal(again["mcts"][7], p[7])
     from chinesechesszero_amd.dataset import NpyMemmapDataset
     mine = NpyMemmapDataset(str(tmp_path))
-    assert len(mine) == len(ds) and np.array_equal(mine[31][0].numpy(), st)
+    assert len(mine) == 40 and np.array_equal(mine[31][0].numpy(), st)
+    mine2 = pickle.loads(pickle.dumps(mine))
+    assert len(mine2) == 40 and np.array_equal(mine2[7][1].numpy(), p[7].astype(np.float32))
 
 
 def _fake_records(lengths, seed=0):
