@@ -97,6 +97,9 @@ PROTOTYPES = {
     "ccz_scouted_run": (C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
     "ccz_gather_priors_planned": (C.c_int, [_P, _P, _P, C.c_int32, _P]),
     "ccz_eval_cache_clear": (C.c_int, [_P, _P]),
+    "ccz_set_routing": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint64]),
+    "ccz_eval_plan_routed": (C.c_int, [_P, _P, _P, _P]),
+    "ccz_gather_priors_routed": (C.c_int, [_P, _P, _P, _P, C.c_int32, _P, _P]),
     "ccz_finish_move": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32]),
     "ccz_root_children": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
     "ccz_root_pi": (C.c_int, [_P, _P, _P, _P]),

@@ -75,6 +75,11 @@ struct ccz_engine {
     uint8_t *st_mask = nullptr, *st_sq = nullptr;
     std::vector<BoardMeta> h_meta;
     int active = 0; // boards 0 .. active - 1 are searched; the rest are scout slots (ccz_set_scouts); 0 = all
+    // two evaluators on one engine (ccz_set_routing): which one plays red on each board, which one owns each board's pending search
+    bool routed = false;
+    uint8_t *route_red = nullptr;  // [B] device
+    uint8_t *route_net = nullptr;  // [B] device: written by k_cache_probe_routed, read by the plan and the gather
+    uint64_t salt[2] = {0, 0};
 };
 
 #define ACTIVE(e) ((unsigned)((e)->active > 0 ? (e)->active : (e)->d.B))
@@ -465,6 +470,69 @@ int ccz_gather_priors_planned(ccz_engine *e, void *stream, const void *logits_co
         hipLaunchKernelGGL((k_softmax_gather<_Float16, true>), dim3(e->d.B), dim3(64), 0, s, e->d, (const _Float16 *)logits_compact_dev, value_compact_dev);
     else
         hipLaunchKernelGGL((k_softmax_gather<float, true>), dim3(e->d.B), dim3(64), 0, s, e->d, (const float *)logits_compact_dev, value_compact_dev);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int ccz_set_routing(ccz_engine *e, void *stream, const uint8_t *red_net_host, uint64_t salt0, uint64_t salt1)
+{
+    NEED(e);
+    if (!red_net_host) {
+        e->routed = false;
+        return 0;
+    }
+    if (!e->d.cache) return fail(-1, "ccz_set_routing: routing works through the evaluation cache (ccz_config.eval_cache_log2)");
+    if (e->active > 0) return fail(-1, "ccz_set_routing: not with scout slots (ccz_set_scouts)");
+    if (salt0 == salt1) return fail(-1, "ccz_set_routing: the two evaluators need different salts (one would be served the other's evaluations)");
+    for (int b = 0; b < e->d.B; ++b)
+        if (red_net_host[b] > 1) return fail(-1, "ccz_set_routing: red_net[%d] = %d (must be 0 or 1)", b, (int)red_net_host[b]);
+    hipError_t he = hipSuccess;
+    if (!e->route_red) {
+        he = dalloc(&e->route_red, (size_t)e->d.B, e->owned, e->bytes);
+        if (he == hipSuccess) he = dalloc(&e->route_net, (size_t)e->d.B, e->owned, e->bytes);
+    }
+    HIP_TRY(he);
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(hipMemcpyAsync(e->route_red, red_net_host, (size_t)e->d.B, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s)); // (the host array may go away after the call)
+    e->salt[0] = salt0;
+    e->salt[1] = salt1;
+    e->routed = true;
+    return 0;
+}
+
+int ccz_eval_plan_routed(ccz_engine *e, void *stream, int32_t *miss_rows_dev, int32_t *n_miss_dev)
+{
+    NEED(e);
+    if (!e->routed) return fail(-1, "ccz_eval_plan_routed: no routing set (ccz_set_routing)");
+    if (!e->d.cache) return fail(-1, "ccz_eval_plan_routed: the engine was created without an evaluation cache");
+    if (e->active > 0) return fail(-1, "ccz_eval_plan_routed: not with scout slots (ccz_set_scouts)");
+    if (!miss_rows_dev || !n_miss_dev) return fail(-1, "ccz_eval_plan_routed: null output");
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_cache_probe_routed, dim3(e->d.B), dim3(64), 0, s, e->d, (const uint8_t *)e->route_red, e->route_net, e->salt[0], e->salt[1]);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_cache_plan_routed, dim3(1), dim3(1024), 0, s, e->d, miss_rows_dev, n_miss_dev, (const uint8_t *)e->route_net,
+                       e->salt[0], e->salt[1]);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int ccz_gather_priors_routed(ccz_engine *e, void *stream, const void *logits0_dev, const void *logits1_dev, int32_t logits_f16,
+                             const float *value0_dev, const float *value1_dev)
+{
+    NEED(e);
+    if (!e->routed) return fail(-1, "ccz_gather_priors_routed: no routing set (ccz_set_routing)");
+    if (!e->d.cache) return fail(-1, "ccz_gather_priors_routed: the engine was created without an evaluation cache");
+    if (e->active > 0) return fail(-1, "ccz_gather_priors_routed: not with scout slots (ccz_set_scouts)");
+    if (!logits0_dev || !logits1_dev || !value0_dev || !value1_dev) return fail(-1, "ccz_gather_priors_routed: null logits / value");
+    hipStream_t s = (hipStream_t)stream;
+    const uint8_t *net = e->route_net;
+    if (logits_f16)
+        hipLaunchKernelGGL(k_softmax_gather_routed<_Float16>, dim3(e->d.B), dim3(64), 0, s, e->d, net, (const _Float16 *)logits0_dev,
+                           (const _Float16 *)logits1_dev, value0_dev, value1_dev, e->salt[0], e->salt[1]);
+    else
+        hipLaunchKernelGGL(k_softmax_gather_routed<float>, dim3(e->d.B), dim3(64), 0, s, e->d, net, (const float *)logits0_dev,
+                           (const float *)logits1_dev, value0_dev, value1_dev, e->salt[0], e->salt[1]);
     HIP_TRY(hipGetLastError());
     return 0;
 }

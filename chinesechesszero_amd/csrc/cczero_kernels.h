@@ -649,11 +649,11 @@ __device__ __forceinline__ uint32_t cache_tag(int id0, int id1, int k, int lane)
 // PLANNED: the evaluator ran on the compact rows of k_cache_plan; board b's logits sit in row row_of[b] of `logits`, its value in
 // vcompact[row_of[b]]; cache hits already hold their priors and value (k_cache_probe); a fresh evaluation whose board won the
 // slot's claim is stored in the cache.
+// `salt` is XORed into the key an entry is stored under (ccz_set_routing: one table, two evaluators; 0 = the plain key).
 template <typename T, bool PLANNED>
-__global__ __launch_bounds__(64) void k_softmax_gather(Dev D, const T *logits, const float *vcompact)
+__device__ __forceinline__ void softmax_gather_board(const Dev &D, int b, int lane, float *row, const T *logits, const float *vcompact,
+                                                     uint64_t salt)
 {
-    const int b = blockIdx.x, lane = threadIdx.x;
-    __shared__ __attribute__((aligned(16))) float row[kNMoves + 2];
     // everything the wave needs to know about its board is requested at once (one memory round trip instead of a chain of four:
     // status -> state -> row -> logits); a board that turns out to have nothing to do leaves after it
     const int status = D.leaf_status[b];
@@ -738,12 +738,31 @@ __global__ __launch_bounds__(64) void k_softmax_gather(Dev D, const T *logits, c
             const uint32_t tag = cache_tag(id0, id1, k, lane);
             e->pri[lane] = p0;
             e->pri[64 + lane] = p1;
-            if (lane == 0) { e->v = v; e->k = tag; e->key = D.leaf_key[b]; D.stats[b].cache_stores += 1u; }
+            if (lane == 0) { e->v = v; e->k = tag; e->key = D.leaf_key[b] ^ salt; D.stats[b].cache_stores += 1u; }
         }
     } else {
         if (lane < k) out[lane] = p0;
         if (64 + lane < k) out[64 + lane] = p1;
     }
+}
+
+template <typename T, bool PLANNED>
+__global__ __launch_bounds__(64) void k_softmax_gather(Dev D, const T *logits, const float *vcompact)
+{
+    __shared__ __attribute__((aligned(16))) float row[kNMoves + 2];
+    softmax_gather_board<T, PLANNED>(D, blockIdx.x, threadIdx.x, row, logits, vcompact, 0ull);
+}
+
+// ROUTED (ccz_gather_priors_routed): board b's leaf was planned for evaluator net[b] (k_cache_probe_routed); its logits / value sit
+// in that evaluator's compact output, row row_of[b] of its segment, and a fresh evaluation is stored under that evaluator's salt.
+template <typename T>
+__global__ __launch_bounds__(64) void k_softmax_gather_routed(Dev D, const uint8_t *net, const T *logits0, const T *logits1,
+                                                              const float *v0, const float *v1, uint64_t salt0, uint64_t salt1)
+{
+    __shared__ __attribute__((aligned(16))) float row[kNMoves + 2];
+    const int b = blockIdx.x;
+    const int n = net[b];
+    softmax_gather_board<T, true>(D, b, threadIdx.x, row, n ? logits1 : logits0, n ? v1 : v0, n ? salt1 : salt0);
 }
 
 // ------------------------------------------------------------------ evaluation cache: probe, plan
@@ -752,10 +771,11 @@ __device__ __forceinline__ uint32_t cache_slot(uint64_t key, uint32_t mask) { re
 // One wave per board: look the pending leaf up. Hit: its priors and value go straight to prior128 / vleaf. Miss: the board
 // bids for the slot (lowest board index wins: deterministic) -- the winner's evaluation will be stored there, and boards that
 // missed with the SAME key in this step share the winner's evaluator row (k_cache_plan).
-__device__ inline int cache_probe_wave(const Dev &D, int b, int lane) // returns the board's plan state (wave-uniform): 0 miss, 1 hit, 2 nothing to evaluate
+// `salt`: XORed into the key before the slot is chosen and the entry compared (ccz_set_routing; 0 = the plain key).
+__device__ inline int cache_probe_wave(const Dev &D, int b, int lane, uint64_t salt = 0) // returns the board's plan state (wave-uniform): 0 miss, 1 hit, 2 nothing to evaluate
 {
     const int status = D.leaf_status[b];
-    const uint64_t key = D.leaf_key[b]; // (requested together with the status: one round trip less in front of the table access)
+    const uint64_t key = D.leaf_key[b] ^ salt; // (requested together with the status: one round trip less in front of the table access)
     if (status != CCZ_LEAF_EXPAND) {
         if (lane == 0) D.cstate[b] = 2;
         return 2;
@@ -792,21 +812,36 @@ __device__ inline int cache_probe_wave(const Dev &D, int b, int lane) // returns
 
 __global__ __launch_bounds__(64) void k_cache_probe(Dev D) { (void)cache_probe_wave(D, blockIdx.x, threadIdx.x); }
 
+// Routed probe (ccz_set_routing): the search on board b belongs to the evaluator that owns the ROOT's side to move -- red_net[b] on
+// a red move, the other one on a black move (game.py:77-130 with two MCTS_AI players: the player to move searches with its own
+// net, whoever is to move at the leaf). net_out[b] <- that evaluator; the board probes under that evaluator's salted key.
+__global__ __launch_bounds__(64) void k_cache_probe_routed(Dev D, const uint8_t *red_net, uint8_t *net_out, uint64_t salt0, uint64_t salt1)
+{
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int n = D.meta[b].turn ? red_net[b] : 1 - red_net[b];
+    if (lane == 0) net_out[b] = (uint8_t)n;
+    (void)cache_probe_wave(D, b, lane, n ? salt1 : salt0);
+}
+
 // One workgroup: representatives and the compaction plan. A miss whose slot was won by a board with the same key uses that
 // board's row; every other miss is its own representative (a different key on the same slot is evaluated but not stored).
 // miss_rows[0 .. n_miss) = the representatives in ascending board order: the rows the evaluator computes.
-__global__ __launch_bounds__(1024) void k_cache_plan(Dev D, int32_t *miss_rows, int32_t *n_miss)
+// ROUTED (ccz_eval_plan_routed): every board belongs to evaluator net[b] (k_cache_probe_routed) and its key is salted with that
+// evaluator's salt; a row is shared only between boards of the same evaluator, and the representatives are compacted into one
+// segment per evaluator: evaluator 0 at miss_rows[0 .. n_miss[0]), evaluator 1 at miss_rows[B .. B + n_miss[1]); row_of[b] is the
+// row within the board's own segment.
+template <bool ROUTED>
+__device__ __forceinline__ void cache_plan_block(const Dev &D, int32_t *miss_rows, int32_t *n_miss, const uint8_t *net, uint64_t salt0,
+                                                 uint64_t salt1, int (&s_wave)[2][16], int (&s_base)[2])
 {
-    __shared__ int s_wave[16];
-    __shared__ int s_base;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    if (tid == 0) s_base = 0;
+    if (tid == 0) s_base[0] = s_base[1] = 0;
     __syncthreads();
     // 4096 boards per pass: a thread looks after boards b0 + tid + 1024 i, i = 0..3. The three dependent load rounds (state / slot /
     // key -> claim -> the claimant's state and key) are issued for all four boards before any is used, so a pass costs three memory
     // round trips instead of twelve (this kernel is one workgroup: nothing else hides its latency)
     for (int b0 = 0; b0 < D.B; b0 += 4096) {
-        int st[4], w[4], rep[4];
+        int st[4], w[4], rep[4], nt[4];
         uint32_t slot[4], tag[4];
         uint64_t key[4];
 #pragma unroll
@@ -816,7 +851,12 @@ __global__ __launch_bounds__(1024) void k_cache_plan(Dev D, int32_t *miss_rows, 
             slot[i] = 0;
             tag[i] = 0;
             key[i] = 0;
-            if (b < D.B) { st[i] = D.cstate[b]; slot[i] = D.cslot[b]; key[i] = D.leaf_key[b]; tag[i] = D.ctag[b]; }
+            nt[i] = 0;
+            if (b < D.B) {
+                st[i] = D.cstate[b]; slot[i] = D.cslot[b]; key[i] = D.leaf_key[b]; tag[i] = D.ctag[b];
+                if (ROUTED) nt[i] = net[b];
+            }
+            if (ROUTED) key[i] ^= nt[i] ? salt1 : salt0;
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) w[i] = st[i] == 0 ? D.claim[slot[i]] : -1;
@@ -829,7 +869,13 @@ __global__ __launch_bounds__(1024) void k_cache_plan(Dev D, int32_t *miss_rows, 
             if (st[i] == 0 && w[i] >= 0 && w[i] < b) {
                 // the same position = the same 64-bit key AND the same legal-move list (count + 24-bit hash of the list in prior order):
                 // what a table hit is checked against (k_cache_probe), now also between two leaves of one step (round 6)
-                const bool same = D.cstate[w[i]] == 0 && D.leaf_key[w[i]] == key[i] && D.ctag[w[i]] == tag[i];
+                bool same = D.cstate[w[i]] == 0 && D.ctag[w[i]] == tag[i];
+                if (ROUTED) {   // (the claim winner of a slot may be the other evaluator's board: never share its row)
+                    const int nw = net[w[i]];
+                    same = same && nw == nt[i] && (D.leaf_key[w[i]] ^ (nw ? salt1 : salt0)) == key[i];
+                } else {
+                    same = same && D.leaf_key[w[i]] == key[i];
+                }
                 rep[i] = same ? w[i] : b;
             }
         }
@@ -843,26 +889,34 @@ __global__ __launch_bounds__(1024) void k_cache_plan(Dev D, int32_t *miss_rows, 
                 isrep = rep[i] == b;
                 if (!isrep) D.stats[b].cache_shared += 1u;
             }
-            // exclusive position of every representative: ballot inside the wave, 16 wave totals through LDS
-            const uint64_t m = __ballot(isrep);
-            const int in_wave = __popcll(m & lanemask_lt(lane)), wave_total = __popcll(m);
-            if (lane == 0) s_wave[wv] = wave_total;
+            // exclusive position of every representative in its segment: ballot inside the wave, 16 wave totals through LDS
+            const uint64_t m0 = __ballot(isrep && nt[i] == 0);
+            const uint64_t m1 = ROUTED ? __ballot(isrep && nt[i] == 1) : 0ull;
+            const int in_wave = __popcll((nt[i] ? m1 : m0) & lanemask_lt(lane));
+            if (lane == 0) {
+                s_wave[0][wv] = __popcll(m0);
+                if (ROUTED) s_wave[1][wv] = __popcll(m1);
+            }
             __syncthreads();
-            int before = 0, total = 0;
+            int before = 0, total0 = 0, total1 = 0;
 #pragma unroll
             for (int j = 0; j < 16; ++j) {
-                const int t = s_wave[j];
-                before += j < wv ? t : 0;
-                total += t;
+                const int t0 = s_wave[0][j], t1 = ROUTED ? s_wave[1][j] : 0;
+                before += j < wv ? (nt[i] ? t1 : t0) : 0;
+                total0 += t0;
+                total1 += t1;
             }
-            const int base = s_base;
+            const int base0 = s_base[0], base1 = ROUTED ? s_base[1] : 0;
             if (isrep) {
-                const int pos = base + before + in_wave;
+                const int pos = (nt[i] ? base1 : base0) + before + in_wave;
                 D.row_of[b] = pos;
-                miss_rows[pos] = b;
+                miss_rows[(nt[i] ? D.B : 0) + pos] = b;
             }
             __syncthreads();
-            if (tid == 0) s_base = base + total;
+            if (tid == 0) {
+                s_base[0] = base0 + total0;
+                if (ROUTED) s_base[1] = base1 + total1;
+            }
             __syncthreads();
         }
         // boards that use another board's row: the representative is the slot's claim winner, i.e. a LOWER board index -- its row
@@ -876,7 +930,25 @@ __global__ __launch_bounds__(1024) void k_cache_plan(Dev D, int32_t *miss_rows, 
                 D.row_of[b] = __hip_atomic_load(D.row_of + rep[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
-    if (tid == 0) *n_miss = s_base;
+    if (tid == 0) {
+        n_miss[0] = s_base[0];
+        if (ROUTED) n_miss[1] = s_base[1];
+    }
+}
+
+__global__ __launch_bounds__(1024) void k_cache_plan(Dev D, int32_t *miss_rows, int32_t *n_miss)
+{
+    __shared__ int s_wave[2][16];
+    __shared__ int s_base[2];
+    cache_plan_block<false>(D, miss_rows, n_miss, nullptr, 0ull, 0ull, s_wave, s_base);
+}
+
+__global__ __launch_bounds__(1024) void k_cache_plan_routed(Dev D, int32_t *miss_rows, int32_t *n_miss, const uint8_t *net, uint64_t salt0,
+                                                            uint64_t salt1)
+{
+    __shared__ int s_wave[2][16];
+    __shared__ int s_base[2];
+    cache_plan_block<true>(D, miss_rows, n_miss, net, salt0, salt1, s_wave, s_base);
 }
 
 // The plan of a step with scouts (ccz_eval_plan_scouted): the evaluator runs -- on ALL slots, row b = slot b, a fixed small batch --

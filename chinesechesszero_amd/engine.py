@@ -278,6 +278,47 @@ class SelfPlayEngine:
         """Forget every cached evaluation (the evaluator's weights changed)."""
         check(self.L.ccz_eval_cache_clear(self.h, self._stream()))
 
+    # ------------------------------------------------------------------ two evaluators on one engine (include/cczero.h ccz_set_routing)
+    def set_routing(self, red_net, salts=(0, 0)):
+        """``red_net`` [B] of 0 / 1: the evaluator that plays red on each board (black: the other one); None = routing off.
+        ``salts`` = (salt0, salt1), different: XORed into each evaluator's cache keys. A board's evaluator for a move is the owner
+        of the root's side to move (:meth:`eval_plan_routed`). Needs an evaluation cache and no scouts."""
+        if red_net is None:
+            check(self.L.ccz_set_routing(self.h, self._stream(), None, 0, 0))
+            return
+        rn = np.ascontiguousarray(red_net, dtype=np.uint8)
+        if rn.shape != (self.B,):
+            raise ValueError(f"red_net must have {self.B} entries")
+        s0, s1 = (int(x) & (2**64 - 1) for x in salts)
+        with torch.cuda.device(self.device):
+            check(self.L.ccz_set_routing(self.h, self._stream(), _ptr(rn), s0, s1))
+        if not hasattr(self, "miss_rows2"):
+            self.miss_rows2 = torch.zeros((2 * self.B,), dtype=torch.int32, device=self.device)
+            self.n_miss2 = torch.zeros((2,), dtype=torch.int32, device=self.device)
+
+    def eval_plan_routed(self):
+        """Probe + plan with the routing: ``(plan0, plan1)``, each ``(rows, n)`` device tensors for one evaluator's planned
+        boundary (``evaluate_leaves_logits(leaf, plan=...)``): evaluator 0's rows are ``miss_rows2[:B]``, evaluator 1's
+        ``miss_rows2[B:]``; the counts ``n_miss2[0:1]`` / ``n_miss2[1:2]`` stay on the device."""
+        check(self.L.ccz_eval_plan_routed(self.h, self._stream(), _ptr(self.miss_rows2), _ptr(self.n_miss2)))
+        B = self.B
+        return (self.miss_rows2[:B], self.n_miss2[0:1]), (self.miss_rows2[B:], self.n_miss2[1:2])
+
+    def gather_priors_routed(self, logits0, value0, logits1, value1):
+        """Each board takes its priors / value from the COMPACT output of its own evaluator (row = its row in that segment)."""
+        f16 = self._check_logits(logits0, value0)
+        if self._check_logits(logits1, value1) != f16:
+            raise TypeError("both evaluators must return logits of the same dtype")
+        check(self.L.ccz_gather_priors_routed(self.h, self._stream(), _ptr(logits0), _ptr(logits1), f16, _ptr(value0), _ptr(value1)))
+
+    def step_routed(self, logits0, value0, logits1, value1) -> torch.Tensor:
+        self.gather_priors_routed(logits0, value0, logits1, value1)
+        return self.step_compact(None)
+
+    def expand_backup_routed(self, logits0, value0, logits1, value1):
+        self.gather_priors_routed(logits0, value0, logits1, value1)
+        check(self.L.ccz_expand_backup_compact(self.h, self._stream(), None))
+
     # ------------------------------------------------------------------ once per move
     def finish_move(self, forced_moves=None, temps=None, keep_tree: bool = True) -> torch.Tensor:
         """Record pi, choose (or accept) the move, re-root, push, detect game end. Returns moves int32[B] (device)."""

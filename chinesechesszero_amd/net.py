@@ -135,6 +135,13 @@ class EvalOptions:
 
 
 _CHAIN_STREAMS: dict = {}
+# The launch chains' streams are created at this priority (lower = higher; torch.cuda.Stream). HIP keeps a separate pool of hardware
+# queues per priority: the chains then never share a queue with a normal-priority stream of the process -- the caller's stream, a
+# process group's, the exchange's -- whatever the order in which those were first used and however few queues the environment allows.
+# All chains of a tower run on these streams, chain 0 included: a chain left on the caller's normal-priority stream next to
+# high-priority ones is starved by them (the evaluator +12 %).
+CHAIN_STREAM_PRIORITY = -1
+N_CHAIN_STREAMS = 8   # every chain of a tower runs on one of these (tower_chains caps the chains at 8)
 
 
 def chain_streams(device):
@@ -143,13 +150,16 @@ def chain_streams(device):
     across the whole process (HIP: GPU_MAX_HW_QUEUES queues, later streams share); measured on one MI355X
     (profiles/r05_hwq_probe.txt): chains bound after the multi-GPU exchange's streams were in use cost the evaluator +6 % (eight or
     sixteen queues) to +21 % (HIP's default four), chains bound before them nothing. ``PolicyValueNet.refresh_inference_copy`` calls
-    this as soon as the first inference copy is on the device -- in every flow before the exchange is first used."""
+    this as soon as the first inference copy is on the device. A process group created with ``device_id`` (eager RCCL init) takes
+    queues before any net exists, and with four queues a chain stream then shared the caller's queue (+21 %, the same with or
+    without the exchange): so EVERY chain, the first one included, runs on one of these streams, at ``CHAIN_STREAM_PRIORITY`` (a
+    queue pool of its own), and the caller's stream only forks and joins them."""
     device = torch.device(device)
     if device.index is None:
         device = torch.device("cuda", torch.cuda.current_device())
     got = _CHAIN_STREAMS.get(device)
     if got is None:
-        got = [torch.cuda.Stream(device=device) for _ in range(7)]
+        got = [torch.cuda.Stream(device=device, priority=CHAIN_STREAM_PRIORITY) for _ in range(N_CHAIN_STREAMS)]
         cur = torch.cuda.current_stream(device)
         ev = torch.cuda.Event()
         ev.record(cur)
@@ -433,18 +443,18 @@ class InferenceNet(nn.Module):
         lay = (_lib.CONV_G16 | (_lib.CONV_G16_EDGE_TILES if edge else 0) | self._persistent_flag()) if g16 else 0
         if chains > 1:
             pool = getattr(self, "_chain_streams", None)
-            if pool is None or pool[0] != x.device or len(pool[1]) < chains - 1:
+            if pool is None or pool[0] != x.device or len(pool[1]) < chains:
                 pool = (x.device, chain_streams(x.device))
                 self._chain_streams = pool
         live = C.c_void_p(plan[1].data_ptr())
         xp, yp = C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr())
         down = 2 if self.opt.zigzag else 0
         for g in range(groups):
-            streams = [cur] + [self._chain_streams[1][k] for k in range(chains - 1)]
+            streams = [cur] if chains == 1 else [self._chain_streams[1][k] for k in range(chains)]
             if chains > 1:
                 fork = torch.cuda.Event()
                 fork.record(cur)
-                for st in streams[1:]:
+                for st in streams:
                     st.wait_event(fork)
             wsrc = self.ws_g16 if g16 else self.ws
             for i in range(0, len(self.ws), 2):
@@ -458,7 +468,7 @@ class InferenceNet(nn.Module):
                     continue
                 for k, st in enumerate(streams):
                     _lib.check(L.ccz_conv3x3_c256_f16_live(C.c_void_p(st.cuda_stream), yp, w2, b2_, xp, xp, cap, 1 | lay, live, g * chains + k, n_parts))
-            for st in streams[1:]:
+            for st in (streams if chains > 1 else []):
                 join = torch.cuda.Event()
                 join.record(st)
                 cur.wait_event(join)
@@ -476,7 +486,7 @@ class InferenceNet(nn.Module):
         bounds = [(lo + b0, lo + min(B, b0 + step)) for b0 in range(0, B, step)]
         if len(bounds) > 1:
             pool = getattr(self, "_chain_streams", None)
-            if pool is None or pool[0] != x.device or len(pool[1]) < len(bounds) - 1:
+            if pool is None or pool[0] != x.device or len(pool[1]) < len(bounds):
                 pool = (x.device, chain_streams(x.device))
                 self._chain_streams = pool
             fork = torch.cuda.Event()
@@ -484,8 +494,8 @@ class InferenceNet(nn.Module):
         row = 90 * 256 * x.element_size()
         chains = []
         for k, (b0, b1) in enumerate(bounds):
-            st = cur if k == 0 else self._chain_streams[1][k - 1]
-            if k:
+            st = cur if len(bounds) == 1 else self._chain_streams[1][k]
+            if len(bounds) > 1:
                 st.wait_event(fork)
             chains.append((st, C.c_void_p(st.cuda_stream), C.c_void_p(x.data_ptr() + b0 * row), C.c_void_p(y.data_ptr() + b0 * row), (b1 - b0) * 90, b0))
         # launches are enqueued layer by layer across the chains, so that the chains advance together (the same layer's
@@ -508,7 +518,7 @@ class InferenceNet(nn.Module):
                 continue
             for _, s, xp, yp, n_pixels, _b0 in chains:
                 _lib.check(L.ccz_conv3x3_c256_f16(s, yp, w2, b2_, xp, xp, n_pixels, 1 | v2))  # output written over the residual input
-        for st, *_ in chains[1:]:  # every side stream is joined into the current stream
+        for st, *_ in (chains if len(chains) > 1 else []):  # every chain stream is joined into the current stream
             join = torch.cuda.Event()
             join.record(st)
             cur.wait_event(join)

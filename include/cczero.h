@@ -280,6 +280,26 @@ int ccz_gather_priors_planned(ccz_engine *e, void *stream, const void *logits_co
                               const float *value_compact_dev);
 int ccz_eval_cache_clear(ccz_engine *e, void *stream);
 
+/* Two evaluators on one engine (an arena between two networks; needs the evaluation cache, no scout slots). The reference's
+ * Game.start_play (game.py:77-130) with two MCTS_AI players: the player to move at the ROOT searches with its own network, which
+ * evaluates every leaf of that search whoever is to move there; the tree is discarded after the move. So board b's evaluator is
+ * fixed for a whole move: red_net[b] when red is to move at the root, 1 - red_net[b] when black is.
+ *   ccz_set_routing: red_net_host uint8 [B] (0 or 1) = the evaluator that plays red on each board (NULL: routing off); salt0 /
+ *     salt1 (must differ) are XORed into the cache key of each evaluator's entries -- slot and stored key alike -- so one table holds
+ *     both networks' evaluations and never serves one network's to the other. New weights for one network: give it a new salt (its
+ *     old entries can then never hit; the other network's stay valid).
+ *   ccz_eval_plan_routed: ccz_eval_plan with the routing: miss_rows_dev int32 [2B], n_miss_dev int32 [2]. Rows are shared only
+ *     between boards of the same evaluator; evaluator 0's rows are miss_rows_dev[0 .. n_miss_dev[0]), evaluator 1's
+ *     miss_rows_dev[B .. B + n_miss_dev[1]), each ascending -- so each evaluator runs the planned boundary unchanged on
+ *     (miss_rows_dev + e * B, n_miss_dev + e), and both base pointers are known on the host. CCZ_FLAG_CACHE_VERIFY rows land in
+ *     their own evaluator's segment.
+ *   ccz_gather_priors_routed: ccz_gather_priors_planned with each board reading the compact output (logits_e, value_e) of its own
+ *     evaluator and storing under that evaluator's salt. Then ccz_step_compact / ccz_expand_backup_compact with value_dev == NULL. */
+int ccz_set_routing(ccz_engine *e, void *stream, const uint8_t *red_net_host, uint64_t salt0, uint64_t salt1);
+int ccz_eval_plan_routed(ccz_engine *e, void *stream, int32_t *miss_rows_dev, int32_t *n_miss_dev);
+int ccz_gather_priors_routed(ccz_engine *e, void *stream, const void *logits0_dev, const void *logits1_dev, int32_t logits_f16,
+                             const float *value0_dev, const float *value1_dev);
+
 /* ---- once per move ------------------------------------------------------------------------ */
 /* Replaces MCTS.get_move_probs' tail (mcts.py:162-166), MCTS_AI.get_action's choice
  * (mcts.py:216-224), MCTS.update_with_move (mcts.py:168-178) and the per-move part of
