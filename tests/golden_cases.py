@@ -20,7 +20,36 @@ STARTS = {
     "wide80": _place({"e1": 7, "a2": 3, "i7": 3, "b4": 2, "h5": 2, "c3": 4, "g6": 4, "a6": 1, "c7": 1, "e6": 1, "g7": 1, "i6": 1,
                       "d0": 6, "f0": 6, "c0": 5, "g0": 5, "d9": 15, "e8": 14, "a9": 11}),
     "pawns": _place({"d0": 7, "a3": 1, "c3": 1, "e3": 1, "g3": 1, "i3": 1, "f9": 15, "a6": 9, "c6": 9, "e6": 9, "g6": 9, "i6": 9}),
+    # widths around one wave (64 lanes): every per-board kernel holds legal move i and 64 + i in lane i (red to move)
+    "wide64": _place({"f0": 6, "e1": 7, "c3": 4, "b4": 2, "h5": 2, "a6": 1, "e6": 1, "g6": 4, "i6": 1, "c7": 1, "g7": 1, "d9": 15}),
+    "wide65": _place({"c0": 5, "g0": 5, "e1": 7, "g2": 3, "b3": 2, "e6": 1, "g6": 4, "g7": 2, "i7": 3, "d9": 15, "h9": 1}),
+    # 108 legal moves (a seeded hill-climb on the oracle); i2g0 (id 2067) is legal, so its mirror has id 2085 (i7g9) legal
+    "widest": _place({"e0": 7, "c1": 3, "d2": 6, "e2": 5, "g2": 4, "i2": 5, "h3": 2, "b4": 2, "a5": 3, "e6": 4, "g6": 1, "d7": 1,
+                      "f7": 1, "e8": 1, "g8": 1, "f9": 15}),
+    # the widest one with its a5 rook on a0: 103 legal moves, a0a1 (id 0, the first logit of the row) among them
+    "wide_a0": _place({"e0": 7, "a0": 3, "c1": 3, "d2": 6, "e2": 5, "g2": 4, "i2": 5, "h3": 2, "b4": 2, "e6": 4, "g6": 1, "d7": 1,
+                       "f7": 1, "e8": 1, "g8": 1, "f9": 15}),
+    "one_move": _place({"e0": 7, "b1": 11, "a2": 11, "d9": 15}),     # red king: f0 only (rank 1 is covered, d0 faces the king)
+    "mated": _place({"e0": 7, "b1": 11, "a0": 11, "d9": 15}),        # red king in check from a0, no legal move
 }
+
+
+def mirrored(squares: np.ndarray) -> np.ndarray:
+    """The same position seen from the other side: ranks reversed, colours swapped. With the other side to move it has the
+    same number of legal moves."""
+    b = np.asarray(squares, np.uint8).reshape(10, 9)[::-1].reshape(90).copy()
+    nz = b != 0
+    b[nz] ^= 8
+    return b
+
+
+for _name in ("wide64", "wide65", "widest", "wide_a0", "one_move", "mated"):
+    STARTS[_name + "_black"] = mirrored(STARTS[_name])
+
+# (side to move, number of legal moves) of the width fixtures; tests/test_cpu_wide_positions.py keeps them true
+WIDTHS = {"wide64": (1, 64), "wide65": (1, 65), "widest": (1, 108), "wide_a0": (1, 103), "one_move": (1, 1), "mated": (1, 0),
+          "wide80": (1, 80)}
+WIDTHS.update({n + "_black": (0, k) for n, (t, k) in list(WIDTHS.items()) if n != "wide80"})
 
 START_ROWS = ["RNBAKABNR", ".........", ".C.....C.", "P.P.P.P.P", ".........",
               ".........", "p.p.p.p.p", ".c.....c.", ".........", "rnbakabnr"]
