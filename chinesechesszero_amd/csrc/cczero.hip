@@ -939,6 +939,11 @@ static int conv3x3_launch(const char *who, void *stream, const void *x_dev, cons
             HIP_TRY(hipGetLastError());
             return 0;
         }
+        if (!pers && (relu & CCZ_CONV_G16_ONE_LAUNCH)) { // both tile classes in one launch (cczero_conv_g16e.h k_conv3x3_g16_one)
+            CCZ_G16(k_conv3x3_g16_one, groups * 4 + 2 * ((groups + 1) / 2), s, fl);
+            HIP_TRY(hipGetLastError());
+            return 0;
+        }
         if (pers) CCZ_G16(k_conv3x3_g16_pers, groups * 4 < pers ? groups * 4 : pers, s, fl | 4);
         else
         CCZ_G16(k_conv3x3_g16, groups * 4, s, fl | 4);   // (edge launch first: measured the same, 194.4 / 194.3 k against 194.8 / 194.0 k sims/s)

@@ -313,33 +313,40 @@ __device__ __forceinline__ void g5_heads_phase(const unsigned char *lds, int w, 
 // ONE: only the first 32 input channels of a row can be non-zero (the stem: 21 live planes in rows of 64 channels) -- the tile runs the
 // nine half-steps of chunk 0 and stops; the second chunk would add products of zeros to accumulators that are never -0 (they start at
 // a bias): the same bits (the board-major and small-batch kernels run both chunks; tests compare them bit for bit).
+// Planned evaluator boundary (ccz_eval_plan): only the first *live_rows boards hold rows to compute, a number that stays on the
+// device. Their 16-board groups are cut into n_parts EQUAL ranges; a launch is range `part` of them (row0 carries part | n_parts << 16)
+// and finds its groups itself: returns how many of them are live (at most `cap`, the groups the launch was sized for) and sets `first`
+// to the first. Workgroups beyond the live tiles leave at once.
+__device__ __forceinline__ int g5_live_groups(const int *live_rows, int row0, int cap, int &first)
+{
+    const int part = row0 & 0xffff, n_parts = row0 >> 16;
+    const int G = (*live_rows + 15) >> 4;
+    const int per = (G + n_parts - 1) / n_parts;
+    first = part * per;
+    int live = G - first;
+    live = live < 0 ? 0 : (live > per ? per : live);
+    return live > cap ? cap : live;
+}
+
+// One two-rank tile. `lds`: the workgroup's kG5Lds bytes (declared by the kernel, so that one kernel can hold two tile classes);
+// `blk`: this workgroup's tile slot, `grid`: the launch's tile count (without a live-row count; with one, the tiles of the live groups).
 template <bool RES, bool HEADS, bool ONE = false>
-__device__ __forceinline__ void g5_tile(const _Float16 *__restrict__ X, const _Float16 *__restrict__ W,
+__device__ __forceinline__ void g5_tile(unsigned char *lds, int blk, int grid, const _Float16 *__restrict__ X, const _Float16 *__restrict__ W,
                                         const float *__restrict__ bias, const _Float16 *R,
                                         _Float16 *Y, int M, int relu, int cin, const int *live_rows, int row0, const G5Heads &ha)
 {
-    __shared__ __attribute__((aligned(16))) unsigned char lds[kG5Lds];
     [[maybe_unused]] long first_board = 0; // (HEADS) global index of this launch's first board: the live parts offset their pointers
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 15, q4 = lane >> 4;
     const int wm = w & 3, wn = w >> 2; // the two waves of a SIMD share their weight fragments' rows
-    int tiles = gridDim.x;
+    int tiles = grid;
     if (live_rows) {
-        // Planned evaluator boundary (ccz_eval_plan): only the first *live_rows boards hold rows to compute, a number that stays
-        // on the device. Their 16-board groups are cut into n_parts EQUAL ranges; this launch is range `part` of them (the argument
-        // carries part | n_parts << 16) and finds its groups itself. The grid is sized for the largest possible range;
-        // workgroups beyond the live tiles leave at once.
-        const int part = row0 & 0xffff, n_parts = row0 >> 16;
-        const int G = (*live_rows + 15) >> 4;
-        const int per = (G + n_parts - 1) / n_parts;
-        const int first = part * per;
-        int live = G - first;
-        live = live < 0 ? 0 : (live > per ? per : live);
-        live = live > M / 1440 ? M / 1440 : live;
+        int first;
+        const int live = g5_live_groups(live_rows, row0, M / 1440, first);
         M = live * 1440;
         tiles = live * ((relu & 4) ? 4 : 5);
-        if ((int)blockIdx.x >= tiles) return;
+        if (blk >= tiles) return;
         const long off = (long)first * 1440 * kCvC;
         X += (long)first * 1440 * cin;
         if (!HEADS) Y += off; // (HEADS: there is no output tensor)
@@ -351,7 +358,7 @@ __device__ __forceinline__ void g5_tile(const _Float16 *__restrict__ X, const _F
     // (with tile = b: 398 MB fetched per half-batch launch against 283 MB algorithmic, profiles/pmc_summary.json)
     int tile;
     {
-        const int b = blockIdx.x, x = b & 7, per = tiles >> 3, rem = tiles & 7;
+        const int b = blk, x = b & 7, per = tiles >> 3, rem = tiles & 7;
         tile = x * per + (x < rem ? x : rem) + (b >> 3);
 #ifdef G5_NO_XCD_MAP
         tile = b;
@@ -519,7 +526,8 @@ __global__ __launch_bounds__(512) void k_conv3x3_g16(const _Float16 *__restrict_
                                                          const float *__restrict__ bias, const _Float16 *R,
                                                          _Float16 *Y, int M, int relu, int cin, const int *live_rows, int row0)
 {
-    g5_tile<RES, false>(X, W, bias, R, Y, M, relu, cin, live_rows, row0, G5Heads{});
+    __shared__ __attribute__((aligned(16))) unsigned char lds[kG5Lds];
+    g5_tile<RES, false>(lds, blockIdx.x, gridDim.x, X, W, bias, R, Y, M, relu, cin, live_rows, row0, G5Heads{});
 }
 
 // The stem (ccz_conv3x3_stem_f16 with CCZ_CONV_G16): rows of 64 channels of which only 0..31 can be non-zero, one chunk (g5_tile ONE)
@@ -527,7 +535,8 @@ __global__ __launch_bounds__(512) void k_conv3x3_g16_stem(const _Float16 *__rest
                                                             const float *__restrict__ bias, _Float16 *Y, int M, int relu, int cin,
                                                             const int *live_rows, int row0)
 {
-    g5_tile<false, false, true>(X, W, bias, nullptr, Y, M, relu, cin, live_rows, row0, G5Heads{});
+    __shared__ __attribute__((aligned(16))) unsigned char lds[kG5Lds];
+    g5_tile<false, false, true>(lds, blockIdx.x, gridDim.x, X, W, bias, nullptr, Y, M, relu, cin, live_rows, row0, G5Heads{});
 }
 
 // The last layer of the tower with the heads in its epilogue (always with residual; Y may be null: nothing is stored to it).
@@ -535,8 +544,9 @@ __global__ __launch_bounds__(512) void k_conv3x3_g16_heads(const _Float16 *__res
                                                              const float *__restrict__ bias, const _Float16 *R, _Float16 *Y, int M,
                                                              int relu, int cin, const int *live_rows, int row0, G5Heads ha)
 {
+    __shared__ __attribute__((aligned(16))) unsigned char lds[kG5Lds];
     if (live_rows) ha.nb = *live_rows; // planned boundary: the pointers are the whole batch's, M only the capacity of this part
-    g5_tile<true, true>(X, W, bias, R, Y, M, relu, cin, live_rows, row0, ha);
+    g5_tile<true, true>(lds, blockIdx.x, gridDim.x, X, W, bias, R, Y, M, relu, cin, live_rows, row0, ha);
 }
 
 // Weights for k_conv3x3_g16: [co][tap][ci] (the memory of a channels-last [co, ci, 3, 3] tensor) -> [ci / 32][tap][co][32], each

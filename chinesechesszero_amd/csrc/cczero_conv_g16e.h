@@ -105,12 +105,12 @@ __device__ __forceinline__ void g5e_step(const G5Ctx &c, cv_f32x4 (&acc)[4][9], 
 
 // X, Y, R: rows in the group-of-16 layout, M rows (a multiple of 1440); W packed (k_pack_conv_weights_g16). grid = 2 * ceil(groups
 // / 2): workgroup e = pair e / 2 of groups, side e & 1 (0: rank 0, 1: rank 9). live_rows / row0: as k_conv3x3_g16 (planned boundary).
+// `lds`, `blk`: the workgroup's LDS and edge-tile slot (as g5_tile).
 template <bool RES, bool HEADS>
-__device__ __forceinline__ void g5e_tile(const _Float16 *__restrict__ X, const _Float16 *__restrict__ W,
+__device__ __forceinline__ void g5e_tile(unsigned char *lds, int blk, const _Float16 *__restrict__ X, const _Float16 *__restrict__ W,
                                          const float *__restrict__ bias, const _Float16 *R, _Float16 *Y, int M,
                                          int relu, int cin, const int *live_rows, int row0, const G5Heads &ha)
 {
-    __shared__ __attribute__((aligned(16))) unsigned char lds[kG5Lds];
     [[maybe_unused]] long first_board = 0;
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -118,21 +118,15 @@ __device__ __forceinline__ void g5e_tile(const _Float16 *__restrict__ X, const _
     const int wm = w & 3, wn = w >> 2;
     int groups = M / 1440;
     if (live_rows) { // the same cut of the live groups into n_parts equal ranges as k_conv3x3_g16
-        const int part = row0 & 0xffff, n_parts = row0 >> 16;
-        const int G = (*live_rows + 15) >> 4;
-        const int per = (G + n_parts - 1) / n_parts;
-        const int first = part * per;
-        int live = G - first;
-        live = live < 0 ? 0 : (live > per ? per : live);
-        live = live > groups ? groups : live;
-        groups = live;
+        int first;
+        groups = g5_live_groups(live_rows, row0, groups, first);
         const long off = (long)first * 1440 * kCvC;
         X += (long)first * 1440 * cin;
         if (!HEADS) Y += off; // (HEADS: there is no output tensor)
         if (RES) R += off;
         first_board = (long)first * 16;
     }
-    const int e = __builtin_amdgcn_readfirstlane((int)blockIdx.x);
+    const int e = __builtin_amdgcn_readfirstlane(blk);
     if (e >= 2 * ((groups + 1) >> 1)) return;
     const int side = e & 1, gA = (e >> 1) * 2;
     const bool dup = gA + 1 >= groups;                       // an odd group count: the last pair is one group twice (wave row 1 stores nothing)
@@ -268,15 +262,41 @@ __global__ __launch_bounds__(512) void k_conv3x3_g16_edge(const _Float16 *__rest
                                                             const float *__restrict__ bias, const _Float16 *R, _Float16 *Y, int M,
                                                             int relu, int cin, const int *live_rows, int row0)
 {
-    g5e_tile<RES, false>(X, W, bias, R, Y, M, relu, cin, live_rows, row0, G5Heads{});
+    __shared__ __attribute__((aligned(16))) unsigned char lds[kG5Lds];
+    g5e_tile<RES, false>(lds, blockIdx.x, X, W, bias, R, Y, M, relu, cin, live_rows, row0, G5Heads{});
 }
 
 __global__ __launch_bounds__(512) void k_conv3x3_g16_edge_heads(const _Float16 *__restrict__ X, const _Float16 *__restrict__ W,
                                                                   const float *__restrict__ bias, const _Float16 *R, _Float16 *Y,
                                                                   int M, int relu, int cin, const int *live_rows, int row0, G5Heads ha)
 {
+    __shared__ __attribute__((aligned(16))) unsigned char lds[kG5Lds];
     if (live_rows) ha.nb = *live_rows; // planned boundary: the pointers are the whole batch's, M only the capacity of this part
-    g5e_tile<true, true>(X, W, bias, R, Y, M, relu, cin, live_rows, row0, ha);
+    g5e_tile<true, true>(lds, blockIdx.x, X, W, bias, R, Y, M, relu, cin, live_rows, row0, ha);
+}
+
+// CCZ_CONV_G16_ONE_LAUNCH: the middle tiles AND the edge-pair tiles of a layer in ONE launch. The two classes are independent (the
+// middle tiles write ranks 1..8, the edge tiles ranks 0 and 9, both read only the layer's input and their own residual rows), so
+// nothing orders them inside a layer; as two launches in a chain's stream the edge launch waited for the middle launch's last tile,
+// and every chain-layer paid two dependent-launch tails instead of one. Slots [0, 4 g) are the middle tiles of the g live groups
+// (k_conv3x3_g16 flag bit 2, same XCD-aware order), slots [4 g, 4 g + 2 ceil(g / 2)) the edge pairs: they are dispatched last, and
+// being ~24 % shorter they fill the launch's last round. Each tile is the same code as in its own kernel (the branch is taken once,
+// before either body starts): the same values. grid = 4 groups + 2 ceil(groups / 2) of the capacity; slots past the live ones leave.
+// Not for the last layer: with the heads in the epilogue both bodies in one kernel spill (one VGPR); it stays two launches.
+template <bool RES>
+__global__ __launch_bounds__(512) void k_conv3x3_g16_one(const _Float16 *__restrict__ X, const _Float16 *__restrict__ W,
+                                                           const float *__restrict__ bias, const _Float16 *R, _Float16 *Y, int M,
+                                                           int relu, int cin, const int *live_rows, int row0)
+{
+    __shared__ __attribute__((aligned(16))) unsigned char lds[kG5Lds];
+    int groups = M / 1440;
+    if (live_rows) {
+        int first;
+        groups = g5_live_groups(live_rows, row0, groups, first);
+    }
+    const int mid = groups * 4, blk = blockIdx.x;
+    if (blk < mid) g5_tile<RES, false>(lds, blk, mid, X, W, bias, R, Y, M, relu | 4, cin, live_rows, row0, G5Heads{});
+    else g5e_tile<RES, false>(lds, blk - mid, X, W, bias, R, Y, M, relu, cin, live_rows, row0, G5Heads{});
 }
 
 } // namespace ccz

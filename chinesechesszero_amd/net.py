@@ -108,9 +108,11 @@ class EvalOptions:
     ``CCZ_FUSED_LAST=0`` (fused_last): the head convolutions as a pass of their own over the stored output of the tower instead of in
     the last layer's epilogue (group-of-16 rows; same bits either way);
     ``CCZ_CONV_PERSISTENT=N`` (persistent; round 6, A/B): the group-of-16 tower layers on N persistent workgroups per launch that walk
-    tile lists (k_conv3x3_g16_pers, csrc/cczero_conv_g16p.h; same bits); 0 = one tile per workgroup (default)."""
+    tile lists (k_conv3x3_g16_pers, csrc/cczero_conv_g16p.h; same bits); 0 = one tile per workgroup (default);
+    ``CCZ_CONV_ONE_LAUNCH=0`` (one_launch; round 7): with the edge-pair kernel, the middle and edge-pair tiles of a layer as two launches
+    instead of one (k_conv3x3_g16_one, csrc/cczero_conv_g16e.h; same bits)."""
 
-    FIELDS = ("fused_conv", "fused_stem", "fused_heads", "fused_last", "layout", "force", "groups", "chains", "zigzag", "edge_tiles", "persistent")
+    FIELDS = ("fused_conv", "fused_stem", "fused_heads", "fused_last", "layout", "force", "groups", "chains", "zigzag", "edge_tiles", "persistent", "one_launch")
 
     def __init__(self, env=None):
         env = os.environ if env is None else env
@@ -126,6 +128,7 @@ class EvalOptions:
         # group-of-16 layout: ranks 0 / 9 on the edge-pair kernel (round 4): "auto" = from 4096 boards on, together with three launch chains
         self.edge_tiles = {"0": False, "1": True}.get(env.get("CCZ_CONV_EDGE_TILES", "auto"), "auto")
         self.persistent = int(env.get("CCZ_CONV_PERSISTENT", "0"))
+        self.one_launch = env.get("CCZ_CONV_ONE_LAUNCH", "1") != "0"
         if self.layout not in ("auto", "nhwc", "g16"):
             raise ValueError("CCZ_CONV_LAYOUT must be auto, nhwc or g16")
 
@@ -440,7 +443,7 @@ class InferenceNet(nn.Module):
             cap = -(-(B // 16) // n_parts) * 1440            # whole 16-board groups (B is padded to a multiple of 16)
         else:
             cap = -(-(-(-B // n_parts)) // 8) * 8 * 90       # pixels of the largest range a launch may get
-        lay = (_lib.CONV_G16 | (_lib.CONV_G16_EDGE_TILES if edge else 0) | self._persistent_flag()) if g16 else 0
+        lay = (_lib.CONV_G16 | self._edge_flags(edge) | self._persistent_flag()) if g16 else 0
         if chains > 1:
             pool = getattr(self, "_chain_streams", None)
             if pool is None or pool[0] != x.device or len(pool[1]) < chains:
@@ -503,7 +506,7 @@ class InferenceNet(nn.Module):
         # alternates from layer to layer: what the previous layer wrote last (still in the Infinity Cache) is read
         # first (-0.7 % on the step; zigzag=False / CCZ_CONV_ZIGZAG=0 switches it off).
         down = 2 if self.opt.zigzag else 0
-        v2 = self.opt.force | ((_lib.CONV_G16 | (_lib.CONV_G16_EDGE_TILES if edge else 0) | self._persistent_flag()) if g16 else 0)
+        v2 = self.opt.force | ((_lib.CONV_G16 | self._edge_flags(edge) | self._persistent_flag()) if g16 else 0)
         wsrc = self.ws_g16 if g16 else self.ws
         for i in range(0, len(self.ws), 2):
             w1, b1_, w2, b2_ = (C.c_void_p(t.data_ptr()) for t in (wsrc[i], self.bs32[i], wsrc[i + 1], self.bs32[i + 1]))
@@ -522,6 +525,11 @@ class InferenceNet(nn.Module):
             join = torch.cuda.Event()
             join.record(st)
             cur.wait_event(join)
+
+    def _edge_flags(self, edge: bool) -> int:
+        """Flag bits of the edge-pair form: middle and edge-pair tiles as ONE launch per layer and chain unless switched off."""
+        from . import _lib
+        return (_lib.CONV_G16_EDGE_TILES | (_lib.CONV_G16_ONE_LAUNCH if self.opt.one_launch else 0)) if edge else 0
 
     def _persistent_flag(self) -> int:
         """A/B switch ``persistent`` (``CCZ_CONV_PERSISTENT=N``): flag bits that run a group-of-16 tower layer on N persistent workgroups."""

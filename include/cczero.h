@@ -442,6 +442,11 @@ int ccz_bias_act_f16(void *stream, void *y_dev, const void *bias_dev, const void
                                        zeroed ranks. Same values; -3 % per layer at 4096 boards in isolation; in the workload it pays only
                                        with three launch chains and from ~4096 boards on (+0.7...0.9 % sims/s), where the evaluator
                                        sets it (InferenceNet edge_tiles=auto); smaller launches lose (profiles/r04_conv_g16.json) */
+#define CCZ_CONV_G16_ONE_LAUNCH 512 /* with CCZ_CONV_G16_EDGE_TILES (round 7): the middle tiles and the edge-pair tiles of a layer as ONE launch
+                                       (csrc/cczero_conv_g16e.h k_conv3x3_g16_one): the two classes do not depend on each other, so a launch
+                                       chain pays one dependent-launch tail per layer instead of two and the shorter edge tiles fill the
+                                       last round of the middle ones. Same tiles, same values; not with CCZ_CONV_G16_PERSISTENT; the heads layer
+                                       (ccz_conv3x3_c256_heads_f16) ignores it */
 #define CCZ_CONV_G16_PERSISTENT 256 /* with CCZ_CONV_G16 (round 6, opt-in, 256 input channels): the same tiles on a FIXED number of workgroups
                                        that walk tile lists -- no prologue after a workgroup's first tile, the next tile's operands arrive
                                        while the epilogue's stores drain (csrc/cczero_conv_g16p.h). Bits 16..27 of the flag word = number of
