@@ -33,6 +33,7 @@ FLAG_NO_MIRROR = 2
 FLAG_VALUE_F16 = 4
 FLAG_CACHE_VERIFY = 8
 ERR_PRUNED, ERR_TRUNCATED = 256, 512   # CCZ_ERR_* set in strict mode only
+ERR_BAD_TEMP = 1024   # CCZ_ERR_BAD_TEMP: a per-board temperature that is NaN or <= 0
 FLAG_STRICT = 16   # parity mode: pruning a kept subtree / adjudicating at max_plies are error bits, not counters
 LEAF_EXPAND, LEAF_DRAW, LEAF_LOSS, LEAF_SKIP = 0, 1, 2, 3
 
@@ -41,7 +42,8 @@ ERR_BITS = {1: "node pool exhausted (raise max_nodes)", 2: "selection path deepe
             16: "forced move is not a child of the root / root not expanded", 32: "NaN priors",
             128: "index out of bounds (bounds-checked diagnostic build)",
             256: "strict mode: a kept subtree was pruned to fit the node pool (the reference's tree is unbounded: raise max_nodes)",
-            512: "strict mode: a game was adjudicated at max_plies (the reference's game has no ply cap: raise max_plies)"}
+            512: "strict mode: a game was adjudicated at max_plies (the reference's game has no ply cap: raise max_plies)",
+            1024: "a per-board temperature was NaN or <= 0 (that board neither recorded nor moved)"}
 
 
 class CczError(RuntimeError):
@@ -104,6 +106,7 @@ PROTOTYPES = {
     "ccz_finish_move": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32]),
     "ccz_root_children": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
     "ccz_root_pi": (C.c_int, [_P, _P, _P, _P]),
+    "ccz_move_distribution": (C.c_int, [_P, _P, _P, _P, _P, _P]),
     "ccz_game_status": (C.c_int, [_P, _P, _P, _P, _P, _P]),
     "ccz_root_positions": (C.c_int, [_P, _P, _P]),
     "ccz_leaf_info": (C.c_int, [_P, _P, _P, _P, _P, _P]),

@@ -6,6 +6,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -71,6 +72,7 @@ struct ccz_engine {
     uint16_t *st_acts = nullptr;
     float *st_q = nullptr, *st_p = nullptr;
     double *st_pi = nullptr, *st_temps = nullptr;
+    double *st_g = nullptr, *st_u = nullptr; // ccz_move_distribution (allocated at its first call)
     long long *st_rowbase = nullptr;
     uint8_t *st_mask = nullptr, *st_sq = nullptr;
     std::vector<BoardMeta> h_meta;
@@ -124,6 +126,10 @@ int ccz_create(const ccz_config *cfg, ccz_engine **out)
 {
     if (!cfg || !out) return fail(-1, "ccz_create: null argument");
     if (cfg->n_boards <= 0) return fail(-1, "ccz_create: n_boards must be > 0");
+    // the sampler's parameters, checked before any device work: out of range, the noise and pi are NaN or meaningless
+    if (!(cfg->eps >= 0.0f && cfg->eps <= 1.0f)) return fail(-1, "ccz_create: eps %g must be in [0, 1]", (double)cfg->eps);
+    if (!(cfg->alpha > 0.0f && std::isfinite(cfg->alpha))) return fail(-1, "ccz_create: alpha %g must be finite and > 0", (double)cfg->alpha);
+    if (!(cfg->temp > 0.0f)) return fail(-1, "ccz_create: temp %g must be > 0", (double)cfg->temp);
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(-3, "ccz_create: no HIP device available (the engine has no CPU fallback)");
@@ -598,6 +604,46 @@ int ccz_root_children(ccz_engine *e, void *stream, int32_t *k_host, uint16_t *ac
     return 0;
 }
 
+static int check_temps(const double *temps_host, int B, const char *fn)
+{
+    if (temps_host)
+        for (int b = 0; b < B; ++b)
+            if (!(temps_host[b] > 0.0)) return fail(-1, "%s: temps[%d] = %g must be > 0", fn, b, temps_host[b]);
+    return 0;
+}
+
+int ccz_move_distribution(ccz_engine *e, void *stream, const double *temps_host, double *gamma_host, double *mixed_host,
+                          double *u_host)
+{
+    NEED(e);
+    if (!gamma_host || !mixed_host || !u_host) return fail(-1, "ccz_move_distribution: null output");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t B = (size_t)e->d.B;
+    if (check_temps(temps_host, (int)B, "ccz_move_distribution")) return -1;
+    if (!e->st_g) {
+        HIP_TRY(hipMalloc(&e->st_g, B * kMaxLegal * 8));
+        e->owned.push_back(e->st_g);
+        HIP_TRY(hipMalloc(&e->st_u, B * 8));
+        e->owned.push_back(e->st_u);
+    }
+    const double *temps = nullptr;
+    if (temps_host) {
+        HIP_TRY(hipMemcpyAsync(e->st_temps, temps_host, B * 8, hipMemcpyHostToDevice, s));
+        temps = e->st_temps;
+    }
+    // boards past ACTIVE (scout slots) are not sampled by ccz_finish_move either: zero rows, u = NaN
+    HIP_TRY(hipMemsetAsync(e->st_g, 0, B * kMaxLegal * 8, s));
+    HIP_TRY(hipMemsetAsync(e->st_pi, 0, B * kMaxLegal * 8, s));
+    HIP_TRY(hipMemsetAsync(e->st_u, 0xff, B * 8, s));
+    hipLaunchKernelGGL(k_move_distribution, dim3(ACTIVE(e)), dim3(64), 0, s, e->d, temps, e->st_g, e->st_pi, e->st_u);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(gamma_host, e->st_g, B * kMaxLegal * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(mixed_host, e->st_pi, B * kMaxLegal * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(u_host, e->st_u, B * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return 0;
+}
+
 int ccz_root_pi(ccz_engine *e, void *stream, const double *temps_host, double *pi_host)
 {
     NEED(e);
@@ -605,6 +651,7 @@ int ccz_root_pi(ccz_engine *e, void *stream, const double *temps_host, double *p
     hipStream_t s = (hipStream_t)stream;
     const size_t B = (size_t)e->d.B;
     const double *temps = nullptr;
+    if (check_temps(temps_host, (int)B, "ccz_root_pi")) return -1;
     if (temps_host) {
         HIP_TRY(hipMemcpyAsync(e->st_temps, temps_host, B * 8, hipMemcpyHostToDevice, s));
         temps = e->st_temps;

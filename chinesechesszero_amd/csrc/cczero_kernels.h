@@ -1093,7 +1093,7 @@ __global__ __launch_bounds__(64 * MAXW) void k_scouted_run(Dev D, uint16_t *leaf
 // ------------------------------------------------------------------ pi from root visits (mcts.py:162-166)
 // s_vis[k] -> s_pi[k] ; softmax(1/temp * log(N + 1e-10)) with the deterministic log/exp; the
 // normalising sum is accumulated sequentially (index order) to match the CPU twin bit for bit.
-__device__ inline void root_pi(const int32_t *s_vis, double *s_pi, int k, double temp, int lane)
+__device__ __forceinline__ void root_pi(const int32_t *s_vis, double *s_pi, int k, double temp, int lane)
 {
     const double it = 1.0 / temp;
     double mx = -__builtin_huge_val();
@@ -1113,6 +1113,36 @@ __device__ inline void root_pi(const int32_t *s_vis, double *s_pi, int k, double
     for (int i = lane; i < k; i += 64) s_pi[i] = s_pi[i] / sum;
     wave_sync();
 }
+
+// move ~ Categorical((1-EPS)*pi + EPS*Dirichlet(ALPHA)) on the board's Philox stream (mcts.py:216-224), s_pi[k] -> *choice
+// (lane 0). s_g[k] is scratch (the Gamma draws, then the cdf). k_finish_move passes null outputs; k_move_distribution passes
+// g_out / mixed_out (float64 [k]) and u_out to read what the sampler drew -- the same instructions, written out on lane 0.
+__device__ __forceinline__ void sample_move(const Dev &D, uint64_t gid, uint64_t move_no, const double *s_pi, double *s_g, int k,
+                                            int lane, int *choice, double *g_out, double *mixed_out, double *u_out)
+{
+    for (int i = lane; i < k; i += 64) s_g[i] = det_gamma(D.seed, gid, move_no, (uint32_t)i, D.alpha);
+    __syncthreads();
+    if (lane == 0) {
+        double gs = 0.0, acc = 0.0, ua, ub;
+        for (int i = 0; i < k; ++i) gs += s_g[i];
+        for (int i = 0; i < k; ++i) {
+            const double dir = gs > 0.0 ? s_g[i] / gs : s_pi[i];
+            const double mx = (1.0 - D.eps) * s_pi[i] + D.eps * dir;
+            if (g_out) g_out[i] = s_g[i];
+            if (mixed_out) mixed_out[i] = mx;
+            acc += mx;
+            s_g[i] = acc; // cdf
+        }
+        uniform2(D.seed, gid, move_no, 0xfffu, 0, ua, ub);
+        if (u_out) *u_out = ua;
+        int idx = 0;
+        for (int i = 0; i < k; ++i) if (s_g[i] / acc <= ua) idx = i + 1; // searchsorted(side="right")
+        *choice = idx < k ? idx : k - 1;
+    }
+}
+
+// a per-board temperature the softmax of root_pi cannot take (1/temp of 0 or NaN): CCZ_ERR_BAD_TEMP, the board neither records nor moves
+__device__ __forceinline__ bool bad_temp(double t) { return !(t > 0.0); }
 
 __device__ __forceinline__ double board_temp(const Dev &D, const BoardMeta &m, const double *temps, int b)
 {
@@ -1153,9 +1183,39 @@ __global__ __launch_bounds__(64) void k_root_children(Dev D, int32_t *k_out, uin
     }
     __syncthreads();
     if (pi_out) {
-        if (k > 0) root_pi(s_vis, s_pi, k, board_temp(D, m, temps, b), lane);
+        const double temp = board_temp(D, m, temps, b);
+        if (bad_temp(temp)) { if (lane == 0) set_err(D, CCZ_ERR_BAD_TEMP); k = 0; }
+        if (k > 0) root_pi(s_vis, s_pi, k, temp, lane);
         for (int i = lane; i < kMaxLegal; i += 64) pi_out[(size_t)b * kMaxLegal + i] = i < k ? s_pi[i] : 0.0;
     }
+}
+
+// ------------------------------------------------------------------ what the next unforced k_finish_move samples from
+// Read-only (moves nothing, records nothing): the same root_pi and sample_move on the same Philox counters as k_finish_move.
+// g_out / mixed_out float64 [B][128] (the raw Gamma draws, (1-eps) pi + eps Dirichlet), u_out float64 [B] (the choice uniform).
+// A board k_finish_move would not sample on (game over, no children, bad temperature) gets zero rows and u = NaN.
+__global__ __launch_bounds__(64) void k_move_distribution(Dev D, const double *temps, double *g_out, double *mixed_out, double *u_out)
+{
+    const int b = blockIdx.x, lane = threadIdx.x;
+    __shared__ int32_t s_vis[kMaxLegal];
+    __shared__ double s_pi[kMaxLegal];
+    __shared__ double s_g[kMaxLegal];
+    __shared__ int s_choice;
+    const BoardMeta m = D.meta[b];
+    const size_t base = ((size_t)b * 2 + *D.half) * (size_t)D.cap;
+    const NodeA *A = D.nodeA + base;
+    const uint32_t *Bn = D.nodeB + base;
+    const NodeA root = A[0];
+    int k = (int)(Bn[0] >> 16);
+    const double temp = board_temp(D, m, temps, b);
+    if (m.over || k > kMaxLegal || bad_temp(temp)) k = 0;
+    double *g = g_out + (size_t)b * kMaxLegal, *mixed = mixed_out + (size_t)b * kMaxLegal;
+    for (int i = lane; i < kMaxLegal; i += 64) if (i >= k) { g[i] = 0.0; mixed[i] = 0.0; }
+    if (k == 0) { if (lane == 0) u_out[b] = __builtin_nan(""); return; }
+    for (int i = lane; i < k; i += 64) s_vis[i] = A[CCZ_IDX(D, root.fc + i, D.cap)].N;
+    __syncthreads();
+    root_pi(s_vis, s_pi, k, temp, lane);
+    sample_move(D, D.board_id_base + (uint64_t)b, m.move_counter, s_pi, s_g, k, lane, &s_choice, g, mixed, u_out + b);
 }
 
 // ------------------------------------------------------------------ K3: once per move
@@ -1190,6 +1250,8 @@ __global__ __launch_bounds__(64) void k_finish_move(Dev D, const int32_t *forced
     if (k > kMaxLegal) { if (lane == 0) set_err(D, 16); return; }
     if (k == 0 && want < 0) { if (lane == 0) set_err(D, 16); return; } // nothing searched, nothing to sample from
     if (want >= kNMoves) { if (lane == 0) set_err(D, 16); return; }
+    const double temp = board_temp(D, m, temps, b);
+    if (bad_temp(temp)) { if (lane == 0) set_err(D, CCZ_ERR_BAD_TEMP); return; }
 
     load_board(s_sq, D.root_sq + (size_t)b * 96, lane);
     for (int i = lane; i < k; i += 64) {
@@ -1199,7 +1261,7 @@ __global__ __launch_bounds__(64) void k_finish_move(Dev D, const int32_t *forced
     __syncthreads();
 
     // ---- pi (mcts.py:162-166) and the training record (game.py:195-198)
-    if (k > 0) root_pi(s_vis, s_pi, k, board_temp(D, m, temps, b), lane);
+    if (k > 0) root_pi(s_vis, s_pi, k, temp, lane);
     if (m.ply >= D.max_plies || m.pi_used + (uint32_t)k > (uint32_t)D.pi_cap) {
         // documented cap: the game is adjudicated a draw, its records so far stay valid
         if (lane == 0) {
@@ -1238,23 +1300,8 @@ __global__ __launch_bounds__(64) void k_finish_move(Dev D, const int32_t *forced
         if (found < 0 && s_sq[c_tab.from[want]] == 0) { if (lane == 0) set_err(D, 16); return; }
         if (lane == 0) s_choice = found;
     } else {
-        // move ~ Categorical((1-EPS)*pi + EPS*Dirichlet(ALPHA)) on the board's Philox stream
         const uint64_t gid = D.board_id_base + (uint64_t)b;
-        for (int i = lane; i < k; i += 64) s_g[i] = det_gamma(D.seed, gid, m.move_counter, (uint32_t)i, D.alpha);
-        __syncthreads();
-        if (lane == 0) {
-            double gs = 0.0, acc = 0.0, ua, ub;
-            for (int i = 0; i < k; ++i) gs += s_g[i];
-            for (int i = 0; i < k; ++i) {
-                const double dir = gs > 0.0 ? s_g[i] / gs : s_pi[i];
-                acc += (1.0 - D.eps) * s_pi[i] + D.eps * dir;
-                s_g[i] = acc; // cdf
-            }
-            uniform2(D.seed, gid, m.move_counter, 0xfffu, 0, ua, ub);
-            int idx = 0;
-            for (int i = 0; i < k; ++i) if (s_g[i] / acc <= ua) idx = i + 1; // searchsorted(side="right")
-            s_choice = idx < k ? idx : k - 1;
-        }
+        sample_move(D, gid, m.move_counter, s_pi, s_g, k, lane, &s_choice, nullptr, nullptr, nullptr);
     }
     __syncthreads();
     const int ci = s_choice;

@@ -350,6 +350,17 @@ class SelfPlayEngine:
         check(self.L.ccz_root_pi(self.h, self._stream(), _ptr(t), _ptr(pi)))
         return pi
 
+    def move_distribution(self, temps=None):
+        """What the next unforced :meth:`finish_move` samples from, without moving (syncs; tests): ``(gamma, mixed, u)`` with
+        the raw Gamma(alpha) draws and ``(1-eps) pi + eps Dirichlet`` as float64 [B,128] aligned with ``root_children()['acts']``
+        (zero past k) and the choice uniform float64 [B] (NaN where no move would be sampled). ``temps`` as for :meth:`root_pi`."""
+        gamma = np.zeros((self.B, MAX_LEGAL), np.float64)
+        mixed = np.zeros((self.B, MAX_LEGAL), np.float64)
+        u = np.zeros(self.B, np.float64)
+        t = None if temps is None else np.ascontiguousarray(np.broadcast_to(np.asarray(temps, np.float64), (self.B,)))
+        check(self.L.ccz_move_distribution(self.h, self._stream(), _ptr(t), _ptr(gamma), _ptr(mixed), _ptr(u)))
+        return gamma, mixed, u
+
     def game_status(self):
         B = self.B
         over = np.zeros(B, np.uint8)

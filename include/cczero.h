@@ -95,9 +95,13 @@ typedef struct ccz_config {
     int32_t n_boards;      /* B: concurrent boards on this GPU                                   */
     int32_t n_playout;     /* simulations per move (parameters.py:14 PLAYOUT; informational)    */
     float c_puct;          /* parameters.py:8  C_PUCT = 5                                        */
-    float eps;             /* parameters.py:10 EPS   = 0.25 (Dirichlet mixing weight)            */
-    float alpha;           /* parameters.py:12 ALPHA = 0.2                                       */
-    float temp;            /* game.py:133 temp=1.0 ; schedule of game.py:159 applied per board   */
+    float eps;             /* parameters.py:10 EPS   = 0.25 (Dirichlet mixing weight); must be in [0, 1] */
+    float alpha;           /* parameters.py:12 ALPHA = 0.2; must be finite and > 0. The device widens the float to double
+                              (0.2f = 0.20000000298...). A Gamma draw g = G(alpha+1) U^(1/alpha) is flushed to 0 when
+                              log(U)/alpha < -708 (det_exp's cutoff), with probability ~exp(-708 alpha): 6e-10 at alpha 0.03,
+                              0.09 % at 0.01, 49 % at 0.001 (measured on the twin); when all k draws of a board are 0 the
+                              noise is pi itself (k = 2: 1.7 % at 0.003). Exact noise needs alpha >= 0.03 */
+    float temp;            /* game.py:133 temp=1.0 ; schedule of game.py:159 applied per board; must be > 0 */
     int32_t max_nodes;     /* tree nodes per board per pool half (0 = 512 x (n_playout + 64))    */
     int32_t max_depth;     /* selection path capacity (0 = 512)                                  */
     int32_t max_plies;     /* recorded plies per game before adjudicating a draw (0 = 2048)      */
@@ -167,6 +171,7 @@ typedef struct ccz_stats {
 #define CCZ_ERR_BOUNDS 128    /* bounds-checked diagnostic build only (-DCCZ_BOUNDS): an index left its array      */
 #define CCZ_ERR_PRUNED 256    /* CCZ_FLAG_STRICT: a kept subtree lost nodes at re-root time (raise max_nodes / lower reserve_nodes) */
 #define CCZ_ERR_TRUNCATED 512 /* CCZ_FLAG_STRICT: a game reached max_plies and was adjudicated a draw (raise max_plies)            */
+#define CCZ_ERR_BAD_TEMP 1024 /* a per-board temperature (ccz_finish_move temps_dev) that is NaN or <= 0: that board neither records nor moves */
 
 /* ---- library ---------------------------------------------------------------------------- */
 int ccz_abi_version(void);
@@ -310,7 +315,8 @@ int ccz_gather_priors_routed(ccz_engine *e, void *stream, const void *logits0_de
  *     or match play); a forced move that is not a child of the root (root never searched, or an
  *     opponent's reply the tree never saw) gives a fresh root, as update_with_move does
  *     (mcts.py:176-178). entry < 0 or NULL: sample on the device stream Philox(seed, board id).
- *   temps_dev: float64 [B] or NULL (NULL: schedule of game.py:159 from cfg.temp).
+ *   temps_dev: float64 [B] or NULL (NULL: schedule of game.py:159 from cfg.temp). An entry that is NaN or <= 0 sets
+ *     CCZ_ERR_BAD_TEMP and that board neither records nor moves.
  *   moves_out_dev: int32 [B] or NULL, receives the move played.
  *   keep_tree: 1 = self-play tree reuse (mcts.py:222-224); 0 = discard (mcts.py:228-229).
  * All live trees move to the other half of their node pool in this call (one flip for every board),
@@ -323,9 +329,16 @@ int ccz_finish_move(ccz_engine *e, void *stream, const int32_t *forced_moves_dev
  * (may be NULL). What mcts.py:162-163 reads. */
 int ccz_root_children(ccz_engine *e, void *stream, int32_t *k_host, uint16_t *acts_host,
                       int32_t *visits_host, float *q_host, float *prior_host, int32_t *root_visits_host);
-/* pi of the root at temperature temps_host[b] (float64 [B], or NULL for the schedule) without
+/* pi of the root at temperature temps_host[b] (float64 [B], or NULL for the schedule; entries must be > 0) without
  * moving: pi_host float64 [B*128] aligned with ccz_root_children's acts (syncs). */
 int ccz_root_pi(ccz_engine *e, void *stream, const double *temps_host, double *pi_host);
+/* what the next unforced ccz_finish_move samples from, without moving (syncs; tests): with the same temps_host as
+ * ccz_root_pi, per board the raw Gamma(alpha) draws gamma_host float64 [B*128], the mixed vector (1-eps) pi + eps g/sum(g)
+ * mixed_host float64 [B*128] (both aligned with ccz_root_children's acts, zero past k) and the choice uniform u_host
+ * float64 [B]; the move is child searchsorted(cumsum(mixed) / sum(mixed), u, side="right"), at most k-1. A board that
+ * would not be sampled (game over, no children) has zero rows and u = NaN. temps_host entries must be > 0. */
+int ccz_move_distribution(ccz_engine *e, void *stream, const double *temps_host, double *gamma_host, double *mixed_host,
+                          double *u_host);
 /* per-board game state (syncs): over_host uint8[B] (1 = finished, waiting for harvest),
  * winner_host int8[B] (1 RED, 0 BLACK, -1 draw), plies_host int32[B], turn_host uint8[B];
  * any pointer may be NULL. */

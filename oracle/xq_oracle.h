@@ -139,6 +139,10 @@ void xq_det_pi(const int32_t *visits, int k, double temp, double *pi);
 /* Dirichlet-mixed move choice (mcts.py:216-224) on the per-board Philox stream; returns child index */
 int xq_det_sample(uint64_t seed, uint64_t board_id, uint64_t move_no, const double *pi, int k,
                   double eps, double alpha, double *mixed_out);
+/* the raw Gamma(alpha) draws of children 0..k-1 of boards board0 .. board0+n_boards-1: out float64 [n_boards][k] */
+void xq_det_gammas(uint64_t seed, uint64_t board0, int n_boards, uint64_t move_no, int k, double alpha, double *out);
+/* the uniform xq_det_sample compares the normalised cdf with */
+double xq_det_choice_uniform(uint64_t seed, uint64_t board_id, uint64_t move_no);
 
 #ifdef __cplusplus
 }

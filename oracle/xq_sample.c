@@ -73,18 +73,19 @@ static void uniform2(uint64_t seed, uint64_t board, uint64_t move_no, uint32_t c
     *ub = (double)(2 * ((((uint64_t)o[2] << 32) | o[3]) >> 12) + 1) * 1.1102230246251565e-16;
 }
 
-/* Gamma(alpha, 1), alpha < 1: Marsaglia-Tsang for alpha+1 with polar normals, then the U^(1/alpha) boost */
+/* Gamma(alpha, 1), alpha < 1: Marsaglia-Tsang for alpha+1 with polar normals, then the U^(1/alpha) boost. Bounded as
+ * the device bounds it (0xffff0 draws, then 0.0), so that a NaN alpha terminates here too and the twins agree at the bound. */
 static double det_gamma(uint64_t seed, uint64_t board, uint64_t move_no, uint32_t child, double alpha)
 {
     double d = (alpha + 1.0) - 1.0 / 3.0, c = 1.0 / sqrt(9.0 * d), ua, ub;
     uint32_t j = 0;
-    for (;;) {
+    while (j < 0xffff0u) {
         double x1, x2, s, z, v;
         for (;;) {
             uniform2(seed, board, move_no, child, j++, &ua, &ub);
             x1 = 2.0 * ua - 1.0; x2 = 2.0 * ub - 1.0;
             s = x1 * x1 + x2 * x2;
-            if (s < 1.0 && s > 0.0) break;
+            if ((s < 1.0 && s > 0.0) || j >= 0xffff0u) break;
         }
         z = x1 * sqrt(-2.0 * xq_det_log(s) / s);
         v = 1.0 + c * z;
@@ -94,6 +95,21 @@ static double det_gamma(uint64_t seed, uint64_t board, uint64_t move_no, uint32_
         if (xq_det_log(ua) < 0.5 * z * z + d - d * v + d * xq_det_log(v))
             return d * v * xq_det_exp(xq_det_log(ub) / alpha);
     }
+    return 0.0;
+}
+
+void xq_det_gammas(uint64_t seed, uint64_t board0, int n_boards, uint64_t move_no, int k, double alpha, double *out)
+{
+    int b, i;
+    for (b = 0; b < n_boards; b++)
+        for (i = 0; i < k; i++) out[(size_t)b * k + i] = det_gamma(seed, board0 + (uint64_t)b, move_no, (uint32_t)i, alpha);
+}
+
+double xq_det_choice_uniform(uint64_t seed, uint64_t board_id, uint64_t move_no)
+{
+    double ua, ub;
+    uniform2(seed, board_id, move_no, 0xfffu, 0, &ua, &ub);
+    return ua;
 }
 
 void xq_det_pi(const int32_t *visits, int k, double temp, double *pi)
