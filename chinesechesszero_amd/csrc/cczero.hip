@@ -19,7 +19,6 @@
 #include "cczero_conv_small.h"
 #include "cczero_conv_g16.h"
 #include "cczero_conv_g16e.h"
-#include "cczero_conv_g16p.h"
 #include "cczero_heads.h"
 
 using namespace ccz;
@@ -947,6 +946,8 @@ static int conv3x3_launch(const char *who, void *stream, const void *x_dev, cons
     if (x_dev == y_dev) return fail(-1, "%s: the output may alias the residual but not the input", who);
     if (n_pixels == 0) return 0;
     if (relu & CCZ_CONV_G16) { // rows in the group-of-16 layout: whole-rank tiles, off-board taps skipped (cczero_conv_g16.h)
+        if (relu & (256 | (0xfff << 16))) // the persistent form's flag and workgroup count (round 6; removed in ABI 8): refused, not ignored
+            return fail(-1, "%s: flag 256 / bits 16..27 were CCZ_CONV_G16_PERSISTENT, retired in ABI 8", who);
         if (n_pixels % 1440) return fail(-1, "%s: CCZ_CONV_G16 needs a multiple of 16 boards", who);
         const int groups = (int)(n_pixels / 1440);
         const int fl = relu & 3;
@@ -975,24 +976,16 @@ static int conv3x3_launch(const char *who, void *stream, const void *x_dev, cons
             HIP_TRY(hipGetLastError());
             return 0;
         }
-        // CCZ_CONV_G16_PERSISTENT: the same tiles on a fixed number of workgroups that walk tile lists (cczero_conv_g16p.h); bits 16..27 =
-        // the number of workgroups (0: one per CU)
-        int pers = (relu & CCZ_CONV_G16_PERSISTENT) ? (((relu >> 16) & 0xfff) ? ((relu >> 16) & 0xfff) : 256) : 0;
-        if (pers && pers < 8) pers = 8; // every XCD that owns tiles needs a workgroup (tile lists are per XCD)
-        if (pers && cin != 256) return fail(-1, "%s: CCZ_CONV_G16_PERSISTENT is the tower shape only (256 input channels)", who);
         if (!(relu & CCZ_CONV_G16_EDGE_TILES) || groups < 2) {
-            if (pers) CCZ_G16(k_conv3x3_g16_pers, groups * 5 < pers ? groups * 5 : pers, s, fl);
-            else CCZ_G16(k_conv3x3_g16, groups * 5, s, fl);
+            CCZ_G16(k_conv3x3_g16, groups * 5, s, fl);
             HIP_TRY(hipGetLastError());
             return 0;
         }
-        if (!pers && (relu & CCZ_CONV_G16_ONE_LAUNCH)) { // both tile classes in one launch (cczero_conv_g16e.h k_conv3x3_g16_one)
+        if (relu & CCZ_CONV_G16_ONE_LAUNCH) { // both tile classes in one launch (cczero_conv_g16e.h k_conv3x3_g16_one)
             CCZ_G16(k_conv3x3_g16_one, groups * 4 + 2 * ((groups + 1) / 2), s, fl);
             HIP_TRY(hipGetLastError());
             return 0;
         }
-        if (pers) CCZ_G16(k_conv3x3_g16_pers, groups * 4 < pers ? groups * 4 : pers, s, fl | 4);
-        else
         CCZ_G16(k_conv3x3_g16, groups * 4, s, fl | 4);   // (edge launch first: measured the same, 194.4 / 194.3 k against 194.8 / 194.0 k sims/s)
         HIP_TRY(hipGetLastError());
         CCZ_G16(k_conv3x3_g16_edge, 2 * ((groups + 1) / 2), s, fl);

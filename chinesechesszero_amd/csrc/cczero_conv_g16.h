@@ -39,7 +39,11 @@
 // off-board taps (-3...-5 %), the halo fetches (-2.4 %), 46 % of the LDS fragment reads (-3 %), the scattered weight reads (-2.2 %),
 // half of the zero stores (-0.9 %). Not everything that removes LDS traffic pays: an epilogue straight from registers (v_permlane16_swap
 // pairs two tiles so that a lane stores 16 contiguous bytes; no LDS image, no barrier) is bit-identical and 5 % slower -- its stores
-// are sixteen 64-byte segments per instruction instead of whole 512-byte rows.
+// are sixteen 64-byte segments per instruction instead of whole 512-byte rows. Nor does hiding the prologue: a persistent form (round 6,
+// a fixed number of workgroups walking tile lists, the next tile's first slab and weights staged while the epilogue drains) was
+// bit-identical and -4.3 % per layer in isolation at exactly five tiles per workgroup, but lost or tied in the workload -- 183.4 k against
+// 193.3-194.0 k sims/s, cache off 176.3 k against 181.4 k, 1024 boards 175.1 k against 180.2 k (profiles/r06_persistent_tower.json): the
+// launch chains buy more at every layer boundary than it hides. It was removed after round 7.
 #pragma once
 #include "cczero_conv.h"
 
@@ -68,26 +72,7 @@ struct G5Ctx {
     int a_off;               // weight fragment offset inside a ring slot (tile 0; tile i: + 1024 i)
     int vb[2];               // this lane's pixel-fragment base in slab 0 / 1 (cell 0 of the wave's rank at tap offset 0 = + 9 * 1024)
     int cin, cmask;          // input channels; number of 32-channel chunks - 1
-    // persistent form only (cczero_conv_g16p.h; all SCALAR): xoff[] is then tile-independent and everything that depends on the tile is
-    // derived at its use from these four numbers (a handful of SALU per DMA: kept as ready-made offsets they cost 16 SGPRs and spill)
-    int p0, k;               // the CURRENT tile: first tensor row; ranks 2k, 2k + 1 of its group (2 = no edge rank next to it)
-    int p0n, kn;             // the NEXT tile of this workgroup (the current one again when there is none)
-    int m_w0, m_w3, rows4;   // wave masks: -1 for wave 0 / waves 3..7, else 0; slab row of staging pass 4 (512; waves 4-7: 384 = pass 3 again)
-    int za[2], zb[2];        // this wave's zero stores j = 0, 1 for a tile with k = 0 / k = 4: offset inside a slab, +1 so that 0 = none
 };
-
-// LDS layout of the persistent form: [ring slots 0-2 | slab 0 | ring slots 3-4 | slab 1 | dump]. Between two tiles of a workgroup the next
-// tile's first three weight half-tiles sit in slots 0-2 and its first slab in slab 0; what is left -- slots 3-4, slab 1 and the dump area
-// = one contiguous 76 KB -- holds the epilogue image of ONE rank (144 rows of 528 B), so the epilogue runs in two passes.
-constexpr int kP5Slab0 = 3 * kG5WBytes;                     // 49,152
-constexpr int kP5Ring3 = kP5Slab0 + kG5SlabBytes;           // 86,016: ring slots 3 and 4; also the epilogue image
-constexpr int kP5Slab1 = kP5Ring3 + 2 * kG5WBytes;          // 118,784
-constexpr int kP5Img = kP5Ring3;
-constexpr int kP5Bias = kG5Lds - 1024;                      // the layer's 256 biases (float): behind the image, in the last KB of the dump area
-static_assert(kP5Img + 144 * kG5ERow <= kP5Bias, "persistent layout: the bias copy sits behind the epilogue image");
-static_assert(kP5Slab1 + kG5SlabBytes == kG5Dump, "persistent layout: the dump area stays where it is");
-static_assert(kP5Img + 144 * kG5ERow <= kG5Lds, "persistent layout: one rank's epilogue image must fit behind slab 0");
-__device__ __forceinline__ int p5_ring(int slot) { return slot * kG5WBytes + (slot >= 3 ? kG5SlabBytes : 0); }
 
 __host__ __device__ constexpr bool g5_slab_tap(int t) { return t >= 1 && t <= 5; }
 // DMA loads younger than the weight half-tile the NEXT half-step reads (issue order per half-step: slab piece, 2 weight loads)
@@ -115,74 +100,20 @@ __device__ __forceinline__ void g5_zero_ranks(const G5Ctx &c, int buf)
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 }
 
-// persistent form. Staging pass `it` of wave w covers slab rows it * 128 + 16 w .. + 15 (waves 4-7 repeat pass 3 in pass 4): rows 0..143
-// are the rank above the tile (pass 0 of every wave, pass 1 of wave 0), rows 432..575 the rank below it (pass 3 of waves 3-7, pass 4).
-// A rank that does not exist (k = 0: above, k = 4: below; zeroed after it has landed) is staged from the tile's own edge rank.
-// The per-thread part of a slab source is the SAME in every pass (xoff[0]: row tid / 4 of the pass's 128, swizzled 16-byte chunk -- the
-// swizzle depends on the row modulo 16 only), so the pass is part of the scalar too: one address register instead of five.
-// Everything here is SCALAR and BRANCH-FREE (a scalar branch inside the loop body costs the register allocation its balance): the
-// conditions on the wave are precomputed masks (G5Ctx::m_*), the conditions on the tile are one compare + select each.
-template <int IT> __device__ __forceinline__ unsigned p5_slab_src(const G5Ctx &c, int p0, int k)
-{
-    const int is0 = k == 0 ? -1 : 0, is4 = k == 4 ? -1 : 0;
-    int fix = 0, rows = IT * 128;
-    if constexpr (IT == 0) fix = 144 & is0;
-    if constexpr (IT == 1) fix = 144 & is0 & c.m_w0;
-    if constexpr (IT == 3) fix = -(144 & is4 & c.m_w3);
-    if constexpr (IT == 4) {
-        fix = -(144 & is4);
-        rows = c.rows4; // waves 4-7 repeat their pass-3 piece
-    }
-    return (unsigned)((p0 - 144 + fix + rows) * c.cin);
-}
-// LDS offset of this wave's zero store j for slab buffer `buf` of a tile with edge index k (the dump KB when it has nothing to zero)
-__device__ __forceinline__ int p5_zero_dst(const G5Ctx &c, int k, int j, int buf)
-{
-    const int is0 = k == 0 ? -1 : 0, is4 = k == 4 ? -1 : 0;
-    const int d = (is0 & c.za[j]) | (is4 & c.zb[j]);       // this wave's piece relative to slab 0, or 0
-    const int real = d != 0 ? -1 : 0;
-    return kG5Dump + (real & (kP5Slab0 - kG5Dump + d - 1 + (buf ? kP5Slab1 - kP5Slab0 : 0)));
-}
-// the slab staged during a tile's LAST chunk is the next tile's first one (buffer 0; the chunk count is even)
-__device__ __forceinline__ void p5_zero_ranks(const G5Ctx &c, int buf, bool next_tile)
-{
-    int l16 = c.lane16, zero = 0;
-    asm volatile("" : "+v"(l16), "+v"(zero));
-    typedef int g5_int4 __attribute__((ext_vector_type(4)));
-    const g5_int4 z = {zero, zero, zero, zero};
-    const int k = next_tile ? c.kn : c.k;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) *(g5_int4 *)(c.lds + (l16 + p5_zero_dst(c, k, j, buf))) = z;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-}
-
 // One half-step = tap T of a 32-channel chunk; J = its index inside the unrolled pair of chunks (parity of the A register
 // set = J & 1, slab buffer = J / 9).
-template <int J, bool PERS = false>
+template <int J>
 __device__ __forceinline__ void g5_step(const G5Ctx &c, cv_f32x4 (&acc)[4][9], int chunk, int &ring_rd, int &ring_wr,
                                          cv_half8 (&a0)[4], cv_half8 (&a1)[4], cv_half8 (&b)[9])
 {
     constexpr int T = J % 9, BUF = J / 9;
     constexpr int Tn = (T + 1) % 9, BUFn = (T == 8) ? 1 - BUF : BUF;
-    [[maybe_unused]] constexpr int deltan = 9 * (Tn / 3 - 1) + (Tn % 3 - 1);
     cv_half8 (&acur)[4] = (J & 1) ? a1 : a0;
     cv_half8 (&anxt)[4] = (J & 1) ? a0 : a1;
     unsigned char *const lds = c.lds;
 
     // the order below is pinned (one scheduling region per cell): a fragment register is refilled right AFTER the MFMAs that read
     // it -- left to the scheduler the refills move up and every fragment needs a second register
-#ifdef G5_BFRAG_PER_TAP /* A/B: round 3's first form -- nine fragment reads per tap, each register refilled after its MFMAs */
-#define G5_CELL(N)                                                                                                        \
-    {                                                                                                                     \
-        if constexpr (g5_on_board<T, N>()) {                                                                              \
-            _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                                 \
-                acc[i][N] = __builtin_amdgcn_mfma_f32_16x16x32_f16(acur[i], b[N], acc[i][N], 0, 0, 0);                    \
-        }                                                                                                                 \
-        if constexpr (g5_on_board<Tn, N>())                                                                               \
-            b[N] = *(const cv_half8 *)(lds + c.vb[BUFn] + (9 + N + deltan) * 1024);                                       \
-        __builtin_amdgcn_sched_barrier(0);                                                                                \
-    }
-#else
     // The three taps of one dy read the SAME nine cells of slab rank (rank + dy): cell N needs cell N + dx. So b[] holds the nine
     // fragments of that rank for three half-steps (cell N multiplies b[N + dx]; N + dx = -1 and 9 are exactly the skipped,
     // off-board pairs) and is refilled once per dy, during the dx = +1 tap: b[N] is dead as soon as cell N - 1 has issued its
@@ -198,7 +129,6 @@ __device__ __forceinline__ void g5_step(const G5Ctx &c, cv_f32x4 (&acc)[4][9], i
         }                                                                                                                 \
         __builtin_amdgcn_sched_barrier(0);                                                                                \
     }
-#endif
 #define G5_CELLS(LO, HI)                                                                                                  \
     if constexpr (LO <= 0 && 0 < HI) G5_CELL(0) if constexpr (LO <= 1 && 1 < HI) G5_CELL(1) if constexpr (LO <= 2 && 2 < HI) G5_CELL(2) \
     if constexpr (LO <= 3 && 3 < HI) G5_CELL(3) if constexpr (LO <= 4 && 4 < HI) G5_CELL(4) if constexpr (LO <= 5 && 5 < HI) G5_CELL(5) \
@@ -209,11 +139,6 @@ __device__ __forceinline__ void g5_step(const G5Ctx &c, cv_f32x4 (&acc)[4][9], i
     if constexpr (g5_slab_tap(T)) { // the next chunk's slab: 5 pieces per thread, in taps 1..5
         constexpr int pass = T - 1;
         const int nxt = (chunk + 1) & c.cmask; // past the last chunk: re-stage chunk 0 into the free buffer (keeps every count static)
-        if constexpr (PERS) { // ... of the workgroup's NEXT tile (of this one again when there is none)
-            const bool last = chunk == c.cmask;
-            const unsigned so = p5_slab_src<pass>(c, last ? c.p0n : c.p0, last ? c.kn : c.k) + (unsigned)(nxt * 32);
-            cv_glds16(c.X + (c.xoff[0] + so), lds + (BUF ? kP5Slab0 : kP5Slab1) + (pass < 4 ? pass * 8192 + c.wave_dst : c.wave_dst4));
-        } else
         cv_glds16(c.X + (c.xoff[pass] + (unsigned)(nxt * 32)), lds + kG5AOff + (1 - BUF) * kG5SlabBytes + (pass < 4 ? pass * 8192 + c.wave_dst : c.wave_dst4));
         __builtin_amdgcn_sched_barrier(0);
     }
@@ -223,7 +148,7 @@ __device__ __forceinline__ void g5_step(const G5Ctx &c, cv_f32x4 (&acc)[4][9], i
         asm volatile("" : "+v"(wo)); // the address is formed here, per half-step: hoisted for 9 taps x 2 pieces it costs 36 registers
         const unsigned o = wo + (unsigned)((T2 + 9 * chunk2) * 8192); // half-tile (chunk2, T2): one contiguous 16 KB block
         const unsigned o2 = o + 4096u;                                 // its rows 128..255
-        unsigned char *const d = lds + (PERS ? p5_ring(ring_wr) : ring_wr * kG5WBytes) + c.wave_dst;
+        unsigned char *const d = lds + ring_wr * kG5WBytes + c.wave_dst;
         cv_glds16(c.W + o, d);
         __builtin_amdgcn_sched_barrier(0);
         G5_CELLS(2, 3)
@@ -234,14 +159,13 @@ __device__ __forceinline__ void g5_step(const G5Ctx &c, cv_f32x4 (&acc)[4][9], i
 
     ring_rd = ring_rd + 1 == kG5Ring ? 0 : ring_rd + 1;
     cv_wait_vm<g5_vmcnt(T)>();
-    if constexpr (T == 7 && PERS) p5_zero_ranks(c, 1 - BUF, chunk == c.cmask);
-    else if constexpr (T == 7) g5_zero_ranks(c, 1 - BUF); // this thread's slab pieces of the next chunk have landed (all but the youngest weight loads)
+    if constexpr (T == 7) g5_zero_ranks(c, 1 - BUF); // this thread's slab pieces of the next chunk have landed (all but the youngest weight loads)
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
 
     {
-        const unsigned char *wa = lds + ((PERS ? p5_ring(ring_rd) : ring_rd * kG5WBytes) + c.a_off);
+        const unsigned char *wa = lds + (ring_rd * kG5WBytes + c.a_off);
 #pragma unroll
         for (int i = 0; i < 4; ++i) anxt[i] = *(const cv_half8 *)(wa + i * 1024);
         __builtin_amdgcn_sched_barrier(0);
@@ -360,9 +284,6 @@ __device__ __forceinline__ void g5_tile(unsigned char *lds, int blk, int grid, c
     {
         const int b = blk, x = b & 7, per = tiles >> 3, rem = tiles & 7;
         tile = x * per + (x < rem ? x : rem) + (b >> 3);
-#ifdef G5_NO_XCD_MAP
-        tile = b;
-#endif
     }
     // flags bit 1: tiles in descending order (the tiles written last by the previous layer are then read first)
     tile = __builtin_amdgcn_readfirstlane((relu & 2) ? tiles - 1 - tile : tile);
@@ -445,14 +366,8 @@ __device__ __forceinline__ void g5_tile(unsigned char *lds, int blk, int grid, c
     cv_half8 a0[4], a1[4], b[9];
 #pragma unroll
     for (int i = 0; i < 4; ++i) a0[i] = *(const cv_half8 *)(lds + c.a_off + i * 1024);
-#ifdef G5_BFRAG_PER_TAP
-#pragma unroll
-    for (int n = 1; n < 9; ++n) b[n] = *(const cv_half8 *)(lds + c.vb[0] + (9 + n - 10) * 1024); // tap 0: delta = -10, cell 0 is off the board
-    b[0] = b[1];
-#else
 #pragma unroll
     for (int n = 0; n < 9; ++n) b[n] = *(const cv_half8 *)(lds + c.vb[0] + (9 + n - 9) * 1024); // the rank above this wave's: dy = -1
-#endif
 #define G5_S(j) g5_step<j>(c, acc, chunk + (j) / 9, ring_rd, ring_wr, a0, a1, b)
     if constexpr (ONE) {
         const int chunk = 0; // (the prefetches past half-step 8 wrap around to chunk 0: valid memory, never read)

@@ -107,12 +107,10 @@ class EvalOptions:
     -14 % at 1024 (where round 3's single launch per layer stays);
     ``CCZ_FUSED_LAST=0`` (fused_last): the head convolutions as a pass of their own over the stored output of the tower instead of in
     the last layer's epilogue (group-of-16 rows; same bits either way);
-    ``CCZ_CONV_PERSISTENT=N`` (persistent; round 6, A/B): the group-of-16 tower layers on N persistent workgroups per launch that walk
-    tile lists (k_conv3x3_g16_pers, csrc/cczero_conv_g16p.h; same bits); 0 = one tile per workgroup (default);
     ``CCZ_CONV_ONE_LAUNCH=0`` (one_launch; round 7): with the edge-pair kernel, the middle and edge-pair tiles of a layer as two launches
     instead of one (k_conv3x3_g16_one, csrc/cczero_conv_g16e.h; same bits)."""
 
-    FIELDS = ("fused_conv", "fused_stem", "fused_heads", "fused_last", "layout", "force", "groups", "chains", "zigzag", "edge_tiles", "persistent", "one_launch")
+    FIELDS = ("fused_conv", "fused_stem", "fused_heads", "fused_last", "layout", "force", "groups", "chains", "zigzag", "edge_tiles", "one_launch")
 
     def __init__(self, env=None):
         env = os.environ if env is None else env
@@ -127,7 +125,6 @@ class EvalOptions:
         self.zigzag = env.get("CCZ_CONV_ZIGZAG", "1") == "1"
         # group-of-16 layout: ranks 0 / 9 on the edge-pair kernel (round 4): "auto" = from 4096 boards on, together with three launch chains
         self.edge_tiles = {"0": False, "1": True}.get(env.get("CCZ_CONV_EDGE_TILES", "auto"), "auto")
-        self.persistent = int(env.get("CCZ_CONV_PERSISTENT", "0"))
         self.one_launch = env.get("CCZ_CONV_ONE_LAUNCH", "1") != "0"
         if self.layout not in ("auto", "nhwc", "g16"):
             raise ValueError("CCZ_CONV_LAYOUT must be auto, nhwc or g16")
@@ -443,17 +440,13 @@ class InferenceNet(nn.Module):
             cap = -(-(B // 16) // n_parts) * 1440            # whole 16-board groups (B is padded to a multiple of 16)
         else:
             cap = -(-(-(-B // n_parts)) // 8) * 8 * 90       # pixels of the largest range a launch may get
-        lay = (_lib.CONV_G16 | self._edge_flags(edge) | self._persistent_flag()) if g16 else 0
-        if chains > 1:
-            pool = getattr(self, "_chain_streams", None)
-            if pool is None or pool[0] != x.device or len(pool[1]) < chains:
-                pool = (x.device, chain_streams(x.device))
-                self._chain_streams = pool
+        lay = (_lib.CONV_G16 | self._edge_flags(edge)) if g16 else 0
+        pool = self._chain_pool(x.device, chains) if chains > 1 else None
         live = C.c_void_p(plan[1].data_ptr())
         xp, yp = C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr())
         down = 2 if self.opt.zigzag else 0
         for g in range(groups):
-            streams = [cur] if chains == 1 else [self._chain_streams[1][k] for k in range(chains)]
+            streams = [cur] if chains == 1 else pool[:chains]
             if chains > 1:
                 fork = torch.cuda.Event()
                 fork.record(cur)
@@ -488,16 +481,13 @@ class InferenceNet(nn.Module):
             step = -(-step // 128) * 128  # 128 boards = 45 whole tiles: no partial tile inside the batch
         bounds = [(lo + b0, lo + min(B, b0 + step)) for b0 in range(0, B, step)]
         if len(bounds) > 1:
-            pool = getattr(self, "_chain_streams", None)
-            if pool is None or pool[0] != x.device or len(pool[1]) < len(bounds):
-                pool = (x.device, chain_streams(x.device))
-                self._chain_streams = pool
+            pool = self._chain_pool(x.device, len(bounds))
             fork = torch.cuda.Event()
             fork.record(cur)
         row = 90 * 256 * x.element_size()
         chains = []
         for k, (b0, b1) in enumerate(bounds):
-            st = cur if len(bounds) == 1 else self._chain_streams[1][k]
+            st = cur if len(bounds) == 1 else pool[k]
             if len(bounds) > 1:
                 st.wait_event(fork)
             chains.append((st, C.c_void_p(st.cuda_stream), C.c_void_p(x.data_ptr() + b0 * row), C.c_void_p(y.data_ptr() + b0 * row), (b1 - b0) * 90, b0))
@@ -506,7 +496,7 @@ class InferenceNet(nn.Module):
         # alternates from layer to layer: what the previous layer wrote last (still in the Infinity Cache) is read
         # first (-0.7 % on the step; zigzag=False / CCZ_CONV_ZIGZAG=0 switches it off).
         down = 2 if self.opt.zigzag else 0
-        v2 = self.opt.force | ((_lib.CONV_G16 | self._edge_flags(edge) | self._persistent_flag()) if g16 else 0)
+        v2 = self.opt.force | ((_lib.CONV_G16 | self._edge_flags(edge)) if g16 else 0)
         wsrc = self.ws_g16 if g16 else self.ws
         for i in range(0, len(self.ws), 2):
             w1, b1_, w2, b2_ = (C.c_void_p(t.data_ptr()) for t in (wsrc[i], self.bs32[i], wsrc[i + 1], self.bs32[i + 1]))
@@ -526,16 +516,19 @@ class InferenceNet(nn.Module):
             join.record(st)
             cur.wait_event(join)
 
+    def _chain_pool(self, device, n):
+        """The launch-chain streams of ``device`` (:func:`chain_streams`, at least ``n``): the ones this copy holds, fetched again when it
+        holds none, another device's or too few."""
+        pool = getattr(self, "_chain_streams", None)
+        if pool is None or pool[0] != device or len(pool[1]) < n:
+            pool = (device, chain_streams(device))
+            self._chain_streams = pool
+        return pool[1]
+
     def _edge_flags(self, edge: bool) -> int:
         """Flag bits of the edge-pair form: middle and edge-pair tiles as ONE launch per layer and chain unless switched off."""
         from . import _lib
         return (_lib.CONV_G16_EDGE_TILES | (_lib.CONV_G16_ONE_LAUNCH if self.opt.one_launch else 0)) if edge else 0
-
-    def _persistent_flag(self) -> int:
-        """A/B switch ``persistent`` (``CCZ_CONV_PERSISTENT=N``): flag bits that run a group-of-16 tower layer on N persistent workgroups."""
-        from . import _lib
-        n = self.opt.persistent
-        return (_lib.CONV_G16_PERSISTENT | ((n & 0xfff) << 16)) if n > 0 else 0
 
     def _force_flag(self) -> int:
         """A/B switch ``force`` (``CCZ_CONV_FORCE=small|tile``): run every convolution on k_conv3x3_small / on the 256-pixel tile

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define CCZ_ABI_VERSION 7
+#define CCZ_ABI_VERSION 8           /* ABI 8: CCZ_CONV_G16 calls refuse flag 256 and bits 16..27 (the retired persistent form) */
 #define CCZ_NSQ 90
 #define CCZ_SQ_STRIDE 96            /* mailbox row stride in bytes (90 squares + 6 pad)         */
 #define CCZ_NMOVES 2086             /* action space, reference tools.py:172-272                 */
@@ -458,12 +458,8 @@ int ccz_bias_act_f16(void *stream, void *y_dev, const void *bias_dev, const void
 #define CCZ_CONV_G16_ONE_LAUNCH 512 /* with CCZ_CONV_G16_EDGE_TILES (round 7): the middle tiles and the edge-pair tiles of a layer as ONE launch
                                        (csrc/cczero_conv_g16e.h k_conv3x3_g16_one): the two classes do not depend on each other, so a launch
                                        chain pays one dependent-launch tail per layer instead of two and the shorter edge tiles fill the
-                                       last round of the middle ones. Same tiles, same values; not with CCZ_CONV_G16_PERSISTENT; the heads layer
-                                       (ccz_conv3x3_c256_heads_f16) ignores it */
-#define CCZ_CONV_G16_PERSISTENT 256 /* with CCZ_CONV_G16 (round 6, opt-in, 256 input channels): the same tiles on a FIXED number of workgroups
-                                       that walk tile lists -- no prologue after a workgroup's first tile, the next tile's operands arrive
-                                       while the epilogue's stores drain (csrc/cczero_conv_g16p.h). Bits 16..27 of the flag word = number of
-                                       workgroups (0 = 256, one per CU). Same values */
+                                       last round of the middle ones. Same tiles, same values; the heads layer (ccz_conv3x3_c256_heads_f16)
+                                       ignores it */
 int ccz_conv3x3_c256_f16(void *stream, const void *x_dev, const void *w_dev, const void *bias_f32_dev,
                          const void *residual_dev, void *y_dev, int64_t n_pixels, int32_t relu);
 /* Weights for the CCZ_CONV_G16 form, once per weight set: w [256, 3, 3, cin] fp16 (cin = 256: tower, 64: stem) ->
