@@ -16,6 +16,10 @@ self-play -- spread evenly over plies 1..200 of their games, diverged positions 
 been searched with the real evaluator up to simulation n - K/2 of the current move, so the timed window
 holds the end of one move's search, a REAL move boundary (finish_move + harvest + restart [+ all-gather])
 and the start of the next move on the kept subtrees, whatever K is. Prints ONE JSON line on rank 0.
+
+A plain run does only what that line's headline needs: set-up, warm-up, the K timed steps, --dump-outputs, the line. ``--full``
+adds what takes runs of its own: the CPU baseline (``cpu_baseline``) and the tower's post-window full-batch figure
+(``net_roofline.*_full_batch``).
 """
 from __future__ import annotations
 
@@ -46,8 +50,10 @@ def parse():
     ap.add_argument("--evaluator", choices=["net", "stub"], default="net")
     ap.add_argument("--blocks", type=int, default=40)
     ap.add_argument("--channels", type=int, default=256)
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need, after the timed window: the CPU "
+                    "baseline (one GPU; --cpu-baseline-seconds) and the tower's full-batch figure (net_roofline.*_full_batch)")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=20.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--train-every", type=int, default=0, help="BASELINE config 5: rank 0 runs one trainer update "
                     "(batch 2048, side stream, GPU0) every this many simulation steps, fed from the replay buffer")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N>1 (nccl = RCCL; gloo only to rehearse "
@@ -333,7 +339,13 @@ def main():
     n = a.playout
     if a.evaluator == "net":
         torch.manual_seed(0)
-        pvn = PolicyValueNet(device=dev, num_channels=a.channels, resblocks_num=a.blocks)
+        # PolicyValueNet also builds the Adam optimizer of its train_step, which self-play never takes; the first optimizer of a
+        # process imports torch._dynamo, 1.3-1.8 s of a plain run on an MI355X box. It is left out: same weights, nothing trains.
+        adam, torch.optim.Adam = torch.optim.Adam, lambda *args, **kwargs: None
+        try:
+            pvn = PolicyValueNet(device=dev, num_channels=a.channels, resblocks_num=a.blocks)
+        finally:
+            torch.optim.Adam = adam
         pvn.refresh_inference_copy()
         evaluator = pvn.evaluate_leaves_logits  # compact boundary: logits in, the engine gathers the legal priors
     else:
@@ -689,7 +701,7 @@ def main():
     rows_per_step = ((probes - (s1["cache_hits"] - s0["cache_hits"]) - (s1["cache_shared_rows"] - s0["cache_shared_rows"])) / a.steps) if planned else float(B)
 
     # the evaluator's dominant kernel (2 x blocks launches per step): the fused tower convolution. In the WINDOW: the HIP-event pair
-    # around the tower of every timed step over the rows those steps really computed; after it: a full-batch tower on the
+    # around the tower of every timed step over the rows those steps really computed; after it (--full): a full-batch tower on the
     # activations of a real leaf batch (what round 3 reported as the only figure)
     net_roofline = None
     if a.evaluator == "net" and rank == 0 and a.channels == 256 and B >= 192 and pvn._infer.opt_fused_conv():
@@ -890,7 +902,7 @@ def main():
                 out["multi_gpu"]["slow_rank"] = {"rank": slow_rank, "sleep_s_per_boundary": slow_s}
         if calibration is not None:
             out["rank0_calibration"] = calibration
-        if world == 1 and not solo_group and not a.no_cpu_baseline:
+        if a.full and world == 1 and not solo_group and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(a.cpu_baseline_seconds, a.blocks, a.channels)
         print(json.dumps(out), flush=True)
     if multi:
@@ -904,8 +916,8 @@ def tower_roofline(a, pvn, e, sp, B, ev, tower_probe, rows_per_step, ms_per_step
 
     ``frac`` / ``achieved`` / ``avg_launch_us`` describe the TIMED WINDOW: the HIP-event pair around the tower of every timed
     step (on the stream its launch chains fork from and join), divided by its 2 x blocks layers, against the algorithmic flops of
-    the rows those steps really computed (the evaluation cache and terminal leaves remove rows). ``*_full_batch`` is the
-    post-window figure round 3 printed: the whole 4096-row tower on the activations of a real leaf batch."""
+    the rows those steps really computed (the evaluation cache and terminal leaves remove rows). ``*_full_batch`` (``--full``) is
+    the post-window figure round 3 printed: the whole 4096-row tower on the activations of a real leaf batch."""
     inf = pvn._infer
     layers = 2 * a.blocks
     flops_per_row_layer = 2.0 * 90 * 256 * 256 * 9           # 106.17 MFLOP: one 3x3 256->256 layer on one board
@@ -931,6 +943,8 @@ def tower_roofline(a, pvn, e, sp, B, ev, tower_probe, rows_per_step, ms_per_step
                    "mfma_flops_issued_per_launch": fl * ((150.0 / 162.0 if not edge else 150.0 / 162.0 * (1.0 - 0.2 / 3.0)) if g16 else 1.0)})
         # a figure that cannot fit in the step it describes must not be printed
         assert layers * nr["avg_launch_us"] <= ms_per_step * 1e3 * 1.001, (layers * nr["avg_launch_us"], ms_per_step)
+    if not a.full:
+        return nr
     # post-window: the whole batch through the tower (no plan), three times on real activations
     leaf = sp._leaf if sp._leaf is not None else e.select_leaves()
     with torch.no_grad():

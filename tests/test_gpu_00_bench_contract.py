@@ -181,7 +181,7 @@ def test_bench_refuses_more_ranks_than_gpus_before_starting_any():
 def test_bench_under_the_launcher_with_one_rank_prints_the_single_gpu_line():
     """SCALE's N = 1 (`torch.distributed.run --nproc-per-node 1 bench.py --gpus 1`) has to be BENCH's N = 1 line: the same keys
     (roofline, cpu_baseline, no multi_gpu block), the same workload description, n_gpus 1."""
-    args = ["--steps", "10", "--warmup", "3", "--cpu-baseline-seconds", "2", "--playout", "64"] + SMALL
+    args = ["--steps", "10", "--warmup", "3", "--full", "--cpu-baseline-seconds", "2", "--playout", "64"] + SMALL
     plain = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=900)
     assert plain.returncode == 0, (plain.stdout[-2000:], plain.stderr[-3000:])
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
@@ -253,10 +253,20 @@ def test_bench_two_ranks_with_concurrent_trainer_on_rank0():
 
 
 def test_bench_single_gpu_line_contract():
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "3", "--cpu-baseline-seconds", "3", "--playout", "64"] + SMALL
+    """The plain line (what the headline needs) and the --full line (+ CPU baseline, + the tower's post-window full-batch figure):
+    the same search and the same headline keys."""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "3", "--playout", "64"] + SMALL
     r = subprocess.run(cmd, cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
+    plain = _json_line(r.stdout)
+    r = subprocess.run(cmd + ["--full", "--cpu-baseline-seconds", "3"], cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     j = _json_line(r.stdout)
+    assert "cpu_baseline" not in plain and not any(k.endswith("_full_batch") for k in plain["net_roofline"])
+    assert set(j) == set(plain) | {"cpu_baseline"} and plain["net_roofline"]["frac"] > 0 and plain["error_flags_any"] == 0
+    for key in ("metric", "unit", "dtype", "higher_is_better", "steps", "warmup", "config"):
+        assert plain[key] == j[key], key
+    assert plain["nodes_peak"] == j["nodes_peak"] and plain["roofline"]["k_bar"] == j["roofline"]["k_bar"] and plain["roofline"]["d_bar"] == j["roofline"]["d_bar"]
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
                 "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert key in j, key
