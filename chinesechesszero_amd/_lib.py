@@ -116,6 +116,8 @@ PROTOTYPES = {
     "ccz_harvest": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "ccz_harvest_records": (C.c_int, [_P, _P, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "ccz_expand_records": (C.c_int, [_P, _P, C.c_int64, C.c_uint32, _P, _P, _P, _P, C.c_int64, C.c_int64, _P]),
+    "ccz_ring_retire": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int32, _P]),
+    "ccz_sample_records": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, C.c_uint32, _P, _P, _P, _P, _P]),
     "ccz_get_stats": (C.c_int, [_P, _P, C.POINTER(Stats)]),
     "ccz_legal_moves": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P]),
     "ccz_apply_moves": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P]),

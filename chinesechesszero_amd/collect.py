@@ -12,6 +12,11 @@ Rows go to a ``TupleSink``: shard files while collecting, merged by ``TupleSink.
 mcts.npy / winners.npy / meta.json`` with the array names, dtypes and ``meta.json`` keys of the reference's
 convert.py:84-99 (what dataset.py:45-89 reads). h5py is not part of this image: the per-game HDF5 groups of
 collect.py:146-167 are not written.
+
+``--replay-plies N --train-every K`` makes the reference's collect.py + train.py pair ONE job without the disk round trip in
+between: the rank that stores the union also keeps it, as compact records, in a ``replay.RecordReplayBuffer`` of N plies in
+HBM, and every K lockstep moves it runs one ``trainer.Trainer`` step on a minibatch drawn from that ring, on the very net the
+boards are evaluated with (``weights_version`` moves: inference copy, captured graphs and evaluation caches follow).
 """
 from __future__ import annotations
 
@@ -24,7 +29,7 @@ import torch
 from .game import RED, Board, Game
 from .mcts import MCTS_AI
 from .net import PolicyValueNet
-from .parameters import C_PUCT, DATA_DIR, MODEL_DIR, PLAYOUT
+from .parameters import BATCH_SIZE, C_PUCT, DATA_DIR, MODEL_DIR, PLAYOUT
 from .tools import flip_map, log
 
 
@@ -430,7 +435,16 @@ class CollectPipeline:
     def __init__(self, init_model=None, n_boards: int = 1, n_playout: int = PLAYOUT, device: int = 0, seed: int = 0,
                  data_dir: str = DATA_DIR, reference_quirks: bool = False, num_channels: int = 256, resblocks_num: int = 40,
                  finalize_every: int = 0, on_playout=None, max_plies: int = 0, eval_cache_log2: int | None = None, gatherer=None,
-                 dense_shards: bool = False):
+                 dense_shards: bool = False, replay_plies: int = 0, train_every: int = 0, train_batch: int = BATCH_SIZE):
+        # collect + train as one job (both 0: off): the rank that stores the union keeps it in a record ring of ``replay_plies`` plies
+        # and runs one Trainer step of ``train_batch`` rows every ``train_every`` lockstep moves, once the ring holds a batch
+        self.replay_plies, self.train_every, self.train_batch = int(replay_plies), int(train_every), int(train_batch)
+        if self.replay_plies < 0 or self.train_every < 0 or self.train_batch <= 0:
+            raise ValueError("replay_plies and train_every must not be negative, train_batch must be positive")
+        if bool(self.replay_plies) != bool(self.train_every):
+            raise ValueError("replay_plies and train_every go together: a ring nobody draws from, or a trainer without one, is a mistake")
+        if self.replay_plies and n_boards <= 1:
+            raise ValueError("the replay ring is fed by the batched path: n_boards must be > 1")
         self.board = Board()                       # collect.py:28 (never advanced: source of the turn-plane quirk)
         self.game = Game(self.board, reference_quirks=reference_quirks)
         self.temp = 1.0
@@ -459,6 +473,9 @@ class CollectPipeline:
         # batched path: False (default) = finished games go to disk as compact ply records and are expanded when the sink is finalized;
         # True = the dense rows themselves while collecting (rounds 1-4: 85 x the bytes through the host per move)
         self.dense_shards = bool(dense_shards)
+        self.ring = None
+        self.trainer = None
+        self._moves_since_step = 0
 
     def load_model(self):
         """collect.py:48-62: load once; on failure fall back to a random-init net."""
@@ -574,6 +591,7 @@ class CollectPipeline:
                         e = self.selfplay.engine
                         for chunk in self.selfplay.harvest_record_chunks(1 << 16):
                             self.sink.append_records(chunk, e.record_flags(), e.plane_of_type, games=done if first else 0)
+                            self._feed_ring(chunk)
                             first = False
             elif hasattr(gatherer, "post"):
                 # asynchronous exchange (replay.AsyncRecordExchange): this rank never waits for its peers -- the finished games join
@@ -609,6 +627,7 @@ class CollectPipeline:
                     chunk = nxt
             self.iters = self.sink.games
             self._maybe_finalize()
+            self._maybe_train(gatherer)
         self.selfplay.engine.check_healthy()
         return self.iters
 
@@ -657,6 +676,7 @@ class CollectPipeline:
         from .engine import expand_records, game_aligned_chunks
         e = self.selfplay.engine
         if gatherer.rank == 0:
+            self._feed_ring(union)
             if not self.dense_shards:   # the records as they are (880 B per ply); TupleSink.finalize expands them on the GPU
                 self.sink.append_records(union, e.record_flags(), e.plane_of_type, games=games)
             else:
@@ -669,6 +689,56 @@ class CollectPipeline:
         else:
             self.sink.games += games
         self.iters = self.sink.games
+
+    # ---- collect + train as one job (reference collect.py + train.py, without data.h5 / convert.py in between) -------------
+    def _feed_ring(self, records):
+        """The storing rank keeps what it stores, as records, in the replay ring (allocated on first use)."""
+        if not getattr(self, "replay_plies", 0) or int(records.shape[0]) == 0:
+            return
+        e = self.selfplay.engine
+        if self.ring is None:
+            from .replay import RecordReplayBuffer
+            longest = int(getattr(e, "max_plies", 0) or 2048)
+            self.ring = RecordReplayBuffer(self.replay_plies, e.device, e.record_flags(), e.plane_of_type, max_game_plies=longest)
+        self.ring.append_records(records, e.record_flags(), e.plane_of_type)
+
+    def _maybe_train(self, gatherer):
+        """Every ``train_every`` lockstep moves: one ``Trainer.step`` on a minibatch of the ring (the storing rank, once the ring holds a
+        batch; ``sync=False``: neither the draw nor the update waits for the host). The step invalidates the inference copy and moves
+        ``weights_version``, so the next evaluation runs on the new weights and evaluation caches keyed to the version empty themselves.
+        Several ranks: every rank drains the exchange and takes rank 0's fp32 state (``replay.broadcast_model``) at the same move count,
+        whether or not rank 0 has trained yet (the ranks cannot know): one collective every ``train_every`` moves."""
+        if not getattr(self, "train_every", 0):
+            return
+        self._moves_since_step += 1
+        if self._moves_since_step < self.train_every:
+            return
+        self._moves_since_step = 0
+        multi = gatherer is not None and getattr(gatherer, "world", 1) > 1
+        if multi and hasattr(gatherer, "flush_iter"):   # no other collective of the job may overtake an exchange in flight
+            for x in gatherer.flush_iter():
+                self._store_union(x.union, x.games, gatherer)
+        if self.ring is not None and self.ring.size >= self.train_batch:
+            if self.trainer is None:
+                from .trainer import Trainer
+                self.trainer = Trainer(self.policy_value_net, amp_dtype="bf16")   # bf16: no GradScaler, so no host sync per update
+            self.last_losses = self.trainer.step(*self.ring.sample(self.train_batch), sync=False)
+        if multi:
+            from .replay import broadcast_model
+            broadcast_model(self.policy_value_net, src=0, what="state")
+
+    def training_report(self) -> dict:
+        """What the one-job mode did so far (syncs): trainer steps, the ring's window and refused records, the last losses."""
+        out = {"trainer_steps": 0 if self.trainer is None else self.trainer.steps, "replay_plies": self.replay_plies,
+               "train_every": self.train_every, "train_batch": self.train_batch}
+        if self.ring is not None:
+            tail, head = self.ring.window()
+            out.update(ring_tail=tail, ring_head=head, ring_bad_records=int(self.ring.bad.item()))
+        if self.trainer is not None and self.trainer.steps:
+            out.update({k: float(v) for k, v in self.last_losses.items()})
+        if self.selfplay is not None:
+            out["error_flags"] = int(self.selfplay.engine.stats()["error_flags"])
+        return out
 
     def drain_exchange(self, gatherer):
         """End of a multi-rank collection with an asynchronous exchange: blocking, every rank calls it; afterwards every record of
@@ -720,7 +790,8 @@ class CollectPipeline:
             self.sink.finalize()
 
 
-if __name__ == "__main__":
+def build_parser():
+    """The command line of ``python -m chinesechesszero_amd.collect``."""
     import argparse
     parser = argparse.ArgumentParser(description="collect Xiangqi self-play data on MI355X")
     parser.add_argument("--show", action="store_true", default=False)
@@ -736,6 +807,16 @@ if __name__ == "__main__":
     parser.add_argument("--seed", type=int, default=0)
     parser.add_argument("--backend", default="nccl", help="several ranks (under torch.distributed.run): nccl = RCCL, one GPU per rank; gloo to rehearse")
     parser.add_argument("--share-gpu", action="store_true", help="rehearsal: every rank uses cuda:0 (with --backend gloo)")
+    parser.add_argument("--replay-plies", type=int, default=0, help="collect + train as one job: the storing rank keeps the finished games "
+                        "as compact records in a replay ring of this many plies in HBM (880 B each; 0 = off; needs --train-every)")
+    parser.add_argument("--train-every", type=int, default=0, help="one trainer step on a minibatch of the ring every this many lockstep moves, "
+                        "once the ring holds a batch (0 = off; needs --replay-plies)")
+    parser.add_argument("--train-batch", type=int, default=BATCH_SIZE, help="rows of that minibatch (parameters.BATCH_SIZE)")
+    return parser
+
+
+if __name__ == "__main__":
+    parser = build_parser()
     args = parser.parse_args()
     # N collectors as ONE job (the reference starts N shell commands, README.md:31-48): python -m torch.distributed.run --nproc-per-node N
     # -m chinesechesszero_amd.collect ... -- every rank plays --boards boards, rank 0 stores the union of the finished games
@@ -761,7 +842,8 @@ if __name__ == "__main__":
             log(f"--show: examples/viewer.py is not importable here ({exc}); running without a window", "WARNING")
     pipe = CollectPipeline(init_model=args.model, n_boards=args.boards, n_playout=args.playout, data_dir=args.data_dir, seed=args.seed,
                            num_channels=args.channels, resblocks_num=args.blocks, max_plies=args.max_plies, device=device,
-                           eval_cache_log2=args.eval_cache_log2, gatherer=gatherer)
+                           eval_cache_log2=args.eval_cache_log2, gatherer=gatherer, replay_plies=args.replay_plies,
+                           train_every=args.train_every, train_batch=args.train_batch)
     if world > 1:
         from .launch import guarded
 
@@ -770,9 +852,13 @@ if __name__ == "__main__":
             # group is gone: under the barrier it kept the peers waiting past the group's timeout for any collection of more than
             # ~15 moves, and the launcher then killed rank 0 in the middle of it
             pipe.run(is_shown=args.show and rank == 0, max_calls=args.moves, viewer=viewer, finalize=False)
+            if args.replay_plies and rank == 0:
+                print("collect+train: " + json.dumps(pipe.training_report()), flush=True)
             torch.distributed.barrier()
             torch.distributed.destroy_process_group()
             pipe.sink.finalize()
             return 0
         raise SystemExit(guarded(_job))
     pipe.run(is_shown=args.show, max_calls=args.moves, viewer=viewer)
+    if args.replay_plies:
+        print("collect+train: " + json.dumps(pipe.training_report()), flush=True)

@@ -825,6 +825,28 @@ int ccz_harvest_records(ccz_engine *e, void *stream, void *records_dev, int64_t 
     return 0;
 }
 
+// plane_of_type_host (as ccz_config.plane_of_type, NULL or all zero = the reference's order) -> typepack of the record kernels
+static int typepack_of(const char *who, const uint8_t *plane_of_type_host, uint32_t *typepack)
+{
+    uint8_t pot[8] = {0, 0, 1, 2, 3, 4, 5, 6};
+    if (plane_of_type_host) {
+        bool all_zero = true;
+        for (int t = 0; t < 8; ++t) all_zero = all_zero && plane_of_type_host[t] == 0;
+        if (!all_zero) {
+            unsigned seen = 0;
+            for (int t = 1; t <= 7; ++t) {
+                const int c = plane_of_type_host[t];
+                if (c > 6 || (seen >> c & 1u)) return fail(-1, "%s: plane_of_type[1..7] must be a permutation of 0..6", who);
+                seen |= 1u << c;
+                pot[t] = (uint8_t)c;
+            }
+        }
+    }
+    *typepack = 0;
+    for (int t = 1; t <= 7; ++t) *typepack |= (uint32_t)(t - 1) << (3 * pot[t]);
+    return 0;
+}
+
 int ccz_expand_records(void *stream, const void *records_dev, int64_t n_plies, uint32_t flags, const uint8_t *plane_of_type_host,
                        void *states_f16_dev, float *pi_dev, float *z_dev, int64_t ring_rows, int64_t head_row, int32_t *bad_records_dev)
 {
@@ -836,25 +858,45 @@ int ccz_expand_records(void *stream, const void *records_dev, int64_t n_plies, u
     const int64_t rows = n_plies * ((flags & CCZ_FLAG_NO_MIRROR) ? 1 : 2);
     if (ring_rows > 0 && rows > ring_rows) return fail(-1, "ccz_expand_records: %lld rows do not fit a ring of %lld", (long long)rows, (long long)ring_rows);
     if (ring_rows == 0 && head_row != 0) return fail(-1, "ccz_expand_records: head_row needs ring_rows");
-    uint8_t pot[8] = {0, 0, 1, 2, 3, 4, 5, 6};
-    if (plane_of_type_host) {
-        bool all_zero = true;
-        for (int t = 0; t < 8; ++t) all_zero = all_zero && plane_of_type_host[t] == 0;
-        if (!all_zero) {
-            unsigned seen = 0;
-            for (int t = 1; t <= 7; ++t) {
-                const int c = plane_of_type_host[t];
-                if (c > 6 || (seen >> c & 1u)) return fail(-1, "ccz_expand_records: plane_of_type[1..7] must be a permutation of 0..6");
-                seen |= 1u << c;
-                pot[t] = (uint8_t)c;
-            }
-        }
-    }
     uint32_t typepack = 0;
-    for (int t = 1; t <= 7; ++t) typepack |= (uint32_t)(t - 1) << (3 * pot[t]);
+    const int rc = typepack_of("ccz_expand_records", plane_of_type_host, &typepack);
+    if (rc) return rc;
     hipLaunchKernelGGL(k_expand_records, dim3((unsigned)n_plies), dim3(256), 0, (hipStream_t)stream, (const uint8_t *)records_dev, (long long)n_plies,
                        flags & (CCZ_FLAG_REFERENCE_QUIRKS | CCZ_FLAG_NO_MIRROR), typepack, (uint16_t *)states_f16_dev, pi_dev, z_dev,
                        (long long)ring_rows, (long long)head_row, bad_records_dev);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int ccz_ring_retire(void *stream, const void *ring_dev, int64_t cap_plies, int64_t *window_dev, int64_t head_new, int32_t max_game_plies,
+                    int32_t *bad_records_dev)
+{
+    if (cap_plies <= 0 || head_new < 0) return fail(-1, "ccz_ring_retire: capacity must be positive and head_new non-negative");
+    if (max_game_plies <= 0 || max_game_plies > 65535) return fail(-1, "ccz_ring_retire: max_game_plies must be 1..65535 (the header's T is 16 bits)");
+    if (cap_plies < 2 * (int64_t)max_game_plies) return fail(-1, "ccz_ring_retire: a ring of %lld plies is smaller than two games of %d", (long long)cap_plies, max_game_plies);
+    if (!ring_dev || !window_dev) return fail(-1, "ccz_ring_retire: null buffer");
+    if (((uintptr_t)ring_dev & 3) || ((uintptr_t)window_dev & 7)) return fail(-1, "ccz_ring_retire: the ring must be 4-byte, the window 8-byte aligned");
+    hipLaunchKernelGGL(k_ring_retire, dim3(1), dim3(64), 0, (hipStream_t)stream, (const uint8_t *)ring_dev, (long long)cap_plies,
+                       (long long *)window_dev, (long long)head_new, (int)max_game_plies, bad_records_dev);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int ccz_sample_records(void *stream, const void *ring_dev, int64_t cap_plies, const int64_t *window_dev, const int64_t *draws_dev, int64_t batch,
+                       uint32_t flags, const uint8_t *plane_of_type_host, void *states_f16_dev, float *pi_dev, float *z_dev, int32_t *bad_records_dev)
+{
+    if (cap_plies <= 0 || batch < 0) return fail(-1, "ccz_sample_records: capacity must be positive and batch non-negative");
+    if (batch == 0) return 0;
+    if (!ring_dev || !window_dev || !draws_dev || !states_f16_dev || !pi_dev || !z_dev) return fail(-1, "ccz_sample_records: null buffer");
+    if (((uintptr_t)ring_dev | (uintptr_t)states_f16_dev) & 3) return fail(-1, "ccz_sample_records: buffers must be 4-byte aligned");
+    if (((uintptr_t)window_dev | (uintptr_t)draws_dev) & 7) return fail(-1, "ccz_sample_records: window and draws must be 8-byte aligned");
+    if (batch > (int64_t)INT32_MAX) return fail(-1, "ccz_sample_records: too many rows for one launch");
+    uint32_t typepack = 0;
+    const int rc = typepack_of("ccz_sample_records", plane_of_type_host, &typepack);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_sample_records, dim3((unsigned)batch), dim3(256), 0, (hipStream_t)stream, (const uint8_t *)ring_dev, (long long)cap_plies,
+                       (const long long *)window_dev, (const long long *)draws_dev, (long long)batch,
+                       flags & (CCZ_FLAG_REFERENCE_QUIRKS | CCZ_FLAG_NO_MIRROR), typepack, (uint16_t *)states_f16_dev, pi_dev, z_dev, bad_records_dev);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -1554,6 +1554,44 @@ __global__ __launch_bounds__(256) void k_harvest_records(Dev D, const long long 
     }
 }
 
+// One dense training row of a ply record: pass 0 = the sample, pass 1 = its mirror image. `hist` = the 8-deep history of
+// game.py:23-44 (index i = the position i plies back, the first one before that), in LDS; `rec` = the ply's own record.
+// The ONE place where a record becomes a row: k_expand_records (the exchange) and k_sample_records (the record ring)
+// both call it, so what they write is equal by construction. All 256 threads of the block call it together.
+__device__ __forceinline__ void record_to_row(const uint8_t (*hist)[96], const uint8_t *rec, const PlyHeader &h, int pass, int turn_plane,
+                                              uint32_t typepack, uint16_t *states, float *pi, float *z, long long row, int tid)
+{
+    uint32_t *srow = (uint32_t *)(states + (size_t)row * 10710);
+    for (int i = tid; i < 5355; i += 256) {
+        uint32_t v = 0;
+#pragma unroll
+        for (int hh = 0; hh < 2; ++hh) {
+            const int e = 2 * i + hh;
+            const int g = e / 630, w = e - g * 630;
+            bool on;
+            if (g == 16) on = turn_plane != 0;
+            else {
+                const int ch = w / 90, s = w - 90 * ch;
+                const int ss = pass ? (s - s % 9) + (8 - s % 9) : s; // np.flip(axis=2): file mirror
+                on = hist[g & 7][ss] == (int)((typepack >> (3 * ch)) & 7u) + 1 + (g >= 8 ? 8 : 0);
+            }
+            if (on) v |= (uint32_t)kHalfOne << (16 * hh);
+        }
+        srow[i] = v;
+    }
+    float *prow = pi + (size_t)row * kNMoves;
+    for (int i = tid; i < kNMoves; i += 256) prow[i] = 0.0f;
+    __syncthreads();
+    const uint16_t *ids = (const uint16_t *)(rec + kRecIds);
+    const float *pv = (const float *)(rec + kRecPi);
+    for (int i = tid; i < h.k; i += 256) {
+        const int id = ids[i];
+        if (id < kNMoves) prow[pass ? c_tab.flip[id] : id] = pv[i]; // mcts_prob[flip_map]
+    }
+    if (tid == 0) z[row] = h.winner < 0 ? 0.0f : (h.turn == (uint8_t)h.winner ? 1.0f : -1.0f); // game.py:213-219
+    __syncthreads();
+}
+
 // Records -> dense training rows, exactly what k_harvest writes for the same games (game.py:213-237 z and history,
 // collect.py:64-131 preprocess + flip_data). One block per ply record; rows go to a ring of ring_rows rows starting at
 // row `head` (head = 0 and ring_rows >= rows: a plain array). flags: CCZ_FLAG_REFERENCE_QUIRKS / CCZ_FLAG_NO_MIRROR;
@@ -1591,36 +1629,115 @@ __global__ __launch_bounds__(256) void k_expand_records(const uint8_t *recs, lon
     for (int pass = 0; pass < (mirror ? 2 : 1); ++pass) {
         long long row = head + mul * first + (pass ? T : 0) + t;
         row = ring_rows > 0 ? row % ring_rows : row;
-        uint32_t *srow = (uint32_t *)(states + (size_t)row * 10710);
-        for (int i = tid; i < 5355; i += 256) {
-            uint32_t v = 0;
-#pragma unroll
-            for (int hh = 0; hh < 2; ++hh) {
-                const int e = 2 * i + hh;
-                const int g = e / 630, w = e - g * 630;
-                bool on;
-                if (g == 16) on = turn_plane != 0;
-                else {
-                    const int ch = w / 90, s = w - 90 * ch;
-                    const int ss = pass ? (s - s % 9) + (8 - s % 9) : s; // np.flip(axis=2): file mirror
-                    on = hist[g & 7][ss] == (int)((typepack >> (3 * ch)) & 7u) + 1 + (g >= 8 ? 8 : 0);
-                }
-                if (on) v |= (uint32_t)kHalfOne << (16 * hh);
-            }
-            srow[i] = v;
-        }
-        float *prow = pi + (size_t)row * kNMoves;
-        for (int i = tid; i < kNMoves; i += 256) prow[i] = 0.0f;
-        __syncthreads();
-        const uint16_t *ids = (const uint16_t *)(rec + kRecIds);
-        const float *pv = (const float *)(rec + kRecPi);
-        for (int i = tid; i < h.k; i += 256) {
-            const int id = ids[i];
-            if (id < kNMoves) prow[pass ? c_tab.flip[id] : id] = pv[i]; // mcts_prob[flip_map]
-        }
-        if (tid == 0) z[row] = h.winner < 0 ? 0.0f : (h.turn == (uint8_t)h.winner ? 1.0f : -1.0f); // game.py:213-219
-        __syncthreads();
+        record_to_row(hist, rec, h, pass, turn_plane, typepack, states, pi, z, row, tid);
     }
+}
+
+// ------------------------------------------------------------------ the replay ring of compact records
+// The ring keeps what the exchange delivers -- 880 B per ply instead of the 2 x 29,768 B of dense rows -- and a row is
+// formed only when a minibatch draws it (train.py:114-122: the DataLoader's shuffle over everything convert.py wrote;
+// collect.py:64-131: what it wrote). window = {tail, head}: logical ply counters that only grow, physical slot =
+// counter % cap_plies; [tail, head) holds whole games only (k_ring_retire), so a game may wrap around the physical end
+// of the ring but is never cut by it.
+#ifdef CCZ_BOUNDS
+// the stateless ring kernels have no Dev: a stray index adds 65536 to *bad (tests ask for bad == 0) and goes to element 0
+__device__ __forceinline__ long long ring_checked(int32_t *bad, long long i, long long n)
+{
+    if (i < 0 || i >= n) { if (bad) atomicAdd(bad, 65536); return 0; }
+    return i;
+}
+#define CCZ_RING_IDX(bad_, i_, n_) ring_checked((bad_), (long long)(i_), (long long)(n_))
+#else
+#define CCZ_RING_IDX(bad_, i_, n_) (i_)
+#endif
+
+// One block per drawn row. draw u -> r = u % live (live = (head - tail) * mul rows, mul = 1 without mirror images),
+// ply p = tail + r / mul, pass = r % mul; output row blockIdx.x gets exactly the bytes k_expand_records writes for that
+// ply and pass. A record that is not part of a whole game inside the window (or an empty window, or a negative draw)
+// counts in *bad and its row is zeros; nothing outside the ring is read. HBM-write-bound: 29.8 KB out, <= 1.6 KB in.
+__global__ __launch_bounds__(256) void k_sample_records(const uint8_t *ring, long long cap_plies, const long long *window, const long long *draws,
+                                                          long long batch, uint32_t flags, uint32_t typepack, uint16_t *states, float *pi,
+                                                          float *z, int32_t *bad)
+{
+    const long long j = blockIdx.x;
+    const int tid = threadIdx.x;
+    if (j >= batch) return;
+    __shared__ __align__(16) uint8_t hist[8][96];
+    __shared__ PlyHeader sh;
+    const bool quirks = (flags & 1u) != 0;
+    const long long mul = (flags & 2u) ? 1 : 2;
+    const long long tail = window[0], head = window[1], u = draws[j];
+    bool ok = tail >= 0 && head > tail && head - tail <= cap_plies && u >= 0; // (block-uniform: every thread reads the same words)
+    long long p = 0;
+    int pass = 0;
+    const uint8_t *rec = ring;
+    if (ok) {
+        const long long r = u % ((head - tail) * mul);
+        p = tail + r / mul;
+        pass = (int)(r % mul);
+        rec = ring + (size_t)CCZ_RING_IDX(bad, p % cap_plies, cap_plies) * kRecBytes;
+        if (tid == 0) sh = *(const PlyHeader *)(rec + kRecHdr);
+    }
+    __syncthreads();
+    PlyHeader h = {};
+    long long first = 0;
+    if (ok) {
+        h = sh;
+        first = p - h.t;
+        ok = h.t < h.T && h.k <= kMaxLegal && first >= tail && first + h.T <= head; // a whole game inside the window
+    }
+    if (!ok) {
+        uint32_t *srow = (uint32_t *)(states + (size_t)j * 10710);
+        for (int i = tid; i < 5355; i += 256) srow[i] = 0u;
+        for (int i = tid; i < kNMoves; i += 256) pi[(size_t)j * kNMoves + i] = 0.0f;
+        if (tid == 0) {
+            z[j] = 0.0f;
+            if (bad) atomicAdd(bad, 1);
+        }
+        return;
+    }
+    const int t = h.t, T = h.T;
+    const int te = quirks ? T - 1 : t; // game.py:234-237: every sample aliases the history at the LAST recorded ply
+    if (tid < 192) { // the 8-deep history of game.py:23-44; the game may wrap around the physical end of the ring
+        const int i = tid / 24, w = tid - 24 * i;
+        int tp = te - i;
+        if (tp < 0) tp = 0;
+        const long long slot = CCZ_RING_IDX(bad, (first + tp) % cap_plies, cap_plies);
+        ((uint32_t *)hist[i])[w] = ((const uint32_t *)(ring + (size_t)slot * kRecBytes))[w];
+    }
+    __syncthreads();
+    record_to_row(hist, rec, h, pass, quirks ? 1 : h.turn, typepack, states, pi, z, j, tid);
+}
+
+// After an append of logical plies [head_old, head_new) has been copied into the ring (it overwrote the slots of
+// [head_old - cap, head_new - cap)): head = head_new, tail = max(tail, head_new - cap), and a tail that landed inside a
+// game moves on to the start of the next one, so the window advances by WHOLE GAMES only. The record at tail is one the
+// copy did not overwrite (tail >= head_new - cap), so this is race-free in stream order and needs no host sync. A game
+// at the tail with more than max_game_plies plies is counted in *bad and skipped; so is a header that cannot be one
+// (t >= T: the window is emptied). One thread; tail and head are written with ordinary vector stores.
+__global__ void k_ring_retire(const uint8_t *ring, long long cap_plies, long long *window, long long head_new, int max_game_plies, int32_t *bad)
+{
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    long long tail = window[0];
+    if (tail < head_new - cap_plies) tail = head_new - cap_plies;
+    if (tail < 0) tail = 0;
+    int nbad = 0;
+    while (tail < head_new) {
+        const PlyHeader h = *(const PlyHeader *)(ring + (size_t)CCZ_RING_IDX(bad, tail % cap_plies, cap_plies) * kRecBytes + kRecHdr);
+        const int t = h.t, T = h.T;
+        if (t >= T) { // not a ply header
+            ++nbad;
+            tail = head_new;
+            break;
+        }
+        if (T > max_game_plies) ++nbad;
+        else if (t == 0) break;
+        tail += T - t; // to the start of the next game
+    }
+    if (tail > head_new) tail = head_new;
+    if (nbad && bad) atomicAdd(bad, nbad);
+    window[0] = tail;
+    window[1] = head_new;
 }
 
 // ------------------------------------------------------------------ stateless batch rules

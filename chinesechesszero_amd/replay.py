@@ -719,6 +719,138 @@ class ReplayBuffer:
         return self.states[idx], self.pi[idx], self.z[idx]
 
 
+class RecordReplayBuffer:
+    """Fixed-capacity ring of COMPACT PLY RECORDS resident in HBM (880 B per ply = 440 B per training row against the 29,768 B
+    of :class:`ReplayBuffer`: 30 GB hold ~34 M plies = 68 M rows); a dense row is formed only when a minibatch draws it.
+
+    The trainer-side counterpart of the exchange: what :class:`AsyncRecordExchange` / :func:`exchange_finished_games` hand over
+    is copied into the ring as it is (:meth:`append_records`, the call shape of :meth:`ReplayBuffer.append_records`), and
+    :meth:`sample` lets ``ccz_sample_records`` write -- byte for byte what ``ccz_expand_records`` would have written -- only
+    the rows it draws, mirror images included (they cost nothing until they are drawn). Replaces reference train.py:114-122
+    (DataLoader shuffle over everything convert.py wrote) + collect.py:64-131 without the disk round trip.
+
+    The live window ``[tail, head)`` counts logical plies (the physical slot is ``counter % capacity_plies``) and holds whole
+    games only: after every append ``ccz_ring_retire`` moves ``tail`` past the games the append overwrote, up to the next game
+    start. ``head`` follows from tensor shapes and is known on the host; ``tail`` lives on the device only, so neither
+    appending nor sampling ever waits for the host (:meth:`window` does, for tests and reports). Records whose game is longer
+    than ``max_game_plies``, or is cut, are counted in the ``bad`` counter and never served.
+
+    ``flags`` (``engine.record_flags()``: quirk mode, mirror) and ``plane_of_type`` are the ring's: every row it serves is
+    formed under them."""
+
+    def __init__(self, capacity_plies: int, device, flags: int = 0, plane_of_type=None, max_game_plies: int = 2048):
+        from . import _lib
+        self.cap = int(capacity_plies)
+        self.max_game_plies = int(max_game_plies)
+        if not 0 < self.max_game_plies <= 65535:
+            raise ValueError("max_game_plies must be 1..65535 (the record header counts plies in 16 bits)")
+        if self.cap < 2 * self.max_game_plies:
+            raise ValueError(f"capacity_plies ({self.cap}) must be at least 2 x max_game_plies ({self.max_game_plies}): "
+                             "the window advances by whole games")
+        self.flags = int(flags)
+        if self.flags & ~(_lib.FLAG_REFERENCE_QUIRKS | _lib.FLAG_NO_MIRROR):
+            raise ValueError("flags: only FLAG_REFERENCE_QUIRKS and FLAG_NO_MIRROR form rows")
+        self.plane_of_type = self._plane_map(plane_of_type)
+        self.mul = 1 if self.flags & _lib.FLAG_NO_MIRROR else 2
+        d = torch.device(device)
+        self.device = d
+        self.records = torch.zeros((self.cap, REC_BYTES), dtype=torch.uint8, device=d)
+        self._window = torch.zeros((2,), dtype=torch.int64, device=d)      # {tail, head}, written by ccz_ring_retire only
+        self.bad = torch.zeros((1,), dtype=torch.int32, device=d)          # records refused so far (cut or over-long games)
+        self.head = 0        # logical plies appended so far (the device's head once the queued appends have run)
+        self.size = 0        # rows the window holds AT MOST (the device may have retired part of a game more)
+        self.total = 0       # rows ever appended
+
+    @staticmethod
+    def _plane_map(plane_of_type):
+        """None, all zero or the identity = the reference's order (None); else ``plane_of_type[1..7]`` as a tuple of 8
+        (``ccz_config.plane_of_type``)."""
+        if plane_of_type is None:
+            return None
+        pot = tuple(int(x) for x in plane_of_type)
+        if len(pot) != 8:
+            raise ValueError("plane_of_type has 8 entries (index = piece type, entry 0 unused)")
+        if not any(pot):
+            return None
+        if sorted(pot[1:]) != list(range(7)):
+            raise ValueError("plane_of_type[1..7] must be a permutation of 0..6")
+        return None if pot[1:] == tuple(range(7)) else (0,) + pot[1:]
+
+    def _pot(self):
+        import ctypes as C
+        return None if self.plane_of_type is None else (C.c_uint8 * 8)(*self.plane_of_type)
+
+    def _stream(self):
+        import ctypes as C
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def append_records(self, records: torch.Tensor, flags: int | None = None, plane_of_type=None, bad=None) -> int:
+        """Copy compact ply records (uint8 [P, 880], whole games) into the ring -- at most two ``copy_`` segments -- and retire
+        the games they overwrote. Returns the ROWS added (``P`` x 1 or 2), as :meth:`ReplayBuffer.append_records` does.
+        ``flags`` / ``plane_of_type``, if given, must be the ring's (``ValueError`` otherwise); ``bad``: an int32 device
+        counter of refused records in place of the ring's own. Asynchronous on the current stream."""
+        from . import _lib
+        from .engine import _ptr, game_aligned_chunks
+        if flags is not None and (int(flags) & (_lib.FLAG_REFERENCE_QUIRKS | _lib.FLAG_NO_MIRROR)) != self.flags:
+            raise ValueError(f"records formed under flags {int(flags)} do not belong in a ring of flags {self.flags}")
+        if plane_of_type is not None and self._plane_map(plane_of_type) != self.plane_of_type:
+            raise ValueError("records of another plane map do not belong in this ring")
+        if records.dim() != 2 or int(records.shape[1]) != REC_BYTES or records.dtype != torch.uint8:
+            raise ValueError("records must be uint8 [P, 880]")
+        P = int(records.shape[0])
+        if P == 0:
+            return 0
+        if P > self.cap:   # more than the ring holds: game by game, so that an append never overwrites itself and the newest games survive
+            return sum(self.append_records(part, None, None, bad) for part in game_aligned_chunks(records, self.cap))
+        lo = self.head % self.cap
+        first = min(P, self.cap - lo)
+        self.records[lo:lo + first].copy_(records[:first], non_blocking=True)
+        if P > first:
+            self.records[:P - first].copy_(records[first:], non_blocking=True)
+        self.head += P
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().ccz_ring_retire(self._stream(), _ptr(self.records), self.cap, _ptr(self._window), self.head,
+                                                  self.max_game_plies, _ptr(self.bad if bad is None else bad)))
+        self.size = min(self.cap, self.size // self.mul + P) * self.mul
+        self.total += P * self.mul
+        return P * self.mul
+
+    def sample_at(self, draws: torch.Tensor, bad=None):
+        """Rows of the given draws (int64 [batch] on the ring's device, non-negative): draw ``u`` is row ``u % live`` of the window,
+        ``live = (head - tail) x mul`` read on the device; row ``r`` is ply ``tail + r // mul``, pass ``r % mul`` (1 = mirror image).
+        Returns ``(states fp16 [batch,17,7,10,9], pi f32 [batch,2086], z f32 [batch])`` as :meth:`ReplayBuffer.sample` does."""
+        from . import _lib
+        from .engine import _ptr
+        if self.head == 0:
+            raise ValueError("the replay ring is empty: nothing was ever appended")
+        if not (draws.dtype == torch.int64 and draws.dim() == 1 and draws.device == self.records.device and draws.is_contiguous()):
+            raise ValueError("draws must be a contiguous int64 [batch] tensor on the ring's device")
+        n = int(draws.shape[0])
+        d = self.records.device
+        states = torch.empty((n, 17, 7, 10, 9), dtype=torch.float16, device=d)
+        pi = torch.empty((n, NMOVES), dtype=torch.float32, device=d)
+        z = torch.empty((n,), dtype=torch.float32, device=d)
+        with torch.cuda.device(d):
+            _lib.check(_lib.lib().ccz_sample_records(self._stream(), _ptr(self.records), self.cap, _ptr(self._window), _ptr(draws), n,
+                                                     self.flags, self._pot(), _ptr(states), _ptr(pi), _ptr(z),
+                                                     _ptr(self.bad if bad is None else bad)))
+        return states, pi, z
+
+    def sample(self, batch: int, generator=None):
+        """A uniform minibatch over the live rows, mirror images included, without a host sync: the draws are
+        ``torch.randint(0, 2**62)`` on the device and the kernel reduces them modulo the live row count, which only the device
+        knows. The modulo bias is below ``live / 2**62`` < 2**-28 for any ring that fits in HBM (live < 2**34 rows)."""
+        if self.head == 0:
+            raise ValueError("the replay ring is empty: nothing was ever appended")
+        draws = torch.randint(0, 2 ** 62, (int(batch),), device=self.records.device, dtype=torch.int64, generator=generator)
+        return self.sample_at(draws)
+
+    def window(self):
+        """``(tail, head)`` in logical plies, as the device has them after everything queued so far (syncs)."""
+        w = self._window.cpu()
+        return int(w[0]), int(w[1])
+
+
 def _flat_bytes(tensors, device):
     """The tensors' memory as ONE uint8 buffer on ``device`` (any mix of dtypes), and the (offset, nbytes) of each."""
     spans, off = [], 0

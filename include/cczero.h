@@ -405,6 +405,29 @@ int ccz_expand_records(void *stream, const void *records_dev, int64_t n_plies, u
                        const uint8_t *plane_of_type_host, void *states_f16_dev, float *pi_dev, float *z_dev,
                        int64_t ring_rows, int64_t head_row, int32_t *bad_records_dev);
 
+/* ---- the replay ring of compact records ------------------------------------------------------------ */
+/* A trainer-side ring that keeps finished games AS RECORDS (ring_dev: cap_plies x 880 B in HBM) and forms a dense row only
+ * when a minibatch draws it: 1/67 of the bytes of a ring of rows, so the trainer sees hours of play, not seconds. Together the
+ * two calls replace the reference's train.py:114-122 (DataLoader shuffle over everything convert.py wrote) + collect.py:64-131
+ * (preprocess, flip_data) without the disk round trip. window_dev: int64 {tail, head} on the device, logical ply counters that
+ * only grow (zero them once); physical slot = counter % cap_plies; [tail, head) holds whole games only. Both calls are
+ * stateless (no engine) and asynchronous on `stream`.
+ *
+ * ccz_ring_retire: call after the records of logical plies [head_old, head_new) have been copied to their slots (an append of
+ * at most cap_plies records, whole games): head = head_new, tail = max(tail, head_new - cap_plies), then tail moves on to the
+ * next game start, so that the window advances by whole games only. Needs cap_plies >= 2 * max_game_plies; a game at the tail
+ * longer than max_game_plies (or a header with t >= T) is counted in *bad_records_dev (int32, may be NULL) and skipped. */
+int ccz_ring_retire(void *stream, const void *ring_dev, int64_t cap_plies, int64_t *window_dev, int64_t head_new,
+                    int32_t max_game_plies, int32_t *bad_records_dev);
+/* ccz_sample_records: draws_dev int64 [batch], non-negative. With live = (head - tail) * mul rows (mul = 1 under
+ * CCZ_FLAG_NO_MIRROR, else 2) draw u means row r = u % live: ply tail + r / mul, pass r % mul (1 = the mirror image). Output
+ * row j of states fp16 [batch,17,7,10,9], pi float32 [batch,2086], z float32 [batch] gets, byte for byte, what
+ * ccz_expand_records writes for that ply and pass (flags, plane_of_type_host: as there). A drawn record that is not part of a
+ * whole game inside the window, or an empty window, counts in *bad_records_dev and yields a row of zeros. */
+int ccz_sample_records(void *stream, const void *ring_dev, int64_t cap_plies, const int64_t *window_dev,
+                       const int64_t *draws_dev, int64_t batch, uint32_t flags, const uint8_t *plane_of_type_host,
+                       void *states_f16_dev, float *pi_dev, float *z_dev, int32_t *bad_records_dev);
+
 int ccz_get_stats(ccz_engine *e, void *stream, ccz_stats *out); /* syncs */
 
 /* ---- stateless batch rules (parity tests, perft; replaces cchess legal_moves / game-end) ---- */
