@@ -1,7 +1,11 @@
 // cczero_conv.h -- the evaluator's tower convolution as ONE kernel: 3x3, 256 -> 256 channels on the
 // 10 x 9 board, NHWC fp16, fp32 accumulate, + bias [+ residual] + ReLU in the epilogue.
 //
-//   y[p, co] = relu( bias[co] + sum_{tap, ci} w[co, tap, ci] * x[p + 9*dy + dx, ci]  [+ res[p, co]] )
+//   a[p, co] = bias[co] + sum_{tap, ci} w[co, tap, ci] * x[p + 9*dy + dx, ci]      fp32 accumulator, started at the bias
+//   y[p, co] = relu?( fp16( fp16(a[p, co]) + res[p, co] ) )                            with a residual: TWO roundings -- the
+//   y[p, co] = relu?( fp16(a[p, co]) )                                                 accumulator to fp16, then an fp16 add
+//
+// (the residual is NOT added to the fp32 accumulator; tests/test_gpu_evaluator_f64.py pins this chain bit for bit)
 //
 // (reference net.py:20-43: conv3x3 -> BN -> [+x] -> ReLU with BN folded into w / bias; 80 of the 83
 // convolutions of the 40-block tower have exactly this shape.) An implicit GEMM built around the board:

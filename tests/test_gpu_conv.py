@@ -7,6 +7,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from evaluator_f64 import _from_g16, _pack_w, _to_g16  # the layout helpers live with the float64 references
+
 pytestmark = pytest.mark.gpu
 
 
@@ -313,28 +315,6 @@ def test_fused_evaluator_inside_hipgraph_capture_equals_eager():
         torch.cuda.synchronize()
     assert torch.equal(t_graph, t_eager)
     assert torch.allclose(p_graph, p_eager, atol=2e-3) and torch.allclose(v_graph, v_eager, atol=2e-2)
-
-
-def _to_g16(t):
-    """[B, C, 10, 9] channels-last (rows b * 90 + pos) -> the same bytes reordered to rows (g * 90 + pos) * 16 + j, board 16 g + j"""
-    B, Cn = t.shape[0], t.shape[1]
-    return t.permute(0, 2, 3, 1).reshape(B // 16, 16, 90, Cn).permute(0, 2, 1, 3).contiguous()
-
-
-def _pack_w(w_nhwc, cin):
-    """ccz_pack_conv_weights_g16_f16 on [256, 3, 3, cin] weights; must equal the torch twin the evaluator uses"""
-    from chinesechesszero_amd import _lib
-    from chinesechesszero_amd.net import pack_conv_weights_g16
-    wp = torch.empty(cin // 32, 9, 256, 32, dtype=torch.float16, device=w_nhwc.device)
-    s = C.c_void_p(torch.cuda.current_stream(w_nhwc.device).cuda_stream)
-    _lib.check(_lib.lib().ccz_pack_conv_weights_g16_f16(s, C.c_void_p(w_nhwc.data_ptr()), C.c_void_p(wp.data_ptr()), cin))
-    assert torch.equal(wp, pack_conv_weights_g16(w_nhwc.view(256, 3, 3, cin)))
-    return wp
-
-
-def _from_g16(t, B):
-    Cn = t.shape[-1]
-    return t.reshape(B // 16, 90, 16, Cn).permute(0, 2, 1, 3).reshape(B, 10, 9, Cn).permute(0, 3, 1, 2)
 
 
 @pytest.mark.parametrize("boards", [16, 80, 96, 272])
