@@ -84,6 +84,7 @@ PROTOTYPES = {
     "ccz_destroy": (C.c_int, [_P]),
     "ccz_reset": (C.c_int, [_P, _P, _P]),
     "ccz_set_position": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, C.c_int32]),
+    "ccz_set_positions": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int32, _P, _P]),
     "ccz_reset_tree": (C.c_int, [_P, _P, _P]),
     "ccz_select_leaves": (C.c_int, [_P, _P, _P]),
     "ccz_zero_leaf_input": (C.c_int, [_P, _P, _P]),
@@ -105,6 +106,7 @@ PROTOTYPES = {
     "ccz_gather_priors_routed": (C.c_int, [_P, _P, _P, _P, C.c_int32, _P, _P]),
     "ccz_finish_move": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32]),
     "ccz_root_children": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
+    "ccz_principal_variations": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
     "ccz_root_pi": (C.c_int, [_P, _P, _P, _P]),
     "ccz_move_distribution": (C.c_int, [_P, _P, _P, _P, _P, _P]),
     "ccz_game_status": (C.c_int, [_P, _P, _P, _P, _P, _P]),

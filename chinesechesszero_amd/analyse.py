@@ -1,0 +1,206 @@
+"""Batched position analysis: "what does the search think of these N positions?" on the lockstep engine.
+
+``BatchedAnalysis`` loads ``n_boards`` positions at a time -- each with the moves that led to it, so that repetitions and the
+sixty-move clock count as they would in the game -- with ONE ``set_positions`` launch, searches them in lockstep
+(``BatchedSelfPlay.search``: no move is played) and reads the principal variations of every tree with ONE
+``principal_variations`` launch. The one-game front ends (``MCTS_AI``, the UCI loop) answer the same question one position at a
+time; this is the path for a file of positions: a test suite, an opening book, games to label.
+
+Command line::
+
+    python -m chinesechesszero_amd.analyse FILE [--playout N] [--boards B] [--multipv K] [--max-len L] [--weights PATH] [--out FILE.jsonl]
+
+FILE holds one UCI position per line (``startpos [moves ...]`` or ``fen <fen> [moves ...]``; blank lines and ``#`` comments are
+skipped); one JSON object per position goes to ``--out`` (stdout without it), a one-line summary to stderr.
+"""
+from __future__ import annotations
+
+import json
+import sys
+import time
+
+import numpy as np
+
+from ._lib import CczError
+from .game import Board
+
+
+def cp_of(q: float, visits: int) -> int:
+    """Centipawn DISPLAY value of a stored Q (side to move's view, -1 .. 1): the project's logistic convention,
+    ``round(arena.elo_of_score((1 + Q) / 2, games=max(1, N)))`` -- the score is clamped half a "game" (visit) from either end, so
+    a forced win shows as a large finite number that grows with the visits. A mapping for GUIs, nothing more: Q is not calibrated
+    in pawns."""
+    from .arena import elo_of_score
+    return int(round(elo_of_score((1.0 + float(q)) / 2.0, games=max(1, int(visits)))))
+
+
+def parse_positions(lines) -> list[tuple[int, Board]]:
+    """``[(line number, Board)]`` of an iterable of text lines, one UCI position each (the arguments of ``position``); blank lines
+    and ``#`` comments are skipped. Moves are NOT checked here (the device does that where they are played); a line that cannot be
+    read at all raises ``ValueError`` naming its line number."""
+    from .uci import parse_position
+    out = []
+    for no, raw in enumerate(lines, 1):
+        text = raw.split("#", 1)[0].strip()
+        if not text:
+            continue
+        tok = text.split()
+        if tok[0] == "position":
+            tok = tok[1:]
+        try:
+            out.append((no, parse_position(tok, validate=False)))
+        except (ValueError, KeyError, IndexError) as e:
+            raise ValueError(f"line {no}: {e} ({text!r})") from None
+    return out
+
+
+def make_record(status: str, root_visits: int = 0, lines=()) -> dict:
+    """One result record: ``status`` ("ok", "illegal move i", "invalid position", "history too long", "game over: ..."),
+    ``bestmove`` (the first move of line 0, or None), ``root_visits``, ``lines`` = [{moves (uci), visits, q, prior}]."""
+    lines = [dict(moves=list(l["moves"]), visits=[int(v) for v in l["visits"]], q=float(l["q"]), prior=float(l["prior"])) for l in lines]
+    return {"status": status, "bestmove": lines[0]["moves"][0] if lines and lines[0]["moves"] else None,
+            "root_visits": int(root_visits), "lines": lines}
+
+
+def _winner_text(winner) -> str:
+    return "game over: draw" if winner is None or winner < 0 else f"game over: {'red' if winner else 'black'} wins"
+
+
+class BatchedAnalysis:
+    """``evaluator``: what ``BatchedSelfPlay`` takes (``leaf fp16 [B,17,7,10,9] -> (prob | logits, value)``), or an object with
+    ``evaluate_leaves_logits`` (a ``PolicyValueNet``). With a plan-capable evaluator and ``eval_cache_log2 > 0`` (the default for
+    192 boards and more, as in self-play) the search runs on the planned boundary with the evaluation cache; the cache is kept
+    across chunks and cleared only when the evaluator's weights version changes."""
+
+    def __init__(self, evaluator, n_boards: int, n_playout: int = 400, multipv: int = 1, max_len: int = 32, **engine_kw):
+        from .selfplay import BatchedSelfPlay
+        ev = getattr(evaluator, "evaluate_leaves_logits", evaluator)
+        if not callable(ev):
+            raise TypeError("BatchedAnalysis: the evaluator must be callable or have evaluate_leaves_logits")
+        if not 1 <= int(multipv) <= 128 or int(max_len) < 1 or int(n_playout) < 1:
+            raise ValueError("BatchedAnalysis: multipv must be 1..128, max_len and n_playout >= 1")
+        if "eval_cache_log2" not in engine_kw:
+            engine_kw["eval_cache_log2"] = 22 if (int(n_boards) >= 192 and getattr(ev, "accepts_plan", False)) else 0
+        engine_kw.setdefault("mirror", False)
+        self.sp = BatchedSelfPlay(ev, int(n_boards), n_playout=int(n_playout), eps=0.0, **engine_kw)   # no GPU: CczError
+        self.engine = self.sp.engine
+        self.B, self.n_playout, self.multipv, self.max_len = int(n_boards), int(n_playout), int(multipv), int(max_len)
+        self.positions = self.steps = self.sims = 0
+        self.seconds = 0.0
+        self._rows = None   # evaluator rows, summed on the device (planned boundary: the plan's count per step)
+
+    def _count_rows(self, stage, _sim):
+        if stage == "eval1":
+            self.steps += 1
+            if self.sp.planned:
+                self._rows += self.engine.n_miss[0]
+
+    def analyse(self, positions) -> list[dict]:
+        """One record (:func:`make_record`) per position, in input order. ``positions``: ``game.Board`` objects (their start
+        position and move stack are loaded) or UCI ``position`` argument strings."""
+        import torch
+        from .tools import move_id2move_action as uci_of
+        from .uci import parse_position
+        boards = [p if isinstance(p, Board) else parse_position(str(p).split(), validate=False) for p in positions]
+        e, sp, B = self.engine, self.sp, self.B
+        if self._rows is None:
+            self._rows = torch.zeros((), dtype=torch.int64, device=e.device)
+        out = []
+        t0 = time.perf_counter()
+        sims0 = e.stats()["sims"]
+        for c0 in range(0, len(boards), B):
+            chunk = boards[c0:c0 + B]
+            n = len(chunk)
+            sq = np.zeros((B, 90), np.uint8)
+            turn = np.ones(B, np.uint8)
+            half = np.zeros(B, np.int32)
+            moves = [[] for _ in range(B)]
+            for j, bd in enumerate(chunk):
+                sq[j], turn[j], half[j] = bd._start[0], 1 if bd._start[1] else 0, bd._start[2]
+                moves[j] = [m.id for m in bd.move_stack]
+            status = e.set_positions(sq, turn, half, moves, park=np.arange(B) >= n)   # the tail of the last chunk is parked
+            sp._sim, sp._leaf, sp._acc = 0, None, 0      # fresh roots: whatever leaf was pending belongs to the old ones
+            st = e.game_status()
+            if not st["over"][:n].all():
+                sp.search(hooks=self._count_rows)
+            pv = e.principal_variations(self.multipv, self.max_len)
+            e.check_healthy()
+            for j, bd in enumerate(chunk):
+                s = int(status[j])
+                if s > 0:
+                    out.append(make_record(f"illegal move {s - 1}"))
+                elif s < 0:
+                    out.append(make_record("invalid position" if s == -1 else "history too long"))
+                elif st["over"][j]:
+                    out.append(make_record(_winner_text(int(st["winner"][j]))))
+                else:
+                    lines = []
+                    for r in range(self.multipv):
+                        ln = int(pv["len"][j, r])
+                        if ln:
+                            lines.append({"moves": [uci_of[int(i)] for i in pv["moves"][j, r, :ln]], "visits": pv["visits"][j, r, :ln],
+                                          "q": pv["q"][j, r], "prior": pv["prior"][j, r]})
+                    if lines:
+                        out.append(make_record("ok", pv["root_visits"][j], lines))
+                    else:   # a position given without moves that is already decided: the root never got children
+                        oc = bd.outcome()
+                        out.append(make_record("ok" if oc is None else _winner_text(None if oc.winner is None else int(bool(oc.winner))),
+                                               pv["root_visits"][j]))
+        torch.cuda.synchronize(e.device)
+        self.seconds += time.perf_counter() - t0
+        self.positions += len(boards)
+        self.sims += e.stats()["sims"] - sims0
+        return out
+
+    def summary(self) -> dict:
+        rows = int(self._rows.item()) if (self._rows is not None and self.sp.planned) else self.steps * self.B
+        sec = max(self.seconds, 1e-9)
+        return {"positions": self.positions, "seconds": round(self.seconds, 3), "positions_per_s": round(self.positions / sec, 2),
+                "sims_per_s": round(self.sims / sec, 1), "evaluator_rows_per_step": round(rows / max(1, self.steps), 2)}
+
+
+def main(argv=None) -> int:
+    import argparse
+    ap = argparse.ArgumentParser(prog="python -m chinesechesszero_amd.analyse", description=__doc__.split("\n\n")[0])
+    ap.add_argument("file", metavar="FILE", help="one UCI position per line: startpos [moves ...] | fen <fen> [moves ...]")
+    ap.add_argument("--playout", type=int, default=400)
+    ap.add_argument("--boards", type=int, default=1024)
+    ap.add_argument("--multipv", type=int, default=1)
+    ap.add_argument("--max-len", type=int, default=32)
+    ap.add_argument("--weights", default=None, help="model file (default: random initialisation)")
+    ap.add_argument("--out", default=None, help="JSON lines file (default: stdout)")
+    args = ap.parse_args(argv)
+    with open(args.file, encoding="utf-8") as f:
+        try:
+            parsed = parse_positions(f)
+        except ValueError as e:
+            print(f"{args.file}: {e}", file=sys.stderr)
+            return 2
+    import torch
+    if not torch.cuda.is_available():
+        print("analyse: no GPU visible to PyTorch-ROCm; the analysis has no CPU fallback", file=sys.stderr)
+        return 1
+    from .net import PolicyValueNet
+    try:
+        pvn = PolicyValueNet(model=args.weights, device="cuda:0")
+        an = BatchedAnalysis(pvn, max(1, min(args.boards, len(parsed) or 1)), n_playout=args.playout, multipv=args.multipv,
+                             max_len=args.max_len)
+        records = an.analyse([b for _, b in parsed])
+    except CczError as e:
+        print(f"analyse: {e}", file=sys.stderr)
+        return 1
+    out = open(args.out, "w", encoding="utf-8") if args.out else sys.stdout
+    try:
+        for (no, _), rec in zip(parsed, records):
+            out.write(json.dumps({"line": no, **rec}) + "\n")
+    finally:
+        if args.out:
+            out.close()
+    s = an.summary()
+    print(f"analysed {s['positions']} positions in {s['seconds']} s: {s['positions_per_s']} positions/s, {s['sims_per_s']} sims/s, "
+          f"{s['evaluator_rows_per_step']} evaluator rows per step", file=sys.stderr)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -194,9 +194,10 @@ class Arena:
         self.opening_of, self.a_colour, self.red_net = pair_layout(self.P)
         self.openings = make_openings(self.P, int(opening_plies), seed=seed, device=device)
         sq, turn, half = self.openings
-        for b in range(self.B):
-            i = self.opening_of[b]
-            e.set_position(b, sq[i], int(turn[i]), int(half[i]))
+        of = np.asarray(self.opening_of)
+        status = e.set_positions(np.asarray(sq)[of], np.asarray(turn)[of], np.asarray(half)[of])   # one launch (no moves: as set_position)
+        if status.any():
+            raise ValueError(f"Arena: opening positions refused by the engine (status {status.tolist()})")
         self._temps = np.full(self.B, self.temp, np.float64)
         self._versions = None
         self.moves = []                      # host int32 [B] per lockstep move (-1: no move on that board)

@@ -325,6 +325,27 @@ int ccz_set_position(ccz_engine *e, void *stream, int32_t board, const uint8_t *
     return 0;
 }
 
+int ccz_set_positions(ccz_engine *e, void *stream, const uint8_t *sq_dev, const uint8_t *turn_dev, const int32_t *halfmove_dev,
+                      const int32_t *moves_dev, const int32_t *n_moves_dev, int32_t max_moves, const uint8_t *mask_host, int32_t *status_dev)
+{
+    NEED(e);
+    if (!sq_dev || !turn_dev || !status_dev) return fail(-1, "ccz_set_positions: null squares / turn / status");
+    if (((uintptr_t)sq_dev) & 3) return fail(-1, "ccz_set_positions: the squares must be 4-byte aligned");
+    if (max_moves < 0) return fail(-1, "ccz_set_positions: negative max_moves");
+    if (n_moves_dev && !moves_dev && max_moves > 0) return fail(-1, "ccz_set_positions: n_moves without moves");
+    hipStream_t s = (hipStream_t)stream;
+    const uint8_t *mask = nullptr;
+    if (mask_host) {
+        HIP_TRY(hipMemcpyAsync(e->st_mask, mask_host, (size_t)e->d.B, hipMemcpyHostToDevice, s));
+        mask = e->st_mask;
+    }
+    hipLaunchKernelGGL(k_set_positions, dim3(e->d.B), dim3(64), 0, s, e->d, mask, sq_dev, turn_dev, halfmove_dev, moves_dev, n_moves_dev,
+                       (int)max_moves, status_dev);
+    HIP_TRY(hipGetLastError());
+    if (mask_host) HIP_TRY(hipStreamSynchronize(s)); // st_mask is reused by the next call
+    return 0;
+}
+
 int ccz_reset_tree(ccz_engine *e, void *stream, const uint8_t *mask_host)
 {
     NEED(e);
@@ -603,6 +624,19 @@ int ccz_root_children(ccz_engine *e, void *stream, int32_t *k_host, uint16_t *ac
     return 0;
 }
 
+int ccz_principal_variations(ccz_engine *e, void *stream, int32_t multipv, int32_t max_len, uint16_t *moves_dev, int32_t *len_dev,
+                             int32_t *visits_dev, float *q_dev, float *prior_dev, int32_t *root_visits_dev)
+{
+    NEED(e);
+    if (multipv < 1 || multipv > kMaxLegal) return fail(-1, "ccz_principal_variations: multipv must be 1..%d (got %d)", kMaxLegal, multipv);
+    if (max_len < 1) return fail(-1, "ccz_principal_variations: max_len must be >= 1 (got %d)", max_len);
+    if (!moves_dev || !len_dev || !visits_dev || !q_dev || !prior_dev || !root_visits_dev) return fail(-1, "ccz_principal_variations: null output");
+    hipLaunchKernelGGL(k_principal_variations, dim3(e->d.B, (unsigned)multipv), dim3(64), 0, (hipStream_t)stream, e->d, (int)ACTIVE(e), (int)multipv,
+                       (int)max_len, moves_dev, len_dev, visits_dev, q_dev, prior_dev, root_visits_dev);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 static int check_temps(const double *temps_host, int B, const char *fn)
 {
     if (temps_host)
@@ -759,7 +793,7 @@ int ccz_harvest(ccz_engine *e, void *stream, void *states_f16_dev, float *pi_dev
     // finished boards are taken in index order while their rows fit the caller's buffers; the rest stay
     // finished and are picked up by the next call (many boards can reach the ply cap in the same move)
     for (int b = 0; b < B; ++b)
-        if (e->h_meta[b].over) {
+        if (e->h_meta[b].over && e->h_meta[b].ply > 0) { // (over with no ply: a parked board, ccz_set_positions -- nothing to emit, stays parked)
             const int64_t add = (int64_t)e->h_meta[b].ply * mul;
             if (rows + add > capacity_rows) {
                 if (!any) return fail(-5, "ccz_harvest: the first finished game needs %lld rows, capacity %lld", (long long)add, (long long)capacity_rows);
@@ -799,7 +833,7 @@ int ccz_harvest_records(ccz_engine *e, void *stream, void *records_dev, int64_t 
     bool any = false;
     // as ccz_harvest: finished boards in index order while their plies fit; the rest stay finished for the next call
     for (int b = 0; b < B; ++b)
-        if (e->h_meta[b].over) {
+        if (e->h_meta[b].over && e->h_meta[b].ply > 0) { // (a parked board stays parked)
             const int64_t add = (int64_t)e->h_meta[b].ply;
             if (plies + add > capacity_plies) {
                 if (!any) return fail(-5, "ccz_harvest_records: the first finished game has %lld plies, capacity %lld", (long long)add, (long long)capacity_plies);

@@ -1218,6 +1218,38 @@ __global__ __launch_bounds__(64) void k_move_distribution(Dev D, const double *t
     sample_move(D, D.board_id_base + (uint64_t)b, m.move_counter, s_pi, s_g, k, lane, &s_choice, g, mixed, u_out + b);
 }
 
+// CCZ_RULE_PERPETUAL_CHECK: the game ends by fourfold repetition; inside the repetition window --
+// the positions after the earliest occurrence of the repeated position -- a side whose EVERY move gave check while the
+// other side's did not loses. Only outcome().winner changes (game.py:210-216): in the search the same leaf is
+// "end and is_tie" -> 0.0 either way (mcts.py:120-122), so visit counts do not depend on this flag.
+// Returns the winner (1 RED / 0 BLACK) or -1. `turn` = the side to move in the position the chain ends with, chk0 / chk1 = the
+// chain's in-check bits including that position's. Shared by k_finish_move and k_set_positions. All 64 lanes call it.
+__device__ __forceinline__ int perpetual_check_winner(uint32_t rule_flags, const LeafEval &L, int halfmove, int chain_len, uint64_t chk0,
+                                                      uint64_t chk1, int turn, int lane)
+{
+    int perpetual_winner = -1;
+    // (the host view and the reference order of checks, game.py:208-214: insufficient material, then the sixty-move rule, then the
+    // repetition -- a game that the sixty-move rule ends at the same ply is a DRAW, whatever the repetition window holds)
+    if ((rule_flags & 1u) && L.n_legal > 0 && !L.insufficient && !(halfmove >= 120) && L.rep >= 4) {
+        const int last = chain_len - 1;
+        bool miss_mover = false, miss_other = false, any_other = false; // mover = the side that just moved (turn ^ 1)
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int i = h * 64 + lane;
+            const bool in = i > L.first_occ && i <= last;
+            const bool bit = ((h ? chk1 : chk0) >> lane) & 1ull;
+            const bool by_mover = ((last - i) & 1) == 0;
+            miss_mover |= __ballot(in && by_mover && !bit) != 0ull;
+            miss_other |= __ballot(in && !by_mover && !bit) != 0ull;
+            any_other |= __ballot(in && !by_mover) != 0ull;
+        }
+        const bool mover_all = !miss_mover, other_all = any_other && !miss_other;
+        if (mover_all && !other_all) perpetual_winner = turn;          // the side that kept checking loses
+        else if (other_all && !mover_all) perpetual_winner = turn ^ 1;
+    }
+    return perpetual_winner;
+}
+
 // ------------------------------------------------------------------ K3: once per move
 __global__ __launch_bounds__(64) void k_finish_move(Dev D, const int32_t *forced, const double *temps,
                                                       int32_t *moves_out, int keep_tree)
@@ -1396,30 +1428,7 @@ __global__ __launch_bounds__(64) void k_finish_move(Dev D, const int32_t *forced
         const int ci = chain_len - 1;
         if (in_check) { if (ci < 64) chk0 |= 1ull << ci; else chk1 |= 1ull << (ci - 64); }
     }
-    // CCZ_RULE_PERPETUAL_CHECK: the game ends by fourfold repetition; inside the repetition window --
-    // the positions after the earliest occurrence of the repeated position -- a side whose EVERY move gave check while the
-    // other side's did not loses. Only outcome().winner changes (game.py:210-216): in the search the same leaf is
-    // "end and is_tie" -> 0.0 either way (mcts.py:120-122), so visit counts do not depend on this flag.
-    int perpetual_winner = -1;
-    // (the host view and the reference order of checks, game.py:208-214: insufficient material, then the sixty-move rule, then the
-    // repetition -- a game that the sixty-move rule ends at the same ply is a DRAW, whatever the repetition window holds)
-    if ((D.rule_flags & 1u) && L.n_legal > 0 && !L.insufficient && !(halfmove >= 120) && L.rep >= 4) {
-        const int last = chain_len - 1;
-        bool miss_mover = false, miss_other = false, any_other = false; // mover = the side that just moved (turn ^ 1)
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int i = h * 64 + lane;
-            const bool in = i > L.first_occ && i <= last;
-            const bool bit = ((h ? chk1 : chk0) >> lane) & 1ull;
-            const bool by_mover = ((last - i) & 1) == 0;
-            miss_mover |= __ballot(in && by_mover && !bit) != 0ull;
-            miss_other |= __ballot(in && !by_mover && !bit) != 0ull;
-            any_other |= __ballot(in && !by_mover) != 0ull;
-        }
-        const bool mover_all = !miss_mover, other_all = any_other && !miss_other;
-        if (mover_all && !other_all) perpetual_winner = turn;          // the side that kept checking loses
-        else if (other_all && !mover_all) perpetual_winner = turn ^ 1;
-    }
+    const int perpetual_winner = perpetual_check_winner(D.rule_flags, L, halfmove, chain_len, chk0, chk1, turn, lane);
     if (lane == 0) {
         D.chain_chk[(size_t)b * 2] = chk0;
         D.chain_chk[(size_t)b * 2 + 1] = chk1;
@@ -1442,6 +1451,230 @@ __global__ __launch_bounds__(64) void k_finish_move(Dev D, const int32_t *forced
         D.meta[b] = m;
         D.leaf_status[b] = CCZ_LEAF_SKIP;
     }
+}
+
+// ------------------------------------------------------------------ many positions with their move history, in one launch
+// One wave per board (ccz_set_positions): validate the position, replay the board's moves with the engine's own rules -- every
+// move must be in the legal-move set of the position it is played in (gen_legal with the engine's rank table: the generator of the
+// selection) --, keep key, turn, clock, history chain and the chain's in-check bits as k_finish_move does per ply, run
+// k_finish_move's game-end test on the position reached (only if moves were played: without moves the board is left exactly as
+// k_set_position leaves it), and finish as init_board does. status: 0 loaded, 1 + i move i is not legal where it is played, -1
+// invalid position, -2 more than kChainCap positions since the last capture. A board with a non-zero status, or with n_moves == -1,
+// is PARKED: empty mailbox, over = 1, winner = -1, ply = 0, a root without children -- the simulator skips it (m.over), the harvest
+// has nothing to emit for it. Bad input sets no sticky error bit. The replay is a chain of n dependent move generations
+// (~ n x the leaf phase of k_step); the moves are fetched 64 at a time so that no load sits between two of them.
+__global__ __launch_bounds__(64) void k_set_positions(Dev D, const uint8_t *mask, const uint8_t *sq_in, const uint8_t *turn_in,
+                                                        const int32_t *halfmove_in, const int32_t *moves, const int32_t *n_moves,
+                                                        int max_moves, int32_t *status_out)
+{
+    const int b = blockIdx.x, lane = threadIdx.x;
+    if (mask && !mask[b]) return;
+    __shared__ __align__(16) uint8_t s_sq[96];
+    __shared__ uint64_t s_chain[kChainCap];
+    __shared__ GenScratch S;
+    const int n = n_moves ? n_moves[b] : 0;
+    int turn = turn_in[b] ? 1 : 0;
+    int halfmove = halfmove_in ? halfmove_in[b] : 0;
+    const uint8_t *src = sq_in + (size_t)b * 96;
+    const int p0 = src[lane], p1 = lane < 26 ? src[64 + lane] : 0;
+    const bool park = n == -1;
+    int status = 0;
+    if (!park) {
+        // what ccz_set_position checks on the host: piece codes, one king per side, the clock; and at most 16 pieces per side
+        // (the generator's piece list), a move count inside the row
+        const bool badcode = p0 > 15 || p0 == 8 || p1 > 15 || p1 == 8;
+        const int kr = __popcll(__ballot(p0 == KING)) + __popcll(__ballot(p1 == KING));
+        const int kb = __popcll(__ballot(p0 == KING + 8)) + __popcll(__ballot(p1 == KING + 8));
+        const int nr = __popcll(__ballot(p0 >= 1 && p0 <= 7)) + __popcll(__ballot(p1 >= 1 && p1 <= 7));
+        const int nb = __popcll(__ballot(p0 >= 9 && p0 <= 15)) + __popcll(__ballot(p1 >= 9 && p1 <= 15));
+        if (__ballot(badcode) != 0ull || kr != 1 || kb != 1 || nr > 16 || nb > 16 || halfmove < 0 || n < -1 || n > max_moves) status = -1;
+    }
+    uint64_t key = 0, chk0 = 0ull, chk1 = 0ull;
+    int chain_len = 1, over = 0, winner = -1;
+    if (!park && status == 0) {
+        s_sq[lane] = (uint8_t)p0;
+        if (lane < 32) s_sq[64 + lane] = (uint8_t)p1; // (p1 == 0 for lanes 26..31: the mailbox pad)
+        if (p0) key ^= zob(p0, lane);
+        if (p1) key ^= zob(p1, 64 + lane);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) key ^= __shfl_xor(key, o);
+        if (turn) key ^= kTurnKey;
+        if (lane == 0) s_chain[0] = key;
+        wave_sync();
+        const int32_t *row = moves + (size_t)b * (size_t)max_moves;
+        int mvreg = -1;
+        for (int i = 0; i < n; ++i) {
+            if ((i & 63) == 0) mvreg = i + lane < n ? row[i + lane] : -1;
+            const int mv = __builtin_amdgcn_readlane(mvreg, __builtin_amdgcn_readfirstlane(i & 63));
+            const GenResult g = gen_legal(s_sq, turn, S, nullptr, lane, nullptr, D.rank, D.unrank, D.trankpack);
+            if (g.overflow) { status = -1; break; }
+            if (i > 0) { // the move before gave check: one bit per chain position, as k_finish_move keeps them
+                const bool in_check = g.ksq >= 0 && king_attacked(s_sq, S, g.ksq, -1, -1, 0, turn);
+                const int ci = chain_len - 1;
+                if (in_check) { if (ci < 64) chk0 |= 1ull << ci; else chk1 |= 1ull << (ci - 64); }
+            }
+            bool legal = (unsigned)mv < (unsigned)kNMoves;
+            if (legal) {
+                const int bit = D.rank ? (int)D.rank[mv] : mv; // bit r of the mask = the move of rank r (gen_legal)
+                legal = ((S.mask[bit >> 5] >> (bit & 31)) & 1u) != 0u;
+            }
+            if (!legal) { status = 1 + i; break; }
+            // board.push(move) and its history: k_finish_move's, without the tree
+            const int from = c_tab.from[mv], to = c_tab.to[mv];
+            const int pc = s_sq[from], cap = s_sq[to];
+            wave_sync();
+            if (lane == 0) { s_sq[to] = (uint8_t)pc; s_sq[from] = 0; }
+            key ^= zob(pc, from) ^ zob(pc, to) ^ kTurnKey;
+            if (cap) key ^= zob(cap, to);
+            const bool zeroing = cap || ((D.rule_flags & 2u) && (pc & 7) == PAWN); // CCZ_RULE_PAWN_MOVE_RESETS_CLOCK
+            halfmove = zeroing ? 0 : halfmove + 1;
+            if (zeroing) { chain_len = 0; chk0 = 0ull; chk1 = 0ull; }
+            if (chain_len >= kChainCap) { status = -2; break; }
+            if (lane == 0) s_chain[chain_len] = key;
+            ++chain_len;
+            turn ^= 1;
+            wave_sync();
+        }
+        if (status == 0 && n > 0) {
+            // game end (game.py:208-219) of the position reached, as after k_finish_move's push
+            bool overflow;
+            const LeafEval L = eval_position(s_sq, turn, halfmove, key, s_chain, chain_len, S, nullptr, lane, overflow);
+            if (overflow) status = -1;
+            const bool in_check = L.ksq >= 0 && king_attacked(s_sq, S, L.ksq, -1, -1, 0, turn);
+            const int ci = chain_len - 1;
+            if (in_check) { if (ci < 64) chk0 |= 1ull << ci; else chk1 |= 1ull << (ci - 64); }
+            const int pw = perpetual_check_winner(D.rule_flags, L, halfmove, chain_len, chk0, chk1, turn, lane);
+            if (L.status != CCZ_LEAF_EXPAND) {
+                over = 1;
+                winner = L.n_legal == 0 ? (turn ^ 1) : pw; // no legal move: side to move loses
+            }
+        }
+        wave_sync();
+    }
+    const bool parked = park || status != 0;
+    if (parked) { key = 0; chain_len = 1; chk0 = 0ull; chk1 = 0ull; over = 1; winner = -1; turn = 1; halfmove = 0; }
+    if (lane < 24) ((uint32_t *)(D.root_sq + (size_t)b * 96))[lane] = parked ? 0u : ((const uint32_t *)s_sq)[lane];
+    uint64_t *chain = D.chain + (size_t)b * kChainCap;
+    if (parked) { if (lane == 0) chain[0] = 0ull; }
+    else for (int i = lane; i < chain_len; i += 64) chain[i] = s_chain[i];
+    if (lane == 0) {
+        BoardMeta m = D.meta[b];
+        m.key = key;
+        m.halfmove = halfmove;
+        m.chain_len = chain_len;
+        m.ply = 0;
+        m.n_nodes = 1;
+        m.turn = (uint8_t)turn;
+        m.over = (uint8_t)over;
+        m.winner = (int8_t)winner;
+        m.pi_used = 0;
+        m.game_no += 1;
+        m.half = (uint8_t)*D.half;
+        D.meta[b] = m;
+        D.chain_chk[(size_t)b * 2] = chk0;
+        D.chain_chk[(size_t)b * 2 + 1] = chk1;
+        fresh_root(D, b, m.half);
+        status_out[b] = status;
+    }
+}
+
+// ------------------------------------------------------------------ principal variations: the tree below the root
+// One wave per (board, line) (ccz_principal_variations). Line r starts at the root child of rank r -- by visits, descending, ties
+// to the lower child index, so rank 0 is the first maximum: the arg-max move (mcts.py:225-229) -- and follows the first child of
+// maximal N while that N is > 0. Per level every lane loads its share of the <= 128 children (NodeA + move word) in one round,
+// the first maximum is the selection's idiom (wave max on the DPP network, ballot, lowest index), and the winner's record is
+// broadcast from its lane. Like the descent of k_step this is a chain of dependent loads, one round trip per level: latency-bound,
+// microseconds per line, no bandwidth to speak of. Boards that are over or scout slots (b >= active) get zero lines.
+struct PvCand {
+    int32_t N, fc, idx;
+    float Q, P;
+    uint32_t w;
+};
+
+__device__ __forceinline__ PvCand pv_bcast(const PvCand &c, int owner)
+{
+    PvCand o;
+    o.N = __builtin_amdgcn_readlane(c.N, owner);
+    o.fc = __builtin_amdgcn_readlane(c.fc, owner);
+    o.idx = __builtin_amdgcn_readlane(c.idx, owner);
+    o.Q = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(c.Q), owner));
+    o.P = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(c.P), owner));
+    o.w = (uint32_t)__builtin_amdgcn_readlane((int)c.w, owner);
+    return o;
+}
+
+__global__ __launch_bounds__(64) void k_principal_variations(Dev D, int active, int multipv, int max_len, uint16_t *moves_out,
+                                                               int32_t *len_out, int32_t *visits_out, float *q_out, float *prior_out,
+                                                               int32_t *root_visits)
+{
+    const int b = blockIdx.x, r = blockIdx.y, lane = threadIdx.x;
+    const size_t line = (size_t)b * (size_t)multipv + (size_t)r;
+    uint16_t *mv_o = moves_out + line * (size_t)max_len;
+    int32_t *n_o = visits_out + line * (size_t)max_len;
+    const BoardMeta m = D.meta[b];
+    const size_t base = ((size_t)b * 2 + *D.half) * (size_t)D.cap;
+    const NodeA *A = D.nodeA + base;
+    const uint32_t *Bn = D.nodeB + base;
+    const NodeA root = A[0];
+    const bool live = b < active && !m.over;
+    if (r == 0 && lane == 0) root_visits[b] = live ? root.N : 0;
+    int len = 0;
+    float q1 = 0.0f, p1 = 0.0f;
+    int fc = root.fc, nc = (int)(Bn[0] >> 16);
+    while (live && len < max_len) {
+        if (nc > kMaxLegal) nc = kMaxLegal;
+        if (nc <= 0 || fc < 0 || fc + nc > D.cap) break; // unexpanded node (or a record no tree of this engine holds: nothing is read)
+        // every lane's share of the children: i = lane and 64 + lane
+        PvCand c0 = PvCand{-1, -1, lane, 0.0f, 0.0f, 0u}, c1 = PvCand{-1, -1, 64 + lane, 0.0f, 0.0f, 0u};
+        if (lane < nc) {
+            const NodeA c = A[CCZ_IDX(D, fc + lane, D.cap)];
+            c0.N = c.N; c0.fc = c.fc; c0.Q = c.Q; c0.P = c.P;
+            c0.w = Bn[CCZ_IDX(D, fc + lane, D.cap)];
+        }
+        if (64 + lane < nc) {
+            const NodeA c = A[CCZ_IDX(D, fc + 64 + lane, D.cap)];
+            c1.N = c.N; c1.fc = c.fc; c1.Q = c.Q; c1.P = c.P;
+            c1.w = Bn[CCZ_IDX(D, fc + 64 + lane, D.cap)];
+        }
+        PvCand mine;
+        bool hit;
+        if (len == 0 && r > 0) {
+            // the root child of rank r: a child's rank = the children with more visits + the earlier ones with as many
+            int rk0 = 0, rk1 = 0;
+            for (int j = 0; j < nc; ++j) {
+                const int js = __builtin_amdgcn_readfirstlane(j & 63);
+                const int nj = j < 64 ? __builtin_amdgcn_readlane(c0.N, js) : __builtin_amdgcn_readlane(c1.N, js);
+                rk0 += (nj > c0.N || (nj == c0.N && j < lane)) ? 1 : 0;
+                rk1 += (nj > c1.N || (nj == c1.N && j < 64 + lane)) ? 1 : 0;
+            }
+            const bool s1 = 64 + lane < nc && rk1 == r;
+            mine = s1 ? c1 : c0;
+            hit = (s1 || (lane < nc && rk0 == r)) && mine.N > 0;
+        } else {
+            // first maximum of N (a lane's own best is its lower index unless the upper one is larger), N > 0
+            mine = c1.N > c0.N ? c1 : c0;
+            const double top = wave_max_f64((double)mine.N);
+            hit = top > 0.0 && (double)mine.N == top && mine.idx < nc;
+        }
+        const uint64_t h0 = __ballot(hit && mine.idx < 64), h1 = __ballot(hit);
+        if (h1 == 0ull) break; // no visited child (or fewer than r + 1 visited root children)
+        const int owner = __builtin_amdgcn_readfirstlane((h0 ? __ffsll((long long)h0) : __ffsll((long long)h1)) - 1);
+        const PvCand ch = pv_bcast(mine, owner);
+        if (lane == 0) {
+            mv_o[len] = (uint16_t)(ch.w & 0xffffu);
+            n_o[len] = ch.N;
+        }
+        if (len == 0) { q1 = ch.Q; p1 = ch.P; }
+        ++len;
+        fc = ch.fc;
+        nc = (int)(ch.w >> 16);
+    }
+    if (lane == 0) {
+        len_out[line] = len;
+        q_out[line] = q1;
+        prior_out[line] = p1;
+    }
+    for (int j = len + lane; j < max_len; j += 64) { mv_o[j] = 0; n_o[j] = 0; }
 }
 
 // ------------------------------------------------------------------ harvest: finished games -> training rows

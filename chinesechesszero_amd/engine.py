@@ -133,6 +133,52 @@ class SelfPlayEngine:
         assert sq.shape == (90,)
         check(self.L.ccz_set_position(self.h, self._stream(), int(board), _ptr(sq), int(turn), int(halfmove)))
 
+    def set_positions(self, squares, turn, halfmove=None, moves=None, park=None, mask=None) -> np.ndarray:
+        """Load all boards in ONE launch, each with the moves that led to its position (``ccz_set_positions``: validated and
+        replayed on the device with the engine's own rules; history chain, clocks and game end as after as many
+        :meth:`finish_move` calls). ``squares`` uint8 [B,90] (or [B,96]), ``turn`` [B] (1 red), ``halfmove`` [B] or None,
+        ``moves``: a list of B move-id lists or a padded int array [B,M] whose unused entries are negative, ``park`` [B]: boards
+        to park (no game: the simulator skips them), ``mask`` [B]: boards to touch (None = all). Returns the status int32 [B]:
+        0 loaded (or parked on request), 1 + i move i is illegal where it is played, -1 invalid position, -2 history chain
+        overflow; a board with a non-zero status is parked. Syncs once, for the status."""
+        B = self.B
+        sq = np.asarray(squares, dtype=np.uint8)
+        if sq.ndim != 2 or sq.shape[0] != B or sq.shape[1] not in (90, SQ_STRIDE):
+            raise ValueError(f"squares must be [{B},90]")
+        sq96 = np.zeros((B, SQ_STRIDE), np.uint8)
+        sq96[:, :90] = sq[:, :90]
+        tn = np.array(np.broadcast_to(np.asarray(turn), (B,)), dtype=np.uint8)          # (a copy: broadcasts are read-only)
+        n = np.zeros(B, np.int32)
+        mv = None
+        if moves is not None:
+            if isinstance(moves, np.ndarray) and moves.ndim == 2:
+                if moves.shape[0] != B:
+                    raise ValueError(f"moves must have {B} rows")
+                mv = np.ascontiguousarray(moves, dtype=np.int32)
+                n = (mv >= 0).sum(axis=1).astype(np.int32)
+                if ((mv >= 0) != (np.arange(mv.shape[1])[None, :] < n[:, None])).any():
+                    raise ValueError("moves: the unused (negative) entries of a padded row must follow its moves")
+            else:
+                if len(moves) != B:
+                    raise ValueError(f"moves must have {B} rows")
+                n = np.array([len(r) for r in moves], np.int32)
+                mv = np.full((B, max(1, int(n.max()) if B else 1)), -1, np.int32)
+                for b, r in enumerate(moves):
+                    mv[b, :len(r)] = np.asarray(r, np.int32)
+        if park is not None:
+            n = np.where(np.asarray(park, bool), np.int32(-1), n).astype(np.int32)
+        dev = self.device
+        d_sq = torch.from_numpy(sq96).to(dev)
+        d_turn = torch.from_numpy(tn).to(dev)
+        d_half = None if halfmove is None else torch.from_numpy(np.array(np.broadcast_to(np.asarray(halfmove), (B,)), dtype=np.int32)).to(dev)
+        d_mv = None if mv is None else torch.from_numpy(mv).to(dev)
+        d_n = None if (mv is None and park is None) else torch.from_numpy(n).to(dev)
+        status = torch.zeros((B,), dtype=torch.int32, device=dev)
+        m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
+        check(self.L.ccz_set_positions(self.h, self._stream(), _ptr(d_sq), _ptr(d_turn), _ptr(d_half), _ptr(d_mv), _ptr(d_n),
+                                       0 if mv is None else int(mv.shape[1]), _ptr(m), _ptr(status)))
+        return status.cpu().numpy()
+
     # ------------------------------------------------------------------ one simulation
     def select_leaves(self) -> torch.Tensor:
         """PUCT descent + leaf rules + evaluator input for all boards; returns [B,17,7,10,9] fp16."""
@@ -343,6 +389,30 @@ class SelfPlayEngine:
         rn = np.zeros(B, np.int32)
         check(self.L.ccz_root_children(self.h, self._stream(), _ptr(k), _ptr(acts), _ptr(visits), _ptr(q), _ptr(p), _ptr(rn)))
         return {"k": k, "acts": acts, "visits": visits, "q": q, "prior": p, "root_visits": rn}
+
+    def principal_variations(self, multipv: int = 1, max_len: int = 32) -> dict:
+        """The best lines of every live tree (``ccz_principal_variations``). Line r starts at the root child of rank r by visits
+        (ties to the lower child index: line 0 starts with the arg-max move) and follows the first most-visited child while it
+        has visits. Returns numpy arrays: ``moves`` uint16 [B,multipv,max_len], ``len`` int32 [B,multipv] (0: unused line),
+        ``visits`` int32 [B,multipv,max_len] (N of every node on the line), ``q`` / ``prior`` float32 [B,multipv] (the first
+        move's stored Q -- root side to move's view -- and P), ``root_visits`` int32 [B]. Boards that are over and scout slots
+        have no lines. Syncs once, like :meth:`root_children`."""
+        B, K, M = self.B, int(multipv), int(max_len)
+        if not 1 <= K <= MAX_LEGAL or M < 1:
+            raise ValueError(f"multipv must be 1..{MAX_LEGAL} and max_len >= 1")
+        dev = self.device
+        out = {"moves": torch.empty((B, K, M), dtype=torch.int16, device=dev), "len": torch.empty((B, K), dtype=torch.int32, device=dev),
+               "visits": torch.empty((B, K, M), dtype=torch.int32, device=dev), "q": torch.empty((B, K), dtype=torch.float32, device=dev),
+               "prior": torch.empty((B, K), dtype=torch.float32, device=dev), "root_visits": torch.empty((B,), dtype=torch.int32, device=dev)}
+        check(self.L.ccz_principal_variations(self.h, self._stream(), K, M, _ptr(out["moves"]), _ptr(out["len"]), _ptr(out["visits"]),
+                                              _ptr(out["q"]), _ptr(out["prior"]), _ptr(out["root_visits"])))
+        host = {k: torch.empty(v.shape, dtype=v.dtype).pin_memory() for k, v in out.items()}
+        for k, v in out.items():
+            host[k].copy_(v, non_blocking=True)
+        torch.cuda.current_stream(dev).synchronize()
+        res = {k: v.numpy().copy() for k, v in host.items()}
+        res["moves"] = res["moves"].view(np.uint16)
+        return res
 
     def root_pi(self, temps=None) -> np.ndarray:
         pi = np.zeros((self.B, MAX_LEGAL), np.float64)

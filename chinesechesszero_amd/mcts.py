@@ -243,8 +243,8 @@ class MCTS:
 class MCTS_AI:
     """reference mcts.py:181-233"""
 
-    def __init__(self, policy_value_fn, c_puct=5, n_playout=2000, is_selfplay=False, device: int = 0, seed: int = 0):
-        self.mcts = MCTS(policy_value_fn, c_puct, n_playout, device=device, seed=seed)
+    def __init__(self, policy_value_fn, c_puct=5, n_playout=2000, is_selfplay=False, device: int = 0, seed: int = 0, scouts: int | None = None):
+        self.mcts = MCTS(policy_value_fn, c_puct, n_playout, device=device, seed=seed, scouts=scouts)
         self.is_selfplay = is_selfplay
         self.agent = "AI"
 

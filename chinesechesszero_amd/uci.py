@@ -3,7 +3,9 @@
 The reference's README (README.md:3) advertises "standard UCI protocol" but ships no loop; what it does
 use everywhere are UCI coordinate strings ("a0a1", tools.py:172-269). This is that missing loop:
 ``uci``, ``isready``, ``ucinewgame``, ``position startpos|fen <fen> [moves ...]``, ``go [nodes N]``,
-``d``, ``quit``. The search is ``MCTS_AI`` on the HIP engine (no CPU fallback).
+``setoption name Playouts|MultiPV value N``, ``d``, ``quit``. ``go`` reports one ``info depth .. multipv .. score cp .. nodes .. pv ..``
+line per principal variation (``SelfPlayEngine.principal_variations``); ``cp`` is a display mapping of the first move's Q
+(``analyse.cp_of``). The search is ``MCTS_AI`` on the HIP engine (no CPU fallback).
 """
 from __future__ import annotations
 
@@ -42,8 +44,9 @@ def board_from_fen(fen: str) -> Board:
     return Board(sq, turn, halfmove)
 
 
-def parse_position(tokens: list[str]) -> Board:
-    """tokens after 'position'."""
+def parse_position(tokens: list[str], validate: bool = True) -> Board:
+    """tokens after 'position'. ``validate=False`` pushes the moves without asking the rules (no GPU call per move): the batched
+    analysis lets the device check them where they are played (``SelfPlayEngine.set_positions``)."""
     if not tokens:
         raise ValueError("position needs startpos or fen")
     if tokens[0] == "startpos":
@@ -58,7 +61,7 @@ def parse_position(tokens: list[str]) -> Board:
     if rest and rest[0] == "moves":
         for u in rest[1:]:
             m = Move.from_uci(u)
-            if m.id not in board.legal_ids():
+            if validate and m.id not in board.legal_ids():
                 raise ValueError(f"illegal move {u}")
             board.push(m)
     return board
@@ -72,6 +75,7 @@ class UciLoop:
         self.out = out
         self.board = None
         self.ai = None
+        self.multipv = 1
 
     def _say(self, s: str):
         print(s, file=self.out, flush=True)
@@ -85,6 +89,18 @@ class UciLoop:
             self.ai = MCTS_AI(self.policy_value_fn, c_puct=C_PUCT, n_playout=nodes, is_selfplay=False, device=self.device)
         return self.ai
 
+    def _say_pvs(self, ai):
+        """One ``info depth <len> multipv <i> score cp <cp> nodes <root visits> pv <m1 m2 ...>`` line per principal variation of the
+        search just finished (the tree is still on the engine: ``get_action`` only marks it for discarding)."""
+        from .analyse import cp_of
+        pv = ai.mcts._engine.principal_variations(multipv=self.multipv, max_len=32)
+        for r in range(self.multipv):
+            ln = int(pv["len"][0, r])
+            if ln:
+                line = " ".join(Move.from_id(int(i)).uci() for i in pv["moves"][0, r, :ln])
+                self._say(f"info depth {ln} multipv {r + 1} score cp {cp_of(pv['q'][0, r], pv['visits'][0, r, 0])} "
+                          f"nodes {int(pv['root_visits'][0])} pv {line}")
+
     def handle(self, line: str) -> bool:
         """Process one command line; returns False on quit."""
         tok = line.split()
@@ -95,11 +111,14 @@ class UciLoop:
             self._say(f"id name {ENGINE_NAME}")
             self._say("id author cczero-mi355x builders")
             self._say(f"option name Playouts type spin default {self.n_playout} min 1 max 1000000")
+            self._say("option name MultiPV type spin default 1 min 1 max 128")
             self._say("uciok")
         elif cmd == "isready":
             self._say("readyok")
         elif cmd == "setoption" and len(tok) >= 5 and tok[1] == "name" and tok[2].lower() == "playouts":
             self.n_playout = int(tok[4])
+        elif cmd == "setoption" and len(tok) >= 5 and tok[1] == "name" and tok[2].lower() == "multipv":
+            self.multipv = max(1, min(128, int(tok[4])))
         elif cmd == "ucinewgame":
             self.board = Board()
             self.ai = None
@@ -119,6 +138,7 @@ class UciLoop:
                 return True
             ai = self._player(nodes)
             move, probs = ai.get_action(self.board, temp=1e-3, return_prob=True)
+            self._say_pvs(ai)
             rc = ai.mcts.root_children()
             self._say(f"info nodes {int(rc['root_visits'])} string visits {int(rc['visits'].max())}/{int(rc['visits'].sum())}")
             self._say(f"bestmove {Move.from_id(move).uci()}")

@@ -195,6 +195,28 @@ int ccz_reset(ccz_engine *e, void *stream, const uint8_t *mask_host);
  * match play. sq_host: 90 piece codes. */
 int ccz_set_position(ccz_engine *e, void *stream, int32_t board, const uint8_t *sq_host,
                      int32_t turn, int32_t halfmove);
+/* Load MANY boards, each with the moves that led to its position, in one launch (one wave per board) -- and with no host
+ * sync when mask_host == NULL. All arrays are in device memory: sq_dev uint8 [B*96] (90 piece codes per board, 4-byte aligned),
+ * turn_dev uint8 [B], halfmove_dev int32 [B] (NULL: 0), moves_dev int32 [B*max_moves] (move ids, applied to the given position in
+ * order), n_moves_dev int32 [B] (NULL: no moves), status_dev int32 [B] (output). mask_host as in ccz_reset.
+ * For every masked board the kernel validates the position (piece codes, exactly one king and at most 16 pieces per side, clock
+ * >= 0), replays the moves with the engine's own rules -- every move must be in the legal-move set of the position it is played
+ * in: the generator and rule tables (move_rank_host, type_rank, rule_flags) of the selection --, keeping key, turn, clock, history
+ * chain and in-check bits exactly as ccz_finish_move does per ply (CCZ_RULE_PAWN_MOVE_RESETS_CLOCK and the chain restart on
+ * captures included), and, if moves were played, runs ccz_finish_move's game-end test on the position reached (the positions on
+ * the way are not tested). It finishes as a new game does: fresh root, empty record, ply 0, game number + 1, no pending leaf.
+ * With no moves the board is left field for field as ccz_set_position leaves it. ccz_stats.moves / .games are not touched.
+ *   status: 0 loaded; 1 + i: move i is not legal where it is played; -1: invalid position (also: a move count outside
+ *   -1 .. max_moves); -2: more than 128 positions since the last capture (the history chain).
+ * Bad input is the caller's mistake, not an engine fault: no sticky error bit is set, the board is PARKED. So is, on request, a
+ * board whose n_moves entry is -1 (status 0). A parked board is over = 1, winner = -1, ply = 0, an empty mailbox and a root without
+ * children: the simulator skips it (CCZ_LEAF_NONE: no evaluator row), ccz_harvest_rows counts nothing for it, ccz_harvest and
+ * ccz_harvest_records emit nothing for it and leave it alone; it stays parked until ccz_reset, ccz_set_position or
+ * ccz_set_positions loads it. (The harvest calls skip every finished board without a recorded ply: a loaded position that is
+ * already decided is such a board as well.) */
+int ccz_set_positions(ccz_engine *e, void *stream, const uint8_t *sq_dev, const uint8_t *turn_dev, const int32_t *halfmove_dev,
+                      const int32_t *moves_dev, const int32_t *n_moves_dev, int32_t max_moves, const uint8_t *mask_host,
+                      int32_t *status_dev);
 /* fresh root `Node(None, 1.0)` on the boards whose mask byte is non-zero (NULL = all), keeping position,
  * history chain, game record and clocks: MCTS.update_with_move(-1) (mcts.py:176-178, what reset_player() and
  * the non-self-play branch of get_action call, mcts.py:200-201,228-229). The pending leaf is dropped. */
@@ -329,6 +351,17 @@ int ccz_finish_move(ccz_engine *e, void *stream, const int32_t *forced_moves_dev
  * (may be NULL). What mcts.py:162-163 reads. */
 int ccz_root_children(ccz_engine *e, void *stream, int32_t *k_host, uint16_t *acts_host,
                       int32_t *visits_host, float *q_host, float *prior_host, int32_t *root_visits_host);
+/* The best lines of every live tree: asynchronous on the stream, device outputs only (one wave per board and line). Line r
+ * (0 <= r < multipv, multipv 1..128) of board b starts at the root child of rank r -- by visits, descending, ties to the lower
+ * child index: rank 0 is the first maximum, the move an arg-max player chooses (mcts.py:225-229); children with N = 0 start no
+ * line -- and follows the first child of maximal N with N > 0 until an unexpanded node, a node without a visited child or max_len
+ * (>= 1) moves. Outputs: moves_dev uint16 [B][multipv][max_len] move ids, len_dev int32 [B][multipv] (0: unused line),
+ * visits_dev int32 [B][multipv][max_len] N of every node on the line, q_dev / prior_dev float32 [B][multipv] the first move's Q and
+ * P as stored (Q from the view of the side that played the move: the root's side to move), root_visits_dev int32 [B]. Entries
+ * past a line's length are 0. Boards that are over, and scout slots (ccz_set_scouts), get zero lines and root visits 0.
+ * A chain of dependent loads, one round per level, like the descent of ccz_step: latency-bound. */
+int ccz_principal_variations(ccz_engine *e, void *stream, int32_t multipv, int32_t max_len, uint16_t *moves_dev, int32_t *len_dev,
+                             int32_t *visits_dev, float *q_dev, float *prior_dev, int32_t *root_visits_dev);
 /* pi of the root at temperature temps_host[b] (float64 [B], or NULL for the schedule; entries must be > 0) without
  * moving: pi_host float64 [B*128] aligned with ccz_root_children's acts (syncs). */
 int ccz_root_pi(ccz_engine *e, void *stream, const double *temps_host, double *pi_host);
