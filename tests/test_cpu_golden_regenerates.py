@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 GENERATORS = {"make_golden.py": ("action_table.txt", "reference_search.npz", "reference_search.json"),
               "make_golden_net.py": ("reference_net.npz", "reference_net.json"),
-              "make_golden_game.py": ("reference_game.npz", "reference_game.json")}
+              "make_golden_game.py": ("reference_game.npz", "reference_game.json", "reference_rows.npz", "reference_rows.json")}
 
 
 @pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="the reference tree is mounted in the build container only")

@@ -101,12 +101,14 @@ def test_device_harvest_reproduces_the_reference_tuples(ref_game, quirks):
         assert all(np.array_equal(s, d["processed_state"]) for s in states[:T])
         assert all(np.array_equal(s, d["flipped_state"]) for s in states[T:])
     else:
-        for t in (0, 1, 9, T - 1):
+        # every ply and every mirror row against the histories the reference computed itself for this game (game 0 of
+        # tests/golden/reference_rows.npz: its update_states_history, snapshotted ply by ply) -- not four plies and two slots
+        import reference_rows as R
+        assert np.array_equal(R.game_arrays(0)["moves"], d["moves"])
+        R.compare_rows((states, pi, z), R.expected_rows(0), pi_atol=1e-6, label="dense harvest of the 72-ply game")
+        for t in range(T):
             (red, black), turn = positions[t]
             assert np.array_equal(states[t][0], red) and np.array_equal(states[t][8], black) and np.all(states[t][16] == (1 if turn else 0))
-            back = max(0, t - 3)
-            assert np.array_equal(states[t][3], positions[back][0][0]) and np.array_equal(states[t][11], positions[back][0][1])
-            assert np.array_equal(states[T + t], states[t][:, :, :, ::-1])
         # the LAST sample's history is what the reference aliases into every sample; its turn plane differs (collect.py:78 quirk)
         assert np.array_equal(states[T - 1][:16], d["processed_state"][:16])
     e.check_healthy()
