@@ -1010,12 +1010,13 @@ int ccz_bias_act_f16(void *stream, void *y_dev, const void *bias_dev, const void
     return 0;
 }
 
+static_assert(((int64_t)INT32_MAX / kCvC) * kCvC * 2 <= (int64_t)UINT32_MAX, "the largest accepted activation tensor must fit 32-bit byte offsets / num_records");
 constexpr int64_t kSmallMaxPixels = 64 * 90; // up to 64 boards (profiles/r03_single_board.json: crossover with the tile kernel)
 
 static int conv3x3_launch(const char *who, void *stream, const void *x_dev, const void *w_dev, const void *bias_f32_dev, const void *residual_dev, void *y_dev,
                           int64_t n_pixels, int32_t relu, int cin, const int32_t *live_rows_dev = nullptr, int32_t row0 = 0)
 {
-    if (!x_dev || !w_dev || !bias_f32_dev || !y_dev || n_pixels < 0 || n_pixels % 90 || n_pixels > (int64_t)INT32_MAX / kCvC) /* 32-bit element offsets in the kernel */
+    if (!x_dev || !w_dev || !bias_f32_dev || !y_dev || n_pixels < 0 || n_pixels % 90 || n_pixels > (int64_t)INT32_MAX / kCvC) /* 32-bit BYTE offsets and a 32-bit num_records in the kernels: n_pixels * kCvC * 2 < 2^32, see the static_assert below */
         return fail(-1, "%s: bad arguments (n_pixels must be boards * 90, at most 93206 boards per call)", who);
     if ((((uintptr_t)x_dev) | ((uintptr_t)w_dev) | ((uintptr_t)bias_f32_dev) | ((uintptr_t)residual_dev) | ((uintptr_t)y_dev)) & 15)
         return fail(-1, "%s: pointers must be 16-byte aligned", who);

@@ -85,6 +85,18 @@ __device__ __forceinline__ void cv_glds16(const void *src, unsigned char *lds_wa
     __builtin_amdgcn_global_load_lds((cv_glb_ptr)src, (cv_lds_ptr)lds_wave_base, 16, 0, 0);
 }
 
+// The same DMA through a raw buffer descriptor over [base, base + bytes) (buffer_load_dwordx4 ... offen lds): a load whose range check
+// fails is still issued and still counted by vmcnt, but fetches nothing (its LDS destination receives zeros). The group-of-16 kernels
+// pass bytes = 0 for the loads whose data nobody reads -- the prefetches past the last chunk that keep their vmcnt counts static -- and
+// the tensor's real size otherwise. `voff` is this lane's byte offset (what the range check sees), `soff` a wave-uniform byte offset
+// added BEHIND the check: a live load is therefore not bounded by `bytes` (voff + soff is inside the tensor by construction, as it was
+// with cv_glds16); the check is used to switch loads off, nothing else. base, bytes and soff stay in SGPRs, the select costs no VALU.
+__device__ __forceinline__ void cv_blds16(const void *base, unsigned bytes, unsigned voff, unsigned soff, unsigned char *lds_wave_base)
+{
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(__builtin_amdgcn_make_buffer_rsrc((void *)base, 0, (int)bytes, 0x00020000), (cv_lds_ptr)lds_wave_base,
+                                             16, (int)voff, (int)soff, 0, 0);
+}
+
 // the activation-slab DMA of the next chunk is spread over half-steps 2, 4, 6, 8, 10 of the current one
 __host__ __device__ constexpr int cv_act_pass(int u) { return (u >= 2 && u <= 10 && !(u & 1)) ? (u - 2) / 2 : -1; }
 // DMA loads younger than the half-tile the NEXT half-step reads (issue order per half-step: slab piece, 2 weight loads):

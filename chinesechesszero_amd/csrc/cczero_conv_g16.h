@@ -29,6 +29,16 @@
 //     are refilled once per dy, IN PLACE, during the dx = +1 tap (b[N] is dead as soon as cell N - 1 has issued its MFMAs there):
 //     27 fragment reads per chunk and wave instead of 78, one register set. The order is pinned (one scheduling region per
 //     cell): left to the scheduler the refills move up and the kernel spills.
+//   * the DMA goes through two buffer descriptors built in the kernel -- the launch part's activation rows, this layer's packed
+//     weights -- as buffer_load_dwordx4 ... offen lds (cv_blds16): per-lane byte offset in one VGPR, everything wave-uniform (chunk,
+//     tap, half-tile) in the scalar offset, no VALU add in the loop. The counted waits need every half-step to issue the same loads
+//     in every chunk, so past the last chunk the loop still issues the next chunk's slab pieces and the weight half-tiles three
+//     ahead -- but against a descriptor of ZERO records (a scalar select of the num_records word): the range check fails, vmcnt
+//     counts the load, nothing is fetched, zeros land in LDS that nobody reads. The same for staging pass 4 of waves 4-7 (2,304
+//     pieces over 512 threads: pass 4 has work for half of them; their zeros go to the wave's dump area). Before, those loads
+//     wrapped around to chunk 0 and re-read valid memory: 40 KB of slab + 48 KB of weights per tile and 4 KB per chunk, 120 KB
+//     on top of the 1,440 KB a middle tile needs (8.3 %; an edge-pair tile 11 %; a stem tile more than its useful stream), and
+//     the epilogue waited for them to land. Measured: profiles/r08_tile_stream_ab.json, CHANGELOG.
 //   * XCD-aware tile order: workgroup b runs on XCD b % 8 and the five tiles of a group read each other's ranks as halo, so XCD x
 //     takes the x-th contiguous eighth of the tiles (HBM traffic per launch 398 MB -> 283-288 MB = algorithmic).
 //
@@ -62,13 +72,16 @@ static_assert(kG5Rows * kG5ERow <= kG5Dump, "epilogue image must fit the operand
 
 struct G5Ctx {
     unsigned char *lds;
-    const _Float16 *X, *W;   // uniform bases: every DMA is base (scalar) + 32-bit element offset (one VGPR)
-    unsigned xoff[5];        // per staging pass: this thread's 16-byte source in X (chunk 0), row clamped into the tensor
-    unsigned woff;           // this thread's 16-byte weight source in W (row pass 0, tap 0, chunk 0)
+    const _Float16 *X, *W;   // uniform bases of the two buffer descriptors: every DMA is descriptor + 32-bit byte offset (one VGPR) + scalar offset
+    unsigned xbytes, wbytes; // SCALAR: bytes of the launch part's activation rows / of this layer's packed weights (the descriptors' num_records)
+    unsigned xbytes4;        // SCALAR: xbytes for waves 0-3, 0 for waves 4-7 -- staging pass 4 has 256 pieces, theirs fetch nothing
+    unsigned xoff[5];        // per staging pass: byte offset of this thread's 16-byte source in X (chunk 0), row clamped into the tensor
+    unsigned woff;           // byte offset of this thread's 16-byte weight source in W (row pass 0, tap 0, chunk 0)
     int zo[2], zd[2];        // SCALAR: where this wave's two zero stores go for slab 0, and the step to slab 1 (0 for the dump area)
     int wave_dst;            // w * 1024
     int lane16;              // (lane & 63) * 16
-    int wave_dst4;           // LDS offset of this wave's piece in staging pass 4 (waves 4-7 repeat their pass-3 piece)
+    int wave_dst4, wave_step4; // SCALAR: LDS offset of this wave's piece of staging pass 4 in slab 0 and the step to slab 1 (waves 4-7: their
+                             // 1 KB of the dump area, step 0 -- the zeros of their out-of-range loads land where nothing is read)
     int a_off;               // weight fragment offset inside a ring slot (tile 0; tile i: + 1024 i)
     int vb[2];               // this lane's pixel-fragment base in slab 0 / 1 (cell 0 of the wave's rank at tap offset 0 = + 9 * 1024)
     int cin, cmask;          // input channels; number of 32-channel chunks - 1
@@ -77,7 +90,15 @@ struct G5Ctx {
 __host__ __device__ constexpr bool g5_slab_tap(int t) { return t >= 1 && t <= 5; }
 // DMA loads younger than the weight half-tile the NEXT half-step reads (issue order per half-step: slab piece, 2 weight loads)
 constexpr int kG5Split = 7; // cells in front of the barrier (3 / 5 / 7 and the weight DMA behind the barrier: 344-351 us, noise)
-__host__ __device__ constexpr int g5_vmcnt(int t) { return 4 + (g5_slab_tap(t) ? 1 : 0) + (g5_slab_tap(t - 1) ? 1 : 0); }
+// DMA loads a thread issues in half-step t, past the last chunk as well (g5_step: its slab piece `if constexpr (g5_dma(T) > 2)`, then
+// the two weight pieces); the wait of half-step t leaves this half-step's and the previous one's in flight
+__host__ __device__ constexpr int g5_dma(int t) { return 2 + (g5_slab_tap(t) ? 1 : 0); }
+__host__ __device__ constexpr int g5_vmcnt(int t) { return g5_dma(t) + g5_dma(t - 1); }
+// the counted waits rest on every half-step issuing the same loads in every chunk, the last included: pinned
+static_assert(g5_vmcnt(0) == 4 && g5_vmcnt(1) == 5 && g5_vmcnt(2) == 6 && g5_vmcnt(3) == 6 && g5_vmcnt(4) == 6 && g5_vmcnt(5) == 6 &&
+              g5_vmcnt(6) == 5 && g5_vmcnt(7) == 4 && g5_vmcnt(8) == 4, "g5_vmcnt table");
+static_assert(g5_dma(0) == 2 && g5_dma(1) == 3 && g5_dma(2) == 3 && g5_dma(3) == 3 && g5_dma(4) == 3 && g5_dma(5) == 3 && g5_dma(6) == 2 &&
+              g5_dma(7) == 2 && g5_dma(8) == 2, "23 DMA loads per chunk and thread: 5 slab pieces + 9 x 2 weight pieces");
 
 template <int T, int N> __host__ __device__ constexpr bool g5_on_board() // is tap T of the cell with file N on the board (dx only)
 {
@@ -134,25 +155,26 @@ __device__ __forceinline__ void g5_step(const G5Ctx &c, cv_f32x4 (&acc)[4][9], i
     if constexpr (LO <= 3 && 3 < HI) G5_CELL(3) if constexpr (LO <= 4 && 4 < HI) G5_CELL(4) if constexpr (LO <= 5 && 5 < HI) G5_CELL(5) \
     if constexpr (LO <= 6 && 6 < HI) G5_CELL(6) if constexpr (LO <= 7 && 7 < HI) G5_CELL(7) if constexpr (LO <= 8 && 8 < HI) G5_CELL(8)
     constexpr int T2 = (T + kG5Ahead) % 9;
-    const int chunk2 = (chunk + (T + kG5Ahead >= 9 ? 1 : 0)) & c.cmask;
+    // Past the last chunk there is nothing left to prefetch, but every load is still ISSUED (the vmcnt counts stay static): its
+    // descriptor then has zero records, the range check fails and nothing is fetched (cv_blds16)
+    const int chunk2 = chunk + (T + kG5Ahead >= 9 ? 1 : 0);
     G5_CELLS(0, 1)
-    if constexpr (g5_slab_tap(T)) { // the next chunk's slab: 5 pieces per thread, in taps 1..5
+    if constexpr (g5_dma(T) > 2) { // the next chunk's slab: 5 pieces per thread, in taps 1..5
         constexpr int pass = T - 1;
-        const int nxt = (chunk + 1) & c.cmask; // past the last chunk: re-stage chunk 0 into the free buffer (keeps every count static)
-        cv_glds16(c.X + (c.xoff[pass] + (unsigned)(nxt * 32)), lds + kG5AOff + (1 - BUF) * kG5SlabBytes + (pass < 4 ? pass * 8192 + c.wave_dst : c.wave_dst4));
+        const unsigned live = pass < 4 ? c.xbytes : c.xbytes4;
+        cv_blds16(c.X, chunk < c.cmask ? live : 0u, c.xoff[pass], (unsigned)((chunk + 1) * 64),
+                  lds + (pass < 4 ? kG5AOff + (1 - BUF) * kG5SlabBytes + pass * 8192 + c.wave_dst : c.wave_dst4 + (1 - BUF) * c.wave_step4));
         __builtin_amdgcn_sched_barrier(0);
     }
     G5_CELLS(1, 2)
     {
-        unsigned wo = c.woff;
-        asm volatile("" : "+v"(wo)); // the address is formed here, per half-step: hoisted for 9 taps x 2 pieces it costs 36 registers
-        const unsigned o = wo + (unsigned)((T2 + 9 * chunk2) * 8192); // half-tile (chunk2, T2): one contiguous 16 KB block
-        const unsigned o2 = o + 4096u;                                 // its rows 128..255
+        const unsigned wlive = chunk2 <= c.cmask ? c.wbytes : 0u;
+        const unsigned so = (unsigned)((T2 + 9 * chunk2) * (2 * 8192)); // half-tile (chunk2, T2): one contiguous 16 KB block, a scalar offset
         unsigned char *const d = lds + ring_wr * kG5WBytes + c.wave_dst;
-        cv_glds16(c.W + o, d);
+        cv_blds16(c.W, wlive, c.woff, so, d);
         __builtin_amdgcn_sched_barrier(0);
         G5_CELLS(2, 3)
-        cv_glds16(c.W + o2, d + 8192);
+        cv_blds16(c.W, wlive, c.woff, so + 8192u, d + 8192);            // its rows 128..255
         __builtin_amdgcn_sched_barrier(0);
     }
     G5_CELLS(3, kG5Split)
@@ -311,33 +333,37 @@ __device__ __forceinline__ void g5_tile(unsigned char *lds, int blk, int grid, c
     }
     c.wave_dst = w * 1024;
     c.lane16 = lane * 16;
-    c.wave_dst4 = (w < 4 ? 4 : 3) * 8192 + w * 1024;
+    c.wave_dst4 = w < 4 ? kG5AOff + 4 * 8192 + w * 1024 : kG5Dump + w * 1024;
+    c.wave_step4 = w < 4 ? kG5SlabBytes : 0;
     c.cin = cin;
     c.cmask = ONE ? 0 : (cin >> 5) - 1;
+    c.xbytes = (unsigned)M * (unsigned)cin * 2u;
+    c.xbytes4 = w < 4 ? c.xbytes : 0u;
+    c.wbytes = 9u * 256u * (unsigned)cin * 2u;
     {
         // slab row sr (0..575) = tensor row p0 - 144 + sr: rank 2k - 1 + sr / 144 of the group; 64-byte rows, position pos of
         // row sr holds source chunk pos ^ f(sr), f = (-(sr >> 2)) & 3 (conflict-free for the 16 rows x 4 chunks one ds_read_b128
         // of this MFMA shape covers)
 #pragma unroll
         for (int it = 0; it < 5; ++it) {
-            const int piece = (it < 4 || w < 4) ? it * 512 + tid : 3 * 512 + tid; // waves 4-7 repeat pass 3 (same bytes, same place)
+            const int piece = (it < 4 || w < 4) ? it * 512 + tid : 3 * 512 + tid; // (waves 4-7 in pass 4: any offset, xbytes4 = 0)
             const int sr = piece >> 2, pos = piece & 3;
             const int schunk = pos ^ ((0 - (sr >> 2)) & 3);
             long p = p0 - 144 + sr;
             p = p < 0 ? 0 : (p > (long)M - 1 ? (long)M - 1 : p);
-            c.xoff[it] = (unsigned)(p * cin + schunk * 8);
+            c.xoff[it] = (unsigned)(p * cin + schunk * 8) * 2u;
         }
-        c.woff = (unsigned)(tid * 8); // packed weights (k_pack_conv_weights_g16): a half-tile is the LDS image itself, read linearly
+        c.woff = (unsigned)(tid * 16); // packed weights (k_pack_conv_weights_g16): a half-tile is the LDS image itself, read linearly
     }
     // ---- prologue: slab of chunk 0, weight half-tiles 0..2; the per-lane setup below runs while the DMA is in flight
 #pragma unroll
-    for (int it = 0; it < 5; ++it) cv_glds16(X + c.xoff[it], lds + kG5AOff + (it < 4 ? it * 8192 + c.wave_dst : c.wave_dst4));
+    for (int it = 0; it < 5; ++it)
+        cv_blds16(X, it < 4 ? c.xbytes : c.xbytes4, c.xoff[it], 0u, lds + (it < 4 ? kG5AOff + it * 8192 + c.wave_dst : c.wave_dst4));
 #pragma unroll
     for (int u = 0; u < kG5Ahead; ++u) {
-        const unsigned o = c.woff + (unsigned)(u * 8192);
         unsigned char *d = lds + u * kG5WBytes + c.wave_dst;
-        cv_glds16(W + o, d);
-        cv_glds16(W + (o + 4096u), d + 8192);
+        cv_blds16(W, c.wbytes, c.woff, (unsigned)(u * 2 * 8192), d);
+        cv_blds16(W, c.wbytes, c.woff, (unsigned)(u * 2 * 8192 + 8192), d + 8192);
     }
     const int lane1 = r * 64 + ((q4 ^ ((0 - (r >> 2)) & 3)) << 4);
     c.a_off = wm * 4096 + lane1;                               // rows 64 wm + 16 i + r of the half-tile
@@ -370,7 +396,7 @@ __device__ __forceinline__ void g5_tile(unsigned char *lds, int blk, int grid, c
     for (int n = 0; n < 9; ++n) b[n] = *(const cv_half8 *)(lds + c.vb[0] + (9 + n - 9) * 1024); // the rank above this wave's: dy = -1
 #define G5_S(j) g5_step<j>(c, acc, chunk + (j) / 9, ring_rd, ring_wr, a0, a1, b)
     if constexpr (ONE) {
-        const int chunk = 0; // (the prefetches past half-step 8 wrap around to chunk 0: valid memory, never read)
+        const int chunk = 0; // (one chunk: every next-chunk prefetch is issued against an empty descriptor and fetches nothing)
         G5_S(0); G5_S(1); G5_S(2); G5_S(3); G5_S(4); G5_S(5); G5_S(6); G5_S(7); G5_S(8);
     } else {
         for (int chunk = 0; chunk <= c.cmask; chunk += 2) {
@@ -379,16 +405,22 @@ __device__ __forceinline__ void g5_tile(unsigned char *lds, int blk, int grid, c
         }
     }
 #undef G5_S
-    cv_wait_vm<0>(); // the wrapped-around DMA loads must land before the LDS is reused / released
+    cv_wait_vm<0>(); // the out-of-range DMA loads (zeros) must have landed before the LDS is reused / released
 
     // ---- epilogue: every wave writes its 64 channels x 144 rows into the [row][channel] image in LDS; then wave w owns
     // rows 36 w .. 36 w + 35 and moves whole 512-byte rows (residual in, output out)
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier(); // every wave is done reading the slabs and the ring
     __builtin_amdgcn_sched_barrier(0);
+    // the lane index is formed again here (v_mbcnt): carried through the loop it is the 257th register of the heads instantiation
+    const int lane_e = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    const int re = lane_e & 15, q4e = lane_e >> 4;
+    const int prow = lane_e >> 5, piece = lane_e & 31;
+    const long pbase = p0 + w * 36 + prow;
+    cv_half8 rv[18];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        const int col = wm * 64 + i * 16 + 4 * q4;
+        const int col = wm * 64 + i * 16 + 4 * q4e;
 #pragma unroll
         for (int n = 0; n < 9; ++n) {
             cv_half4 o;
@@ -396,12 +428,9 @@ __device__ __forceinline__ void g5_tile(unsigned char *lds, int blk, int grid, c
             o[1] = (_Float16)acc[i][n][1];
             o[2] = (_Float16)acc[i][n][2];
             o[3] = (_Float16)acc[i][n][3];
-            *(cv_half4 *)(lds + ((wn * 9 + n) * 16 + r) * kG5ERow + col * 2) = o;
+            *(cv_half4 *)(lds + ((wn * 9 + n) * 16 + re) * kG5ERow + col * 2) = o;
         }
     }
-    const int prow = lane >> 5, piece = lane & 31;
-    const long pbase = p0 + w * 36 + prow;
-    cv_half8 rv[18];
     if (RES) {
 #pragma unroll
         for (int it = 0; it < 18; ++it) rv[it] = *(const cv_half8 *)(R + (pbase + it * 2) * kCvC + piece * 8);
@@ -432,7 +461,7 @@ __device__ __forceinline__ void g5_tile(unsigned char *lds, int blk, int grid, c
         const int rank0 = (int)((p0 - grp * 1440) / 144);
         const long board0[2] = {first_board + grp * 16, first_board + grp * 16};
         const int pos0[2] = {rank0 * 9, rank0 * 9 + 9};
-        g5_heads_phase(lds, w, lane, ha, board0, pos0, false);
+        g5_heads_phase(lds, w, lane_e, ha, board0, pos0, false);
     }
 }
 

@@ -21,6 +21,7 @@
 // Everything else -- ring of five weight half-tiles three ahead, one raw s_barrier per half-step with counted vmcnt, pixel fragments
 // shared by the three dx taps of a dy and refilled in place, LDS-transposed epilogue -- is k_conv3x3_g16's. The next chunk's slab
 // is staged in half-steps 0-2 (2 + 2 + 1 pieces) instead of taps 1-5: its first fragments are read in half-step 5.
+// The DMA goes through k_conv3x3_g16's buffer descriptors; past the last chunk the prefetches are issued against zero records.
 #pragma once
 #include "cczero_conv_g16.h"
 
@@ -28,7 +29,11 @@ namespace ccz {
 
 __host__ __device__ constexpr int g5e_nslab(int h) { return h == 0 ? 2 : h == 1 ? 2 : h == 2 ? 1 : 0; } // slab pieces issued in half-step h
 // DMA loads younger than the weight half-tile the NEXT half-step reads (issue order per half-step: slab pieces, 2 weight loads)
-__host__ __device__ constexpr int g5e_vmcnt(int h) { return 4 + g5e_nslab(h) + g5e_nslab((h + 5) % 6); }
+__host__ __device__ constexpr int g5e_dma(int h) { return 2 + g5e_nslab(h); } // DMA loads a thread issues in half-step h, past the last chunk as well
+__host__ __device__ constexpr int g5e_vmcnt(int h) { return g5e_dma(h) + g5e_dma((h + 5) % 6); }
+static_assert(g5e_vmcnt(0) == 6 && g5e_vmcnt(1) == 8 && g5e_vmcnt(2) == 7 && g5e_vmcnt(3) == 5 && g5e_vmcnt(4) == 4 && g5e_vmcnt(5) == 4, "g5e_vmcnt table");
+static_assert(g5e_dma(0) == 4 && g5e_dma(1) == 4 && g5e_dma(2) == 3 && g5e_dma(3) == 2 && g5e_dma(4) == 2 && g5e_dma(5) == 2,
+              "17 DMA loads per chunk and thread: 5 slab pieces + 6 x 2 weight pieces");
 
 // One half-step of an edge tile: live tap H = J % 6 of a 32-channel chunk (tap index H + toff in the packed weights), J = its
 // index inside the unrolled pair of chunks (A register set = J & 1, slab buffer = J / 6). vb[BUF] = this lane's fragment base of
@@ -60,27 +65,28 @@ __device__ __forceinline__ void g5e_step(const G5Ctx &c, cv_f32x4 (&acc)[4][9], 
     if constexpr (LO <= 3 && 3 < HI) G5E_CELL(3) if constexpr (LO <= 4 && 4 < HI) G5E_CELL(4) if constexpr (LO <= 5 && 5 < HI) G5E_CELL(5) \
     if constexpr (LO <= 6 && 6 < HI) G5E_CELL(6) if constexpr (LO <= 7 && 7 < HI) G5E_CELL(7) if constexpr (LO <= 8 && 8 < HI) G5E_CELL(8)
     constexpr int H2 = (H + kG5Ahead) % 6;
-    const int chunk2 = (chunk + (H + kG5Ahead >= 6 ? 1 : 0)) & c.cmask;
+    // past the last chunk: as in g5_step, the loads are issued against descriptors of zero records and fetch nothing
+    const int chunk2 = chunk + (H + kG5Ahead >= 6 ? 1 : 0);
     G5E_CELLS(0, 1)
-    if constexpr (g5e_nslab(H) > 0) { // the next chunk's slab: passes 0,1 | 2,3 | 4 in half-steps 0 | 1 | 2
-        const int nxt = (chunk + 1) & c.cmask; // past the last chunk: re-stage chunk 0 into the free buffer (keeps every count static)
+    if constexpr (g5e_dma(H) > 2) { // the next chunk's slab: passes 0,1 | 2,3 | 4 in half-steps 0 | 1 | 2
         constexpr int p0 = H * 2;
-        cv_glds16(c.X + (c.xoff[p0] + (unsigned)(nxt * 32)), lds + kG5AOff + (1 - BUF) * kG5SlabBytes + (p0 < 4 ? p0 * 8192 + c.wave_dst : c.wave_dst4));
-        if constexpr (g5e_nslab(H) > 1)
-            cv_glds16(c.X + (c.xoff[p0 + 1] + (unsigned)(nxt * 32)), lds + kG5AOff + (1 - BUF) * kG5SlabBytes + ((p0 + 1) * 8192 + c.wave_dst));
+        const unsigned so = (unsigned)((chunk + 1) * 64);
+        const unsigned live = chunk < c.cmask ? (p0 < 4 ? c.xbytes : c.xbytes4) : 0u;
+        cv_blds16(c.X, live, c.xoff[p0], so,
+                  lds + (p0 < 4 ? kG5AOff + (1 - BUF) * kG5SlabBytes + p0 * 8192 + c.wave_dst : c.wave_dst4 + (1 - BUF) * c.wave_step4));
+        if constexpr (g5e_dma(H) > 3)
+            cv_blds16(c.X, live, c.xoff[p0 + 1], so, lds + kG5AOff + (1 - BUF) * kG5SlabBytes + ((p0 + 1) * 8192 + c.wave_dst));
         __builtin_amdgcn_sched_barrier(0);
     }
     G5E_CELLS(1, 2)
     {
-        unsigned wo = c.woff;
-        asm volatile("" : "+v"(wo)); // the address is formed here, per half-step (as in g5_step)
-        const unsigned o = wo + (unsigned)((H2 + toff + 9 * chunk2) * 8192); // half-tile (chunk2, tap H2 + toff): one contiguous 16 KB block
-        const unsigned o2 = o + 4096u;
+        const unsigned wlive = chunk2 <= c.cmask ? c.wbytes : 0u;
+        const unsigned so = (unsigned)((H2 + toff + 9 * chunk2) * (2 * 8192)); // half-tile (chunk2, tap H2 + toff): one contiguous 16 KB block
         unsigned char *const d = lds + ring_wr * kG5WBytes + c.wave_dst;
-        cv_glds16(c.W + o, d);
+        cv_blds16(c.W, wlive, c.woff, so, d);
         __builtin_amdgcn_sched_barrier(0);
         G5E_CELLS(2, 3)
-        cv_glds16(c.W + o2, d + 8192);
+        cv_blds16(c.W, wlive, c.woff, so + 8192u, d + 8192);
         __builtin_amdgcn_sched_barrier(0);
     }
     G5E_CELLS(3, kG5Split)
@@ -144,31 +150,35 @@ __device__ __forceinline__ void g5e_tile(unsigned char *lds, int blk, const _Flo
     c.W = W;
     c.wave_dst = w * 1024;
     c.lane16 = lane * 16;
-    c.wave_dst4 = (w < 4 ? 4 : 3) * 8192 + w * 1024;
+    c.wave_dst4 = w < 4 ? kG5AOff + 4 * 8192 + w * 1024 : kG5Dump + w * 1024;
+    c.wave_step4 = w < 4 ? kG5SlabBytes : 0;
     c.cin = cin;
     c.cmask = (cin >> 5) - 1;
+    c.xbytes = (unsigned)groups * (1440u * 2u) * (unsigned)cin;
+    c.xbytes4 = w < 4 ? c.xbytes : 0u;
+    c.wbytes = 9u * 256u * (unsigned)cin * 2u;
     {
         // slab row sr: 0..287 = group A's rows srcA + sr, 288..575 = group B's; 64-byte rows, position pos of row sr holds source
         // chunk pos ^ f(sr), f = (-(sr >> 2)) & 3 (the swizzle of k_conv3x3_g16)
 #pragma unroll
         for (int it = 0; it < 5; ++it) {
-            const int piece = (it < 4 || w < 4) ? it * 512 + tid : 3 * 512 + tid; // waves 4-7 repeat pass 3 (same bytes, same place)
+            const int piece = (it < 4 || w < 4) ? it * 512 + tid : 3 * 512 + tid; // (waves 4-7 in pass 4: any offset, xbytes4 = 0)
             const int sr = piece >> 2, pos = piece & 3;
             const int schunk = pos ^ ((0 - (sr >> 2)) & 3);
             const long p = sr < 288 ? srcA + sr : srcB + (sr - 288);
-            c.xoff[it] = (unsigned)(p * cin + schunk * 8);
+            c.xoff[it] = (unsigned)(p * cin + schunk * 8) * 2u;
         }
-        c.woff = (unsigned)(tid * 8);
+        c.woff = (unsigned)(tid * 16);
     }
     // ---- prologue: slab of chunk 0, weight half-tiles of the first three live taps
 #pragma unroll
-    for (int it = 0; it < 5; ++it) cv_glds16(X + c.xoff[it], lds + kG5AOff + (it < 4 ? it * 8192 + c.wave_dst : c.wave_dst4));
+    for (int it = 0; it < 5; ++it)
+        cv_blds16(X, it < 4 ? c.xbytes : c.xbytes4, c.xoff[it], 0u, lds + (it < 4 ? kG5AOff + it * 8192 + c.wave_dst : c.wave_dst4));
 #pragma unroll
     for (int u = 0; u < kG5Ahead; ++u) {
-        const unsigned o = c.woff + (unsigned)((u + toff) * 8192);
         unsigned char *d = lds + u * kG5WBytes + c.wave_dst;
-        cv_glds16(W + o, d);
-        cv_glds16(W + (o + 4096u), d + 8192);
+        cv_blds16(W, c.wbytes, c.woff, (unsigned)((u + toff) * 2 * 8192), d);
+        cv_blds16(W, c.wbytes, c.woff, (unsigned)((u + toff) * 2 * 8192 + 8192), d + 8192);
     }
     const int lane1 = r * 64 + ((q4 ^ ((0 - (r >> 2)) & 3)) << 4);
     c.a_off = wm * 4096 + lane1;                               // rows 64 wm + 16 i + r of the half-tile
@@ -202,7 +212,7 @@ __device__ __forceinline__ void g5e_tile(unsigned char *lds, int blk, const _Flo
         G5E_S(6); G5E_S(7); G5E_S(8); G5E_S(9); G5E_S(10); G5E_S(11);
 #undef G5E_S
     }
-    cv_wait_vm<0>(); // the wrapped-around DMA loads must land before the LDS is reused / released
+    cv_wait_vm<0>(); // the out-of-range DMA loads (zeros) must have landed before the LDS is reused / released
 
     // ---- epilogue (k_conv3x3_g16's): the [row][channel] image in LDS, rows 0..143 = group A's edge rank, 144..287 = group B's;
     // wave w owns image rows 36 w .. 36 w + 35 and moves whole 512-byte rows (residual in, output out)
