@@ -21,6 +21,7 @@ MAX_LEGAL = 128
 MASK_WORDS = 66
 PLANES = 10710
 REC_BYTES, REC_HDR, REC_IDS, REC_PI = 880, 96, 112, 368  # compact ply record (include/cczero.h CCZ_REC_*)
+REC_FLAGS, REC_FAST = 103, 1  # byte of the header's flags; CCZ_REC_FAST: a fast ply of playout-cap randomisation (no policy target)
 HEAD_POL_STRIDE, HEAD_VAL_STRIDE = 1536, 640  # CCZ_HEAD_*_STRIDE: fp16 elements per board of the head kernels' outputs
 
 ABI_VERSION = 8
@@ -104,6 +105,10 @@ PROTOTYPES = {
     "ccz_set_routing": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint64]),
     "ccz_eval_plan_routed": (C.c_int, [_P, _P, _P, _P]),
     "ccz_gather_priors_routed": (C.c_int, [_P, _P, _P, _P, C.c_int32, _P, _P]),
+    "ccz_set_budgets": (C.c_int, [_P, _P, _P, _P]),
+    "ccz_draw_budgets": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_double, _P]),
+    "ccz_expand_record_targets": (C.c_int, [_P, _P, C.c_int64, C.c_uint32, C.c_int64, C.c_int64, _P]),
+    "ccz_sample_record_targets": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, C.c_uint32, _P]),
     "ccz_finish_move": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32]),
     "ccz_root_children": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
     "ccz_principal_variations": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),

@@ -171,11 +171,14 @@ def _version(net, ev):
 
 class Arena:
     """``n_pairs`` pairs of games between ``net_a`` (A) and ``net_b`` (B). Engine: eps 0, temperature 1e-3, tree discarded after
-    every move, evaluation cache of 2^``eval_cache_log2`` positions shared by both networks (salted per network)."""
+    every move, evaluation cache of 2^``eval_cache_log2`` positions shared by both networks (salted per network).
+    ``n_playout_b``: playout odds -- A searches ``n_playout`` simulations per move, B ``n_playout_b`` (per-board simulation budgets,
+    ``engine.set_budgets``: the lockstep loop runs max(nA, nB) steps and a board that has used its budget costs no evaluator row);
+    None: both search ``n_playout``."""
 
     def __init__(self, net_a, net_b, n_pairs: int, n_playout: int = 400, opening_plies: int = 6, seed: int = 0,
                  max_plies: int = 0, c_puct: float = C_PUCT, eval_cache_log2: int = 22, device: int = 0,
-                 cache_verify: bool = False):
+                 cache_verify: bool = False, n_playout_b: int | None = None):
         from .engine import SelfPlayEngine
         self.nets = (net_a, net_b)
         self.ev = (_as_evaluator(net_a, "A"), _as_evaluator(net_b, "B"))
@@ -186,8 +189,12 @@ class Arena:
         self.P = int(n_pairs)
         self.B = 2 * self.P
         self.n_playout = int(n_playout)
+        self.n_playout_b = None if n_playout_b is None else int(n_playout_b)
+        if self.n_playout < 1 or (self.n_playout_b is not None and self.n_playout_b < 1):
+            raise ValueError("Arena: n_playout and n_playout_b must be >= 1")
+        self.n_steps = self.n_playout if self.n_playout_b is None else max(self.n_playout, self.n_playout_b)   # lockstep steps per move
         self.temp = 1e-3
-        self.engine = e = SelfPlayEngine(self.B, n_playout=self.n_playout, c_puct=c_puct, eps=0.0, alpha=0.2, temp=self.temp,
+        self.engine = e = SelfPlayEngine(self.B, n_playout=self.n_steps, c_puct=c_puct, eps=0.0, alpha=0.2, temp=self.temp,
                                          seed=seed, device=device, max_plies=max_plies, mirror=False,
                                          eval_cache_log2=eval_cache_log2, cache_verify=cache_verify)
         self.max_plies = e.max_plies
@@ -198,6 +205,7 @@ class Arena:
         status = e.set_positions(np.asarray(sq)[of], np.asarray(turn)[of], np.asarray(half)[of])   # one launch (no moves: as set_position)
         if status.any():
             raise ValueError(f"Arena: opening positions refused by the engine (status {status.tolist()})")
+        self._turn = np.asarray(turn)[of].astype(np.uint8)      # side to move on every board (kept from the per-move status read)
         self._temps = np.full(self.B, self.temp, np.float64)
         self._versions = None
         self.moves = []                      # host int32 [B] per lockstep move (-1: no move on that board)
@@ -219,19 +227,27 @@ class Arena:
         each plan (tests)."""
         e, (ev0, ev1) = self.engine, self.ev
         self._sync_routing()
+        if self.n_playout_b is not None:
+            e.set_budgets(self.move_budgets())
         leaf = e.select_leaves()
-        for i in range(self.n_playout):
+        for i in range(self.n_steps):
             p0, p1 = e.eval_plan_routed()
             self._rows += e.n_miss2
             if on_step is not None:
                 on_step(self, p0, p1)
             lg0, v0 = ev0(leaf, plan=p0)
             lg1, v1 = ev1(leaf, plan=p1)
-            if i + 1 < self.n_playout:
+            if i + 1 < self.n_steps:
                 leaf = e.step_routed(lg0, v0, lg1, v1)
             else:
                 e.expand_backup_routed(lg0, v0, lg1, v1)
             self.steps += 1
+
+    def move_budgets(self) -> np.ndarray:
+        """int32 [B]: the simulations every board searches in the move at hand -- ``n_playout`` where A is to move, ``n_playout_b``
+        (``n_playout`` without odds) where B is."""
+        nb = self.n_playout if self.n_playout_b is None else self.n_playout_b
+        return np.where(self._turn == self.a_colour, self.n_playout, nb).astype(np.int32)
 
     def play_move(self, on_step=None, before_move=None):
         """One lockstep move of every unfinished board: search, move at temperature 1e-3, tree discarded. Returns the moves
@@ -247,7 +263,9 @@ class Arena:
         over = e.game_status()["over"]
         moves = e.finish_move(temps=self._temps, keep_tree=False).cpu().numpy().copy()
         # a game adjudicated at max_plies ends INSTEAD of a move (finish_move plays none on that board)
-        self.truncated |= (over == 0) & (e.game_status()["over"] == 1) & (moves < 0)
+        st = e.game_status()
+        self.truncated |= (over == 0) & (st["over"] == 1) & (moves < 0)
+        self._turn = st["turn"].astype(np.uint8)
         self.moves.append(moves)
         return moves
 
@@ -275,6 +293,7 @@ class Arena:
         rows = self._rows.cpu().numpy()
         steps = max(1, self.steps)
         out = {"pairs": self.P, "games": self.B, "n_playout": self.n_playout,
+               "n_playout_b": self.n_playout if self.n_playout_b is None else self.n_playout_b,
                "wins": int(np.sum(w == self.a_colour)), "draws": int(np.sum(w == -1)), "losses": int(np.sum((w != -1) & (w != self.a_colour))),
                "truncated": int(self.truncated.sum()), "unfinished": int((st["over"] == 0).sum())}
         out.update(pair_stats(pair_pts))
@@ -314,6 +333,7 @@ def main(argv=None) -> int:
     ap.add_argument("--b", required=True, help="opponent weights (state_dict file), or random:<seed>")
     ap.add_argument("--pairs", type=int, default=512, help="pairs of games (one opening, both colours)")
     ap.add_argument("--playout", type=int, default=400, help="simulations per move")
+    ap.add_argument("--playout-b", type=int, default=None, help="playout odds: simulations per move of B (default: as A)")
     ap.add_argument("--opening-plies", type=int, default=6, help="random legal plies of every opening")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--max-plies", type=int, default=0, help="ply cap (0 = the engine's 2048); a capped game is a draw, counted as truncated")
@@ -326,7 +346,7 @@ def main(argv=None) -> int:
     na = _load(a.a, a.channels, a.blocks, a.device)
     nb = _load(a.b, a.channels, a.blocks, a.device)
     arena = Arena(na, nb, a.pairs, n_playout=a.playout, opening_plies=a.opening_plies, seed=a.seed, max_plies=a.max_plies,
-                  eval_cache_log2=a.eval_cache_log2, device=a.device)
+                  eval_cache_log2=a.eval_cache_log2, device=a.device, n_playout_b=a.playout_b)
     r = arena.play()
     r.update({"a": a.a, "b": a.b, "opening_plies": a.opening_plies, "seed": a.seed, "net": f"{a.blocks}x{a.channels}",
               "promote": promote(r, a.threshold), "threshold": a.threshold})

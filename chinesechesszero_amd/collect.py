@@ -53,6 +53,11 @@ class TupleSink:
     write, longer than the move's search on the GPU. ``finalize`` expands the record shards with the GPU expander
     (``ccz_expand_records``: byte for byte the rows ``ccz_harvest`` writes, tests/test_gpu_harvest.py) before it merges; the
     reference, too, converts offline (convert.py).
+
+    Playout-cap randomisation: a row may carry a policy-target byte (0 = the fast plies, ``CCZ_REC_FAST`` in the record header:
+    keep them out of the policy loss). ``finalize`` writes them as ``policy_targets.npy`` (uint8, row-aligned with ``states.npy``;
+    rows stored without a flag count as targets) -- but only once some row was flagged: a data set without fast plies has no such
+    file and its other files are byte for byte what they were.
     """
 
     ARRAYS = {"states": ("_s.npy", np.float16, (17, 7, 10, 9)), "mcts": ("_p.npy", None, (2086,)), "winners": ("_z.npy", np.float32, ())}
@@ -190,9 +195,18 @@ class TupleSink:
     def _dtype(self, key):
         return self.pi_dtype if key == "mcts" else np.dtype(self.ARRAYS[key][1])
 
-    def _write_dense_shard(self, base: str, s, p, w):
+    TARGETS = "policy_targets.npy"
+
+    def _write_dense_shard(self, base: str, s, p, w, t=None):
+        """``t``: the rows' policy-target bytes; a ``_t.npy`` file is written only when one of them is 0."""
+        if t is not None:
+            t = (np.asarray(t).reshape(-1) != 0).astype(np.uint8)
+            if len(t) != len(w):
+                raise ValueError(f"{len(t)} policy-target bytes for {len(w)} rows")
         np.save(base + "_s.npy", s.astype(np.float16, copy=False).reshape(-1, 17, 7, 10, 9))
         np.save(base + "_p.npy", p.astype(self.pi_dtype, copy=False).reshape(-1, 2086))
+        if t is not None and not t.all():
+            np.save(base + "_t.npy", t)
         np.save(base + "_z.npy", w.astype(np.float32, copy=False).reshape(-1))   # (written last: a shard counts once its z file exists)
         self._shards.append((base, int(len(w))))
 
@@ -204,7 +218,8 @@ class TupleSink:
                 json.dump({"iters": self.games}, f)
             os.replace(tmp, os.path.join(self.out_dir, "collect_state.json"))
 
-    def append(self, states, pi, z, games: int = 1):
+    def append(self, states, pi, z, games: int = 1, targets=None):
+        """``targets``: uint8 [rows] policy-target bytes or None (every row a target)."""
         to_np = lambda t: t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
         s, p, w = to_np(states), to_np(pi), to_np(z)
         if len(w):
@@ -213,7 +228,7 @@ class TupleSink:
                 self._next += 1
                 base = os.path.join(self.out_dir, f".shard_{os.getpid()}_{self._next:06d}")
             self._next += 1
-            self._write_dense_shard(base, s, p, w)
+            self._write_dense_shard(base, s, p, w, None if targets is None else to_np(targets))
         self._count_games(games)
 
     # ---- compact record shards (what the batched collector writes while it runs) ----------------------
@@ -267,7 +282,8 @@ class TupleSink:
             from ._lib import CczError
             raise CczError(f"{self.out_dir}: {len(self._rshards)} record shard(s) ({sum(r[1] for r in self._rshards)} plies) wait for the GPU expander "
                            "(ccz_expand_records): run finalize() where the collector ran; nothing was changed")
-        from .engine import expand_records, game_aligned_chunks
+        from ._lib import REC_FAST, REC_FLAGS
+        from .engine import expand_record_targets, expand_records, game_aligned_chunks
         for path, plies, flags, pot in list(self._rshards):
             tag = os.path.basename(path)[len(".rshard_"):-len(".npy")]
             prefix = f".shard_r{tag}_"
@@ -277,8 +293,10 @@ class TupleSink:
             self._shards = [(b, n) for b, n in self._shards if not os.path.basename(b).startswith(prefix)]
             rec = torch.from_numpy(np.load(path)).cuda()
             for k, part in enumerate(game_aligned_chunks(rec, 1 << 14)):   # bounds the dense temporary (2^15 rows = 1 GB)
-                s, p, z = expand_records(part.contiguous(), flags, pot)
-                self._write_dense_shard(os.path.join(self.out_dir, f"{prefix}{k:04d}"), s.cpu().numpy(), p.cpu().numpy(), z.cpu().numpy())
+                part = part.contiguous()
+                s, p, z = expand_records(part, flags, pot)
+                t = expand_record_targets(part, flags).cpu().numpy() if bool((part[:, REC_FLAGS] & REC_FAST).any()) else None
+                self._write_dense_shard(os.path.join(self.out_dir, f"{prefix}{k:04d}"), s.cpu().numpy(), p.cpu().numpy(), z.cpu().numpy(), t)
             os.remove(path)
             self._rshards.remove((path, plies, flags, pot))
 
@@ -370,12 +388,43 @@ class TupleSink:
             out.flush()
             del out
             os.replace(tmp, paths[k])
+        self._merge_targets(n_old, total, shards)
         self._write_meta(total)
         for base, _ in shards:
-            for suffix, _, _ in self.ARRAYS.values():
+            for suffix in [sfx for sfx, _, _ in self.ARRAYS.values()] + ["_t.npy"]:
                 if os.path.exists(base + suffix):
                     os.remove(base + suffix)
         os.remove(self._journal())
+
+    def _merge_targets(self, n_old: int, total: int, shards):
+        """``policy_targets.npy`` next to the three arrays, if this merge or an earlier one saw a flagged row: the old rows (ones
+        where there was no file), then every shard's ``_t.npy`` (ones where it has none). Skipped when already at ``total``."""
+        path = os.path.join(self.out_dir, self.TARGETS)
+        cur_n = None
+        if os.path.exists(path):
+            cur = np.load(path, mmap_mode="r")
+            if cur.dtype != np.uint8 or cur.ndim != 1 or int(cur.shape[0]) not in (n_old, total):
+                raise ValueError(f"{path}: {cur.dtype}{cur.shape}, the merge in progress expects uint8 ({n_old},) or ({total},)")
+            cur_n = int(cur.shape[0])
+            del cur
+        if (cur_n == total and n_old != total) or (cur_n is None and not any(os.path.exists(b + "_t.npy") for b, _ in shards)):
+            return
+        tmp = path + ".tmp"
+        out = np.lib.format.open_memmap(tmp, mode="w+", dtype=np.uint8, shape=(total,))
+        out[:] = 1
+        if cur_n is not None:
+            out[:n_old] = np.load(path, mmap_mode="r")[:n_old]
+        pos = n_old
+        for base, n in shards:
+            if os.path.exists(base + "_t.npy"):
+                t = np.load(base + "_t.npy", mmap_mode="r")
+                if t.dtype != np.uint8 or t.shape != (n,):
+                    raise ValueError(f"{base}_t.npy: {t.dtype}{t.shape}, expected uint8({n},)")
+                out[pos:pos + n] = t
+            pos += n
+        out.flush()
+        del out
+        os.replace(tmp, path)
 
     def _recover(self):
         """A journal on disk = a merge that did not finish: complete it (its shards are then gone before they could be
@@ -435,7 +484,8 @@ class CollectPipeline:
     def __init__(self, init_model=None, n_boards: int = 1, n_playout: int = PLAYOUT, device: int = 0, seed: int = 0,
                  data_dir: str = DATA_DIR, reference_quirks: bool = False, num_channels: int = 256, resblocks_num: int = 40,
                  finalize_every: int = 0, on_playout=None, max_plies: int = 0, eval_cache_log2: int | None = None, gatherer=None,
-                 dense_shards: bool = False, replay_plies: int = 0, train_every: int = 0, train_batch: int = BATCH_SIZE):
+                 dense_shards: bool = False, replay_plies: int = 0, train_every: int = 0, train_batch: int = BATCH_SIZE,
+                 playout_cap_fast: int = 0, playout_cap_prob: float | None = None):
         # collect + train as one job (both 0: off): the rank that stores the union keeps it in a record ring of ``replay_plies`` plies
         # and runs one Trainer step of ``train_batch`` rows every ``train_every`` lockstep moves, once the ring holds a batch
         self.replay_plies, self.train_every, self.train_batch = int(replay_plies), int(train_every), int(train_batch)
@@ -445,6 +495,24 @@ class CollectPipeline:
             raise ValueError("replay_plies and train_every go together: a ring nobody draws from, or a trainer without one, is a mistake")
         if self.replay_plies and n_boards <= 1:
             raise ValueError("the replay ring is fed by the batched path: n_boards must be > 1")
+        # playout-cap randomisation (both or neither): a move is a full search of ``n_playout`` simulations with probability
+        # ``playout_cap_prob``, else a fast one of ``playout_cap_fast``; fast plies stay out of the policy loss (selfplay.BatchedSelfPlay)
+        self.playout_cap = None
+        if bool(playout_cap_fast) != (playout_cap_prob is not None):
+            raise ValueError("playout_cap_fast and playout_cap_prob go together: a fast budget without a probability, or the other way round, is a mistake")
+        if playout_cap_fast:
+            if n_boards <= 1:
+                raise ValueError("playout-cap randomisation runs on the batched path: n_boards must be > 1")
+            if dense_shards:
+                raise ValueError("playout-cap randomisation needs the record shards (dense_shards=False): dense rows carry no flag")
+            if gatherer is not None and not (hasattr(gatherer, "post") or hasattr(gatherer, "_payload")):
+                raise ValueError("playout-cap randomisation needs a record exchange (AsyncRecordExchange / RecordGatherer): "
+                                 "the dense rows a TupleGatherer moves carry no flag")
+            if not 1 <= int(playout_cap_fast) <= int(n_playout):
+                raise ValueError(f"playout_cap_fast must be in 1..n_playout (got {playout_cap_fast})")
+            if not 0.0 <= float(playout_cap_prob) <= 1.0:
+                raise ValueError(f"playout_cap_prob must be in [0, 1] (got {playout_cap_prob})")
+            self.playout_cap = (int(playout_cap_fast), float(playout_cap_prob))
         self.board = Board()                       # collect.py:28 (never advanced: source of the turn-plane quirk)
         self.game = Game(self.board, reference_quirks=reference_quirks)
         self.temp = 1.0
@@ -570,7 +638,8 @@ class CollectPipeline:
             self.selfplay = BatchedSelfPlay(self.policy_value_net.evaluate_leaves_logits, self.n_boards, n_playout=self.n_playout,
                                             eval_cache_log2=(24 if self.n_boards >= 192 else 0) if self.eval_cache_log2 is None else int(self.eval_cache_log2),
                                             c_puct=self.c_puct, temp=self.temp, seed=self.seed, board_id_base=rank * self.n_boards,
-                                            device=self.device, reference_quirks=self.reference_quirks, max_plies=self.max_plies)
+                                            device=self.device, reference_quirks=self.reference_quirks, max_plies=self.max_plies,
+                                            playout_cap=self.playout_cap)
             if getattr(self, "_viewer", None) is not None:
                 self.selfplay.watch(0, self._viewer)
         for _ in range(n_moves):
@@ -722,7 +791,11 @@ class CollectPipeline:
             if self.trainer is None:
                 from .trainer import Trainer
                 self.trainer = Trainer(self.policy_value_net, amp_dtype="bf16")   # bf16: no GradScaler, so no host sync per update
-            self.last_losses = self.trainer.step(*self.ring.sample(self.train_batch), sync=False)
+            if self.playout_cap is None:
+                self.last_losses = self.trainer.step(*self.ring.sample(self.train_batch), sync=False)
+            else:   # fast plies train the value head only
+                st, pi, z, tg = self.ring.sample(self.train_batch, targets=True)
+                self.last_losses = self.trainer.step(st, pi, z, sync=False, policy_mask=tg)
         if multi:
             from .replay import broadcast_model
             broadcast_model(self.policy_value_net, src=0, what="state")
@@ -812,6 +885,9 @@ def build_parser():
     parser.add_argument("--train-every", type=int, default=0, help="one trainer step on a minibatch of the ring every this many lockstep moves, "
                         "once the ring holds a batch (0 = off; needs --replay-plies)")
     parser.add_argument("--train-batch", type=int, default=BATCH_SIZE, help="rows of that minibatch (parameters.BATCH_SIZE)")
+    parser.add_argument("--playout-cap-fast", type=int, default=0, help="playout-cap randomisation: simulations of a fast move (0 = off; needs "
+                        "--playout-cap-prob). Fast plies are flagged and stay out of the policy loss")
+    parser.add_argument("--playout-cap-prob", type=float, default=None, help="probability that a move is a full search of --playout simulations")
     return parser
 
 
@@ -843,7 +919,8 @@ if __name__ == "__main__":
     pipe = CollectPipeline(init_model=args.model, n_boards=args.boards, n_playout=args.playout, data_dir=args.data_dir, seed=args.seed,
                            num_channels=args.channels, resblocks_num=args.blocks, max_plies=args.max_plies, device=device,
                            eval_cache_log2=args.eval_cache_log2, gatherer=gatherer, replay_plies=args.replay_plies,
-                           train_every=args.train_every, train_batch=args.train_batch)
+                           train_every=args.train_every, train_batch=args.train_batch, playout_cap_fast=args.playout_cap_fast,
+                           playout_cap_prob=args.playout_cap_prob)
     if world > 1:
         from .launch import guarded
 

@@ -81,6 +81,7 @@ struct ccz_engine {
     uint8_t *route_red = nullptr;  // [B] device
     uint8_t *route_net = nullptr;  // [B] device: written by k_cache_probe_routed, read by the plan and the gather
     uint64_t salt[2] = {0, 0};
+    bool budgets_on = false;       // ccz_set_budgets / ccz_draw_budgets (off: every budget INT32_MAX, every target 1)
 };
 
 #define ACTIVE(e) ((unsigned)((e)->active > 0 ? (e)->active : (e)->d.B))
@@ -236,6 +237,10 @@ int ccz_create(const ccz_config *cfg, ccz_engine **out)
     ALLOC(d.rec_turn, B * d.max_plies);
     ALLOC(d.rec_k, B * d.max_plies);
     ALLOC(d.rec_off, B * d.max_plies);
+    ALLOC(d.rec_target, B * d.max_plies);
+    ALLOC(d.budget, B);
+    ALLOC(d.move_sims, B);
+    ALLOC(d.target, B);
     ALLOC(d.rec_ids, B * d.pi_cap);
     ALLOC(d.rec_pi, B * d.pi_cap);
     ALLOC(d.stats, B);
@@ -271,6 +276,8 @@ int ccz_create(const ccz_config *cfg, ccz_engine **out)
         return fail(-2, "ccz_create: device allocation failed after %zu bytes: %s", got, hipGetErrorString(he));
     }
     e->h_meta.resize(B);
+    hipLaunchKernelGGL(k_set_budgets, dim3((d.B + 255) / 256), dim3(256), 0, 0, d, d.B, (const int32_t *)nullptr, (const uint8_t *)nullptr);
+    HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_reset, dim3(d.B), dim3(64), 0, 0, d, (const uint8_t *)nullptr);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
@@ -427,6 +434,7 @@ int ccz_set_scouts(ccz_engine *e, int32_t n_scouts)
     NEED(e);
     if (n_scouts < 0 || n_scouts >= e->d.B) return fail(-1, "ccz_set_scouts: n_scouts must be in 0 .. n_boards - 1 (got %d of %d boards)", n_scouts, e->d.B);
     if (n_scouts && !e->d.cache) return fail(-1, "ccz_set_scouts: scouts work through the evaluation cache (ccz_config.eval_cache_log2)");
+    if (n_scouts && e->budgets_on) return fail(-1, "ccz_set_scouts: not while simulation budgets are on (ccz_set_budgets(NULL) turns them off)");
     e->active = n_scouts ? e->d.B - n_scouts : 0;
     return 0;
 }
@@ -560,6 +568,29 @@ int ccz_gather_priors_routed(ccz_engine *e, void *stream, const void *logits0_de
         hipLaunchKernelGGL(k_softmax_gather_routed<float>, dim3(e->d.B), dim3(64), 0, s, e->d, net, (const float *)logits0_dev,
                            (const float *)logits1_dev, value0_dev, value1_dev, e->salt[0], e->salt[1]);
     HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int ccz_set_budgets(ccz_engine *e, void *stream, const int32_t *budgets_dev, const uint8_t *targets_dev)
+{
+    NEED(e);
+    if (e->active > 0) return fail(-1, "ccz_set_budgets: not with scout slots (ccz_set_scouts)");
+    hipLaunchKernelGGL(k_set_budgets, dim3((e->d.B + 255) / 256), dim3(256), 0, (hipStream_t)stream, e->d, e->d.B, budgets_dev, targets_dev);
+    HIP_TRY(hipGetLastError());
+    e->budgets_on = budgets_dev != nullptr;
+    return 0;
+}
+
+int ccz_draw_budgets(ccz_engine *e, void *stream, int32_t n_full, int32_t n_fast, double p_full, int32_t *budgets_out_dev)
+{
+    NEED(e);
+    if (e->active > 0) return fail(-1, "ccz_draw_budgets: not with scout slots (ccz_set_scouts)");
+    if (n_full < 1 || n_fast < 1) return fail(-1, "ccz_draw_budgets: n_full and n_fast must be >= 1 (got %d, %d)", n_full, n_fast);
+    if (!(p_full >= 0.0 && p_full <= 1.0)) return fail(-1, "ccz_draw_budgets: p_full %g must be in [0, 1]", p_full);
+    hipLaunchKernelGGL(k_draw_budgets, dim3((e->d.B + 255) / 256), dim3(256), 0, (hipStream_t)stream, e->d, e->d.B, (int)n_full, (int)n_fast, p_full,
+                       budgets_out_dev);
+    HIP_TRY(hipGetLastError());
+    e->budgets_on = true;
     return 0;
 }
 
@@ -931,6 +962,39 @@ int ccz_sample_records(void *stream, const void *ring_dev, int64_t cap_plies, co
     hipLaunchKernelGGL(k_sample_records, dim3((unsigned)batch), dim3(256), 0, (hipStream_t)stream, (const uint8_t *)ring_dev, (long long)cap_plies,
                        (const long long *)window_dev, (const long long *)draws_dev, (long long)batch,
                        flags & (CCZ_FLAG_REFERENCE_QUIRKS | CCZ_FLAG_NO_MIRROR), typepack, (uint16_t *)states_f16_dev, pi_dev, z_dev, bad_records_dev);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int ccz_expand_record_targets(void *stream, const void *records_dev, int64_t n_plies, uint32_t flags, int64_t ring_rows, int64_t head_row,
+                              uint8_t *target_dev)
+{
+    if (n_plies < 0 || ring_rows < 0 || head_row < 0) return fail(-1, "ccz_expand_record_targets: negative size");
+    if (n_plies == 0) return 0;
+    if (!records_dev || !target_dev) return fail(-1, "ccz_expand_record_targets: null buffer");
+    if (((uintptr_t)records_dev) & 3) return fail(-1, "ccz_expand_record_targets: the records must be 4-byte aligned");
+    if (n_plies > (int64_t)INT32_MAX) return fail(-1, "ccz_expand_record_targets: too many records for one launch");
+    const int64_t rows = n_plies * ((flags & CCZ_FLAG_NO_MIRROR) ? 1 : 2);
+    if (ring_rows > 0 && rows > ring_rows) return fail(-1, "ccz_expand_record_targets: %lld rows do not fit a ring of %lld", (long long)rows, (long long)ring_rows);
+    if (ring_rows == 0 && head_row != 0) return fail(-1, "ccz_expand_record_targets: head_row needs ring_rows");
+    hipLaunchKernelGGL(k_expand_record_targets, dim3((unsigned)((n_plies + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const uint8_t *)records_dev,
+                       (long long)n_plies, flags & CCZ_FLAG_NO_MIRROR, (long long)ring_rows, (long long)head_row, target_dev);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int ccz_sample_record_targets(void *stream, const void *ring_dev, int64_t cap_plies, const int64_t *window_dev, const int64_t *draws_dev,
+                              int64_t batch, uint32_t flags, uint8_t *target_dev)
+{
+    if (cap_plies <= 0 || batch < 0) return fail(-1, "ccz_sample_record_targets: capacity must be positive and batch non-negative");
+    if (batch == 0) return 0;
+    if (!ring_dev || !window_dev || !draws_dev || !target_dev) return fail(-1, "ccz_sample_record_targets: null buffer");
+    if (((uintptr_t)ring_dev) & 3) return fail(-1, "ccz_sample_record_targets: the ring must be 4-byte aligned");
+    if (((uintptr_t)window_dev | (uintptr_t)draws_dev) & 7) return fail(-1, "ccz_sample_record_targets: window and draws must be 8-byte aligned");
+    if (batch > (int64_t)INT32_MAX) return fail(-1, "ccz_sample_record_targets: too many rows for one launch");
+    hipLaunchKernelGGL(k_sample_record_targets, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const uint8_t *)ring_dev,
+                       (long long)cap_plies, (const long long *)window_dev, (const long long *)draws_dev, (long long)batch,
+                       flags & CCZ_FLAG_NO_MIRROR, target_dev);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -121,6 +121,12 @@ struct Dev {
     uint32_t trankpack;     // 3 bits per piece type: major key of `legal_moves` order by the mover's type; 0 = none
     uint32_t rule_flags;    // CCZ_RULE_*: bit 0 = perpetual check loses (game end only), bit 1 = pawn moves restart the
                             // sixty-move clock and the history chain like captures
+    // ---- per-board simulation budgets (ccz_set_budgets / ccz_draw_budgets). Always allocated: "off" is a budget of INT32_MAX and
+    // target 1 on every board, so the kernels carry no second code path (and a captured graph holds nothing that changes)
+    int32_t *budget;     // [B] simulations a board may back up per move
+    int32_t *move_sims;  // [B] simulations backed up since the board's last move boundary
+    uint8_t *target;     // [B] 1: this move's pi is a policy target (0: a fast move of playout-cap randomisation)
+    uint8_t *rec_target; // [B][max_plies] `target` as it stood when the ply was recorded
 };
 __device__ __forceinline__ int plane_of(const Dev &D, int type) { return (int)((D.chanpack >> (3 * type)) & 7u); }
 __device__ __forceinline__ int type_in_plane(const Dev &D, int chan) { return (int)((D.typepack >> (3 * chan)) & 7u) + 1; }

@@ -37,6 +37,7 @@ __device__ __forceinline__ void fresh_root(const Dev &D, int b, int half)
     D.nodeB[base] = 0u;
     D.path_len[b] = 0;
     D.leaf_status[b] = CCZ_LEAF_SKIP;
+    D.move_sims[b] = 0; // a move boundary: the board's simulation budget (Dev.budget) starts over
 }
 
 // (re)initialise board b from D.root_sq[b] / the given turn+halfmove: key, chain, fresh tree, empty record
@@ -167,6 +168,8 @@ struct Prefetch {
     uint32_t rootw;
     NodeA kid;         // lane i: node 1 + i = child i of the root (the root's children always start at node 1)
     uint32_t kidw;
+    int32_t budget;    // simulations the board may back up in this move (INT32_MAX: budgets off)
+    int32_t move_sims; // ... and how many it has, as of the top of the kernel (this launch's backup is not in it)
 };
 
 // what the expand+backup phase of this launch changed at the top of the tree (the prefetched root and
@@ -196,6 +199,8 @@ __device__ __forceinline__ Prefetch prefetch_board(const Dev &D, int b, int lane
     P.rootw = D.nodeB[base];
     P.kid = D.nodeA[base + 1 + lane];
     P.kidw = D.nodeB[base + 1 + lane];
+    P.budget = D.budget[b];
+    P.move_sims = D.move_sims[b];
     return P;
 }
 
@@ -324,7 +329,9 @@ __device__ inline void select_phase(const Dev &D, int b, int lane, uint16_t *lea
     uint8_t *s_sq = sh.sq;
     uint64_t *s_chain = sh.chain;
     const BoardMeta m = P.m;
-    if (m.over) {
+    // a board whose move has used up its simulation budget selects nothing, like a finished one: no evaluator row, no simulation
+    // counted (the prefetched count predates this launch's backup: tp.active adds it)
+    if (m.over || P.move_sims + (tp.active ? 1 : 0) >= P.budget) {
         if (lane == 0) D.leaf_status[b] = CCZ_LEAF_SKIP;
         return;
     }
@@ -561,6 +568,7 @@ __device__ inline TopPatch expand_backup_phase(const Dev &D, int b, int lane, co
     }
     if (lane == 0) {
         D.stats[b].sims += 1;
+        D.move_sims[b] += 1;
         D.leaf_status[b] = CCZ_LEAF_SKIP; // consumed: a repeated call must not back the same leaf up twice
     }
     // Node.update_recursive(-leaf_value) (mcts.py:73-78,129): leaf gets -v, its parent +v, ...
@@ -1268,6 +1276,7 @@ __global__ __launch_bounds__(64) void k_finish_move(Dev D, const int32_t *forced
     BoardMeta m = D.meta[b];
     if (moves_out && lane == 0) moves_out[b] = -1;
     if (m.over) return;
+    if (lane == 0) D.move_sims[b] = 0; // a move boundary for every live board, whether or not it moves below
     const int oh = *D.half, nh = oh ^ 1; // every board moves to the other pool half (the host flips the word afterwards)
     const size_t baseOld = ((size_t)b * 2 + oh) * (size_t)D.cap;
     {   // whatever happens below, the new half holds a valid (empty) tree for this board
@@ -1309,7 +1318,7 @@ __global__ __launch_bounds__(64) void k_finish_move(Dev D, const int32_t *forced
     {
         const size_t r = (size_t)b * D.max_plies + CCZ_IDX(D, m.ply, D.max_plies);
         if (lane < 24) ((uint32_t *)(D.rec_sq + r * 96))[lane] = ((const uint32_t *)s_sq)[lane];
-        if (lane == 0) { D.rec_turn[r] = m.turn; D.rec_k[r] = (uint8_t)k; D.rec_off[r] = m.pi_used; }
+        if (lane == 0) { D.rec_turn[r] = m.turn; D.rec_k[r] = (uint8_t)k; D.rec_off[r] = m.pi_used; D.rec_target[r] = D.target[b]; }
         const size_t po = (size_t)b * D.pi_cap + m.pi_used;
         for (int i = lane; i < k; i += 64) {
             const size_t o = (size_t)b * D.pi_cap + CCZ_IDX(D, m.pi_used + (uint32_t)i, D.pi_cap);
@@ -1743,6 +1752,7 @@ __global__ __launch_bounds__(256) void k_harvest(Dev D, const long long *row_bas
 // at 2 * first + t and 2 * first + T + t: expansion needs no prefix sum and no engine state. 880 B per ply against
 // 2 x 29,768 B of dense rows: what the all-gather moves (k_expand_records rebuilds the rows on the receiving side).
 constexpr int kRecBytes = 880, kRecHdr = 96, kRecIds = 112, kRecPi = 368;
+constexpr uint8_t kRecFast = 1; // PlyHeader.flags (CCZ_REC_FAST): a fast move of playout-cap randomisation, its pi is no policy target
 struct __align__(4) PlyHeader {
     uint16_t t, T;      // ply index inside its game, plies of the game
     int8_t winner;      // 1 RED, 0 BLACK, -1 draw
@@ -1772,7 +1782,8 @@ __global__ __launch_bounds__(256) void k_harvest_records(Dev D, const long long 
             rec[tid] = v;
         } else if (tid == 24) {
             PlyHeader h;
-            h.t = (uint16_t)t; h.T = (uint16_t)T; h.winner = m.winner; h.turn = D.rec_turn[r]; h.k = (uint8_t)k; h.flags = 0;
+            h.t = (uint16_t)t; h.T = (uint16_t)T; h.winner = m.winner; h.turn = D.rec_turn[r]; h.k = (uint8_t)k;
+            h.flags = D.rec_target[r] ? 0 : kRecFast;
             h.board_id = (uint32_t)(D.board_id_base + (uint64_t)b); h.game_no = m.game_no;
             *(PlyHeader *)(rec + kRecHdr / 4) = h;
         }
@@ -1971,6 +1982,80 @@ __global__ void k_ring_retire(const uint8_t *ring, long long cap_plies, long lon
     if (nbad && bad) atomicAdd(bad, nbad);
     window[0] = tail;
     window[1] = head_new;
+}
+
+// ------------------------------------------------------------------ per-board simulation budgets
+// budgets == nullptr: budgets off (unlimited, every move a policy target). An entry below 1 counts as 1: a board always searches.
+__global__ void k_set_budgets(Dev D, int n, const int32_t *budgets, const uint8_t *targets)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= n) return;
+    int v = 0x7fffffff;
+    if (budgets) { v = budgets[b]; if (v < 1) v = 1; }
+    D.budget[b] = v;
+    D.target[b] = (budgets && targets) ? (uint8_t)(targets[b] != 0) : (uint8_t)1;
+}
+
+// Playout-cap randomisation: the move board b is about to search is a full one (n_full simulations, a policy target) with
+// probability p_full, else a fast one (n_fast, no target). The uniform is word 0xffe of the board's Philox stream for this move:
+// the Gamma draws use children 0..127 and the choice uniform 0xfff (sample_move), so the Dirichlet and move streams are untouched,
+// and the draw is a function of (seed, global board id, move counter): independent of the GPU count.
+__global__ void k_draw_budgets(Dev D, int n, int n_full, int n_fast, double p_full, int32_t *budgets_out)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= n) return;
+    double ua, ub;
+    uniform2(D.seed, D.board_id_base + (uint64_t)b, D.meta[b].move_counter, 0xffeu, 0, ua, ub);
+    const bool full = ua < p_full;
+    const int v = full ? n_full : n_fast;
+    D.budget[b] = v;
+    D.target[b] = full ? 1 : 0;
+    if (budgets_out) budgets_out[b] = v;
+}
+
+// The policy-target byte of every dense row k_expand_records writes (same row indexing, same validity rule): the sample and its
+// mirror image carry their ply's flag. A record whose game is cut writes no row there; the rows it would have stood for in a
+// buffer of whole games -- (head + mul * p + q) % ring_rows, q < mul: exactly the rows the whole games leave out -- get 0.
+__global__ void k_expand_record_targets(const uint8_t *recs, long long n_plies, uint32_t flags, long long ring_rows, long long head,
+                                        uint8_t *target)
+{
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n_plies) return;
+    const PlyHeader h = *(const PlyHeader *)(recs + (size_t)p * kRecBytes + kRecHdr);
+    const long long mul = (flags & 2u) ? 1 : 2;
+    const int t = h.t, T = h.T;
+    const long long first = p - t;
+    if (first < 0 || t >= T || first + T > n_plies || h.k > kMaxLegal) {
+        for (long long q = 0; q < mul; ++q) {
+            const long long row = head + mul * p + q;
+            target[ring_rows > 0 ? row % ring_rows : row] = 0;
+        }
+        return;
+    }
+    const uint8_t v = (h.flags & kRecFast) ? 0 : 1;
+    for (long long pass = 0; pass < mul; ++pass) {
+        const long long row = head + mul * first + (pass ? T : 0) + t;
+        target[ring_rows > 0 ? row % ring_rows : row] = v;
+    }
+}
+
+// The policy-target byte of every row k_sample_records forms (same draw -> ply map, same validity rule): 0 for a bad draw.
+__global__ void k_sample_record_targets(const uint8_t *ring, long long cap_plies, const long long *window, const long long *draws,
+                                        long long batch, uint32_t flags, uint8_t *target)
+{
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= batch) return;
+    const long long mul = (flags & 2u) ? 1 : 2;
+    const long long tail = window[0], head = window[1], u = draws[j];
+    uint8_t v = 0;
+    if (tail >= 0 && head > tail && head - tail <= cap_plies && u >= 0) {
+        const long long p = tail + (u % ((head - tail) * mul)) / mul;
+        // (the entry point has no bad-record counter: a bounds-checked build sends a stray slot to element 0 without counting it)
+        const PlyHeader h = *(const PlyHeader *)(ring + (size_t)CCZ_RING_IDX((int32_t *)nullptr, p % cap_plies, cap_plies) * kRecBytes + kRecHdr);
+        const long long first = p - h.t;
+        if (h.t < h.T && h.k <= kMaxLegal && first >= tail && first + h.T <= head) v = (h.flags & kRecFast) ? 0 : 1;
+    }
+    target[j] = v;
 }
 
 // ------------------------------------------------------------------ stateless batch rules

@@ -101,6 +101,7 @@ class SelfPlayEngine:
         self.leaf_input = torch.zeros((self.B, 17, 7, 10, 9), dtype=torch.float16, device=self.device)
         self.moves_out = torch.full((self.B,), -1, dtype=torch.int32, device=self.device)
         self._forced = torch.full((self.B,), -1, dtype=torch.int32, device=self.device)
+        self.budgets_out = torch.zeros((self.B,), dtype=torch.int32, device=self.device)   # what draw_budgets drew last
         self._temps = torch.ones((self.B,), dtype=torch.float64, device=self.device)
 
     # ------------------------------------------------------------------ lifetime
@@ -365,6 +366,36 @@ class SelfPlayEngine:
         self.gather_priors_routed(logits0, value0, logits1, value1)
         check(self.L.ccz_expand_backup_compact(self.h, self._stream(), None))
 
+    # ------------------------------------------------------------------ per-board simulation budgets (include/cczero.h ccz_set_budgets)
+    def set_budgets(self, budgets=None, targets=None):
+        """``budgets`` int32 [B] (>= 1; array or device tensor): the simulations board b searches per move from now on, however
+        many lockstep steps the host runs -- a board that has used its budget selects nothing (``LEAF_SKIP``, no row in ``eval_plan``).
+        ``targets`` uint8 [B] or None (all 1): 1 = this move's pi is a policy target; the byte is stored with the ply and comes
+        back as the record header's ``REC_FAST`` flag. ``budgets`` None: budgets off (unlimited, every move a target), the state of
+        a new engine. Device tensors are taken as they are, with no host sync; an array is copied to the device first (a blocking
+        copy of B words). Not with scout slots."""
+        if budgets is None:
+            check(self.L.ccz_set_budgets(self.h, self._stream(), None, None))
+            return
+        b = self._to_dev(budgets, torch.int32, "budgets")
+        t = None if targets is None else self._to_dev(targets, torch.uint8, "targets")
+        check(self.L.ccz_set_budgets(self.h, self._stream(), _ptr(b), _ptr(t)))
+
+    def draw_budgets(self, n_full: int, n_fast: int, p_full: float) -> torch.Tensor:
+        """Playout-cap randomisation for the move about to be searched (``ccz_draw_budgets``): every board is a full search
+        (``n_full`` simulations, policy target) with probability ``p_full``, else a fast one (``n_fast``, no target), drawn on the
+        board's own Philox stream (counter word 0xffe: the Dirichlet and move streams are untouched). Returns the budgets, device
+        int32 [B] (``self.budgets_out``, overwritten by the next draw). No host sync. Call it at a move boundary."""
+        check(self.L.ccz_draw_budgets(self.h, self._stream(), int(n_full), int(n_fast), float(p_full), _ptr(self.budgets_out)))
+        return self.budgets_out
+
+    def _to_dev(self, x, dtype, name):
+        t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x, dtype={torch.int32: np.int32, torch.uint8: np.uint8}[dtype]))
+        t = t.to(device=self.device, dtype=dtype).contiguous()
+        if tuple(t.shape) != (self.B,):
+            raise ValueError(f"{name} must have {self.B} entries")
+        return t
+
     # ------------------------------------------------------------------ once per move
     def finish_move(self, forced_moves=None, temps=None, keep_tree: bool = True) -> torch.Tensor:
         """Record pi, choose (or accept) the move, re-root, push, detect game end. Returns moves int32[B] (device)."""
@@ -607,6 +638,31 @@ def expand_records(records: torch.Tensor, flags: int = 0, plane_of_type=None, ou
         check(L.ccz_expand_records(C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), _ptr(records), P, int(flags), pot,
                                    _ptr(states), _ptr(pi), _ptr(z), ring, int(head_row) if ring else 0, _ptr(bad)))
     return states, pi, z
+
+
+def expand_record_targets(records: torch.Tensor, flags: int = 0, out=None, head_row: int = 0) -> torch.Tensor:
+    """The policy-target byte (1 = target, 0 = a ``REC_FAST`` ply) of every row :func:`expand_records` writes for ``records``
+    (``ccz_expand_record_targets``): uint8 [R], the mirror row carries its ply's flag, rows of cut games get 0. ``out``: a uint8
+    ring [N] written at (head_row + i) % N, as :func:`expand_records` writes its ``out``. Asynchronous on the current stream."""
+    L = _lib.lib()
+    if not (records.is_cuda and records.dtype == torch.uint8 and records.is_contiguous()):
+        raise ValueError("records must be a contiguous uint8 device tensor")
+    if records.numel() % _lib.REC_BYTES:
+        raise ValueError("records must hold whole 880-byte ply records")
+    P = records.numel() // _lib.REC_BYTES
+    dev = records.device
+    if out is None:
+        target = torch.zeros((rows_of_records(P, flags),), dtype=torch.uint8, device=dev)
+        ring = 0
+    else:
+        target = out
+        ring = int(target.shape[0])
+        if not (target.is_contiguous() and target.dtype == torch.uint8 and target.dim() == 1 and target.device == dev):
+            raise ValueError("out must be a contiguous uint8 [N] tensor on the records' device")
+    with torch.cuda.device(dev):
+        check(L.ccz_expand_record_targets(C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), _ptr(records), P, int(flags), ring,
+                                          int(head_row) if ring else 0, _ptr(target)))
+    return target
 
 
 # ---------------------------------------------------------------------- stateless batch rules

@@ -660,7 +660,9 @@ class TupleGatherer(_FusedGather):
 
 
 class ReplayBuffer:
-    """Fixed-capacity ring of training rows resident in HBM (sized for 288 GB: 1M rows = 30 GB)."""
+    """Fixed-capacity ring of training rows resident in HBM (sized for 288 GB: 1M rows = 30 GB). A parallel uint8 ring
+    (``targets``) holds every row's policy-target byte: 0 for the fast plies of playout-cap randomisation (``REC_FAST`` records),
+    1 for everything else, rows appended without a flag included."""
 
     def __init__(self, capacity_rows: int, device):
         d = torch.device(device)
@@ -668,18 +670,25 @@ class ReplayBuffer:
         self.states = torch.zeros((self.cap, 17, 7, 10, 9), dtype=torch.float16, device=d)
         self.pi = torch.zeros((self.cap, NMOVES), dtype=torch.float32, device=d)
         self.z = torch.zeros((self.cap,), dtype=torch.float32, device=d)
+        self.targets = torch.ones((self.cap,), dtype=torch.uint8, device=d)
         self.size = 0
         self.head = 0
         self.total = 0
 
-    def append(self, states, pi, z):
+    def append(self, states, pi, z, targets=None):
+        """``targets`` uint8 [n] or None (every row a policy target)."""
         n = int(states.shape[0])
         if n == 0:
             return
+        if targets is None:
+            targets = torch.ones((n,), dtype=torch.uint8, device=self.targets.device)
         if n > self.cap:
-            states, pi, z = states[-self.cap:], pi[-self.cap:], z[-self.cap:]
+            states, pi, z, targets = states[-self.cap:], pi[-self.cap:], z[-self.cap:], targets[-self.cap:]
             n = self.cap
         first = min(n, self.cap - self.head)
+        self.targets[self.head:self.head + first].copy_(targets[:first])
+        if n > first:
+            self.targets[:n - first].copy_(targets[first:])
         self.states[self.head:self.head + first].copy_(states[:first])
         self.pi[self.head:self.head + first].copy_(pi[:first])
         self.z[self.head:self.head + first].copy_(z[:first])
@@ -695,7 +704,7 @@ class ReplayBuffer:
     def append_records(self, records: torch.Tensor, flags: int = 0, plane_of_type=None, bad=None) -> int:
         """Expand compact ply records (uint8 [P, 880], whole games; :class:`RecordGatherer`'s output) straight INTO the ring:
         ``ccz_expand_records`` writes the dense rows at (head + i) % capacity, no intermediate copy. Returns the rows added."""
-        from .engine import expand_records, game_aligned_chunks, rows_of_records
+        from .engine import expand_record_targets, expand_records, game_aligned_chunks, rows_of_records
         mul = rows_of_records(1, flags)
         if rows_of_records(int(records.shape[0]), flags) > self.cap:  # more than the ring holds: game by game, the ring wraps
             if self.cap < mul:
@@ -708,14 +717,19 @@ class ReplayBuffer:
         if n > self.cap:
             raise ValueError(f"one game of {n} rows exceeds the replay ring ({self.cap} rows)")
         rec = records if records.device == self.states.device else records.to(self.states.device, non_blocking=True)
-        expand_records(rec.contiguous(), flags, plane_of_type, out=(self.states, self.pi, self.z), head_row=self.head, bad=bad)
+        rec = rec.contiguous()
+        expand_records(rec, flags, plane_of_type, out=(self.states, self.pi, self.z), head_row=self.head, bad=bad)
+        expand_record_targets(rec, flags, out=self.targets, head_row=self.head)
         self.head = (self.head + n) % self.cap
         self.size = min(self.cap, self.size + n)
         self.total += n
         return n
 
-    def sample(self, batch: int, generator=None):
+    def sample(self, batch: int, generator=None, targets: bool = False):
+        """``targets``: also return the rows' policy-target bytes (uint8 [batch]) as a fourth tensor."""
         idx = torch.randint(0, self.size, (batch,), device=self.states.device, generator=generator)
+        if targets:
+            return self.states[idx], self.pi[idx], self.z[idx], self.targets[idx]
         return self.states[idx], self.pi[idx], self.z[idx]
 
 
@@ -815,10 +829,12 @@ class RecordReplayBuffer:
         self.total += P * self.mul
         return P * self.mul
 
-    def sample_at(self, draws: torch.Tensor, bad=None):
+    def sample_at(self, draws: torch.Tensor, bad=None, targets: bool = False):
         """Rows of the given draws (int64 [batch] on the ring's device, non-negative): draw ``u`` is row ``u % live`` of the window,
         ``live = (head - tail) x mul`` read on the device; row ``r`` is ply ``tail + r // mul``, pass ``r % mul`` (1 = mirror image).
-        Returns ``(states fp16 [batch,17,7,10,9], pi f32 [batch,2086], z f32 [batch])`` as :meth:`ReplayBuffer.sample` does."""
+        Returns ``(states fp16 [batch,17,7,10,9], pi f32 [batch,2086], z f32 [batch])`` as :meth:`ReplayBuffer.sample` does.
+        ``targets``: a fourth tensor, uint8 [batch] -- 1 where the row is a policy target, 0 for a ``REC_FAST`` ply (a fast move
+        of playout-cap randomisation) and for a bad draw (``ccz_sample_record_targets``)."""
         from . import _lib
         from .engine import _ptr
         if self.head == 0:
@@ -834,16 +850,21 @@ class RecordReplayBuffer:
             _lib.check(_lib.lib().ccz_sample_records(self._stream(), _ptr(self.records), self.cap, _ptr(self._window), _ptr(draws), n,
                                                      self.flags, self._pot(), _ptr(states), _ptr(pi), _ptr(z),
                                                      _ptr(self.bad if bad is None else bad)))
+            if targets:
+                tg = torch.empty((n,), dtype=torch.uint8, device=d)
+                _lib.check(_lib.lib().ccz_sample_record_targets(self._stream(), _ptr(self.records), self.cap, _ptr(self._window), _ptr(draws), n,
+                                                                self.flags, _ptr(tg)))
+                return states, pi, z, tg
         return states, pi, z
 
-    def sample(self, batch: int, generator=None):
+    def sample(self, batch: int, generator=None, targets: bool = False):
         """A uniform minibatch over the live rows, mirror images included, without a host sync: the draws are
         ``torch.randint(0, 2**62)`` on the device and the kernel reduces them modulo the live row count, which only the device
         knows. The modulo bias is below ``live / 2**62`` < 2**-28 for any ring that fits in HBM (live < 2**34 rows)."""
         if self.head == 0:
             raise ValueError("the replay ring is empty: nothing was ever appended")
         draws = torch.randint(0, 2 ** 62, (int(batch),), device=self.records.device, dtype=torch.int64, generator=generator)
-        return self.sample_at(draws)
+        return self.sample_at(draws, targets=targets)
 
     def window(self):
         """``(tail, head)`` in logical plies, as the device has them after everything queued so far (syncs)."""

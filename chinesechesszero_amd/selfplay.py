@@ -216,12 +216,28 @@ class BatchedSelfPlay:
 
     def __init__(self, evaluator, n_boards: int, n_playout: int = 400, c_puct: float = C_PUCT, eps: float = EPS,
                  alpha: float = ALPHA, temp: float = 1.0, seed: int = 0, board_id_base: int = 0, device: int = 0,
-                 sampling: str = "device", use_graph: bool = False, version_fn=None, **engine_kw):
-        """``version_fn() -> hashable``: what tells the evaluation cache (and a captured hipGraph) that the evaluator's weights
+                 sampling: str = "device", use_graph: bool = False, version_fn=None, playout_cap=None, **engine_kw):
+        """``playout_cap`` = ``(n_fast, p_full)``: playout-cap randomisation -- every move of every board is a full search of
+        ``n_playout`` simulations with probability ``p_full``, else a fast one of ``n_fast``; fast plies carry ``REC_FAST`` in their
+        record header so that a trainer can keep them out of the policy loss (``engine.draw_budgets``). The loop still runs
+        ``n_playout`` lockstep steps per move: a board that has used its budget selects nothing for the rest of them, and on the
+        planned boundary (``eval_cache_log2`` > 0 with a planning evaluator) it gets no evaluator row; an evaluator without a plan
+        still computes all B rows. The budgets are drawn by :meth:`advance` (so by :meth:`search` and :meth:`run_move`) at a move's
+        first simulation; :meth:`simulate` draws nothing and searches with the budgets the engine holds.
+        None (default): every board searches ``n_playout`` simulations, as ever.
+        ``version_fn() -> hashable``: what tells the evaluation cache (and a captured hipGraph) that the evaluator's weights
         changed; default: ``weights_version`` of the evaluator's owner. An evaluator that accepts a plan but exposes neither is
         refused: its cached evaluations could never be invalidated."""
         if sampling not in ("device", "numpy"):
             raise ValueError("sampling must be 'device' (Philox on the GPU) or 'numpy' (reference-exact host RNG)")
+        self.playout_cap = None
+        if playout_cap is not None:
+            n_fast, p_full = playout_cap
+            if int(n_fast) != n_fast or not 1 <= int(n_fast) <= int(n_playout):
+                raise ValueError(f"playout_cap: n_fast must be an integer in 1..n_playout (got {n_fast})")
+            if not 0.0 <= float(p_full) <= 1.0:
+                raise ValueError(f"playout_cap: p_full must be in [0, 1] (got {p_full})")
+            self.playout_cap = (int(n_fast), float(p_full))
         self.evaluator = evaluator
         self.engine = SelfPlayEngine(n_boards, n_playout=n_playout, c_puct=c_puct, eps=eps, alpha=alpha, temp=temp,
                                      seed=seed, board_id_base=board_id_base, device=device, **engine_kw)
@@ -264,7 +280,7 @@ class BatchedSelfPlay:
             self._cache_version = v
         return self.evaluator(leaf, plan=e.eval_plan())
 
-    # one lockstep simulation of every board
+    # one lockstep simulation of every board (outside advance's move bookkeeping: no playout-cap draw happens here)
     def simulate(self):
         e = self.engine
         leaf = e.select_leaves()
@@ -294,6 +310,8 @@ class BatchedSelfPlay:
             i = self._sim
             last = i + 1 == n
             if self._leaf is None:
+                if self.playout_cap is not None and i == 0:   # the move's budgets, after a harvest restarted boards
+                    e.draw_budgets(n, *self.playout_cap)
                 self._leaf = e.select_leaves()
                 if self.use_graph and self._graph is None and not self.planned:
                     self._graph = GraphedStep(e, self.evaluator, version_fn=self.version_fn)

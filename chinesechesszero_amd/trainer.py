@@ -31,7 +31,10 @@ class Trainer:
         self.scaler = torch.amp.GradScaler("cuda", enabled=self.use_amp and amp_dtype == "fp16")
         self.steps = 0
 
-    def step(self, states: torch.Tensor, pi: torch.Tensor, z: torch.Tensor, sync: bool = True) -> dict:
+    def step(self, states: torch.Tensor, pi: torch.Tensor, z: torch.Tensor, sync: bool = True, policy_mask=None) -> dict:
+        """``policy_mask`` [batch] of 0 / 1 (any dtype) or None: rows with 0 (the fast plies of playout-cap randomisation) stay out
+        of the policy term, which becomes ``-sum_i m_i sum_a t_ia logp_ia / max(1, sum_i m_i)``; the value loss and the entropy
+        report take every row. None: the unmasked mean, today's code path."""
         self.pvn._require_current_fp32("Trainer.step")   # a rank that received only the inference copy holds OLD fp32 weights
         self.net.train()
         dev = next(self.net.parameters()).device
@@ -45,7 +48,11 @@ class Trainer:
             log_act_probs, value = self.net(states)
             value_loss = F.mse_loss(value.flatten().float(), z)
             target = (1 - self.eps) * pi + self.eps / pi.size(1) if self.eps > 0 else pi
-            policy_loss = -torch.mean(torch.sum(target * log_act_probs.float(), dim=1))
+            if policy_mask is None:
+                policy_loss = -torch.mean(torch.sum(target * log_act_probs.float(), dim=1))
+            else:
+                m = policy_mask.to(dev).float().flatten()
+                policy_loss = -torch.sum(m * torch.sum(target * log_act_probs.float(), dim=1)) / torch.clamp(m.sum(), min=1.0)
             loss = value_loss + policy_loss
         self.scaler.scale(loss).backward()
         self.scaler.unscale_(self.opt)

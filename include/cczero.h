@@ -87,7 +87,7 @@ extern "C" {
 #define CCZ_LEAF_EXPAND 0 /* non-terminal: children are created from the evaluator's priors */
 #define CCZ_LEAF_DRAW 1   /* game over and is_tie(): leaf value 0.0   (mcts.py:120-122)   */
 #define CCZ_LEAF_LOSS 2   /* side to move has no legal move: leaf value -1.0 (mcts.py:123-126) */
-#define CCZ_LEAF_NONE 3   /* no pending leaf: board finished, leaf already backed up, or nothing selected yet */
+#define CCZ_LEAF_NONE 3   /* no pending leaf: board finished, simulation budget used up, leaf already backed up, or nothing selected yet */
 
 typedef struct ccz_engine ccz_engine;
 
@@ -327,6 +327,29 @@ int ccz_eval_plan_routed(ccz_engine *e, void *stream, int32_t *miss_rows_dev, in
 int ccz_gather_priors_routed(ccz_engine *e, void *stream, const void *logits0_dev, const void *logits1_dev, int32_t logits_f16,
                              const float *value0_dev, const float *value1_dev);
 
+/* ---- per-board simulation budgets (additive to ABI 8) ---------------------------------------------------------------------------
+ * Every board counts the simulations it has backed up since its last move boundary (ccz_finish_move on a live board, ccz_reset,
+ * ccz_set_position(s), a harvest restart, ccz_reset_tree). With budgets on, a board whose count has reached its budget selects
+ * nothing more: CCZ_LEAF_NONE, no evaluator row from ccz_eval_plan[_routed], no simulation counted -- exactly as a finished board.
+ * A board therefore searches exactly budget[b] simulations per move however many lockstep steps the host runs, and its tree is,
+ * bit for bit, the tree of an engine that runs budget[b] steps. Both calls are asynchronous on `stream` (no host sync) and take
+ * effect with the next ccz_select_leaves / ccz_step*; both fail while scout slots are active, and ccz_set_scouts fails while
+ * budgets are on. After ccz_create budgets are off.
+ *   ccz_set_budgets: budgets_dev int32 [B] (an entry below 1 counts as 1), targets_dev uint8 [B] or NULL (all 1): 1 = this move's
+ *     pi is a policy target. budgets_dev == NULL: budgets off (unlimited, every move a target; targets_dev is ignored).
+ *   ccz_draw_budgets: playout-cap randomisation. Board b draws ua of uniform2(seed, board_id_base + b, its move counter, child
+ *     0xffe, draw 0) -- the sampler's Philox stream, a counter word neither the Gamma draws (children 0..127) nor the choice uniform
+ *     (0xfff) use: Dirichlet noise and moves are what they are without the call, and a board's budgets do not depend on the GPU
+ *     count. ua < p_full: budget n_full, target 1; else budget n_fast, target 0. budgets_out_dev int32 [B] (may be NULL) receives
+ *     the budgets. n_full, n_fast >= 1, p_full in [0, 1]. Call it at a move boundary (before the move's first selection).
+ * ccz_finish_move stores the board's target byte with the ply; ccz_harvest_records writes it into the record header as
+ * flags = target ? 0 : CCZ_REC_FAST. The dense-row calls (ccz_harvest, ccz_expand_records, ccz_sample_records) form a row for
+ * every ply as before (a fast ply's pi is still a distribution, and its z a value target); the two calls below hand the flag
+ * to the consumer, row-aligned with what their siblings write. */
+#define CCZ_REC_FAST 1 /* record header flags: the ply was a fast move of playout-cap randomisation -- keep it out of the policy loss */
+int ccz_set_budgets(ccz_engine *e, void *stream, const int32_t *budgets_dev, const uint8_t *targets_dev);
+int ccz_draw_budgets(ccz_engine *e, void *stream, int32_t n_full, int32_t n_fast, double p_full, int32_t *budgets_out_dev);
+
 /* ---- once per move ------------------------------------------------------------------------ */
 /* Replaces MCTS.get_move_probs' tail (mcts.py:162-166), MCTS_AI.get_action's choice
  * (mcts.py:216-224), MCTS.update_with_move (mcts.py:168-178) and the per-move part of
@@ -413,7 +436,7 @@ int ccz_harvest(ccz_engine *e, void *stream, void *states_f16_dev, float *pi_dev
 /* One fixed-size record per PLY of a finished game, plies of a game contiguous and in order:
  *   bytes   0..89   position before the move (piece codes, square = file + 9*rank), 90..95 zero
  *   bytes  96..111  header: uint16 t (ply index), uint16 T (plies of the game), int8 winner (1 RED, 0 BLACK, -1 draw),
- *                   uint8 turn (side to move), uint8 k (entries of pi), uint8 flags (0), uint32 board_id (global),
+ *                   uint8 turn (side to move), uint8 k (entries of pi), uint8 flags (CCZ_REC_FAST or 0), uint32 board_id (global),
  *                   uint32 game_no
  *   bytes 112..367  uint16 ids[128]   move ids of the root's children (mcts.py:162), zero-padded
  *   bytes 368..879  float  pi[128]    visit distribution of the move (mcts.py:163-166), zero-padded
@@ -460,6 +483,17 @@ int ccz_ring_retire(void *stream, const void *ring_dev, int64_t cap_plies, int64
 int ccz_sample_records(void *stream, const void *ring_dev, int64_t cap_plies, const int64_t *window_dev,
                        const int64_t *draws_dev, int64_t batch, uint32_t flags, const uint8_t *plane_of_type_host,
                        void *states_f16_dev, float *pi_dev, float *z_dev, int32_t *bad_records_dev);
+
+/* The policy-target byte (1 = target, 0 = a CCZ_REC_FAST ply) of the rows the two calls above write; stateless, asynchronous.
+ * ccz_expand_record_targets: target_dev uint8, one byte per row of ccz_expand_records with the same records_dev / n_plies / flags
+ *   (CCZ_FLAG_NO_MIRROR) / ring_rows / head_row: the sample and its mirror image carry their ply's flag. The rows of a buffer of
+ *   whole games that a cut game leaves unwritten there -- (head_row + mul * p + q) % ring_rows for its records p, q < mul -- get 0.
+ * ccz_sample_record_targets: target_dev uint8 [batch], one byte per drawn row of ccz_sample_records with the same ring_dev /
+ *   cap_plies / window_dev / draws_dev / flags; a draw that ccz_sample_records counts as bad gives 0. */
+int ccz_expand_record_targets(void *stream, const void *records_dev, int64_t n_plies, uint32_t flags, int64_t ring_rows, int64_t head_row,
+                              uint8_t *target_dev);
+int ccz_sample_record_targets(void *stream, const void *ring_dev, int64_t cap_plies, const int64_t *window_dev, const int64_t *draws_dev,
+                              int64_t batch, uint32_t flags, uint8_t *target_dev);
 
 int ccz_get_stats(ccz_engine *e, void *stream, ccz_stats *out); /* syncs */
 
