@@ -161,7 +161,7 @@ def test_convolution_group_of_16_rows(boards):
         E.assert_same(_g16_host(y, boards), _want(c, True, True), f"boards {boards}, {name}, over the residual", NAMES)
 
 
-@pytest.mark.parametrize("live,n_parts", [(1, 1), (16, 2), (17, 1), (100, 3), (160, 4)])
+@pytest.mark.parametrize("live,n_parts", [(1, 1), (16, 2), (17, 1), (100, 3), (160, 4), (100, 6), (160, 6)])
 def test_convolution_group_of_16_live_rows(live, n_parts):
     """ccz_conv3x3_c256_f16_live: the first `live` boards (a device value) cut into n_parts ranges of whole groups; together the
     parts compute exactly the groups that hold live boards -- against float64 -- and the rows beyond them stay NaN."""
@@ -369,7 +369,7 @@ def test_heads_in_the_last_layers_epilogue(boards, live, n_parts):
 
 # ------------------------------------------------------------------ FC
 FC_FORMS = (("128 x 128 tiles", 2), ("256 x 144 tiles", 4), ("selected", 0))      # ccz_fc_f16's relu bits 1 / 2; M <= 16 selects k_fc_skinny_f16
-FC_MS = [1, 5, 11, 16, 17, 128, 129, 300, 2048, 4096]
+FC_MS = [1, 5, 11, 16, 17, 128, 129, 300, 2048, 4096, 4097]
 #           K     N    relu lda   ldc
 FC_SHAPES = {
     "policy": (1536, 2086, 0, 1536, 2096),      # N = 2 (mod 4): the last dword of a row of the skinny kernel is half a store
@@ -478,7 +478,7 @@ def test_value_output_nearest_candidate(M):
 
 
 # ------------------------------------------------------------------ ccz_bias_act_f16
-@pytest.mark.parametrize("rows,channels", [(630, 64), (90 * 257, 256)])
+@pytest.mark.parametrize("rows,channels", [(630, 64), (90 * 257, 256), (90 * 400, 256)])
 def test_bias_act_bit_for_bit(rows, channels):
     """relu(rn16(rn16(y + b) + r)) on arbitrary finite fp16 operands -- every exponent, subnormals, sums that overflow to inf --
     with and without a residual. Pure fp16 adds: no grid is needed."""
