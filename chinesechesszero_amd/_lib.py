@@ -27,6 +27,7 @@ HEAD_POL_STRIDE, HEAD_VAL_STRIDE = 1536, 640  # CCZ_HEAD_*_STRIDE: fp16 elements
 ABI_VERSION = 8
 CONV_RELU, CONV_DESCENDING, CONV_FORCE_SMALL, CONV_FORCE_TILE, CONV_G16, CONV_G16_EDGE_TILES = 1, 2, 16, 32, 64, 128  # CCZ_CONV_* flag bits
 CONV_G16_ONE_LAUNCH = 512  # CCZ_CONV_G16_ONE_LAUNCH
+CONV_G16_QUAD = 1 << 16    # CCZ_CONV_G16_QUAD
 RULE_PERPETUAL_CHECK = 1
 RULE_PAWN_MOVE_RESETS_CLOCK = 2
 FLAG_REFERENCE_QUIRKS = 1

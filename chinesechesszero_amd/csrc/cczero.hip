@@ -1087,8 +1087,8 @@ static int conv3x3_launch(const char *who, void *stream, const void *x_dev, cons
     if (x_dev == y_dev) return fail(-1, "%s: the output may alias the residual but not the input", who);
     if (n_pixels == 0) return 0;
     if (relu & CCZ_CONV_G16) { // rows in the group-of-16 layout: whole-rank tiles, off-board taps skipped (cczero_conv_g16.h)
-        if (relu & (256 | (0xfff << 16))) // the persistent form's flag and workgroup count (round 6; removed in ABI 8): refused, not ignored
-            return fail(-1, "%s: flag 256 / bits 16..27 were CCZ_CONV_G16_PERSISTENT, retired in ABI 8", who);
+        if (relu & (256 | (0xffe << 16))) // the persistent form's flag and workgroup count (round 6; removed in ABI 8): refused, not ignored
+            return fail(-1, "%s: flag 256 / bits 17..27 were CCZ_CONV_G16_PERSISTENT, retired in ABI 8", who); // (bit 16 is CCZ_CONV_G16_QUAD now)
         if (n_pixels % 1440) return fail(-1, "%s: CCZ_CONV_G16 needs a multiple of 16 boards", who);
         const int groups = (int)(n_pixels / 1440);
         const int fl = relu & 3;
@@ -1122,12 +1122,16 @@ static int conv3x3_launch(const char *who, void *stream, const void *x_dev, cons
             HIP_TRY(hipGetLastError());
             return 0;
         }
+        // CCZ_CONV_G16_QUAD: the middle slots as four-rank x 128-channel tiles (cczero_conv_g16.h g5q_tile) -- as many, as large, half the weight stream
+        const bool quad = (relu & CCZ_CONV_G16_QUAD) != 0;
         if (relu & CCZ_CONV_G16_ONE_LAUNCH) { // both tile classes in one launch (cczero_conv_g16e.h k_conv3x3_g16_one)
-            CCZ_G16(k_conv3x3_g16_one, groups * 4 + 2 * ((groups + 1) / 2), s, fl);
+            if (quad) CCZ_G16(k_conv3x3_g16_one_quad, groups * 4 + 2 * ((groups + 1) / 2), s, fl);
+            else CCZ_G16(k_conv3x3_g16_one, groups * 4 + 2 * ((groups + 1) / 2), s, fl);
             HIP_TRY(hipGetLastError());
             return 0;
         }
-        CCZ_G16(k_conv3x3_g16, groups * 4, s, fl | 4);   // (edge launch first: measured the same, 194.4 / 194.3 k against 194.8 / 194.0 k sims/s)
+        if (quad) CCZ_G16(k_conv3x3_g16_quad, groups * 4, s, fl);
+        else CCZ_G16(k_conv3x3_g16, groups * 4, s, fl | 4);   // (edge launch first: measured the same, 194.4 / 194.3 k against 194.8 / 194.0 k sims/s)
         HIP_TRY(hipGetLastError());
         CCZ_G16(k_conv3x3_g16_edge, 2 * ((groups + 1) / 2), s, fl);
         HIP_TRY(hipGetLastError());

@@ -39,6 +39,11 @@
 //     wrapped around to chunk 0 and re-read valid memory: 40 KB of slab + 48 KB of weights per tile and 4 KB per chunk, 120 KB
 //     on top of the 1,440 KB a middle tile needs (8.3 %; an edge-pair tile 11 %; a stem tile more than its useful stream), and
 //     the epilogue waited for them to land. Measured: profiles/r08_tile_stream_ab.json, CHANGELOG.
+//   * QUAD middle tiles (CCZ_CONV_G16_QUAD; g5q_tile below; what the evaluator runs on ranks 1..8 from 4096 boards on): the same wave body
+//     on 4 ranks x 128 output channels -- as many tiles of as many rows x channels and MFMAs, but a tile streams half the layer's
+//     weights: 1,032 instead of 1,475 KB of LDS-DMA per tile, 16 instead of 23 DMA instructions per thread and chunk. Same bits.
+//     Measured (profiles/r09_quad_tiles_ab.json, CHANGELOG): 200.2-200.8 k -> 202.8-203.3 k sims/s. The two-rank tile stays for the
+//     five-tile mode, the stem and the heads layer (its 1x1 epilogue needs all 256 channels of a row in one workgroup).
 //   * XCD-aware tile order: workgroup b runs on XCD b % 8 and the five tiles of a group read each other's ranks as halo, so XCD x
 //     takes the x-th contiguous eighth of the tiles (HBM traffic per launch 398 MB -> 283-288 MB = algorithmic).
 //
@@ -69,18 +74,32 @@ constexpr int kG5Dump = kG5AOff + 2 * kG5SlabBytes;        // 8 x 1 KB: where a 
 constexpr int kG5Lds = kG5Dump + 8 * 1024;                 // 163,840 B = all of it
 constexpr int kG5ERow = 528;                               // epilogue image: bytes per row (512 + pad)
 static_assert(kG5Rows * kG5ERow <= kG5Dump, "epilogue image must fit the operand buffers");
+// the QUAD middle tile (g5q_tile below): 4 ranks x 128 output channels -- weight half-tiles of 8 KB, slabs of 6 ranks
+constexpr int kG5QRows = 576;                              // rows per tile (36 cells x 16 boards)
+constexpr int kG5QSlabRows = 864;                          // 54 cells
+constexpr int kG5QSlabBytes = kG5QSlabRows * 64;           // 55,296 B per 32-channel chunk: six staging passes of 8 KB + one of 6 KB
+constexpr int kG5QWBytes = 128 * 64;                       // one half-step of weights: 128 output channels
+constexpr int kG5QAOff = kG5Ring * kG5QWBytes;             // LDS: [weight ring | slab 0 | slab 1 | dump]
+constexpr int kG5QDump = kG5QAOff + 2 * kG5QSlabBytes;     // 8 x 1 KB: where waves 6-7 aim staging pass 6, which has no piece for them
+constexpr int kG5QLds = kG5QDump + 8 * 1024;
+constexpr int kG5QERow = 272;                              // epilogue image: bytes per row (256 + pad)
+static_assert(kG5QLds == 159744 && kG5QLds <= kG5Lds, "quad tile: ring + two slabs + dump must fit the workgroup's LDS");
+static_assert(kG5QRows * kG5QERow == 156672 && kG5QRows * kG5QERow <= kG5QLds,
+              "quad tile: the epilogue image covers the operand buffers AND most of the dump area (free once every DMA has landed)");
 
 struct G5Ctx {
     unsigned char *lds;
     const _Float16 *X, *W;   // uniform bases of the two buffer descriptors: every DMA is descriptor + 32-bit byte offset (one VGPR) + scalar offset
     unsigned xbytes, wbytes; // SCALAR: bytes of the launch part's activation rows / of this layer's packed weights (the descriptors' num_records)
-    unsigned xbytes4;        // SCALAR: xbytes for waves 0-3, 0 for waves 4-7 -- staging pass 4 has 256 pieces, theirs fetch nothing
+    unsigned xbytes_part;        // SCALAR: xbytes for waves 0-3, 0 for waves 4-7 -- staging pass 4 has 256 pieces, theirs fetch nothing
     unsigned xoff[5];        // per staging pass: byte offset of this thread's 16-byte source in X (chunk 0), row clamped into the tensor
+                             // (quad tile: xoff[0] alone -- nothing is clamped, pass `it` is + it * xstep in the scalar offset)
+    unsigned xstep, whalf;   // SCALAR (quad tile): bytes between two staging passes (128 rows); byte offset of the tile's channel half in a half-tile
     unsigned woff;           // byte offset of this thread's 16-byte weight source in W (row pass 0, tap 0, chunk 0)
     int zo[2], zd[2];        // SCALAR: where this wave's two zero stores go for slab 0, and the step to slab 1 (0 for the dump area)
     int wave_dst;            // w * 1024
     int lane16;              // (lane & 63) * 16
-    int wave_dst4, wave_step4; // SCALAR: LDS offset of this wave's piece of staging pass 4 in slab 0 and the step to slab 1 (waves 4-7: their
+    int wave_dst_part, wave_step_part; // SCALAR: LDS offset of this wave's piece of staging pass 4 in slab 0 and the step to slab 1 (waves 4-7: their
                              // 1 KB of the dump area, step 0 -- the zeros of their out-of-range loads land where nothing is read)
     int a_off;               // weight fragment offset inside a ring slot (tile 0; tile i: + 1024 i)
     int vb[2];               // this lane's pixel-fragment base in slab 0 / 1 (cell 0 of the wave's rank at tap offset 0 = + 9 * 1024)
@@ -99,6 +118,16 @@ static_assert(g5_vmcnt(0) == 4 && g5_vmcnt(1) == 5 && g5_vmcnt(2) == 6 && g5_vmc
               g5_vmcnt(6) == 5 && g5_vmcnt(7) == 4 && g5_vmcnt(8) == 4, "g5_vmcnt table");
 static_assert(g5_dma(0) == 2 && g5_dma(1) == 3 && g5_dma(2) == 3 && g5_dma(3) == 3 && g5_dma(4) == 3 && g5_dma(5) == 3 && g5_dma(6) == 2 &&
               g5_dma(7) == 2 && g5_dma(8) == 2, "23 DMA loads per chunk and thread: 5 slab pieces + 9 x 2 weight pieces");
+// The quad tile: ONE weight piece per half-step (8 KB over 512 threads) and seven slab pieces per chunk. The next chunk's slab is first
+// read in half-step 8 (the refill for dy = -1), published by the barrier of half-step 7, whose wait leaves the loads of half-steps 6
+// and 7 in flight: the pieces go into half-steps 0..5 -- passes 0 and 1 in half-step 0, pass t + 1 in half-step t.
+__host__ __device__ constexpr int g5q_nslab(int t) { return t == 0 ? 2 : t <= 5 ? 1 : 0; }
+__host__ __device__ constexpr int g5q_dma(int t) { return 1 + g5q_nslab(t); }
+__host__ __device__ constexpr int g5q_vmcnt(int t) { return g5q_dma(t) + g5q_dma((t + 8) % 9); }
+static_assert(g5q_vmcnt(0) == 4 && g5q_vmcnt(1) == 5 && g5q_vmcnt(2) == 4 && g5q_vmcnt(3) == 4 && g5q_vmcnt(4) == 4 && g5q_vmcnt(5) == 4 &&
+              g5q_vmcnt(6) == 3 && g5q_vmcnt(7) == 2 && g5q_vmcnt(8) == 2, "g5q_vmcnt table");
+static_assert(g5q_dma(0) == 3 && g5q_dma(1) == 2 && g5q_dma(2) == 2 && g5q_dma(3) == 2 && g5q_dma(4) == 2 && g5q_dma(5) == 2 && g5q_dma(6) == 1 &&
+              g5q_dma(7) == 1 && g5q_dma(8) == 1, "16 DMA loads per chunk and thread: 7 slab pieces + 9 weight pieces");
 
 template <int T, int N> __host__ __device__ constexpr bool g5_on_board() // is tap T of the cell with file N on the board (dx only)
 {
@@ -122,13 +151,14 @@ __device__ __forceinline__ void g5_zero_ranks(const G5Ctx &c, int buf)
 }
 
 // One half-step = tap T of a 32-channel chunk; J = its index inside the unrolled pair of chunks (parity of the A register
-// set = J & 1, slab buffer = J / 9).
-template <int J>
+// set = J & 1, slab buffer = J / 9). Q: the quad tile's staging (8 KB ring slots, slabs of six ranks, g5q_dma) around the SAME cells.
+template <int J, bool Q = false>
 __device__ __forceinline__ void g5_step(const G5Ctx &c, cv_f32x4 (&acc)[4][9], int chunk, int &ring_rd, int &ring_wr,
                                          cv_half8 (&a0)[4], cv_half8 (&a1)[4], cv_half8 (&b)[9])
 {
     constexpr int T = J % 9, BUF = J / 9;
     constexpr int Tn = (T + 1) % 9, BUFn = (T == 8) ? 1 - BUF : BUF;
+    constexpr int kWB = Q ? kG5QWBytes : kG5WBytes, kAOff = Q ? kG5QAOff : kG5AOff, kSlab = Q ? kG5QSlabBytes : kG5SlabBytes;
     cv_half8 (&acur)[4] = (J & 1) ? a1 : a0;
     cv_half8 (&anxt)[4] = (J & 1) ? a0 : a1;
     unsigned char *const lds = c.lds;
@@ -159,15 +189,28 @@ __device__ __forceinline__ void g5_step(const G5Ctx &c, cv_f32x4 (&acc)[4][9], i
     // descriptor then has zero records, the range check fails and nothing is fetched (cv_blds16)
     const int chunk2 = chunk + (T + kG5Ahead >= 9 ? 1 : 0);
     G5_CELLS(0, 1)
-    if constexpr (g5_dma(T) > 2) { // the next chunk's slab: 5 pieces per thread, in taps 1..5
+    if constexpr (Q && g5q_nslab(T) > 0) { // the next chunk's slab: 7 pieces per thread, passes 0, 1 | 2 | .. | 6 in taps 0 | 1 | .. | 5
+        constexpr int pass = T == 0 ? 0 : T + 1;
+        const unsigned so = (unsigned)((chunk + 1) * 64);
+        const unsigned live = chunk < c.cmask ? (pass < 6 ? c.xbytes : c.xbytes_part) : 0u;
+        cv_blds16(c.X, live, c.xoff[0], so + pass * c.xstep,
+                  lds + (pass < 6 ? kAOff + (1 - BUF) * kSlab + pass * 8192 + c.wave_dst : c.wave_dst_part + (1 - BUF) * c.wave_step_part));
+        if constexpr (g5q_nslab(T) > 1) cv_blds16(c.X, live, c.xoff[0], so + (pass + 1) * c.xstep, lds + kAOff + (1 - BUF) * kSlab + ((pass + 1) * 8192 + c.wave_dst));
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    if constexpr (!Q && g5_dma(T) > 2) { // the next chunk's slab: 5 pieces per thread, in taps 1..5
         constexpr int pass = T - 1;
-        const unsigned live = pass < 4 ? c.xbytes : c.xbytes4;
+        const unsigned live = pass < 4 ? c.xbytes : c.xbytes_part;
         cv_blds16(c.X, chunk < c.cmask ? live : 0u, c.xoff[pass], (unsigned)((chunk + 1) * 64),
-                  lds + (pass < 4 ? kG5AOff + (1 - BUF) * kG5SlabBytes + pass * 8192 + c.wave_dst : c.wave_dst4 + (1 - BUF) * c.wave_step4));
+                  lds + (pass < 4 ? kG5AOff + (1 - BUF) * kG5SlabBytes + pass * 8192 + c.wave_dst : c.wave_dst_part + (1 - BUF) * c.wave_step_part));
         __builtin_amdgcn_sched_barrier(0);
     }
     G5_CELLS(1, 2)
-    {
+    if constexpr (Q) { // this tile's half (8 KB: rows 128 h .. 128 h + 127) of half-tile (chunk2, T2): one piece per thread
+        cv_blds16(c.W, chunk2 <= c.cmask ? c.wbytes : 0u, c.woff, (unsigned)((T2 + 9 * chunk2) * (2 * 8192)) + c.whalf, lds + ring_wr * kWB + c.wave_dst);
+        __builtin_amdgcn_sched_barrier(0);
+        G5_CELLS(2, 3)
+    } else {
         const unsigned wlive = chunk2 <= c.cmask ? c.wbytes : 0u;
         const unsigned so = (unsigned)((T2 + 9 * chunk2) * (2 * 8192)); // half-tile (chunk2, T2): one contiguous 16 KB block, a scalar offset
         unsigned char *const d = lds + ring_wr * kG5WBytes + c.wave_dst;
@@ -180,14 +223,14 @@ __device__ __forceinline__ void g5_step(const G5Ctx &c, cv_f32x4 (&acc)[4][9], i
     G5_CELLS(3, kG5Split)
 
     ring_rd = ring_rd + 1 == kG5Ring ? 0 : ring_rd + 1;
-    cv_wait_vm<g5_vmcnt(T)>();
-    if constexpr (T == 7) g5_zero_ranks(c, 1 - BUF); // this thread's slab pieces of the next chunk have landed (all but the youngest weight loads)
+    cv_wait_vm<Q ? g5q_vmcnt(T) : g5_vmcnt(T)>();
+    if constexpr (!Q && T == 7) g5_zero_ranks(c, 1 - BUF); // this thread's slab pieces of the next chunk have landed (all but the youngest weight loads)
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
 
     {
-        const unsigned char *wa = lds + (ring_rd * kG5WBytes + c.a_off);
+        const unsigned char *wa = lds + (ring_rd * kWB + c.a_off);
 #pragma unroll
         for (int i = 0; i < 4; ++i) anxt[i] = *(const cv_half8 *)(wa + i * 1024);
         __builtin_amdgcn_sched_barrier(0);
@@ -333,12 +376,12 @@ __device__ __forceinline__ void g5_tile(unsigned char *lds, int blk, int grid, c
     }
     c.wave_dst = w * 1024;
     c.lane16 = lane * 16;
-    c.wave_dst4 = w < 4 ? kG5AOff + 4 * 8192 + w * 1024 : kG5Dump + w * 1024;
-    c.wave_step4 = w < 4 ? kG5SlabBytes : 0;
+    c.wave_dst_part = w < 4 ? kG5AOff + 4 * 8192 + w * 1024 : kG5Dump + w * 1024;
+    c.wave_step_part = w < 4 ? kG5SlabBytes : 0;
     c.cin = cin;
     c.cmask = ONE ? 0 : (cin >> 5) - 1;
     c.xbytes = (unsigned)M * (unsigned)cin * 2u;
-    c.xbytes4 = w < 4 ? c.xbytes : 0u;
+    c.xbytes_part = w < 4 ? c.xbytes : 0u;
     c.wbytes = 9u * 256u * (unsigned)cin * 2u;
     {
         // slab row sr (0..575) = tensor row p0 - 144 + sr: rank 2k - 1 + sr / 144 of the group; 64-byte rows, position pos of
@@ -346,7 +389,7 @@ __device__ __forceinline__ void g5_tile(unsigned char *lds, int blk, int grid, c
         // of this MFMA shape covers)
 #pragma unroll
         for (int it = 0; it < 5; ++it) {
-            const int piece = (it < 4 || w < 4) ? it * 512 + tid : 3 * 512 + tid; // (waves 4-7 in pass 4: any offset, xbytes4 = 0)
+            const int piece = (it < 4 || w < 4) ? it * 512 + tid : 3 * 512 + tid; // (waves 4-7 in pass 4: any offset, xbytes_part = 0)
             const int sr = piece >> 2, pos = piece & 3;
             const int schunk = pos ^ ((0 - (sr >> 2)) & 3);
             long p = p0 - 144 + sr;
@@ -358,7 +401,7 @@ __device__ __forceinline__ void g5_tile(unsigned char *lds, int blk, int grid, c
     // ---- prologue: slab of chunk 0, weight half-tiles 0..2; the per-lane setup below runs while the DMA is in flight
 #pragma unroll
     for (int it = 0; it < 5; ++it)
-        cv_blds16(X, it < 4 ? c.xbytes : c.xbytes4, c.xoff[it], 0u, lds + (it < 4 ? kG5AOff + it * 8192 + c.wave_dst : c.wave_dst4));
+        cv_blds16(X, it < 4 ? c.xbytes : c.xbytes_part, c.xoff[it], 0u, lds + (it < 4 ? kG5AOff + it * 8192 + c.wave_dst : c.wave_dst_part));
 #pragma unroll
     for (int u = 0; u < kG5Ahead; ++u) {
         unsigned char *d = lds + u * kG5WBytes + c.wave_dst;
@@ -465,6 +508,155 @@ __device__ __forceinline__ void g5_tile(unsigned char *lds, int blk, int grid, c
     }
 }
 
+// ---- the QUAD middle tile (CCZ_CONV_G16_QUAD): four ranks x 128 output channels ----------------------------------------------------
+// A two-rank middle tile streams the WHOLE layer's weights (72 x 16 KB = 1,180 KB) for 288 rows: 80 % of its 1,475 KB of DMA. The quad
+// tile runs the same MFMAs -- a wave is still 64 output channels x one rank, the same cells in the same order (g5_step), the same K
+// order: the same bits -- on ranks 1-4 or 5-8 of a group x ONE HALF of the output channels: 72 x 8 KB of weights + 8 x 55,296 B of
+// slab (six ranks) = 1,032 KB per tile, -30 % DMA bytes per MFMA, 16 DMA instructions per thread and chunk instead of 23.
+//   * waves: wm = w & 1 (64 of the tile's 128 channels), wn = w >> 1 (rank of the quad).
+//   * tile slot t of a group (four, as in middle mode): quad t >> 1, channel half h = t & 1 -- the two halves of a quad are neighbours
+//     in the XCD-aware order: they run on the same XCD at about the same time and the second finds the slab in that L2.
+//   * a middle tile's slab never leaves its group's 1,440 rows: nothing is clamped, nothing is zeroed, and staging pass `it` is the
+//     thread's pass-0 offset + it * 128 rows in the SCALAR offset (one VGPR instead of five). Pass 6 has 384 pieces: waves 6-7 issue
+//     theirs against the zero-record descriptor into their KB of the dump area.
+//   * epilogue image: 576 rows x 272 B; wave w owns rows 72 w .. 72 w + 71 and moves 256-byte row segments (channels 128 h ..).
+template <bool RES>
+__device__ __forceinline__ void g5q_tile(unsigned char *lds, int blk, int grid, const _Float16 *__restrict__ X, const _Float16 *__restrict__ W,
+                                         const float *__restrict__ bias, const _Float16 *R, _Float16 *Y, int M, int relu, int cin,
+                                         const int *live_rows, int row0)
+{
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r = lane & 15, q4 = lane >> 4;
+    const int wm = w & 1, wn = w >> 1;
+    int tiles = grid;
+    if (live_rows) {
+        int first;
+        const int live = g5_live_groups(live_rows, row0, M / 1440, first);
+        M = live * 1440;
+        tiles = live * 4;
+        if (blk >= tiles) return;
+        const long off = (long)first * 1440 * kCvC;
+        X += (long)first * 1440 * cin;
+        Y += off;
+        if (RES) R += off;
+    }
+    int tile; // XCD-aware order and flags bit 1 as in g5_tile
+    {
+        const int b = blk, x = b & 7, per = tiles >> 3, rem = tiles & 7;
+        tile = x * per + (x < rem ? x : rem) + (b >> 3);
+    }
+    tile = __builtin_amdgcn_readfirstlane((relu & 2) ? tiles - 1 - tile : tile);
+    const int h = tile & 1;                                                              // output channels 128 h .. 128 h + 127
+    const long p0 = (long)(tile >> 2) * 1440 + 144 + (long)((tile >> 1) & 1) * kG5QRows; // = (group * 90 + 9 * (1 or 5)) * 16
+    relu &= 1;
+
+    G5Ctx c;
+    c.lds = lds;
+    c.X = X;
+    c.W = W;
+    c.wave_dst = w * 1024;
+    c.wave_dst_part = w < 6 ? kG5QAOff + 6 * 8192 + w * 1024 : kG5QDump + w * 1024;
+    c.wave_step_part = w < 6 ? kG5QSlabBytes : 0;
+    c.cin = cin;
+    c.cmask = (cin >> 5) - 1;
+    c.xbytes = (unsigned)M * (unsigned)cin * 2u;
+    c.xbytes_part = w < 6 ? c.xbytes : 0u;
+    c.wbytes = 9u * 256u * (unsigned)cin * 2u;
+    c.xstep = 128u * (unsigned)cin * 2u;
+    c.whalf = (unsigned)h * 8192u;
+    {
+        // slab row sr (0..863) = tensor row p0 - 144 + sr: rank (1 or 5) - 1 + sr / 144 of the group; piece it * 512 + tid is row
+        // it * 128 + (tid >> 2), and the swizzle f(sr) = (-(sr >> 2)) & 3 does not depend on `it`
+        const int sr = tid >> 2, pos = tid & 3;
+        const int schunk = pos ^ ((0 - (sr >> 2)) & 3);
+        c.xoff[0] = (unsigned)((p0 - 144 + sr) * cin + schunk * 8) * 2u;
+        c.woff = (unsigned)(tid * 16);
+    }
+    // ---- prologue: slab of chunk 0, this half's weight blocks of taps 0..2
+#pragma unroll
+    for (int it = 0; it < 7; ++it)
+        cv_blds16(X, it < 6 ? c.xbytes : c.xbytes_part, c.xoff[0], it * c.xstep, lds + (it < 6 ? kG5QAOff + it * 8192 + c.wave_dst : c.wave_dst_part));
+#pragma unroll
+    for (int u = 0; u < kG5Ahead; ++u) cv_blds16(W, c.wbytes, c.woff, (unsigned)(u * 2 * 8192) + c.whalf, lds + u * kG5QWBytes + c.wave_dst);
+    const int lane1 = r * 64 + ((q4 ^ ((0 - (r >> 2)) & 3)) << 4);
+    c.a_off = wm * 4096 + lane1;                               // rows 128 h + 64 wm + 16 i + r of the half-tile
+    c.vb[0] = kG5QAOff + wn * 9 * 1024 + lane1;                // slab cell 9 wn + n + 9 + delta, row r of it
+    c.vb[1] = c.vb[0] + kG5QSlabBytes;
+
+    cv_f32x4 acc[4][9];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const float4 bv = *(const float4 *)(bias + h * 128 + wm * 64 + i * 16 + 4 * q4);
+#pragma unroll
+        for (int n = 0; n < 9; ++n) {
+            acc[i][n][0] = bv.x; acc[i][n][1] = bv.y; acc[i][n][2] = bv.z; acc[i][n][3] = bv.w;
+        }
+    }
+
+    cv_wait_vm<2>(); // all but the weight blocks of taps 1 and 2
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+
+    int ring_rd = 0, ring_wr = kG5Ahead;
+    cv_half8 a0[4], a1[4], b[9];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) a0[i] = *(const cv_half8 *)(lds + c.a_off + i * 1024);
+#pragma unroll
+    for (int n = 0; n < 9; ++n) b[n] = *(const cv_half8 *)(lds + c.vb[0] + n * 1024); // the rank above this wave's: dy = -1
+    for (int chunk = 0; chunk <= c.cmask; chunk += 2) {
+#define G5Q_S(j) g5_step<j, true>(c, acc, chunk + (j) / 9, ring_rd, ring_wr, a0, a1, b)
+        G5Q_S(0); G5Q_S(1); G5Q_S(2); G5Q_S(3); G5Q_S(4); G5Q_S(5); G5Q_S(6); G5Q_S(7); G5Q_S(8);
+        G5Q_S(9); G5Q_S(10); G5Q_S(11); G5Q_S(12); G5Q_S(13); G5Q_S(14); G5Q_S(15); G5Q_S(16); G5Q_S(17);
+#undef G5Q_S
+    }
+    cv_wait_vm<0>(); // the out-of-range DMA loads (zeros) must have landed: the image below covers the dump area too
+
+    // ---- epilogue: every wave writes its 64 channels x 144 rows into the [row][channel] image; then wave w owns rows 72 w .. 72 w + 71
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_barrier(); // every wave is done reading the slabs and the ring
+    __builtin_amdgcn_sched_barrier(0);
+    const int lane_e = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); // formed again, as in g5_tile
+    const int re = lane_e & 15, q4e = lane_e >> 4;
+    const int prow = lane_e >> 4, piece = lane_e & 15;
+    const long pbase = p0 + w * 72 + prow;
+    const int gcol = h * 128 + piece * 8;
+    cv_half8 rv[18];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int col = wm * 64 + i * 16 + 4 * q4e;
+#pragma unroll
+        for (int n = 0; n < 9; ++n) {
+            cv_half4 o;
+            o[0] = (_Float16)acc[i][n][0];
+            o[1] = (_Float16)acc[i][n][1];
+            o[2] = (_Float16)acc[i][n][2];
+            o[3] = (_Float16)acc[i][n][3];
+            *(cv_half4 *)(lds + ((wn * 9 + n) * 16 + re) * kG5QERow + col * 2) = o;
+        }
+    }
+    if (RES) {
+#pragma unroll
+        for (int it = 0; it < 18; ++it) rv[it] = *(const cv_half8 *)(R + (pbase + it * 4) * kCvC + gcol);
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+    {
+        const cv_half8 zero = (cv_half8)(_Float16)0;
+        const unsigned char *eb = lds + (w * 72 + prow) * kG5QERow + piece * 16;
+#pragma unroll
+        for (int it = 0; it < 18; ++it) {
+            cv_half8 v = *(const cv_half8 *)(eb + it * 4 * kG5QERow);
+            if (RES) v = v + rv[it];
+            if (relu) v = __builtin_elementwise_max(v, zero);
+            *(cv_half8 *)(Y + (pbase + it * 4) * kCvC + gcol) = v;
+        }
+    }
+}
+
 template <bool RES>
 __global__ __launch_bounds__(512) void k_conv3x3_g16(const _Float16 *__restrict__ X, const _Float16 *__restrict__ W,
                                                          const float *__restrict__ bias, const _Float16 *R,
@@ -472,6 +664,16 @@ __global__ __launch_bounds__(512) void k_conv3x3_g16(const _Float16 *__restrict_
 {
     __shared__ __attribute__((aligned(16))) unsigned char lds[kG5Lds];
     g5_tile<RES, false>(lds, blockIdx.x, gridDim.x, X, W, bias, R, Y, M, relu, cin, live_rows, row0, G5Heads{});
+}
+
+// The middle launch of quad tiles (CCZ_CONV_G16_QUAD without CCZ_CONV_G16_ONE_LAUNCH): grid = 4 tiles per group, ranks 1..8
+template <bool RES>
+__global__ __launch_bounds__(512) void k_conv3x3_g16_quad(const _Float16 *__restrict__ X, const _Float16 *__restrict__ W,
+                                                            const float *__restrict__ bias, const _Float16 *R,
+                                                            _Float16 *Y, int M, int relu, int cin, const int *live_rows, int row0)
+{
+    __shared__ __attribute__((aligned(16))) unsigned char lds[kG5Lds];
+    g5q_tile<RES>(lds, blockIdx.x, gridDim.x, X, W, bias, R, Y, M, relu, cin, live_rows, row0);
 }
 
 // The stem (ccz_conv3x3_stem_f16 with CCZ_CONV_G16): rows of 64 channels of which only 0..31 can be non-zero, one chunk (g5_tile ONE)

@@ -71,9 +71,9 @@ __device__ __forceinline__ void g5e_step(const G5Ctx &c, cv_f32x4 (&acc)[4][9], 
     if constexpr (g5e_dma(H) > 2) { // the next chunk's slab: passes 0,1 | 2,3 | 4 in half-steps 0 | 1 | 2
         constexpr int p0 = H * 2;
         const unsigned so = (unsigned)((chunk + 1) * 64);
-        const unsigned live = chunk < c.cmask ? (p0 < 4 ? c.xbytes : c.xbytes4) : 0u;
+        const unsigned live = chunk < c.cmask ? (p0 < 4 ? c.xbytes : c.xbytes_part) : 0u;
         cv_blds16(c.X, live, c.xoff[p0], so,
-                  lds + (p0 < 4 ? kG5AOff + (1 - BUF) * kG5SlabBytes + p0 * 8192 + c.wave_dst : c.wave_dst4 + (1 - BUF) * c.wave_step4));
+                  lds + (p0 < 4 ? kG5AOff + (1 - BUF) * kG5SlabBytes + p0 * 8192 + c.wave_dst : c.wave_dst_part + (1 - BUF) * c.wave_step_part));
         if constexpr (g5e_dma(H) > 3)
             cv_blds16(c.X, live, c.xoff[p0 + 1], so, lds + kG5AOff + (1 - BUF) * kG5SlabBytes + ((p0 + 1) * 8192 + c.wave_dst));
         __builtin_amdgcn_sched_barrier(0);
@@ -150,19 +150,19 @@ __device__ __forceinline__ void g5e_tile(unsigned char *lds, int blk, const _Flo
     c.W = W;
     c.wave_dst = w * 1024;
     c.lane16 = lane * 16;
-    c.wave_dst4 = w < 4 ? kG5AOff + 4 * 8192 + w * 1024 : kG5Dump + w * 1024;
-    c.wave_step4 = w < 4 ? kG5SlabBytes : 0;
+    c.wave_dst_part = w < 4 ? kG5AOff + 4 * 8192 + w * 1024 : kG5Dump + w * 1024;
+    c.wave_step_part = w < 4 ? kG5SlabBytes : 0;
     c.cin = cin;
     c.cmask = (cin >> 5) - 1;
     c.xbytes = (unsigned)groups * (1440u * 2u) * (unsigned)cin;
-    c.xbytes4 = w < 4 ? c.xbytes : 0u;
+    c.xbytes_part = w < 4 ? c.xbytes : 0u;
     c.wbytes = 9u * 256u * (unsigned)cin * 2u;
     {
         // slab row sr: 0..287 = group A's rows srcA + sr, 288..575 = group B's; 64-byte rows, position pos of row sr holds source
         // chunk pos ^ f(sr), f = (-(sr >> 2)) & 3 (the swizzle of k_conv3x3_g16)
 #pragma unroll
         for (int it = 0; it < 5; ++it) {
-            const int piece = (it < 4 || w < 4) ? it * 512 + tid : 3 * 512 + tid; // (waves 4-7 in pass 4: any offset, xbytes4 = 0)
+            const int piece = (it < 4 || w < 4) ? it * 512 + tid : 3 * 512 + tid; // (waves 4-7 in pass 4: any offset, xbytes_part = 0)
             const int sr = piece >> 2, pos = piece & 3;
             const int schunk = pos ^ ((0 - (sr >> 2)) & 3);
             const long p = sr < 288 ? srcA + sr : srcB + (sr - 288);
@@ -173,7 +173,7 @@ __device__ __forceinline__ void g5e_tile(unsigned char *lds, int blk, const _Flo
     // ---- prologue: slab of chunk 0, weight half-tiles of the first three live taps
 #pragma unroll
     for (int it = 0; it < 5; ++it)
-        cv_blds16(X, it < 4 ? c.xbytes : c.xbytes4, c.xoff[it], 0u, lds + (it < 4 ? kG5AOff + it * 8192 + c.wave_dst : c.wave_dst4));
+        cv_blds16(X, it < 4 ? c.xbytes : c.xbytes_part, c.xoff[it], 0u, lds + (it < 4 ? kG5AOff + it * 8192 + c.wave_dst : c.wave_dst_part));
 #pragma unroll
     for (int u = 0; u < kG5Ahead; ++u) {
         unsigned char *d = lds + u * kG5WBytes + c.wave_dst;
@@ -293,20 +293,40 @@ __global__ __launch_bounds__(512) void k_conv3x3_g16_edge_heads(const _Float16 *
 // being ~24 % shorter they fill the launch's last round. Each tile is the same code as in its own kernel (the branch is taken once,
 // before either body starts): the same values. grid = 4 groups + 2 ceil(groups / 2) of the capacity; slots past the live ones leave.
 // Not for the last layer: with the heads in the epilogue both bodies in one kernel spill (one VGPR); it stays two launches.
-template <bool RES>
-__global__ __launch_bounds__(512) void k_conv3x3_g16_one(const _Float16 *__restrict__ X, const _Float16 *__restrict__ W,
-                                                           const float *__restrict__ bias, const _Float16 *R, _Float16 *Y, int M,
-                                                           int relu, int cin, const int *live_rows, int row0)
+template <bool RES, bool QUAD>
+__device__ __forceinline__ void g5_one_launch(unsigned char *lds, const _Float16 *__restrict__ X, const _Float16 *__restrict__ W,
+                                              const float *__restrict__ bias, const _Float16 *R, _Float16 *Y, int M,
+                                              int relu, int cin, const int *live_rows, int row0)
 {
-    __shared__ __attribute__((aligned(16))) unsigned char lds[kG5Lds];
     int groups = M / 1440;
     if (live_rows) {
         int first;
         groups = g5_live_groups(live_rows, row0, groups, first);
     }
     const int mid = groups * 4, blk = blockIdx.x;
-    if (blk < mid) g5_tile<RES, false>(lds, blk, mid, X, W, bias, R, Y, M, relu | 4, cin, live_rows, row0, G5Heads{});
-    else g5e_tile<RES, false>(lds, blk - mid, X, W, bias, R, Y, M, relu, cin, live_rows, row0, G5Heads{});
+    if (blk < mid) {
+        if constexpr (QUAD) g5q_tile<RES>(lds, blk, mid, X, W, bias, R, Y, M, relu, cin, live_rows, row0);
+        else g5_tile<RES, false>(lds, blk, mid, X, W, bias, R, Y, M, relu | 4, cin, live_rows, row0, G5Heads{});
+    } else g5e_tile<RES, false>(lds, blk - mid, X, W, bias, R, Y, M, relu, cin, live_rows, row0, G5Heads{});
+}
+
+template <bool RES>
+__global__ __launch_bounds__(512) void k_conv3x3_g16_one(const _Float16 *__restrict__ X, const _Float16 *__restrict__ W,
+                                                           const float *__restrict__ bias, const _Float16 *R, _Float16 *Y, int M,
+                                                           int relu, int cin, const int *live_rows, int row0)
+{
+    __shared__ __attribute__((aligned(16))) unsigned char lds[kG5Lds];
+    g5_one_launch<RES, false>(lds, X, W, bias, R, Y, M, relu, cin, live_rows, row0);
+}
+
+// The same with the middle slots as QUAD tiles (CCZ_CONV_G16_QUAD, cczero_conv_g16.h g5q_tile): slot t of group g = quad t >> 1, channel half t & 1
+template <bool RES>
+__global__ __launch_bounds__(512) void k_conv3x3_g16_one_quad(const _Float16 *__restrict__ X, const _Float16 *__restrict__ W,
+                                                                const float *__restrict__ bias, const _Float16 *R, _Float16 *Y, int M,
+                                                                int relu, int cin, const int *live_rows, int row0)
+{
+    __shared__ __attribute__((aligned(16))) unsigned char lds[kG5Lds];
+    g5_one_launch<RES, true>(lds, X, W, bias, R, Y, M, relu, cin, live_rows, row0);
 }
 
 } // namespace ccz

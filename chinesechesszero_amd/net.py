@@ -108,9 +108,12 @@ class EvalOptions:
     ``CCZ_FUSED_LAST=0`` (fused_last): the head convolutions as a pass of their own over the stored output of the tower instead of in
     the last layer's epilogue (group-of-16 rows; same bits either way);
     ``CCZ_CONV_ONE_LAUNCH=0`` (one_launch; round 7): with the edge-pair kernel, the middle and edge-pair tiles of a layer as two launches
-    instead of one (k_conv3x3_g16_one, csrc/cczero_conv_g16e.h; same bits)."""
+    instead of one (k_conv3x3_g16_one, csrc/cczero_conv_g16e.h; same bits);
+    ``CCZ_CONV_QUAD=0`` (quad): with the edge-pair kernel, the middle tiles as two ranks x 256 output channels instead of four ranks x
+    128 (g5q_tile, csrc/cczero_conv_g16.h; same bits)."""
 
-    FIELDS = ("fused_conv", "fused_stem", "fused_heads", "fused_last", "layout", "force", "groups", "chains", "zigzag", "edge_tiles", "one_launch")
+    FIELDS = ("fused_conv", "fused_stem", "fused_heads", "fused_last", "layout", "force", "groups", "chains", "zigzag", "edge_tiles", "one_launch",
+              "quad")
 
     def __init__(self, env=None):
         env = os.environ if env is None else env
@@ -126,6 +129,7 @@ class EvalOptions:
         # group-of-16 layout: ranks 0 / 9 on the edge-pair kernel (round 4): "auto" = from 4096 boards on, together with three launch chains
         self.edge_tiles = {"0": False, "1": True}.get(env.get("CCZ_CONV_EDGE_TILES", "auto"), "auto")
         self.one_launch = env.get("CCZ_CONV_ONE_LAUNCH", "1") != "0"
+        self.quad = env.get("CCZ_CONV_QUAD", "1") != "0"
         if self.layout not in ("auto", "nhwc", "g16"):
             raise ValueError("CCZ_CONV_LAYOUT must be auto, nhwc or g16")
 
@@ -526,9 +530,11 @@ class InferenceNet(nn.Module):
         return pool[1]
 
     def _edge_flags(self, edge: bool) -> int:
-        """Flag bits of the edge-pair form: middle and edge-pair tiles as ONE launch per layer and chain unless switched off."""
+        """Flag bits of the edge-pair form: middle and edge-pair tiles as ONE launch per layer and chain, the middle tiles as quad
+        tiles, unless switched off."""
         from . import _lib
-        return (_lib.CONV_G16_EDGE_TILES | (_lib.CONV_G16_ONE_LAUNCH if self.opt.one_launch else 0)) if edge else 0
+        return (_lib.CONV_G16_EDGE_TILES | (_lib.CONV_G16_ONE_LAUNCH if self.opt.one_launch else 0)
+                | (_lib.CONV_G16_QUAD if self.opt.quad else 0)) if edge else 0
 
     def _force_flag(self) -> int:
         """A/B switch ``force`` (``CCZ_CONV_FORCE=small|tile``): run every convolution on k_conv3x3_small / on the 256-pixel tile

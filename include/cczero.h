@@ -550,6 +550,13 @@ int ccz_bias_act_f16(void *stream, void *y_dev, const void *bias_dev, const void
                                        chain pays one dependent-launch tail per layer instead of two and the shorter edge tiles fill the
                                        last round of the middle ones. Same tiles, same values; the heads layer (ccz_conv3x3_c256_heads_f16)
                                        ignores it */
+#define CCZ_CONV_G16_QUAD 65536     /* with CCZ_CONV_G16_EDGE_TILES (additive to ABI 8: bit 16, which ABI-8 libraries before it refuse with the retired
+                                       persistent form's bits 16..27 -- an older library fails the call, it never ignores the flag): the middle
+                                       tiles as FOUR ranks x 128 output channels instead of two ranks x 256 (csrc/cczero_conv_g16.h g5q_tile):
+                                       as many tiles of as many rows x channels and the same MFMAs in the same order, but a tile streams half
+                                       the layer's weights: -30 % LDS-DMA bytes per tile. Same values. Where the five-tile launch runs (no
+                                       CCZ_CONV_G16_EDGE_TILES, or fewer than 32 boards) it has no effect; the heads layer
+                                       (ccz_conv3x3_c256_heads_f16) ignores it: its epilogue needs all 256 channels of a row */
 int ccz_conv3x3_c256_f16(void *stream, const void *x_dev, const void *w_dev, const void *bias_f32_dev,
                          const void *residual_dev, void *y_dev, int64_t n_pixels, int32_t relu);
 /* Weights for the CCZ_CONV_G16 form, once per weight set: w [256, 3, 3, cin] fp16 (cin = 256: tower, 64: stem) ->
