@@ -21,6 +21,10 @@ rn16 of the exact float64 sum of two fp16 numbers. The chains, as the kernels do
     FC (all three kernels)     rn16( relu?(bias + S_K) )
     value output               tanh( rn16(b2 + S_256) )                     nearest-candidate check, see value_candidates
     ccz_bias_act_f16           relu( rn16( rn16(y + b) + r ) )              pure fp16 adds: any fp16 operands
+
+The planned boundary on board-major rows (tests/test_gpu_board_major_live.py): planned_cap / live_ranges restate how net.py sizes and
+k_conv3x3_c256 cuts the live boards, conv_live_expected places the chain's rows in a filled buffer, pack_live_planes_rows is the
+gathering plane pack; assert_same_bits compares bit patterns, for buffers whose untouched elements must keep their fill.
 """
 import ctypes as C
 
@@ -190,6 +194,61 @@ def assert_same(got, want, what, names=None):
         at = tuple(int(i) for i in np.argwhere(bad)[0])
         where = ", ".join(f"{n} {i}" for n, i in zip(names, at)) if names else str(at)
         raise AssertionError(f"{what}: {where}: device {g[at]!r} vs float64 chain {w[at]!r}; {int(bad.sum())} of {bad.size} elements differ")
+
+
+def assert_same_bits(got, want, what, names=None):
+    """Equality on BIT PATTERNS of two fp16 arrays (-0 differs from +0, a NaN equals the same NaN): for buffers whose untouched
+    elements hold a fill that must survive a call, 0xFFFF included. On failure: the first differing element and the count."""
+    got, want = np.ascontiguousarray(got), np.ascontiguousarray(want)
+    assert got.shape == want.shape and got.dtype == want.dtype == np.float16, (what, got.shape, want.shape, got.dtype, want.dtype)
+    bad = got.view(np.uint16) != want.view(np.uint16)
+    if bad.any():
+        at = tuple(int(i) for i in np.argwhere(bad)[0])
+        where = ", ".join(f"{n} {i}" for n, i in zip(names, at)) if names else str(at)
+        raise AssertionError(f"{what}: {where}: device bits 0x{int(got.view(np.uint16)[at]):04x} vs expected 0x{int(want.view(np.uint16)[at]):04x}; "
+                             f"{int(bad.sum())} of {bad.size} elements differ")
+
+
+# ------------------------------------------------------------------ the planned boundary on board-major rows (restatements of the host code and the kernels' addressing)
+def planned_cap(boards, n_parts):
+    """pixels of the largest range one launch of the board-major live form may get, as InferenceNet._tower_planned passes them:
+    ceil(ceil(B / n_parts) / 8) * 8 * 90 (it may reach past the tensor: the kernel never computes more than the live boards)"""
+    return -(-(-(-boards // n_parts)) // 8) * 8 * 90
+
+
+def live_ranges(live, n_parts, cap_boards):
+    """k_conv3x3_c256 with a live count: the first `live` boards cut into n_parts ranges of per = ceil(ceil(live / n_parts) / 8) * 8
+    boards; range `part` starts at board part * per and holds min(per, live - part * per, cap_boards) boards (none when that is <= 0).
+    -> [(first board, boards)] for part = 0 .. n_parts - 1"""
+    per = -(-(-(-live // n_parts)) // 8) * 8
+    return [(part * per, max(0, min(per, live - part * per, cap_boards))) for part in range(n_parts)]
+
+
+def conv_live_expected(s, res, relu, ranges, fill):
+    """What the launches of `ranges` leave in an output that held `fill` [B, 10, 9, C] fp16: conv_chain on the boards of every range,
+    the fill everywhere else. (With the ranges of live_ranges: the chain on the first `live` boards.)"""
+    out = np.array(fill, dtype=np.float16, copy=True)
+    for first, n in ranges:
+        if n > 0:
+            out[first:first + n] = conv_chain(s[first:first + n], None if res is None else res[first:first + n], relu)
+    return out
+
+
+def pack_live_planes_rows(leaf, rows, n_rows, out, g16=False):
+    """k_pack_live_planes in its gathering (planned) form on out [R, 64] fp16, R = 90 * boards (g16: 1440 * groups): for i < n_rows
+    and pixel p, channels 0..20 of output row i * 90 + p (g16: ((i >> 4) * 90 + p) * 16 + (i & 15)) are planes 49..55 and 105..118 of
+    board rows[i] (leaf [B, 119, 10, 9]), channels 21..23 are zero -- three 16-byte chunks; channels 24..63 and every other row keep
+    what they held. Returns a copy."""
+    out = np.array(out, dtype=np.float16, copy=True)
+    leaf = np.asarray(leaf)
+    p = np.arange(90)
+    for i in range(int(n_rows)):
+        b = int(rows[i])
+        live = np.concatenate([leaf[b, 49:56], leaf[b, 105:119]], axis=0).reshape(21, 90).T        # [pixel, 21]
+        at = ((i >> 4) * 90 + p) * 16 + (i & 15) if g16 else i * 90 + p
+        out[at, :21] = live.astype(np.float16)
+        out[at, 21:24] = 0
+    return out
 
 
 # ------------------------------------------------------------------ float32 emulations (the checker's own check; mutants build on them)

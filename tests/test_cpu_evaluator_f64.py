@@ -344,3 +344,110 @@ def test_mutation_table():
     # an epilogue that adds the residual before the rounding)
     assert by_name["accumulator rounded to fp16 between 32-channel chunks"][1]
     assert by_name["residual added in fp32, single rounding"][1]
+
+
+# ------------------------------------------------------------------ (4) the planned boundary on board-major rows (tests/test_gpu_board_major_live.py)
+def test_live_ranges_cover_the_live_boards_once_inside_the_capacity():
+    """live_ranges restates the range arithmetic of k_conv3x3_c256: for every live count up to the batch and 1..6 parts the ranges
+    start on multiples of 8 boards, do not overlap, never exceed the capacity _tower_planned passes, and together are [0, live)."""
+    assert E.planned_cap(40, 1) == 40 * 90 and E.planned_cap(40, 3) == 16 * 90 and E.planned_cap(40, 6) == 8 * 90
+    assert E.planned_cap(37, 1) == 40 * 90 and E.planned_cap(600, 2) == 304 * 90 and E.planned_cap(11, 1) == 16 * 90
+    assert E.live_ranges(9, 3, 16) == [(0, 8), (8, 1), (16, 0)]
+    assert E.live_ranges(40, 6, 8) == [(0, 8), (8, 8), (16, 8), (24, 8), (32, 8), (40, 0)]
+    assert E.live_ranges(0, 1, 40) == [(0, 0)] and E.live_ranges(17, 2, 24) == [(0, 16), (16, 1)]
+    for B in (11, 37, 40, 600):
+        for n_parts in range(1, 7):
+            cap = E.planned_cap(B, n_parts) // 90
+            for live in range(0, B + 1):
+                ranges = E.live_ranges(live, n_parts, cap)
+                assert len(ranges) == n_parts
+                covered = np.zeros(B, np.int32)
+                for first, n in ranges:
+                    assert first % 8 == 0 and 0 <= n <= cap
+                    covered[first:first + n] += 1
+                    assert n == 0 or first + n <= B                              # (an empty range may start past the batch: it addresses nothing)
+                assert np.all(covered[:live] == 1) and np.all(covered[live:] == 0), (B, n_parts, live)
+
+
+def _live_case():
+    """24 boards of 8 channels: any float64 sums do (the references below only place conv_chain's rows)"""
+    rs = np.random.RandomState(12)
+    s = rs.standard_normal((24, 10, 9, 8)) * 3
+    r = E.grid_acts(rs, (24, 10, 9, 8), relu=False)
+    fill = np.full((24, 10, 9, 8), -1, np.int16).view(np.float16)            # 0xFFFF: what an arena holds
+    return s, r, fill
+
+
+def test_live_reference_rejects_a_part_boundary_moved_by_eight_boards():
+    s, r, fill = _live_case()
+    ranges = E.live_ranges(17, 2, 16)
+    want = E.conv_live_expected(s, r, True, ranges, fill)
+    E.assert_same(want[:17], E.conv_chain(s[:17], r[:17], True), "live reference")
+    assert np.all(want.view(np.int16)[17:] == -1)
+    E.assert_same_bits(want, E.conv_live_expected(s, r, True, [(0, 17)], fill), "one part")       # the cut itself changes nothing
+    # part 1 starts eight boards late (its end stays): boards 16.. keep the fill
+    late = E.conv_live_expected(s, r, True, [(0, 16), (24, 0)], fill)
+    with pytest.raises(AssertionError, match="board 16"):
+        E.assert_same(late[:17], want[:17], "late part", ("board", "rank", "file", "channel"))
+    with pytest.raises(AssertionError):
+        E.assert_same_bits(late, want, "late part")
+    # full case, three parts of eight: the middle part moved up by eight boards leaves boards 8..15 unwritten
+    want24 = E.conv_live_expected(s, r, True, E.live_ranges(24, 3, 8), fill)
+    moved = E.conv_live_expected(s, r, True, [(0, 8), (16, 8), (16, 8)], fill)
+    with pytest.raises(AssertionError, match="board 8"):
+        E.assert_same(moved, want24, "moved part", ("board", "rank", "file", "channel"))
+    # the last range ends eight boards late: rows past the live count are written -- values cannot see it, the bit comparison does
+    long = E.conv_live_expected(s, r, True, [(0, 16), (16, 8)], fill)
+    E.assert_same(long[:17], want[:17], "long part")
+    with pytest.raises(AssertionError):
+        E.assert_same_bits(long, want, "long part")
+    # the residual of another range (R not moved with Y)
+    wrong_r = E.conv_live_expected(s, np.roll(r, 8, axis=0), True, ranges, fill)
+    with pytest.raises(AssertionError):
+        E.assert_same(wrong_r[:17], want[:17], "residual of another range")
+
+
+@pytest.mark.parametrize("g16", [False, True])
+def test_pack_restatement_against_plain_indexing_and_swapped_chunks(g16):
+    rs = np.random.RandomState(5 + g16)
+    B = 20
+    leaf = (rs.random_sample((B, 119, 10, 9)) > 0.7).astype(np.float16)
+    leaf[:, :7] = 1
+    rows = rs.permutation(B).astype(np.int32)
+    R = 2 * 1440 if g16 else B * 90
+    for n_rows in (0, 1, 11, 20):
+        out = np.full((R, 64), 7.5, np.float16)                                  # sentinel A
+        out[:, 24:] = -3.25                                                      # sentinel B
+        got = E.pack_live_planes_rows(leaf, rows, n_rows, out, g16)
+        planes = list(range(49, 56)) + list(range(105, 119))
+        want = out.copy()
+        for i in range(n_rows):
+            for p in range(90):
+                at = ((i // 16) * 90 + p) * 16 + i % 16 if g16 else i * 90 + p
+                for c in range(24):
+                    want[at, c] = leaf[rows[i], planes[c], p // 9, p % 9] if c < 21 else 0
+        E.assert_same_bits(got, want, f"pack restatement n_rows {n_rows}")
+        assert np.all(got[:, 24:] == np.float16(-3.25))
+        if n_rows == 0:
+            E.assert_same_bits(got, out, "nothing written")
+            continue
+        assert (got[:, :24] == 7.5).sum() == (R - 90 * n_rows) * 24 and got[:, :21].astype(np.float64).sum() > 0
+        swapped = got.copy()                                                     # two 16-byte chunks of every written row exchanged
+        live = np.flatnonzero(got[:, 21] == 0)
+        swapped[live, 0:8], swapped[live, 8:16] = got[live, 8:16], got[live, 0:8]
+        with pytest.raises(AssertionError):
+            E.assert_same_bits(swapped, want, "swapped chunks")
+        other = E.pack_live_planes_rows(leaf, np.roll(rows, 1), n_rows, out, g16)   # the boards of another permutation
+        with pytest.raises(AssertionError):
+            E.assert_same_bits(other, want, "other rows")
+
+
+def test_bit_comparison_sees_what_value_comparison_cannot():
+    a = np.array([0.0, 1.0, np.nan], np.float16)
+    b = np.array([-0.0, 1.0, np.nan], np.float16)
+    E.assert_same_bits(a, a.copy(), "same NaN")
+    with pytest.raises(AssertionError):
+        E.assert_same_bits(a, b, "signed zero")
+    E.assert_same(a[:2], b[:2], "values")
+    with pytest.raises(AssertionError):
+        E.assert_same(a, a.copy(), "NaN equals nothing")

@@ -388,8 +388,10 @@ def _fc_rows(M):
     return np.unique(np.array([r for r in rows if 0 <= r < M]))
 
 
-def _fc_check(shape, M, sw=0, sx=0, forms=FC_FORMS):
-    L = _lib()
+def _fc_operands(shape, M, sw=0, sx=0):
+    """float64 operands of one FC case on the grids, the weight matrix and the bias padded to whole 128-row tiles (as net.py pads
+    them: the kernels' contract), the activations in a [M, lda] buffer with NaN between K and lda; the exact sums on `rows`
+    (_fc_rows) and the expected fp16 output there."""
     K, N, relu, lda, ldc = FC_SHAPES[shape]
     rs = np.random.RandomState(K + N + M)
     Np = -(-N // 128) * 128
@@ -402,11 +404,17 @@ def _fc_check(shape, M, sw=0, sx=0, forms=FC_FORMS):
     E.assert_on_grid(a, E.EA + sx)
     rows = _fc_rows(M)
     s, worst, share = E.gemm_exact(a[rows], w[:N], b[:N], G * 2.0 ** -(sw + sx), f"fc {shape} M {M}")
-    report(f"fc {shape} M {M}{' (subnormal weights)' if sw else ''}", worst, share)
-    want = E.fc_chain(s, relu)
     buf = np.full((M, lda), np.nan)                                              # poison between K and lda: never read
     buf[:, :K] = a
-    ad, wd, bd = h16(buf), h16(w), f32(b)
+    return dict(K=K, N=N, relu=relu, lda=lda, ldc=ldc, buf=buf, w=w, b=b, rows=rows, worst=worst, share=share, want=E.fc_chain(s, relu))
+
+
+def _fc_check(shape, M, sw=0, sx=0, forms=FC_FORMS):
+    L = _lib()
+    o = _fc_operands(shape, M, sw, sx)
+    K, N, relu, lda, ldc, rows, want = o["K"], o["N"], o["relu"], o["lda"], o["ldc"], o["rows"], o["want"]
+    report(f"fc {shape} M {M}{' (subnormal weights)' if sw else ''}", o["worst"], o["share"])
+    ad, wd, bd = h16(o["buf"]), h16(o["w"]), f32(o["b"])
     for live in (None, M // 2 + 1) if M > 1 else (None,):
         n = M if live is None else live
         nl = None if live is None else torch.tensor([live], dtype=torch.int32, device=_dev())
