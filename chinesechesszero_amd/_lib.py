@@ -22,6 +22,9 @@ MASK_WORDS = 66
 PLANES = 10710
 REC_BYTES, REC_HDR, REC_IDS, REC_PI = 880, 96, 112, 368  # compact ply record (include/cczero.h CCZ_REC_*)
 REC_FLAGS, REC_FAST = 103, 1  # byte of the header's flags; CCZ_REC_FAST: a fast ply of playout-cap randomisation (no policy target)
+REC_RESIGNED, REC_PLAYON, REC_VALUE = 2, 4, 8  # CCZ_REC_*: the game ended by resignation / drew the play-on lot; the ply carries its root value
+REC_VALUE_OFF = 92  # float32 root value of a REC_VALUE ply (record bytes 92..95)
+RESIGN_RESIGNED, RESIGN_PLAYON = 2, 4  # CCZ_RESIGN_*: resign_status state, bit 0 = the side that resigned / would have
 HEAD_POL_STRIDE, HEAD_VAL_STRIDE = 1536, 640  # CCZ_HEAD_*_STRIDE: fp16 elements per board of the head kernels' outputs
 
 ABI_VERSION = 8
@@ -74,6 +77,11 @@ class Stats(C.Structure):
     ]
 
 
+class ResignStats(C.Structure):
+    _fields_ = [("resigned_games", C.c_int64), ("resigned_by_red", C.c_int64), ("resigned_plies", C.c_int64), ("playon_games", C.c_int64),
+                ("playon_won", C.c_int64), ("playon_drawn", C.c_int64), ("playon_plies_after", C.c_int64)]
+
+
 # every symbol include/cczero.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 PROTOTYPES = {
@@ -110,6 +118,11 @@ PROTOTYPES = {
     "ccz_draw_budgets": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_double, _P]),
     "ccz_expand_record_targets": (C.c_int, [_P, _P, C.c_int64, C.c_uint32, C.c_int64, C.c_int64, _P]),
     "ccz_sample_record_targets": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, C.c_uint32, _P]),
+    "ccz_expand_record_values": (C.c_int, [_P, _P, C.c_int64, C.c_uint32, C.c_int64, C.c_int64, _P]),
+    "ccz_sample_record_values": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, C.c_uint32, _P]),
+    "ccz_set_resign": (C.c_int, [_P, _P, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_double]),
+    "ccz_get_resign_stats": (C.c_int, [_P, _P, C.POINTER(ResignStats)]),
+    "ccz_resign_status": (C.c_int, [_P, _P, _P, _P, _P, _P]),
     "ccz_finish_move": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32]),
     "ccz_root_children": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
     "ccz_principal_variations": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),

@@ -23,6 +23,7 @@ import numpy as np
 
 from .parameters import C_PUCT
 
+_RESIGNED = 2   # _lib.RESIGN_RESIGNED (this module imports the engine lazily: its statistics run without a GPU)
 PROMOTE_THRESHOLD = 0.55   # AlphaGo Zero's gate, kept by the AlphaZero_Gomoku lineage the reference cites
 
 
@@ -174,11 +175,14 @@ class Arena:
     every move, evaluation cache of 2^``eval_cache_log2`` positions shared by both networks (salted per network).
     ``n_playout_b``: playout odds -- A searches ``n_playout`` simulations per move, B ``n_playout_b`` (per-board simulation budgets,
     ``engine.set_budgets``: the lockstep loop runs max(nA, nB) steps and a board that has used its budget costs no evaluator row);
-    None: both search ``n_playout``."""
+    None: both search ``n_playout``. ``resign``: a threshold in [-1, 0] or a dict with ``threshold`` and optionally ``consecutive`` /
+    ``min_ply`` (``engine.set_resign``): the side to move resigns when its root value stayed below the threshold -- a resigned game
+    is a win for the other side like any other, counted in ``result()["resigned"]``; no game is played on (``p_playon`` = 0).
+    None (default): games end by the rules or the ply cap only."""
 
     def __init__(self, net_a, net_b, n_pairs: int, n_playout: int = 400, opening_plies: int = 6, seed: int = 0,
                  max_plies: int = 0, c_puct: float = C_PUCT, eval_cache_log2: int = 22, device: int = 0,
-                 cache_verify: bool = False, n_playout_b: int | None = None):
+                 cache_verify: bool = False, n_playout_b: int | None = None, resign=None):
         from .engine import SelfPlayEngine
         self.nets = (net_a, net_b)
         self.ev = (_as_evaluator(net_a, "A"), _as_evaluator(net_b, "B"))
@@ -198,6 +202,13 @@ class Arena:
                                          seed=seed, device=device, max_plies=max_plies, mirror=False,
                                          eval_cache_log2=eval_cache_log2, cache_verify=cache_verify)
         self.max_plies = e.max_plies
+        self.resign = None
+        if resign is not None:
+            self.resign = dict(resign) if isinstance(resign, dict) else {"threshold": float(resign)}
+            if self.resign.get("p_playon", 0.0) != 0.0:
+                raise ValueError("Arena: a match plays no game on after the resignation rule fired (p_playon is fixed at 0)")
+            self.resign["p_playon"] = 0.0
+            e.set_resign(**self.resign)
         self.opening_of, self.a_colour, self.red_net = pair_layout(self.P)
         self.openings = make_openings(self.P, int(opening_plies), seed=seed, device=device)
         sq, turn, half = self.openings
@@ -262,9 +273,12 @@ class Arena:
         e = self.engine
         over = e.game_status()["over"]
         moves = e.finish_move(temps=self._temps, keep_tree=False).cpu().numpy().copy()
-        # a game adjudicated at max_plies ends INSTEAD of a move (finish_move plays none on that board)
+        # a game adjudicated at max_plies ends INSTEAD of a move (finish_move plays none on that board); so does a resigned one
         st = e.game_status()
-        self.truncated |= (over == 0) & (st["over"] == 1) & (moves < 0)
+        ended = (over == 0) & (st["over"] == 1) & (moves < 0)
+        if self.resign is not None and ended.any():
+            ended &= (e.resign_status()["state"] & _RESIGNED) == 0
+        self.truncated |= ended
         self._turn = st["turn"].astype(np.uint8)
         self.moves.append(moves)
         return moves
@@ -296,6 +310,8 @@ class Arena:
                "n_playout_b": self.n_playout if self.n_playout_b is None else self.n_playout_b,
                "wins": int(np.sum(w == self.a_colour)), "draws": int(np.sum(w == -1)), "losses": int(np.sum((w != -1) & (w != self.a_colour))),
                "truncated": int(self.truncated.sum()), "unfinished": int((st["over"] == 0).sum())}
+        if self.resign is not None:
+            out["resigned"] = int(((self.engine.resign_status()["state"] & _RESIGNED) != 0).sum())
         out.update(pair_stats(pair_pts))
         out.update({"plies_mean": float(plies.mean()), "plies_min": int(plies.min()), "plies_max": int(plies.max()),
                     "steps": self.steps, "rows_per_step": [float(rows[0]) / steps, float(rows[1]) / steps]})
@@ -342,11 +358,21 @@ def main(argv=None) -> int:
     ap.add_argument("--blocks", type=int, default=40)
     ap.add_argument("--threshold", type=float, default=PROMOTE_THRESHOLD, help="promotion threshold of the score")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--resign-threshold", type=float, default=None,
+                    help="resignation: the side to move resigns when its root value stayed below this (in [-1, 0]); absent = off")
+    ap.add_argument("--resign-moves", type=int, default=None, help="... for this many of its moves in a row (default 2)")
+    ap.add_argument("--resign-min-ply", type=int, default=None, help="... and not before this ply (default 30)")
     a = ap.parse_args(argv)
+    if a.resign_threshold is None and (a.resign_moves is not None or a.resign_min_ply is not None):
+        ap.error("--resign-moves / --resign-min-ply need --resign-threshold")
+    resign = None
+    if a.resign_threshold is not None:
+        resign = {"threshold": a.resign_threshold, "consecutive": 2 if a.resign_moves is None else a.resign_moves,
+                  "min_ply": 30 if a.resign_min_ply is None else a.resign_min_ply}
     na = _load(a.a, a.channels, a.blocks, a.device)
     nb = _load(a.b, a.channels, a.blocks, a.device)
     arena = Arena(na, nb, a.pairs, n_playout=a.playout, opening_plies=a.opening_plies, seed=a.seed, max_plies=a.max_plies,
-                  eval_cache_log2=a.eval_cache_log2, device=a.device, n_playout_b=a.playout_b)
+                  eval_cache_log2=a.eval_cache_log2, device=a.device, n_playout_b=a.playout_b, resign=resign)
     r = arena.play()
     r.update({"a": a.a, "b": a.b, "opening_plies": a.opening_plies, "seed": a.seed, "net": f"{a.blocks}x{a.channels}",
               "promote": promote(r, a.threshold), "threshold": a.threshold})

@@ -58,6 +58,11 @@ class TupleSink:
     keep them out of the policy loss). ``finalize`` writes them as ``policy_targets.npy`` (uint8, row-aligned with ``states.npy``;
     rows stored without a flag count as targets) -- but only once some row was flagged: a data set without fast plies has no such
     file and its other files are byte for byte what they were.
+
+    Root values: a row may carry the search's root value of its position (side to move's view; ``CCZ_REC_VALUE`` records, bytes
+    92..95: the engine records them while resignation is configured). ``finalize`` writes them as ``root_values.npy`` (float32,
+    row-aligned with ``states.npy``, NaN where unknown) under the rules of ``policy_targets.npy``: only once some row carried a
+    value, and merged across shards the same way (rows of older shards: NaN). The second value target of ``Trainer.step(q=...)``.
     """
 
     ARRAYS = {"states": ("_s.npy", np.float16, (17, 7, 10, 9)), "mcts": ("_p.npy", None, (2086,)), "winners": ("_z.npy", np.float32, ())}
@@ -196,9 +201,15 @@ class TupleSink:
         return self.pi_dtype if key == "mcts" else np.dtype(self.ARRAYS[key][1])
 
     TARGETS = "policy_targets.npy"
+    VALUES = "root_values.npy"
 
-    def _write_dense_shard(self, base: str, s, p, w, t=None):
-        """``t``: the rows' policy-target bytes; a ``_t.npy`` file is written only when one of them is 0."""
+    def _write_dense_shard(self, base: str, s, p, w, t=None, v=None):
+        """``t``: the rows' policy-target bytes; a ``_t.npy`` file is written only when one of them is 0. ``v``: the rows' root
+        values; a ``_v.npy`` file is written only when one of them is not NaN."""
+        if v is not None:
+            v = np.asarray(v, np.float32).reshape(-1)
+            if len(v) != len(w):
+                raise ValueError(f"{len(v)} root values for {len(w)} rows")
         if t is not None:
             t = (np.asarray(t).reshape(-1) != 0).astype(np.uint8)
             if len(t) != len(w):
@@ -207,6 +218,8 @@ class TupleSink:
         np.save(base + "_p.npy", p.astype(self.pi_dtype, copy=False).reshape(-1, 2086))
         if t is not None and not t.all():
             np.save(base + "_t.npy", t)
+        if v is not None and not np.isnan(v).all():
+            np.save(base + "_v.npy", v)
         np.save(base + "_z.npy", w.astype(np.float32, copy=False).reshape(-1))   # (written last: a shard counts once its z file exists)
         self._shards.append((base, int(len(w))))
 
@@ -218,8 +231,9 @@ class TupleSink:
                 json.dump({"iters": self.games}, f)
             os.replace(tmp, os.path.join(self.out_dir, "collect_state.json"))
 
-    def append(self, states, pi, z, games: int = 1, targets=None):
-        """``targets``: uint8 [rows] policy-target bytes or None (every row a target)."""
+    def append(self, states, pi, z, games: int = 1, targets=None, values=None):
+        """``targets``: uint8 [rows] policy-target bytes or None (every row a target); ``values``: float32 [rows] root values (NaN:
+        unknown) or None."""
         to_np = lambda t: t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
         s, p, w = to_np(states), to_np(pi), to_np(z)
         if len(w):
@@ -228,7 +242,7 @@ class TupleSink:
                 self._next += 1
                 base = os.path.join(self.out_dir, f".shard_{os.getpid()}_{self._next:06d}")
             self._next += 1
-            self._write_dense_shard(base, s, p, w, None if targets is None else to_np(targets))
+            self._write_dense_shard(base, s, p, w, None if targets is None else to_np(targets), None if values is None else to_np(values))
         self._count_games(games)
 
     # ---- compact record shards (what the batched collector writes while it runs) ----------------------
@@ -282,8 +296,8 @@ class TupleSink:
             from ._lib import CczError
             raise CczError(f"{self.out_dir}: {len(self._rshards)} record shard(s) ({sum(r[1] for r in self._rshards)} plies) wait for the GPU expander "
                            "(ccz_expand_records): run finalize() where the collector ran; nothing was changed")
-        from ._lib import REC_FAST, REC_FLAGS
-        from .engine import expand_record_targets, expand_records, game_aligned_chunks
+        from ._lib import REC_FAST, REC_FLAGS, REC_VALUE
+        from .engine import expand_record_targets, expand_record_values, expand_records, game_aligned_chunks
         for path, plies, flags, pot in list(self._rshards):
             tag = os.path.basename(path)[len(".rshard_"):-len(".npy")]
             prefix = f".shard_r{tag}_"
@@ -296,7 +310,8 @@ class TupleSink:
                 part = part.contiguous()
                 s, p, z = expand_records(part, flags, pot)
                 t = expand_record_targets(part, flags).cpu().numpy() if bool((part[:, REC_FLAGS] & REC_FAST).any()) else None
-                self._write_dense_shard(os.path.join(self.out_dir, f"{prefix}{k:04d}"), s.cpu().numpy(), p.cpu().numpy(), z.cpu().numpy(), t)
+                v = expand_record_values(part, flags).cpu().numpy() if bool((part[:, REC_FLAGS] & REC_VALUE).any()) else None
+                self._write_dense_shard(os.path.join(self.out_dir, f"{prefix}{k:04d}"), s.cpu().numpy(), p.cpu().numpy(), z.cpu().numpy(), t, v)
             os.remove(path)
             self._rshards.remove((path, plies, flags, pot))
 
@@ -389,9 +404,10 @@ class TupleSink:
             del out
             os.replace(tmp, paths[k])
         self._merge_targets(n_old, total, shards)
+        self._merge_side(self.VALUES, "_v.npy", np.float32, np.nan, n_old, total, shards)
         self._write_meta(total)
         for base, _ in shards:
-            for suffix in [sfx for sfx, _, _ in self.ARRAYS.values()] + ["_t.npy"]:
+            for suffix in [sfx for sfx, _, _ in self.ARRAYS.values()] + ["_t.npy", "_v.npy"]:
                 if os.path.exists(base + suffix):
                     os.remove(base + suffix)
         os.remove(self._journal())
@@ -399,27 +415,33 @@ class TupleSink:
     def _merge_targets(self, n_old: int, total: int, shards):
         """``policy_targets.npy`` next to the three arrays, if this merge or an earlier one saw a flagged row: the old rows (ones
         where there was no file), then every shard's ``_t.npy`` (ones where it has none). Skipped when already at ``total``."""
-        path = os.path.join(self.out_dir, self.TARGETS)
+        self._merge_side(self.TARGETS, "_t.npy", np.uint8, 1, n_old, total, shards)
+
+    def _merge_side(self, name: str, suffix: str, dtype, fill, n_old: int, total: int, shards):
+        """A row-aligned side array (``policy_targets.npy`` / ``root_values.npy``) that exists only once a shard brought its
+        ``suffix`` file: the old rows (``fill`` where there was no file), then every shard's file (``fill`` where it has none)."""
+        dtype = np.dtype(dtype)
+        path = os.path.join(self.out_dir, name)
         cur_n = None
         if os.path.exists(path):
             cur = np.load(path, mmap_mode="r")
-            if cur.dtype != np.uint8 or cur.ndim != 1 or int(cur.shape[0]) not in (n_old, total):
-                raise ValueError(f"{path}: {cur.dtype}{cur.shape}, the merge in progress expects uint8 ({n_old},) or ({total},)")
+            if cur.dtype != dtype or cur.ndim != 1 or int(cur.shape[0]) not in (n_old, total):
+                raise ValueError(f"{path}: {cur.dtype}{cur.shape}, the merge in progress expects {dtype} ({n_old},) or ({total},)")
             cur_n = int(cur.shape[0])
             del cur
-        if (cur_n == total and n_old != total) or (cur_n is None and not any(os.path.exists(b + "_t.npy") for b, _ in shards)):
+        if (cur_n == total and n_old != total) or (cur_n is None and not any(os.path.exists(b + suffix) for b, _ in shards)):
             return
         tmp = path + ".tmp"
-        out = np.lib.format.open_memmap(tmp, mode="w+", dtype=np.uint8, shape=(total,))
-        out[:] = 1
+        out = np.lib.format.open_memmap(tmp, mode="w+", dtype=dtype, shape=(total,))
+        out[:] = fill
         if cur_n is not None:
             out[:n_old] = np.load(path, mmap_mode="r")[:n_old]
         pos = n_old
         for base, n in shards:
-            if os.path.exists(base + "_t.npy"):
-                t = np.load(base + "_t.npy", mmap_mode="r")
-                if t.dtype != np.uint8 or t.shape != (n,):
-                    raise ValueError(f"{base}_t.npy: {t.dtype}{t.shape}, expected uint8({n},)")
+            if os.path.exists(base + suffix):
+                t = np.load(base + suffix, mmap_mode="r")
+                if t.dtype != dtype or t.shape != (n,):
+                    raise ValueError(f"{base}{suffix}: {t.dtype}{t.shape}, expected {dtype}({n},)")
                 out[pos:pos + n] = t
             pos += n
         out.flush()
@@ -485,7 +507,7 @@ class CollectPipeline:
                  data_dir: str = DATA_DIR, reference_quirks: bool = False, num_channels: int = 256, resblocks_num: int = 40,
                  finalize_every: int = 0, on_playout=None, max_plies: int = 0, eval_cache_log2: int | None = None, gatherer=None,
                  dense_shards: bool = False, replay_plies: int = 0, train_every: int = 0, train_batch: int = BATCH_SIZE,
-                 playout_cap_fast: int = 0, playout_cap_prob: float | None = None):
+                 playout_cap_fast: int = 0, playout_cap_prob: float | None = None, resign=None, value_q_weight: float = 0.0):
         # collect + train as one job (both 0: off): the rank that stores the union keeps it in a record ring of ``replay_plies`` plies
         # and runs one Trainer step of ``train_batch`` rows every ``train_every`` lockstep moves, once the ring holds a batch
         self.replay_plies, self.train_every, self.train_batch = int(replay_plies), int(train_every), int(train_batch)
@@ -513,6 +535,18 @@ class CollectPipeline:
             if not 0.0 <= float(playout_cap_prob) <= 1.0:
                 raise ValueError(f"playout_cap_prob must be in [0, 1] (got {playout_cap_prob})")
             self.playout_cap = (int(playout_cap_fast), float(playout_cap_prob))
+        # self-play resignation with play-on calibration (``resign``: a threshold, or a dict of SelfPlayEngine.set_resign's arguments;
+        # None = off) and the weight of the search's root value q in the trainer's value target ((1 - w) z + w q; 0 = z alone)
+        self.resign = None
+        if resign is not None:
+            if n_boards <= 1:
+                raise ValueError("resignation runs on the batched path: n_boards must be > 1")
+            self.resign = dict(resign) if isinstance(resign, dict) else {"threshold": float(resign)}
+        self.value_q_weight = float(value_q_weight)
+        if not 0.0 <= self.value_q_weight <= 1.0:
+            raise ValueError(f"value_q_weight must be in [0, 1] (got {value_q_weight})")
+        if self.value_q_weight and not self.train_every:
+            raise ValueError("value_q_weight weighs the trainer's value target: it needs train_every / replay_plies")
         self.board = Board()                       # collect.py:28 (never advanced: source of the turn-plane quirk)
         self.game = Game(self.board, reference_quirks=reference_quirks)
         self.temp = 1.0
@@ -639,7 +673,7 @@ class CollectPipeline:
                                             eval_cache_log2=(24 if self.n_boards >= 192 else 0) if self.eval_cache_log2 is None else int(self.eval_cache_log2),
                                             c_puct=self.c_puct, temp=self.temp, seed=self.seed, board_id_base=rank * self.n_boards,
                                             device=self.device, reference_quirks=self.reference_quirks, max_plies=self.max_plies,
-                                            playout_cap=self.playout_cap)
+                                            playout_cap=self.playout_cap, resign=getattr(self, "resign", None))
             if getattr(self, "_viewer", None) is not None:
                 self.selfplay.watch(0, self._viewer)
         for _ in range(n_moves):
@@ -791,11 +825,13 @@ class CollectPipeline:
             if self.trainer is None:
                 from .trainer import Trainer
                 self.trainer = Trainer(self.policy_value_net, amp_dtype="bf16")   # bf16: no GradScaler, so no host sync per update
-            if self.playout_cap is None:
+            qw = getattr(self, "value_q_weight", 0.0)
+            if self.playout_cap is None and not qw:
                 self.last_losses = self.trainer.step(*self.ring.sample(self.train_batch), sync=False)
-            else:   # fast plies train the value head only
-                st, pi, z, tg = self.ring.sample(self.train_batch, targets=True)
-                self.last_losses = self.trainer.step(st, pi, z, sync=False, policy_mask=tg)
+            else:   # fast plies train the value head only; rows that carry a root value blend it into the value target
+                st, pi, z, tg, q = self.ring.sample(self.train_batch, targets=True, values=True)
+                self.last_losses = self.trainer.step(st, pi, z, sync=False, policy_mask=None if self.playout_cap is None else tg,
+                                                     q=q if qw else None, q_weight=qw)
         if multi:
             from .replay import broadcast_model
             broadcast_model(self.policy_value_net, src=0, what="state")
@@ -812,6 +848,17 @@ class CollectPipeline:
         if self.selfplay is not None:
             out["error_flags"] = int(self.selfplay.engine.stats()["error_flags"])
         return out
+
+    def resign_report(self) -> str:
+        """The resignation part of the periodic log line (empty with resignation off; syncs): games resigned, the false-positive
+        rate ``playon_won / playon_games`` of the games played on, and their mean plies after the fire ply."""
+        if getattr(self, "resign", None) is None or getattr(self, "selfplay", None) is None:
+            return ""
+        r = self.selfplay.engine.resign_stats()
+        n = r["playon_games"]
+        fp = f"{r['playon_won'] / n:.3f}" if n else "n/a"
+        after = f"{r['playon_plies_after'] / n:.1f}" if n else "n/a"
+        return f", resigned {r['resigned_games']}, play-on {n} (false positives {fp}, mean plies after {after})"
 
     def drain_exchange(self, gatherer):
         """End of a multi-rank collection with an asynchronous exchange: blocking, every rank calls it; afterwards every record of
@@ -847,7 +894,7 @@ class CollectPipeline:
                 while max_calls <= 0 or calls < max_calls:
                     iters = self.collect_data(is_shown=is_shown)
                     calls += 1
-                    log(f"Episode {iters}, steps {self.episode_len}")
+                    log(f"Episode {iters}, steps {self.episode_len}" + self.resign_report())
             except KeyboardInterrupt:
                 log("Exit")
             if self.gatherer is not None and hasattr(self.gatherer, "flush_iter") and self.selfplay is not None:
@@ -888,12 +935,41 @@ def build_parser():
     parser.add_argument("--playout-cap-fast", type=int, default=0, help="playout-cap randomisation: simulations of a fast move (0 = off; needs "
                         "--playout-cap-prob). Fast plies are flagged and stay out of the policy loss")
     parser.add_argument("--playout-cap-prob", type=float, default=None, help="probability that a move is a full search of --playout simulations")
+    parser.add_argument("--resign-threshold", type=float, default=None, help="self-play resignation: the side to move resigns when its root value "
+                        "stayed below this (in [-1, 0]); absent = off. Root values are then recorded with every ply (root_values.npy)")
+    parser.add_argument("--resign-moves", type=int, default=None, help=f"... for this many of its full-search moves in a row (default {RESIGN_MOVES})")
+    parser.add_argument("--resign-min-ply", type=int, default=None, help=f"... and not before this ply (default {RESIGN_MIN_PLY})")
+    parser.add_argument("--resign-playon", type=float, default=None, help="fraction of such games played on to measure the false positives "
+                        f"(default {RESIGN_PLAYON}, AlphaGo Zero's)")
+    parser.add_argument("--value-q-weight", type=float, default=0.0, help="with --train-every: weight of the recorded root value q in the value "
+                        "target, (1 - w) z + w q on rows that carry one (0 = z alone)")
     return parser
 
 
-if __name__ == "__main__":
+RESIGN_MOVES, RESIGN_MIN_PLY, RESIGN_PLAYON = 2, 30, 0.1
+
+
+def parse_args(argv=None):
+    """Parse the command line; refuses ``--resign-moves`` / ``--resign-min-ply`` / ``--resign-playon`` without ``--resign-threshold``
+    (they would silently do nothing). ``args.resign`` is the dict for ``CollectPipeline(resign=...)`` or None."""
     parser = build_parser()
-    args = parser.parse_args()
+    args = parser.parse_args(argv)
+    extras = {"--resign-moves": args.resign_moves, "--resign-min-ply": args.resign_min_ply, "--resign-playon": args.resign_playon}
+    args.resign = None
+    if args.resign_threshold is None:
+        given = [k for k, v in extras.items() if v is not None]
+        if given:
+            parser.error(f"{', '.join(given)} without --resign-threshold: resignation is off")
+    else:
+        args.resign = {"threshold": args.resign_threshold,
+                       "consecutive": RESIGN_MOVES if args.resign_moves is None else args.resign_moves,
+                       "min_ply": RESIGN_MIN_PLY if args.resign_min_ply is None else args.resign_min_ply,
+                       "p_playon": RESIGN_PLAYON if args.resign_playon is None else args.resign_playon}
+    return args
+
+
+if __name__ == "__main__":
+    args = parse_args()
     # N collectors as ONE job (the reference starts N shell commands, README.md:31-48): python -m torch.distributed.run --nproc-per-node N
     # -m chinesechesszero_amd.collect ... -- every rank plays --boards boards, rank 0 stores the union of the finished games
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
@@ -920,7 +996,7 @@ if __name__ == "__main__":
                            num_channels=args.channels, resblocks_num=args.blocks, max_plies=args.max_plies, device=device,
                            eval_cache_log2=args.eval_cache_log2, gatherer=gatherer, replay_plies=args.replay_plies,
                            train_every=args.train_every, train_batch=args.train_batch, playout_cap_fast=args.playout_cap_fast,
-                           playout_cap_prob=args.playout_cap_prob)
+                           playout_cap_prob=args.playout_cap_prob, resign=args.resign, value_q_weight=args.value_q_weight)
     if world > 1:
         from .launch import guarded
 

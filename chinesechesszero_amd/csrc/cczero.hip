@@ -241,6 +241,16 @@ int ccz_create(const ccz_config *cfg, ccz_engine **out)
     ALLOC(d.budget, B);
     ALLOC(d.move_sims, B);
     ALLOC(d.target, B);
+    ResignCfg *rs_cfg = nullptr;
+    ALLOC(rs_cfg, 1); // zeroed: resignation off
+    d.rs_cfg = rs_cfg;
+    ALLOC(d.rs_state, B);
+    ALLOC(d.rs_run, B * 2);
+    ALLOC(d.rs_fire, B);
+    ALLOC(d.rs_last, B);
+    ALLOC(d.rec_value, B * d.max_plies);
+    ALLOC(d.rec_hasv, B * d.max_plies);
+    ALLOC(d.rs_stats, B);
     ALLOC(d.rec_ids, B * d.pi_cap);
     ALLOC(d.rec_pi, B * d.pi_cap);
     ALLOC(d.stats, B);
@@ -591,6 +601,58 @@ int ccz_draw_budgets(ccz_engine *e, void *stream, int32_t n_full, int32_t n_fast
                        budgets_out_dev);
     HIP_TRY(hipGetLastError());
     e->budgets_on = true;
+    return 0;
+}
+
+int ccz_set_resign(ccz_engine *e, void *stream, int32_t enabled, float threshold, int32_t consecutive, int32_t min_ply, double p_playon)
+{
+    NEED(e);
+    if (!(std::isfinite(threshold) && threshold >= -1.0f && threshold <= 0.0f)) return fail(-1, "ccz_set_resign: threshold %g must be finite and in [-1, 0]", (double)threshold);
+    if (consecutive < 0 || consecutive > 255) return fail(-1, "ccz_set_resign: consecutive %d must be 0..255", consecutive);
+    if (min_ply < 0) return fail(-1, "ccz_set_resign: negative min_ply %d", min_ply);
+    if (!(p_playon >= 0.0 && p_playon <= 1.0)) return fail(-1, "ccz_set_resign: p_playon %g must be in [0, 1]", p_playon);
+    ResignCfg v;
+    v.enabled = enabled ? 1 : 0;
+    v.consecutive = consecutive;
+    v.min_ply = min_ply;
+    v.threshold = threshold;
+    v.p_playon = p_playon;
+    hipLaunchKernelGGL(k_set_resign, dim3(1), dim3(1), 0, (hipStream_t)stream, const_cast<ResignCfg *>(e->d.rs_cfg), v);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int ccz_get_resign_stats(ccz_engine *e, void *stream, ccz_resign_stats *out)
+{
+    NEED(e);
+    if (!out) return fail(-1, "ccz_get_resign_stats: null output");
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<ResignBoardStats> st((size_t)e->d.B);
+    HIP_TRY(hipMemcpyAsync(st.data(), e->d.rs_stats, st.size() * sizeof(ResignBoardStats), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    memset(out, 0, sizeof *out);
+    for (const ResignBoardStats &b : st) {
+        out->resigned_games += (int64_t)b.resigned;
+        out->resigned_by_red += (int64_t)b.resigned_red;
+        out->resigned_plies += (int64_t)b.resigned_plies;
+        out->playon_games += (int64_t)b.playon;
+        out->playon_won += (int64_t)b.playon_won;
+        out->playon_drawn += (int64_t)b.playon_drawn;
+        out->playon_plies_after += (int64_t)b.playon_after;
+    }
+    return 0;
+}
+
+int ccz_resign_status(ccz_engine *e, void *stream, uint8_t *state_host, uint8_t *run_host, int32_t *fire_ply_host, float *last_value_host)
+{
+    NEED(e);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t B = (size_t)e->d.B;
+    if (state_host) HIP_TRY(hipMemcpyAsync(state_host, e->d.rs_state, B, hipMemcpyDeviceToHost, s));
+    if (run_host) HIP_TRY(hipMemcpyAsync(run_host, e->d.rs_run, B * 2, hipMemcpyDeviceToHost, s));
+    if (fire_ply_host) HIP_TRY(hipMemcpyAsync(fire_ply_host, e->d.rs_fire, B * 4, hipMemcpyDeviceToHost, s));
+    if (last_value_host) HIP_TRY(hipMemcpyAsync(last_value_host, e->d.rs_last, B * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
     return 0;
 }
 
@@ -995,6 +1057,39 @@ int ccz_sample_record_targets(void *stream, const void *ring_dev, int64_t cap_pl
     hipLaunchKernelGGL(k_sample_record_targets, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const uint8_t *)ring_dev,
                        (long long)cap_plies, (const long long *)window_dev, (const long long *)draws_dev, (long long)batch,
                        flags & CCZ_FLAG_NO_MIRROR, target_dev);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int ccz_expand_record_values(void *stream, const void *records_dev, int64_t n_plies, uint32_t flags, int64_t ring_rows, int64_t head_row,
+                             float *value_dev)
+{
+    if (n_plies < 0 || ring_rows < 0 || head_row < 0) return fail(-1, "ccz_expand_record_values: negative size");
+    if (n_plies == 0) return 0;
+    if (!records_dev || !value_dev) return fail(-1, "ccz_expand_record_values: null buffer");
+    if (((uintptr_t)records_dev | (uintptr_t)value_dev) & 3) return fail(-1, "ccz_expand_record_values: the records and the values must be 4-byte aligned");
+    if (n_plies > (int64_t)INT32_MAX) return fail(-1, "ccz_expand_record_values: too many records for one launch");
+    const int64_t rows = n_plies * ((flags & CCZ_FLAG_NO_MIRROR) ? 1 : 2);
+    if (ring_rows > 0 && rows > ring_rows) return fail(-1, "ccz_expand_record_values: %lld rows do not fit a ring of %lld", (long long)rows, (long long)ring_rows);
+    if (ring_rows == 0 && head_row != 0) return fail(-1, "ccz_expand_record_values: head_row needs ring_rows");
+    hipLaunchKernelGGL(k_expand_record_values, dim3((unsigned)((n_plies + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const uint8_t *)records_dev,
+                       (long long)n_plies, flags & CCZ_FLAG_NO_MIRROR, (long long)ring_rows, (long long)head_row, value_dev);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int ccz_sample_record_values(void *stream, const void *ring_dev, int64_t cap_plies, const int64_t *window_dev, const int64_t *draws_dev,
+                             int64_t batch, uint32_t flags, float *value_dev)
+{
+    if (cap_plies <= 0 || batch < 0) return fail(-1, "ccz_sample_record_values: capacity must be positive and batch non-negative");
+    if (batch == 0) return 0;
+    if (!ring_dev || !window_dev || !draws_dev || !value_dev) return fail(-1, "ccz_sample_record_values: null buffer");
+    if (((uintptr_t)ring_dev | (uintptr_t)value_dev) & 3) return fail(-1, "ccz_sample_record_values: the ring and the values must be 4-byte aligned");
+    if (((uintptr_t)window_dev | (uintptr_t)draws_dev) & 7) return fail(-1, "ccz_sample_record_values: window and draws must be 8-byte aligned");
+    if (batch > (int64_t)INT32_MAX) return fail(-1, "ccz_sample_record_values: too many rows for one launch");
+    hipLaunchKernelGGL(k_sample_record_values, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const uint8_t *)ring_dev,
+                       (long long)cap_plies, (const long long *)window_dev, (const long long *)draws_dev, (long long)batch,
+                       flags & CCZ_FLAG_NO_MIRROR, value_dev);
     HIP_TRY(hipGetLastError());
     return 0;
 }

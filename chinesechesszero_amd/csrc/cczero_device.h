@@ -67,6 +67,19 @@ struct BoardStats {
     unsigned int cache_verified, cache_mismatch;
 };
 
+// Self-play resignation (ccz_set_resign): the settings as the device reads them, and the per-board calibration counters.
+struct ResignCfg {
+    int32_t enabled;     // 0: k_finish_move records no root value and keeps no run counter
+    int32_t consecutive; // full-search plies in a row below the threshold before a side resigns; 0: values and counters only
+    int32_t min_ply;     // no resignation before this ply
+    float threshold;     // root value (side to move's view) below which a ply counts
+    double p_playon;     // fraction of the games the rule fires in that are played on (the false-positive measurement)
+};
+constexpr uint8_t kResigned = 2, kPlayOn = 4; // Dev.rs_state, and the record header's CCZ_REC_RESIGNED / CCZ_REC_PLAYON
+struct ResignBoardStats {
+    unsigned long long resigned, resigned_red, resigned_plies, playon, playon_won, playon_drawn, playon_after;
+};
+
 struct Dev {
     int32_t B, cap, maxd, max_plies, pi_cap;
     int32_t reserve;   // nodes of every pool half kept free at re-root time for the next move's expansions
@@ -127,6 +140,16 @@ struct Dev {
     int32_t *move_sims;  // [B] simulations backed up since the board's last move boundary
     uint8_t *target;     // [B] 1: this move's pi is a policy target (0: a fast move of playout-cap randomisation)
     uint8_t *rec_target; // [B][max_plies] `target` as it stood when the ply was recorded
+    // ---- self-play resignation (ccz_set_resign). Always allocated; "off" is ResignCfg.enabled == 0: k_finish_move then reads that
+    // one word and touches none of the arrays below, so records, moves and counters are what they are without the feature
+    const ResignCfg *rs_cfg; // [1] written by k_set_resign in stream order (nothing of it is a kernel argument: a captured graph holds no setting)
+    uint8_t *rs_state;       // [B] 0, or kResigned / kPlayOn | the side that resigned (would have resigned) in bit 0
+    uint8_t *rs_run;         // [B][2] consecutive full-search plies of side s whose root value was below the threshold (saturates at 255)
+    int32_t *rs_fire;        // [B] ply at which the rule fired (-1: it has not)
+    float *rs_last;          // [B] root value of the last recorded ply (NaN: none in this game)
+    float *rec_value;        // [B][max_plies] root value of the ply, in the view of its side to move
+    uint8_t *rec_hasv;       // [B][max_plies] 1: rec_value holds the ply's value
+    ResignBoardStats *rs_stats; // [B]
 };
 __device__ __forceinline__ int plane_of(const Dev &D, int type) { return (int)((D.chanpack >> (3 * type)) & 7u); }
 __device__ __forceinline__ int type_in_plane(const Dev &D, int chan) { return (int)((D.typepack >> (3 * chan)) & 7u) + 1; }

@@ -40,6 +40,27 @@ __device__ __forceinline__ void fresh_root(const Dev &D, int b, int half)
     D.move_sims[b] = 0; // a move boundary: the board's simulation budget (Dev.budget) starts over
 }
 
+// A new game carries no resignation state: no run of low values, no play-on lot, no last value (the calibration counters in
+// Dev.rs_stats are sums over games and stay). One lane. Called wherever a game starts; k_reset_tree keeps the state.
+__device__ __forceinline__ void resign_clear(const Dev &D, int b)
+{
+    D.rs_state[b] = 0;
+    D.rs_run[(size_t)b * 2] = 0;
+    D.rs_run[(size_t)b * 2 + 1] = 0;
+    D.rs_fire[b] = -1;
+    D.rs_last[b] = __builtin_nanf("");
+}
+
+// A game that drew the play-on lot has ended with winner w after T plies: what resigning at the fire ply would have cost or saved
+__device__ __forceinline__ void playon_count(const Dev &D, int b, int state, int winner, int T)
+{
+    ResignBoardStats &rs = D.rs_stats[b];
+    rs.playon += 1;
+    if (winner < 0) rs.playon_drawn += 1;
+    else if (winner == (state & 1)) rs.playon_won += 1; // the side that would have resigned won: a false positive
+    rs.playon_after += (unsigned long long)(T - D.rs_fire[b]);
+}
+
 // (re)initialise board b from D.root_sq[b] / the given turn+halfmove: key, chain, fresh tree, empty record
 __device__ inline void init_board(const Dev &D, int b, int lane, int turn, int halfmove, bool new_game_no)
 {
@@ -70,6 +91,7 @@ __device__ inline void init_board(const Dev &D, int b, int lane, int turn, int h
         D.chain_chk[(size_t)b * 2] = 0ull; // (the first position of a chain never lies inside a repetition window)
         D.chain_chk[(size_t)b * 2 + 1] = 0ull;
         fresh_root(D, b, m.half);
+        resign_clear(D, b);
     }
 }
 
@@ -1312,13 +1334,17 @@ __global__ __launch_bounds__(64) void k_finish_move(Dev D, const int32_t *forced
             D.meta[b] = m;
             D.stats[b].truncated += 1;
             D.stats[b].games += 1;
+            const int rstate = D.rs_state[b];
+            if (rstate & kPlayOn) playon_count(D, b, rstate, -1, m.ply);
         }
         return;
     }
+    const ResignCfg rc = *D.rs_cfg;
+    const int tgt = D.target[b];
     {
         const size_t r = (size_t)b * D.max_plies + CCZ_IDX(D, m.ply, D.max_plies);
         if (lane < 24) ((uint32_t *)(D.rec_sq + r * 96))[lane] = ((const uint32_t *)s_sq)[lane];
-        if (lane == 0) { D.rec_turn[r] = m.turn; D.rec_k[r] = (uint8_t)k; D.rec_off[r] = m.pi_used; D.rec_target[r] = D.target[b]; }
+        if (lane == 0) { D.rec_turn[r] = m.turn; D.rec_k[r] = (uint8_t)k; D.rec_off[r] = m.pi_used; D.rec_target[r] = (uint8_t)tgt; D.rec_hasv[r] = 0; }
         const size_t po = (size_t)b * D.pi_cap + m.pi_used;
         for (int i = lane; i < k; i += 64) {
             const size_t o = (size_t)b * D.pi_cap + CCZ_IDX(D, m.pi_used + (uint32_t)i, D.pi_cap);
@@ -1326,6 +1352,62 @@ __global__ __launch_bounds__(64) void k_finish_move(Dev D, const int32_t *forced
             D.rec_pi[o] = (float)s_pi[i];
         }
         (void)po;
+    }
+
+    // ---- resignation (ccz_set_resign; off: one word read above, nothing below runs). The root value is the visit-weighted mean of
+    // the children's Q as stored (the view of the root's side to move), summed in child order in float64: every lane runs the same
+    // <= 128 terms on the same LDS words, so the decision is wave-uniform without a broadcast. s_g is free until sample_move.
+    if (rc.enabled) {
+        for (int i = lane; i < k; i += 64) s_g[i] = (double)A[CCZ_IDX(D, root.fc + i, D.cap)].Q;
+        __syncthreads();
+        double acc = 0.0;
+        long long nsum = 0;
+        for (int i = 0; i < k; ++i) { acc = acc + (double)s_vis[i] * s_g[i]; nsum += s_vis[i]; }
+        const double v = nsum ? acc / (double)nsum : 0.0;
+        const int s = m.turn;
+        const int state = D.rs_state[b];
+        int run = D.rs_run[(size_t)b * 2 + s];
+        if (tgt) { run = v < (double)rc.threshold ? (run < 255 ? run + 1 : 255) : 0; } // a fast ply records v and leaves the run alone
+        bool fire = tgt && rc.consecutive > 0 && run >= rc.consecutive && m.ply >= rc.min_ply && want < 0 && !(state & kPlayOn);
+        bool playon = false;
+        if (fire) { // the lot: word 0xffd of the board's Philox stream for this move (Gamma draws: 0..127, budgets: 0xffe, move choice: 0xfff)
+            double ua, ub;
+            uniform2(D.seed, D.board_id_base + (uint64_t)b, m.move_counter, 0xffdu, 0, ua, ub);
+            playon = ua < rc.p_playon;
+            fire = !playon;
+        }
+        __syncthreads(); // s_g is read above by every lane before sample_move writes it
+        if (lane == 0) {
+            const size_t r = (size_t)b * D.max_plies + CCZ_IDX(D, m.ply, D.max_plies);
+            D.rec_value[r] = (float)v;
+            D.rec_hasv[r] = 1;
+            D.rs_last[b] = (float)v;
+            if (tgt) D.rs_run[(size_t)b * 2 + s] = (uint8_t)run;
+            if (playon) { D.rs_state[b] = (uint8_t)(kPlayOn | s); D.rs_fire[b] = m.ply; }
+        }
+        if (fire) {
+            // the side to move resigns: the ply is a sample like any other (the search was done), no move is pushed -- root position,
+            // key, clock, history chain and check bits stay -- and the new pool half keeps the empty root written above
+            if (lane == 0) {
+                D.rs_state[b] = (uint8_t)(kResigned | s);
+                D.rs_fire[b] = m.ply;
+                m.ply += 1;
+                m.move_counter += 1;
+                m.n_nodes = 1;
+                m.half = (uint8_t)nh;
+                m.pi_used += (uint32_t)k;
+                m.over = 1;
+                m.winner = (int8_t)(s ^ 1);
+                D.meta[b] = m;
+                D.stats[b].games += 1;
+                D.leaf_status[b] = CCZ_LEAF_SKIP;
+                ResignBoardStats &rs = D.rs_stats[b];
+                rs.resigned += 1;
+                rs.resigned_red += (unsigned long long)s;
+                rs.resigned_plies += (unsigned long long)m.ply;
+            }
+            return;
+        }
     }
 
     // ---- move choice (mcts.py:216-229)
@@ -1456,6 +1538,8 @@ __global__ __launch_bounds__(64) void k_finish_move(Dev D, const int32_t *forced
             m.over = 1;
             m.winner = L.n_legal == 0 ? (int8_t)(turn ^ 1) : (int8_t)perpetual_winner; // no legal move: side to move loses
             st.games += 1;
+            const int rstate = D.rs_state[b];
+            if (rstate & kPlayOn) playon_count(D, b, rstate, m.winner, m.ply);
         }
         D.meta[b] = m;
         D.leaf_status[b] = CCZ_LEAF_SKIP;
@@ -1583,6 +1667,7 @@ __global__ __launch_bounds__(64) void k_set_positions(Dev D, const uint8_t *mask
         D.chain_chk[(size_t)b * 2] = chk0;
         D.chain_chk[(size_t)b * 2 + 1] = chk1;
         fresh_root(D, b, m.half);
+        resign_clear(D, b);
         status_out[b] = status;
     }
 }
@@ -1753,6 +1838,8 @@ __global__ __launch_bounds__(256) void k_harvest(Dev D, const long long *row_bas
 // 2 x 29,768 B of dense rows: what the all-gather moves (k_expand_records rebuilds the rows on the receiving side).
 constexpr int kRecBytes = 880, kRecHdr = 96, kRecIds = 112, kRecPi = 368;
 constexpr uint8_t kRecFast = 1; // PlyHeader.flags (CCZ_REC_FAST): a fast move of playout-cap randomisation, its pi is no policy target
+constexpr uint8_t kRecValue = 8; // PlyHeader.flags (CCZ_REC_VALUE): bytes 92..95 of the record hold the ply's root value (float32)
+constexpr int kRecValueOff = 92; // (flags 2 and 4, CCZ_REC_RESIGNED / CCZ_REC_PLAYON on every ply of such a game, are kResigned / kPlayOn)
 struct __align__(4) PlyHeader {
     uint16_t t, T;      // ply index inside its game, plies of the game
     int8_t winner;      // 1 RED, 0 BLACK, -1 draw
@@ -1778,12 +1865,12 @@ __global__ __launch_bounds__(256) void k_harvest_records(Dev D, const long long 
         if (tid < 24) {
             uint32_t v = ((const uint32_t *)(D.rec_sq + r * 96))[tid];
             if (tid == 22) v &= 0x0000ffffu;
-            if (tid == 23) v = 0u;
+            if (tid == 23) v = D.rec_hasv[r] ? __float_as_uint(D.rec_value[r]) : 0u; // bytes 92..95: the ply's root value (CCZ_REC_VALUE)
             rec[tid] = v;
         } else if (tid == 24) {
             PlyHeader h;
             h.t = (uint16_t)t; h.T = (uint16_t)T; h.winner = m.winner; h.turn = D.rec_turn[r]; h.k = (uint8_t)k;
-            h.flags = D.rec_target[r] ? 0 : kRecFast;
+            h.flags = (uint8_t)((D.rec_target[r] ? 0 : kRecFast) | (D.rs_state[b] & (kResigned | kPlayOn)) | (D.rec_hasv[r] ? kRecValue : 0));
             h.board_id = (uint32_t)(D.board_id_base + (uint64_t)b); h.game_no = m.game_no;
             *(PlyHeader *)(rec + kRecHdr / 4) = h;
         }
@@ -2056,6 +2143,60 @@ __global__ void k_sample_record_targets(const uint8_t *ring, long long cap_plies
         if (h.t < h.T && h.k <= kMaxLegal && first >= tail && first + h.T <= head) v = (h.flags & kRecFast) ? 0 : 1;
     }
     target[j] = v;
+}
+
+// The root value of every dense row k_expand_records writes (k_expand_record_targets' row indexing and validity rule): the sample
+// and its mirror image carry their ply's value -- a position and its mirror image have the same value. NaN where there is none:
+// a ply without CCZ_REC_VALUE, and the rows a cut game leaves unwritten.
+__global__ void k_expand_record_values(const uint8_t *recs, long long n_plies, uint32_t flags, long long ring_rows, long long head,
+                                       float *value)
+{
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n_plies) return;
+    const uint8_t *rec = recs + (size_t)p * kRecBytes;
+    const PlyHeader h = *(const PlyHeader *)(rec + kRecHdr);
+    const long long mul = (flags & 2u) ? 1 : 2;
+    const int t = h.t, T = h.T;
+    const long long first = p - t;
+    const float none = __builtin_nanf("");
+    if (first < 0 || t >= T || first + T > n_plies || h.k > kMaxLegal) {
+        for (long long q = 0; q < mul; ++q) {
+            const long long row = head + mul * p + q;
+            value[ring_rows > 0 ? row % ring_rows : row] = none;
+        }
+        return;
+    }
+    const float v = (h.flags & kRecValue) ? *(const float *)(rec + kRecValueOff) : none;
+    for (long long pass = 0; pass < mul; ++pass) {
+        const long long row = head + mul * first + (pass ? T : 0) + t;
+        value[ring_rows > 0 ? row % ring_rows : row] = v;
+    }
+}
+
+// The root value of every row k_sample_records forms (same draw -> ply map, same validity rule): NaN for a bad draw and for a ply
+// without CCZ_REC_VALUE.
+__global__ void k_sample_record_values(const uint8_t *ring, long long cap_plies, const long long *window, const long long *draws,
+                                       long long batch, uint32_t flags, float *value)
+{
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= batch) return;
+    const long long mul = (flags & 2u) ? 1 : 2;
+    const long long tail = window[0], head = window[1], u = draws[j];
+    float v = __builtin_nanf("");
+    if (tail >= 0 && head > tail && head - tail <= cap_plies && u >= 0) {
+        const long long p = tail + (u % ((head - tail) * mul)) / mul;
+        const uint8_t *rec = ring + (size_t)CCZ_RING_IDX((int32_t *)nullptr, p % cap_plies, cap_plies) * kRecBytes;
+        const PlyHeader h = *(const PlyHeader *)(rec + kRecHdr);
+        const long long first = p - h.t;
+        if (h.t < h.T && h.k <= kMaxLegal && first >= tail && first + h.T <= head && (h.flags & kRecValue)) v = *(const float *)(rec + kRecValueOff);
+    }
+    value[j] = v;
+}
+
+// ccz_set_resign: the settings reach the device in stream order, so they hold from the next k_finish_move on
+__global__ void k_set_resign(ResignCfg *cfg, ResignCfg v)
+{
+    if (blockIdx.x == 0 && threadIdx.x == 0) *cfg = v;
 }
 
 // ------------------------------------------------------------------ stateless batch rules

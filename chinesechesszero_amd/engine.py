@@ -389,6 +389,35 @@ class SelfPlayEngine:
         check(self.L.ccz_draw_budgets(self.h, self._stream(), int(n_full), int(n_fast), float(p_full), _ptr(self.budgets_out)))
         return self.budgets_out
 
+    # ------------------------------------------------------------------ resignation (include/cczero.h ccz_set_resign)
+    def set_resign(self, threshold, consecutive: int = 2, min_ply: int = 30, p_playon: float = 0.1):
+        """Self-play resignation from the next :meth:`finish_move` on: the side to move resigns when the root value of its last
+        ``consecutive`` full-search plies was below ``threshold`` (in [-1, 0]) and the game has at least ``min_ply`` plies; a
+        fraction ``p_playon`` of such games is played on instead, for :meth:`resign_stats` to measure the false positives.
+        ``consecutive`` 0: root values are recorded (``REC_VALUE``) and nothing resigns. ``threshold`` None: off, the state of a
+        new engine. No host sync."""
+        if threshold is None:
+            check(self.L.ccz_set_resign(self.h, self._stream(), 0, 0.0, 0, 0, 0.0))
+            return
+        check(self.L.ccz_set_resign(self.h, self._stream(), 1, float(threshold), int(consecutive), int(min_ply), float(p_playon)))
+
+    def resign_status(self) -> dict:
+        """Per-board resignation state (syncs): ``state`` uint8 [B] (0, or ``RESIGN_RESIGNED`` / ``RESIGN_PLAYON`` | side), ``run``
+        uint8 [B,2] (indexed by side: 1 red), ``fire_ply`` int32 [B] (-1: not fired), ``last_value`` float32 [B] (NaN: none)."""
+        B = self.B
+        state = np.zeros(B, np.uint8)
+        run = np.zeros((B, 2), np.uint8)
+        fire = np.zeros(B, np.int32)
+        last = np.zeros(B, np.float32)
+        check(self.L.ccz_resign_status(self.h, self._stream(), _ptr(state), _ptr(run), _ptr(fire), _ptr(last)))
+        return {"state": state, "run": run, "fire_ply": fire, "last_value": last}
+
+    def resign_stats(self) -> dict:
+        """The calibration counters (``ccz_resign_stats``; syncs): the false-positive rate is ``playon_won / playon_games``."""
+        s = _lib.ResignStats()
+        check(self.L.ccz_get_resign_stats(self.h, self._stream(), C.byref(s)))
+        return {f: int(getattr(s, f)) for f, _ in _lib.ResignStats._fields_}
+
     def _to_dev(self, x, dtype, name):
         t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x, dtype={torch.int32: np.int32, torch.uint8: np.uint8}[dtype]))
         t = t.to(device=self.device, dtype=dtype).contiguous()
@@ -663,6 +692,31 @@ def expand_record_targets(records: torch.Tensor, flags: int = 0, out=None, head_
         check(L.ccz_expand_record_targets(C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), _ptr(records), P, int(flags), ring,
                                           int(head_row) if ring else 0, _ptr(target)))
     return target
+
+
+def expand_record_values(records: torch.Tensor, flags: int = 0, out=None, head_row: int = 0) -> torch.Tensor:
+    """The root value (``REC_VALUE`` plies: record bytes 92..95, the side to move's view) of every row :func:`expand_records`
+    writes for ``records`` (``ccz_expand_record_values``): float32 [R], the mirror row carries its ply's value, NaN for a ply
+    without a value and for rows of cut games. ``out``: a float32 ring [N] written at (head_row + i) % N. Asynchronous."""
+    L = _lib.lib()
+    if not (records.is_cuda and records.dtype == torch.uint8 and records.is_contiguous()):
+        raise ValueError("records must be a contiguous uint8 device tensor")
+    if records.numel() % _lib.REC_BYTES:
+        raise ValueError("records must hold whole 880-byte ply records")
+    P = records.numel() // _lib.REC_BYTES
+    dev = records.device
+    if out is None:
+        value = torch.full((rows_of_records(P, flags),), float("nan"), dtype=torch.float32, device=dev)
+        ring = 0
+    else:
+        value = out
+        ring = int(value.shape[0])
+        if not (value.is_contiguous() and value.dtype == torch.float32 and value.dim() == 1 and value.device == dev):
+            raise ValueError("out must be a contiguous float32 [N] tensor on the records' device")
+    with torch.cuda.device(dev):
+        check(L.ccz_expand_record_values(C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), _ptr(records), P, int(flags), ring,
+                                         int(head_row) if ring else 0, _ptr(value)))
+    return value
 
 
 # ---------------------------------------------------------------------- stateless batch rules

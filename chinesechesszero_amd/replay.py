@@ -662,7 +662,9 @@ class TupleGatherer(_FusedGather):
 class ReplayBuffer:
     """Fixed-capacity ring of training rows resident in HBM (sized for 288 GB: 1M rows = 30 GB). A parallel uint8 ring
     (``targets``) holds every row's policy-target byte: 0 for the fast plies of playout-cap randomisation (``REC_FAST`` records),
-    1 for everything else, rows appended without a flag included."""
+    1 for everything else, rows appended without a flag included. A parallel float32 ring (``values``) holds every row's root
+    value (the search's value of the position, side to move's view: ``REC_VALUE`` records, or what :meth:`append` is given), NaN
+    where none is known."""
 
     def __init__(self, capacity_rows: int, device):
         d = torch.device(device)
@@ -671,24 +673,29 @@ class ReplayBuffer:
         self.pi = torch.zeros((self.cap, NMOVES), dtype=torch.float32, device=d)
         self.z = torch.zeros((self.cap,), dtype=torch.float32, device=d)
         self.targets = torch.ones((self.cap,), dtype=torch.uint8, device=d)
+        self.values = torch.full((self.cap,), float("nan"), dtype=torch.float32, device=d)
         self.size = 0
         self.head = 0
         self.total = 0
 
-    def append(self, states, pi, z, targets=None):
-        """``targets`` uint8 [n] or None (every row a policy target)."""
+    def append(self, states, pi, z, targets=None, values=None):
+        """``targets`` uint8 [n] or None (every row a policy target); ``values`` float32 [n] or None (no root value known: NaN)."""
         n = int(states.shape[0])
         if n == 0:
             return
         if targets is None:
             targets = torch.ones((n,), dtype=torch.uint8, device=self.targets.device)
+        if values is None:
+            values = torch.full((n,), float("nan"), dtype=torch.float32, device=self.values.device)
         if n > self.cap:
-            states, pi, z, targets = states[-self.cap:], pi[-self.cap:], z[-self.cap:], targets[-self.cap:]
+            states, pi, z, targets, values = states[-self.cap:], pi[-self.cap:], z[-self.cap:], targets[-self.cap:], values[-self.cap:]
             n = self.cap
         first = min(n, self.cap - self.head)
         self.targets[self.head:self.head + first].copy_(targets[:first])
+        self.values[self.head:self.head + first].copy_(values[:first])
         if n > first:
             self.targets[:n - first].copy_(targets[first:])
+            self.values[:n - first].copy_(values[first:])
         self.states[self.head:self.head + first].copy_(states[:first])
         self.pi[self.head:self.head + first].copy_(pi[:first])
         self.z[self.head:self.head + first].copy_(z[:first])
@@ -704,7 +711,7 @@ class ReplayBuffer:
     def append_records(self, records: torch.Tensor, flags: int = 0, plane_of_type=None, bad=None) -> int:
         """Expand compact ply records (uint8 [P, 880], whole games; :class:`RecordGatherer`'s output) straight INTO the ring:
         ``ccz_expand_records`` writes the dense rows at (head + i) % capacity, no intermediate copy. Returns the rows added."""
-        from .engine import expand_record_targets, expand_records, game_aligned_chunks, rows_of_records
+        from .engine import expand_record_targets, expand_record_values, expand_records, game_aligned_chunks, rows_of_records
         mul = rows_of_records(1, flags)
         if rows_of_records(int(records.shape[0]), flags) > self.cap:  # more than the ring holds: game by game, the ring wraps
             if self.cap < mul:
@@ -720,17 +727,26 @@ class ReplayBuffer:
         rec = rec.contiguous()
         expand_records(rec, flags, plane_of_type, out=(self.states, self.pi, self.z), head_row=self.head, bad=bad)
         expand_record_targets(rec, flags, out=self.targets, head_row=self.head)
+        expand_record_values(rec, flags, out=self.values, head_row=self.head)
         self.head = (self.head + n) % self.cap
         self.size = min(self.cap, self.size + n)
         self.total += n
         return n
 
-    def sample(self, batch: int, generator=None, targets: bool = False):
-        """``targets``: also return the rows' policy-target bytes (uint8 [batch]) as a fourth tensor."""
+    def sample(self, batch: int, generator=None, targets: bool = False, values: bool = False):
+        """``targets``: also return the rows' policy-target bytes (uint8 [batch]); ``values``: also their root values (float32
+        [batch], NaN where unknown) -- appended after (states, pi, z) in this order."""
         idx = torch.randint(0, self.size, (batch,), device=self.states.device, generator=generator)
+        return self.sample_at(idx, targets=targets, values=values)
+
+    def sample_at(self, idx: torch.Tensor, targets: bool = False, values: bool = False):
+        """The rows at ring indices ``idx`` (int64, below ``size``): what :meth:`sample` returns for these draws."""
+        out = (self.states[idx], self.pi[idx], self.z[idx])
         if targets:
-            return self.states[idx], self.pi[idx], self.z[idx], self.targets[idx]
-        return self.states[idx], self.pi[idx], self.z[idx]
+            out += (self.targets[idx],)
+        if values:
+            out += (self.values[idx],)
+        return out
 
 
 class RecordReplayBuffer:
@@ -829,12 +845,14 @@ class RecordReplayBuffer:
         self.total += P * self.mul
         return P * self.mul
 
-    def sample_at(self, draws: torch.Tensor, bad=None, targets: bool = False):
+    def sample_at(self, draws: torch.Tensor, bad=None, targets: bool = False, values: bool = False):
         """Rows of the given draws (int64 [batch] on the ring's device, non-negative): draw ``u`` is row ``u % live`` of the window,
         ``live = (head - tail) x mul`` read on the device; row ``r`` is ply ``tail + r // mul``, pass ``r % mul`` (1 = mirror image).
         Returns ``(states fp16 [batch,17,7,10,9], pi f32 [batch,2086], z f32 [batch])`` as :meth:`ReplayBuffer.sample` does.
         ``targets``: a fourth tensor, uint8 [batch] -- 1 where the row is a policy target, 0 for a ``REC_FAST`` ply (a fast move
-        of playout-cap randomisation) and for a bad draw (``ccz_sample_record_targets``)."""
+        of playout-cap randomisation) and for a bad draw (``ccz_sample_record_targets``). ``values``: a further tensor, float32
+        [batch] -- the ply's root value (a ``REC_VALUE`` record's bytes 92..95; a row and its mirror image carry the same), NaN for
+        a ply without one and for a bad draw (``ccz_sample_record_values``)."""
         from . import _lib
         from .engine import _ptr
         if self.head == 0:
@@ -850,21 +868,27 @@ class RecordReplayBuffer:
             _lib.check(_lib.lib().ccz_sample_records(self._stream(), _ptr(self.records), self.cap, _ptr(self._window), _ptr(draws), n,
                                                      self.flags, self._pot(), _ptr(states), _ptr(pi), _ptr(z),
                                                      _ptr(self.bad if bad is None else bad)))
+            out = (states, pi, z)
             if targets:
                 tg = torch.empty((n,), dtype=torch.uint8, device=d)
                 _lib.check(_lib.lib().ccz_sample_record_targets(self._stream(), _ptr(self.records), self.cap, _ptr(self._window), _ptr(draws), n,
                                                                 self.flags, _ptr(tg)))
-                return states, pi, z, tg
-        return states, pi, z
+                out += (tg,)
+            if values:
+                vals = torch.empty((n,), dtype=torch.float32, device=d)
+                _lib.check(_lib.lib().ccz_sample_record_values(self._stream(), _ptr(self.records), self.cap, _ptr(self._window), _ptr(draws), n,
+                                                               self.flags, _ptr(vals)))
+                out += (vals,)
+        return out
 
-    def sample(self, batch: int, generator=None, targets: bool = False):
+    def sample(self, batch: int, generator=None, targets: bool = False, values: bool = False):
         """A uniform minibatch over the live rows, mirror images included, without a host sync: the draws are
         ``torch.randint(0, 2**62)`` on the device and the kernel reduces them modulo the live row count, which only the device
         knows. The modulo bias is below ``live / 2**62`` < 2**-28 for any ring that fits in HBM (live < 2**34 rows)."""
         if self.head == 0:
             raise ValueError("the replay ring is empty: nothing was ever appended")
         draws = torch.randint(0, 2 ** 62, (int(batch),), device=self.records.device, dtype=torch.int64, generator=generator)
-        return self.sample_at(draws, targets=targets)
+        return self.sample_at(draws, targets=targets, values=values)
 
     def window(self):
         """``(tail, head)`` in logical plies, as the device has them after everything queued so far (syncs)."""

@@ -216,7 +216,7 @@ class BatchedSelfPlay:
 
     def __init__(self, evaluator, n_boards: int, n_playout: int = 400, c_puct: float = C_PUCT, eps: float = EPS,
                  alpha: float = ALPHA, temp: float = 1.0, seed: int = 0, board_id_base: int = 0, device: int = 0,
-                 sampling: str = "device", use_graph: bool = False, version_fn=None, playout_cap=None, **engine_kw):
+                 sampling: str = "device", use_graph: bool = False, version_fn=None, playout_cap=None, resign=None, **engine_kw):
         """``playout_cap`` = ``(n_fast, p_full)``: playout-cap randomisation -- every move of every board is a full search of
         ``n_playout`` simulations with probability ``p_full``, else a fast one of ``n_fast``; fast plies carry ``REC_FAST`` in their
         record header so that a trainer can keep them out of the policy loss (``engine.draw_budgets``). The loop still runs
@@ -225,11 +225,16 @@ class BatchedSelfPlay:
         still computes all B rows. The budgets are drawn by :meth:`advance` (so by :meth:`search` and :meth:`run_move`) at a move's
         first simulation; :meth:`simulate` draws nothing and searches with the budgets the engine holds.
         None (default): every board searches ``n_playout`` simulations, as ever.
+        ``resign``: a threshold in [-1, 0], or a dict of :meth:`SelfPlayEngine.set_resign`'s arguments (``threshold``,
+        ``consecutive``, ``min_ply``, ``p_playon``): self-play resignation with play-on calibration. Device sampling only: with
+        host sampling every move is forced and a forced board never resigns. None (default): off.
         ``version_fn() -> hashable``: what tells the evaluation cache (and a captured hipGraph) that the evaluator's weights
         changed; default: ``weights_version`` of the evaluator's owner. An evaluator that accepts a plan but exposes neither is
         refused: its cached evaluations could never be invalidated."""
         if sampling not in ("device", "numpy"):
             raise ValueError("sampling must be 'device' (Philox on the GPU) or 'numpy' (reference-exact host RNG)")
+        if resign is not None and sampling != "device":
+            raise ValueError("resign needs sampling='device': with host sampling every move is forced, and a forced board never resigns")
         self.playout_cap = None
         if playout_cap is not None:
             n_fast, p_full = playout_cap
@@ -241,6 +246,10 @@ class BatchedSelfPlay:
         self.evaluator = evaluator
         self.engine = SelfPlayEngine(n_boards, n_playout=n_playout, c_puct=c_puct, eps=eps, alpha=alpha, temp=temp,
                                      seed=seed, board_id_base=board_id_base, device=device, **engine_kw)
+        self.resign = None
+        if resign is not None:
+            self.resign = dict(resign) if isinstance(resign, dict) else {"threshold": float(resign)}
+            self.engine.set_resign(**self.resign)
         self.B = n_boards
         self.n_playout = n_playout
         self.sampling = sampling

@@ -31,10 +31,16 @@ class Trainer:
         self.scaler = torch.amp.GradScaler("cuda", enabled=self.use_amp and amp_dtype == "fp16")
         self.steps = 0
 
-    def step(self, states: torch.Tensor, pi: torch.Tensor, z: torch.Tensor, sync: bool = True, policy_mask=None) -> dict:
+    def step(self, states: torch.Tensor, pi: torch.Tensor, z: torch.Tensor, sync: bool = True, policy_mask=None, q=None,
+             q_weight: float = 0.0) -> dict:
         """``policy_mask`` [batch] of 0 / 1 (any dtype) or None: rows with 0 (the fast plies of playout-cap randomisation) stay out
         of the policy term, which becomes ``-sum_i m_i sum_a t_ia logp_ia / max(1, sum_i m_i)``; the value loss and the entropy
-        report take every row. None: the unmasked mean, today's code path."""
+        report take every row. None: the unmasked mean, today's code path. ``q`` float32 [batch] (the search's root value of the row's
+        position, side to move's view: ``root_values.npy`` / ``sample(values=True)``; NaN where unknown) with ``q_weight`` = lambda in
+        [0, 1]: the value target is ``(1 - lambda) z + lambda q`` on rows whose q is not NaN and z elsewhere. ``q`` None or lambda 0:
+        the target is z, today's code path."""
+        if not 0.0 <= float(q_weight) <= 1.0:
+            raise ValueError("q_weight must be in [0, 1]")
         self.pvn._require_current_fp32("Trainer.step")   # a rank that received only the inference copy holds OLD fp32 weights
         self.net.train()
         dev = next(self.net.parameters()).device
@@ -43,6 +49,9 @@ class Trainer:
             sums = pi.sum(dim=1)
             if not ((sums > 0.99) & (sums < 1.01)).all():  # train.py:134-136
                 raise ValueError("mcts_probs rows must sum to 1 (+-0.01)")
+        if q is not None and q_weight != 0.0:
+            q = q.to(dev).float().flatten()
+            z = torch.where(torch.isnan(q), z, (1.0 - float(q_weight)) * z + float(q_weight) * q)
         self.opt.zero_grad(set_to_none=True)
         with torch.autocast("cuda", dtype=self.amp_dtype, enabled=self.use_amp):
             log_act_probs, value = self.net(states)

@@ -350,6 +350,53 @@ int ccz_gather_priors_routed(ccz_engine *e, void *stream, const void *logits0_de
 int ccz_set_budgets(ccz_engine *e, void *stream, const int32_t *budgets_dev, const uint8_t *targets_dev);
 int ccz_draw_budgets(ccz_engine *e, void *stream, int32_t n_full, int32_t n_fast, double p_full, int32_t *budgets_out_dev);
 
+/* ---- self-play resignation with play-on calibration (additive to ABI 8) -----------------------------------------------------------
+ * AlphaZero-style: a side resigns when the search's root value stays below a threshold for a few of its moves in a row; a random
+ * fraction of such games is played on so that the false-positive rate can be measured; the threshold is set from that
+ * measurement. Off after ccz_create: ccz_finish_move then computes, records and counts exactly what it does without the feature
+ * (record bytes 90..95 zero, none of the three flags below).
+ *   ccz_set_resign: asynchronous on `stream`, takes effect with the next ccz_finish_move. enabled = 0: off (the other arguments are
+ *     still validated). threshold finite and in [-1, 0]; consecutive 0..255 (0: values are recorded and the run counters kept, but
+ *     nothing ever resigns); min_ply >= 0; p_playon in [0, 1].
+ * With the feature on, ccz_finish_move does this on every live board that records a ply, in this order:
+ *   1. root value v = sum_i N_i * (double)Q_i / sum_i N_i over the root's k children (what ccz_root_children returns: Q in the view
+ *      of the root's side to move), accumulated in child order in float64; no visited child: 0.0. (float)v is stored with the ply.
+ *   2. s = side to move. On a full-search ply (target byte 1): run[b][s] = v < (double)threshold ? min(run + 1, 255) : 0. A fast ply
+ *      of playout-cap randomisation records v and leaves the counter alone.
+ *   3. the rule fires when: full-search ply, consecutive > 0, run[b][s] >= consecutive, ply >= min_ply, no forced move on this board
+ *      (a host that forces a move has decided), and the game has not drawn the play-on lot before.
+ *   4. on firing, u = ua of uniform2(seed, board_id_base + b, move counter, child 0xffd, draw 0): a word no other draw uses (Gamma:
+ *      0..127, budgets: 0xffe, move choice: 0xfff), so noise, moves and budgets are unchanged and the lot does not depend on the GPU
+ *      count. u < p_playon: the game is marked CCZ_RESIGN_PLAYON | s with this fire ply, plays its normal move and can never
+ *      resign. Otherwise the game ENDS here: the ply is recorded like any other (position, pi, v: the search was done), ply and
+ *      move counter advance, no move is pushed (root position, key, clock, history stay), moves_out = -1, over = 1, winner = the
+ *      other side, ccz_stats.games + 1, state CCZ_RESIGN_RESIGNED | s.
+ *   5. when a play-on game ends (by the rules or at the ply cap) the calibration counters below are updated.
+ * A board's state is cleared wherever a new game starts (harvest restart, ccz_reset, ccz_set_position(s)); ccz_reset_tree keeps it.
+ * ccz_harvest_records writes CCZ_REC_RESIGNED / CCZ_REC_PLAYON on every ply of such a game, CCZ_REC_VALUE and the float32 value in
+ * record bytes 92..95 on a ply that carries one (bytes 90..91 stay zero). The dense-row calls write what they always wrote. */
+#define CCZ_REC_RESIGNED 2  /* record header flags: the game ended by resignation (of the side to move at its last ply)  */
+#define CCZ_REC_PLAYON 4    /* ... the rule fired in this game and the game was played on                               */
+#define CCZ_REC_VALUE 8     /* ... bytes 92..95 of this record hold the ply's root value, float32, side to move's view   */
+#define CCZ_REC_VALUE_OFF 92
+#define CCZ_RESIGN_RESIGNED 2 /* ccz_resign_status state: bit 0 = the side (1 RED, 0 BLACK) that resigned / would have resigned */
+#define CCZ_RESIGN_PLAYON 4
+typedef struct ccz_resign_stats {
+    int64_t resigned_games;     /* games that ended by resignation                                                      */
+    int64_t resigned_by_red;    /* ... in which red resigned                                                             */
+    int64_t resigned_plies;     /* sum of their recorded plies T (the resign ply included)                               */
+    int64_t playon_games;       /* FINISHED games that drew the play-on lot                                              */
+    int64_t playon_won;         /* ... that the side which would have resigned won: the false positives                  */
+    int64_t playon_drawn;       /* ... that were drawn (adjudications at the ply cap included)                           */
+    int64_t playon_plies_after; /* sum of T - fire ply over them: the plies resignation would have saved                 */
+} ccz_resign_stats;
+int ccz_set_resign(ccz_engine *e, void *stream, int32_t enabled, float threshold, int32_t consecutive, int32_t min_ply, double p_playon);
+int ccz_get_resign_stats(ccz_engine *e, void *stream, ccz_resign_stats *out); /* syncs */
+/* per-board state (syncs): state_host uint8 [B] (0, or CCZ_RESIGN_* | side), run_host uint8 [B*2] (run[b][side]), fire_ply_host
+ * int32 [B] (-1: the rule has not fired in this game), last_value_host float [B] (the last recorded ply's v; NaN: none in this
+ * game); any pointer may be NULL. */
+int ccz_resign_status(ccz_engine *e, void *stream, uint8_t *state_host, uint8_t *run_host, int32_t *fire_ply_host, float *last_value_host);
+
 /* ---- once per move ------------------------------------------------------------------------ */
 /* Replaces MCTS.get_move_probs' tail (mcts.py:162-166), MCTS_AI.get_action's choice
  * (mcts.py:216-224), MCTS.update_with_move (mcts.py:168-178) and the per-move part of
@@ -434,9 +481,10 @@ int ccz_harvest(ccz_engine *e, void *stream, void *states_f16_dev, float *pi_dev
 
 /* ---- compact game records: the wire format of the multi-GPU exchange ------------------------------ */
 /* One fixed-size record per PLY of a finished game, plies of a game contiguous and in order:
- *   bytes   0..89   position before the move (piece codes, square = file + 9*rank), 90..95 zero
+ *   bytes   0..89   position before the move (piece codes, square = file + 9*rank), 90..91 zero, 92..95 the root value
+ *                   (float32) on a CCZ_REC_VALUE ply, else zero
  *   bytes  96..111  header: uint16 t (ply index), uint16 T (plies of the game), int8 winner (1 RED, 0 BLACK, -1 draw),
- *                   uint8 turn (side to move), uint8 k (entries of pi), uint8 flags (CCZ_REC_FAST or 0), uint32 board_id (global),
+ *                   uint8 turn (side to move), uint8 k (entries of pi), uint8 flags (CCZ_REC_*), uint32 board_id (global),
  *                   uint32 game_no
  *   bytes 112..367  uint16 ids[128]   move ids of the root's children (mcts.py:162), zero-padded
  *   bytes 368..879  float  pi[128]    visit distribution of the move (mcts.py:163-166), zero-padded
@@ -494,6 +542,14 @@ int ccz_expand_record_targets(void *stream, const void *records_dev, int64_t n_p
                               uint8_t *target_dev);
 int ccz_sample_record_targets(void *stream, const void *ring_dev, int64_t cap_plies, const int64_t *window_dev, const int64_t *draws_dev,
                               int64_t batch, uint32_t flags, uint8_t *target_dev);
+
+/* The root value (record bytes 92..95) of the rows the same two calls write, float32, row-aligned with the *_record_targets pair
+ * and with the same arguments: the sample and its mirror image carry their ply's v. NaN: a ply without CCZ_REC_VALUE, a row a cut
+ * game leaves unwritten (ccz_expand_record_values), a bad draw (ccz_sample_record_values). */
+int ccz_expand_record_values(void *stream, const void *records_dev, int64_t n_plies, uint32_t flags, int64_t ring_rows, int64_t head_row,
+                             float *value_dev);
+int ccz_sample_record_values(void *stream, const void *ring_dev, int64_t cap_plies, const int64_t *window_dev, const int64_t *draws_dev,
+                             int64_t batch, uint32_t flags, float *value_dev);
 
 int ccz_get_stats(ccz_engine *e, void *stream, ccz_stats *out); /* syncs */
 
