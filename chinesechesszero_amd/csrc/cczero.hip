@@ -86,6 +86,39 @@ struct ccz_engine {
 
 #define ACTIVE(e) ((unsigned)((e)->active > 0 ? (e)->active : (e)->d.B))
 
+// ---- the launches of the group-of-16 tower kernels (cczero_conv_g16.h, cczero_conv_g16e.h) ----
+static bool g16_bad_part(int32_t part, int32_t n_parts) { return n_parts < 1 || n_parts > 256 || part < 0 || part >= n_parts; }
+
+// The launch shape of a layer of `groups` 16-board groups. Without CCZ_CONV_G16_EDGE_TILES (or below two groups): `mid` = five two-rank
+// tiles per group, no edge tiles. With it: `mid` = four middle tiles per group (ranks 1..8; two-rank or quad), `edge` = one edge-pair
+// tile per side and pair of groups (ranks 0 and 9, cczero_conv_g16e.h) -- in their own launch or, CCZ_CONV_G16_ONE_LAUNCH, as slots
+// [mid, mid + edge) of the same.
+struct G16Shape {
+    unsigned mid, edge;
+};
+static G16Shape g16_shape(int groups, int flags)
+{
+    const bool split = (flags & CCZ_CONV_G16_EDGE_TILES) && groups >= 2;
+    return {(unsigned)(groups * (split ? 4 : 5)), split ? 2u * (unsigned)((groups + 1) / 2) : 0u};
+}
+
+// What every tower kernel of a layer is launched with; one launch = `grid` tile slots of 512 threads. `tail`: the heads kernels' G5Heads.
+struct G16Args {
+    const _Float16 *x, *w;
+    const float *bias;
+    const _Float16 *res;
+    _Float16 *y;
+    int n_pixels, cin;
+    const int *live_rows;
+    int row0;
+};
+template <typename Kernel, typename... Tail> static void g16_launch(Kernel kernel, unsigned grid, hipStream_t s, const G16Args &a, int flags, Tail... tail)
+{
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(512), 0, s, a.x, a.w, a.bias, a.res, a.y, a.n_pixels, flags, a.cin, a.live_rows, a.row0, tail...);
+}
+// (a kernel with and without the residual read: two instantiations)
+#define CCZ_G16_RES(KERNEL_, RES_) ((RES_) ? KERNEL_<true> : KERNEL_<false>)
+
 extern "C" {
 
 int ccz_abi_version(void) { return CCZ_ABI_VERSION; }
@@ -1188,15 +1221,10 @@ static int conv3x3_launch(const char *who, void *stream, const void *x_dev, cons
         const int groups = (int)(n_pixels / 1440);
         const int fl = relu & 3;
         hipStream_t s = (hipStream_t)stream;
-#define CCZ_G16(KERNEL_, GRID_, STREAM_, FLAGS_)                                                                                   \
-        do {                                                                                                                       \
-            if (residual_dev)                                                                                                      \
-                hipLaunchKernelGGL(KERNEL_<true>, dim3((unsigned)(GRID_)), dim3(512), 0, STREAM_, (const _Float16 *)x_dev, (const _Float16 *)w_dev, \
-                                   (const float *)bias_f32_dev, (const _Float16 *)residual_dev, (_Float16 *)y_dev, (int)n_pixels, (int)(FLAGS_), cin, (const int *)live_rows_dev, (int)row0); \
-            else                                                                                                                   \
-                hipLaunchKernelGGL(KERNEL_<false>, dim3((unsigned)(GRID_)), dim3(512), 0, STREAM_, (const _Float16 *)x_dev, (const _Float16 *)w_dev, \
-                                   (const float *)bias_f32_dev, (const _Float16 *)nullptr, (_Float16 *)y_dev, (int)n_pixels, (int)(FLAGS_), cin, (const int *)live_rows_dev, (int)row0); \
-        } while (0)
+        const G16Shape shape = g16_shape(groups, relu);
+        const G16Args a = {(const _Float16 *)x_dev, (const _Float16 *)w_dev, (const float *)bias_f32_dev, (const _Float16 *)residual_dev, (_Float16 *)y_dev,
+                           (int)n_pixels, cin, (const int *)live_rows_dev, (int)row0};
+        const bool res = residual_dev != nullptr;
         // Without the flag: ONE launch of five two-rank tiles per group. CCZ_CONV_G16_EDGE_TILES (flag bit 7, round 4): the edge ranks (0
         // and 9) of two groups at a time are their own tiles on their own kernel (six live taps instead of nine, cczero_conv_g16e.h) and
         // the middle launch covers ranks 1..8 with four two-rank tiles per group -- two ordinary launches back to back in the caller's
@@ -1212,25 +1240,23 @@ static int conv3x3_launch(const char *who, void *stream, const void *x_dev, cons
             HIP_TRY(hipGetLastError());
             return 0;
         }
-        if (!(relu & CCZ_CONV_G16_EDGE_TILES) || groups < 2) {
-            CCZ_G16(k_conv3x3_g16, groups * 5, s, fl);
+        if (!shape.edge) {
+            g16_launch(CCZ_G16_RES(k_conv3x3_g16, res), shape.mid, s, a, fl);
             HIP_TRY(hipGetLastError());
             return 0;
         }
         // CCZ_CONV_G16_QUAD: the middle slots as four-rank x 128-channel tiles (cczero_conv_g16.h g5q_tile) -- as many, as large, half the weight stream
         const bool quad = (relu & CCZ_CONV_G16_QUAD) != 0;
         if (relu & CCZ_CONV_G16_ONE_LAUNCH) { // both tile classes in one launch (cczero_conv_g16e.h k_conv3x3_g16_one)
-            if (quad) CCZ_G16(k_conv3x3_g16_one_quad, groups * 4 + 2 * ((groups + 1) / 2), s, fl);
-            else CCZ_G16(k_conv3x3_g16_one, groups * 4 + 2 * ((groups + 1) / 2), s, fl);
+            g16_launch(quad ? CCZ_G16_RES(k_conv3x3_g16_one_quad, res) : CCZ_G16_RES(k_conv3x3_g16_one, res), shape.mid + shape.edge, s, a, fl);
             HIP_TRY(hipGetLastError());
             return 0;
         }
-        if (quad) CCZ_G16(k_conv3x3_g16_quad, groups * 4, s, fl);
-        else CCZ_G16(k_conv3x3_g16, groups * 4, s, fl | 4);   // (edge launch first: measured the same, 194.4 / 194.3 k against 194.8 / 194.0 k sims/s)
+        if (quad) g16_launch(CCZ_G16_RES(k_conv3x3_g16_quad, res), shape.mid, s, a, fl);
+        else g16_launch(CCZ_G16_RES(k_conv3x3_g16, res), shape.mid, s, a, fl | 4);   // (edge launch first: measured the same, 194.4 / 194.3 k against 194.8 / 194.0 k sims/s)
         HIP_TRY(hipGetLastError());
-        CCZ_G16(k_conv3x3_g16_edge, 2 * ((groups + 1) / 2), s, fl);
+        g16_launch(CCZ_G16_RES(k_conv3x3_g16_edge, res), shape.edge, s, a, fl);
         HIP_TRY(hipGetLastError());
-#undef CCZ_G16
         return 0;
     }
     // Small batches (one game at a time; up to kSmallMaxPixels): the 16-channel x 64-pixel-block kernel spreads them over the chip
@@ -1281,10 +1307,12 @@ int ccz_conv3x3_c256_heads_f16(void *stream, const void *x_dev, const void *w_de
     if ((((uintptr_t)x_dev) | ((uintptr_t)w_dev) | ((uintptr_t)bias_f32_dev) | ((uintptr_t)residual_dev) | ((uintptr_t)head_w32_dev) | ((uintptr_t)head_b32_dev)) & 15)
         return fail(-1, "%s: pointers must be 16-byte aligned", who);
     if ((((uintptr_t)pol_dev) | ((uintptr_t)val_dev)) & 1) return fail(-1, "%s: outputs must be 2-byte aligned", who);
-    if (live_rows_dev && (n_parts < 1 || n_parts > 256 || part < 0 || part >= n_parts)) return fail(-1, "%s: bad part / n_parts", who);
+    if (live_rows_dev && g16_bad_part(part, n_parts)) return fail(-1, "%s: bad part / n_parts", who);
     if (n_pixels == 0) return 0;
-    const int groups = (int)(n_pixels / 1440);
-    const int fl = flags & 3, row0 = live_rows_dev ? (part | (n_parts << 16)) : 0;
+    const G16Shape shape = g16_shape((int)(n_pixels / 1440), flags);
+    const int fl = flags & 3;
+    const G16Args a = {(const _Float16 *)x_dev, (const _Float16 *)w_dev, (const float *)bias_f32_dev, (const _Float16 *)residual_dev, nullptr,
+                       (int)n_pixels, 256, (const int *)live_rows_dev, live_rows_dev ? (part | (n_parts << 16)) : 0};
     G5Heads ha;
     ha.w32 = (const _Float16 *)head_w32_dev;
     ha.b32 = (const float *)head_b32_dev;
@@ -1292,19 +1320,11 @@ int ccz_conv3x3_c256_heads_f16(void *stream, const void *x_dev, const void *w_de
     ha.val = (_Float16 *)val_dev;
     ha.nb = (int)(n_pixels / 90);
     hipStream_t s = (hipStream_t)stream;
-#define CCZ_G16H(KERNEL_, GRID_, FLAGS_)                                                                                                \
-    hipLaunchKernelGGL(KERNEL_, dim3((unsigned)(GRID_)), dim3(512), 0, s, (const _Float16 *)x_dev, (const _Float16 *)w_dev, (const float *)bias_f32_dev, \
-                       (const _Float16 *)residual_dev, (_Float16 *)nullptr, (int)n_pixels, (int)(FLAGS_), 256, (const int *)live_rows_dev, row0, ha)
-    if (!(flags & CCZ_CONV_G16_EDGE_TILES) || groups < 2) {
-        CCZ_G16H(k_conv3x3_g16_heads, groups * 5, fl);
-        HIP_TRY(hipGetLastError());
-        return 0;
-    }
-    CCZ_G16H(k_conv3x3_g16_heads, groups * 4, fl | 4);
+    g16_launch(k_conv3x3_g16_heads, shape.mid, s, a, shape.edge ? fl | 4 : fl, ha);
     HIP_TRY(hipGetLastError());
-    CCZ_G16H(k_conv3x3_g16_edge_heads, 2 * ((groups + 1) / 2), fl);
+    if (!shape.edge) return 0;
+    g16_launch(k_conv3x3_g16_edge_heads, shape.edge, s, a, fl, ha);
     HIP_TRY(hipGetLastError());
-#undef CCZ_G16H
     return 0;
 }
 
@@ -1316,14 +1336,14 @@ int ccz_conv3x3_stem_f16(void *stream, const void *x64_dev, const void *w_dev, c
 int ccz_conv3x3_c256_f16_live(void *stream, const void *x_dev, const void *w_dev, const void *bias_f32_dev, const void *residual_dev, void *y_dev,
                               int64_t n_pixels, int32_t relu, const int32_t *live_rows_dev, int32_t part, int32_t n_parts)
 {
-    if (!live_rows_dev || n_parts < 1 || n_parts > 256 || part < 0 || part >= n_parts) return fail(-1, "ccz_conv3x3_c256_f16_live: null live-row count or bad part / n_parts");
+    if (!live_rows_dev || g16_bad_part(part, n_parts)) return fail(-1, "ccz_conv3x3_c256_f16_live: null live-row count or bad part / n_parts");
     return conv3x3_launch("ccz_conv3x3_c256_f16_live", stream, x_dev, w_dev, bias_f32_dev, residual_dev, y_dev, n_pixels, relu, 256, live_rows_dev, part | (n_parts << 16));
 }
 
 int ccz_conv3x3_stem_f16_live(void *stream, const void *x64_dev, const void *w_dev, const void *bias_f32_dev, void *y_dev, int64_t n_pixels, int32_t relu,
                               const int32_t *live_rows_dev, int32_t part, int32_t n_parts)
 {
-    if (!live_rows_dev || n_parts < 1 || n_parts > 256 || part < 0 || part >= n_parts) return fail(-1, "ccz_conv3x3_stem_f16_live: null live-row count or bad part / n_parts");
+    if (!live_rows_dev || g16_bad_part(part, n_parts)) return fail(-1, "ccz_conv3x3_stem_f16_live: null live-row count or bad part / n_parts");
     return conv3x3_launch("ccz_conv3x3_stem_f16_live", stream, x64_dev, w_dev, bias_f32_dev, nullptr, y_dev, n_pixels, relu, 64, live_rows_dev, part | (n_parts << 16));
 }
 

@@ -44,6 +44,11 @@
 //     weights: 1,032 instead of 1,475 KB of LDS-DMA per tile, 16 instead of 23 DMA instructions per thread and chunk. Same bits.
 //     Measured (profiles/r09_quad_tiles_ab.json, CHANGELOG): 200.2-200.8 k -> 202.8-203.3 k sims/s. The two-rank tile stays for the
 //     five-tile mode, the stem and the heads layer (its 1x1 epilogue needs all 256 channels of a row in one workgroup).
+//   * ONE skeleton for the three tile forms (g5_tile and g5q_tile here, g5e_tile in cczero_conv_g16e.h): a form keeps its geometry, its
+//     staging passes, its zeroing and dump-area rules, its step loop; the rest is shared -- g5_live_part (a launch part's pointers),
+//     g5_xcd_tile (tile order), g5_ctx_common / g5_ctx_frags (G5Ctx), g5_acc_row_from_bias, g5_image_store / g5_rows_out (epilogue),
+//     g5_barrier, and the cell macros G5_CELL / G5_CELLS of both step functions. What stayed per form, and what the compiler did with
+//     the forms that were tried: CHANGELOG, "one prologue and epilogue for the three g16 tile forms".
 //   * XCD-aware tile order: workgroup b runs on XCD b % 8 and the five tiles of a group read each other's ranks as halo, so XCD x
 //     takes the x-th contiguous eighth of the tiles (HBM traffic per launch 398 MB -> 283-288 MB = algorithmic).
 //
@@ -98,7 +103,7 @@ struct G5Ctx {
     unsigned woff;           // byte offset of this thread's 16-byte weight source in W (row pass 0, tap 0, chunk 0)
     int zo[2], zd[2];        // SCALAR: where this wave's two zero stores go for slab 0, and the step to slab 1 (0 for the dump area)
     int wave_dst;            // w * 1024
-    int lane16;              // (lane & 63) * 16
+    int lane16;              // (lane & 63) * 16 (the two-rank tile alone: g5_zero_ranks)
     int wave_dst_part, wave_step_part; // SCALAR: LDS offset of this wave's piece of staging pass 4 in slab 0 and the step to slab 1 (waves 4-7: their
                              // 1 KB of the dump area, step 0 -- the zeros of their out-of-range loads land where nothing is read)
     int a_off;               // weight fragment offset inside a ring slot (tile 0; tile i: + 1024 i)
@@ -134,6 +139,16 @@ template <int T, int N> __host__ __device__ constexpr bool g5_on_board() // is t
     return !((T % 3 == 0 && N == 0) || (T % 3 == 2 && N == 8));
 }
 
+// The workgroup barrier of these kernels: a raw s_barrier fenced on both sides, so that nothing is scheduled across it.
+// LDS_DONE: this wave's own LDS stores and loads have completed first (lgkmcnt(0)).
+template <bool LDS_DONE = false> __device__ __forceinline__ void g5_barrier()
+{
+    if constexpr (LDS_DONE) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+}
+
 // The rank above rank 0 (tiles with k = 0) and the rank below rank 9 (k = 4) do not exist: their slab rows were staged from
 // clamped addresses (the DMA count stays static) and are overwritten with zeros by the thread that staged them, after its DMA has
 // landed and before the barrier that publishes the slab. Rows 0..143 / 432..575 = whole 16-row pieces, so the tests are
@@ -149,6 +164,25 @@ __device__ __forceinline__ void g5_zero_ranks(const G5Ctx &c, int buf)
     for (int j = 0; j < 2; ++j) *(g5_int4 *)(c.lds + (l16 + (c.zo[j] + buf * c.zd[j]))) = z;
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 }
+
+// The cells of one half-step (g5_step here, g5e_step in cczero_conv_g16e.h): G5_CELLS(TAP, LO, HI) runs cells LO..HI-1 of tap TAP inside a
+// step function that has `lds`, `c`, `acc`, `acur`, `b`, `BUFn` in scope and defines G5_REFILL(N) = the slab cell that b[N] is refilled
+// from during a dx = +1 tap. The order is pinned, one scheduling region per cell (see g5_step). Both macros end with cczero_conv_g16e.h.
+#define G5_CELL(TAP, N)                                                                                                   \
+    {                                                                                                                     \
+        if constexpr (TAP % 3 == 2)                                                                                       \
+            b[N] = *(const cv_half8 *)(lds + c.vb[BUFn] + G5_REFILL(N) * 1024);                                           \
+        if constexpr (g5_on_board<TAP, N>()) {                                                                            \
+            constexpr int NB = N + TAP % 3 - 1;                                                                           \
+            _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                                 \
+                acc[i][N] = __builtin_amdgcn_mfma_f32_16x16x32_f16(acur[i], b[NB], acc[i][N], 0, 0, 0);                   \
+        }                                                                                                                 \
+        __builtin_amdgcn_sched_barrier(0);                                                                                \
+    }
+#define G5_CELLS(TAP, LO, HI)                                                                                             \
+    if constexpr (LO <= 0 && 0 < HI) G5_CELL(TAP, 0) if constexpr (LO <= 1 && 1 < HI) G5_CELL(TAP, 1) if constexpr (LO <= 2 && 2 < HI) G5_CELL(TAP, 2) \
+    if constexpr (LO <= 3 && 3 < HI) G5_CELL(TAP, 3) if constexpr (LO <= 4 && 4 < HI) G5_CELL(TAP, 4) if constexpr (LO <= 5 && 5 < HI) G5_CELL(TAP, 5) \
+    if constexpr (LO <= 6 && 6 < HI) G5_CELL(TAP, 6) if constexpr (LO <= 7 && 7 < HI) G5_CELL(TAP, 7) if constexpr (LO <= 8 && 8 < HI) G5_CELL(TAP, 8)
 
 // One half-step = tap T of a 32-channel chunk; J = its index inside the unrolled pair of chunks (parity of the A register
 // set = J & 1, slab buffer = J / 9). Q: the quad tile's staging (8 KB ring slots, slabs of six ranks, g5q_dma) around the SAME cells.
@@ -169,26 +203,12 @@ __device__ __forceinline__ void g5_step(const G5Ctx &c, cv_f32x4 (&acc)[4][9], i
     // fragments of that rank for three half-steps (cell N multiplies b[N + dx]; N + dx = -1 and 9 are exactly the skipped,
     // off-board pairs) and is refilled once per dy, during the dx = +1 tap: b[N] is dead as soon as cell N - 1 has issued its
     // MFMAs there, so it is reloaded for the next dy right in front of cell N's MFMAs -- 27 fragment reads per chunk instead of 78.
-#define G5_CELL(N)                                                                                                        \
-    {                                                                                                                     \
-        if constexpr (T % 3 == 2)                                                                                         \
-            b[N] = *(const cv_half8 *)(lds + c.vb[BUFn] + (9 + N + 9 * (Tn / 3 - 1)) * 1024);                             \
-        if constexpr (g5_on_board<T, N>()) {                                                                              \
-            constexpr int NB = N + T % 3 - 1;                                                                             \
-            _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                                 \
-                acc[i][N] = __builtin_amdgcn_mfma_f32_16x16x32_f16(acur[i], b[NB], acc[i][N], 0, 0, 0);                   \
-        }                                                                                                                 \
-        __builtin_amdgcn_sched_barrier(0);                                                                                \
-    }
-#define G5_CELLS(LO, HI)                                                                                                  \
-    if constexpr (LO <= 0 && 0 < HI) G5_CELL(0) if constexpr (LO <= 1 && 1 < HI) G5_CELL(1) if constexpr (LO <= 2 && 2 < HI) G5_CELL(2) \
-    if constexpr (LO <= 3 && 3 < HI) G5_CELL(3) if constexpr (LO <= 4 && 4 < HI) G5_CELL(4) if constexpr (LO <= 5 && 5 < HI) G5_CELL(5) \
-    if constexpr (LO <= 6 && 6 < HI) G5_CELL(6) if constexpr (LO <= 7 && 7 < HI) G5_CELL(7) if constexpr (LO <= 8 && 8 < HI) G5_CELL(8)
+#define G5_REFILL(N) (9 + N + 9 * (Tn / 3 - 1))
     constexpr int T2 = (T + kG5Ahead) % 9;
     // Past the last chunk there is nothing left to prefetch, but every load is still ISSUED (the vmcnt counts stay static): its
     // descriptor then has zero records, the range check fails and nothing is fetched (cv_blds16)
     const int chunk2 = chunk + (T + kG5Ahead >= 9 ? 1 : 0);
-    G5_CELLS(0, 1)
+    G5_CELLS(T, 0, 1)
     if constexpr (Q && g5q_nslab(T) > 0) { // the next chunk's slab: 7 pieces per thread, passes 0, 1 | 2 | .. | 6 in taps 0 | 1 | .. | 5
         constexpr int pass = T == 0 ? 0 : T + 1;
         const unsigned so = (unsigned)((chunk + 1) * 64);
@@ -205,29 +225,27 @@ __device__ __forceinline__ void g5_step(const G5Ctx &c, cv_f32x4 (&acc)[4][9], i
                   lds + (pass < 4 ? kG5AOff + (1 - BUF) * kG5SlabBytes + pass * 8192 + c.wave_dst : c.wave_dst_part + (1 - BUF) * c.wave_step_part));
         __builtin_amdgcn_sched_barrier(0);
     }
-    G5_CELLS(1, 2)
+    G5_CELLS(T, 1, 2)
     if constexpr (Q) { // this tile's half (8 KB: rows 128 h .. 128 h + 127) of half-tile (chunk2, T2): one piece per thread
         cv_blds16(c.W, chunk2 <= c.cmask ? c.wbytes : 0u, c.woff, (unsigned)((T2 + 9 * chunk2) * (2 * 8192)) + c.whalf, lds + ring_wr * kWB + c.wave_dst);
         __builtin_amdgcn_sched_barrier(0);
-        G5_CELLS(2, 3)
+        G5_CELLS(T, 2, 3)
     } else {
         const unsigned wlive = chunk2 <= c.cmask ? c.wbytes : 0u;
         const unsigned so = (unsigned)((T2 + 9 * chunk2) * (2 * 8192)); // half-tile (chunk2, T2): one contiguous 16 KB block, a scalar offset
         unsigned char *const d = lds + ring_wr * kG5WBytes + c.wave_dst;
         cv_blds16(c.W, wlive, c.woff, so, d);
         __builtin_amdgcn_sched_barrier(0);
-        G5_CELLS(2, 3)
+        G5_CELLS(T, 2, 3)
         cv_blds16(c.W, wlive, c.woff, so + 8192u, d + 8192);            // its rows 128..255
         __builtin_amdgcn_sched_barrier(0);
     }
-    G5_CELLS(3, kG5Split)
+    G5_CELLS(T, 3, kG5Split)
 
     ring_rd = ring_rd + 1 == kG5Ring ? 0 : ring_rd + 1;
     cv_wait_vm<Q ? g5q_vmcnt(T) : g5_vmcnt(T)>();
     if constexpr (!Q && T == 7) g5_zero_ranks(c, 1 - BUF); // this thread's slab pieces of the next chunk have landed (all but the youngest weight loads)
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
+    g5_barrier();
 
     {
         const unsigned char *wa = lds + (ring_rd * kWB + c.a_off);
@@ -235,10 +253,9 @@ __device__ __forceinline__ void g5_step(const G5Ctx &c, cv_f32x4 (&acc)[4][9], i
         for (int i = 0; i < 4; ++i) anxt[i] = *(const cv_half8 *)(wa + i * 1024);
         __builtin_amdgcn_sched_barrier(0);
     }
-    G5_CELLS(kG5Split, 9)
+    G5_CELLS(T, kG5Split, 9)
     ring_wr = ring_wr + 1 == kG5Ring ? 0 : ring_wr + 1;
-#undef G5_CELLS
-#undef G5_CELL
+#undef G5_REFILL
 }
 
 // ---- the heads fused into the LAST tower layer (round 4) ------------------------------------------------------------------------------
@@ -317,6 +334,106 @@ __device__ __forceinline__ int g5_live_groups(const int *live_rows, int row0, in
     return live > cap ? cap : live;
 }
 
+// A launch part's pointers moved to its first live group `first` (g5_live_groups); `first_board` = that group's global board
+// index for the heads. HEADS: there is no output tensor, Y stays.
+template <bool RES, bool HEADS>
+__device__ __forceinline__ void g5_live_part(int first, int cin, const _Float16 *__restrict__ &X, const _Float16 *&R, _Float16 *&Y, long &first_board)
+{
+    const long off = (long)first * 1440 * kCvC;
+    X += (long)first * 1440 * cin;
+    if (!HEADS) Y += off;
+    if (RES) R += off;
+    first_board = (long)first * 16;
+}
+
+// XCD-aware order: workgroup b runs on XCD b % 8 (round-robin dispatch), and the five tiles of a group read each other's
+// ranks as halo -- so XCD x takes the x-th CONTIGUOUS eighth of the tiles, in order: a halo rank is then in that XCD's L2
+// (with tile = b: 398 MB fetched per half-batch launch against 283 MB algorithmic, profiles/pmc_summary.json).
+// flags bit 1: tiles in descending order (the tiles written last by the previous layer are then read first)
+__device__ __forceinline__ int g5_xcd_tile(int blk, int tiles, int flags)
+{
+    const int b = blk, x = b & 7, per = tiles >> 3, rem = tiles & 7;
+    const int tile = x * per + (x < rem ? x : rem) + (b >> 3);
+    return __builtin_amdgcn_readfirstlane((flags & 2) ? tiles - 1 - tile : tile);
+}
+
+// The G5Ctx fields that every tile form sets the same way. `xbytes`: bytes of the launch part's activation rows; `chunks`: 32-channel
+// chunks to run. (`woff` is as common but stays behind each form's `xoff`: set here, in front of them, the loop of
+// k_conv3x3_g16<no residual> compiles to other instructions; `lane16` is the two-rank tile's alone, for g5_zero_ranks.)
+__device__ __forceinline__ void g5_ctx_common(G5Ctx &c, unsigned char *lds, const _Float16 *X, const _Float16 *W, int w, unsigned xbytes, int cin, int chunks)
+{
+    c.lds = lds;
+    c.X = X;
+    c.W = W;
+    c.wave_dst = w * 1024;
+    c.cin = cin;
+    c.cmask = chunks - 1;
+    c.xbytes = xbytes;
+    c.wbytes = 9u * 256u * (unsigned)cin * 2u;
+}
+
+// This lane's fragment addresses: weight rows 64 wm + 16 i + r of a ring slot, and row r of slab cell `cell0` (+ n, + the tap's offset)
+// in the slabs at `aoff`, `slab` bytes apart -- both through the swizzle of the 64-byte rows
+__device__ __forceinline__ void g5_ctx_frags(G5Ctx &c, int r, int q4, int wm, int cell0, int aoff, int slab)
+{
+    const int lane1 = r * 64 + ((q4 ^ ((0 - (r >> 2)) & 3)) << 4);
+    c.a_off = wm * 4096 + lane1;
+    c.vb[0] = aoff + cell0 * 1024 + lane1;
+    c.vb[1] = c.vb[0] + slab;
+}
+
+// Epilogue, part 1: the wave's 64 channels x 144 rows (wave row `wn`, channels from 64 wm) as fp16 into the [row][channel] image in
+// LDS, EROW bytes per image row. `r`, `q4`: lane & 15, lane >> 4.
+template <int EROW>
+__device__ __forceinline__ void g5_image_store(unsigned char *lds, cv_f32x4 (&acc)[4][9], int wm, int wn, int r, int q4)
+{
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int col = wm * 64 + i * 16 + 4 * q4;
+#pragma unroll
+        for (int n = 0; n < 9; ++n) {
+            cv_half4 o;
+            o[0] = (_Float16)acc[i][n][0];
+            o[1] = (_Float16)acc[i][n][1];
+            o[2] = (_Float16)acc[i][n][2];
+            o[3] = (_Float16)acc[i][n][3];
+            *(cv_half4 *)(lds + ((wn * 9 + n) * 16 + r) * EROW + col * 2) = o;
+        }
+    }
+}
+
+// Epilogue, part 2, behind the barrier that publishes the image: a lane moves 18 16-byte pieces, STEP image rows apart -- image row
+// `irow` + STEP it, piece `piece` of it = tensor row `pbase` + STEP it, channels `gcol` .. + 7. Image + residual `rv` (loaded by the
+// caller in front of that barrier) (+ ReLU) out to Y -- or (HEADS) back into the image: the finished row stays there, Y is not written.
+// The two-rank and the quad tile; the edge pair keeps its own copy under its store predicate (cczero_conv_g16e.h: in
+// k_conv3x3_g16_one* the compiler folds two bodies' identical store tails into one, and the kernels' instruction counts move).
+template <int EROW, int STEP, bool RES, bool HEADS>
+__device__ __forceinline__ void g5_rows_out(unsigned char *lds, int irow, int piece, long pbase, int gcol, _Float16 *Y, int relu, const cv_half8 (&rv)[18])
+{
+    const cv_half8 zero = (cv_half8)(_Float16)0;
+    unsigned char *eb = lds + irow * EROW + piece * 16;
+#pragma unroll
+    for (int it = 0; it < 18; ++it) {
+        cv_half8 v = *(const cv_half8 *)(eb + it * STEP * EROW);
+        if (RES) v = v + rv[it];
+        if (relu) v = __builtin_elementwise_max(v, zero);
+        if constexpr (HEADS) *(cv_half8 *)(eb + it * STEP * EROW) = v;
+        else *(cv_half8 *)(Y + (pbase + it * STEP) * kCvC + gcol) = v;
+    }
+}
+
+// The accumulators start at the bias: the nine tiles of one accumulator row, from the four bias values at `bias4`. One row per call, the
+// loop over the four rows is the caller's: with it in here (acc[4][9] by reference) k_conv3x3_g16_quad<residual> and
+// k_conv3x3_g16_one_quad<residual> spill 16 VGPRs and the loops of the other kernels change (CHANGELOG).
+__device__ __forceinline__ void g5_acc_row_from_bias(cv_f32x4 (&row)[9], const float *bias4)
+{
+    const float4 bv = *(const float4 *)bias4;
+#pragma unroll
+    for (int n = 0; n < 9; ++n) {
+        row[n][0] = bv.x; row[n][1] = bv.y; row[n][2] = bv.z; row[n][3] = bv.w;
+    }
+}
+
 // One two-rank tile. `lds`: the workgroup's kG5Lds bytes (declared by the kernel, so that one kernel can hold two tile classes);
 // `blk`: this workgroup's tile slot, `grid`: the launch's tile count (without a live-row count; with one, the tiles of the live groups).
 template <bool RES, bool HEADS, bool ONE = false>
@@ -336,22 +453,9 @@ __device__ __forceinline__ void g5_tile(unsigned char *lds, int blk, int grid, c
         M = live * 1440;
         tiles = live * ((relu & 4) ? 4 : 5);
         if (blk >= tiles) return;
-        const long off = (long)first * 1440 * kCvC;
-        X += (long)first * 1440 * cin;
-        if (!HEADS) Y += off; // (HEADS: there is no output tensor)
-        if (RES) R += off;
-        first_board = (long)first * 16;
+        g5_live_part<RES, HEADS>(first, cin, X, R, Y, first_board);
     }
-    // XCD-aware order: workgroup b runs on XCD b % 8 (round-robin dispatch), and the five tiles of a group read each other's
-    // ranks as halo -- so XCD x takes the x-th CONTIGUOUS eighth of the tiles, in order: a halo rank is then in that XCD's L2
-    // (with tile = b: 398 MB fetched per half-batch launch against 283 MB algorithmic, profiles/pmc_summary.json)
-    int tile;
-    {
-        const int b = blk, x = b & 7, per = tiles >> 3, rem = tiles & 7;
-        tile = x * per + (x < rem ? x : rem) + (b >> 3);
-    }
-    // flags bit 1: tiles in descending order (the tiles written last by the previous layer are then read first)
-    tile = __builtin_amdgcn_readfirstlane((relu & 2) ? tiles - 1 - tile : tile);
+    const int tile = g5_xcd_tile(blk, tiles, relu);
     // flags bit 2 ("middle" mode, round 4): the launch covers ranks 1..8 only, four tiles per group (ranks 1-2, 3-4, 5-6, 7-8: every
     // neighbour rank exists, nothing is zeroed); ranks 0 and 9 are k_conv3x3_g16_edge's (cczero_conv_g16e.h)
     const int mid = relu & 4;
@@ -361,9 +465,6 @@ __device__ __forceinline__ void g5_tile(unsigned char *lds, int blk, int grid, c
     relu &= 1;
 
     G5Ctx c;
-    c.lds = lds;
-    c.X = X;
-    c.W = W;
     {
         // rows 0..143 (k = 0) = pass 0 of every wave + pass 1 of wave 0; rows 432..575 (k = 4) = pass 3 of waves 3..7 + pass 4 of
         // waves 0..3: two stores per wave cover either (wave 0 resp. wave 3 need both of theirs); anything else goes to the dump area
@@ -374,15 +475,11 @@ __device__ __forceinline__ void g5_tile(unsigned char *lds, int blk, int grid, c
             c.zd[j] = __builtin_amdgcn_readfirstlane(piece[j] >= 0 ? kG5SlabBytes : 0);
         }
     }
-    c.wave_dst = w * 1024;
-    c.lane16 = lane * 16;
+    g5_ctx_common(c, lds, X, W, w, (unsigned)M * (unsigned)cin * 2u, cin, ONE ? 1 : cin >> 5);
+    c.lane16 = lane * 16; // (g5_zero_ranks)
     c.wave_dst_part = w < 4 ? kG5AOff + 4 * 8192 + w * 1024 : kG5Dump + w * 1024;
     c.wave_step_part = w < 4 ? kG5SlabBytes : 0;
-    c.cin = cin;
-    c.cmask = ONE ? 0 : (cin >> 5) - 1;
-    c.xbytes = (unsigned)M * (unsigned)cin * 2u;
     c.xbytes_part = w < 4 ? c.xbytes : 0u;
-    c.wbytes = 9u * 256u * (unsigned)cin * 2u;
     {
         // slab row sr (0..575) = tensor row p0 - 144 + sr: rank 2k - 1 + sr / 144 of the group; 64-byte rows, position pos of
         // row sr holds source chunk pos ^ f(sr), f = (-(sr >> 2)) & 3 (conflict-free for the 16 rows x 4 chunks one ds_read_b128
@@ -408,28 +505,15 @@ __device__ __forceinline__ void g5_tile(unsigned char *lds, int blk, int grid, c
         cv_blds16(W, c.wbytes, c.woff, (unsigned)(u * 2 * 8192), d);
         cv_blds16(W, c.wbytes, c.woff, (unsigned)(u * 2 * 8192 + 8192), d + 8192);
     }
-    const int lane1 = r * 64 + ((q4 ^ ((0 - (r >> 2)) & 3)) << 4);
-    c.a_off = wm * 4096 + lane1;                               // rows 64 wm + 16 i + r of the half-tile
-    c.vb[0] = kG5AOff + wn * 9 * 1024 + lane1;                 // slab cell 9 wn + n + 9 + delta, row r of it
-    c.vb[1] = c.vb[0] + kG5SlabBytes;
+    g5_ctx_frags(c, r, q4, wm, wn * 9, kG5AOff, kG5SlabBytes); // slab cell 9 wn + n + 9 + delta
 
-    // the accumulators start at the bias
     cv_f32x4 acc[4][9];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const float4 bv = *(const float4 *)(bias + wm * 64 + i * 16 + 4 * q4);
-#pragma unroll
-        for (int n = 0; n < 9; ++n) {
-            acc[i][n][0] = bv.x; acc[i][n][1] = bv.y; acc[i][n][2] = bv.z; acc[i][n][3] = bv.w;
-        }
-    }
+    for (int i = 0; i < 4; ++i) g5_acc_row_from_bias(acc[i], bias + wm * 64 + i * 16 + 4 * q4);
 
     cv_wait_vm<4>();
     g5_zero_ranks(c, 0);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
+    g5_barrier<true>();
 
     int ring_rd = 0, ring_wr = kG5Ahead;
     cv_half8 a0[4], a1[4], b[9];
@@ -452,53 +536,22 @@ __device__ __forceinline__ void g5_tile(unsigned char *lds, int blk, int grid, c
 
     // ---- epilogue: every wave writes its 64 channels x 144 rows into the [row][channel] image in LDS; then wave w owns
     // rows 36 w .. 36 w + 35 and moves whole 512-byte rows (residual in, output out)
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier(); // every wave is done reading the slabs and the ring
-    __builtin_amdgcn_sched_barrier(0);
+    g5_barrier(); // every wave is done reading the slabs and the ring
     // the lane index is formed again here (v_mbcnt): carried through the loop it is the 257th register of the heads instantiation
     const int lane_e = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
     const int re = lane_e & 15, q4e = lane_e >> 4;
     const int prow = lane_e >> 5, piece = lane_e & 31;
     const long pbase = p0 + w * 36 + prow;
     cv_half8 rv[18];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int col = wm * 64 + i * 16 + 4 * q4e;
-#pragma unroll
-        for (int n = 0; n < 9; ++n) {
-            cv_half4 o;
-            o[0] = (_Float16)acc[i][n][0];
-            o[1] = (_Float16)acc[i][n][1];
-            o[2] = (_Float16)acc[i][n][2];
-            o[3] = (_Float16)acc[i][n][3];
-            *(cv_half4 *)(lds + ((wn * 9 + n) * 16 + re) * kG5ERow + col * 2) = o;
-        }
-    }
+    g5_image_store<kG5ERow>(lds, acc, wm, wn, re, q4e);
     if (RES) {
 #pragma unroll
         for (int it = 0; it < 18; ++it) rv[it] = *(const cv_half8 *)(R + (pbase + it * 2) * kCvC + piece * 8);
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    {
-        const cv_half8 zero = (cv_half8)(_Float16)0;
-        unsigned char *eb = lds + (w * 36 + prow) * kG5ERow + piece * 16;
-#pragma unroll
-        for (int it = 0; it < 18; ++it) {
-            cv_half8 v = *(const cv_half8 *)(eb + it * 2 * kG5ERow);
-            if (RES) v = v + rv[it];
-            if (relu) v = __builtin_elementwise_max(v, zero);
-            if constexpr (HEADS) *(cv_half8 *)(eb + it * 2 * kG5ERow) = v;   // the finished row stays in the image; Y is not written
-            else *(cv_half8 *)(Y + (pbase + it * 2) * kCvC + piece * 8) = v;
-        }
-    }
+    g5_barrier<true>();
+    g5_rows_out<kG5ERow, 2, RES, HEADS>(lds, w * 36 + prow, piece, pbase, piece * 8, Y, relu, rv);
     if constexpr (HEADS) {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier(); // every finished row is in the image
-        __builtin_amdgcn_sched_barrier(0);
+        g5_barrier<true>(); // every finished row is in the image
         // image rows 0..143 = the tile's first rank, 144..287 = its second: tensor row p0 + i = (group * 90 + 9 * rank + cell) * 16 + board
         const long grp = p0 / 1440;
         const int rank0 = (int)((p0 - grp * 1440) / 144);
@@ -536,33 +589,19 @@ __device__ __forceinline__ void g5q_tile(unsigned char *lds, int blk, int grid, 
         M = live * 1440;
         tiles = live * 4;
         if (blk >= tiles) return;
-        const long off = (long)first * 1440 * kCvC;
-        X += (long)first * 1440 * cin;
-        Y += off;
-        if (RES) R += off;
+        long first_board;
+        g5_live_part<RES, false>(first, cin, X, R, Y, first_board);
     }
-    int tile; // XCD-aware order and flags bit 1 as in g5_tile
-    {
-        const int b = blk, x = b & 7, per = tiles >> 3, rem = tiles & 7;
-        tile = x * per + (x < rem ? x : rem) + (b >> 3);
-    }
-    tile = __builtin_amdgcn_readfirstlane((relu & 2) ? tiles - 1 - tile : tile);
+    const int tile = g5_xcd_tile(blk, tiles, relu);
     const int h = tile & 1;                                                              // output channels 128 h .. 128 h + 127
     const long p0 = (long)(tile >> 2) * 1440 + 144 + (long)((tile >> 1) & 1) * kG5QRows; // = (group * 90 + 9 * (1 or 5)) * 16
     relu &= 1;
 
     G5Ctx c;
-    c.lds = lds;
-    c.X = X;
-    c.W = W;
-    c.wave_dst = w * 1024;
+    g5_ctx_common(c, lds, X, W, w, (unsigned)M * (unsigned)cin * 2u, cin, cin >> 5);
     c.wave_dst_part = w < 6 ? kG5QAOff + 6 * 8192 + w * 1024 : kG5QDump + w * 1024;
     c.wave_step_part = w < 6 ? kG5QSlabBytes : 0;
-    c.cin = cin;
-    c.cmask = (cin >> 5) - 1;
-    c.xbytes = (unsigned)M * (unsigned)cin * 2u;
     c.xbytes_part = w < 6 ? c.xbytes : 0u;
-    c.wbytes = 9u * 256u * (unsigned)cin * 2u;
     c.xstep = 128u * (unsigned)cin * 2u;
     c.whalf = (unsigned)h * 8192u;
     {
@@ -579,25 +618,14 @@ __device__ __forceinline__ void g5q_tile(unsigned char *lds, int blk, int grid, 
         cv_blds16(X, it < 6 ? c.xbytes : c.xbytes_part, c.xoff[0], it * c.xstep, lds + (it < 6 ? kG5QAOff + it * 8192 + c.wave_dst : c.wave_dst_part));
 #pragma unroll
     for (int u = 0; u < kG5Ahead; ++u) cv_blds16(W, c.wbytes, c.woff, (unsigned)(u * 2 * 8192) + c.whalf, lds + u * kG5QWBytes + c.wave_dst);
-    const int lane1 = r * 64 + ((q4 ^ ((0 - (r >> 2)) & 3)) << 4);
-    c.a_off = wm * 4096 + lane1;                               // rows 128 h + 64 wm + 16 i + r of the half-tile
-    c.vb[0] = kG5QAOff + wn * 9 * 1024 + lane1;                // slab cell 9 wn + n + 9 + delta, row r of it
-    c.vb[1] = c.vb[0] + kG5QSlabBytes;
+    g5_ctx_frags(c, r, q4, wm, wn * 9, kG5QAOff, kG5QSlabBytes); // weight rows 128 h + 64 wm + ..; slab cell 9 wn + n + 9 + delta
 
     cv_f32x4 acc[4][9];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const float4 bv = *(const float4 *)(bias + h * 128 + wm * 64 + i * 16 + 4 * q4);
-#pragma unroll
-        for (int n = 0; n < 9; ++n) {
-            acc[i][n][0] = bv.x; acc[i][n][1] = bv.y; acc[i][n][2] = bv.z; acc[i][n][3] = bv.w;
-        }
-    }
+    for (int i = 0; i < 4; ++i) g5_acc_row_from_bias(acc[i], bias + h * 128 + wm * 64 + i * 16 + 4 * q4);
 
     cv_wait_vm<2>(); // all but the weight blocks of taps 1 and 2
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
+    g5_barrier();
 
     int ring_rd = 0, ring_wr = kG5Ahead;
     cv_half8 a0[4], a1[4], b[9];
@@ -614,47 +642,20 @@ __device__ __forceinline__ void g5q_tile(unsigned char *lds, int blk, int grid, 
     cv_wait_vm<0>(); // the out-of-range DMA loads (zeros) must have landed: the image below covers the dump area too
 
     // ---- epilogue: every wave writes its 64 channels x 144 rows into the [row][channel] image; then wave w owns rows 72 w .. 72 w + 71
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier(); // every wave is done reading the slabs and the ring
-    __builtin_amdgcn_sched_barrier(0);
+    g5_barrier(); // every wave is done reading the slabs and the ring
     const int lane_e = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); // formed again, as in g5_tile
     const int re = lane_e & 15, q4e = lane_e >> 4;
     const int prow = lane_e >> 4, piece = lane_e & 15;
     const long pbase = p0 + w * 72 + prow;
     const int gcol = h * 128 + piece * 8;
     cv_half8 rv[18];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int col = wm * 64 + i * 16 + 4 * q4e;
-#pragma unroll
-        for (int n = 0; n < 9; ++n) {
-            cv_half4 o;
-            o[0] = (_Float16)acc[i][n][0];
-            o[1] = (_Float16)acc[i][n][1];
-            o[2] = (_Float16)acc[i][n][2];
-            o[3] = (_Float16)acc[i][n][3];
-            *(cv_half4 *)(lds + ((wn * 9 + n) * 16 + re) * kG5QERow + col * 2) = o;
-        }
-    }
+    g5_image_store<kG5QERow>(lds, acc, wm, wn, re, q4e);
     if (RES) {
 #pragma unroll
         for (int it = 0; it < 18; ++it) rv[it] = *(const cv_half8 *)(R + (pbase + it * 4) * kCvC + gcol);
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    {
-        const cv_half8 zero = (cv_half8)(_Float16)0;
-        const unsigned char *eb = lds + (w * 72 + prow) * kG5QERow + piece * 16;
-#pragma unroll
-        for (int it = 0; it < 18; ++it) {
-            cv_half8 v = *(const cv_half8 *)(eb + it * 4 * kG5QERow);
-            if (RES) v = v + rv[it];
-            if (relu) v = __builtin_elementwise_max(v, zero);
-            *(cv_half8 *)(Y + (pbase + it * 4) * kCvC + gcol) = v;
-        }
-    }
+    g5_barrier<true>();
+    g5_rows_out<kG5QERow, 4, RES, false>(lds, w * 72 + prow, piece, pbase, gcol, Y, relu, rv);
 }
 
 template <bool RES>

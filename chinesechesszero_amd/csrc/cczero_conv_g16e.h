@@ -49,25 +49,11 @@ __device__ __forceinline__ void g5e_step(const G5Ctx &c, cv_f32x4 (&acc)[4][9], 
     unsigned char *const lds = c.lds;
     // as in g5_step: the nine fragments of a sub-rank serve its three dx taps (cell N multiplies b[N + dx]) and are refilled in
     // place for the next sub-rank during the dx = +1 tap; the order is pinned, one scheduling region per cell
-#define G5E_CELL(N)                                                                                                       \
-    {                                                                                                                     \
-        if constexpr (H % 3 == 2)                                                                                         \
-            b[N] = *(const cv_half8 *)(lds + c.vb[BUFn] + ((Hn / 3) * 9 + N) * 1024);                                     \
-        if constexpr (g5_on_board<H, N>()) {                                                                              \
-            constexpr int NB = N + H % 3 - 1;                                                                             \
-            _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                                 \
-                acc[i][N] = __builtin_amdgcn_mfma_f32_16x16x32_f16(acur[i], b[NB], acc[i][N], 0, 0, 0);                   \
-        }                                                                                                                 \
-        __builtin_amdgcn_sched_barrier(0);                                                                                \
-    }
-#define G5E_CELLS(LO, HI)                                                                                                 \
-    if constexpr (LO <= 0 && 0 < HI) G5E_CELL(0) if constexpr (LO <= 1 && 1 < HI) G5E_CELL(1) if constexpr (LO <= 2 && 2 < HI) G5E_CELL(2) \
-    if constexpr (LO <= 3 && 3 < HI) G5E_CELL(3) if constexpr (LO <= 4 && 4 < HI) G5E_CELL(4) if constexpr (LO <= 5 && 5 < HI) G5E_CELL(5) \
-    if constexpr (LO <= 6 && 6 < HI) G5E_CELL(6) if constexpr (LO <= 7 && 7 < HI) G5E_CELL(7) if constexpr (LO <= 8 && 8 < HI) G5E_CELL(8)
+#define G5_REFILL(N) ((Hn / 3) * 9 + N)
     constexpr int H2 = (H + kG5Ahead) % 6;
     // past the last chunk: as in g5_step, the loads are issued against descriptors of zero records and fetch nothing
     const int chunk2 = chunk + (H + kG5Ahead >= 6 ? 1 : 0);
-    G5E_CELLS(0, 1)
+    G5_CELLS(H, 0, 1)
     if constexpr (g5e_dma(H) > 2) { // the next chunk's slab: passes 0,1 | 2,3 | 4 in half-steps 0 | 1 | 2
         constexpr int p0 = H * 2;
         const unsigned so = (unsigned)((chunk + 1) * 64);
@@ -78,24 +64,22 @@ __device__ __forceinline__ void g5e_step(const G5Ctx &c, cv_f32x4 (&acc)[4][9], 
             cv_blds16(c.X, live, c.xoff[p0 + 1], so, lds + kG5AOff + (1 - BUF) * kG5SlabBytes + ((p0 + 1) * 8192 + c.wave_dst));
         __builtin_amdgcn_sched_barrier(0);
     }
-    G5E_CELLS(1, 2)
+    G5_CELLS(H, 1, 2)
     {
         const unsigned wlive = chunk2 <= c.cmask ? c.wbytes : 0u;
         const unsigned so = (unsigned)((H2 + toff + 9 * chunk2) * (2 * 8192)); // half-tile (chunk2, tap H2 + toff): one contiguous 16 KB block
         unsigned char *const d = lds + ring_wr * kG5WBytes + c.wave_dst;
         cv_blds16(c.W, wlive, c.woff, so, d);
         __builtin_amdgcn_sched_barrier(0);
-        G5E_CELLS(2, 3)
+        G5_CELLS(H, 2, 3)
         cv_blds16(c.W, wlive, c.woff, so + 8192u, d + 8192);
         __builtin_amdgcn_sched_barrier(0);
     }
-    G5E_CELLS(3, kG5Split)
+    G5_CELLS(H, 3, kG5Split)
 
     ring_rd = ring_rd + 1 == kG5Ring ? 0 : ring_rd + 1;
     cv_wait_vm<g5e_vmcnt(H)>();
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
+    g5_barrier();
 
     {
         const unsigned char *wa = lds + (ring_rd * kG5WBytes + c.a_off);
@@ -103,10 +87,9 @@ __device__ __forceinline__ void g5e_step(const G5Ctx &c, cv_f32x4 (&acc)[4][9], 
         for (int i = 0; i < 4; ++i) anxt[i] = *(const cv_half8 *)(wa + i * 1024);
         __builtin_amdgcn_sched_barrier(0);
     }
-    G5E_CELLS(kG5Split, 9)
+    G5_CELLS(H, kG5Split, 9)
     ring_wr = ring_wr + 1 == kG5Ring ? 0 : ring_wr + 1;
-#undef G5E_CELLS
-#undef G5E_CELL
+#undef G5_REFILL
 }
 
 // X, Y, R: rows in the group-of-16 layout, M rows (a multiple of 1440); W packed (k_pack_conv_weights_g16). grid = 2 * ceil(groups
@@ -126,11 +109,7 @@ __device__ __forceinline__ void g5e_tile(unsigned char *lds, int blk, const _Flo
     if (live_rows) { // the same cut of the live groups into n_parts equal ranges as k_conv3x3_g16
         int first;
         groups = g5_live_groups(live_rows, row0, groups, first);
-        const long off = (long)first * 1440 * kCvC;
-        X += (long)first * 1440 * cin;
-        if (!HEADS) Y += off; // (HEADS: there is no output tensor)
-        if (RES) R += off;
-        first_board = (long)first * 16;
+        g5_live_part<RES, HEADS>(first, cin, X, R, Y, first_board);
     }
     const int e = __builtin_amdgcn_readfirstlane(blk);
     if (e >= 2 * ((groups + 1) >> 1)) return;
@@ -145,18 +124,10 @@ __device__ __forceinline__ void g5e_tile(unsigned char *lds, int blk, const _Flo
     relu &= 1;
 
     G5Ctx c;
-    c.lds = lds;
-    c.X = X;
-    c.W = W;
-    c.wave_dst = w * 1024;
-    c.lane16 = lane * 16;
+    g5_ctx_common(c, lds, X, W, w, (unsigned)groups * (1440u * 2u) * (unsigned)cin, cin, cin >> 5);
     c.wave_dst_part = w < 4 ? kG5AOff + 4 * 8192 + w * 1024 : kG5Dump + w * 1024;
     c.wave_step_part = w < 4 ? kG5SlabBytes : 0;
-    c.cin = cin;
-    c.cmask = (cin >> 5) - 1;
-    c.xbytes = (unsigned)groups * (1440u * 2u) * (unsigned)cin;
     c.xbytes_part = w < 4 ? c.xbytes : 0u;
-    c.wbytes = 9u * 256u * (unsigned)cin * 2u;
     {
         // slab row sr: 0..287 = group A's rows srcA + sr, 288..575 = group B's; 64-byte rows, position pos of row sr holds source
         // chunk pos ^ f(sr), f = (-(sr >> 2)) & 3 (the swizzle of k_conv3x3_g16)
@@ -180,25 +151,14 @@ __device__ __forceinline__ void g5e_tile(unsigned char *lds, int blk, const _Flo
         cv_blds16(W, c.wbytes, c.woff, (unsigned)((u + toff) * 2 * 8192), d);
         cv_blds16(W, c.wbytes, c.woff, (unsigned)((u + toff) * 2 * 8192 + 8192), d + 8192);
     }
-    const int lane1 = r * 64 + ((q4 ^ ((0 - (r >> 2)) & 3)) << 4);
-    c.a_off = wm * 4096 + lane1;                               // rows 64 wm + 16 i + r of the half-tile
-    c.vb[0] = kG5AOff + wn * 18 * 1024 + lane1;                // slab cell 18 wn + 9 d + n, row r of it
-    c.vb[1] = c.vb[0] + kG5SlabBytes;
+    g5_ctx_frags(c, r, q4, wm, wn * 18, kG5AOff, kG5SlabBytes); // slab cell 18 wn + 9 d + n
 
     cv_f32x4 acc[4][9];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const float4 bv = *(const float4 *)(bias + wm * 64 + i * 16 + 4 * q4);
-#pragma unroll
-        for (int n = 0; n < 9; ++n) {
-            acc[i][n][0] = bv.x; acc[i][n][1] = bv.y; acc[i][n][2] = bv.z; acc[i][n][3] = bv.w;
-        }
-    }
+    for (int i = 0; i < 4; ++i) g5_acc_row_from_bias(acc[i], bias + wm * 64 + i * 16 + 4 * q4);
 
     cv_wait_vm<4>();
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
+    g5_barrier();
 
     int ring_rd = 0, ring_wr = kG5Ahead;
     cv_half8 a0[4], a1[4], b[9];
@@ -215,23 +175,10 @@ __device__ __forceinline__ void g5e_tile(unsigned char *lds, int blk, const _Flo
     cv_wait_vm<0>(); // the out-of-range DMA loads (zeros) must have landed before the LDS is reused / released
 
     // ---- epilogue (k_conv3x3_g16's): the [row][channel] image in LDS, rows 0..143 = group A's edge rank, 144..287 = group B's;
-    // wave w owns image rows 36 w .. 36 w + 35 and moves whole 512-byte rows (residual in, output out)
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int col = wm * 64 + i * 16 + 4 * q4;
-#pragma unroll
-        for (int n = 0; n < 9; ++n) {
-            cv_half4 o;
-            o[0] = (_Float16)acc[i][n][0];
-            o[1] = (_Float16)acc[i][n][1];
-            o[2] = (_Float16)acc[i][n][2];
-            o[3] = (_Float16)acc[i][n][3];
-            *(cv_half4 *)(lds + ((wn * 9 + n) * 16 + r) * kG5ERow + col * 2) = o;
-        }
-    }
+    // wave w owns image rows 36 w .. 36 w + 35 and moves whole 512-byte rows (residual in, output out). The rows go out under the
+    // store predicate in this tile's own copy of g5_rows_out (cczero_conv_g16.h: why)
+    g5_barrier();
+    g5_image_store<kG5ERow>(lds, acc, wm, wn, r, q4);
     const int prow = lane >> 5, piece = lane & 31;
     const long pbase = (w < 4 ? outA : outB) + (w & 3) * 36 + prow;
     const bool store = !(dup && w >= 4);
@@ -240,10 +187,7 @@ __device__ __forceinline__ void g5e_tile(unsigned char *lds, int blk, const _Flo
 #pragma unroll
         for (int it = 0; it < 18; ++it) rv[it] = *(const cv_half8 *)(R + (pbase + it * 2) * kCvC + piece * 8);
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
+    g5_barrier<true>();
     if (store) {
         const cv_half8 zero = (cv_half8)(_Float16)0;
         unsigned char *eb = lds + (w * 36 + prow) * kG5ERow + piece * 16;
@@ -257,10 +201,7 @@ __device__ __forceinline__ void g5e_tile(unsigned char *lds, int blk, const _Flo
         }
     }
     if constexpr (HEADS) { // the heads on the finished rows (cczero_conv_g16.h g5_heads_phase): image rows 0..143 group A's edge rank, 144..287 group B's
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
+        g5_barrier<true>();
         const long board0[2] = {first_board + (long)gA * 16, first_board + (long)gB * 16};
         const int pos0[2] = {side ? 81 : 0, side ? 81 : 0};
         g5_heads_phase(lds, w, lane, ha, board0, pos0, dup);
@@ -328,5 +269,8 @@ __global__ __launch_bounds__(512) void k_conv3x3_g16_one_quad(const _Float16 *__
     __shared__ __attribute__((aligned(16))) unsigned char lds[kG5Lds];
     g5_one_launch<RES, true>(lds, X, W, bias, R, Y, M, relu, cin, live_rows, row0);
 }
+
+#undef G5_CELLS
+#undef G5_CELL
 
 } // namespace ccz
