@@ -82,6 +82,10 @@ class ResignStats(C.Structure):
                 ("playon_won", C.c_int64), ("playon_drawn", C.c_int64), ("playon_plies_after", C.c_int64)]
 
 
+class ExplorationStats(C.Structure):
+    _fields_ = [("explored_moves", C.c_int64), ("forced_selections", C.c_int64), ("visits_pruned", C.c_int64), ("children_pruned", C.c_int64)]
+
+
 # every symbol include/cczero.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 PROTOTYPES = {
@@ -123,6 +127,9 @@ PROTOTYPES = {
     "ccz_set_resign": (C.c_int, [_P, _P, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_double]),
     "ccz_get_resign_stats": (C.c_int, [_P, _P, C.POINTER(ResignStats)]),
     "ccz_resign_status": (C.c_int, [_P, _P, _P, _P, _P, _P]),
+    "ccz_set_root_exploration": (C.c_int, [_P, _P, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32]),
+    "ccz_get_exploration_stats": (C.c_int, [_P, _P, C.POINTER(ExplorationStats)]),
+    "ccz_root_noise": (C.c_int, [_P, _P, _P, _P]),
     "ccz_finish_move": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32]),
     "ccz_root_children": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
     "ccz_principal_variations": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),

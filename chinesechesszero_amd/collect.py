@@ -507,7 +507,8 @@ class CollectPipeline:
                  data_dir: str = DATA_DIR, reference_quirks: bool = False, num_channels: int = 256, resblocks_num: int = 40,
                  finalize_every: int = 0, on_playout=None, max_plies: int = 0, eval_cache_log2: int | None = None, gatherer=None,
                  dense_shards: bool = False, replay_plies: int = 0, train_every: int = 0, train_batch: int = BATCH_SIZE,
-                 playout_cap_fast: int = 0, playout_cap_prob: float | None = None, resign=None, value_q_weight: float = 0.0):
+                 playout_cap_fast: int = 0, playout_cap_prob: float | None = None, resign=None, value_q_weight: float = 0.0,
+                 root_exploration=None):
         # collect + train as one job (both 0: off): the rank that stores the union keeps it in a record ring of ``replay_plies`` plies
         # and runs one Trainer step of ``train_batch`` rows every ``train_every`` lockstep moves, once the ring holds a batch
         self.replay_plies, self.train_every, self.train_batch = int(replay_plies), int(train_every), int(train_batch)
@@ -542,6 +543,13 @@ class CollectPipeline:
             if n_boards <= 1:
                 raise ValueError("resignation runs on the batched path: n_boards must be > 1")
             self.resign = dict(resign) if isinstance(resign, dict) else {"threshold": float(resign)}
+        # exploration inside the search on full-search moves (``root_exploration``: a dict of SelfPlayEngine.set_root_exploration's
+        # arguments; None = off, the reference's search with the sampler's noise after it)
+        self.root_exploration = None
+        if root_exploration is not None:
+            if n_boards <= 1:
+                raise ValueError("root exploration runs on the batched path: n_boards must be > 1")
+            self.root_exploration = dict(root_exploration)
         self.value_q_weight = float(value_q_weight)
         if not 0.0 <= self.value_q_weight <= 1.0:
             raise ValueError(f"value_q_weight must be in [0, 1] (got {value_q_weight})")
@@ -673,7 +681,8 @@ class CollectPipeline:
                                             eval_cache_log2=(24 if self.n_boards >= 192 else 0) if self.eval_cache_log2 is None else int(self.eval_cache_log2),
                                             c_puct=self.c_puct, temp=self.temp, seed=self.seed, board_id_base=rank * self.n_boards,
                                             device=self.device, reference_quirks=self.reference_quirks, max_plies=self.max_plies,
-                                            playout_cap=self.playout_cap, resign=getattr(self, "resign", None))
+                                            playout_cap=self.playout_cap, resign=getattr(self, "resign", None),
+                                            root_exploration=getattr(self, "root_exploration", None))
             if getattr(self, "_viewer", None) is not None:
                 self.selfplay.watch(0, self._viewer)
         for _ in range(n_moves):
@@ -860,6 +869,13 @@ class CollectPipeline:
         after = f"{r['playon_plies_after'] / n:.1f}" if n else "n/a"
         return f", resigned {r['resigned_games']}, play-on {n} (false positives {fp}, mean plies after {after})"
 
+    def exploration_report(self) -> str:
+        """The root-exploration part of the periodic log line (empty with the feature off; syncs)."""
+        if getattr(self, "root_exploration", None) is None or getattr(self, "selfplay", None) is None:
+            return ""
+        e = self.selfplay.engine
+        return format_exploration(e.exploration_stats(), e.stats()["sims"])
+
     def drain_exchange(self, gatherer):
         """End of a multi-rank collection with an asynchronous exchange: blocking, every rank calls it; afterwards every record of
         every rank has reached rank 0's store."""
@@ -894,7 +910,7 @@ class CollectPipeline:
                 while max_calls <= 0 or calls < max_calls:
                     iters = self.collect_data(is_shown=is_shown)
                     calls += 1
-                    log(f"Episode {iters}, steps {self.episode_len}" + self.resign_report())
+                    log(f"Episode {iters}, steps {self.episode_len}" + self.resign_report() + self.exploration_report())
             except KeyboardInterrupt:
                 log("Exit")
             if self.gatherer is not None and hasattr(self.gatherer, "flush_iter") and self.selfplay is not None:
@@ -908,6 +924,16 @@ class CollectPipeline:
             raise
         if finalize:
             self.sink.finalize()
+
+
+def format_exploration(x: dict, sims: int) -> str:
+    """``x`` = ``SelfPlayEngine.exploration_stats()``, ``sims`` = the simulations backed up so far (``stats()['sims']``, fast moves
+    included): explored moves, forced selections per explored move, and the visits pruned from the policy targets as a share of
+    the simulations run."""
+    n = x["explored_moves"]
+    forced = f"{x['forced_selections'] / n:.2f}" if n else "n/a"
+    share = f"{x['visits_pruned'] / sims:.4f}" if sims else "n/a"
+    return f", explored moves {n}, forced selections per move {forced}, pruned share of visits {share} ({x['children_pruned']} children dropped)"
 
 
 def build_parser():
@@ -941,17 +967,25 @@ def build_parser():
     parser.add_argument("--resign-min-ply", type=int, default=None, help=f"... and not before this ply (default {RESIGN_MIN_PLY})")
     parser.add_argument("--resign-playon", type=float, default=None, help="fraction of such games played on to measure the false positives "
                         f"(default {RESIGN_PLAYON}, AlphaGo Zero's)")
+    parser.add_argument("--root-noise-eps", type=float, default=None, help="exploration inside the search on full-search moves: weight of the "
+                        "Dirichlet noise in the ROOT's priors (in [0, 1]); absent = off (the noise is mixed into pi after the search)")
+    parser.add_argument("--root-noise-alpha", type=float, default=None, help="... its Dirichlet alpha (default: the sampler's)")
+    parser.add_argument("--forced-playouts", type=float, default=None, help=f"... forced playouts: a root child is searched until N >= sqrt(k P' S) "
+                        f"(default k = {FORCED_PLAYOUTS}, KataGo's; 0 = none)")
+    parser.add_argument("--no-target-pruning", action="store_true", default=False, help="... keep the forced visits in the recorded policy targets")
     parser.add_argument("--value-q-weight", type=float, default=0.0, help="with --train-every: weight of the recorded root value q in the value "
                         "target, (1 - w) z + w q on rows that carry one (0 = z alone)")
     return parser
 
 
 RESIGN_MOVES, RESIGN_MIN_PLY, RESIGN_PLAYON = 2, 30, 0.1
+FORCED_PLAYOUTS = 2.0
 
 
 def parse_args(argv=None):
     """Parse the command line; refuses ``--resign-moves`` / ``--resign-min-ply`` / ``--resign-playon`` without ``--resign-threshold``
-    (they would silently do nothing). ``args.resign`` is the dict for ``CollectPipeline(resign=...)`` or None."""
+    (they would silently do nothing), and likewise ``--root-noise-alpha`` / ``--forced-playouts`` / ``--no-target-pruning`` without
+    ``--root-noise-eps``. ``args.resign`` / ``args.root_exploration`` are the dicts for ``CollectPipeline(...)`` or None."""
     parser = build_parser()
     args = parser.parse_args(argv)
     extras = {"--resign-moves": args.resign_moves, "--resign-min-ply": args.resign_min_ply, "--resign-playon": args.resign_playon}
@@ -965,6 +999,25 @@ def parse_args(argv=None):
                        "consecutive": RESIGN_MOVES if args.resign_moves is None else args.resign_moves,
                        "min_ply": RESIGN_MIN_PLY if args.resign_min_ply is None else args.resign_min_ply,
                        "p_playon": RESIGN_PLAYON if args.resign_playon is None else args.resign_playon}
+    extras = {"--root-noise-alpha": args.root_noise_alpha, "--forced-playouts": args.forced_playouts,
+              "--no-target-pruning": True if args.no_target_pruning else None}
+    args.root_exploration = None
+    if args.root_noise_eps is None:
+        given = [k for k, v in extras.items() if v is not None]
+        if given:
+            parser.error(f"{', '.join(given)} without --root-noise-eps: root exploration is off")
+    else:
+        if not 0.0 <= args.root_noise_eps <= 1.0:
+            parser.error(f"--root-noise-eps must be in [0, 1] (got {args.root_noise_eps})")
+        if args.root_noise_alpha is not None and not args.root_noise_alpha > 0.0:
+            parser.error(f"--root-noise-alpha must be > 0 (got {args.root_noise_alpha})")
+        if args.forced_playouts is not None and not args.forced_playouts >= 0.0:
+            parser.error(f"--forced-playouts must be >= 0 (got {args.forced_playouts})")
+        if args.boards <= 1:
+            parser.error("--root-noise-eps runs on the batched path: --boards must be > 1")
+        args.root_exploration = {"eps": args.root_noise_eps, "alpha": args.root_noise_alpha,
+                                 "forced_k": FORCED_PLAYOUTS if args.forced_playouts is None else args.forced_playouts,
+                                 "prune_targets": not args.no_target_pruning}
     return args
 
 
@@ -996,7 +1049,8 @@ if __name__ == "__main__":
                            num_channels=args.channels, resblocks_num=args.blocks, max_plies=args.max_plies, device=device,
                            eval_cache_log2=args.eval_cache_log2, gatherer=gatherer, replay_plies=args.replay_plies,
                            train_every=args.train_every, train_batch=args.train_batch, playout_cap_fast=args.playout_cap_fast,
-                           playout_cap_prob=args.playout_cap_prob, resign=args.resign, value_q_weight=args.value_q_weight)
+                           playout_cap_prob=args.playout_cap_prob, resign=args.resign, value_q_weight=args.value_q_weight,
+                           root_exploration=args.root_exploration)
     if world > 1:
         from .launch import guarded
 

@@ -82,6 +82,7 @@ struct ccz_engine {
     uint8_t *route_net = nullptr;  // [B] device: written by k_cache_probe_routed, read by the plan and the gather
     uint64_t salt[2] = {0, 0};
     bool budgets_on = false;       // ccz_set_budgets / ccz_draw_budgets (off: every budget INT32_MAX, every target 1)
+    bool explore_on = false;       // ccz_set_root_exploration(enabled): the host's shadow of ExploreCfg.enabled (scouts are refused with it)
 };
 
 #define ACTIVE(e) ((unsigned)((e)->active > 0 ? (e)->active : (e)->d.B))
@@ -284,6 +285,12 @@ int ccz_create(const ccz_config *cfg, ccz_engine **out)
     ALLOC(d.rec_value, B * d.max_plies);
     ALLOC(d.rec_hasv, B * d.max_plies);
     ALLOC(d.rs_stats, B);
+    ExploreCfg *ex_cfg = nullptr;
+    ALLOC(ex_cfg, 1); // zeroed: root exploration off
+    d.ex_cfg = ex_cfg;
+    ALLOC(d.ex_dir, B * kMaxLegal);
+    ALLOC(d.ex_stamp, B * 2);
+    ALLOC(d.ex_stats, B);
     ALLOC(d.rec_ids, B * d.pi_cap);
     ALLOC(d.rec_pi, B * d.pi_cap);
     ALLOC(d.stats, B);
@@ -478,6 +485,7 @@ int ccz_set_scouts(ccz_engine *e, int32_t n_scouts)
     if (n_scouts < 0 || n_scouts >= e->d.B) return fail(-1, "ccz_set_scouts: n_scouts must be in 0 .. n_boards - 1 (got %d of %d boards)", n_scouts, e->d.B);
     if (n_scouts && !e->d.cache) return fail(-1, "ccz_set_scouts: scouts work through the evaluation cache (ccz_config.eval_cache_log2)");
     if (n_scouts && e->budgets_on) return fail(-1, "ccz_set_scouts: not while simulation budgets are on (ccz_set_budgets(NULL) turns them off)");
+    if (n_scouts && e->explore_on) return fail(-1, "ccz_set_scouts: not while root exploration is on (ccz_set_root_exploration)");
     e->active = n_scouts ? e->d.B - n_scouts : 0;
     return 0;
 }
@@ -686,6 +694,66 @@ int ccz_resign_status(ccz_engine *e, void *stream, uint8_t *state_host, uint8_t 
     if (fire_ply_host) HIP_TRY(hipMemcpyAsync(fire_ply_host, e->d.rs_fire, B * 4, hipMemcpyDeviceToHost, s));
     if (last_value_host) HIP_TRY(hipMemcpyAsync(last_value_host, e->d.rs_last, B * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
+    return 0;
+}
+
+int ccz_set_root_exploration(ccz_engine *e, void *stream, int32_t enabled, double eps, double alpha, double forced_k, int32_t prune_targets)
+{
+    NEED(e);
+    if (!(eps >= 0.0 && eps <= 1.0)) return fail(-1, "ccz_set_root_exploration: eps %g must be in [0, 1]", eps);
+    if (!(alpha > 0.0 && std::isfinite(alpha))) return fail(-1, "ccz_set_root_exploration: alpha %g must be finite and > 0", alpha);
+    if (!(forced_k >= 0.0 && std::isfinite(forced_k))) return fail(-1, "ccz_set_root_exploration: forced_k %g must be finite and >= 0", forced_k);
+    if (enabled && e->active > 0) return fail(-1, "ccz_set_root_exploration: not with scout slots (ccz_set_scouts): the one-game path keeps the reference's search");
+    ExploreCfg v;
+    v.enabled = enabled ? 1 : 0;
+    v.prune = prune_targets ? 1 : 0;
+    v.eps = eps;
+    v.alpha = alpha;
+    v.forced_k = forced_k;
+    const int n = 2 * e->d.B;
+    hipLaunchKernelGGL(k_set_root_exploration, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, const_cast<ExploreCfg *>(e->d.ex_cfg), v, e->d.ex_stamp, n);
+    HIP_TRY(hipGetLastError());
+    e->explore_on = enabled != 0;
+    return 0;
+}
+
+int ccz_get_exploration_stats(ccz_engine *e, void *stream, ccz_exploration_stats *out)
+{
+    NEED(e);
+    if (!out) return fail(-1, "ccz_get_exploration_stats: null output");
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<ExploreBoardStats> st((size_t)e->d.B);
+    HIP_TRY(hipMemcpyAsync(st.data(), e->d.ex_stats, st.size() * sizeof(ExploreBoardStats), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    memset(out, 0, sizeof *out);
+    for (const ExploreBoardStats &b : st) {
+        out->explored_moves += (int64_t)b.explored;
+        out->forced_selections += (int64_t)b.forced;
+        out->visits_pruned += (int64_t)b.visits_pruned;
+        out->children_pruned += (int64_t)b.children_pruned;
+    }
+    return 0;
+}
+
+static int fetch_meta(ccz_engine *e, hipStream_t s);
+
+int ccz_root_noise(ccz_engine *e, void *stream, float *noise_host, int32_t *k_host)
+{
+    NEED(e);
+    if (!noise_host || !k_host) return fail(-1, "ccz_root_noise: null output");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t B = (size_t)e->d.B;
+    std::vector<uint32_t> stamp(B * 2);
+    HIP_TRY(hipMemcpyAsync(noise_host, e->d.ex_dir, B * kMaxLegal * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(stamp.data(), e->d.ex_stamp, B * 8, hipMemcpyDeviceToHost, s));
+    const int rc = fetch_meta(e, s); // syncs
+    if (rc) return rc;
+    for (size_t b = 0; b < B; ++b) { // a row filled for an earlier move (or never) is no noise of this one: k = 0, zeros
+        const bool live = stamp[2 * b] == e->h_meta[b].move_counter + 1u && stamp[2 * b + 1] <= (uint32_t)kMaxLegal;
+        const int k = live ? (int)stamp[2 * b + 1] : 0;
+        k_host[b] = k;
+        for (int i = k; i < kMaxLegal; ++i) noise_host[b * kMaxLegal + i] = 0.0f;
+    }
     return 0;
 }
 

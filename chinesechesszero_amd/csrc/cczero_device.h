@@ -80,6 +80,18 @@ struct ResignBoardStats {
     unsigned long long resigned, resigned_red, resigned_plies, playon, playon_won, playon_drawn, playon_after;
 };
 
+// Root exploration in the search (ccz_set_root_exploration): the settings as the device reads them, and the per-board counters.
+struct ExploreCfg {
+    int32_t enabled;  // 0: the selection reads this one word and is the reference's PUCT on raw priors; k_finish_move likewise
+    int32_t prune;    // 1: policy target pruning in k_finish_move
+    double eps;       // weight of the Dirichlet noise in the root's priors
+    double alpha;     // Dirichlet(alpha)
+    double forced_k;  // forced playouts: a root child with N < sqrt(forced_k * P' * S) is selected first; 0: none
+};
+struct ExploreBoardStats {
+    unsigned long long explored, forced, visits_pruned, children_pruned;
+};
+
 struct Dev {
     int32_t B, cap, maxd, max_plies, pi_cap;
     int32_t reserve;   // nodes of every pool half kept free at re-root time for the next move's expansions
@@ -150,6 +162,11 @@ struct Dev {
     float *rec_value;        // [B][max_plies] root value of the ply, in the view of its side to move
     uint8_t *rec_hasv;       // [B][max_plies] 1: rec_value holds the ply's value
     ResignBoardStats *rs_stats; // [B]
+    // ---- root exploration (ccz_set_root_exploration). Always allocated; "off" is ExploreCfg.enabled == 0
+    const ExploreCfg *ex_cfg;   // [1] written by k_set_root_exploration in stream order
+    float *ex_dir;              // [B][128] Dirichlet component dir_i of the root's child i for the move the stamp names
+    uint32_t *ex_stamp;         // [B][2] (move_counter + 1, k) the row of ex_dir was filled for; (0, 0): none
+    ExploreBoardStats *ex_stats; // [B]
 };
 __device__ __forceinline__ int plane_of(const Dev &D, int type) { return (int)((D.chanpack >> (3 * type)) & 7u); }
 __device__ __forceinline__ int type_in_plane(const Dev &D, int chan) { return (int)((D.typepack >> (3 * chan)) & 7u) + 1; }

@@ -192,6 +192,7 @@ struct Prefetch {
     uint32_t kidw;
     int32_t budget;    // simulations the board may back up in this move (INT32_MAX: budgets off)
     int32_t move_sims; // ... and how many it has, as of the top of the kernel (this launch's backup is not in it)
+    int32_t ex;        // root exploration (ccz_set_root_exploration) applies to the board's current move: on, and a policy-target move
 };
 
 // what the expand+backup phase of this launch changed at the top of the tree (the prefetched root and
@@ -223,6 +224,7 @@ __device__ __forceinline__ Prefetch prefetch_board(const Dev &D, int b, int lane
     P.kidw = D.nodeB[base + 1 + lane];
     P.budget = D.budget[b];
     P.move_sims = D.move_sims[b];
+    P.ex = D.ex_cfg->enabled * (int32_t)D.target[b]; // (both words are requested with the rest: no load waits for the other)
     return P;
 }
 
@@ -342,9 +344,56 @@ __device__ inline void leaf_tail(const Dev &D, int b, int lane, uint16_t *leaf_i
     }
 }
 
+// ------------------------------------------------------------------ root exploration (ccz_set_root_exploration)
+// The Dirichlet component of the root's children `lane` and `64 + lane` for the board's current move: dir_i = g_i / sum(g), g_i the
+// board's Gamma(alpha) draws on Philox words 0..127 of (seed, board id, move counter) -- the draws the sampler mixes into pi when
+// the feature is off --, summed in index order in float64 on lane 0 and stored as float32 in D.ex_dir. The row is filled once per
+// move and board, under the wave-uniform stamp test; every later call reads it back. kids = the root's children; s_g = 128 doubles
+// of LDS scratch. All 64 lanes call it.
+__device__ inline void explore_dir(const Dev &D, const ExploreCfg &xc, int b, int lane, int k, uint32_t move_counter, const NodeA *kids,
+                                   double *s_g, float &d0, float &d1)
+{
+    k = __builtin_amdgcn_readfirstlane(k); // (the same in every lane: say so, the tests below are scalar)
+    move_counter = (uint32_t)__builtin_amdgcn_readfirstlane((int)move_counter);
+    uint32_t *stp = D.ex_stamp + (size_t)b * 2;
+    float *row = D.ex_dir + (size_t)b * kMaxLegal;
+    const uint32_t st0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)stp[0]), st1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)stp[1]);
+    if (st0 == move_counter + 1u && st1 == (uint32_t)k) {
+        d0 = row[lane];
+        d1 = row[64 + lane];
+        return;
+    }
+    const uint64_t gid = D.board_id_base + (uint64_t)b;
+    for (int i = lane; i < k; i += 64) s_g[i] = det_gamma(D.seed, gid, move_counter, (uint32_t)i, xc.alpha);
+    wave_sync();
+    double gs = 0.0;
+    if (lane == 0) for (int i = 0; i < k; ++i) gs += s_g[i];
+    gs = __shfl(gs, 0);
+    d0 = 0.0f;
+    d1 = 0.0f;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int i = 64 * h + lane;
+        if (i < k) {
+            const float f = (float)(gs > 0.0 ? s_g[i] / gs : (double)kids[CCZ_IDX(D, i, D.cap)].P);
+            row[i] = f;
+            if (h) d1 = f; else d0 = f;
+        }
+    }
+    if (lane == 0) { stp[0] = move_counter + 1u; stp[1] = (uint32_t)k; }
+    wave_sync();
+}
+// P'_i = (1 - eps) P_i + eps dir_i in float64, rounded to float32: what the root's score uses in place of the raw prior
+__device__ __forceinline__ float explore_prior(const ExploreCfg &xc, float p, float dir)
+{
+    return (float)((1.0 - xc.eps) * (double)p + xc.eps * (double)dir);
+}
+
 // One wave: PUCT descent from the root of board b, leaf rules, evaluator input. Per tree level there is
 // ONE dependent global load round (the children's 16-B NodeA records + their move/count words); the
 // chosen child's own N / first_child / count are broadcast from the winning lane, not re-read.
+// EX: the root exploration of ccz_set_root_exploration is compiled in (not in the scouted run: the two exclude each other).
+template <bool EX>
 __device__ inline void select_phase(const Dev &D, int b, int lane, uint16_t *leaf_in, SelectShared &sh, const Prefetch &P,
                                     const TopPatch &tp)
 {
@@ -386,6 +435,17 @@ __device__ inline void select_phase(const Dev &D, int b, int lane, uint16_t *lea
     bool bad = false;
     if (lane == 0) path[0] = 0;
 
+    // ---- root exploration: noisy priors and forced playouts at depth 0 (off: the one prefetched word tested here)
+    bool ex = false;
+    ExploreCfg xc;
+    xc.enabled = 0; xc.prune = 0; xc.eps = 0.0; xc.alpha = 1.0; xc.forced_k = 0.0;
+    float xd0 = 0.0f, xd1 = 0.0f;
+    if (EX && __builtin_amdgcn_readfirstlane(P.ex) && (nb >> 16) != 0u) {
+        ex = true;
+        xc = *D.ex_cfg;
+        explore_dir(D, xc, b, lane, (int)(nb >> 16), m.move_counter, A + pa.fc, (double *)sh.S.cand, xd0, xd1);
+    }
+
     // ---- PUCT descent (mcts.py:105-111, 41-61)
     for (;;) {
         const int nc = (int)(nb >> 16);
@@ -395,6 +455,8 @@ __device__ inline void select_phase(const Dev &D, int b, int lane, uint16_t *lea
         int besti = 0x7fffffff, bN = 0, bfc = -1;
         float bQ = 0.0f;
         uint32_t bw = 0;
+        bool bF = false;
+        const bool exroot = EX && ex && depth == 0;
         for (int c0 = 0; c0 < nc; c0 += 64) {
             const int i = c0 + lane;
             if (i < nc) {
@@ -414,9 +476,15 @@ __device__ inline void select_phase(const Dev &D, int b, int lane, uint16_t *lea
                     w = Bn[CCZ_IDX(D, pa.fc + i, D.cap)];
                 }
                 // value + c_puct*prob*sqrt(N_parent)/(1+N): float32 product, float64 elsewhere; inf if unvisited
-                const double sc = c.N == 0 ? __builtin_huge_val()
-                                           : (double)c.Q + (double)(D.c_puct * c.P) * sqrtNp / (double)(1 + c.N);
-                if (sc > best) { best = sc; besti = i; bN = c.N; bQ = c.Q; bfc = c.fc; bw = w; }
+                float pp = c.P;
+                bool fsel = false;
+                if (exroot) { // P' for P, and a visited child short of its forced playouts scores like an unvisited one
+                    pp = explore_prior(xc, c.P, c0 ? xd1 : xd0);
+                    fsel = xc.forced_k > 0.0 && c.N > 0 && (double)c.N < sqrt(xc.forced_k * (double)pp * (double)(pa.N - 1));
+                }
+                const double sc = (c.N == 0 || fsel) ? __builtin_huge_val()
+                                                     : (double)c.Q + (double)(D.c_puct * pp) * sqrtNp / (double)(1 + c.N);
+                if (sc > best) { best = sc; besti = i; bN = c.N; bQ = c.Q; bfc = c.fc; bw = w; bF = fsel; }
             }
         }
         // first maximum in insertion order wins (Python max()): wave max of the score, then the lowest index
@@ -427,6 +495,7 @@ __device__ inline void select_phase(const Dev &D, int b, int lane, uint16_t *lea
         if (h1 == 0ull) { bad = true; set_err(D, 32); break; } // NaN priors: no comparable child
         const int owner = __builtin_amdgcn_readfirstlane((h0 ? __ffsll((long long)h0) : __ffsll((long long)h1)) - 1);
         besti = __builtin_amdgcn_readlane(besti, owner);
+        if (exroot && __builtin_amdgcn_readlane((int)bF, owner) && lane == 0) D.ex_stats[b].forced += 1;
         const int child = pa.fc + besti;
         pa.N = __builtin_amdgcn_readlane(bN, owner);
         pa.Q = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(bQ), owner));
@@ -456,7 +525,7 @@ __global__ __launch_bounds__(64) void k_select(Dev D, uint16_t *leaf_in)
     TopPatch none;
     none.active = false; none.root_expanded = false; none.kid_expanded = false; none.k = 0; none.first_id = 0; none.n0 = 0;
     none.rootN = 0; none.rootQ = 0.0f; none.node1 = -1; none.N1 = 0; none.Q1 = 0.0f; none.has1 = false;
-    select_phase(D, blockIdx.x, threadIdx.x, leaf_in, sh, P, none);
+    select_phase<true>(D, blockIdx.x, threadIdx.x, leaf_in, sh, P, none);
 }
 
 // ------------------------------------------------------------------ scouts: the NEXT leaves of a board, before it asks for them
@@ -653,7 +722,7 @@ __global__ __launch_bounds__(64) void k_step(Dev D, const float *prob, const flo
     __threadfence_block();
     __syncthreads();
     CCZ_STAMP(D, b, lane, 2)
-    select_phase(D, b, lane, leaf_in, sh, P, tp);
+    select_phase<true>(D, b, lane, leaf_in, sh, P, tp);
     CCZ_STAMP(D, b, lane, 9)
 }
 
@@ -1085,7 +1154,7 @@ __global__ __launch_bounds__(64 * MAXW) void k_scouted_run(Dev D, uint16_t *leaf
         ++done;
         if (--left <= 0) break;         // the move's last simulation: nothing is selected behind it (ccz_expand_backup_compact)
         if (real) {
-            select_phase(D, w, lane, leaf_in, sh[w], P, tp);
+            select_phase<false>(D, w, lane, leaf_in, sh[w], P, tp);
             __threadfence_block();      // the leaf (global memory, written by this wave) is read back by its own probe
             const int st = cache_probe_wave(D, w, lane);
             if (lane == 0) s_state[w] = st;
@@ -1148,16 +1217,18 @@ __device__ __forceinline__ void root_pi(const int32_t *s_vis, double *s_pi, int 
 // (lane 0). s_g[k] is scratch (the Gamma draws, then the cdf). k_finish_move passes null outputs; k_move_distribution passes
 // g_out / mixed_out (float64 [k]) and u_out to read what the sampler drew -- the same instructions, written out on lane 0.
 __device__ __forceinline__ void sample_move(const Dev &D, uint64_t gid, uint64_t move_no, const double *s_pi, double *s_g, int k,
-                                            int lane, int *choice, double *g_out, double *mixed_out, double *u_out)
+                                            int lane, int *choice, double *g_out, double *mixed_out, double *u_out, bool mix = true)
 {
-    for (int i = lane; i < k; i += 64) s_g[i] = det_gamma(D.seed, gid, move_no, (uint32_t)i, D.alpha);
+    // mix == false (a move searched with root exploration: the noise has acted in the search): the move is drawn from pi itself on the
+    // same choice word; the Gamma draws are made only for a caller that reads them
+    if (mix || g_out) for (int i = lane; i < k; i += 64) s_g[i] = det_gamma(D.seed, gid, move_no, (uint32_t)i, D.alpha);
     __syncthreads();
     if (lane == 0) {
         double gs = 0.0, acc = 0.0, ua, ub;
-        for (int i = 0; i < k; ++i) gs += s_g[i];
+        if (mix) for (int i = 0; i < k; ++i) gs += s_g[i];
         for (int i = 0; i < k; ++i) {
             const double dir = gs > 0.0 ? s_g[i] / gs : s_pi[i];
-            const double mx = (1.0 - D.eps) * s_pi[i] + D.eps * dir;
+            const double mx = mix ? (1.0 - D.eps) * s_pi[i] + D.eps * dir : s_pi[i];
             if (g_out) g_out[i] = s_g[i];
             if (mixed_out) mixed_out[i] = mx;
             acc += mx;
@@ -1169,6 +1240,66 @@ __device__ __forceinline__ void sample_move(const Dev &D, uint64_t gid, uint64_t
         for (int i = 0; i < k; ++i) if (s_g[i] / acc <= ua) idx = i + 1; // searchsorted(side="right")
         *choice = idx < k ? idx : k - 1;
     }
+}
+
+// Policy target pruning of a move searched with root exploration (ccz_set_root_exploration, include/cczero.h): s_vis[k] -> s_vp[k],
+// the visit counts pi is formed from. c* = the most visited child (lowest index on ties) keeps its count; every other visited child
+// gives back the visits PUCT would not have made without its forced playouts: at most nf_i = ceil(sqrt(forced_k P'_i S)) of them, and
+// no more than bring its score Q_i + E_i / (1 + N') up to c*'s; what would be left with at most one visit is dropped. All float64.
+// s_q / s_pn [128] and s_g [128] are LDS scratch. All 64 lanes call it; count: the board's counters are updated (k_finish_move).
+__device__ inline void explore_targets(const Dev &D, const ExploreCfg &xc, int b, int lane, int k, uint32_t move_counter, const NodeA &root,
+                                       const NodeA *kids, const int32_t *s_vis, int32_t *s_vp, float *s_q, float *s_pn, double *s_g, bool count)
+{
+    float xd0, xd1;
+    explore_dir(D, xc, b, lane, k, move_counter, kids, s_g, xd0, xd1);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int i = 64 * h + lane;
+        if (i < k) {
+            const NodeA c = kids[CCZ_IDX(D, i, D.cap)];
+            s_q[i] = c.Q;
+            s_pn[i] = explore_prior(xc, c.P, h ? xd1 : xd0);
+            s_vp[i] = s_vis[i];
+        }
+    }
+    __syncthreads();
+    int vp = 0, cp = 0;
+    if (xc.prune) {
+        int cs = 0; // every lane runs the same <= 128 terms on the same LDS words: wave-uniform without a broadcast
+        for (int i = 1; i < k; ++i) if (s_vis[i] > s_vis[cs]) cs = i;
+        const double sq = sqrt((double)root.N), S = (double)(root.N - 1);
+        const double top = (double)s_q[cs] + (double)(D.c_puct * s_pn[cs]) * sq / (double)(1 + s_vis[cs]);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int i = 64 * h + lane;
+            if (i < k && i != cs && s_vis[i] > 0) {
+                const int n = s_vis[i];
+                const double E = (double)(D.c_puct * s_pn[i]) * sq;
+                const double nf = ceil(sqrt(xc.forced_k * (double)s_pn[i] * S));
+                const double gap = top - (double)s_q[i];
+                double need = (double)n;
+                if (gap > 0.0) { const double t = ceil(E / gap - 1.0); need = t > 0.0 ? t : 0.0; }
+                double keep = (double)n - nf;
+                keep = keep > need ? keep : need;
+                int np = keep >= (double)n ? n : (keep > 0.0 ? (int)keep : 0);
+                if (np < n && np <= 1) np = 0;
+                s_vp[i] = np;
+                vp += n - np;
+                cp += np == 0 ? 1 : 0;
+            }
+        }
+    }
+    if (count) {
+        vp = __builtin_amdgcn_readlane(wave_incl_scan(vp, lane), 63);
+        cp = __builtin_amdgcn_readlane(wave_incl_scan(cp, lane), 63);
+        if (lane == 0) {
+            ExploreBoardStats &xs = D.ex_stats[b];
+            xs.explored += 1;
+            xs.visits_pruned += (unsigned long long)vp;
+            xs.children_pruned += (unsigned long long)cp;
+        }
+    }
+    __syncthreads();
 }
 
 // a per-board temperature the softmax of root_pi cannot take (1/temp of 0 or NaN): CCZ_ERR_BAD_TEMP, the board neither records nor moves
@@ -1230,6 +1361,8 @@ __global__ __launch_bounds__(64) void k_move_distribution(Dev D, const double *t
     __shared__ int32_t s_vis[kMaxLegal];
     __shared__ double s_pi[kMaxLegal];
     __shared__ double s_g[kMaxLegal];
+    __shared__ int32_t s_vp[kMaxLegal];
+    __shared__ float s_q[kMaxLegal], s_pn[kMaxLegal];
     __shared__ int s_choice;
     const BoardMeta m = D.meta[b];
     const size_t base = ((size_t)b * 2 + *D.half) * (size_t)D.cap;
@@ -1244,8 +1377,12 @@ __global__ __launch_bounds__(64) void k_move_distribution(Dev D, const double *t
     if (k == 0) { if (lane == 0) u_out[b] = __builtin_nan(""); return; }
     for (int i = lane; i < k; i += 64) s_vis[i] = A[CCZ_IDX(D, root.fc + i, D.cap)].N;
     __syncthreads();
-    root_pi(s_vis, s_pi, k, temp, lane);
-    sample_move(D, D.board_id_base + (uint64_t)b, m.move_counter, s_pi, s_g, k, lane, &s_choice, g, mixed, u_out + b);
+    // a move searched with root exploration: pi of the pruned counts, no mixing (mixed == pi), the Gamma draws as they would have been
+    const ExploreCfg xc = *D.ex_cfg;
+    const bool explored = xc.enabled && D.target[b];
+    if (explored) explore_targets(D, xc, b, lane, k, m.move_counter, root, A + root.fc, s_vis, s_vp, s_q, s_pn, s_g, false);
+    root_pi(explored ? s_vp : s_vis, s_pi, k, temp, lane);
+    sample_move(D, D.board_id_base + (uint64_t)b, m.move_counter, s_pi, s_g, k, lane, &s_choice, g, mixed, u_out + b, !explored);
 }
 
 // CCZ_RULE_PERPETUAL_CHECK: the game ends by fourfold repetition; inside the repetition window --
@@ -1293,6 +1430,8 @@ __global__ __launch_bounds__(64) void k_finish_move(Dev D, const int32_t *forced
     __shared__ double s_pi[kMaxLegal];
     __shared__ double s_g[kMaxLegal];
     __shared__ int32_t s_src[64], s_dst[64], s_cnt[64];
+    __shared__ int32_t s_vp[kMaxLegal];
+    __shared__ float s_q[kMaxLegal], s_pn[kMaxLegal];
     __shared__ int s_choice;
 
     BoardMeta m = D.meta[b];
@@ -1324,7 +1463,6 @@ __global__ __launch_bounds__(64) void k_finish_move(Dev D, const int32_t *forced
     __syncthreads();
 
     // ---- pi (mcts.py:162-166) and the training record (game.py:195-198)
-    if (k > 0) root_pi(s_vis, s_pi, k, temp, lane);
     if (m.ply >= D.max_plies || m.pi_used + (uint32_t)k > (uint32_t)D.pi_cap) {
         // documented cap: the game is adjudicated a draw, its records so far stay valid
         if (lane == 0) {
@@ -1341,6 +1479,12 @@ __global__ __launch_bounds__(64) void k_finish_move(Dev D, const int32_t *forced
     }
     const ResignCfg rc = *D.rs_cfg;
     const int tgt = D.target[b];
+    // root exploration (ccz_set_root_exploration; off: one word read): pi is formed from the pruned counts, the move drawn from it
+    // without Dirichlet mixing. The resignation value below, ccz_root_children and the lines read the counts as searched (s_vis).
+    const ExploreCfg xc = *D.ex_cfg;
+    const bool explored = xc.enabled && tgt && k > 0;
+    if (explored) explore_targets(D, xc, b, lane, k, m.move_counter, root, A + root.fc, s_vis, s_vp, s_q, s_pn, s_g, true);
+    if (k > 0) root_pi(explored ? s_vp : s_vis, s_pi, k, temp, lane);
     {
         const size_t r = (size_t)b * D.max_plies + CCZ_IDX(D, m.ply, D.max_plies);
         if (lane < 24) ((uint32_t *)(D.rec_sq + r * 96))[lane] = ((const uint32_t *)s_sq)[lane];
@@ -1424,7 +1568,7 @@ __global__ __launch_bounds__(64) void k_finish_move(Dev D, const int32_t *forced
         if (lane == 0) s_choice = found;
     } else {
         const uint64_t gid = D.board_id_base + (uint64_t)b;
-        sample_move(D, gid, m.move_counter, s_pi, s_g, k, lane, &s_choice, nullptr, nullptr, nullptr);
+        sample_move(D, gid, m.move_counter, s_pi, s_g, k, lane, &s_choice, nullptr, nullptr, nullptr, !explored);
     }
     __syncthreads();
     const int ci = s_choice;
@@ -2197,6 +2341,14 @@ __global__ void k_sample_record_values(const uint8_t *ring, long long cap_plies,
 __global__ void k_set_resign(ResignCfg *cfg, ResignCfg v)
 {
     if (blockIdx.x == 0 && threadIdx.x == 0) *cfg = v;
+}
+
+// ccz_set_root_exploration: the settings reach the device in stream order; every board's noise row is invalidated (alpha may have changed)
+__global__ void k_set_root_exploration(ExploreCfg *cfg, ExploreCfg v, uint32_t *stamps, int n)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) stamps[i] = 0u;
+    if (i == 0) *cfg = v;
 }
 
 // ------------------------------------------------------------------ stateless batch rules

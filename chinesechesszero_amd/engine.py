@@ -49,6 +49,7 @@ class SelfPlayEngine:
         self.device = torch.device("cuda", device)
         self.B = int(n_boards)
         self.n_playout = int(n_playout)
+        self.alpha = float(np.float32(alpha))   # the sampler's Dirichlet alpha as ccz_config carries it (float32): the default of set_root_exploration
         flags = (_lib.FLAG_REFERENCE_QUIRKS if reference_quirks else 0) | (0 if mirror else _lib.FLAG_NO_MIRROR) \
             | (_lib.FLAG_VALUE_F16 if value_f16 else 0) | (_lib.FLAG_CACHE_VERIFY if cache_verify else 0) | (_lib.FLAG_STRICT if strict else 0)
         self.strict = bool(strict)
@@ -417,6 +418,34 @@ class SelfPlayEngine:
         s = _lib.ResignStats()
         check(self.L.ccz_get_resign_stats(self.h, self._stream(), C.byref(s)))
         return {f: int(getattr(s, f)) for f, _ in _lib.ResignStats._fields_}
+
+    # ------------------------------------------------------------------ root exploration (include/cczero.h ccz_set_root_exploration)
+    def set_root_exploration(self, eps, alpha: float | None = None, forced_k: float = 2.0, prune_targets: bool = True):
+        """Exploration inside the search, on policy-target moves: Dirichlet(``alpha``) noise of weight ``eps`` in the ROOT's priors
+        (nodes keep their raw priors), forced playouts (``forced_k``, KataGo's 2; 0 = none) and policy target pruning
+        (``prune_targets``): pi is formed from the pruned visit counts and the move drawn from it without the sampler's mixing.
+        ``alpha`` None: the engine's sampler alpha. ``eps`` None: off, the state of a new engine. Fast moves of playout-cap
+        randomisation search and sample as without it. Not with scout slots. No host sync."""
+        if eps is None:
+            check(self.L.ccz_set_root_exploration(self.h, self._stream(), 0, 0.0, 1.0, 0.0, 0))
+            return
+        a = self.alpha if alpha is None else float(alpha)
+        check(self.L.ccz_set_root_exploration(self.h, self._stream(), 1, float(eps), a, float(forced_k), 1 if prune_targets else 0))
+
+    def exploration_stats(self) -> dict:
+        """Sums over boards (``ccz_exploration_stats``; syncs): ``explored_moves``, ``forced_selections`` (root selections won by the
+        forced-playout rule on a visited child), ``visits_pruned`` and ``children_pruned`` (taken out of the policy targets)."""
+        s = _lib.ExplorationStats()
+        check(self.L.ccz_get_exploration_stats(self.h, self._stream(), C.byref(s)))
+        return {f: int(getattr(s, f)) for f, _ in _lib.ExplorationStats._fields_}
+
+    def root_noise(self):
+        """``(noise float32 [B,128], k int32 [B])``: the Dirichlet component of every root child for the move being searched, as the
+        score used it (zero past k; k = 0 on a board without noise for its current move). Syncs (tests, diagnostics)."""
+        noise = np.zeros((self.B, MAX_LEGAL), np.float32)
+        k = np.zeros(self.B, np.int32)
+        check(self.L.ccz_root_noise(self.h, self._stream(), _ptr(noise), _ptr(k)))
+        return noise, k
 
     def _to_dev(self, x, dtype, name):
         t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x, dtype={torch.int32: np.int32, torch.uint8: np.uint8}[dtype]))

@@ -216,7 +216,8 @@ class BatchedSelfPlay:
 
     def __init__(self, evaluator, n_boards: int, n_playout: int = 400, c_puct: float = C_PUCT, eps: float = EPS,
                  alpha: float = ALPHA, temp: float = 1.0, seed: int = 0, board_id_base: int = 0, device: int = 0,
-                 sampling: str = "device", use_graph: bool = False, version_fn=None, playout_cap=None, resign=None, **engine_kw):
+                 sampling: str = "device", use_graph: bool = False, version_fn=None, playout_cap=None, resign=None,
+                 root_exploration=None, **engine_kw):
         """``playout_cap`` = ``(n_fast, p_full)``: playout-cap randomisation -- every move of every board is a full search of
         ``n_playout`` simulations with probability ``p_full``, else a fast one of ``n_fast``; fast plies carry ``REC_FAST`` in their
         record header so that a trainer can keep them out of the policy loss (``engine.draw_budgets``). The loop still runs
@@ -228,6 +229,10 @@ class BatchedSelfPlay:
         ``resign``: a threshold in [-1, 0], or a dict of :meth:`SelfPlayEngine.set_resign`'s arguments (``threshold``,
         ``consecutive``, ``min_ply``, ``p_playon``): self-play resignation with play-on calibration. Device sampling only: with
         host sampling every move is forced and a forced board never resigns. None (default): off.
+        ``root_exploration``: a dict of :meth:`SelfPlayEngine.set_root_exploration`'s arguments (``eps``, and optionally ``alpha``,
+        ``forced_k``, ``prune_targets``): the Dirichlet noise acts on the root's priors inside the search, with forced playouts and
+        policy target pruning, on full-search moves; fast moves of ``playout_cap`` are left alone. Device sampling only: the host
+        sampler would mix its own noise into the pruned pi a second time. None (default): off.
         ``version_fn() -> hashable``: what tells the evaluation cache (and a captured hipGraph) that the evaluator's weights
         changed; default: ``weights_version`` of the evaluator's owner. An evaluator that accepts a plan but exposes neither is
         refused: its cached evaluations could never be invalidated."""
@@ -235,6 +240,8 @@ class BatchedSelfPlay:
             raise ValueError("sampling must be 'device' (Philox on the GPU) or 'numpy' (reference-exact host RNG)")
         if resign is not None and sampling != "device":
             raise ValueError("resign needs sampling='device': with host sampling every move is forced, and a forced board never resigns")
+        if root_exploration is not None and sampling != "device":
+            raise ValueError("root_exploration needs sampling='device': the host sampler mixes Dirichlet noise into pi after the search")
         self.playout_cap = None
         if playout_cap is not None:
             n_fast, p_full = playout_cap
@@ -250,6 +257,10 @@ class BatchedSelfPlay:
         if resign is not None:
             self.resign = dict(resign) if isinstance(resign, dict) else {"threshold": float(resign)}
             self.engine.set_resign(**self.resign)
+        self.root_exploration = None
+        if root_exploration is not None:
+            self.root_exploration = dict(root_exploration)
+            self.engine.set_root_exploration(**self.root_exploration)
         self.B = n_boards
         self.n_playout = n_playout
         self.sampling = sampling

@@ -397,6 +397,45 @@ int ccz_get_resign_stats(ccz_engine *e, void *stream, ccz_resign_stats *out); /*
  * game); any pointer may be NULL. */
 int ccz_resign_status(ccz_engine *e, void *stream, uint8_t *state_host, uint8_t *run_host, int32_t *fire_ply_host, float *last_value_host);
 
+/* ---- root exploration in the search: root noise, forced playouts, policy target pruning (additive to ABI 8) ---------------------------
+ * AlphaZero puts the Dirichlet noise into the root's PRIORS; KataGo adds forced playouts and policy target pruning, so that a move the
+ * noise favours gets real visits and the visits spent on exploration are taken out of the policy target again. Off after ccz_create:
+ * every kernel then computes, records and counts exactly what it does without the feature (the noise is mixed into pi by the sampler
+ * after the search, mcts.py:216-224, and pi is the raw visit distribution).
+ *   ccz_set_root_exploration: asynchronous on `stream`, takes effect with the next selection / ccz_finish_move. enabled = 0: off (the
+ *     other arguments are still validated). eps in [0, 1]; alpha finite and > 0; forced_k finite and >= 0 (KataGo: 2; 0: no forced
+ *     playouts); prune_targets 0 / 1. Fails while scout slots are active, and ccz_set_scouts(n > 0) fails while it is enabled.
+ * It applies to a board whose current move is a policy-target move (target byte 1: every board unless ccz_set_budgets /
+ * ccz_draw_budgets say otherwise); a fast move of playout-cap randomisation searches and samples as without the feature. On such a
+ * board, k = number of root children, S = root.N - 1 (= the sum of the children's N while no kept subtree was pruned):
+ *   1. noise: g_i = the board's Gamma(alpha) draw i of this move (the draws the sampler uses when the feature is off), G = sum g_i in
+ *      index order in float64, dir_i = (float)(G > 0 ? g_i / G : P_i), P'_i = (float)((1 - eps) (double)P_i + eps (double)dir_i).
+ *      The selection scores the ROOT's children with (double)(c_puct * P'_i) * sqrt(N_root) / (1 + N_i); nodes keep their raw P (a
+ *      kept subtree never carries noise, the evaluation cache is untouched, ccz_root_children reports raw P). dir is computed once
+ *      per move and board, at the first selection that finds the root expanded.
+ *   2. forced playouts (forced_k > 0): a root child with N_i > 0 and (double)N_i < sqrt(forced_k * (double)P'_i * (double)S) scores
+ *      +inf like an unvisited one; the first maximum in child order still wins.
+ *   3. ccz_finish_move, policy target pruning (prune_targets): c* = the child of largest N (lowest index on ties) keeps N'_* = N_*.
+ *      With E_i = (double)(c_puct * P'_i) * sqrt((double)N_root) and top = Q_* + E_* / (1 + N_*), every other child with N_i > 0 gets
+ *      nf_i = ceil(sqrt(forced_k P'_i S)), gap = top - Q_i, need_i = gap > 0 ? max(0, ceil(E_i / gap - 1)) : N_i,
+ *      N'_i = min(N_i, max(need_i, N_i - nf_i, 0)), and N'_i = 0 if N'_i < N_i and N'_i <= 1; all in float64. Without pruning N' = N.
+ *      pi = the usual softmax chain on N'; that pi is recorded (also under a forced move) and the move is drawn from it on the usual
+ *      choice word with NO Dirichlet mixing, whatever eps -- the call's or ccz_config's -- is: enabled alone decides. (So enabled = 1,
+ *      eps = 0, forced_k = 0, prune_targets = 0 searches and records exactly like an engine without the call, and moves like one
+ *      whose ccz_config.eps is 0.) ccz_move_distribution returns that pi as `mixed` and the unused Gamma draws.
+ * The resignation value, ccz_root_children and ccz_principal_variations read the counts as searched. */
+typedef struct ccz_exploration_stats { /* sums over boards */
+    int64_t explored_moves;    /* plies recorded with root exploration                                                        */
+    int64_t forced_selections; /* root selections in which the chosen child had N > 0 and won by the forced-playout rule       */
+    int64_t visits_pruned;     /* sum of N_i - N'_i                                                                            */
+    int64_t children_pruned;   /* children with N_i > 0 and N'_i = 0                                                           */
+} ccz_exploration_stats;
+int ccz_set_root_exploration(ccz_engine *e, void *stream, int32_t enabled, double eps, double alpha, double forced_k, int32_t prune_targets);
+int ccz_get_exploration_stats(ccz_engine *e, void *stream, ccz_exploration_stats *out); /* syncs */
+/* the noise of the move being searched (syncs; tests, diagnostics): noise_host float [B*128] = dir_i as the score used it, zero past
+ * k; k_host int32 [B] = the root's child count the row was filled for, 0 on a board that has no row for its current move. */
+int ccz_root_noise(ccz_engine *e, void *stream, float *noise_host, int32_t *k_host);
+
 /* ---- once per move ------------------------------------------------------------------------ */
 /* Replaces MCTS.get_move_probs' tail (mcts.py:162-166), MCTS_AI.get_action's choice
  * (mcts.py:216-224), MCTS.update_with_move (mcts.py:168-178) and the per-move part of
