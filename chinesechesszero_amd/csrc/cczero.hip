@@ -87,6 +87,15 @@ struct ccz_engine {
 
 #define ACTIVE(e) ((unsigned)((e)->active > 0 ? (e)->active : (e)->d.B))
 
+// one record of counters per board, read back for the caller to sum (syncs)
+template <typename T> static int fetch_board_stats(ccz_engine *e, hipStream_t s, const T *dev, std::vector<T> &st)
+{
+    st.resize((size_t)e->d.B);
+    HIP_TRY(hipMemcpyAsync(st.data(), dev, st.size() * sizeof(T), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return 0;
+}
+
 // ---- the launches of the group-of-16 tower kernels (cczero_conv_g16.h, cczero_conv_g16e.h) ----
 static bool g16_bad_part(int32_t part, int32_t n_parts) { return n_parts < 1 || n_parts > 256 || part < 0 || part >= n_parts; }
 
@@ -347,15 +356,21 @@ int ccz_destroy(ccz_engine *e)
 
 #define NEED(e) do { if (!(e)) return fail(-1, "%s: null engine", __func__); } while (0)
 
+// the caller's host mask on the device: *mask = st_mask, null without one. st_mask is reused by the next call, so a caller that passed a
+// mask syncs after its launch
+static int stage_mask(ccz_engine *e, hipStream_t s, const uint8_t *mask_host, const uint8_t **mask)
+{
+    if (mask_host) HIP_TRY(hipMemcpyAsync(e->st_mask, mask_host, (size_t)e->d.B, hipMemcpyHostToDevice, s));
+    *mask = mask_host ? e->st_mask : nullptr;
+    return 0;
+}
+
 int ccz_reset(ccz_engine *e, void *stream, const uint8_t *mask_host)
 {
     NEED(e);
     hipStream_t s = (hipStream_t)stream;
-    const uint8_t *mask = nullptr;
-    if (mask_host) {
-        HIP_TRY(hipMemcpyAsync(e->st_mask, mask_host, (size_t)e->d.B, hipMemcpyHostToDevice, s));
-        mask = e->st_mask;
-    }
+    const uint8_t *mask;
+    if (const int rc = stage_mask(e, s, mask_host, &mask)) return rc;
     hipLaunchKernelGGL(k_reset, dim3(e->d.B), dim3(64), 0, s, e->d, mask);
     HIP_TRY(hipGetLastError());
     if (mask_host) HIP_TRY(hipStreamSynchronize(s)); // st_mask is reused by the next call
@@ -391,11 +406,8 @@ int ccz_set_positions(ccz_engine *e, void *stream, const uint8_t *sq_dev, const 
     if (max_moves < 0) return fail(-1, "ccz_set_positions: negative max_moves");
     if (n_moves_dev && !moves_dev && max_moves > 0) return fail(-1, "ccz_set_positions: n_moves without moves");
     hipStream_t s = (hipStream_t)stream;
-    const uint8_t *mask = nullptr;
-    if (mask_host) {
-        HIP_TRY(hipMemcpyAsync(e->st_mask, mask_host, (size_t)e->d.B, hipMemcpyHostToDevice, s));
-        mask = e->st_mask;
-    }
+    const uint8_t *mask;
+    if (const int rc = stage_mask(e, s, mask_host, &mask)) return rc;
     hipLaunchKernelGGL(k_set_positions, dim3(e->d.B), dim3(64), 0, s, e->d, mask, sq_dev, turn_dev, halfmove_dev, moves_dev, n_moves_dev,
                        (int)max_moves, status_dev);
     HIP_TRY(hipGetLastError());
@@ -407,11 +419,8 @@ int ccz_reset_tree(ccz_engine *e, void *stream, const uint8_t *mask_host)
 {
     NEED(e);
     hipStream_t s = (hipStream_t)stream;
-    const uint8_t *mask = nullptr;
-    if (mask_host) {
-        HIP_TRY(hipMemcpyAsync(e->st_mask, mask_host, (size_t)e->d.B, hipMemcpyHostToDevice, s));
-        mask = e->st_mask;
-    }
+    const uint8_t *mask;
+    if (const int rc = stage_mask(e, s, mask_host, &mask)) return rc;
     hipLaunchKernelGGL(k_reset_tree, dim3((e->d.B + 255) / 256), dim3(256), 0, s, e->d, mask);
     HIP_TRY(hipGetLastError());
     if (mask_host) HIP_TRY(hipStreamSynchronize(s)); // st_mask is reused by the next call
@@ -667,10 +676,8 @@ int ccz_get_resign_stats(ccz_engine *e, void *stream, ccz_resign_stats *out)
 {
     NEED(e);
     if (!out) return fail(-1, "ccz_get_resign_stats: null output");
-    hipStream_t s = (hipStream_t)stream;
-    std::vector<ResignBoardStats> st((size_t)e->d.B);
-    HIP_TRY(hipMemcpyAsync(st.data(), e->d.rs_stats, st.size() * sizeof(ResignBoardStats), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
+    std::vector<ResignBoardStats> st;
+    if (const int rc = fetch_board_stats(e, (hipStream_t)stream, e->d.rs_stats, st)) return rc;
     memset(out, 0, sizeof *out);
     for (const ResignBoardStats &b : st) {
         out->resigned_games += (int64_t)b.resigned;
@@ -721,10 +728,8 @@ int ccz_get_exploration_stats(ccz_engine *e, void *stream, ccz_exploration_stats
 {
     NEED(e);
     if (!out) return fail(-1, "ccz_get_exploration_stats: null output");
-    hipStream_t s = (hipStream_t)stream;
-    std::vector<ExploreBoardStats> st((size_t)e->d.B);
-    HIP_TRY(hipMemcpyAsync(st.data(), e->d.ex_stats, st.size() * sizeof(ExploreBoardStats), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
+    std::vector<ExploreBoardStats> st;
+    if (const int rc = fetch_board_stats(e, (hipStream_t)stream, e->d.ex_stats, st)) return rc;
     memset(out, 0, sizeof *out);
     for (const ExploreBoardStats &b : st) {
         out->explored_moves += (int64_t)b.explored;
@@ -831,11 +836,13 @@ int ccz_principal_variations(ccz_engine *e, void *stream, int32_t multipv, int32
     return 0;
 }
 
-static int check_temps(const double *temps_host, int B, const char *fn)
+// per-board temperatures of the caller `fn`, checked and copied to st_temps: *temps is the device pointer, null without temperatures
+static int stage_temps(ccz_engine *e, hipStream_t s, const double *temps_host, const char *fn, const double **temps)
 {
-    if (temps_host)
-        for (int b = 0; b < B; ++b)
-            if (!(temps_host[b] > 0.0)) return fail(-1, "%s: temps[%d] = %g must be > 0", fn, b, temps_host[b]);
+    for (int b = 0; temps_host && b < e->d.B; ++b)
+        if (!(temps_host[b] > 0.0)) return fail(-1, "%s: temps[%d] = %g must be > 0", fn, b, temps_host[b]);
+    if (temps_host) HIP_TRY(hipMemcpyAsync(e->st_temps, temps_host, (size_t)e->d.B * 8, hipMemcpyHostToDevice, s));
+    *temps = temps_host ? e->st_temps : nullptr;
     return 0;
 }
 
@@ -846,17 +853,13 @@ int ccz_move_distribution(ccz_engine *e, void *stream, const double *temps_host,
     if (!gamma_host || !mixed_host || !u_host) return fail(-1, "ccz_move_distribution: null output");
     hipStream_t s = (hipStream_t)stream;
     const size_t B = (size_t)e->d.B;
-    if (check_temps(temps_host, (int)B, "ccz_move_distribution")) return -1;
+    const double *temps;
+    if (const int rc = stage_temps(e, s, temps_host, "ccz_move_distribution", &temps)) return rc;
     if (!e->st_g) {
         HIP_TRY(hipMalloc(&e->st_g, B * kMaxLegal * 8));
         e->owned.push_back(e->st_g);
         HIP_TRY(hipMalloc(&e->st_u, B * 8));
         e->owned.push_back(e->st_u);
-    }
-    const double *temps = nullptr;
-    if (temps_host) {
-        HIP_TRY(hipMemcpyAsync(e->st_temps, temps_host, B * 8, hipMemcpyHostToDevice, s));
-        temps = e->st_temps;
     }
     // boards past ACTIVE (scout slots) are not sampled by ccz_finish_move either: zero rows, u = NaN
     HIP_TRY(hipMemsetAsync(e->st_g, 0, B * kMaxLegal * 8, s));
@@ -877,12 +880,8 @@ int ccz_root_pi(ccz_engine *e, void *stream, const double *temps_host, double *p
     if (!pi_host) return fail(-1, "ccz_root_pi: null output");
     hipStream_t s = (hipStream_t)stream;
     const size_t B = (size_t)e->d.B;
-    const double *temps = nullptr;
-    if (check_temps(temps_host, (int)B, "ccz_root_pi")) return -1;
-    if (temps_host) {
-        HIP_TRY(hipMemcpyAsync(e->st_temps, temps_host, B * 8, hipMemcpyHostToDevice, s));
-        temps = e->st_temps;
-    }
+    const double *temps;
+    if (const int rc = stage_temps(e, s, temps_host, "ccz_root_pi", &temps)) return rc;
     hipLaunchKernelGGL(k_root_children, dim3(e->d.B), dim3(64), 0, s, e->d, (int32_t *)nullptr, (uint16_t *)nullptr,
                        (int32_t *)nullptr, (float *)nullptr, (float *)nullptr, (int32_t *)nullptr, temps, e->st_pi);
     HIP_TRY(hipGetLastError());
@@ -971,86 +970,84 @@ int ccz_harvest_rows(ccz_engine *e, void *stream, int64_t *rows_host)
     return 0;
 }
 
+// The finished boards one harvest call takes, in units of `mul` per ply (rows or plies): in index order while they fit the caller's
+// capacity; the rest stay finished and are picked up by the next call (many boards can reach the ply cap in the same move). base[b] =
+// where board b's game starts in the output (-1: not taken). The first game must fit: else -5 with the caller's text `first_fmt`.
+struct HarvestPlan {
+    std::vector<long long> base;
+    std::vector<uint8_t> mask;
+    int64_t total = 0;
+    bool any = false;
+};
+
+static int plan_harvest(ccz_engine *e, hipStream_t s, int mul, int64_t capacity, const char *first_fmt, HarvestPlan &p)
+{
+    const int rc = fetch_meta(e, s);
+    if (rc) return rc;
+    const int B = e->d.B;
+    p.base.assign((size_t)B, -1);
+    p.mask.assign((size_t)B, 0);
+    for (int b = 0; b < B; ++b)
+        if (e->h_meta[b].over && e->h_meta[b].ply > 0) { // (over with no ply: a parked board, ccz_set_positions -- nothing to emit, stays parked)
+            const int64_t add = (int64_t)e->h_meta[b].ply * mul;
+            if (p.total + add > capacity) {
+                if (!p.any) return fail(-5, first_fmt, (long long)add, (long long)capacity);
+                break;
+            }
+            p.base[b] = p.total;
+            p.mask[b] = 1;
+            p.any = true;
+            p.total += add;
+        }
+    return 0;
+}
+
+// a new game on every board the plan took (syncs: st_mask and the plan's arrays are free afterwards)
+static int restart_harvested(ccz_engine *e, hipStream_t s, const HarvestPlan &p)
+{
+    HIP_TRY(hipMemcpyAsync(e->st_mask, p.mask.data(), (size_t)e->d.B, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_reset, dim3(e->d.B), dim3(64), 0, s, e->d, (const uint8_t *)e->st_mask);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));
+    return 0;
+}
+
 int ccz_harvest(ccz_engine *e, void *stream, void *states_f16_dev, float *pi_dev, float *z_dev, int64_t capacity_rows,
                 int64_t *rows_host)
 {
     NEED(e);
     hipStream_t s = (hipStream_t)stream;
-    const int rc = fetch_meta(e, s);
+    HarvestPlan p;
+    const int rc = plan_harvest(e, s, (e->d.flags & CCZ_FLAG_NO_MIRROR) ? 1 : 2, capacity_rows,
+                                "ccz_harvest: the first finished game needs %lld rows, capacity %lld", p);
     if (rc) return rc;
-    const int B = e->d.B;
-    const int mul = (e->d.flags & CCZ_FLAG_NO_MIRROR) ? 1 : 2;
-    std::vector<long long> base((size_t)B, -1);
-    std::vector<uint8_t> mask((size_t)B, 0);
-    int64_t rows = 0;
-    bool any = false;
-    // finished boards are taken in index order while their rows fit the caller's buffers; the rest stay
-    // finished and are picked up by the next call (many boards can reach the ply cap in the same move)
-    for (int b = 0; b < B; ++b)
-        if (e->h_meta[b].over && e->h_meta[b].ply > 0) { // (over with no ply: a parked board, ccz_set_positions -- nothing to emit, stays parked)
-            const int64_t add = (int64_t)e->h_meta[b].ply * mul;
-            if (rows + add > capacity_rows) {
-                if (!any) return fail(-5, "ccz_harvest: the first finished game needs %lld rows, capacity %lld", (long long)add, (long long)capacity_rows);
-                break;
-            }
-            base[b] = rows;
-            mask[b] = 1;
-            any = true;
-            rows += add;
-        }
-    if (rows_host) *rows_host = rows;
-    if (!any) return 0;
-    if (rows > 0 && (!states_f16_dev || !pi_dev || !z_dev)) return fail(-1, "ccz_harvest: null output buffer");
-    if (rows > 0) {
-        HIP_TRY(hipMemcpyAsync(e->st_rowbase, base.data(), (size_t)B * 8, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_harvest, dim3(B, kHarvestSlices), dim3(256), 0, s, e->d, (const long long *)e->st_rowbase,
+    if (rows_host) *rows_host = p.total;
+    if (!p.any) return 0;
+    if (p.total > 0) {
+        if (!states_f16_dev || !pi_dev || !z_dev) return fail(-1, "ccz_harvest: null output buffer");
+        HIP_TRY(hipMemcpyAsync(e->st_rowbase, p.base.data(), (size_t)e->d.B * 8, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_harvest, dim3(e->d.B, kHarvestSlices), dim3(256), 0, s, e->d, (const long long *)e->st_rowbase,
                            (uint16_t *)states_f16_dev, pi_dev, z_dev);
         HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(hipMemcpyAsync(e->st_mask, mask.data(), (size_t)B, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_reset, dim3(B), dim3(64), 0, s, e->d, (const uint8_t *)e->st_mask);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(s));
-    return 0;
+    return restart_harvested(e, s, p);
 }
 
 int ccz_harvest_records(ccz_engine *e, void *stream, void *records_dev, int64_t capacity_plies, int64_t *plies_host)
 {
     NEED(e);
     hipStream_t s = (hipStream_t)stream;
-    const int rc = fetch_meta(e, s);
-    if (rc) return rc;
-    const int B = e->d.B;
-    std::vector<long long> base((size_t)B, -1);
-    std::vector<uint8_t> mask((size_t)B, 0);
-    int64_t plies = 0;
-    bool any = false;
-    // as ccz_harvest: finished boards in index order while their plies fit; the rest stay finished for the next call
-    for (int b = 0; b < B; ++b)
-        if (e->h_meta[b].over && e->h_meta[b].ply > 0) { // (a parked board stays parked)
-            const int64_t add = (int64_t)e->h_meta[b].ply;
-            if (plies + add > capacity_plies) {
-                if (!any) return fail(-5, "ccz_harvest_records: the first finished game has %lld plies, capacity %lld", (long long)add, (long long)capacity_plies);
-                break;
-            }
-            base[b] = plies;
-            mask[b] = 1;
-            any = true;
-            plies += add;
-        }
-    if (plies_host) *plies_host = plies;
-    if (!any) return 0;
-    if (plies > 0 && !records_dev) return fail(-1, "ccz_harvest_records: null output buffer");
-    if (plies > 0) {
-        HIP_TRY(hipMemcpyAsync(e->st_rowbase, base.data(), (size_t)B * 8, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_harvest_records, dim3(B, kHarvestSlices), dim3(256), 0, s, e->d, (const long long *)e->st_rowbase, (uint8_t *)records_dev);
+    HarvestPlan p;
+    if (const int rc = plan_harvest(e, s, 1, capacity_plies, "ccz_harvest_records: the first finished game has %lld plies, capacity %lld", p)) return rc;
+    if (plies_host) *plies_host = p.total;
+    if (!p.any) return 0;
+    if (p.total > 0) {
+        if (!records_dev) return fail(-1, "ccz_harvest_records: null output buffer");
+        HIP_TRY(hipMemcpyAsync(e->st_rowbase, p.base.data(), (size_t)e->d.B * 8, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_harvest_records, dim3(e->d.B, kHarvestSlices), dim3(256), 0, s, e->d, (const long long *)e->st_rowbase, (uint8_t *)records_dev);
         HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(hipMemcpyAsync(e->st_mask, mask.data(), (size_t)B, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_reset, dim3(B), dim3(64), 0, s, e->d, (const uint8_t *)e->st_mask);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(s));
-    return 0;
+    return restart_harvested(e, s, p);
 }
 
 // plane_of_type_host (as ccz_config.plane_of_type, NULL or all zero = the reference's order) -> typepack of the record kernels

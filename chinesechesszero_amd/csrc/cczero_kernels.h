@@ -1313,6 +1313,36 @@ __device__ __forceinline__ double board_temp(const Dev &D, const BoardMeta &m, c
     return (m.ply + 1) <= 30 ? D.temp : (half > 0.1 ? half : 0.1);
 }
 
+// ------------------------------------------------------------------ the move boundary: phases with one definition each
+// What k_root_children, k_move_distribution, k_finish_move and k_set_positions are made of. Every phase
+// works on the calling kernel's LDS arrays (it declares none), is called by all 64 lanes and returns wave-uniform results by value.
+// the board's tree in the current pool half: node arrays and root record. The child count as stored is root_k(); what a count above
+// kMaxLegal means is the caller's policy (k_root_children clamps, k_move_distribution reports nothing, k_finish_move raises error 16).
+struct RootView { const NodeA *A; const uint32_t *Bn; NodeA root; int half; };
+
+__device__ __forceinline__ RootView root_view(const Dev &D, int b)
+{
+    const int half = *D.half;
+    const size_t base = ((size_t)b * 2 + half) * (size_t)D.cap;
+    return RootView{D.nodeA + base, D.nodeB + base, D.nodeA[base], half};
+}
+__device__ __forceinline__ int root_k(const RootView &rv) { return (int)(rv.Bn[0] >> 16); }
+
+// What the policy target and the drawn move are formed from: s_vis[k] (the counts as searched) -> s_pi[k]. A policy-target move
+// searched with root exploration (ccz_set_root_exploration; off: one word read) takes pi from the pruned counts s_vp and is drawn
+// from it without Dirichlet mixing: that is the `explored` returned, and the caller's sample_move gets mix = !explored. count: the
+// board's exploration counters move (k_finish_move) or not (k_move_distribution). s_q / s_pn / s_g: scratch of explore_targets.
+__device__ __forceinline__ bool move_target_pi(const Dev &D, int b, int lane, const RootView &rv, int k, uint32_t move_counter, int target,
+                                               double temp, const int32_t *s_vis, int32_t *s_vp, float *s_q, float *s_pn, double *s_g,
+                                               double *s_pi, bool count)
+{
+    const ExploreCfg xc = *D.ex_cfg;
+    const bool explored = xc.enabled && target && k > 0;
+    if (explored) explore_targets(D, xc, b, lane, k, move_counter, rv.root, rv.A + rv.root.fc, s_vis, s_vp, s_q, s_pn, s_g, count);
+    if (k > 0) root_pi(explored ? s_vp : s_vis, s_pi, k, temp, lane);
+    return explored;
+}
+
 __global__ __launch_bounds__(64) void k_root_children(Dev D, int32_t *k_out, uint16_t *acts, int32_t *visits,
                                                         float *q, float *prior, int32_t *root_visits,
                                                         const double *temps, double *pi_out)
@@ -1321,20 +1351,16 @@ __global__ __launch_bounds__(64) void k_root_children(Dev D, int32_t *k_out, uin
     __shared__ int32_t s_vis[kMaxLegal];
     __shared__ double s_pi[kMaxLegal];
     const BoardMeta m = D.meta[b];
-    const size_t base = ((size_t)b * 2 + *D.half) * (size_t)D.cap;
-    const NodeA *A = D.nodeA + base;
-    const uint32_t *Bn = D.nodeB + base;
-    const NodeA root = A[0];
-    int k = (int)(Bn[0] >> 16);
-    if (k > kMaxLegal) k = kMaxLegal;
+    const RootView rv = root_view(D, b);
+    int k = root_k(rv) > kMaxLegal ? kMaxLegal : root_k(rv);
     if (lane == 0) {
         if (k_out) k_out[b] = k;
-        if (root_visits) root_visits[b] = root.N;
+        if (root_visits) root_visits[b] = rv.root.N;
     }
     for (int i = lane; i < kMaxLegal; i += 64) {
         NodeA c = NodeA{0, 0.0f, 0.0f, -1};
         uint32_t w = 0;
-        if (i < k) { c = A[root.fc + i]; w = Bn[root.fc + i]; }
+        if (i < k) { c = rv.A[rv.root.fc + i]; w = rv.Bn[rv.root.fc + i]; }
         s_vis[i] = c.N;
         const size_t o = (size_t)b * kMaxLegal + i;
         if (acts) acts[o] = (uint16_t)(w & 0xffffu);
@@ -1352,8 +1378,9 @@ __global__ __launch_bounds__(64) void k_root_children(Dev D, int32_t *k_out, uin
 }
 
 // ------------------------------------------------------------------ what the next unforced k_finish_move samples from
-// Read-only (moves nothing, records nothing): the same root_pi and sample_move on the same Philox counters as k_finish_move.
-// g_out / mixed_out float64 [B][128] (the raw Gamma draws, (1-eps) pi + eps Dirichlet), u_out float64 [B] (the choice uniform).
+// Read-only (moves nothing, records nothing): move_target_pi and sample_move as k_finish_move calls them, on the same Philox counters.
+// g_out / mixed_out float64 [B][128] (the raw Gamma draws, (1-eps) pi + eps Dirichlet; a move searched with root exploration: the
+// draws as they would have been, mixed == pi of the pruned counts), u_out float64 [B] (the choice uniform).
 // A board k_finish_move would not sample on (game over, no children, bad temperature) gets zero rows and u = NaN.
 __global__ __launch_bounds__(64) void k_move_distribution(Dev D, const double *temps, double *g_out, double *mixed_out, double *u_out)
 {
@@ -1365,23 +1392,16 @@ __global__ __launch_bounds__(64) void k_move_distribution(Dev D, const double *t
     __shared__ float s_q[kMaxLegal], s_pn[kMaxLegal];
     __shared__ int s_choice;
     const BoardMeta m = D.meta[b];
-    const size_t base = ((size_t)b * 2 + *D.half) * (size_t)D.cap;
-    const NodeA *A = D.nodeA + base;
-    const uint32_t *Bn = D.nodeB + base;
-    const NodeA root = A[0];
-    int k = (int)(Bn[0] >> 16);
+    const RootView rv = root_view(D, b);
+    int k = root_k(rv);
     const double temp = board_temp(D, m, temps, b);
     if (m.over || k > kMaxLegal || bad_temp(temp)) k = 0;
     double *g = g_out + (size_t)b * kMaxLegal, *mixed = mixed_out + (size_t)b * kMaxLegal;
     for (int i = lane; i < kMaxLegal; i += 64) if (i >= k) { g[i] = 0.0; mixed[i] = 0.0; }
     if (k == 0) { if (lane == 0) u_out[b] = __builtin_nan(""); return; }
-    for (int i = lane; i < k; i += 64) s_vis[i] = A[CCZ_IDX(D, root.fc + i, D.cap)].N;
+    for (int i = lane; i < k; i += 64) s_vis[i] = rv.A[CCZ_IDX(D, rv.root.fc + i, D.cap)].N;
     __syncthreads();
-    // a move searched with root exploration: pi of the pruned counts, no mixing (mixed == pi), the Gamma draws as they would have been
-    const ExploreCfg xc = *D.ex_cfg;
-    const bool explored = xc.enabled && D.target[b];
-    if (explored) explore_targets(D, xc, b, lane, k, m.move_counter, root, A + root.fc, s_vis, s_vp, s_q, s_pn, s_g, false);
-    root_pi(explored ? s_vp : s_vis, s_pi, k, temp, lane);
+    const bool explored = move_target_pi(D, b, lane, rv, k, m.move_counter, D.target[b], temp, s_vis, s_vp, s_q, s_pn, s_g, s_pi, false);
     sample_move(D, D.board_id_base + (uint64_t)b, m.move_counter, s_pi, s_g, k, lane, &s_choice, g, mixed, u_out + b, !explored);
 }
 
@@ -1390,7 +1410,7 @@ __global__ __launch_bounds__(64) void k_move_distribution(Dev D, const double *t
 // other side's did not loses. Only outcome().winner changes (game.py:210-216): in the search the same leaf is
 // "end and is_tie" -> 0.0 either way (mcts.py:120-122), so visit counts do not depend on this flag.
 // Returns the winner (1 RED / 0 BLACK) or -1. `turn` = the side to move in the position the chain ends with, chk0 / chk1 = the
-// chain's in-check bits including that position's. Shared by k_finish_move and k_set_positions. All 64 lanes call it.
+// chain's in-check bits including that position's. Called by root_game_end. All 64 lanes call it.
 __device__ __forceinline__ int perpetual_check_winner(uint32_t rule_flags, const LeafEval &L, int halfmove, int chain_len, uint64_t chk0,
                                                       uint64_t chk1, int turn, int lane)
 {
@@ -1417,6 +1437,57 @@ __device__ __forceinline__ int perpetual_check_winner(uint32_t rule_flags, const
     return perpetual_winner;
 }
 
+// ------------------------------------------------------------------ a move on the root (k_finish_move, k_set_positions)
+// What it changes besides the squares: key, side to move, sixty-move clock, length of the history chain (the keys
+// since the last zeroing move: s_chain) and the chain's in-check bits: the side to move stands in check at that chain position.
+struct RootState { uint64_t key; int turn, halfmove, chain_len; uint64_t chk0, chk1; };
+
+// board.push(move) on the root (game.py:201) and its history: squares, key, clock, and the chain -- restarted, with its check bits,
+// by a zeroing move --, then the new key appended. True: the chain was full, its last key is overwritten and the caller reports it
+// (k_finish_move: sticky bit 64, k_set_positions: status -2). sync(): the caller's own barrier, before and after lane 0's writes.
+template <typename Sync>
+__device__ __forceinline__ bool push_root_move(const Dev &D, int mv, uint8_t *s_sq, uint64_t *s_chain, RootState &st, int lane, Sync sync)
+{
+    const int from = c_tab.from[mv], to = c_tab.to[mv];
+    const int pc = s_sq[from], cap = s_sq[to];
+    sync();
+    if (lane == 0) { s_sq[to] = (uint8_t)pc; s_sq[from] = 0; }
+    st.key ^= zob(pc, from) ^ zob(pc, to) ^ kTurnKey;
+    if (cap) st.key ^= zob(cap, to);
+    st.turn ^= 1;
+    const bool zeroing = cap || ((D.rule_flags & 2u) && (pc & 7) == PAWN); // CCZ_RULE_PAWN_MOVE_RESETS_CLOCK
+    st.halfmove = zeroing ? 0 : st.halfmove + 1;
+    if (zeroing) { st.chain_len = 0; st.chk0 = 0ull; st.chk1 = 0ull; }
+    const bool full = st.chain_len >= kChainCap;
+    if (full) st.chain_len = kChainCap - 1;
+    if (lane == 0) s_chain[CCZ_IDX(D, st.chain_len, kChainCap)] = st.key;
+    ++st.chain_len;
+    sync();
+    return full;
+}
+
+// the in-check bit of the chain's last position (st.turn to move there, its king on ksq)
+__device__ __forceinline__ void mark_check(const uint8_t *s_sq, GenScratch &S, int ksq, RootState &st)
+{
+    const bool in_check = ksq >= 0 && king_attacked(s_sq, S, ksq, -1, -1, 0, st.turn);
+    const int ci = st.chain_len - 1;
+    if (in_check) { if (ci < 64) st.chk0 |= 1ull << ci; else st.chk1 |= 1ull << (ci - 64); }
+}
+
+// game end (game.py:208-219) of the position a push reached: is_game_over() or is_tie(); winner from outcome() (1 RED / 0 BLACK /
+// -1: a draw, or not over); overflow: the move generator's lists overflowed. Marks the position's check bit in st.
+struct GameEnd { bool over; int winner; bool overflow; };
+__device__ __forceinline__ GameEnd root_game_end(uint32_t rule_flags, const uint8_t *s_sq, const uint64_t *s_chain, GenScratch &S, RootState &st, int lane)
+{
+    GameEnd e;
+    const LeafEval L = eval_position(s_sq, st.turn, st.halfmove, st.key, s_chain, st.chain_len, S, nullptr, lane, e.overflow);
+    mark_check(s_sq, S, L.ksq, st);
+    const int pw = perpetual_check_winner(rule_flags, L, st.halfmove, st.chain_len, st.chk0, st.chk1, st.turn, lane);
+    e.over = L.status != CCZ_LEAF_EXPAND;
+    e.winner = !e.over ? -1 : L.n_legal == 0 ? (st.turn ^ 1) : pw; // no legal move: side to move loses
+    return e;
+}
+
 // ------------------------------------------------------------------ K3: once per move
 __global__ __launch_bounds__(64) void k_finish_move(Dev D, const int32_t *forced, const double *temps,
                                                       int32_t *moves_out, int keep_tree)
@@ -1434,37 +1505,30 @@ __global__ __launch_bounds__(64) void k_finish_move(Dev D, const int32_t *forced
     __shared__ float s_q[kMaxLegal], s_pn[kMaxLegal];
     __shared__ int s_choice;
 
+    // ---- guards
     BoardMeta m = D.meta[b];
     if (moves_out && lane == 0) moves_out[b] = -1;
     if (m.over) return;
     if (lane == 0) D.move_sims[b] = 0; // a move boundary for every live board, whether or not it moves below
-    const int oh = *D.half, nh = oh ^ 1; // every board moves to the other pool half (the host flips the word afterwards)
-    const size_t baseOld = ((size_t)b * 2 + oh) * (size_t)D.cap;
-    {   // whatever happens below, the new half holds a valid (empty) tree for this board
-        const size_t bn = ((size_t)b * 2 + nh) * (size_t)D.cap;
-        if (lane == 0) { D.nodeA[bn] = NodeA{0, 0.0f, 1.0f, -1}; D.nodeB[bn] = 0u; }
-    }
-    const NodeA *A = D.nodeA + baseOld;
-    const uint32_t *Bn = D.nodeB + baseOld;
-    const NodeA root = A[0];
-    int k = (int)(Bn[0] >> 16);
+    const RootView rv = root_view(D, b);
+    const int k = root_k(rv), nh = rv.half ^ 1; // every board moves to the other pool half (the host flips the word afterwards)
+    const size_t baseNew = ((size_t)b * 2 + nh) * (size_t)D.cap;
+    if (lane == 0) { D.nodeA[baseNew] = NodeA{0, 0.0f, 1.0f, -1}; D.nodeB[baseNew] = 0u; } // whatever happens below, the new half holds a valid (empty) tree
     const int want = forced ? forced[b] : -1;
-    if (k > kMaxLegal) { if (lane == 0) set_err(D, 16); return; }
-    if (k == 0 && want < 0) { if (lane == 0) set_err(D, 16); return; } // nothing searched, nothing to sample from
-    if (want >= kNMoves) { if (lane == 0) set_err(D, 16); return; }
+    // (k == 0 and no forced move: nothing searched, nothing to sample from)
+    if (k > kMaxLegal || (k == 0 && want < 0) || want >= kNMoves) { if (lane == 0) set_err(D, 16); return; }
     const double temp = board_temp(D, m, temps, b);
     if (bad_temp(temp)) { if (lane == 0) set_err(D, CCZ_ERR_BAD_TEMP); return; }
 
     load_board(s_sq, D.root_sq + (size_t)b * 96, lane);
     for (int i = lane; i < k; i += 64) {
-        s_vis[i] = A[CCZ_IDX(D, root.fc + i, D.cap)].N;
-        s_act[i] = (uint16_t)(Bn[CCZ_IDX(D, root.fc + i, D.cap)] & 0xffffu);
+        s_vis[i] = rv.A[CCZ_IDX(D, rv.root.fc + i, D.cap)].N;
+        s_act[i] = (uint16_t)(rv.Bn[CCZ_IDX(D, rv.root.fc + i, D.cap)] & 0xffffu);
     }
     __syncthreads();
 
-    // ---- pi (mcts.py:162-166) and the training record (game.py:195-198)
+    // ---- the documented caps: the game is adjudicated a draw, its records so far stay valid
     if (m.ply >= D.max_plies || m.pi_used + (uint32_t)k > (uint32_t)D.pi_cap) {
-        // documented cap: the game is adjudicated a draw, its records so far stay valid
         if (lane == 0) {
             if (m.ply < D.max_plies) set_err(D, 8);
             else if (D.flags & CCZ_FLAG_STRICT) set_err(D, CCZ_ERR_TRUNCATED); // the reference's game has no ply cap (game.py:155)
@@ -1477,32 +1541,30 @@ __global__ __launch_bounds__(64) void k_finish_move(Dev D, const int32_t *forced
         }
         return;
     }
-    const ResignCfg rc = *D.rs_cfg;
+
+    // ---- pi (mcts.py:162-166) and the training record. The resignation value below, ccz_root_children and the lines read the
+    // counts as searched (s_vis), whatever pi is formed from.
     const int tgt = D.target[b];
-    // root exploration (ccz_set_root_exploration; off: one word read): pi is formed from the pruned counts, the move drawn from it
-    // without Dirichlet mixing. The resignation value below, ccz_root_children and the lines read the counts as searched (s_vis).
-    const ExploreCfg xc = *D.ex_cfg;
-    const bool explored = xc.enabled && tgt && k > 0;
-    if (explored) explore_targets(D, xc, b, lane, k, m.move_counter, root, A + root.fc, s_vis, s_vp, s_q, s_pn, s_g, true);
-    if (k > 0) root_pi(explored ? s_vp : s_vis, s_pi, k, temp, lane);
-    {
-        const size_t r = (size_t)b * D.max_plies + CCZ_IDX(D, m.ply, D.max_plies);
-        if (lane < 24) ((uint32_t *)(D.rec_sq + r * 96))[lane] = ((const uint32_t *)s_sq)[lane];
-        if (lane == 0) { D.rec_turn[r] = m.turn; D.rec_k[r] = (uint8_t)k; D.rec_off[r] = m.pi_used; D.rec_target[r] = (uint8_t)tgt; D.rec_hasv[r] = 0; }
-        const size_t po = (size_t)b * D.pi_cap + m.pi_used;
-        for (int i = lane; i < k; i += 64) {
-            const size_t o = (size_t)b * D.pi_cap + CCZ_IDX(D, m.pi_used + (uint32_t)i, D.pi_cap);
-            D.rec_ids[o] = s_act[i];
-            D.rec_pi[o] = (float)s_pi[i];
-        }
-        (void)po;
+    const bool explored = move_target_pi(D, b, lane, rv, k, m.move_counter, tgt, temp, s_vis, s_vp, s_q, s_pn, s_g, s_pi, true);
+    const size_t r = (size_t)b * D.max_plies + CCZ_IDX(D, m.ply, D.max_plies);
+    if (lane < 24) ((uint32_t *)(D.rec_sq + r * 96))[lane] = ((const uint32_t *)s_sq)[lane];
+    if (lane == 0) { D.rec_turn[r] = m.turn; D.rec_k[r] = (uint8_t)k; D.rec_off[r] = m.pi_used; D.rec_target[r] = (uint8_t)tgt; D.rec_hasv[r] = 0; }
+    for (int i = lane; i < k; i += 64) {
+        const size_t o = (size_t)b * D.pi_cap + CCZ_IDX(D, m.pi_used + (uint32_t)i, D.pi_cap);
+        D.rec_ids[o] = s_act[i];
+        D.rec_pi[o] = (float)s_pi[i];
     }
 
-    // ---- resignation (ccz_set_resign; off: one word read above, nothing below runs). The root value is the visit-weighted mean of
-    // the children's Q as stored (the view of the root's side to move), summed in child order in float64: every lane runs the same
-    // <= 128 terms on the same LDS words, so the decision is wave-uniform without a broadcast. s_g is free until sample_move.
+    // A ply is played by a move or by resigning: the record took k entries, the board's Philox move counter advances, and the board's
+    // tree (n_nodes nodes) lies in the other pool half
+    const auto ply_played = [&](int n_nodes) { m.ply += 1; m.move_counter += 1; m.n_nodes = n_nodes; m.half = (uint8_t)nh; m.pi_used += (uint32_t)k; };
+
+    // ---- resignation (ccz_set_resign; off: one word read, nothing below runs). The root value is the visit-weighted mean of the
+    // children's Q as stored (the view of the root's side to move), summed in child order in float64: every lane runs the same <= 128
+    // terms on the same LDS words, so the decision is wave-uniform without a broadcast. s_g is free until sample_move.
+    const ResignCfg rc = *D.rs_cfg;
     if (rc.enabled) {
-        for (int i = lane; i < k; i += 64) s_g[i] = (double)A[CCZ_IDX(D, root.fc + i, D.cap)].Q;
+        for (int i = lane; i < k; i += 64) s_g[i] = (double)rv.A[CCZ_IDX(D, rv.root.fc + i, D.cap)].Q;
         __syncthreads();
         double acc = 0.0;
         long long nsum = 0;
@@ -1522,7 +1584,6 @@ __global__ __launch_bounds__(64) void k_finish_move(Dev D, const int32_t *forced
         }
         __syncthreads(); // s_g is read above by every lane before sample_move writes it
         if (lane == 0) {
-            const size_t r = (size_t)b * D.max_plies + CCZ_IDX(D, m.ply, D.max_plies);
             D.rec_value[r] = (float)v;
             D.rec_hasv[r] = 1;
             D.rs_last[b] = (float)v;
@@ -1535,11 +1596,7 @@ __global__ __launch_bounds__(64) void k_finish_move(Dev D, const int32_t *forced
             if (lane == 0) {
                 D.rs_state[b] = (uint8_t)(kResigned | s);
                 D.rs_fire[b] = m.ply;
-                m.ply += 1;
-                m.move_counter += 1;
-                m.n_nodes = 1;
-                m.half = (uint8_t)nh;
-                m.pi_used += (uint32_t)k;
+                ply_played(1);
                 m.over = 1;
                 m.winner = (int8_t)(s ^ 1);
                 D.meta[b] = m;
@@ -1567,23 +1624,21 @@ __global__ __launch_bounds__(64) void k_finish_move(Dev D, const int32_t *forced
         if (found < 0 && s_sq[c_tab.from[want]] == 0) { if (lane == 0) set_err(D, 16); return; }
         if (lane == 0) s_choice = found;
     } else {
-        const uint64_t gid = D.board_id_base + (uint64_t)b;
-        sample_move(D, gid, m.move_counter, s_pi, s_g, k, lane, &s_choice, nullptr, nullptr, nullptr, !explored);
+        sample_move(D, D.board_id_base + (uint64_t)b, m.move_counter, s_pi, s_g, k, lane, &s_choice, nullptr, nullptr, nullptr, !explored);
     }
     __syncthreads();
     const int ci = s_choice;
     const int mv = ci >= 0 ? (int)s_act[ci] : want;
-    if (ci < 0) keep_tree = 0;
     if (moves_out && lane == 0) moves_out[b] = mv;
 
-    // ---- MCTS.update_with_move (mcts.py:168-178): re-root on the chosen child, subtree copied
-    // breadth-first into the other pool half (children of a node stay contiguous)
-    const size_t baseNew = ((size_t)b * 2 + nh) * (size_t)D.cap;
+    // ---- MCTS.update_with_move (mcts.py:168-178): re-root on the chosen child, subtree copied breadth-first into the other pool
+    // half (children of a node stay contiguous); a forced move that is no child of the root, or !keep_tree: a fresh root
     NodeA *NA = D.nodeA + baseNew;
     uint32_t *NB = D.nodeB + baseNew;
     int n_new = 1;
+    if (ci < 0) keep_tree = 0;
     if (keep_tree) {
-        if (lane == 0) { NA[0] = A[CCZ_IDX(D, root.fc + ci, D.cap)]; NB[0] = Bn[CCZ_IDX(D, root.fc + ci, D.cap)]; }
+        if (lane == 0) { NA[0] = rv.A[CCZ_IDX(D, rv.root.fc + ci, D.cap)]; NB[0] = rv.Bn[CCZ_IDX(D, rv.root.fc + ci, D.cap)]; }
         __syncthreads();
         int head = 0, pruned = 0;
         // The kept subtree may use the pool up to `budget`, leaving room for a whole move of new expansions.
@@ -1599,13 +1654,13 @@ __global__ __launch_bounds__(64) void k_finish_move(Dev D, const int32_t *forced
             int nc = 0;
             if (valid) { rec = NA[CCZ_IDX(D, i, D.cap)]; nc = (int)(NB[CCZ_IDX(D, i, D.cap)] >> 16); }
             const int incl = wave_incl_scan(nc, lane);
-            const bool keep = nc > 0 && n_new + incl <= budget;   // a prefix of the lanes: incl is non-decreasing
-            const bool drop = nc > 0 && !keep;
-            const uint64_t km = __ballot(keep);
+            const bool keep_kids = nc > 0 && n_new + incl <= budget;   // a prefix of the lanes: incl is non-decreasing
+            const bool drop = nc > 0 && !keep_kids;
+            const uint64_t km = __ballot(keep_kids);
             const int total = km ? __builtin_amdgcn_readlane(incl, __builtin_amdgcn_readfirstlane(63 - __builtin_clzll(km))) : 0;
             const int dst = n_new + incl - nc;
-            s_cnt[lane] = keep ? nc : 0;
-            if (keep) { s_src[lane] = rec.fc; s_dst[lane] = dst; NA[i].fc = dst; }
+            s_cnt[lane] = keep_kids ? nc : 0;
+            if (keep_kids) { s_src[lane] = rec.fc; s_dst[lane] = dst; NA[i].fc = dst; }
             if (drop) { NA[i].fc = -1; NB[i] = NB[i] & 0xffffu; }
             pruned += __popcll(__ballot(drop));
             __syncthreads();
@@ -1615,8 +1670,8 @@ __global__ __launch_bounds__(64) void k_finish_move(Dev D, const int32_t *forced
                 todo &= todo - 1;
                 const int src = s_src[L], dd = s_dst[L], cn = s_cnt[L];
                 for (int j = lane; j < cn; j += 64) {
-                    NA[CCZ_IDX(D, dd + j, D.cap)] = A[CCZ_IDX(D, src + j, D.cap)];
-                    NB[CCZ_IDX(D, dd + j, D.cap)] = Bn[CCZ_IDX(D, src + j, D.cap)];
+                    NA[CCZ_IDX(D, dd + j, D.cap)] = rv.A[CCZ_IDX(D, src + j, D.cap)];
+                    NB[CCZ_IDX(D, dd + j, D.cap)] = rv.Bn[CCZ_IDX(D, src + j, D.cap)];
                 }
             }
             const int nbatch = n_new - head < 64 ? n_new - head : 64;
@@ -1634,54 +1689,30 @@ __global__ __launch_bounds__(64) void k_finish_move(Dev D, const int32_t *forced
         n_new = 1;
     }
 
-    // ---- board.push(move) on the root (game.py:201) and its history
-    const int from = c_tab.from[mv], to = c_tab.to[mv];
-    const int pc = s_sq[from], cap = s_sq[to];
-    __syncthreads();
-    if (lane == 0) { s_sq[to] = (uint8_t)pc; s_sq[from] = 0; }
-    uint64_t key = m.key ^ zob(pc, from) ^ zob(pc, to) ^ kTurnKey;
-    if (cap) key ^= zob(cap, to);
-    const int turn = m.turn ^ 1;
-    const bool zeroing = cap || ((D.rule_flags & 2u) && (pc & 7) == PAWN); // CCZ_RULE_PAWN_MOVE_RESETS_CLOCK
-    int halfmove = zeroing ? 0 : m.halfmove + 1;
-    int chain_len = zeroing ? 0 : m.chain_len;
-    if (chain_len >= kChainCap) { chain_len = kChainCap - 1; set_err(D, 64); }
-    for (int i = lane; i < chain_len; i += 64) s_chain[i] = D.chain[(size_t)b * kChainCap + i];
-    if (lane == 0) { s_chain[CCZ_IDX(D, chain_len, kChainCap)] = key; D.chain[(size_t)b * kChainCap + CCZ_IDX(D, chain_len, kChainCap)] = key; }
-    ++chain_len;
-    __syncthreads();
+    // ---- push on the root, its history (the chain comes from memory, the new key goes back), game end
+    RootState st = {m.key, m.turn, m.halfmove, m.chain_len, D.chain_chk[(size_t)b * 2], D.chain_chk[(size_t)b * 2 + 1]};
+    for (int i = lane; i < st.chain_len; i += 64) s_chain[i] = D.chain[(size_t)b * kChainCap + i];
+    if (push_root_move(D, mv, s_sq, s_chain, st, lane, [] { __syncthreads(); })) set_err(D, 64);
+    if (lane == 0) D.chain[(size_t)b * kChainCap + CCZ_IDX(D, st.chain_len - 1, kChainCap)] = st.key;
     if (lane < 24) ((uint32_t *)(D.root_sq + (size_t)b * 96))[lane] = ((const uint32_t *)s_sq)[lane];
+    const GameEnd end = root_game_end(D.rule_flags, s_sq, s_chain, S, st, lane);
+    if (end.overflow) set_err(D, 4);
 
-    // ---- game end (game.py:208-219): is_game_over() or is_tie(); winner from outcome()
-    bool overflow;
-    const LeafEval L = eval_position(s_sq, turn, halfmove, key, s_chain, chain_len, S, nullptr, lane, overflow);
-    if (overflow) set_err(D, 4);
-    // one bit per chain position: the side to move stands in check there (the move that led to it gave check)
-    uint64_t chk0 = zeroing ? 0ull : D.chain_chk[(size_t)b * 2], chk1 = zeroing ? 0ull : D.chain_chk[(size_t)b * 2 + 1];
-    {
-        const bool in_check = L.ksq >= 0 && king_attacked(s_sq, S, L.ksq, -1, -1, 0, turn);
-        const int ci = chain_len - 1;
-        if (in_check) { if (ci < 64) chk0 |= 1ull << ci; else chk1 |= 1ull << (ci - 64); }
-    }
-    const int perpetual_winner = perpetual_check_winner(D.rule_flags, L, halfmove, chain_len, chk0, chk1, turn, lane);
+    // ---- commit
     if (lane == 0) {
-        D.chain_chk[(size_t)b * 2] = chk0;
-        D.chain_chk[(size_t)b * 2 + 1] = chk1;
-        m.key = key;
-        m.halfmove = halfmove;
-        m.chain_len = chain_len;
-        m.ply += 1;
-        m.move_counter += 1;
-        m.n_nodes = n_new;
-        m.turn = (uint8_t)turn;
-        m.half = (uint8_t)nh;
-        m.pi_used += (uint32_t)k;
-        BoardStats &st = D.stats[b];
-        st.moves += 1;
-        if (L.status != CCZ_LEAF_EXPAND) {
+        D.chain_chk[(size_t)b * 2] = st.chk0;
+        D.chain_chk[(size_t)b * 2 + 1] = st.chk1;
+        m.key = st.key;
+        m.halfmove = st.halfmove;
+        m.chain_len = st.chain_len;
+        m.turn = (uint8_t)st.turn;
+        ply_played(n_new);
+        BoardStats &bs = D.stats[b];
+        bs.moves += 1;
+        if (end.over) {
             m.over = 1;
-            m.winner = L.n_legal == 0 ? (int8_t)(turn ^ 1) : (int8_t)perpetual_winner; // no legal move: side to move loses
-            st.games += 1;
+            m.winner = (int8_t)end.winner;
+            bs.games += 1;
             const int rstate = D.rs_state[b];
             if (rstate & kPlayOn) playon_count(D, b, rstate, m.winner, m.ply);
         }
@@ -1693,13 +1724,13 @@ __global__ __launch_bounds__(64) void k_finish_move(Dev D, const int32_t *forced
 // ------------------------------------------------------------------ many positions with their move history, in one launch
 // One wave per board (ccz_set_positions): validate the position, replay the board's moves with the engine's own rules -- every
 // move must be in the legal-move set of the position it is played in (gen_legal with the engine's rank table: the generator of the
-// selection) --, keep key, turn, clock, history chain and the chain's in-check bits as k_finish_move does per ply, run
-// k_finish_move's game-end test on the position reached (only if moves were played: without moves the board is left exactly as
-// k_set_position leaves it), and finish as init_board does. status: 0 loaded, 1 + i move i is not legal where it is played, -1
-// invalid position, -2 more than kChainCap positions since the last capture. A board with a non-zero status, or with n_moves == -1,
-// is PARKED: empty mailbox, over = 1, winner = -1, ply = 0, a root without children -- the simulator skips it (m.over), the harvest
-// has nothing to emit for it. Bad input sets no sticky error bit. The replay is a chain of n dependent move generations
-// (~ n x the leaf phase of k_step); the moves are fetched 64 at a time so that no load sits between two of them.
+// selection) and is pushed by push_root_move, the check bit of the position before it set by mark_check --, call root_game_end on
+// the position reached (only if moves were played: without moves the board is left exactly as k_set_position leaves it), and finish
+// as init_board does. status: 0 loaded, 1 + i move i is not legal where it is played, -1 invalid position, -2 more than kChainCap
+// positions since the last zeroing move. A board with a non-zero status, or with n_moves == -1, is PARKED: empty mailbox, over = 1,
+// winner = -1, ply = 0, a root without children -- the simulator skips it (m.over), the harvest has nothing to emit for it. Bad input
+// sets no sticky error bit. The replay is a chain of n dependent move generations (~ n x the leaf phase of k_step); the moves are
+// fetched 64 at a time so that no load sits between two of them.
 __global__ __launch_bounds__(64) void k_set_positions(Dev D, const uint8_t *mask, const uint8_t *sq_in, const uint8_t *turn_in,
                                                         const int32_t *halfmove_in, const int32_t *moves, const int32_t *n_moves,
                                                         int max_moves, int32_t *status_out)
@@ -1710,8 +1741,7 @@ __global__ __launch_bounds__(64) void k_set_positions(Dev D, const uint8_t *mask
     __shared__ uint64_t s_chain[kChainCap];
     __shared__ GenScratch S;
     const int n = n_moves ? n_moves[b] : 0;
-    int turn = turn_in[b] ? 1 : 0;
-    int halfmove = halfmove_in ? halfmove_in[b] : 0;
+    RootState st = {0ull, turn_in[b] ? 1 : 0, halfmove_in ? halfmove_in[b] : 0, 1, 0ull, 0ull};
     const uint8_t *src = sq_in + (size_t)b * 96;
     const int p0 = src[lane], p1 = lane < 26 ? src[64 + lane] : 0;
     const bool park = n == -1;
@@ -1724,92 +1754,63 @@ __global__ __launch_bounds__(64) void k_set_positions(Dev D, const uint8_t *mask
         const int kb = __popcll(__ballot(p0 == KING + 8)) + __popcll(__ballot(p1 == KING + 8));
         const int nr = __popcll(__ballot(p0 >= 1 && p0 <= 7)) + __popcll(__ballot(p1 >= 1 && p1 <= 7));
         const int nb = __popcll(__ballot(p0 >= 9 && p0 <= 15)) + __popcll(__ballot(p1 >= 9 && p1 <= 15));
-        if (__ballot(badcode) != 0ull || kr != 1 || kb != 1 || nr > 16 || nb > 16 || halfmove < 0 || n < -1 || n > max_moves) status = -1;
+        if (__ballot(badcode) != 0ull || kr != 1 || kb != 1 || nr > 16 || nb > 16 || st.halfmove < 0 || n < -1 || n > max_moves) status = -1;
     }
-    uint64_t key = 0, chk0 = 0ull, chk1 = 0ull;
-    int chain_len = 1, over = 0, winner = -1;
+    GameEnd end = {false, -1, false};
     if (!park && status == 0) {
         s_sq[lane] = (uint8_t)p0;
         if (lane < 32) s_sq[64 + lane] = (uint8_t)p1; // (p1 == 0 for lanes 26..31: the mailbox pad)
-        if (p0) key ^= zob(p0, lane);
-        if (p1) key ^= zob(p1, 64 + lane);
+        if (p0) st.key ^= zob(p0, lane);
+        if (p1) st.key ^= zob(p1, 64 + lane);
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) key ^= __shfl_xor(key, o);
-        if (turn) key ^= kTurnKey;
-        if (lane == 0) s_chain[0] = key;
+        for (int o = 32; o > 0; o >>= 1) st.key ^= __shfl_xor(st.key, o);
+        if (st.turn) st.key ^= kTurnKey;
+        if (lane == 0) s_chain[0] = st.key;
         wave_sync();
         const int32_t *row = moves + (size_t)b * (size_t)max_moves;
         int mvreg = -1;
         for (int i = 0; i < n; ++i) {
             if ((i & 63) == 0) mvreg = i + lane < n ? row[i + lane] : -1;
             const int mv = __builtin_amdgcn_readlane(mvreg, __builtin_amdgcn_readfirstlane(i & 63));
-            const GenResult g = gen_legal(s_sq, turn, S, nullptr, lane, nullptr, D.rank, D.unrank, D.trankpack);
+            const GenResult g = gen_legal(s_sq, st.turn, S, nullptr, lane, nullptr, D.rank, D.unrank, D.trankpack);
             if (g.overflow) { status = -1; break; }
-            if (i > 0) { // the move before gave check: one bit per chain position, as k_finish_move keeps them
-                const bool in_check = g.ksq >= 0 && king_attacked(s_sq, S, g.ksq, -1, -1, 0, turn);
-                const int ci = chain_len - 1;
-                if (in_check) { if (ci < 64) chk0 |= 1ull << ci; else chk1 |= 1ull << (ci - 64); }
-            }
+            if (i > 0) mark_check(s_sq, S, g.ksq, st); // the move before gave check
             bool legal = (unsigned)mv < (unsigned)kNMoves;
             if (legal) {
                 const int bit = D.rank ? (int)D.rank[mv] : mv; // bit r of the mask = the move of rank r (gen_legal)
                 legal = ((S.mask[bit >> 5] >> (bit & 31)) & 1u) != 0u;
             }
             if (!legal) { status = 1 + i; break; }
-            // board.push(move) and its history: k_finish_move's, without the tree
-            const int from = c_tab.from[mv], to = c_tab.to[mv];
-            const int pc = s_sq[from], cap = s_sq[to];
-            wave_sync();
-            if (lane == 0) { s_sq[to] = (uint8_t)pc; s_sq[from] = 0; }
-            key ^= zob(pc, from) ^ zob(pc, to) ^ kTurnKey;
-            if (cap) key ^= zob(cap, to);
-            const bool zeroing = cap || ((D.rule_flags & 2u) && (pc & 7) == PAWN); // CCZ_RULE_PAWN_MOVE_RESETS_CLOCK
-            halfmove = zeroing ? 0 : halfmove + 1;
-            if (zeroing) { chain_len = 0; chk0 = 0ull; chk1 = 0ull; }
-            if (chain_len >= kChainCap) { status = -2; break; }
-            if (lane == 0) s_chain[chain_len] = key;
-            ++chain_len;
-            turn ^= 1;
-            wave_sync();
+            if (push_root_move(D, mv, s_sq, s_chain, st, lane, [] { wave_sync(); })) { status = -2; break; }
         }
         if (status == 0 && n > 0) {
-            // game end (game.py:208-219) of the position reached, as after k_finish_move's push
-            bool overflow;
-            const LeafEval L = eval_position(s_sq, turn, halfmove, key, s_chain, chain_len, S, nullptr, lane, overflow);
-            if (overflow) status = -1;
-            const bool in_check = L.ksq >= 0 && king_attacked(s_sq, S, L.ksq, -1, -1, 0, turn);
-            const int ci = chain_len - 1;
-            if (in_check) { if (ci < 64) chk0 |= 1ull << ci; else chk1 |= 1ull << (ci - 64); }
-            const int pw = perpetual_check_winner(D.rule_flags, L, halfmove, chain_len, chk0, chk1, turn, lane);
-            if (L.status != CCZ_LEAF_EXPAND) {
-                over = 1;
-                winner = L.n_legal == 0 ? (turn ^ 1) : pw; // no legal move: side to move loses
-            }
+            end = root_game_end(D.rule_flags, s_sq, s_chain, S, st, lane);
+            if (end.overflow) status = -1;
         }
         wave_sync();
     }
     const bool parked = park || status != 0;
-    if (parked) { key = 0; chain_len = 1; chk0 = 0ull; chk1 = 0ull; over = 1; winner = -1; turn = 1; halfmove = 0; }
+    if (parked) { st = RootState{0ull, 1, 0, 1, 0ull, 0ull}; end.over = true; end.winner = -1; }
     if (lane < 24) ((uint32_t *)(D.root_sq + (size_t)b * 96))[lane] = parked ? 0u : ((const uint32_t *)s_sq)[lane];
     uint64_t *chain = D.chain + (size_t)b * kChainCap;
     if (parked) { if (lane == 0) chain[0] = 0ull; }
-    else for (int i = lane; i < chain_len; i += 64) chain[i] = s_chain[i];
+    else for (int i = lane; i < st.chain_len; i += 64) chain[i] = s_chain[i];
     if (lane == 0) {
         BoardMeta m = D.meta[b];
-        m.key = key;
-        m.halfmove = halfmove;
-        m.chain_len = chain_len;
+        m.key = st.key;
+        m.halfmove = st.halfmove;
+        m.chain_len = st.chain_len;
         m.ply = 0;
         m.n_nodes = 1;
-        m.turn = (uint8_t)turn;
-        m.over = (uint8_t)over;
-        m.winner = (int8_t)winner;
+        m.turn = (uint8_t)st.turn;
+        m.over = (uint8_t)end.over;
+        m.winner = (int8_t)end.winner;
         m.pi_used = 0;
         m.game_no += 1;
         m.half = (uint8_t)*D.half;
         D.meta[b] = m;
-        D.chain_chk[(size_t)b * 2] = chk0;
-        D.chain_chk[(size_t)b * 2 + 1] = chk1;
+        D.chain_chk[(size_t)b * 2] = st.chk0;
+        D.chain_chk[(size_t)b * 2 + 1] = st.chk1;
         fresh_root(D, b, m.half);
         resign_clear(D, b);
         status_out[b] = status;

@@ -34,6 +34,18 @@ STARTS = {
 }
 
 
+def perpetual_case(checker_is_red: bool):
+    """A rook that checks a bare king back and forth (a9+ Ke8, a8+ Ke9, ...): (squares, side to move, the 4-ply cycle)."""
+    if checker_is_red:
+        return _place({"d0": 7, "a8": 3, "e9": 7 + 8}), 1, ["a8a9", "e9e8", "a9a8", "e8e9"]
+    return _place({"d9": 7 + 8, "a1": 3 + 8, "e0": 7}), 0, ["a1a0", "e0e1", "a0a1", "e1e0"]
+
+
+def perpetual_quiet_cycle(checker_is_red: bool):
+    """From the position of perpetual_case: the rook shuffles without giving check, the king steps aside and back."""
+    return ["a8a7", "e9f9", "a7a8", "f9e9"] if checker_is_red else ["a1a2", "e0f0", "a2a1", "f0e0"]
+
+
 def mirrored(squares: np.ndarray) -> np.ndarray:
     """The same position seen from the other side: ranks reversed, colours swapped. With the other side to move it has the
     same number of legal moves."""

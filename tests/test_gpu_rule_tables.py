@@ -306,18 +306,8 @@ def test_pawn_move_clock_rule_is_switchable():
 
 
 def _perpetual_case(checker_is_red: bool):
-    """A rook that checks a bare king back and forth (a9+ Ke8, a8+ Ke9, ...): (squares, side to move, the 4-ply cycle)."""
-    from golden_cases import sq as S
-    pos = np.zeros(90, np.uint8)
-    if checker_is_red:
-        pos[S("d0")] = 7            # red king
-        pos[S("a8")] = 3            # red rook
-        pos[S("e9")] = 7 + 8        # black king
-        return pos, 1, ["a8a9", "e9e8", "a9a8", "e8e9"]
-    pos[S("d9")] = 7 + 8
-    pos[S("a1")] = 3 + 8            # black rook
-    pos[S("e0")] = 7
-    return pos, 0, ["a1a0", "e0e1", "a0a1", "e1e0"]
+    from golden_cases import perpetual_case
+    return perpetual_case(checker_is_red)
 
 
 @pytest.mark.parametrize("checker_is_red", [True, False])
@@ -327,14 +317,14 @@ def test_perpetual_check_rule_decides_a_fourfold_repetition(checker_is_red):
     a repetition without checks stays a draw under the flag; the search below such a root is unchanged (leaf value 0.0)."""
     import oracle
     from gpu_harness import Lockstep
-    from golden_cases import sq as S
+    from golden_cases import perpetual_quiet_cycle, sq as S
     from oracle import OracleBoard
     from chinesechesszero_amd import tools
     from chinesechesszero_amd.game import Board
     L = oracle.lib()
     uid = lambda u: L.xq_move_id(S(u[:2]), S(u[2:]))
     pos, turn, cycle = _perpetual_case(checker_is_red)
-    quiet = ["a8a7", "e9f9", "a7a8", "f9e9"] if checker_is_red else ["a1a2", "e0f0", "a2a1", "f0e0"]   # the rook shuffles, no check
+    quiet = perpetual_quiet_cycle(checker_is_red)   # the rook shuffles, no check
     results = {}
     for flag, seq, name in ((True, cycle, "perpetual"), (False, cycle, "flag off"), (True, quiet, "no checks")):
         try:
