@@ -41,6 +41,8 @@ ERR_PRUNED, ERR_TRUNCATED = 256, 512   # CCZ_ERR_* set in strict mode only
 ERR_BAD_TEMP = 1024   # CCZ_ERR_BAD_TEMP: a per-board temperature that is NaN or <= 0
 FLAG_STRICT = 16   # parity mode: pruning a kept subtree / adjudicating at max_plies are error bits, not counters
 LEAF_EXPAND, LEAF_DRAW, LEAF_LOSS, LEAF_SKIP = 0, 1, 2, 3
+LEAF_WIN = 4   # CCZ_LEAF_WIN: MCTS-solver only -- the descent ended at a node proven won for its side to move
+PROOF_UNKNOWN, PROOF_WIN, PROOF_LOSS, PROOF_DRAW = 0, 1, 2, 3   # CCZ_PROOF_*: state of a proof byte (side to move's view)
 
 ERR_BITS = {1: "node pool exhausted (raise max_nodes)", 2: "selection path deeper than max_depth", 64: "history chain overflow (> 128 positions since the last capture)",
             4: "more than 128 legal moves or pseudo-move overflow", 8: "pi record arena overflow",
@@ -84,6 +86,10 @@ class ResignStats(C.Structure):
 
 class ExplorationStats(C.Structure):
     _fields_ = [("explored_moves", C.c_int64), ("forced_selections", C.c_int64), ("visits_pruned", C.c_int64), ("children_pruned", C.c_int64)]
+
+
+class SolverStats(C.Structure):
+    _fields_ = [("nodes_proven", C.c_int64), ("proven_stops", C.c_int64), ("roots_proven", C.c_int64)]
 
 
 # every symbol include/cczero.h declares: name -> (restype, argtypes)
@@ -130,6 +136,10 @@ PROTOTYPES = {
     "ccz_set_root_exploration": (C.c_int, [_P, _P, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32]),
     "ccz_get_exploration_stats": (C.c_int, [_P, _P, C.POINTER(ExplorationStats)]),
     "ccz_root_noise": (C.c_int, [_P, _P, _P, _P]),
+    "ccz_set_solver": (C.c_int, [_P, _P, C.c_int32]),
+    "ccz_root_proof": (C.c_int, [_P, _P, _P, _P, _P, _P]),
+    "ccz_get_solver_stats": (C.c_int, [_P, _P, C.POINTER(SolverStats)]),
+    "ccz_proof_combine": (C.c_int, [_P, _P, _P, C.c_int32, _P]),
     "ccz_finish_move": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32]),
     "ccz_root_children": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
     "ccz_principal_variations": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),

@@ -54,12 +54,22 @@ def parse_positions(lines) -> list[tuple[int, Board]]:
     return out
 
 
-def make_record(status: str, root_visits: int = 0, lines=()) -> dict:
+def make_record(status: str, root_visits: int = 0, lines=(), solver=None) -> dict:
     """One result record: ``status`` ("ok", "illegal move i", "invalid position", "history too long", "game over: ..."),
-    ``bestmove`` (the first move of line 0, or None), ``root_visits``, ``lines`` = [{moves (uci), visits, q, prior}]."""
-    lines = [dict(moves=list(l["moves"]), visits=[int(v) for v in l["visits"]], q=float(l["q"]), prior=float(l["prior"])) for l in lines]
-    return {"status": status, "bestmove": lines[0]["moves"][0] if lines and lines[0]["moves"] else None,
-            "root_visits": int(root_visits), "lines": lines}
+    ``bestmove`` (the first move of line 0, or None), ``root_visits``, ``lines`` = [{moves (uci), visits, q, prior}].
+    ``solver`` (an analysis with the MCTS-solver; None without): ``{"proven": uci or None, "mates": {uci: N}}`` -- the record and
+    every line gain ``"mate"``: N in moves (``engine.mate_score``; negative: the side to move is mated) or None, and ``bestmove``
+    is the proven move where the root is decided."""
+    keep = [dict(moves=list(l["moves"]), visits=[int(v) for v in l["visits"]], q=float(l["q"]), prior=float(l["prior"])) for l in lines]
+    rec = {"status": status, "bestmove": keep[0]["moves"][0] if keep and keep[0]["moves"] else None,
+           "root_visits": int(root_visits), "lines": keep}
+    if solver is not None:
+        for l in keep:
+            l["mate"] = solver["mates"].get(l["moves"][0]) if l["moves"] else None
+        if solver.get("proven") is not None:
+            rec["bestmove"] = solver["proven"]
+        rec["mate"] = solver["mates"].get(rec["bestmove"]) if rec["bestmove"] is not None else None
+    return rec
 
 
 def _winner_text(winner) -> str:
@@ -72,7 +82,7 @@ class BatchedAnalysis:
     192 boards and more, as in self-play) the search runs on the planned boundary with the evaluation cache; the cache is kept
     across chunks and cleared only when the evaluator's weights version changes."""
 
-    def __init__(self, evaluator, n_boards: int, n_playout: int = 400, multipv: int = 1, max_len: int = 32, **engine_kw):
+    def __init__(self, evaluator, n_boards: int, n_playout: int = 400, multipv: int = 1, max_len: int = 32, solver: bool = False, **engine_kw):
         from .selfplay import BatchedSelfPlay
         ev = getattr(evaluator, "evaluate_leaves_logits", evaluator)
         if not callable(ev):
@@ -84,6 +94,9 @@ class BatchedAnalysis:
         engine_kw.setdefault("mirror", False)
         self.sp = BatchedSelfPlay(ev, int(n_boards), n_playout=int(n_playout), eps=0.0, **engine_kw)   # no GPU: CczError
         self.engine = self.sp.engine
+        self.solver = bool(solver)     # the MCTS-solver: records gain "mate", bestmove follows the proof (make_record)
+        if self.solver:
+            self.engine.set_solver(True)
         self.B, self.n_playout, self.multipv, self.max_len = int(n_boards), int(n_playout), int(multipv), int(max_len)
         self.positions = self.steps = self.sims = 0
         self.seconds = 0.0
@@ -125,6 +138,7 @@ class BatchedAnalysis:
                 sp.search(hooks=self._count_rows)
             pv = e.principal_variations(self.multipv, self.max_len)
             e.check_healthy()
+            rp, rc = (e.root_proof(), e.root_children()) if self.solver else (None, None)
             for j, bd in enumerate(chunk):
                 s = int(status[j])
                 if s > 0:
@@ -140,8 +154,15 @@ class BatchedAnalysis:
                         if ln:
                             lines.append({"moves": [uci_of[int(i)] for i in pv["moves"][j, r, :ln]], "visits": pv["visits"][j, r, :ln],
                                           "q": pv["q"][j, r], "prior": pv["prior"][j, r]})
+                    sv = None
+                    if self.solver:
+                        from .engine import mate_score, proof_move
+                        k = int(rc["k"][j])
+                        pm = proof_move(rp["state"][j], rp["dist"][j], rp["child_state"][j], rp["child_dist"][j], rc["acts"][j])
+                        sv = {"proven": None if pm is None else uci_of[pm],
+                              "mates": {uci_of[int(rc["acts"][j][i])]: mate_score(rp["child_state"][j][i], rp["child_dist"][j][i]) for i in range(k)}}
                     if lines:
-                        out.append(make_record("ok", pv["root_visits"][j], lines))
+                        out.append(make_record("ok", pv["root_visits"][j], lines, solver=sv))
                     else:   # a position given without moves that is already decided: the root never got children
                         oc = bd.outcome()
                         out.append(make_record("ok" if oc is None else _winner_text(None if oc.winner is None else int(bool(oc.winner))),
@@ -169,6 +190,7 @@ def main(argv=None) -> int:
     ap.add_argument("--max-len", type=int, default=32)
     ap.add_argument("--weights", default=None, help="model file (default: random initialisation)")
     ap.add_argument("--out", default=None, help="JSON lines file (default: stdout)")
+    ap.add_argument("--solver", action="store_true", help="MCTS-solver: prove decided positions in the tree; every record gains \"mate\": N or null")
     args = ap.parse_args(argv)
     with open(args.file, encoding="utf-8") as f:
         try:
@@ -184,7 +206,7 @@ def main(argv=None) -> int:
     try:
         pvn = PolicyValueNet(model=args.weights, device="cuda:0")
         an = BatchedAnalysis(pvn, max(1, min(args.boards, len(parsed) or 1)), n_playout=args.playout, multipv=args.multipv,
-                             max_len=args.max_len)
+                             max_len=args.max_len, solver=args.solver)
         records = an.analyse([b for _, b in parsed])
     except CczError as e:
         print(f"analyse: {e}", file=sys.stderr)

@@ -178,11 +178,12 @@ class Arena:
     None: both search ``n_playout``. ``resign``: a threshold in [-1, 0] or a dict with ``threshold`` and optionally ``consecutive`` /
     ``min_ply`` (``engine.set_resign``): the side to move resigns when its root value stayed below the threshold -- a resigned game
     is a win for the other side like any other, counted in ``result()["resigned"]``; no game is played on (``p_playon`` = 0).
-    None (default): games end by the rules or the ply cap only."""
+    None (default): games end by the rules or the ply cap only. ``solver``: both sides search with the MCTS-solver
+    (``engine.set_solver``) and play the proven move where the root is decided (``engine.proof_moves``)."""
 
     def __init__(self, net_a, net_b, n_pairs: int, n_playout: int = 400, opening_plies: int = 6, seed: int = 0,
                  max_plies: int = 0, c_puct: float = C_PUCT, eval_cache_log2: int = 22, device: int = 0,
-                 cache_verify: bool = False, n_playout_b: int | None = None, resign=None):
+                 cache_verify: bool = False, n_playout_b: int | None = None, resign=None, solver: bool = False):
         from .engine import SelfPlayEngine
         self.nets = (net_a, net_b)
         self.ev = (_as_evaluator(net_a, "A"), _as_evaluator(net_b, "B"))
@@ -202,6 +203,10 @@ class Arena:
                                          seed=seed, device=device, max_plies=max_plies, mirror=False,
                                          eval_cache_log2=eval_cache_log2, cache_verify=cache_verify)
         self.max_plies = e.max_plies
+        self.solver = bool(solver)
+        self.proven_moves = 0                # moves played from a proof
+        if self.solver:
+            e.set_solver(True)
         self.resign = None
         if resign is not None:
             self.resign = dict(resign) if isinstance(resign, dict) else {"threshold": float(resign)}
@@ -272,7 +277,12 @@ class Arena:
         """The move after a :meth:`search`: arg-max visits up to ties (temperature 1e-3), the tree is discarded."""
         e = self.engine
         over = e.game_status()["over"]
-        moves = e.finish_move(temps=self._temps, keep_tree=False).cpu().numpy().copy()
+        forced = None
+        if self.solver:
+            forced = e.proof_moves()
+            forced[over != 0] = -1
+            self.proven_moves += int((forced >= 0).sum())
+        moves = e.finish_move(forced_moves=forced, temps=self._temps, keep_tree=False).cpu().numpy().copy()
         # a game adjudicated at max_plies ends INSTEAD of a move (finish_move plays none on that board); so does a resigned one
         st = e.game_status()
         ended = (over == 0) & (st["over"] == 1) & (moves < 0)
@@ -310,6 +320,8 @@ class Arena:
                "n_playout_b": self.n_playout if self.n_playout_b is None else self.n_playout_b,
                "wins": int(np.sum(w == self.a_colour)), "draws": int(np.sum(w == -1)), "losses": int(np.sum((w != -1) & (w != self.a_colour))),
                "truncated": int(self.truncated.sum()), "unfinished": int((st["over"] == 0).sum())}
+        if self.solver:
+            out["solver"] = dict(self.engine.solver_stats(), proven_moves=self.proven_moves)
         if self.resign is not None:
             out["resigned"] = int(((self.engine.resign_status()["state"] & _RESIGNED) != 0).sum())
         out.update(pair_stats(pair_pts))
@@ -361,6 +373,7 @@ def main(argv=None) -> int:
     ap.add_argument("--resign-threshold", type=float, default=None,
                     help="resignation: the side to move resigns when its root value stayed below this (in [-1, 0]); absent = off")
     ap.add_argument("--resign-moves", type=int, default=None, help="... for this many of its moves in a row (default 2)")
+    ap.add_argument("--solver", action="store_true", help="MCTS-solver on both sides: decided positions are proven in the tree and the proven move is played")
     ap.add_argument("--resign-min-ply", type=int, default=None, help="... and not before this ply (default 30)")
     a = ap.parse_args(argv)
     if a.resign_threshold is None and (a.resign_moves is not None or a.resign_min_ply is not None):
@@ -372,7 +385,7 @@ def main(argv=None) -> int:
     na = _load(a.a, a.channels, a.blocks, a.device)
     nb = _load(a.b, a.channels, a.blocks, a.device)
     arena = Arena(na, nb, a.pairs, n_playout=a.playout, opening_plies=a.opening_plies, seed=a.seed, max_plies=a.max_plies,
-                  eval_cache_log2=a.eval_cache_log2, device=a.device, n_playout_b=a.playout_b, resign=resign)
+                  eval_cache_log2=a.eval_cache_log2, device=a.device, n_playout_b=a.playout_b, resign=resign, solver=a.solver)
     r = arena.play()
     r.update({"a": a.a, "b": a.b, "opening_plies": a.opening_plies, "seed": a.seed, "net": f"{a.blocks}x{a.channels}",
               "promote": promote(r, a.threshold), "threshold": a.threshold})

@@ -508,7 +508,10 @@ class CollectPipeline:
                  finalize_every: int = 0, on_playout=None, max_plies: int = 0, eval_cache_log2: int | None = None, gatherer=None,
                  dense_shards: bool = False, replay_plies: int = 0, train_every: int = 0, train_batch: int = BATCH_SIZE,
                  playout_cap_fast: int = 0, playout_cap_prob: float | None = None, resign=None, value_q_weight: float = 0.0,
-                 root_exploration=None):
+                 root_exploration=None, solver: bool = False):
+        self.solver = bool(solver)     # the MCTS-solver in the search of the batched path (only the search changes)
+        if self.solver and n_boards <= 1:
+            raise ValueError("the solver option of the collector runs on the batched path: n_boards must be > 1")
         # collect + train as one job (both 0: off): the rank that stores the union keeps it in a record ring of ``replay_plies`` plies
         # and runs one Trainer step of ``train_batch`` rows every ``train_every`` lockstep moves, once the ring holds a batch
         self.replay_plies, self.train_every, self.train_batch = int(replay_plies), int(train_every), int(train_batch)
@@ -682,7 +685,7 @@ class CollectPipeline:
                                             c_puct=self.c_puct, temp=self.temp, seed=self.seed, board_id_base=rank * self.n_boards,
                                             device=self.device, reference_quirks=self.reference_quirks, max_plies=self.max_plies,
                                             playout_cap=self.playout_cap, resign=getattr(self, "resign", None),
-                                            root_exploration=getattr(self, "root_exploration", None))
+                                            root_exploration=getattr(self, "root_exploration", None), solver=getattr(self, "solver", False))
             if getattr(self, "_viewer", None) is not None:
                 self.selfplay.watch(0, self._viewer)
         for _ in range(n_moves):
@@ -869,6 +872,13 @@ class CollectPipeline:
         after = f"{r['playon_plies_after'] / n:.1f}" if n else "n/a"
         return f", resigned {r['resigned_games']}, play-on {n} (false positives {fp}, mean plies after {after})"
 
+    def solver_report(self) -> str:
+        """The MCTS-solver part of the periodic log line (empty with the solver off; syncs): the three counters."""
+        if not getattr(self, "solver", False) or getattr(self, "selfplay", None) is None:
+            return ""
+        s = self.selfplay.engine.solver_stats()
+        return f", nodes proven {s['nodes_proven']}, simulations ended at a proven node {s['proven_stops']}, roots proven {s['roots_proven']}"
+
     def exploration_report(self) -> str:
         """The root-exploration part of the periodic log line (empty with the feature off; syncs)."""
         if getattr(self, "root_exploration", None) is None or getattr(self, "selfplay", None) is None:
@@ -910,7 +920,7 @@ class CollectPipeline:
                 while max_calls <= 0 or calls < max_calls:
                     iters = self.collect_data(is_shown=is_shown)
                     calls += 1
-                    log(f"Episode {iters}, steps {self.episode_len}" + self.resign_report() + self.exploration_report())
+                    log(f"Episode {iters}, steps {self.episode_len}" + self.resign_report() + self.exploration_report() + self.solver_report())
             except KeyboardInterrupt:
                 log("Exit")
             if self.gatherer is not None and hasattr(self.gatherer, "flush_iter") and self.selfplay is not None:
@@ -973,6 +983,8 @@ def build_parser():
     parser.add_argument("--forced-playouts", type=float, default=None, help=f"... forced playouts: a root child is searched until N >= sqrt(k P' S) "
                         f"(default k = {FORCED_PLAYOUTS}, KataGo's; 0 = none)")
     parser.add_argument("--no-target-pruning", action="store_true", default=False, help="... keep the forced visits in the recorded policy targets")
+    parser.add_argument("--solver", action="store_true", default=False, help="batched path: search with the MCTS-solver (decided positions are proven "
+                        "in the tree and cost no evaluator row); sampling, records and targets are as without it")
     parser.add_argument("--value-q-weight", type=float, default=0.0, help="with --train-every: weight of the recorded root value q in the value "
                         "target, (1 - w) z + w q on rows that carry one (0 = z alone)")
     return parser
@@ -1050,7 +1062,7 @@ if __name__ == "__main__":
                            eval_cache_log2=args.eval_cache_log2, gatherer=gatherer, replay_plies=args.replay_plies,
                            train_every=args.train_every, train_batch=args.train_batch, playout_cap_fast=args.playout_cap_fast,
                            playout_cap_prob=args.playout_cap_prob, resign=args.resign, value_q_weight=args.value_q_weight,
-                           root_exploration=args.root_exploration)
+                           root_exploration=args.root_exploration, solver=args.solver)
     if world > 1:
         from .launch import guarded
 

@@ -83,6 +83,10 @@ struct ccz_engine {
     uint64_t salt[2] = {0, 0};
     bool budgets_on = false;       // ccz_set_budgets / ccz_draw_budgets (off: every budget INT32_MAX, every target 1)
     bool explore_on = false;       // ccz_set_root_exploration(enabled): the host's shadow of ExploreCfg.enabled (scouts are refused with it)
+    // MCTS-solver (ccz_set_solver): the proof bytes [B][2][cap] (allocated by the first call that turns it on), the host's shadow of
+    // SolverCfg.enabled, staging of ccz_root_proof (state [B], dist [B], child state [B][128], child dist [B][128])
+    uint8_t *proof = nullptr, *st_proof = nullptr;
+    bool solver_on = false;
 };
 
 #define ACTIVE(e) ((unsigned)((e)->active > 0 ? (e)->active : (e)->d.B))
@@ -300,6 +304,10 @@ int ccz_create(const ccz_config *cfg, ccz_engine **out)
     ALLOC(d.ex_dir, B * kMaxLegal);
     ALLOC(d.ex_stamp, B * 2);
     ALLOC(d.ex_stats, B);
+    SolverCfg *sv_cfg = nullptr;
+    ALLOC(sv_cfg, 1); // zeroed: solver off, no proof array
+    d.sv_cfg = sv_cfg;
+    ALLOC(d.sv_stats, B);
     ALLOC(d.rec_ids, B * d.pi_cap);
     ALLOC(d.rec_pi, B * d.pi_cap);
     ALLOC(d.stats, B);
@@ -737,6 +745,81 @@ int ccz_get_exploration_stats(ccz_engine *e, void *stream, ccz_exploration_stats
         out->visits_pruned += (int64_t)b.visits_pruned;
         out->children_pruned += (int64_t)b.children_pruned;
     }
+    return 0;
+}
+
+int ccz_set_solver(ccz_engine *e, void *stream, int32_t enabled)
+{
+    NEED(e);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t n = (size_t)e->d.B * 2 * (size_t)e->d.cap;
+    if (enabled && !e->proof) {
+        HIP_TRY(hipSetDevice(e->cfg.device));
+        HIP_TRY(dalloc(&e->proof, n, e->owned, e->bytes)); // (zeroed; may sync)
+    } else if (enabled && !e->solver_on) {
+        HIP_TRY(hipMemsetAsync(e->proof, 0, n, s)); // nothing kept the bytes up to date while it was off
+    }
+    SolverCfg v;
+    v.enabled = enabled ? 1 : 0;
+    v.pad = 0;
+    v.proof = e->proof;
+    hipLaunchKernelGGL(k_set_solver, dim3(1), dim3(1), 0, s, const_cast<SolverCfg *>(e->d.sv_cfg), v);
+    HIP_TRY(hipGetLastError());
+    e->solver_on = enabled != 0;
+    return 0;
+}
+
+// k_root_proof into the staging block (allocated at the first call); the caller copies what it wants and syncs
+static int stage_root_proof(ccz_engine *e, hipStream_t s)
+{
+    const size_t B = (size_t)e->d.B;
+    if (!e->st_proof) HIP_TRY(dalloc(&e->st_proof, B * (2 + 2 * kMaxLegal), e->owned, e->bytes));
+    uint8_t *p = e->st_proof;
+    hipLaunchKernelGGL(k_root_proof, dim3(e->d.B), dim3(64), 0, s, e->d, p, p + B, p + 2 * B, p + 2 * B + B * kMaxLegal);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int ccz_root_proof(ccz_engine *e, void *stream, uint8_t *state_host, uint8_t *dist_host, uint8_t *child_state_host, uint8_t *child_dist_host)
+{
+    NEED(e);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t B = (size_t)e->d.B;
+    if (const int rc = stage_root_proof(e, s)) return rc;
+    const uint8_t *p = e->st_proof;
+    if (state_host) HIP_TRY(hipMemcpyAsync(state_host, p, B, hipMemcpyDeviceToHost, s));
+    if (dist_host) HIP_TRY(hipMemcpyAsync(dist_host, p + B, B, hipMemcpyDeviceToHost, s));
+    if (child_state_host) HIP_TRY(hipMemcpyAsync(child_state_host, p + 2 * B, B * kMaxLegal, hipMemcpyDeviceToHost, s));
+    if (child_dist_host) HIP_TRY(hipMemcpyAsync(child_dist_host, p + 2 * B + B * kMaxLegal, B * kMaxLegal, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return 0;
+}
+
+int ccz_get_solver_stats(ccz_engine *e, void *stream, ccz_solver_stats *out)
+{
+    NEED(e);
+    if (!out) return fail(-1, "ccz_get_solver_stats: null output");
+    hipStream_t s = (hipStream_t)stream;
+    if (const int rc = stage_root_proof(e, s)) return rc;
+    std::vector<uint8_t> root((size_t)e->d.B);
+    HIP_TRY(hipMemcpyAsync(root.data(), e->st_proof, root.size(), hipMemcpyDeviceToHost, s));
+    std::vector<SolverBoardStats> st;
+    if (const int rc = fetch_board_stats(e, s, e->d.sv_stats, st)) return rc; // syncs
+    memset(out, 0, sizeof *out);
+    for (const SolverBoardStats &b : st) {
+        out->nodes_proven += (int64_t)b.proven;
+        out->proven_stops += (int64_t)b.stops;
+    }
+    for (unsigned b = 0; b < ACTIVE(e); ++b) out->roots_proven += root[b] ? 1 : 0;
+    return 0;
+}
+
+int ccz_proof_combine(void *stream, const uint8_t *bytes_dev, const int32_t *counts_dev, int32_t n_cases, uint8_t *out_dev)
+{
+    if (n_cases < 0 || !bytes_dev || !counts_dev || !out_dev) return fail(-1, "ccz_proof_combine: bad arguments");
+    if (n_cases == 0) return 0;
+    hipLaunchKernelGGL(k_proof_combine, dim3((unsigned)n_cases), dim3(64), 0, (hipStream_t)stream, bytes_dev, counts_dev, (int)n_cases, out_dev);
+    HIP_TRY(hipGetLastError());
     return 0;
 }
 

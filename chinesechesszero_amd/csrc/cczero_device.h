@@ -92,6 +92,20 @@ struct ExploreBoardStats {
     unsigned long long explored, forced, visits_pruned, children_pruned;
 };
 
+// MCTS-solver (ccz_set_solver): the settings as the device reads them, and the per-board counters. A proof byte holds the state in
+// bits 0..1 -- the view of the side to move at the node -- and the distance to the end in plies in bits 2..7 (saturating at 63; 0 for a
+// draw). The array lives behind the settings, not in Dev: it is allocated by the first ccz_set_solver(1), and a graph captured before
+// that call holds Dev by value.
+constexpr uint32_t kProofWin = 1u, kProofLoss = 2u, kProofDraw = 3u;
+struct SolverCfg {
+    int32_t enabled;  // 0: no kernel reads or writes a proof byte
+    int32_t pad;
+    uint8_t *proof;   // [B][2][cap], indexed like nodeA / nodeB
+};
+struct SolverBoardStats {
+    unsigned long long proven, stops; // nodes whose byte left "unknown"; simulations that ended at a node proven before
+};
+
 struct Dev {
     int32_t B, cap, maxd, max_plies, pi_cap;
     int32_t reserve;   // nodes of every pool half kept free at re-root time for the next move's expansions
@@ -167,6 +181,9 @@ struct Dev {
     float *ex_dir;              // [B][128] Dirichlet component dir_i of the root's child i for the move the stamp names
     uint32_t *ex_stamp;         // [B][2] (move_counter + 1, k) the row of ex_dir was filled for; (0, 0): none
     ExploreBoardStats *ex_stats; // [B]
+    // ---- MCTS-solver (ccz_set_solver). "Off" is SolverCfg.enabled == 0: one word read per kernel, next to the ones above
+    const SolverCfg *sv_cfg;     // [1] written by k_set_solver in stream order
+    SolverBoardStats *sv_stats;  // [B]
 };
 __device__ __forceinline__ int plane_of(const Dev &D, int type) { return (int)((D.chanpack >> (3 * type)) & 7u); }
 __device__ __forceinline__ int type_in_plane(const Dev &D, int chan) { return (int)((D.typepack >> (3 * chan)) & 7u) + 1; }

@@ -1,5 +1,7 @@
 // cczero_kernels.h -- the gfx950 kernels of the lockstep self-play engine (one wave per board).
 #pragma once
+#include <type_traits>
+
 #include "cczero_device.h"
 
 namespace ccz {
@@ -35,6 +37,8 @@ __device__ __forceinline__ void fresh_root(const Dev &D, int b, int half)
     const size_t base = ((size_t)b * 2 + half) * (size_t)D.cap;
     D.nodeA[base] = NodeA{0, 0.0f, 1.0f, -1};
     D.nodeB[base] = 0u;
+    const SolverCfg sv = *D.sv_cfg;
+    if (sv.enabled) sv.proof[base] = 0; // a fresh root is unproven
     D.path_len[b] = 0;
     D.leaf_status[b] = CCZ_LEAF_SKIP;
     D.move_sims[b] = 0; // a move boundary: the board's simulation budget (Dev.budget) starts over
@@ -166,6 +170,40 @@ __device__ inline LeafEval eval_position(const uint8_t *s_sq, int turn, int half
     return L;
 }
 
+// ------------------------------------------------------------------ MCTS-solver: the proof byte of a node from its children's
+// p0 / p1: the bytes of children `lane` and `64 + lane` of a node with nc <= 128 children (whatever a lane past nc passes is ignored).
+// In this order: a child that is LOSS -> WIN in 1 + the smallest such distance; else an unknown child -> unknown; else a DRAW child
+// -> DRAW; else every child is WIN -> LOSS in 1 + the largest distance. Distances saturate at 63. Two passes over the lanes (children
+// 0..63, 64..127), the verdicts by ballot, the distances by a wave reduction. All 64 lanes call it; the result is wave-uniform.
+__device__ __forceinline__ uint32_t proof_combine(uint32_t p0, uint32_t p1, int nc, int lane)
+{
+    if (nc <= 0) return 0u;
+    bool anyL = false, anyU = false, anyD = false;
+    int minL = 63, maxW = 0;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const bool in = 64 * h + lane < nc;
+        const uint32_t p = h ? p1 : p0;
+        const uint32_t st = p & 3u;
+        const int ds = (int)((p >> 2) & 63u);
+        anyL |= __ballot(in && st == kProofLoss) != 0ull;
+        anyU |= __ballot(in && st == 0u) != 0ull;
+        anyD |= __ballot(in && st == kProofDraw) != 0ull;
+        if (in && st == kProofLoss && ds < minL) minL = ds;
+        if (in && st == kProofWin && ds > maxW) maxW = ds;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const int a = __shfl_xor(minL, o), c = __shfl_xor(maxW, o);
+        minL = a < minL ? a : minL;
+        maxW = c > maxW ? c : maxW;
+    }
+    if (anyL) return kProofWin | ((uint32_t)(minL < 62 ? minL + 1 : 63) << 2);
+    if (anyU) return 0u;
+    if (anyD) return kProofDraw;
+    return kProofLoss | ((uint32_t)(maxW < 62 ? maxW + 1 : 63) << 2);
+}
+
 // ------------------------------------------------------------------ K1: select + make-move + movegen + terminal + encode
 struct SelectShared {
     __align__(16) uint8_t sq[96];
@@ -193,6 +231,8 @@ struct Prefetch {
     int32_t budget;    // simulations the board may back up in this move (INT32_MAX: budgets off)
     int32_t move_sims; // ... and how many it has, as of the top of the kernel (this launch's backup is not in it)
     int32_t ex;        // root exploration (ccz_set_root_exploration) applies to the board's current move: on, and a policy-target move
+    SolverCfg sv;      // MCTS-solver (ccz_set_solver): on / off and where the proof bytes are
+    uint32_t kidp;     // solver on: lane i: the proof byte of child i of the root (off: 0, nothing is read)
 };
 
 // what the expand+backup phase of this launch changed at the top of the tree (the prefetched root and
@@ -207,7 +247,17 @@ struct TopPatch {
     int node1, N1;     // path node at depth 1 (if depth >= 1) with its updated N, Q
     float Q1;
     bool has1;
+    bool hasp1;        // solver: the backup rewrote the proof byte of node1 ...
+    uint32_t p1;       // ... to this
 };
+
+// the solver's settings as a kernel reads them: once; `enabled` is tested wave-uniformly
+__device__ __forceinline__ SolverCfg solver_cfg(const Dev &D)
+{
+    SolverCfg sv = *D.sv_cfg;
+    sv.enabled = __builtin_amdgcn_readfirstlane(sv.enabled);
+    return sv;
+}
 
 __device__ __forceinline__ Prefetch prefetch_board(const Dev &D, int b, int lane)
 {
@@ -225,6 +275,9 @@ __device__ __forceinline__ Prefetch prefetch_board(const Dev &D, int b, int lane
     P.budget = D.budget[b];
     P.move_sims = D.move_sims[b];
     P.ex = D.ex_cfg->enabled * (int32_t)D.target[b]; // (both words are requested with the rest: no load waits for the other)
+    P.sv = solver_cfg(D); // (requested with the rest; off: no load waits for it)
+    P.kidp = 0u;
+    if (P.sv.enabled) P.kidp = P.sv.proof[base + 1 + lane];
     return P;
 }
 
@@ -434,6 +487,9 @@ __device__ inline void select_phase(const Dev &D, int b, int lane, uint16_t *lea
     uint64_t key = m.key;
     bool bad = false;
     if (lane == 0) path[0] = 0;
+    const bool solver = P.sv.enabled != 0;
+    const uint8_t *proof = P.sv.proof + base;
+    uint32_t proven = 0u;
 
     // ---- root exploration: noisy priors and forced playouts at depth 0 (off: the one prefetched word tested here)
     bool ex = false;
@@ -446,72 +502,97 @@ __device__ inline void select_phase(const Dev &D, int b, int lane, uint16_t *lea
         explore_dir(D, xc, b, lane, (int)(nb >> 16), m.move_counter, A + pa.fc, (double *)sh.S.cand, xd0, xd1);
     }
 
-    // ---- PUCT descent (mcts.py:105-111, 41-61)
-    for (;;) {
-        const int nc = (int)(nb >> 16);
-        if (nc == 0) break;
-        const double sqrtNp = sqrt((double)pa.N); // np.sqrt(parent.visits): float64
-        double best = -__builtin_huge_val();
-        int besti = 0x7fffffff, bN = 0, bfc = -1;
-        float bQ = 0.0f;
-        uint32_t bw = 0;
-        bool bF = false;
-        const bool exroot = EX && ex && depth == 0;
-        for (int c0 = 0; c0 < nc; c0 += 64) {
-            const int i = c0 + lane;
-            if (i < nc) {
-                NodeA c;
-                uint32_t w;
-                if (depth == 0 && c0 == 0 && pa.fc == 1) { // root children: prefetched (+ this launch's backup)
-                    c = P.kid;
-                    w = P.kidw;
-                    if (tp.root_expanded) { c.N = 0; c.Q = 0.0f; c.fc = -1; w = (uint32_t)tp.first_id; }
-                    else if (tp.has1 && 1 + i == tp.node1) {
-                        c.N = tp.N1;
-                        c.Q = tp.Q1;
-                        if (tp.kid_expanded) { c.fc = tp.n0; w = (w & 0xffffu) | ((uint32_t)tp.k << 16); }
+    // ---- PUCT descent (mcts.py:105-111, 41-61). Compiled twice, chosen by the wave-uniform solver word: with the solver off the
+    // loop is the one it was (no proof byte in it); SV: std::true_type / std::false_type
+    const auto descend = [&](auto SV) {
+        constexpr bool SOLVER = decltype(SV)::value;
+        for (;;) {
+            const int nc = (int)(nb >> 16);
+            if (nc == 0) break;
+            const double sqrtNp = sqrt((double)pa.N); // np.sqrt(parent.visits): float64
+            double best = -__builtin_huge_val();
+            int besti = 0x7fffffff, bN = 0, bfc = -1;
+            float bQ = 0.0f;
+            uint32_t bw = 0, bP = 0;
+            bool bF = false;
+            const bool exroot = EX && ex && depth == 0;
+            for (int c0 = 0; c0 < nc; c0 += 64) {
+                const int i = c0 + lane;
+                if (i < nc) {
+                    NodeA c;
+                    uint32_t w, pb = 0u; // pb: the candidate's proof byte, loaded in the round of its record (solver off: none)
+                    if (depth == 0 && c0 == 0 && pa.fc == 1) { // root children: prefetched (+ this launch's backup)
+                        c = P.kid;
+                        w = P.kidw;
+                        if (SOLVER) pb = P.kidp;
+                        if (tp.root_expanded) { c.N = 0; c.Q = 0.0f; c.fc = -1; w = (uint32_t)tp.first_id; pb = 0u; }
+                        else if (tp.has1 && 1 + i == tp.node1) {
+                            c.N = tp.N1;
+                            c.Q = tp.Q1;
+                            if (tp.kid_expanded) { c.fc = tp.n0; w = (w & 0xffffu) | ((uint32_t)tp.k << 16); }
+                            if (SOLVER && tp.hasp1) pb = tp.p1;
+                        }
+                    } else {
+                        c = A[CCZ_IDX(D, pa.fc + i, D.cap)];
+                        w = Bn[CCZ_IDX(D, pa.fc + i, D.cap)];
+                        if (SOLVER) pb = proof[CCZ_IDX(D, pa.fc + i, D.cap)];
                     }
-                } else {
-                    c = A[CCZ_IDX(D, pa.fc + i, D.cap)];
-                    w = Bn[CCZ_IDX(D, pa.fc + i, D.cap)];
+                    // value + c_puct*prob*sqrt(N_parent)/(1+N): float32 product, float64 elsewhere; inf if unvisited
+                    float pp = c.P;
+                    bool fsel = false;
+                    if (exroot) { // P' for P, and a visited child short of its forced playouts scores like an unvisited one
+                        pp = explore_prior(xc, c.P, c0 ? xd1 : xd0);
+                        fsel = xc.forced_k > 0.0 && c.N > 0 && (double)c.N < sqrt(xc.forced_k * (double)pp * (double)(pa.N - 1));
+                    }
+                    const double sc = (c.N == 0 || fsel) ? __builtin_huge_val()
+                                                         : (double)c.Q + (double)(D.c_puct * pp) * sqrtNp / (double)(1 + c.N);
+                    if (sc > best) { best = sc; besti = i; bN = c.N; bQ = c.Q; bfc = c.fc; bw = w; bF = fsel; if (SOLVER) bP = pb; }
                 }
-                // value + c_puct*prob*sqrt(N_parent)/(1+N): float32 product, float64 elsewhere; inf if unvisited
-                float pp = c.P;
-                bool fsel = false;
-                if (exroot) { // P' for P, and a visited child short of its forced playouts scores like an unvisited one
-                    pp = explore_prior(xc, c.P, c0 ? xd1 : xd0);
-                    fsel = xc.forced_k > 0.0 && c.N > 0 && (double)c.N < sqrt(xc.forced_k * (double)pp * (double)(pa.N - 1));
-                }
-                const double sc = (c.N == 0 || fsel) ? __builtin_huge_val()
-                                                     : (double)c.Q + (double)(D.c_puct * pp) * sqrtNp / (double)(1 + c.N);
-                if (sc > best) { best = sc; besti = i; bN = c.N; bQ = c.Q; bfc = c.fc; bw = w; bF = fsel; }
+            }
+            // first maximum in insertion order wins (Python max()): wave max of the score, then the lowest index
+            // holding it (a lane's running best is its lowest-index maximum; indices < 64 precede the second pass)
+            const double top = wave_max_f64(best);
+            const bool hit = best == top && besti < nc;
+            const uint64_t h0 = __ballot(hit && besti < 64), h1 = __ballot(hit);
+            if (h1 == 0ull) { bad = true; set_err(D, 32); break; } // NaN priors: no comparable child
+            const int owner = __builtin_amdgcn_readfirstlane((h0 ? __ffsll((long long)h0) : __ffsll((long long)h1)) - 1);
+            besti = __builtin_amdgcn_readlane(besti, owner);
+            if (exroot && __builtin_amdgcn_readlane((int)bF, owner) && lane == 0) D.ex_stats[b].forced += 1;
+            const int child = pa.fc + besti;
+            pa.N = __builtin_amdgcn_readlane(bN, owner);
+            pa.Q = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(bQ), owner));
+            pa.fc = __builtin_amdgcn_readlane(bfc, owner);
+            nb = (uint32_t)__builtin_amdgcn_readlane((int)bw, owner);
+            const int mv = (int)(nb & 0xffffu);
+            // board.push(move) (mcts.py:111) is DEFERRED: only the move id is noted here, so that a tree level costs
+            // one global load round plus the arg-max and nothing else sits on the critical path
+            if (lane == 0) sh.pm.mv[depth] = (uint16_t)mv;
+            ++depth;
+            if (depth >= D.maxd) { bad = true; set_err(D, 2); break; }
+            if (lane == 0) path[CCZ_IDX(D, depth, D.maxd)] = child;
+            // MCTS-solver: a chosen child (depth >= 1: never the root) whose result is proven ends the descent
+            if (SOLVER) {
+                proven = (uint32_t)__builtin_amdgcn_readlane((int)bP, owner) & 3u;
+                if (proven) break;
             }
         }
-        // first maximum in insertion order wins (Python max()): wave max of the score, then the lowest index
-        // holding it (a lane's running best is its lowest-index maximum; indices < 64 precede the second pass)
-        const double top = wave_max_f64(best);
-        const bool hit = best == top && besti < nc;
-        const uint64_t h0 = __ballot(hit && besti < 64), h1 = __ballot(hit);
-        if (h1 == 0ull) { bad = true; set_err(D, 32); break; } // NaN priors: no comparable child
-        const int owner = __builtin_amdgcn_readfirstlane((h0 ? __ffsll((long long)h0) : __ffsll((long long)h1)) - 1);
-        besti = __builtin_amdgcn_readlane(besti, owner);
-        if (exroot && __builtin_amdgcn_readlane((int)bF, owner) && lane == 0) D.ex_stats[b].forced += 1;
-        const int child = pa.fc + besti;
-        pa.N = __builtin_amdgcn_readlane(bN, owner);
-        pa.Q = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(bQ), owner));
-        pa.fc = __builtin_amdgcn_readlane(bfc, owner);
-        nb = (uint32_t)__builtin_amdgcn_readlane((int)bw, owner);
-        const int mv = (int)(nb & 0xffffu);
-        // board.push(move) (mcts.py:111) is DEFERRED: only the move id is noted here, so that a tree level costs
-        // one global load round plus the arg-max and nothing else sits on the critical path
-        if (lane == 0) sh.pm.mv[depth] = (uint16_t)mv;
-        ++depth;
-        if (depth >= D.maxd) { bad = true; set_err(D, 2); break; }
-        if (lane == 0) path[CCZ_IDX(D, depth, D.maxd)] = child;
-    }
+    };
+    if (solver) descend(std::true_type{});
+    else descend(std::false_type{});
     wave_sync();
     if (bad) {
         if (lane == 0) D.leaf_status[b] = CCZ_LEAF_SKIP;
+        return;
+    }
+    if (proven) { // the leaf is that node: no pushes, no move generation, no evaluator row; the backup takes the value from the status
+        if (lane == 0) {
+            D.path_len[b] = depth;
+            D.leaf_k[b] = 0;
+            D.leaf_status[b] = (uint8_t)(proven == kProofWin ? CCZ_LEAF_WIN : proven == kProofLoss ? CCZ_LEAF_LOSS : CCZ_LEAF_DRAW);
+            BoardStats &st = D.stats[b];
+            st.sum_depth += (unsigned long long)depth;
+            if (depth > st.depth_peak) st.depth_peak = depth;
+        }
         return;
     }
 
@@ -524,7 +605,7 @@ __global__ __launch_bounds__(64) void k_select(Dev D, uint16_t *leaf_in)
     const Prefetch P = prefetch_board(D, blockIdx.x, threadIdx.x);
     TopPatch none;
     none.active = false; none.root_expanded = false; none.kid_expanded = false; none.k = 0; none.first_id = 0; none.n0 = 0;
-    none.rootN = 0; none.rootQ = 0.0f; none.node1 = -1; none.N1 = 0; none.Q1 = 0.0f; none.has1 = false;
+    none.rootN = 0; none.rootQ = 0.0f; none.node1 = -1; none.N1 = 0; none.Q1 = 0.0f; none.has1 = false; none.hasp1 = false; none.p1 = 0u;
     select_phase<true>(D, blockIdx.x, threadIdx.x, leaf_in, sh, P, none);
 }
 
@@ -591,15 +672,84 @@ __global__ __launch_bounds__(64) void k_scout(Dev D, uint16_t *leaf_in, int acti
     scout_wave(D, leaf_in, active, blockIdx.x, threadIdx.x, sh);
 }
 
+// ------------------------------------------------------------------ MCTS-solver: the backup of a decided simulation
+// Wave-uniform and sequential: the leaf's byte, then from its parent up to the root byte <- proof_combine(children) until a byte does
+// not change. The path nodes' child ranges and stored bytes come in one round (lane j: path node j = pj), then one round per level
+// walked: the children's bytes -- the child just rewritten is taken from registers, not read back. proof / A / Bn: the board's live
+// pool half; leaf = path node d if d < 64. Returns the new byte of the depth-1 path node | 0x100 if it was rewritten (TopPatch).
+// Runs on terminal simulations only: kept out of line, so that the simulator kernels carry its registers only across the call.
+__device__ __attribute__((noinline)) uint32_t proof_backup(const Dev &D, uint8_t *proof, const NodeA *A, const uint32_t *Bn, const int32_t *path,
+                                                           SolverBoardStats *stats, int pj, int d, int status, int leaf, int lane)
+{
+    uint32_t top = 0u;
+    int fcl = -1, ncl = 0;
+    uint32_t pl = 0u;
+    if (lane <= d && lane < 64) {
+        const int node = (int)CCZ_IDX(D, pj, D.cap);
+        fcl = A[node].fc;
+        ncl = (int)(Bn[node] >> 16);
+        pl = proof[node];
+    }
+    int childn = (int)CCZ_IDX(D, d < 64 ? leaf : path[CCZ_IDX(D, d, D.maxd)], D.cap);
+    uint32_t cur = d < 64 ? (uint32_t)__builtin_amdgcn_readlane((int)pl, __builtin_amdgcn_readfirstlane(d < 64 ? d : 0)) : (uint32_t)proof[childn];
+    const bool stopped = (cur & 3u) != 0u; // the descent ended at a node proven earlier: its byte stays
+    int newly = 0;
+    bool walk = true;
+    if (!stopped) {
+        if (status == CCZ_LEAF_WIN) walk = false; // (no such leaf: a WIN status comes from a proven byte)
+        else {
+            cur = status == CCZ_LEAF_DRAW ? kProofDraw : kProofLoss; // decided by the rules: distance 0
+            if (lane == 0) proof[childn] = (uint8_t)cur;
+            newly = 1;
+        }
+    }
+    if (walk && d == 1) top = 0x100u | cur;
+    for (int j = d - 1; walk && j >= 0; --j) {
+        int node, fc, nc;
+        uint32_t stored;
+        if (j < 64) {
+            const int js = __builtin_amdgcn_readfirstlane(j);
+            node = (int)CCZ_IDX(D, __builtin_amdgcn_readlane(pj, js), D.cap);
+            fc = __builtin_amdgcn_readlane(fcl, js);
+            nc = __builtin_amdgcn_readlane(ncl, js);
+            stored = (uint32_t)__builtin_amdgcn_readlane((int)pl, js);
+        } else {
+            node = (int)CCZ_IDX(D, path[CCZ_IDX(D, j, D.maxd)], D.cap);
+            fc = A[node].fc;
+            nc = (int)(Bn[node] >> 16);
+            stored = proof[node];
+        }
+        if (nc > kMaxLegal) nc = kMaxLegal;
+        uint32_t p0 = 0u, p1 = 0u;
+        if (lane < nc) p0 = proof[CCZ_IDX(D, fc + lane, D.cap)];
+        if (64 + lane < nc) p1 = proof[CCZ_IDX(D, fc + 64 + lane, D.cap)];
+        if (fc + lane == childn) p0 = cur;
+        if (fc + 64 + lane == childn) p1 = cur;
+        const uint32_t nw = proof_combine(p0, p1, nc, lane);
+        if (nw == stored) break;
+        if (lane == 0) proof[node] = (uint8_t)nw;
+        newly += ((stored & 3u) == 0u && (nw & 3u) != 0u) ? 1 : 0;
+        if (j == 1) top = 0x100u | nw;
+        cur = nw;
+        childn = node;
+    }
+    if (lane == 0) {
+        stats->proven += (unsigned long long)newly;
+        stats->stops += stopped ? 1ull : 0ull;
+    }
+    return top;
+}
+
 // ------------------------------------------------------------------ K2: expand + backup
 // prob: dense [B][2086] priors (compact == false) or compact [B][128] priors aligned with leaf_ids (compact == true)
 template <bool COMPACT>
 __device__ inline TopPatch expand_backup_phase(const Dev &D, int b, int lane, const float *prob, const float *value,
-                                               const BoardMeta &m0, int half)
+                                               const BoardMeta &m0, int half, const SolverCfg &sv)
 {
     TopPatch tp;
     tp.active = false; tp.root_expanded = false; tp.kid_expanded = false; tp.k = 0; tp.first_id = 0; tp.n0 = 0; tp.rootN = 0;
-    tp.rootQ = 0.0f; tp.node1 = -1; tp.N1 = 0; tp.Q1 = 0.0f; tp.has1 = false;
+    tp.rootQ = 0.0f; tp.node1 = -1; tp.N1 = 0; tp.Q1 = 0.0f; tp.has1 = false; tp.hasp1 = false; tp.p1 = 0u;
+    const bool solver = sv.enabled != 0;
     // everything that does not depend on another load is requested first
     const int status = D.leaf_status[b];
     const int d = D.path_len[b];
@@ -637,6 +787,11 @@ __device__ inline TopPatch expand_backup_phase(const Dev &D, int b, int lane, co
                 A[CCZ_IDX(D, n0 + 64 + lane, D.cap)] = NodeA{0, 0.0f, COMPACT ? cp1 : pr[COMPACT ? 0 : CCZ_IDX(D, id1, kNMoves)], -1};
                 Bn[CCZ_IDX(D, n0 + 64 + lane, D.cap)] = (uint32_t)id1;
             }
+            if (solver) { // pool slots are reused across moves: the new children are unproven
+                uint8_t *proof = sv.proof + base;
+                if (lane < k) proof[CCZ_IDX(D, n0 + lane, D.cap)] = 0;
+                if (64 + lane < k) proof[CCZ_IDX(D, n0 + 64 + lane, D.cap)] = 0;
+            }
             tp.root_expanded = d == 0;
             tp.kid_expanded = d == 1;
             tp.n0 = n0;
@@ -654,7 +809,7 @@ __device__ inline TopPatch expand_backup_phase(const Dev &D, int b, int lane, co
             }
         }
     } else {
-        v = status == CCZ_LEAF_DRAW ? 0.0f : -1.0f; // mcts.py:120-126
+        v = status == CCZ_LEAF_DRAW ? 0.0f : status == CCZ_LEAF_WIN ? 1.0f : -1.0f; // mcts.py:120-126; WIN: a node proven won (solver)
         if (lane == 0) D.stats[b].terminal += 1;
     }
     if (lane == 0) {
@@ -697,6 +852,12 @@ __device__ inline TopPatch expand_backup_phase(const Dev &D, int b, int lane, co
     tp.node1 = __builtin_amdgcn_readlane(pj, 1);
     tp.N1 = __builtin_amdgcn_readlane(myN, 1);
     tp.Q1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(myQ), 1));
+    // ---- MCTS-solver: a simulation that ended in a decided position proves what it can of its path (off, or an expansion: nothing)
+    if (solver && status != CCZ_LEAF_EXPAND) {
+        const uint32_t r = proof_backup(D, sv.proof + base, A, Bn, path, D.sv_stats + b, pj, d, status, leaf, lane);
+        tp.hasp1 = (r & 0x100u) != 0u;
+        tp.p1 = r & 0xffu;
+    }
     return tp;
 }
 
@@ -704,7 +865,8 @@ template <bool COMPACT>
 __global__ __launch_bounds__(64) void k_expand_backup(Dev D, const float *prob, const float *value)
 {
     const BoardMeta m0 = D.meta[blockIdx.x];
-    (void)expand_backup_phase<COMPACT>(D, blockIdx.x, threadIdx.x, prob, value, m0, *D.half);
+    const SolverCfg sv = solver_cfg(D);
+    (void)expand_backup_phase<COMPACT>(D, blockIdx.x, threadIdx.x, prob, value, m0, *D.half, sv);
 }
 
 // ------------------------------------------------------------------ fused step: expand+backup of the pending leaf, then the next select
@@ -717,7 +879,7 @@ __global__ __launch_bounds__(64) void k_step(Dev D, const float *prob, const flo
     const int b = blockIdx.x, lane = threadIdx.x;
     CCZ_STAMP(D, b, lane, 0)
     const Prefetch P = prefetch_board(D, b, lane); // root board, chain and meta: untouched by the expand phase
-    const TopPatch tp = expand_backup_phase<COMPACT>(D, b, lane, prob, value, P.m, P.half);
+    const TopPatch tp = expand_backup_phase<COMPACT>(D, b, lane, prob, value, P.m, P.half, P.sv);
     CCZ_STAMP(D, b, lane, 1)
     __threadfence_block();
     __syncthreads();
@@ -1147,7 +1309,7 @@ __global__ __launch_bounds__(64 * MAXW) void k_scouted_run(Dev D, uint16_t *leaf
         TopPatch tp;
         if (real) {
             P = prefetch_board(D, w, lane);
-            tp = expand_backup_phase<true>(D, w, lane, D.prior128, nullptr, P.m, P.half);
+            tp = expand_backup_phase<true>(D, w, lane, D.prior128, nullptr, P.m, P.half, P.sv);
             __threadfence_block();      // (k_step: the phases touch the same nodes from different lanes of the wave)
             __builtin_amdgcn_wave_barrier();
         }
@@ -1513,7 +1675,11 @@ __global__ __launch_bounds__(64) void k_finish_move(Dev D, const int32_t *forced
     const RootView rv = root_view(D, b);
     const int k = root_k(rv), nh = rv.half ^ 1; // every board moves to the other pool half (the host flips the word afterwards)
     const size_t baseNew = ((size_t)b * 2 + nh) * (size_t)D.cap;
-    if (lane == 0) { D.nodeA[baseNew] = NodeA{0, 0.0f, 1.0f, -1}; D.nodeB[baseNew] = 0u; } // whatever happens below, the new half holds a valid (empty) tree
+    // MCTS-solver (off: this one word read): a kept node's proof byte moves with its records; a fresh root is unproven
+    const SolverCfg sv = *D.sv_cfg;
+    const uint8_t *PO = sv.proof + ((size_t)b * 2 + rv.half) * (size_t)D.cap;
+    uint8_t *PN = sv.proof + baseNew;
+    if (lane == 0) { D.nodeA[baseNew] = NodeA{0, 0.0f, 1.0f, -1}; D.nodeB[baseNew] = 0u; if (sv.enabled) PN[0] = 0; } // whatever happens below, the new half holds a valid (empty) tree
     const int want = forced ? forced[b] : -1;
     // (k == 0 and no forced move: nothing searched, nothing to sample from)
     if (k > kMaxLegal || (k == 0 && want < 0) || want >= kNMoves) { if (lane == 0) set_err(D, 16); return; }
@@ -1638,7 +1804,11 @@ __global__ __launch_bounds__(64) void k_finish_move(Dev D, const int32_t *forced
     int n_new = 1;
     if (ci < 0) keep_tree = 0;
     if (keep_tree) {
-        if (lane == 0) { NA[0] = rv.A[CCZ_IDX(D, rv.root.fc + ci, D.cap)]; NB[0] = rv.Bn[CCZ_IDX(D, rv.root.fc + ci, D.cap)]; }
+        if (lane == 0) {
+            NA[0] = rv.A[CCZ_IDX(D, rv.root.fc + ci, D.cap)];
+            NB[0] = rv.Bn[CCZ_IDX(D, rv.root.fc + ci, D.cap)];
+            if (sv.enabled) PN[0] = PO[CCZ_IDX(D, rv.root.fc + ci, D.cap)];
+        }
         __syncthreads();
         int head = 0, pruned = 0;
         // The kept subtree may use the pool up to `budget`, leaving room for a whole move of new expansions.
@@ -1672,6 +1842,7 @@ __global__ __launch_bounds__(64) void k_finish_move(Dev D, const int32_t *forced
                 for (int j = lane; j < cn; j += 64) {
                     NA[CCZ_IDX(D, dd + j, D.cap)] = rv.A[CCZ_IDX(D, src + j, D.cap)];
                     NB[CCZ_IDX(D, dd + j, D.cap)] = rv.Bn[CCZ_IDX(D, src + j, D.cap)];
+                    if (sv.enabled) PN[CCZ_IDX(D, dd + j, D.cap)] = PO[CCZ_IDX(D, src + j, D.cap)];
                 }
             }
             const int nbatch = n_new - head < 64 ? n_new - head : 64;
@@ -1685,7 +1856,7 @@ __global__ __launch_bounds__(64) void k_finish_move(Dev D, const int32_t *forced
         }
     }
     if (!keep_tree || n_new == 0) {
-        if (lane == 0) { NA[0] = NodeA{0, 0.0f, 1.0f, -1}; NB[0] = 0u; }
+        if (lane == 0) { NA[0] = NodeA{0, 0.0f, 1.0f, -1}; NB[0] = 0u; if (sv.enabled) PN[0] = 0; }
         n_new = 1;
     }
 
@@ -2350,6 +2521,47 @@ __global__ void k_set_root_exploration(ExploreCfg *cfg, ExploreCfg v, uint32_t *
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) stamps[i] = 0u;
     if (i == 0) *cfg = v;
+}
+
+// ------------------------------------------------------------------ MCTS-solver: settings, inspection, the combine rule on its own
+// ccz_set_solver: the settings reach the device in stream order (the proof array is zeroed in front of this launch when it turns on)
+__global__ void k_set_solver(SolverCfg *cfg, SolverCfg v)
+{
+    if (blockIdx.x == 0 && threadIdx.x == 0) *cfg = v;
+}
+
+// ccz_root_proof: the proof byte of every root and of its children, split into state and distance; zeros while the solver is off
+__global__ __launch_bounds__(64) void k_root_proof(Dev D, uint8_t *state, uint8_t *dist, uint8_t *cstate, uint8_t *cdist)
+{
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const SolverCfg sv = *D.sv_cfg;
+    const RootView rv = root_view(D, b);
+    int k = root_k(rv) > kMaxLegal ? kMaxLegal : root_k(rv);
+    if (!sv.enabled) k = 0;
+    const uint8_t *proof = sv.proof + ((size_t)b * 2 + rv.half) * (size_t)D.cap;
+    if (lane == 0) {
+        const uint32_t p = sv.enabled ? proof[0] : 0u;
+        state[b] = (uint8_t)(p & 3u);
+        dist[b] = (uint8_t)(p >> 2);
+    }
+    for (int i = lane; i < kMaxLegal; i += 64) {
+        const uint32_t p = i < k ? proof[CCZ_IDX(D, rv.root.fc + i, D.cap)] : 0u;
+        cstate[(size_t)b * kMaxLegal + i] = (uint8_t)(p & 3u);
+        cdist[(size_t)b * kMaxLegal + i] = (uint8_t)(p >> 2);
+    }
+}
+
+// ccz_proof_combine: one wave per case, proof_combine on bytes[case][0 .. counts[case])
+__global__ __launch_bounds__(64) void k_proof_combine(const uint8_t *bytes, const int32_t *counts, int n, uint8_t *out)
+{
+    const int c = blockIdx.x, lane = threadIdx.x;
+    if (c >= n) return;
+    int nc = counts[c];
+    nc = nc < 0 ? 0 : (nc > kMaxLegal ? kMaxLegal : nc);
+    const uint8_t *row = bytes + (size_t)c * kMaxLegal;
+    const uint32_t p0 = lane < nc ? row[lane] : 0u, p1 = 64 + lane < nc ? row[64 + lane] : 0u;
+    const uint32_t r = proof_combine(p0, p1, nc, lane);
+    if (lane == 0) out[c] = (uint8_t)r;
 }
 
 // ------------------------------------------------------------------ stateless batch rules

@@ -447,6 +447,46 @@ class SelfPlayEngine:
         check(self.L.ccz_root_noise(self.h, self._stream(), _ptr(noise), _ptr(k)))
         return noise, k
 
+    # ------------------------------------------------------------------ MCTS-solver (include/cczero.h ccz_set_solver)
+    def set_solver(self, enabled: bool = True):
+        """Exact propagation of decided positions (Winands' MCTS-solver): a terminal leaf proves its node, a node with a lost child
+        is won, a node whose children are all won is lost, and the descent stops at a proven node (``LEAF_WIN`` / ``LEAF_LOSS`` /
+        ``LEAF_DRAW`` with k = 0: no move generation, no evaluator row). PUCT, N, Q and the move choice are untouched; a front-end
+        forces the proven move with :func:`proof_move`. The first call that turns it on allocates one byte per tree node and may
+        sync. Off (the state of a new engine): every output is what it is without the feature."""
+        with torch.cuda.device(self.device):
+            check(self.L.ccz_set_solver(self.h, self._stream(), 1 if enabled else 0))
+        self.solver = bool(enabled)
+
+    def root_proof(self) -> dict:
+        """Proof bytes at the top of every tree (``ccz_root_proof``; syncs): ``state`` / ``dist`` uint8 [B] of the root,
+        ``child_state`` / ``child_dist`` uint8 [B,128] aligned with ``root_children()['acts']`` (zero past k). States are
+        ``PROOF_WIN`` / ``PROOF_LOSS`` / ``PROOF_DRAW`` in the view of the side to move AT THAT NODE (0: unknown); ``dist``: plies
+        to the end, saturating at 63. All zeros while the solver is off."""
+        B = self.B
+        out = {"state": np.zeros(B, np.uint8), "dist": np.zeros(B, np.uint8),
+               "child_state": np.zeros((B, MAX_LEGAL), np.uint8), "child_dist": np.zeros((B, MAX_LEGAL), np.uint8)}
+        check(self.L.ccz_root_proof(self.h, self._stream(), _ptr(out["state"]), _ptr(out["dist"]), _ptr(out["child_state"]), _ptr(out["child_dist"])))
+        return out
+
+    def proof_moves(self) -> np.ndarray:
+        """int32 [B]: :func:`proof_move` of every board (-1: its root is not decided, or the solver is off) -- what a front-end hands
+        :meth:`finish_move` as ``forced_moves`` (-1 leaves the choice to the sampler). Syncs."""
+        rp, rc = self.root_proof(), self.root_children()
+        out = np.full(self.B, -1, np.int32)
+        for b in np.nonzero(rp["state"])[0]:
+            mv = proof_move(rp["state"][b], rp["dist"][b], rp["child_state"][b], rp["child_dist"][b], rc["acts"][b])
+            if mv is not None:
+                out[b] = mv
+        return out
+
+    def solver_stats(self) -> dict:
+        """Sums over boards (``ccz_solver_stats``; syncs): ``nodes_proven``, ``proven_stops`` (simulations whose descent ended at a
+        node proven earlier), ``roots_proven`` (searched boards whose root is proven now)."""
+        s = _lib.SolverStats()
+        check(self.L.ccz_get_solver_stats(self.h, self._stream(), C.byref(s)))
+        return {f: int(getattr(s, f)) for f, _ in _lib.SolverStats._fields_}
+
     def _to_dev(self, x, dtype, name):
         t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x, dtype={torch.int32: np.int32, torch.uint8: np.uint8}[dtype]))
         t = t.to(device=self.device, dtype=dtype).contiguous()
@@ -746,6 +786,57 @@ def expand_record_values(records: torch.Tensor, flags: int = 0, out=None, head_r
         check(L.ccz_expand_record_values(C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), _ptr(records), P, int(flags), ring,
                                          int(head_row) if ring else 0, _ptr(value)))
     return value
+
+
+# ---------------------------------------------------------------------- MCTS-solver helpers
+def proof_move(state, dist, child_state, child_dist, acts):
+    """The move a front-end should force on ONE board given :meth:`SelfPlayEngine.root_proof` (``state`` / ``dist`` of its root, the
+    children's rows) and ``root_children()['acts']``: under a WIN root the LOSS child with the smallest distance (the fastest mate;
+    the first in insertion order on ties), under a LOSS root the WIN child with the largest distance (the longest defence), else
+    None. ``child_state`` / ``child_dist`` / ``acts`` may be whole 128-entry rows: entries past the children have state 0."""
+    cs, cd = np.asarray(child_state, np.int64), np.asarray(child_dist, np.int64)
+    st = int(state)
+    if st == _lib.PROOF_WIN:
+        idx = np.nonzero(cs == _lib.PROOF_LOSS)[0]
+        if len(idx):
+            return int(acts[int(idx[int(np.argmin(cd[idx]))])])
+    elif st == _lib.PROOF_LOSS:
+        idx = np.nonzero(cs == _lib.PROOF_WIN)[0]
+        if len(idx):
+            return int(acts[int(idx[int(np.argmax(cd[idx]))])])
+    return None
+
+
+def mate_score(child_state, child_dist):
+    """``score mate N`` of a move whose child carries (``child_state``, ``child_dist``): N in moves, positive when the side that
+    plays the move mates, negative when it is mated; None for an unproven or drawn child. The child is LOSS in d plies: the mover
+    mates in (d + 1) plies; WIN in d: the mover is mated in d + 1."""
+    st, d = int(child_state), int(child_dist) + 1
+    if st == _lib.PROOF_LOSS:
+        return (d + 1) // 2
+    if st == _lib.PROOF_WIN:
+        return -((d + 1) // 2)
+    return None
+
+
+def proof_combine(cases, device: int = 0) -> np.ndarray:
+    """The solver's combine rule on the GPU (``ccz_proof_combine``, one wave per case): ``cases`` = lists of up to 128 proof bytes;
+    returns the byte of each case's parent, uint8 [n]."""
+    L = _lib.lib()
+    dev = torch.device("cuda", device)
+    n = len(cases)
+    rows = np.zeros((n, MAX_LEGAL), np.uint8)
+    counts = np.zeros(n, np.int32)
+    for i, c in enumerate(cases):
+        if len(c) > MAX_LEGAL:
+            raise ValueError("a node has at most 128 children")
+        rows[i, :len(c)] = np.asarray(c, np.uint8)
+        counts[i] = len(c)
+    d_rows, d_counts = torch.from_numpy(rows).to(dev), torch.from_numpy(counts).to(dev)
+    out = torch.zeros((n,), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        check(L.ccz_proof_combine(C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), _ptr(d_rows), _ptr(d_counts), n, _ptr(out)))
+    return out.cpu().numpy()
 
 
 # ---------------------------------------------------------------------- stateless batch rules

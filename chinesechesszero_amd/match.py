@@ -17,7 +17,9 @@ from .parameters import C_PUCT
 
 class BatchedMatch:
     def __init__(self, evaluator_red, evaluator_black, n_boards: int, n_playout: int = 400, c_puct: float = C_PUCT,
-                 seed: int = 0, device: int = 0, max_plies: int = 0, temp: float = 1e-3):
+                 seed: int = 0, device: int = 0, max_plies: int = 0, temp: float = 1e-3, solver: bool = False):
+        """``solver``: both sides search with the MCTS-solver (``engine.set_solver``) and play the proven move where the root is
+        decided (``engine.proof_moves``); every other move is drawn as without it."""
         self.ev = {1: evaluator_red, 0: evaluator_black}
         self.B = n_boards
         self.n_playout = n_playout
@@ -25,6 +27,10 @@ class BatchedMatch:
         # eps = 0: the sampling distribution is pi itself (mcts.py:227), drawn from the board's Philox stream
         self.engine = SelfPlayEngine(n_boards, n_playout=n_playout, c_puct=c_puct, eps=0.0, alpha=0.2, temp=temp,
                                      seed=seed, device=device, max_plies=max_plies, mirror=False)
+        self.solver = bool(solver)
+        self.proven_moves = 0
+        if self.solver:
+            self.engine.set_solver(True)
         self.before_move = self.on_move = None
         self._temps = np.full(n_boards, temp, np.float64)
 
@@ -43,7 +49,12 @@ class BatchedMatch:
                 e.expand_backup(prob, value)
         if self.before_move is not None:
             self.before_move(self)
-        moves = e.finish_move(temps=self._temps, keep_tree=False).cpu().numpy()
+        forced = None
+        if self.solver:
+            forced = e.proof_moves()
+            forced[e.game_status()["over"] != 0] = -1
+            self.proven_moves += int((forced >= 0).sum())
+        moves = e.finish_move(forced_moves=forced, temps=self._temps, keep_tree=False).cpu().numpy()
         if self.on_move is not None:
             self.on_move(self, moves)
         return moves

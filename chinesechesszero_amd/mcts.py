@@ -66,10 +66,14 @@ SCOUTS = 10  # scout slots of a one-game search (ScoutedSearch): 1 + 10 = 11 row
 
 
 class MCTS:
-    def __init__(self, policy_value_fn, c_puct=5, n_playout=10000, device: int = 0, seed: int = 0, scouts: int | None = None):
+    def __init__(self, policy_value_fn, c_puct=5, n_playout=10000, device: int = 0, seed: int = 0, scouts: int | None = None,
+                 solver: bool = False):
         """``scouts``: scout slots of the one-game search (``selfplay.ScoutedSearch``; same visit counts, fewer evaluator calls);
-        None = ``SCOUTS`` (env ``CCZ_SCOUTS``) when the evaluator is a batched one that returns logits, else 0."""
+        None = ``SCOUTS`` (env ``CCZ_SCOUTS``) when the evaluator is a batched one that returns logits, else 0. ``solver``: the
+        MCTS-solver (``SelfPlayEngine.set_solver``): decided positions are proven in the tree, :meth:`proof_move` names the move
+        a proven root asks for."""
         self.policy = policy_value_fn
+        self.solver = bool(solver)
         self.c_puct = c_puct
         self.n_playout = n_playout
         self.red_history = None
@@ -105,6 +109,8 @@ class MCTS:
                                           strict=True)   # the reference's tree and game are unbounded: a prune or an adjudication raises here
             if self.scouts:
                 self._engine.set_scouts(self.scouts)
+            if self.solver:
+                self._engine.set_solver(True)
         return self._engine
 
     def _forced(self, mid: int):
@@ -239,12 +245,29 @@ class MCTS:
         k = int(rc["k"][0])
         return {key: (val[0][:k] if val.ndim == 2 else val[0]) for key, val in rc.items()}
 
+    def root_proof(self):
+        """``SelfPlayEngine.root_proof`` of the game's board: ``state`` / ``dist`` of the root, ``child_state`` / ``child_dist`` [k]."""
+        e = self._ensure_engine()
+        k = int(e.root_children()["k"][0])
+        return {key: (val[0][:k] if val.ndim == 2 else val[0]) for key, val in e.root_proof().items()}
+
+    def proof_move(self):
+        """The move id a proven root asks for (``engine.proof_move``: the fastest mate, or the longest defence), or None."""
+        if not self.solver or self._engine is None:
+            return None
+        from .engine import proof_move
+        rp, rc = self._engine.root_proof(), self._engine.root_children()
+        return proof_move(rp["state"][0], rp["dist"][0], rp["child_state"][0], rp["child_dist"][0], rc["acts"][0])
+
 
 class MCTS_AI:
     """reference mcts.py:181-233"""
 
-    def __init__(self, policy_value_fn, c_puct=5, n_playout=2000, is_selfplay=False, device: int = 0, seed: int = 0, scouts: int | None = None):
-        self.mcts = MCTS(policy_value_fn, c_puct, n_playout, device=device, seed=seed, scouts=scouts)
+    def __init__(self, policy_value_fn, c_puct=5, n_playout=2000, is_selfplay=False, device: int = 0, seed: int = 0, scouts: int | None = None,
+                 solver: bool = False):
+        """``solver``: search with the MCTS-solver and play the proven move when the root is decided (the fastest mate, the longest
+        defence) instead of drawing from the visit counts."""
+        self.mcts = MCTS(policy_value_fn, c_puct, n_playout, device=device, seed=seed, scouts=scouts, solver=solver)
         self.is_selfplay = is_selfplay
         self.agent = "AI"
 
@@ -258,7 +281,11 @@ class MCTS_AI:
         move_probs = np.zeros(2086)
         acts, probs = self.mcts.get_move_probs(board, temp, on_playout=on_playout)
         move_probs[list(acts)] = probs
-        if self.is_selfplay:
+        proven = self.mcts.proof_move()
+        if proven is not None:
+            move = proven
+            self.mcts.update_with_move(move if self.is_selfplay else -1)
+        elif self.is_selfplay:
             # Dirichlet noise on the sampling distribution only (mcts.py:216-221)
             move = np.random.choice(acts, p=(1 - EPS) * probs + EPS * np.random.dirichlet(ALPHA * np.ones(len(probs))))
             self.mcts.update_with_move(move)

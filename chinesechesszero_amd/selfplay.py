@@ -217,8 +217,10 @@ class BatchedSelfPlay:
     def __init__(self, evaluator, n_boards: int, n_playout: int = 400, c_puct: float = C_PUCT, eps: float = EPS,
                  alpha: float = ALPHA, temp: float = 1.0, seed: int = 0, board_id_base: int = 0, device: int = 0,
                  sampling: str = "device", use_graph: bool = False, version_fn=None, playout_cap=None, resign=None,
-                 root_exploration=None, **engine_kw):
-        """``playout_cap`` = ``(n_fast, p_full)``: playout-cap randomisation -- every move of every board is a full search of
+                 root_exploration=None, solver: bool = False, **engine_kw):
+        """``solver``: search with the MCTS-solver (:meth:`SelfPlayEngine.set_solver`). Only the search changes: moves are sampled,
+        recorded and targeted as without it.
+        ``playout_cap`` = ``(n_fast, p_full)``: playout-cap randomisation -- every move of every board is a full search of
         ``n_playout`` simulations with probability ``p_full``, else a fast one of ``n_fast``; fast plies carry ``REC_FAST`` in their
         record header so that a trainer can keep them out of the policy loss (``engine.draw_budgets``). The loop still runs
         ``n_playout`` lockstep steps per move: a board that has used its budget selects nothing for the rest of them, and on the
@@ -261,6 +263,9 @@ class BatchedSelfPlay:
         if root_exploration is not None:
             self.root_exploration = dict(root_exploration)
             self.engine.set_root_exploration(**self.root_exploration)
+        self.solver = bool(solver)
+        if self.solver:
+            self.engine.set_solver(True)
         self.B = n_boards
         self.n_playout = n_playout
         self.sampling = sampling

@@ -3,7 +3,7 @@
 The reference's README (README.md:3) advertises "standard UCI protocol" but ships no loop; what it does
 use everywhere are UCI coordinate strings ("a0a1", tools.py:172-269). This is that missing loop:
 ``uci``, ``isready``, ``ucinewgame``, ``position startpos|fen <fen> [moves ...]``, ``go [nodes N]``,
-``setoption name Playouts|MultiPV value N``, ``d``, ``quit``. ``go`` reports one ``info depth .. multipv .. score cp .. nodes .. pv ..``
+``setoption name Playouts|MultiPV value N``, ``setoption name Solver value true|false`` (MCTS-solver: ``score mate N``), ``d``, ``quit``. ``go`` reports one ``info depth .. multipv .. score cp .. nodes .. pv ..``
 line per principal variation (``SelfPlayEngine.principal_variations``); ``cp`` is a display mapping of the first move's Q
 (``analyse.cp_of``). The search is ``MCTS_AI`` on the HIP engine (no CPU fallback).
 """
@@ -76,6 +76,7 @@ class UciLoop:
         self.board = None
         self.ai = None
         self.multipv = 1
+        self.solver = False
 
     def _say(self, s: str):
         print(s, file=self.out, flush=True)
@@ -85,21 +86,33 @@ class UciLoop:
         if self.policy_value_fn is None:
             from .net import PolicyValueNet
             self.policy_value_fn = PolicyValueNet(device=f"cuda:{self.device}").policy_value_fn
-        if self.ai is None or self.ai.mcts.n_playout != nodes:
-            self.ai = MCTS_AI(self.policy_value_fn, c_puct=C_PUCT, n_playout=nodes, is_selfplay=False, device=self.device)
+        if self.ai is None or self.ai.mcts.n_playout != nodes or self.ai.mcts.solver != self.solver:
+            self.ai = MCTS_AI(self.policy_value_fn, c_puct=C_PUCT, n_playout=nodes, is_selfplay=False, device=self.device, solver=self.solver)
         return self.ai
 
     def _say_pvs(self, ai):
         """One ``info depth <len> multipv <i> score cp <cp> nodes <root visits> pv <m1 m2 ...>`` line per principal variation of the
         search just finished (the tree is still on the engine: ``get_action`` only marks it for discarding)."""
         from .analyse import cp_of
+        from .engine import mate_score
         pv = ai.mcts._engine.principal_variations(multipv=self.multipv, max_len=32)
+        # Solver on: a line whose first move leads to a proven child says `score mate N` (N in moves, negative: the side to move is
+        # mated); the move a proven root asks for (bestmove follows it) leads line 1 when the most visited move is another one
+        mates, proven = {}, None
+        if self.solver:
+            rp, rc = ai.mcts.root_proof(), ai.mcts.root_children()
+            mates = {int(a): mate_score(rp["child_state"][i], rp["child_dist"][i]) for i, a in enumerate(rc["acts"])}
+            proven = ai.mcts.proof_move()
         for r in range(self.multipv):
             ln = int(pv["len"][0, r])
             if ln:
-                line = " ".join(Move.from_id(int(i)).uci() for i in pv["moves"][0, r, :ln])
-                self._say(f"info depth {ln} multipv {r + 1} score cp {cp_of(pv['q'][0, r], pv['visits'][0, r, 0])} "
-                          f"nodes {int(pv['root_visits'][0])} pv {line}")
+                ids = [int(i) for i in pv["moves"][0, r, :ln]]
+                if r == 0 and proven is not None and ids[0] != proven:
+                    ids = [proven]
+                mate = mates.get(ids[0])
+                score = f"mate {mate}" if mate is not None else f"cp {cp_of(pv['q'][0, r], pv['visits'][0, r, 0])}"
+                line = " ".join(Move.from_id(i).uci() for i in ids)
+                self._say(f"info depth {len(ids)} multipv {r + 1} score {score} nodes {int(pv['root_visits'][0])} pv {line}")
 
     def handle(self, line: str) -> bool:
         """Process one command line; returns False on quit."""
@@ -112,6 +125,7 @@ class UciLoop:
             self._say("id author cczero-mi355x builders")
             self._say(f"option name Playouts type spin default {self.n_playout} min 1 max 1000000")
             self._say("option name MultiPV type spin default 1 min 1 max 128")
+            self._say("option name Solver type check default false")
             self._say("uciok")
         elif cmd == "isready":
             self._say("readyok")
@@ -119,6 +133,8 @@ class UciLoop:
             self.n_playout = int(tok[4])
         elif cmd == "setoption" and len(tok) >= 5 and tok[1] == "name" and tok[2].lower() == "multipv":
             self.multipv = max(1, min(128, int(tok[4])))
+        elif cmd == "setoption" and len(tok) >= 5 and tok[1] == "name" and tok[2].lower() == "solver":
+            self.solver = tok[4].lower() == "true"
         elif cmd == "ucinewgame":
             self.board = Board()
             self.ai = None

@@ -88,6 +88,7 @@ extern "C" {
 #define CCZ_LEAF_DRAW 1   /* game over and is_tie(): leaf value 0.0   (mcts.py:120-122)   */
 #define CCZ_LEAF_LOSS 2   /* side to move has no legal move: leaf value -1.0 (mcts.py:123-126) */
 #define CCZ_LEAF_NONE 3   /* no pending leaf: board finished, simulation budget used up, leaf already backed up, or nothing selected yet */
+#define CCZ_LEAF_WIN 4    /* MCTS-solver only (ccz_set_solver): the descent ended at a node proven won for its side to move: leaf value +1.0 */
 
 typedef struct ccz_engine ccz_engine;
 
@@ -435,6 +436,41 @@ int ccz_get_exploration_stats(ccz_engine *e, void *stream, ccz_exploration_stats
 /* the noise of the move being searched (syncs; tests, diagnostics): noise_host float [B*128] = dir_i as the score used it, zero past
  * k; k_host int32 [B] = the root's child count the row was filled for, 0 on a board that has no row for its current move. */
 int ccz_root_noise(ccz_engine *e, void *stream, float *noise_host, int32_t *k_host);
+
+/* ---- MCTS-solver: exact propagation of decided positions through the tree (additive to ABI 8) ----
+ * One proof byte per tree node, in a device array of its own (uint8 [B][2][max_nodes], allocated and zeroed by the first
+ * ccz_set_solver(enabled = 1), which may sync; never touched while the solver is off). Bits 0..1: the state in the view of the side
+ * to move at the node -- 0 unknown, CCZ_PROOF_WIN, CCZ_PROOF_LOSS, CCZ_PROOF_DRAW --, bits 2..7: plies to the end, saturating at 63
+ * (0 for a draw).
+ *   combine(children of a node), in this order: a LOSS child -> WIN in 1 + the smallest such distance; else an unknown child ->
+ *     unknown; else a DRAW child -> DRAW; else (all WIN) -> LOSS in 1 + the largest distance.
+ *   backup: a simulation whose leaf is CCZ_LEAF_DRAW / CCZ_LEAF_LOSS / CCZ_LEAF_WIN sets the leaf's byte (rules-terminal: LOSS or
+ *     DRAW, distance 0; a node proven earlier keeps its byte) and walks up the path: parent <- combine(its children), until a byte
+ *     does not change. N and Q are backed up as without the solver (CCZ_LEAF_WIN: leaf value +1).
+ *   selection: PUCT and the first-maximum rule are unchanged; a chosen child at depth >= 1 whose state is not 0 ends the descent
+ *     there: status DRAW / LOSS / WIN by its state, k = 0, no move generation, no evaluator row. The root is never treated as
+ *     decided: a proven root keeps descending, and its visits converge on the proving move by themselves.
+ *   expansion zeroes the new children's bytes; the re-root of ccz_finish_move copies a kept node's byte with its records (the new
+ *     root's byte is the chosen child's); a fresh root (ccz_reset, ccz_reset_tree, keep_tree = 0, ccz_set_position[s]) is unknown.
+ * Off (the state of a new engine, and after ccz_set_solver(0)): every output of every call is what it is without the feature.
+ * ccz_set_solver(1) after ccz_set_solver(0) starts from an all-unknown array. Works with scout slots and in ccz_scouted_run.
+ * ccz_root_proof (syncs): state / distance of every root (uint8 [B]) and of its children (uint8 [B][128], aligned with
+ * ccz_root_children's acts; zero past k); all zeros while the solver is off. Any output may be NULL.
+ * ccz_get_solver_stats (syncs): sums over boards.
+ * ccz_proof_combine: the combine rule on its own, one wave per case: bytes_dev uint8 [n_cases][128], counts_dev int32 [n_cases]
+ * (0..128 children; 0 -> unknown), out_dev uint8 [n_cases]. Stateless, asynchronous. */
+#define CCZ_PROOF_WIN 1
+#define CCZ_PROOF_LOSS 2
+#define CCZ_PROOF_DRAW 3
+typedef struct ccz_solver_stats {
+    int64_t nodes_proven;  /* nodes whose byte left "unknown"                                        */
+    int64_t proven_stops;  /* simulations backed up whose descent ended at a node proven earlier     */
+    int64_t roots_proven;  /* searched boards whose root is proven now (a state, not a running sum) */
+} ccz_solver_stats;
+int ccz_set_solver(ccz_engine *e, void *stream, int32_t enabled);
+int ccz_root_proof(ccz_engine *e, void *stream, uint8_t *state_host, uint8_t *dist_host, uint8_t *child_state_host, uint8_t *child_dist_host);
+int ccz_get_solver_stats(ccz_engine *e, void *stream, ccz_solver_stats *out);
+int ccz_proof_combine(void *stream, const uint8_t *bytes_dev, const int32_t *counts_dev, int32_t n_cases, uint8_t *out_dev);
 
 /* ---- once per move ------------------------------------------------------------------------ */
 /* Replaces MCTS.get_move_probs' tail (mcts.py:162-166), MCTS_AI.get_action's choice
