@@ -27,7 +27,7 @@ REC_VALUE_OFF = 92  # float32 root value of a REC_VALUE ply (record bytes 92..95
 RESIGN_RESIGNED, RESIGN_PLAYON = 2, 4  # CCZ_RESIGN_*: resign_status state, bit 0 = the side that resigned / would have
 HEAD_POL_STRIDE, HEAD_VAL_STRIDE = 1536, 640  # CCZ_HEAD_*_STRIDE: fp16 elements per board of the head kernels' outputs
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 CONV_RELU, CONV_DESCENDING, CONV_FORCE_SMALL, CONV_FORCE_TILE, CONV_G16, CONV_G16_EDGE_TILES = 1, 2, 16, 32, 64, 128  # CCZ_CONV_* flag bits
 CONV_G16_ONE_LAUNCH = 512  # CCZ_CONV_G16_ONE_LAUNCH
 CONV_G16_QUAD = 1 << 16    # CCZ_CONV_G16_QUAD
@@ -126,10 +126,6 @@ PROTOTYPES = {
     "ccz_gather_priors_routed": (C.c_int, [_P, _P, _P, _P, C.c_int32, _P, _P]),
     "ccz_set_budgets": (C.c_int, [_P, _P, _P, _P]),
     "ccz_draw_budgets": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_double, _P]),
-    "ccz_expand_record_targets": (C.c_int, [_P, _P, C.c_int64, C.c_uint32, C.c_int64, C.c_int64, _P]),
-    "ccz_sample_record_targets": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, C.c_uint32, _P]),
-    "ccz_expand_record_values": (C.c_int, [_P, _P, C.c_int64, C.c_uint32, C.c_int64, C.c_int64, _P]),
-    "ccz_sample_record_values": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, C.c_uint32, _P]),
     "ccz_set_resign": (C.c_int, [_P, _P, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_double]),
     "ccz_get_resign_stats": (C.c_int, [_P, _P, C.POINTER(ResignStats)]),
     "ccz_resign_status": (C.c_int, [_P, _P, _P, _P, _P, _P]),
@@ -153,9 +149,9 @@ PROTOTYPES = {
     "ccz_harvest_rows": (C.c_int, [_P, _P, C.POINTER(C.c_int64)]),
     "ccz_harvest": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "ccz_harvest_records": (C.c_int, [_P, _P, _P, C.c_int64, C.POINTER(C.c_int64)]),
-    "ccz_expand_records": (C.c_int, [_P, _P, C.c_int64, C.c_uint32, _P, _P, _P, _P, C.c_int64, C.c_int64, _P]),
+    "ccz_expand_records": (C.c_int, [_P, _P, C.c_int64, C.c_uint32, _P, _P, _P, _P, C.c_int64, C.c_int64, _P, _P, _P]),
     "ccz_ring_retire": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int32, _P]),
-    "ccz_sample_records": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, C.c_uint32, _P, _P, _P, _P, _P]),
+    "ccz_sample_records": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, C.c_uint32, _P, _P, _P, _P, _P, _P, _P]),
     "ccz_get_stats": (C.c_int, [_P, _P, C.POINTER(Stats)]),
     "ccz_legal_moves": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P]),
     "ccz_apply_moves": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P]),

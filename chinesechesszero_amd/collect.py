@@ -297,7 +297,7 @@ class TupleSink:
             raise CczError(f"{self.out_dir}: {len(self._rshards)} record shard(s) ({sum(r[1] for r in self._rshards)} plies) wait for the GPU expander "
                            "(ccz_expand_records): run finalize() where the collector ran; nothing was changed")
         from ._lib import REC_FAST, REC_FLAGS, REC_VALUE
-        from .engine import expand_record_targets, expand_record_values, expand_records, game_aligned_chunks
+        from .engine import expand_records, game_aligned_chunks
         for path, plies, flags, pot in list(self._rshards):
             tag = os.path.basename(path)[len(".rshard_"):-len(".npy")]
             prefix = f".shard_r{tag}_"
@@ -308,10 +308,10 @@ class TupleSink:
             rec = torch.from_numpy(np.load(path)).cuda()
             for k, part in enumerate(game_aligned_chunks(rec, 1 << 14)):   # bounds the dense temporary (2^15 rows = 1 GB)
                 part = part.contiguous()
-                s, p, z = expand_records(part, flags, pot)
-                t = expand_record_targets(part, flags).cpu().numpy() if bool((part[:, REC_FLAGS] & REC_FAST).any()) else None
-                v = expand_record_values(part, flags).cpu().numpy() if bool((part[:, REC_FLAGS] & REC_VALUE).any()) else None
-                self._write_dense_shard(os.path.join(self.out_dir, f"{prefix}{k:04d}"), s.cpu().numpy(), p.cpu().numpy(), z.cpu().numpy(), t, v)
+                fast, valued = bool((part[:, REC_FLAGS] & REC_FAST).any()), bool((part[:, REC_FLAGS] & REC_VALUE).any())
+                rows = [x.cpu().numpy() for x in expand_records(part, flags, pot, targets=fast, values=valued)]
+                t, v = (rows[3] if fast else None), (rows[-1] if valued else None)
+                self._write_dense_shard(os.path.join(self.out_dir, f"{prefix}{k:04d}"), rows[0], rows[1], rows[2], t, v)
             os.remove(path)
             self._rshards.remove((path, plies, flags, pot))
 

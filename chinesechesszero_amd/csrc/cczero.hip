@@ -1155,23 +1155,47 @@ static int typepack_of(const char *who, const uint8_t *plane_of_type_host, uint3
     return 0;
 }
 
-int ccz_expand_records(void *stream, const void *records_dev, int64_t n_plies, uint32_t flags, const uint8_t *plane_of_type_host,
-                       void *states_f16_dev, float *pi_dev, float *z_dev, int64_t ring_rows, int64_t head_row, int32_t *bad_records_dev)
+// the argument checks of the two record -> row call families: what may be NULL is the caller's business, the rest is here
+static int check_expand_args(const char *who, const void *records_dev, int64_t n_plies, uint32_t flags, const void *states_f16_dev, const float *value_dev,
+                             int64_t ring_rows, int64_t head_row)
 {
-    if (n_plies < 0 || ring_rows < 0 || head_row < 0) return fail(-1, "ccz_expand_records: negative size");
-    if (n_plies == 0) return 0;
-    if (!records_dev || !states_f16_dev || !pi_dev || !z_dev) return fail(-1, "ccz_expand_records: null buffer");
-    if (((uintptr_t)records_dev | (uintptr_t)states_f16_dev) & 3) return fail(-1, "ccz_expand_records: buffers must be 4-byte aligned");
-    if (n_plies > (int64_t)INT32_MAX) return fail(-1, "ccz_expand_records: too many records for one launch");
+    if (!records_dev) return fail(-1, "%s: null buffer", who);
+    if (((uintptr_t)records_dev | (uintptr_t)states_f16_dev) & 3) return fail(-1, "%s: buffers must be 4-byte aligned", who);
+    if ((uintptr_t)value_dev & 3) return fail(-1, "%s: the values must be 4-byte aligned", who);
+    if (n_plies > (int64_t)INT32_MAX) return fail(-1, "%s: too many records for one launch", who);
     const int64_t rows = n_plies * ((flags & CCZ_FLAG_NO_MIRROR) ? 1 : 2);
-    if (ring_rows > 0 && rows > ring_rows) return fail(-1, "ccz_expand_records: %lld rows do not fit a ring of %lld", (long long)rows, (long long)ring_rows);
-    if (ring_rows == 0 && head_row != 0) return fail(-1, "ccz_expand_records: head_row needs ring_rows");
+    if (ring_rows > 0 && rows > ring_rows) return fail(-1, "%s: %lld rows do not fit a ring of %lld", who, (long long)rows, (long long)ring_rows);
+    if (ring_rows == 0 && head_row != 0) return fail(-1, "%s: head_row needs ring_rows", who);
+    return 0;
+}
+
+static int check_sample_args(const char *who, const void *ring_dev, const int64_t *window_dev, const int64_t *draws_dev, int64_t batch,
+                             const void *states_f16_dev, const float *pi_dev, const float *z_dev, const float *value_dev)
+{
+    if (!ring_dev || !window_dev || !draws_dev || !states_f16_dev || !pi_dev || !z_dev) return fail(-1, "%s: null buffer", who);
+    if (((uintptr_t)ring_dev | (uintptr_t)states_f16_dev) & 3) return fail(-1, "%s: buffers must be 4-byte aligned", who);
+    if ((uintptr_t)value_dev & 3) return fail(-1, "%s: the values must be 4-byte aligned", who);
+    if (((uintptr_t)window_dev | (uintptr_t)draws_dev) & 7) return fail(-1, "%s: window and draws must be 8-byte aligned", who);
+    if (batch > (int64_t)INT32_MAX) return fail(-1, "%s: too many rows for one launch", who);
+    return 0;
+}
+
+int ccz_expand_records(void *stream, const void *records_dev, int64_t n_plies, uint32_t flags, const uint8_t *plane_of_type_host,
+                       void *states_f16_dev, float *pi_dev, float *z_dev, int64_t ring_rows, int64_t head_row, int32_t *bad_records_dev,
+                       uint8_t *target_dev, float *value_dev)
+{
+    const char *who = "ccz_expand_records";
+    if (n_plies < 0 || ring_rows < 0 || head_row < 0) return fail(-1, "%s: negative size", who);
+    if (n_plies == 0) return 0;
+    const int dense = (states_f16_dev != nullptr) + (pi_dev != nullptr) + (z_dev != nullptr);
+    // all three dense outputs, or none of them and a side output: the side-only mode of k_expand_records
+    if (dense != 3 && !(dense == 0 && (target_dev || value_dev))) return fail(-1, "%s: null buffer", who);
+    if (const int rc = check_expand_args(who, records_dev, n_plies, flags, states_f16_dev, value_dev, ring_rows, head_row)) return rc;
     uint32_t typepack = 0;
-    const int rc = typepack_of("ccz_expand_records", plane_of_type_host, &typepack);
-    if (rc) return rc;
+    if (const int rc = typepack_of(who, plane_of_type_host, &typepack)) return rc;
     hipLaunchKernelGGL(k_expand_records, dim3((unsigned)n_plies), dim3(256), 0, (hipStream_t)stream, (const uint8_t *)records_dev, (long long)n_plies,
                        flags & (CCZ_FLAG_REFERENCE_QUIRKS | CCZ_FLAG_NO_MIRROR), typepack, (uint16_t *)states_f16_dev, pi_dev, z_dev,
-                       (long long)ring_rows, (long long)head_row, bad_records_dev);
+                       (long long)ring_rows, (long long)head_row, bad_records_dev, target_dev, value_dev);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1191,86 +1215,19 @@ int ccz_ring_retire(void *stream, const void *ring_dev, int64_t cap_plies, int64
 }
 
 int ccz_sample_records(void *stream, const void *ring_dev, int64_t cap_plies, const int64_t *window_dev, const int64_t *draws_dev, int64_t batch,
-                       uint32_t flags, const uint8_t *plane_of_type_host, void *states_f16_dev, float *pi_dev, float *z_dev, int32_t *bad_records_dev)
+                       uint32_t flags, const uint8_t *plane_of_type_host, void *states_f16_dev, float *pi_dev, float *z_dev, int32_t *bad_records_dev,
+                       uint8_t *target_dev, float *value_dev)
 {
-    if (cap_plies <= 0 || batch < 0) return fail(-1, "ccz_sample_records: capacity must be positive and batch non-negative");
+    const char *who = "ccz_sample_records";
+    if (cap_plies <= 0 || batch < 0) return fail(-1, "%s: capacity must be positive and batch non-negative", who);
     if (batch == 0) return 0;
-    if (!ring_dev || !window_dev || !draws_dev || !states_f16_dev || !pi_dev || !z_dev) return fail(-1, "ccz_sample_records: null buffer");
-    if (((uintptr_t)ring_dev | (uintptr_t)states_f16_dev) & 3) return fail(-1, "ccz_sample_records: buffers must be 4-byte aligned");
-    if (((uintptr_t)window_dev | (uintptr_t)draws_dev) & 7) return fail(-1, "ccz_sample_records: window and draws must be 8-byte aligned");
-    if (batch > (int64_t)INT32_MAX) return fail(-1, "ccz_sample_records: too many rows for one launch");
+    if (const int rc = check_sample_args(who, ring_dev, window_dev, draws_dev, batch, states_f16_dev, pi_dev, z_dev, value_dev)) return rc;
     uint32_t typepack = 0;
-    const int rc = typepack_of("ccz_sample_records", plane_of_type_host, &typepack);
-    if (rc) return rc;
+    if (const int rc = typepack_of(who, plane_of_type_host, &typepack)) return rc;
     hipLaunchKernelGGL(k_sample_records, dim3((unsigned)batch), dim3(256), 0, (hipStream_t)stream, (const uint8_t *)ring_dev, (long long)cap_plies,
                        (const long long *)window_dev, (const long long *)draws_dev, (long long)batch,
-                       flags & (CCZ_FLAG_REFERENCE_QUIRKS | CCZ_FLAG_NO_MIRROR), typepack, (uint16_t *)states_f16_dev, pi_dev, z_dev, bad_records_dev);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int ccz_expand_record_targets(void *stream, const void *records_dev, int64_t n_plies, uint32_t flags, int64_t ring_rows, int64_t head_row,
-                              uint8_t *target_dev)
-{
-    if (n_plies < 0 || ring_rows < 0 || head_row < 0) return fail(-1, "ccz_expand_record_targets: negative size");
-    if (n_plies == 0) return 0;
-    if (!records_dev || !target_dev) return fail(-1, "ccz_expand_record_targets: null buffer");
-    if (((uintptr_t)records_dev) & 3) return fail(-1, "ccz_expand_record_targets: the records must be 4-byte aligned");
-    if (n_plies > (int64_t)INT32_MAX) return fail(-1, "ccz_expand_record_targets: too many records for one launch");
-    const int64_t rows = n_plies * ((flags & CCZ_FLAG_NO_MIRROR) ? 1 : 2);
-    if (ring_rows > 0 && rows > ring_rows) return fail(-1, "ccz_expand_record_targets: %lld rows do not fit a ring of %lld", (long long)rows, (long long)ring_rows);
-    if (ring_rows == 0 && head_row != 0) return fail(-1, "ccz_expand_record_targets: head_row needs ring_rows");
-    hipLaunchKernelGGL(k_expand_record_targets, dim3((unsigned)((n_plies + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const uint8_t *)records_dev,
-                       (long long)n_plies, flags & CCZ_FLAG_NO_MIRROR, (long long)ring_rows, (long long)head_row, target_dev);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int ccz_sample_record_targets(void *stream, const void *ring_dev, int64_t cap_plies, const int64_t *window_dev, const int64_t *draws_dev,
-                              int64_t batch, uint32_t flags, uint8_t *target_dev)
-{
-    if (cap_plies <= 0 || batch < 0) return fail(-1, "ccz_sample_record_targets: capacity must be positive and batch non-negative");
-    if (batch == 0) return 0;
-    if (!ring_dev || !window_dev || !draws_dev || !target_dev) return fail(-1, "ccz_sample_record_targets: null buffer");
-    if (((uintptr_t)ring_dev) & 3) return fail(-1, "ccz_sample_record_targets: the ring must be 4-byte aligned");
-    if (((uintptr_t)window_dev | (uintptr_t)draws_dev) & 7) return fail(-1, "ccz_sample_record_targets: window and draws must be 8-byte aligned");
-    if (batch > (int64_t)INT32_MAX) return fail(-1, "ccz_sample_record_targets: too many rows for one launch");
-    hipLaunchKernelGGL(k_sample_record_targets, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const uint8_t *)ring_dev,
-                       (long long)cap_plies, (const long long *)window_dev, (const long long *)draws_dev, (long long)batch,
-                       flags & CCZ_FLAG_NO_MIRROR, target_dev);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int ccz_expand_record_values(void *stream, const void *records_dev, int64_t n_plies, uint32_t flags, int64_t ring_rows, int64_t head_row,
-                             float *value_dev)
-{
-    if (n_plies < 0 || ring_rows < 0 || head_row < 0) return fail(-1, "ccz_expand_record_values: negative size");
-    if (n_plies == 0) return 0;
-    if (!records_dev || !value_dev) return fail(-1, "ccz_expand_record_values: null buffer");
-    if (((uintptr_t)records_dev | (uintptr_t)value_dev) & 3) return fail(-1, "ccz_expand_record_values: the records and the values must be 4-byte aligned");
-    if (n_plies > (int64_t)INT32_MAX) return fail(-1, "ccz_expand_record_values: too many records for one launch");
-    const int64_t rows = n_plies * ((flags & CCZ_FLAG_NO_MIRROR) ? 1 : 2);
-    if (ring_rows > 0 && rows > ring_rows) return fail(-1, "ccz_expand_record_values: %lld rows do not fit a ring of %lld", (long long)rows, (long long)ring_rows);
-    if (ring_rows == 0 && head_row != 0) return fail(-1, "ccz_expand_record_values: head_row needs ring_rows");
-    hipLaunchKernelGGL(k_expand_record_values, dim3((unsigned)((n_plies + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const uint8_t *)records_dev,
-                       (long long)n_plies, flags & CCZ_FLAG_NO_MIRROR, (long long)ring_rows, (long long)head_row, value_dev);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int ccz_sample_record_values(void *stream, const void *ring_dev, int64_t cap_plies, const int64_t *window_dev, const int64_t *draws_dev,
-                             int64_t batch, uint32_t flags, float *value_dev)
-{
-    if (cap_plies <= 0 || batch < 0) return fail(-1, "ccz_sample_record_values: capacity must be positive and batch non-negative");
-    if (batch == 0) return 0;
-    if (!ring_dev || !window_dev || !draws_dev || !value_dev) return fail(-1, "ccz_sample_record_values: null buffer");
-    if (((uintptr_t)ring_dev | (uintptr_t)value_dev) & 3) return fail(-1, "ccz_sample_record_values: the ring and the values must be 4-byte aligned");
-    if (((uintptr_t)window_dev | (uintptr_t)draws_dev) & 7) return fail(-1, "ccz_sample_record_values: window and draws must be 8-byte aligned");
-    if (batch > (int64_t)INT32_MAX) return fail(-1, "ccz_sample_record_values: too many rows for one launch");
-    hipLaunchKernelGGL(k_sample_record_values, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const uint8_t *)ring_dev,
-                       (long long)cap_plies, (const long long *)window_dev, (const long long *)draws_dev, (long long)batch,
-                       flags & CCZ_FLAG_NO_MIRROR, value_dev);
+                       flags & (CCZ_FLAG_REFERENCE_QUIRKS | CCZ_FLAG_NO_MIRROR), typepack, (uint16_t *)states_f16_dev, pi_dev, z_dev, bad_records_dev,
+                       target_dev, value_dev);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -2093,9 +2093,76 @@ __global__ __launch_bounds__(64) void k_principal_variations(Dev D, int active, 
 // only a few dozen games end per move, so the plies of a game are spread over kHarvestSlices blocks (one 256-thread
 // block per game left the chip nearly empty: 1.8 ms for 28 k rows; the blocks of boards that are not harvested exit at once).
 constexpr int kHarvestSlices = 32;
+// One dense training row (game.py:213-237 z and history, collect.py:64-131 preprocess + flip_data): the 17 x 7 x 10 x 9 fp16
+// planes, the sparse -> dense pi scatter and z; pass 0 = the sample, pass 1 = its mirror image. The ONE place where a row is
+// formed: k_harvest, k_expand_records and k_sample_records all call it, so what they write is equal by construction. They
+// differ only in where a ply is read from, which `src` says (HarvestPly: the engine's arrays; RecordPly: a record and its
+// staged history): sq(i, s) = the piece on square s of the position i plies back (game.py:23-44), turn(), winner(), k(),
+// pi_id(i) (< 0: skip the entry) and pi_val(i). All 256 threads of the block call it together.
+template <class Src>
+__device__ __forceinline__ void form_row(const Src &src, int pass, int turn_plane, uint32_t typepack, uint16_t *states, float *pi, float *z,
+                                         long long row)
+{
+    const int tid = threadIdx.x;
+    uint32_t *srow = (uint32_t *)(states + (size_t)row * 10710);
+    for (int i = tid; i < 5355; i += 256) {
+        uint32_t v = 0;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int e = 2 * i + h;
+            const int g = e / 630, w = e - g * 630;
+            bool on;
+            if (g == 16) on = turn_plane != 0;
+            else {
+                const int ch = w / 90, s = w - 90 * ch;
+                const int ss = pass ? (s - s % 9) + (8 - s % 9) : s; // np.flip(axis=2): file mirror
+                on = src.sq(g & 7, ss) == (int)((typepack >> (3 * ch)) & 7u) + 1 + (g >= 8 ? 8 : 0);
+            }
+            if (on) v |= (uint32_t)kHalfOne << (16 * h);
+        }
+        srow[i] = v;
+    }
+    float *prow = pi + (size_t)row * kNMoves;
+    for (int i = tid; i < kNMoves; i += 256) prow[i] = 0.0f;
+    __syncthreads();
+    const int k = src.k();
+    for (int i = tid; i < k; i += 256) {
+        const int id = src.pi_id(i);
+        if (id >= 0) prow[pass ? c_tab.flip[id] : id] = src.pi_val(i); // mcts_prob[flip_map]
+    }
+    if (tid == 0) { // game.py:213-219
+        const int8_t w = src.winner();
+        z[row] = w < 0 ? 0.0f : (src.turn() == (uint8_t)w ? 1.0f : -1.0f);
+    }
+    __syncthreads();
+}
+
+// ply t of board b's finished game, where k_harvest reads it: D.rec_sq / rec_turn / rec_k / rec_off / rec_ids / rec_pi in global memory
+struct HarvestPly {
+    const Dev &D;
+    const BoardMeta &m;
+    int b, te; // te: the ply whose history the row shows
+    size_t r;
+    const uint8_t *rsq; // the board's recorded positions
+    __device__ __forceinline__ int sq(int back, int ss) const
+    {
+        int tp = te - back;
+        if (tp < 0) tp = 0;
+        return rsq[(size_t)CCZ_IDX(D, tp, D.max_plies) * 96 + CCZ_IDX(D, ss, 90)];
+    }
+    __device__ __forceinline__ uint8_t turn() const { return D.rec_turn[r]; }
+    __device__ __forceinline__ int8_t winner() const { return m.winner; }
+    __device__ __forceinline__ int k() const { return D.rec_k[r]; }
+    __device__ __forceinline__ int pi_id(int i) const
+    {
+        return (int)CCZ_IDX(D, D.rec_ids[(size_t)b * D.pi_cap + CCZ_IDX(D, D.rec_off[r] + (uint32_t)i, D.pi_cap)], kNMoves);
+    }
+    __device__ __forceinline__ float pi_val(int i) const { return D.rec_pi[(size_t)b * D.pi_cap + D.rec_off[r] + i]; }
+};
+
 __global__ __launch_bounds__(256) void k_harvest(Dev D, const long long *row_base, uint16_t *states, float *pi, float *z)
 {
-    const int b = blockIdx.x, tid = threadIdx.x;
+    const int b = blockIdx.x;
     const long long rb = row_base[b];
     if (rb < 0) return;
     const BoardMeta m = D.meta[b];
@@ -2103,46 +2170,10 @@ __global__ __launch_bounds__(256) void k_harvest(Dev D, const long long *row_bas
     const bool quirks = (D.flags & 1u) != 0, mirror = (D.flags & 2u) == 0;
     const uint8_t *rsq = D.rec_sq + (size_t)b * D.max_plies * 96;
     for (int t = blockIdx.y; t < T; t += gridDim.y) {
-        const size_t r = (size_t)b * D.max_plies + t;
-        // game.py:23-44: index i of the 8-deep history holds the position i plies back (start position
-        // before that); reference quirk: every sample aliases the history at the LAST recorded ply
-        const int te = quirks ? T - 1 : t;
-        const int turn_plane = quirks ? 1 : D.rec_turn[r]; // collect.py:78 reads a board that never advances
-        for (int pass = 0; pass < (mirror ? 2 : 1); ++pass) {
-            const long long row = rb + (pass ? T : 0) + t;
-            uint32_t *srow = (uint32_t *)(states + (size_t)row * 10710);
-            for (int i = tid; i < 5355; i += 256) {
-                uint32_t v = 0;
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const int e = 2 * i + h;
-                    const int g = e / 630, w = e - g * 630;
-                    bool on;
-                    if (g == 16) on = turn_plane != 0;
-                    else {
-                        const int ch = w / 90, s = w - 90 * ch;
-                        const int ss = pass ? (s - s % 9) + (8 - s % 9) : s; // np.flip(axis=2): file mirror
-                        int tp = te - (g & 7);
-                        if (tp < 0) tp = 0;
-                        on = rsq[(size_t)CCZ_IDX(D, tp, D.max_plies) * 96 + CCZ_IDX(D, ss, 90)] == type_in_plane(D, ch) + (g >= 8 ? 8 : 0);
-                    }
-                    if (on) v |= (uint32_t)kHalfOne << (16 * h);
-                }
-                srow[i] = v;
-            }
-            float *prow = pi + (size_t)row * kNMoves;
-            for (int i = tid; i < kNMoves; i += 256) prow[i] = 0.0f;
-            __syncthreads();
-            const int k = D.rec_k[r];
-            const size_t po = (size_t)b * D.pi_cap + D.rec_off[r];
-            for (int i = tid; i < k; i += 256) {
-                const int id = (int)CCZ_IDX(D, D.rec_ids[(size_t)b * D.pi_cap + CCZ_IDX(D, D.rec_off[r] + (uint32_t)i, D.pi_cap)], kNMoves);
-                prow[pass ? c_tab.flip[id] : id] = D.rec_pi[po + i]; // mcts_prob[flip_map]
-            }
-            if (tid == 0) // game.py:213-219
-                z[row] = m.winner < 0 ? 0.0f : (D.rec_turn[r] == (uint8_t)m.winner ? 1.0f : -1.0f);
-            __syncthreads();
-        }
+        // reference quirk: every sample aliases the history at the LAST recorded ply
+        const HarvestPly src{D, m, b, quirks ? T - 1 : t, (size_t)b * D.max_plies + t, rsq};
+        const int turn_plane = quirks ? 1 : src.turn(); // collect.py:78 reads a board that never advances
+        for (int pass = 0; pass < (mirror ? 2 : 1); ++pass) form_row(src, pass, turn_plane, D.typepack, states, pi, z, rb + (pass ? T : 0) + t);
     }
 }
 
@@ -2201,83 +2232,109 @@ __global__ __launch_bounds__(256) void k_harvest_records(Dev D, const long long 
     }
 }
 
-// One dense training row of a ply record: pass 0 = the sample, pass 1 = its mirror image. `hist` = the 8-deep history of
-// game.py:23-44 (index i = the position i plies back, the first one before that), in LDS; `rec` = the ply's own record.
-// The ONE place where a record becomes a row: k_expand_records (the exchange) and k_sample_records (the record ring)
-// both call it, so what they write is equal by construction. All 256 threads of the block call it together.
-__device__ __forceinline__ void record_to_row(const uint8_t (*hist)[96], const uint8_t *rec, const PlyHeader &h, int pass, int turn_plane,
-                                              uint32_t typepack, uint16_t *states, float *pi, float *z, long long row, int tid)
+// the policy-target byte of a ply (0: a fast move of playout-cap randomisation) and its root value (NaN: the record carries none)
+__device__ __forceinline__ uint8_t rec_target(const PlyHeader &h) { return (h.flags & kRecFast) ? 0 : 1; }
+__device__ __forceinline__ float rec_value(const uint8_t *rec, const PlyHeader &h)
 {
-    uint32_t *srow = (uint32_t *)(states + (size_t)row * 10710);
-    for (int i = tid; i < 5355; i += 256) {
-        uint32_t v = 0;
-#pragma unroll
-        for (int hh = 0; hh < 2; ++hh) {
-            const int e = 2 * i + hh;
-            const int g = e / 630, w = e - g * 630;
-            bool on;
-            if (g == 16) on = turn_plane != 0;
-            else {
-                const int ch = w / 90, s = w - 90 * ch;
-                const int ss = pass ? (s - s % 9) + (8 - s % 9) : s; // np.flip(axis=2): file mirror
-                on = hist[g & 7][ss] == (int)((typepack >> (3 * ch)) & 7u) + 1 + (g >= 8 ? 8 : 0);
-            }
-            if (on) v |= (uint32_t)kHalfOne << (16 * hh);
-        }
-        srow[i] = v;
+    return (h.flags & kRecValue) ? *(const float *)(rec + kRecValueOff) : __builtin_nanf("");
+}
+// the side outputs of one row (either may be null), written by one thread next to z
+__device__ __forceinline__ void write_side(uint8_t *target, float *value, long long row, uint8_t tg, float v)
+{
+    if (target) target[row] = tg;
+    if (value) value[row] = v;
+}
+
+// a ply where the record kernels read it: its own record and the 8-deep history stage_history put into LDS
+struct RecordPly {
+    const uint8_t (*hist)[96];
+    const uint8_t *rec;
+    const PlyHeader &h;
+    __device__ __forceinline__ int sq(int back, int ss) const { return hist[back][ss]; }
+    __device__ __forceinline__ uint8_t turn() const { return h.turn; }
+    __device__ __forceinline__ int8_t winner() const { return h.winner; }
+    __device__ __forceinline__ int k() const { return h.k; }
+    __device__ __forceinline__ int pi_id(int i) const
+    {
+        const int id = ((const uint16_t *)(rec + kRecIds))[i];
+        return id < kNMoves ? id : -1;
     }
-    float *prow = pi + (size_t)row * kNMoves;
-    for (int i = tid; i < kNMoves; i += 256) prow[i] = 0.0f;
-    __syncthreads();
-    const uint16_t *ids = (const uint16_t *)(rec + kRecIds);
-    const float *pv = (const float *)(rec + kRecPi);
-    for (int i = tid; i < h.k; i += 256) {
-        const int id = ids[i];
-        if (id < kNMoves) prow[pass ? c_tab.flip[id] : id] = pv[i]; // mcts_prob[flip_map]
+    __device__ __forceinline__ float pi_val(int i) const { return ((const float *)(rec + kRecPi))[i]; }
+};
+
+// The 8-deep history of game.py:23-44 of ply h.t of the game whose first record is record `first`: index i = the position i
+// plies back, the first one before that (game.py:234-237, quirk mode: every sample aliases the history at the LAST recorded
+// ply). slot_of(record index) = where that record lies in `recs`. Ends with a barrier: all 256 threads call it together.
+template <class SlotOf>
+__device__ __forceinline__ void stage_history(uint8_t (*hist)[96], const uint8_t *recs, long long first, const PlyHeader &h, bool quirks, SlotOf slot_of)
+{
+    const int tid = threadIdx.x, te = quirks ? h.T - 1 : h.t;
+    if (tid < 192) {
+        const int i = tid / 24, w = tid - 24 * i;
+        int tp = te - i;
+        if (tp < 0) tp = 0;
+        ((uint32_t *)hist[i])[w] = ((const uint32_t *)(recs + (size_t)slot_of(first + tp) * kRecBytes))[w];
     }
-    if (tid == 0) z[row] = h.winner < 0 ? 0.0f : (h.turn == (uint8_t)h.winner ? 1.0f : -1.0f); // game.py:213-219
     __syncthreads();
 }
 
-// Records -> dense training rows, exactly what k_harvest writes for the same games (game.py:213-237 z and history,
-// collect.py:64-131 preprocess + flip_data). One block per ply record; rows go to a ring of ring_rows rows starting at
-// row `head` (head = 0 and ring_rows >= rows: a plain array). flags: CCZ_FLAG_REFERENCE_QUIRKS / CCZ_FLAG_NO_MIRROR;
-// typepack: 3 bits per plane channel = piece type - 1 encoded there (ccz_config.plane_of_type inverted).
+// Record p of a buffer of n_plies records, as k_expand_records sees it: its header, the first record of its game, whether the
+// game is whole in the buffer, and row(q), q < mul: the dense row of pass q -- for a record whose game is cut, the q-th of the
+// rows it would have stood for in a buffer of whole games, (head + mul * p + q) % ring_rows: exactly the rows the whole games
+// leave out.
+struct ExpandPly {
+    PlyHeader h;
+    long long p, first, mul, ring_rows, head;
+    bool whole; // else nothing of the game may be read: its records may lie outside the buffer
+    __device__ __forceinline__ long long row(int q) const
+    {
+        const long long i = head + (whole ? mul * first + (q ? h.T : 0) + h.t : mul * p + q);
+        return ring_rows > 0 ? i % ring_rows : i;
+    }
+};
+__device__ __forceinline__ ExpandPly locate_expand_ply(const uint8_t *recs, long long p, long long n_plies, uint32_t flags, long long ring_rows,
+                                                       long long head)
+{
+    ExpandPly e;
+    e.h = *(const PlyHeader *)(recs + (size_t)p * kRecBytes + kRecHdr);
+    e.p = p;
+    e.first = p - e.h.t;
+    e.mul = (flags & 2u) ? 1 : 2;
+    e.ring_rows = ring_rows;
+    e.head = head;
+    e.whole = !(e.first < 0 || e.h.t >= e.h.T || e.first + e.h.T > n_plies || e.h.k > kMaxLegal);
+    return e;
+}
+
+// Records -> dense training rows, exactly what k_harvest writes for the same games (form_row). One block per ply record; rows
+// go to a ring of ring_rows rows starting at row `head` (head = 0 and ring_rows >= rows: a plain array). flags:
+// CCZ_FLAG_REFERENCE_QUIRKS / CCZ_FLAG_NO_MIRROR; typepack: 3 bits per plane channel = piece type - 1 encoded there
+// (ccz_config.plane_of_type inverted). target / value (either may be null): the policy-target byte and the root value of every
+// row, the mirror row carrying its ply's; the rows a cut game leaves unwritten get 0 / NaN, and the record counts in *bad.
+// Side-only mode: states == nullptr (then pi and z are null too) stages no history and forms no row; only target / value are
+// written. It serves callers that want the side outputs alone and is no faster than it looks: one thread per block works.
 __global__ __launch_bounds__(256) void k_expand_records(const uint8_t *recs, long long n_plies, uint32_t flags, uint32_t typepack,
                                                           uint16_t *states, float *pi, float *z, long long ring_rows, long long head,
-                                                          int32_t *bad)
+                                                          int32_t *bad, uint8_t *target, float *value)
 {
     const long long p = blockIdx.x;
     const int tid = threadIdx.x;
     if (p >= n_plies) return;
     __shared__ __align__(16) uint8_t hist[8][96];
-    __shared__ PlyHeader sh;
     const uint8_t *rec = recs + (size_t)p * kRecBytes;
-    if (tid == 0) sh = *(const PlyHeader *)(rec + kRecHdr);
-    __syncthreads();
-    const PlyHeader h = sh;
-    const bool quirks = (flags & 1u) != 0, mirror = (flags & 2u) == 0;
-    const int t = h.t, T = h.T;
-    const long long first = p - t;
-    if (first < 0 || t >= T || first + T > n_plies || h.k > kMaxLegal) { // not a whole game in this buffer: nothing is read out of bounds
-        if (tid == 0 && bad) atomicAdd(bad, 1);
-        return;
+    const ExpandPly e = locate_expand_ply(recs, p, n_plies, flags, ring_rows, head);
+    const int passes = (int)e.mul;
+    const long long row[2] = {e.row(0), e.row(passes - 1)};
+    if (tid == 0) {
+        if (!e.whole && bad) atomicAdd(bad, 1);
+        for (int q = 0; q < passes; ++q) write_side(target, value, row[q], e.whole ? rec_target(e.h) : 0, e.whole ? rec_value(rec, e.h) : __builtin_nanf(""));
     }
-    const int te = quirks ? T - 1 : t; // game.py:234-237: every sample aliases the history at the LAST recorded ply
-    if (tid < 192) { // the 8-deep history of game.py:23-44: index i = the position i plies back, the first one before that
-        const int i = tid / 24, w = tid - 24 * i;
-        int tp = te - i;
-        if (tp < 0) tp = 0;
-        ((uint32_t *)hist[i])[w] = ((const uint32_t *)(recs + (size_t)(first + tp) * kRecBytes))[w];
-    }
-    __syncthreads();
-    const int turn_plane = quirks ? 1 : h.turn; // collect.py:78 reads a board that never advances
-    const long long mul = mirror ? 2 : 1;
-    for (int pass = 0; pass < (mirror ? 2 : 1); ++pass) {
-        long long row = head + mul * first + (pass ? T : 0) + t;
-        row = ring_rows > 0 ? row % ring_rows : row;
-        record_to_row(hist, rec, h, pass, turn_plane, typepack, states, pi, z, row, tid);
-    }
+    if (!e.whole || !states) return;
+    const bool quirks = (flags & 1u) != 0;
+    stage_history(hist, recs, e.first, e.h, quirks, [](long long q) { return q; });
+    const RecordPly src{hist, rec, e.h};
+    const int turn_plane = quirks ? 1 : e.h.turn; // collect.py:78 reads a board that never advances
+    for (int pass = 0; pass < passes; ++pass) form_row(src, pass, turn_plane, typepack, states, pi, z, row[pass]);
 }
 
 // ------------------------------------------------------------------ the replay ring of compact records
@@ -2287,7 +2344,7 @@ __global__ __launch_bounds__(256) void k_expand_records(const uint8_t *recs, lon
 // counter % cap_plies; [tail, head) holds whole games only (k_ring_retire), so a game may wrap around the physical end
 // of the ring but is never cut by it.
 #ifdef CCZ_BOUNDS
-// the stateless ring kernels have no Dev: a stray index adds 65536 to *bad (tests ask for bad == 0) and goes to element 0
+// the stateless ring kernels have no Dev: a stray index adds 65536 to the launch's *bad (tests ask for bad == 0) and goes to element 0
 __device__ __forceinline__ long long ring_checked(int32_t *bad, long long i, long long n)
 {
     if (i < 0 || i >= n) { if (bad) atomicAdd(bad, 65536); return 0; }
@@ -2298,62 +2355,60 @@ __device__ __forceinline__ long long ring_checked(int32_t *bad, long long i, lon
 #define CCZ_RING_IDX(bad_, i_, n_) (i_)
 #endif
 
-// One block per drawn row. draw u -> r = u % live (live = (head - tail) * mul rows, mul = 1 without mirror images),
-// ply p = tail + r / mul, pass = r % mul; output row blockIdx.x gets exactly the bytes k_expand_records writes for that
-// ply and pass. A record that is not part of a whole game inside the window (or an empty window, or a negative draw)
-// counts in *bad and its row is zeros; nothing outside the ring is read. HBM-write-bound: 29.8 KB out, <= 1.6 KB in.
+// Draw u of a window {tail, head}, as k_sample_records sees it: r = u % live (live = (head - tail) * mul rows, mul = 1 without
+// mirror images), ply p = tail + r / mul, pass = r % mul. ok: the window and the draw are sane and the record is part of a
+// whole game inside the window; else nothing more may be read. Nothing outside the ring is read either way.
+struct SampledPly {
+    bool ok;
+    long long p, first;
+    int pass;
+    const uint8_t *rec;
+    PlyHeader h;
+};
+__device__ __forceinline__ SampledPly locate_sampled_ply(const uint8_t *ring, long long cap_plies, const long long *window, long long u, long long mul,
+                                                         int32_t *bad)
+{
+    SampledPly s = {};
+    const long long tail = window[0], head = window[1];
+    if (!(tail >= 0 && head > tail && head - tail <= cap_plies && u >= 0)) return s;
+    const long long r = u % ((head - tail) * mul);
+    s.p = tail + r / mul;
+    s.pass = (int)(r % mul);
+    s.rec = ring + (size_t)CCZ_RING_IDX(bad, s.p % cap_plies, cap_plies) * kRecBytes;
+    s.h = *(const PlyHeader *)(s.rec + kRecHdr);
+    s.first = s.p - s.h.t;
+    s.ok = s.h.t < s.h.T && s.h.k <= kMaxLegal && s.first >= tail && s.first + s.h.T <= head; // a whole game inside the window
+    return s;
+}
+
+// One block per drawn row (locate_sampled_ply): output row blockIdx.x gets exactly the bytes k_expand_records writes for that
+// ply and pass (form_row), and in target / value (either may be null) the ply's policy-target byte and root value. A bad draw
+// counts in *bad and its row is zeros, 0 and NaN. HBM-write-bound: 29.8 KB out, <= 1.6 KB in.
 __global__ __launch_bounds__(256) void k_sample_records(const uint8_t *ring, long long cap_plies, const long long *window, const long long *draws,
                                                           long long batch, uint32_t flags, uint32_t typepack, uint16_t *states, float *pi,
-                                                          float *z, int32_t *bad)
+                                                          float *z, int32_t *bad, uint8_t *target, float *value)
 {
     const long long j = blockIdx.x;
     const int tid = threadIdx.x;
     if (j >= batch) return;
     __shared__ __align__(16) uint8_t hist[8][96];
-    __shared__ PlyHeader sh;
     const bool quirks = (flags & 1u) != 0;
-    const long long mul = (flags & 2u) ? 1 : 2;
-    const long long tail = window[0], head = window[1], u = draws[j];
-    bool ok = tail >= 0 && head > tail && head - tail <= cap_plies && u >= 0; // (block-uniform: every thread reads the same words)
-    long long p = 0;
-    int pass = 0;
-    const uint8_t *rec = ring;
-    if (ok) {
-        const long long r = u % ((head - tail) * mul);
-        p = tail + r / mul;
-        pass = (int)(r % mul);
-        rec = ring + (size_t)CCZ_RING_IDX(bad, p % cap_plies, cap_plies) * kRecBytes;
-        if (tid == 0) sh = *(const PlyHeader *)(rec + kRecHdr);
-    }
-    __syncthreads();
-    PlyHeader h = {};
-    long long first = 0;
-    if (ok) {
-        h = sh;
-        first = p - h.t;
-        ok = h.t < h.T && h.k <= kMaxLegal && first >= tail && first + h.T <= head; // a whole game inside the window
-    }
-    if (!ok) {
+    const SampledPly s = locate_sampled_ply(ring, cap_plies, window, draws[j], (flags & 2u) ? 1 : 2, bad); // (block-uniform)
+    if (!s.ok) {
         uint32_t *srow = (uint32_t *)(states + (size_t)j * 10710);
         for (int i = tid; i < 5355; i += 256) srow[i] = 0u;
         for (int i = tid; i < kNMoves; i += 256) pi[(size_t)j * kNMoves + i] = 0.0f;
         if (tid == 0) {
             z[j] = 0.0f;
+            write_side(target, value, j, 0, __builtin_nanf(""));
             if (bad) atomicAdd(bad, 1);
         }
         return;
     }
-    const int t = h.t, T = h.T;
-    const int te = quirks ? T - 1 : t; // game.py:234-237: every sample aliases the history at the LAST recorded ply
-    if (tid < 192) { // the 8-deep history of game.py:23-44; the game may wrap around the physical end of the ring
-        const int i = tid / 24, w = tid - 24 * i;
-        int tp = te - i;
-        if (tp < 0) tp = 0;
-        const long long slot = CCZ_RING_IDX(bad, (first + tp) % cap_plies, cap_plies);
-        ((uint32_t *)hist[i])[w] = ((const uint32_t *)(ring + (size_t)slot * kRecBytes))[w];
-    }
-    __syncthreads();
-    record_to_row(hist, rec, h, pass, quirks ? 1 : h.turn, typepack, states, pi, z, j, tid);
+    // the game may wrap around the physical end of the ring
+    stage_history(hist, ring, s.first, s.h, quirks, [&](long long q) { return CCZ_RING_IDX(bad, q % cap_plies, cap_plies); });
+    form_row(RecordPly{hist, s.rec, s.h}, s.pass, quirks ? 1 : s.h.turn, typepack, states, pi, z, j);
+    if (tid == 0) write_side(target, value, j, rec_target(s.h), rec_value(s.rec, s.h));
 }
 
 // After an append of logical plies [head_old, head_new) has been copied into the ring (it overwrote the slots of
@@ -2414,99 +2469,6 @@ __global__ void k_draw_budgets(Dev D, int n, int n_full, int n_fast, double p_fu
     D.budget[b] = v;
     D.target[b] = full ? 1 : 0;
     if (budgets_out) budgets_out[b] = v;
-}
-
-// The policy-target byte of every dense row k_expand_records writes (same row indexing, same validity rule): the sample and its
-// mirror image carry their ply's flag. A record whose game is cut writes no row there; the rows it would have stood for in a
-// buffer of whole games -- (head + mul * p + q) % ring_rows, q < mul: exactly the rows the whole games leave out -- get 0.
-__global__ void k_expand_record_targets(const uint8_t *recs, long long n_plies, uint32_t flags, long long ring_rows, long long head,
-                                        uint8_t *target)
-{
-    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n_plies) return;
-    const PlyHeader h = *(const PlyHeader *)(recs + (size_t)p * kRecBytes + kRecHdr);
-    const long long mul = (flags & 2u) ? 1 : 2;
-    const int t = h.t, T = h.T;
-    const long long first = p - t;
-    if (first < 0 || t >= T || first + T > n_plies || h.k > kMaxLegal) {
-        for (long long q = 0; q < mul; ++q) {
-            const long long row = head + mul * p + q;
-            target[ring_rows > 0 ? row % ring_rows : row] = 0;
-        }
-        return;
-    }
-    const uint8_t v = (h.flags & kRecFast) ? 0 : 1;
-    for (long long pass = 0; pass < mul; ++pass) {
-        const long long row = head + mul * first + (pass ? T : 0) + t;
-        target[ring_rows > 0 ? row % ring_rows : row] = v;
-    }
-}
-
-// The policy-target byte of every row k_sample_records forms (same draw -> ply map, same validity rule): 0 for a bad draw.
-__global__ void k_sample_record_targets(const uint8_t *ring, long long cap_plies, const long long *window, const long long *draws,
-                                        long long batch, uint32_t flags, uint8_t *target)
-{
-    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= batch) return;
-    const long long mul = (flags & 2u) ? 1 : 2;
-    const long long tail = window[0], head = window[1], u = draws[j];
-    uint8_t v = 0;
-    if (tail >= 0 && head > tail && head - tail <= cap_plies && u >= 0) {
-        const long long p = tail + (u % ((head - tail) * mul)) / mul;
-        // (the entry point has no bad-record counter: a bounds-checked build sends a stray slot to element 0 without counting it)
-        const PlyHeader h = *(const PlyHeader *)(ring + (size_t)CCZ_RING_IDX((int32_t *)nullptr, p % cap_plies, cap_plies) * kRecBytes + kRecHdr);
-        const long long first = p - h.t;
-        if (h.t < h.T && h.k <= kMaxLegal && first >= tail && first + h.T <= head) v = (h.flags & kRecFast) ? 0 : 1;
-    }
-    target[j] = v;
-}
-
-// The root value of every dense row k_expand_records writes (k_expand_record_targets' row indexing and validity rule): the sample
-// and its mirror image carry their ply's value -- a position and its mirror image have the same value. NaN where there is none:
-// a ply without CCZ_REC_VALUE, and the rows a cut game leaves unwritten.
-__global__ void k_expand_record_values(const uint8_t *recs, long long n_plies, uint32_t flags, long long ring_rows, long long head,
-                                       float *value)
-{
-    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n_plies) return;
-    const uint8_t *rec = recs + (size_t)p * kRecBytes;
-    const PlyHeader h = *(const PlyHeader *)(rec + kRecHdr);
-    const long long mul = (flags & 2u) ? 1 : 2;
-    const int t = h.t, T = h.T;
-    const long long first = p - t;
-    const float none = __builtin_nanf("");
-    if (first < 0 || t >= T || first + T > n_plies || h.k > kMaxLegal) {
-        for (long long q = 0; q < mul; ++q) {
-            const long long row = head + mul * p + q;
-            value[ring_rows > 0 ? row % ring_rows : row] = none;
-        }
-        return;
-    }
-    const float v = (h.flags & kRecValue) ? *(const float *)(rec + kRecValueOff) : none;
-    for (long long pass = 0; pass < mul; ++pass) {
-        const long long row = head + mul * first + (pass ? T : 0) + t;
-        value[ring_rows > 0 ? row % ring_rows : row] = v;
-    }
-}
-
-// The root value of every row k_sample_records forms (same draw -> ply map, same validity rule): NaN for a bad draw and for a ply
-// without CCZ_REC_VALUE.
-__global__ void k_sample_record_values(const uint8_t *ring, long long cap_plies, const long long *window, const long long *draws,
-                                       long long batch, uint32_t flags, float *value)
-{
-    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= batch) return;
-    const long long mul = (flags & 2u) ? 1 : 2;
-    const long long tail = window[0], head = window[1], u = draws[j];
-    float v = __builtin_nanf("");
-    if (tail >= 0 && head > tail && head - tail <= cap_plies && u >= 0) {
-        const long long p = tail + (u % ((head - tail) * mul)) / mul;
-        const uint8_t *rec = ring + (size_t)CCZ_RING_IDX((int32_t *)nullptr, p % cap_plies, cap_plies) * kRecBytes;
-        const PlyHeader h = *(const PlyHeader *)(rec + kRecHdr);
-        const long long first = p - h.t;
-        if (h.t < h.T && h.k <= kMaxLegal && first >= tail && first + h.T <= head && (h.flags & kRecValue)) v = *(const float *)(rec + kRecValueOff);
-    }
-    value[j] = v;
 }
 
 // ccz_set_resign: the settings reach the device in stream order, so they hold from the next k_finish_move on

@@ -706,85 +706,84 @@ def game_aligned_chunks(records: torch.Tensor, max_plies: int):
         lo = hi
 
 
-def expand_records(records: torch.Tensor, flags: int = 0, plane_of_type=None, out=None, head_row: int = 0, bad=None):
-    """Compact ply records (uint8 [P, 880] on the GPU, whole games) -> the dense training rows ``ccz_harvest`` would have
-    written for those games: (states fp16 [R,17,7,10,9], pi f32 [R,2086], z f32 [R]), R = P x (1 or 2 with mirror images).
-    Stateless (no engine: the records may come from another rank). ``out=(states, pi, z)`` writes into existing arrays as a
-    ring: row i goes to (head_row + i) % len(z). ``bad``: int32 device tensor [1] counting records of cut games (skipped).
-    Asynchronous on the current stream. reference game.py:213-237 + collect.py:64-131 (preprocess, flip_data)."""
-    L = _lib.lib()
+def _expand(records: torch.Tensor, flags, plane_of_type, dense, ring: int, head_row, bad, target, value):
+    """One ``ccz_expand_records`` launch on the current stream. ``dense``: (states, pi, z) or None (the side-only mode);
+    ``target`` / ``value``: the side outputs or None; ``ring``: the outputs' length if they are a ring, else 0."""
     if not (records.is_cuda and records.dtype == torch.uint8 and records.is_contiguous()):
         raise ValueError("records must be a contiguous uint8 device tensor")
     if records.numel() % _lib.REC_BYTES:
         raise ValueError("records must hold whole 880-byte ply records")
-    P = records.numel() // _lib.REC_BYTES
-    R = rows_of_records(P, flags)
+    dev = records.device
+    pot = None if plane_of_type is None else (C.c_uint8 * 8)(*[int(x) for x in plane_of_type])
+    states, pi, z = dense if dense is not None else (None, None, None)
+    with torch.cuda.device(dev):
+        check(_lib.lib().ccz_expand_records(C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), _ptr(records), records.numel() // _lib.REC_BYTES,
+                                            int(flags), pot, _ptr(states), _ptr(pi), _ptr(z), ring, int(head_row) if ring else 0, _ptr(bad),
+                                            _ptr(target), _ptr(value)))
+
+
+def _side_ring(name: str, t, dtype, dev, ring=None):
+    """A side output of :func:`_expand` given by the caller: a 1-d ring on the records' device (of ``ring`` entries, if given)."""
+    if not (t.is_contiguous() and t.dtype == dtype and t.dim() == 1 and t.device == dev):
+        raise ValueError(f"{name} must be a contiguous {'uint8' if dtype == torch.uint8 else 'float32'} [N] tensor on the records' device")
+    if ring is not None and int(t.shape[0]) != ring:
+        raise ValueError(f"{name} must have the length of z ({ring})")
+    return t
+
+
+def expand_records(records: torch.Tensor, flags: int = 0, plane_of_type=None, out=None, head_row: int = 0, bad=None, targets=False, values=False):
+    """Compact ply records (uint8 [P, 880] on the GPU, whole games) -> the dense training rows ``ccz_harvest`` would have
+    written for those games: (states fp16 [R,17,7,10,9], pi f32 [R,2086], z f32 [R]), R = P x (1 or 2 with mirror images).
+    Stateless (no engine: the records may come from another rank). ``out=(states, pi, z)`` writes into existing arrays as a
+    ring: row i goes to (head_row + i) % len(z). ``bad``: int32 device tensor [1] counting records of cut games (skipped).
+    ``targets`` / ``values``: also return, after ``z`` and in this order, the rows' policy-target bytes (uint8 [R]: 0 for a
+    ``REC_FAST`` ply and for rows of cut games) and root values (float32 [R]: NaN for a ply without ``REC_VALUE`` and for rows of
+    cut games), written by the same launch; the mirror row carries its ply's. With ``out`` they are no flags: the tuple may carry
+    a 4th (targets) and 5th (values) ring tensor of the length of ``z``, written at the same ``head_row``.
+    Asynchronous on the current stream. reference game.py:213-237 + collect.py:64-131 (preprocess, flip_data)."""
+    R = rows_of_records(records.numel() // _lib.REC_BYTES, flags)
     dev = records.device
     if out is None:
         states = torch.empty((R, 17, 7, 10, 9), dtype=torch.float16, device=dev)
         pi = torch.empty((R, NMOVES), dtype=torch.float32, device=dev)
         z = torch.empty((R,), dtype=torch.float32, device=dev)
+        target = torch.empty((R,), dtype=torch.uint8, device=dev) if targets else None
+        value = torch.empty((R,), dtype=torch.float32, device=dev) if values else None
         ring = 0
     else:
-        states, pi, z = out
+        states, pi, z = out[:3]
         ring = int(z.shape[0])
         if not (states.is_contiguous() and pi.is_contiguous() and z.is_contiguous() and states.shape[0] == ring and pi.shape[0] == ring
                 and states.dtype == torch.float16 and pi.dtype == torch.float32 and z.dtype == torch.float32):
             raise ValueError("out must be contiguous (states fp16 [N,17,7,10,9], pi f32 [N,2086], z f32 [N])")
-    pot = None if plane_of_type is None else (C.c_uint8 * 8)(*[int(x) for x in plane_of_type])
-    with torch.cuda.device(dev):
-        check(L.ccz_expand_records(C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), _ptr(records), P, int(flags), pot,
-                                   _ptr(states), _ptr(pi), _ptr(z), ring, int(head_row) if ring else 0, _ptr(bad)))
-    return states, pi, z
+        target = _side_ring("out[3]", out[3], torch.uint8, dev, ring) if len(out) > 3 and out[3] is not None else None
+        value = _side_ring("out[4]", out[4], torch.float32, dev, ring) if len(out) > 4 and out[4] is not None else None
+    _expand(records, flags, plane_of_type, (states, pi, z), ring, head_row, bad, target, value)
+    return (states, pi, z) + ((target,) if target is not None else ()) + ((value,) if value is not None else ())
 
 
 def expand_record_targets(records: torch.Tensor, flags: int = 0, out=None, head_row: int = 0) -> torch.Tensor:
     """The policy-target byte (1 = target, 0 = a ``REC_FAST`` ply) of every row :func:`expand_records` writes for ``records``
-    (``ccz_expand_record_targets``): uint8 [R], the mirror row carries its ply's flag, rows of cut games get 0. ``out``: a uint8
-    ring [N] written at (head_row + i) % N, as :func:`expand_records` writes its ``out``. Asynchronous on the current stream."""
-    L = _lib.lib()
-    if not (records.is_cuda and records.dtype == torch.uint8 and records.is_contiguous()):
-        raise ValueError("records must be a contiguous uint8 device tensor")
-    if records.numel() % _lib.REC_BYTES:
-        raise ValueError("records must hold whole 880-byte ply records")
-    P = records.numel() // _lib.REC_BYTES
-    dev = records.device
+    (its ``targets`` output alone: the same launch without the rows): uint8 [R], the mirror row carries its ply's flag, rows of cut
+    games get 0. ``out``: a uint8 ring [N] written at (head_row + i) % N, as :func:`expand_records` writes its ``out``.
+    Asynchronous on the current stream."""
     if out is None:
-        target = torch.zeros((rows_of_records(P, flags),), dtype=torch.uint8, device=dev)
-        ring = 0
+        target = torch.zeros((rows_of_records(records.numel() // _lib.REC_BYTES, flags),), dtype=torch.uint8, device=records.device)
     else:
-        target = out
-        ring = int(target.shape[0])
-        if not (target.is_contiguous() and target.dtype == torch.uint8 and target.dim() == 1 and target.device == dev):
-            raise ValueError("out must be a contiguous uint8 [N] tensor on the records' device")
-    with torch.cuda.device(dev):
-        check(L.ccz_expand_record_targets(C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), _ptr(records), P, int(flags), ring,
-                                          int(head_row) if ring else 0, _ptr(target)))
+        target = _side_ring("out", out, torch.uint8, records.device)
+    _expand(records, flags, None, None, 0 if out is None else int(target.shape[0]), head_row, None, target, None)
     return target
 
 
 def expand_record_values(records: torch.Tensor, flags: int = 0, out=None, head_row: int = 0) -> torch.Tensor:
     """The root value (``REC_VALUE`` plies: record bytes 92..95, the side to move's view) of every row :func:`expand_records`
-    writes for ``records`` (``ccz_expand_record_values``): float32 [R], the mirror row carries its ply's value, NaN for a ply
+    writes for ``records`` (its ``values`` output alone): float32 [R], the mirror row carries its ply's value, NaN for a ply
     without a value and for rows of cut games. ``out``: a float32 ring [N] written at (head_row + i) % N. Asynchronous."""
-    L = _lib.lib()
-    if not (records.is_cuda and records.dtype == torch.uint8 and records.is_contiguous()):
-        raise ValueError("records must be a contiguous uint8 device tensor")
-    if records.numel() % _lib.REC_BYTES:
-        raise ValueError("records must hold whole 880-byte ply records")
-    P = records.numel() // _lib.REC_BYTES
-    dev = records.device
     if out is None:
-        value = torch.full((rows_of_records(P, flags),), float("nan"), dtype=torch.float32, device=dev)
-        ring = 0
+        value = torch.full((rows_of_records(records.numel() // _lib.REC_BYTES, flags),), float("nan"), dtype=torch.float32, device=records.device)
     else:
-        value = out
-        ring = int(value.shape[0])
-        if not (value.is_contiguous() and value.dtype == torch.float32 and value.dim() == 1 and value.device == dev):
-            raise ValueError("out must be a contiguous float32 [N] tensor on the records' device")
-    with torch.cuda.device(dev):
-        check(L.ccz_expand_record_values(C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), _ptr(records), P, int(flags), ring,
-                                         int(head_row) if ring else 0, _ptr(value)))
+        value = _side_ring("out", out, torch.float32, records.device)
+    _expand(records, flags, None, None, 0 if out is None else int(value.shape[0]), head_row, None, None, value)
     return value
 
 

@@ -711,7 +711,7 @@ class ReplayBuffer:
     def append_records(self, records: torch.Tensor, flags: int = 0, plane_of_type=None, bad=None) -> int:
         """Expand compact ply records (uint8 [P, 880], whole games; :class:`RecordGatherer`'s output) straight INTO the ring:
         ``ccz_expand_records`` writes the dense rows at (head + i) % capacity, no intermediate copy. Returns the rows added."""
-        from .engine import expand_record_targets, expand_record_values, expand_records, game_aligned_chunks, rows_of_records
+        from .engine import expand_records, game_aligned_chunks, rows_of_records
         mul = rows_of_records(1, flags)
         if rows_of_records(int(records.shape[0]), flags) > self.cap:  # more than the ring holds: game by game, the ring wraps
             if self.cap < mul:
@@ -725,9 +725,7 @@ class ReplayBuffer:
             raise ValueError(f"one game of {n} rows exceeds the replay ring ({self.cap} rows)")
         rec = records if records.device == self.states.device else records.to(self.states.device, non_blocking=True)
         rec = rec.contiguous()
-        expand_records(rec, flags, plane_of_type, out=(self.states, self.pi, self.z), head_row=self.head, bad=bad)
-        expand_record_targets(rec, flags, out=self.targets, head_row=self.head)
-        expand_record_values(rec, flags, out=self.values, head_row=self.head)
+        expand_records(rec, flags, plane_of_type, out=(self.states, self.pi, self.z, self.targets, self.values), head_row=self.head, bad=bad)
         self.head = (self.head + n) % self.cap
         self.size = min(self.cap, self.size + n)
         self.total += n
@@ -850,9 +848,9 @@ class RecordReplayBuffer:
         ``live = (head - tail) x mul`` read on the device; row ``r`` is ply ``tail + r // mul``, pass ``r % mul`` (1 = mirror image).
         Returns ``(states fp16 [batch,17,7,10,9], pi f32 [batch,2086], z f32 [batch])`` as :meth:`ReplayBuffer.sample` does.
         ``targets``: a fourth tensor, uint8 [batch] -- 1 where the row is a policy target, 0 for a ``REC_FAST`` ply (a fast move
-        of playout-cap randomisation) and for a bad draw (``ccz_sample_record_targets``). ``values``: a further tensor, float32
-        [batch] -- the ply's root value (a ``REC_VALUE`` record's bytes 92..95; a row and its mirror image carry the same), NaN for
-        a ply without one and for a bad draw (``ccz_sample_record_values``)."""
+        of playout-cap randomisation) and for a bad draw. ``values``: a further tensor, float32 [batch] -- the ply's root value (a
+        ``REC_VALUE`` record's bytes 92..95; a row and its mirror image carry the same), NaN for a ply without one and for a bad
+        draw. The same ``ccz_sample_records`` launch writes them."""
         from . import _lib
         from .engine import _ptr
         if self.head == 0:
@@ -864,22 +862,13 @@ class RecordReplayBuffer:
         states = torch.empty((n, 17, 7, 10, 9), dtype=torch.float16, device=d)
         pi = torch.empty((n, NMOVES), dtype=torch.float32, device=d)
         z = torch.empty((n,), dtype=torch.float32, device=d)
+        tg = torch.empty((n,), dtype=torch.uint8, device=d) if targets else None
+        vals = torch.empty((n,), dtype=torch.float32, device=d) if values else None
         with torch.cuda.device(d):
             _lib.check(_lib.lib().ccz_sample_records(self._stream(), _ptr(self.records), self.cap, _ptr(self._window), _ptr(draws), n,
                                                      self.flags, self._pot(), _ptr(states), _ptr(pi), _ptr(z),
-                                                     _ptr(self.bad if bad is None else bad)))
-            out = (states, pi, z)
-            if targets:
-                tg = torch.empty((n,), dtype=torch.uint8, device=d)
-                _lib.check(_lib.lib().ccz_sample_record_targets(self._stream(), _ptr(self.records), self.cap, _ptr(self._window), _ptr(draws), n,
-                                                                self.flags, _ptr(tg)))
-                out += (tg,)
-            if values:
-                vals = torch.empty((n,), dtype=torch.float32, device=d)
-                _lib.check(_lib.lib().ccz_sample_record_values(self._stream(), _ptr(self.records), self.cap, _ptr(self._window), _ptr(draws), n,
-                                                               self.flags, _ptr(vals)))
-                out += (vals,)
-        return out
+                                                     _ptr(self.bad if bad is None else bad), _ptr(tg), _ptr(vals)))
+        return (states, pi, z) + ((tg,) if targets else ()) + ((vals,) if values else ())
 
     def sample(self, batch: int, generator=None, targets: bool = False, values: bool = False):
         """A uniform minibatch over the live rows, mirror images included, without a host sync: the draws are

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define CCZ_ABI_VERSION 8           /* ABI 8: CCZ_CONV_G16 calls refuse flag 256 and bits 16..27 (the retired persistent form) */
+#define CCZ_ABI_VERSION 9           /* ABI 9: ccz_expand_records / ccz_sample_records write target_dev / value_dev themselves; the four ccz_*_record_targets / _values calls are gone */
 #define CCZ_NSQ 90
 #define CCZ_SQ_STRIDE 96            /* mailbox row stride in bytes (90 squares + 6 pad)         */
 #define CCZ_NMOVES 2086             /* action space, reference tools.py:172-272                 */
@@ -579,10 +579,16 @@ int ccz_harvest_records(ccz_engine *e, void *stream, void *records_dev, int64_t 
  * games (a record whose game is cut is skipped and counted in *bad_records_dev, int32 on the device, may be NULL).
  * flags: CCZ_FLAG_REFERENCE_QUIRKS | CCZ_FLAG_NO_MIRROR; plane_of_type_host: as ccz_config.plane_of_type or NULL.
  * Rows are written to row (head_row + i) % ring_rows of the output arrays (a replay ring resident in HBM);
- * ring_rows = 0: a plain array, row i. Asynchronous on `stream`. */
+ * ring_rows = 0: a plain array, row i. Asynchronous on `stream`.
+ * target_dev uint8 / value_dev float32 (4-byte aligned), either may be NULL: one entry per row, written at the same index as z.
+ * target: the policy-target byte (1 = target, 0 = a CCZ_REC_FAST ply); value: the ply's root value (record bytes 92..95), NaN
+ * for a ply without CCZ_REC_VALUE. The sample and its mirror image carry their ply's byte and value. The rows of a buffer of
+ * whole games that a cut game leaves unwritten -- (head_row + mul * p + q) % ring_rows for its records p, q < mul -- get 0 / NaN.
+ * states_f16_dev, pi_dev and z_dev may be NULL all three together if a side output is given: then only the side outputs are
+ * written (one launch of the same kernel, no row is formed). */
 int ccz_expand_records(void *stream, const void *records_dev, int64_t n_plies, uint32_t flags,
                        const uint8_t *plane_of_type_host, void *states_f16_dev, float *pi_dev, float *z_dev,
-                       int64_t ring_rows, int64_t head_row, int32_t *bad_records_dev);
+                       int64_t ring_rows, int64_t head_row, int32_t *bad_records_dev, uint8_t *target_dev, float *value_dev);
 
 /* ---- the replay ring of compact records ------------------------------------------------------------ */
 /* A trainer-side ring that keeps finished games AS RECORDS (ring_dev: cap_plies x 880 B in HBM) and forms a dense row only
@@ -602,29 +608,13 @@ int ccz_ring_retire(void *stream, const void *ring_dev, int64_t cap_plies, int64
  * CCZ_FLAG_NO_MIRROR, else 2) draw u means row r = u % live: ply tail + r / mul, pass r % mul (1 = the mirror image). Output
  * row j of states fp16 [batch,17,7,10,9], pi float32 [batch,2086], z float32 [batch] gets, byte for byte, what
  * ccz_expand_records writes for that ply and pass (flags, plane_of_type_host: as there). A drawn record that is not part of a
- * whole game inside the window, or an empty window, counts in *bad_records_dev and yields a row of zeros. */
+ * whole game inside the window, or an empty window, counts in *bad_records_dev and yields a row of zeros.
+ * target_dev uint8 [batch] / value_dev float32 [batch] (4-byte aligned), either may be NULL: the drawn row's policy-target byte
+ * and root value, as ccz_expand_records gives them for that ply (the mirror row carries its ply's); a bad draw gets 0 / NaN. */
 int ccz_sample_records(void *stream, const void *ring_dev, int64_t cap_plies, const int64_t *window_dev,
                        const int64_t *draws_dev, int64_t batch, uint32_t flags, const uint8_t *plane_of_type_host,
-                       void *states_f16_dev, float *pi_dev, float *z_dev, int32_t *bad_records_dev);
-
-/* The policy-target byte (1 = target, 0 = a CCZ_REC_FAST ply) of the rows the two calls above write; stateless, asynchronous.
- * ccz_expand_record_targets: target_dev uint8, one byte per row of ccz_expand_records with the same records_dev / n_plies / flags
- *   (CCZ_FLAG_NO_MIRROR) / ring_rows / head_row: the sample and its mirror image carry their ply's flag. The rows of a buffer of
- *   whole games that a cut game leaves unwritten there -- (head_row + mul * p + q) % ring_rows for its records p, q < mul -- get 0.
- * ccz_sample_record_targets: target_dev uint8 [batch], one byte per drawn row of ccz_sample_records with the same ring_dev /
- *   cap_plies / window_dev / draws_dev / flags; a draw that ccz_sample_records counts as bad gives 0. */
-int ccz_expand_record_targets(void *stream, const void *records_dev, int64_t n_plies, uint32_t flags, int64_t ring_rows, int64_t head_row,
-                              uint8_t *target_dev);
-int ccz_sample_record_targets(void *stream, const void *ring_dev, int64_t cap_plies, const int64_t *window_dev, const int64_t *draws_dev,
-                              int64_t batch, uint32_t flags, uint8_t *target_dev);
-
-/* The root value (record bytes 92..95) of the rows the same two calls write, float32, row-aligned with the *_record_targets pair
- * and with the same arguments: the sample and its mirror image carry their ply's v. NaN: a ply without CCZ_REC_VALUE, a row a cut
- * game leaves unwritten (ccz_expand_record_values), a bad draw (ccz_sample_record_values). */
-int ccz_expand_record_values(void *stream, const void *records_dev, int64_t n_plies, uint32_t flags, int64_t ring_rows, int64_t head_row,
-                             float *value_dev);
-int ccz_sample_record_values(void *stream, const void *ring_dev, int64_t cap_plies, const int64_t *window_dev, const int64_t *draws_dev,
-                             int64_t batch, uint32_t flags, float *value_dev);
+                       void *states_f16_dev, float *pi_dev, float *z_dev, int32_t *bad_records_dev, uint8_t *target_dev,
+                       float *value_dev);
 
 int ccz_get_stats(ccz_engine *e, void *stream, ccz_stats *out); /* syncs */
 

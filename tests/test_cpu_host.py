@@ -29,14 +29,14 @@ def test_abi_version_and_struct_layout():
     from chinesechesszero_amd import _lib
     hdr = open(os.path.join(ROOT, "include", "cczero.h")).read()
     L = _lib.lib()
-    assert L.ccz_abi_version() == 8 == _lib.ABI_VERSION   # ABI 8: CCZ_CONV_G16 calls refuse flag 256 / bits 16..27 (CCZ_CONV_G16_PERSISTENT retired); ABI 7: CCZ_FLAG_STRICT + CCZ_ERR_PRUNED / _TRUNCATED, CCZ_CONV_G16_PERSISTENT; ABI 5: ccz_leaf_priors, CCZ_FLAG_CACHE_VERIFY + two ccz_stats counters; ABI 6: ccz_conv3x3_c256_heads_f16, ccz_fc_f16 relu bits 1 / 2
+    assert L.ccz_abi_version() == 9 == _lib.ABI_VERSION   # ABI 9: ccz_expand_records / ccz_sample_records gain target_dev / value_dev, the four ccz_*_record_targets / _values calls removed; ABI 8: CCZ_CONV_G16 calls refuse flag 256 / bits 16..27 (CCZ_CONV_G16_PERSISTENT retired); ABI 7: CCZ_FLAG_STRICT + CCZ_ERR_PRUNED / _TRUNCATED, CCZ_CONV_G16_PERSISTENT; ABI 5: ccz_leaf_priors, CCZ_FLAG_CACHE_VERIFY + two ccz_stats counters; ABI 6: ccz_conv3x3_c256_heads_f16, ccz_fc_f16 relu bits 1 / 2
     assert ctypes.sizeof(_lib.Config) == 96 and ctypes.sizeof(_lib.Stats) == 152      # ABI 3: four evaluation-cache counters appended; ABI 5: two verify counters
     # ABI 2 fields sit where include/cczero.h puts them (pointer at 64, plane map at 72, rule flags at 80); ABI 3 gives the word
     # behind rule_flags a meaning (eval_cache_log2) without moving anything
     assert _lib.Config.move_rank_host.offset == 64 and _lib.Config.plane_of_type.offset == 72 and _lib.Config.rule_flags.offset == 80 and _lib.Config.type_rank.offset == 88
     assert _lib.Config.eval_cache_log2.offset == 84 and _lib.Stats.cache_probes.offset == 104
     m = re.search(r"#define CCZ_ABI_VERSION (\d+)", hdr)
-    assert m and int(m.group(1)) == 8
+    assert m and int(m.group(1)) == 9
 
 
 def test_tables_from_library_match_reference_golden(golden):

@@ -28,8 +28,10 @@ def test_header_library_and_shim_agree_on_the_two_entry_points():
         assert hasattr(L, name)
     # the shim's arity rule holds for the call the new ones are modelled on, too
     assert len(_lib.PROTOTYPES["ccz_expand_records"][1]) == _declared_arity(hdr, "ccz_expand_records")
-    # additive symbols: the ABI version does not move
-    assert L.ccz_abi_version() == _lib.ABI_VERSION == 8
+    # ABI 9: both calls gained target_dev / value_dev and the four side calls went away
+    assert L.ccz_abi_version() == _lib.ABI_VERSION == 9
+    assert _declared_arity(hdr, "ccz_sample_records") == 14 and _declared_arity(hdr, "ccz_expand_records") == 13
+    assert not any(n.endswith(("_record_targets", "_record_values")) for n in _lib.PROTOTYPES)
 
 
 def test_entry_points_validate_their_arguments_before_any_launch():
@@ -44,11 +46,20 @@ def test_entry_points_validate_their_arguments_before_any_launch():
     assert L.ccz_ring_retire(None, p, 64, p, 0, 70000, None) != 0          # T is 16 bits
     assert L.ccz_ring_retire(None, None, 64, p, 0, 14, None) != 0
     assert L.ccz_ring_retire(None, p, 64, p, -1, 14, None) != 0
-    assert L.ccz_sample_records(None, p, 0, p, p, 4, 0, None, p, p, p, None) != 0 and b"ccz_sample_records" in L.ccz_last_error()
-    assert L.ccz_sample_records(None, p, 64, p, p, -1, 0, None, p, p, p, None) != 0
-    assert L.ccz_sample_records(None, p, 64, None, p, 4, 0, None, p, p, p, None) != 0
-    assert L.ccz_sample_records(None, p, 64, p, p, 4, 0, bad_map, p, p, p, None) != 0 and b"permutation" in L.ccz_last_error()
-    assert L.ccz_sample_records(None, p, 64, p, p, 0, 0, None, p, p, p, None) == 0      # an empty batch launches nothing
+    assert L.ccz_sample_records(None, p, 0, p, p, 4, 0, None, p, p, p, None, None, None) != 0 and b"ccz_sample_records" in L.ccz_last_error()
+    assert L.ccz_sample_records(None, p, 64, p, p, -1, 0, None, p, p, p, None, None, None) != 0
+    assert L.ccz_sample_records(None, p, 64, None, p, 4, 0, None, p, p, p, None, None, None) != 0
+    assert L.ccz_sample_records(None, p, 64, p, p, 4, 0, bad_map, p, p, p, None, None, None) != 0 and b"permutation" in L.ccz_last_error()
+    assert L.ccz_sample_records(None, p, 64, p, p, 0, 0, None, p, p, p, None, None, None) == 0      # an empty batch launches nothing
+    # ccz_expand_records: the dense outputs are all given, or none of them and then a side output (the side-only mode)
+    assert L.ccz_expand_records(None, p, 4, 0, None, None, None, None, 0, 0, None, None, None) != 0 and b"ccz_expand_records: null buffer" in L.ccz_last_error()
+    for trio in ((None, p, p), (p, None, p), (p, p, None), (p, None, None)):
+        assert L.ccz_expand_records(None, p, 4, 0, None, *trio, 0, 0, None, p, p) != 0 and b"ccz_expand_records: null buffer" in L.ccz_last_error()
+    assert L.ccz_expand_records(None, p, 4, 0, None, None, None, None, 0, 3, None, p, None) != 0 and b"head_row needs ring_rows" in L.ccz_last_error()
+    assert L.ccz_expand_records(None, p, 4, 0, None, None, None, None, 7, 0, None, p, None) != 0 and b"do not fit" in L.ccz_last_error()
+    assert L.ccz_expand_records(None, p, 4, 0, None, None, None, None, 0, 0, None, None, ctypes.c_void_p(p.value + 2)) != 0 and b"4-byte aligned" in L.ccz_last_error()
+    assert L.ccz_sample_records(None, p, 64, p, p, 4, 0, None, p, p, p, None, None, ctypes.c_void_p(p.value + 2)) != 0 and b"4-byte aligned" in L.ccz_last_error()
+    assert L.ccz_expand_records(None, p, 0, 0, None, None, None, None, 0, 0, None, None, None) == 0      # no records: nothing to refuse
 
 
 def test_record_ring_refuses_bad_arguments_without_a_device():

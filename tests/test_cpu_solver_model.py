@@ -193,7 +193,7 @@ def test_abi_has_the_solver_entry_points():
     lib = _lib.lib()
     for name in ("ccz_set_solver", "ccz_root_proof", "ccz_get_solver_stats", "ccz_proof_combine"):
         assert name in _lib.PROTOTYPES and getattr(lib, name) is not None
-    assert lib.ccz_abi_version() == 8 == _lib.ABI_VERSION
+    assert lib.ccz_abi_version() == 9 == _lib.ABI_VERSION
     assert _lib.LEAF_WIN == 4
 
 
