@@ -8,6 +8,7 @@ reference architecture with identical ``state_dict`` keys (net.py:46-110) so ref
 """
 from __future__ import annotations
 
+import ctypes as C
 import os
 
 import numpy as np
@@ -136,6 +137,11 @@ class EvalOptions:
     def non_default(self):
         d = EvalOptions(env={})
         return {f: getattr(self, f) for f in self.FIELDS if getattr(self, f) != getattr(d, f)}
+
+
+def _ptr(t, offset: int = 0):
+    """A tensor's data pointer (plus a byte offset) as the library's entry points take it."""
+    return C.c_void_p(t.data_ptr() + offset)
 
 
 _CHAIN_STREAMS: dict = {}
@@ -349,13 +355,10 @@ class InferenceNet(nn.Module):
         plain torch ops otherwise (CPU tests, other dtypes)."""
         if y.is_cuda and y.dtype == torch.float16 and y.is_contiguous(memory_format=torch.channels_last) \
                 and (residual is None or residual.is_contiguous(memory_format=torch.channels_last)):
-            import ctypes as C
             from . import _lib
             n, c, h, w = y.shape
-            _lib.check(_lib.lib().ccz_bias_act_f16(C.c_void_p(torch.cuda.current_stream(y.device).cuda_stream),
-                                                   C.c_void_p(y.data_ptr()), C.c_void_p(bias.data_ptr()),
-                                                   C.c_void_p(residual.data_ptr()) if residual is not None else None,
-                                                   n * h * w, c))
+            _lib.check(_lib.lib().ccz_bias_act_f16(C.c_void_p(torch.cuda.current_stream(y.device).cuda_stream), _ptr(y), _ptr(bias),
+                                                   _ptr(residual) if residual is not None else None, n * h * w, c))
             return y
         y = y + bias.view(1, -1, 1, 1)
         if residual is not None:
@@ -402,123 +405,104 @@ class InferenceNet(nn.Module):
         (4096 boards, 80 different weight sets; round 2, board-major rows): 1 chain 29.2 ms/step, 2 chains 27.9, 3: 28.0, 4: 28.5,
         8: 28.6 (same-weights microbench profiles/conv_streams.py: 352 -> 319 -> 311 us per layer for 1 / 2 / 8 chains); round 3,
         group-of-16 rows with the evaluation cache: 1 chain 24.9, 2 chains 23.5, 3: 23.3-24.0, 4: 24.4 (profiles/r03_conv_g16.json).
-        Inside a stream capture (hipGraph) one chain is used. ``g16``: the rows of ``x`` are in the group-of-16 order
+        Inside a stream capture (hipGraph) one chain is used. The launch structure is :meth:`tower_schedule`'s, enqueued by
+        :meth:`_tower_enqueue`. ``g16``: the rows of ``x`` are in the group-of-16 order
         (``None``: as :meth:`_stem_fused` lays out a batch of this size). ``heads`` = (pol, val) buffers of :meth:`_head_buffers`
         (group-of-16 rows only): the LAST layer runs as ``ccz_conv3x3_c256_heads_f16`` -- both head convolutions in its epilogue,
         its own output never stored: the returned tensor then holds the input of the last block, not the tower's output."""
-        import ctypes as C
-        from . import _lib
-        L = _lib.lib()
         if g16 is None:   # x as _stem_fused returned it for a batch of this size (padded to whole groups of 16 boards)
             g16 = self._g16(x.shape[0]) and x.shape[0] % 16 == 0
-        y = torch.empty_like(x)
-        # groups of TOWER_GROUP_BOARDS boards go through all 80 layers one after the other: the two activation buffers of a
-        # group (2 x 94 MB at 2048 boards) then stay inside the 256 MB Infinity Cache from layer to layer
-        # (4096 boards: 1 group 27.55 ms/step, 2 groups 27.19, 3: 28.0, 4: 28.4)
-        Bt = x.shape[0]
-        # (group-of-16 layout, round 3, 4096 boards with the evaluation cache: 1 group x 2 chains 23.54 ms/step, 2 x 2 23.80,
-        # 1 x 1 24.89, 1 x 4 24.42: the cache-residency gain of two groups is gone, the tail-filling of two chains is not)
-        groups = self.tower_groups(Bt, g16)
-        if torch.cuda.is_current_stream_capturing():
-            groups = 1
-        if plan is not None:
-            self._tower_planned(L, C, x, y, plan, groups, g16, heads)
-            return x
-        gstep = -(-(-(-Bt // groups)) // 128) * 128 if groups > 1 else Bt
-        for g0 in range(0, Bt, gstep):
-            self._tower_range(L, C, x, y, g0, min(Bt, g0 + gstep), g16, heads)
+        sched = self.tower_schedule(x.shape[0], g16, plan is not None, torch.cuda.is_current_stream_capturing())
+        self._tower_enqueue(sched, x, torch.empty_like(x), plan, heads)
         return x
 
-    def _tower_planned(self, L, C, x, y, plan, groups, g16=False, heads=None):
-        """The tower on the LIVE rows of a planned batch (``ccz_eval_plan``): the live rows -- a device-side count -- are cut
-        into groups x chains EQUAL ranges by the kernel itself (``ccz_conv3x3_c256_f16_live``: part / n_parts), so that the
-        concurrent chains of a group stay balanced whatever the live count is. Launch structure as in :meth:`_tower_range`:
-        groups one after the other (Infinity-Cache residency), the chains of a group on separate streams."""
+    def tower_schedule(self, B: int, g16: bool, planned: bool = False, capturing: bool = False):
+        """The tower's launch structure over ``B`` rows (padded to whole groups of 16 for ``g16``) as data: a list of sequential
+        board groups, each a list of concurrent launch chains, each a tuple of plain integers -- ``(lo, hi, flags1, flags2)`` for the
+        whole batch (boards [lo, hi) through pointer offsets), ``(cap_pixels, part, n_parts, flags1, flags2)`` for a ``planned``
+        batch (``ccz_eval_plan``: the live rows -- a device-side count -- are cut into n_parts EQUAL ranges by the kernel itself,
+        so that the chains of a group stay balanced whatever the count is; ``cap_pixels`` is the largest range a launch may get).
+        ``flags1`` / ``flags2``: the flag words of the first / second convolution of every block.
+
+        Groups of TOWER_GROUP_BOARDS boards go through all layers one after the other: the two activation buffers of a group
+        (2 x 94 MB at 2048 boards) then stay inside the 256 MB Infinity Cache from layer to layer (board-major rows, 4096 boards:
+        1 group 27.55 ms/step, 2 groups 27.19, 3: 28.0, 4: 28.4; group-of-16 rows, round 3, with the evaluation cache: 1 group x 2
+        chains 23.54 ms/step, 2 x 2 23.80, 1 x 1 24.89, 1 x 4 24.42: the cache-residency gain of two groups is gone there, the
+        tail-filling of two chains is not). The tile order alternates from layer to layer: what the previous layer wrote last
+        (still in the Infinity Cache) is read first (-0.7 % on the step; zigzag=False / CCZ_CONV_ZIGZAG=0 switches it off).
+        ``capturing`` (a hipGraph capture): one group of one chain, on the capturing stream."""
         from . import _lib
-        B = x.shape[0]
-        cur = torch.cuda.current_stream(x.device)
+        groups = 1 if capturing else self.tower_groups(B, g16)
         edge = self._edge(B, g16)
-        chains = 1 if torch.cuda.is_current_stream_capturing() else self.tower_chains(B, groups, edge)
-        n_parts = groups * chains
-        if g16:
-            cap = -(-(B // 16) // n_parts) * 1440            # whole 16-board groups (B is padded to a multiple of 16)
-        else:
-            cap = -(-(-(-B // n_parts)) // 8) * 8 * 90       # pixels of the largest range a launch may get
-        lay = (_lib.CONV_G16 | self._edge_flags(edge)) if g16 else 0
-        pool = self._chain_pool(x.device, chains) if chains > 1 else None
-        live = C.c_void_p(plan[1].data_ptr())
-        xp, yp = C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr())
-        down = 2 if self.opt.zigzag else 0
-        for g in range(groups):
-            streams = [cur] if chains == 1 else pool[:chains]
+        f2 = 1 | ((_lib.CONV_G16 | self._edge_flags(edge)) if g16 else 0) | (0 if planned else self.opt.force)
+        f1 = f2 | (2 if self.opt.zigzag else 0)
+        if planned:
+            chains = 1 if capturing else self.tower_chains(B, groups, edge)
+            n_parts = groups * chains
+            if g16:
+                cap = -(-(B // 16) // n_parts) * 1440            # whole 16-board groups
+            else:
+                cap = -(-(-(-B // n_parts)) // 8) * 8 * 90
+            return [[(cap, g * chains + k, n_parts, f1, f2) for k in range(chains)] for g in range(groups)]
+        gstep = -(-(-(-B // groups)) // 128) * 128 if groups > 1 else B
+        sched = []
+        for g0 in range(0, B, gstep):
+            n = min(B, g0 + gstep) - g0
+            chains = 1 if capturing else self.tower_chains(n, 1, edge)
+            step = -(-n // chains)
             if chains > 1:
+                step = -(-step // 128) * 128  # 128 boards = 45 whole tiles: no partial tile inside the batch
+            sched.append([(g0 + b0, g0 + min(n, b0 + step), f1, f2) for b0 in range(0, n, step)])
+        return sched
+
+    def _tower_enqueue(self, sched, x, y, plan=None, heads=None):
+        """Enqueue a :meth:`tower_schedule`: the groups one after the other; the chains of a group forked from the current stream
+        onto the first streams of :meth:`_chain_pool` (chain 0 as well) and joined into it at the end -- a single chain runs on the
+        current stream itself, without events. Launches are enqueued layer by layer across the chains, so that the chains advance
+        together (the same layer's weights stay hot in L2) and no chain waits for the host to finish enqueuing another one. With
+        ``heads`` the last layer writes them from its epilogue and stores no output."""
+        from . import _lib
+        L = _lib.lib()
+        cur = torch.cuda.current_stream(x.device)
+        wsrc = self.ws_g16 if sched[0][0][-1] & _lib.CONV_G16 else self.ws
+        layers = [(_ptr(w), _ptr(b)) for w, b in zip(wsrc, self.bs32)]
+        hw, hb = (_ptr(self.head_w32), _ptr(self.head_b32)) if heads is not None else (None, None)
+        conv = L.ccz_conv3x3_c256_f16 if plan is None else L.ccz_conv3x3_c256_f16_live
+        row = 90 * 256 * x.element_size()
+
+        def chain(st, d):
+            """One chain's arguments: stream, x, y, head buffers, pixels, the two flag words, and what a convolution / the heads
+            layer takes after them. The ONE place where the whole-batch and the planned form differ."""
+            s = C.c_void_p(st.cuda_stream)
+            if plan is None:
+                lo, hi, f1, f2 = d
+                return s, _ptr(x, lo * row), _ptr(y, lo * row), [_ptr(h, lo * h.stride(0) * 2) for h in heads or ()], (hi - lo) * 90, f1, f2, (), (None, 0, 1)
+            cap, part, n_parts, f1, f2 = d
+            live = (_ptr(plan[1]), part, n_parts)
+            return s, _ptr(x), _ptr(y), [_ptr(h) for h in heads or ()], cap, f1, f2, live, live
+
+        for group in sched:
+            streams = [cur] if len(group) == 1 else self._chain_pool(x.device, len(group))[:len(group)]
+            if len(group) > 1:
                 fork = torch.cuda.Event()
                 fork.record(cur)
                 for st in streams:
                     st.wait_event(fork)
-            wsrc = self.ws_g16 if g16 else self.ws
-            for i in range(0, len(self.ws), 2):
-                w1, b1_, w2, b2_ = (C.c_void_p(t.data_ptr()) for t in (wsrc[i], self.bs32[i], wsrc[i + 1], self.bs32[i + 1]))
-                for k, st in enumerate(streams):
-                    _lib.check(L.ccz_conv3x3_c256_f16_live(C.c_void_p(st.cuda_stream), xp, w1, b1_, None, yp, cap, 1 | down | lay, live, g * chains + k, n_parts))
-                if heads is not None and i == len(self.ws) - 2:   # the last layer: heads in the epilogue, no output tensor
-                    hw, hb, hp, hv = (C.c_void_p(t.data_ptr()) for t in (self.head_w32, self.head_b32, heads[0], heads[1]))
-                    for k, st in enumerate(streams):
-                        _lib.check(L.ccz_conv3x3_c256_heads_f16(C.c_void_p(st.cuda_stream), yp, w2, b2_, xp, hw, hb, hp, hv, cap, 1 | lay, live, g * chains + k, n_parts))
+            chains = [chain(st, d) for st, d in zip(streams, group)]
+            for i in range(0, len(layers), 2):
+                (w1, b1), (w2, b2) = layers[i], layers[i + 1]
+                for s, xp, yp, _, n, f1, _, tail, _ in chains:
+                    _lib.check(conv(s, xp, w1, b1, None, yp, n, f1, *tail))
+                if heads is not None and i == len(layers) - 2:   # the last layer: heads in the epilogue, no output tensor
+                    for s, xp, yp, hd, n, _, f2, _, tail in chains:
+                        _lib.check(L.ccz_conv3x3_c256_heads_f16(s, yp, w2, b2, xp, hw, hb, *hd, n, f2, *tail))
                     continue
-                for k, st in enumerate(streams):
-                    _lib.check(L.ccz_conv3x3_c256_f16_live(C.c_void_p(st.cuda_stream), yp, w2, b2_, xp, xp, cap, 1 | lay, live, g * chains + k, n_parts))
-            for st in (streams if chains > 1 else []):
+                for s, xp, yp, _, n, _, f2, tail, _ in chains:
+                    _lib.check(conv(s, yp, w2, b2, xp, xp, n, f2, *tail))  # output written over the residual input
+            for st in streams if len(group) > 1 else ():  # every chain stream is joined into the current stream
                 join = torch.cuda.Event()
                 join.record(st)
                 cur.wait_event(join)
-
-    def _tower_range(self, L, C, x, y, lo, hi, g16=False, heads=None):
-        """Boards [lo, hi) through all 80 layers, as TOWER_CHAINS concurrent launch chains."""
-        from . import _lib
-        B = hi - lo
-        cur = torch.cuda.current_stream(x.device)
-        edge = self._edge(x.shape[0], g16)
-        parts = 1 if torch.cuda.is_current_stream_capturing() else self.tower_chains(B, 1, edge)
-        step = -(-B // parts)
-        if parts > 1:
-            step = -(-step // 128) * 128  # 128 boards = 45 whole tiles: no partial tile inside the batch
-        bounds = [(lo + b0, lo + min(B, b0 + step)) for b0 in range(0, B, step)]
-        if len(bounds) > 1:
-            pool = self._chain_pool(x.device, len(bounds))
-            fork = torch.cuda.Event()
-            fork.record(cur)
-        row = 90 * 256 * x.element_size()
-        chains = []
-        for k, (b0, b1) in enumerate(bounds):
-            st = cur if len(bounds) == 1 else pool[k]
-            if len(bounds) > 1:
-                st.wait_event(fork)
-            chains.append((st, C.c_void_p(st.cuda_stream), C.c_void_p(x.data_ptr() + b0 * row), C.c_void_p(y.data_ptr() + b0 * row), (b1 - b0) * 90, b0))
-        # launches are enqueued layer by layer across the chains, so that the chains advance together (the same layer's
-        # weights stay hot in L2) and no chain waits for the host to finish enqueuing another one. The tile order
-        # alternates from layer to layer: what the previous layer wrote last (still in the Infinity Cache) is read
-        # first (-0.7 % on the step; zigzag=False / CCZ_CONV_ZIGZAG=0 switches it off).
-        down = 2 if self.opt.zigzag else 0
-        v2 = self.opt.force | ((_lib.CONV_G16 | self._edge_flags(edge)) if g16 else 0)
-        wsrc = self.ws_g16 if g16 else self.ws
-        for i in range(0, len(self.ws), 2):
-            w1, b1_, w2, b2_ = (C.c_void_p(t.data_ptr()) for t in (wsrc[i], self.bs32[i], wsrc[i + 1], self.bs32[i + 1]))
-            for _, s, xp, yp, n_pixels, _b0 in chains:
-                _lib.check(L.ccz_conv3x3_c256_f16(s, xp, w1, b1_, None, yp, n_pixels, 1 | down | v2))
-            if heads is not None and i == len(self.ws) - 2:   # the last layer: heads in the epilogue, no output tensor
-                hw, hb = C.c_void_p(self.head_w32.data_ptr()), C.c_void_p(self.head_b32.data_ptr())
-                for _, s, xp, yp, n_pixels, b0 in chains:
-                    hp = C.c_void_p(heads[0].data_ptr() + b0 * heads[0].stride(0) * 2)
-                    hv = C.c_void_p(heads[1].data_ptr() + b0 * heads[1].stride(0) * 2)
-                    _lib.check(L.ccz_conv3x3_c256_heads_f16(s, yp, w2, b2_, xp, hw, hb, hp, hv, n_pixels, 1 | v2, None, 0, 1))
-                continue
-            for _, s, xp, yp, n_pixels, _b0 in chains:
-                _lib.check(L.ccz_conv3x3_c256_f16(s, yp, w2, b2_, xp, xp, n_pixels, 1 | v2))  # output written over the residual input
-        for st, *_ in (chains if len(chains) > 1 else []):  # every chain stream is joined into the current stream
-            join = torch.cuda.Event()
-            join.record(st)
-            cur.wait_event(join)
 
     def _chain_pool(self, device, n):
         """The launch-chain streams of ``device`` (:func:`chain_streams`, at least ``n``): the ones this copy holds, fetched again when it
@@ -536,47 +520,36 @@ class InferenceNet(nn.Module):
         return (_lib.CONV_G16_EDGE_TILES | (_lib.CONV_G16_ONE_LAUNCH if self.opt.one_launch else 0)
                 | (_lib.CONV_G16_QUAD if self.opt.quad else 0)) if edge else 0
 
-    def _force_flag(self) -> int:
-        """A/B switch ``force`` (``CCZ_CONV_FORCE=small|tile``): run every convolution on k_conv3x3_small / on the 256-pixel tile
-        kernel whatever the batch size (the library picks by batch size otherwise; the results are bit-identical either way)."""
-        return self.opt.force
-
     def _stem_fused(self, leaf_input, plan=None, g16=None):
         """Stem on the same MFMA kernel: pack the 21 live planes as NHWC rows of 64 channels, then one 64-channel chunk of
         the tower convolution (conv3x3 + bias + ReLU). Replaces cat + layout copy + MIOpen convolution + epilogue pass.
         With a ``plan`` the pack GATHERS: output row i is board rows[i], for the live rows only."""
-        import ctypes as C
         from . import _lib
         L = _lib.lib()
-        B = leaf_input.shape[0]
+        B, dev = leaf_input.shape[0], leaf_input.device
         if g16 is None:
             g16 = self._g16(B)
-        s = C.c_void_p(torch.cuda.current_stream(leaf_input.device).cuda_stream)
+        s = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         Bp = -(-B // 16) * 16 if g16 else B          # group-of-16 layout: whole groups; the padding boards hold zeros
         lay = _lib.CONV_G16 if g16 else 0   # (the stem is one launch over the whole batch, not chained: the single-kernel form)
         if plan is None:
-            x64 = (torch.zeros if Bp != B else torch.empty)((Bp, 90, 64), dtype=torch.float16, device=leaf_input.device)
-            y = torch.empty((Bp, 256, 10, 9), dtype=torch.float16, device=leaf_input.device, memory_format=torch.channels_last)
-            if g16:
-                _lib.check(L.ccz_pack_live_planes_g16_f16(s, C.c_void_p(leaf_input.data_ptr()), C.c_void_p(x64.data_ptr()), B, None, None))
-            else:
-                _lib.check(L.ccz_pack_live_planes_f16(s, C.c_void_p(leaf_input.data_ptr()), C.c_void_p(x64.data_ptr()), B))
-            _lib.check(L.ccz_conv3x3_stem_f16(s, C.c_void_p(x64.data_ptr()), C.c_void_p((self.stem_w64_g16 if g16 else self.stem_w64).data_ptr()), C.c_void_p(self.stem_b32.data_ptr()),
-                                              C.c_void_p(y.data_ptr()), Bp * 90, 1 | self._force_flag() | lay))
-            return y
-        rows, n_rows = plan
-        # rows past the live ones are never computed: they must still hold finite numbers for the heads' GEMMs (whose results
-        # for those rows nobody reads). Two persistent buffers, zeroed ONCE: whatever a row holds later is an old finite result.
-        bufs = self.__dict__.setdefault("_plan_bufs", {})
-        key = (Bp, leaf_input.device, g16)
-        if key not in bufs:
-            bufs[key] = (torch.zeros((Bp, 90, 64), dtype=torch.float16, device=leaf_input.device),
-                         torch.empty((Bp, 256, 10, 9), dtype=torch.float16, device=leaf_input.device, memory_format=torch.channels_last).zero_())
-        x64, y = bufs[key]
-        pack = L.ccz_pack_live_planes_g16_f16 if g16 else L.ccz_pack_live_planes_rows_f16
-        _lib.check(pack(s, C.c_void_p(leaf_input.data_ptr()), C.c_void_p(x64.data_ptr()), B, C.c_void_p(rows.data_ptr()), C.c_void_p(n_rows.data_ptr())))
-        _lib.check(L.ccz_conv3x3_stem_f16_live(s, C.c_void_p(x64.data_ptr()), C.c_void_p((self.stem_w64_g16 if g16 else self.stem_w64).data_ptr()), C.c_void_p(self.stem_b32.data_ptr()),
-                                               C.c_void_p(y.data_ptr()), Bp * 90 if g16 else -(-B // 8) * 8 * 90, 1 | lay, C.c_void_p(n_rows.data_ptr()), 0, 1))
+            x64 = (torch.zeros if Bp != B else torch.empty)((Bp, 90, 64), dtype=torch.float16, device=dev)
+            y = torch.empty((Bp, 256, 10, 9), dtype=torch.float16, device=dev, memory_format=torch.channels_last)
+            pack, gather = (L.ccz_pack_live_planes_g16_f16, (None, None)) if g16 else (L.ccz_pack_live_planes_f16, ())
+            stem, tail = L.ccz_conv3x3_stem_f16, (Bp * 90, 1 | self.opt.force | lay)   # (force: CCZ_CONV_FORCE=small|tile, an A/B switch)
+        else:
+            # rows past the live ones are never computed: they must still hold finite numbers for the heads' GEMMs (whose results
+            # for those rows nobody reads). Two persistent buffers, zeroed ONCE: whatever a row holds later is an old finite result.
+            bufs = self.__dict__.setdefault("_plan_bufs", {})
+            key = (Bp, dev, g16)
+            if key not in bufs:
+                bufs[key] = (torch.zeros((Bp, 90, 64), dtype=torch.float16, device=dev),
+                             torch.empty((Bp, 256, 10, 9), dtype=torch.float16, device=dev, memory_format=torch.channels_last).zero_())
+            x64, y = bufs[key]
+            pack, gather = (L.ccz_pack_live_planes_g16_f16 if g16 else L.ccz_pack_live_planes_rows_f16), (_ptr(plan[0]), _ptr(plan[1]))
+            stem, tail = L.ccz_conv3x3_stem_f16_live, (Bp * 90 if g16 else -(-B // 8) * 8 * 90, 1 | lay, _ptr(plan[1]), 0, 1)
+        _lib.check(pack(s, _ptr(leaf_input), _ptr(x64), B, *gather))
+        _lib.check(stem(s, _ptr(x64), _ptr(self.stem_w64_g16 if g16 else self.stem_w64), _ptr(self.stem_b32), _ptr(y), *tail))
         return y
 
     @torch.no_grad()
@@ -679,7 +652,6 @@ class InferenceNet(nn.Module):
         group-of-16 -> board permutation in ONE pass over the tower's rows, the two big FC layers as MFMA GEMMs, value_fc2 + tanh
         -- on the LIVE rows only (``plan``: a device-side count), the same bits for a board at every batch size. Returns
         (logits fp16 [B, 2086], value float32 [B])."""
-        import ctypes as C
         from . import _lib
         L = _lib.lib()
         Bx, dev = x.shape[0], x.device
@@ -687,13 +659,12 @@ class InferenceNet(nn.Module):
         logits = torch.empty((B, 2086), dtype=torch.float16, device=dev)
         v = torch.empty((B,), dtype=torch.float32, device=dev)
         s = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        live = C.c_void_p(plan[1].data_ptr()) if plan is not None else None
-        P = lambda t: C.c_void_p(t.data_ptr())
+        live = _ptr(plan[1]) if plan is not None else None
         if not conv_done:   # (conv_done: the last tower layer wrote pol / val from its epilogue, ``x`` is not the tower's output)
-            _lib.check(L.ccz_heads_conv1x1_f16(s, P(x), P(self.head_w32), P(self.head_b32), P(pol), P(val), Bx, _lib.CONV_G16 if g16 else 0, live))
-        _lib.check(L.ccz_fc_f16(s, P(pol), _lib.HEAD_POL_STRIDE, P(self.policy_fc_wp), P(self.policy_fc_b32), P(logits), 2086, B, 2086, 1536, 0, live))
-        _lib.check(L.ccz_fc_f16(s, P(val), _lib.HEAD_VAL_STRIDE, P(self.value_fc1_wp), P(self.value_fc1_b32), P(h1), 256, B, 256, 640, 1, live))
-        _lib.check(L.ccz_value_out_f32(s, P(h1), P(self.value_fc2_w), self._value_b2(), P(v), B, live))
+            _lib.check(L.ccz_heads_conv1x1_f16(s, _ptr(x), _ptr(self.head_w32), _ptr(self.head_b32), _ptr(pol), _ptr(val), Bx, _lib.CONV_G16 if g16 else 0, live))
+        _lib.check(L.ccz_fc_f16(s, _ptr(pol), _lib.HEAD_POL_STRIDE, _ptr(self.policy_fc_wp), _ptr(self.policy_fc_b32), _ptr(logits), 2086, B, 2086, 1536, 0, live))
+        _lib.check(L.ccz_fc_f16(s, _ptr(val), _lib.HEAD_VAL_STRIDE, _ptr(self.value_fc1_wp), _ptr(self.value_fc1_b32), _ptr(h1), 256, B, 256, 640, 1, live))
+        _lib.check(L.ccz_value_out_f32(s, _ptr(h1), _ptr(self.value_fc2_w), self._value_b2(), _ptr(v), B, live))
         return logits, v
 
     def _value_b2(self) -> float:

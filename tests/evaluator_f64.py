@@ -211,7 +211,7 @@ def assert_same_bits(got, want, what, names=None):
 
 # ------------------------------------------------------------------ the planned boundary on board-major rows (restatements of the host code and the kernels' addressing)
 def planned_cap(boards, n_parts):
-    """pixels of the largest range one launch of the board-major live form may get, as InferenceNet._tower_planned passes them:
+    """pixels of the largest range one launch of the board-major live form may get, as InferenceNet.tower_schedule (planned) gives them:
     ceil(ceil(B / n_parts) / 8) * 8 * 90 (it may reach past the tensor: the kernel never computes more than the live boards)"""
     return -(-(-(-boards // n_parts)) // 8) * 8 * 90
 

@@ -349,7 +349,7 @@ def test_mutation_table():
 # ------------------------------------------------------------------ (4) the planned boundary on board-major rows (tests/test_gpu_board_major_live.py)
 def test_live_ranges_cover_the_live_boards_once_inside_the_capacity():
     """live_ranges restates the range arithmetic of k_conv3x3_c256: for every live count up to the batch and 1..6 parts the ranges
-    start on multiples of 8 boards, do not overlap, never exceed the capacity _tower_planned passes, and together are [0, live)."""
+    start on multiples of 8 boards, do not overlap, never exceed the capacity the planned tower_schedule gives, and together are [0, live)."""
     assert E.planned_cap(40, 1) == 40 * 90 and E.planned_cap(40, 3) == 16 * 90 and E.planned_cap(40, 6) == 8 * 90
     assert E.planned_cap(37, 1) == 40 * 90 and E.planned_cap(600, 2) == 304 * 90 and E.planned_cap(11, 1) == 16 * 90
     assert E.live_ranges(9, 3, 16) == [(0, 8), (8, 1), (16, 0)]

@@ -5,8 +5,8 @@
   `w < b` rule and the routed second segment at miss_rows[B + pos] run only with more than one pass. B = 4097 puts one board into
   pass 2, B = 8200 has a third pass.
 - InferenceNet.tower_groups (net.py, TOWER_GROUP_BOARDS_G16 = 4096): on the group-of-16 layout groups > 1 happens only above 4096
-  boards; _tower_fused then cuts the batch at gstep and hands _tower_range pointer offsets into the rows and the head buffers, and
-  _tower_planned runs groups x chains = 6 (or 9) launch parts.
+  boards; tower_schedule then cuts the batch at gstep, _tower_fused launches every range with pointer offsets into the rows and the head buffers, and
+  a planned batch runs groups x chains = 6 (or 9) launch parts.
 
 The plan is compared with a NumPy restatement of the comments above cache_probe_wave and cache_plan_block (exactly: rows and count);
 priors with the float64 softmax and the derived bound of test_gpu_boundary_f64.py (no tolerance of this file's own); values,
@@ -532,7 +532,7 @@ def _byte_fill(shape, dtype, dev):
 
 @pytest.mark.parametrize("B", [4097, 4112, B_MAX])
 def test_planned_evaluator_above_4096_boards_live_rows_only(B):
-    """_tower_planned with groups x chains = 6 (9) launch parts: live counts 1, 4096, 4097 and B with permuted rows. The live rows
+    """_tower_fused on a planned batch with groups x chains = 6 (9) launch parts: live counts 1, 4096, 4097 and B with permuted rows. The live rows
     carry the bits of the chunked run; in the evaluator's persistent buffers (plane pack, stem output = tower ping-pong buffer,
     head outputs, hidden value layer), poisoned before the call, nothing outside the live rows -- whole groups of 16 for the
     group-of-16 buffers -- is written."""

@@ -3,7 +3,7 @@
 (1) ccz_conv3x3_c256_f16_live / ccz_conv3x3_stem_f16_live WITHOUT CONV_G16 always land on k_conv3x3_c256, which cuts the live boards (a
     device value) into n_parts ranges of ceil(ceil(L / n_parts) / 8) * 8 boards, moves X, Y and R to its range, clamps its halo rows
     into the range and leaves when the range is empty. Against the float64 chain on the first `live` boards; every row past them
-    keeps its fill, down to the byte. The capacity argument is what InferenceNet._tower_planned / _stem_fused pass
+    keeps its fill, down to the byte. The capacity argument is what InferenceNet.tower_schedule (planned) / _stem_fused pass
     (evaluator_f64.planned_cap), for 37 boards it reaches past the tensor.
 (2) The gathering plane pack (ccz_pack_live_planes_rows_f16, ccz_pack_live_planes_g16_f16 with rows) against the NumPy restatement
     evaluator_f64.pack_live_planes_rows: output row i from board rows[i] for i < *n_rows, three 16-byte chunks of 128 bytes.
@@ -69,7 +69,7 @@ def live_operands(boards):
 
 
 def launch_live(x, w, b, r, y, boards, live_dev, n_parts, relu):
-    """as _tower_planned: the same capacity for every part, odd parts in descending tile order (as launch_layer of the tile-stream file)"""
+    """as the planned tower_schedule: the same capacity for every part, odd parts in descending tile order (as launch_layer of the tile-stream file)"""
     L = _L()
     cap = E.planned_cap(boards, n_parts)
     for part in range(n_parts):
