@@ -795,6 +795,8 @@ int ccz_root_proof(ccz_engine *e, void *stream, uint8_t *state_host, uint8_t *di
     return 0;
 }
 
+static int fetch_meta(ccz_engine *e, hipStream_t s);
+
 int ccz_get_solver_stats(ccz_engine *e, void *stream, ccz_solver_stats *out)
 {
     NEED(e);
@@ -810,7 +812,10 @@ int ccz_get_solver_stats(ccz_engine *e, void *stream, ccz_solver_stats *out)
         out->nodes_proven += (int64_t)b.proven;
         out->proven_stops += (int64_t)b.stops;
     }
-    for (unsigned b = 0; b < ACTIVE(e); ++b) out->roots_proven += root[b] ? 1 : 0;
+    // a finished board is searched no more, and k_finish_move leaves it behind when the pool halves flip: what lies at its tree top is
+    // an older move's tree, not a root
+    if (const int rc = fetch_meta(e, s)) return rc;
+    for (unsigned b = 0; b < ACTIVE(e); ++b) out->roots_proven += (root[b] && !e->h_meta[b].over) ? 1 : 0;
     return 0;
 }
 

@@ -482,7 +482,7 @@ class SelfPlayEngine:
 
     def solver_stats(self) -> dict:
         """Sums over boards (``ccz_solver_stats``; syncs): ``nodes_proven``, ``proven_stops`` (simulations whose descent ended at a
-        node proven earlier), ``roots_proven`` (searched boards whose root is proven now)."""
+        node proven earlier), ``roots_proven`` (searched boards whose game is running and whose root is proven now)."""
         s = _lib.SolverStats()
         check(self.L.ccz_get_solver_stats(self.h, self._stream(), C.byref(s)))
         return {f: int(getattr(s, f)) for f, _ in _lib.SolverStats._fields_}

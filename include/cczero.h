@@ -465,7 +465,7 @@ int ccz_root_noise(ccz_engine *e, void *stream, float *noise_host, int32_t *k_ho
 typedef struct ccz_solver_stats {
     int64_t nodes_proven;  /* nodes whose byte left "unknown"                                        */
     int64_t proven_stops;  /* simulations backed up whose descent ended at a node proven earlier     */
-    int64_t roots_proven;  /* searched boards whose root is proven now (a state, not a running sum) */
+    int64_t roots_proven;  /* searched boards whose game is running and whose root is proven now (a state, not a running sum) */
 } ccz_solver_stats;
 int ccz_set_solver(ccz_engine *e, void *stream, int32_t enabled);
 int ccz_root_proof(ccz_engine *e, void *stream, uint8_t *state_host, uint8_t *dist_host, uint8_t *child_state_host, uint8_t *child_dist_host);

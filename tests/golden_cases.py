@@ -32,6 +32,10 @@ STARTS = {
     "one_move": _place({"e0": 7, "b1": 11, "a2": 11, "d9": 15}),     # red king: f0 only (rank 1 is covered, d0 faces the king)
     "mated": _place({"e0": 7, "b1": 11, "a0": 11, "d9": 15}),        # red king in check from a0, no legal move
 }
+# the widest one plus a black knight on h7 and a black rook on a9: 105 legal moves, of which exactly one ends the game -- a5a9, child
+# 67 of the root, i.e. in the second 64-lane pass of every per-node loop -- and nothing else is decided within 2 plies
+STARTS["wide_late_mate"] = STARTS["widest"].copy()
+STARTS["wide_late_mate"][[sq("h7"), sq("a9")]] = (12, 11)
 
 
 def perpetual_case(checker_is_red: bool):
@@ -62,6 +66,7 @@ for _name in ("wide64", "wide65", "widest", "wide_a0", "one_move", "mated"):
 WIDTHS = {"wide64": (1, 64), "wide65": (1, 65), "widest": (1, 108), "wide_a0": (1, 103), "one_move": (1, 1), "mated": (1, 0),
           "wide80": (1, 80)}
 WIDTHS.update({n + "_black": (0, k) for n, (t, k) in list(WIDTHS.items()) if n != "wide80"})
+WIDTHS["wide_late_mate"] = (1, 105)
 
 START_ROWS = ["RNBAKABNR", ".........", ".C.....C.", "P.P.P.P.P", ".........",
               ".........", "p.p.p.p.p", ".c.....c.", ".........", "rnbakabnr"]

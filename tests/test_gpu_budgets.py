@@ -2,13 +2,13 @@
 records (CCZ_REC_FAST, ccz_expand_record_targets / ccz_sample_record_targets), playout-cap randomisation in BatchedSelfPlay and
 playout odds in the arena. Everything here is exact: a board with budget n is, bit for bit, the same board of an engine that runs
 n lockstep steps, and the draws are those of a host twin of the device's Philox stream."""
-import ctypes as C
 import functools
 
 import numpy as np
 import pytest
 import torch
 
+from budget_twin import twin_budgets as _twin_budgets, ua as _ua
 from chinesechesszero_amd import _lib
 
 pytestmark = pytest.mark.gpu
@@ -163,19 +163,6 @@ def test_the_planned_boundary_plans_no_row_for_a_board_that_is_done():
 
 
 # ---------------------------------------------------------------------- the draws
-def _ua(seed, board_id, move_no, child=0xffe, draw=0):
-    """uniform2's first uniform (csrc/cczero_device.h) on the oracle's Philox."""
-    import oracle
-    o = (C.c_uint32 * 4)()
-    lo = ((move_no << 32) | ((child & 0xfff) << 20) | (draw & 0xfffff)) & (2**64 - 1)
-    oracle.lib().xq_philox4x32(C.c_uint64(seed), C.c_uint64(board_id), C.c_uint64(lo), o)
-    return float(2 * (((o[0] << 32) | o[1]) >> 12) + 1) * 1.1102230246251565e-16
-
-
-def _twin_budgets(seed, base, n_boards, move_no, n_full, n_fast, p_full):
-    return np.array([n_full if _ua(seed, base + b, move_no) < p_full else n_fast for b in range(n_boards)], np.int32)
-
-
 def test_the_draws_are_the_host_twins():
     from chinesechesszero_amd.engine import SelfPlayEngine
     from chinesechesszero_amd.net import uniform_evaluator
