@@ -6,7 +6,10 @@ Plain Python + NumPy, one sequential MCTS per board. The rules come from ``oracl
 model restates itself is the reference's selection arithmetic (float32 ``c_puct * P``, float64 score, first maximum) and the four
 solver rules: combine, backup, expansion, selection -- and the re-root. tests/test_cpu_solver_model.py pins the model to
 ``oracle.OracleMCTS`` with the solver off and certifies its proofs with an exhaustive negamax; tests/test_gpu_solver.py compares the
-engine with the model, exactly.
+engine with the model, exactly. tests/test_cpu_solver_deep.py and tests/test_gpu_solver_deep.py do the same for proof walks of 64 and
+more plies (scripted priors) and for a re-root that prunes (``prune_copy``, the budgeted breadth-first copy of ``k_finish_move``).
+
+``wrong=`` names a mis-stated rule so that a test can show that its fixtures tell the difference; the model itself never does.
 
 A proof byte: bits 0..1 the state in the view of the side to move at the node (0 unknown, WIN, LOSS, DRAW), bits 2..7 the distance
 to the end in plies, saturating at 63 (0 for a draw)."""
@@ -85,10 +88,41 @@ class SNode(Node):
         self.proof = 0
 
 
+WRONG_WALKS = ("deep_not_written", "stop_at_63", "no_substitution")
+WRONG_PRUNES = ("prune_zeroes_byte", "root_not_recombined")
+
+
+def prune_copy(root, budget, wrong=None):
+    """The re-root's copy of the subtree under ``root`` into a pool that may hold ``budget`` nodes (``k_finish_move``), in place:
+    breadth-first, in batches of 64 nodes of that order. Within a batch a node keeps its children while
+    n_new + inclusive_sum(nc) <= budget -- n_new: the nodes placed when the batch starts, the sum: over the batch in order, the
+    children that end up dropped included. A node that fails becomes a leaf again and keeps N, Q, P and its proof byte.
+    Returns (nodes kept, [(node, n_new, inclusive sum) of every node that lost its children])."""
+    order, head, n_new, dropped = [root], 0, 1, []
+    while head < n_new:
+        batch = order[head:head + 64]
+        incl = total = 0
+        for node in batch:
+            nc = len(node.kids or [])
+            incl += nc
+            if nc and n_new + incl <= budget:
+                order.extend(node.kids)
+                total = incl
+            elif nc:
+                dropped.append((node, n_new, incl))
+                node.kids = None
+                if wrong == "prune_zeroes_byte":
+                    node.proof = 0
+        head += len(batch)
+        n_new += total
+    assert n_new == len(order)
+    return n_new, dropped
+
+
 class SolverModel:
     """B boards, each a sequential search; ``solver`` on or off for all of them."""
 
-    def __init__(self, boards, salts, c_puct=5, solver=True, evaluator=None):
+    def __init__(self, boards, salts, c_puct=5, solver=True, evaluator=None, wrong=None):
         """``evaluator(b, board) -> (P float32 [2086], v float32)``: where the priors of an expanded leaf come from (default: the
         harness's ``hash`` evaluator under ``salts[b]``; the GPU test's compact paths pass the priors as the device's softmax forms
         them)."""
@@ -103,6 +137,9 @@ class SolverModel:
         self.proven_stops = 0          # simulations whose descent ended at a node proven earlier
         self.rows = 0                  # leaves that asked for the evaluator (status EXPAND)
         self.sims = 0
+        self.pruned_subtrees = 0       # nodes that lost their children in a re-root (stats()["pruned_subtrees"] of the engine)
+        assert wrong is None or wrong in WRONG_WALKS + WRONG_PRUNES
+        self.wrong = wrong
 
     # -------------------------------------------------------------------------------------------------------- one simulation
     def _select_child(self, node):
@@ -153,21 +190,34 @@ class SolverModel:
         return status, k, depth
 
     def _prove(self, path, status, stopped):
-        leaf = path[-1]
+        """The leaf's byte, then parent <- combine(children) from the leaf's parent up to the root until a byte does not change. The
+        child just rewritten enters its parent's combine as the new byte (the engine carries it in registers)."""
+        w, d, leaf = self.wrong, len(path) - 1, path[-1]
+        child_old = cur = leaf.proof
         if stopped:
             self.proven_stops += 1
         elif status == LEAF_WIN:
             return
         else:
-            leaf.proof = pack(DRAW) if status == LEAF_DRAW else pack(LOSS, 0)
+            cur = pack(DRAW) if status == LEAF_DRAW else pack(LOSS, 0)
+            if not (w == "deep_not_written" and d >= 64):
+                leaf.proof = cur
             self.nodes_proven += 1
-        for node in reversed(path[:-1]):
-            new = combine([c.proof for c in node.kids])
+        child = leaf
+        for j in range(d - 1, -1, -1):
+            node = path[j]
+            if (w == "stop_at_63" and j == 63) or (w == "root_not_recombined" and j == 0):
+                break
+            sub = child_old if w == "no_substitution" else cur
+            new = combine([sub if c is child else c.proof for c in node.kids])
             if new == node.proof:
                 break
             if state_of(node.proof) == UNKNOWN and state_of(new) != UNKNOWN:
                 self.nodes_proven += 1
-            node.proof = new
+            child_old = node.proof
+            if not (w == "deep_not_written" and j >= 64):
+                node.proof = new
+            cur, child = new, node
 
     def search(self, sims):
         """sims[b] (or the same int for all) playouts per board; returns the per-board lists of (status, k, depth)."""
@@ -212,12 +262,15 @@ class SolverModel:
         return None if best is None else int(acts[best])
 
     # -------------------------------------------------------------------------------------------------------- the move boundary
-    def update_with_move(self, b, move, keep_tree=True):
+    def update_with_move(self, b, move, keep_tree=True, budget=None):
         """MCTS.update_with_move: re-root on the child that plays ``move`` with its subtree and proof bytes; a move that is no child
-        of the root, or ``keep_tree`` False: a fresh, unknown root. The move is pushed on the board."""
+        of the root, or ``keep_tree`` False: a fresh, unknown root. The move is pushed on the board. ``budget``: the nodes the kept
+        subtree may use (the engine's max_nodes - reserve_nodes; None: the reference's unbounded tree), see ``prune_copy``."""
         root = self.roots[b]
         kid = next((c for c in (root.kids or []) if c.move == int(move)), None)
         self.roots[b] = kid if (keep_tree and kid is not None) else SNode(1.0, -1)
+        if budget is not None and keep_tree and kid is not None:
+            self.pruned_subtrees += len(prune_copy(kid, int(budget), self.wrong)[1])
         self.boards[b].push_id(int(move))
 
     def walk(self, b):
