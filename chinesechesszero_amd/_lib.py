@@ -46,7 +46,7 @@ PROOF_UNKNOWN, PROOF_WIN, PROOF_LOSS, PROOF_DRAW = 0, 1, 2, 3   # CCZ_PROOF_*: s
 
 ERR_BITS = {1: "node pool exhausted (raise max_nodes)", 2: "selection path deeper than max_depth", 64: "history chain overflow (> 128 positions since the last capture)",
             4: "more than 128 legal moves or pseudo-move overflow", 8: "pi record arena overflow",
-            16: "forced move is not a child of the root / root not expanded", 32: "NaN priors",
+            16: "forced move is not a legal move of the root, or nothing searched and nothing forced (that board neither recorded nor moved)", 32: "NaN priors",
             128: "index out of bounds (bounds-checked diagnostic build)",
             256: "strict mode: a kept subtree was pruned to fit the node pool (the reference's tree is unbounded: raise max_nodes)",
             512: "strict mode: a game was adjudicated at max_plies (the reference's game has no ply cap: raise max_plies)",

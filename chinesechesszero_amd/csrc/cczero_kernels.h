@@ -1681,10 +1681,15 @@ __global__ __launch_bounds__(64) void k_finish_move(Dev D, const int32_t *forced
     uint8_t *PN = sv.proof + baseNew;
     if (lane == 0) { D.nodeA[baseNew] = NodeA{0, 0.0f, 1.0f, -1}; D.nodeB[baseNew] = 0u; if (sv.enabled) PN[0] = 0; } // whatever happens below, the new half holds a valid (empty) tree
     const int want = forced ? forced[b] : -1;
+    // A refused board neither records nor moves: position, clocks, history, ply and move counter stay. Its tree is the empty root just
+    // written, so its pool accounting restarts with it (the host flips the half word for every board), and its pending leaf is dropped.
+    const auto refuse = [&](int bit) {
+        if (lane == 0) { set_err(D, bit); m.n_nodes = 1; m.half = (uint8_t)nh; D.meta[b] = m; D.leaf_status[b] = CCZ_LEAF_SKIP; }
+    };
     // (k == 0 and no forced move: nothing searched, nothing to sample from)
-    if (k > kMaxLegal || (k == 0 && want < 0) || want >= kNMoves) { if (lane == 0) set_err(D, 16); return; }
+    if (k > kMaxLegal || (k == 0 && want < 0) || want >= kNMoves) { refuse(16); return; }
     const double temp = board_temp(D, m, temps, b);
-    if (bad_temp(temp)) { if (lane == 0) set_err(D, CCZ_ERR_BAD_TEMP); return; }
+    if (bad_temp(temp)) { refuse(CCZ_ERR_BAD_TEMP); return; }
 
     load_board(s_sq, D.root_sq + (size_t)b * 96, lane);
     for (int i = lane; i < k; i += 64) {
@@ -1706,6 +1711,26 @@ __global__ __launch_bounds__(64) void k_finish_move(Dev D, const int32_t *forced
             if (rstate & kPlayOn) playon_count(D, b, rstate, -1, m.ply);
         }
         return;
+    }
+
+    // ---- a forced move must be a legal move of the root. A searched root's children are all of its legal moves (an expansion is
+    // all or nothing, pruning drops whole child lists); an unsearched root asks the generator, as k_set_positions does per ply.
+    // found: the forced move's child index, -1 on an unsearched root (a fresh root below, as MCTS.update_with_move does, mcts.py:176-178)
+    int found = -1;
+    if (want >= 0) {
+        for (int i0 = 0; i0 < k; i0 += 64) {
+            const int i = i0 + lane;
+            const uint64_t hit = __ballot(i < k && s_act[i] == want);
+            if (hit && found < 0) found = i0 + __ffsll((long long)hit) - 1;
+        }
+        bool legal = found >= 0;
+        if (k == 0) {
+            const GenResult g = gen_legal(s_sq, m.turn, S, nullptr, lane, nullptr, D.rank, D.unrank, D.trankpack);
+            if (g.overflow) set_err(D, 4);
+            const int bit = D.rank ? (int)D.rank[want] : want; // bit r of the mask = the move of rank r (gen_legal)
+            legal = ((S.mask[bit >> 5] >> (bit & 31)) & 1u) != 0u;
+        }
+        if (!legal) { refuse(16); return; }
     }
 
     // ---- pi (mcts.py:162-166) and the training record. The resignation value below, ccz_root_children and the lines read the
@@ -1779,15 +1804,6 @@ __global__ __launch_bounds__(64) void k_finish_move(Dev D, const int32_t *forced
 
     // ---- move choice (mcts.py:216-229)
     if (want >= 0) {
-        // a forced move that is not a child of the root (root unexpanded, or an opponent's reply the
-        // search never saw) gives a fresh root, as MCTS.update_with_move does (mcts.py:176-178)
-        int found = -1;
-        for (int i0 = 0; i0 < k; i0 += 64) {
-            const int i = i0 + lane;
-            const uint64_t hit = __ballot(i < k && s_act[i] == want);
-            if (hit && found < 0) found = i0 + __ffsll((long long)hit) - 1;
-        }
-        if (found < 0 && s_sq[c_tab.from[want]] == 0) { if (lane == 0) set_err(D, 16); return; }
         if (lane == 0) s_choice = found;
     } else {
         sample_move(D, D.board_id_base + (uint64_t)b, m.move_counter, s_pi, s_g, k, lane, &s_choice, nullptr, nullptr, nullptr, !explored);

@@ -479,11 +479,19 @@ int ccz_proof_combine(void *stream, const uint8_t *bytes_dev, const int32_t *cou
  * record (position, turn, pi), choose the move, re-root the tree on the chosen child (subtree
  * kept), make the move on the root position, detect the end of the game and its winner.
  *   forced_moves_dev: int32 [B] or NULL. entry >= 0: play that move id (host-exact numpy sampling
- *     or match play); a forced move that is not a child of the root (root never searched, or an
- *     opponent's reply the tree never saw) gives a fresh root, as update_with_move does
- *     (mcts.py:176-178). entry < 0 or NULL: sample on the device stream Philox(seed, board id).
+ *     or match play). It must be a LEGAL move of the root position: on a searched root one of its children (they are all of
+ *     its legal moves), on a root never searched -- which then gives a fresh root, as update_with_move does (mcts.py:176-178) --
+ *     a move the engine's generator lists, as ccz_set_positions checks per ply. Anything else (an id >= 2086, an empty
+ *     from-square, the opponent's piece, a move through a blocker, a move that leaves the own king in check) sets
+ *     CCZ_ERR_BAD_MOVE, as does a board with nothing forced and nothing searched. entry < 0 or NULL: sample on the device
+ *     stream Philox(seed, board id).
  *   temps_dev: float64 [B] or NULL (NULL: schedule of game.py:159 from cfg.temp). An entry that is NaN or <= 0 sets
- *     CCZ_ERR_BAD_TEMP and that board neither records nor moves.
+ *     CCZ_ERR_BAD_TEMP.
+ *   A board REFUSED with CCZ_ERR_BAD_MOVE or CCZ_ERR_BAD_TEMP neither records nor moves: moves_out is -1; position, side to move,
+ *     clock, history chain, ply, move counter (its Philox stream) and game record are kept. It loses its tree and its pending leaf:
+ *     the tree is a fresh root of one node, and the board's node-pool accounting restarts there. The checks run in this order:
+ *     finished board (skipped), bad id / nothing to move, bad temperature, the ply cap and the pi arena (the game is adjudicated
+ *     a draw, records kept: CCZ_ERR_RECORD for the arena, CCZ_ERR_TRUNCATED for the ply cap in strict mode), forced-move legality.
  *   moves_out_dev: int32 [B] or NULL, receives the move played.
  *   keep_tree: 1 = self-play tree reuse (mcts.py:222-224); 0 = discard (mcts.py:228-229).
  * All live trees move to the other half of their node pool in this call (one flip for every board),

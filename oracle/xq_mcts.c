@@ -61,6 +61,8 @@ struct xq_mcts {
     int value_f16;  /* the evaluator's value is a float16 ndarray (reference CUDA/autocast path, net.py:178-189) */
     node *cur_leaf; /* set by xq_mcts_select */
     int64_t live_nodes;
+    int max_depth;  /* > 0: the engine's limits (ccz_ref.c): path capacity -- a descent that would reach it is dropped --, and so is one
+                       without a comparable child. 0: the sequential reference, unbounded */
     /* optional wall-clock split of a playout (bench.py's cpu_baseline leg): seconds spent in the rules (push along the path,
        legal-move generation, game-end / draw predicates) and in the tree (PUCT scan, expansion, backup); the evaluator callback
        is timed by the caller. Off by default: no clock call is made. */
@@ -180,11 +182,17 @@ int xq_mcts_select(xq_mcts *t, const xq_board *root_board, xq_board *leaf_out, i
     double t0 = t->timing ? now_s() : 0.0, tr = 0.0;
     *leaf_out = *root_board; /* board.copy()  mcts.py:151 */
     while (n->nchild != 0) {
-        int i, best = 0;
-        double bestv = puct_value(n->child[0], t->c_puct);
-        for (i = 1; i < n->nchild; i++) {
+        int i, best = -1;
+        double bestv = -INFINITY;
+        for (i = 0; i < n->nchild; i++) {
             double v = puct_value(n->child[i], t->c_puct);
             if (v > bestv) { bestv = v; best = i; } /* strict: first maximum wins */
+        }
+        /* no child compares: every score is NaN (or -inf). The sequential reference takes child 0 (Python max() of incomparable
+           values keeps the first); under the engine's limits (ccz_ref.c sets max_depth) the descent is dropped */
+        if (best < 0) {
+            if (t->max_depth > 0) { t->cur_leaf = NULL; if (depth_out) *depth_out = depth; return XQ_SELECT_NAN; }
+            best = 0;
         }
         if (t->timing) {
             double p0 = now_s();
@@ -194,6 +202,7 @@ int xq_mcts_select(xq_mcts *t, const xq_board *root_board, xq_board *leaf_out, i
             xq_push(leaf_out, xq_move_from(n->act[best]), xq_move_to(n->act[best]));
         n = n->child[best];
         depth++;
+        if (t->max_depth > 0 && depth >= t->max_depth) { t->cur_leaf = NULL; if (depth_out) *depth_out = depth; return XQ_SELECT_DEPTH; }
     }
     if (t->timing) { t->t_rules += tr; t->t_tree += now_s() - t0 - tr; }
     t->cur_leaf = n;
@@ -234,6 +243,16 @@ void xq_mcts_expand_backup(xq_mcts *t, const xq_board *leaf, int k, const uint16
     t->cur_leaf = NULL;
 }
 
+/* the leaf chosen by xq_mcts_select stays unexpanded (the engine's node pool is full, ccz_ref.c): the evaluator's value is backed
+   up as after an expansion (mcts.py:129) */
+void xq_mcts_backup_unexpanded(xq_mcts *t, float value)
+{
+    node_update_recursive(t->cur_leaf, 1, -value, 0.0, t->value_f16);
+    t->cur_leaf = NULL;
+}
+
+void xq_mcts_set_max_depth(xq_mcts *t, int max_depth) { t->max_depth = max_depth; }
+
 void xq_mcts_playout(xq_mcts *t, const xq_board *root_board, xq_eval_fn fn, void *user)
 {
     xq_board leaf;
@@ -241,7 +260,7 @@ void xq_mcts_playout(xq_mcts *t, const xq_board *root_board, xq_eval_fn fn, void
     float prob[XQ_MAX_LEGAL];
     float value = 0.0f;
     int k, depth;
-    xq_mcts_select(t, root_board, &leaf, &depth);
+    if (xq_mcts_select(t, root_board, &leaf, &depth)) return; /* a dropped descent: no leaf, no visit */
     if (t->timing) {
         double p0 = now_s();
         k = xq_legal_ids(&leaf, ids);

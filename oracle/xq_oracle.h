@@ -125,7 +125,15 @@ void xq_mcts_update_with_move(xq_mcts *t, int move_id); /* -1 resets (mcts.py:16
 int xq_mcts_root_children(const xq_mcts *t, int32_t *acts, int32_t *visits, float *q, float *p);
 int xq_mcts_root_visits(const xq_mcts *t);
 int64_t xq_mcts_node_count(const xq_mcts *t);
-/* step-wise twin of the batched engine: select (returns leaf board), then expand/backup */
+/* step-wise twin of the batched engine: select (returns leaf board), then expand/backup. xq_mcts_select returns 0 with a leaf, or
+   -- only after xq_mcts_set_max_depth(> 0), the engine's limits -- the reason the descent was dropped (no leaf, nothing to back up):
+   at some node no child's score compares (NaN priors), or the path would reach max_depth moves. Without it (0, the default) the
+   search is the reference's: unbounded, and Python's max() of incomparable scores keeps child 0 */
+#define XQ_SELECT_NAN 1
+#define XQ_SELECT_DEPTH 2
+void xq_mcts_set_max_depth(xq_mcts *t, int max_depth);
+/* the selected leaf is not expanded (a bounded node pool is full); its value is backed up all the same */
+void xq_mcts_backup_unexpanded(xq_mcts *t, float value);
 int xq_mcts_select(xq_mcts *t, const xq_board *root_board, xq_board *leaf_out, int *depth_out);
 void xq_mcts_expand_backup(xq_mcts *t, const xq_board *leaf, int k, const uint16_t *ids,
                            const float *prob, float value);
