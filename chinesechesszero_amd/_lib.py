@@ -88,6 +88,10 @@ class ExplorationStats(C.Structure):
     _fields_ = [("explored_moves", C.c_int64), ("forced_selections", C.c_int64), ("visits_pruned", C.c_int64), ("children_pruned", C.c_int64)]
 
 
+class GumbelStats(C.Structure):
+    _fields_ = [("gumbel_moves", C.c_int64), ("considered_sum", C.c_int64), ("offvisit_moves", C.c_int64)]
+
+
 class SolverStats(C.Structure):
     _fields_ = [("nodes_proven", C.c_int64), ("proven_stops", C.c_int64), ("roots_proven", C.c_int64)]
 
@@ -132,6 +136,10 @@ PROTOTYPES = {
     "ccz_set_root_exploration": (C.c_int, [_P, _P, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32]),
     "ccz_get_exploration_stats": (C.c_int, [_P, _P, C.POINTER(ExplorationStats)]),
     "ccz_root_noise": (C.c_int, [_P, _P, _P, _P]),
+    "ccz_set_gumbel": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double]),
+    "ccz_get_gumbel_stats": (C.c_int, [_P, _P, C.POINTER(GumbelStats)]),
+    "ccz_gumbel_root": (C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
+    "ccz_gumbel_sequence": (C.c_int, [_P, C.c_int32, C.c_int32, _P]),
     "ccz_set_solver": (C.c_int, [_P, _P, C.c_int32]),
     "ccz_root_proof": (C.c_int, [_P, _P, _P, _P, _P, _P]),
     "ccz_get_solver_stats": (C.c_int, [_P, _P, C.POINTER(SolverStats)]),

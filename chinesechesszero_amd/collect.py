@@ -508,7 +508,7 @@ class CollectPipeline:
                  finalize_every: int = 0, on_playout=None, max_plies: int = 0, eval_cache_log2: int | None = None, gatherer=None,
                  dense_shards: bool = False, replay_plies: int = 0, train_every: int = 0, train_batch: int = BATCH_SIZE,
                  playout_cap_fast: int = 0, playout_cap_prob: float | None = None, resign=None, value_q_weight: float = 0.0,
-                 root_exploration=None, solver: bool = False):
+                 root_exploration=None, solver: bool = False, gumbel=None):
         self.solver = bool(solver)     # the MCTS-solver in the search of the batched path (only the search changes)
         if self.solver and n_boards <= 1:
             raise ValueError("the solver option of the collector runs on the batched path: n_boards must be > 1")
@@ -553,6 +553,15 @@ class CollectPipeline:
             if n_boards <= 1:
                 raise ValueError("root exploration runs on the batched path: n_boards must be > 1")
             self.root_exploration = dict(root_exploration)
+        # Gumbel root search (``gumbel``: True, or a dict of SelfPlayEngine.set_gumbel's arguments; None = off): sequential halving at
+        # the root, pi' from the completed Q as the policy target of every move
+        self.gumbel = None
+        if gumbel is not None and gumbel is not False:
+            if n_boards <= 1:
+                raise ValueError("the Gumbel root search runs on the batched path: n_boards must be > 1")
+            if root_exploration is not None:
+                raise ValueError("gumbel and root_exploration exclude each other: the Gumbel draw is the root's exploration")
+            self.gumbel = dict(gumbel) if isinstance(gumbel, dict) else {}
         self.value_q_weight = float(value_q_weight)
         if not 0.0 <= self.value_q_weight <= 1.0:
             raise ValueError(f"value_q_weight must be in [0, 1] (got {value_q_weight})")
@@ -685,7 +694,8 @@ class CollectPipeline:
                                             c_puct=self.c_puct, temp=self.temp, seed=self.seed, board_id_base=rank * self.n_boards,
                                             device=self.device, reference_quirks=self.reference_quirks, max_plies=self.max_plies,
                                             playout_cap=self.playout_cap, resign=getattr(self, "resign", None),
-                                            root_exploration=getattr(self, "root_exploration", None), solver=getattr(self, "solver", False))
+                                            root_exploration=getattr(self, "root_exploration", None), solver=getattr(self, "solver", False),
+                                            gumbel=getattr(self, "gumbel", None))
             if getattr(self, "_viewer", None) is not None:
                 self.selfplay.watch(0, self._viewer)
         for _ in range(n_moves):
@@ -886,6 +896,12 @@ class CollectPipeline:
         e = self.selfplay.engine
         return format_exploration(e.exploration_stats(), e.stats()["sims"])
 
+    def gumbel_report(self) -> str:
+        """The Gumbel part of the periodic log line (empty with the feature off; syncs)."""
+        if getattr(self, "gumbel", None) is None or getattr(self, "selfplay", None) is None:
+            return ""
+        return format_gumbel(self.selfplay.engine.gumbel_stats())
+
     def drain_exchange(self, gatherer):
         """End of a multi-rank collection with an asynchronous exchange: blocking, every rank calls it; afterwards every record of
         every rank has reached rank 0's store."""
@@ -920,7 +936,7 @@ class CollectPipeline:
                 while max_calls <= 0 or calls < max_calls:
                     iters = self.collect_data(is_shown=is_shown)
                     calls += 1
-                    log(f"Episode {iters}, steps {self.episode_len}" + self.resign_report() + self.exploration_report() + self.solver_report())
+                    log(f"Episode {iters}, steps {self.episode_len}" + self.resign_report() + self.exploration_report() + self.gumbel_report() + self.solver_report())
             except KeyboardInterrupt:
                 log("Exit")
             if self.gatherer is not None and hasattr(self.gatherer, "flush_iter") and self.selfplay is not None:
@@ -944,6 +960,15 @@ def format_exploration(x: dict, sims: int) -> str:
     forced = f"{x['forced_selections'] / n:.2f}" if n else "n/a"
     share = f"{x['visits_pruned'] / sims:.4f}" if sims else "n/a"
     return f", explored moves {n}, forced selections per move {forced}, pruned share of visits {share} ({x['children_pruned']} children dropped)"
+
+
+def format_gumbel(x: dict) -> str:
+    """``x`` = ``SelfPlayEngine.gumbel_stats()``: the moves played by the Gumbel root rule, the mean number of moves considered, and the
+    share of them whose played move was not the most visited one."""
+    n = x["gumbel_moves"]
+    m = f"{x['considered_sum'] / n:.2f}" if n else "n/a"
+    off = f"{x['offvisit_moves'] / n:.4f}" if n else "n/a"
+    return f", gumbel moves {n}, mean considered {m}, off-visit share {off}"
 
 
 def build_parser():
@@ -983,6 +1008,14 @@ def build_parser():
     parser.add_argument("--forced-playouts", type=float, default=None, help=f"... forced playouts: a root child is searched until N >= sqrt(k P' S) "
                         f"(default k = {FORCED_PLAYOUTS}, KataGo's; 0 = none)")
     parser.add_argument("--no-target-pruning", action="store_true", default=False, help="... keep the forced visits in the recorded policy targets")
+    parser.add_argument("--gumbel", action="store_true", default=False, help="batched path: Gumbel root search -- one Gumbel draw per move, sequential "
+                        "halving over the considered moves within the move's simulations, the winner is played and pi' = softmax(logits + "
+                        "sigma(completed Q)) is the recorded policy target. With --playout-cap-fast the pi' of a fast ply is a valid target too "
+                        "(it improves on the prior at any simulation count); such plies are still flagged and the trainer treats the flag as before. "
+                        "Not with --root-noise-eps")
+    parser.add_argument("--gumbel-considered", type=int, default=None, help=f"... moves considered at the root, 2..128 (default {GUMBEL_CONSIDERED})")
+    parser.add_argument("--gumbel-c-visit", type=float, default=None, help=f"... c_visit of sigma, >= 0 (default {GUMBEL_C_VISIT})")
+    parser.add_argument("--gumbel-c-scale", type=float, default=None, help=f"... c_scale of sigma, >= 0 (default {GUMBEL_C_SCALE})")
     parser.add_argument("--solver", action="store_true", default=False, help="batched path: search with the MCTS-solver (decided positions are proven "
                         "in the tree and cost no evaluator row); sampling, records and targets are as without it")
     parser.add_argument("--value-q-weight", type=float, default=0.0, help="with --train-every: weight of the recorded root value q in the value "
@@ -992,12 +1025,15 @@ def build_parser():
 
 RESIGN_MOVES, RESIGN_MIN_PLY, RESIGN_PLAYON = 2, 30, 0.1
 FORCED_PLAYOUTS = 2.0
+GUMBEL_CONSIDERED, GUMBEL_C_VISIT, GUMBEL_C_SCALE = 16, 50.0, 1.0
 
 
 def parse_args(argv=None):
     """Parse the command line; refuses ``--resign-moves`` / ``--resign-min-ply`` / ``--resign-playon`` without ``--resign-threshold``
     (they would silently do nothing), and likewise ``--root-noise-alpha`` / ``--forced-playouts`` / ``--no-target-pruning`` without
-    ``--root-noise-eps``. ``args.resign`` / ``args.root_exploration`` are the dicts for ``CollectPipeline(...)`` or None."""
+    ``--root-noise-eps``, and ``--gumbel-considered`` / ``--gumbel-c-visit`` / ``--gumbel-c-scale`` without ``--gumbel``; ``--gumbel``
+    with ``--root-noise-eps`` is refused too. ``args.resign`` / ``args.root_exploration`` / ``args.gumbel_cfg`` are the dicts for
+    ``CollectPipeline(...)`` or None."""
     parser = build_parser()
     args = parser.parse_args(argv)
     extras = {"--resign-moves": args.resign_moves, "--resign-min-ply": args.resign_min_ply, "--resign-playon": args.resign_playon}
@@ -1030,6 +1066,28 @@ def parse_args(argv=None):
         args.root_exploration = {"eps": args.root_noise_eps, "alpha": args.root_noise_alpha,
                                  "forced_k": FORCED_PLAYOUTS if args.forced_playouts is None else args.forced_playouts,
                                  "prune_targets": not args.no_target_pruning}
+    extras = {"--gumbel-considered": args.gumbel_considered, "--gumbel-c-visit": args.gumbel_c_visit, "--gumbel-c-scale": args.gumbel_c_scale}
+    args.gumbel_cfg = None
+    if not args.gumbel:
+        given = [k for k, v in extras.items() if v is not None]
+        if given:
+            parser.error(f"{', '.join(given)} without --gumbel: the Gumbel root search is off")
+    else:
+        if args.root_noise_eps is not None:
+            parser.error("--gumbel with --root-noise-eps: the Gumbel draw is the root's exploration, the two exclude each other")
+        if args.gumbel_considered is not None and not 2 <= args.gumbel_considered <= 128:
+            parser.error(f"--gumbel-considered must be in 2..128 (got {args.gumbel_considered})")
+        for name, v in (("--gumbel-c-visit", args.gumbel_c_visit), ("--gumbel-c-scale", args.gumbel_c_scale)):
+            if v is not None and not (v >= 0.0 and v != float("inf")):
+                parser.error(f"{name} must be finite and >= 0 (got {v})")
+        if args.boards <= 1:
+            parser.error("--gumbel runs on the batched path: --boards must be > 1")
+        if args.playout < 1:
+            parser.error(f"--gumbel needs --playout >= 1 (got {args.playout})")
+        args.gumbel_cfg = {"n_sims": args.playout,
+                           "max_considered": GUMBEL_CONSIDERED if args.gumbel_considered is None else args.gumbel_considered,
+                           "c_visit": GUMBEL_C_VISIT if args.gumbel_c_visit is None else args.gumbel_c_visit,
+                           "c_scale": GUMBEL_C_SCALE if args.gumbel_c_scale is None else args.gumbel_c_scale}
     return args
 
 
@@ -1062,7 +1120,7 @@ if __name__ == "__main__":
                            eval_cache_log2=args.eval_cache_log2, gatherer=gatherer, replay_plies=args.replay_plies,
                            train_every=args.train_every, train_batch=args.train_batch, playout_cap_fast=args.playout_cap_fast,
                            playout_cap_prob=args.playout_cap_prob, resign=args.resign, value_q_weight=args.value_q_weight,
-                           root_exploration=args.root_exploration, solver=args.solver)
+                           root_exploration=args.root_exploration, solver=args.solver, gumbel=args.gumbel_cfg)
     if world > 1:
         from .launch import guarded
 

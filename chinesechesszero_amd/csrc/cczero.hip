@@ -83,6 +83,7 @@ struct ccz_engine {
     uint64_t salt[2] = {0, 0};
     bool budgets_on = false;       // ccz_set_budgets / ccz_draw_budgets (off: every budget INT32_MAX, every target 1)
     bool explore_on = false;       // ccz_set_root_exploration(enabled): the host's shadow of ExploreCfg.enabled (scouts are refused with it)
+    bool gumbel_on = false;        // ccz_set_gumbel(enabled): the host's shadow of GumbelCfg.enabled (scouts and root exploration are refused with it)
     // MCTS-solver (ccz_set_solver): the proof bytes [B][2][cap] (allocated by the first call that turns it on), the host's shadow of
     // SolverCfg.enabled, staging of ccz_root_proof (state [B], dist [B], child state [B][128], child dist [B][128])
     uint8_t *proof = nullptr, *st_proof = nullptr;
@@ -308,6 +309,14 @@ int ccz_create(const ccz_config *cfg, ccz_engine **out)
     ALLOC(sv_cfg, 1); // zeroed: solver off, no proof array
     d.sv_cfg = sv_cfg;
     ALLOC(d.sv_stats, B);
+    GumbelCfg *gm_cfg = nullptr;
+    ALLOC(gm_cfg, 1); // zeroed: Gumbel root search off
+    d.gm_cfg = gm_cfg;
+    ALLOC(d.gm_g, B * kMaxLegal);
+    ALLOC(d.gm_logit, B * kMaxLegal);
+    ALLOC(d.gm_n0, B * kMaxLegal);
+    ALLOC(d.gm_stamp, B * 4);
+    ALLOC(d.gm_stats, B);
     ALLOC(d.rec_ids, B * d.pi_cap);
     ALLOC(d.rec_pi, B * d.pi_cap);
     ALLOC(d.stats, B);
@@ -503,6 +512,7 @@ int ccz_set_scouts(ccz_engine *e, int32_t n_scouts)
     if (n_scouts && !e->d.cache) return fail(-1, "ccz_set_scouts: scouts work through the evaluation cache (ccz_config.eval_cache_log2)");
     if (n_scouts && e->budgets_on) return fail(-1, "ccz_set_scouts: not while simulation budgets are on (ccz_set_budgets(NULL) turns them off)");
     if (n_scouts && e->explore_on) return fail(-1, "ccz_set_scouts: not while root exploration is on (ccz_set_root_exploration)");
+    if (n_scouts && e->gumbel_on) return fail(-1, "ccz_set_scouts: not while the Gumbel root search is on (ccz_set_gumbel)");
     e->active = n_scouts ? e->d.B - n_scouts : 0;
     return 0;
 }
@@ -719,6 +729,7 @@ int ccz_set_root_exploration(ccz_engine *e, void *stream, int32_t enabled, doubl
     if (!(alpha > 0.0 && std::isfinite(alpha))) return fail(-1, "ccz_set_root_exploration: alpha %g must be finite and > 0", alpha);
     if (!(forced_k >= 0.0 && std::isfinite(forced_k))) return fail(-1, "ccz_set_root_exploration: forced_k %g must be finite and >= 0", forced_k);
     if (enabled && e->active > 0) return fail(-1, "ccz_set_root_exploration: not with scout slots (ccz_set_scouts): the one-game path keeps the reference's search");
+    if (enabled && e->gumbel_on) return fail(-1, "ccz_set_root_exploration: not while the Gumbel root search is on (ccz_set_gumbel): it has its own root rule");
     ExploreCfg v;
     v.enabled = enabled ? 1 : 0;
     v.prune = prune_targets ? 1 : 0;
@@ -745,6 +756,82 @@ int ccz_get_exploration_stats(ccz_engine *e, void *stream, ccz_exploration_stats
         out->visits_pruned += (int64_t)b.visits_pruned;
         out->children_pruned += (int64_t)b.children_pruned;
     }
+    return 0;
+}
+
+int ccz_set_gumbel(ccz_engine *e, void *stream, int32_t enabled, int32_t n_sims, int32_t max_considered, double c_visit, double c_scale)
+{
+    NEED(e);
+    if (n_sims < 1) return fail(-1, "ccz_set_gumbel: n_sims %d must be >= 1", n_sims);
+    if (max_considered < 2 || max_considered > kMaxLegal) return fail(-1, "ccz_set_gumbel: max_considered %d must be in 2..%d", max_considered, kMaxLegal);
+    if (!(c_visit >= 0.0 && std::isfinite(c_visit))) return fail(-1, "ccz_set_gumbel: c_visit %g must be finite and >= 0", c_visit);
+    if (!(c_scale >= 0.0 && std::isfinite(c_scale))) return fail(-1, "ccz_set_gumbel: c_scale %g must be finite and >= 0", c_scale);
+    if (enabled && e->active > 0) return fail(-1, "ccz_set_gumbel: not with scout slots (ccz_set_scouts): the one-game path keeps the reference's search");
+    if (enabled && e->explore_on) return fail(-1, "ccz_set_gumbel: not while root exploration is on (ccz_set_root_exploration)");
+    GumbelCfg v;
+    v.enabled = enabled ? 1 : 0;
+    v.n_sims = n_sims;
+    v.max_considered = max_considered;
+    v.pad = 0;
+    v.c_visit = c_visit;
+    v.c_scale = c_scale;
+    const int n = 4 * e->d.B;
+    hipLaunchKernelGGL(k_set_gumbel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, const_cast<GumbelCfg *>(e->d.gm_cfg), v, e->d.gm_stamp, n);
+    HIP_TRY(hipGetLastError());
+    e->gumbel_on = enabled != 0;
+    return 0;
+}
+
+int ccz_get_gumbel_stats(ccz_engine *e, void *stream, ccz_gumbel_stats *out)
+{
+    NEED(e);
+    if (!out) return fail(-1, "ccz_get_gumbel_stats: null output");
+    std::vector<GumbelBoardStats> st;
+    if (const int rc = fetch_board_stats(e, (hipStream_t)stream, e->d.gm_stats, st)) return rc;
+    memset(out, 0, sizeof *out);
+    for (const GumbelBoardStats &b : st) {
+        out->gumbel_moves += (int64_t)b.moves;
+        out->considered_sum += (int64_t)b.considered;
+        out->offvisit_moves += (int64_t)b.offvisit;
+    }
+    return 0;
+}
+
+static int fetch_meta(ccz_engine *e, hipStream_t s);
+
+int ccz_gumbel_root(ccz_engine *e, void *stream, double *g_host, double *logit_host, int32_t *n0_host, int32_t *k_host, int32_t *n_eff_host)
+{
+    NEED(e);
+    if (!k_host) return fail(-1, "ccz_gumbel_root: null k output");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t B = (size_t)e->d.B;
+    std::vector<uint32_t> stamp(B * 4);
+    if (g_host) HIP_TRY(hipMemcpyAsync(g_host, e->d.gm_g, B * kMaxLegal * 8, hipMemcpyDeviceToHost, s));
+    if (logit_host) HIP_TRY(hipMemcpyAsync(logit_host, e->d.gm_logit, B * kMaxLegal * 8, hipMemcpyDeviceToHost, s));
+    if (n0_host) HIP_TRY(hipMemcpyAsync(n0_host, e->d.gm_n0, B * kMaxLegal * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(stamp.data(), e->d.gm_stamp, B * 16, hipMemcpyDeviceToHost, s));
+    const int rc = fetch_meta(e, s); // syncs
+    if (rc) return rc;
+    for (size_t b = 0; b < B; ++b) { // a row filled for an earlier move (or never) is no row of this one: k = 0, zeros
+        const bool live = stamp[4 * b] == e->h_meta[b].move_counter + 1u && stamp[4 * b + 1] <= (uint32_t)kMaxLegal;
+        const int k = live ? (int)stamp[4 * b + 1] : 0;
+        k_host[b] = k;
+        if (n_eff_host) n_eff_host[b] = live ? (int32_t)stamp[4 * b + 2] : 0;
+        for (int i = k; i < kMaxLegal; ++i) {
+            if (g_host) g_host[b * kMaxLegal + i] = 0.0;
+            if (logit_host) logit_host[b * kMaxLegal + i] = 0.0;
+            if (n0_host) n0_host[b * kMaxLegal + i] = 0;
+        }
+    }
+    return 0;
+}
+
+int ccz_gumbel_sequence(void *stream, int32_t m, int32_t n, int32_t *seq_dev)
+{
+    if (m < 0 || n < 0 || !seq_dev) return fail(-1, "ccz_gumbel_sequence: bad arguments");
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(k_gumbel_sequence, dim3(1), dim3(64), 0, (hipStream_t)stream, (int)m, (int)n, seq_dev);
+    HIP_TRY(hipGetLastError());
     return 0;
 }
 

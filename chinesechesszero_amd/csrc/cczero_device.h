@@ -92,6 +92,18 @@ struct ExploreBoardStats {
     unsigned long long explored, forced, visits_pruned, children_pruned;
 };
 
+// Gumbel root search (ccz_set_gumbel): the settings as the device reads them, and the per-board counters.
+struct GumbelCfg {
+    int32_t enabled;        // 0: the selection reads this one word and is the reference's PUCT at the root too; k_finish_move likewise
+    int32_t n_sims;         // the simulations of a move when the board has no budget
+    int32_t max_considered; // 2..128
+    int32_t pad;
+    double c_visit, c_scale;
+};
+struct GumbelBoardStats {
+    unsigned long long moves, considered, offvisit;
+};
+
 // MCTS-solver (ccz_set_solver): the settings as the device reads them, and the per-board counters. A proof byte holds the state in
 // bits 0..1 -- the view of the side to move at the node -- and the distance to the end in plies in bits 2..7 (saturating at 63; 0 for a
 // draw). The array lives behind the settings, not in Dev: it is allocated by the first ccz_set_solver(1), and a graph captured before
@@ -184,6 +196,13 @@ struct Dev {
     // ---- MCTS-solver (ccz_set_solver). "Off" is SolverCfg.enabled == 0: one word read per kernel, next to the ones above
     const SolverCfg *sv_cfg;     // [1] written by k_set_solver in stream order
     SolverBoardStats *sv_stats;  // [B]
+    // ---- Gumbel root search (ccz_set_gumbel). Always allocated; "off" is GumbelCfg.enabled == 0
+    const GumbelCfg *gm_cfg;     // [1] written by k_set_gumbel in stream order
+    double *gm_g;                // [B][128] Gumbel draw g_i of the root's child i for the move the stamp names
+    double *gm_logit;            // [B][128] det_log(P_i)
+    int32_t *gm_n0;              // [B][128] N_i when the row was filled (the kept subtree's visits)
+    uint32_t *gm_stamp;          // [B][4] (move_counter + 1, k, n_eff, m) the rows were filled for; zeros: none
+    GumbelBoardStats *gm_stats;  // [B]
 };
 __device__ __forceinline__ int plane_of(const Dev &D, int type) { return (int)((D.chanpack >> (3 * type)) & 7u); }
 __device__ __forceinline__ int type_in_plane(const Dev &D, int chan) { return (int)((D.typepack >> (3 * chan)) & 7u) + 1; }

@@ -231,6 +231,7 @@ struct Prefetch {
     int32_t budget;    // simulations the board may back up in this move (INT32_MAX: budgets off)
     int32_t move_sims; // ... and how many it has, as of the top of the kernel (this launch's backup is not in it)
     int32_t ex;        // root exploration (ccz_set_root_exploration) applies to the board's current move: on, and a policy-target move
+    int32_t gm;        // Gumbel root search (ccz_set_gumbel) is on
     SolverCfg sv;      // MCTS-solver (ccz_set_solver): on / off and where the proof bytes are
     uint32_t kidp;     // solver on: lane i: the proof byte of child i of the root (off: 0, nothing is read)
 };
@@ -275,6 +276,7 @@ __device__ __forceinline__ Prefetch prefetch_board(const Dev &D, int b, int lane
     P.budget = D.budget[b];
     P.move_sims = D.move_sims[b];
     P.ex = D.ex_cfg->enabled * (int32_t)D.target[b]; // (both words are requested with the rest: no load waits for the other)
+    P.gm = D.gm_cfg->enabled;
     P.sv = solver_cfg(D); // (requested with the rest; off: no load waits for it)
     P.kidp = 0u;
     if (P.sv.enabled) P.kidp = P.sv.proof[base + 1 + lane];
@@ -442,6 +444,166 @@ __device__ __forceinline__ float explore_prior(const ExploreCfg &xc, float p, fl
     return (float)((1.0 - xc.eps) * (double)p + xc.eps * (double)dir);
 }
 
+// ------------------------------------------------------------------ Gumbel root search (ccz_set_gumbel, include/cczero.h)
+// Entry t (0 <= t < n) of the considered-visits sequence seq(m, n): sequential halving over m moves with n simulations, written out
+// as "how many move-visits the child to visit next has". Wave-uniform arguments give a wave-uniform loop of about 2 log2(m) rounds.
+__device__ inline int gumbel_seq_at(int m, int n, int t)
+{
+    if (m <= 1) return t;
+    int L = 0;
+    while (L < 30 && (1 << L) < m) ++L;
+    long long pos = 0, v = 0;
+    int c = m;
+    for (;;) {
+        long long x = (long long)n / ((long long)L * c);
+        if (x < 1) x = 1;
+        const long long block = x * c;
+        if ((long long)t < pos + block) return (int)(v + ((long long)t - pos) / c);
+        pos += block;
+        v += x;
+        c = c / 2 > 2 ? c / 2 : 2;
+    }
+}
+
+// lowest index among the root's children `lane` (s0, if c0) and `64 + lane` (s1, if c1) whose score is the maximum; -1: nothing
+// comparable (no candidate, or NaN on every one). Wave-uniform result.
+__device__ inline int gumbel_first_max(double s0, bool c0, double s1, bool c1, int lane)
+{
+    const double ninf = -__builtin_huge_val();
+    const double a0 = (c0 && s0 == s0) ? s0 : ninf, a1 = (c1 && s1 == s1) ? s1 : ninf;
+    const double top = wave_max_f64(a0 > a1 ? a0 : a1);
+    const uint64_t h0 = __ballot(c0 && s0 == top), h1 = __ballot(c1 && s1 == top);
+    if (h0) return __ffsll((long long)h0) - 1;
+    if (h1) return 64 + __ffsll((long long)h1) - 1;
+    return -1;
+}
+__device__ inline int wave_max_i32(int v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { const int t = __shfl_xor(v, o); if (t > v) v = t; }
+    return v;
+}
+
+// The row of the board's current move for the root's children `lane` ([0]) and `64 + lane` ([1]): Gumbel draw, logit of the raw
+// prior, the visits the child had when the row was filled, and the move's n_eff and m. c[2]: those children's records as they stand.
+// store (the selection): the row is filled once per move and board, under the wave-uniform stamp test, and read back afterwards.
+// !store (k_finish_move, k_move_distribution): a board without a row gets one computed on the spot (N0 = N) and nothing is written.
+struct GumbelRow { double g[2], logit[2]; int n0[2]; int n_eff, m; };
+__device__ inline GumbelRow gumbel_row(const Dev &D, const GumbelCfg &gc, int b, int lane, int k, uint32_t move_counter, const NodeA *c,
+                                       int sims_done, int budget, bool store)
+{
+    GumbelRow r;
+    uint32_t *stp = D.gm_stamp + (size_t)b * 4;
+    const size_t o = (size_t)b * kMaxLegal;
+    const uint32_t st0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)stp[0]), st1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)stp[1]);
+    if (st0 == move_counter + 1u && st1 == (uint32_t)k) {
+        r.n_eff = __builtin_amdgcn_readfirstlane((int)stp[2]);
+        r.m = __builtin_amdgcn_readfirstlane((int)stp[3]);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int i = 64 * h + lane;
+            r.g[h] = i < k ? D.gm_g[o + i] : 0.0;
+            r.logit[h] = i < k ? D.gm_logit[o + i] : 0.0;
+            r.n0[h] = i < k ? D.gm_n0[o + i] : 0;
+        }
+        return r;
+    }
+    const uint64_t gid = D.board_id_base + (uint64_t)b;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int i = 64 * h + lane;
+        r.g[h] = 0.0; r.logit[h] = 0.0; r.n0[h] = 0;
+        if (i < k) {
+            double ua, ub;
+            uniform2(D.seed, gid, move_counter, (uint32_t)i, 0xfffffu, ua, ub); // (the Gamma loop of child i stops below draw 0xffff2)
+            r.g[h] = -det_log(-det_log(ua));
+            r.logit[h] = det_log((double)c[h].P);
+            r.n0[h] = c[h].N;
+            if (store) { D.gm_g[o + i] = r.g[h]; D.gm_logit[o + i] = r.logit[h]; D.gm_n0[o + i] = r.n0[h]; }
+        }
+    }
+    const int n_b = budget == 0x7fffffff ? gc.n_sims : budget;
+    r.n_eff = n_b - sims_done > 1 ? n_b - sims_done : 1;
+    r.m = gc.max_considered < k ? gc.max_considered : k;
+    if (store && lane == 0) { stp[0] = move_counter + 1u; stp[1] = (uint32_t)k; stp[2] = (uint32_t)r.n_eff; stp[3] = (uint32_t)r.m; }
+    return r;
+}
+
+// sigma_i = (c_visit + max_j N_j) * c_scale * cq_i for the children `lane` and `64 + lane` (c[2]), cq the completed Q in [0, 1]: the
+// child's own (Q_i + 1) / 2 when visited, else v_mix, the prior-weighted mean of the visited children's mixed with the root's own
+// mean. Float64; the two prior-weighted sums run in child order on lane 0. s_w: 128 doubles, s_p: 128 floats of LDS scratch.
+__device__ inline void gumbel_sigma(const GumbelCfg &gc, int lane, int k, const NodeA *c, float rootQ, double *s_w, float *s_p, double *sig)
+{
+    double qt[2];
+    int nsum = 0, nmax = 0;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int i = 64 * h + lane;
+        qt[h] = 0.0;
+        if (i < k) {
+            qt[h] = ((double)c[h].Q + 1.0) / 2.0;
+            s_w[i] = (double)c[h].P * qt[h];
+            s_p[i] = c[h].P;
+            nsum += c[h].N;
+            if (c[h].N > nmax) nmax = c[h].N;
+        }
+    }
+    const uint64_t v0m = __ballot(lane < k && c[0].N > 0), v1m = __ballot(64 + lane < k && c[1].N > 0);
+    wave_sync();
+    const double S = (double)__builtin_amdgcn_readlane(wave_incl_scan(nsum, lane), 63);
+    nmax = wave_max_i32(nmax);
+    double vmix = (-(double)rootQ + 1.0) / 2.0;
+    if (lane == 0 && (v0m | v1m)) {
+        double wsum = 0.0, psum = 0.0;
+        for (int i = 0; i < k; ++i)
+            if (((i < 64 ? v0m : v1m) >> (i & 63)) & 1ull) { wsum += s_w[i]; psum += (double)s_p[i]; }
+        vmix = (vmix + S * wsum / psum) / (1.0 + S);
+    }
+    vmix = __shfl(vmix, 0);
+    wave_sync();
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int i = 64 * h + lane;
+        const double cq = (i < k && c[h].N > 0) ? qt[h] : vmix;
+        sig[h] = (gc.c_visit + (double)nmax) * gc.c_scale * cq;
+    }
+}
+
+// The root rule of the selection: which of the root's children are candidates (masks c0: children 0..63, c1: 64..127) and their
+// scores g + logit + sigma (s0: child `lane`, s1: child `64 + lane`). kids = the root's children as they stand in memory.
+struct GumbelPick { double s0, s1; uint64_t c0, c1; };
+__device__ inline GumbelPick gumbel_select(const Dev &D, const GumbelCfg &gc, int b, int lane, int k, uint32_t move_counter, const NodeA *kids,
+                                           float rootQ, int sims_done, int budget, double *s_w, float *s_p)
+{
+    k = __builtin_amdgcn_readfirstlane(k);
+    move_counter = (uint32_t)__builtin_amdgcn_readfirstlane((int)move_counter);
+    NodeA c[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) c[h] = 64 * h + lane < k ? kids[CCZ_IDX(D, 64 * h + lane, D.cap)] : NodeA{0, 0.0f, 0.0f, -1};
+    const GumbelRow r = gumbel_row(D, gc, b, lane, k, move_counter, c, sims_done, budget, true);
+    double sig[2];
+    gumbel_sigma(gc, lane, k, c, rootQ, s_w, s_p, sig);
+    const int M0 = c[0].N - r.n0[0], M1 = c[1].N - r.n0[1]; // (past k: 0 - 0)
+    const int t = __builtin_amdgcn_readlane(wave_incl_scan(M0 + M1, lane), 63);
+    const bool in0 = lane < k, in1 = 64 + lane < k;
+    GumbelPick p;
+    p.s0 = r.g[0] + r.logit[0] + sig[0];
+    p.s1 = r.g[1] + r.logit[1] + sig[1];
+    p.c0 = 0ull; p.c1 = 0ull;
+    if (t < r.n_eff) {
+        const int want = gumbel_seq_at(r.m, r.n_eff, t);
+        p.c0 = __ballot(in0 && M0 == want);
+        p.c1 = __ballot(in1 && M1 == want);
+    }
+    if ((p.c0 | p.c1) == 0ull) {
+        const int a0 = in0 ? M0 : (int)0x80000000, a1 = in1 ? M1 : (int)0x80000000;
+        const int mx = wave_max_i32(a0 > a1 ? a0 : a1);
+        p.c0 = __ballot(in0 && M0 == mx);
+        p.c1 = __ballot(in1 && M1 == mx);
+    }
+    return p;
+}
+
 // One wave: PUCT descent from the root of board b, leaf rules, evaluator input. Per tree level there is
 // ONE dependent global load round (the children's 16-B NodeA records + their move/count words); the
 // chosen child's own N / first_child / count are broadcast from the winning lane, not re-read.
@@ -501,11 +663,28 @@ __device__ inline void select_phase(const Dev &D, int b, int lane, uint16_t *lea
         xc = *D.ex_cfg;
         explore_dir(D, xc, b, lane, (int)(nb >> 16), m.move_counter, A + pa.fc, (double *)sh.S.cand, xd0, xd1);
     }
+    // ---- Gumbel root search: candidates and scores of the root's children (off: the one prefetched word tested here). The children
+    // are read as they stand in memory: the fence in front of this phase made this launch's backup visible
+    bool gm = false;
+    GumbelPick gp;
+    gp.s0 = 0.0; gp.s1 = 0.0; gp.c0 = 0ull; gp.c1 = 0ull;
+    if (EX && __builtin_amdgcn_readfirstlane(P.gm) && (nb >> 16) == 0u) {
+        // an unexpanded root is a fresh tree (reset, set position, a refused move): whatever row the board holds for this move counter
+        // belonged to another tree
+        if (lane == 0) D.gm_stamp[(size_t)b * 4] = 0u;
+    } else if (EX && __builtin_amdgcn_readfirstlane(P.gm)) {
+        gm = true;
+        const GumbelCfg gc = *D.gm_cfg;
+        gp = gumbel_select(D, gc, b, lane, (int)(nb >> 16), m.move_counter, A + pa.fc, pa.Q, P.move_sims + (tp.active ? 1 : 0), P.budget,
+                           (double *)sh.S.cand, (float *)sh.S.list);
+    }
 
     // ---- PUCT descent (mcts.py:105-111, 41-61). Compiled twice, chosen by the wave-uniform solver word: with the solver off the
-    // loop is the one it was (no proof byte in it); SV: std::true_type / std::false_type
-    const auto descend = [&](auto SV) {
+    // loop is the one it was (no proof byte in it); SV: std::true_type / std::false_type. Likewise GM, the Gumbel root: off, no word of
+    // it is in the loop
+    const auto descend = [&](auto SV, auto GM) {
         constexpr bool SOLVER = decltype(SV)::value;
+        constexpr bool GUMBEL = decltype(GM)::value;
         for (;;) {
             const int nc = (int)(nb >> 16);
             if (nc == 0) break;
@@ -515,13 +694,16 @@ __device__ inline void select_phase(const Dev &D, int b, int lane, uint16_t *lea
             float bQ = 0.0f;
             uint32_t bw = 0, bP = 0;
             bool bF = false;
-            const bool exroot = EX && ex && depth == 0;
+            const bool exroot = EX && !GUMBEL && ex && depth == 0; // (the two exclude each other)
+            const bool gmroot = GUMBEL && depth == 0;
             for (int c0 = 0; c0 < nc; c0 += 64) {
                 const int i = c0 + lane;
                 if (i < nc) {
                     NodeA c;
                     uint32_t w, pb = 0u; // pb: the candidate's proof byte, loaded in the round of its record (solver off: none)
-                    if (depth == 0 && c0 == 0 && pa.fc == 1) { // root children: prefetched (+ this launch's backup)
+                    // root children: prefetched (+ this launch's backup). The patch of a root expanded in this launch knows child 0's
+                    // move only (PUCT takes the first unvisited child): the Gumbel root reads the records as they stand in memory
+                    if (depth == 0 && c0 == 0 && pa.fc == 1 && !gmroot) {
                         c = P.kid;
                         w = P.kidw;
                         if (SOLVER) pb = P.kidp;
@@ -544,8 +726,10 @@ __device__ inline void select_phase(const Dev &D, int b, int lane, uint16_t *lea
                         pp = explore_prior(xc, c.P, c0 ? xd1 : xd0);
                         fsel = xc.forced_k > 0.0 && c.N > 0 && (double)c.N < sqrt(xc.forced_k * (double)pp * (double)(pa.N - 1));
                     }
-                    const double sc = (c.N == 0 || fsel) ? __builtin_huge_val()
-                                                         : (double)c.Q + (double)(D.c_puct * pp) * sqrtNp / (double)(1 + c.N);
+                    double sc = (c.N == 0 || fsel) ? __builtin_huge_val()
+                                                   : (double)c.Q + (double)(D.c_puct * pp) * sqrtNp / (double)(1 + c.N);
+                    // Gumbel root: g + logit + sigma of a candidate; every other child is out of the comparison (like a NaN score)
+                    if (gmroot) sc = (((c0 ? gp.c1 : gp.c0) >> lane) & 1ull) ? (c0 ? gp.s1 : gp.s0) : __builtin_nan("");
                     if (sc > best) { best = sc; besti = i; bN = c.N; bQ = c.Q; bfc = c.fc; bw = w; bF = fsel; if (SOLVER) bP = pb; }
                 }
             }
@@ -577,8 +761,11 @@ __device__ inline void select_phase(const Dev &D, int b, int lane, uint16_t *lea
             }
         }
     };
-    if (solver) descend(std::true_type{});
-    else descend(std::false_type{});
+    if (EX && gm) {
+        if (solver) descend(std::true_type{}, std::true_type{});
+        else descend(std::false_type{}, std::true_type{});
+    } else if (solver) descend(std::true_type{}, std::false_type{});
+    else descend(std::false_type{}, std::false_type{});
     wave_sync();
     if (bad) {
         if (lane == 0) D.leaf_status[b] = CCZ_LEAF_SKIP;
@@ -1505,6 +1692,51 @@ __device__ __forceinline__ bool move_target_pi(const Dev &D, int b, int lane, co
     return explored;
 }
 
+// The move boundary of a board searched with the Gumbel root rule (ccz_set_gumbel): s_pi[k] = pi' = softmax(logit + sigma) with the
+// deterministic exp, the sum in child order on lane 0; returns the child the rule plays: the first maximum of g + logit + sigma among
+// the children of most move-visits (wave-uniform). played: the forced move's child, or -1. count: the board's counters move
+// (k_finish_move) or not (k_move_distribution). s_w [128] doubles / s_p [128] floats: LDS scratch.
+__device__ inline int gumbel_targets(const Dev &D, const GumbelCfg &gc, int b, int lane, int k, uint32_t move_counter, const RootView &rv,
+                                     double *s_w, float *s_p, double *s_pi, int played, bool count)
+{
+    NodeA c[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) c[h] = 64 * h + lane < k ? rv.A[CCZ_IDX(D, rv.root.fc + 64 * h + lane, D.cap)] : NodeA{0, 0.0f, 0.0f, -1};
+    const GumbelRow r = gumbel_row(D, gc, b, lane, k, move_counter, c, 0, D.budget[b], false);
+    double sig[2];
+    gumbel_sigma(gc, lane, k, c, rv.root.Q, s_w, s_p, sig);
+    const bool in0 = lane < k, in1 = 64 + lane < k;
+    const double ninf = -__builtin_huge_val();
+    const double l0 = r.logit[0] + sig[0], l1 = r.logit[1] + sig[1];
+    const double a0 = (in0 && l0 == l0) ? l0 : ninf, a1 = (in1 && l1 == l1) ? l1 : ninf;
+    const double mx = wave_max_f64(a0 > a1 ? a0 : a1);
+    if (in0) s_pi[lane] = det_exp(l0 - mx);
+    if (in1) s_pi[64 + lane] = det_exp(l1 - mx);
+    wave_sync();
+    double sum = 0.0;
+    if (lane == 0) for (int i = 0; i < k; ++i) sum += s_pi[i];
+    sum = __shfl(sum, 0);
+    wave_sync();
+    if (in0) s_pi[lane] = s_pi[lane] / sum;
+    if (in1) s_pi[64 + lane] = s_pi[64 + lane] / sum;
+    wave_sync();
+    const int M0 = c[0].N - r.n0[0], M1 = c[1].N - r.n0[1];
+    const int b0 = in0 ? M0 : (int)0x80000000, b1 = in1 ? M1 : (int)0x80000000;
+    const int mm = wave_max_i32(b0 > b1 ? b0 : b1);
+    int choice = gumbel_first_max(r.g[0] + r.logit[0] + sig[0], in0 && M0 == mm, r.g[1] + r.logit[1] + sig[1], in1 && M1 == mm, lane);
+    if (choice < 0) { set_err(D, 32); choice = 0; } // NaN priors: no comparable child
+    if (count) {
+        const int most = gumbel_first_max((double)c[0].N, in0, (double)c[1].N, in1, lane);
+        if (lane == 0) {
+            GumbelBoardStats &gs = D.gm_stats[b];
+            gs.moves += 1;
+            gs.considered += (unsigned long long)r.m;
+            gs.offvisit += (played >= 0 ? played : choice) != most ? 1 : 0;
+        }
+    }
+    return choice;
+}
+
 __global__ __launch_bounds__(64) void k_root_children(Dev D, int32_t *k_out, uint16_t *acts, int32_t *visits,
                                                         float *q, float *prior, int32_t *root_visits,
                                                         const double *temps, double *pi_out)
@@ -1563,6 +1795,13 @@ __global__ __launch_bounds__(64) void k_move_distribution(Dev D, const double *t
     if (k == 0) { if (lane == 0) u_out[b] = __builtin_nan(""); return; }
     for (int i = lane; i < k; i += 64) s_vis[i] = rv.A[CCZ_IDX(D, rv.root.fc + i, D.cap)].N;
     __syncthreads();
+    const GumbelCfg gc = *D.gm_cfg;
+    if (gc.enabled) { // a Gumbel board draws nothing: mixed = pi', no Gamma draws, no choice uniform
+        (void)gumbel_targets(D, gc, b, lane, k, m.move_counter, rv, s_g, s_pn, s_pi, -1, false);
+        for (int i = lane; i < k; i += 64) { g[i] = 0.0; mixed[i] = s_pi[i]; }
+        if (lane == 0) u_out[b] = __builtin_nan("");
+        return;
+    }
     const bool explored = move_target_pi(D, b, lane, rv, k, m.move_counter, D.target[b], temp, s_vis, s_vp, s_q, s_pn, s_g, s_pi, false);
     sample_move(D, D.board_id_base + (uint64_t)b, m.move_counter, s_pi, s_g, k, lane, &s_choice, g, mixed, u_out + b, !explored);
 }
@@ -1736,7 +1975,13 @@ __global__ __launch_bounds__(64) void k_finish_move(Dev D, const int32_t *forced
     // ---- pi (mcts.py:162-166) and the training record. The resignation value below, ccz_root_children and the lines read the
     // counts as searched (s_vis), whatever pi is formed from.
     const int tgt = D.target[b];
-    const bool explored = move_target_pi(D, b, lane, rv, k, m.move_counter, tgt, temp, s_vis, s_vp, s_q, s_pn, s_g, s_pi, true);
+    // Gumbel root search (ccz_set_gumbel; off: this one word read): pi' and the rule's move in place of the visit softmax and the draw
+    const GumbelCfg gc = *D.gm_cfg;
+    const bool gumbel = gc.enabled && k > 0;
+    int gchoice = -1;
+    bool explored = false;
+    if (gumbel) gchoice = gumbel_targets(D, gc, b, lane, k, m.move_counter, rv, s_g, s_pn, s_pi, found, true);
+    else explored = move_target_pi(D, b, lane, rv, k, m.move_counter, tgt, temp, s_vis, s_vp, s_q, s_pn, s_g, s_pi, true);
     const size_t r = (size_t)b * D.max_plies + CCZ_IDX(D, m.ply, D.max_plies);
     if (lane < 24) ((uint32_t *)(D.rec_sq + r * 96))[lane] = ((const uint32_t *)s_sq)[lane];
     if (lane == 0) { D.rec_turn[r] = m.turn; D.rec_k[r] = (uint8_t)k; D.rec_off[r] = m.pi_used; D.rec_target[r] = (uint8_t)tgt; D.rec_hasv[r] = 0; }
@@ -1805,6 +2050,8 @@ __global__ __launch_bounds__(64) void k_finish_move(Dev D, const int32_t *forced
     // ---- move choice (mcts.py:216-229)
     if (want >= 0) {
         if (lane == 0) s_choice = found;
+    } else if (gumbel) {
+        if (lane == 0) s_choice = gchoice;
     } else {
         sample_move(D, D.board_id_base + (uint64_t)b, m.move_counter, s_pi, s_g, k, lane, &s_choice, nullptr, nullptr, nullptr, !explored);
     }
@@ -2491,6 +2738,20 @@ __global__ void k_draw_budgets(Dev D, int n, int n_full, int n_fast, double p_fu
 __global__ void k_set_resign(ResignCfg *cfg, ResignCfg v)
 {
     if (blockIdx.x == 0 && threadIdx.x == 0) *cfg = v;
+}
+
+// ccz_set_gumbel: the settings reach the device in stream order; every board's row is invalidated (n_eff and m may have changed)
+__global__ void k_set_gumbel(GumbelCfg *cfg, GumbelCfg v, uint32_t *stamps, int n)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) stamps[i] = 0u;
+    if (i == 0) *cfg = v;
+}
+
+// ccz_gumbel_sequence: seq(m, n) written out, one wave
+__global__ __launch_bounds__(64) void k_gumbel_sequence(int m, int n, int32_t *seq)
+{
+    for (int t = threadIdx.x; t < n; t += 64) seq[t] = gumbel_seq_at(m, n, t);
 }
 
 // ccz_set_root_exploration: the settings reach the device in stream order; every board's noise row is invalidated (alpha may have changed)

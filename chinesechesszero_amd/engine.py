@@ -447,6 +447,36 @@ class SelfPlayEngine:
         check(self.L.ccz_root_noise(self.h, self._stream(), _ptr(noise), _ptr(k)))
         return noise, k
 
+    # ------------------------------------------------------------------ Gumbel root search (include/cczero.h ccz_set_gumbel)
+    def set_gumbel(self, n_sims, max_considered: int = 16, c_visit: float = 50.0, c_scale: float = 1.0):
+        """Gumbel root search (Danihelka et al. 2022) on every move of every board: one Gumbel draw per root child and move,
+        sequential halving over the ``max_considered`` best of them within the move's simulations (the board's budget, else
+        ``n_sims``), the winner is played and pi' = softmax(logit + sigma(completed Q)) is recorded as the policy target --
+        fast moves of playout-cap randomisation included. Below the root the search is unchanged. ``n_sims`` None: off, the
+        state of a new engine. Not with scout slots or root exploration. No host sync."""
+        if n_sims is None:
+            check(self.L.ccz_set_gumbel(self.h, self._stream(), 0, 1, 16, 50.0, 1.0))
+            return
+        check(self.L.ccz_set_gumbel(self.h, self._stream(), 1, int(n_sims), int(max_considered), float(c_visit), float(c_scale)))
+
+    def gumbel_stats(self) -> dict:
+        """Sums over boards (``ccz_gumbel_stats``; syncs): ``gumbel_moves``, ``considered_sum`` (sum of m over them) and
+        ``offvisit_moves`` (plies whose played child is not the most visited one)."""
+        s = _lib.GumbelStats()
+        check(self.L.ccz_get_gumbel_stats(self.h, self._stream(), C.byref(s)))
+        return {f: int(getattr(s, f)) for f, _ in _lib.GumbelStats._fields_}
+
+    def gumbel_root(self):
+        """``(g float64 [B,128], logit float64 [B,128], n0 int32 [B,128], k int32 [B], n_eff int32 [B])``: the Gumbel rows of the
+        move being searched (zero past k; k = 0 on a board without a row for its current move). Syncs (tests, diagnostics)."""
+        g = np.zeros((self.B, MAX_LEGAL), np.float64)
+        logit = np.zeros((self.B, MAX_LEGAL), np.float64)
+        n0 = np.zeros((self.B, MAX_LEGAL), np.int32)
+        k = np.zeros(self.B, np.int32)
+        n_eff = np.zeros(self.B, np.int32)
+        check(self.L.ccz_gumbel_root(self.h, self._stream(), _ptr(g), _ptr(logit), _ptr(n0), _ptr(k), _ptr(n_eff)))
+        return g, logit, n0, k, n_eff
+
     # ------------------------------------------------------------------ MCTS-solver (include/cczero.h ccz_set_solver)
     def set_solver(self, enabled: bool = True):
         """Exact propagation of decided positions (Winands' MCTS-solver): a terminal leaf proves its node, a node with a lost child

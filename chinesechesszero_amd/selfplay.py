@@ -217,8 +217,12 @@ class BatchedSelfPlay:
     def __init__(self, evaluator, n_boards: int, n_playout: int = 400, c_puct: float = C_PUCT, eps: float = EPS,
                  alpha: float = ALPHA, temp: float = 1.0, seed: int = 0, board_id_base: int = 0, device: int = 0,
                  sampling: str = "device", use_graph: bool = False, version_fn=None, playout_cap=None, resign=None,
-                 root_exploration=None, solver: bool = False, **engine_kw):
-        """``solver``: search with the MCTS-solver (:meth:`SelfPlayEngine.set_solver`). Only the search changes: moves are sampled,
+                 root_exploration=None, solver: bool = False, gumbel=None, **engine_kw):
+        """``gumbel``: True, or a dict of :meth:`SelfPlayEngine.set_gumbel`'s arguments (``n_sims`` defaults to ``n_playout``;
+        ``max_considered``, ``c_visit``, ``c_scale``): Gumbel root search with sequential halving; pi' from the completed Q is the
+        recorded policy target of every move, fast moves of ``playout_cap`` included (they still carry ``REC_FAST``). Device
+        sampling only (the rule plays its own move), and not together with ``root_exploration``. None / False (default): off.
+        ``solver``: search with the MCTS-solver (:meth:`SelfPlayEngine.set_solver`). Only the search changes: moves are sampled,
         recorded and targeted as without it.
         ``playout_cap`` = ``(n_fast, p_full)``: playout-cap randomisation -- every move of every board is a full search of
         ``n_playout`` simulations with probability ``p_full``, else a fast one of ``n_fast``; fast plies carry ``REC_FAST`` in their
@@ -244,6 +248,11 @@ class BatchedSelfPlay:
             raise ValueError("resign needs sampling='device': with host sampling every move is forced, and a forced board never resigns")
         if root_exploration is not None and sampling != "device":
             raise ValueError("root_exploration needs sampling='device': the host sampler mixes Dirichlet noise into pi after the search")
+        if gumbel is not None and gumbel is not False:
+            if sampling != "device":
+                raise ValueError("gumbel needs sampling='device': the rule plays the move itself, a host-sampled move would be forced over it")
+            if root_exploration is not None:
+                raise ValueError("gumbel and root_exploration exclude each other: the Gumbel draw is the root's exploration")
         self.playout_cap = None
         if playout_cap is not None:
             n_fast, p_full = playout_cap
@@ -263,6 +272,11 @@ class BatchedSelfPlay:
         if root_exploration is not None:
             self.root_exploration = dict(root_exploration)
             self.engine.set_root_exploration(**self.root_exploration)
+        self.gumbel = None
+        if gumbel is not None and gumbel is not False:
+            self.gumbel = dict(gumbel) if isinstance(gumbel, dict) else {}
+            self.gumbel.setdefault("n_sims", n_playout)
+            self.engine.set_gumbel(**self.gumbel)
         self.solver = bool(solver)
         if self.solver:
             self.engine.set_solver(True)

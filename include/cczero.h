@@ -437,6 +437,58 @@ int ccz_get_exploration_stats(ccz_engine *e, void *stream, ccz_exploration_stats
  * k; k_host int32 [B] = the root's child count the row was filled for, 0 on a board that has no row for its current move. */
 int ccz_root_noise(ccz_engine *e, void *stream, float *noise_host, int32_t *k_host);
 
+/* ---- Gumbel root search: sequential halving at the root, completed-Q policy targets (additive to ABI 9) ----------------------------
+ * "Policy improvement by planning with Gumbel" (Danihelka et al., ICLR 2022) at the ROOT: one Gumbel draw per move, sequential halving
+ * over the considered moves, the winner is played and pi' = softmax(logits + sigma(completed Q)) is the policy target -- a target that
+ * improves on the prior at any simulation count, which the visit distribution of PUCT does not at the counts of a fast move. Below the
+ * root the descent is the reference's PUCT with the first-maximum rule. Off after ccz_create: every output of every call is then bit
+ * for bit what it is without the feature (the selection and ccz_finish_move each test one word).
+ *   ccz_set_gumbel: asynchronous on `stream`, takes effect with the next selection / ccz_finish_move. enabled = 0: off (the other
+ *     arguments are still validated). n_sims >= 1; max_considered in 2..128; c_visit and c_scale finite and >= 0 (the paper: 50, 1).
+ *     Fails while scout slots are active or root exploration is enabled; ccz_set_scouts(n > 0) and ccz_set_root_exploration(enabled =
+ *     1) fail while it is on. Every board's row (below) is invalidated.
+ * It applies to EVERY move of a running board, fast moves of playout-cap randomisation included (the target byte is recorded as
+ * before). Float64 unless said otherwise; all sums run in child index order on one lane; i = the root's children in insertion order,
+ * k their number.
+ *   1. row, filled once per move and board, at the first selection that finds the root expanded:
+ *      g_i = -det_log(-det_log(ua)), ua = the first uniform of Philox word (seed, board_id_base + b, move counter, child i, draw
+ *      0xfffff) -- the Gamma loop of child i stops below draw 0xffff2, so the Dirichlet draws, budgets, the resign lot and the choice
+ *      uniform are what they are --; logit_i = det_log((double)P_i) of the raw stored prior (P_i = 0: what det_log returns for 0, a
+ *      finite -709.09); N0_i = N_i at that moment (the kept subtree's visits; "move-visits" M_i = N_i - N0_i); n_b = the board's
+ *      budget if it has one (ccz_set_budgets / ccz_draw_budgets; INT32_MAX counts as none), else n_sims; n_eff = max(1, n_b - the
+ *      simulations of this move already backed up): n_b - 1 on a fresh root, n_b on a kept tree; m = min(max_considered, k).
+ *      A selection that finds the root unexpanded (a fresh tree: reset, set position, a refused move) drops the board's row.
+ *   2. seq(m, n), n entries: m <= 1: 0, 1, .., n - 1. Else L = ceil(log2 m), v = 0, c = m, and until n entries exist:
+ *      x = max(1, floor(n / (L c))); x times: c copies of v, v += 1; then c = max(2, floor(c / 2)). Cut to n entries.
+ *      ((4, 8): 0 0 0 0 1 1 2 2; (3, 7): 0 0 0 1 1 2 2.)
+ *   3. completed Q: S = sum N_i; qt_i = ((double)Q_i + 1) / 2 for N_i > 0 (Q_i as stored: the view of the root's side to move);
+ *      v0 = (-(double)Q_root + 1) / 2, the root's own running mean turned to its side to move;
+ *      v_mix = (v0 + S * (sum_{N_i>0} (double)P_i qt_i) / (sum_{N_i>0} (double)P_i)) / (1 + S), v_mix = v0 when no child is visited;
+ *      cq_i = qt_i if N_i > 0 else v_mix; sigma_i = (c_visit + max_j N_j) * c_scale * cq_i.
+ *   4. root selection (depth 0, in place of PUCT): t = sum M_i; if t < n_eff the candidates are the children with M_i =
+ *      seq(m, n_eff)[t]; if t >= n_eff or no child qualifies, the children with M_i = max_j M_j. The first maximum in child order
+ *      of score_i = g_i + logit_i + sigma_i among the candidates wins; NaN on every candidate: CCZ_ERR_NAN. The solver's
+ *      proven-stop rule applies to the chosen child as under PUCT.
+ *   5. ccz_finish_move: pi'_i = det_exp(s_i - max s) / sum, s_i = logit_i + sigma_i over all k children, recorded as float32 (also
+ *      under a forced move) and returned by ccz_move_distribution as `mixed` (gamma zero, u NaN). The temperature is not applied
+ *      (a bad one still refuses the board). The move, unless forced, is the first maximum of score_i among the children with M_i =
+ *      max_j M_j: no choice uniform, no Dirichlet mixing. A board whose current move has no row (the call came after the search)
+ *      uses the row it would get now (M = 0 everywhere). Resignation, ccz_root_children, ccz_root_pi and
+ *      ccz_principal_variations read the counts as searched. */
+typedef struct ccz_gumbel_stats { /* sums over boards */
+    int64_t gumbel_moves;   /* plies recorded under the Gumbel root rule                                     */
+    int64_t considered_sum; /* sum of m over those plies                                                     */
+    int64_t offvisit_moves; /* plies whose played child is not the first maximum of N                        */
+} ccz_gumbel_stats;
+int ccz_set_gumbel(ccz_engine *e, void *stream, int32_t enabled, int32_t n_sims, int32_t max_considered, double c_visit, double c_scale);
+int ccz_get_gumbel_stats(ccz_engine *e, void *stream, ccz_gumbel_stats *out); /* syncs */
+/* the rows of the move being searched (syncs; tests, diagnostics): g_host / logit_host double [B*128], n0_host int32 [B*128], zero
+ * past k; k_host int32 [B] = the root's child count the row was filled for, 0 on a board that has no row for its current move;
+ * n_eff_host int32 [B]. Any output but k_host may be NULL. */
+int ccz_gumbel_root(ccz_engine *e, void *stream, double *g_host, double *logit_host, int32_t *n0_host, int32_t *k_host, int32_t *n_eff_host);
+/* seq(m, n) of rule 2 written to seq_dev int32 [n], one wave. Stateless, asynchronous. */
+int ccz_gumbel_sequence(void *stream, int32_t m, int32_t n, int32_t *seq_dev);
+
 /* ---- MCTS-solver: exact propagation of decided positions through the tree (additive to ABI 8) ----
  * One proof byte per tree node, in a device array of its own (uint8 [B][2][max_nodes], allocated and zeroed by the first
  * ccz_set_solver(enabled = 1), which may sync; never touched while the solver is off). Bits 0..1: the state in the view of the side
