@@ -92,6 +92,11 @@ class GumbelStats(C.Structure):
     _fields_ = [("gumbel_moves", C.c_int64), ("considered_sum", C.c_int64), ("offvisit_moves", C.c_int64)]
 
 
+class SearchCfg(C.Structure):
+    _fields_ = [("enabled", C.c_int32), ("fpu_mode", C.c_int32), ("fpu_root_mode", C.c_int32), ("reserved", C.c_int32),
+                ("fpu_value", C.c_double), ("fpu_root_value", C.c_double), ("c_base", C.c_double), ("c_factor", C.c_double)]
+
+
 class SolverStats(C.Structure):
     _fields_ = [("nodes_proven", C.c_int64), ("proven_stops", C.c_int64), ("roots_proven", C.c_int64)]
 
@@ -140,6 +145,8 @@ PROTOTYPES = {
     "ccz_get_gumbel_stats": (C.c_int, [_P, _P, C.POINTER(GumbelStats)]),
     "ccz_gumbel_root": (C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
     "ccz_gumbel_sequence": (C.c_int, [_P, C.c_int32, C.c_int32, _P]),
+    "ccz_set_search": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_double, C.c_double, C.c_double]),
+    "ccz_get_search": (C.c_int, [_P, _P, C.POINTER(SearchCfg)]),
     "ccz_set_solver": (C.c_int, [_P, _P, C.c_int32]),
     "ccz_root_proof": (C.c_int, [_P, _P, _P, _P, _P, _P]),
     "ccz_get_solver_stats": (C.c_int, [_P, _P, C.POINTER(SolverStats)]),

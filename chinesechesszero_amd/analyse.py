@@ -23,6 +23,7 @@ import numpy as np
 
 from ._lib import CczError
 from .game import Board
+from .searchcfg import add_search_args, mean_leaf_depth, search_from_args
 
 
 def cp_of(q: float, visits: int) -> int:
@@ -82,7 +83,10 @@ class BatchedAnalysis:
     192 boards and more, as in self-play) the search runs on the planned boundary with the evaluation cache; the cache is kept
     across chunks and cleared only when the evaluator's weights version changes."""
 
-    def __init__(self, evaluator, n_boards: int, n_playout: int = 400, multipv: int = 1, max_len: int = 32, solver: bool = False, **engine_kw):
+    def __init__(self, evaluator, n_boards: int, n_playout: int = 400, multipv: int = 1, max_len: int = 32, solver: bool = False, search=None,
+                 **engine_kw):
+        """``search``: a dict of ``SelfPlayEngine.set_search``'s arguments (first-play urgency, visit-scaled c_puct); None: the
+        reference's PUCT."""
         from .selfplay import BatchedSelfPlay
         ev = getattr(evaluator, "evaluate_leaves_logits", evaluator)
         if not callable(ev):
@@ -92,7 +96,7 @@ class BatchedAnalysis:
         if "eval_cache_log2" not in engine_kw:
             engine_kw["eval_cache_log2"] = 22 if (int(n_boards) >= 192 and getattr(ev, "accepts_plan", False)) else 0
         engine_kw.setdefault("mirror", False)
-        self.sp = BatchedSelfPlay(ev, int(n_boards), n_playout=int(n_playout), eps=0.0, **engine_kw)   # no GPU: CczError
+        self.sp = BatchedSelfPlay(ev, int(n_boards), n_playout=int(n_playout), eps=0.0, search=search, **engine_kw)   # no GPU: CczError
         self.engine = self.sp.engine
         self.solver = bool(solver)     # the MCTS-solver: records gain "mate", bestmove follows the proof (make_record)
         if self.solver:
@@ -176,8 +180,11 @@ class BatchedAnalysis:
     def summary(self) -> dict:
         rows = int(self._rows.item()) if (self._rows is not None and self.sp.planned) else self.steps * self.B
         sec = max(self.seconds, 1e-9)
-        return {"positions": self.positions, "seconds": round(self.seconds, 3), "positions_per_s": round(self.positions / sec, 2),
-                "sims_per_s": round(self.sims / sec, 1), "evaluator_rows_per_step": round(rows / max(1, self.steps), 2)}
+        out = {"positions": self.positions, "seconds": round(self.seconds, 3), "positions_per_s": round(self.positions / sec, 2),
+               "sims_per_s": round(self.sims / sec, 1), "evaluator_rows_per_step": round(rows / max(1, self.steps), 2)}
+        if self.sp.search_cfg is not None:      # the settings as the kernels read them, and how deep the leaves lay
+            out.update(search=self.engine.search_settings(), mean_leaf_depth=round(mean_leaf_depth(self.engine.stats()), 3))
+        return out
 
 
 def main(argv=None) -> int:
@@ -191,7 +198,9 @@ def main(argv=None) -> int:
     ap.add_argument("--weights", default=None, help="model file (default: random initialisation)")
     ap.add_argument("--out", default=None, help="JSON lines file (default: stdout)")
     ap.add_argument("--solver", action="store_true", help="MCTS-solver: prove decided positions in the tree; every record gains \"mate\": N or null")
+    add_search_args(ap)
     args = ap.parse_args(argv)
+    search = search_from_args(ap, args)
     with open(args.file, encoding="utf-8") as f:
         try:
             parsed = parse_positions(f)
@@ -206,7 +215,7 @@ def main(argv=None) -> int:
     try:
         pvn = PolicyValueNet(model=args.weights, device="cuda:0")
         an = BatchedAnalysis(pvn, max(1, min(args.boards, len(parsed) or 1)), n_playout=args.playout, multipv=args.multipv,
-                             max_len=args.max_len, solver=args.solver)
+                             max_len=args.max_len, solver=args.solver, search=search)
         records = an.analyse([b for _, b in parsed])
     except CczError as e:
         print(f"analyse: {e}", file=sys.stderr)
@@ -220,7 +229,8 @@ def main(argv=None) -> int:
             out.close()
     s = an.summary()
     print(f"analysed {s['positions']} positions in {s['seconds']} s: {s['positions_per_s']} positions/s, {s['sims_per_s']} sims/s, "
-          f"{s['evaluator_rows_per_step']} evaluator rows per step", file=sys.stderr)
+          f"{s['evaluator_rows_per_step']} evaluator rows per step"
+          + (f", mean leaf depth {s['mean_leaf_depth']}, search {json.dumps(s['search'])}" if "search" in s else ""), file=sys.stderr)
     return 0
 
 

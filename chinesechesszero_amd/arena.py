@@ -22,6 +22,7 @@ import time
 import numpy as np
 
 from .parameters import C_PUCT
+from .searchcfg import add_search_args, mean_leaf_depth, search_from_args
 
 _RESIGNED = 2   # _lib.RESIGN_RESIGNED (this module imports the engine lazily: its statistics run without a GPU)
 PROMOTE_THRESHOLD = 0.55   # AlphaGo Zero's gate, kept by the AlphaZero_Gomoku lineage the reference cites
@@ -179,11 +180,12 @@ class Arena:
     ``min_ply`` (``engine.set_resign``): the side to move resigns when its root value stayed below the threshold -- a resigned game
     is a win for the other side like any other, counted in ``result()["resigned"]``; no game is played on (``p_playon`` = 0).
     None (default): games end by the rules or the ply cap only. ``solver``: both sides search with the MCTS-solver
-    (``engine.set_solver``) and play the proven move where the root is decided (``engine.proof_moves``)."""
+    (``engine.set_solver``) and play the proven move where the root is decided (``engine.proof_moves``). ``search``: a dict of
+    ``engine.set_search``'s arguments (first-play urgency, visit-scaled c_puct), for both sides alike; None: the reference's PUCT."""
 
     def __init__(self, net_a, net_b, n_pairs: int, n_playout: int = 400, opening_plies: int = 6, seed: int = 0,
                  max_plies: int = 0, c_puct: float = C_PUCT, eval_cache_log2: int = 22, device: int = 0,
-                 cache_verify: bool = False, n_playout_b: int | None = None, resign=None, solver: bool = False):
+                 cache_verify: bool = False, n_playout_b: int | None = None, resign=None, solver: bool = False, search=None):
         from .engine import SelfPlayEngine
         self.nets = (net_a, net_b)
         self.ev = (_as_evaluator(net_a, "A"), _as_evaluator(net_b, "B"))
@@ -207,6 +209,9 @@ class Arena:
         self.proven_moves = 0                # moves played from a proof
         if self.solver:
             e.set_solver(True)
+        self.search_cfg = None if search is None else dict(search)
+        if self.search_cfg is not None:
+            e.set_search(**self.search_cfg)
         self.resign = None
         if resign is not None:
             self.resign = dict(resign) if isinstance(resign, dict) else {"threshold": float(resign)}
@@ -331,6 +336,9 @@ class Arena:
             out["wall_s"] = wall
             out["games_per_s"] = self.B / wall if wall > 0 else float("nan")
         s = self.engine.stats()
+        if self.search_cfg is not None:
+            out["search"] = self.engine.search_settings()
+            out["mean_leaf_depth"] = mean_leaf_depth(s)
         out["cache"] = {k: s[k] for k in ("cache_probes", "cache_hits", "cache_shared_rows", "cache_stores",
                                            "cache_verified", "cache_verify_mismatches")}
         return out
@@ -375,7 +383,9 @@ def main(argv=None) -> int:
     ap.add_argument("--resign-moves", type=int, default=None, help="... for this many of its moves in a row (default 2)")
     ap.add_argument("--solver", action="store_true", help="MCTS-solver on both sides: decided positions are proven in the tree and the proven move is played")
     ap.add_argument("--resign-min-ply", type=int, default=None, help="... and not before this ply (default 30)")
+    add_search_args(ap)
     a = ap.parse_args(argv)
+    search = search_from_args(ap, a)
     if a.resign_threshold is None and (a.resign_moves is not None or a.resign_min_ply is not None):
         ap.error("--resign-moves / --resign-min-ply need --resign-threshold")
     resign = None
@@ -385,7 +395,7 @@ def main(argv=None) -> int:
     na = _load(a.a, a.channels, a.blocks, a.device)
     nb = _load(a.b, a.channels, a.blocks, a.device)
     arena = Arena(na, nb, a.pairs, n_playout=a.playout, opening_plies=a.opening_plies, seed=a.seed, max_plies=a.max_plies,
-                  eval_cache_log2=a.eval_cache_log2, device=a.device, n_playout_b=a.playout_b, resign=resign, solver=a.solver)
+                  eval_cache_log2=a.eval_cache_log2, device=a.device, n_playout_b=a.playout_b, resign=resign, solver=a.solver, search=search)
     r = arena.play()
     r.update({"a": a.a, "b": a.b, "opening_plies": a.opening_plies, "seed": a.seed, "net": f"{a.blocks}x{a.channels}",
               "promote": promote(r, a.threshold), "threshold": a.threshold})

@@ -30,6 +30,7 @@ from .game import RED, Board, Game
 from .mcts import MCTS_AI
 from .net import PolicyValueNet
 from .parameters import BATCH_SIZE, C_PUCT, DATA_DIR, MODEL_DIR, PLAYOUT
+from .searchcfg import add_search_args, mean_leaf_depth, search_from_args
 from .tools import flip_map, log
 
 
@@ -508,7 +509,10 @@ class CollectPipeline:
                  finalize_every: int = 0, on_playout=None, max_plies: int = 0, eval_cache_log2: int | None = None, gatherer=None,
                  dense_shards: bool = False, replay_plies: int = 0, train_every: int = 0, train_batch: int = BATCH_SIZE,
                  playout_cap_fast: int = 0, playout_cap_prob: float | None = None, resign=None, value_q_weight: float = 0.0,
-                 root_exploration=None, solver: bool = False, gumbel=None):
+                 root_exploration=None, solver: bool = False, gumbel=None, search=None):
+        # search parameters (``search``: a dict of SelfPlayEngine.set_search's arguments; None = the reference's PUCT): first-play
+        # urgency and the visit-scaled c_puct, on the batched path and in the one-game loop (which then runs without scout slots)
+        self.search = None if search is None else dict(search)
         self.solver = bool(solver)     # the MCTS-solver in the search of the batched path (only the search changes)
         if self.solver and n_boards <= 1:
             raise ValueError("the solver option of the collector runs on the batched path: n_boards must be > 1")
@@ -617,7 +621,7 @@ class CollectPipeline:
                 from .replay import broadcast_model
                 broadcast_model(self.policy_value_net, src=0, what="state")
             self.mcts_ai = MCTS_AI(self.policy_value_net.policy_value_fn, c_puct=self.c_puct, n_playout=self.n_playout,
-                                   is_selfplay=True, device=self.device, seed=self.seed)
+                                   is_selfplay=True, device=self.device, seed=self.seed, search=getattr(self, "search", None))
 
     # ---- host path (one game at a time, the reference's own steps) ---------------------------------
     def preprocess(self, play_data):
@@ -695,7 +699,7 @@ class CollectPipeline:
                                             device=self.device, reference_quirks=self.reference_quirks, max_plies=self.max_plies,
                                             playout_cap=self.playout_cap, resign=getattr(self, "resign", None),
                                             root_exploration=getattr(self, "root_exploration", None), solver=getattr(self, "solver", False),
-                                            gumbel=getattr(self, "gumbel", None))
+                                            gumbel=getattr(self, "gumbel", None), search=getattr(self, "search", None))
             if getattr(self, "_viewer", None) is not None:
                 self.selfplay.watch(0, self._viewer)
         for _ in range(n_moves):
@@ -896,6 +900,13 @@ class CollectPipeline:
         e = self.selfplay.engine
         return format_exploration(e.exploration_stats(), e.stats()["sims"])
 
+    def search_report(self) -> str:
+        """The search-parameter part of the periodic log line (empty with the rule off; syncs)."""
+        if getattr(self, "search", None) is None or getattr(self, "selfplay", None) is None:
+            return ""
+        e = self.selfplay.engine
+        return format_search(e.search_settings(), e.stats())
+
     def gumbel_report(self) -> str:
         """The Gumbel part of the periodic log line (empty with the feature off; syncs)."""
         if getattr(self, "gumbel", None) is None or getattr(self, "selfplay", None) is None:
@@ -936,7 +947,7 @@ class CollectPipeline:
                 while max_calls <= 0 or calls < max_calls:
                     iters = self.collect_data(is_shown=is_shown)
                     calls += 1
-                    log(f"Episode {iters}, steps {self.episode_len}" + self.resign_report() + self.exploration_report() + self.gumbel_report() + self.solver_report())
+                    log(f"Episode {iters}, steps {self.episode_len}" + self.resign_report() + self.exploration_report() + self.gumbel_report() + self.solver_report() + self.search_report())
             except KeyboardInterrupt:
                 log("Exit")
             if self.gatherer is not None and hasattr(self.gatherer, "flush_iter") and self.selfplay is not None:
@@ -960,6 +971,16 @@ def format_exploration(x: dict, sims: int) -> str:
     forced = f"{x['forced_selections'] / n:.2f}" if n else "n/a"
     share = f"{x['visits_pruned'] / sims:.4f}" if sims else "n/a"
     return f", explored moves {n}, forced selections per move {forced}, pruned share of visits {share} ({x['children_pruned']} children dropped)"
+
+
+def format_search(cfg: dict, stats: dict) -> str:
+    """``cfg`` = ``SelfPlayEngine.search_settings()``, ``stats`` = ``SelfPlayEngine.stats()``: the urgency of the tree and of the root,
+    the growth of c_puct, and the mean depth of the leaves selected so far."""
+    def fpu(mode, value):
+        return {0: "off", 1: f"reduction {value:g}", 2: f"absolute {value:g}"}[int(mode)]
+    growth = f"base {cfg['c_base']:g} factor {cfg['c_factor']:g}" if cfg["c_factor"] else "constant"
+    return (f", fpu {fpu(cfg['fpu_mode'], cfg['fpu_value'])} (root {fpu(cfg['fpu_root_mode'], cfg['fpu_root_value'])}), c_puct {growth}, "
+            f"mean leaf depth {mean_leaf_depth(stats):.2f}")
 
 
 def format_gumbel(x: dict) -> str:
@@ -1018,6 +1039,7 @@ def build_parser():
     parser.add_argument("--gumbel-c-scale", type=float, default=None, help=f"... c_scale of sigma, >= 0 (default {GUMBEL_C_SCALE})")
     parser.add_argument("--solver", action="store_true", default=False, help="batched path: search with the MCTS-solver (decided positions are proven "
                         "in the tree and cost no evaluator row); sampling, records and targets are as without it")
+    add_search_args(parser)
     parser.add_argument("--value-q-weight", type=float, default=0.0, help="with --train-every: weight of the recorded root value q in the value "
                         "target, (1 - w) z + w q on rows that carry one (0 = z alone)")
     return parser
@@ -1088,6 +1110,7 @@ def parse_args(argv=None):
                            "max_considered": GUMBEL_CONSIDERED if args.gumbel_considered is None else args.gumbel_considered,
                            "c_visit": GUMBEL_C_VISIT if args.gumbel_c_visit is None else args.gumbel_c_visit,
                            "c_scale": GUMBEL_C_SCALE if args.gumbel_c_scale is None else args.gumbel_c_scale}
+    args.search = search_from_args(parser, args)
     return args
 
 
@@ -1120,7 +1143,7 @@ if __name__ == "__main__":
                            eval_cache_log2=args.eval_cache_log2, gatherer=gatherer, replay_plies=args.replay_plies,
                            train_every=args.train_every, train_batch=args.train_batch, playout_cap_fast=args.playout_cap_fast,
                            playout_cap_prob=args.playout_cap_prob, resign=args.resign, value_q_weight=args.value_q_weight,
-                           root_exploration=args.root_exploration, solver=args.solver, gumbel=args.gumbel_cfg)
+                           root_exploration=args.root_exploration, solver=args.solver, gumbel=args.gumbel_cfg, search=args.search)
     if world > 1:
         from .launch import guarded
 

@@ -83,6 +83,7 @@ struct ccz_engine {
     uint64_t salt[2] = {0, 0};
     bool budgets_on = false;       // ccz_set_budgets / ccz_draw_budgets (off: every budget INT32_MAX, every target 1)
     bool explore_on = false;       // ccz_set_root_exploration(enabled): the host's shadow of ExploreCfg.enabled (scouts are refused with it)
+    bool search_on = false;        // ccz_set_search(enabled): the host's shadow of SearchCfg.enabled (scouts are refused with it)
     bool gumbel_on = false;        // ccz_set_gumbel(enabled): the host's shadow of GumbelCfg.enabled (scouts and root exploration are refused with it)
     // MCTS-solver (ccz_set_solver): the proof bytes [B][2][cap] (allocated by the first call that turns it on), the host's shadow of
     // SolverCfg.enabled, staging of ccz_root_proof (state [B], dist [B], child state [B][128], child dist [B][128])
@@ -102,6 +103,15 @@ template <typename T> static int fetch_board_stats(ccz_engine *e, hipStream_t s,
 }
 
 // ---- the launches of the group-of-16 tower kernels (cczero_conv_g16.h, cczero_conv_g16e.h) ----
+// ccz_set_search off: what ccz_create writes and ccz_get_search reads back (c_base: AlphaZero's; it is idle while c_factor is 0)
+static SearchCfg search_defaults()
+{
+    SearchCfg v;
+    v.enabled = 0; v.fpu_mode = 0; v.fpu_root_mode = 0; v.pad = 0;
+    v.fpu_value = 0.0; v.fpu_root_value = 0.0; v.c_base = 19652.0; v.c_factor = 0.0;
+    return v;
+}
+
 static bool g16_bad_part(int32_t part, int32_t n_parts) { return n_parts < 1 || n_parts > 256 || part < 0 || part >= n_parts; }
 
 // The launch shape of a layer of `groups` 16-board groups. Without CCZ_CONV_G16_EDGE_TILES (or below two groups): `mid` = five two-rank
@@ -317,6 +327,13 @@ int ccz_create(const ccz_config *cfg, ccz_engine **out)
     ALLOC(d.gm_n0, B * kMaxLegal);
     ALLOC(d.gm_stamp, B * 4);
     ALLOC(d.gm_stats, B);
+    SearchCfg *sr_cfg = nullptr;
+    ALLOC(sr_cfg, 1); // off; the defaults are written below
+    d.sr_cfg = sr_cfg;
+    {
+        const SearchCfg off = search_defaults();
+        if (he == hipSuccess) he = hipMemcpy(sr_cfg, &off, sizeof off, hipMemcpyHostToDevice);
+    }
     ALLOC(d.rec_ids, B * d.pi_cap);
     ALLOC(d.rec_pi, B * d.pi_cap);
     ALLOC(d.stats, B);
@@ -513,6 +530,7 @@ int ccz_set_scouts(ccz_engine *e, int32_t n_scouts)
     if (n_scouts && e->budgets_on) return fail(-1, "ccz_set_scouts: not while simulation budgets are on (ccz_set_budgets(NULL) turns them off)");
     if (n_scouts && e->explore_on) return fail(-1, "ccz_set_scouts: not while root exploration is on (ccz_set_root_exploration)");
     if (n_scouts && e->gumbel_on) return fail(-1, "ccz_set_scouts: not while the Gumbel root search is on (ccz_set_gumbel)");
+    if (n_scouts && e->search_on) return fail(-1, "ccz_set_scouts: not while the search parameters are on (ccz_set_search): scouts rest on children being first visited in legal-move order");
     e->active = n_scouts ? e->d.B - n_scouts : 0;
     return 0;
 }
@@ -832,6 +850,60 @@ int ccz_gumbel_sequence(void *stream, int32_t m, int32_t n, int32_t *seq_dev)
     if (n == 0) return 0;
     hipLaunchKernelGGL(k_gumbel_sequence, dim3(1), dim3(64), 0, (hipStream_t)stream, (int)m, (int)n, seq_dev);
     HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// one urgency pair of ccz_set_search: nullptr, or what is wrong with it
+static const char *bad_fpu(int32_t mode, double value)
+{
+    if (mode < 0 || mode > 2) return "must be 0 (off), 1 (reduction) or 2 (absolute)";
+    if (mode == 1 && !(value >= 0.0 && std::isfinite(value))) return "is a reduction: its value must be finite and >= 0";
+    if (mode == 2 && !(value >= -1.0 && value <= 1.0)) return "is absolute: its value must be in [-1, 1]";
+    return nullptr;
+}
+
+int ccz_set_search(ccz_engine *e, void *stream, int32_t enabled, int32_t fpu_mode, double fpu_value, int32_t fpu_root_mode,
+                   double fpu_root_value, double c_base, double c_factor)
+{
+    NEED(e);
+    SearchCfg v = search_defaults(); // enabled = 0: the other arguments are ignored
+    if (enabled) {
+        if (const char *why = bad_fpu(fpu_mode, fpu_value)) return fail(-1, "ccz_set_search: fpu_mode %d / fpu_value %g: the mode %s", fpu_mode, fpu_value, why);
+        if (const char *why = bad_fpu(fpu_root_mode, fpu_root_value))
+            return fail(-1, "ccz_set_search: fpu_root_mode %d / fpu_root_value %g: the mode %s", fpu_root_mode, fpu_root_value, why);
+        if (!(c_base > 0.0 && std::isfinite(c_base))) return fail(-1, "ccz_set_search: c_base %g must be finite and > 0", c_base);
+        if (!(c_factor >= 0.0 && std::isfinite(c_factor))) return fail(-1, "ccz_set_search: c_factor %g must be finite and >= 0", c_factor);
+        if (e->active > 0) return fail(-1, "ccz_set_search: not with scout slots (ccz_set_scouts): the one-game path keeps the reference's search");
+        v.enabled = 1;
+        v.fpu_mode = fpu_mode;
+        v.fpu_root_mode = fpu_root_mode;
+        v.fpu_value = fpu_mode ? fpu_value : 0.0; // (a mode that is off has no value)
+        v.fpu_root_value = fpu_root_mode ? fpu_root_value : 0.0;
+        v.c_base = c_base;
+        v.c_factor = c_factor;
+    }
+    hipLaunchKernelGGL(k_set_search, dim3(1), dim3(1), 0, (hipStream_t)stream, const_cast<SearchCfg *>(e->d.sr_cfg), v);
+    HIP_TRY(hipGetLastError());
+    e->search_on = enabled != 0;
+    return 0;
+}
+
+int ccz_get_search(ccz_engine *e, void *stream, ccz_search_cfg *out)
+{
+    NEED(e);
+    if (!out) return fail(-1, "ccz_get_search: null output");
+    hipStream_t s = (hipStream_t)stream;
+    SearchCfg v;
+    HIP_TRY(hipMemcpyAsync(&v, e->d.sr_cfg, sizeof v, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    out->enabled = v.enabled;
+    out->fpu_mode = v.fpu_mode;
+    out->fpu_root_mode = v.fpu_root_mode;
+    out->reserved = 0;
+    out->fpu_value = v.fpu_value;
+    out->fpu_root_value = v.fpu_root_value;
+    out->c_base = v.c_base;
+    out->c_factor = v.c_factor;
     return 0;
 }
 

@@ -104,6 +104,16 @@ struct GumbelBoardStats {
     unsigned long long moves, considered, offvisit;
 };
 
+// Search parameters (ccz_set_search): first-play urgency and the visit-scaled exploration constant, as the device reads them.
+struct SearchCfg {
+    int32_t enabled;        // 0: the selection reads this one word and is the reference's PUCT (an unvisited child scores +inf)
+    int32_t fpu_mode;       // below the root: 0 +inf, 1 reduction, 2 absolute
+    int32_t fpu_root_mode;  // at the root, likewise
+    int32_t pad;
+    double fpu_value, fpu_root_value; // the reduction (>= 0) or the absolute value (in [-1, 1]) of the mode next to it
+    double c_base, c_factor;          // c_eff = c_puct + c_factor * log((N + c_base + 1) / c_base); c_factor 0: c_puct as it is
+};
+
 // MCTS-solver (ccz_set_solver): the settings as the device reads them, and the per-board counters. A proof byte holds the state in
 // bits 0..1 -- the view of the side to move at the node -- and the distance to the end in plies in bits 2..7 (saturating at 63; 0 for a
 // draw). The array lives behind the settings, not in Dev: it is allocated by the first ccz_set_solver(1), and a graph captured before
@@ -203,6 +213,8 @@ struct Dev {
     int32_t *gm_n0;              // [B][128] N_i when the row was filled (the kept subtree's visits)
     uint32_t *gm_stamp;          // [B][4] (move_counter + 1, k, n_eff, m) the rows were filled for; zeros: none
     GumbelBoardStats *gm_stats;  // [B]
+    // ---- search parameters (ccz_set_search). Always allocated; "off" is SearchCfg.enabled == 0
+    const SearchCfg *sr_cfg;     // [1] written by k_set_search in stream order
 };
 __device__ __forceinline__ int plane_of(const Dev &D, int type) { return (int)((D.chanpack >> (3 * type)) & 7u); }
 __device__ __forceinline__ int type_in_plane(const Dev &D, int chan) { return (int)((D.typepack >> (3 * chan)) & 7u) + 1; }

@@ -232,6 +232,7 @@ struct Prefetch {
     int32_t move_sims; // ... and how many it has, as of the top of the kernel (this launch's backup is not in it)
     int32_t ex;        // root exploration (ccz_set_root_exploration) applies to the board's current move: on, and a policy-target move
     int32_t gm;        // Gumbel root search (ccz_set_gumbel) is on
+    int32_t sr;        // search parameters (ccz_set_search) are on
     SolverCfg sv;      // MCTS-solver (ccz_set_solver): on / off and where the proof bytes are
     uint32_t kidp;     // solver on: lane i: the proof byte of child i of the root (off: 0, nothing is read)
 };
@@ -277,6 +278,7 @@ __device__ __forceinline__ Prefetch prefetch_board(const Dev &D, int b, int lane
     P.move_sims = D.move_sims[b];
     P.ex = D.ex_cfg->enabled * (int32_t)D.target[b]; // (both words are requested with the rest: no load waits for the other)
     P.gm = D.gm_cfg->enabled;
+    P.sr = D.sr_cfg->enabled;
     P.sv = solver_cfg(D); // (requested with the rest; off: no load waits for it)
     P.kidp = 0u;
     if (P.sv.enabled) P.kidp = P.sv.proof[base + 1 + lane];
@@ -604,6 +606,32 @@ __device__ inline GumbelPick gumbel_select(const Dev &D, const GumbelCfg &gc, in
     return p;
 }
 
+// ------------------------------------------------------------------ search parameters (ccz_set_search, include/cczero.h)
+// R1: the exploration constant of a node with N visits. c_factor == 0 (or the rule off): c_puct as it is, no logarithm.
+__device__ __forceinline__ float search_c_eff(float c_puct, const SearchCfg &sr, int N)
+{
+    if (!sr.enabled || sr.c_factor == 0.0) return c_puct;
+    return (float)((double)c_puct + sr.c_factor * det_log(((double)N + sr.c_base + 1.0) / sr.c_base));
+}
+// R2: the visited prior mass of a node, from lane l's children l (a) and 64 + l (b), each the child's raw prior when it exists and
+// has visits, else 0.0: m_l = a + b, then m_l = m_l + m_{l xor s} for s = 32, 16, 8, 4, 2, 1. IEEE addition is commutative, so every
+// lane ends with the same bits.
+__device__ __forceinline__ double search_mass(double a, double b)
+{
+    double m = a + b;
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) m = m + __shfl_xor(m, s);
+    return m;
+}
+// R3: the value an unvisited child of a node takes for Q. q: the node's running mean as stored (the view of the side that moved into
+// it), mass: R2.
+__device__ __forceinline__ double search_fpu(int mode, double value, float q, double mass)
+{
+    if (mode == 1) return (double)(-q) - value * sqrt(mass);
+    if (mode == 2) return value;
+    return __builtin_huge_val();
+}
+
 // One wave: PUCT descent from the root of board b, leaf rules, evaluator input. Per tree level there is
 // ONE dependent global load round (the children's 16-B NodeA records + their move/count words); the
 // chosen child's own N / first_child / count are broadcast from the winning lane, not re-read.
@@ -679,12 +707,20 @@ __device__ inline void select_phase(const Dev &D, int b, int lane, uint16_t *lea
                            (double *)sh.S.cand, (float *)sh.S.list);
     }
 
+    // ---- search parameters (ccz_set_search; off: the one prefetched word tested here)
+    const bool srch = EX && __builtin_amdgcn_readfirstlane(P.sr) != 0;
+    SearchCfg sr;
+    sr.enabled = 0; sr.fpu_mode = 0; sr.fpu_root_mode = 0; sr.pad = 0;
+    sr.fpu_value = 0.0; sr.fpu_root_value = 0.0; sr.c_base = 1.0; sr.c_factor = 0.0;
+    if (srch) sr = *D.sr_cfg;
+
     // ---- PUCT descent (mcts.py:105-111, 41-61). Compiled twice, chosen by the wave-uniform solver word: with the solver off the
-    // loop is the one it was (no proof byte in it); SV: std::true_type / std::false_type. Likewise GM, the Gumbel root: off, no word of
-    // it is in the loop
-    const auto descend = [&](auto SV, auto GM) {
+    // loop is the one it was (no proof byte in it); SV: std::true_type / std::false_type. Likewise GM, the Gumbel root, and SR, the
+    // search parameters: off, no word of them is in the loop
+    const auto descend = [&](auto SV, auto GM, auto SR) {
         constexpr bool SOLVER = decltype(SV)::value;
         constexpr bool GUMBEL = decltype(GM)::value;
+        constexpr bool SEARCH = decltype(SR)::value;
         for (;;) {
             const int nc = (int)(nb >> 16);
             if (nc == 0) break;
@@ -696,29 +732,55 @@ __device__ inline void select_phase(const Dev &D, int b, int lane, uint16_t *lea
             bool bF = false;
             const bool exroot = EX && !GUMBEL && ex && depth == 0; // (the two exclude each other)
             const bool gmroot = GUMBEL && depth == 0;
+            // the record, move / count word and proof byte (solver off: none) of child i = c0 + lane, in one load round. Root
+            // children: prefetched (+ this launch's backup). The patch of a root expanded in this launch knows child 0's move only
+            // (PUCT takes the first unvisited child): the Gumbel root reads the records as they stand in memory, and so does a root
+            // under the search parameters, whose first choice is the first maximum of R4
+            const auto load = [&](int c0, int i, NodeA &c, uint32_t &w, uint32_t &pb) {
+                if (depth == 0 && c0 == 0 && pa.fc == 1 && !gmroot && !(SEARCH && tp.root_expanded)) {
+                    c = P.kid;
+                    w = P.kidw;
+                    if (SOLVER) pb = P.kidp;
+                    if (tp.root_expanded) { c.N = 0; c.Q = 0.0f; c.fc = -1; w = (uint32_t)tp.first_id; pb = 0u; }
+                    else if (tp.has1 && 1 + i == tp.node1) {
+                        c.N = tp.N1;
+                        c.Q = tp.Q1;
+                        if (tp.kid_expanded) { c.fc = tp.n0; w = (w & 0xffffu) | ((uint32_t)tp.k << 16); }
+                        if (SOLVER && tp.hasp1) pb = tp.p1;
+                    }
+                } else {
+                    c = A[CCZ_IDX(D, pa.fc + i, D.cap)];
+                    w = Bn[CCZ_IDX(D, pa.fc + i, D.cap)];
+                    if (SOLVER) pb = proof[CCZ_IDX(D, pa.fc + i, D.cap)];
+                }
+            };
+            // search parameters, once per level: the children (a node has at most 128) are loaded ahead of the scoring pass, which
+            // takes them from registers; the mass of the visited ones (R2), the urgency (R3) and the exploration constant (R1)
+            NodeA kc[2];
+            uint32_t kw[2], kp[2];
+            double fpu = __builtin_huge_val();
+            float ceff = D.c_puct;
+            if (SEARCH) {
+                double pm[2];
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    kc[h] = NodeA{0, 0.0f, 0.0f, -1};
+                    kw[h] = 0u;
+                    kp[h] = 0u;
+                    if (64 * h + lane < nc) load(64 * h, 64 * h + lane, kc[h], kw[h], kp[h]);
+                    pm[h] = kc[h].N > 0 ? (double)kc[h].P : 0.0; // (past nc: N = 0)
+                }
+                const double mass = search_mass(pm[0], pm[1]);
+                fpu = search_fpu(depth == 0 ? sr.fpu_root_mode : sr.fpu_mode, depth == 0 ? sr.fpu_root_value : sr.fpu_value, pa.Q, mass);
+                ceff = search_c_eff(D.c_puct, sr, pa.N);
+            }
             for (int c0 = 0; c0 < nc; c0 += 64) {
                 const int i = c0 + lane;
                 if (i < nc) {
                     NodeA c;
                     uint32_t w, pb = 0u; // pb: the candidate's proof byte, loaded in the round of its record (solver off: none)
-                    // root children: prefetched (+ this launch's backup). The patch of a root expanded in this launch knows child 0's
-                    // move only (PUCT takes the first unvisited child): the Gumbel root reads the records as they stand in memory
-                    if (depth == 0 && c0 == 0 && pa.fc == 1 && !gmroot) {
-                        c = P.kid;
-                        w = P.kidw;
-                        if (SOLVER) pb = P.kidp;
-                        if (tp.root_expanded) { c.N = 0; c.Q = 0.0f; c.fc = -1; w = (uint32_t)tp.first_id; pb = 0u; }
-                        else if (tp.has1 && 1 + i == tp.node1) {
-                            c.N = tp.N1;
-                            c.Q = tp.Q1;
-                            if (tp.kid_expanded) { c.fc = tp.n0; w = (w & 0xffffu) | ((uint32_t)tp.k << 16); }
-                            if (SOLVER && tp.hasp1) pb = tp.p1;
-                        }
-                    } else {
-                        c = A[CCZ_IDX(D, pa.fc + i, D.cap)];
-                        w = Bn[CCZ_IDX(D, pa.fc + i, D.cap)];
-                        if (SOLVER) pb = proof[CCZ_IDX(D, pa.fc + i, D.cap)];
-                    }
+                    if (SEARCH && c0 < 128) { c = kc[c0 >> 6]; w = kw[c0 >> 6]; pb = kp[c0 >> 6]; }
+                    else load(c0, i, c, w, pb);
                     // value + c_puct*prob*sqrt(N_parent)/(1+N): float32 product, float64 elsewhere; inf if unvisited
                     float pp = c.P;
                     bool fsel = false;
@@ -726,8 +788,14 @@ __device__ inline void select_phase(const Dev &D, int b, int lane, uint16_t *lea
                         pp = explore_prior(xc, c.P, c0 ? xd1 : xd0);
                         fsel = xc.forced_k > 0.0 && c.N > 0 && (double)c.N < sqrt(xc.forced_k * (double)pp * (double)(pa.N - 1));
                     }
-                    double sc = (c.N == 0 || fsel) ? __builtin_huge_val()
-                                                   : (double)c.Q + (double)(D.c_puct * pp) * sqrtNp / (double)(1 + c.N);
+                    double sc;
+                    if (SEARCH) // R4: an unvisited child scores like a visited one with Q = the urgency (+inf under mode 0) and N = 0
+                        sc = (fsel || (c.N == 0 && fpu == __builtin_huge_val()))
+                                 ? __builtin_huge_val()
+                                 : (c.N == 0 ? fpu : (double)c.Q) + (double)(ceff * pp) * sqrtNp / (double)(1 + c.N);
+                    else
+                        sc = (c.N == 0 || fsel) ? __builtin_huge_val()
+                                                : (double)c.Q + (double)(D.c_puct * pp) * sqrtNp / (double)(1 + c.N);
                     // Gumbel root: g + logit + sigma of a candidate; every other child is out of the comparison (like a NaN score)
                     if (gmroot) sc = (((c0 ? gp.c1 : gp.c0) >> lane) & 1ull) ? (c0 ? gp.s1 : gp.s0) : __builtin_nan("");
                     if (sc > best) { best = sc; besti = i; bN = c.N; bQ = c.Q; bfc = c.fc; bw = w; bF = fsel; if (SOLVER) bP = pb; }
@@ -761,11 +829,17 @@ __device__ inline void select_phase(const Dev &D, int b, int lane, uint16_t *lea
             }
         }
     };
-    if (EX && gm) {
-        if (solver) descend(std::true_type{}, std::true_type{});
-        else descend(std::false_type{}, std::true_type{});
-    } else if (solver) descend(std::true_type{}, std::false_type{});
-    else descend(std::false_type{}, std::false_type{});
+    const std::true_type on{};
+    const std::false_type off{};
+    if (EX && srch) {
+        if (gm) { if (solver) descend(on, on, on); else descend(off, on, on); }
+        else if (solver) descend(on, off, on);
+        else descend(off, off, on);
+    } else if (EX && gm) {
+        if (solver) descend(on, on, off);
+        else descend(off, on, off);
+    } else if (solver) descend(on, off, off);
+    else descend(off, off, off);
     wave_sync();
     if (bad) {
         if (lane == 0) D.leaf_status[b] = CCZ_LEAF_SKIP;
@@ -1617,13 +1691,14 @@ __device__ inline void explore_targets(const Dev &D, const ExploreCfg &xc, int b
         int cs = 0; // every lane runs the same <= 128 terms on the same LDS words: wave-uniform without a broadcast
         for (int i = 1; i < k; ++i) if (s_vis[i] > s_vis[cs]) cs = i;
         const double sq = sqrt((double)root.N), S = (double)(root.N - 1);
-        const double top = (double)s_q[cs] + (double)(D.c_puct * s_pn[cs]) * sq / (double)(1 + s_vis[cs]);
+        const float ce = search_c_eff(D.c_puct, *D.sr_cfg, root.N); // (ccz_set_search off, or c_factor 0: c_puct as it is)
+        const double top = (double)s_q[cs] + (double)(ce * s_pn[cs]) * sq / (double)(1 + s_vis[cs]);
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const int i = 64 * h + lane;
             if (i < k && i != cs && s_vis[i] > 0) {
                 const int n = s_vis[i];
-                const double E = (double)(D.c_puct * s_pn[i]) * sq;
+                const double E = (double)(ce * s_pn[i]) * sq;
                 const double nf = ceil(sqrt(xc.forced_k * (double)s_pn[i] * S));
                 const double gap = top - (double)s_q[i];
                 double need = (double)n;
@@ -2760,6 +2835,12 @@ __global__ void k_set_root_exploration(ExploreCfg *cfg, ExploreCfg v, uint32_t *
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) stamps[i] = 0u;
     if (i == 0) *cfg = v;
+}
+
+// ccz_set_search: the settings reach the device in stream order
+__global__ void k_set_search(SearchCfg *cfg, SearchCfg v)
+{
+    if (blockIdx.x == 0 && threadIdx.x == 0) *cfg = v;
 }
 
 // ------------------------------------------------------------------ MCTS-solver: settings, inspection, the combine rule on its own

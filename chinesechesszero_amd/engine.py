@@ -477,6 +477,31 @@ class SelfPlayEngine:
         check(self.L.ccz_gumbel_root(self.h, self._stream(), _ptr(g), _ptr(logit), _ptr(n0), _ptr(k), _ptr(n_eff)))
         return g, logit, n0, k, n_eff
 
+    # ------------------------------------------------------------------ search parameters (include/cczero.h ccz_set_search)
+    def set_search(self, enabled: bool = True, fpu_mode: int = 0, fpu_value: float = 0.0, fpu_root_mode: int | None = None,
+                   fpu_root_value: float | None = None, c_base: float = 19652.0, c_factor: float = 0.0):
+        """First-play urgency and the visit-scaled exploration constant. ``fpu_mode``: 0 an unvisited child scores +inf (the
+        reference's rule), 1 reduction (the parent's value minus ``fpu_value`` * sqrt(visited prior mass), Lc0 / KataGo), 2 absolute
+        (``fpu_value``, AlphaZero). ``fpu_root_mode`` / ``fpu_root_value``: the same at the root (None: the tree's setting).
+        ``c_factor`` > 0: c_puct grows by ``c_factor * log((N + c_base + 1) / c_base)`` with the node's visits. ``enabled`` False or
+        None: off, the state of a new engine; the other arguments are ignored. Not with scout slots. No host sync."""
+        if not enabled:
+            check(self.L.ccz_set_search(self.h, self._stream(), 0, 0, 0.0, 0, 0.0, 19652.0, 0.0))
+            return
+        rm = fpu_mode if fpu_root_mode is None else fpu_root_mode
+        rv = (fpu_value if fpu_root_mode is None else 0.0) if fpu_root_value is None else fpu_root_value
+        check(self.L.ccz_set_search(self.h, self._stream(), 1, int(fpu_mode), float(fpu_value), int(rm), float(rv), float(c_base),
+                                    float(c_factor)))
+
+    def search_settings(self) -> dict:
+        """The search parameters as the kernels read them (``ccz_get_search``; syncs): ``enabled``, ``fpu_mode``, ``fpu_value``,
+        ``fpu_root_mode``, ``fpu_root_value``, ``c_base``, ``c_factor``."""
+        s = _lib.SearchCfg()
+        check(self.L.ccz_get_search(self.h, self._stream(), C.byref(s)))
+        out = {f: getattr(s, f) for f, _ in _lib.SearchCfg._fields_ if f != "reserved"}
+        out["enabled"] = bool(out["enabled"])
+        return out
+
     # ------------------------------------------------------------------ MCTS-solver (include/cczero.h ccz_set_solver)
     def set_solver(self, enabled: bool = True):
         """Exact propagation of decided positions (Winands' MCTS-solver): a terminal leaf proves its node, a node with a lost child

@@ -17,8 +17,9 @@ from .parameters import C_PUCT
 
 class BatchedMatch:
     def __init__(self, evaluator_red, evaluator_black, n_boards: int, n_playout: int = 400, c_puct: float = C_PUCT,
-                 seed: int = 0, device: int = 0, max_plies: int = 0, temp: float = 1e-3, solver: bool = False):
-        """``solver``: both sides search with the MCTS-solver (``engine.set_solver``) and play the proven move where the root is
+                 seed: int = 0, device: int = 0, max_plies: int = 0, temp: float = 1e-3, solver: bool = False, search=None):
+        """``search``: a dict of ``engine.set_search``'s arguments (first-play urgency, visit-scaled c_puct) for both sides; None: the
+        reference's PUCT. ``solver``: both sides search with the MCTS-solver (``engine.set_solver``) and play the proven move where the root is
         decided (``engine.proof_moves``); every other move is drawn as without it."""
         self.ev = {1: evaluator_red, 0: evaluator_black}
         self.B = n_boards
@@ -31,6 +32,9 @@ class BatchedMatch:
         self.proven_moves = 0
         if self.solver:
             self.engine.set_solver(True)
+        self.search_cfg = None if search is None else dict(search)
+        if self.search_cfg is not None:
+            self.engine.set_search(**self.search_cfg)
         self.before_move = self.on_move = None
         self._temps = np.full(n_boards, temp, np.float64)
 

@@ -22,6 +22,7 @@ import torch
 
 from .engine import SelfPlayEngine
 from .parameters import ALPHA, C_PUCT, EPS
+from .searchcfg import resolve_scouts
 from .tools import softmax
 
 
@@ -67,12 +68,17 @@ SCOUTS = 10  # scout slots of a one-game search (ScoutedSearch): 1 + 10 = 11 row
 
 class MCTS:
     def __init__(self, policy_value_fn, c_puct=5, n_playout=10000, device: int = 0, seed: int = 0, scouts: int | None = None,
-                 solver: bool = False):
-        """``scouts``: scout slots of the one-game search (``selfplay.ScoutedSearch``; same visit counts, fewer evaluator calls);
+                 solver: bool = False, search=None):
+        """``search``: a dict of ``SelfPlayEngine.set_search``'s arguments (first-play urgency, visit-scaled c_puct). Scout slots rest
+        on children being first visited in legal-move order, which the rule ends: with ``search`` given and ``scouts`` None the search
+        runs with ``scouts=0``; both given explicitly raise ValueError.
+        ``scouts``: scout slots of the one-game search (``selfplay.ScoutedSearch``; same visit counts, fewer evaluator calls);
         None = ``SCOUTS`` (env ``CCZ_SCOUTS``) when the evaluator is a batched one that returns logits, else 0. ``solver``: the
         MCTS-solver (``SelfPlayEngine.set_solver``): decided positions are proven in the tree, :meth:`proof_move` names the move
         a proven root asks for."""
         self.policy = policy_value_fn
+        self.search_cfg = None if search is None else dict(search)
+        scouts = resolve_scouts(self.search_cfg, scouts)
         self.solver = bool(solver)
         self.c_puct = c_puct
         self.n_playout = n_playout
@@ -111,6 +117,8 @@ class MCTS:
                 self._engine.set_scouts(self.scouts)
             if self.solver:
                 self._engine.set_solver(True)
+            if self.search_cfg is not None:
+                self._engine.set_search(**self.search_cfg)
         return self._engine
 
     def _forced(self, mid: int):
@@ -264,10 +272,11 @@ class MCTS_AI:
     """reference mcts.py:181-233"""
 
     def __init__(self, policy_value_fn, c_puct=5, n_playout=2000, is_selfplay=False, device: int = 0, seed: int = 0, scouts: int | None = None,
-                 solver: bool = False):
-        """``solver``: search with the MCTS-solver and play the proven move when the root is decided (the fastest mate, the longest
+                 solver: bool = False, search=None):
+        """``search``: as in :class:`MCTS` (with it, ``scouts`` None means 0 and ``scouts`` > 0 raises ValueError).
+        ``solver``: search with the MCTS-solver and play the proven move when the root is decided (the fastest mate, the longest
         defence) instead of drawing from the visit counts."""
-        self.mcts = MCTS(policy_value_fn, c_puct, n_playout, device=device, seed=seed, scouts=scouts, solver=solver)
+        self.mcts = MCTS(policy_value_fn, c_puct, n_playout, device=device, seed=seed, scouts=scouts, solver=solver, search=search)
         self.is_selfplay = is_selfplay
         self.agent = "AI"
 

@@ -217,8 +217,11 @@ class BatchedSelfPlay:
     def __init__(self, evaluator, n_boards: int, n_playout: int = 400, c_puct: float = C_PUCT, eps: float = EPS,
                  alpha: float = ALPHA, temp: float = 1.0, seed: int = 0, board_id_base: int = 0, device: int = 0,
                  sampling: str = "device", use_graph: bool = False, version_fn=None, playout_cap=None, resign=None,
-                 root_exploration=None, solver: bool = False, gumbel=None, **engine_kw):
-        """``gumbel``: True, or a dict of :meth:`SelfPlayEngine.set_gumbel`'s arguments (``n_sims`` defaults to ``n_playout``;
+                 root_exploration=None, solver: bool = False, gumbel=None, search=None, **engine_kw):
+        """``search``: a dict of :meth:`SelfPlayEngine.set_search`'s arguments (``fpu_mode``, ``fpu_value``, ``fpu_root_mode``,
+        ``fpu_root_value``, ``c_base``, ``c_factor``): first-play urgency and the visit-scaled c_puct inside the tree. Works with every
+        other option here (under ``gumbel`` from depth 1). None (default): off, the reference's PUCT.
+        ``gumbel``: True, or a dict of :meth:`SelfPlayEngine.set_gumbel`'s arguments (``n_sims`` defaults to ``n_playout``;
         ``max_considered``, ``c_visit``, ``c_scale``): Gumbel root search with sequential halving; pi' from the completed Q is the
         recorded policy target of every move, fast moves of ``playout_cap`` included (they still carry ``REC_FAST``). Device
         sampling only (the rule plays its own move), and not together with ``root_exploration``. None / False (default): off.
@@ -280,6 +283,10 @@ class BatchedSelfPlay:
         self.solver = bool(solver)
         if self.solver:
             self.engine.set_solver(True)
+        self.search_cfg = None
+        if search is not None:
+            self.search_cfg = dict(search)
+            self.engine.set_search(**self.search_cfg)
         self.B = n_boards
         self.n_playout = n_playout
         self.sampling = sampling

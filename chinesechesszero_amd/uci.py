@@ -77,6 +77,13 @@ class UciLoop:
         self.ai = None
         self.multipv = 1
         self.solver = False
+        self.search_opts = {}        # FpuReduction / FpuAbsolute / CpuctBase / CpuctFactor as set; empty: the reference's PUCT
+
+    def _search(self):
+        """The ``search`` dict of ``MCTS_AI`` for the options set so far (None: none was set)."""
+        from .searchcfg import make_search
+        o = self.search_opts
+        return make_search(o.get("fpureduction"), o.get("fpuabsolute"), None, None, o.get("cpuctbase"), o.get("cpuctfactor"))
 
     def _say(self, s: str):
         print(s, file=self.out, flush=True)
@@ -86,8 +93,10 @@ class UciLoop:
         if self.policy_value_fn is None:
             from .net import PolicyValueNet
             self.policy_value_fn = PolicyValueNet(device=f"cuda:{self.device}").policy_value_fn
-        if self.ai is None or self.ai.mcts.n_playout != nodes or self.ai.mcts.solver != self.solver:
-            self.ai = MCTS_AI(self.policy_value_fn, c_puct=C_PUCT, n_playout=nodes, is_selfplay=False, device=self.device, solver=self.solver)
+        search = self._search()
+        if self.ai is None or self.ai.mcts.n_playout != nodes or self.ai.mcts.solver != self.solver or self.ai.mcts.search_cfg != search:
+            self.ai = MCTS_AI(self.policy_value_fn, c_puct=C_PUCT, n_playout=nodes, is_selfplay=False, device=self.device, solver=self.solver,
+                              search=search)
         return self.ai
 
     def _say_pvs(self, ai):
@@ -126,6 +135,10 @@ class UciLoop:
             self._say(f"option name Playouts type spin default {self.n_playout} min 1 max 1000000")
             self._say("option name MultiPV type spin default 1 min 1 max 128")
             self._say("option name Solver type check default false")
+            self._say("option name FpuReduction type string default <empty>")
+            self._say("option name FpuAbsolute type string default <empty>")
+            self._say("option name CpuctBase type string default <empty>")
+            self._say("option name CpuctFactor type string default <empty>")
             self._say("uciok")
         elif cmd == "isready":
             self._say("readyok")
@@ -135,6 +148,19 @@ class UciLoop:
             self.multipv = max(1, min(128, int(tok[4])))
         elif cmd == "setoption" and len(tok) >= 5 and tok[1] == "name" and tok[2].lower() == "solver":
             self.solver = tok[4].lower() == "true"
+        elif cmd == "setoption" and len(tok) >= 5 and tok[1] == "name" and tok[2].lower() in ("fpureduction", "fpuabsolute", "cpuctbase", "cpuctfactor"):
+            name = tok[2].lower()
+            old = dict(self.search_opts)
+            try:
+                self.search_opts[name] = float(tok[4])
+                if name in ("fpureduction", "fpuabsolute"):      # the later of the two forms stands
+                    self.search_opts.pop("fpuabsolute" if name == "fpureduction" else "fpureduction", None)
+                self._search()
+            except ValueError as e:
+                self.search_opts = old
+                self._say(f"info string error {e}")
+            else:
+                self._say("info string search parameters set: scout slots are off for this session")
         elif cmd == "ucinewgame":
             self.board = Board()
             self.ai = None

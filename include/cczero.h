@@ -489,6 +489,46 @@ int ccz_gumbel_root(ccz_engine *e, void *stream, double *g_host, double *logit_h
 /* seq(m, n) of rule 2 written to seq_dev int32 [n], one wave. Stateless, asynchronous. */
 int ccz_gumbel_sequence(void *stream, int32_t m, int32_t n, int32_t *seq_dev);
 
+/* ---- Search parameters: first-play urgency and a visit-scaled exploration constant (additive to ABI 9) ----------------------------
+ * In the reference's PUCT an unvisited child scores +inf (mcts.py:47-48): every simulation that reaches a node first walks through all
+ * of its children in legal-move order. With first-play urgency (FPU) an unvisited child is scored from its parent's value instead --
+ * the "reduction" form of Lc0 / KataGo, or an absolute value as in AlphaZero --, and c_puct may grow with the node's visits as in
+ * AlphaZero. Off after ccz_create: every output of every call is then bit for bit what it is without the feature (the selection
+ * tests one word).
+ *   ccz_set_search: asynchronous on `stream`, takes effect with the next selection. enabled = 0: off; the other arguments are ignored
+ *     and the defaults are stored (modes 0, values 0, c_base 19652, c_factor 0). enabled = 1: fpu_mode / fpu_root_mode in {0 off
+ *     (+inf), 1 reduction, 2 absolute}; the value of a mode-1 pair finite and >= 0, of a mode-2 pair in [-1, 1], of a mode-0 pair
+ *     ignored (stored as 0); c_base finite and > 0; c_factor finite and >= 0 (0: c_puct is constant). A refused call names the field
+ *     in ccz_last_error and leaves the old settings in place. Fails while scout slots are active, and ccz_set_scouts(n > 0) fails
+ *     while it is on: the scout scheme rests on "children are first visited in legal-move order", which R4 ends.
+ *   ccz_get_search: syncs; what the kernels read.
+ * A node X has children i = 0 .. k-1, each with N_i, Q_i and raw float32 prior P_i; its own N_X; and Q_X, its running mean as stored,
+ * from the side that moved into X: -Q_X is X's value for its side to move (the sign convention of v0 in the Gumbel rule above).
+ *   R1. Exploration constant. c_eff(X) = c_puct (the float32 of ccz_config) when c_factor == 0. Otherwise
+ *       c_eff(X) = (float)((double)c_puct + c_factor * det_log(((double)N_X + c_base + 1.0) / c_base)). It enters the score exactly
+ *       where c_puct does, as the float32 product c_eff * P, then float64.
+ *   R2. Visited prior mass. M(X) is the float64 sum of (double)P_i over children with N_i > 0, in this order: lane l (0..63) forms
+ *       m_l = a + b, where a = P_l if l < k and N_l > 0 else 0.0, and b is the same for child l + 64; then for s = 32, 16, 8, 4, 2, 1:
+ *       m_l = m_l + m_{l xor s}. IEEE addition is commutative, so every lane ends with the same bits. M uses the RAW priors, also at
+ *       an explored root (ccz_set_root_exploration): the noisy P' stays in the U term only.
+ *   R3. Urgency. mode / value are the root pair at depth 0 and the tree pair below it. Mode 1: f(X) = (double)(-Q_X) - value *
+ *       sqrt(M(X)). Mode 2: f(X) = value. Mode 0: +inf, the reference's rule. No clamping.
+ *   R4. Score of an unvisited child: f(X) + (double)(c_eff * P_i) * sqrt((double)N_X) -- the visited formula with Q_i := f, N_i := 0
+ *       (under mode 0: +inf). First maximum in child order wins, as without the feature.
+ *   R5. What stays as it is. A visited root child short of its forced playouts still scores +inf; an unvisited root child of an
+ *       explored root uses P'_i in R4. At a Gumbel root the candidates and scores are Gumbel's: the root pair is unused, and the tree
+ *       pair applies from depth 1. The solver's stop at a proven chosen child, budgets and CCZ_LEAF_SKIP, NaN priors (CCZ_ERR_NAN: no
+ *       comparable child) and the depth and pool limits meet the rule where they meet PUCT.
+ *   R6. Target pruning (ccz_set_root_exploration, rule 3) uses c_eff(root) where it uses c_puct. With c_factor == 0 it is untouched.
+ * Q_X is the running mean of X, not the raw network value of X (Lc0 uses the same); nothing new is stored per node. */
+typedef struct ccz_search_cfg {
+    int32_t enabled, fpu_mode, fpu_root_mode, reserved;
+    double fpu_value, fpu_root_value, c_base, c_factor;
+} ccz_search_cfg;
+int ccz_set_search(ccz_engine *e, void *stream, int32_t enabled, int32_t fpu_mode, double fpu_value, int32_t fpu_root_mode,
+                   double fpu_root_value, double c_base, double c_factor);
+int ccz_get_search(ccz_engine *e, void *stream, ccz_search_cfg *out); /* syncs */
+
 /* ---- MCTS-solver: exact propagation of decided positions through the tree (additive to ABI 8) ----
  * One proof byte per tree node, in a device array of its own (uint8 [B][2][max_nodes], allocated and zeroed by the first
  * ccz_set_solver(enabled = 1), which may sync; never touched while the solver is off). Bits 0..1: the state in the view of the side
