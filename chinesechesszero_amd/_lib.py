@@ -97,6 +97,10 @@ class SearchCfg(C.Structure):
                 ("fpu_value", C.c_double), ("fpu_root_value", C.c_double), ("c_base", C.c_double), ("c_factor", C.c_double)]
 
 
+class WideStats(C.Structure):
+    _fields_ = [("steps", C.c_int64), ("leaves", C.c_int64), ("collisions", C.c_int64), ("inflight_now", C.c_int64)]
+
+
 class SolverStats(C.Structure):
     _fields_ = [("nodes_proven", C.c_int64), ("proven_stops", C.c_int64), ("roots_proven", C.c_int64)]
 
@@ -151,6 +155,10 @@ PROTOTYPES = {
     "ccz_root_proof": (C.c_int, [_P, _P, _P, _P, _P, _P]),
     "ccz_get_solver_stats": (C.c_int, [_P, _P, C.POINTER(SolverStats)]),
     "ccz_proof_combine": (C.c_int, [_P, _P, _P, C.c_int32, _P]),
+    "ccz_set_width": (C.c_int, [_P, _P, C.c_int32]),
+    "ccz_select_wide": (C.c_int, [_P, _P, _P, _P]),
+    "ccz_step_wide": (C.c_int, [_P, _P, _P, _P, _P]),
+    "ccz_get_wide_stats": (C.c_int, [_P, _P, C.POINTER(WideStats)]),
     "ccz_finish_move": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32]),
     "ccz_root_children": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
     "ccz_principal_variations": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),

@@ -84,8 +84,11 @@ class BatchedAnalysis:
     across chunks and cleared only when the evaluator's weights version changes."""
 
     def __init__(self, evaluator, n_boards: int, n_playout: int = 400, multipv: int = 1, max_len: int = 32, solver: bool = False, search=None,
-                 **engine_kw):
-        """``search``: a dict of ``SelfPlayEngine.set_search``'s arguments (first-play urgency, visit-scaled c_puct); None: the
+                 width: int = 1, **engine_kw):
+        """``width`` > 1: every position gathers up to ``width`` leaves of its tree per step, kept apart by virtual loss
+        (``wide.WideSearch``: an engine of ``n_boards * width`` slots) -- for a handful of positions, where the sequential search
+        runs at the evaluator's latency; another tree than the sequential one; excludes ``solver`` and ``search``.
+        ``search``: a dict of ``SelfPlayEngine.set_search``'s arguments (first-play urgency, visit-scaled c_puct); None: the
         reference's PUCT."""
         from .selfplay import BatchedSelfPlay
         ev = getattr(evaluator, "evaluate_leaves_logits", evaluator)
@@ -96,6 +99,24 @@ class BatchedAnalysis:
         if "eval_cache_log2" not in engine_kw:
             engine_kw["eval_cache_log2"] = 22 if (int(n_boards) >= 192 and getattr(ev, "accepts_plan", False)) else 0
         engine_kw.setdefault("mirror", False)
+        self.width = int(width)
+        self.wide = None
+        if self.width != 1:
+            if solver or search is not None:
+                raise ValueError("BatchedAnalysis: width > 1 excludes the solver and the search parameters")
+            from .wide import WideSearch
+            if engine_kw["eval_cache_log2"] == 0 and getattr(ev, "accepts_plan", False):
+                engine_kw["eval_cache_log2"] = 16   # slots of one tree reach one position often: they share an evaluator row
+            engine_kw.setdefault("eps", 0.0)
+            self.wide = WideSearch(ev, int(n_boards), self.width, n_playout=int(n_playout), **engine_kw)   # ValueError: width not in 2..64
+            self.sp = None
+            self.engine = self.wide.engine
+            self.solver = False
+            self.B, self.n_playout, self.multipv, self.max_len = int(n_boards), int(n_playout), int(multipv), int(max_len)
+            self.positions = self.steps = self.sims = 0
+            self.seconds = 0.0
+            self._rows = None
+            return
         self.sp = BatchedSelfPlay(ev, int(n_boards), n_playout=int(n_playout), eps=0.0, search=search, **engine_kw)   # no GPU: CczError
         self.engine = self.sp.engine
         self.solver = bool(solver)     # the MCTS-solver: records gain "mate", bestmove follows the proof (make_record)
@@ -120,6 +141,7 @@ class BatchedAnalysis:
         from .uci import parse_position
         boards = [p if isinstance(p, Board) else parse_position(str(p).split(), validate=False) for p in positions]
         e, sp, B = self.engine, self.sp, self.B
+        S = e.B             # slots of the engine: B, or B * width (only the first B carry positions)
         if self._rows is None:
             self._rows = torch.zeros((), dtype=torch.int64, device=e.device)
         out = []
@@ -128,17 +150,22 @@ class BatchedAnalysis:
         for c0 in range(0, len(boards), B):
             chunk = boards[c0:c0 + B]
             n = len(chunk)
-            sq = np.zeros((B, 90), np.uint8)
-            turn = np.ones(B, np.uint8)
-            half = np.zeros(B, np.int32)
-            moves = [[] for _ in range(B)]
+            sq = np.zeros((S, 90), np.uint8)
+            turn = np.ones(S, np.uint8)
+            half = np.zeros(S, np.int32)
+            moves = [[] for _ in range(S)]
             for j, bd in enumerate(chunk):
                 sq[j], turn[j], half[j] = bd._start[0], 1 if bd._start[1] else 0, bd._start[2]
                 moves[j] = [m.id for m in bd.move_stack]
-            status = e.set_positions(sq, turn, half, moves, park=np.arange(B) >= n)   # the tail of the last chunk is parked
-            sp._sim, sp._leaf, sp._acc = 0, None, 0      # fresh roots: whatever leaf was pending belongs to the old ones
+            status = e.set_positions(sq, turn, half, moves, park=np.arange(S) >= n)   # the tail of the last chunk is parked
+            if sp is not None:
+                sp._sim, sp._leaf, sp._acc = 0, None, 0      # fresh roots: whatever leaf was pending belongs to the old ones
             st = e.game_status()
-            if not st["over"][:n].all():
+            if self.wide is not None:
+                self.wide.boundary()
+                if not st["over"][:n].all():
+                    self.steps += self.wide.search()
+            elif not st["over"][:n].all():
                 sp.search(hooks=self._count_rows)
             pv = e.principal_variations(self.multipv, self.max_len)
             e.check_healthy()
@@ -178,6 +205,10 @@ class BatchedAnalysis:
         return out
 
     def summary(self) -> dict:
+        if self.wide is not None:
+            sec = max(self.seconds, 1e-9)
+            return {"positions": self.positions, "seconds": round(self.seconds, 3), "positions_per_s": round(self.positions / sec, 2),
+                    "sims_per_s": round(self.sims / sec, 1), **self.wide.summary()}
         rows = int(self._rows.item()) if (self._rows is not None and self.sp.planned) else self.steps * self.B
         sec = max(self.seconds, 1e-9)
         out = {"positions": self.positions, "seconds": round(self.seconds, 3), "positions_per_s": round(self.positions / sec, 2),
@@ -197,6 +228,7 @@ def main(argv=None) -> int:
     ap.add_argument("--max-len", type=int, default=32)
     ap.add_argument("--weights", default=None, help="model file (default: random initialisation)")
     ap.add_argument("--out", default=None, help="JSON lines file (default: stdout)")
+    ap.add_argument("--width", type=int, default=1, help="leaves per position and evaluator call (virtual loss); 1: the sequential search")
     ap.add_argument("--solver", action="store_true", help="MCTS-solver: prove decided positions in the tree; every record gains \"mate\": N or null")
     add_search_args(ap)
     args = ap.parse_args(argv)
@@ -215,7 +247,7 @@ def main(argv=None) -> int:
     try:
         pvn = PolicyValueNet(model=args.weights, device="cuda:0")
         an = BatchedAnalysis(pvn, max(1, min(args.boards, len(parsed) or 1)), n_playout=args.playout, multipv=args.multipv,
-                             max_len=args.max_len, solver=args.solver, search=search)
+                             max_len=args.max_len, solver=args.solver, search=search, width=args.width)
         records = an.analyse([b for _, b in parsed])
     except CczError as e:
         print(f"analyse: {e}", file=sys.stderr)
@@ -229,7 +261,8 @@ def main(argv=None) -> int:
             out.close()
     s = an.summary()
     print(f"analysed {s['positions']} positions in {s['seconds']} s: {s['positions_per_s']} positions/s, {s['sims_per_s']} sims/s, "
-          f"{s['evaluator_rows_per_step']} evaluator rows per step"
+          + (f"width {s['width']}: {s['mean_leaves_per_step']} leaves per board-step, collision share {s['collision_share']}" if "width" in s
+             else f"{s['evaluator_rows_per_step']} evaluator rows per step")
           + (f", mean leaf depth {s['mean_leaf_depth']}, search {json.dumps(s['search'])}" if "search" in s else ""), file=sys.stderr)
     return 0
 

@@ -9,6 +9,7 @@
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <new>
 #include <vector>
@@ -89,9 +90,20 @@ struct ccz_engine {
     // SolverCfg.enabled, staging of ccz_root_proof (state [B], dist [B], child state [B][128], child dist [B][128])
     uint8_t *proof = nullptr, *st_proof = nullptr;
     bool solver_on = false;
+    // wide search (ccz_set_width): slots per board (1: off; above 1 `active` = n_boards / width), the in-flight counts F [B][2][cap] and
+    // the per-board counters (both allocated by the first call that turns it on), staging of ccz_get_wide_stats
+    int width = 1;
+    uint8_t *wide_F = nullptr;
+    WideBoardStats *wide_stats = nullptr;
+    unsigned long long *st_wide = nullptr;
 };
 
 #define ACTIVE(e) ((unsigned)((e)->active > 0 ? (e)->active : (e)->d.B))
+#define SCOUTS(e) ((e)->active > 0 && (e)->width == 1) // the slots past `active` are scout slots (not the leaves of a wide search)
+#define WIDE(e) ((e)->width > 1)
+// the sequential step calls of a wide engine would silently use slot 0 of each board
+#define NOT_WIDE(e) do { if (WIDE(e)) return fail(-1, "%s: not while the width is %d (ccz_set_width): a wide engine steps with ccz_select_wide / ccz_step_wide", __func__, (e)->width); } while (0)
+static WideArgs wide_args(const ccz_engine *e) { return WideArgs{e->active, e->width, e->wide_F, e->wide_stats}; }
 
 // one record of counters per board, read back for the caller to sum (syncs)
 template <typename T> static int fetch_board_stats(ccz_engine *e, hipStream_t s, const T *dev, std::vector<T> &st)
@@ -399,12 +411,23 @@ static int stage_mask(ccz_engine *e, hipStream_t s, const uint8_t *mask_host, co
     return 0;
 }
 
+// The move boundary of a wide engine (width > 1 only: one extra launch): the pending leaves of the boards about to be reset, reloaded or
+// moved leave the in-flight counts, their slots get CCZ_LEAF_NONE. mask: the staged device mask or null; only >= 0: that board alone
+static int wide_drop(ccz_engine *e, hipStream_t s, const uint8_t *mask, int only)
+{
+    if (!WIDE(e)) return 0;
+    hipLaunchKernelGGL(k_wide_drop, dim3((unsigned)((e->active + 63) / 64)), dim3(64), 0, s, e->d, wide_args(e), mask, only);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 int ccz_reset(ccz_engine *e, void *stream, const uint8_t *mask_host)
 {
     NEED(e);
     hipStream_t s = (hipStream_t)stream;
     const uint8_t *mask;
     if (const int rc = stage_mask(e, s, mask_host, &mask)) return rc;
+    if (const int rc = wide_drop(e, s, mask, -1)) return rc;
     hipLaunchKernelGGL(k_reset, dim3(e->d.B), dim3(64), 0, s, e->d, mask);
     HIP_TRY(hipGetLastError());
     if (mask_host) HIP_TRY(hipStreamSynchronize(s)); // st_mask is reused by the next call
@@ -425,6 +448,7 @@ int ccz_set_position(ccz_engine *e, void *stream, int32_t board, const uint8_t *
     if (halfmove < 0) return fail(-1, "ccz_set_position: negative halfmove clock");
     hipStream_t s = (hipStream_t)stream;
     HIP_TRY(hipMemcpyAsync(e->st_sq, sq_host, 90, hipMemcpyHostToDevice, s));
+    if (const int rc = wide_drop(e, s, nullptr, board)) return rc;
     hipLaunchKernelGGL(k_set_position, dim3(1), dim3(64), 0, s, e->d, board, (const uint8_t *)e->st_sq, turn ? 1 : 0, halfmove);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(s));
@@ -442,6 +466,7 @@ int ccz_set_positions(ccz_engine *e, void *stream, const uint8_t *sq_dev, const 
     hipStream_t s = (hipStream_t)stream;
     const uint8_t *mask;
     if (const int rc = stage_mask(e, s, mask_host, &mask)) return rc;
+    if (const int rc = wide_drop(e, s, mask, -1)) return rc;
     hipLaunchKernelGGL(k_set_positions, dim3(e->d.B), dim3(64), 0, s, e->d, mask, sq_dev, turn_dev, halfmove_dev, moves_dev, n_moves_dev,
                        (int)max_moves, status_dev);
     HIP_TRY(hipGetLastError());
@@ -455,6 +480,7 @@ int ccz_reset_tree(ccz_engine *e, void *stream, const uint8_t *mask_host)
     hipStream_t s = (hipStream_t)stream;
     const uint8_t *mask;
     if (const int rc = stage_mask(e, s, mask_host, &mask)) return rc;
+    if (const int rc = wide_drop(e, s, mask, -1)) return rc;
     hipLaunchKernelGGL(k_reset_tree, dim3((e->d.B + 255) / 256), dim3(256), 0, s, e->d, mask);
     HIP_TRY(hipGetLastError());
     if (mask_host) HIP_TRY(hipStreamSynchronize(s)); // st_mask is reused by the next call
@@ -472,6 +498,7 @@ int ccz_zero_leaf_input(ccz_engine *e, void *stream, void *leaf_input_f16_dev)
 int ccz_select_leaves(ccz_engine *e, void *stream, void *leaf_input_f16_dev)
 {
     NEED(e);
+    NOT_WIDE(e);
     hipLaunchKernelGGL(k_select, dim3(ACTIVE(e)), dim3(64), 0, (hipStream_t)stream, e->d, (uint16_t *)leaf_input_f16_dev);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -480,6 +507,7 @@ int ccz_select_leaves(ccz_engine *e, void *stream, void *leaf_input_f16_dev)
 int ccz_expand_backup(ccz_engine *e, void *stream, const float *prob_dev, const float *value_dev)
 {
     NEED(e);
+    NOT_WIDE(e);
     if (!prob_dev || !value_dev) return fail(-1, "ccz_expand_backup: null prob/value");
     hipLaunchKernelGGL(k_expand_backup<false>, dim3(ACTIVE(e)), dim3(64), 0, (hipStream_t)stream, e->d, prob_dev, value_dev);
     HIP_TRY(hipGetLastError());
@@ -489,6 +517,7 @@ int ccz_expand_backup(ccz_engine *e, void *stream, const float *prob_dev, const 
 int ccz_step(ccz_engine *e, void *stream, const float *prob_dev, const float *value_dev, void *leaf_input_f16_dev)
 {
     NEED(e);
+    NOT_WIDE(e);
     if (!prob_dev || !value_dev) return fail(-1, "ccz_step: null prob/value");
     hipLaunchKernelGGL(k_step<false>, dim3(ACTIVE(e)), dim3(64), 0, (hipStream_t)stream, e->d, prob_dev, value_dev,
                        (uint16_t *)leaf_input_f16_dev);
@@ -526,6 +555,7 @@ int ccz_set_scouts(ccz_engine *e, int32_t n_scouts)
 {
     NEED(e);
     if (n_scouts < 0 || n_scouts >= e->d.B) return fail(-1, "ccz_set_scouts: n_scouts must be in 0 .. n_boards - 1 (got %d of %d boards)", n_scouts, e->d.B);
+    if (WIDE(e)) return fail(-1, "ccz_set_scouts: not while the width is %d (ccz_set_width): the slots past the searched boards hold the boards' own leaves", e->width);
     if (n_scouts && !e->d.cache) return fail(-1, "ccz_set_scouts: scouts work through the evaluation cache (ccz_config.eval_cache_log2)");
     if (n_scouts && e->budgets_on) return fail(-1, "ccz_set_scouts: not while simulation budgets are on (ccz_set_budgets(NULL) turns them off)");
     if (n_scouts && e->explore_on) return fail(-1, "ccz_set_scouts: not while root exploration is on (ccz_set_root_exploration)");
@@ -538,6 +568,7 @@ int ccz_set_scouts(ccz_engine *e, int32_t n_scouts)
 int ccz_scout(ccz_engine *e, void *stream, void *leaf_input_f16_dev)
 {
     NEED(e);
+    NOT_WIDE(e);
     if (e->active <= 0) return fail(-1, "ccz_scout: no scout slots (ccz_set_scouts)");
     if (!leaf_input_f16_dev) return fail(-1, "ccz_scout: null leaf input");
     hipLaunchKernelGGL(k_scout, dim3((unsigned)(e->d.B - e->active)), dim3(64), 0, (hipStream_t)stream, e->d, (uint16_t *)leaf_input_f16_dev, e->active);
@@ -548,6 +579,7 @@ int ccz_scout(ccz_engine *e, void *stream, void *leaf_input_f16_dev)
 int ccz_eval_plan_scouted(ccz_engine *e, void *stream, int32_t *miss_rows_dev, int32_t *n_miss_dev, int32_t *state_dev)
 {
     NEED(e);
+    NOT_WIDE(e);
     if (!e->d.cache) return fail(-1, "ccz_eval_plan_scouted: the engine was created without an evaluation cache (ccz_config.eval_cache_log2)");
     if (e->active <= 0) return fail(-1, "ccz_eval_plan_scouted: no scout slots (ccz_set_scouts)");
     if (!miss_rows_dev || !n_miss_dev) return fail(-1, "ccz_eval_plan_scouted: null output");
@@ -562,6 +594,7 @@ int ccz_eval_plan_scouted(ccz_engine *e, void *stream, int32_t *miss_rows_dev, i
 int ccz_scout_and_plan(ccz_engine *e, void *stream, void *leaf_input_f16_dev, int32_t *miss_rows_dev, int32_t *n_miss_dev, int32_t *state_dev)
 {
     NEED(e);
+    NOT_WIDE(e);
     if (!e->d.cache || e->active <= 0) return fail(-1, "ccz_scout_and_plan: needs an evaluation cache and scout slots (ccz_set_scouts)");
     if (!leaf_input_f16_dev || !miss_rows_dev || !n_miss_dev) return fail(-1, "ccz_scout_and_plan: null leaf input / output");
     if (e->d.B > kScoutFusedMax) {     // more slots than one workgroup has waves: the three launches
@@ -577,6 +610,7 @@ int ccz_scout_and_plan(ccz_engine *e, void *stream, void *leaf_input_f16_dev, in
 int ccz_scouted_run(ccz_engine *e, void *stream, void *leaf_input_f16_dev, int32_t *miss_rows_dev, int32_t *n_miss_dev, int32_t *state_dev, int32_t *run_dev)
 {
     NEED(e);
+    NOT_WIDE(e);
     if (!e->d.cache || e->active <= 0 || e->active == e->d.B) return fail(-1, "ccz_scouted_run: needs an evaluation cache and scout slots (ccz_set_scouts)");
     if (e->d.B > kScoutFusedMax) return fail(-1, "ccz_scouted_run: at most %d slots (one workgroup, one wave per slot); this engine has %d", kScoutFusedMax, e->d.B);
     if (!leaf_input_f16_dev || !miss_rows_dev || !n_miss_dev || !state_dev || !run_dev) return fail(-1, "ccz_scouted_run: null leaf input / output / run block");
@@ -611,8 +645,9 @@ int ccz_set_routing(ccz_engine *e, void *stream, const uint8_t *red_net_host, ui
         e->routed = false;
         return 0;
     }
+    if (WIDE(e)) return fail(-1, "ccz_set_routing: not while the width is %d (ccz_set_width)", e->width);
     if (!e->d.cache) return fail(-1, "ccz_set_routing: routing works through the evaluation cache (ccz_config.eval_cache_log2)");
-    if (e->active > 0) return fail(-1, "ccz_set_routing: not with scout slots (ccz_set_scouts)");
+    if (SCOUTS(e)) return fail(-1, "ccz_set_routing: not with scout slots (ccz_set_scouts)");
     if (salt0 == salt1) return fail(-1, "ccz_set_routing: the two evaluators need different salts (one would be served the other's evaluations)");
     for (int b = 0; b < e->d.B; ++b)
         if (red_net_host[b] > 1) return fail(-1, "ccz_set_routing: red_net[%d] = %d (must be 0 or 1)", b, (int)red_net_host[b]);
@@ -636,7 +671,7 @@ int ccz_eval_plan_routed(ccz_engine *e, void *stream, int32_t *miss_rows_dev, in
     NEED(e);
     if (!e->routed) return fail(-1, "ccz_eval_plan_routed: no routing set (ccz_set_routing)");
     if (!e->d.cache) return fail(-1, "ccz_eval_plan_routed: the engine was created without an evaluation cache");
-    if (e->active > 0) return fail(-1, "ccz_eval_plan_routed: not with scout slots (ccz_set_scouts)");
+    if (SCOUTS(e)) return fail(-1, "ccz_eval_plan_routed: not with scout slots (ccz_set_scouts)");
     if (!miss_rows_dev || !n_miss_dev) return fail(-1, "ccz_eval_plan_routed: null output");
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(k_cache_probe_routed, dim3(e->d.B), dim3(64), 0, s, e->d, (const uint8_t *)e->route_red, e->route_net, e->salt[0], e->salt[1]);
@@ -653,7 +688,7 @@ int ccz_gather_priors_routed(ccz_engine *e, void *stream, const void *logits0_de
     NEED(e);
     if (!e->routed) return fail(-1, "ccz_gather_priors_routed: no routing set (ccz_set_routing)");
     if (!e->d.cache) return fail(-1, "ccz_gather_priors_routed: the engine was created without an evaluation cache");
-    if (e->active > 0) return fail(-1, "ccz_gather_priors_routed: not with scout slots (ccz_set_scouts)");
+    if (SCOUTS(e)) return fail(-1, "ccz_gather_priors_routed: not with scout slots (ccz_set_scouts)");
     if (!logits0_dev || !logits1_dev || !value0_dev || !value1_dev) return fail(-1, "ccz_gather_priors_routed: null logits / value");
     hipStream_t s = (hipStream_t)stream;
     const uint8_t *net = e->route_net;
@@ -670,7 +705,7 @@ int ccz_gather_priors_routed(ccz_engine *e, void *stream, const void *logits0_de
 int ccz_set_budgets(ccz_engine *e, void *stream, const int32_t *budgets_dev, const uint8_t *targets_dev)
 {
     NEED(e);
-    if (e->active > 0) return fail(-1, "ccz_set_budgets: not with scout slots (ccz_set_scouts)");
+    if (SCOUTS(e)) return fail(-1, "ccz_set_budgets: not with scout slots (ccz_set_scouts)");
     hipLaunchKernelGGL(k_set_budgets, dim3((e->d.B + 255) / 256), dim3(256), 0, (hipStream_t)stream, e->d, e->d.B, budgets_dev, targets_dev);
     HIP_TRY(hipGetLastError());
     e->budgets_on = budgets_dev != nullptr;
@@ -680,7 +715,7 @@ int ccz_set_budgets(ccz_engine *e, void *stream, const int32_t *budgets_dev, con
 int ccz_draw_budgets(ccz_engine *e, void *stream, int32_t n_full, int32_t n_fast, double p_full, int32_t *budgets_out_dev)
 {
     NEED(e);
-    if (e->active > 0) return fail(-1, "ccz_draw_budgets: not with scout slots (ccz_set_scouts)");
+    if (SCOUTS(e)) return fail(-1, "ccz_draw_budgets: not with scout slots (ccz_set_scouts)");
     if (n_full < 1 || n_fast < 1) return fail(-1, "ccz_draw_budgets: n_full and n_fast must be >= 1 (got %d, %d)", n_full, n_fast);
     if (!(p_full >= 0.0 && p_full <= 1.0)) return fail(-1, "ccz_draw_budgets: p_full %g must be in [0, 1]", p_full);
     hipLaunchKernelGGL(k_draw_budgets, dim3((e->d.B + 255) / 256), dim3(256), 0, (hipStream_t)stream, e->d, e->d.B, (int)n_full, (int)n_fast, p_full,
@@ -746,7 +781,8 @@ int ccz_set_root_exploration(ccz_engine *e, void *stream, int32_t enabled, doubl
     if (!(eps >= 0.0 && eps <= 1.0)) return fail(-1, "ccz_set_root_exploration: eps %g must be in [0, 1]", eps);
     if (!(alpha > 0.0 && std::isfinite(alpha))) return fail(-1, "ccz_set_root_exploration: alpha %g must be finite and > 0", alpha);
     if (!(forced_k >= 0.0 && std::isfinite(forced_k))) return fail(-1, "ccz_set_root_exploration: forced_k %g must be finite and >= 0", forced_k);
-    if (enabled && e->active > 0) return fail(-1, "ccz_set_root_exploration: not with scout slots (ccz_set_scouts): the one-game path keeps the reference's search");
+    if (enabled && WIDE(e)) return fail(-1, "ccz_set_root_exploration: not while the width is %d (ccz_set_width): the wide search has the plain PUCT rule only", e->width);
+    if (enabled && SCOUTS(e)) return fail(-1, "ccz_set_root_exploration: not with scout slots (ccz_set_scouts): the one-game path keeps the reference's search");
     if (enabled && e->gumbel_on) return fail(-1, "ccz_set_root_exploration: not while the Gumbel root search is on (ccz_set_gumbel): it has its own root rule");
     ExploreCfg v;
     v.enabled = enabled ? 1 : 0;
@@ -784,7 +820,8 @@ int ccz_set_gumbel(ccz_engine *e, void *stream, int32_t enabled, int32_t n_sims,
     if (max_considered < 2 || max_considered > kMaxLegal) return fail(-1, "ccz_set_gumbel: max_considered %d must be in 2..%d", max_considered, kMaxLegal);
     if (!(c_visit >= 0.0 && std::isfinite(c_visit))) return fail(-1, "ccz_set_gumbel: c_visit %g must be finite and >= 0", c_visit);
     if (!(c_scale >= 0.0 && std::isfinite(c_scale))) return fail(-1, "ccz_set_gumbel: c_scale %g must be finite and >= 0", c_scale);
-    if (enabled && e->active > 0) return fail(-1, "ccz_set_gumbel: not with scout slots (ccz_set_scouts): the one-game path keeps the reference's search");
+    if (enabled && WIDE(e)) return fail(-1, "ccz_set_gumbel: not while the width is %d (ccz_set_width): the wide search has the plain PUCT rule only", e->width);
+    if (enabled && SCOUTS(e)) return fail(-1, "ccz_set_gumbel: not with scout slots (ccz_set_scouts): the one-game path keeps the reference's search");
     if (enabled && e->explore_on) return fail(-1, "ccz_set_gumbel: not while root exploration is on (ccz_set_root_exploration)");
     GumbelCfg v;
     v.enabled = enabled ? 1 : 0;
@@ -873,7 +910,8 @@ int ccz_set_search(ccz_engine *e, void *stream, int32_t enabled, int32_t fpu_mod
             return fail(-1, "ccz_set_search: fpu_root_mode %d / fpu_root_value %g: the mode %s", fpu_root_mode, fpu_root_value, why);
         if (!(c_base > 0.0 && std::isfinite(c_base))) return fail(-1, "ccz_set_search: c_base %g must be finite and > 0", c_base);
         if (!(c_factor >= 0.0 && std::isfinite(c_factor))) return fail(-1, "ccz_set_search: c_factor %g must be finite and >= 0", c_factor);
-        if (e->active > 0) return fail(-1, "ccz_set_search: not with scout slots (ccz_set_scouts): the one-game path keeps the reference's search");
+        if (WIDE(e)) return fail(-1, "ccz_set_search: not while the width is %d (ccz_set_width): the wide search has the plain PUCT rule only", e->width);
+        if (SCOUTS(e)) return fail(-1, "ccz_set_search: not with scout slots (ccz_set_scouts): the one-game path keeps the reference's search");
         v.enabled = 1;
         v.fpu_mode = fpu_mode;
         v.fpu_root_mode = fpu_root_mode;
@@ -911,6 +949,7 @@ int ccz_set_solver(ccz_engine *e, void *stream, int32_t enabled)
 {
     NEED(e);
     hipStream_t s = (hipStream_t)stream;
+    if (enabled && WIDE(e)) return fail(-1, "ccz_set_solver: not while the width is %d (ccz_set_width): the wide search has the plain PUCT rule only", e->width);
     const size_t n = (size_t)e->d.B * 2 * (size_t)e->d.cap;
     if (enabled && !e->proof) {
         HIP_TRY(hipSetDevice(e->cfg.device));
@@ -1022,6 +1061,7 @@ int ccz_eval_cache_clear(ccz_engine *e, void *stream)
 int ccz_step_compact(ccz_engine *e, void *stream, const float *value_dev, void *leaf_input_f16_dev)
 {
     NEED(e);
+    NOT_WIDE(e);
     if (!value_dev && !e->d.cache) return fail(-1, "ccz_step_compact: null value (engine-owned leaf values exist only with an evaluation cache)");
     hipLaunchKernelGGL(k_step<true>, dim3(ACTIVE(e)), dim3(64), 0, (hipStream_t)stream, e->d, (const float *)e->d.prior128, value_dev,
                        (uint16_t *)leaf_input_f16_dev);
@@ -1032,6 +1072,7 @@ int ccz_step_compact(ccz_engine *e, void *stream, const float *value_dev, void *
 int ccz_expand_backup_compact(ccz_engine *e, void *stream, const float *value_dev)
 {
     NEED(e);
+    NOT_WIDE(e);
     if (!value_dev && !e->d.cache) return fail(-1, "ccz_expand_backup_compact: null value (engine-owned leaf values exist only with an evaluation cache)");
     hipLaunchKernelGGL(k_expand_backup<true>, dim3(ACTIVE(e)), dim3(64), 0, (hipStream_t)stream, e->d, (const float *)e->d.prior128,
                        value_dev);
@@ -1039,10 +1080,117 @@ int ccz_expand_backup_compact(ccz_engine *e, void *stream, const float *value_de
     return 0;
 }
 
+// ---- wide search (cczero.h: "Wide search")
+int ccz_set_width(ccz_engine *e, void *stream, int32_t width)
+{
+    NEED(e);
+    if (width < 1 || width > 64) return fail(-1, "ccz_set_width: width %d must be in 1 .. 64", width);
+    if (e->d.B % width) return fail(-1, "ccz_set_width: width %d does not divide n_boards %d", width, e->d.B);
+    if (width > 1) {
+        if (SCOUTS(e)) return fail(-1, "ccz_set_width: not with scout slots (ccz_set_scouts)");
+        if (e->explore_on) return fail(-1, "ccz_set_width: not while root exploration is on (ccz_set_root_exploration)");
+        if (e->gumbel_on) return fail(-1, "ccz_set_width: not while the Gumbel root search is on (ccz_set_gumbel)");
+        if (e->solver_on) return fail(-1, "ccz_set_width: not while the solver is on (ccz_set_solver)");
+        if (e->search_on) return fail(-1, "ccz_set_width: not while the search parameters are on (ccz_set_search)");
+        if (e->routed) return fail(-1, "ccz_set_width: not while routing is on (ccz_set_routing)");
+    }
+    hipStream_t s = (hipStream_t)stream;
+    if (width == 1) {
+        if (WIDE(e)) {
+            if (const int rc = wide_drop(e, s, nullptr, -1)) return rc; // (the contract says none is pending: this keeps F zero anyway)
+            e->active = 0;
+        }
+        e->width = 1;
+        return 0;
+    }
+    const size_t n = (size_t)e->d.B * 2 * (size_t)e->d.cap;
+    if (!e->wide_F) {
+        HIP_TRY(hipSetDevice(e->cfg.device));
+        HIP_TRY(dalloc(&e->wide_F, n, e->owned, e->bytes)); // (zeroed; may sync)
+        HIP_TRY(dalloc(&e->wide_stats, (size_t)e->d.B, e->owned, e->bytes));
+        HIP_TRY(dalloc(&e->st_wide, 1, e->owned, e->bytes));
+    } else {
+        HIP_TRY(hipMemsetAsync(e->wide_F, 0, n, s)); // no leaf is pending: all counts are zero
+    }
+    e->width = width;
+    e->active = e->d.B / width;
+    // every slot, not only those past the searched boards: a leaf left pending by the sequential calls (the contract says there is
+    // none) was never counted in F and must not be taken out of it at the next move boundary
+    hipLaunchKernelGGL(k_wide_clear_slots, dim3((unsigned)((e->d.B + 255) / 256)), dim3(256), 0, s, e->d, 0);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// waves of a board's workgroup: one per slot up to 16 (CCZ_WIDE_TAIL_WAVES: an A/B knob of the measurements, 1 = one wave does everything)
+static int wide_waves(int width)
+{
+    static const int forced = [] { const char *v = getenv("CCZ_WIDE_TAIL_WAVES"); return v ? atoi(v) : 0; }();
+    const int want = forced > 0 ? forced : width;
+    return want <= 1 ? 1 : want <= 2 ? 2 : want <= 4 ? 4 : want <= 8 ? 8 : 16;
+}
+
+static int wide_launch(ccz_engine *e, hipStream_t s, const float *value_dev, void *leaf_in, int32_t *n_leaves_dev, int backup)
+{
+    const dim3 grid((unsigned)e->active);
+    const WideArgs wa = wide_args(e);
+    uint16_t *li = (uint16_t *)leaf_in;
+    switch (wide_waves(e->width)) {
+    case 1: hipLaunchKernelGGL(k_wide<1>, grid, dim3(64), 0, s, e->d, wa, value_dev, li, n_leaves_dev, backup); break;
+    case 2: hipLaunchKernelGGL(k_wide<2>, grid, dim3(128), 0, s, e->d, wa, value_dev, li, n_leaves_dev, backup); break;
+    case 4: hipLaunchKernelGGL(k_wide<4>, grid, dim3(256), 0, s, e->d, wa, value_dev, li, n_leaves_dev, backup); break;
+    case 8: hipLaunchKernelGGL(k_wide<8>, grid, dim3(512), 0, s, e->d, wa, value_dev, li, n_leaves_dev, backup); break;
+    default: hipLaunchKernelGGL(k_wide<16>, grid, dim3(1024), 0, s, e->d, wa, value_dev, li, n_leaves_dev, backup); break;
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int ccz_select_wide(ccz_engine *e, void *stream, void *leaf_input_f16_dev, int32_t *n_leaves_dev)
+{
+    NEED(e);
+    if (!WIDE(e)) return fail(-1, "ccz_select_wide: the width is 1 (ccz_set_width): the sequential search selects with ccz_select_leaves");
+    if (!n_leaves_dev) return fail(-1, "ccz_select_wide: null n_leaves");
+    return wide_launch(e, (hipStream_t)stream, nullptr, leaf_input_f16_dev, n_leaves_dev, 0);
+}
+
+int ccz_step_wide(ccz_engine *e, void *stream, const float *value_dev, void *leaf_input_f16_dev, int32_t *n_leaves_dev)
+{
+    NEED(e);
+    if (!WIDE(e)) return fail(-1, "ccz_step_wide: the width is 1 (ccz_set_width): the sequential search steps with ccz_step_compact");
+    if (!n_leaves_dev) return fail(-1, "ccz_step_wide: null n_leaves");
+    if (!value_dev && !e->d.cache) return fail(-1, "ccz_step_wide: null value (engine-owned leaf values exist only with an evaluation cache)");
+    return wide_launch(e, (hipStream_t)stream, value_dev, leaf_input_f16_dev, n_leaves_dev, 1);
+}
+
+int ccz_get_wide_stats(ccz_engine *e, void *stream, ccz_wide_stats *out)
+{
+    NEED(e);
+    if (!out) return fail(-1, "ccz_get_wide_stats: null output");
+    memset(out, 0, sizeof *out);
+    if (!e->wide_F) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<WideBoardStats> st;
+    if (const int rc = fetch_board_stats(e, s, e->wide_stats, st)) return rc;
+    for (const WideBoardStats &b : st) {
+        out->steps += (int64_t)b.steps;
+        out->leaves += (int64_t)b.leaves;
+        out->collisions += (int64_t)b.collisions;
+    }
+    unsigned long long sum = 0;
+    HIP_TRY(hipMemsetAsync(e->st_wide, 0, sizeof sum, s));
+    hipLaunchKernelGGL(k_wide_inflight, dim3(ACTIVE(e)), dim3(256), 0, s, e->d, wide_args(e), e->st_wide);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&sum, e->st_wide, sizeof sum, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    out->inflight_now = (int64_t)sum;
+    return 0;
+}
+
 int ccz_finish_move(ccz_engine *e, void *stream, const int32_t *forced_moves_dev, const double *temps_dev,
                     int32_t *moves_out_dev, int32_t keep_tree)
 {
     NEED(e);
+    if (const int rc = wide_drop(e, (hipStream_t)stream, nullptr, -1)) return rc;
     hipLaunchKernelGGL(k_finish_move, dim3(ACTIVE(e)), dim3(64), 0, (hipStream_t)stream, e->d, forced_moves_dev, temps_dev,
                        moves_out_dev, keep_tree ? 1 : 0);
     HIP_TRY(hipGetLastError());

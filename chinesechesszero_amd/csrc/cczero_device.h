@@ -128,6 +128,18 @@ struct SolverBoardStats {
     unsigned long long proven, stops; // nodes whose byte left "unknown"; simulations that ended at a node proven before
 };
 
+// Wide search (ccz_set_width): several pending leaves per board and step, with virtual loss. The in-flight counts F (uint8 per tree
+// node, [B][2][cap], indexed like nodeA / nodeB) and the counters live behind the host's engine, not in Dev: they are allocated by the
+// first ccz_set_width(width > 1) and handed to the wide kernels as arguments; no other kernel knows of them.
+struct WideBoardStats {
+    unsigned long long steps, leaves, collisions; // board-steps that selected a leaf; leaves selected; batches ended by a collision
+};
+struct WideArgs {
+    int32_t A, W;          // searched boards; slots per board (slot r + j * A = the j-th pending leaf of board r)
+    uint8_t *F;
+    WideBoardStats *stats; // [A]
+};
+
 struct Dev {
     int32_t B, cap, maxd, max_plies, pi_cap;
     int32_t reserve;   // nodes of every pool half kept free at re-root time for the next move's expansions

@@ -1003,8 +1003,10 @@ __device__ __attribute__((noinline)) uint32_t proof_backup(const Dev &D, uint8_t
 
 // ------------------------------------------------------------------ K2: expand + backup
 // prob: dense [B][2086] priors (compact == false) or compact [B][128] priors aligned with leaf_ids (compact == true)
+// r: the board whose tree, node pool and counters are updated; b: the slot holding the pending leaf (path, ids, status, priors, value).
+// r == b everywhere but in the wide search (k_wide), where slot r + j * A holds the j-th pending leaf of board r.
 template <bool COMPACT>
-__device__ inline TopPatch expand_backup_phase(const Dev &D, int b, int lane, const float *prob, const float *value,
+__device__ inline TopPatch expand_backup_phase(const Dev &D, int r, int b, int lane, const float *prob, const float *value,
                                                const BoardMeta &m0, int half, const SolverCfg &sv)
 {
     TopPatch tp;
@@ -1025,8 +1027,8 @@ __device__ inline TopPatch expand_backup_phase(const Dev &D, int b, int lane, co
     const int pj = path[lane < D.maxd ? lane : 0];
     if (status == CCZ_LEAF_SKIP) return tp;
     CCZ_STAMP(D, b, lane, 8)
-    BoardMeta *mp = D.meta + b;
-    const size_t base = ((size_t)b * 2 + half) * (size_t)D.cap;
+    BoardMeta *mp = D.meta + r;
+    const size_t base = ((size_t)r * 2 + half) * (size_t)D.cap;
     NodeA *A = D.nodeA + base;
     uint32_t *Bn = D.nodeB + base;
     const int leaf = __builtin_amdgcn_readlane(pj, __builtin_amdgcn_readfirstlane(d < 64 ? d : 0));
@@ -1063,7 +1065,7 @@ __device__ inline TopPatch expand_backup_phase(const Dev &D, int b, int lane, co
                 A[leaf0].fc = n0;
                 Bn[leaf0] = (Bn[leaf0] & 0xffffu) | ((uint32_t)k << 16);
                 mp->n_nodes = n0 + k;
-                BoardStats &st = D.stats[b];
+                BoardStats &st = D.stats[r];
                 st.sum_children += (unsigned long long)k;
                 st.expansions += 1;
                 if (n0 + k > st.nodes_peak) st.nodes_peak = n0 + k;
@@ -1071,11 +1073,11 @@ __device__ inline TopPatch expand_backup_phase(const Dev &D, int b, int lane, co
         }
     } else {
         v = status == CCZ_LEAF_DRAW ? 0.0f : status == CCZ_LEAF_WIN ? 1.0f : -1.0f; // mcts.py:120-126; WIN: a node proven won (solver)
-        if (lane == 0) D.stats[b].terminal += 1;
+        if (lane == 0) D.stats[r].terminal += 1;
     }
     if (lane == 0) {
-        D.stats[b].sims += 1;
-        D.move_sims[b] += 1;
+        D.stats[r].sims += 1;
+        D.move_sims[r] += 1;
         D.leaf_status[b] = CCZ_LEAF_SKIP; // consumed: a repeated call must not back the same leaf up twice
     }
     // Node.update_recursive(-leaf_value) (mcts.py:73-78,129): leaf gets -v, its parent +v, ...
@@ -1115,9 +1117,9 @@ __device__ inline TopPatch expand_backup_phase(const Dev &D, int b, int lane, co
     tp.Q1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(myQ), 1));
     // ---- MCTS-solver: a simulation that ended in a decided position proves what it can of its path (off, or an expansion: nothing)
     if (solver && status != CCZ_LEAF_EXPAND) {
-        const uint32_t r = proof_backup(D, sv.proof + base, A, Bn, path, D.sv_stats + b, pj, d, status, leaf, lane);
-        tp.hasp1 = (r & 0x100u) != 0u;
-        tp.p1 = r & 0xffu;
+        const uint32_t top = proof_backup(D, sv.proof + base, A, Bn, path, D.sv_stats + r, pj, d, status, leaf, lane);
+        tp.hasp1 = (top & 0x100u) != 0u;
+        tp.p1 = top & 0xffu;
     }
     return tp;
 }
@@ -1127,7 +1129,7 @@ __global__ __launch_bounds__(64) void k_expand_backup(Dev D, const float *prob, 
 {
     const BoardMeta m0 = D.meta[blockIdx.x];
     const SolverCfg sv = solver_cfg(D);
-    (void)expand_backup_phase<COMPACT>(D, blockIdx.x, threadIdx.x, prob, value, m0, *D.half, sv);
+    (void)expand_backup_phase<COMPACT>(D, blockIdx.x, blockIdx.x, threadIdx.x, prob, value, m0, *D.half, sv);
 }
 
 // ------------------------------------------------------------------ fused step: expand+backup of the pending leaf, then the next select
@@ -1140,7 +1142,7 @@ __global__ __launch_bounds__(64) void k_step(Dev D, const float *prob, const flo
     const int b = blockIdx.x, lane = threadIdx.x;
     CCZ_STAMP(D, b, lane, 0)
     const Prefetch P = prefetch_board(D, b, lane); // root board, chain and meta: untouched by the expand phase
-    const TopPatch tp = expand_backup_phase<COMPACT>(D, b, lane, prob, value, P.m, P.half, P.sv);
+    const TopPatch tp = expand_backup_phase<COMPACT>(D, b, b, lane, prob, value, P.m, P.half, P.sv);
     CCZ_STAMP(D, b, lane, 1)
     __threadfence_block();
     __syncthreads();
@@ -1570,7 +1572,7 @@ __global__ __launch_bounds__(64 * MAXW) void k_scouted_run(Dev D, uint16_t *leaf
         TopPatch tp;
         if (real) {
             P = prefetch_board(D, w, lane);
-            tp = expand_backup_phase<true>(D, w, lane, D.prior128, nullptr, P.m, P.half, P.sv);
+            tp = expand_backup_phase<true>(D, w, w, lane, D.prior128, nullptr, P.m, P.half, P.sv);
             __threadfence_block();      // (k_step: the phases touch the same nodes from different lanes of the wave)
             __builtin_amdgcn_wave_barrier();
         }
@@ -2929,5 +2931,230 @@ __global__ void k_apply_moves(int n, uint8_t *sq, uint8_t *turn, const int32_t *
 
 namespace ccz {
 // one thread, after k_finish_move: all live trees now sit in the other pool half
+
+// ------------------------------------------------------------------ wide search: several leaves per board and step, with virtual loss
+// (ccz_set_width / ccz_select_wide / ccz_step_wide; the rule is stated in cczero.h). One workgroup per searched board r. Wave 0 runs
+// the cheap, inherently serial part -- phase A, the backups of the board's pending slots in slot order, then phase B's descents, each
+// seeing the in-flight counts F the earlier ones left -- with one dependent load round per tree level, as select_phase has. The
+// expensive part of a selection (replaying the path, move generation, game end, key, evaluator input row: leaf_tail) does not touch
+// the tree, so the workgroup's NW waves then run the selected slots' tails side by side, each in its own SelectShared, like the scout
+// waves of k_scouted_run. All hand-offs stay inside the workgroup (one CU, one L1): workgroup-scope fences and barriers.
+// The options the wide search excludes (root exploration, Gumbel, solver, search parameters) are refused on the host: none is read.
+
+// one descent under wide PUCT from the root of board r; returns the depth of the node it ends at (its path is written to `path`), or
+// -1 after CCZ_ERR_NAN / CCZ_ERR_DEPTH. leafF <- the in-flight count of that node. All 64 lanes call it.
+__device__ inline int wide_descend(const Dev &D, const NodeA *A, const uint32_t *Bn, const uint8_t *F, int32_t *path, int lane, int &leafF)
+{
+    NodeA pa = A[0];
+    uint32_t nb = Bn[0];
+    int pF = F[0];
+    int depth = 0;
+    if (lane == 0) path[0] = 0;
+    for (;;) {
+        const int nc = (int)(nb >> 16);
+        if (nc == 0) break;
+        const double sqrtNp = sqrt((double)(pa.N + pF));
+        double best = -__builtin_huge_val();
+        int besti = 0x7fffffff, bN = 0, bfc = -1, bFl = 0;
+        float bQ = 0.0f;
+        uint32_t bw = 0;
+        for (int c0 = 0; c0 < nc; c0 += 64) {
+            const int i = c0 + lane;
+            if (i < nc) {
+                const NodeA c = A[CCZ_IDX(D, pa.fc + i, D.cap)];
+                const uint32_t w = Bn[CCZ_IDX(D, pa.fc + i, D.cap)];
+                const int f = F[CCZ_IDX(D, pa.fc + i, D.cap)];
+                const int ne = c.N + f;
+                // every in-flight visit counts as one loss for the side that moved into the child; F = 0: the expression of select_phase
+                double qe = (double)c.Q;
+                if (f != 0) qe = ((double)c.N * (double)c.Q - (double)f) / (double)ne;
+                const double sc = ne == 0 ? __builtin_huge_val() : qe + (double)(D.c_puct * c.P) * sqrtNp / (double)(1 + ne);
+                if (sc > best) { best = sc; besti = i; bN = c.N; bQ = c.Q; bfc = c.fc; bw = w; bFl = f; }
+            }
+        }
+        const double top = wave_max_f64(best);
+        const bool hit = best == top && besti < nc;
+        const uint64_t h0 = __ballot(hit && besti < 64), h1 = __ballot(hit);
+        if (h1 == 0ull) { set_err(D, 32); return -1; } // NaN priors: no comparable child
+        const int owner = __builtin_amdgcn_readfirstlane((h0 ? __ffsll((long long)h0) : __ffsll((long long)h1)) - 1);
+        besti = __builtin_amdgcn_readlane(besti, owner);
+        const int child = pa.fc + besti;
+        pa.N = __builtin_amdgcn_readlane(bN, owner);
+        pa.Q = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(bQ), owner));
+        pa.fc = __builtin_amdgcn_readlane(bfc, owner);
+        nb = (uint32_t)__builtin_amdgcn_readlane((int)bw, owner);
+        pF = __builtin_amdgcn_readlane(bFl, owner);
+        ++depth;
+        if (depth >= D.maxd) { set_err(D, 2); return -1; }
+        if (lane == 0) path[CCZ_IDX(D, depth, D.maxd)] = child;
+    }
+    leafF = pF;
+    return depth;
+}
+
+// F += delta on the nodes path[0 .. d] (distinct nodes: one lane each)
+__device__ __forceinline__ void wide_count(const Dev &D, uint8_t *F, const int32_t *path, int d, int delta, int lane)
+{
+    for (int j = lane; j <= d; j += 64) {
+        const int node = (int)CCZ_IDX(D, path[CCZ_IDX(D, j, D.maxd)], D.cap);
+        F[node] = (uint8_t)((int)F[node] + delta);
+    }
+}
+
+// what one wave hands the next phase of the same wave through global memory
+__device__ __forceinline__ void wide_fence()
+{
+    __threadfence_block();
+    __builtin_amdgcn_wave_barrier();
+}
+
+template <int NW>
+__global__ __launch_bounds__(64 * NW) void k_wide(Dev D, WideArgs wa, const float *value, uint16_t *leaf_in, int32_t *n_leaves, int backup)
+{
+    __shared__ SelectShared sh[NW];
+    __shared__ int s_depth[64]; // slot j of this step: the depth of its selected leaf, -1: nothing selected
+    __shared__ int s_undo[64];  // ... its tail refused the leaf (CCZ_ERR_CHAIN): the path leaves F again
+    const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int A = wa.A, W = wa.W;
+    const int half = *D.half;
+    const size_t base = ((size_t)r * 2 + half) * (size_t)D.cap;
+    uint8_t *F = wa.F + base;
+    const BoardMeta m = D.meta[r];
+    if (w == 0) {
+        if (lane < 64) { s_depth[lane] = -1; s_undo[lane] = 0; }
+        SolverCfg sv;
+        sv.enabled = 0; sv.pad = 0; sv.proof = nullptr;
+        int sims = D.move_sims[r];
+        // ---- phase A: the pending slots are backed up in slot order
+        if (backup) {
+            BoardMeta mm = m;
+            for (int j = 0; j < W; ++j) {
+                const int s = r + j * A;
+                const int d = D.path_len[s]; // (read before the backup: the slot's status decides whether it counts)
+                const TopPatch tp = expand_backup_phase<true>(D, r, s, lane, D.prior128, value, mm, half, sv);
+                if (tp.active) {
+                    wide_count(D, F, D.path + (size_t)s * D.maxd, d, -1, lane);
+                    if (tp.k > 0) mm.n_nodes = tp.n0 + tp.k;
+                    ++sims;
+                    wide_fence(); // the next slot's backup reads N, Q and F of shared path nodes from other lanes
+                }
+            }
+        }
+        // ---- phase B: up to W descents, each seeing the in-flight counts of the earlier ones
+        const int budget = D.budget[r];
+        const NodeA *An = D.nodeA + base;
+        const uint32_t *Bn = D.nodeB + base;
+        int t = 0;
+        bool ended = m.over != 0;
+        bool collided = false;
+        for (int j = 0; j < W; ++j) {
+            const int s = r + j * A;
+            int32_t *path = D.path + (size_t)s * D.maxd;
+            int d = -1;
+            if (!ended && sims + t < budget) {
+                int leafF = 0;
+                d = wide_descend(D, An, Bn, F, path, lane, leafF);
+                if (d < 0) ended = true; // (the slot gets SKIP below: the same byte as NONE)
+                else if (leafF > 0) { ended = true; collided = true; d = -1; }
+            }
+            if (d < 0) {
+                if (lane == 0) { D.leaf_status[s] = CCZ_LEAF_NONE; D.leaf_k[s] = 0; D.path_len[s] = 0; }
+                continue;
+            }
+            wide_fence();                 // the path (lane 0's stores) is read by every lane
+            wide_count(D, F, path, d, +1, lane);
+            wide_fence();                 // ... and the counts by the next descent
+            if (lane == 0) s_depth[j] = d;
+            ++t;
+        }
+        if (lane == 0) {
+            n_leaves[r] = t;
+            WideBoardStats &ws = wa.stats[r];
+            if (t > 0) ws.steps += 1;
+            ws.leaves += (unsigned long long)t;
+            if (collided) ws.collisions += 1;
+        }
+    }
+    __threadfence_block(); // the selected slots' paths and the tree as backed up: read by every wave from here on
+    __syncthreads();
+    // ---- the leaf tails of the selected slots, one wave per slot (slots NW apart share a wave)
+    for (int j = w; j < W; j += NW) {
+        const int d = s_depth[j];
+        if (d < 0) continue;
+        const int s = r + j * A;
+        SelectShared &S = sh[w];
+        const int32_t *path = D.path + (size_t)s * D.maxd;
+        const uint32_t *Bn = D.nodeB + base;
+        if (lane < 24) {
+            uint32_t v = ((const uint32_t *)(D.root_sq + (size_t)r * 96))[lane];
+            if (lane == 22) v &= 0x0000ffffu;
+            if (lane == 23) v = 0u;
+            ((uint32_t *)S.sq)[lane] = v;
+        }
+        S.chain[lane] = D.chain[(size_t)r * kChainCap + lane];
+        if (m.chain_len > 64) S.chain[64 + lane] = D.chain[(size_t)r * kChainCap + 64 + lane];
+        for (int i = 1 + lane; i <= d; i += 64)
+            S.pm.mv[i - 1] = (uint16_t)(Bn[CCZ_IDX(D, path[CCZ_IDX(D, i, D.maxd)], D.cap)] & 0xffffu);
+        wave_sync();
+        leaf_tail(D, s, lane, leaf_in, S, d, m.turn, m.halfmove, m.chain_len, m.key, true);
+        if (lane == 0 && D.leaf_status[s] == CCZ_LEAF_SKIP) s_undo[j] = 1; // (lane 0 wrote the status itself)
+        wave_sync(); // the next slot of this wave reuses the LDS block
+    }
+    __syncthreads();
+    if (w == 0) {
+        for (int j = 0; j < W; ++j)
+            if (s_undo[j]) {
+                const int s = r + j * A;
+                wide_count(D, F, D.path + (size_t)s * D.maxd, s_depth[j], -1, lane);
+                if (lane == 0) D.path_len[s] = 0;
+                wide_fence();
+            }
+    }
+}
+
+// The move boundary of a wide engine: the pending leaves of board r's slots are dropped -- their paths leave F, the slots get
+// CCZ_LEAF_NONE. Launched in front of the kernel that resets, re-roots or reloads the trees (between moves F is zero everywhere).
+// only >= 0: that board alone; mask: as in k_reset. One thread per board: the slots of a board share path nodes.
+__global__ void k_wide_drop(Dev D, WideArgs wa, const uint8_t *mask, int only)
+{
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= wa.A || (only >= 0 && r != only) || (mask && !mask[r])) return;
+    uint8_t *F = wa.F + ((size_t)r * 2 + *D.half) * (size_t)D.cap;
+    for (int j = 0; j < wa.W; ++j) {
+        const int s = r + j * wa.A;
+        if (D.leaf_status[s] != CCZ_LEAF_NONE) {
+            const int32_t *path = D.path + (size_t)s * D.maxd;
+            const int d = D.path_len[s];
+            for (int i = 0; i <= d && i < D.maxd; ++i) {
+                const int node = (int)CCZ_IDX(D, path[i], D.cap);
+                F[node] = (uint8_t)(F[node] - 1);
+            }
+        }
+        D.leaf_status[s] = CCZ_LEAF_NONE;
+        D.leaf_k[s] = 0;
+        D.path_len[s] = 0;
+    }
+}
+
+// slots A .. B - 1 of an engine whose width was just set (ccz_set_width passes A = 0: every slot): no pending leaf
+__global__ void k_wide_clear_slots(Dev D, int A)
+{
+    const int s = A + blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= D.B) return;
+    D.leaf_status[s] = CCZ_LEAF_NONE;
+    D.leaf_k[s] = 0;
+    D.path_len[s] = 0;
+}
+
+// sum of F over the live pool half of the searched boards (ccz_get_wide_stats.inflight_now); *out is zeroed by the caller
+__global__ __launch_bounds__(256) void k_wide_inflight(Dev D, WideArgs wa, unsigned long long *out)
+{
+    const uint8_t *F = wa.F + ((size_t)blockIdx.x * 2 + *D.half) * (size_t)D.cap;
+    unsigned long long sum = 0;
+    for (int i = threadIdx.x; i < D.cap; i += 256) sum += F[i];
+    if (sum) atomicAdd(out, sum);
+}
+
 __global__ void k_flip_half(Dev D) { *D.half ^= 1; }
 } // namespace ccz

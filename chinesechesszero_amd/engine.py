@@ -240,6 +240,45 @@ class SelfPlayEngine:
         check(self.L.ccz_step_compact(self.h, self._stream(), _ptr(value), _ptr(self.leaf_input)))
         return self.leaf_input
 
+    # ------------------------------------------------------------------ wide search (include/cczero.h "Wide search")
+    def set_width(self, width: int):
+        """``width`` > 1: boards 0 .. B / width - 1 are searched and gather up to ``width`` leaves of their one tree per step, kept
+        apart by virtual loss; slot ``r + j * A`` holds the j-th pending leaf of board r. 1: off, the sequential search. Call it
+        with no leaf pending."""
+        check(self.L.ccz_set_width(self.h, self._stream(), int(width)))
+        self.width = int(width)
+        self.A = self.B // self.width
+        if not hasattr(self, "n_leaves_host"):
+            self.n_leaves_host = torch.zeros((self.B,), dtype=torch.int32).pin_memory()   # written by the wide kernels: [A] leaves selected
+            self._n_leaves_np = self.n_leaves_host.numpy()
+
+    def select_wide(self) -> torch.Tensor:
+        """Phase B alone (a move's first step): up to ``width`` leaves per searched board; the evaluator input of all ``B`` slots."""
+        self._need_wide()
+        check(self.L.ccz_select_wide(self.h, self._stream(), _ptr(self.leaf_input), C.c_void_p(self.n_leaves_host.data_ptr())))
+        return self.leaf_input
+
+    def step_wide(self, value: torch.Tensor | None) -> torch.Tensor:
+        """Back the pending slots up from the engine's prior rows and ``value`` [B] (None: the engine-owned leaf values of the
+        planned boundary), then select the next leaves: one launch. With every budget used up it is the move's last backup."""
+        self._need_wide()
+        check(self.L.ccz_step_wide(self.h, self._stream(), _ptr(value), _ptr(self.leaf_input), C.c_void_p(self.n_leaves_host.data_ptr())))
+        return self.leaf_input
+
+    def _need_wide(self):
+        if getattr(self, "width", 1) <= 1:
+            raise CczError("the width is 1: set_width(width > 1) turns the wide search on")
+
+    def n_leaves(self) -> np.ndarray:
+        """Wait for the stream; leaves selected per searched board by the last :meth:`select_wide` / :meth:`step_wide` (int32 [A])."""
+        torch.cuda.current_stream(self.device).synchronize()
+        return self._n_leaves_np[: self.A].copy()
+
+    def wide_stats(self) -> dict:
+        st = _lib.WideStats()
+        check(self.L.ccz_get_wide_stats(self.h, self._stream(), C.byref(st)))
+        return {k: int(getattr(st, k)) for k, _ in st._fields_}
+
     # ------------------------------------------------------------------ planned evaluator boundary (evaluation cache)
     def eval_plan(self):
         """Probe the evaluation cache for the pending leaves and plan the evaluator's batch: returns the device tensors

@@ -68,8 +68,11 @@ SCOUTS = 10  # scout slots of a one-game search (ScoutedSearch): 1 + 10 = 11 row
 
 class MCTS:
     def __init__(self, policy_value_fn, c_puct=5, n_playout=10000, device: int = 0, seed: int = 0, scouts: int | None = None,
-                 solver: bool = False, search=None):
-        """``search``: a dict of ``SelfPlayEngine.set_search``'s arguments (first-play urgency, visit-scaled c_puct). Scout slots rest
+                 solver: bool = False, search=None, width: int | None = None):
+        """``width``: None / 1 (default): the sequential search, scouted as below. 2..64: the wide search (``wide.WideSearch``): up to
+        ``width`` leaves of the tree per evaluator call, kept apart by virtual loss -- another tree than the reference's; needs a
+        batched evaluator that returns logits, and excludes ``scouts`` > 0, ``solver`` and ``search`` (ValueError).
+        ``search``: a dict of ``SelfPlayEngine.set_search``'s arguments (first-play urgency, visit-scaled c_puct). Scout slots rest
         on children being first visited in legal-move order, which the rule ends: with ``search`` given and ``scouts`` None the search
         runs with ``scouts=0``; both given explicitly raise ValueError.
         ``scouts``: scout slots of the one-game search (``selfplay.ScoutedSearch``; same visit counts, fewer evaluator calls);
@@ -78,6 +81,14 @@ class MCTS:
         a proven root asks for."""
         self.policy = policy_value_fn
         self.search_cfg = None if search is None else dict(search)
+        self.width = 1 if width is None else int(width)
+        if not 1 <= self.width <= 64:
+            raise ValueError(f"width must be in 1..64 (got {width})")
+        if self.width > 1:
+            if scouts or solver or search is not None:
+                raise ValueError("width > 1 (the wide search) excludes scouts, the solver and the search parameters")
+            scouts = 0
+        self._wide = None
         scouts = resolve_scouts(self.search_cfg, scouts)
         self.solver = bool(solver)
         self.c_puct = c_puct
@@ -103,10 +114,20 @@ class MCTS:
         want = int(os.environ.get("CCZ_SCOUTS", SCOUTS)) if scouts is None else int(scouts)
         ok = self._batched is not None and getattr(self._batched, "returns_logits", False)
         self.scouts = max(0, min(want, 63)) if ok else 0
+        if self.width > 1:
+            if not ok:
+                raise ValueError("width > 1 (the wide search) needs a batched evaluator that returns logits (PolicyValueNet.policy_value_fn)")
+            self.scouts = 0
         self._scouted = None
 
     # ---- engine management -----------------------------------------------------------------------
     def _ensure_engine(self):
+        if self._engine is None and self.width > 1:
+            # one searched board, `width` slots for its pending leaves: every step is one evaluator call on all (at most 64) rows
+            from .wide import WideSearch
+            self._wide = WideSearch(self._batched, 1, self.width, n_playout=max(1, self.n_playout), c_puct=self.c_puct, device=self._device,
+                                    seed=self._seed, use_graph=self.use_graph, mirror=True, strict=True)
+            self._engine = self._wide.engine
         if self._engine is None:
             # board 0 is the game; the scout slots behind it (no tree, no game of their own) carry the leaves board 0 will ask for next
             # through a small evaluation cache (2^16 positions, 34 MB)
@@ -134,12 +155,14 @@ class MCTS:
         same_start = self._start is not None and np.array_equal(self._start[0], start[0]) and self._start[1:] == start[1:]
         if not same_start or self._synced is None or ids[:len(self._synced)] != self._synced:
             e.set_position(0, start[0], 1 if start[1] else 0, start[2])
+            self._boundary()
             self._start = (start[0].copy(), start[1], start[2])
             self._synced = []
             self._discard = False
         new = ids[len(self._synced):]
         for mid in new:
             e.finish_move(forced_moves=self._forced(mid), keep_tree=not self._discard)
+            self._boundary()
             self._synced.append(mid)
         if self._discard and not new:
             self._reset_tree_keep_position(board)
@@ -149,7 +172,12 @@ class MCTS:
     def _reset_tree_keep_position(self, board):
         # Node(None, 1.0) (mcts.py:176-178): one launch; position, history chain and clocks stay on the engine
         self._engine.reset_tree()
+        self._boundary()
         self._discard = False
+
+    def _boundary(self):
+        if self._wide is not None:
+            self._wide.boundary()   # the board's simulation count starts over: the next search is n_playout simulations again
 
     # ---- reference surface ------------------------------------------------------------------------
     def playout(self, board=None, red_states=None, black_states=None):
@@ -184,6 +212,24 @@ class MCTS:
         e = self._engine
         fused = self._batched is not None
         logits = fused and getattr(self._batched, "returns_logits", False)
+        if self._wide is not None:
+            # the wide search: every step backs up and selects up to `width` leaves; on_playout sees the leaves of each step
+            def on_step(nl):
+                nonlocal acc
+                acc += int(nl[0])
+                if on_playout is not None and acc >= interval:
+                    try:
+                        on_playout(acc)
+                    except Exception:
+                        pass
+                    acc = 0
+            self._wide.search(on_step=on_step)
+            if on_playout is not None and acc:
+                try:
+                    on_playout(acc)
+                except Exception:
+                    pass
+            return self._root_probs(temp)
         if fused and self.scouts:
             # one game at a time with scout slots: the evaluator runs only when board 0's leaf is not in the table yet, on 1 + scouts rows
             if self._scouted is None:
@@ -232,6 +278,9 @@ class MCTS:
                 (e.expand_backup_logits if logits else e.expand_backup)(*self._batched(leaf))
             acc += 1
             report(i == self.n_playout - 1)
+        return self._root_probs(temp)
+
+    def _root_probs(self, temp):
         rc = self._engine.root_children()
         self._engine.check_healthy()
         k = int(rc["k"][0])
@@ -246,6 +295,7 @@ class MCTS:
             self._discard = True
             return
         self._engine.finish_move(forced_moves=self._forced(last_move), keep_tree=True)
+        self._boundary()
         self._synced.append(int(last_move))
 
     def root_children(self):
@@ -272,11 +322,12 @@ class MCTS_AI:
     """reference mcts.py:181-233"""
 
     def __init__(self, policy_value_fn, c_puct=5, n_playout=2000, is_selfplay=False, device: int = 0, seed: int = 0, scouts: int | None = None,
-                 solver: bool = False, search=None):
-        """``search``: as in :class:`MCTS` (with it, ``scouts`` None means 0 and ``scouts`` > 0 raises ValueError).
+                 solver: bool = False, search=None, width: int | None = None):
+        """``width``: as in :class:`MCTS` (None / 1: the scouted sequential search; 2..64: the wide search).
+        ``search``: as in :class:`MCTS` (with it, ``scouts`` None means 0 and ``scouts`` > 0 raises ValueError).
         ``solver``: search with the MCTS-solver and play the proven move when the root is decided (the fastest mate, the longest
         defence) instead of drawing from the visit counts."""
-        self.mcts = MCTS(policy_value_fn, c_puct, n_playout, device=device, seed=seed, scouts=scouts, solver=solver, search=search)
+        self.mcts = MCTS(policy_value_fn, c_puct, n_playout, device=device, seed=seed, scouts=scouts, solver=solver, search=search, width=width)
         self.is_selfplay = is_selfplay
         self.agent = "AI"
 

@@ -77,6 +77,7 @@ class UciLoop:
         self.ai = None
         self.multipv = 1
         self.solver = False
+        self.width = 1               # Width: leaves per evaluator call (1: the sequential, scouted search)
         self.search_opts = {}        # FpuReduction / FpuAbsolute / CpuctBase / CpuctFactor as set; empty: the reference's PUCT
 
     def _search(self):
@@ -94,9 +95,10 @@ class UciLoop:
             from .net import PolicyValueNet
             self.policy_value_fn = PolicyValueNet(device=f"cuda:{self.device}").policy_value_fn
         search = self._search()
-        if self.ai is None or self.ai.mcts.n_playout != nodes or self.ai.mcts.solver != self.solver or self.ai.mcts.search_cfg != search:
+        if self.ai is None or self.ai.mcts.n_playout != nodes or self.ai.mcts.solver != self.solver or self.ai.mcts.search_cfg != search \
+                or self.ai.mcts.width != self.width:
             self.ai = MCTS_AI(self.policy_value_fn, c_puct=C_PUCT, n_playout=nodes, is_selfplay=False, device=self.device, solver=self.solver,
-                              search=search)
+                              search=search, width=self.width)
         return self.ai
 
     def _say_pvs(self, ai):
@@ -135,6 +137,7 @@ class UciLoop:
             self._say(f"option name Playouts type spin default {self.n_playout} min 1 max 1000000")
             self._say("option name MultiPV type spin default 1 min 1 max 128")
             self._say("option name Solver type check default false")
+            self._say("option name Width type spin default 1 min 1 max 64")
             self._say("option name FpuReduction type string default <empty>")
             self._say("option name FpuAbsolute type string default <empty>")
             self._say("option name CpuctBase type string default <empty>")
@@ -147,11 +150,27 @@ class UciLoop:
         elif cmd == "setoption" and len(tok) >= 5 and tok[1] == "name" and tok[2].lower() == "multipv":
             self.multipv = max(1, min(128, int(tok[4])))
         elif cmd == "setoption" and len(tok) >= 5 and tok[1] == "name" and tok[2].lower() == "solver":
-            self.solver = tok[4].lower() == "true"
+            if tok[4].lower() == "true" and self.width > 1:
+                self._say("info string error the solver and Width > 1 exclude each other")
+            else:
+                self.solver = tok[4].lower() == "true"
+        elif cmd == "setoption" and len(tok) >= 5 and tok[1] == "name" and tok[2].lower() == "width":
+            try:
+                w = int(tok[4])
+                if not 1 <= w <= 64:
+                    raise ValueError(f"Width {w} must be in 1..64")
+                if w > 1 and (self.solver or self.search_opts):
+                    raise ValueError("Width > 1 excludes the solver and the search parameters")
+            except ValueError as e:
+                self._say(f"info string error {e}")
+            else:
+                self.width = w
         elif cmd == "setoption" and len(tok) >= 5 and tok[1] == "name" and tok[2].lower() in ("fpureduction", "fpuabsolute", "cpuctbase", "cpuctfactor"):
             name = tok[2].lower()
             old = dict(self.search_opts)
             try:
+                if self.width > 1:
+                    raise ValueError("the search parameters and Width > 1 exclude each other")
                 self.search_opts[name] = float(tok[4])
                 if name in ("fpureduction", "fpuabsolute"):      # the later of the two forms stands
                     self.search_opts.pop("fpuabsolute" if name == "fpureduction" else "fpureduction", None)

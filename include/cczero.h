@@ -564,6 +564,66 @@ int ccz_root_proof(ccz_engine *e, void *stream, uint8_t *state_host, uint8_t *di
 int ccz_get_solver_stats(ccz_engine *e, void *stream, ccz_solver_stats *out);
 int ccz_proof_combine(void *stream, const uint8_t *bytes_dev, const int32_t *counts_dev, int32_t n_cases, uint8_t *out_dev);
 
+/* ---- Wide search: several pending leaves per board and step, with virtual loss (additive to ABI 9) -------------------------------------
+ * Every board runs a strictly sequential MCTS by default: one leaf per board and lockstep step. That fills the chip at thousands of
+ * boards and leaves it idle where boards are few (one game, a handful of analysed positions): the evaluator call costs the same for
+ * one row as for 64. With a width W > 1 a board gathers up to W leaves of its ONE tree per step, as Lc0 / KataGo / AlphaGo do, kept
+ * apart by virtual loss. Off (width 1: the state of a new engine): every output of every call is bit for bit what it is without the
+ * feature; nothing of it is allocated or read.
+ *
+ * The rule ("wide PUCT"). An engine of n_boards = A * W slots has A searched boards, 0 .. A-1: trees and games exist only there (as
+ * with scout slots). Slot s(r, j) = r + j * A, j = 0 .. W-1, holds the j-th pending leaf of board r in the per-board hand-over arrays
+ * (path, depth, leaf ids, k, status, key, prior row, leaf value, evaluator input row): ccz_leaf_info, ccz_leaf_priors, ccz_leaf_keys,
+ * ccz_eval_plan, ccz_gather_priors[_planned] and the evaluator see n_boards independent leaves, and share a row between slots with
+ * one position. Every tree node has an in-flight count F: uint8, in an array of its own indexed like the node records, allocated and
+ * zeroed by the first ccz_set_width(width > 1) (which may sync) and never touched while the width is 1.
+ * A step on board r is two phases, both sequential in j:
+ *   A. Backup. For j = 0 .. W-1, slot s = s(r, j) whose status is not CCZ_LEAF_NONE: F -= 1 on every node of the slot's path (depths
+ *      0 .. d); an EXPAND leaf gets its k children from the slot's prior row and ids as in ccz_expand_backup_compact (node-pool
+ *      accounting and CCZ_ERR_NODE_POOL included); the value value_dev[s] -- or the engine-owned leaf value of slot s when value_dev
+ *      == NULL; DRAW: 0, LOSS: -1 -- is backed up along the path with the float32 incremental mean and alternating sign of
+ *      ccz_expand_backup; the board's simulation count + 1 (ccz_stats counts as always); the slot's status becomes NONE.
+ *   B. Select. t = 0. For j = 0 .. W-1: if the board is over, or its simulation count + t >= its budget (ccz_set_budgets), or the
+ *      batch has ended (below), slot s(r, j) gets CCZ_LEAF_NONE, k = 0, depth 0. Otherwise descend from the root. At node X with
+ *      children i: Ne = N_i + F_i; score_i = +inf if Ne == 0, else
+ *          Qe + (double)(c_puct * P_i) * sqrt((double)(N_X + F_X)) / (double)(1 + Ne),
+ *      Qe = (double)Q_i if F_i == 0, else ((double)N_i * (double)Q_i - (double)F_i) / (double)Ne: each in-flight visit counts as one
+ *      loss for the side that moved into the child. Every operation is rounded on its own (the library is built -ffp-contract=off);
+ *      the first maximum in child order wins. With all F = 0 this is the sequential search's expression, operation for operation.
+ *      CCZ_ERR_NAN and CCZ_ERR_DEPTH arise where they do there: the slot gets NONE and the batch ends. The descent ends at the first
+ *      node L without children. F[L] > 0 is a COLLISION: L is the pending leaf of an earlier slot of this step and the tree is
+ *      unchanged, so every later descent would arrive there too: the slot gets NONE and the batch ends. Otherwise F += 1 on every
+ *      node of the path (visible to the next descent), the path goes to the slot, t += 1, and the slot receives what
+ *      ccz_select_leaves writes for a board: legal moves, game end, key, evaluator input row. A terminal node with F = 0 may be
+ *      selected again in a later step, as in the sequential search. n_leaves_dev[r] = t.
+ * Move boundary: ccz_finish_move, ccz_reset, ccz_reset_tree and ccz_set_position(s) drop pending leaves as always; at a width > 1
+ * one extra launch in front of them takes the dropped slots' paths out of F and sets the slots to NONE. Between moves F is zero.
+ * Budgets (ccz_set_budgets / ccz_draw_budgets) work and are what makes a move exactly n simulations; the evaluation cache (planned
+ * boundary) and the unplanned compact boundary work unchanged; resignation, ccz_principal_variations, ccz_root_children and ccz_root_pi
+ * read the counts as searched. Refused both ways, naming the other call in ccz_last_error and leaving every setting as it was: scout
+ * slots, root exploration, the Gumbel root, the solver, ccz_set_search and routing. While the width is above 1 the sequential step
+ * calls fail instead of silently using slot 0 of each board: ccz_select_leaves, ccz_step, ccz_step_compact, ccz_expand_backup,
+ * ccz_expand_backup_compact, ccz_scout*. ccz_select_wide / ccz_step_wide in turn need a width above 1: at width 1 the sequential
+ * calls ARE the search, and F does not exist.
+ *   ccz_set_width: width 1 .. 64, a divisor of n_boards; call it with no leaf pending (at a move boundary). Width 1: off. A width
+ *     above 1 sets every slot to CCZ_LEAF_NONE (the slots >= A, and whatever the sequential calls left pending on a searched board:
+ *     such a leaf was never counted in F); going back to width 1 drops the pending leaves like a move boundary.
+ *   ccz_select_wide: phase B alone, for a move's first step.
+ *   ccz_step_wide: phases A then B in one launch, reading the engine's prior rows as ccz_step_compact does (value_dev == NULL: the
+ *     engine-owned leaf values of the planned boundary). When every budget is used up it selects nothing: it is also the move's
+ *     last backup. n_leaves_dev: int32 [A], device or pinned host memory.
+ *   ccz_get_wide_stats (syncs): sums over boards; all zero while the width has never been above 1. */
+typedef struct ccz_wide_stats {
+    int64_t steps;        /* board-steps that selected at least one leaf                                                   */
+    int64_t leaves;       /* leaves selected                                                                                */
+    int64_t collisions;   /* batches ended by a collision                                                                   */
+    int64_t inflight_now; /* sum of F over the live pool half: 0 between moves and after a finished search                  */
+} ccz_wide_stats;
+int ccz_set_width(ccz_engine *e, void *stream, int32_t width);
+int ccz_select_wide(ccz_engine *e, void *stream, void *leaf_input_f16_dev, int32_t *n_leaves_dev);
+int ccz_step_wide(ccz_engine *e, void *stream, const float *value_dev, void *leaf_input_f16_dev, int32_t *n_leaves_dev);
+int ccz_get_wide_stats(ccz_engine *e, void *stream, ccz_wide_stats *out);
+
 /* ---- once per move ------------------------------------------------------------------------ */
 /* Replaces MCTS.get_move_probs' tail (mcts.py:162-166), MCTS_AI.get_action's choice
  * (mcts.py:216-224), MCTS.update_with_move (mcts.py:168-178) and the per-move part of
