@@ -1623,7 +1623,7 @@ static_assert(((int64_t)INT32_MAX / kCvC) * kCvC * 2 <= (int64_t)UINT32_MAX, "th
 constexpr int64_t kSmallMaxPixels = 64 * 90; // up to 64 boards (profiles/r03_single_board.json: crossover with the tile kernel)
 
 static int conv3x3_launch(const char *who, void *stream, const void *x_dev, const void *w_dev, const void *bias_f32_dev, const void *residual_dev, void *y_dev,
-                          int64_t n_pixels, int32_t relu, int cin, const int32_t *live_rows_dev = nullptr, int32_t row0 = 0)
+                          int64_t n_pixels, int32_t relu, int cin, const int32_t *live_rows_dev = nullptr, int32_t row0 = 0, bool g16c = false)
 {
     if (!x_dev || !w_dev || !bias_f32_dev || !y_dev || n_pixels < 0 || n_pixels % 90 || n_pixels > (int64_t)INT32_MAX / kCvC) /* 32-bit BYTE offsets and a 32-bit num_records in the kernels: n_pixels * kCvC * 2 < 2^32, see the static_assert below */
         return fail(-1, "%s: bad arguments (n_pixels must be boards * 90, at most 93206 boards per call)", who);
@@ -1642,6 +1642,21 @@ static int conv3x3_launch(const char *who, void *stream, const void *x_dev, cons
         const G16Args a = {(const _Float16 *)x_dev, (const _Float16 *)w_dev, (const float *)bias_f32_dev, (const _Float16 *)residual_dev, (_Float16 *)y_dev,
                            (int)n_pixels, cin, (const int *)live_rows_dev, (int)row0};
         const bool res = residual_dev != nullptr;
+        if (g16c) { // the chunk-major G16C layout (cczero_conv_g16.h g16c_off): the stem, and the quad one-launch form of a tower layer
+            if (cin == 64) {
+                hipLaunchKernelGGL(k_conv3x3_g16c_stem, dim3((unsigned)(groups * 5)), dim3(512), 0, s, (const _Float16 *)x_dev, (const _Float16 *)w_dev,
+                                   (const float *)bias_f32_dev, (_Float16 *)y_dev, (int)n_pixels, (int)fl, cin, (const int *)live_rows_dev, (int)row0);
+                HIP_TRY(hipGetLastError());
+                return 0;
+            }
+            const int need = CCZ_CONV_G16_EDGE_TILES | CCZ_CONV_G16_ONE_LAUNCH | CCZ_CONV_G16_QUAD;
+            if ((relu & need) != need)
+                return fail(-1, "%s: the G16C layout runs the quad one-launch form only (CCZ_CONV_G16_EDGE_TILES | _ONE_LAUNCH | _QUAD)", who);
+            // (a single group too: its edge pair is that group twice, as for an odd live count)
+            g16_launch(CCZ_G16_RES(k_conv3x3_g16c_one_quad, res), (unsigned)(groups * 4 + 2 * ((groups + 1) / 2)), s, a, fl);
+            HIP_TRY(hipGetLastError());
+            return 0;
+        }
         // Without the flag: ONE launch of five two-rank tiles per group. CCZ_CONV_G16_EDGE_TILES (flag bit 7, round 4): the edge ranks (0
         // and 9) of two groups at a time are their own tiles on their own kernel (six live taps instead of nine, cczero_conv_g16e.h) and
         // the middle launch covers ranks 1..8 with four two-rank tiles per group -- two ordinary launches back to back in the caller's
@@ -1712,11 +1727,42 @@ int ccz_conv3x3_c256_f16(void *stream, const void *x_dev, const void *w_dev, con
     return conv3x3_launch("ccz_conv3x3_c256_f16", stream, x_dev, w_dev, bias_f32_dev, residual_dev, y_dev, n_pixels, relu, 256);
 }
 
-int ccz_conv3x3_c256_heads_f16(void *stream, const void *x_dev, const void *w_dev, const void *bias_f32_dev, const void *residual_dev,
-                               const void *head_w32_dev, const void *head_b32_dev, void *pol_dev, void *val_dev, int64_t n_pixels, int32_t flags,
-                               const int32_t *live_rows_dev, int32_t part, int32_t n_parts)
+// ---- the chunk-major "G16C" activation layout (cczero_conv_g16.h g16c_off): additive twins of the CCZ_CONV_G16 calls ----
+int ccz_conv3x3_c256_g16c_f16(void *stream, const void *x_dev, const void *w_dev, const void *bias_f32_dev, const void *residual_dev, void *y_dev,
+                              int64_t n_pixels, int32_t relu)
 {
-    const char *who = "ccz_conv3x3_c256_heads_f16";
+    if (!(relu & CCZ_CONV_G16)) return fail(-1, "ccz_conv3x3_c256_g16c_f16: CCZ_CONV_G16 must be set");
+    return conv3x3_launch("ccz_conv3x3_c256_g16c_f16", stream, x_dev, w_dev, bias_f32_dev, residual_dev, y_dev, n_pixels, relu, 256, nullptr, 0, true);
+}
+
+int ccz_conv3x3_c256_g16c_f16_live(void *stream, const void *x_dev, const void *w_dev, const void *bias_f32_dev, const void *residual_dev, void *y_dev,
+                                   int64_t n_pixels, int32_t relu, const int32_t *live_rows_dev, int32_t part, int32_t n_parts)
+{
+    if (!(relu & CCZ_CONV_G16)) return fail(-1, "ccz_conv3x3_c256_g16c_f16_live: CCZ_CONV_G16 must be set");
+    if (!live_rows_dev || g16_bad_part(part, n_parts)) return fail(-1, "ccz_conv3x3_c256_g16c_f16_live: null live-row count or bad part / n_parts");
+    return conv3x3_launch("ccz_conv3x3_c256_g16c_f16_live", stream, x_dev, w_dev, bias_f32_dev, residual_dev, y_dev, n_pixels, relu, 256, live_rows_dev,
+                          part | (n_parts << 16), true);
+}
+
+int ccz_conv3x3_stem_g16c_f16(void *stream, const void *x64_dev, const void *w_dev, const void *bias_f32_dev, void *y_dev, int64_t n_pixels, int32_t relu)
+{
+    if (!(relu & CCZ_CONV_G16)) return fail(-1, "ccz_conv3x3_stem_g16c_f16: CCZ_CONV_G16 must be set");
+    return conv3x3_launch("ccz_conv3x3_stem_g16c_f16", stream, x64_dev, w_dev, bias_f32_dev, nullptr, y_dev, n_pixels, relu, 64, nullptr, 0, true);
+}
+
+int ccz_conv3x3_stem_g16c_f16_live(void *stream, const void *x64_dev, const void *w_dev, const void *bias_f32_dev, void *y_dev, int64_t n_pixels, int32_t relu,
+                                   const int32_t *live_rows_dev, int32_t part, int32_t n_parts)
+{
+    if (!(relu & CCZ_CONV_G16)) return fail(-1, "ccz_conv3x3_stem_g16c_f16_live: CCZ_CONV_G16 must be set");
+    if (!live_rows_dev || g16_bad_part(part, n_parts)) return fail(-1, "ccz_conv3x3_stem_g16c_f16_live: null live-row count or bad part / n_parts");
+    return conv3x3_launch("ccz_conv3x3_stem_g16c_f16_live", stream, x64_dev, w_dev, bias_f32_dev, nullptr, y_dev, n_pixels, relu, 64, live_rows_dev,
+                          part | (n_parts << 16), true);
+}
+
+static int heads_layer_launch(const char *who, bool g16c, void *stream, const void *x_dev, const void *w_dev, const void *bias_f32_dev, const void *residual_dev,
+                              const void *head_w32_dev, const void *head_b32_dev, void *pol_dev, void *val_dev, int64_t n_pixels, int32_t flags,
+                              const int32_t *live_rows_dev, int32_t part, int32_t n_parts)
+{
     if (!x_dev || !w_dev || !bias_f32_dev || !residual_dev || !head_w32_dev || !head_b32_dev || !pol_dev || !val_dev || n_pixels < 0 || n_pixels % 1440 ||
         n_pixels > (int64_t)INT32_MAX / kCvC)
         return fail(-1, "%s: bad arguments (n_pixels must be a multiple of 16 boards * 90, at most 93200 boards per call)", who);
@@ -1737,12 +1783,37 @@ int ccz_conv3x3_c256_heads_f16(void *stream, const void *x_dev, const void *w_de
     ha.val = (_Float16 *)val_dev;
     ha.nb = (int)(n_pixels / 90);
     hipStream_t s = (hipStream_t)stream;
+    if (g16c) { // middle + edge-pair launches whatever the group count (a single group: its edge pair is that group twice)
+        if (!(flags & CCZ_CONV_G16_EDGE_TILES)) return fail(-1, "%s: the G16C layout needs CCZ_CONV_G16_EDGE_TILES", who);
+        const int groups = (int)(n_pixels / 1440);
+        g16_launch(k_conv3x3_g16c_heads, (unsigned)(groups * 4), s, a, fl | 4, ha);
+        HIP_TRY(hipGetLastError());
+        g16_launch(k_conv3x3_g16c_edge_heads, 2u * (unsigned)((groups + 1) / 2), s, a, fl, ha);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    }
     g16_launch(k_conv3x3_g16_heads, shape.mid, s, a, shape.edge ? fl | 4 : fl, ha);
     HIP_TRY(hipGetLastError());
     if (!shape.edge) return 0;
     g16_launch(k_conv3x3_g16_edge_heads, shape.edge, s, a, fl, ha);
     HIP_TRY(hipGetLastError());
     return 0;
+}
+
+int ccz_conv3x3_c256_heads_f16(void *stream, const void *x_dev, const void *w_dev, const void *bias_f32_dev, const void *residual_dev,
+                               const void *head_w32_dev, const void *head_b32_dev, void *pol_dev, void *val_dev, int64_t n_pixels, int32_t flags,
+                               const int32_t *live_rows_dev, int32_t part, int32_t n_parts)
+{
+    return heads_layer_launch("ccz_conv3x3_c256_heads_f16", false, stream, x_dev, w_dev, bias_f32_dev, residual_dev, head_w32_dev, head_b32_dev, pol_dev, val_dev,
+                              n_pixels, flags, live_rows_dev, part, n_parts);
+}
+
+int ccz_conv3x3_c256_heads_g16c_f16(void *stream, const void *x_dev, const void *w_dev, const void *bias_f32_dev, const void *residual_dev,
+                                    const void *head_w32_dev, const void *head_b32_dev, void *pol_dev, void *val_dev, int64_t n_pixels, int32_t flags,
+                                    const int32_t *live_rows_dev, int32_t part, int32_t n_parts)
+{
+    return heads_layer_launch("ccz_conv3x3_c256_heads_g16c_f16", true, stream, x_dev, w_dev, bias_f32_dev, residual_dev, head_w32_dev, head_b32_dev, pol_dev, val_dev,
+                              n_pixels, flags, live_rows_dev, part, n_parts);
 }
 
 int ccz_conv3x3_stem_f16(void *stream, const void *x64_dev, const void *w_dev, const void *bias_f32_dev, void *y_dev, int64_t n_pixels, int32_t relu)

@@ -92,6 +92,16 @@ static_assert(kG5QLds == 159744 && kG5QLds <= kG5Lds, "quad tile: ring + two sla
 static_assert(kG5QRows * kG5QERow == 156672 && kG5QRows * kG5QERow <= kG5QLds,
               "quad tile: the epilogue image covers the operand buffers AND most of the dump area (free once every DMA has landed)");
 
+// Layout "G16C" (the CM forms): inside each 16-board group the rows are chunk-major -- [chunk 0..7][row 0..1439][32 channels], row
+// stride 64 B, chunk stride 92,160 B, the group stride (737,280 B) as in G16 -- so that a chunk's slab is one contiguous run of whole
+// 128-byte lines. Byte offset of chunk 0 of G16 row p:
+constexpr int kG16CChunk = 1440 * 64;
+__device__ __forceinline__ unsigned g16c_off(long p)
+{
+    const long g = p / 1440;
+    return (unsigned)(g * (1440 * 512) + (p - g * 1440) * 64);
+}
+
 struct G5Ctx {
     unsigned char *lds;
     const _Float16 *X, *W;   // uniform bases of the two buffer descriptors: every DMA is descriptor + 32-bit byte offset (one VGPR) + scalar offset
@@ -186,7 +196,7 @@ __device__ __forceinline__ void g5_zero_ranks(const G5Ctx &c, int buf)
 
 // One half-step = tap T of a 32-channel chunk; J = its index inside the unrolled pair of chunks (parity of the A register
 // set = J & 1, slab buffer = J / 9). Q: the quad tile's staging (8 KB ring slots, slabs of six ranks, g5q_dma) around the SAME cells.
-template <int J, bool Q = false>
+template <int J, bool Q = false, bool CM = false>
 __device__ __forceinline__ void g5_step(const G5Ctx &c, cv_f32x4 (&acc)[4][9], int chunk, int &ring_rd, int &ring_wr,
                                          cv_half8 (&a0)[4], cv_half8 (&a1)[4], cv_half8 (&b)[9])
 {
@@ -211,7 +221,7 @@ __device__ __forceinline__ void g5_step(const G5Ctx &c, cv_f32x4 (&acc)[4][9], i
     G5_CELLS(T, 0, 1)
     if constexpr (Q && g5q_nslab(T) > 0) { // the next chunk's slab: 7 pieces per thread, passes 0, 1 | 2 | .. | 6 in taps 0 | 1 | .. | 5
         constexpr int pass = T == 0 ? 0 : T + 1;
-        const unsigned so = (unsigned)((chunk + 1) * 64);
+        const unsigned so = (unsigned)((chunk + 1) * (CM ? kG16CChunk : 64));
         const unsigned live = chunk < c.cmask ? (pass < 6 ? c.xbytes : c.xbytes_part) : 0u;
         cv_blds16(c.X, live, c.xoff[0], so + pass * c.xstep,
                   lds + (pass < 6 ? kAOff + (1 - BUF) * kSlab + pass * 8192 + c.wave_dst : c.wave_dst_part + (1 - BUF) * c.wave_step_part));
@@ -221,7 +231,7 @@ __device__ __forceinline__ void g5_step(const G5Ctx &c, cv_f32x4 (&acc)[4][9], i
     if constexpr (!Q && g5_dma(T) > 2) { // the next chunk's slab: 5 pieces per thread, in taps 1..5
         constexpr int pass = T - 1;
         const unsigned live = pass < 4 ? c.xbytes : c.xbytes_part;
-        cv_blds16(c.X, chunk < c.cmask ? live : 0u, c.xoff[pass], (unsigned)((chunk + 1) * 64),
+        cv_blds16(c.X, chunk < c.cmask ? live : 0u, c.xoff[pass], (unsigned)((chunk + 1) * (CM ? kG16CChunk : 64)),
                   lds + (pass < 4 ? kG5AOff + (1 - BUF) * kG5SlabBytes + pass * 8192 + c.wave_dst : c.wave_dst_part + (1 - BUF) * c.wave_step_part));
         __builtin_amdgcn_sched_barrier(0);
     }
@@ -422,6 +432,32 @@ __device__ __forceinline__ void g5_rows_out(unsigned char *lds, int irow, int pi
     }
 }
 
+// Epilogue, part 2, of the G16C forms: one wave instruction moves 16 rows x 64 B of ONE chunk -- 1 KB contiguous in memory, whole lines.
+// A wave owns one chunk of the image and 18 cells of it, one per iteration (cell = 16 image rows, 1 KB of tensor). Within an
+// instruction a lane takes 16-byte piece lane & 3 of the row g16c_lane_row(lane): ds_read_b128 serves the lanes in four fixed groups
+// of four quads ({0,3,5,6}, {1,2,4,7}, {8,11,13,14}, {9,10,12,15}), an image row is 16 (mod 256) bytes after the one before (EROW =
+// 272, 528), so the four rows of a group must lie four rows apart (0, 4, 8, 12 + k) for their 64-byte pieces to cover the 64 banks
+// once; and the four quads 4 q .. 4 q + 3 are given two PAIRS of neighbouring rows, so that each quarter-wave still covers two whole
+// 128-byte lines of the tensor. The image and the accumulator stores into it are untouched.
+__device__ __forceinline__ int g16c_lane_row(int lane) { return (int)((0xFEAB6732DC894510ull >> (4 * (lane >> 2))) & 15); }
+
+// `img`: this lane's byte offset in the image at iteration 0 (iteration it: + it * 16 * EROW); `yoff`: its byte offset in the tensor
+// (iteration it: + it * 1024). `rv`: the residual pieces, loaded by the caller from the same offsets.
+template <int EROW, bool RES, bool HEADS>
+__device__ __forceinline__ void g5c_rows_out(unsigned char *lds, int img, size_t yoff, _Float16 *Y, int relu, const cv_half8 (&rv)[18])
+{
+    const cv_half8 zero = (cv_half8)(_Float16)0;
+    unsigned char *eb = lds + img;
+#pragma unroll
+    for (int it = 0; it < 18; ++it) {
+        cv_half8 v = *(const cv_half8 *)(eb + it * 16 * EROW);
+        if (RES) v = v + rv[it];
+        if (relu) v = __builtin_elementwise_max(v, zero);
+        if constexpr (HEADS) *(cv_half8 *)(eb + it * 16 * EROW) = v;
+        else *(cv_half8 *)((unsigned char *)Y + yoff + it * 1024) = v;
+    }
+}
+
 // The accumulators start at the bias: the nine tiles of one accumulator row, from the four bias values at `bias4`. One row per call, the
 // loop over the four rows is the caller's: with it in here (acc[4][9] by reference) k_conv3x3_g16_quad<residual> and
 // k_conv3x3_g16_one_quad<residual> spill 16 VGPRs and the loops of the other kernels change (CHANGELOG).
@@ -436,7 +472,8 @@ __device__ __forceinline__ void g5_acc_row_from_bias(cv_f32x4 (&row)[9], const f
 
 // One two-rank tile. `lds`: the workgroup's kG5Lds bytes (declared by the kernel, so that one kernel can hold two tile classes);
 // `blk`: this workgroup's tile slot, `grid`: the launch's tile count (without a live-row count; with one, the tiles of the live groups).
-template <bool RES, bool HEADS, bool ONE = false>
+// CM: the layer's tensors are in the chunk-major G16C layout -- X and R where they are read (not the stem's packed planes: ONE), Y.
+template <bool RES, bool HEADS, bool ONE = false, bool CM = false>
 __device__ __forceinline__ void g5_tile(unsigned char *lds, int blk, int grid, const _Float16 *__restrict__ X, const _Float16 *__restrict__ W,
                                         const float *__restrict__ bias, const _Float16 *R,
                                         _Float16 *Y, int M, int relu, int cin, const int *live_rows, int row0, const G5Heads &ha)
@@ -491,7 +528,8 @@ __device__ __forceinline__ void g5_tile(unsigned char *lds, int blk, int grid, c
             const int schunk = pos ^ ((0 - (sr >> 2)) & 3);
             long p = p0 - 144 + sr;
             p = p < 0 ? 0 : (p > (long)M - 1 ? (long)M - 1 : p);
-            c.xoff[it] = (unsigned)(p * cin + schunk * 8) * 2u;
+            if constexpr (CM && !ONE) c.xoff[it] = g16c_off(p) + (unsigned)(schunk * 16);
+            else c.xoff[it] = (unsigned)(p * cin + schunk * 8) * 2u;
         }
         c.woff = (unsigned)(tid * 16); // packed weights (k_pack_conv_weights_g16): a half-tile is the LDS image itself, read linearly
     }
@@ -521,7 +559,7 @@ __device__ __forceinline__ void g5_tile(unsigned char *lds, int blk, int grid, c
     for (int i = 0; i < 4; ++i) a0[i] = *(const cv_half8 *)(lds + c.a_off + i * 1024);
 #pragma unroll
     for (int n = 0; n < 9; ++n) b[n] = *(const cv_half8 *)(lds + c.vb[0] + (9 + n - 9) * 1024); // the rank above this wave's: dy = -1
-#define G5_S(j) g5_step<j>(c, acc, chunk + (j) / 9, ring_rd, ring_wr, a0, a1, b)
+#define G5_S(j) g5_step<j, false, CM && !ONE>(c, acc, chunk + (j) / 9, ring_rd, ring_wr, a0, a1, b)
     if constexpr (ONE) {
         const int chunk = 0; // (one chunk: every next-chunk prefetch is issued against an empty descriptor and fetches nothing)
         G5_S(0); G5_S(1); G5_S(2); G5_S(3); G5_S(4); G5_S(5); G5_S(6); G5_S(7); G5_S(8);
@@ -544,12 +582,23 @@ __device__ __forceinline__ void g5_tile(unsigned char *lds, int blk, int grid, c
     const long pbase = p0 + w * 36 + prow;
     cv_half8 rv[18];
     g5_image_store<kG5ERow>(lds, acc, wm, wn, re, q4e);
-    if (RES) {
+    if constexpr (CM) { // wave w owns chunk w of the 18 cells (g5c_rows_out)
+        const int erow = g16c_lane_row(lane_e), ep = lane_e & 3;
+        const size_t yo = (size_t)g16c_off(p0 + erow) + (size_t)(w * kG16CChunk + ep * 16);
+        if (RES) {
 #pragma unroll
-        for (int it = 0; it < 18; ++it) rv[it] = *(const cv_half8 *)(R + (pbase + it * 2) * kCvC + piece * 8);
+            for (int it = 0; it < 18; ++it) rv[it] = *(const cv_half8 *)((const unsigned char *)R + yo + it * 1024);
+        }
+        g5_barrier<true>();
+        g5c_rows_out<kG5ERow, RES, HEADS>(lds, erow * kG5ERow + w * 64 + ep * 16, yo, Y, relu, rv);
+    } else {
+        if (RES) {
+#pragma unroll
+            for (int it = 0; it < 18; ++it) rv[it] = *(const cv_half8 *)(R + (pbase + it * 2) * kCvC + piece * 8);
+        }
+        g5_barrier<true>();
+        g5_rows_out<kG5ERow, 2, RES, HEADS>(lds, w * 36 + prow, piece, pbase, piece * 8, Y, relu, rv);
     }
-    g5_barrier<true>();
-    g5_rows_out<kG5ERow, 2, RES, HEADS>(lds, w * 36 + prow, piece, pbase, piece * 8, Y, relu, rv);
     if constexpr (HEADS) {
         g5_barrier<true>(); // every finished row is in the image
         // image rows 0..143 = the tile's first rank, 144..287 = its second: tensor row p0 + i = (group * 90 + 9 * rank + cell) * 16 + board
@@ -573,7 +622,7 @@ __device__ __forceinline__ void g5_tile(unsigned char *lds, int blk, int grid, c
 //     thread's pass-0 offset + it * 128 rows in the SCALAR offset (one VGPR instead of five). Pass 6 has 384 pieces: waves 6-7 issue
 //     theirs against the zero-record descriptor into their KB of the dump area.
 //   * epilogue image: 576 rows x 272 B; wave w owns rows 72 w .. 72 w + 71 and moves 256-byte row segments (channels 128 h ..).
-template <bool RES>
+template <bool RES, bool CM = false>
 __device__ __forceinline__ void g5q_tile(unsigned char *lds, int blk, int grid, const _Float16 *__restrict__ X, const _Float16 *__restrict__ W,
                                          const float *__restrict__ bias, const _Float16 *R, _Float16 *Y, int M, int relu, int cin,
                                          const int *live_rows, int row0)
@@ -602,14 +651,15 @@ __device__ __forceinline__ void g5q_tile(unsigned char *lds, int blk, int grid, 
     c.wave_dst_part = w < 6 ? kG5QAOff + 6 * 8192 + w * 1024 : kG5QDump + w * 1024;
     c.wave_step_part = w < 6 ? kG5QSlabBytes : 0;
     c.xbytes_part = w < 6 ? c.xbytes : 0u;
-    c.xstep = 128u * (unsigned)cin * 2u;
+    c.xstep = CM ? 128u * 64u : 128u * (unsigned)cin * 2u;
     c.whalf = (unsigned)h * 8192u;
     {
         // slab row sr (0..863) = tensor row p0 - 144 + sr: rank (1 or 5) - 1 + sr / 144 of the group; piece it * 512 + tid is row
         // it * 128 + (tid >> 2), and the swizzle f(sr) = (-(sr >> 2)) & 3 does not depend on `it`
         const int sr = tid >> 2, pos = tid & 3;
         const int schunk = pos ^ ((0 - (sr >> 2)) & 3);
-        c.xoff[0] = (unsigned)((p0 - 144 + sr) * cin + schunk * 8) * 2u;
+        if constexpr (CM) c.xoff[0] = g16c_off(p0 - 144 + sr) + (unsigned)(schunk * 16); // a wave's 16 rows x 64 B: 1 KB of whole lines
+        else c.xoff[0] = (unsigned)((p0 - 144 + sr) * cin + schunk * 8) * 2u;
         c.woff = (unsigned)(tid * 16);
     }
     // ---- prologue: slab of chunk 0, this half's weight blocks of taps 0..2
@@ -634,7 +684,7 @@ __device__ __forceinline__ void g5q_tile(unsigned char *lds, int blk, int grid, 
 #pragma unroll
     for (int n = 0; n < 9; ++n) b[n] = *(const cv_half8 *)(lds + c.vb[0] + n * 1024); // the rank above this wave's: dy = -1
     for (int chunk = 0; chunk <= c.cmask; chunk += 2) {
-#define G5Q_S(j) g5_step<j, true>(c, acc, chunk + (j) / 9, ring_rd, ring_wr, a0, a1, b)
+#define G5Q_S(j) g5_step<j, true, CM>(c, acc, chunk + (j) / 9, ring_rd, ring_wr, a0, a1, b)
         G5Q_S(0); G5Q_S(1); G5Q_S(2); G5Q_S(3); G5Q_S(4); G5Q_S(5); G5Q_S(6); G5Q_S(7); G5Q_S(8);
         G5Q_S(9); G5Q_S(10); G5Q_S(11); G5Q_S(12); G5Q_S(13); G5Q_S(14); G5Q_S(15); G5Q_S(16); G5Q_S(17);
 #undef G5Q_S
@@ -650,12 +700,23 @@ __device__ __forceinline__ void g5q_tile(unsigned char *lds, int blk, int grid, 
     const int gcol = h * 128 + piece * 8;
     cv_half8 rv[18];
     g5_image_store<kG5QERow>(lds, acc, wm, wn, re, q4e);
-    if (RES) {
+    if constexpr (CM) { // wave w owns chunk 4 h + (w & 3), cells 18 (w >> 2) .. + 17 of the tile's 36 (g5c_rows_out)
+        const int erow = g16c_lane_row(lane_e), ep = lane_e & 3, ch = w & 3, irow = (w >> 2) * 288 + erow;
+        const size_t yo = (size_t)g16c_off(p0 + irow) + (size_t)((h * 4 + ch) * kG16CChunk + ep * 16);
+        if (RES) {
 #pragma unroll
-        for (int it = 0; it < 18; ++it) rv[it] = *(const cv_half8 *)(R + (pbase + it * 4) * kCvC + gcol);
+            for (int it = 0; it < 18; ++it) rv[it] = *(const cv_half8 *)((const unsigned char *)R + yo + it * 1024);
+        }
+        g5_barrier<true>();
+        g5c_rows_out<kG5QERow, RES, false>(lds, irow * kG5QERow + ch * 64 + ep * 16, yo, Y, relu, rv);
+    } else {
+        if (RES) {
+#pragma unroll
+            for (int it = 0; it < 18; ++it) rv[it] = *(const cv_half8 *)(R + (pbase + it * 4) * kCvC + gcol);
+        }
+        g5_barrier<true>();
+        g5_rows_out<kG5QERow, 4, RES, false>(lds, w * 72 + prow, piece, pbase, gcol, Y, relu, rv);
     }
-    g5_barrier<true>();
-    g5_rows_out<kG5QERow, 4, RES, false>(lds, w * 72 + prow, piece, pbase, gcol, Y, relu, rv);
 }
 
 template <bool RES>
@@ -694,6 +755,24 @@ __global__ __launch_bounds__(512) void k_conv3x3_g16_heads(const _Float16 *__res
     __shared__ __attribute__((aligned(16))) unsigned char lds[kG5Lds];
     if (live_rows) ha.nb = *live_rows; // planned boundary: the pointers are the whole batch's, M only the capacity of this part
     g5_tile<true, true>(lds, blockIdx.x, gridDim.x, X, W, bias, R, Y, M, relu, cin, live_rows, row0, ha);
+}
+
+// The G16C forms of the stem (writes chunk-major rows; its input stays the packed planes) and of the heads layer (reads them)
+__global__ __launch_bounds__(512) void k_conv3x3_g16c_stem(const _Float16 *__restrict__ X, const _Float16 *__restrict__ W,
+                                                             const float *__restrict__ bias, _Float16 *Y, int M, int relu, int cin,
+                                                             const int *live_rows, int row0)
+{
+    __shared__ __attribute__((aligned(16))) unsigned char lds[kG5Lds];
+    g5_tile<false, false, true, true>(lds, blockIdx.x, gridDim.x, X, W, bias, nullptr, Y, M, relu, cin, live_rows, row0, G5Heads{});
+}
+
+__global__ __launch_bounds__(512) void k_conv3x3_g16c_heads(const _Float16 *__restrict__ X, const _Float16 *__restrict__ W,
+                                                              const float *__restrict__ bias, const _Float16 *R, _Float16 *Y, int M,
+                                                              int relu, int cin, const int *live_rows, int row0, G5Heads ha)
+{
+    __shared__ __attribute__((aligned(16))) unsigned char lds[kG5Lds];
+    if (live_rows) ha.nb = *live_rows;
+    g5_tile<true, true, false, true>(lds, blockIdx.x, gridDim.x, X, W, bias, R, Y, M, relu, cin, live_rows, row0, ha);
 }
 
 // Weights for k_conv3x3_g16: [co][tap][ci] (the memory of a channels-last [co, ci, 3, 3] tensor) -> [ci / 32][tap][co][32], each

@@ -38,7 +38,7 @@ static_assert(g5e_dma(0) == 4 && g5e_dma(1) == 4 && g5e_dma(2) == 3 && g5e_dma(3
 // One half-step of an edge tile: live tap H = J % 6 of a 32-channel chunk (tap index H + toff in the packed weights), J = its
 // index inside the unrolled pair of chunks (A register set = J & 1, slab buffer = J / 6). vb[BUF] = this lane's fragment base of
 // the wave row's sub-rank 0 in slab buffer BUF; sub-rank d = H / 3 is at + 9 * 1024 d.
-template <int J>
+template <int J, bool CM = false>
 __device__ __forceinline__ void g5e_step(const G5Ctx &c, cv_f32x4 (&acc)[4][9], int chunk, int &ring_rd, int &ring_wr,
                                           cv_half8 (&a0)[4], cv_half8 (&a1)[4], cv_half8 (&b)[9], int toff)
 {
@@ -56,7 +56,7 @@ __device__ __forceinline__ void g5e_step(const G5Ctx &c, cv_f32x4 (&acc)[4][9], 
     G5_CELLS(H, 0, 1)
     if constexpr (g5e_dma(H) > 2) { // the next chunk's slab: passes 0,1 | 2,3 | 4 in half-steps 0 | 1 | 2
         constexpr int p0 = H * 2;
-        const unsigned so = (unsigned)((chunk + 1) * 64);
+        const unsigned so = (unsigned)((chunk + 1) * (CM ? kG16CChunk : 64));
         const unsigned live = chunk < c.cmask ? (p0 < 4 ? c.xbytes : c.xbytes_part) : 0u;
         cv_blds16(c.X, live, c.xoff[p0], so,
                   lds + (p0 < 4 ? kG5AOff + (1 - BUF) * kG5SlabBytes + p0 * 8192 + c.wave_dst : c.wave_dst_part + (1 - BUF) * c.wave_step_part));
@@ -95,7 +95,7 @@ __device__ __forceinline__ void g5e_step(const G5Ctx &c, cv_f32x4 (&acc)[4][9], 
 // X, Y, R: rows in the group-of-16 layout, M rows (a multiple of 1440); W packed (k_pack_conv_weights_g16). grid = 2 * ceil(groups
 // / 2): workgroup e = pair e / 2 of groups, side e & 1 (0: rank 0, 1: rank 9). live_rows / row0: as k_conv3x3_g16 (planned boundary).
 // `lds`, `blk`: the workgroup's LDS and edge-tile slot (as g5_tile).
-template <bool RES, bool HEADS>
+template <bool RES, bool HEADS, bool CM = false>
 __device__ __forceinline__ void g5e_tile(unsigned char *lds, int blk, const _Float16 *__restrict__ X, const _Float16 *__restrict__ W,
                                          const float *__restrict__ bias, const _Float16 *R, _Float16 *Y, int M,
                                          int relu, int cin, const int *live_rows, int row0, const G5Heads &ha)
@@ -137,7 +137,8 @@ __device__ __forceinline__ void g5e_tile(unsigned char *lds, int blk, const _Flo
             const int sr = piece >> 2, pos = piece & 3;
             const int schunk = pos ^ ((0 - (sr >> 2)) & 3);
             const long p = sr < 288 ? srcA + sr : srcB + (sr - 288);
-            c.xoff[it] = (unsigned)(p * cin + schunk * 8) * 2u;
+            if constexpr (CM) c.xoff[it] = g16c_off(p) + (unsigned)(schunk * 16);
+            else c.xoff[it] = (unsigned)(p * cin + schunk * 8) * 2u;
         }
         c.woff = (unsigned)(tid * 16);
     }
@@ -167,7 +168,7 @@ __device__ __forceinline__ void g5e_tile(unsigned char *lds, int blk, const _Flo
 #pragma unroll
     for (int n = 0; n < 9; ++n) b[n] = *(const cv_half8 *)(lds + c.vb[0] + n * 1024); // sub-rank 0
     for (int chunk = 0; chunk <= c.cmask; chunk += 2) {
-#define G5E_S(j) g5e_step<j>(c, acc, chunk + (j) / 6, ring_rd, ring_wr, a0, a1, b, toff)
+#define G5E_S(j) g5e_step<j, CM>(c, acc, chunk + (j) / 6, ring_rd, ring_wr, a0, a1, b, toff)
         G5E_S(0); G5E_S(1); G5E_S(2); G5E_S(3); G5E_S(4); G5E_S(5);
         G5E_S(6); G5E_S(7); G5E_S(8); G5E_S(9); G5E_S(10); G5E_S(11);
 #undef G5E_S
@@ -183,21 +184,44 @@ __device__ __forceinline__ void g5e_tile(unsigned char *lds, int blk, const _Flo
     const long pbase = (w < 4 ? outA : outB) + (w & 3) * 36 + prow;
     const bool store = !(dup && w >= 4);
     cv_half8 rv[18];
-    if (RES) {
+    if constexpr (CM) { // wave w owns chunk w of the 18 cells (g5c_rows_out): cells 0..8 group A's edge rank, 9..17 group B's
+        const int erow = g16c_lane_row(lane), ep = lane & 3;
+        const size_t yoA = (size_t)g16c_off(outA + erow) + (size_t)(w * kG16CChunk + ep * 16);
+        const size_t yoB = (size_t)g16c_off(outB + erow) + (size_t)(w * kG16CChunk + ep * 16);
+        if (RES) {
 #pragma unroll
-        for (int it = 0; it < 18; ++it) rv[it] = *(const cv_half8 *)(R + (pbase + it * 2) * kCvC + piece * 8);
-    }
-    g5_barrier<true>();
-    if (store) {
+            for (int it = 0; it < 18; ++it) rv[it] = *(const cv_half8 *)((const unsigned char *)R + (it < 9 ? yoA + it * 1024 : yoB + (it - 9) * 1024));
+        }
+        g5_barrier<true>();
         const cv_half8 zero = (cv_half8)(_Float16)0;
-        unsigned char *eb = lds + (w * 36 + prow) * kG5ERow + piece * 16;
+        unsigned char *eb = lds + erow * kG5ERow + w * 64 + ep * 16;
 #pragma unroll
         for (int it = 0; it < 18; ++it) {
-            cv_half8 v = *(const cv_half8 *)(eb + it * 2 * kG5ERow);
-            if (RES) v = v + rv[it];
-            if (relu) v = __builtin_elementwise_max(v, zero);
-            if constexpr (HEADS) *(cv_half8 *)(eb + it * 2 * kG5ERow) = v;   // the finished row stays in the image; Y is not written
-            else *(cv_half8 *)(Y + (pbase + it * 2) * kCvC + piece * 8) = v;
+            if (it < 9 || !dup) {                                            // (wave-uniform: with `dup` group B is group A again)
+                cv_half8 v = *(const cv_half8 *)(eb + it * 16 * kG5ERow);
+                if (RES) v = v + rv[it];
+                if (relu) v = __builtin_elementwise_max(v, zero);
+                if constexpr (HEADS) *(cv_half8 *)(eb + it * 16 * kG5ERow) = v;
+                else *(cv_half8 *)((unsigned char *)Y + (it < 9 ? yoA + it * 1024 : yoB + (it - 9) * 1024)) = v;
+            }
+        }
+    } else {
+        if (RES) {
+#pragma unroll
+            for (int it = 0; it < 18; ++it) rv[it] = *(const cv_half8 *)(R + (pbase + it * 2) * kCvC + piece * 8);
+        }
+        g5_barrier<true>();
+        if (store) {
+            const cv_half8 zero = (cv_half8)(_Float16)0;
+            unsigned char *eb = lds + (w * 36 + prow) * kG5ERow + piece * 16;
+#pragma unroll
+            for (int it = 0; it < 18; ++it) {
+                cv_half8 v = *(const cv_half8 *)(eb + it * 2 * kG5ERow);
+                if (RES) v = v + rv[it];
+                if (relu) v = __builtin_elementwise_max(v, zero);
+                if constexpr (HEADS) *(cv_half8 *)(eb + it * 2 * kG5ERow) = v;   // the finished row stays in the image; Y is not written
+                else *(cv_half8 *)(Y + (pbase + it * 2) * kCvC + piece * 8) = v;
+            }
         }
     }
     if constexpr (HEADS) { // the heads on the finished rows (cczero_conv_g16.h g5_heads_phase): image rows 0..143 group A's edge rank, 144..287 group B's
@@ -234,7 +258,7 @@ __global__ __launch_bounds__(512) void k_conv3x3_g16_edge_heads(const _Float16 *
 // being ~24 % shorter they fill the launch's last round. Each tile is the same code as in its own kernel (the branch is taken once,
 // before either body starts): the same values. grid = 4 groups + 2 ceil(groups / 2) of the capacity; slots past the live ones leave.
 // Not for the last layer: with the heads in the epilogue both bodies in one kernel spill (one VGPR); it stays two launches.
-template <bool RES, bool QUAD>
+template <bool RES, bool QUAD, bool CM = false>
 __device__ __forceinline__ void g5_one_launch(unsigned char *lds, const _Float16 *__restrict__ X, const _Float16 *__restrict__ W,
                                               const float *__restrict__ bias, const _Float16 *R, _Float16 *Y, int M,
                                               int relu, int cin, const int *live_rows, int row0)
@@ -246,9 +270,9 @@ __device__ __forceinline__ void g5_one_launch(unsigned char *lds, const _Float16
     }
     const int mid = groups * 4, blk = blockIdx.x;
     if (blk < mid) {
-        if constexpr (QUAD) g5q_tile<RES>(lds, blk, mid, X, W, bias, R, Y, M, relu, cin, live_rows, row0);
+        if constexpr (QUAD) g5q_tile<RES, CM>(lds, blk, mid, X, W, bias, R, Y, M, relu, cin, live_rows, row0);
         else g5_tile<RES, false>(lds, blk, mid, X, W, bias, R, Y, M, relu | 4, cin, live_rows, row0, G5Heads{});
-    } else g5e_tile<RES, false>(lds, blk - mid, X, W, bias, R, Y, M, relu, cin, live_rows, row0, G5Heads{});
+    } else g5e_tile<RES, false, CM>(lds, blk - mid, X, W, bias, R, Y, M, relu, cin, live_rows, row0, G5Heads{});
 }
 
 template <bool RES>
@@ -268,6 +292,25 @@ __global__ __launch_bounds__(512) void k_conv3x3_g16_one_quad(const _Float16 *__
 {
     __shared__ __attribute__((aligned(16))) unsigned char lds[kG5Lds];
     g5_one_launch<RES, true>(lds, X, W, bias, R, Y, M, relu, cin, live_rows, row0);
+}
+
+// The G16C forms (cczero_conv_g16.h g16c_off): every activation tensor of the layer chunk-major
+template <bool RES>
+__global__ __launch_bounds__(512) void k_conv3x3_g16c_one_quad(const _Float16 *__restrict__ X, const _Float16 *__restrict__ W,
+                                                                 const float *__restrict__ bias, const _Float16 *R, _Float16 *Y, int M,
+                                                                 int relu, int cin, const int *live_rows, int row0)
+{
+    __shared__ __attribute__((aligned(16))) unsigned char lds[kG5Lds];
+    g5_one_launch<RES, true, true>(lds, X, W, bias, R, Y, M, relu, cin, live_rows, row0);
+}
+
+__global__ __launch_bounds__(512) void k_conv3x3_g16c_edge_heads(const _Float16 *__restrict__ X, const _Float16 *__restrict__ W,
+                                                                   const float *__restrict__ bias, const _Float16 *R, _Float16 *Y,
+                                                                   int M, int relu, int cin, const int *live_rows, int row0, G5Heads ha)
+{
+    __shared__ __attribute__((aligned(16))) unsigned char lds[kG5Lds];
+    if (live_rows) ha.nb = *live_rows;
+    g5e_tile<true, true, true>(lds, blockIdx.x, X, W, bias, R, Y, M, relu, cin, live_rows, row0, ha);
 }
 
 #undef G5_CELLS

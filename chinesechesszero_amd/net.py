@@ -92,6 +92,50 @@ def pack_conv_weights_g16(w):
     return w5.permute(2, 1, 0, 3, 4).contiguous().view(cin // 32, 9, co, 32)
 
 
+def _memory_rows(t, width):
+    """The MEMORY of ``t`` -- a [N, C, H, W] channels-last tensor or any contiguous one -- as a [-1, width] view."""
+    if t.dim() == 4 and not t.is_contiguous():
+        t = t.permute(0, 2, 3, 1)
+    if not t.is_contiguous():
+        raise ValueError("expected a channels-last or a contiguous tensor")
+    return t.reshape(-1, width)
+
+
+def g16_to_g16c(t):
+    """Group-of-16 rows ([groups * 1440, 256] in memory: row (g * 90 + pos) * 16 + j = board 16 g + j) -> the chunk-major G16C layout
+    of the same groups ([group][chunk 0..7][row 0..1439][32 channels], csrc/cczero_conv_g16.h g16c_off); the shape of ``t`` is kept."""
+    rows = _memory_rows(t, 256)
+    out = rows.view(-1, 1440, 8, 32).permute(0, 2, 1, 3).contiguous()
+    return out.view(t.shape[0], 10, 9, 256).permute(0, 3, 1, 2) if t.dim() == 4 else out.view(t.shape)
+
+
+def g16c_to_g16(t):
+    """The inverse of :func:`g16_to_g16c`."""
+    rows = _memory_rows(t, 32)
+    out = rows.view(-1, 8, 1440, 32).permute(0, 2, 1, 3).contiguous()
+    return out.view(t.shape[0], 10, 9, 256).permute(0, 3, 1, 2) if t.dim() == 4 else out.view(t.shape)
+
+
+def g16c_to_boards(t, boards=None):
+    """Activations in the chunk-major G16C layout (the memory of ``t``: whole groups of 16 boards x 90 positions x 256 channels)
+    -> a [boards, 256, 10, 9] channels-last tensor in BOARD order (tests and probes). ``boards``: drop the padding boards past it."""
+    m = _memory_rows(t, 32)
+    G = m.shape[0] // (8 * 1440)
+    out = m.view(G, 8, 90, 16, 32).permute(0, 3, 2, 1, 4).reshape(G * 16, 10, 9, 256)
+    return out[:boards].permute(0, 3, 1, 2)
+
+
+def boards_to_g16c(x):
+    """The inverse of :func:`g16c_to_boards`: [B, 256, 10, 9] in board order -> ceil(B / 16) groups in the G16C layout (the padding
+    boards zero), as a [16 * groups, 256, 10, 9] channels-last-shaped tensor whose MEMORY is the layout."""
+    B = x.shape[0]
+    G = -(-B // 16)
+    rows = torch.zeros((G * 16, 90, 256), dtype=x.dtype, device=x.device)
+    rows[:B] = x.permute(0, 2, 3, 1).reshape(B, 90, 256)
+    out = rows.view(G, 16, 90, 8, 32).permute(0, 3, 2, 1, 4).contiguous()
+    return out.view(G * 16, 10, 9, 256).permute(0, 3, 1, 2)
+
+
 class EvalOptions:
     """The evaluator's A/B switches, read from the environment ONCE (when an ``InferenceNet`` is built) instead of on every
     call of the hot host path; non-default values are logged once. Tests and A/B scripts change them on a live object with
@@ -111,10 +155,13 @@ class EvalOptions:
     ``CCZ_CONV_ONE_LAUNCH=0`` (one_launch; round 7): with the edge-pair kernel, the middle and edge-pair tiles of a layer as two launches
     instead of one (k_conv3x3_g16_one, csrc/cczero_conv_g16e.h; same bits);
     ``CCZ_CONV_QUAD=0`` (quad): with the edge-pair kernel, the middle tiles as two ranks x 256 output channels instead of four ranks x
-    128 (g5q_tile, csrc/cczero_conv_g16.h; same bits)."""
+    128 (g5q_tile, csrc/cczero_conv_g16.h; same bits);
+    ``CCZ_CONV_CHUNK_MAJOR=0`` (chunk_major): the tower's activations as group-of-16 ROWS at every size instead of the chunk-major
+    G16C layout (csrc/cczero_conv_g16.h g16c_off: a tile's slab DMA moves whole cache lines; same bits) where the quad one-launch
+    form with the heads in the last layer runs (:meth:`InferenceNet._g16c`)."""
 
     FIELDS = ("fused_conv", "fused_stem", "fused_heads", "fused_last", "layout", "force", "groups", "chains", "zigzag", "edge_tiles", "one_launch",
-              "quad")
+              "quad", "chunk_major")
 
     def __init__(self, env=None):
         env = os.environ if env is None else env
@@ -131,6 +178,7 @@ class EvalOptions:
         self.edge_tiles = {"0": False, "1": True}.get(env.get("CCZ_CONV_EDGE_TILES", "auto"), "auto")
         self.one_launch = env.get("CCZ_CONV_ONE_LAUNCH", "1") != "0"
         self.quad = env.get("CCZ_CONV_QUAD", "1") != "0"
+        self.chunk_major = env.get("CCZ_CONV_CHUNK_MAJOR", "1") != "0"
         if self.layout not in ("auto", "nhwc", "g16"):
             raise ValueError("CCZ_CONV_LAYOUT must be auto, nhwc or g16")
 
@@ -395,7 +443,7 @@ class InferenceNet(nn.Module):
     TOWER_GROUP_BOARDS = 2048  # boards per sequential group (working set of a group fits the Infinity Cache); env CCZ_TOWER_GROUPS
     TOWER_CHAINS = 2  # independent board ranges run as concurrent launch chains (one HIP stream each); env CCZ_TOWER_CHAINS (<= 8); three with the edge-pair kernel (TOWER_CHAINS_EDGE)
 
-    def _tower_fused(self, x, plan=None, g16=None, heads=None):
+    def _tower_fused(self, x, plan=None, g16=None, heads=None, chunk_major=False):
         """40 residual blocks = 80 launches of one kernel: conv3x3 + bias [+ x] + ReLU each (reference net.py:20-43).
         ``plan`` = (rows, n_rows) of the planned evaluator boundary: only the first ``n_rows`` (a device value) boards of ``x``
         are live; every launch skips the tiles past them (``ccz_conv3x3_c256_f16_live``).
@@ -409,11 +457,13 @@ class InferenceNet(nn.Module):
         :meth:`_tower_enqueue`. ``g16``: the rows of ``x`` are in the group-of-16 order
         (``None``: as :meth:`_stem_fused` lays out a batch of this size). ``heads`` = (pol, val) buffers of :meth:`_head_buffers`
         (group-of-16 rows only): the LAST layer runs as ``ccz_conv3x3_c256_heads_f16`` -- both head convolutions in its epilogue,
-        its own output never stored: the returned tensor then holds the input of the last block, not the tower's output."""
+        its own output never stored: the returned tensor then holds the input of the last block, not the tower's output.
+        ``chunk_major``: the memory of ``x`` is the G16C layout (:meth:`_g16c` says when that form exists); the same launches on the
+        G16C entry points."""
         if g16 is None:   # x as _stem_fused returned it for a batch of this size (padded to whole groups of 16 boards)
             g16 = self._g16(x.shape[0]) and x.shape[0] % 16 == 0
         sched = self.tower_schedule(x.shape[0], g16, plan is not None, torch.cuda.is_current_stream_capturing())
-        self._tower_enqueue(sched, x, torch.empty_like(x), plan, heads)
+        self._tower_enqueue(sched, x, torch.empty_like(x), plan, heads, chunk_major)
         return x
 
     def tower_schedule(self, B: int, g16: bool, planned: bool = False, capturing: bool = False):
@@ -455,7 +505,7 @@ class InferenceNet(nn.Module):
             sched.append([(g0 + b0, g0 + min(n, b0 + step), f1, f2) for b0 in range(0, n, step)])
         return sched
 
-    def _tower_enqueue(self, sched, x, y, plan=None, heads=None):
+    def _tower_enqueue(self, sched, x, y, plan=None, heads=None, chunk_major=False):
         """Enqueue a :meth:`tower_schedule`: the groups one after the other; the chains of a group forked from the current stream
         onto the first streams of :meth:`_chain_pool` (chain 0 as well) and joined into it at the end -- a single chain runs on the
         current stream itself, without events. Launches are enqueued layer by layer across the chains, so that the chains advance
@@ -468,6 +518,10 @@ class InferenceNet(nn.Module):
         layers = [(_ptr(w), _ptr(b)) for w, b in zip(wsrc, self.bs32)]
         hw, hb = (_ptr(self.head_w32), _ptr(self.head_b32)) if heads is not None else (None, None)
         conv = L.ccz_conv3x3_c256_f16 if plan is None else L.ccz_conv3x3_c256_f16_live
+        heads_layer = L.ccz_conv3x3_c256_heads_f16
+        if chunk_major:   # the G16C twins: same arguments (a chain's board range is whole 128-board blocks: the group stride is the rows')
+            conv = L.ccz_conv3x3_c256_g16c_f16 if plan is None else L.ccz_conv3x3_c256_g16c_f16_live
+            heads_layer = L.ccz_conv3x3_c256_heads_g16c_f16
         row = 90 * 256 * x.element_size()
 
         def chain(st, d):
@@ -495,7 +549,7 @@ class InferenceNet(nn.Module):
                     _lib.check(conv(s, xp, w1, b1, None, yp, n, f1, *tail))
                 if heads is not None and i == len(layers) - 2:   # the last layer: heads in the epilogue, no output tensor
                     for s, xp, yp, hd, n, _, f2, _, tail in chains:
-                        _lib.check(L.ccz_conv3x3_c256_heads_f16(s, yp, w2, b2, xp, hw, hb, *hd, n, f2, *tail))
+                        _lib.check(heads_layer(s, yp, w2, b2, xp, hw, hb, *hd, n, f2, *tail))
                     continue
                 for s, xp, yp, _, n, _, f2, tail, _ in chains:
                     _lib.check(conv(s, yp, w2, b2, xp, xp, n, f2, *tail))  # output written over the residual input
@@ -520,10 +574,11 @@ class InferenceNet(nn.Module):
         return (_lib.CONV_G16_EDGE_TILES | (_lib.CONV_G16_ONE_LAUNCH if self.opt.one_launch else 0)
                 | (_lib.CONV_G16_QUAD if self.opt.quad else 0)) if edge else 0
 
-    def _stem_fused(self, leaf_input, plan=None, g16=None):
+    def _stem_fused(self, leaf_input, plan=None, g16=None, chunk_major=False):
         """Stem on the same MFMA kernel: pack the 21 live planes as NHWC rows of 64 channels, then one 64-channel chunk of
         the tower convolution (conv3x3 + bias + ReLU). Replaces cat + layout copy + MIOpen convolution + epilogue pass.
-        With a ``plan`` the pack GATHERS: output row i is board rows[i], for the live rows only."""
+        With a ``plan`` the pack GATHERS: output row i is board rows[i], for the live rows only. ``chunk_major`` (group-of-16 only):
+        the output is written in the G16C layout."""
         from . import _lib
         L = _lib.lib()
         B, dev = leaf_input.shape[0], leaf_input.device
@@ -541,13 +596,15 @@ class InferenceNet(nn.Module):
             # rows past the live ones are never computed: they must still hold finite numbers for the heads' GEMMs (whose results
             # for those rows nobody reads). Two persistent buffers, zeroed ONCE: whatever a row holds later is an old finite result.
             bufs = self.__dict__.setdefault("_plan_bufs", {})
-            key = (Bp, dev, g16)
+            key = (Bp, dev, g16)   # (either layout of the group-of-16 rows: a dead row holds an old finite result of some layout, read by nobody)
             if key not in bufs:
                 bufs[key] = (torch.zeros((Bp, 90, 64), dtype=torch.float16, device=dev),
                              torch.empty((Bp, 256, 10, 9), dtype=torch.float16, device=dev, memory_format=torch.channels_last).zero_())
             x64, y = bufs[key]
             pack, gather = (L.ccz_pack_live_planes_g16_f16 if g16 else L.ccz_pack_live_planes_rows_f16), (_ptr(plan[0]), _ptr(plan[1]))
             stem, tail = L.ccz_conv3x3_stem_f16_live, (Bp * 90 if g16 else -(-B // 8) * 8 * 90, 1 | lay, _ptr(plan[1]), 0, 1)
+        if chunk_major:
+            stem = L.ccz_conv3x3_stem_g16c_f16 if plan is None else L.ccz_conv3x3_stem_g16c_f16_live
         _lib.check(pack(s, _ptr(leaf_input), _ptr(x64), B, *gather))
         _lib.check(stem(s, _ptr(x64), _ptr(self.stem_w64_g16 if g16 else self.stem_w64), _ptr(self.stem_b32), _ptr(y), *tail))
         return y
@@ -596,14 +653,17 @@ class InferenceNet(nn.Module):
             plan = None
         g16 = path == "g16"   # True: x holds its rows in the group-of-16 layout (and ceil(B / 16) * 16 boards)
         if path in ("g16", "nhwc"):
-            x = self._stem_fused(leaf_input, plan, g16)
+            cm = g16 and self._g16c(-(-B // 16) * 16)
+            x = self._stem_fused(leaf_input, plan, g16, cm)
             probe = self.__dict__.get("tower_probe")   # bench.py: a list that receives one HIP-event pair around the 80 tower launches
             if probe is not None:   # (recorded on the current stream: the chains fork from it and join it)
                 p0, p1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 p0.record()
             # group-of-16 rows: the head convolutions ride in the last tower layer's epilogue (fused_last; CCZ_FUSED_LAST=0: a pass of their own)
             heads = self._head_buffers(x.shape[0], x.device)[:2] if (g16 and self.opt.fused_last and self._fused_heads_ok(x)) else None
-            x = self._tower_fused(x, plan, g16, heads)
+            if cm and heads is None:   # (_g16c has checked what the heads need: the stem has written G16C, only the heads layer reads it last)
+                raise RuntimeError("chunk-major tower without the heads in its last layer")
+            x = self._tower_fused(x, plan, g16, heads, cm)
             if probe is not None:
                 p1.record()
                 probe.append((p0, p1))
@@ -630,6 +690,14 @@ class InferenceNet(nn.Module):
                     y = self._epilogue(F.conv2d(x, self.ws[i], None, padding=1), self.bs[i])
                     x = self._epilogue(F.conv2d(y, self.ws[i + 1], None, padding=1), self.bs[i + 1], x)
         return self._heads(x, B, g16, plan, return_logits)
+
+    def _g16c(self, Bp: int) -> bool:
+        """Does a group-of-16 batch of ``Bp`` boards run in the chunk-major G16C layout? The layout exists for the forms the large
+        batches run -- edge tiles, one launch per layer, quad middle tiles, the heads in the last layer's epilogue; anything else
+        stays on rows (``chunk_major=False`` / ``CCZ_CONV_CHUNK_MAJOR=0``: always)."""
+        o = self.opt
+        return bool(o.chunk_major and o.one_launch and o.quad and o.fused_last and o.fused_heads and hasattr(self, "head_w32")
+                    and self.dtype == torch.float16 and self._edge(Bp, True))
 
     def _fused_heads_ok(self, x) -> bool:
         return bool(self.opt.fused_heads and hasattr(self, "head_w32") and x.is_cuda and x.dtype == torch.float16 and x.shape[1] == 256

@@ -919,6 +919,32 @@ int ccz_conv3x3_c256_heads_f16(void *stream, const void *x_dev, const void *w_de
                                void *pol_dev, void *val_dev, int64_t n_pixels, int32_t flags,
                                const int32_t *live_rows_dev, int32_t part, int32_t n_parts);
 
+/* ---- the chunk-major activation layout "G16C" (additive; csrc/cczero_conv_g16.h g16c_off) -------------------------------------
+ * The same 16-board groups as CCZ_CONV_G16 and the same group stride (1440 rows x 512 B), but inside a group the bytes are
+ * [chunk 0..7][row 0..1439][32 channels]: channel c of G16 row p of group g is at byte g * 737280 + (c / 32) * 92160 + p * 64 +
+ * (c % 32) * 2. A tile's activation slab of one 32-channel chunk is then ONE contiguous run of whole cache lines (in CCZ_CONV_G16
+ * rows it is 64-byte pieces 512 B apart, and every line crosses the L2 -> L1 path twice). Same tiles, same MFMAs in the same
+ * order: the same values as the CCZ_CONV_G16 calls, permuted. The calls below take the arguments of their CCZ_CONV_G16 twins;
+ * `relu` / `flags` must hold CCZ_CONV_G16. ccz_conv3x3_c256_g16c_f16(_live): x, residual, y in G16C; only the quad one-launch form
+ * exists (CCZ_CONV_G16_EDGE_TILES | CCZ_CONV_G16_ONE_LAUNCH | CCZ_CONV_G16_QUAD must be set: anything else is refused; a single
+ * group runs that form too). ccz_conv3x3_stem_g16c_f16(_live): x64 as for ccz_conv3x3_stem_f16 with CCZ_CONV_G16 (rows), y in G16C.
+ * ccz_conv3x3_c256_heads_g16c_f16: x and residual in G16C (CCZ_CONV_G16_EDGE_TILES must be set: middle + edge-pair launches); pol / val in
+ * board order as ever. */
+int ccz_conv3x3_c256_g16c_f16(void *stream, const void *x_dev, const void *w_dev, const void *bias_f32_dev,
+                              const void *residual_dev, void *y_dev, int64_t n_pixels, int32_t relu);
+int ccz_conv3x3_c256_g16c_f16_live(void *stream, const void *x_dev, const void *w_dev, const void *bias_f32_dev,
+                                   const void *residual_dev, void *y_dev, int64_t n_pixels, int32_t relu,
+                                   const int32_t *live_rows_dev, int32_t part, int32_t n_parts);
+int ccz_conv3x3_stem_g16c_f16(void *stream, const void *x64_dev, const void *w_dev, const void *bias_f32_dev,
+                              void *y_dev, int64_t n_pixels, int32_t relu);
+int ccz_conv3x3_stem_g16c_f16_live(void *stream, const void *x64_dev, const void *w_dev, const void *bias_f32_dev,
+                                   void *y_dev, int64_t n_pixels, int32_t relu, const int32_t *live_rows_dev,
+                                   int32_t part, int32_t n_parts);
+int ccz_conv3x3_c256_heads_g16c_f16(void *stream, const void *x_dev, const void *w_dev, const void *bias_f32_dev,
+                                    const void *residual_dev, const void *head_w32_dev, const void *head_bias32_f32_dev,
+                                    void *pol_dev, void *val_dev, int64_t n_pixels, int32_t flags,
+                                    const int32_t *live_rows_dev, int32_t part, int32_t n_parts);
+
 #ifdef __cplusplus
 }
 #endif
