@@ -22,6 +22,7 @@ import time
 import numpy as np
 
 from ._lib import CczError
+from .boundary import describe
 from .game import Board
 from .searchcfg import add_search_args, mean_leaf_depth, search_from_args
 
@@ -91,41 +92,38 @@ class BatchedAnalysis:
         ``search``: a dict of ``SelfPlayEngine.set_search``'s arguments (first-play urgency, visit-scaled c_puct); None: the
         reference's PUCT."""
         from .selfplay import BatchedSelfPlay
-        ev = getattr(evaluator, "evaluate_leaves_logits", evaluator)
+        desc = describe(evaluator)
+        ev = desc.fn
         if not callable(ev):
             raise TypeError("BatchedAnalysis: the evaluator must be callable or have evaluate_leaves_logits")
         if not 1 <= int(multipv) <= 128 or int(max_len) < 1 or int(n_playout) < 1:
             raise ValueError("BatchedAnalysis: multipv must be 1..128, max_len and n_playout >= 1")
         if "eval_cache_log2" not in engine_kw:
-            engine_kw["eval_cache_log2"] = 22 if (int(n_boards) >= 192 and getattr(ev, "accepts_plan", False)) else 0
+            engine_kw["eval_cache_log2"] = 22 if (int(n_boards) >= 192 and desc.accepts_plan) else 0
         engine_kw.setdefault("mirror", False)
         self.width = int(width)
         self.wide = None
+        self.B, self.n_playout, self.multipv, self.max_len = int(n_boards), int(n_playout), int(multipv), int(max_len)
+        self.positions = self.steps = self.sims = 0
+        self.seconds = 0.0
+        self._rows = None   # evaluator rows, summed on the device (planned boundary: the plan's count per step)
         if self.width != 1:
             if solver or search is not None:
                 raise ValueError("BatchedAnalysis: width > 1 excludes the solver and the search parameters")
             from .wide import WideSearch
-            if engine_kw["eval_cache_log2"] == 0 and getattr(ev, "accepts_plan", False):
+            if engine_kw["eval_cache_log2"] == 0 and desc.accepts_plan:
                 engine_kw["eval_cache_log2"] = 16   # slots of one tree reach one position often: they share an evaluator row
             engine_kw.setdefault("eps", 0.0)
             self.wide = WideSearch(ev, int(n_boards), self.width, n_playout=int(n_playout), **engine_kw)   # ValueError: width not in 2..64
             self.sp = None
             self.engine = self.wide.engine
             self.solver = False
-            self.B, self.n_playout, self.multipv, self.max_len = int(n_boards), int(n_playout), int(multipv), int(max_len)
-            self.positions = self.steps = self.sims = 0
-            self.seconds = 0.0
-            self._rows = None
             return
         self.sp = BatchedSelfPlay(ev, int(n_boards), n_playout=int(n_playout), eps=0.0, search=search, **engine_kw)   # no GPU: CczError
         self.engine = self.sp.engine
         self.solver = bool(solver)     # the MCTS-solver: records gain "mate", bestmove follows the proof (make_record)
         if self.solver:
             self.engine.set_solver(True)
-        self.B, self.n_playout, self.multipv, self.max_len = int(n_boards), int(n_playout), int(multipv), int(max_len)
-        self.positions = self.steps = self.sims = 0
-        self.seconds = 0.0
-        self._rows = None   # evaluator rows, summed on the device (planned boundary: the plan's count per step)
 
     def _count_rows(self, stage, _sim):
         if stage == "eval1":
@@ -159,7 +157,7 @@ class BatchedAnalysis:
                 moves[j] = [m.id for m in bd.move_stack]
             status = e.set_positions(sq, turn, half, moves, park=np.arange(S) >= n)   # the tail of the last chunk is parked
             if sp is not None:
-                sp._sim, sp._leaf, sp._acc = 0, None, 0      # fresh roots: whatever leaf was pending belongs to the old ones
+                sp._sim, sp._leaf, sp._ticker.acc = 0, None, 0      # fresh roots: whatever leaf was pending belongs to the old ones
             st = e.game_status()
             if self.wide is not None:
                 self.wide.boundary()

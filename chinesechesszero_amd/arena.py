@@ -21,6 +21,7 @@ import time
 
 import numpy as np
 
+from .boundary import WeightsWatch, describe
 from .parameters import C_PUCT
 from .searchcfg import add_search_args, mean_leaf_depth, search_from_args
 
@@ -156,19 +157,11 @@ def promote(result, threshold: float = PROMOTE_THRESHOLD) -> bool:
 
 # ---------------------------------------------------------------------- the arena
 def _as_evaluator(net, name):
-    ev = getattr(net, "evaluate_leaves_logits", net)
-    if not callable(ev) or not (getattr(ev, "accepts_plan", False) and getattr(ev, "returns_logits", False)):
+    ev = describe(net)
+    if not callable(ev.fn) or not (ev.accepts_plan and ev.returns_logits):
         raise TypeError(f"Arena: network {name} must be a plan-capable logits evaluator (a PolicyValueNet, or a callable marked "
                         "accepts_plan and returns_logits: ev(leaf, plan=(rows, n)) -> compact (logits, value))")
     return ev
-
-
-def _version(net, ev):
-    for obj in (net, getattr(ev, "__self__", None), ev):
-        v = getattr(obj, "weights_version", None)
-        if v is not None:
-            return int(v)
-    return 0
 
 
 class Arena:
@@ -188,7 +181,11 @@ class Arena:
                  cache_verify: bool = False, n_playout_b: int | None = None, resign=None, solver: bool = False, search=None):
         from .engine import SelfPlayEngine
         self.nets = (net_a, net_b)
-        self.ev = (_as_evaluator(net_a, "A"), _as_evaluator(net_b, "B"))
+        described = (_as_evaluator(net_a, "A"), _as_evaluator(net_b, "B"))
+        self.ev = (described[0].fn, described[1].fn)
+        # the two weights versions as the cache salts take them (an evaluator that exposes none counts as version 0)
+        self._versions = lambda: tuple(int(d.version() or 0) for d in described)
+        self._weights = WeightsWatch()       # nothing seen: the first search sets the routing
         if int(n_pairs) < 1:
             raise ValueError("Arena: n_pairs must be >= 1")
         if int(eval_cache_log2) < 1:
@@ -228,7 +225,6 @@ class Arena:
             raise ValueError(f"Arena: opening positions refused by the engine (status {status.tolist()})")
         self._turn = np.asarray(turn)[of].astype(np.uint8)      # side to move on every board (kept from the per-move status read)
         self._temps = np.full(self.B, self.temp, np.float64)
-        self._versions = None
         self.moves = []                      # host int32 [B] per lockstep move (-1: no move on that board)
         self.truncated = np.zeros(self.B, bool)
         self.steps = 0
@@ -238,10 +234,8 @@ class Arena:
     def _sync_routing(self):
         """(Re)set the routing when a network's weights version changed: that network gets a new salt, and its old entries can
         never be served again (the other network's stay valid)."""
-        v = (_version(self.nets[0], self.ev[0]), _version(self.nets[1], self.ev[1]))
-        if v != self._versions:
-            self.engine.set_routing(self.red_net, cache_salts(*v))
-            self._versions = v
+        if self._weights.moved(self._versions()):
+            self.engine.set_routing(self.red_net, cache_salts(*self._weights.seen))
 
     def search(self, on_step=None):
         """``n_playout`` routed simulations on every unfinished board (fresh trees). ``on_step(arena, plan0, plan1)`` runs after

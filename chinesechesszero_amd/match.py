@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import numpy as np
 
+from .boundary import deliver, kind_of
 from .engine import SelfPlayEngine
 from .parameters import C_PUCT
 
@@ -46,11 +47,7 @@ class BatchedMatch:
         ev = self.ev[turn]
         leaf = e.select_leaves()
         for i in range(self.n_playout):
-            prob, value = ev(leaf)
-            if i + 1 < self.n_playout:
-                leaf = e.step(prob, value)
-            else:
-                e.expand_backup(prob, value)
+            leaf = deliver(e, kind_of(ev), *ev(leaf), i + 1 == self.n_playout)
         if self.before_move is not None:
             self.before_move(self)
         forced = None

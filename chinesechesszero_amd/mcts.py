@@ -20,9 +20,11 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from .boundary import PlayoutTicker, deliver, describe, kind_of, may_graph
 from .engine import SelfPlayEngine
 from .parameters import ALPHA, C_PUCT, EPS
 from .searchcfg import resolve_scouts
+from .selfplay import GraphedStep, ScoutedSearch
 from .tools import softmax
 
 
@@ -103,16 +105,16 @@ class MCTS:
         self._discard = False
         self._graph = None
         self.use_graph = True   # single-board play is launch-bound: replay (evaluator, k_step) as one hipGraph
+        # (the module docstring's forms: batched as it is, policy_value_fn routed to its object's batched one, else a callback: _ev None)
         owner = getattr(policy_value_fn, "__self__", None)
-        if getattr(policy_value_fn, "batched", False):
-            self._batched = policy_value_fn
-        elif owner is not None and hasattr(owner, "evaluate_leaves") and getattr(policy_value_fn, "__name__", "") == "policy_value_fn":
-            self._batched = getattr(owner, "evaluate_leaves_logits", owner.evaluate_leaves)
-        else:
-            self._batched = None
+        ev = describe(policy_value_fn)
+        if not ev.batched and hasattr(owner, "evaluate_leaves") and getattr(policy_value_fn, "__name__", "") == "policy_value_fn":
+            ev = describe(getattr(owner, "evaluate_leaves_logits", owner.evaluate_leaves))
+        self._ev = ev if ev.batched else None
+        self._kind = kind_of(self._ev)
         import os
         want = int(os.environ.get("CCZ_SCOUTS", SCOUTS)) if scouts is None else int(scouts)
-        ok = self._batched is not None and getattr(self._batched, "returns_logits", False)
+        ok = self._ev is not None and ev.returns_logits
         self.scouts = max(0, min(want, 63)) if ok else 0
         if self.width > 1:
             if not ok:
@@ -125,7 +127,7 @@ class MCTS:
         if self._engine is None and self.width > 1:
             # one searched board, `width` slots for its pending leaves: every step is one evaluator call on all (at most 64) rows
             from .wide import WideSearch
-            self._wide = WideSearch(self._batched, 1, self.width, n_playout=max(1, self.n_playout), c_puct=self.c_puct, device=self._device,
+            self._wide = WideSearch(self._ev.fn, 1, self.width, n_playout=max(1, self.n_playout), c_puct=self.c_puct, device=self._device,
                                     seed=self._seed, use_graph=self.use_graph, mirror=True, strict=True)
             self._engine = self._wide.engine
         if self._engine is None:
@@ -180,105 +182,86 @@ class MCTS:
             self._wide.boundary()   # the board's simulation count starts over: the next search is n_playout simulations again
 
     # ---- reference surface ------------------------------------------------------------------------
+    def _callback(self, leaf, red_states, black_states):
+        """The compatibility path: the leaf goes to the reference-style ``f(board)`` as a ``LeafView``; (prob, value) on the device."""
+        e = self._engine
+        info = e.leaf_info()
+        sq, turn = _planes_to_squares(leaf[0].float().cpu().numpy())
+        k = int(info["k"][0])
+        view = LeafView(sq, turn, info["ids"][0][:k].astype(np.int64).tolist())
+        act_probs, leaf_value = self.policy(view, red_states, black_states)
+        p = np.zeros((1, 2086), np.float32)
+        for a, pr in act_probs:
+            p[0, int(a)] = np.float32(pr)
+        return torch.from_numpy(p).to(e.device), torch.from_numpy(np.asarray(leaf_value, np.float32).reshape(1)).to(e.device)
+
     def playout(self, board=None, red_states=None, black_states=None):
         """One simulation (mcts.py:101-129) of the engine's root."""
         e = self._ensure_engine()
         leaf = e.select_leaves()
-        if self._batched is not None:
-            prob, value = self._batched(leaf)
-            if getattr(self._batched, "returns_logits", False):
-                e.expand_backup_logits(prob, value)
-                return
-        else:
-            info = e.leaf_info()
-            sq, turn = _planes_to_squares(leaf[0].float().cpu().numpy())
-            k = int(info["k"][0])
-            view = LeafView(sq, turn, info["ids"][0][:k].astype(np.int64).tolist())
-            act_probs, leaf_value = self.policy(view, red_states, black_states)
-            p = np.zeros((1, 2086), np.float32)
-            for a, pr in act_probs:
-                p[0, int(a)] = np.float32(pr)
-            prob = torch.from_numpy(p).to(e.device)
-            value = torch.from_numpy(np.asarray(leaf_value, np.float32).reshape(1)).to(e.device)
-        e.expand_backup(prob, value)
+        deliver(e, self._kind, *(self._ev.fn(leaf) if self._ev is not None else self._callback(leaf, red_states, black_states)), True)
 
     def get_move_probs(self, board, temp=1e-3, red_states=None, black_states=None, on_playout=None):
         """mcts.py:131-166: run n_playout simulations, return (acts, probs) over the root's children."""
         self.red_history = red_states
         self.black_history = black_states
         self._sync_root(board)
-        interval = max(1, self.n_playout // 100)
-        acc = 0
-        e = self._engine
-        fused = self._batched is not None
-        logits = fused and getattr(self._batched, "returns_logits", False)
-        if self._wide is not None:
-            # the wide search: every step backs up and selects up to `width` leaves; on_playout sees the leaves of each step
-            def on_step(nl):
-                nonlocal acc
-                acc += int(nl[0])
-                if on_playout is not None and acc >= interval:
-                    try:
-                        on_playout(acc)
-                    except Exception:
-                        pass
-                    acc = 0
-            self._wide.search(on_step=on_step)
-            if on_playout is not None and acc:
-                try:
-                    on_playout(acc)
-                except Exception:
-                    pass
-            return self._root_probs(temp)
-        if fused and self.scouts:
-            # one game at a time with scout slots: the evaluator runs only when board 0's leaf is not in the table yet, on 1 + scouts rows
-            if self._scouted is None:
-                from .selfplay import ScoutedSearch
-                self._scouted = ScoutedSearch(e, self._batched, use_graph=self.use_graph)
-            self._scouted.begin_move()
-        elif fused:
-            # launch sequence of a move: select, (evaluator, fused step) x (n-1), evaluator, expand_backup
-            leaf = e.select_leaves()
-            if self.use_graph and self._graph is None and getattr(self._batched, "graph_safe", False) and e.device.type == "cuda":
-                from .selfplay import GraphedStep
-                self._graph = GraphedStep(e, self._batched)
-
-        def report(last):
-            nonlocal acc
-            if on_playout is not None and (acc >= interval or last):   # mcts.py:154-160
-                try:
-                    on_playout(acc)
-                except Exception:
-                    pass
-                acc = 0
-
-        if fused and self.scouts and self._scouted.device_loop:
-            # simulations that find their leaf in the table repeat on the device (ccz_scouted_run): the host sees the search when the
-            # evaluator has to run -- and at the playouts on_playout is due at, the same ones as in the loop below
-            left = self.n_playout
-            while left > 0:
-                done = self._scouted.run(left, left if on_playout is None else min(left, interval - acc))
-                left -= done
-                acc += done
-                report(left == 0)
-            n_host = 0
-        else:
-            n_host = self.n_playout
-        for i in range(n_host):
-            if not fused:
-                self.playout(board, red_states, black_states)
-            elif self.scouts:
-                self._scouted.simulate(last=i + 1 == self.n_playout)
-            elif i + 1 < self.n_playout:
-                if self._graph is not None:
-                    self._graph.replay()
-                else:
-                    leaf = (e.step_logits if logits else e.step)(*self._batched(leaf))
-            else:
-                (e.expand_backup_logits if logits else e.expand_backup)(*self._batched(leaf))
-            acc += 1
-            report(i == self.n_playout - 1)
+        self._strategy()(PlayoutTicker(self.n_playout, on_playout))
         return self._root_probs(temp)
+
+    def _strategy(self):
+        """How this object searches a move: one of the ``_search_*`` methods below (each takes the move's ``PlayoutTicker``)."""
+        if self._wide is not None:
+            return self._search_wide
+        if self._ev is None:
+            return self._search_callback
+        if not self.scouts:
+            return self._search_fused
+        if self._scouted is None:
+            self._scouted = ScoutedSearch(self._engine, self._ev.fn, use_graph=self.use_graph)
+        return self._search_scouted_device if self._scouted.device_loop else self._search_scouted_host
+
+    def _search_wide(self, ticker):
+        # every step backs up and selects up to `width` leaves; on_playout sees the leaves of each step
+        self._wide.search(on_step=lambda nl: ticker.tick(int(nl[0])))
+        ticker.tick(0, last=True)
+
+    def _search_callback(self, ticker):
+        for i in range(self.n_playout):
+            self.playout(None, self.red_history, self.black_history)
+            ticker.tick(1, i + 1 == self.n_playout)
+
+    def _search_scouted_device(self, ticker):
+        # one game at a time with scout slots: the evaluator runs only when board 0's leaf is not in the table yet, on 1 + scouts rows.
+        # Simulations that find their leaf in the table repeat on the device (ccz_scouted_run): the host sees the search when the
+        # evaluator has to run -- and at the playouts on_playout is due at, the same ones as in the host loop
+        self._scouted.begin_move()
+        left = self.n_playout
+        while left > 0:
+            done = self._scouted.run(left, ticker.room(left))
+            left -= done
+            ticker.tick(done, left == 0)
+
+    def _search_scouted_host(self, ticker):
+        self._scouted.begin_move()
+        for i in range(self.n_playout):
+            self._scouted.simulate(last=i + 1 == self.n_playout)
+            ticker.tick(1, i + 1 == self.n_playout)
+
+    def _search_fused(self, ticker):
+        # launch sequence of a move: select, (evaluator, fused step) x (n-1), evaluator, expand_backup; the inner iteration replayed
+        # as one hipGraph where that may be
+        e, ev = self._engine, self._ev
+        leaf = e.select_leaves()
+        if self._graph is None and may_graph(self.use_graph, ev, e.device):
+            self._graph = GraphedStep(e, ev.fn)
+        for i in range(self.n_playout):
+            last = i + 1 == self.n_playout
+            if self._graph is not None and not last:
+                self._graph.replay()
+            else:
+                leaf = deliver(e, self._kind, *ev.fn(leaf), last)
+            ticker.tick(1, last)
 
     def _root_probs(self, temp):
         rc = self._engine.root_children()

@@ -922,3 +922,4 @@ def uniform_evaluator(leaf_input: torch.Tensor):
 
 
 uniform_evaluator.batched = True
+uniform_evaluator.stateless = True   # no weights: a captured graph or a cache of its answers never goes stale

@@ -10,8 +10,8 @@ from __future__ import annotations
 import os
 
 import numpy as np
-import torch
 
+from .boundary import PlayoutTicker, WeightsWatch, capture, deliver, describe, kind_of, may_graph, need_version
 from .engine import SelfPlayEngine
 from .parameters import ALPHA, C_PUCT, EPS
 
@@ -26,54 +26,30 @@ class GraphedStep:
     """
 
     def __init__(self, engine: SelfPlayEngine, evaluator, warmup: int = 3, version_fn=None):
-        """``version_fn() -> hashable``: what tells this object that the evaluator's weights changed (a re-capture follows).
-        Default: the ``weights_version`` of the object the evaluator is a bound method of (``PolicyValueNet``). An evaluator
-        wrapped in a lambda / partial / closure has no such owner: pass ``version_fn`` (e.g. ``lambda: pvn.weights_version``),
-        otherwise the captured graph can never notice a weight change -- that case is logged once."""
+        """``version_fn() -> hashable``: what tells this object that the evaluator's weights changed (a re-capture follows);
+        default and lookup order: :func:`boundary.describe`. An evaluator nothing says that of is logged once: its graph can
+        never notice a weight change."""
         self.engine = engine
         self.evaluator = evaluator
         self.warmup = warmup
         self.captures = 0
-        self.version_fn = version_fn
-        if version_fn is None and not hasattr(getattr(evaluator, "__self__", None), "weights_version") \
-                and not getattr(evaluator, "stateless", False) and getattr(evaluator, "__name__", "") != "uniform_evaluator":
-            from .tools import log
-            log("GraphedStep: the evaluator exposes no weights_version and no version_fn was given: the captured hipGraph will "
-                "keep replaying the weights it was captured with (pass version_fn=... if they can change)", "WARNING")
+        self._ev = describe(evaluator, version_fn)
+        need_version(self._ev, "GraphedStep: ", consequence="the captured hipGraph will keep replaying the weights it was captured "
+                     "with (pass version_fn=... if they can change)")
+        self._weights = WeightsWatch(self._ev.version())
         self._capture()
 
-    def _weights_version(self):
-        """The captured graph holds the device addresses of the evaluator's inference weights. ``PolicyValueNet`` bumps
-        ``weights_version`` whenever that copy is rebuilt or invalidated (training step, hot reload): a replay against
-        the old addresses would silently search with stale or freed weights."""
-        if self.version_fn is not None:
-            return self.version_fn()
-        owner = getattr(self.evaluator, "__self__", None)
-        return getattr(owner, "weights_version", None)
-
     def _capture(self):
-        engine, evaluator = self.engine, self.evaluator
-        dev = engine.device
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            for _ in range(self.warmup):  # results are discarded: the pending leaf is only evaluated, never stepped
-                evaluator(engine.leaf_input)  # (also rebuilds a stale inference copy OUTSIDE the capture)
-        torch.cuda.current_stream(dev).wait_stream(side)
-        torch.cuda.synchronize(dev)
-        self.version = self._weights_version()
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            prob, value = evaluator(engine.leaf_input)
-            if getattr(evaluator, "returns_logits", False):
-                engine.step_logits(prob, value)
-            else:
-                engine.step(prob, value)
-        # capture does not execute: nothing has been applied to the trees yet
+        engine, ev = self.engine, self._ev
+        # warm-up: the pending leaf is only evaluated, never stepped (and a stale inference copy is rebuilt OUTSIDE the capture,
+        # which moves the version: it is read after that); capture does not execute: nothing is applied to the trees yet
+        self.graph = capture(engine.device, lambda: deliver(engine, kind_of(ev), *ev.fn(engine.leaf_input), False),
+                             warm=lambda: ev.fn(engine.leaf_input), warmup=self.warmup)
+        self._weights.moved(ev.version())
         self.captures += 1
 
     def replay(self):
-        if self._weights_version() != self.version:
+        if self._weights.moved(self._ev.version()):
             self._capture()  # weights changed since the capture (train_step / refresh_inference_copy / broadcast_model)
         self.graph.replay()
 
@@ -90,18 +66,17 @@ class ScoutedSearch:
     a row does not depend on the batch it sits in (tests/test_gpu_scouts.py)."""
 
     def __init__(self, engine: SelfPlayEngine, evaluator, version_fn=None, use_graph: bool = True, warmup: int = 3, device_loop=None):
-        if not (getattr(evaluator, "returns_logits", False) and getattr(evaluator, "batched", False)):
+        ev = describe(evaluator, version_fn)
+        if not (ev.returns_logits and ev.batched):
             raise ValueError("scouts need a batched evaluator that returns logits (PolicyValueNet.evaluate_leaves_logits)")
         if getattr(engine, "n_scouts", 0) < 1:
             raise ValueError("the engine has no scout slots (SelfPlayEngine.set_scouts)")
-        self.engine, self.evaluator, self.version_fn = engine, evaluator, version_fn
-        self.use_graph = bool(use_graph and getattr(evaluator, "graph_safe", False) and engine.device.type == "cuda")
+        self.engine, self.evaluator, self._version = engine, ev.fn, ev.version
+        self.use_graph = may_graph(use_graph, ev, engine.device)
         self.warmup = warmup
-        if version_fn is None and not hasattr(getattr(evaluator, "__self__", None), "weights_version") and not getattr(evaluator, "stateless", False):
-            from .tools import log
-            log("ScoutedSearch: the evaluator exposes no weights_version and no version_fn was given: evaluations cached for other weights "
-                "cannot be told apart (pass version_fn=... if its weights can change)", "WARNING")
-        self.version = self._weights_version()
+        need_version(ev, "ScoutedSearch: ", consequence="evaluations cached for other weights cannot be told apart (pass version_fn=... "
+                     "if its weights can change)")
+        self._weights = WeightsWatch(ev.version())
         self._g_step = self._g_eval = self._g_run = self._g_eval_run = None
         self.evaluator_calls = self.simulations = 0
         # simulations that hit the table are repeated ON THE DEVICE (ccz_scouted_run: one launch per evaluator call instead of two
@@ -110,51 +85,34 @@ class ScoutedSearch:
         self.device_loop = self.device_loop and engine.B <= 16
         self._need = True
 
-    def _weights_version(self):
-        if self.version_fn is not None:
-            return self.version_fn()
-        return getattr(getattr(self.evaluator, "__self__", None), "weights_version", None)
-
     def _check_weights(self):
-        v = self._weights_version()
-        if v != self.version:          # cached evaluations (and captured addresses) of other weights must not reach the tree
+        if self._weights.moved(self._version()):        # cached evaluations (and captured addresses) of other weights must not reach the tree
             self.engine.clear_eval_cache()
-            self.version = v
             self._g_eval = self._g_eval_run = None
 
-    def _plan(self):
-        self.engine.scout_and_plan()
+    def _warm(self):
+        self.evaluator(self.engine.leaf_input)
 
     def _evaluate(self):
         e = self.engine
         logits, value = self.evaluator(e.leaf_input)
         e.gather_priors_planned(logits, value)
 
-    def _capture(self, fn):
-        dev = self.engine.device
-        torch.cuda.synchronize(dev)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            fn()
-        return g
+    def _do(self, name: str, body, warm=None):
+        """``body()``: eagerly, or as a replay of the hipGraph kept in attribute ``name`` (captured when first needed)."""
+        if not self.use_graph:
+            return body()
+        if getattr(self, name) is None:
+            setattr(self, name, capture(self.engine.device, body, warm=warm, warmup=self.warmup))
+        getattr(self, name).replay()
 
     def begin_move(self):
         """After a re-root / new position: select board 0's first leaf, scout, plan."""
         self._check_weights()
         self.engine.select_leaves()
-        self._plan()
+        self.engine.scout_and_plan()
         if self.device_loop:
             self._need = self.engine.plan_state_of_board0() == 0
-
-    def _warm_evaluator(self):
-        e = self.engine
-        dev = e.device
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            for _ in range(self.warmup):     # allocator / inference-copy warm-up outside the capture; results discarded
-                self.evaluator(e.leaf_input)
-        torch.cuda.current_stream(dev).wait_stream(side)
 
     def run(self, left: int, budget: int) -> int:
         """Up to ``budget`` simulations of the move (``left`` = how many it still has, the pending one included) with ONE launch
@@ -164,21 +122,10 @@ class ScoutedSearch:
         e = self.engine
         e.set_run(min(budget, left), left)
         if self._need:
-            if self.use_graph:
-                if self._g_eval_run is None:
-                    self._warm_evaluator()
-                    self._g_eval_run = self._capture(lambda: (self._evaluate(), e.scouted_run_launch()))
-                self._g_eval_run.replay()
-            else:
-                self._evaluate()
-                e.scouted_run_launch()
+            self._do("_g_eval_run", lambda: (self._evaluate(), e.scouted_run_launch()), self._warm)
             self.evaluator_calls += 1
-        elif self.use_graph:
-            if self._g_run is None:
-                self._g_run = self._capture(e.scouted_run_launch)
-            self._g_run.replay()
         else:
-            e.scouted_run_launch()
+            self._do("_g_run", e.scouted_run_launch)
         done, self._need = e.run_outcome()
         if done < 1:
             raise RuntimeError("ccz_scouted_run reported no simulation")
@@ -190,25 +137,13 @@ class ScoutedSearch:
         selection, scouting and plan unless ``last``)."""
         e = self.engine
         if e.plan_state_of_board0() == 0:
-            if self.use_graph:
-                if self._g_eval is None:
-                    self._warm_evaluator()
-                    self._g_eval = self._capture(self._evaluate)
-                self._g_eval.replay()
-            else:
-                self._evaluate()
+            self._do("_g_eval", self._evaluate, self._warm)
             self.evaluator_calls += 1
         self.simulations += 1
         if last:
             e.expand_backup_compact(None)
-            return
-        if self.use_graph:
-            if self._g_step is None:
-                self._g_step = self._capture(lambda: (e.step_compact(None), self._plan()))
-            self._g_step.replay()
         else:
-            e.step_compact(None)
-            self._plan()
+            self._do("_g_step", lambda: (e.step_compact(None), e.scout_and_plan()))
 
 
 class BatchedSelfPlay:
@@ -298,43 +233,46 @@ class BatchedSelfPlay:
         # planned evaluator boundary: the engine holds an evaluation cache (eval_cache_log2 > 0) and the evaluator can compute a
         # planned subset of the rows (PolicyValueNet.evaluate_leaves_logits): positions evaluated before are not sent through
         # the network again (include/cczero.h ccz_eval_plan). Same results, bit for bit.
-        self.planned = bool(self.engine.eval_cache_log2 > 0 and getattr(evaluator, "accepts_plan", False)
-                            and getattr(evaluator, "returns_logits", False))
+        ev = describe(evaluator, version_fn)
+        self.planned = bool(self.engine.eval_cache_log2 > 0 and ev.accepts_plan and ev.returns_logits)
         self.version_fn = version_fn
-        if self.planned and version_fn is None and not hasattr(getattr(evaluator, "__self__", None), "weights_version") \
-                and not getattr(evaluator, "stateless", False):
-            raise ValueError("planned evaluator boundary (evaluation cache) with an evaluator that exposes no weights_version: "
-                             "pass version_fn=... (what changes when its weights do), mark it `stateless = True`, or use eval_cache_log2=0")
-        self._cache_version = self._evaluator_version()
+        if self.planned:
+            need_version(ev, planned=True)
+        # (``evaluator`` and ``planned`` stay plain attributes read at every call -- bench.py swaps a stub in and out --: the version
+        # is asked of whatever evaluator is current)
+        self._weights = WeightsWatch(self._evaluator_version())
         self._sim = 0        # simulations done of the current move
         self._leaf = None    # the pending leaf batch (None: the next simulation starts with select_leaves)
-        self._acc = 0
+        self._ticker = PlayoutTicker(n_playout)
 
     def _evaluator_version(self):
-        """What tells the evaluation cache that the evaluator's weights changed: ``version_fn()`` if one was given, else the
-        ``weights_version`` of the object the evaluator is a bound method of (``PolicyValueNet``)."""
-        if self.version_fn is not None:
-            return self.version_fn()
-        return getattr(getattr(self.evaluator, "__self__", None), "weights_version", None)
+        """What tells the evaluation cache that the evaluator's weights changed (:func:`boundary.describe`)."""
+        return describe(self.evaluator, self.version_fn).version()
+
+    @property
+    def _cache_version(self):
+        return self._weights.seen
+
+    @_cache_version.setter
+    def _cache_version(self, v):
+        self._weights.seen = v
 
     def _planned_eval(self, leaf):
         """(logits, value) of the planned rows; cached evaluations of other weights are dropped first."""
         e = self.engine
-        v = self._evaluator_version()
-        if v != self._cache_version:
+        if self._weights.moved(self._evaluator_version()):
             e.clear_eval_cache()
-            self._cache_version = v
         return self.evaluator(leaf, plan=e.eval_plan())
+
+    def _evaluate(self, leaf):
+        """``(boundary kind, outputs, value)`` of the pending leaf batch from the evaluator that is current."""
+        if self.planned:   # cache probe + plan, the network on the planned rows only
+            return ("planned", *self._planned_eval(leaf))
+        return (kind_of(self.evaluator), *self.evaluator(leaf))
 
     # one lockstep simulation of every board (outside advance's move bookkeeping: no playout-cap draw happens here)
     def simulate(self):
-        e = self.engine
-        leaf = e.select_leaves()
-        if self.planned:
-            e.expand_backup_planned(*self._planned_eval(leaf))
-            return
-        prob, value = self.evaluator(leaf)
-        (e.expand_backup_logits if getattr(self.evaluator, "returns_logits", False) else e.expand_backup)(prob, value)
+        deliver(self.engine, *self._evaluate(self.engine.select_leaves()), True)
 
     def advance(self, steps: int, hooks=None, boundary=None, on_playout=None):
         """``steps`` lockstep simulations of every board from wherever the search stands in its move; a move that completes on the
@@ -349,8 +287,8 @@ class BatchedSelfPlay:
         events and triggers the concurrent trainer. THE loop: ``run_move``, the bench, the soak and the tests all run this one."""
         e = self.engine
         n = self.n_playout
-        logits = getattr(self.evaluator, "returns_logits", False)
-        interval = max(1, n // 100)
+        self._ticker.on_playout = on_playout
+        between = None if hooks is None else lambda: hooks("eval1", self._sim)
         moves = None
         for _ in range(int(steps)):
             i = self._sim
@@ -359,6 +297,8 @@ class BatchedSelfPlay:
                 if self.playout_cap is not None and i == 0:   # the move's budgets, after a harvest restarted boards
                     e.draw_budgets(n, *self.playout_cap)
                 self._leaf = e.select_leaves()
+                # (not boundary.may_graph: this front end captures whatever it is given when asked to -- bench.py --graph captures a
+                # stub that is not marked graph_safe, and tests/test_gpu_above_4096_boards.py expects a graph exactly when use_graph)
                 if self.use_graph and self._graph is None and not self.planned:
                     self._graph = GraphedStep(e, self.evaluator, version_fn=self.version_fn)
             if hooks is not None:
@@ -366,33 +306,14 @@ class BatchedSelfPlay:
             if self._graph is not None and not last and hooks is None:
                 self._graph.replay()   # evaluator + fused step as one captured graph (launch-bound small batches)
             else:
-                if self.planned:   # cache probe + plan, the network on the planned rows only, softmax + gather + cache store
-                    e.gather_priors_planned(*self._planned_eval(self._leaf))
-                    value = None   # step / expand_backup then use the engine-owned leaf values (hits and fresh evaluations alike)
-                else:
-                    prob, value = self.evaluator(self._leaf)
-                    if logits:     # the softmax + gather of the legal priors belongs to the evaluator side of the split
-                        e.gather_priors(prob, value)
-                if hooks is not None:
-                    hooks("eval1", i)
-                if last:
-                    e.expand_backup_compact(value) if (logits or self.planned) else e.expand_backup(prob, value)
-                    self._leaf = None
-                else:
-                    self._leaf = e.step_compact(value) if (logits or self.planned) else e.step(prob, value)
+                self._leaf = deliver(e, *self._evaluate(self._leaf), last, between)
             if hooks is not None:
                 hooks("step1", i)
             self._sim = 0 if last else i + 1
-            self._acc += 1
-            if on_playout is not None and (self._acc >= interval or last):
-                try:
-                    on_playout(self._acc)  # mcts.py:153-160
-                except Exception:
-                    pass
-                self._acc = 0
+            self._ticker.tick(1, last)
             if last:
-                self._acc = 0
                 moves = boundary() if boundary is not None else self.finish_move()
+        self._ticker.on_playout = None   # (the caller's callback is not kept past the call: it may refer to this object)
         return moves
 
     def search(self, on_playout=None, hooks=None):
@@ -425,7 +346,7 @@ class BatchedSelfPlay:
                             + (" - game over" if st["over"][b] else ""))
 
     def finish_move(self):
-        self._sim, self._leaf, self._acc = 0, None, 0   # whatever leaf was pending belongs to the old root
+        self._sim, self._leaf, self._ticker.acc = 0, None, 0   # whatever leaf was pending belongs to the old root
         moves = self._finish_move()
         if getattr(self, "_watch", None) is not None:
             self._show(moves)

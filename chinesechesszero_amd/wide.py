@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import torch
 
+from .boundary import WeightsWatch, capture, describe, may_graph, need_version
 from .engine import SelfPlayEngine
 from .parameters import ALPHA, C_PUCT, EPS
 
@@ -32,43 +33,34 @@ class WideSearch:
 
     def __init__(self, evaluator, n_positions: int, width: int, n_playout: int = 400, c_puct: float = C_PUCT, device: int = 0, seed: int = 0,
                  use_graph: bool = False, version_fn=None, warmup: int = 3, planned: bool | None = None, **engine_kw):
-        ev = getattr(evaluator, "evaluate_leaves_logits", evaluator)
-        if not callable(ev) or not getattr(ev, "returns_logits", False):
+        ev = describe(evaluator, version_fn)
+        if not callable(ev.fn) or not ev.returns_logits:
             raise ValueError("WideSearch: the evaluator must be batched and return logits (returns_logits; PolicyValueNet.evaluate_leaves_logits)")
         if int(n_positions) < 1 or not 2 <= int(width) <= 64 or int(n_playout) < 1:
             raise ValueError("WideSearch: n_positions and n_playout must be >= 1 and width in 2..64 (width 1 is the sequential search)")
-        self.evaluator = ev
+        self.evaluator = ev.fn
         self.A, self.width, self.n_playout = int(n_positions), int(width), int(n_playout)
         engine_kw.setdefault("eps", EPS)
         engine_kw.setdefault("alpha", ALPHA)
         self.engine = SelfPlayEngine(self.A * self.width, n_playout=self.n_playout, c_puct=c_puct, device=device, seed=seed, **engine_kw)
         self.engine.set_width(self.width)
-        can_plan = bool(self.engine.eval_cache_log2 > 0 and getattr(ev, "accepts_plan", False))
+        can_plan = bool(self.engine.eval_cache_log2 > 0 and ev.accepts_plan)
         if planned and not can_plan:
             raise ValueError("WideSearch: planned=True needs eval_cache_log2 > 0 and an evaluator that accepts a plan")
         self.planned = can_plan and (self.engine.B >= self.PLAN_MIN_SLOTS if planned is None else bool(planned))
-        self.version_fn = version_fn
-        if self.planned and version_fn is None and not hasattr(getattr(ev, "__self__", None), "weights_version") and not getattr(ev, "stateless", False):
-            raise ValueError("WideSearch: planned boundary (evaluation cache) with an evaluator that exposes no weights_version: pass "
-                             "version_fn=..., mark it `stateless = True`, or use eval_cache_log2=0")
-        self._version = self._evaluator_version()
-        self.use_graph = bool(use_graph and getattr(ev, "graph_safe", False))
+        if self.planned:
+            need_version(ev, "WideSearch: ", planned=True)
+        self._version, self._weights = ev.version, WeightsWatch(ev.version())
+        self.use_graph = may_graph(use_graph, ev, self.engine.device)
         self.warmup = int(warmup)
         self._graph = None
         self._budgets = torch.zeros((self.engine.B,), dtype=torch.int32, device=self.engine.device)
         self._done = 0              # simulations every board has been given since its last move boundary
         self.steps = self.evaluator_calls = 0
 
-    def _evaluator_version(self):
-        if self.version_fn is not None:
-            return self.version_fn()
-        return getattr(getattr(self.evaluator, "__self__", None), "weights_version", None)
-
     def _check_weights(self):
-        v = self._evaluator_version()
-        if v != self._version:      # cached evaluations (and captured addresses) of other weights must not reach the tree
+        if self._weights.moved(self._version()):     # cached evaluations (and captured addresses) of other weights must not reach the tree
             self.engine.clear_eval_cache()
-            self._version = v
             self._graph = None
 
     def _iteration(self):
@@ -86,21 +78,10 @@ class WideSearch:
     def _replay(self):
         if self._graph is None:
             e = self.engine
-            dev = e.device
-            side = torch.cuda.Stream(device=dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):
-                # allocator / inference-copy warm-up outside the capture, in the form the capture uses (a plan of all rows: the
-                # engine's own plan is not touched); results discarded
-                plan = (torch.arange(e.B, dtype=torch.int32, device=dev), torch.full((1,), e.B, dtype=torch.int32, device=dev))
-                for _ in range(self.warmup):
-                    self.evaluator(e.leaf_input, plan=plan) if self.planned else self.evaluator(e.leaf_input)
-            torch.cuda.current_stream(dev).wait_stream(side)
-            torch.cuda.synchronize(dev)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._iteration()
-            self._graph = g
+            # warm-up in the form the capture uses (a plan of all rows: the engine's own plan is not touched)
+            plan = (torch.arange(e.B, dtype=torch.int32, device=e.device), torch.full((1,), e.B, dtype=torch.int32, device=e.device))
+            warm = (lambda: self.evaluator(e.leaf_input, plan=plan)) if self.planned else (lambda: self.evaluator(e.leaf_input))
+            self._graph = capture(e.device, self._iteration, warm=warm, warmup=self.warmup)
         self._graph.replay()
 
     # ------------------------------------------------------------------ the search

@@ -10,7 +10,9 @@ analyse: BatchedAnalysis of 16 and of 64 positions x 400 simulations: width 1 ag
 steps:   time per launch of ccz_step_wide (widths 8 and 16) against ccz_step_compact at A = 1 and 16 searched boards, device events
          around 100 launches of (ccz_gather_priors + the step) on constant logits; the environment variable CCZ_WIDE_TAIL_WAVES=1
          makes one wave do everything (run the part once with and once without it to compare the two kernel shapes).
-The net is the full-size tower with random weights: speed does not depend on the weights, playing strength is not measured here.
+The net is the full-size tower with random weights drawn from ``--seed``: playing strength is not measured here, but the tree -- and
+with it the scouted search's table hit rate, 20 to 49 evaluator calls per 200 simulations from one unseeded process to the next -- does
+depend on the weights, so runs are comparable only under one seed.
 """
 from __future__ import annotations
 
@@ -153,11 +155,13 @@ def main():
     ap.add_argument("--part", choices=("game", "analyse", "steps"), required=True)
     ap.add_argument("--out", default=None)
     ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--seed", type=int, default=0, help="torch seed of the net's random weights")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         print("wide_search_bench: no GPU; nothing is measured without one", file=sys.stderr)
         return 1
-    res = {"part": args.part, "device": torch.cuda.get_device_name(0),
+    torch.manual_seed(args.seed)
+    res = {"part": args.part, "seed": args.seed, "device": torch.cuda.get_device_name(0),
            **{"game": part_game, "analyse": part_analyse, "steps": part_steps}[args.part](args.repeats)}
     text = json.dumps(res, indent=1)
     print(text)

@@ -220,3 +220,91 @@ def test_model_hot_reload_changes_the_evaluator_eager_and_graphed():
         sp.run_move()
     assert same_trees() and graphed._graph.captures == 3
     graphed.engine.check_healthy()
+
+
+def _two_nets():
+    """Two 256-wide nets (the hand-written evaluator and its fused logits path) that search different trees."""
+    from chinesechesszero_amd.net import PolicyValueNet
+    nets = []
+    for seed in (1, 2):
+        torch.manual_seed(seed)
+        pvn = PolicyValueNet(device="cuda:0", num_channels=256, resblocks_num=2)
+        for m in pvn.policy_value_net.modules():
+            if isinstance(m, torch.nn.BatchNorm2d):
+                m.running_mean.normal_(0, 0.1)
+                m.running_var.uniform_(0.5, 1.5)
+        nets.append(pvn)
+    return nets
+
+
+def _reload(a, b):
+    """The trainer's rank publishes new weights (as in the test above): ``a`` becomes ``b``."""
+    from chinesechesszero_amd.replay import broadcast_model
+    v0 = a.weights_version
+    a.policy_value_net.load_state_dict(b.policy_value_net.state_dict())
+    broadcast_model(a, src=0)
+    assert a.weights_version > v0
+
+
+def _same_root(r1, r2, boards=1):
+    return all(np.array_equal(r1["k"][:boards], r2["k"][:boards]) and np.array_equal(r1[key][:boards], r2[key][:boards])
+               for key in ("acts", "visits"))
+
+
+@pytest.mark.parametrize("use_graph", [False, True])
+def test_hot_reload_reaches_the_scouted_one_game_search(use_graph):
+    """MCTS_AI with scout slots keeps an evaluation table (and, graphed, the addresses of the inference copy) across moves: after
+    a reload the next search must be the search of a player built on the new weights -- no table entry of the old ones, no
+    replay against the old copy."""
+    from chinesechesszero_amd.game import Board
+    from chinesechesszero_amd.mcts import MCTS_AI
+    a, b = _two_nets()
+    n = 48
+
+    def player(pvn):
+        ai = MCTS_AI(pvn.policy_value_fn, n_playout=n, scouts=10)
+        ai.mcts.use_graph = use_graph
+        return ai
+
+    def root(ai):
+        ai.mcts.get_move_probs(Board())
+        rc = ai.mcts._engine.root_children()
+        ai.mcts._engine.check_healthy()
+        return {k: v.copy() for k, v in rc.items()}
+
+    ai = player(a)
+    old = root(ai)
+    assert ai.mcts.scouts == 10 and ai.mcts._scouted.use_graph == use_graph and int(old["root_visits"][0]) == n
+    _reload(a, b)
+    ai.mcts.update_with_move(-1)            # a fresh root: the same position is searched again
+    got, want = root(ai), root(player(b))
+    assert _same_root(got, want) and int(got["root_visits"][0]) == n
+    assert not _same_root(old, want)        # (the two nets do search different trees: the comparison can fail)
+
+
+@pytest.mark.parametrize("planned", [False, True])
+@pytest.mark.parametrize("use_graph", [False, True])
+def test_hot_reload_reaches_the_wide_search(use_graph, planned):
+    from chinesechesszero_amd.wide import WideSearch
+    a, b = _two_nets()
+
+    def wide(pvn):
+        ws = WideSearch(pvn, 2, 4, n_playout=48, eval_cache_log2=12, use_graph=use_graph, planned=planned)
+        assert ws.use_graph == use_graph and ws.planned == planned
+        return ws
+
+    def root(ws):
+        ws.search()
+        rc = ws.engine.root_children()
+        ws.engine.check_healthy()
+        return {k: v.copy() for k, v in rc.items()}
+
+    ws = wide(a)
+    old = root(ws)
+    assert (old["root_visits"][:2] == 48).all()
+    _reload(a, b)
+    ws.engine.reset_tree()                  # fresh roots: the same positions are searched again
+    ws.boundary()
+    got, want = root(ws), root(wide(b))
+    assert _same_root(got, want, 2) and (got["root_visits"][:2] == 48).all()
+    assert not _same_root(old, want, 2)
