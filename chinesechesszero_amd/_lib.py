@@ -97,6 +97,15 @@ class SearchCfg(C.Structure):
                 ("fpu_value", C.c_double), ("fpu_root_value", C.c_double), ("c_base", C.c_double), ("c_factor", C.c_double)]
 
 
+class EarlyStopCfg(C.Structure):
+    _fields_ = [("enabled", C.c_int32), ("single_reply", C.c_int32), ("kld_interval", C.c_int32), ("min_sims", C.c_int32),
+                ("n_sims", C.c_int32), ("reserved", C.c_int32), ("gap_factor", C.c_double), ("min_gain", C.c_double)]
+
+
+class EarlyStopStats(C.Structure):
+    _fields_ = [("stops", C.c_int64 * 4), ("sims_saved", C.c_int64), ("evaluations", C.c_int64)]
+
+
 class WideStats(C.Structure):
     _fields_ = [("steps", C.c_int64), ("leaves", C.c_int64), ("collisions", C.c_int64), ("inflight_now", C.c_int64)]
 
@@ -151,6 +160,11 @@ PROTOTYPES = {
     "ccz_gumbel_sequence": (C.c_int, [_P, C.c_int32, C.c_int32, _P]),
     "ccz_set_search": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_double, C.c_double, C.c_double]),
     "ccz_get_search": (C.c_int, [_P, _P, C.POINTER(SearchCfg)]),
+    "ccz_set_early_stop": (C.c_int, [_P, _P, C.POINTER(EarlyStopCfg)]),
+    "ccz_get_early_stop": (C.c_int, [_P, _P, C.POINTER(EarlyStopCfg)]),
+    "ccz_get_early_stop_stats": (C.c_int, [_P, _P, C.POINTER(EarlyStopStats)]),
+    "ccz_early_stop_status": (C.c_int, [_P, _P, _P, _P]),
+    "ccz_searching": (C.c_int, [_P, _P, C.POINTER(C.c_int32)]),
     "ccz_set_solver": (C.c_int, [_P, _P, C.c_int32]),
     "ccz_root_proof": (C.c_int, [_P, _P, _P, _P, _P, _P]),
     "ccz_get_solver_stats": (C.c_int, [_P, _P, C.POINTER(SolverStats)]),

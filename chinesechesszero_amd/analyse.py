@@ -25,6 +25,7 @@ from ._lib import CczError
 from .boundary import describe
 from .game import Board
 from .searchcfg import add_search_args, mean_leaf_depth, search_from_args
+from .stopcfg import add_early_stop_args, early_stop_from_args
 
 
 def cp_of(q: float, visits: int) -> int:
@@ -85,12 +86,14 @@ class BatchedAnalysis:
     across chunks and cleared only when the evaluator's weights version changes."""
 
     def __init__(self, evaluator, n_boards: int, n_playout: int = 400, multipv: int = 1, max_len: int = 32, solver: bool = False, search=None,
-                 width: int = 1, **engine_kw):
+                 width: int = 1, early_stop=None, **engine_kw):
         """``width`` > 1: every position gathers up to ``width`` leaves of its tree per step, kept apart by virtual loss
         (``wide.WideSearch``: an engine of ``n_boards * width`` slots) -- for a handful of positions, where the sequential search
         runs at the evaluator's latency; another tree than the sequential one; excludes ``solver`` and ``search``.
         ``search``: a dict of ``SelfPlayEngine.set_search``'s arguments (first-play urgency, visit-scaled c_puct); None: the
-        reference's PUCT."""
+        reference's PUCT. ``early_stop``: a dict of ``SelfPlayEngine.set_early_stop``'s arguments (``stopcfg.make_early_stop``): a
+        position stops being searched when its best move can no longer change, and a chunk's loop ends when
+        ``engine.searching()``, asked every 16 steps, is 0; excludes ``width`` > 1. None: off."""
         from .selfplay import BatchedSelfPlay
         desc = describe(evaluator)
         ev = desc.fn
@@ -108,8 +111,8 @@ class BatchedAnalysis:
         self.seconds = 0.0
         self._rows = None   # evaluator rows, summed on the device (planned boundary: the plan's count per step)
         if self.width != 1:
-            if solver or search is not None:
-                raise ValueError("BatchedAnalysis: width > 1 excludes the solver and the search parameters")
+            if solver or search is not None or early_stop is not None:
+                raise ValueError("BatchedAnalysis: width > 1 excludes the solver, the search parameters and the early stop")
             from .wide import WideSearch
             if engine_kw["eval_cache_log2"] == 0 and desc.accepts_plan:
                 engine_kw["eval_cache_log2"] = 16   # slots of one tree reach one position often: they share an evaluator row
@@ -119,7 +122,7 @@ class BatchedAnalysis:
             self.engine = self.wide.engine
             self.solver = False
             return
-        self.sp = BatchedSelfPlay(ev, int(n_boards), n_playout=int(n_playout), eps=0.0, search=search, **engine_kw)   # no GPU: CczError
+        self.sp = BatchedSelfPlay(ev, int(n_boards), n_playout=int(n_playout), eps=0.0, search=search, early_stop=early_stop, **engine_kw)   # no GPU: CczError
         self.engine = self.sp.engine
         self.solver = bool(solver)     # the MCTS-solver: records gain "mate", bestmove follows the proof (make_record)
         if self.solver:
@@ -164,7 +167,7 @@ class BatchedAnalysis:
                 if not st["over"][:n].all():
                     self.steps += self.wide.search()
             elif not st["over"][:n].all():
-                sp.search(hooks=self._count_rows)
+                sp.search(hooks=self._count_rows, poll=True)
             pv = e.principal_variations(self.multipv, self.max_len)
             e.check_healthy()
             rp, rc = (e.root_proof(), e.root_children()) if self.solver else (None, None)
@@ -213,6 +216,8 @@ class BatchedAnalysis:
                "sims_per_s": round(self.sims / sec, 1), "evaluator_rows_per_step": round(rows / max(1, self.steps), 2)}
         if self.sp.search_cfg is not None:      # the settings as the kernels read them, and how deep the leaves lay
             out.update(search=self.engine.search_settings(), mean_leaf_depth=round(mean_leaf_depth(self.engine.stats()), 3))
+        if self.sp.early_stop is not None:      # stops per reason, and what a position cost on average
+            out["early_stop"] = dict(self.sp.stop_report(), mean_sims_per_position=round(self.sims / max(1, self.positions), 3))
         return out
 
 
@@ -229,8 +234,10 @@ def main(argv=None) -> int:
     ap.add_argument("--width", type=int, default=1, help="leaves per position and evaluator call (virtual loss); 1: the sequential search")
     ap.add_argument("--solver", action="store_true", help="MCTS-solver: prove decided positions in the tree; every record gains \"mate\": N or null")
     add_search_args(ap)
+    add_early_stop_args(ap)
     args = ap.parse_args(argv)
     search = search_from_args(ap, args)
+    early_stop = early_stop_from_args(ap, args)
     with open(args.file, encoding="utf-8") as f:
         try:
             parsed = parse_positions(f)
@@ -245,7 +252,8 @@ def main(argv=None) -> int:
     try:
         pvn = PolicyValueNet(model=args.weights, device="cuda:0")
         an = BatchedAnalysis(pvn, max(1, min(args.boards, len(parsed) or 1)), n_playout=args.playout, multipv=args.multipv,
-                             max_len=args.max_len, solver=args.solver, search=search, width=args.width)
+                             max_len=args.max_len, solver=args.solver, search=search, width=args.width,
+                             early_stop=early_stop)
         records = an.analyse([b for _, b in parsed])
     except CczError as e:
         print(f"analyse: {e}", file=sys.stderr)

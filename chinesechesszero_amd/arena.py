@@ -24,6 +24,7 @@ import numpy as np
 from .boundary import WeightsWatch, describe
 from .parameters import C_PUCT
 from .searchcfg import add_search_args, mean_leaf_depth, search_from_args
+from .stopcfg import StopPoll, add_early_stop_args, early_stop_from_args, stop_report
 
 _RESIGNED = 2   # _lib.RESIGN_RESIGNED (this module imports the engine lazily: its statistics run without a GPU)
 PROMOTE_THRESHOLD = 0.55   # AlphaGo Zero's gate, kept by the AlphaZero_Gomoku lineage the reference cites
@@ -174,11 +175,13 @@ class Arena:
     is a win for the other side like any other, counted in ``result()["resigned"]``; no game is played on (``p_playon`` = 0).
     None (default): games end by the rules or the ply cap only. ``solver``: both sides search with the MCTS-solver
     (``engine.set_solver``) and play the proven move where the root is decided (``engine.proof_moves``). ``search``: a dict of
-    ``engine.set_search``'s arguments (first-play urgency, visit-scaled c_puct), for both sides alike; None: the reference's PUCT."""
+    ``engine.set_search``'s arguments (first-play urgency, visit-scaled c_puct), for both sides alike; None: the reference's PUCT. ``early_stop``: a dict of
+    ``engine.set_early_stop``'s arguments (``stopcfg.make_early_stop``): a board stops searching its move when the outcome can no longer
+    change; the move's loop asks ``engine.searching()`` every 16 steps and ends when no board would select any more. None: off."""
 
     def __init__(self, net_a, net_b, n_pairs: int, n_playout: int = 400, opening_plies: int = 6, seed: int = 0,
                  max_plies: int = 0, c_puct: float = C_PUCT, eval_cache_log2: int = 22, device: int = 0,
-                 cache_verify: bool = False, n_playout_b: int | None = None, resign=None, solver: bool = False, search=None):
+                 cache_verify: bool = False, n_playout_b: int | None = None, resign=None, solver: bool = False, search=None, early_stop=None):
         from .engine import SelfPlayEngine
         self.nets = (net_a, net_b)
         described = (_as_evaluator(net_a, "A"), _as_evaluator(net_b, "B"))
@@ -209,6 +212,10 @@ class Arena:
         self.search_cfg = None if search is None else dict(search)
         if self.search_cfg is not None:
             e.set_search(**self.search_cfg)
+        self.early_stop = None if early_stop is None else dict(early_stop)
+        if self.early_stop is not None:
+            e.set_early_stop(**self.early_stop)
+        self._poll = StopPoll(e, self.early_stop)
         self.resign = None
         if resign is not None:
             self.resign = dict(resign) if isinstance(resign, dict) else {"threshold": float(resign)}
@@ -246,6 +253,8 @@ class Arena:
             e.set_budgets(self.move_budgets())
         leaf = e.select_leaves()
         for i in range(self.n_steps):
+            if self._poll.done(i):               # no board would select any more: no leaf is pending either
+                break
             p0, p1 = e.eval_plan_routed()
             self._rows += e.n_miss2
             if on_step is not None:
@@ -333,6 +342,8 @@ class Arena:
         if self.search_cfg is not None:
             out["search"] = self.engine.search_settings()
             out["mean_leaf_depth"] = mean_leaf_depth(s)
+        if self.early_stop is not None:
+            out["early_stop"] = stop_report(self.engine.early_stop_stats(), s["moves"], s["sims"])
         out["cache"] = {k: s[k] for k in ("cache_probes", "cache_hits", "cache_shared_rows", "cache_stores",
                                            "cache_verified", "cache_verify_mismatches")}
         return out
@@ -378,8 +389,10 @@ def main(argv=None) -> int:
     ap.add_argument("--solver", action="store_true", help="MCTS-solver on both sides: decided positions are proven in the tree and the proven move is played")
     ap.add_argument("--resign-min-ply", type=int, default=None, help="... and not before this ply (default 30)")
     add_search_args(ap)
+    add_early_stop_args(ap)
     a = ap.parse_args(argv)
     search = search_from_args(ap, a)
+    early_stop = early_stop_from_args(ap, a)
     if a.resign_threshold is None and (a.resign_moves is not None or a.resign_min_ply is not None):
         ap.error("--resign-moves / --resign-min-ply need --resign-threshold")
     resign = None
@@ -389,7 +402,8 @@ def main(argv=None) -> int:
     na = _load(a.a, a.channels, a.blocks, a.device)
     nb = _load(a.b, a.channels, a.blocks, a.device)
     arena = Arena(na, nb, a.pairs, n_playout=a.playout, opening_plies=a.opening_plies, seed=a.seed, max_plies=a.max_plies,
-                  eval_cache_log2=a.eval_cache_log2, device=a.device, n_playout_b=a.playout_b, resign=resign, solver=a.solver, search=search)
+                  eval_cache_log2=a.eval_cache_log2, device=a.device, n_playout_b=a.playout_b, resign=resign, solver=a.solver, search=search,
+                  early_stop=early_stop)
     r = arena.play()
     r.update({"a": a.a, "b": a.b, "opening_plies": a.opening_plies, "seed": a.seed, "net": f"{a.blocks}x{a.channels}",
               "promote": promote(r, a.threshold), "threshold": a.threshold})

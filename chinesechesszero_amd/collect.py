@@ -31,6 +31,7 @@ from .mcts import MCTS_AI
 from .net import PolicyValueNet
 from .parameters import BATCH_SIZE, C_PUCT, DATA_DIR, MODEL_DIR, PLAYOUT
 from .searchcfg import add_search_args, mean_leaf_depth, search_from_args
+from .stopcfg import add_early_stop_args, early_stop_from_args
 from .tools import flip_map, log
 
 
@@ -509,7 +510,14 @@ class CollectPipeline:
                  finalize_every: int = 0, on_playout=None, max_plies: int = 0, eval_cache_log2: int | None = None, gatherer=None,
                  dense_shards: bool = False, replay_plies: int = 0, train_every: int = 0, train_batch: int = BATCH_SIZE,
                  playout_cap_fast: int = 0, playout_cap_prob: float | None = None, resign=None, value_q_weight: float = 0.0,
-                 root_exploration=None, solver: bool = False, gumbel=None, search=None):
+                 root_exploration=None, solver: bool = False, gumbel=None, search=None, early_stop=None):
+        # early stop per board (``early_stop``: a dict of SelfPlayEngine.set_early_stop's arguments; None = off), on the batched path: a
+        # board stops searching its move early and selects nothing for the rest of the move's ``n_playout`` steps
+        self.early_stop = None if early_stop is None else dict(early_stop)
+        if self.early_stop is not None and n_boards <= 1:
+            raise ValueError("the early stop of the collector runs on the batched path: n_boards must be > 1")
+        if self.early_stop is not None and gumbel is not None and gumbel is not False:
+            raise ValueError("the early stop and the Gumbel root search exclude each other: sequential halving plans the whole budget")
         # search parameters (``search``: a dict of SelfPlayEngine.set_search's arguments; None = the reference's PUCT): first-play
         # urgency and the visit-scaled c_puct, on the batched path and in the one-game loop (which then runs without scout slots)
         self.search = None if search is None else dict(search)
@@ -699,7 +707,8 @@ class CollectPipeline:
                                             device=self.device, reference_quirks=self.reference_quirks, max_plies=self.max_plies,
                                             playout_cap=self.playout_cap, resign=getattr(self, "resign", None),
                                             root_exploration=getattr(self, "root_exploration", None), solver=getattr(self, "solver", False),
-                                            gumbel=getattr(self, "gumbel", None), search=getattr(self, "search", None))
+                                            gumbel=getattr(self, "gumbel", None), search=getattr(self, "search", None),
+                                            early_stop=getattr(self, "early_stop", None))
             if getattr(self, "_viewer", None) is not None:
                 self.selfplay.watch(0, self._viewer)
         for _ in range(n_moves):
@@ -900,6 +909,14 @@ class CollectPipeline:
         e = self.selfplay.engine
         return format_exploration(e.exploration_stats(), e.stats()["sims"])
 
+    def stop_report(self) -> str:
+        """The early-stop part of the periodic log line (empty with the feature off; syncs)."""
+        if getattr(self, "early_stop", None) is None or getattr(self, "selfplay", None) is None:
+            return ""
+        r = self.selfplay.stop_report()
+        return (f", early stops {r['single_reply']} single reply / {r['visit_gap']} gap / {r['kld_gain']} kld, "
+                f"{r['mean_sims_per_move']} simulations per move")
+
     def search_report(self) -> str:
         """The search-parameter part of the periodic log line (empty with the rule off; syncs)."""
         if getattr(self, "search", None) is None or getattr(self, "selfplay", None) is None:
@@ -947,7 +964,7 @@ class CollectPipeline:
                 while max_calls <= 0 or calls < max_calls:
                     iters = self.collect_data(is_shown=is_shown)
                     calls += 1
-                    log(f"Episode {iters}, steps {self.episode_len}" + self.resign_report() + self.exploration_report() + self.gumbel_report() + self.solver_report() + self.search_report())
+                    log(f"Episode {iters}, steps {self.episode_len}" + self.resign_report() + self.exploration_report() + self.gumbel_report() + self.solver_report() + self.search_report() + self.stop_report())
             except KeyboardInterrupt:
                 log("Exit")
             if self.gatherer is not None and hasattr(self.gatherer, "flush_iter") and self.selfplay is not None:
@@ -1040,6 +1057,7 @@ def build_parser():
     parser.add_argument("--solver", action="store_true", default=False, help="batched path: search with the MCTS-solver (decided positions are proven "
                         "in the tree and cost no evaluator row); sampling, records and targets are as without it")
     add_search_args(parser)
+    add_early_stop_args(parser)
     parser.add_argument("--value-q-weight", type=float, default=0.0, help="with --train-every: weight of the recorded root value q in the value "
                         "target, (1 - w) z + w q on rows that carry one (0 = z alone)")
     return parser
@@ -1111,6 +1129,11 @@ def parse_args(argv=None):
                            "c_visit": GUMBEL_C_VISIT if args.gumbel_c_visit is None else args.gumbel_c_visit,
                            "c_scale": GUMBEL_C_SCALE if args.gumbel_c_scale is None else args.gumbel_c_scale}
     args.search = search_from_args(parser, args)
+    args.early_stop = early_stop_from_args(parser, args)
+    if args.early_stop is not None and args.gumbel:
+        parser.error("--stop-* and --gumbel exclude each other: sequential halving plans the whole budget")
+    if args.early_stop is not None and args.boards <= 1:
+        parser.error("--stop-* run on the batched path: --boards must be > 1")
     return args
 
 
@@ -1143,7 +1166,8 @@ if __name__ == "__main__":
                            eval_cache_log2=args.eval_cache_log2, gatherer=gatherer, replay_plies=args.replay_plies,
                            train_every=args.train_every, train_batch=args.train_batch, playout_cap_fast=args.playout_cap_fast,
                            playout_cap_prob=args.playout_cap_prob, resign=args.resign, value_q_weight=args.value_q_weight,
-                           root_exploration=args.root_exploration, solver=args.solver, gumbel=args.gumbel_cfg, search=args.search)
+                           root_exploration=args.root_exploration, solver=args.solver, gumbel=args.gumbel_cfg, search=args.search,
+                           early_stop=args.early_stop)
     if world > 1:
         from .launch import guarded
 

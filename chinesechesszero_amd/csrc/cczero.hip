@@ -85,6 +85,8 @@ struct ccz_engine {
     bool budgets_on = false;       // ccz_set_budgets / ccz_draw_budgets (off: every budget INT32_MAX, every target 1)
     bool explore_on = false;       // ccz_set_root_exploration(enabled): the host's shadow of ExploreCfg.enabled (scouts are refused with it)
     bool search_on = false;        // ccz_set_search(enabled): the host's shadow of SearchCfg.enabled (scouts are refused with it)
+    bool stop_on = false;          // ccz_set_early_stop(enabled): the host's shadow of StopCfg.enabled (scouts, a width above 1 and the Gumbel root are refused with it)
+    int32_t *st_count = nullptr;   // ccz_searching: the count on the device
     bool gumbel_on = false;        // ccz_set_gumbel(enabled): the host's shadow of GumbelCfg.enabled (scouts and root exploration are refused with it)
     // MCTS-solver (ccz_set_solver): the proof bytes [B][2][cap] (allocated by the first call that turns it on), the host's shadow of
     // SolverCfg.enabled, staging of ccz_root_proof (state [B], dist [B], child state [B][128], child dist [B][128])
@@ -346,6 +348,14 @@ int ccz_create(const ccz_config *cfg, ccz_engine **out)
         const SearchCfg off = search_defaults();
         if (he == hipSuccess) he = hipMemcpy(sr_cfg, &off, sizeof off, hipMemcpyHostToDevice);
     }
+    StopCfg *es_cfg = nullptr;
+    ALLOC(es_cfg, 1); // zeroed: early stop off
+    d.es_cfg = es_cfg;
+    ALLOC(d.es_stopped, B);
+    ALLOC(d.es_snap_s, B); // (k_reset below writes the -1 of "no snapshot")
+    ALLOC(d.es_snap, B * kMaxLegal);
+    ALLOC(d.es_stats, B);
+    ALLOC(e->st_count, 4);
     ALLOC(d.rec_ids, B * d.pi_cap);
     ALLOC(d.rec_pi, B * d.pi_cap);
     ALLOC(d.stats, B);
@@ -560,6 +570,7 @@ int ccz_set_scouts(ccz_engine *e, int32_t n_scouts)
     if (n_scouts && e->budgets_on) return fail(-1, "ccz_set_scouts: not while simulation budgets are on (ccz_set_budgets(NULL) turns them off)");
     if (n_scouts && e->explore_on) return fail(-1, "ccz_set_scouts: not while root exploration is on (ccz_set_root_exploration)");
     if (n_scouts && e->gumbel_on) return fail(-1, "ccz_set_scouts: not while the Gumbel root search is on (ccz_set_gumbel)");
+    if (n_scouts && e->stop_on) return fail(-1, "ccz_set_scouts: not while the early stop is on (ccz_set_early_stop)");
     if (n_scouts && e->search_on) return fail(-1, "ccz_set_scouts: not while the search parameters are on (ccz_set_search): scouts rest on children being first visited in legal-move order");
     e->active = n_scouts ? e->d.B - n_scouts : 0;
     return 0;
@@ -823,6 +834,7 @@ int ccz_set_gumbel(ccz_engine *e, void *stream, int32_t enabled, int32_t n_sims,
     if (enabled && WIDE(e)) return fail(-1, "ccz_set_gumbel: not while the width is %d (ccz_set_width): the wide search has the plain PUCT rule only", e->width);
     if (enabled && SCOUTS(e)) return fail(-1, "ccz_set_gumbel: not with scout slots (ccz_set_scouts): the one-game path keeps the reference's search");
     if (enabled && e->explore_on) return fail(-1, "ccz_set_gumbel: not while root exploration is on (ccz_set_root_exploration)");
+    if (enabled && e->stop_on) return fail(-1, "ccz_set_gumbel: not while the early stop is on (ccz_set_early_stop): sequential halving plans the whole budget");
     GumbelCfg v;
     v.enabled = enabled ? 1 : 0;
     v.n_sims = n_sims;
@@ -942,6 +954,99 @@ int ccz_get_search(ccz_engine *e, void *stream, ccz_search_cfg *out)
     out->fpu_root_value = v.fpu_root_value;
     out->c_base = v.c_base;
     out->c_factor = v.c_factor;
+    return 0;
+}
+
+// ---- early stop per board (cczero.h: "Early stop per board")
+int ccz_set_early_stop(ccz_engine *e, void *stream, const ccz_early_stop_cfg *cfg)
+{
+    NEED(e);
+    if (!cfg) return fail(-1, "ccz_set_early_stop: null settings");
+    StopCfg v;
+    memset(&v, 0, sizeof v); // enabled = 0: the other fields are ignored
+    if (cfg->enabled != 0 && cfg->enabled != 1) return fail(-1, "ccz_set_early_stop: enabled %d must be 0 or 1", cfg->enabled);
+    if (cfg->enabled) {
+        if (cfg->single_reply != 0 && cfg->single_reply != 1) return fail(-1, "ccz_set_early_stop: single_reply %d must be 0 or 1", cfg->single_reply);
+        if (cfg->kld_interval < 0) return fail(-1, "ccz_set_early_stop: kld_interval %d must be 0 (off) or >= 1", cfg->kld_interval);
+        if (cfg->min_sims < 0) return fail(-1, "ccz_set_early_stop: negative min_sims %d", cfg->min_sims);
+        if (cfg->n_sims < 1) return fail(-1, "ccz_set_early_stop: n_sims %d must be >= 1", cfg->n_sims);
+        if (cfg->reserved != 0) return fail(-1, "ccz_set_early_stop: reserved %d must be 0", cfg->reserved);
+        if (!(cfg->gap_factor == 0.0 || (cfg->gap_factor >= 1.0 && std::isfinite(cfg->gap_factor))))
+            return fail(-1, "ccz_set_early_stop: gap_factor %g must be 0 (off) or finite and >= 1", cfg->gap_factor);
+        if (!(cfg->min_gain >= 0.0 && std::isfinite(cfg->min_gain))) return fail(-1, "ccz_set_early_stop: min_gain %g must be finite and >= 0", cfg->min_gain);
+        if (SCOUTS(e)) return fail(-1, "ccz_set_early_stop: not with scout slots (ccz_set_scouts): the one-game path keeps the reference's search");
+        if (WIDE(e)) return fail(-1, "ccz_set_early_stop: not while the width is %d (ccz_set_width): the wide search has its own budget test", e->width);
+        if (e->gumbel_on) return fail(-1, "ccz_set_early_stop: not while the Gumbel root search is on (ccz_set_gumbel): sequential halving plans the whole budget");
+        v.enabled = 1;
+        v.single_reply = cfg->single_reply;
+        v.kld_interval = cfg->kld_interval;
+        v.min_sims = cfg->min_sims;
+        v.n_sims = cfg->n_sims;
+        v.gap_factor = cfg->gap_factor;
+        v.min_gain = cfg->min_gain;
+    }
+    const int n = e->d.B;
+    hipLaunchKernelGGL(k_set_early_stop, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, const_cast<StopCfg *>(e->d.es_cfg), v, e->d.es_stopped,
+                       e->d.es_snap_s, n);
+    HIP_TRY(hipGetLastError());
+    e->stop_on = v.enabled != 0;
+    return 0;
+}
+
+int ccz_get_early_stop(ccz_engine *e, void *stream, ccz_early_stop_cfg *out)
+{
+    NEED(e);
+    if (!out) return fail(-1, "ccz_get_early_stop: null output");
+    hipStream_t s = (hipStream_t)stream;
+    StopCfg v;
+    HIP_TRY(hipMemcpyAsync(&v, e->d.es_cfg, sizeof v, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    out->enabled = v.enabled;
+    out->single_reply = v.single_reply;
+    out->kld_interval = v.kld_interval;
+    out->min_sims = v.min_sims;
+    out->n_sims = v.n_sims;
+    out->reserved = 0;
+    out->gap_factor = v.gap_factor;
+    out->min_gain = v.min_gain;
+    return 0;
+}
+
+int ccz_get_early_stop_stats(ccz_engine *e, void *stream, ccz_early_stop_stats *out)
+{
+    NEED(e);
+    if (!out) return fail(-1, "ccz_get_early_stop_stats: null output");
+    std::vector<StopBoardStats> st;
+    if (const int rc = fetch_board_stats(e, (hipStream_t)stream, e->d.es_stats, st)) return rc;
+    memset(out, 0, sizeof *out);
+    for (const StopBoardStats &b : st) {
+        for (int r = 0; r < 4; ++r) out->stops[r] += (int64_t)b.stops[r];
+        out->sims_saved += (int64_t)b.sims_saved;
+        out->evaluations += (int64_t)b.evaluations;
+    }
+    return 0;
+}
+
+int ccz_early_stop_status(ccz_engine *e, void *stream, uint8_t *reason_host, int32_t *sims_host)
+{
+    NEED(e);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t B = (size_t)e->d.B;
+    if (reason_host) HIP_TRY(hipMemcpyAsync(reason_host, e->d.es_stopped, B, hipMemcpyDeviceToHost, s));
+    if (sims_host) HIP_TRY(hipMemcpyAsync(sims_host, e->d.move_sims, B * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return 0;
+}
+
+int ccz_searching(ccz_engine *e, void *stream, int32_t *count_host)
+{
+    NEED(e);
+    if (!count_host) return fail(-1, "ccz_searching: null output");
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_searching, dim3(1), dim3(1024), 0, s, e->d, (int)ACTIVE(e), e->st_count);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(count_host, e->st_count, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
     return 0;
 }
 
@@ -1092,6 +1197,7 @@ int ccz_set_width(ccz_engine *e, void *stream, int32_t width)
         if (e->gumbel_on) return fail(-1, "ccz_set_width: not while the Gumbel root search is on (ccz_set_gumbel)");
         if (e->solver_on) return fail(-1, "ccz_set_width: not while the solver is on (ccz_set_solver)");
         if (e->search_on) return fail(-1, "ccz_set_width: not while the search parameters are on (ccz_set_search)");
+        if (e->stop_on) return fail(-1, "ccz_set_width: not while the early stop is on (ccz_set_early_stop)");
         if (e->routed) return fail(-1, "ccz_set_width: not while routing is on (ccz_set_routing)");
     }
     hipStream_t s = (hipStream_t)stream;

@@ -114,6 +114,23 @@ struct SearchCfg {
     double c_base, c_factor;          // c_eff = c_puct + c_factor * log((N + c_base + 1) / c_base); c_factor 0: c_puct as it is
 };
 
+// Early stop per board (ccz_set_early_stop, rules S1-S5 of include/cczero.h): the settings as the device reads them, and the per-board
+// counters. A stopped board selects nothing for the rest of its move, exactly like one whose budget is spent.
+struct StopCfg {
+    int32_t enabled;      // 0: the selection reads this one word and no board ever stops early
+    int32_t single_reply; // S2: a root with one child stops
+    int32_t kld_interval; // S4: the gain is looked at every so many simulations; 0: off
+    int32_t min_sims;     // S1: no rule runs below this many simulations of the move
+    int32_t n_sims;       // the simulations of a move when the board has no budget
+    int32_t pad;
+    double gap_factor;    // S3: 0 off, else >= 1
+    double min_gain;      // S4: the gain per new visit below which the board stops
+};
+struct StopBoardStats {
+    unsigned long long stops[4]; // by reason (1 single reply, 2 visit gap, 3 KLD gain; [0] unused)
+    unsigned long long sims_saved, evaluations; // sum of n_b - s over the stops; snapshots taken by S4
+};
+
 // MCTS-solver (ccz_set_solver): the settings as the device reads them, and the per-board counters. A proof byte holds the state in
 // bits 0..1 -- the view of the side to move at the node -- and the distance to the end in plies in bits 2..7 (saturating at 63; 0 for a
 // draw). The array lives behind the settings, not in Dev: it is allocated by the first ccz_set_solver(1), and a graph captured before
@@ -227,6 +244,12 @@ struct Dev {
     GumbelBoardStats *gm_stats;  // [B]
     // ---- search parameters (ccz_set_search). Always allocated; "off" is SearchCfg.enabled == 0
     const SearchCfg *sr_cfg;     // [1] written by k_set_search in stream order
+    // ---- early stop per board (ccz_set_early_stop). Always allocated; "off" is StopCfg.enabled == 0
+    const StopCfg *es_cfg;       // [1] written by k_set_early_stop in stream order
+    uint8_t *es_stopped;         // [B] 0, or the reason the board stopped in its current move (cleared wherever move_sims is zeroed)
+    int32_t *es_snap_s;          // [B] simulations of the move when the snapshot was taken; -1: none in this move
+    int32_t *es_snap;            // [B][128] S4: the root children's visit counts at that time (zero past k)
+    StopBoardStats *es_stats;    // [B]
 };
 __device__ __forceinline__ int plane_of(const Dev &D, int type) { return (int)((D.chanpack >> (3 * type)) & 7u); }
 __device__ __forceinline__ int type_in_plane(const Dev &D, int chan) { return (int)((D.typepack >> (3 * chan)) & 7u) + 1; }

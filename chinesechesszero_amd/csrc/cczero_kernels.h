@@ -42,6 +42,8 @@ __device__ __forceinline__ void fresh_root(const Dev &D, int b, int half)
     D.path_len[b] = 0;
     D.leaf_status[b] = CCZ_LEAF_SKIP;
     D.move_sims[b] = 0; // a move boundary: the board's simulation budget (Dev.budget) starts over
+    D.es_stopped[b] = 0; // ... and so does the early stop (S5): not stopped, no snapshot
+    D.es_snap_s[b] = -1;
 }
 
 // A new game carries no resignation state: no run of low values, no play-on lot, no last value (the calibration counters in
@@ -233,7 +235,8 @@ struct Prefetch {
     int32_t ex;        // root exploration (ccz_set_root_exploration) applies to the board's current move: on, and a policy-target move
     int32_t gm;        // Gumbel root search (ccz_set_gumbel) is on
     int32_t sr;        // search parameters (ccz_set_search) are on
-    SolverCfg sv;      // MCTS-solver (ccz_set_solver): on / off and where the proof bytes are
+    int32_t es;        // early stop per board (ccz_set_early_stop) is on
+    SolverCfg sv;     // MCTS-solver (ccz_set_solver): on / off and where the proof bytes are
     uint32_t kidp;     // solver on: lane i: the proof byte of child i of the root (off: 0, nothing is read)
 };
 
@@ -279,6 +282,7 @@ __device__ __forceinline__ Prefetch prefetch_board(const Dev &D, int b, int lane
     P.ex = D.ex_cfg->enabled * (int32_t)D.target[b]; // (both words are requested with the rest: no load waits for the other)
     P.gm = D.gm_cfg->enabled;
     P.sr = D.sr_cfg->enabled;
+    P.es = D.es_cfg->enabled;
     P.sv = solver_cfg(D); // (requested with the rest; off: no load waits for it)
     P.kidp = 0u;
     if (P.sv.enabled) P.kidp = P.sv.proof[base + 1 + lane];
@@ -632,6 +636,78 @@ __device__ __forceinline__ double search_fpu(int mode, double value, float q, do
     return __builtin_huge_val();
 }
 
+// ------------------------------------------------------------------ early stop per board (ccz_set_early_stop, include/cczero.h)
+// S1-S5 at one selection of board b: the reason the board is stopped (one it stopped with earlier in the move, or the rule that
+// fires now: 1 single reply, 2 visit gap, 3 KLD gain), 0: it goes on searching. root / rootw: the root record with this launch's
+// backup patched in. The counts of children 0..63 come from the prefetched records (P.kid + TopPatch), those of children 64..127
+// from memory, where the fence in front of the selection made this launch's backup visible. All 64 lanes call it; everything it
+// branches on is wave-uniform, and the state (Dev.es_*) is written by ordinary stores, the scalars from lane 0.
+__device__ inline int early_stop(const Dev &D, int b, int lane, const Prefetch &P, const TopPatch &tp, const NodeA &root, uint32_t rootw,
+                                 const NodeA *A)
+{
+    const int was = __builtin_amdgcn_readfirstlane((int)D.es_stopped[b]);
+    if (was) return was; // S5: stopped earlier in this move
+    int k = __builtin_amdgcn_readfirstlane((int)(rootw >> 16));
+    if (k < 1) return 0;
+    if (k > kMaxLegal) k = kMaxLegal;
+    const StopCfg sc = *D.es_cfg;
+    const int s = __builtin_amdgcn_readfirstlane(P.move_sims + (tp.active ? 1 : 0));
+    const int n_b = __builtin_amdgcn_readfirstlane(P.budget == 0x7fffffff ? sc.n_sims : P.budget);
+    if (s >= n_b || s < sc.min_sims) return 0; // S1
+    const int fc = __builtin_amdgcn_readfirstlane(root.fc);
+    const bool in0 = lane < k, in1 = 64 + lane < k;
+    int n0 = 0, n1 = 0;
+    if (in0) {
+        if (fc == 1) {
+            n0 = P.kid.N;
+            if (tp.root_expanded) n0 = 0;
+            else if (tp.has1 && 1 + lane == tp.node1) n0 = tp.N1;
+        } else {
+            n0 = A[CCZ_IDX(D, fc + lane, D.cap)].N;
+        }
+    }
+    if (in1) n1 = A[CCZ_IDX(D, fc + 64 + lane, D.cap)].N;
+    int reason = 0;
+    if (sc.single_reply && k == 1) reason = 1; // S2
+    if (!reason && sc.gap_factor != 0.0) {     // S3: the first maximum, then the best of the others (both over children 0..127)
+        const int a0 = in0 ? n0 : -1, a1 = in1 ? n1 : -1;
+        const int N1 = wave_max_i32(a0 > a1 ? a0 : a1);
+        const uint64_t h0 = __ballot(a0 == N1), h1 = __ballot(a1 == N1);
+        const int i1 = h0 ? __ffsll((long long)h0) - 1 : 64 + __ffsll((long long)h1) - 1;
+        const int r0 = (in0 && lane != i1) ? n0 : 0, r1 = (in1 && 64 + lane != i1) ? n1 : 0;
+        const int N2 = wave_max_i32(r0 > r1 ? r0 : r1);
+        if ((double)(N1 - N2) * sc.gap_factor > (double)(n_b - s)) reason = 2;
+    }
+    if (!reason && sc.kld_interval > 0 && s > 0 && s % sc.kld_interval == 0) { // S4
+        int32_t *snap = D.es_snap + (size_t)b * kMaxLegal;
+        const int snap_s = __builtin_amdgcn_readfirstlane(D.es_snap_s[b]);
+        if (s != snap_s) { // (a selection repeated without a backup finds its own snapshot)
+            if (snap_s >= 0) {
+                const int p0 = snap[lane], p1 = snap[64 + lane];
+                const int Sc = __builtin_amdgcn_readlane(wave_incl_scan(n0 + n1, lane), 63);
+                const int Sp = __builtin_amdgcn_readlane(wave_incl_scan(p0 + p1, lane), 63);
+                if (Sc > Sp) {
+                    double t0 = 0.0, t1 = 0.0;
+                    if (p0 > 0) { const double o = (double)p0 / (double)Sp, n = (double)n0 / (double)Sc; t0 = o * det_log(o / n); }
+                    if (p1 > 0) { const double o = (double)p1 / (double)Sp, n = (double)n1 / (double)Sc; t1 = o * det_log(o / n); }
+                    const double G = search_mass(t0, t1) / (double)(Sc - Sp);
+                    if (G < sc.min_gain) reason = 3; // (a NaN does not fire)
+                }
+            }
+            snap[lane] = n0;
+            snap[64 + lane] = n1;
+            if (lane == 0) { D.es_snap_s[b] = s; D.es_stats[b].evaluations += 1; }
+        }
+    }
+    if (reason && lane == 0) { // S5
+        D.es_stopped[b] = (uint8_t)reason;
+        StopBoardStats &st = D.es_stats[b];
+        st.stops[reason] += 1;
+        st.sims_saved += (unsigned long long)(n_b - s);
+    }
+    return reason;
+}
+
 // One wave: PUCT descent from the root of board b, leaf rules, evaluator input. Per tree level there is
 // ONE dependent global load round (the children's 16-B NodeA records + their move/count words); the
 // chosen child's own N / first_child / count are broadcast from the winning lane, not re-read.
@@ -660,6 +736,11 @@ __device__ inline void select_phase(const Dev &D, int b, int lane, uint16_t *lea
         pa.N = tp.rootN;
         pa.Q = tp.rootQ;
         if (tp.root_expanded) { pa.fc = 1; nb = (nb & 0xffffu) | ((uint32_t)tp.k << 16); }
+    }
+    // ---- early stop per board (off: the one prefetched word tested here): a stopped board is a board whose budget is spent
+    if (__builtin_amdgcn_readfirstlane(P.es) && early_stop(D, b, lane, P, tp, pa, nb, A) != 0) {
+        if (lane == 0) D.leaf_status[b] = CCZ_LEAF_SKIP;
+        return;
     }
     if (lane < 24) {
         uint32_t v = P.sqw;
@@ -1987,7 +2068,11 @@ __global__ __launch_bounds__(64) void k_finish_move(Dev D, const int32_t *forced
     BoardMeta m = D.meta[b];
     if (moves_out && lane == 0) moves_out[b] = -1;
     if (m.over) return;
-    if (lane == 0) D.move_sims[b] = 0; // a move boundary for every live board, whether or not it moves below
+    if (lane == 0) { // a move boundary for every live board, whether or not it moves below
+        D.move_sims[b] = 0;
+        D.es_stopped[b] = 0; // (early stop, S5)
+        D.es_snap_s[b] = -1;
+    }
     const RootView rv = root_view(D, b);
     const int k = root_k(rv), nh = rv.half ^ 1; // every board moves to the other pool half (the host flips the word afterwards)
     const size_t baseNew = ((size_t)b * 2 + nh) * (size_t)D.cap;
@@ -2843,6 +2928,35 @@ __global__ void k_set_root_exploration(ExploreCfg *cfg, ExploreCfg v, uint32_t *
 __global__ void k_set_search(SearchCfg *cfg, SearchCfg v)
 {
     if (blockIdx.x == 0 && threadIdx.x == 0) *cfg = v;
+}
+
+// ccz_set_early_stop: the settings reach the device in stream order; every board's stop and snapshot are dropped (the rules may have
+// changed under them), so turning the feature on and off again leaves nothing behind
+__global__ void k_set_early_stop(StopCfg *cfg, StopCfg v, uint8_t *stopped, int32_t *snap_s, int n)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) { stopped[i] = 0; snap_s[i] = -1; }
+    if (i == 0) *cfg = v;
+}
+
+// ccz_searching: how many of the boards 0 .. n - 1 would still select a leaf -- the game running, the budget not spent, not stopped.
+// One workgroup; the count is summed per wave and then over the waves in LDS.
+__global__ __launch_bounds__(1024) void k_searching(Dev D, int n, int32_t *count)
+{
+    __shared__ int s_part[16];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const bool es = D.es_cfg->enabled != 0;
+    int c = 0;
+    for (int b = tid; b < n; b += 1024)
+        c += (!D.meta[b].over && D.move_sims[b] < D.budget[b] && !(es && D.es_stopped[b])) ? 1 : 0;
+    c = __builtin_amdgcn_readlane(wave_incl_scan(c, lane), 63);
+    if (lane == 0) s_part[w] = c;
+    __syncthreads();
+    if (tid == 0) {
+        int t = 0;
+        for (int i = 0; i < 16; ++i) t += s_part[i];
+        *count = t;
+    }
 }
 
 // ------------------------------------------------------------------ MCTS-solver: settings, inspection, the combine rule on its own

@@ -541,6 +541,53 @@ class SelfPlayEngine:
         out["enabled"] = bool(out["enabled"])
         return out
 
+    # ------------------------------------------------------------------ early stop per board (include/cczero.h ccz_set_early_stop)
+    def set_early_stop(self, enabled: bool = True, single_reply: bool = False, gap_factor: float = 0.0, kld_interval: int = 0,
+                       min_gain: float = 0.0, min_sims: int = 0, n_sims: int | None = None):
+        """A board stops searching its move early and from then on selects nothing (``LEAF_SKIP``, no evaluator row), like one whose
+        budget is spent: with one legal reply (``single_reply``), when the most visited root child leads the runner-up by more than
+        the simulations left can make up (``gap_factor`` f >= 1: ``(N1 - N2) * f > n_b - s``; 0 off), or when the KL divergence
+        between the root's visit distributions ``kld_interval`` simulations apart, per new visit, falls below ``min_gain``. No rule
+        runs below ``min_sims`` simulations. ``n_sims``: the simulations of a move on a board without a budget (None: the engine's
+        ``n_playout``). ``enabled`` False or None: off, the state of a new engine. Not with scout slots, a width above 1 or the
+        Gumbel root. No host sync."""
+        c = _lib.EarlyStopCfg()
+        if enabled:
+            c.enabled, c.single_reply, c.kld_interval, c.min_sims = 1, int(single_reply), int(kld_interval), int(min_sims)
+            c.n_sims = self.n_playout if n_sims is None else int(n_sims)
+            c.gap_factor, c.min_gain = float(gap_factor), float(min_gain)
+        check(self.L.ccz_set_early_stop(self.h, self._stream(), C.byref(c)))
+
+    def early_stop_settings(self) -> dict:
+        """The early-stop settings as the kernels read them (``ccz_get_early_stop``; syncs): ``enabled``, ``single_reply``,
+        ``gap_factor``, ``kld_interval``, ``min_gain``, ``min_sims``, ``n_sims``."""
+        c = _lib.EarlyStopCfg()
+        check(self.L.ccz_get_early_stop(self.h, self._stream(), C.byref(c)))
+        return {"enabled": bool(c.enabled), "single_reply": bool(c.single_reply), "gap_factor": c.gap_factor,
+                "kld_interval": c.kld_interval, "min_gain": c.min_gain, "min_sims": c.min_sims, "n_sims": c.n_sims}
+
+    def early_stop_stats(self) -> dict:
+        """Sums over boards (``ccz_get_early_stop_stats``; syncs): ``single_reply`` / ``visit_gap`` / ``kld_gain`` (stops by
+        reason), ``sims_saved`` (simulations the stopped boards had left) and ``evaluations`` (KLD snapshots taken)."""
+        s = _lib.EarlyStopStats()
+        check(self.L.ccz_get_early_stop_stats(self.h, self._stream(), C.byref(s)))
+        return {"single_reply": int(s.stops[1]), "visit_gap": int(s.stops[2]), "kld_gain": int(s.stops[3]),
+                "sims_saved": int(s.sims_saved), "evaluations": int(s.evaluations)}
+
+    def early_stop_status(self) -> dict:
+        """Per board (``ccz_early_stop_status``; syncs): ``reason`` uint8 [B] (0: not stopped in its current move, 1 single reply,
+        2 visit gap, 3 KLD gain) and ``sims`` int32 [B], the simulations its current move has backed up."""
+        out = {"reason": np.zeros(self.B, np.uint8), "sims": np.zeros(self.B, np.int32)}
+        check(self.L.ccz_early_stop_status(self.h, self._stream(), _ptr(out["reason"]), _ptr(out["sims"])))
+        return out
+
+    def searching(self) -> int:
+        """How many searched boards would still select a leaf (``ccz_searching``; one small kernel and a 4-byte copy; syncs): the
+        game running, the budget not spent, not stopped. 0: the rest of the move's steps would do nothing."""
+        n = C.c_int32(0)
+        check(self.L.ccz_searching(self.h, self._stream(), C.byref(n)))
+        return int(n.value)
+
     # ------------------------------------------------------------------ MCTS-solver (include/cczero.h ccz_set_solver)
     def set_solver(self, enabled: bool = True):
         """Exact propagation of decided positions (Winands' MCTS-solver): a terminal leaf proves its node, a node with a lost child

@@ -18,8 +18,10 @@ from .parameters import C_PUCT
 
 class BatchedMatch:
     def __init__(self, evaluator_red, evaluator_black, n_boards: int, n_playout: int = 400, c_puct: float = C_PUCT,
-                 seed: int = 0, device: int = 0, max_plies: int = 0, temp: float = 1e-3, solver: bool = False, search=None):
-        """``search``: a dict of ``engine.set_search``'s arguments (first-play urgency, visit-scaled c_puct) for both sides; None: the
+                 seed: int = 0, device: int = 0, max_plies: int = 0, temp: float = 1e-3, solver: bool = False, search=None, early_stop=None):
+        """``early_stop``: a dict of ``engine.set_early_stop``'s arguments (``stopcfg.make_early_stop``): a board stops searching its move
+        when the outcome can no longer change, and the move's loop ends when ``engine.searching()``, asked every 16 steps, is 0; None: off.
+        ``search``: a dict of ``engine.set_search``'s arguments (first-play urgency, visit-scaled c_puct) for both sides; None: the
         reference's PUCT. ``solver``: both sides search with the MCTS-solver (``engine.set_solver``) and play the proven move where the root is
         decided (``engine.proof_moves``); every other move is drawn as without it."""
         self.ev = {1: evaluator_red, 0: evaluator_black}
@@ -36,6 +38,11 @@ class BatchedMatch:
         self.search_cfg = None if search is None else dict(search)
         if self.search_cfg is not None:
             self.engine.set_search(**self.search_cfg)
+        from .stopcfg import StopPoll
+        self.early_stop = None if early_stop is None else dict(early_stop)
+        if self.early_stop is not None:
+            self.engine.set_early_stop(**self.early_stop)
+        self._poll = StopPoll(self.engine, self.early_stop)
         self.before_move = self.on_move = None
         self._temps = np.full(n_boards, temp, np.float64)
 
@@ -47,6 +54,8 @@ class BatchedMatch:
         ev = self.ev[turn]
         leaf = e.select_leaves()
         for i in range(self.n_playout):
+            if self._poll.done(i):               # no board would select any more: no leaf is pending either
+                break
             leaf = deliver(e, kind_of(ev), *ev(leaf), i + 1 == self.n_playout)
         if self.before_move is not None:
             self.before_move(self)

@@ -152,8 +152,12 @@ class BatchedSelfPlay:
     def __init__(self, evaluator, n_boards: int, n_playout: int = 400, c_puct: float = C_PUCT, eps: float = EPS,
                  alpha: float = ALPHA, temp: float = 1.0, seed: int = 0, board_id_base: int = 0, device: int = 0,
                  sampling: str = "device", use_graph: bool = False, version_fn=None, playout_cap=None, resign=None,
-                 root_exploration=None, solver: bool = False, gumbel=None, search=None, **engine_kw):
-        """``search``: a dict of :meth:`SelfPlayEngine.set_search`'s arguments (``fpu_mode``, ``fpu_value``, ``fpu_root_mode``,
+                 root_exploration=None, solver: bool = False, gumbel=None, search=None, early_stop=None, **engine_kw):
+        """``early_stop``: a dict of :meth:`SelfPlayEngine.set_early_stop`'s arguments (``single_reply``, ``gap_factor``,
+        ``kld_interval``, ``min_gain``, ``min_sims``; see :func:`stopcfg.make_early_stop`): a board stops searching its move when the
+        outcome can no longer change or its visit distribution has stopped moving, and selects nothing for the rest of the move's
+        ``n_playout`` lockstep steps (no evaluator row with an evaluation cache). Not with ``gumbel``. None (default): off.
+        ``search``: a dict of :meth:`SelfPlayEngine.set_search`'s arguments (``fpu_mode``, ``fpu_value``, ``fpu_root_mode``,
         ``fpu_root_value``, ``c_base``, ``c_factor``): first-play urgency and the visit-scaled c_puct inside the tree. Works with every
         other option here (under ``gumbel`` from depth 1). None (default): off, the reference's PUCT.
         ``gumbel``: True, or a dict of :meth:`SelfPlayEngine.set_gumbel`'s arguments (``n_sims`` defaults to ``n_playout``;
@@ -222,6 +226,10 @@ class BatchedSelfPlay:
         if search is not None:
             self.search_cfg = dict(search)
             self.engine.set_search(**self.search_cfg)
+        self.early_stop = None
+        if early_stop is not None:
+            self.early_stop = dict(early_stop)
+            self.engine.set_early_stop(**self.early_stop)
         self.B = n_boards
         self.n_playout = n_playout
         self.sampling = sampling
@@ -316,9 +324,22 @@ class BatchedSelfPlay:
         self._ticker.on_playout = None   # (the caller's callback is not kept past the call: it may refer to this object)
         return moves
 
-    def search(self, on_playout=None, hooks=None):
+    def stop_report(self) -> dict:
+        """Stops per reason and the mean simulations per move so far (:func:`stopcfg.stop_report`; syncs)."""
+        from .stopcfg import stop_report
+        st = self.engine.stats()
+        return stop_report(self.engine.early_stop_stats(), st["moves"], st["sims"])
+
+    def search(self, on_playout=None, hooks=None, poll: bool = False):
         """The simulations that are left of the current move (all ``n_playout`` from a move's start) WITHOUT playing it: the roots
-        can be read (``engine.root_children()``) before :meth:`finish_move`."""
+        can be read (``engine.root_children()``) before :meth:`finish_move`. ``poll`` (an arg-max front end with ``early_stop``):
+        ``engine.searching()`` is asked every 16 steps and the move's loop ends when no board would select any more."""
+        if poll and self.early_stop is not None and self._graph is None:
+            while self.n_playout - self._sim > 1:
+                if self._sim > 0 and self._sim % 16 == 0 and self.engine.searching() == 0:   # (no leaf is pending either)
+                    self._sim, self._leaf, self._ticker.acc = 0, None, 0
+                    return
+                self.advance(1, hooks=hooks, on_playout=on_playout)
         left = self.n_playout - self._sim
         if left > 1:
             self.advance(left - 1, hooks=hooks, on_playout=on_playout)

@@ -529,6 +529,64 @@ int ccz_set_search(ccz_engine *e, void *stream, int32_t enabled, int32_t fpu_mod
                    double fpu_root_value, double c_base, double c_factor);
 int ccz_get_search(ccz_engine *e, void *stream, ccz_search_cfg *out); /* syncs */
 
+/* ---- Early stop per board: single reply, visit gap, KLD gain (additive to ABI 9) ----------------------------------------------------
+ * A board whose budget is spent selects nothing for the rest of a lockstep move (ccz_set_budgets). With this feature a board also
+ * stops when searching on cannot change its move -- one legal reply, or a leader the runner-up cannot catch with the simulations
+ * left (Lc0's "smart pruning") -- or when its visit distribution has stopped moving (the KL-divergence gain per new visit, as in Lc0
+ * and KataGo). Off after ccz_create: every output of every call is then bit for bit what it is without the feature (the selection
+ * tests one prefetched word).
+ *   ccz_set_early_stop: asynchronous on `stream`, takes effect with the next selection. cfg->enabled = 0: off; the other fields are
+ *     ignored and zeros are stored. enabled = 1: single_reply in {0, 1}; gap_factor 0 (off) or finite and >= 1; kld_interval 0 (off)
+ *     or >= 1; min_gain finite and >= 0; min_sims >= 0; n_sims >= 1; reserved 0. A refused call names the field in ccz_last_error and
+ *     leaves the old settings in place. Every accepted call clears each board's stop and snapshot. Fails with scout slots, a width
+ *     above 1 or the Gumbel root (whose sequential halving plans the whole budget), and ccz_set_scouts / ccz_set_width /
+ *     ccz_set_gumbel fail while it is on. It works with budgets, routing, root exploration, ccz_set_search, the solver, resignation
+ *     and the evaluation cache.
+ *   ccz_get_early_stop: syncs; what the kernels read.
+ * Per board, at a selection (ccz_select_leaves, the selection of ccz_step*): s = the simulations of the current move backed up so
+ * far, this launch's backup included (what the budget test compares); n_b = the board's budget when budgets are on, else n_sims;
+ * the root has children i = 0 .. k-1 with counts N_i as they stand after this launch's backup.
+ *   S1. When. The rules run when the game is not over, s < n_b, the root is expanded (k >= 1), the board is not already stopped in
+ *       this move, and s >= min_sims; in the order S2, S3, S4, and the first that fires wins.
+ *   S2. Single reply (single_reply = 1): k == 1 fires with reason 1.
+ *   S3. Visit gap (gap_factor f != 0): i1 = the first maximum of N_i in child order, N1 = N_{i1}, N2 = max_{i != i1} N_i (0 when
+ *       k == 1). Fires with reason 2 if (double)(N1 - N2) * f > (double)(n_b - s). Both maxima run over children 0 .. 127.
+ *   S4. KLD gain (kld_interval I > 0). Per board a snapshot p_i (int32 [128], zero past k) and snap_s, which is -1 at every move
+ *       boundary. The rule is evaluated only if s > 0, s % I == 0 and s != snap_s (a selection repeated without a backup must not
+ *       meet its own snapshot). If snap_s >= 0 and S_c = sum N_i > S_p = sum p_i: for p_i > 0, o = (double)p_i / (double)S_p,
+ *       n = (double)N_i / (double)S_c, t_i = o * det_log(o / n), else t_i = 0.0; T = the butterfly sum of R2 above (lane l forms
+ *       t_l + t_{l+64}, then m_l = m_l + m_{l xor s} for s = 32 .. 1); G = T / (double)(S_c - S_p); fires with reason 3 if
+ *       G < min_gain (a NaN does not fire). Fired or not, the snapshot becomes N_i and snap_s = s (counted in `evaluations`).
+ *   S5. Effect. stopped[b] = reason; this selection and every later one of the move treat the board exactly as a spent budget:
+ *       CCZ_LEAF_SKIP, no evaluator row, no simulation counted. stops[reason] += 1 and sims_saved += n_b - s. stopped and snap_s
+ *       are cleared wherever the move's simulation count is zeroed (ccz_finish_move on every running board, a fresh root:
+ *       ccz_reset, ccz_reset_tree, ccz_set_position(s)). Everything else reads the counts as searched: pi, records, resignation,
+ *       ccz_root_children, ccz_principal_variations.
+ * Consequence: with f = 1, the solver and root exploration off, the first maximum of N at a root stopped by S3 is the first maximum
+ * of the same search run to n_b (the leader gains nothing less than the runner-up can gain), and the stopped board is bit for bit
+ * the board of an engine whose budget is s. */
+typedef struct ccz_early_stop_cfg {
+    int32_t enabled, single_reply, kld_interval, min_sims, n_sims, reserved;
+    double gap_factor, min_gain;
+} ccz_early_stop_cfg;
+typedef struct ccz_early_stop_stats { /* sums over boards */
+    int64_t stops[4];     /* by reason: [1] single reply, [2] visit gap, [3] KLD gain ([0] unused)          */
+    int64_t sims_saved;   /* sum of n_b - s over the stops                                                  */
+    int64_t evaluations;  /* snapshots taken by S4                                                          */
+} ccz_early_stop_stats;
+#define CCZ_STOP_SINGLE_REPLY 1
+#define CCZ_STOP_VISIT_GAP 2
+#define CCZ_STOP_KLD_GAIN 3
+int ccz_set_early_stop(ccz_engine *e, void *stream, const ccz_early_stop_cfg *cfg);
+int ccz_get_early_stop(ccz_engine *e, void *stream, ccz_early_stop_cfg *out);         /* syncs */
+int ccz_get_early_stop_stats(ccz_engine *e, void *stream, ccz_early_stop_stats *out); /* syncs */
+/* per board: the reason it stopped with in its current move (0: it has not; uint8 [B]) and the simulations its move has backed up
+ * (int32 [B]). Either output may be NULL. Syncs. */
+int ccz_early_stop_status(ccz_engine *e, void *stream, uint8_t *reason_host, int32_t *sims_host);
+/* the number of searched boards that would still select a leaf: the game running, the budget not spent, not stopped. One small
+ * kernel and a 4-byte copy; syncs. What a front end polls to end a move's loop early. */
+int ccz_searching(ccz_engine *e, void *stream, int32_t *count_host);
+
 /* ---- MCTS-solver: exact propagation of decided positions through the tree (additive to ABI 8) ----
  * One proof byte per tree node, in a device array of its own (uint8 [B][2][max_nodes], allocated and zeroed by the first
  * ccz_set_solver(enabled = 1), which may sync; never touched while the solver is off). Bits 0..1: the state in the view of the side
