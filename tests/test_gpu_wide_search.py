@@ -39,11 +39,15 @@ def _evaluator():
 
 
 class Twin:
-    """A wide engine next to the model. ``inputs``: [(squares, turn)] of the A searched boards; ``budgets`` [A] or None."""
+    """A wide engine next to the model. ``inputs``: [(squares, turn)] of the A searched boards; ``budgets`` [A] or None.
+    ``max_nodes`` / ``max_depth``: the engine's limits, which the model is told as ccz_create derives them; ``overrides``: {board:
+    an evaluator override of wide_model.override_rows} (unplanned only); ``model_kw`` / ``engine_kw``: further arguments of both."""
 
-    def __init__(self, W, inputs, budgets, planned=True, check_leaves=True):
+    def __init__(self, W, inputs, budgets, planned=True, check_leaves=True, max_nodes=None, max_depth=None, overrides=None, model_kw=None,
+                 engine_kw=None):
         self.A, self.W, self.planned, self.check_leaves = len(inputs), W, planned, check_leaves
-        self.e = e = _engine(self.A * W, eval_cache_log2=CACHE_LOG2 if planned else 0)
+        limits = {k: v for k, v in (("max_nodes", max_nodes), ("max_depth", max_depth)) if v is not None}
+        self.e = e = _engine(self.A * W, eval_cache_log2=CACHE_LOG2 if planned else 0, **limits, **(engine_kw or {}))
         for r, (sq, turn) in enumerate(inputs):
             e.set_position(r, sq, turn)
         e.set_width(W)
@@ -51,9 +55,14 @@ class Twin:
         if budgets is not None:
             e.set_budgets(np.array(list(budgets) + [1] * (e.B - self.A), np.int32))
         self.roots = [OracleBoard.from_array(sq, turn) for sq, turn in inputs]
-        self.model = wm.WideModel(self.A, W, c_puct=5.0, budgets=self.budgets)
+        if max_nodes is not None:
+            limits["max_nodes"] = max(130, max_nodes)       # (Dev.cap: root + one full expansion at the least)
+        self.model = wm.WideModel(self.A, W, c_puct=5.0, budgets=self.budgets, **limits, **(model_kw or {}))
         self.keys = {}          # position bytes -> leaf key: one key per position, one position per key
         self.ev = _evaluator()
+        if overrides:
+            assert not planned, "an override cannot go through the plan"
+            self.ev = wm.with_overrides(self.ev, self.A, overrides)
         self.steps = 0
 
     # what the engine's slots hold after a selection, against what the model selects
@@ -125,6 +134,15 @@ class Twin:
                 return self
             self.step()
         raise AssertionError("the search did not end")
+
+    def finish_move(self, forced):
+        """The move boundary with keep_tree: ``forced`` [A] move ids, on the engine, the model and the rules oracle."""
+        f = np.full(self.e.B, -1, np.int32)
+        f[:self.A] = forced
+        assert np.array_equal(self.e.finish_move(forced_moves=f, keep_tree=True).cpu().numpy()[:self.A], f[:self.A])
+        for r in range(self.A):
+            self.model.reroot(r, int(forced[r]))
+            self.roots[r].push_id(int(forced[r]))
 
     def compare_roots(self):
         rc = self.e.root_children()
