@@ -24,7 +24,8 @@ import numpy as np
 from ._lib import CczError
 from .boundary import describe
 from .game import Board
-from .searchcfg import add_search_args, mean_leaf_depth, search_from_args
+from .options import SearchOptions
+from .searchcfg import add_search_args, search_from_args
 from .stopcfg import add_early_stop_args, early_stop_from_args
 
 
@@ -90,10 +91,8 @@ class BatchedAnalysis:
         """``width`` > 1: every position gathers up to ``width`` leaves of its tree per step, kept apart by virtual loss
         (``wide.WideSearch``: an engine of ``n_boards * width`` slots) -- for a handful of positions, where the sequential search
         runs at the evaluator's latency; another tree than the sequential one; excludes ``solver`` and ``search``.
-        ``search``: a dict of ``SelfPlayEngine.set_search``'s arguments (first-play urgency, visit-scaled c_puct); None: the
-        reference's PUCT. ``early_stop``: a dict of ``SelfPlayEngine.set_early_stop``'s arguments (``stopcfg.make_early_stop``): a
-        position stops being searched when its best move can no longer change, and a chunk's loop ends when
-        ``engine.searching()``, asked every 16 steps, is 0; excludes ``width`` > 1. None: off."""
+        ``solver`` / ``search`` / ``early_stop``: the engine options (``options.OPTIONS``; None / False: off). With the early stop a position
+        stops being searched when its best move can no longer change, and a chunk's loop ends when no board would select any more."""
         from .selfplay import BatchedSelfPlay
         desc = describe(evaluator)
         ev = desc.fn
@@ -101,6 +100,7 @@ class BatchedAnalysis:
             raise TypeError("BatchedAnalysis: the evaluator must be callable or have evaluate_leaves_logits")
         if not 1 <= int(multipv) <= 128 or int(max_len) < 1 or int(n_playout) < 1:
             raise ValueError("BatchedAnalysis: multipv must be 1..128, max_len and n_playout >= 1")
+        SearchOptions(n_playout, width=width, solver=solver, search=search, early_stop=early_stop)   # (ValueError: width > 1 excludes them)
         if "eval_cache_log2" not in engine_kw:
             engine_kw["eval_cache_log2"] = 22 if (int(n_boards) >= 192 and desc.accepts_plan) else 0
         engine_kw.setdefault("mirror", False)
@@ -111,8 +111,6 @@ class BatchedAnalysis:
         self.seconds = 0.0
         self._rows = None   # evaluator rows, summed on the device (planned boundary: the plan's count per step)
         if self.width != 1:
-            if solver or search is not None or early_stop is not None:
-                raise ValueError("BatchedAnalysis: width > 1 excludes the solver, the search parameters and the early stop")
             from .wide import WideSearch
             if engine_kw["eval_cache_log2"] == 0 and desc.accepts_plan:
                 engine_kw["eval_cache_log2"] = 16   # slots of one tree reach one position often: they share an evaluator row
@@ -124,9 +122,9 @@ class BatchedAnalysis:
             return
         self.sp = BatchedSelfPlay(ev, int(n_boards), n_playout=int(n_playout), eps=0.0, search=search, early_stop=early_stop, **engine_kw)   # no GPU: CczError
         self.engine = self.sp.engine
-        self.solver = bool(solver)     # the MCTS-solver: records gain "mate", bestmove follows the proof (make_record)
-        if self.solver:
-            self.engine.set_solver(True)
+        opts = SearchOptions(solver=solver)     # (search and early stop: the self-play front end's own, above)
+        self.solver = opts.solver               # the MCTS-solver: records gain "mate", bestmove follows the proof (make_record)
+        opts.apply(self.engine)
 
     def _count_rows(self, stage, _sim):
         if stage == "eval1":
@@ -214,10 +212,11 @@ class BatchedAnalysis:
         sec = max(self.seconds, 1e-9)
         out = {"positions": self.positions, "seconds": round(self.seconds, 3), "positions_per_s": round(self.positions / sec, 2),
                "sims_per_s": round(self.sims / sec, 1), "evaluator_rows_per_step": round(rows / max(1, self.steps), 2)}
-        if self.sp.search_cfg is not None:      # the settings as the kernels read them, and how deep the leaves lay
-            out.update(search=self.engine.search_settings(), mean_leaf_depth=round(mean_leaf_depth(self.engine.stats()), 3))
-        if self.sp.early_stop is not None:      # stops per reason, and what a position cost on average
-            out["early_stop"] = dict(self.sp.stop_report(), mean_sims_per_position=round(self.sims / max(1, self.positions), 3))
+        out.update(self.sp.options.report(self.engine))   # search: the settings as the kernels read them, and how deep the leaves lay
+        if "search" in out:
+            out["mean_leaf_depth"] = round(out["mean_leaf_depth"], 3)
+        if "early_stop" in out:                 # stops per reason, and what a position cost on average
+            out["early_stop"]["mean_sims_per_position"] = round(self.sims / max(1, self.positions), 3)
         return out
 
 

@@ -23,8 +23,9 @@ import numpy as np
 
 from .boundary import WeightsWatch, describe
 from .parameters import C_PUCT
-from .searchcfg import add_search_args, mean_leaf_depth, search_from_args
-from .stopcfg import StopPoll, add_early_stop_args, early_stop_from_args, stop_report
+from .options import SearchOptions, add_resign_args, proven_moves, resign_from_args, search_move
+from .searchcfg import add_search_args, search_from_args
+from .stopcfg import StopPoll, add_early_stop_args, early_stop_from_args
 
 _RESIGNED = 2   # _lib.RESIGN_RESIGNED (this module imports the engine lazily: its statistics run without a GPU)
 PROMOTE_THRESHOLD = 0.55   # AlphaGo Zero's gate, kept by the AlphaZero_Gomoku lineage the reference cites
@@ -173,11 +174,9 @@ class Arena:
     None: both search ``n_playout``. ``resign``: a threshold in [-1, 0] or a dict with ``threshold`` and optionally ``consecutive`` /
     ``min_ply`` (``engine.set_resign``): the side to move resigns when its root value stayed below the threshold -- a resigned game
     is a win for the other side like any other, counted in ``result()["resigned"]``; no game is played on (``p_playon`` = 0).
-    None (default): games end by the rules or the ply cap only. ``solver``: both sides search with the MCTS-solver
-    (``engine.set_solver``) and play the proven move where the root is decided (``engine.proof_moves``). ``search``: a dict of
-    ``engine.set_search``'s arguments (first-play urgency, visit-scaled c_puct), for both sides alike; None: the reference's PUCT. ``early_stop``: a dict of
-    ``engine.set_early_stop``'s arguments (``stopcfg.make_early_stop``): a board stops searching its move when the outcome can no longer
-    change; the move's loop asks ``engine.searching()`` every 16 steps and ends when no board would select any more. None: off."""
+    None (default): games end by the rules or the ply cap only. ``solver`` / ``search`` / ``early_stop``: the engine options
+    (``options.OPTIONS``; None / False: off), for both sides alike: with the solver the proven move is played where the root is decided
+    (``options.proven_moves``), with the early stop the move's loop ends when no board would select any more (``options.search_move``)."""
 
     def __init__(self, net_a, net_b, n_pairs: int, n_playout: int = 400, opening_plies: int = 6, seed: int = 0,
                  max_plies: int = 0, c_puct: float = C_PUCT, eval_cache_log2: int = 22, device: int = 0,
@@ -200,29 +199,20 @@ class Arena:
         if self.n_playout < 1 or (self.n_playout_b is not None and self.n_playout_b < 1):
             raise ValueError("Arena: n_playout and n_playout_b must be >= 1")
         self.n_steps = self.n_playout if self.n_playout_b is None else max(self.n_playout, self.n_playout_b)   # lockstep steps per move
+        self.options = o = SearchOptions(self.n_steps, resign=resign, solver=solver, search=search, early_stop=early_stop)
+        self.resign, self.solver, self.search_cfg, self.early_stop = o.keywords().values()
+        if self.resign is not None:          # (the dict ``o.apply`` hands to the engine)
+            if self.resign.get("p_playon", 0.0) != 0.0:
+                raise ValueError("Arena: a match plays no game on after the resignation rule fired (p_playon is fixed at 0)")
+            self.resign["p_playon"] = 0.0
         self.temp = 1e-3
         self.engine = e = SelfPlayEngine(self.B, n_playout=self.n_steps, c_puct=c_puct, eps=0.0, alpha=0.2, temp=self.temp,
                                          seed=seed, device=device, max_plies=max_plies, mirror=False,
                                          eval_cache_log2=eval_cache_log2, cache_verify=cache_verify)
         self.max_plies = e.max_plies
-        self.solver = bool(solver)
         self.proven_moves = 0                # moves played from a proof
-        if self.solver:
-            e.set_solver(True)
-        self.search_cfg = None if search is None else dict(search)
-        if self.search_cfg is not None:
-            e.set_search(**self.search_cfg)
-        self.early_stop = None if early_stop is None else dict(early_stop)
-        if self.early_stop is not None:
-            e.set_early_stop(**self.early_stop)
+        o.apply(e)
         self._poll = StopPoll(e, self.early_stop)
-        self.resign = None
-        if resign is not None:
-            self.resign = dict(resign) if isinstance(resign, dict) else {"threshold": float(resign)}
-            if self.resign.get("p_playon", 0.0) != 0.0:
-                raise ValueError("Arena: a match plays no game on after the resignation rule fired (p_playon is fixed at 0)")
-            self.resign["p_playon"] = 0.0
-            e.set_resign(**self.resign)
         self.opening_of, self.a_colour, self.red_net = pair_layout(self.P)
         self.openings = make_openings(self.P, int(opening_plies), seed=seed, device=device)
         sq, turn, half = self.openings
@@ -251,21 +241,17 @@ class Arena:
         self._sync_routing()
         if self.n_playout_b is not None:
             e.set_budgets(self.move_budgets())
-        leaf = e.select_leaves()
-        for i in range(self.n_steps):
-            if self._poll.done(i):               # no board would select any more: no leaf is pending either
-                break
+        def step(leaf, last):
             p0, p1 = e.eval_plan_routed()
             self._rows += e.n_miss2
             if on_step is not None:
                 on_step(self, p0, p1)
             lg0, v0 = ev0(leaf, plan=p0)
             lg1, v1 = ev1(leaf, plan=p1)
-            if i + 1 < self.n_steps:
-                leaf = e.step_routed(lg0, v0, lg1, v1)
-            else:
-                e.expand_backup_routed(lg0, v0, lg1, v1)
+            leaf = e.expand_backup_routed(lg0, v0, lg1, v1) if last else e.step_routed(lg0, v0, lg1, v1)
             self.steps += 1
+            return leaf
+        search_move(e, self.n_steps, step, self._poll)
 
     def move_budgets(self) -> np.ndarray:
         """int32 [B]: the simulations every board searches in the move at hand -- ``n_playout`` where A is to move, ``n_playout_b``
@@ -285,11 +271,8 @@ class Arena:
         """The move after a :meth:`search`: arg-max visits up to ties (temperature 1e-3), the tree is discarded."""
         e = self.engine
         over = e.game_status()["over"]
-        forced = None
-        if self.solver:
-            forced = e.proof_moves()
-            forced[over != 0] = -1
-            self.proven_moves += int((forced >= 0).sum())
+        forced, proven = proven_moves(e, self.solver, over)
+        self.proven_moves += proven
         moves = e.finish_move(forced_moves=forced, temps=self._temps, keep_tree=False).cpu().numpy().copy()
         # a game adjudicated at max_plies ends INSTEAD of a move (finish_move plays none on that board); so does a resigned one
         st = e.game_status()
@@ -328,8 +311,6 @@ class Arena:
                "n_playout_b": self.n_playout if self.n_playout_b is None else self.n_playout_b,
                "wins": int(np.sum(w == self.a_colour)), "draws": int(np.sum(w == -1)), "losses": int(np.sum((w != -1) & (w != self.a_colour))),
                "truncated": int(self.truncated.sum()), "unfinished": int((st["over"] == 0).sum())}
-        if self.solver:
-            out["solver"] = dict(self.engine.solver_stats(), proven_moves=self.proven_moves)
         if self.resign is not None:
             out["resigned"] = int(((self.engine.resign_status()["state"] & _RESIGNED) != 0).sum())
         out.update(pair_stats(pair_pts))
@@ -338,12 +319,10 @@ class Arena:
         if wall is not None:
             out["wall_s"] = wall
             out["games_per_s"] = self.B / wall if wall > 0 else float("nan")
+        out.update(self.options.report(self.engine))
+        if self.solver:
+            out["solver"]["proven_moves"] = self.proven_moves
         s = self.engine.stats()
-        if self.search_cfg is not None:
-            out["search"] = self.engine.search_settings()
-            out["mean_leaf_depth"] = mean_leaf_depth(s)
-        if self.early_stop is not None:
-            out["early_stop"] = stop_report(self.engine.early_stop_stats(), s["moves"], s["sims"])
         out["cache"] = {k: s[k] for k in ("cache_probes", "cache_hits", "cache_shared_rows", "cache_stores",
                                            "cache_verified", "cache_verify_mismatches")}
         return out
@@ -383,22 +362,14 @@ def main(argv=None) -> int:
     ap.add_argument("--blocks", type=int, default=40)
     ap.add_argument("--threshold", type=float, default=PROMOTE_THRESHOLD, help="promotion threshold of the score")
     ap.add_argument("--device", type=int, default=0)
-    ap.add_argument("--resign-threshold", type=float, default=None,
-                    help="resignation: the side to move resigns when its root value stayed below this (in [-1, 0]); absent = off")
-    ap.add_argument("--resign-moves", type=int, default=None, help="... for this many of its moves in a row (default 2)")
+    add_resign_args(ap, playon=False)
     ap.add_argument("--solver", action="store_true", help="MCTS-solver on both sides: decided positions are proven in the tree and the proven move is played")
-    ap.add_argument("--resign-min-ply", type=int, default=None, help="... and not before this ply (default 30)")
     add_search_args(ap)
     add_early_stop_args(ap)
     a = ap.parse_args(argv)
     search = search_from_args(ap, a)
     early_stop = early_stop_from_args(ap, a)
-    if a.resign_threshold is None and (a.resign_moves is not None or a.resign_min_ply is not None):
-        ap.error("--resign-moves / --resign-min-ply need --resign-threshold")
-    resign = None
-    if a.resign_threshold is not None:
-        resign = {"threshold": a.resign_threshold, "consecutive": 2 if a.resign_moves is None else a.resign_moves,
-                  "min_ply": 30 if a.resign_min_ply is None else a.resign_min_ply}
+    resign = resign_from_args(ap, a)
     na = _load(a.a, a.channels, a.blocks, a.device)
     nb = _load(a.b, a.channels, a.blocks, a.device)
     arena = Arena(na, nb, a.pairs, n_playout=a.playout, opening_plies=a.opening_plies, seed=a.seed, max_plies=a.max_plies,

@@ -30,7 +30,9 @@ from .game import RED, Board, Game
 from .mcts import MCTS_AI
 from .net import PolicyValueNet
 from .parameters import BATCH_SIZE, C_PUCT, DATA_DIR, MODEL_DIR, PLAYOUT
-from .searchcfg import add_search_args, mean_leaf_depth, search_from_args
+from .options import (SearchOptions, add_gumbel_args, add_resign_args, add_root_exploration_args, format_exploration, format_gumbel,  # noqa: F401
+                      format_search, gumbel_from_args, resign_from_args, root_exploration_from_args)
+from .searchcfg import add_search_args, search_from_args
 from .stopcfg import add_early_stop_args, early_stop_from_args
 from .tools import flip_map, log
 
@@ -505,25 +507,19 @@ def write_games_hdf5(records: torch.Tensor, h5_path: str, flags: int = 0, plane_
 
 
 class CollectPipeline:
+    options = SearchOptions()   # (a pipeline made without __init__ -- tests do -- has none on)
+
     def __init__(self, init_model=None, n_boards: int = 1, n_playout: int = PLAYOUT, device: int = 0, seed: int = 0,
                  data_dir: str = DATA_DIR, reference_quirks: bool = False, num_channels: int = 256, resblocks_num: int = 40,
                  finalize_every: int = 0, on_playout=None, max_plies: int = 0, eval_cache_log2: int | None = None, gatherer=None,
                  dense_shards: bool = False, replay_plies: int = 0, train_every: int = 0, train_batch: int = BATCH_SIZE,
                  playout_cap_fast: int = 0, playout_cap_prob: float | None = None, resign=None, value_q_weight: float = 0.0,
                  root_exploration=None, solver: bool = False, gumbel=None, search=None, early_stop=None):
-        # early stop per board (``early_stop``: a dict of SelfPlayEngine.set_early_stop's arguments; None = off), on the batched path: a
-        # board stops searching its move early and selects nothing for the rest of the move's ``n_playout`` steps
-        self.early_stop = None if early_stop is None else dict(early_stop)
-        if self.early_stop is not None and n_boards <= 1:
-            raise ValueError("the early stop of the collector runs on the batched path: n_boards must be > 1")
-        if self.early_stop is not None and gumbel is not None and gumbel is not False:
-            raise ValueError("the early stop and the Gumbel root search exclude each other: sequential halving plans the whole budget")
-        # search parameters (``search``: a dict of SelfPlayEngine.set_search's arguments; None = the reference's PUCT): first-play
-        # urgency and the visit-scaled c_puct, on the batched path and in the one-game loop (which then runs without scout slots)
-        self.search = None if search is None else dict(search)
-        self.solver = bool(solver)     # the MCTS-solver in the search of the batched path (only the search changes)
-        if self.solver and n_boards <= 1:
-            raise ValueError("the solver option of the collector runs on the batched path: n_boards must be > 1")
+        # the engine options of the batched path, as BatchedSelfPlay takes them (options.OPTIONS: each None / False = off); only the search
+        # parameters also run in the one-game loop (which then runs without scout slots)
+        self.options = o = SearchOptions(n_playout, batched=n_boards > 1, resign=resign, root_exploration=root_exploration, gumbel=gumbel,
+                                         solver=solver, search=search, early_stop=early_stop)
+        self.resign, self.root_exploration, self.gumbel, self.solver, self.search, self.early_stop = o.keywords().values()
         # collect + train as one job (both 0: off): the rank that stores the union keeps it in a record ring of ``replay_plies`` plies
         # and runs one Trainer step of ``train_batch`` rows every ``train_every`` lockstep moves, once the ring holds a batch
         self.replay_plies, self.train_every, self.train_batch = int(replay_plies), int(train_every), int(train_batch)
@@ -551,29 +547,7 @@ class CollectPipeline:
             if not 0.0 <= float(playout_cap_prob) <= 1.0:
                 raise ValueError(f"playout_cap_prob must be in [0, 1] (got {playout_cap_prob})")
             self.playout_cap = (int(playout_cap_fast), float(playout_cap_prob))
-        # self-play resignation with play-on calibration (``resign``: a threshold, or a dict of SelfPlayEngine.set_resign's arguments;
-        # None = off) and the weight of the search's root value q in the trainer's value target ((1 - w) z + w q; 0 = z alone)
-        self.resign = None
-        if resign is not None:
-            if n_boards <= 1:
-                raise ValueError("resignation runs on the batched path: n_boards must be > 1")
-            self.resign = dict(resign) if isinstance(resign, dict) else {"threshold": float(resign)}
-        # exploration inside the search on full-search moves (``root_exploration``: a dict of SelfPlayEngine.set_root_exploration's
-        # arguments; None = off, the reference's search with the sampler's noise after it)
-        self.root_exploration = None
-        if root_exploration is not None:
-            if n_boards <= 1:
-                raise ValueError("root exploration runs on the batched path: n_boards must be > 1")
-            self.root_exploration = dict(root_exploration)
-        # Gumbel root search (``gumbel``: True, or a dict of SelfPlayEngine.set_gumbel's arguments; None = off): sequential halving at
-        # the root, pi' from the completed Q as the policy target of every move
-        self.gumbel = None
-        if gumbel is not None and gumbel is not False:
-            if n_boards <= 1:
-                raise ValueError("the Gumbel root search runs on the batched path: n_boards must be > 1")
-            if root_exploration is not None:
-                raise ValueError("gumbel and root_exploration exclude each other: the Gumbel draw is the root's exploration")
-            self.gumbel = dict(gumbel) if isinstance(gumbel, dict) else {}
+        # the weight of the search's root value q in the trainer's value target ((1 - w) z + w q; 0 = z alone)
         self.value_q_weight = float(value_q_weight)
         if not 0.0 <= self.value_q_weight <= 1.0:
             raise ValueError(f"value_q_weight must be in [0, 1] (got {value_q_weight})")
@@ -629,7 +603,7 @@ class CollectPipeline:
                 from .replay import broadcast_model
                 broadcast_model(self.policy_value_net, src=0, what="state")
             self.mcts_ai = MCTS_AI(self.policy_value_net.policy_value_fn, c_puct=self.c_puct, n_playout=self.n_playout,
-                                   is_selfplay=True, device=self.device, seed=self.seed, search=getattr(self, "search", None))
+                                   is_selfplay=True, device=self.device, seed=self.seed, search=self.search)
 
     # ---- host path (one game at a time, the reference's own steps) ---------------------------------
     def preprocess(self, play_data):
@@ -705,10 +679,7 @@ class CollectPipeline:
                                             eval_cache_log2=(24 if self.n_boards >= 192 else 0) if self.eval_cache_log2 is None else int(self.eval_cache_log2),
                                             c_puct=self.c_puct, temp=self.temp, seed=self.seed, board_id_base=rank * self.n_boards,
                                             device=self.device, reference_quirks=self.reference_quirks, max_plies=self.max_plies,
-                                            playout_cap=self.playout_cap, resign=getattr(self, "resign", None),
-                                            root_exploration=getattr(self, "root_exploration", None), solver=getattr(self, "solver", False),
-                                            gumbel=getattr(self, "gumbel", None), search=getattr(self, "search", None),
-                                            early_stop=getattr(self, "early_stop", None))
+                                            playout_cap=self.playout_cap, **self.options.keywords())
             if getattr(self, "_viewer", None) is not None:
                 self.selfplay.watch(0, self._viewer)
         for _ in range(n_moves):
@@ -884,52 +855,6 @@ class CollectPipeline:
             out["error_flags"] = int(self.selfplay.engine.stats()["error_flags"])
         return out
 
-    def resign_report(self) -> str:
-        """The resignation part of the periodic log line (empty with resignation off; syncs): games resigned, the false-positive
-        rate ``playon_won / playon_games`` of the games played on, and their mean plies after the fire ply."""
-        if getattr(self, "resign", None) is None or getattr(self, "selfplay", None) is None:
-            return ""
-        r = self.selfplay.engine.resign_stats()
-        n = r["playon_games"]
-        fp = f"{r['playon_won'] / n:.3f}" if n else "n/a"
-        after = f"{r['playon_plies_after'] / n:.1f}" if n else "n/a"
-        return f", resigned {r['resigned_games']}, play-on {n} (false positives {fp}, mean plies after {after})"
-
-    def solver_report(self) -> str:
-        """The MCTS-solver part of the periodic log line (empty with the solver off; syncs): the three counters."""
-        if not getattr(self, "solver", False) or getattr(self, "selfplay", None) is None:
-            return ""
-        s = self.selfplay.engine.solver_stats()
-        return f", nodes proven {s['nodes_proven']}, simulations ended at a proven node {s['proven_stops']}, roots proven {s['roots_proven']}"
-
-    def exploration_report(self) -> str:
-        """The root-exploration part of the periodic log line (empty with the feature off; syncs)."""
-        if getattr(self, "root_exploration", None) is None or getattr(self, "selfplay", None) is None:
-            return ""
-        e = self.selfplay.engine
-        return format_exploration(e.exploration_stats(), e.stats()["sims"])
-
-    def stop_report(self) -> str:
-        """The early-stop part of the periodic log line (empty with the feature off; syncs)."""
-        if getattr(self, "early_stop", None) is None or getattr(self, "selfplay", None) is None:
-            return ""
-        r = self.selfplay.stop_report()
-        return (f", early stops {r['single_reply']} single reply / {r['visit_gap']} gap / {r['kld_gain']} kld, "
-                f"{r['mean_sims_per_move']} simulations per move")
-
-    def search_report(self) -> str:
-        """The search-parameter part of the periodic log line (empty with the rule off; syncs)."""
-        if getattr(self, "search", None) is None or getattr(self, "selfplay", None) is None:
-            return ""
-        e = self.selfplay.engine
-        return format_search(e.search_settings(), e.stats())
-
-    def gumbel_report(self) -> str:
-        """The Gumbel part of the periodic log line (empty with the feature off; syncs)."""
-        if getattr(self, "gumbel", None) is None or getattr(self, "selfplay", None) is None:
-            return ""
-        return format_gumbel(self.selfplay.engine.gumbel_stats())
-
     def drain_exchange(self, gatherer):
         """End of a multi-rank collection with an asynchronous exchange: blocking, every rank calls it; afterwards every record of
         every rank has reached rank 0's store."""
@@ -964,7 +889,8 @@ class CollectPipeline:
                 while max_calls <= 0 or calls < max_calls:
                     iters = self.collect_data(is_shown=is_shown)
                     calls += 1
-                    log(f"Episode {iters}, steps {self.episode_len}" + self.resign_report() + self.exploration_report() + self.gumbel_report() + self.solver_report() + self.search_report() + self.stop_report())
+                    batched = self.options.on and self.selfplay is not None     # (the options' part: empty with none on; syncs)
+                    log(f"Episode {iters}, steps {self.episode_len}" + (self.options.log_line(self.selfplay.engine) if batched else ""))
             except KeyboardInterrupt:
                 log("Exit")
             if self.gatherer is not None and hasattr(self.gatherer, "flush_iter") and self.selfplay is not None:
@@ -978,35 +904,6 @@ class CollectPipeline:
             raise
         if finalize:
             self.sink.finalize()
-
-
-def format_exploration(x: dict, sims: int) -> str:
-    """``x`` = ``SelfPlayEngine.exploration_stats()``, ``sims`` = the simulations backed up so far (``stats()['sims']``, fast moves
-    included): explored moves, forced selections per explored move, and the visits pruned from the policy targets as a share of
-    the simulations run."""
-    n = x["explored_moves"]
-    forced = f"{x['forced_selections'] / n:.2f}" if n else "n/a"
-    share = f"{x['visits_pruned'] / sims:.4f}" if sims else "n/a"
-    return f", explored moves {n}, forced selections per move {forced}, pruned share of visits {share} ({x['children_pruned']} children dropped)"
-
-
-def format_search(cfg: dict, stats: dict) -> str:
-    """``cfg`` = ``SelfPlayEngine.search_settings()``, ``stats`` = ``SelfPlayEngine.stats()``: the urgency of the tree and of the root,
-    the growth of c_puct, and the mean depth of the leaves selected so far."""
-    def fpu(mode, value):
-        return {0: "off", 1: f"reduction {value:g}", 2: f"absolute {value:g}"}[int(mode)]
-    growth = f"base {cfg['c_base']:g} factor {cfg['c_factor']:g}" if cfg["c_factor"] else "constant"
-    return (f", fpu {fpu(cfg['fpu_mode'], cfg['fpu_value'])} (root {fpu(cfg['fpu_root_mode'], cfg['fpu_root_value'])}), c_puct {growth}, "
-            f"mean leaf depth {mean_leaf_depth(stats):.2f}")
-
-
-def format_gumbel(x: dict) -> str:
-    """``x`` = ``SelfPlayEngine.gumbel_stats()``: the moves played by the Gumbel root rule, the mean number of moves considered, and the
-    share of them whose played move was not the most visited one."""
-    n = x["gumbel_moves"]
-    m = f"{x['considered_sum'] / n:.2f}" if n else "n/a"
-    off = f"{x['offvisit_moves'] / n:.4f}" if n else "n/a"
-    return f", gumbel moves {n}, mean considered {m}, off-visit share {off}"
 
 
 def build_parser():
@@ -1034,26 +931,9 @@ def build_parser():
     parser.add_argument("--playout-cap-fast", type=int, default=0, help="playout-cap randomisation: simulations of a fast move (0 = off; needs "
                         "--playout-cap-prob). Fast plies are flagged and stay out of the policy loss")
     parser.add_argument("--playout-cap-prob", type=float, default=None, help="probability that a move is a full search of --playout simulations")
-    parser.add_argument("--resign-threshold", type=float, default=None, help="self-play resignation: the side to move resigns when its root value "
-                        "stayed below this (in [-1, 0]); absent = off. Root values are then recorded with every ply (root_values.npy)")
-    parser.add_argument("--resign-moves", type=int, default=None, help=f"... for this many of its full-search moves in a row (default {RESIGN_MOVES})")
-    parser.add_argument("--resign-min-ply", type=int, default=None, help=f"... and not before this ply (default {RESIGN_MIN_PLY})")
-    parser.add_argument("--resign-playon", type=float, default=None, help="fraction of such games played on to measure the false positives "
-                        f"(default {RESIGN_PLAYON}, AlphaGo Zero's)")
-    parser.add_argument("--root-noise-eps", type=float, default=None, help="exploration inside the search on full-search moves: weight of the "
-                        "Dirichlet noise in the ROOT's priors (in [0, 1]); absent = off (the noise is mixed into pi after the search)")
-    parser.add_argument("--root-noise-alpha", type=float, default=None, help="... its Dirichlet alpha (default: the sampler's)")
-    parser.add_argument("--forced-playouts", type=float, default=None, help=f"... forced playouts: a root child is searched until N >= sqrt(k P' S) "
-                        f"(default k = {FORCED_PLAYOUTS}, KataGo's; 0 = none)")
-    parser.add_argument("--no-target-pruning", action="store_true", default=False, help="... keep the forced visits in the recorded policy targets")
-    parser.add_argument("--gumbel", action="store_true", default=False, help="batched path: Gumbel root search -- one Gumbel draw per move, sequential "
-                        "halving over the considered moves within the move's simulations, the winner is played and pi' = softmax(logits + "
-                        "sigma(completed Q)) is the recorded policy target. With --playout-cap-fast the pi' of a fast ply is a valid target too "
-                        "(it improves on the prior at any simulation count); such plies are still flagged and the trainer treats the flag as before. "
-                        "Not with --root-noise-eps")
-    parser.add_argument("--gumbel-considered", type=int, default=None, help=f"... moves considered at the root, 2..128 (default {GUMBEL_CONSIDERED})")
-    parser.add_argument("--gumbel-c-visit", type=float, default=None, help=f"... c_visit of sigma, >= 0 (default {GUMBEL_C_VISIT})")
-    parser.add_argument("--gumbel-c-scale", type=float, default=None, help=f"... c_scale of sigma, >= 0 (default {GUMBEL_C_SCALE})")
+    add_resign_args(parser, playon=True, what="self-play resignation")
+    add_root_exploration_args(parser)
+    add_gumbel_args(parser)
     parser.add_argument("--solver", action="store_true", default=False, help="batched path: search with the MCTS-solver (decided positions are proven "
                         "in the tree and cost no evaluator row); sampling, records and targets are as without it")
     add_search_args(parser)
@@ -1063,77 +943,23 @@ def build_parser():
     return parser
 
 
-RESIGN_MOVES, RESIGN_MIN_PLY, RESIGN_PLAYON = 2, 30, 0.1
-FORCED_PLAYOUTS = 2.0
-GUMBEL_CONSIDERED, GUMBEL_C_VISIT, GUMBEL_C_SCALE = 16, 50.0, 1.0
-
-
 def parse_args(argv=None):
-    """Parse the command line; refuses ``--resign-moves`` / ``--resign-min-ply`` / ``--resign-playon`` without ``--resign-threshold``
-    (they would silently do nothing), and likewise ``--root-noise-alpha`` / ``--forced-playouts`` / ``--no-target-pruning`` without
-    ``--root-noise-eps``, and ``--gumbel-considered`` / ``--gumbel-c-visit`` / ``--gumbel-c-scale`` without ``--gumbel``; ``--gumbel``
-    with ``--root-noise-eps`` is refused too. ``args.resign`` / ``args.root_exploration`` / ``args.gumbel_cfg`` are the dicts for
-    ``CollectPipeline(...)`` or None."""
+    """Parse the command line. ``args.options``: the option keywords of ``CollectPipeline(...)`` (``args.resign`` / ``args.root_exploration``
+    / ``args.gumbel_cfg`` / ``args.search`` / ``args.early_stop``: dicts or None). An extra flag without its main flag (``options.py``) and
+    what ``CollectPipeline`` would refuse (``SearchOptions``) end in ``parser.error``."""
     parser = build_parser()
     args = parser.parse_args(argv)
-    extras = {"--resign-moves": args.resign_moves, "--resign-min-ply": args.resign_min_ply, "--resign-playon": args.resign_playon}
-    args.resign = None
-    if args.resign_threshold is None:
-        given = [k for k, v in extras.items() if v is not None]
-        if given:
-            parser.error(f"{', '.join(given)} without --resign-threshold: resignation is off")
-    else:
-        args.resign = {"threshold": args.resign_threshold,
-                       "consecutive": RESIGN_MOVES if args.resign_moves is None else args.resign_moves,
-                       "min_ply": RESIGN_MIN_PLY if args.resign_min_ply is None else args.resign_min_ply,
-                       "p_playon": RESIGN_PLAYON if args.resign_playon is None else args.resign_playon}
-    extras = {"--root-noise-alpha": args.root_noise_alpha, "--forced-playouts": args.forced_playouts,
-              "--no-target-pruning": True if args.no_target_pruning else None}
-    args.root_exploration = None
-    if args.root_noise_eps is None:
-        given = [k for k, v in extras.items() if v is not None]
-        if given:
-            parser.error(f"{', '.join(given)} without --root-noise-eps: root exploration is off")
-    else:
-        if not 0.0 <= args.root_noise_eps <= 1.0:
-            parser.error(f"--root-noise-eps must be in [0, 1] (got {args.root_noise_eps})")
-        if args.root_noise_alpha is not None and not args.root_noise_alpha > 0.0:
-            parser.error(f"--root-noise-alpha must be > 0 (got {args.root_noise_alpha})")
-        if args.forced_playouts is not None and not args.forced_playouts >= 0.0:
-            parser.error(f"--forced-playouts must be >= 0 (got {args.forced_playouts})")
-        if args.boards <= 1:
-            parser.error("--root-noise-eps runs on the batched path: --boards must be > 1")
-        args.root_exploration = {"eps": args.root_noise_eps, "alpha": args.root_noise_alpha,
-                                 "forced_k": FORCED_PLAYOUTS if args.forced_playouts is None else args.forced_playouts,
-                                 "prune_targets": not args.no_target_pruning}
-    extras = {"--gumbel-considered": args.gumbel_considered, "--gumbel-c-visit": args.gumbel_c_visit, "--gumbel-c-scale": args.gumbel_c_scale}
-    args.gumbel_cfg = None
-    if not args.gumbel:
-        given = [k for k, v in extras.items() if v is not None]
-        if given:
-            parser.error(f"{', '.join(given)} without --gumbel: the Gumbel root search is off")
-    else:
-        if args.root_noise_eps is not None:
-            parser.error("--gumbel with --root-noise-eps: the Gumbel draw is the root's exploration, the two exclude each other")
-        if args.gumbel_considered is not None and not 2 <= args.gumbel_considered <= 128:
-            parser.error(f"--gumbel-considered must be in 2..128 (got {args.gumbel_considered})")
-        for name, v in (("--gumbel-c-visit", args.gumbel_c_visit), ("--gumbel-c-scale", args.gumbel_c_scale)):
-            if v is not None and not (v >= 0.0 and v != float("inf")):
-                parser.error(f"{name} must be finite and >= 0 (got {v})")
-        if args.boards <= 1:
-            parser.error("--gumbel runs on the batched path: --boards must be > 1")
-        if args.playout < 1:
-            parser.error(f"--gumbel needs --playout >= 1 (got {args.playout})")
-        args.gumbel_cfg = {"n_sims": args.playout,
-                           "max_considered": GUMBEL_CONSIDERED if args.gumbel_considered is None else args.gumbel_considered,
-                           "c_visit": GUMBEL_C_VISIT if args.gumbel_c_visit is None else args.gumbel_c_visit,
-                           "c_scale": GUMBEL_C_SCALE if args.gumbel_c_scale is None else args.gumbel_c_scale}
+    args.resign = resign_from_args(parser, args)
+    args.root_exploration = root_exploration_from_args(parser, args)
+    args.gumbel_cfg = gumbel_from_args(parser, args)
     args.search = search_from_args(parser, args)
     args.early_stop = early_stop_from_args(parser, args)
-    if args.early_stop is not None and args.gumbel:
-        parser.error("--stop-* and --gumbel exclude each other: sequential halving plans the whole budget")
-    if args.early_stop is not None and args.boards <= 1:
-        parser.error("--stop-* run on the batched path: --boards must be > 1")
+    args.options = dict(resign=args.resign, root_exploration=args.root_exploration, gumbel=args.gumbel_cfg, solver=args.solver, search=args.search,
+                        early_stop=args.early_stop)
+    try:
+        SearchOptions(args.playout, batched=args.boards > 1, **args.options)
+    except ValueError as ex:
+        parser.error(str(ex))
     return args
 
 
@@ -1165,9 +991,7 @@ if __name__ == "__main__":
                            num_channels=args.channels, resblocks_num=args.blocks, max_plies=args.max_plies, device=device,
                            eval_cache_log2=args.eval_cache_log2, gatherer=gatherer, replay_plies=args.replay_plies,
                            train_every=args.train_every, train_batch=args.train_batch, playout_cap_fast=args.playout_cap_fast,
-                           playout_cap_prob=args.playout_cap_prob, resign=args.resign, value_q_weight=args.value_q_weight,
-                           root_exploration=args.root_exploration, solver=args.solver, gumbel=args.gumbel_cfg, search=args.search,
-                           early_stop=args.early_stop)
+                           playout_cap_prob=args.playout_cap_prob, value_q_weight=args.value_q_weight, **args.options)
     if world > 1:
         from .launch import guarded
 

@@ -13,17 +13,19 @@ import numpy as np
 
 from .boundary import deliver, kind_of
 from .engine import SelfPlayEngine
+from .options import SearchOptions, proven_moves, search_move
 from .parameters import C_PUCT
+from .stopcfg import StopPoll
 
 
 class BatchedMatch:
     def __init__(self, evaluator_red, evaluator_black, n_boards: int, n_playout: int = 400, c_puct: float = C_PUCT,
                  seed: int = 0, device: int = 0, max_plies: int = 0, temp: float = 1e-3, solver: bool = False, search=None, early_stop=None):
-        """``early_stop``: a dict of ``engine.set_early_stop``'s arguments (``stopcfg.make_early_stop``): a board stops searching its move
-        when the outcome can no longer change, and the move's loop ends when ``engine.searching()``, asked every 16 steps, is 0; None: off.
-        ``search``: a dict of ``engine.set_search``'s arguments (first-play urgency, visit-scaled c_puct) for both sides; None: the
-        reference's PUCT. ``solver``: both sides search with the MCTS-solver (``engine.set_solver``) and play the proven move where the root is
-        decided (``engine.proof_moves``); every other move is drawn as without it."""
+        """``solver`` / ``search`` / ``early_stop``: the engine options (``options.OPTIONS``: what ``engine.set_solver`` / ``set_search`` /
+        ``set_early_stop`` take; None / False: off), for both sides alike. With the solver the proven move is played where the root is decided
+        (``options.proven_moves``); with the early stop the move's loop ends when no board would select any more (``options.search_move``)."""
+        self.options = o = SearchOptions(n_playout, solver=solver, search=search, early_stop=early_stop)
+        self.solver, self.search_cfg, self.early_stop = o.keywords().values()
         self.ev = {1: evaluator_red, 0: evaluator_black}
         self.B = n_boards
         self.n_playout = n_playout
@@ -31,17 +33,8 @@ class BatchedMatch:
         # eps = 0: the sampling distribution is pi itself (mcts.py:227), drawn from the board's Philox stream
         self.engine = SelfPlayEngine(n_boards, n_playout=n_playout, c_puct=c_puct, eps=0.0, alpha=0.2, temp=temp,
                                      seed=seed, device=device, max_plies=max_plies, mirror=False)
-        self.solver = bool(solver)
         self.proven_moves = 0
-        if self.solver:
-            self.engine.set_solver(True)
-        self.search_cfg = None if search is None else dict(search)
-        if self.search_cfg is not None:
-            self.engine.set_search(**self.search_cfg)
-        from .stopcfg import StopPoll
-        self.early_stop = None if early_stop is None else dict(early_stop)
-        if self.early_stop is not None:
-            self.engine.set_early_stop(**self.early_stop)
+        o.apply(self.engine)
         self._poll = StopPoll(self.engine, self.early_stop)
         self.before_move = self.on_move = None
         self._temps = np.full(n_boards, temp, np.float64)
@@ -52,18 +45,11 @@ class BatchedMatch:
         played (host int32 [B], -1 on finished boards)."""
         e = self.engine
         ev = self.ev[turn]
-        leaf = e.select_leaves()
-        for i in range(self.n_playout):
-            if self._poll.done(i):               # no board would select any more: no leaf is pending either
-                break
-            leaf = deliver(e, kind_of(ev), *ev(leaf), i + 1 == self.n_playout)
+        search_move(e, self.n_playout, lambda leaf, last: deliver(e, kind_of(ev), *ev(leaf), last), self._poll)
         if self.before_move is not None:
             self.before_move(self)
-        forced = None
-        if self.solver:
-            forced = e.proof_moves()
-            forced[e.game_status()["over"] != 0] = -1
-            self.proven_moves += int((forced >= 0).sum())
+        forced, proven = proven_moves(e, self.solver)
+        self.proven_moves += proven
         moves = e.finish_move(forced_moves=forced, temps=self._temps, keep_tree=False).cpu().numpy()
         if self.on_move is not None:
             self.on_move(self, moves)

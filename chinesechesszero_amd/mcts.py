@@ -22,6 +22,7 @@ import torch
 
 from .boundary import PlayoutTicker, deliver, describe, kind_of, may_graph
 from .engine import SelfPlayEngine
+from .options import SearchOptions
 from .parameters import ALPHA, C_PUCT, EPS
 from .searchcfg import resolve_scouts
 from .selfplay import GraphedStep, ScoutedSearch
@@ -82,17 +83,15 @@ class MCTS:
         MCTS-solver (``SelfPlayEngine.set_solver``): decided positions are proven in the tree, :meth:`proof_move` names the move
         a proven root asks for."""
         self.policy = policy_value_fn
-        self.search_cfg = None if search is None else dict(search)
         self.width = 1 if width is None else int(width)
         if not 1 <= self.width <= 64:
             raise ValueError(f"width must be in 1..64 (got {width})")
-        if self.width > 1:
-            if scouts or solver or search is not None:
-                raise ValueError("width > 1 (the wide search) excludes scouts, the solver and the search parameters")
-            scouts = 0
+        self.options = SearchOptions(n_playout, width=self.width, solver=solver, search=search)
+        self.solver, self.search_cfg = self.options.keywords().values()
+        if self.width > 1 and scouts:
+            raise ValueError("width > 1 (the wide search) excludes scouts")
         self._wide = None
-        scouts = resolve_scouts(self.search_cfg, scouts)
-        self.solver = bool(solver)
+        scouts = 0 if self.width > 1 else resolve_scouts(self.search_cfg, scouts)
         self.c_puct = c_puct
         self.n_playout = n_playout
         self.red_history = None
@@ -138,10 +137,7 @@ class MCTS:
                                           strict=True)   # the reference's tree and game are unbounded: a prune or an adjudication raises here
             if self.scouts:
                 self._engine.set_scouts(self.scouts)
-            if self.solver:
-                self._engine.set_solver(True)
-            if self.search_cfg is not None:
-                self._engine.set_search(**self.search_cfg)
+            self.options.apply(self._engine)
         return self._engine
 
     def _forced(self, mid: int):

@@ -1,0 +1,254 @@
+"""The engine options of the search front ends -- resign, root exploration, the Gumbel root, the MCTS-solver, the search parameters, the
+early stop -- each described ONCE (:data:`OPTIONS`), and what a front end does with them (:class:`SearchOptions`): refuse what excludes
+what, call the setters in one order, report. Also the command line of resign / root exploration / Gumbel in the shape of ``searchcfg`` /
+``stopcfg`` (which keep the search parameters' and the early stop's), and the move of the arg-max front ends. No GPU here. Adding an
+option: ``ccz_set_x`` on the C side (which refuses what it excludes), the setter in ``engine.py``, ONE entry in ``OPTIONS`` (and a rule
+in ``SearchOptions.__init__`` if it excludes another), the keyword on the front ends that allow it."""
+from __future__ import annotations
+
+from collections import namedtuple
+
+from .searchcfg import mean_leaf_depth
+from .stopcfg import stop_report
+
+RESIGN_MOVES, RESIGN_MIN_PLY, RESIGN_PLAYON, FORCED_PLAYOUTS = 2, 30, 0.1, 2.0
+GUMBEL_CONSIDERED, GUMBEL_C_VISIT, GUMBEL_C_SCALE = 16, 50.0, 1.0
+
+
+# ---------------------------------------------------------------------- fragments of the collector's periodic log line
+def format_resign(r: dict) -> str:
+    """``r`` = ``SelfPlayEngine.resign_stats()``: games resigned, the false-positive rate ``playon_won / playon_games`` of the games
+    played on, and their mean plies after the fire ply."""
+    n = r["playon_games"]
+    fp = f"{r['playon_won'] / n:.3f}" if n else "n/a"
+    after = f"{r['playon_plies_after'] / n:.1f}" if n else "n/a"
+    return f", resigned {r['resigned_games']}, play-on {n} (false positives {fp}, mean plies after {after})"
+
+
+def format_exploration(x: dict, sims: int) -> str:
+    """``x`` = ``SelfPlayEngine.exploration_stats()``, ``sims`` = the simulations backed up so far (``stats()['sims']``, fast moves
+    included): explored moves, forced selections per explored move, and the visits pruned from the policy targets as a share of
+    the simulations run."""
+    n = x["explored_moves"]
+    forced = f"{x['forced_selections'] / n:.2f}" if n else "n/a"
+    share = f"{x['visits_pruned'] / sims:.4f}" if sims else "n/a"
+    return f", explored moves {n}, forced selections per move {forced}, pruned share of visits {share} ({x['children_pruned']} children dropped)"
+
+
+def format_gumbel(x: dict) -> str:
+    """``x`` = ``SelfPlayEngine.gumbel_stats()``: the moves played by the Gumbel root rule, the mean number of moves considered, and the
+    share of them whose played move was not the most visited one."""
+    n = x["gumbel_moves"]
+    m = f"{x['considered_sum'] / n:.2f}" if n else "n/a"
+    off = f"{x['offvisit_moves'] / n:.4f}" if n else "n/a"
+    return f", gumbel moves {n}, mean considered {m}, off-visit share {off}"
+
+
+def format_search(cfg: dict, stats: dict) -> str:
+    """``cfg`` = ``SelfPlayEngine.search_settings()``, ``stats`` = ``SelfPlayEngine.stats()``: the urgency of the tree and of the root,
+    the growth of c_puct, and the mean depth of the leaves selected so far."""
+    def fpu(mode, value):
+        return {0: "off", 1: f"reduction {value:g}", 2: f"absolute {value:g}"}[int(mode)]
+    growth = f"base {cfg['c_base']:g} factor {cfg['c_factor']:g}" if cfg["c_factor"] else "constant"
+    return (f", fpu {fpu(cfg['fpu_mode'], cfg['fpu_value'])} (root {fpu(cfg['fpu_root_mode'], cfg['fpu_root_value'])}), c_puct {growth}, "
+            f"mean leaf depth {mean_leaf_depth(stats):.2f}")
+
+
+def engine_stop_report(e) -> dict:
+    """:func:`stopcfg.stop_report` of an engine's counters so far (syncs)."""
+    st = e.stats()
+    return stop_report(e.early_stop_stats(), st["moves"], st["sims"])
+
+
+# ``setter``: the SelfPlayEngine method that takes the option's dict; ``what``: its name in messages; ``log(engine)``: its fragment of the log
+# line; ``report(engine)``: its entries in the JSON of Arena.result / BatchedAnalysis.summary (None: none); ``of_scalar``: the dict of a value
+# that is not one; ``device_only``: why it needs sampling='device' (None: it does not); ``one_game``: it also runs in the collector's one-game loop
+Option = namedtuple("Option", "setter what log report of_scalar device_only one_game", defaults=(None, dict, None, False))
+SOLVER_LOG = ", nodes proven {nodes_proven}, simulations ended at a proven node {proven_stops}, roots proven {roots_proven}"
+STOP_LOG = ", early stops {single_reply} single reply / {visit_gap} gap / {kld_gain} kld, {mean_sims_per_move} simulations per move"
+
+# (in the order SearchOptions.apply calls the setters and log_line joins the fragments)
+OPTIONS = {
+    "resign": Option("set_resign", "resignation", lambda e: format_resign(e.resign_stats()), of_scalar=lambda x: {"threshold": float(x)},
+                     device_only="with host sampling every move is forced, and a forced board never resigns"),
+    "root_exploration": Option("set_root_exploration", "root exploration", lambda e: format_exploration(e.exploration_stats(), e.stats()["sims"]),
+                               device_only="the host sampler mixes Dirichlet noise into pi after the search"),
+    "gumbel": Option("set_gumbel", "the Gumbel root search", lambda e: format_gumbel(e.gumbel_stats()), of_scalar=lambda x: {},
+                     device_only="the rule plays the move itself, a host-sampled move would be forced over it"),
+    "solver": Option("set_solver", "the solver option of the collector", lambda e: SOLVER_LOG.format(**e.solver_stats()),
+                     report=lambda e: {"solver": e.solver_stats()}, of_scalar=lambda x: {"enabled": True}),
+    "search": Option("set_search", "the search parameters", lambda e: format_search(e.search_settings(), e.stats()),
+                     report=lambda e: {"search": e.search_settings(), "mean_leaf_depth": mean_leaf_depth(e.stats())}, one_game=True),
+    "early_stop": Option("set_early_stop", "the early stop of the collector", lambda e: STOP_LOG.format(**engine_stop_report(e)),
+                         report=lambda e: {"early_stop": engine_stop_report(e)}),
+}
+
+
+class SearchOptions:
+    """The options of ONE front end, from the keywords it was given (``resign=..., solver=..., ...``: the options it allows). None / False: off;
+    a dict is copied, another value goes through ``of_scalar``; ``gumbel`` searches ``n_playout`` (the front end's simulations per move) unless
+    it says otherwise. ``sampling``: ``BatchedSelfPlay``'s; ``batched``: False on the collector's one-game path; ``width``: ``wide.WideSearch``'s.
+    Raises ValueError for every combination that is refused before an engine exists (``csrc/cczero.hip`` refuses them again, and more: it stays the
+    authority). Then every allowed option is an attribute: its dict, None when off (``solver``: a bool); ``on``: those that are on, in OPTIONS' order."""
+
+    def __init__(self, n_playout=None, sampling: str = "device", batched: bool = True, width: int = 1, **given):
+        self.on = on = {}
+        for name, o in OPTIONS.items():
+            if name in given:
+                cfg = given.pop(name)
+                if cfg is not None and cfg is not False and (cfg or name != "solver"):
+                    on[name] = dict(cfg) if isinstance(cfg, dict) else o.of_scalar(cfg)
+                setattr(self, name, on.get(name) if name != "solver" else name in on)
+        if given:
+            raise TypeError(f"no such search option: {', '.join(given)}")
+        if "gumbel" in on:
+            on["gumbel"].setdefault("n_sims", n_playout)
+        for name in on:
+            if sampling != "device" and OPTIONS[name].device_only:
+                raise ValueError(f"{name} needs sampling='device': {OPTIONS[name].device_only}")
+            if not batched and not OPTIONS[name].one_game:
+                raise ValueError(f"{OPTIONS[name].what} runs on the batched path: n_boards (--boards) must be > 1")
+        if "gumbel" in on and "root_exploration" in on:
+            raise ValueError("gumbel and root_exploration (--gumbel, --root-noise-eps) exclude each other: the Gumbel draw is the root's exploration")
+        if "gumbel" in on and "early_stop" in on:
+            raise ValueError("the early stop (--stop-*) and the Gumbel root search (--gumbel) exclude each other: sequential halving plans the whole budget")
+        if int(width) > 1 and any(name in on for name in ("solver", "search", "early_stop")):
+            raise ValueError("width > 1 (the wide search) excludes scouts, the solver, the search parameters and the early stop")
+
+    def keywords(self) -> dict:
+        """``{keyword: value}`` of every allowed option, on or off, as a front end takes them (and in OPTIONS' order)."""
+        return {name: getattr(self, name) for name in OPTIONS if hasattr(self, name)}
+
+    def apply(self, engine):
+        """Call the setters of the options that are on, and no others: resign, root exploration, gumbel, solver, search, early stop.
+        Every setter writes its own settings block only, so the order decides nothing."""
+        for name, cfg in self.on.items():
+            getattr(engine, OPTIONS[name].setter)(**cfg)
+
+    def report(self, engine) -> dict:
+        """The entries of the options that are on in a front end's JSON result (syncs)."""
+        return {k: v for name in self.on if OPTIONS[name].report for k, v in OPTIONS[name].report(engine).items()}
+
+    def log_line(self, engine) -> str:
+        """The fragments of the options that are on, for the collector's periodic log line (empty with none on; syncs)."""
+        return "".join(OPTIONS[name].log(engine) for name in self.on)
+
+
+# ---------------------------------------------------------------------- the move of an arg-max front end
+def search_move(engine, n_steps: int, step, poll):
+    """One move's search of ``Arena`` / ``BatchedMatch``: select, then up to ``n_steps`` times ``step(leaf, last) -> next leaf batch``;
+    ``poll`` (:class:`stopcfg.StopPoll`) ends the loop when no board would select any more (no leaf is pending then either)."""
+    leaf = engine.select_leaves()
+    for i in range(n_steps):
+        if poll.done(i):
+            break
+        leaf = step(leaf, i + 1 == n_steps)
+
+
+def proven_moves(engine, solver: bool, over=None):
+    """``(forced_moves for finish_move, how many of them are proven)`` after a search with the MCTS-solver: the proven move where a running game's
+    root is decided, -1 (the sampler's choice) elsewhere; ``(None, 0)`` with the solver off. ``over``: ``game_status()["over"]`` if already read."""
+    if not solver:
+        return None, 0
+    forced = engine.proof_moves()
+    forced[(engine.game_status()["over"] if over is None else over) != 0] = -1
+    return forced, int((forced >= 0).sum())
+
+
+# ---------------------------------------------------------------------- command lines: make_x (ValueError), add_x_args, x_from_args (ap.error)
+def _from_args(ap, a, main: str, off: str, extras, make, *values):
+    """``make(*values)``; a ValueError ends in ``ap.error``, and so does an extra flag without the main one (it would silently do nothing)."""
+    def is_set(flag):
+        v = getattr(a, flag[2:].replace("-", "_"), None)
+        return v is not None and v is not False
+    if not is_set(main) and any(map(is_set, extras)):
+        ap.error(f"{', '.join(filter(is_set, extras))} without {main}: {off}")
+    try:
+        return make(*values)
+    except ValueError as ex:
+        ap.error(str(ex))
+
+
+def make_resign(threshold, moves=None, min_ply=None, playon=None, with_playon: bool = True):
+    """The dict of ``SelfPlayEngine.set_resign``'s arguments (None without a threshold); ``with_playon`` False (a match): no ``p_playon``."""
+    if threshold is None:
+        return None
+    cfg = {"threshold": threshold, "consecutive": RESIGN_MOVES if moves is None else moves, "min_ply": RESIGN_MIN_PLY if min_ply is None else min_ply}
+    return dict(cfg, p_playon=RESIGN_PLAYON if playon is None else playon) if with_playon else cfg
+
+
+def add_resign_args(ap, playon: bool, what: str = "resignation"):
+    """--resign-threshold / --resign-moves / --resign-min-ply, and with ``playon`` (the collector) --resign-playon."""
+    ap.add_argument("--resign-threshold", type=float, default=None, help=f"{what}: the side to move resigns when its root value stayed below this "
+                    "(in [-1, 0]); absent = off" + (". Root values are then recorded with every ply (root_values.npy)" if playon else ""))
+    ap.add_argument("--resign-moves", type=int, default=None, help=f"... for this many of its full-search moves in a row (default {RESIGN_MOVES})")
+    ap.add_argument("--resign-min-ply", type=int, default=None, help=f"... and not before this ply (default {RESIGN_MIN_PLY})")
+    if playon:
+        ap.add_argument("--resign-playon", type=float, default=None,
+                        help=f"fraction of such games played on to measure the false positives (default {RESIGN_PLAYON}, AlphaGo Zero's)")
+
+
+def resign_from_args(ap, a):
+    return _from_args(ap, a, "--resign-threshold", "resignation is off", ("--resign-moves", "--resign-min-ply", "--resign-playon"), make_resign,
+                      a.resign_threshold, a.resign_moves, a.resign_min_ply, getattr(a, "resign_playon", None), hasattr(a, "resign_playon"))
+
+
+def make_root_exploration(eps, alpha=None, forced_playouts=None, prune_targets: bool = True):
+    """The dict of ``SelfPlayEngine.set_root_exploration``'s arguments (None without ``eps``). ValueError: what ``ccz_set_root_exploration`` refuses."""
+    if eps is None:
+        return None
+    if not 0.0 <= eps <= 1.0:
+        raise ValueError(f"--root-noise-eps must be in [0, 1] (got {eps})")
+    if alpha is not None and not alpha > 0.0:
+        raise ValueError(f"--root-noise-alpha must be > 0 (got {alpha})")
+    if forced_playouts is not None and not forced_playouts >= 0.0:
+        raise ValueError(f"--forced-playouts must be >= 0 (got {forced_playouts})")
+    return {"eps": eps, "alpha": alpha, "forced_k": FORCED_PLAYOUTS if forced_playouts is None else forced_playouts, "prune_targets": bool(prune_targets)}
+
+
+def add_root_exploration_args(ap):
+    """--root-noise-eps / --root-noise-alpha / --forced-playouts / --no-target-pruning."""
+    ap.add_argument("--root-noise-eps", type=float, default=None, help="exploration inside the search on full-search moves: weight of the "
+                    "Dirichlet noise in the ROOT's priors (in [0, 1]); absent = off (the noise is mixed into pi after the search)")
+    ap.add_argument("--root-noise-alpha", type=float, default=None, help="... its Dirichlet alpha (default: the sampler's)")
+    ap.add_argument("--forced-playouts", type=float, default=None, help=f"... forced playouts: a root child is searched until N >= sqrt(k P' S) "
+                    f"(default k = {FORCED_PLAYOUTS}, KataGo's; 0 = none)")
+    ap.add_argument("--no-target-pruning", action="store_true", default=False, help="... keep the forced visits in the recorded policy targets")
+
+
+def root_exploration_from_args(ap, a):
+    return _from_args(ap, a, "--root-noise-eps", "root exploration is off", ("--root-noise-alpha", "--forced-playouts", "--no-target-pruning"),
+                      make_root_exploration, a.root_noise_eps, a.root_noise_alpha, a.forced_playouts, not a.no_target_pruning)
+
+
+def make_gumbel(on, n_sims, considered=None, c_visit=None, c_scale=None):
+    """The dict of ``SelfPlayEngine.set_gumbel``'s arguments (None when not ``on``). ValueError: what ``ccz_set_gumbel`` would refuse."""
+    if not on:
+        return None
+    if considered is not None and not 2 <= considered <= 128:
+        raise ValueError(f"--gumbel-considered must be in 2..128 (got {considered})")
+    for name, v in (("--gumbel-c-visit", c_visit), ("--gumbel-c-scale", c_scale)):
+        if v is not None and not 0.0 <= v < float("inf"):
+            raise ValueError(f"{name} must be finite and >= 0 (got {v})")
+    if n_sims < 1:
+        raise ValueError(f"--gumbel needs --playout >= 1 (got {n_sims})")
+    return {"n_sims": n_sims, "max_considered": GUMBEL_CONSIDERED if considered is None else considered,
+            "c_visit": GUMBEL_C_VISIT if c_visit is None else c_visit, "c_scale": GUMBEL_C_SCALE if c_scale is None else c_scale}
+
+
+def add_gumbel_args(ap):
+    """--gumbel / --gumbel-considered / --gumbel-c-visit / --gumbel-c-scale."""
+    ap.add_argument("--gumbel", action="store_true", default=False, help="batched path: Gumbel root search -- one Gumbel draw per move, sequential "
+                    "halving over the considered moves within the move's simulations, the winner is played and pi' = softmax(logits + "
+                    "sigma(completed Q)) is the recorded policy target. With --playout-cap-fast the pi' of a fast ply is a valid target too "
+                    "(it improves on the prior at any simulation count); such plies are still flagged and the trainer treats the flag as before. "
+                    "Not with --root-noise-eps")
+    ap.add_argument("--gumbel-considered", type=int, default=None, help=f"... moves considered at the root, 2..128 (default {GUMBEL_CONSIDERED})")
+    ap.add_argument("--gumbel-c-visit", type=float, default=None, help=f"... c_visit of sigma, >= 0 (default {GUMBEL_C_VISIT})")
+    ap.add_argument("--gumbel-c-scale", type=float, default=None, help=f"... c_scale of sigma, >= 0 (default {GUMBEL_C_SCALE})")
+
+
+def gumbel_from_args(ap, a):
+    """(``a.playout``: the simulations of a move.)"""
+    return _from_args(ap, a, "--gumbel", "the Gumbel root search is off", ("--gumbel-considered", "--gumbel-c-visit", "--gumbel-c-scale"),
+                      make_gumbel, a.gumbel, a.playout, a.gumbel_considered, a.gumbel_c_visit, a.gumbel_c_scale)

@@ -13,7 +13,9 @@ import numpy as np
 
 from .boundary import PlayoutTicker, WeightsWatch, capture, deliver, describe, kind_of, may_graph, need_version
 from .engine import SelfPlayEngine
+from .options import SearchOptions
 from .parameters import ALPHA, C_PUCT, EPS
+from .stopcfg import StopPoll
 
 
 class GraphedStep:
@@ -156,14 +158,14 @@ class BatchedSelfPlay:
         """``early_stop``: a dict of :meth:`SelfPlayEngine.set_early_stop`'s arguments (``single_reply``, ``gap_factor``,
         ``kld_interval``, ``min_gain``, ``min_sims``; see :func:`stopcfg.make_early_stop`): a board stops searching its move when the
         outcome can no longer change or its visit distribution has stopped moving, and selects nothing for the rest of the move's
-        ``n_playout`` lockstep steps (no evaluator row with an evaluation cache). Not with ``gumbel``. None (default): off.
+        ``n_playout`` lockstep steps (no evaluator row with an evaluation cache). None (default): off. (``options.SearchOptions``: what
+        excludes what -- ``gumbel`` this and ``root_exploration`` --, and why ``resign``, ``root_exploration``, ``gumbel`` need device sampling.)
         ``search``: a dict of :meth:`SelfPlayEngine.set_search`'s arguments (``fpu_mode``, ``fpu_value``, ``fpu_root_mode``,
         ``fpu_root_value``, ``c_base``, ``c_factor``): first-play urgency and the visit-scaled c_puct inside the tree. Works with every
         other option here (under ``gumbel`` from depth 1). None (default): off, the reference's PUCT.
         ``gumbel``: True, or a dict of :meth:`SelfPlayEngine.set_gumbel`'s arguments (``n_sims`` defaults to ``n_playout``;
         ``max_considered``, ``c_visit``, ``c_scale``): Gumbel root search with sequential halving; pi' from the completed Q is the
-        recorded policy target of every move, fast moves of ``playout_cap`` included (they still carry ``REC_FAST``). Device
-        sampling only (the rule plays its own move), and not together with ``root_exploration``. None / False (default): off.
+        recorded policy target of every move, fast moves of ``playout_cap`` included (they still carry ``REC_FAST``). None / False: off.
         ``solver``: search with the MCTS-solver (:meth:`SelfPlayEngine.set_solver`). Only the search changes: moves are sampled,
         recorded and targeted as without it.
         ``playout_cap`` = ``(n_fast, p_full)``: playout-cap randomisation -- every move of every board is a full search of
@@ -175,26 +177,18 @@ class BatchedSelfPlay:
         first simulation; :meth:`simulate` draws nothing and searches with the budgets the engine holds.
         None (default): every board searches ``n_playout`` simulations, as ever.
         ``resign``: a threshold in [-1, 0], or a dict of :meth:`SelfPlayEngine.set_resign`'s arguments (``threshold``,
-        ``consecutive``, ``min_ply``, ``p_playon``): self-play resignation with play-on calibration. Device sampling only: with
-        host sampling every move is forced and a forced board never resigns. None (default): off.
+        ``consecutive``, ``min_ply``, ``p_playon``): self-play resignation with play-on calibration. None (default): off.
         ``root_exploration``: a dict of :meth:`SelfPlayEngine.set_root_exploration`'s arguments (``eps``, and optionally ``alpha``,
         ``forced_k``, ``prune_targets``): the Dirichlet noise acts on the root's priors inside the search, with forced playouts and
-        policy target pruning, on full-search moves; fast moves of ``playout_cap`` are left alone. Device sampling only: the host
-        sampler would mix its own noise into the pruned pi a second time. None (default): off.
+        policy target pruning, on full-search moves; fast moves of ``playout_cap`` are left alone. None (default): off.
         ``version_fn() -> hashable``: what tells the evaluation cache (and a captured hipGraph) that the evaluator's weights
         changed; default: ``weights_version`` of the evaluator's owner. An evaluator that accepts a plan but exposes neither is
         refused: its cached evaluations could never be invalidated."""
         if sampling not in ("device", "numpy"):
             raise ValueError("sampling must be 'device' (Philox on the GPU) or 'numpy' (reference-exact host RNG)")
-        if resign is not None and sampling != "device":
-            raise ValueError("resign needs sampling='device': with host sampling every move is forced, and a forced board never resigns")
-        if root_exploration is not None and sampling != "device":
-            raise ValueError("root_exploration needs sampling='device': the host sampler mixes Dirichlet noise into pi after the search")
-        if gumbel is not None and gumbel is not False:
-            if sampling != "device":
-                raise ValueError("gumbel needs sampling='device': the rule plays the move itself, a host-sampled move would be forced over it")
-            if root_exploration is not None:
-                raise ValueError("gumbel and root_exploration exclude each other: the Gumbel draw is the root's exploration")
+        self.options = o = SearchOptions(n_playout, sampling, resign=resign, root_exploration=root_exploration, gumbel=gumbel, solver=solver,
+                                         search=search, early_stop=early_stop)       # (ValueError: what excludes what)
+        self.resign, self.root_exploration, self.gumbel, self.solver, self.search_cfg, self.early_stop = o.keywords().values()
         self.playout_cap = None
         if playout_cap is not None:
             n_fast, p_full = playout_cap
@@ -206,30 +200,7 @@ class BatchedSelfPlay:
         self.evaluator = evaluator
         self.engine = SelfPlayEngine(n_boards, n_playout=n_playout, c_puct=c_puct, eps=eps, alpha=alpha, temp=temp,
                                      seed=seed, board_id_base=board_id_base, device=device, **engine_kw)
-        self.resign = None
-        if resign is not None:
-            self.resign = dict(resign) if isinstance(resign, dict) else {"threshold": float(resign)}
-            self.engine.set_resign(**self.resign)
-        self.root_exploration = None
-        if root_exploration is not None:
-            self.root_exploration = dict(root_exploration)
-            self.engine.set_root_exploration(**self.root_exploration)
-        self.gumbel = None
-        if gumbel is not None and gumbel is not False:
-            self.gumbel = dict(gumbel) if isinstance(gumbel, dict) else {}
-            self.gumbel.setdefault("n_sims", n_playout)
-            self.engine.set_gumbel(**self.gumbel)
-        self.solver = bool(solver)
-        if self.solver:
-            self.engine.set_solver(True)
-        self.search_cfg = None
-        if search is not None:
-            self.search_cfg = dict(search)
-            self.engine.set_search(**self.search_cfg)
-        self.early_stop = None
-        if early_stop is not None:
-            self.early_stop = dict(early_stop)
-            self.engine.set_early_stop(**self.early_stop)
+        o.apply(self.engine)
         self.B = n_boards
         self.n_playout = n_playout
         self.sampling = sampling
@@ -324,22 +295,16 @@ class BatchedSelfPlay:
         self._ticker.on_playout = None   # (the caller's callback is not kept past the call: it may refer to this object)
         return moves
 
-    def stop_report(self) -> dict:
-        """Stops per reason and the mean simulations per move so far (:func:`stopcfg.stop_report`; syncs)."""
-        from .stopcfg import stop_report
-        st = self.engine.stats()
-        return stop_report(self.engine.early_stop_stats(), st["moves"], st["sims"])
-
     def search(self, on_playout=None, hooks=None, poll: bool = False):
         """The simulations that are left of the current move (all ``n_playout`` from a move's start) WITHOUT playing it: the roots
         can be read (``engine.root_children()``) before :meth:`finish_move`. ``poll`` (an arg-max front end with ``early_stop``):
-        ``engine.searching()`` is asked every 16 steps and the move's loop ends when no board would select any more."""
-        if poll and self.early_stop is not None and self._graph is None:
-            while self.n_playout - self._sim > 1:
-                if self._sim > 0 and self._sim % 16 == 0 and self.engine.searching() == 0:   # (no leaf is pending either)
-                    self._sim, self._leaf, self._ticker.acc = 0, None, 0
-                    return
-                self.advance(1, hooks=hooks, on_playout=on_playout)
+        ``engine.searching()`` is asked every ``stopcfg.POLL_EVERY`` steps and the move's loop ends when no board would select any more."""
+        stop = StopPoll(self.engine, self.early_stop if poll and self._graph is None else None)
+        while stop.on and self.n_playout - self._sim > 1:
+            if stop.done(self._sim):   # (no leaf is pending either)
+                self._sim, self._leaf, self._ticker.acc = 0, None, 0
+                return
+            self.advance(1, hooks=hooks, on_playout=on_playout)
         left = self.n_playout - self._sim
         if left > 1:
             self.advance(left - 1, hooks=hooks, on_playout=on_playout)

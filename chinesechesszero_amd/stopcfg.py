@@ -8,6 +8,7 @@ SINGLE_REPLY, VISIT_GAP, KLD_GAIN = 1, 2, 3
 REASONS = {SINGLE_REPLY: "single_reply", VISIT_GAP: "visit_gap", KLD_GAIN: "kld_gain"}
 GAP_DEFAULT = 1.0          # the exact rule: the runner-up cannot catch the leader
 KLD_INTERVAL = 16
+POLL_EVERY = 16            # steps between two questions of an arg-max front end's move loop to the engine (StopPoll)
 
 
 def make_early_stop(single_reply=False, gap=None, kld_gain=None, kld_interval=None, min_sims=None):
@@ -71,7 +72,7 @@ class StopPoll:
     """The move loop of an arg-max front end: ``done(step)`` is True when no board would select any more -- asked of the engine
     every ``every`` steps (one small kernel and a 4-byte copy), never when the feature is off."""
 
-    def __init__(self, engine, cfg, every: int = 16):
+    def __init__(self, engine, cfg, every: int = POLL_EVERY):
         self.engine, self.on, self.every = engine, cfg is not None, int(every)
 
     def done(self, step: int) -> bool:

@@ -14,6 +14,7 @@ import sys
 import numpy as np
 
 from .game import RED, Board, Move, _SYMBOL
+from .options import SearchOptions
 from .parameters import C_PUCT, PLAYOUT
 
 ENGINE_NAME = "cczero-mi355x"
@@ -86,6 +87,21 @@ class UciLoop:
         o = self.search_opts
         return make_search(o.get("fpureduction"), o.get("fpuabsolute"), None, None, o.get("cpuctbase"), o.get("cpuctfactor"))
 
+    def _set(self, **new) -> bool:
+        """Set ``solver`` / ``width`` / ``search_opts`` if they still go together (``SearchOptions``); else say why not and leave all as it was."""
+        old = {k: getattr(self, k) for k in new}
+        vars(self).update(new)
+        try:
+            self.width = int(self.width)
+            if not 1 <= self.width <= 64:
+                raise ValueError(f"Width {self.width} must be in 1..64")
+            SearchOptions(self.n_playout, width=self.width, solver=self.solver, search=self._search())
+        except ValueError as e:
+            vars(self).update(old)
+            self._say(f"info string error {e}")
+            return False
+        return True
+
     def _say(self, s: str):
         print(s, file=self.out, flush=True)
 
@@ -150,35 +166,20 @@ class UciLoop:
         elif cmd == "setoption" and len(tok) >= 5 and tok[1] == "name" and tok[2].lower() == "multipv":
             self.multipv = max(1, min(128, int(tok[4])))
         elif cmd == "setoption" and len(tok) >= 5 and tok[1] == "name" and tok[2].lower() == "solver":
-            if tok[4].lower() == "true" and self.width > 1:
-                self._say("info string error the solver and Width > 1 exclude each other")
-            else:
-                self.solver = tok[4].lower() == "true"
+            self._set(solver=tok[4].lower() == "true")
         elif cmd == "setoption" and len(tok) >= 5 and tok[1] == "name" and tok[2].lower() == "width":
-            try:
-                w = int(tok[4])
-                if not 1 <= w <= 64:
-                    raise ValueError(f"Width {w} must be in 1..64")
-                if w > 1 and (self.solver or self.search_opts):
-                    raise ValueError("Width > 1 excludes the solver and the search parameters")
-            except ValueError as e:
-                self._say(f"info string error {e}")
-            else:
-                self.width = w
+            self._set(width=tok[4])
         elif cmd == "setoption" and len(tok) >= 5 and tok[1] == "name" and tok[2].lower() in ("fpureduction", "fpuabsolute", "cpuctbase", "cpuctfactor"):
             name = tok[2].lower()
-            old = dict(self.search_opts)
+            opts = dict(self.search_opts)
             try:
-                if self.width > 1:
-                    raise ValueError("the search parameters and Width > 1 exclude each other")
-                self.search_opts[name] = float(tok[4])
-                if name in ("fpureduction", "fpuabsolute"):      # the later of the two forms stands
-                    self.search_opts.pop("fpuabsolute" if name == "fpureduction" else "fpureduction", None)
-                self._search()
+                opts[name] = float(tok[4])
             except ValueError as e:
-                self.search_opts = old
                 self._say(f"info string error {e}")
-            else:
+                return True
+            if name in ("fpureduction", "fpuabsolute"):      # the later of the two forms stands
+                opts.pop("fpuabsolute" if name == "fpureduction" else "fpureduction", None)
+            if self._set(search_opts=opts):
                 self._say("info string search parameters set: scout slots are off for this session")
         elif cmd == "ucinewgame":
             self.board = Board()

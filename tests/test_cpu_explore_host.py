@@ -40,7 +40,8 @@ def test_defaults_and_what_reaches_the_pipeline():
 
 
 def test_log_fields_from_fabricated_counters():
-    from chinesechesszero_amd.collect import CollectPipeline, format_exploration
+    from chinesechesszero_amd.collect import format_exploration
+    from chinesechesszero_amd.options import OPTIONS, SearchOptions
     x = {"explored_moves": 200, "forced_selections": 1500, "visits_pruned": 12000, "children_pruned": 3100}
     line = format_exploration(x, 80000)
     assert line == ", explored moves 200, forced selections per move 7.50, pruned share of visits 0.1500 (3100 children dropped)"
@@ -54,14 +55,8 @@ def test_log_fields_from_fabricated_counters():
         def stats(self):
             return {"sims": 80000}
 
-    class _SelfPlay:
-        engine = _Engine()
-
-    pipe = CollectPipeline.__new__(CollectPipeline)
-    pipe.root_exploration, pipe.selfplay = {"eps": 0.25}, _SelfPlay()
-    assert pipe.exploration_report() == line
-    pipe.root_exploration = None
-    assert pipe.exploration_report() == ""          # off: the log line is what it was
+    assert OPTIONS["root_exploration"].log(_Engine()) == line == SearchOptions(8, root_exploration={"eps": 0.25}).log_line(_Engine())
+    assert SearchOptions(8, root_exploration=None).log_line(_Engine()) == ""          # off: the log line is what it was
 
 
 def test_selfplay_refuses_host_sampling_before_it_builds_an_engine():

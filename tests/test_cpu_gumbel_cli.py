@@ -59,7 +59,8 @@ def test_the_help_text_says_what_a_fast_ply_records():
 
 
 def test_log_fields_from_fabricated_counters():
-    from chinesechesszero_amd.collect import CollectPipeline, format_gumbel
+    from chinesechesszero_amd.collect import format_gumbel
+    from chinesechesszero_amd.options import OPTIONS, SearchOptions
     x = {"gumbel_moves": 400, "considered_sum": 6100, "offvisit_moves": 30}
     line = format_gumbel(x)
     assert line == ", gumbel moves 400, mean considered 15.25, off-visit share 0.0750"
@@ -70,14 +71,8 @@ def test_log_fields_from_fabricated_counters():
         def gumbel_stats(self):
             return x
 
-    class _SelfPlay:
-        engine = _Engine()
-
-    pipe = CollectPipeline.__new__(CollectPipeline)
-    pipe.gumbel, pipe.selfplay = {}, _SelfPlay()
-    assert pipe.gumbel_report() == line
-    pipe.gumbel = None
-    assert pipe.gumbel_report() == ""               # off: the log line is what it was
+    assert OPTIONS["gumbel"].log(_Engine()) == line == SearchOptions(8, gumbel={}).log_line(_Engine())
+    assert SearchOptions(8, gumbel=None).log_line(_Engine()) == ""               # off: the log line is what it was
 
 
 def test_selfplay_refusals_come_before_an_engine_is_built():
