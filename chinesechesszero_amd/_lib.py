@@ -189,6 +189,10 @@ PROTOTYPES = {
     "ccz_expand_records": (C.c_int, [_P, _P, C.c_int64, C.c_uint32, _P, _P, _P, _P, C.c_int64, C.c_int64, _P, _P, _P]),
     "ccz_ring_retire": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int32, _P]),
     "ccz_sample_records": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, C.c_uint32, _P, _P, _P, _P, _P, _P, _P]),
+    "ccz_snapshot_size": (C.c_int, [_P, _P, C.POINTER(C.c_uint64)]),
+    "ccz_snapshot_save": (C.c_int, [_P, _P, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "ccz_snapshot_load": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_int32]),
+    "ccz_snapshot_layout": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_uint32, _P]),
     "ccz_get_stats": (C.c_int, [_P, _P, C.POINTER(Stats)]),
     "ccz_legal_moves": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P]),
     "ccz_apply_moves": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P]),

@@ -17,6 +17,19 @@ collect.py:146-167 are not written.
 between: the rank that stores the union also keeps it, as compact records, in a ``replay.RecordReplayBuffer`` of N plies in
 HBM, and every K lockstep moves it runs one ``trainer.Trainer`` step on a minibatch drawn from that ring, on the very net the
 boards are evaluated with (``weights_version`` moves: inference copy, captured graphs and evaluation caches follow).
+
+Checkpoints (``--checkpoint-dir DIR --checkpoint-every N``, ``--resume``; one rank, the batched path): every N lockstep moves, at the
+move boundary and after the move's harvest has reached the sink and the ring and its trainer step has run, the whole job is written to
+ONE file in DIR (``checkpoint.py``: temporary name, rename, the newest two kept): the games in progress with their kept trees
+(``BatchedSelfPlay.state_dict``: the engine's snapshot, ``include/cczero.h`` "Engine snapshots"), the replay ring's retained window,
+the net's and the optimiser's ``state_dict``s and the trainer's step count, the state of the generator the minibatches are drawn with
+(with checkpoints the job owns one, seeded with ``--seed``; without them the draws come from torch's global generator as ever), and the
+sink's row and game counts at that moment. ``--resume`` loads the newest complete checkpoint, refuses one written with other options
+(it names them) and a missing or empty directory, and goes on bit for bit. NO ROW TWICE: a job that died after its last checkpoint
+left later appends in the data directory; the resumed job replays those moves, producing the same rows, and the sink -- which knows
+from the checkpoint how many rows it held then and counts how many it finds now -- drops exactly that many leading rows of the replayed
+appends (``checkpoint.RowSkipper``). It deletes nothing it finds; after ``finalize`` the files hold the rows of an uninterrupted run,
+each once.
 """
 from __future__ import annotations
 
@@ -32,6 +45,7 @@ from .net import PolicyValueNet
 from .parameters import BATCH_SIZE, C_PUCT, DATA_DIR, MODEL_DIR, PLAYOUT
 from .options import (SearchOptions, add_gumbel_args, add_resign_args, add_root_exploration_args, format_exploration, format_gumbel,  # noqa: F401
                       format_search, gumbel_from_args, resign_from_args, root_exploration_from_args)
+from .checkpoint import add_checkpoint_args, checkpoint_from_args
 from .searchcfg import add_search_args, search_from_args
 from .stopcfg import add_early_stop_args, early_stop_from_args
 from .tools import flip_map, log
@@ -78,6 +92,7 @@ class TupleSink:
         self._rshards: list[tuple[str, int, int, tuple]] = []   # record shards: (path, plies, flags, plane_of_type)
         self._next = 0
         self.games = 0
+        self._skip = None   # checkpoint.RowSkipper of a resumed job (resume_from): the replayed appends it drops
         os.makedirs(out_dir, exist_ok=True)
         self._take_lock()
         state = os.path.join(out_dir, "collect_state.json")
@@ -235,11 +250,28 @@ class TupleSink:
                 json.dump({"iters": self.games}, f)
             os.replace(tmp, os.path.join(self.out_dir, "collect_state.json"))
 
+    def total_rows(self) -> int:
+        """Rows this directory holds: merged into the trainer's files + waiting in shards."""
+        return int(self._merged_rows + self.rows())
+
+    def resume_from(self, rows: int, games: int):
+        """A resumed job (``CollectPipeline(resume=True)``): the sink held ``rows`` rows and ``games`` games when the checkpoint was
+        written. Whatever it holds beyond that was appended after the checkpoint by the job that died; the resumed job replays those
+        moves bit for bit, and that many leading rows / games of its appends are dropped (``checkpoint.RowSkipper``). Nothing found is
+        deleted; fewer rows than the checkpoint saw is refused."""
+        from .checkpoint import RowSkipper
+        self._skip = RowSkipper(rows, self.total_rows())
+        self.games = int(games)   # (the games the dead job counted after the checkpoint are counted again by the replay)
+
     def append(self, states, pi, z, games: int = 1, targets=None, values=None):
         """``targets``: uint8 [rows] policy-target bytes or None (every row a target); ``values``: float32 [rows] root values (NaN:
         unknown) or None."""
         to_np = lambda t: t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
         s, p, w = to_np(states), to_np(pi), to_np(z)
+        if self._skip is not None:   # a resumed job replaying what its predecessor already stored
+            drop = self._skip.take(len(w))
+            s, p, w = s[drop:], p[drop:], w[drop:]
+            targets, values = (None if targets is None else to_np(targets)[drop:]), (None if values is None else to_np(values)[drop:])
         if len(w):
             base = os.path.join(self.out_dir, f".shard_{os.getpid()}_{self._next:06d}")
             while os.path.exists(base + "_z.npy"):
@@ -277,6 +309,11 @@ class TupleSink:
         pot = (0, 0, 1, 2, 3, 4, 5, 6) if plane_of_type is None else tuple(int(x) for x in plane_of_type)
         if len(pot) != 8 or max(pot) > 9 or min(pot) < 0:
             raise ValueError("plane_of_type must be 8 entries in 0..6")
+        if self._skip is not None:   # a resumed job replaying what its predecessor already stored
+            from ._lib import FLAG_NO_MIRROR
+            mul = 1 if int(flags) & FLAG_NO_MIRROR else 2
+            drop = self._skip.take(len(rec) * mul)
+            rec = rec[drop // mul:]
         if len(rec):
             tail = f"_f{int(flags)}_p{''.join(str(x) for x in pot)}"
             path = os.path.join(self.out_dir, f".rshard_{os.getpid()}_{self._next:06d}{tail}.npy")
@@ -514,7 +551,8 @@ class CollectPipeline:
                  finalize_every: int = 0, on_playout=None, max_plies: int = 0, eval_cache_log2: int | None = None, gatherer=None,
                  dense_shards: bool = False, replay_plies: int = 0, train_every: int = 0, train_batch: int = BATCH_SIZE,
                  playout_cap_fast: int = 0, playout_cap_prob: float | None = None, resign=None, value_q_weight: float = 0.0,
-                 root_exploration=None, solver: bool = False, gumbel=None, search=None, early_stop=None):
+                 root_exploration=None, solver: bool = False, gumbel=None, search=None, early_stop=None,
+                 checkpoint_dir: str | None = None, checkpoint_every: int = 0, resume: bool = False):
         # the engine options of the batched path, as BatchedSelfPlay takes them (options.OPTIONS: each None / False = off); only the search
         # parameters also run in the one-game loop (which then runs without scout slots)
         self.options = o = SearchOptions(n_playout, batched=n_boards > 1, resign=resign, root_exploration=root_exploration, gumbel=gumbel,
@@ -584,6 +622,77 @@ class CollectPipeline:
         self.ring = None
         self.trainer = None
         self._moves_since_step = 0
+        # resumable checkpoints of the batched path (module docstring "Checkpoints"; checkpoint.py): off without a directory
+        self.checkpoint_dir, self.checkpoint_every, self.resume = checkpoint_dir, int(checkpoint_every), bool(resume)
+        if (self.checkpoint_every or self.resume) and not checkpoint_dir:
+            raise ValueError("checkpoint_every / resume need checkpoint_dir")
+        if checkpoint_dir:
+            from . import checkpoint
+            if n_boards <= 1:
+                raise ValueError("checkpoints are taken on the batched path: n_boards must be > 1")
+            if gatherer is not None and getattr(gatherer, "world", 1) > 1:
+                raise ValueError(checkpoint.MULTI_RANK)
+            if self.resume:
+                checkpoint.newest(checkpoint_dir)   # (FileNotFoundError now, before a net is loaded: never a silent fresh start)
+        self.moves_done = 0        # lockstep moves of this job, the ones before a resume included
+        self._sample_gen = None    # with checkpoints: the minibatch draws come from a generator of the job's own, whose state is saved
+
+    # ---- checkpoints ------------------------------------------------------------------------------------------------------------
+    def _signature(self) -> dict:
+        """The options a checkpoint depends on: a job that resumes must have been started with the same."""
+        return {"n_boards": self.n_boards, "n_playout": self.n_playout, "seed": self.seed, "max_plies": self.max_plies,
+                "eval_cache_log2": self.eval_cache_log2, "reference_quirks": self.reference_quirks, "net": tuple(self._net_shape),
+                "dense_shards": self.dense_shards, "replay_plies": self.replay_plies, "train_every": self.train_every,
+                "train_batch": self.train_batch, "playout_cap": self.playout_cap, "value_q_weight": self.value_q_weight,
+                "init_model": self.init_model, **{f"option {k}": v for k, v in self.options.keywords().items()}}
+
+    def _generator(self):
+        if self.checkpoint_dir and self._sample_gen is None:
+            self._sample_gen = torch.Generator(device=f"cuda:{self.device}")
+            self._sample_gen.manual_seed(int(self.seed))
+        return self._sample_gen
+
+    def save_checkpoint(self) -> str:
+        """The whole job at this move boundary as one file in ``checkpoint_dir`` (``checkpoint.write``: temporary name, rename, the newest
+        two kept): the games in progress (``BatchedSelfPlay.state_dict``), the replay ring, the net's and the optimiser's ``state_dict``s
+        with the trainer's step count, the sampling generator, the move counters and the sink's row and game counts."""
+        from . import checkpoint
+        net = self.policy_value_net
+        payload = {"signature": self._signature(), "moves_done": self.moves_done, "moves_since_step": self._moves_since_step,
+                   "selfplay": self.selfplay.state_dict(), "ring": None if self.ring is None else self.ring.state_dict(),
+                   "model": net.policy_value_net.state_dict(), "optimizer": net.optimizer.state_dict(),
+                   "trainer_steps": None if self.trainer is None else self.trainer.steps,
+                   "generator": None if self._sample_gen is None else self._sample_gen.get_state(),
+                   "sink_rows": self.sink.total_rows(), "sink_games": self.sink.games, "finalized_at": self._finalized_at}
+        return checkpoint.write(self.checkpoint_dir, self.moves_done, payload)
+
+    def _resume(self):
+        """Continue from the newest complete checkpoint: called once, when the batched path has built its net and its boards."""
+        from . import checkpoint
+        moves, ck = checkpoint.load_newest(self.checkpoint_dir)
+        diff = checkpoint.differences(ck["signature"], self._signature())
+        if diff:
+            raise ValueError(f"--resume: the checkpoint in {self.checkpoint_dir} was written with other options -- " + "; ".join(diff))
+        net, e = self.policy_value_net, self.selfplay.engine
+        net.policy_value_net.load_state_dict(ck["model"])
+        net.optimizer.load_state_dict(ck["optimizer"])
+        net.invalidate_inference_copy()      # (weights_version moves: the next evaluation runs on the loaded weights)
+        if ck["trainer_steps"] is not None:
+            from .trainer import Trainer
+            self.trainer = Trainer(net, amp_dtype="bf16")
+            net.optimizer.load_state_dict(ck["optimizer"])   # (the constructor wrote its own learning rate)
+            self.trainer.steps = int(ck["trainer_steps"])
+        self.selfplay.load_state_dict(ck["selfplay"])
+        if ck["ring"] is not None:
+            from .replay import RecordReplayBuffer
+            self.ring = RecordReplayBuffer(self.replay_plies, e.device, e.record_flags(), e.plane_of_type, max_game_plies=int(ck["ring"]["max_game_plies"]))
+            self.ring.load_state_dict(ck["ring"])
+        if ck["generator"] is not None:
+            self._generator().set_state(ck["generator"])
+        self.moves_done, self._moves_since_step = int(ck["moves_done"]), int(ck["moves_since_step"])
+        self.sink.resume_from(int(ck["sink_rows"]), int(ck["sink_games"]))
+        self.iters, self._finalized_at = self.sink.games, int(ck["finalized_at"])
+        log(f"Resumed from {checkpoint.path_of(self.checkpoint_dir, moves)} (move {moves}, {ck['sink_rows']} rows, {ck['sink_games']} games)")
 
     def load_model(self):
         """collect.py:48-62: load once; on failure fall back to a random-init net."""
@@ -682,6 +791,8 @@ class CollectPipeline:
                                             playout_cap=self.playout_cap, **self.options.keywords())
             if getattr(self, "_viewer", None) is not None:
                 self.selfplay.watch(0, self._viewer)
+            if getattr(self, "resume", False):
+                self._resume()
         for _ in range(n_moves):
             if hasattr(gatherer, "tick_until"):
                 self._run_move_ticking(gatherer)
@@ -737,6 +848,9 @@ class CollectPipeline:
             self.iters = self.sink.games
             self._maybe_finalize()
             self._maybe_train(gatherer)
+            self.moves_done = getattr(self, "moves_done", 0) + 1
+            if getattr(self, "checkpoint_every", 0) and self.moves_done % self.checkpoint_every == 0:
+                self.save_checkpoint()   # a move boundary: the move's harvest is in the sink and the ring, its trainer step is done
         self.selfplay.engine.check_healthy()
         return self.iters
 
@@ -832,10 +946,11 @@ class CollectPipeline:
                 from .trainer import Trainer
                 self.trainer = Trainer(self.policy_value_net, amp_dtype="bf16")   # bf16: no GradScaler, so no host sync per update
             qw = getattr(self, "value_q_weight", 0.0)
+            gen = self._generator() if getattr(self, "checkpoint_dir", None) else None   # (None: torch's global generator, as ever)
             if self.playout_cap is None and not qw:
-                self.last_losses = self.trainer.step(*self.ring.sample(self.train_batch), sync=False)
+                self.last_losses = self.trainer.step(*self.ring.sample(self.train_batch, generator=gen), sync=False)
             else:   # fast plies train the value head only; rows that carry a root value blend it into the value target
-                st, pi, z, tg, q = self.ring.sample(self.train_batch, targets=True, values=True)
+                st, pi, z, tg, q = self.ring.sample(self.train_batch, generator=gen, targets=True, values=True)
                 self.last_losses = self.trainer.step(st, pi, z, sync=False, policy_mask=None if self.playout_cap is None else tg,
                                                      q=q if qw else None, q_weight=qw)
         if multi:
@@ -940,6 +1055,7 @@ def build_parser():
     add_early_stop_args(parser)
     parser.add_argument("--value-q-weight", type=float, default=0.0, help="with --train-every: weight of the recorded root value q in the value "
                         "target, (1 - w) z + w q on rows that carry one (0 = z alone)")
+    add_checkpoint_args(parser)
     return parser
 
 
@@ -960,6 +1076,7 @@ def parse_args(argv=None):
         SearchOptions(args.playout, batched=args.boards > 1, **args.options)
     except ValueError as ex:
         parser.error(str(ex))
+    args.checkpoint = checkpoint_from_args(parser, args, world=int(os.environ.get("WORLD_SIZE", "1")))
     return args
 
 
@@ -991,7 +1108,7 @@ if __name__ == "__main__":
                            num_channels=args.channels, resblocks_num=args.blocks, max_plies=args.max_plies, device=device,
                            eval_cache_log2=args.eval_cache_log2, gatherer=gatherer, replay_plies=args.replay_plies,
                            train_every=args.train_every, train_batch=args.train_batch, playout_cap_fast=args.playout_cap_fast,
-                           playout_cap_prob=args.playout_cap_prob, value_q_weight=args.value_q_weight, **args.options)
+                           playout_cap_prob=args.playout_cap_prob, value_q_weight=args.value_q_weight, **args.options, **args.checkpoint)
     if world > 1:
         from .launch import guarded
 

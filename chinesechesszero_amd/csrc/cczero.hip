@@ -10,6 +10,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
+#include <cstddef>
 #include <cstring>
 #include <new>
 #include <vector>
@@ -21,6 +22,7 @@
 #include "cczero_conv_g16.h"
 #include "cczero_conv_g16e.h"
 #include "cczero_heads.h"
+#include "cczero_snapshot.h"
 
 using namespace ccz;
 
@@ -98,6 +100,12 @@ struct ccz_engine {
     uint8_t *wide_F = nullptr;
     WideBoardStats *wide_stats = nullptr;
     unsigned long long *st_wide = nullptr;
+    // engine snapshots (ccz_snapshot_*): a hash of the move-rank table (0: none), the section offsets on the device [B + 1] (allocated at
+    // the first call), and the host's side of a save / load: the header and the directory (offsets, then meta)
+    uint64_t rank_hash = 0;
+    uint64_t *snap_off = nullptr;
+    SnapHeader snap_hdr;
+    std::vector<uint64_t> snap_dir;
 };
 
 #define ACTIVE(e) ((unsigned)((e)->active > 0 ? (e)->active : (e)->d.B))
@@ -271,6 +279,8 @@ int ccz_create(const ccz_config *cfg, ccz_engine **out)
             if (h_rank[i] >= kNMoves || h_unrank[h_rank[i]] != 0xffff) { delete e; return fail(-1, "ccz_create: move_rank_host must be a permutation of 0..2085 (entry %d)", i); }
             h_unrank[h_rank[i]] = (uint16_t)i;
         }
+        e->rank_hash = 0xcbf29ce484222325ull; // FNV-1a over the table's entries: what a snapshot's header says of it
+        for (int i = 0; i < kNMoves; ++i) e->rank_hash = (e->rank_hash ^ (uint64_t)h_rank[i]) * 0x100000001b3ull;
     }
     const size_t B = (size_t)d.B;
     hipError_t he = hipSuccess;
@@ -1646,6 +1656,248 @@ int ccz_sample_records(void *stream, const void *ring_dev, int64_t cap_plies, co
                        (const long long *)window_dev, (const long long *)draws_dev, (long long)batch,
                        flags & (CCZ_FLAG_REFERENCE_QUIRKS | CCZ_FLAG_NO_MIRROR), typepack, (uint16_t *)states_f16_dev, pi_dev, z_dev, bad_records_dev,
                        target_dev, value_dev);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---- engine snapshots (cczero.h: "Engine snapshots"; the kernels and the blob's layout: cczero_snapshot.h)
+static uint32_t snap_sections(const ccz_engine *e) { return (e->proof ? kSnapProof : 0u) | kSnapValues; }
+static size_t snap_dir_bytes(int B) { return ((size_t)B + 1) * 8 + (size_t)B * sizeof(BoardMeta); }
+static uint64_t snap_sections_start(int B) { return snap_pad16((uint64_t)kSnapHeader + snap_dir_bytes(B)); }
+
+// the settings as the device holds them, the sticky error word and the half word -> h (syncs)
+static int snap_read_settings(ccz_engine *e, hipStream_t s, SnapHeader &h)
+{
+    SolverCfg sv;
+    HIP_TRY(hipMemcpyAsync(&h.resign, e->d.rs_cfg, sizeof h.resign, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&h.explore, e->d.ex_cfg, sizeof h.explore, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&h.gumbel, e->d.gm_cfg, sizeof h.gumbel, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&h.search, e->d.sr_cfg, sizeof h.search, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&h.stop, e->d.es_cfg, sizeof h.stop, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&sv, e->d.sv_cfg, sizeof sv, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&h.err, e->d.err, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&h.half, e->d.half, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    h.solver_enabled = sv.enabled;
+    h.width = e->width;
+    return 0;
+}
+
+// the header of a snapshot of this engine as it stands (without the total) and the section offsets on the device (e->snap_off), checked
+// against the host's own sum over the meta records; *total = the snapshot's bytes. Syncs.
+static int snap_prepare(ccz_engine *e, hipStream_t s, const char *who, uint64_t *total)
+{
+    const Dev &d = e->d;
+    const int B = d.B;
+    if (!e->snap_off) {
+        HIP_TRY(hipSetDevice(e->cfg.device));
+        HIP_TRY(dalloc(&e->snap_off, (size_t)B + 1, e->owned, e->bytes));
+    }
+    const uint32_t sections = snap_sections(e);
+    const BoardMeta *m0 = d.meta;
+    hipLaunchKernelGGL(k_snapshot_layout, dim3(1), dim3(1024), 0, s, B, &m0->n_nodes, &m0->ply, &m0->pi_used, (int)(sizeof(BoardMeta) / 4), sections,
+                       e->snap_off);
+    HIP_TRY(hipGetLastError());
+    uint64_t sum_dev = 0;
+    HIP_TRY(hipMemcpyAsync(&sum_dev, e->snap_off + B, 8, hipMemcpyDeviceToHost, s));
+    SnapHeader &h = e->snap_hdr;
+    memset(&h, 0, sizeof h);
+    if (const int rc = snap_read_settings(e, s, h)) return rc;
+    if (const int rc = fetch_meta(e, s)) return rc;
+    uint64_t sum = 0;
+    for (int b = 0; b < B; ++b) {
+        const BoardMeta &m = e->h_meta[(size_t)b];
+        if (m.n_nodes < 0 || m.n_nodes > d.cap || m.ply < 0 || m.ply > d.max_plies || m.pi_used > (uint32_t)d.pi_cap)
+            return fail(-1, "%s: board %d holds counts outside the engine's arrays (n_nodes %d, ply %d, pi_used %u)", who, b, m.n_nodes, m.ply, m.pi_used);
+        sum += snap_section_bytes(sections, (uint64_t)m.n_nodes, (uint64_t)m.ply, (uint64_t)m.pi_used);
+    }
+    if (sum != sum_dev) return fail(-2, "%s: the layout kernel's total %llu differs from the host's %llu", who, (unsigned long long)sum_dev, (unsigned long long)sum);
+    h.magic = kSnapMagic;
+    h.version = kSnapVersion;
+    h.header_bytes = (uint32_t)kSnapHeader;
+    h.sections_start = snap_sections_start(B);
+    h.total_bytes = h.sections_start + sum;
+    h.B = d.B; h.cap = d.cap; h.maxd = d.maxd; h.max_plies = d.max_plies; h.pi_cap = d.pi_cap; h.reserve = d.reserve;
+    h.c_puct = d.c_puct; h.flags = d.flags;
+    h.eps = d.eps; h.alpha = d.alpha; h.temp = d.temp;
+    h.seed = d.seed; h.board_id_base = d.board_id_base;
+    h.rule_flags = d.rule_flags; h.chanpack = d.chanpack; h.typepack = d.typepack; h.trankpack = d.trankpack;
+    h.rank_hash = e->rank_hash;
+    h.sections = sections;
+    h.budgets_on = e->budgets_on ? 1 : 0;
+    h.fixed_bytes = (uint32_t)kSnapFixed;
+    h.meta_bytes = (uint32_t)sizeof(BoardMeta);
+    *total = h.total_bytes;
+    return 0;
+}
+
+int ccz_snapshot_size(ccz_engine *e, void *stream, uint64_t *bytes_host)
+{
+    NEED(e);
+    if (!bytes_host) return fail(-1, "ccz_snapshot_size: null output");
+    return snap_prepare(e, (hipStream_t)stream, "ccz_snapshot_size", bytes_host);
+}
+
+int ccz_snapshot_save(ccz_engine *e, void *stream, void *blob_dev, uint64_t capacity, uint64_t *bytes_host)
+{
+    NEED(e);
+    if (!blob_dev) return fail(-1, "ccz_snapshot_save: null blob");
+    if ((uintptr_t)blob_dev & 15) return fail(-1, "ccz_snapshot_save: the blob must be 16-byte aligned");
+    if (SCOUTS(e)) return fail(-1, "ccz_snapshot_save: not with scout slots (ccz_set_scouts): a scout slot has no game and no tree");
+    hipStream_t s = (hipStream_t)stream;
+    uint64_t total = 0;
+    if (const int rc = snap_prepare(e, s, "ccz_snapshot_save", &total)) return rc;
+    if (bytes_host) *bytes_host = total;
+    if (capacity < total)
+        return fail(-1, "ccz_snapshot_save: capacity %llu is below the snapshot's %llu bytes (nothing was written)", (unsigned long long)capacity,
+                    (unsigned long long)total);
+    const int B = e->d.B;
+    uint8_t *blob = (uint8_t *)blob_dev;
+    const size_t dir_end = (size_t)kSnapHeader + snap_dir_bytes(B);
+    HIP_TRY(hipMemcpyAsync(blob, &e->snap_hdr, sizeof e->snap_hdr, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(blob + kSnapHeader, e->snap_off, ((size_t)B + 1) * 8, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(blob + kSnapHeader + ((size_t)B + 1) * 8, e->d.meta, (size_t)B * sizeof(BoardMeta), hipMemcpyDeviceToDevice, s));
+    if (e->snap_hdr.sections_start > dir_end) HIP_TRY(hipMemsetAsync(blob + dir_end, 0, (size_t)e->snap_hdr.sections_start - dir_end, s));
+    hipLaunchKernelGGL(k_snapshot_pack, dim3((unsigned)B), dim3(256), 0, s, e->d, (const uint64_t *)e->snap_off, blob + e->snap_hdr.sections_start,
+                       e->snap_hdr.sections, e->proof, e->wide_stats);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s)); // (the header travels from the engine's own host copy)
+    return 0;
+}
+
+int ccz_snapshot_load(ccz_engine *e, void *stream, const void *blob_dev, uint64_t bytes, int32_t keep_board_id_base)
+{
+    NEED(e);
+    if (!blob_dev) return fail(-1, "ccz_snapshot_load: null blob");
+    if ((uintptr_t)blob_dev & 15) return fail(-1, "ccz_snapshot_load: the blob must be 16-byte aligned");
+    if (SCOUTS(e)) return fail(-1, "ccz_snapshot_load: not with scout slots (ccz_set_scouts)");
+    hipStream_t s = (hipStream_t)stream;
+    const Dev &d = e->d;
+    const int B = d.B;
+    const uint8_t *blob = (const uint8_t *)blob_dev;
+    if (bytes < (uint64_t)kSnapHeader) return fail(-1, "ccz_snapshot_load: truncated: %llu bytes are less than the header's %d", (unsigned long long)bytes, kSnapHeader);
+    // ---- everything below up to the unpack launch only reads: a refused blob leaves the engine exactly as it was
+    SnapHeader &h = e->snap_hdr;
+    HIP_TRY(hipMemcpyAsync(&h, blob, sizeof h, hipMemcpyDeviceToHost, s));
+    SnapHeader mine;
+    memset(&mine, 0, sizeof mine);
+    if (const int rc = snap_read_settings(e, s, mine)) return rc; // syncs
+    if (h.magic != kSnapMagic) return fail(-1, "ccz_snapshot_load: bad magic 0x%016llx (not an engine snapshot)", (unsigned long long)h.magic);
+    if (h.version != kSnapVersion) return fail(-1, "ccz_snapshot_load: format version %u, this library reads %u", h.version, kSnapVersion);
+    if (h.header_bytes != (uint32_t)kSnapHeader || h.fixed_bytes != (uint32_t)kSnapFixed || h.meta_bytes != (uint32_t)sizeof(BoardMeta))
+        return fail(-1, "ccz_snapshot_load: header_bytes / fixed_bytes / meta_bytes %u / %u / %u, this library reads %d / %d / %d", h.header_bytes,
+                    h.fixed_bytes, h.meta_bytes, kSnapHeader, kSnapFixed, (int)sizeof(BoardMeta));
+#define SNAP_SAME(NAME_, FMT_, CAST_, A_, B_)                                                                                           \
+    if ((A_) != (B_)) return fail(-1, "ccz_snapshot_load: " NAME_ " differs: the snapshot has " FMT_ ", the engine " FMT_, (CAST_)(A_), (CAST_)(B_))
+    SNAP_SAME("B (n_boards)", "%d", int, h.B, d.B);
+    SNAP_SAME("cap (max_nodes)", "%d", int, h.cap, d.cap);
+    SNAP_SAME("maxd (max_depth)", "%d", int, h.maxd, d.maxd);
+    SNAP_SAME("max_plies", "%d", int, h.max_plies, d.max_plies);
+    SNAP_SAME("pi_cap", "%d", int, h.pi_cap, d.pi_cap);
+    SNAP_SAME("reserve (reserve_nodes)", "%d", int, h.reserve, d.reserve);
+    SNAP_SAME("c_puct", "%.9g", double, h.c_puct, d.c_puct);
+    SNAP_SAME("eps", "%.17g", double, h.eps, d.eps);
+    SNAP_SAME("alpha", "%.17g", double, h.alpha, d.alpha);
+    SNAP_SAME("temp", "%.17g", double, h.temp, d.temp);
+    SNAP_SAME("flags", "0x%x", unsigned, h.flags, d.flags);
+    SNAP_SAME("seed", "%llu", unsigned long long, h.seed, d.seed);
+    if (!keep_board_id_base && h.board_id_base != d.board_id_base)
+        return fail(-1, "ccz_snapshot_load: board_id_base differs: the snapshot has %llu, the engine %llu (keep_board_id_base = 1 keeps the engine's)",
+                    (unsigned long long)h.board_id_base, (unsigned long long)d.board_id_base);
+    SNAP_SAME("rule_flags", "0x%x", unsigned, h.rule_flags, d.rule_flags);
+    SNAP_SAME("chanpack (plane_of_type)", "0x%x", unsigned, h.chanpack, d.chanpack);
+    SNAP_SAME("typepack (plane_of_type)", "0x%x", unsigned, h.typepack, d.typepack);
+    SNAP_SAME("trankpack (type_rank)", "0x%x", unsigned, h.trankpack, d.trankpack);
+    SNAP_SAME("the move-rank table's hash", "0x%016llx", unsigned long long, h.rank_hash, e->rank_hash);
+    SNAP_SAME("width (ccz_set_width)", "%d", int, h.width, mine.width);
+    SNAP_SAME("solver enabled (ccz_set_solver)", "%d", int, h.solver_enabled, mine.solver_enabled);
+    SNAP_SAME("resign.enabled", "%d", int, h.resign.enabled, mine.resign.enabled);
+    SNAP_SAME("resign.consecutive", "%d", int, h.resign.consecutive, mine.resign.consecutive);
+    SNAP_SAME("resign.min_ply", "%d", int, h.resign.min_ply, mine.resign.min_ply);
+    SNAP_SAME("resign.threshold", "%.9g", double, h.resign.threshold, mine.resign.threshold);
+    SNAP_SAME("resign.p_playon", "%.17g", double, h.resign.p_playon, mine.resign.p_playon);
+    SNAP_SAME("root_exploration.enabled", "%d", int, h.explore.enabled, mine.explore.enabled);
+    SNAP_SAME("root_exploration.prune", "%d", int, h.explore.prune, mine.explore.prune);
+    SNAP_SAME("root_exploration.eps", "%.17g", double, h.explore.eps, mine.explore.eps);
+    SNAP_SAME("root_exploration.alpha", "%.17g", double, h.explore.alpha, mine.explore.alpha);
+    SNAP_SAME("root_exploration.forced_k", "%.17g", double, h.explore.forced_k, mine.explore.forced_k);
+    SNAP_SAME("gumbel.enabled", "%d", int, h.gumbel.enabled, mine.gumbel.enabled);
+    SNAP_SAME("gumbel.n_sims", "%d", int, h.gumbel.n_sims, mine.gumbel.n_sims);
+    SNAP_SAME("gumbel.max_considered", "%d", int, h.gumbel.max_considered, mine.gumbel.max_considered);
+    SNAP_SAME("gumbel.c_visit", "%.17g", double, h.gumbel.c_visit, mine.gumbel.c_visit);
+    SNAP_SAME("gumbel.c_scale", "%.17g", double, h.gumbel.c_scale, mine.gumbel.c_scale);
+    SNAP_SAME("search.enabled", "%d", int, h.search.enabled, mine.search.enabled);
+    SNAP_SAME("search.fpu_mode", "%d", int, h.search.fpu_mode, mine.search.fpu_mode);
+    SNAP_SAME("search.fpu_root_mode", "%d", int, h.search.fpu_root_mode, mine.search.fpu_root_mode);
+    SNAP_SAME("search.fpu_value", "%.17g", double, h.search.fpu_value, mine.search.fpu_value);
+    SNAP_SAME("search.fpu_root_value", "%.17g", double, h.search.fpu_root_value, mine.search.fpu_root_value);
+    SNAP_SAME("search.c_base", "%.17g", double, h.search.c_base, mine.search.c_base);
+    SNAP_SAME("search.c_factor", "%.17g", double, h.search.c_factor, mine.search.c_factor);
+    SNAP_SAME("early_stop.enabled", "%d", int, h.stop.enabled, mine.stop.enabled);
+    SNAP_SAME("early_stop.single_reply", "%d", int, h.stop.single_reply, mine.stop.single_reply);
+    SNAP_SAME("early_stop.kld_interval", "%d", int, h.stop.kld_interval, mine.stop.kld_interval);
+    SNAP_SAME("early_stop.min_sims", "%d", int, h.stop.min_sims, mine.stop.min_sims);
+    SNAP_SAME("early_stop.n_sims", "%d", int, h.stop.n_sims, mine.stop.n_sims);
+    SNAP_SAME("early_stop.gap_factor", "%.17g", double, h.stop.gap_factor, mine.stop.gap_factor);
+    SNAP_SAME("early_stop.min_gain", "%.17g", double, h.stop.min_gain, mine.stop.min_gain);
+#undef SNAP_SAME
+    if (h.sections & ~(kSnapProof | kSnapValues)) return fail(-1, "ccz_snapshot_load: unknown sections bits 0x%x", h.sections);
+    if (h.total_bytes != bytes)
+        return fail(-1, "ccz_snapshot_load: total size: the header says %llu bytes, the caller passes %llu (a truncated or padded blob)",
+                    (unsigned long long)h.total_bytes, (unsigned long long)bytes);
+    const uint64_t start = snap_sections_start(B);
+    if (h.sections_start != start || bytes < start)
+        return fail(-1, "ccz_snapshot_load: sections_start %llu, expected %llu within %llu bytes", (unsigned long long)h.sections_start,
+                    (unsigned long long)start, (unsigned long long)bytes);
+    // ---- the directory: offsets monotone and inside the blob, every board's counts inside the engine's arrays, every section as long
+    // as its counts say
+    e->snap_dir.resize((snap_dir_bytes(B) + 7) / 8);
+    HIP_TRY(hipMemcpyAsync(e->snap_dir.data(), blob + kSnapHeader, snap_dir_bytes(B), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    const uint64_t *off = e->snap_dir.data();
+    const uint8_t *metab = (const uint8_t *)(off + B + 1);
+    if (off[0] != 0) return fail(-1, "ccz_snapshot_load: offsets[0] is %llu, not 0", (unsigned long long)off[0]);
+    for (int b = 0; b < B; ++b)
+        if (off[b + 1] < off[b] || off[b + 1] > bytes - start)
+            return fail(-1, "ccz_snapshot_load: offsets[%d] = %llu after %llu: the offset table is not monotone inside the blob's %llu section bytes", b + 1,
+                        (unsigned long long)off[b + 1], (unsigned long long)off[b], (unsigned long long)(bytes - start));
+    for (int b = 0; b < B; ++b) {
+        BoardMeta m;
+        memcpy(&m, metab + (size_t)b * sizeof(BoardMeta), sizeof m);
+        if (m.n_nodes < 1 || m.n_nodes > d.cap) return fail(-1, "ccz_snapshot_load: board %d: n_nodes %d outside 1 .. cap %d", b, m.n_nodes, d.cap);
+        if (m.ply < 0 || m.ply > d.max_plies) return fail(-1, "ccz_snapshot_load: board %d: ply %d outside 0 .. max_plies %d", b, m.ply, d.max_plies);
+        if (m.pi_used > (uint32_t)d.pi_cap) return fail(-1, "ccz_snapshot_load: board %d: pi_used %u above pi_cap %d", b, m.pi_used, d.pi_cap);
+        if (m.chain_len < 1 || m.chain_len > kChainCap) return fail(-1, "ccz_snapshot_load: board %d: chain_len %d outside 1 .. %d", b, m.chain_len, kChainCap);
+        const uint64_t want = snap_section_bytes(h.sections, (uint64_t)m.n_nodes, (uint64_t)m.ply, (uint64_t)m.pi_used);
+        if (off[b + 1] - off[b] != want)
+            return fail(-1, "ccz_snapshot_load: offsets[%d] .. offsets[%d] span %llu bytes, board %d's counts need %llu", b, b + 1,
+                        (unsigned long long)(off[b + 1] - off[b]), b, (unsigned long long)want);
+    }
+    if (start + off[B] != bytes)
+        return fail(-1, "ccz_snapshot_load: offsets[%d] = %llu ends the sections at %llu of %llu bytes", B, (unsigned long long)off[B],
+                    (unsigned long long)(start + off[B]), (unsigned long long)bytes);
+    // ---- the writes
+    hipLaunchKernelGGL(k_snapshot_unpack, dim3((unsigned)B), dim3(256), 0, s, e->d, (const uint64_t *)(blob + kSnapHeader),
+                       (const BoardMeta *)(blob + kSnapHeader + ((size_t)B + 1) * 8), const_cast<uint8_t *>(blob) + start, h.sections, e->proof, e->wide_stats);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(e->d.err, &h.err, 4, hipMemcpyHostToDevice, s));
+    if (const int rc = ccz_eval_cache_clear(e, stream)) return rc; // a cold cache: claim refilled with it
+    if (e->wide_F) { // a move boundary: no leaf in flight, on any slot
+        HIP_TRY(hipMemsetAsync(e->wide_F, 0, (size_t)B * 2 * (size_t)d.cap, s));
+        hipLaunchKernelGGL(k_wide_clear_slots, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, e->d, 0);
+        HIP_TRY(hipGetLastError());
+    }
+    e->budgets_on = h.budgets_on != 0;
+    HIP_TRY(hipStreamSynchronize(s));
+    return 0;
+}
+
+int ccz_snapshot_layout(void *stream, int32_t B, const int32_t *n_nodes_dev, const int32_t *ply_dev, const uint32_t *pi_used_dev, uint32_t sections,
+                        uint64_t *offsets_dev)
+{
+    if (B < 1 || !n_nodes_dev || !ply_dev || !pi_used_dev || !offsets_dev) return fail(-1, "ccz_snapshot_layout: bad arguments");
+    if (sections & ~(kSnapProof | kSnapValues)) return fail(-1, "ccz_snapshot_layout: unknown sections bits 0x%x", sections);
+    hipLaunchKernelGGL(k_snapshot_layout, dim3(1), dim3(1024), 0, (hipStream_t)stream, (int)B, n_nodes_dev, ply_dev, pi_used_dev, 1, sections, offsets_dev);
     HIP_TRY(hipGetLastError());
     return 0;
 }

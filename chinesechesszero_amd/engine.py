@@ -821,6 +821,44 @@ class SelfPlayEngine:
                 break
             yield rec[:int(got.value)]
 
+    # ------------------------------------------------------------------ snapshots (include/cczero.h "Engine snapshots")
+    def snapshot_size(self) -> int:
+        """Bytes :meth:`save_state` would write now (``ccz_snapshot_size``; syncs)."""
+        n = C.c_uint64(0)
+        with torch.cuda.device(self.device):
+            check(self.L.ccz_snapshot_size(self.h, self._stream(), C.byref(n)))
+        return int(n.value)
+
+    def save_state(self) -> torch.Tensor:
+        """The engine's state as one uint8 device tensor of exactly the snapshot's size (``ccz_snapshot_save``): the live prefixes of
+        the node pool and the record arrays and every per-board row, not the allocations (:mod:`chinesechesszero_amd.snapshot`).
+        Call it at a MOVE BOUNDARY -- after :meth:`finish_move`, before or after the harvest, with no leaf pending; whether one is
+        pending the engine cannot tell (``BatchedSelfPlay.state_dict`` checks it). The evaluation cache is not saved. Syncs."""
+        blob = torch.empty((self.snapshot_size(),), dtype=torch.uint8, device=self.device)
+        n = C.c_uint64(0)
+        with torch.cuda.device(self.device):
+            check(self.L.ccz_snapshot_save(self.h, self._stream(), _ptr(blob), blob.numel(), C.byref(n)))
+        if int(n.value) != blob.numel():
+            raise CczError(f"ccz_snapshot_save wrote {int(n.value)} bytes into a blob of {blob.numel()}")
+        return blob
+
+    def load_state(self, blob, keep_board_id_base: bool = False):
+        """Continue from a snapshot: ``blob`` is what :meth:`save_state` returned (a device or CPU uint8 tensor) or the path of a
+        ``torch.save``d one. STRICT: the engine must have been created with the same arguments and hold the same settings
+        (resign, root exploration, Gumbel, search, early stop, solver, width); any difference raises :class:`CczError` naming the field
+        and leaves the engine exactly as it was. ``keep_board_id_base``: the one override -- the engine keeps its own
+        ``board_id_base``. The evaluation cache starts cold (the trees do not depend on it; the cache counters of :meth:`stats` do).
+        Graphs captured before the load stay valid. Syncs."""
+        if not isinstance(blob, torch.Tensor):
+            blob = torch.load(blob, map_location="cpu")
+        if not isinstance(blob, torch.Tensor) or blob.dtype != torch.uint8:
+            raise TypeError("an engine snapshot is a uint8 tensor")
+        t = blob.reshape(-1).to(self.device).contiguous()
+        if t.data_ptr() % 16:        # (a view into a larger tensor)
+            t = t.clone()
+        with torch.cuda.device(self.device):
+            check(self.L.ccz_snapshot_load(self.h, self._stream(), _ptr(t), t.numel(), 1 if keep_board_id_base else 0))
+
     def record_flags(self) -> int:
         """The ``flags`` :func:`expand_records` needs to reproduce this engine's :meth:`harvest` (quirk mode, mirror)."""
         return (_lib.FLAG_REFERENCE_QUIRKS if self.reference_quirks else 0) | (0 if self.mirror else _lib.FLAG_NO_MIRROR)
@@ -977,6 +1015,27 @@ def proof_combine(cases, device: int = 0) -> np.ndarray:
     with torch.cuda.device(dev):
         check(L.ccz_proof_combine(C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), _ptr(d_rows), _ptr(d_counts), n, _ptr(out)))
     return out.cpu().numpy()
+
+
+def snapshot_layout(n_nodes, ply, pi_used, sections: int = 2, device: int = 0) -> np.ndarray:
+    """The snapshot's layout scan on the GPU (``ccz_snapshot_layout``): the exclusive scan, in 64 bits, of the section sizes of B
+    boards with the given counts (arrays or device tensors); returns uint64 [B + 1], the last entry their sum. ``sections``:
+    ``snapshot.SNAP_PROOF | snapshot.SNAP_VALUES``. Only the count and offset arrays are allocated."""
+    L = _lib.lib()
+    dev = torch.device("cuda", device)
+
+    def dev_i32(x, np_dtype):
+        if isinstance(x, torch.Tensor):
+            return x.to(dev).contiguous()
+        return torch.from_numpy(np.ascontiguousarray(x, dtype=np_dtype).view(np.int32)).to(dev)
+    d_n, d_p, d_u = dev_i32(n_nodes, np.int32), dev_i32(ply, np.int32), dev_i32(pi_used, np.uint32)
+    B = int(d_n.numel())
+    if B < 1 or d_p.numel() != B or d_u.numel() != B:
+        raise ValueError("n_nodes, ply and pi_used must have the same length >= 1")
+    off = torch.zeros((B + 1,), dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        check(L.ccz_snapshot_layout(C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), B, _ptr(d_n), _ptr(d_p), _ptr(d_u), int(sections), _ptr(off)))
+    return off.cpu().numpy().view(np.uint64)
 
 
 # ---------------------------------------------------------------------- stateless batch rules

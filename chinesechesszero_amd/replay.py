@@ -884,6 +884,43 @@ class RecordReplayBuffer:
         w = self._window.cpu()
         return int(w[0]), int(w[1])
 
+    def _segments(self, tail: int, head: int):
+        """The physical slices of the logical plies ``[tail, head)``: one, or two when the window wraps."""
+        n, lo = head - tail, tail % self.cap
+        first = min(n, self.cap - lo)
+        return [(lo, lo + first)] + ([(0, n - first)] if n > first else [])
+
+    def state_dict(self) -> dict:
+        """The ring at this moment (syncs): the records of the retained window only -- logical plies ``[tail, head)`` in order, a CPU
+        tensor --, the window / head words, the counters, the flags and the plane map. A ring that loads it serves, for the same
+        generator state, the rows this one would have served: a draw is a row of the window, wherever its head has wrapped to."""
+        tail, head = self.window()
+        rec = torch.cat([self.records[a:b] for a, b in self._segments(tail, head)]).cpu() if head > tail \
+            else torch.zeros((0, REC_BYTES), dtype=torch.uint8)
+        return {"records": rec, "tail": tail, "head_device": head, "head": int(self.head), "size": int(self.size), "total": int(self.total),
+                "bad": int(self.bad.item()), "capacity_plies": self.cap, "max_game_plies": self.max_game_plies, "flags": self.flags,
+                "plane_of_type": self.plane_of_type}
+
+    def load_state_dict(self, state: dict):
+        """Continue from :meth:`state_dict` of a ring of the same shape (capacity, longest game, flags, plane map: ``ValueError``
+        names what differs, and nothing has changed then)."""
+        for name, mine in (("capacity_plies", self.cap), ("max_game_plies", self.max_game_plies), ("flags", self.flags),
+                           ("plane_of_type", self.plane_of_type)):
+            theirs = state[name]
+            if (tuple(theirs) if isinstance(theirs, (list, tuple)) else theirs) != mine:
+                raise ValueError(f"replay ring: {name} differs: the state has {theirs!r}, this ring {mine!r}")
+        tail, head = int(state["tail"]), int(state["head_device"])
+        rec = state["records"]
+        if not 0 <= head - tail <= self.cap or tuple(rec.shape) != (head - tail, REC_BYTES) or rec.dtype != torch.uint8:
+            raise ValueError(f"replay ring: the state's records {tuple(rec.shape)} do not fill its window [{tail}, {head})")
+        at = 0
+        for a, b in (self._segments(tail, head) if head > tail else []):
+            self.records[a:b].copy_(rec[at:at + b - a])
+            at += b - a
+        self._window.copy_(torch.tensor([tail, head], dtype=torch.int64))
+        self.bad.fill_(int(state["bad"]))
+        self.head, self.size, self.total = int(state["head"]), int(state["size"]), int(state["total"])
+
 
 def _flat_bytes(tensors, device):
     """The tensors' memory as ONE uint8 buffer on ``device`` (any mix of dtypes), and the (offset, nbytes) of each."""

@@ -362,6 +362,40 @@ class BatchedSelfPlay:
             forced[b] = int(rs.choice(rc["acts"][b][:k].astype(np.int64), p=p))
         return e.finish_move(forced_moves=forced, temps=temps)
 
+    # ------------------------------------------------------------------ snapshots (include/cczero.h "Engine snapshots")
+    def _need_move_boundary(self, what: str):
+        if self._sim != 0 or self._leaf is not None:
+            raise RuntimeError(f"{what}: the search stands inside a move ({self._sim} of {self.n_playout} simulations done, "
+                               f"{'a' if self._leaf is not None else 'no'} leaf pending): a snapshot is taken at a move boundary, after finish_move")
+
+    def state_dict(self) -> dict:
+        """Everything that decides what this object does next, at a move boundary (after :meth:`finish_move` / :meth:`run_move`, before
+        or after the harvest; RuntimeError inside a move): the engine's snapshot (``engine.save_state()``: a uint8 device tensor),
+        the playout ticker, and under ``sampling="numpy"`` the per-board ``RandomState``s. The playout-cap draws have no host side:
+        they come from the boards' Philox streams, which the engine's snapshot carries. ``torch.save`` takes the dict as it is."""
+        self._need_move_boundary("state_dict")
+        return {"engine": self.engine.save_state(), "ticker_acc": int(self._ticker.acc), "sampling": self.sampling,
+                "n_playout": int(self.n_playout), "playout_cap": self.playout_cap,
+                "rngs": None if self.rngs is None else [r.get_state() for r in self.rngs]}
+
+    def load_state_dict(self, state: dict, keep_board_id_base: bool = False):
+        """Continue from :meth:`state_dict` of an object built with the same arguments (the engine's load is strict: ``CczError`` names
+        what differs, and nothing has changed then). The evaluation cache starts cold and its weights version is re-read from the
+        evaluator that is current."""
+        self._need_move_boundary("load_state_dict")
+        for name, mine in (("sampling", self.sampling), ("n_playout", int(self.n_playout)), ("playout_cap", self.playout_cap)):
+            theirs = state[name]
+            if (tuple(theirs) if isinstance(theirs, (list, tuple)) else theirs) != mine:
+                raise ValueError(f"load_state_dict: {name} differs: the state has {theirs!r}, this object {mine!r}")
+        if (state["rngs"] is None) != (self.rngs is None) or (self.rngs is not None and len(state["rngs"]) != len(self.rngs)):
+            raise ValueError("load_state_dict: the per-board RandomStates of the state do not match this object's boards")
+        self.engine.load_state(state["engine"], keep_board_id_base=keep_board_id_base)
+        if self.rngs is not None:
+            for r, s in zip(self.rngs, state["rngs"]):
+                r.set_state(s)
+        self._sim, self._leaf, self._ticker.acc = 0, None, int(state["ticker_acc"])
+        self._weights.seen = self._evaluator_version()   # the load cleared the cache: what it holds from here on is of these weights
+
     def harvest(self):
         return self.engine.harvest()
 

@@ -1003,6 +1003,54 @@ int ccz_conv3x3_c256_heads_g16c_f16(void *stream, const void *x_dev, const void 
                                     void *pol_dev, void *val_dev, int64_t n_pixels, int32_t flags,
                                     const int32_t *live_rows_dev, int32_t part, int32_t n_parts);
 
+/* ---- Engine snapshots: save a self-play run and resume it bit for bit (additive to ABI 9) -------------------------------------
+ * A snapshot is one contiguous device blob that holds what decides what the engine does next and nothing else: of the node pool
+ * ([B][2][cap] records) the first n_nodes nodes of every board's pool half -- the re-root's breadth-first copy leaves every kept tree
+ * contiguous from node 0 --, of the record arrays the first `ply` plies and `pi_used` pi entries, and every per-board row (position,
+ * history chain, check bits, budgets, resignation / exploration / Gumbel / early-stop state, all counters). The evaluation cache is
+ * NOT saved: a loaded engine starts with a cold cache. The trees are the same with and without the cache; the cache counters of
+ * ccz_stats (cache_probes, cache_hits, cache_shared_rows, cache_stores, cache_verified) go on from the saved sums and therefore
+ * differ from those of an uninterrupted run.
+ *   THE MOVE-BOUNDARY CONTRACT. ccz_snapshot_save and ccz_snapshot_load are called at a move boundary: after ccz_finish_move (before
+ *     or after the harvest) or before the first selection, with NO LEAF PENDING on any board or slot. The selection path, the pending
+ *     leaf, the cache plan, the compact prior rows and the wide search's in-flight counts are not saved; whether a leaf is pending is the
+ *     caller's knowledge (BatchedSelfPlay.state_dict checks it), the engine cannot tell. A snapshot taken inside a move resumes from
+ *     the tree as it stood, minus the pending simulation.
+ *   The blob (csrc/cczero_snapshot.h, chinesechesszero_amd/snapshot.py): a 512-byte header -- magic, format version, the
+ *     configuration that decides the layout and the arithmetic (B, cap, max_depth, max_plies, pi_cap, reserve, c_puct, eps, alpha, temp,
+ *     flags, seed, board_id_base, rule_flags, the plane / type-rank packs, a hash of the move-rank table), the settings structs as the
+ *     device holds them (resign, root exploration, Gumbel, search, early stop, solver on, width), the sticky error word --, the B + 1
+ *     64-bit section offsets, the B meta records, and per board one section that starts on a 16-byte boundary.
+ *   ccz_snapshot_size (syncs): the bytes a save would write now.
+ *   ccz_snapshot_save (syncs): blob_dev is a device buffer of `capacity` bytes, 16-byte aligned; *bytes_host (may be NULL) = the bytes
+ *     written, exactly ccz_snapshot_size's. A capacity below that: -1, *bytes_host says what is needed, nothing is written. Refused
+ *     with scout slots (ccz_set_scouts). Changes nothing in the engine.
+ *   ccz_snapshot_load (syncs): STRICT. The engine must have been created with the same configuration and hold the same settings;
+ *     magic, version, total size, the offset table (monotone, inside `bytes`, every section as long as its board's counts say) and
+ *     every board's counts (n_nodes <= cap, ply <= max_plies, pi_used <= pi_cap) are checked BEFORE anything is written: -1,
+ *     ccz_last_error() names the field, the engine is exactly as it was. keep_board_id_base != 0: the one field a load may override
+ *     -- the engine keeps its own board_id_base (the boards' Philox streams are those of ids board_id_base + b from here on);
+ *     0: a different base is refused like any other field. Every tree lands in the pool half the engine's half word names; no
+ *     pointer changes, so a hipGraph captured before the load stays valid. The load also restores what a move boundary guarantees:
+ *     no pending leaf, zero in-flight counts, the evaluation cache cleared (ccz_eval_cache_clear). Growing cap, another B and loading a
+ *     subset of the boards are not supported.
+ *   ccz_snapshot_layout: the layout scan on its own: offsets_dev uint64 [B + 1] = the exclusive scan, in 64 bits, of the section sizes
+ *     of B boards with the counts n_nodes_dev / ply_dev (int32 [B], negative counts as 0) / pi_used_dev (uint32 [B]);
+ *     offsets_dev[B] = the sum. `sections`: CCZ_SNAP_PROOF (one proof byte per node) | CCZ_SNAP_VALUES (root value + flag per ply);
+ *     an engine's own blobs have CCZ_SNAP_VALUES always and CCZ_SNAP_PROOF once ccz_set_solver(1) has allocated the bytes. With
+ *     pad16(n) = n rounded up to 16, a section is CCZ_SNAP_FIXED_BYTES + 16 n_nodes + pad16(4 n_nodes) [+ pad16(n_nodes)] + 96 ply +
+ *     pad16(4 ply) + 3 pad16(ply) [+ pad16(4 ply) + pad16(ply)] + pad16(2 pi_used) + pad16(4 pi_used) bytes. Any B >= 1; stateless,
+ *     asynchronous. */
+#define CCZ_SNAP_PROOF 1u
+#define CCZ_SNAP_VALUES 2u
+#define CCZ_SNAP_HEADER_BYTES 512
+#define CCZ_SNAP_FIXED_BYTES 5088
+int ccz_snapshot_size(ccz_engine *e, void *stream, uint64_t *bytes_host);
+int ccz_snapshot_save(ccz_engine *e, void *stream, void *blob_dev, uint64_t capacity, uint64_t *bytes_host);
+int ccz_snapshot_load(ccz_engine *e, void *stream, const void *blob_dev, uint64_t bytes, int32_t keep_board_id_base);
+int ccz_snapshot_layout(void *stream, int32_t B, const int32_t *n_nodes_dev, const int32_t *ply_dev, const uint32_t *pi_used_dev,
+                        uint32_t sections, uint64_t *offsets_dev /* [B + 1] */);
+
 #ifdef __cplusplus
 }
 #endif
