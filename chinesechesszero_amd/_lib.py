@@ -24,6 +24,7 @@ REC_BYTES, REC_HDR, REC_IDS, REC_PI = 880, 96, 112, 368  # compact ply record (i
 REC_FLAGS, REC_FAST = 103, 1  # byte of the header's flags; CCZ_REC_FAST: a fast ply of playout-cap randomisation (no policy target)
 REC_RESIGNED, REC_PLAYON, REC_VALUE = 2, 4, 8  # CCZ_REC_*: the game ended by resignation / drew the play-on lot; the ply carries its root value
 REC_VALUE_OFF = 92  # float32 root value of a REC_VALUE ply (record bytes 92..95)
+REC_WEIGHT, REC_WEIGHT_OFF, REC_WEIGHT_ONE = 16, 90, 4096  # CCZ_REC_WEIGHT: record bytes 90..91 hold the ply's sampling weight, uint16 in 1/4096
 RESIGN_RESIGNED, RESIGN_PLAYON = 2, 4  # CCZ_RESIGN_*: resign_status state, bit 0 = the side that resigned / would have
 HEAD_POL_STRIDE, HEAD_VAL_STRIDE = 1536, 640  # CCZ_HEAD_*_STRIDE: fp16 elements per board of the head kernels' outputs
 
@@ -82,6 +83,10 @@ class Stats(C.Structure):
 class ResignStats(C.Structure):
     _fields_ = [("resigned_games", C.c_int64), ("resigned_by_red", C.c_int64), ("resigned_plies", C.c_int64), ("playon_games", C.c_int64),
                 ("playon_won", C.c_int64), ("playon_drawn", C.c_int64), ("playon_plies_after", C.c_int64)]
+
+
+class SurpriseStats(C.Structure):
+    _fields_ = [("target_plies", C.c_int64), ("surprise_sum", C.c_double), ("weights_clipped", C.c_int64)]
 
 
 class ExplorationStats(C.Structure):
@@ -151,6 +156,9 @@ PROTOTYPES = {
     "ccz_set_resign": (C.c_int, [_P, _P, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_double]),
     "ccz_get_resign_stats": (C.c_int, [_P, _P, C.POINTER(ResignStats)]),
     "ccz_resign_status": (C.c_int, [_P, _P, _P, _P, _P, _P]),
+    "ccz_set_surprise": (C.c_int, [_P, _P, C.c_int32, C.c_double, C.c_double]),
+    "ccz_get_surprise_stats": (C.c_int, [_P, _P, C.POINTER(SurpriseStats)]),
+    "ccz_ply_surprise": (C.c_int, [_P, _P, _P, _P]),
     "ccz_set_root_exploration": (C.c_int, [_P, _P, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32]),
     "ccz_get_exploration_stats": (C.c_int, [_P, _P, C.POINTER(ExplorationStats)]),
     "ccz_root_noise": (C.c_int, [_P, _P, _P, _P]),
@@ -189,6 +197,7 @@ PROTOTYPES = {
     "ccz_expand_records": (C.c_int, [_P, _P, C.c_int64, C.c_uint32, _P, _P, _P, _P, C.c_int64, C.c_int64, _P, _P, _P]),
     "ccz_ring_retire": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int32, _P]),
     "ccz_sample_records": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, C.c_uint32, _P, _P, _P, _P, _P, _P, _P]),
+    "ccz_sample_records_weighted": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int32, _P, _P, C.c_int64, C.c_uint32, _P, _P, _P, _P, _P, _P, _P]),
     "ccz_snapshot_size": (C.c_int, [_P, _P, C.POINTER(C.c_uint64)]),
     "ccz_snapshot_save": (C.c_int, [_P, _P, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
     "ccz_snapshot_load": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_int32]),

@@ -44,7 +44,7 @@ from .mcts import MCTS_AI
 from .net import PolicyValueNet
 from .parameters import BATCH_SIZE, C_PUCT, DATA_DIR, MODEL_DIR, PLAYOUT
 from .options import (SearchOptions, add_gumbel_args, add_resign_args, add_root_exploration_args, format_exploration, format_gumbel,  # noqa: F401
-                      format_search, gumbel_from_args, resign_from_args, root_exploration_from_args)
+                      add_surprise_args, format_search, gumbel_from_args, resign_from_args, root_exploration_from_args, surprise_from_args)
 from .checkpoint import add_checkpoint_args, checkpoint_from_args
 from .searchcfg import add_search_args, search_from_args
 from .stopcfg import add_early_stop_args, early_stop_from_args
@@ -81,6 +81,10 @@ class TupleSink:
     92..95: the engine records them while resignation is configured). ``finalize`` writes them as ``root_values.npy`` (float32,
     row-aligned with ``states.npy``, NaN where unknown) under the rules of ``policy_targets.npy``: only once some row carried a
     value, and merged across shards the same way (rows of older shards: NaN). The second value target of ``Trainer.step(q=...)``.
+
+    Sampling weights: a record may carry its ply's sampling weight (policy surprise weighting; ``CCZ_REC_WEIGHT`` records, bytes
+    90..91). ``finalize`` writes them as ``sample_weights.npy`` (float32, row-aligned with ``states.npy``, a row and its mirror image
+    sharing their ply's; ``replay.record_weights``) under the same rules: only once some record carried one, rows of older shards 1.0.
     """
 
     ARRAYS = {"states": ("_s.npy", np.float16, (17, 7, 10, 9)), "mcts": ("_p.npy", None, (2086,)), "winners": ("_z.npy", np.float32, ())}
@@ -221,10 +225,16 @@ class TupleSink:
 
     TARGETS = "policy_targets.npy"
     VALUES = "root_values.npy"
+    WEIGHTS = "sample_weights.npy"
 
-    def _write_dense_shard(self, base: str, s, p, w, t=None, v=None):
+    def _write_dense_shard(self, base: str, s, p, w, t=None, v=None, sw=None):
         """``t``: the rows' policy-target bytes; a ``_t.npy`` file is written only when one of them is 0. ``v``: the rows' root
-        values; a ``_v.npy`` file is written only when one of them is not NaN."""
+        values; a ``_v.npy`` file is written only when one of them is not NaN. ``sw``: the rows' sampling weights (given only for
+        records that carry them); a ``_sw.npy`` file is written whenever they are given."""
+        if sw is not None:
+            sw = np.asarray(sw, np.float32).reshape(-1)
+            if len(sw) != len(w):
+                raise ValueError(f"{len(sw)} sampling weights for {len(w)} rows")
         if v is not None:
             v = np.asarray(v, np.float32).reshape(-1)
             if len(v) != len(w):
@@ -239,6 +249,8 @@ class TupleSink:
             np.save(base + "_t.npy", t)
         if v is not None and not np.isnan(v).all():
             np.save(base + "_v.npy", v)
+        if sw is not None:
+            np.save(base + "_sw.npy", sw)
         np.save(base + "_z.npy", w.astype(np.float32, copy=False).reshape(-1))   # (written last: a shard counts once its z file exists)
         self._shards.append((base, int(len(w))))
 
@@ -337,8 +349,9 @@ class TupleSink:
             from ._lib import CczError
             raise CczError(f"{self.out_dir}: {len(self._rshards)} record shard(s) ({sum(r[1] for r in self._rshards)} plies) wait for the GPU expander "
                            "(ccz_expand_records): run finalize() where the collector ran; nothing was changed")
-        from ._lib import REC_FAST, REC_FLAGS, REC_VALUE
+        from ._lib import FLAG_NO_MIRROR, REC_FAST, REC_FLAGS, REC_HDR, REC_VALUE, REC_WEIGHT
         from .engine import expand_records, game_aligned_chunks
+        from .replay import record_weights
         for path, plies, flags, pot in list(self._rshards):
             tag = os.path.basename(path)[len(".rshard_"):-len(".npy")]
             prefix = f".shard_r{tag}_"
@@ -352,7 +365,17 @@ class TupleSink:
                 fast, valued = bool((part[:, REC_FLAGS] & REC_FAST).any()), bool((part[:, REC_FLAGS] & REC_VALUE).any())
                 rows = [x.cpu().numpy() for x in expand_records(part, flags, pot, targets=fast, values=valued)]
                 t, v = (rows[3] if fast else None), (rows[-1] if valued else None)
-                self._write_dense_shard(os.path.join(self.out_dir, f"{prefix}{k:04d}"), rows[0], rows[1], rows[2], t, v)
+                sw = None
+                if bool((part[:, REC_FLAGS] & REC_WEIGHT).any()):   # in row order: per game its T samples, then their T mirror images
+                    hdr = part[:, REC_HDR:REC_HDR + 4].contiguous().cpu().numpy().view(np.uint16).astype(np.int64)   # (t, T) of every record
+                    mul = 1 if flags & FLAG_NO_MIRROR else 2
+                    row = mul * (np.arange(len(hdr)) - hdr[:, 0]) + hdr[:, 0]
+                    wt = record_weights(part).cpu().numpy()
+                    sw = np.ones(mul * len(hdr), np.float32)
+                    sw[row] = wt
+                    if mul == 2:
+                        sw[row + hdr[:, 1]] = wt
+                self._write_dense_shard(os.path.join(self.out_dir, f"{prefix}{k:04d}"), rows[0], rows[1], rows[2], t, v, sw)
             os.remove(path)
             self._rshards.remove((path, plies, flags, pot))
 
@@ -446,9 +469,10 @@ class TupleSink:
             os.replace(tmp, paths[k])
         self._merge_targets(n_old, total, shards)
         self._merge_side(self.VALUES, "_v.npy", np.float32, np.nan, n_old, total, shards)
+        self._merge_side(self.WEIGHTS, "_sw.npy", np.float32, 1.0, n_old, total, shards)
         self._write_meta(total)
         for base, _ in shards:
-            for suffix in [sfx for sfx, _, _ in self.ARRAYS.values()] + ["_t.npy", "_v.npy"]:
+            for suffix in [sfx for sfx, _, _ in self.ARRAYS.values()] + ["_t.npy", "_v.npy", "_sw.npy"]:
                 if os.path.exists(base + suffix):
                     os.remove(base + suffix)
         os.remove(self._journal())
@@ -551,13 +575,21 @@ class CollectPipeline:
                  finalize_every: int = 0, on_playout=None, max_plies: int = 0, eval_cache_log2: int | None = None, gatherer=None,
                  dense_shards: bool = False, replay_plies: int = 0, train_every: int = 0, train_batch: int = BATCH_SIZE,
                  playout_cap_fast: int = 0, playout_cap_prob: float | None = None, resign=None, value_q_weight: float = 0.0,
-                 root_exploration=None, solver: bool = False, gumbel=None, search=None, early_stop=None,
+                 root_exploration=None, solver: bool = False, gumbel=None, search=None, early_stop=None, surprise=None,
                  checkpoint_dir: str | None = None, checkpoint_every: int = 0, resume: bool = False):
         # the engine options of the batched path, as BatchedSelfPlay takes them (options.OPTIONS: each None / False = off); only the search
         # parameters also run in the one-game loop (which then runs without scout slots)
         self.options = o = SearchOptions(n_playout, batched=n_boards > 1, resign=resign, root_exploration=root_exploration, gumbel=gumbel,
-                                         solver=solver, search=search, early_stop=early_stop)
-        self.resign, self.root_exploration, self.gumbel, self.solver, self.search, self.early_stop = o.keywords().values()
+                                         solver=solver, search=search, early_stop=early_stop, surprise=surprise)
+        self.resign, self.root_exploration, self.gumbel, self.solver, self.search, self.early_stop, self.surprise = o.keywords().values()
+        # policy surprise weighting: the records carry a sampling weight; with a ring the trainer's minibatch is drawn by it, without
+        # one the sink writes the weights next to the rows (sample_weights.npy)
+        if self.surprise is not None:
+            if dense_shards:
+                raise ValueError("policy surprise weighting needs the record shards (dense_shards=False): dense rows carry no weight")
+            if gatherer is not None and not (hasattr(gatherer, "post") or hasattr(gatherer, "_payload")):
+                raise ValueError("policy surprise weighting needs a record exchange (AsyncRecordExchange / RecordGatherer): "
+                                 "the dense rows a TupleGatherer moves carry no weight")
         # collect + train as one job (both 0: off): the rank that stores the union keeps it in a record ring of ``replay_plies`` plies
         # and runs one Trainer step of ``train_batch`` rows every ``train_every`` lockstep moves, once the ring holds a batch
         self.replay_plies, self.train_every, self.train_batch = int(replay_plies), int(train_every), int(train_batch)
@@ -947,10 +979,12 @@ class CollectPipeline:
                 self.trainer = Trainer(self.policy_value_net, amp_dtype="bf16")   # bf16: no GradScaler, so no host sync per update
             qw = getattr(self, "value_q_weight", 0.0)
             gen = self._generator() if getattr(self, "checkpoint_dir", None) else None   # (None: torch's global generator, as ever)
+            sp = getattr(self, "surprise", None)   # policy surprise weighting: the rows are drawn by their plies' weights
+            draw = dict(weighted=True, cap=sp.get("cap", 8.0)) if sp is not None else {}
             if self.playout_cap is None and not qw:
-                self.last_losses = self.trainer.step(*self.ring.sample(self.train_batch, generator=gen), sync=False)
+                self.last_losses = self.trainer.step(*self.ring.sample(self.train_batch, generator=gen, **draw), sync=False)
             else:   # fast plies train the value head only; rows that carry a root value blend it into the value target
-                st, pi, z, tg, q = self.ring.sample(self.train_batch, generator=gen, targets=True, values=True)
+                st, pi, z, tg, q = self.ring.sample(self.train_batch, generator=gen, targets=True, values=True, **draw)
                 self.last_losses = self.trainer.step(st, pi, z, sync=False, policy_mask=None if self.playout_cap is None else tg,
                                                      q=q if qw else None, q_weight=qw)
         if multi:
@@ -964,6 +998,8 @@ class CollectPipeline:
         if self.ring is not None:
             tail, head = self.ring.window()
             out.update(ring_tail=tail, ring_head=head, ring_bad_records=int(self.ring.bad.item()))
+            if getattr(self, "surprise", None) is not None:
+                out["ring_fallbacks"] = int(self.ring.fallbacks.item())
         if self.trainer is not None and self.trainer.steps:
             out.update({k: float(v) for k, v in self.last_losses.items()})
         if self.selfplay is not None:
@@ -1053,6 +1089,7 @@ def build_parser():
                         "in the tree and cost no evaluator row); sampling, records and targets are as without it")
     add_search_args(parser)
     add_early_stop_args(parser)
+    add_surprise_args(parser)
     parser.add_argument("--value-q-weight", type=float, default=0.0, help="with --train-every: weight of the recorded root value q in the value "
                         "target, (1 - w) z + w q on rows that carry one (0 = z alone)")
     add_checkpoint_args(parser)
@@ -1070,8 +1107,9 @@ def parse_args(argv=None):
     args.gumbel_cfg = gumbel_from_args(parser, args)
     args.search = search_from_args(parser, args)
     args.early_stop = early_stop_from_args(parser, args)
+    args.surprise = surprise_from_args(parser, args)
     args.options = dict(resign=args.resign, root_exploration=args.root_exploration, gumbel=args.gumbel_cfg, solver=args.solver, search=args.search,
-                        early_stop=args.early_stop)
+                        early_stop=args.early_stop, surprise=args.surprise)
     try:
         SearchOptions(args.playout, batched=args.boards > 1, **args.options)
     except ValueError as ex:

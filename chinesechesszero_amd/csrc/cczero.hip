@@ -90,6 +90,9 @@ struct ccz_engine {
     bool stop_on = false;          // ccz_set_early_stop(enabled): the host's shadow of StopCfg.enabled (scouts, a width above 1 and the Gumbel root are refused with it)
     int32_t *st_count = nullptr;   // ccz_searching: the count on the device
     bool gumbel_on = false;        // ccz_set_gumbel(enabled): the host's shadow of GumbelCfg.enabled (scouts and root exploration are refused with it)
+    SurpriseBlock *sp_block = nullptr; // device: the surprise settings and array pointers, behind the resignation settings (BoundaryCfg)
+    SurpriseBlock sp_host = {};        // the host's copy of the pointers (cfg stays zero here: the device's is the truth)
+    bool surprise_on = false;      // ccz_set_surprise(enabled): the host's shadow of SurpriseCfg.enabled (scouts are refused with it; a snapshot gets its section)
     // MCTS-solver (ccz_set_solver): the proof bytes [B][2][cap] (allocated by the first call that turns it on), the host's shadow of
     // SolverCfg.enabled, staging of ccz_root_proof (state [B], dist [B], child state [B][128], child dist [B][128])
     uint8_t *proof = nullptr, *st_proof = nullptr;
@@ -323,9 +326,10 @@ int ccz_create(const ccz_config *cfg, ccz_engine **out)
     ALLOC(d.budget, B);
     ALLOC(d.move_sims, B);
     ALLOC(d.target, B);
-    ResignCfg *rs_cfg = nullptr;
-    ALLOC(rs_cfg, 1); // zeroed: resignation off
-    d.rs_cfg = rs_cfg;
+    BoundaryCfg *bd_cfg = nullptr;
+    ALLOC(bd_cfg, 1); // zeroed: resignation off, policy surprise weighting off (its array pointers are written below)
+    d.rs_cfg = bd_cfg ? &bd_cfg->resign : nullptr;
+    e->sp_block = bd_cfg ? &bd_cfg->surprise : nullptr;
     ALLOC(d.rs_state, B);
     ALLOC(d.rs_run, B * 2);
     ALLOC(d.rs_fire, B);
@@ -365,6 +369,10 @@ int ccz_create(const ccz_config *cfg, ccz_engine **out)
     ALLOC(d.es_snap_s, B); // (k_reset below writes the -1 of "no snapshot")
     ALLOC(d.es_snap, B * kMaxLegal);
     ALLOC(d.es_stats, B);
+    ALLOC(e->sp_host.rec_kl, B * d.max_plies);
+    ALLOC(e->sp_host.rec_hask, B * d.max_plies);
+    ALLOC(e->sp_host.sp_stats, B);
+    if (he == hipSuccess) he = hipMemcpy(e->sp_block, &e->sp_host, sizeof e->sp_host, hipMemcpyHostToDevice); // (cfg zeros: off)
     ALLOC(e->st_count, 4);
     ALLOC(d.rec_ids, B * d.pi_cap);
     ALLOC(d.rec_pi, B * d.pi_cap);
@@ -580,6 +588,7 @@ int ccz_set_scouts(ccz_engine *e, int32_t n_scouts)
     if (n_scouts && e->budgets_on) return fail(-1, "ccz_set_scouts: not while simulation budgets are on (ccz_set_budgets(NULL) turns them off)");
     if (n_scouts && e->explore_on) return fail(-1, "ccz_set_scouts: not while root exploration is on (ccz_set_root_exploration)");
     if (n_scouts && e->gumbel_on) return fail(-1, "ccz_set_scouts: not while the Gumbel root search is on (ccz_set_gumbel)");
+    if (n_scouts && e->surprise_on) return fail(-1, "ccz_set_scouts: not while policy surprise weighting is on (ccz_set_surprise)");
     if (n_scouts && e->stop_on) return fail(-1, "ccz_set_scouts: not while the early stop is on (ccz_set_early_stop)");
     if (n_scouts && e->search_on) return fail(-1, "ccz_set_scouts: not while the search parameters are on (ccz_set_search): scouts rest on children being first visited in legal-move order");
     e->active = n_scouts ? e->d.B - n_scouts : 0;
@@ -780,6 +789,50 @@ int ccz_get_resign_stats(ccz_engine *e, void *stream, ccz_resign_stats *out)
         out->playon_drawn += (int64_t)b.playon_drawn;
         out->playon_plies_after += (int64_t)b.playon_after;
     }
+    return 0;
+}
+
+int ccz_set_surprise(ccz_engine *e, void *stream, int32_t enabled, double alpha, double cap)
+{
+    NEED(e);
+    if (!(alpha >= 0.0 && alpha <= 1.0)) return fail(-1, "ccz_set_surprise: alpha %g must be in [0, 1]", alpha);
+    if (!(cap >= 1.0 && cap <= 15.0)) return fail(-1, "ccz_set_surprise: cap %g must be in [1, 15]", cap);
+    if (enabled && SCOUTS(e)) return fail(-1, "ccz_set_surprise: not with scout slots (ccz_set_scouts): the one-game path records no game");
+    SurpriseCfg v;
+    v.enabled = enabled ? 1 : 0;
+    v.pad = 0;
+    v.alpha = alpha;
+    v.cap = cap;
+    const size_t n = (size_t)e->d.B * (size_t)e->d.max_plies;
+    hipLaunchKernelGGL(k_set_surprise, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, e->sp_block, v, n);
+    HIP_TRY(hipGetLastError());
+    e->surprise_on = enabled != 0;
+    return 0;
+}
+
+int ccz_get_surprise_stats(ccz_engine *e, void *stream, ccz_surprise_stats *out)
+{
+    NEED(e);
+    if (!out) return fail(-1, "ccz_get_surprise_stats: null output");
+    std::vector<SurpriseBoardStats> st;
+    if (const int rc = fetch_board_stats(e, (hipStream_t)stream, e->sp_host.sp_stats, st)) return rc;
+    memset(out, 0, sizeof *out);
+    for (const SurpriseBoardStats &b : st) { // in board order: the float64 total is the same on every run
+        out->target_plies += (int64_t)b.plies;
+        out->surprise_sum = out->surprise_sum + b.sum;
+        out->weights_clipped += (int64_t)b.clipped;
+    }
+    return 0;
+}
+
+int ccz_ply_surprise(ccz_engine *e, void *stream, float *kl_host, uint8_t *has_host)
+{
+    NEED(e);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t n = (size_t)e->d.B * (size_t)e->d.max_plies;
+    if (kl_host) HIP_TRY(hipMemcpyAsync(kl_host, e->sp_host.rec_kl, n * 4, hipMemcpyDeviceToHost, s));
+    if (has_host) HIP_TRY(hipMemcpyAsync(has_host, e->sp_host.rec_hask, n, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
     return 0;
 }
 
@@ -1660,8 +1713,29 @@ int ccz_sample_records(void *stream, const void *ring_dev, int64_t cap_plies, co
     return 0;
 }
 
+int ccz_sample_records_weighted(void *stream, const void *ring_dev, int64_t cap_plies, const int64_t *window_dev, const uint64_t *seed_dev, int32_t cap_q,
+                                int64_t *chosen_dev, int32_t *fallback_dev, int64_t batch, uint32_t flags, const uint8_t *plane_of_type_host,
+                                void *states_f16_dev, float *pi_dev, float *z_dev, int32_t *bad_records_dev, uint8_t *target_dev, float *value_dev)
+{
+    const char *who = "ccz_sample_records_weighted";
+    if (cap_plies <= 0 || batch < 0) return fail(-1, "%s: capacity must be positive and batch non-negative", who);
+    if (cap_q < 4096 || cap_q > 15 * 4096) return fail(-1, "%s: cap_q %d must be in 4096 .. 61440 (a cap of 1 .. 15 in 1/4096)", who, cap_q);
+    if (batch == 0) return 0;
+    if (const int rc = check_sample_args(who, ring_dev, window_dev, (const int64_t *)seed_dev, batch, states_f16_dev, pi_dev, z_dev, value_dev)) return rc;
+    if ((uintptr_t)chosen_dev & 7) return fail(-1, "%s: chosen must be 8-byte aligned", who);
+    if ((uintptr_t)fallback_dev & 3) return fail(-1, "%s: the fallback counter must be 4-byte aligned", who);
+    uint32_t typepack = 0;
+    if (const int rc = typepack_of(who, plane_of_type_host, &typepack)) return rc;
+    hipLaunchKernelGGL(k_sample_records_weighted, dim3((unsigned)batch), dim3(256), 0, (hipStream_t)stream, (const uint8_t *)ring_dev, (long long)cap_plies,
+                       (const long long *)window_dev, seed_dev, (int)cap_q, (long long *)chosen_dev, fallback_dev, (long long)batch,
+                       flags & (CCZ_FLAG_REFERENCE_QUIRKS | CCZ_FLAG_NO_MIRROR), typepack, (uint16_t *)states_f16_dev, pi_dev, z_dev, bad_records_dev,
+                       target_dev, value_dev);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // ---- engine snapshots (cczero.h: "Engine snapshots"; the kernels and the blob's layout: cczero_snapshot.h)
-static uint32_t snap_sections(const ccz_engine *e) { return (e->proof ? kSnapProof : 0u) | kSnapValues; }
+static uint32_t snap_sections(const ccz_engine *e) { return (e->proof ? kSnapProof : 0u) | kSnapValues | (e->surprise_on ? kSnapSurprise : 0u); }
 static size_t snap_dir_bytes(int B) { return ((size_t)B + 1) * 8 + (size_t)B * sizeof(BoardMeta); }
 static uint64_t snap_sections_start(int B) { return snap_pad16((uint64_t)kSnapHeader + snap_dir_bytes(B)); }
 
@@ -1674,6 +1748,7 @@ static int snap_read_settings(ccz_engine *e, hipStream_t s, SnapHeader &h)
     HIP_TRY(hipMemcpyAsync(&h.gumbel, e->d.gm_cfg, sizeof h.gumbel, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(&h.search, e->d.sr_cfg, sizeof h.search, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(&h.stop, e->d.es_cfg, sizeof h.stop, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&h.surprise, &e->sp_block->cfg, sizeof h.surprise, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(&sv, e->d.sv_cfg, sizeof sv, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(&h.err, e->d.err, 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(&h.half, e->d.half, 4, hipMemcpyDeviceToHost, s));
@@ -1840,8 +1915,11 @@ int ccz_snapshot_load(ccz_engine *e, void *stream, const void *blob_dev, uint64_
     SNAP_SAME("early_stop.n_sims", "%d", int, h.stop.n_sims, mine.stop.n_sims);
     SNAP_SAME("early_stop.gap_factor", "%.17g", double, h.stop.gap_factor, mine.stop.gap_factor);
     SNAP_SAME("early_stop.min_gain", "%.17g", double, h.stop.min_gain, mine.stop.min_gain);
+    SNAP_SAME("surprise.enabled", "%d", int, h.surprise.enabled, mine.surprise.enabled);
+    SNAP_SAME("surprise.alpha", "%.17g", double, h.surprise.alpha, mine.surprise.alpha);
+    SNAP_SAME("surprise.cap", "%.17g", double, h.surprise.cap, mine.surprise.cap);
 #undef SNAP_SAME
-    if (h.sections & ~(kSnapProof | kSnapValues)) return fail(-1, "ccz_snapshot_load: unknown sections bits 0x%x", h.sections);
+    if (h.sections & ~(kSnapProof | kSnapValues | kSnapSurprise)) return fail(-1, "ccz_snapshot_load: unknown sections bits 0x%x", h.sections);
     if (h.total_bytes != bytes)
         return fail(-1, "ccz_snapshot_load: total size: the header says %llu bytes, the caller passes %llu (a truncated or padded blob)",
                     (unsigned long long)h.total_bytes, (unsigned long long)bytes);
@@ -1896,7 +1974,7 @@ int ccz_snapshot_layout(void *stream, int32_t B, const int32_t *n_nodes_dev, con
                         uint64_t *offsets_dev)
 {
     if (B < 1 || !n_nodes_dev || !ply_dev || !pi_used_dev || !offsets_dev) return fail(-1, "ccz_snapshot_layout: bad arguments");
-    if (sections & ~(kSnapProof | kSnapValues)) return fail(-1, "ccz_snapshot_layout: unknown sections bits 0x%x", sections);
+    if (sections & ~(kSnapProof | kSnapValues | kSnapSurprise)) return fail(-1, "ccz_snapshot_layout: unknown sections bits 0x%x", sections);
     hipLaunchKernelGGL(k_snapshot_layout, dim3(1), dim3(1024), 0, (hipStream_t)stream, (int)B, n_nodes_dev, ply_dev, pi_used_dev, 1, sections, offsets_dev);
     HIP_TRY(hipGetLastError());
     return 0;

@@ -131,6 +131,29 @@ struct StopBoardStats {
     unsigned long long sims_saved, evaluations; // sum of n_b - s over the stops; snapshots taken by S4
 };
 
+// Policy surprise weighting (ccz_set_surprise): the settings as the device reads them, and the per-board counters.
+struct SurpriseCfg {
+    int32_t enabled; // 0: k_finish_move and k_harvest_records read this one word and do what they do without the feature
+    int32_t pad;
+    double alpha;    // share of a game's sampling weight that is spread by surprise, in [0, 1]
+    double cap;      // the largest weight of a ply, in [1, 15]
+};
+struct SurpriseBoardStats {
+    unsigned long long plies;   // target plies whose surprise was measured
+    double sum;                 // the sum of their stored (float32) surprise, in ply order
+    unsigned long long clipped; // weights the harvest clipped at the cap
+};
+// The settings and the arrays behind them, as the solver's proof bytes lie behind SolverCfg -- and the whole block behind the resignation
+// settings, in ONE allocation (BoundaryCfg: Dev.rs_cfg points at its first member). Dev is a by-value argument of every kernel: with four
+// more pointers in it the compiler schedules k_step, k_select and k_scouted_run differently (9834 -> 9721 instructions in k_step) though
+// their source is the same; this way Dev keeps its bytes and every kernel that does not read the block is the code it was.
+struct SurpriseBlock {
+    SurpriseCfg cfg;              // written by k_set_surprise in stream order
+    float *rec_kl;                // [B][max_plies] KL(pi || prior) of the ply as recorded
+    uint8_t *rec_hask;            // [B][max_plies] 1: rec_kl holds the ply's surprise (a policy target recorded with the option on)
+    SurpriseBoardStats *sp_stats; // [B]
+};
+
 // MCTS-solver (ccz_set_solver): the settings as the device reads them, and the per-board counters. A proof byte holds the state in
 // bits 0..1 -- the view of the side to move at the node -- and the distance to the end in plies in bits 2..7 (saturating at 63; 0 for a
 // draw). The array lives behind the settings, not in Dev: it is allocated by the first ccz_set_solver(1), and a graph captured before
@@ -251,6 +274,13 @@ struct Dev {
     int32_t *es_snap;            // [B][128] S4: the root children's visit counts at that time (zero past k)
     StopBoardStats *es_stats;    // [B]
 };
+// ---- policy surprise weighting (ccz_set_surprise). Always allocated; "off" is SurpriseCfg.enabled == 0: k_finish_move and
+// k_harvest_records read that one word, through rs_cfg (see SurpriseBlock)
+struct BoundaryCfg {
+    ResignCfg resign;
+    SurpriseBlock surprise;
+};
+__device__ __forceinline__ const SurpriseBlock *surprise_block(const Dev &D) { return &reinterpret_cast<const BoundaryCfg *>(D.rs_cfg)->surprise; }
 __device__ __forceinline__ int plane_of(const Dev &D, int type) { return (int)((D.chanpack >> (3 * type)) & 7u); }
 __device__ __forceinline__ int type_in_plane(const Dev &D, int chan) { return (int)((D.typepack >> (3 * chan)) & 7u) + 1; }
 

@@ -2153,6 +2153,42 @@ __global__ __launch_bounds__(64) void k_finish_move(Dev D, const int32_t *forced
         D.rec_pi[o] = (float)s_pi[i];
     }
 
+    // ---- policy surprise weighting (ccz_set_surprise; off: this one word read). s = KL(pi || prior) of a policy-target ply: pi is s_pi
+    // as just recorded, the prior the children's stored P (root noise is never stored). A lane forms the terms of its own children (the
+    // two logarithms are the cost), then every lane adds the same <= 128 LDS words in child order in float64: s is wave-uniform without
+    // a broadcast and is the sequential sum bit for bit (a term of pi_i = 0 is +0.0, which changes no sum). s_g is free until the
+    // resignation's root value and sample_move.
+    const SurpriseBlock *sp = surprise_block(D);
+    if (sp->cfg.enabled) {
+        double s = 0.0;
+        if (tgt) {
+            __syncthreads(); // s_pi and the scratch rows of the targets are complete
+            for (int i = lane; i < k; i += 64) {
+                const double p = s_pi[i];
+                double term = 0.0;
+                if (p > 0.0) {
+                    double q = (double)rv.A[CCZ_IDX(D, rv.root.fc + i, D.cap)].P;
+                    if (!(q >= 0x1p-100)) q = 0x1p-100;
+                    term = p * (det_log(p) - det_log(q));
+                }
+                s_g[i] = term;
+            }
+            __syncthreads();
+            for (int i = 0; i < k; ++i) s = s + s_g[i];
+            if (!(s > 0.0)) s = 0.0;
+            __syncthreads(); // every lane has read s_g before the code below writes it
+        }
+        if (lane == 0) {
+            sp->rec_kl[r] = (float)s;
+            sp->rec_hask[r] = tgt ? 1 : 0;
+            if (tgt) {
+                SurpriseBoardStats &ss = sp->sp_stats[b];
+                ss.plies += 1;
+                ss.sum = ss.sum + (double)(float)s;
+            }
+        }
+    }
+
     // A ply is played by a move or by resigning: the record took k entries, the board's Philox move counter advances, and the board's
     // tree (n_nodes nodes) lies in the other pool half
     const auto ply_played = [&](int n_nodes) { m.ply += 1; m.move_counter += 1; m.n_nodes = n_nodes; m.half = (uint8_t)nh; m.pi_used += (uint32_t)k; };
@@ -2611,6 +2647,8 @@ __global__ __launch_bounds__(256) void k_harvest(Dev D, const long long *row_bas
 constexpr int kRecBytes = 880, kRecHdr = 96, kRecIds = 112, kRecPi = 368;
 constexpr uint8_t kRecFast = 1; // PlyHeader.flags (CCZ_REC_FAST): a fast move of playout-cap randomisation, its pi is no policy target
 constexpr uint8_t kRecValue = 8; // PlyHeader.flags (CCZ_REC_VALUE): bytes 92..95 of the record hold the ply's root value (float32)
+constexpr uint8_t kRecWeight = 16; // PlyHeader.flags (CCZ_REC_WEIGHT): bytes 90..91 of the record hold the ply's sampling weight (uint16, 1/4096)
+constexpr int kRecWeightOff = 90;
 constexpr int kRecValueOff = 92; // (flags 2 and 4, CCZ_REC_RESIGNED / CCZ_REC_PLAYON on every ply of such a game, are kResigned / kPlayOn)
 struct __align__(4) PlyHeader {
     uint16_t t, T;      // ply index inside its game, plies of the game
@@ -2629,6 +2667,24 @@ __global__ __launch_bounds__(256) void k_harvest_records(Dev D, const long long 
     if (rb < 0) return;
     const BoardMeta m = D.meta[b];
     const int T = m.ply;
+    // policy surprise weighting (ccz_set_surprise; off: this one word read): the game's n plies that carry a surprise and their sum S, the
+    // float32 values added as doubles in ply order -- by every block of the game in the same order, so no block waits for another
+    const SurpriseBlock *sp = surprise_block(D);
+    const bool weigh = sp->cfg.enabled != 0;
+    double sp_alpha = 0.0, sp_cap = 0.0, S = 0.0;
+    const float *rec_kl = nullptr;
+    const uint8_t *rec_hask = nullptr;
+    int n = 0;
+    if (weigh) {
+        sp_alpha = sp->cfg.alpha;
+        sp_cap = sp->cfg.cap;
+        rec_kl = sp->rec_kl;
+        rec_hask = sp->rec_hask;
+        for (int t = 0; t < T; ++t) {
+            const size_t r = (size_t)b * D.max_plies + t;
+            if (rec_hask[r]) { S = S + (double)rec_kl[r]; n += 1; }
+        }
+    }
     for (int t = blockIdx.y; t < T; t += gridDim.y) {
         const size_t r = (size_t)b * D.max_plies + t;
         uint32_t *rec = (uint32_t *)(out + (size_t)(rb + t) * kRecBytes);
@@ -2636,13 +2692,21 @@ __global__ __launch_bounds__(256) void k_harvest_records(Dev D, const long long 
         const size_t po = (size_t)b * D.pi_cap + D.rec_off[r];
         if (tid < 24) {
             uint32_t v = ((const uint32_t *)(D.rec_sq + r * 96))[tid];
-            if (tid == 22) v &= 0x0000ffffu;
+            if (tid == 22) {
+                v &= 0x0000ffffu;
+                if (weigh) { // bytes 90..91: the ply's sampling weight in 1/4096 (CCZ_REC_WEIGHT)
+                    double w = 1.0;
+                    if (rec_hask[r] && S > 0.0) w = (1.0 - sp_alpha) + sp_alpha * (double)n * (double)rec_kl[r] / S;
+                    if (w > sp_cap) { w = sp_cap; atomicAdd(&sp->sp_stats[b].clipped, 1ull); }
+                    v |= (uint32_t)(uint16_t)floor(w * 4096.0 + 0.5) << 16;
+                }
+            }
             if (tid == 23) v = D.rec_hasv[r] ? __float_as_uint(D.rec_value[r]) : 0u; // bytes 92..95: the ply's root value (CCZ_REC_VALUE)
             rec[tid] = v;
         } else if (tid == 24) {
             PlyHeader h;
             h.t = (uint16_t)t; h.T = (uint16_t)T; h.winner = m.winner; h.turn = D.rec_turn[r]; h.k = (uint8_t)k;
-            h.flags = (uint8_t)((D.rec_target[r] ? 0 : kRecFast) | (D.rs_state[b] & (kResigned | kPlayOn)) | (D.rec_hasv[r] ? kRecValue : 0));
+            h.flags = (uint8_t)((D.rec_target[r] ? 0 : kRecFast) | (D.rs_state[b] & (kResigned | kPlayOn)) | (D.rec_hasv[r] ? kRecValue : 0) | (weigh ? kRecWeight : 0));
             h.board_id = (uint32_t)(D.board_id_base + (uint64_t)b); h.game_no = m.game_no;
             *(PlyHeader *)(rec + kRecHdr / 4) = h;
         }
@@ -2806,19 +2870,15 @@ __device__ __forceinline__ SampledPly locate_sampled_ply(const uint8_t *ring, lo
     return s;
 }
 
-// One block per drawn row (locate_sampled_ply): output row blockIdx.x gets exactly the bytes k_expand_records writes for that
-// ply and pass (form_row), and in target / value (either may be null) the ply's policy-target byte and root value. A bad draw
-// counts in *bad and its row is zeros, 0 and NaN. HBM-write-bound: 29.8 KB out, <= 1.6 KB in.
-__global__ __launch_bounds__(256) void k_sample_records(const uint8_t *ring, long long cap_plies, const long long *window, const long long *draws,
-                                                          long long batch, uint32_t flags, uint32_t typepack, uint16_t *states, float *pi,
-                                                          float *z, int32_t *bad, uint8_t *target, float *value)
+// Output row j of a located draw, by the 256 threads of a block (s is block-uniform): exactly the bytes k_expand_records writes for
+// that ply and pass (form_row), and in target / value (either may be null) the ply's policy-target byte and root value. A bad draw
+// counts in *bad and its row is zeros, 0 and NaN. The ONE tail of k_sample_records and k_sample_records_weighted.
+__device__ __forceinline__ void write_sampled_row(const uint8_t *ring, long long cap_plies, const SampledPly &s, long long j, uint32_t flags,
+                                                  uint32_t typepack, uint8_t (*hist)[96], uint16_t *states, float *pi, float *z, int32_t *bad,
+                                                  uint8_t *target, float *value)
 {
-    const long long j = blockIdx.x;
     const int tid = threadIdx.x;
-    if (j >= batch) return;
-    __shared__ __align__(16) uint8_t hist[8][96];
     const bool quirks = (flags & 1u) != 0;
-    const SampledPly s = locate_sampled_ply(ring, cap_plies, window, draws[j], (flags & 2u) ? 1 : 2, bad); // (block-uniform)
     if (!s.ok) {
         uint32_t *srow = (uint32_t *)(states + (size_t)j * 10710);
         for (int i = tid; i < 5355; i += 256) srow[i] = 0u;
@@ -2834,6 +2894,68 @@ __global__ __launch_bounds__(256) void k_sample_records(const uint8_t *ring, lon
     stage_history(hist, ring, s.first, s.h, quirks, [&](long long q) { return CCZ_RING_IDX(bad, q % cap_plies, cap_plies); });
     form_row(RecordPly{hist, s.rec, s.h}, s.pass, quirks ? 1 : s.h.turn, typepack, states, pi, z, j);
     if (tid == 0) write_side(target, value, j, rec_target(s.h), rec_value(s.rec, s.h));
+}
+
+// One block per drawn row (locate_sampled_ply, write_sampled_row): output row blockIdx.x is that of draw draws[blockIdx.x].
+// HBM-write-bound: 29.8 KB out, <= 1.6 KB in.
+__global__ __launch_bounds__(256) void k_sample_records(const uint8_t *ring, long long cap_plies, const long long *window, const long long *draws,
+                                                          long long batch, uint32_t flags, uint32_t typepack, uint16_t *states, float *pi,
+                                                          float *z, int32_t *bad, uint8_t *target, float *value)
+{
+    const long long j = blockIdx.x;
+    if (j >= batch) return;
+    __shared__ __align__(16) uint8_t hist[8][96];
+    const SampledPly s = locate_sampled_ply(ring, cap_plies, window, draws[j], (flags & 2u) ? 1 : 2, bad); // (block-uniform)
+    write_sampled_row(ring, cap_plies, s, j, flags, typepack, hist, states, pi, z, bad, target, value);
+}
+
+// The ring draws by weight (include/cczero.h "policy surprise weighting"): one block per output row j, as above, but the block draws
+// its own u by rejection. In round r = 0..3, lane l of the first wave takes the Philox4x32-10 words o of (key *seed, counter {hi = j,
+// lo = 64 r + l}): candidate u = (o0:o1) >> 2 (62 bits), a = ((o2:o3) >> 11) * 2^-53 in [0, 1). It locates u (locate_sampled_ply),
+// reads the ply's weight wq (uint16 at byte 90 of a CCZ_REC_WEIGHT record, else 4096 = 1.0) and accepts iff the candidate is ok and
+// a * cap_q < wq. The lowest accepting (round, lane) wins by ballot; later rounds are not run. Nothing accepted in 256 candidates: the
+// row takes candidate (0, 0) and *fallback counts it. The chosen u goes through LDS to the whole block and to chosen[j]; from there the
+// row is what k_sample_records writes for draw u. Candidates that lose are counted nowhere, ok or not.
+__global__ __launch_bounds__(256) void k_sample_records_weighted(const uint8_t *ring, long long cap_plies, const long long *window,
+                                                                   const uint64_t *seed, int cap_q, long long *chosen, int32_t *fallback,
+                                                                   long long batch, uint32_t flags, uint32_t typepack, uint16_t *states,
+                                                                   float *pi, float *z, int32_t *bad, uint8_t *target, float *value)
+{
+    const long long j = blockIdx.x;
+    const int tid = threadIdx.x;
+    if (j >= batch) return;
+    __shared__ __align__(16) uint8_t hist[8][96];
+    __shared__ long long s_u;
+    const long long mul = (flags & 2u) ? 1 : 2;
+    if (tid < 64) {
+        const uint64_t key = *seed;
+        long long u00 = 0;
+        bool found = false;
+        for (int r = 0; r < 4 && !found; ++r) {
+            uint32_t o[4];
+            philox4x32(key, (uint64_t)j, (uint64_t)(r * 64 + tid), o);
+            const long long u = (long long)((((uint64_t)o[0] << 32) | o[1]) >> 2);
+            const double a = (double)((((uint64_t)o[2] << 32) | o[3]) >> 11) * 0x1p-53;
+            if (r == 0) u00 = u; // (lane 0's is candidate (0, 0))
+            const SampledPly c = locate_sampled_ply(ring, cap_plies, window, u, mul, bad);
+            int wq = 4096;
+            if (c.ok && (c.h.flags & kRecWeight)) wq = *(const uint16_t *)(c.rec + kRecWeightOff);
+            const uint64_t hit = __ballot(c.ok && a * (double)cap_q < (double)wq);
+            if (hit) {
+                if (tid == __ffsll((long long)hit) - 1) s_u = u;
+                found = true; // (wave-uniform: the ballot is)
+            }
+        }
+        if (!found && tid == 0) {
+            s_u = u00;
+            if (fallback) atomicAdd(fallback, 1);
+        }
+    }
+    __syncthreads();
+    const long long u = s_u;
+    if (tid == 0 && chosen) chosen[j] = u;
+    const SampledPly s = locate_sampled_ply(ring, cap_plies, window, u, mul, bad); // (block-uniform)
+    write_sampled_row(ring, cap_plies, s, j, flags, typepack, hist, states, pi, z, bad, target, value);
 }
 
 // After an append of logical plies [head_old, head_new) has been copied into the ring (it overwrote the slots of
@@ -2900,6 +3022,15 @@ __global__ void k_draw_budgets(Dev D, int n, int n_full, int n_fast, double p_fu
 __global__ void k_set_resign(ResignCfg *cfg, ResignCfg v)
 {
     if (blockIdx.x == 0 && threadIdx.x == 0) *cfg = v;
+}
+
+// ccz_set_surprise: the settings reach the device in stream order; the has-bits of all n plies are cleared, so a ply recorded before the
+// call carries no surprise whatever an earlier game left at its index
+__global__ void k_set_surprise(SurpriseBlock *blk, SurpriseCfg v, size_t n)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) blk->rec_hask[i] = 0;
+    if (i == 0) blk->cfg = v;
 }
 
 // ccz_set_gumbel: the settings reach the device in stream order; every board's row is invalidated (n_eff and m may have changed)

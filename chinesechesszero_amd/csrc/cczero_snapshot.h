@@ -12,13 +12,14 @@
 //   sections_start           = the above rounded up to 16; board b's section is [sections_start + offsets[b], sections_start + offsets[b + 1])
 // A section: the fixed rows (kSnapFixed bytes, the table below), then nodeA [n_nodes][16], nodeB [n_nodes][4], proof [n_nodes] (with
 // kSnapProof), rec_sq [ply][96], rec_off [ply][4], rec_turn / rec_k / rec_target [ply], rec_value [ply][4] and rec_hasv [ply] (with
-// kSnapValues), rec_ids [pi_used][2], rec_pi [pi_used][4] -- every array rounded up to 16 bytes with zeros.
+// kSnapValues), rec_kl [ply][4], rec_hask [ply] and the board's SurpriseBoardStats row (with kSnapSurprise: only while ccz_set_surprise is
+// on), rec_ids [pi_used][2], rec_pi [pi_used][4] -- every array rounded up to 16 bytes with zeros.
 #pragma once
 #include "cczero_device.h"
 
 namespace ccz {
 
-constexpr uint32_t kSnapProof = 1u, kSnapValues = 2u; // CCZ_SNAP_PROOF / CCZ_SNAP_VALUES
+constexpr uint32_t kSnapProof = 1u, kSnapValues = 2u, kSnapSurprise = 4u; // CCZ_SNAP_PROOF / CCZ_SNAP_VALUES / CCZ_SNAP_SURPRISE
 constexpr uint64_t kSnapMagic = 0x0050414E535A4343ull; // "CCZSNAP\0"
 constexpr uint32_t kSnapVersion = 1u;
 constexpr int kSnapHeader = 512;
@@ -80,10 +81,13 @@ struct SnapHeader {
     GumbelCfg gumbel;
     SearchCfg search;
     StopCfg stop;
-    uint8_t pad[kSnapHeader - 336];
+    SurpriseCfg surprise;     // (zeros while ccz_set_surprise never was on: the bytes a header without the field has there)
+    uint8_t pad[kSnapHeader - 360];
 };
 static_assert(sizeof(SnapHeader) == kSnapHeader, "the snapshot header is 512 bytes");
-static_assert(offsetof(SnapHeader, resign) == 160 && offsetof(SnapHeader, stop) == 296, "snapshot.py reads the settings at these offsets");
+static_assert(offsetof(SnapHeader, resign) == 160 && offsetof(SnapHeader, stop) == 296 && offsetof(SnapHeader, surprise) == 336,
+              "snapshot.py reads the settings at these offsets");
+static_assert(sizeof(SurpriseCfg) == 24 && sizeof(SurpriseBoardStats) == 24, "the snapshot's surprise settings and counter row");
 
 __host__ __device__ __forceinline__ uint64_t snap_pad16(uint64_t n) { return (n + 15ull) & ~15ull; }
 
@@ -94,6 +98,7 @@ __host__ __device__ __forceinline__ uint64_t snap_section_bytes(uint32_t section
     if (sections & kSnapProof) s += snap_pad16(n_nodes);
     s += ply * 96ull + snap_pad16(ply * 4ull) + 3ull * snap_pad16(ply);
     if (sections & kSnapValues) s += snap_pad16(ply * 4ull) + snap_pad16(ply);
+    if (sections & kSnapSurprise) s += snap_pad16(ply * 4ull) + snap_pad16(ply) + snap_pad16(sizeof(SurpriseBoardStats));
     s += snap_pad16(pi_used * 2ull) + snap_pad16(pi_used * 4ull);
     return s;
 }
@@ -226,6 +231,12 @@ template <bool PACK> __device__ __forceinline__ void snap_section(const Dev &D, 
     if (sections & kSnapValues) {
         p = snap_array<PACK>(o, p, D.rec_value + rbase, pl * 4, t, nt);
         p = snap_array<PACK>(o, p, D.rec_hasv + rbase, pl, t, nt);
+    }
+    if (sections & kSnapSurprise) {
+        const SurpriseBlock *sp = surprise_block(D);
+        p = snap_array<PACK>(o, p, sp->rec_kl + rbase, pl * 4, t, nt);
+        p = snap_array<PACK>(o, p, sp->rec_hask + rbase, pl, t, nt);
+        p = snap_array<PACK>(o, p, sp->sp_stats + sb, sizeof(SurpriseBoardStats), t, nt);
     }
     p = snap_array<PACK>(o, p, D.rec_ids + pbase, pu * 2, t, nt);
     p = snap_array<PACK>(o, p, D.rec_pi + pbase, pu * 4, t, nt);

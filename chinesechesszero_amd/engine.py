@@ -458,6 +458,33 @@ class SelfPlayEngine:
         check(self.L.ccz_get_resign_stats(self.h, self._stream(), C.byref(s)))
         return {f: int(getattr(s, f)) for f, _ in _lib.ResignStats._fields_}
 
+    # ------------------------------------------------------------------ policy surprise weighting (include/cczero.h ccz_set_surprise)
+    def set_surprise(self, alpha=0.5, cap: float = 8.0):
+        """Policy surprise weighting from the next :meth:`finish_move` on: every policy-target ply stores KL(pi || prior), and
+        :meth:`harvest_record_chunks` writes a sampling weight into the records (``REC_WEIGHT``, bytes 90..91): a share
+        ``1 - alpha`` of a game's weight spread evenly, the share ``alpha`` (in [0, 1]) by surprise, no ply above ``cap`` (in
+        [1, 15]). ``alpha`` None: off, the state of a new engine. Plies recorded before the call carry no surprise. Not with
+        scout slots. No host sync."""
+        if alpha is None:
+            check(self.L.ccz_set_surprise(self.h, self._stream(), 0, 0.5, 8.0))
+            return
+        check(self.L.ccz_set_surprise(self.h, self._stream(), 1, float(alpha), float(cap)))
+
+    def surprise_stats(self) -> dict:
+        """Sums over boards in board order (``ccz_surprise_stats``; syncs): ``target_plies`` measured, ``surprise_sum`` (float) of
+        their stored surprise and ``weights_clipped`` at the cap by the harvest."""
+        s = _lib.SurpriseStats()
+        check(self.L.ccz_get_surprise_stats(self.h, self._stream(), C.byref(s)))
+        return {"target_plies": int(s.target_plies), "surprise_sum": float(s.surprise_sum), "weights_clipped": int(s.weights_clipped)}
+
+    def ply_surprise(self):
+        """``(kl float32 [B, max_plies], has uint8 [B, max_plies])``: the surprise stored with the plies of the boards' current
+        games and whether a ply carries one; entries at or past a board's ply count are stale. Syncs (tests, reports)."""
+        kl = np.zeros((self.B, self.max_plies), np.float32)
+        has = np.zeros((self.B, self.max_plies), np.uint8)
+        check(self.L.ccz_ply_surprise(self.h, self._stream(), _ptr(kl), _ptr(has)))
+        return kl, has
+
     # ------------------------------------------------------------------ root exploration (include/cczero.h ccz_set_root_exploration)
     def set_root_exploration(self, eps, alpha: float | None = None, forced_k: float = 2.0, prune_targets: bool = True):
         """Exploration inside the search, on policy-target moves: Dirichlet(``alpha``) noise of weight ``eps`` in the ROOT's priors

@@ -3,7 +3,8 @@ early stop -- each described ONCE (:data:`OPTIONS`), and what a front end does w
 what, call the setters in one order, report. Also the command line of resign / root exploration / Gumbel in the shape of ``searchcfg`` /
 ``stopcfg`` (which keep the search parameters' and the early stop's), and the move of the arg-max front ends. No GPU here. Adding an
 option: ``ccz_set_x`` on the C side (which refuses what it excludes), the setter in ``engine.py``, ONE entry in ``OPTIONS`` (and a rule
-in ``SearchOptions.__init__`` if it excludes another), the keyword on the front ends that allow it."""
+in ``SearchOptions.__init__`` if it excludes another), the keyword on the front ends that allow it. ``RECORD_OPTIONS`` holds, in the same
+shape, what decides how a recorded game is trained on (policy surprise weighting); ``SearchOptions`` handles both tables alike."""
 from __future__ import annotations
 
 from collections import namedtuple
@@ -13,6 +14,7 @@ from .stopcfg import stop_report
 
 RESIGN_MOVES, RESIGN_MIN_PLY, RESIGN_PLAYON, FORCED_PLAYOUTS = 2, 30, 0.1, 2.0
 GUMBEL_CONSIDERED, GUMBEL_C_VISIT, GUMBEL_C_SCALE = 16, 50.0, 1.0
+SURPRISE_WEIGHT, SURPRISE_CAP = 0.5, 8.0
 
 
 # ---------------------------------------------------------------------- fragments of the collector's periodic log line
@@ -42,6 +44,20 @@ def format_gumbel(x: dict) -> str:
     m = f"{x['considered_sum'] / n:.2f}" if n else "n/a"
     off = f"{x['offvisit_moves'] / n:.4f}" if n else "n/a"
     return f", gumbel moves {n}, mean considered {m}, off-visit share {off}"
+
+
+def surprise_report(x: dict) -> dict:
+    """``x`` = ``SelfPlayEngine.surprise_stats()`` and what the log line says of it: the mean surprise per policy-target ply and the
+    share of those plies whose weight the harvest clipped at the cap (None before the first)."""
+    n = x["target_plies"]
+    return dict(x, mean_surprise=x["surprise_sum"] / n if n else None, clipped_share=x["weights_clipped"] / n if n else None)
+
+
+def format_surprise(x: dict) -> str:
+    r = surprise_report(x)
+    mean = f"{r['mean_surprise']:.4f}" if r["target_plies"] else "n/a"
+    share = f"{r['clipped_share']:.4f}" if r["target_plies"] else "n/a"
+    return f", surprise per target ply {mean} over {r['target_plies']}, weights clipped {share}"
 
 
 def format_search(cfg: dict, stats: dict) -> str:
@@ -84,6 +100,16 @@ OPTIONS = {
 }
 
 
+# What decides how a recorded game is trained on, not how it is searched: the same description, applied and reported after OPTIONS. Only the
+# front ends that record games (BatchedSelfPlay, the collector) take these keywords.
+RECORD_OPTIONS = {
+    "surprise": Option("set_surprise", "policy surprise weighting", lambda e: format_surprise(e.surprise_stats()),
+                       report=lambda e: {"surprise": surprise_report(e.surprise_stats())},
+                       of_scalar=lambda x: {} if x is True else {"alpha": float(x)}),
+}
+ALL_OPTIONS = {**OPTIONS, **RECORD_OPTIONS}
+
+
 class SearchOptions:
     """The options of ONE front end, from the keywords it was given (``resign=..., solver=..., ...``: the options it allows). None / False: off;
     a dict is copied, another value goes through ``of_scalar``; ``gumbel`` searches ``n_playout`` (the front end's simulations per move) unless
@@ -93,7 +119,7 @@ class SearchOptions:
 
     def __init__(self, n_playout=None, sampling: str = "device", batched: bool = True, width: int = 1, **given):
         self.on = on = {}
-        for name, o in OPTIONS.items():
+        for name, o in ALL_OPTIONS.items():
             if name in given:
                 cfg = given.pop(name)
                 if cfg is not None and cfg is not False and (cfg or name != "solver"):
@@ -104,10 +130,10 @@ class SearchOptions:
         if "gumbel" in on:
             on["gumbel"].setdefault("n_sims", n_playout)
         for name in on:
-            if sampling != "device" and OPTIONS[name].device_only:
-                raise ValueError(f"{name} needs sampling='device': {OPTIONS[name].device_only}")
-            if not batched and not OPTIONS[name].one_game:
-                raise ValueError(f"{OPTIONS[name].what} runs on the batched path: n_boards (--boards) must be > 1")
+            if sampling != "device" and ALL_OPTIONS[name].device_only:
+                raise ValueError(f"{name} needs sampling='device': {ALL_OPTIONS[name].device_only}")
+            if not batched and not ALL_OPTIONS[name].one_game:
+                raise ValueError(f"{ALL_OPTIONS[name].what} runs on the batched path: n_boards (--boards) must be > 1")
         if "gumbel" in on and "root_exploration" in on:
             raise ValueError("gumbel and root_exploration (--gumbel, --root-noise-eps) exclude each other: the Gumbel draw is the root's exploration")
         if "gumbel" in on and "early_stop" in on:
@@ -117,21 +143,21 @@ class SearchOptions:
 
     def keywords(self) -> dict:
         """``{keyword: value}`` of every allowed option, on or off, as a front end takes them (and in OPTIONS' order)."""
-        return {name: getattr(self, name) for name in OPTIONS if hasattr(self, name)}
+        return {name: getattr(self, name) for name in ALL_OPTIONS if hasattr(self, name)}
 
     def apply(self, engine):
-        """Call the setters of the options that are on, and no others: resign, root exploration, gumbel, solver, search, early stop.
+        """Call the setters of the options that are on, and no others: resign, root exploration, gumbel, solver, search, early stop, surprise.
         Every setter writes its own settings block only, so the order decides nothing."""
         for name, cfg in self.on.items():
-            getattr(engine, OPTIONS[name].setter)(**cfg)
+            getattr(engine, ALL_OPTIONS[name].setter)(**cfg)
 
     def report(self, engine) -> dict:
         """The entries of the options that are on in a front end's JSON result (syncs)."""
-        return {k: v for name in self.on if OPTIONS[name].report for k, v in OPTIONS[name].report(engine).items()}
+        return {k: v for name in self.on if ALL_OPTIONS[name].report for k, v in ALL_OPTIONS[name].report(engine).items()}
 
     def log_line(self, engine) -> str:
         """The fragments of the options that are on, for the collector's periodic log line (empty with none on; syncs)."""
-        return "".join(OPTIONS[name].log(engine) for name in self.on)
+        return "".join(ALL_OPTIONS[name].log(engine) for name in self.on)
 
 
 # ---------------------------------------------------------------------- the move of an arg-max front end
@@ -252,3 +278,28 @@ def gumbel_from_args(ap, a):
     """(``a.playout``: the simulations of a move.)"""
     return _from_args(ap, a, "--gumbel", "the Gumbel root search is off", ("--gumbel-considered", "--gumbel-c-visit", "--gumbel-c-scale"),
                       make_gumbel, a.gumbel, a.playout, a.gumbel_considered, a.gumbel_c_visit, a.gumbel_c_scale)
+
+
+def make_surprise(weight, cap=None):
+    """The dict of ``SelfPlayEngine.set_surprise``'s arguments (None without a weight). ValueError: what ``ccz_set_surprise`` refuses."""
+    if weight is None:
+        return None
+    if not 0.0 <= weight <= 1.0:
+        raise ValueError(f"--surprise-weight must be in [0, 1] (got {weight})")
+    if cap is not None and not 1.0 <= cap <= 15.0:
+        raise ValueError(f"--surprise-cap must be in [1, 15] (got {cap})")
+    return {"alpha": float(weight), "cap": SURPRISE_CAP if cap is None else float(cap)}
+
+
+def add_surprise_args(ap):
+    """--surprise-weight / --surprise-cap."""
+    ap.add_argument("--surprise-weight", type=float, default=None, metavar="A", help="batched path: policy surprise weighting -- every recorded "
+                    "ply gets a sampling weight: the share 1 - A of its game's weight spread evenly, the share A (in [0, 1], KataGo's "
+                    f"{SURPRISE_WEIGHT}) over the full-search plies by KL(search policy || prior). With --train-every the ring draws by it; "
+                    "without a ring the weights are written to sample_weights.npy; absent = off")
+    ap.add_argument("--surprise-cap", type=float, default=None, metavar="C", help=f"... the largest weight of a ply, in [1, 15] (default {SURPRISE_CAP:g})")
+
+
+def surprise_from_args(ap, a):
+    return _from_args(ap, a, "--surprise-weight", "policy surprise weighting is off", ("--surprise-cap",), make_surprise, a.surprise_weight,
+                      a.surprise_cap)

@@ -747,6 +747,18 @@ class ReplayBuffer:
         return out
 
 
+def record_weights(records: torch.Tensor) -> torch.Tensor:
+    """float32 [P]: the sampling weight of every compact ply record (uint8 [P, 880]) -- bytes 90..91 in 1/4096 where the header
+    carries ``REC_WEIGHT`` (policy surprise weighting, ``set_surprise``), 1.0 where it does not. A plain torch op on the
+    records' device."""
+    from ._lib import REC_FLAGS, REC_WEIGHT, REC_WEIGHT_OFF, REC_WEIGHT_ONE
+    if records.dim() != 2 or int(records.shape[1]) != REC_BYTES or records.dtype != torch.uint8:
+        raise ValueError("records must be uint8 [P, 880]")
+    wq = records[:, REC_WEIGHT_OFF].to(torch.int32) + records[:, REC_WEIGHT_OFF + 1].to(torch.int32) * 256
+    has = (records[:, REC_FLAGS] & REC_WEIGHT) != 0
+    return torch.where(has, wq.to(torch.float32) / float(REC_WEIGHT_ONE), torch.ones((), dtype=torch.float32, device=records.device))
+
+
 class RecordReplayBuffer:
     """Fixed-capacity ring of COMPACT PLY RECORDS resident in HBM (880 B per ply = 440 B per training row against the 29,768 B
     of :class:`ReplayBuffer`: 30 GB hold ~34 M plies = 68 M rows); a dense row is formed only when a minibatch draws it.
@@ -785,6 +797,7 @@ class RecordReplayBuffer:
         self.records = torch.zeros((self.cap, REC_BYTES), dtype=torch.uint8, device=d)
         self._window = torch.zeros((2,), dtype=torch.int64, device=d)      # {tail, head}, written by ccz_ring_retire only
         self.bad = torch.zeros((1,), dtype=torch.int32, device=d)          # records refused so far (cut or over-long games)
+        self.fallbacks = torch.zeros((1,), dtype=torch.int32, device=d)    # weighted rows whose 256 candidates were all rejected
         self.head = 0        # logical plies appended so far (the device's head once the queued appends have run)
         self.size = 0        # rows the window holds AT MOST (the device may have retired part of a game more)
         self.total = 0       # rows ever appended
@@ -870,14 +883,44 @@ class RecordReplayBuffer:
                                                      _ptr(self.bad if bad is None else bad), _ptr(tg), _ptr(vals)))
         return (states, pi, z) + ((tg,) if targets else ()) + ((vals,) if values else ())
 
-    def sample(self, batch: int, generator=None, targets: bool = False, values: bool = False):
-        """A uniform minibatch over the live rows, mirror images included, without a host sync: the draws are
+    def sample(self, batch: int, generator=None, targets: bool = False, values: bool = False, weighted: bool = False, cap: float = 8.0,
+               chosen: bool = False):
+        """A minibatch over the live rows, mirror images included, without a host sync. Uniform by default: the draws are
         ``torch.randint(0, 2**62)`` on the device and the kernel reduces them modulo the live row count, which only the device
-        knows. The modulo bias is below ``live / 2**62`` < 2**-28 for any ring that fits in HBM (live < 2**34 rows)."""
+        knows. The modulo bias is below ``live / 2**62`` < 2**-28 for any ring that fits in HBM (live < 2**34 rows).
+
+        ``weighted``: a row is drawn in proportion to its ply's sampling weight (:func:`record_weights`: bytes 90..91 of a
+        ``REC_WEIGHT`` record, 1 without the flag; a row and its mirror image share it) by ``ccz_sample_records_weighted``: the
+        one seed word is ``torch.randint`` on the device from ``generator`` and is never read by the host, every row's block
+        rejects candidates against ``cap`` (the largest weight the records may carry, in [1, 15]: ``set_surprise``'s) and a row
+        whose 256 candidates were all rejected takes its first one and counts in ``self.fallbacks``. ``chosen``: a last tensor,
+        int64 [batch] -- the draw every row took, so that ``sample_at(chosen)`` forms the same rows (``weighted`` only)."""
         if self.head == 0:
             raise ValueError("the replay ring is empty: nothing was ever appended")
-        draws = torch.randint(0, 2 ** 62, (int(batch),), device=self.records.device, dtype=torch.int64, generator=generator)
-        return self.sample_at(draws, targets=targets, values=values)
+        d = self.records.device
+        if not weighted:
+            if chosen:
+                raise ValueError("chosen: only a weighted draw is made on the device")
+            draws = torch.randint(0, 2 ** 62, (int(batch),), device=d, dtype=torch.int64, generator=generator)
+            return self.sample_at(draws, targets=targets, values=values)
+        from . import _lib
+        from .engine import _ptr
+        if not 1.0 <= float(cap) <= 15.0:
+            raise ValueError(f"cap {cap} must be in [1, 15]")
+        cap_q = int(float(cap) * _lib.REC_WEIGHT_ONE + 0.5)
+        n = int(batch)
+        seed = torch.randint(0, 2 ** 63 - 1, (1,), device=d, dtype=torch.int64, generator=generator)
+        states = torch.empty((n, 17, 7, 10, 9), dtype=torch.float16, device=d)
+        pi = torch.empty((n, NMOVES), dtype=torch.float32, device=d)
+        z = torch.empty((n,), dtype=torch.float32, device=d)
+        tg = torch.empty((n,), dtype=torch.uint8, device=d) if targets else None
+        vals = torch.empty((n,), dtype=torch.float32, device=d) if values else None
+        ch = torch.empty((n,), dtype=torch.int64, device=d) if chosen else None
+        with torch.cuda.device(d):
+            _lib.check(_lib.lib().ccz_sample_records_weighted(self._stream(), _ptr(self.records), self.cap, _ptr(self._window), _ptr(seed), cap_q,
+                                                              _ptr(ch), _ptr(self.fallbacks), n, self.flags, self._pot(), _ptr(states), _ptr(pi),
+                                                              _ptr(z), _ptr(self.bad), _ptr(tg), _ptr(vals)))
+        return (states, pi, z) + ((tg,) if targets else ()) + ((vals,) if values else ()) + ((ch,) if chosen else ())
 
     def window(self):
         """``(tail, head)`` in logical plies, as the device has them after everything queued so far (syncs)."""
@@ -898,7 +941,7 @@ class RecordReplayBuffer:
         rec = torch.cat([self.records[a:b] for a, b in self._segments(tail, head)]).cpu() if head > tail \
             else torch.zeros((0, REC_BYTES), dtype=torch.uint8)
         return {"records": rec, "tail": tail, "head_device": head, "head": int(self.head), "size": int(self.size), "total": int(self.total),
-                "bad": int(self.bad.item()), "capacity_plies": self.cap, "max_game_plies": self.max_game_plies, "flags": self.flags,
+                "bad": int(self.bad.item()), "fallbacks": int(self.fallbacks.item()), "capacity_plies": self.cap, "max_game_plies": self.max_game_plies, "flags": self.flags,
                 "plane_of_type": self.plane_of_type}
 
     def load_state_dict(self, state: dict):
@@ -919,6 +962,7 @@ class RecordReplayBuffer:
             at += b - a
         self._window.copy_(torch.tensor([tail, head], dtype=torch.int64))
         self.bad.fill_(int(state["bad"]))
+        self.fallbacks.fill_(int(state.get("fallbacks", 0)))
         self.head, self.size, self.total = int(state["head"]), int(state["size"]), int(state["total"])
 
 

@@ -154,8 +154,11 @@ class BatchedSelfPlay:
     def __init__(self, evaluator, n_boards: int, n_playout: int = 400, c_puct: float = C_PUCT, eps: float = EPS,
                  alpha: float = ALPHA, temp: float = 1.0, seed: int = 0, board_id_base: int = 0, device: int = 0,
                  sampling: str = "device", use_graph: bool = False, version_fn=None, playout_cap=None, resign=None,
-                 root_exploration=None, solver: bool = False, gumbel=None, search=None, early_stop=None, **engine_kw):
-        """``early_stop``: a dict of :meth:`SelfPlayEngine.set_early_stop`'s arguments (``single_reply``, ``gap_factor``,
+                 root_exploration=None, solver: bool = False, gumbel=None, search=None, early_stop=None, surprise=None, **engine_kw):
+        """``surprise``: True, a weight in [0, 1], or a dict of :meth:`SelfPlayEngine.set_surprise`'s arguments (``alpha``, ``cap``): policy
+        surprise weighting -- the records of harvested games carry a sampling weight (``REC_WEIGHT``) that ``RecordReplayBuffer.sample(weighted=True)``
+        draws by. Changes no search and no move; works with every other option and both sampling modes. None (default): off.
+        ``early_stop``: a dict of :meth:`SelfPlayEngine.set_early_stop`'s arguments (``single_reply``, ``gap_factor``,
         ``kld_interval``, ``min_gain``, ``min_sims``; see :func:`stopcfg.make_early_stop`): a board stops searching its move when the
         outcome can no longer change or its visit distribution has stopped moving, and selects nothing for the rest of the move's
         ``n_playout`` lockstep steps (no evaluator row with an evaluation cache). None (default): off. (``options.SearchOptions``: what
@@ -187,8 +190,8 @@ class BatchedSelfPlay:
         if sampling not in ("device", "numpy"):
             raise ValueError("sampling must be 'device' (Philox on the GPU) or 'numpy' (reference-exact host RNG)")
         self.options = o = SearchOptions(n_playout, sampling, resign=resign, root_exploration=root_exploration, gumbel=gumbel, solver=solver,
-                                         search=search, early_stop=early_stop)       # (ValueError: what excludes what)
-        self.resign, self.root_exploration, self.gumbel, self.solver, self.search_cfg, self.early_stop = o.keywords().values()
+                                         search=search, early_stop=early_stop, surprise=surprise)       # (ValueError: what excludes what)
+        self.resign, self.root_exploration, self.gumbel, self.solver, self.search_cfg, self.early_stop, self.surprise = o.keywords().values()
         self.playout_cap = None
         if playout_cap is not None:
             n_fast, p_full = playout_cap

@@ -10,7 +10,8 @@ without a GPU). The blob is written by ``ccz_snapshot_save`` (``include/cczero.h
 
 A section: FIXED_BYTES of per-board rows (FIXED_ROWS), then ``nodeA [n_nodes][16]``, ``nodeB [n_nodes][4]``, ``proof [n_nodes]``
 (with SNAP_PROOF), ``rec_sq [ply][96]``, ``rec_off [ply][4]``, ``rec_turn`` / ``rec_k`` / ``rec_target [ply]``, ``rec_value
-[ply][4]`` and ``rec_hasv [ply]`` (with SNAP_VALUES), ``rec_ids [pi_used][2]``, ``rec_pi [pi_used][4]``; every array is rounded up
+[ply][4]`` and ``rec_hasv [ply]`` (with SNAP_VALUES), ``rec_kl [ply][4]``, ``rec_hask [ply]`` and the board's 24-byte surprise counter
+row (with SNAP_SURPRISE: only while policy surprise weighting is on), ``rec_ids [pi_used][2]``, ``rec_pi [pi_used][4]``; every array is rounded up
 to 16 bytes with zeros (:func:`section_bytes`).
 """
 from __future__ import annotations
@@ -22,7 +23,7 @@ VERSION = 1
 HEADER_BYTES = 512
 FIXED_BYTES = 5088
 META_BYTES = 40
-SNAP_PROOF, SNAP_VALUES = 1, 2
+SNAP_PROOF, SNAP_VALUES, SNAP_SURPRISE = 1, 2, 4
 
 _RESIGN = np.dtype([("enabled", "<i4"), ("consecutive", "<i4"), ("min_ply", "<i4"), ("threshold", "<f4"), ("p_playon", "<f8")])
 _EXPLORE = np.dtype([("enabled", "<i4"), ("prune", "<i4"), ("eps", "<f8"), ("alpha", "<f8"), ("forced_k", "<f8")])
@@ -31,6 +32,8 @@ _SEARCH = np.dtype([("enabled", "<i4"), ("fpu_mode", "<i4"), ("fpu_root_mode", "
                     ("fpu_root_value", "<f8"), ("c_base", "<f8"), ("c_factor", "<f8")])
 _STOP = np.dtype([("enabled", "<i4"), ("single_reply", "<i4"), ("kld_interval", "<i4"), ("min_sims", "<i4"), ("n_sims", "<i4"), ("pad", "<i4"),
                   ("gap_factor", "<f8"), ("min_gain", "<f8")])
+_SURPRISE = np.dtype([("enabled", "<i4"), ("pad", "<i4"), ("alpha", "<f8"), ("cap", "<f8")])   # (zeros while the option never was on)
+SURPRISE_STATS_DTYPE = np.dtype([("target_plies", "<u8"), ("surprise_sum", "<f8"), ("weights_clipped", "<u8")])
 HEADER_DTYPE = np.dtype([
     ("magic", "<u8"), ("version", "<u4"), ("header_bytes", "<u4"), ("total_bytes", "<u8"), ("sections_start", "<u8"),
     ("B", "<i4"), ("cap", "<i4"), ("maxd", "<i4"), ("max_plies", "<i4"), ("pi_cap", "<i4"), ("reserve", "<i4"),
@@ -39,7 +42,7 @@ HEADER_DTYPE = np.dtype([
     ("sections", "<u4"), ("width", "<i4"), ("solver_enabled", "<i4"), ("budgets_on", "<i4"), ("err", "<i4"), ("half", "<i4"),
     ("fixed_bytes", "<u4"), ("meta_bytes", "<u4"),
     ("resign", _RESIGN), ("root_exploration", _EXPLORE), ("gumbel", _GUMBEL), ("search", _SEARCH), ("early_stop", _STOP),
-    ("pad", "u1", (HEADER_BYTES - 336,))])
+    ("surprise", _SURPRISE), ("pad", "u1", (HEADER_BYTES - 360,))])
 assert HEADER_DTYPE.itemsize == HEADER_BYTES
 META_DTYPE = np.dtype([("key", "<u8"), ("halfmove", "<i4"), ("chain_len", "<i4"), ("ply", "<i4"), ("move_counter", "<u4"), ("n_nodes", "<i4"),
                        ("turn", "u1"), ("over", "u1"), ("winner", "i1"), ("half", "u1"), ("pi_used", "<u4"), ("game_no", "<u4")])
@@ -73,6 +76,8 @@ def section_bytes(n_nodes, ply, pi_used, sections: int = SNAP_VALUES):
     s = s + p * c(96) + pad16(p * c(4)) + c(3) * pad16(p)
     if sections & SNAP_VALUES:
         s = s + pad16(p * c(4)) + pad16(p)
+    if sections & SNAP_SURPRISE:
+        s = s + pad16(p * c(4)) + pad16(p) + pad16(c(SURPRISE_STATS_DTYPE.itemsize))
     return s + pad16(u * c(2)) + pad16(u * c(4))
 
 
@@ -133,3 +138,20 @@ def fixed_row(blob, info: dict, board: int, name: str) -> np.ndarray:
     o, dt, n = FIXED_ROWS[name]
     p = int(info["sections_start"]) + int(info["offsets"][board]) + o
     return a[p:p + n * np.dtype(dt).itemsize].view(dt).copy()
+
+
+def surprise_rows(blob, info: dict, board: int):
+    """``(kl float32 [ply], has uint8 [ply], counters)`` of board ``board``'s section in a snapshot with SNAP_SURPRISE (ValueError without):
+    the surprise stored with the plies of its game and its ``SURPRISE_STATS_DTYPE`` counter row, as copies."""
+    sections = int(info["sections"])
+    if not sections & SNAP_SURPRISE:
+        raise ValueError("the snapshot has no surprise section (policy surprise weighting was off when it was saved)")
+    a = _as_bytes(blob)
+    n, ply = int(info["n_nodes"][board]), int(info["ply"][board])
+    before = section_bytes(n, ply, 0, sections & ~SNAP_SURPRISE)          # (pi_used = 0: the arrays behind the surprise section left out)
+    p = int(info["sections_start"]) + int(info["offsets"][board]) + int(before)
+    kl = a[p:p + 4 * ply].view("<f4").copy()
+    p += int(pad16(4 * ply))
+    has = a[p:p + ply].copy()
+    p += int(pad16(ply))
+    return kl, has, a[p:p + SURPRISE_STATS_DTYPE.itemsize].view(SURPRISE_STATS_DTYPE)[0].copy()

@@ -398,6 +398,38 @@ int ccz_get_resign_stats(ccz_engine *e, void *stream, ccz_resign_stats *out); /*
  * game); any pointer may be NULL. */
 int ccz_resign_status(ccz_engine *e, void *stream, uint8_t *state_host, uint8_t *run_host, int32_t *fire_ply_host, float *last_value_host);
 
+/* ---- policy surprise weighting (additive to ABI 9) -----------------------------------------------------------------------------------
+ * KataGo's rule for how often a recorded ply is trained on: a share 1 - alpha of a game's sampling weight is spread evenly over its
+ * plies, the share alpha goes to the policy-target plies in proportion to s = KL(search policy || network prior). Off after
+ * ccz_create: ccz_finish_move and ccz_harvest_records then read one word of the settings and do exactly what they do without the
+ * feature (record bytes 90..91 zero, no CCZ_REC_WEIGHT).
+ *   ccz_set_surprise: asynchronous on `stream`, takes effect with the next ccz_finish_move / ccz_harvest_records. alpha in [0, 1],
+ *     cap in [1, 15] (validated also with enabled = 0). Refused with scout slots. The call clears the has-bit of every stored ply: a
+ *     ply recorded before it carries no surprise.
+ * With the feature on, ccz_finish_move stores with every ply it records (a resigned ply is a ply like any other):
+ *   target byte 1: s = sum_i pi_i * (det_log(pi_i) - det_log(max((double)P_i, 2^-100))) over the root's children with pi_i > 0, in child
+ *     order in float64, a negative sum clamped to 0; (float)s and the has-bit 1. pi is the float64 distribution that is recorded
+ *     (rounded to float32 only in the record): the visit softmax at the move's temperature, the pruned-count pi under root exploration,
+ *     pi' under the Gumbel root. P_i is the child's stored prior (root noise is never stored).
+ *   target byte 0 (a fast ply of playout-cap randomisation): 0 and the has-bit 0.
+ * ccz_harvest_records, with the feature on, gives every ply of a harvested game CCZ_REC_WEIGHT and in record bytes 90..91 the uint16
+ *   wq = floor(w * 4096 + 0.5), w = min(w', cap), where with F = the game's plies with the has-bit, n = |F| and S = the sum of their
+ *   float32 s as doubles in ply order: w' = (1 - alpha) + alpha * n * s_t / S for t in F if S > 0, else 1. A ply with w' > cap counts
+ *   in weights_clipped. The dense-row call ccz_harvest writes what it always wrote. */
+#define CCZ_REC_WEIGHT 16     /* record header flags: bytes 90..91 of this record hold the ply's sampling weight, uint16 in 1/4096 */
+#define CCZ_REC_WEIGHT_OFF 90
+#define CCZ_REC_WEIGHT_ONE 4096
+typedef struct ccz_surprise_stats { /* sums over boards, taken in board order */
+    int64_t target_plies;    /* policy-target plies whose surprise was measured                   */
+    double surprise_sum;     /* the sum of their stored float32 surprise                          */
+    int64_t weights_clipped; /* harvested plies whose weight was cut to the cap                   */
+} ccz_surprise_stats;
+int ccz_set_surprise(ccz_engine *e, void *stream, int32_t enabled, double alpha, double cap);
+int ccz_get_surprise_stats(ccz_engine *e, void *stream, ccz_surprise_stats *out); /* syncs */
+/* the surprise stored with the plies of the boards' current games (syncs): kl_host float [B * max_plies], has_host uint8 [B * max_plies],
+ * either may be NULL; entries at or past a board's ply count are stale. */
+int ccz_ply_surprise(ccz_engine *e, void *stream, float *kl_host, uint8_t *has_host);
+
 /* ---- root exploration in the search: root noise, forced playouts, policy target pruning (additive to ABI 8) ---------------------------
  * AlphaZero puts the Dirichlet noise into the root's PRIORS; KataGo adds forced playouts and policy target pruning, so that a move the
  * noise favours gets real visits and the visits spent on exploration are taken out of the policy target again. Off after ccz_create:
@@ -774,8 +806,8 @@ int ccz_harvest(ccz_engine *e, void *stream, void *states_f16_dev, float *pi_dev
 
 /* ---- compact game records: the wire format of the multi-GPU exchange ------------------------------ */
 /* One fixed-size record per PLY of a finished game, plies of a game contiguous and in order:
- *   bytes   0..89   position before the move (piece codes, square = file + 9*rank), 90..91 zero, 92..95 the root value
- *                   (float32) on a CCZ_REC_VALUE ply, else zero
+ *   bytes   0..89   position before the move (piece codes, square = file + 9*rank), 90..91 the sampling weight (uint16, 1/4096)
+ *                   on a CCZ_REC_WEIGHT ply, else zero, 92..95 the root value (float32) on a CCZ_REC_VALUE ply, else zero
  *   bytes  96..111  header: uint16 t (ply index), uint16 T (plies of the game), int8 winner (1 RED, 0 BLACK, -1 draw),
  *                   uint8 turn (side to move), uint8 k (entries of pi), uint8 flags (CCZ_REC_*), uint32 board_id (global),
  *                   uint32 game_no
@@ -833,6 +865,21 @@ int ccz_sample_records(void *stream, const void *ring_dev, int64_t cap_plies, co
                        const int64_t *draws_dev, int64_t batch, uint32_t flags, const uint8_t *plane_of_type_host,
                        void *states_f16_dev, float *pi_dev, float *z_dev, int32_t *bad_records_dev, uint8_t *target_dev,
                        float *value_dev);
+/* ccz_sample_records_weighted: ccz_sample_records with the draws made on the device, by weight. seed_dev: one uint64 on the device
+ * (8-byte aligned); cap_q: the cap on a weight in 1/4096, 4096 .. 61440; chosen_dev int64 [batch] (may be NULL) receives the draw u
+ * every row took; *fallback_dev (int32, may be NULL) counts the rows that fell back. Row j is chosen by rejection: candidate (r, l),
+ * r = 0..3, l = 0..63, takes the Philox4x32-10 words o of key *seed_dev and counter {hi = j, lo = 64 r + l}; u = (o0:o1) >> 2 (62
+ * bits), a = ((o2:o3) >> 11) * 2^-53. Its ply is that of draw u in ccz_sample_records; wq = the uint16 at record byte 90 with
+ * CCZ_REC_WEIGHT, else 4096. It is accepted iff the ply is part of a whole game inside the window and a * cap_q < wq; the first
+ * accepted candidate in (r, l) order is the row's. None of the 256 accepted: the row takes candidate (0, 0) and counts in
+ * *fallback_dev (weights at most cap_q / 4096 of mean m: a chance of (1 - m * 4096 / cap_q)^256 per row). Output row j, target and
+ * value are byte for byte what ccz_sample_records writes for draw u, a bad row (candidate (0, 0) of a fallback that is no whole game,
+ * or an empty window) included; candidates that lose count nowhere. The pass (mirror image or not) comes from u; both passes share
+ * the ply's weight. Asynchronous, no host sync. */
+int ccz_sample_records_weighted(void *stream, const void *ring_dev, int64_t cap_plies, const int64_t *window_dev,
+                                const uint64_t *seed_dev, int32_t cap_q, int64_t *chosen_dev, int32_t *fallback_dev, int64_t batch,
+                                uint32_t flags, const uint8_t *plane_of_type_host, void *states_f16_dev, float *pi_dev, float *z_dev,
+                                int32_t *bad_records_dev, uint8_t *target_dev, float *value_dev);
 
 int ccz_get_stats(ccz_engine *e, void *stream, ccz_stats *out); /* syncs */
 
@@ -1040,9 +1087,12 @@ int ccz_conv3x3_c256_heads_g16c_f16(void *stream, const void *x_dev, const void 
  *     an engine's own blobs have CCZ_SNAP_VALUES always and CCZ_SNAP_PROOF once ccz_set_solver(1) has allocated the bytes. With
  *     pad16(n) = n rounded up to 16, a section is CCZ_SNAP_FIXED_BYTES + 16 n_nodes + pad16(4 n_nodes) [+ pad16(n_nodes)] + 96 ply +
  *     pad16(4 ply) + 3 pad16(ply) [+ pad16(4 ply) + pad16(ply)] + pad16(2 pi_used) + pad16(4 pi_used) bytes. Any B >= 1; stateless,
- *     asynchronous. */
+ *     asynchronous. CCZ_SNAP_SURPRISE (the surprise and has-bit per ply and the board's counter row; in an engine's own blobs only
+ *     while ccz_set_surprise is on, whose settings the header then holds in bytes 336..359, zero otherwise) adds pad16(4 ply) +
+ *     pad16(ply) + 32 bytes behind the value arrays. */
 #define CCZ_SNAP_PROOF 1u
 #define CCZ_SNAP_VALUES 2u
+#define CCZ_SNAP_SURPRISE 4u
 #define CCZ_SNAP_HEADER_BYTES 512
 #define CCZ_SNAP_FIXED_BYTES 5088
 int ccz_snapshot_size(ccz_engine *e, void *stream, uint64_t *bytes_host);
