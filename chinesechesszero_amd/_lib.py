@@ -148,6 +148,8 @@ PROTOTYPES = {
     "ccz_scouted_run": (C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
     "ccz_gather_priors_planned": (C.c_int, [_P, _P, _P, C.c_int32, _P]),
     "ccz_eval_cache_clear": (C.c_int, [_P, _P]),
+    "ccz_set_leaf_history": (C.c_int, [_P, _P, C.c_int32]),
+    "ccz_get_leaf_history": (C.c_int, [_P, C.POINTER(C.c_int32)]),
     "ccz_set_routing": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint64]),
     "ccz_eval_plan_routed": (C.c_int, [_P, _P, _P, _P]),
     "ccz_gather_priors_routed": (C.c_int, [_P, _P, _P, _P, C.c_int32, _P, _P]),
@@ -208,6 +210,11 @@ PROTOTYPES = {
     "ccz_bias_act_f16": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int32]),
     "ccz_conv3x3_c256_f16": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, C.c_int32]),
     "ccz_conv3x3_stem_f16": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int32]),
+    "ccz_pack_planes128_f16": (C.c_int, [_P, _P, _P, C.c_int32]),
+    "ccz_pack_planes128_g16_f16": (C.c_int, [_P, _P, _P, C.c_int32, _P, _P]),
+    "ccz_pack_planes128_rows_f16": (C.c_int, [_P, _P, _P, C.c_int32, _P, _P]),
+    "ccz_conv3x3_stem128_f16": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int32]),
+    "ccz_conv3x3_stem128_f16_live": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int32, _P, C.c_int32, C.c_int32]),
     "ccz_pack_live_planes_f16": (C.c_int, [_P, _P, _P, C.c_int32]),
     "ccz_pack_live_planes_rows_f16": (C.c_int, [_P, _P, _P, C.c_int32, _P, _P]),
     "ccz_pack_live_planes_g16_f16": (C.c_int, [_P, _P, _P, C.c_int32, _P, _P]),

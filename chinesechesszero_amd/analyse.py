@@ -24,7 +24,7 @@ import numpy as np
 from ._lib import CczError
 from .boundary import describe
 from .game import Board
-from .options import SearchOptions
+from .options import SearchOptions, add_leaf_history_args, leaf_history_from_args
 from .searchcfg import add_search_args, search_from_args
 from .stopcfg import add_early_stop_args, early_stop_from_args
 
@@ -87,7 +87,7 @@ class BatchedAnalysis:
     across chunks and cleared only when the evaluator's weights version changes."""
 
     def __init__(self, evaluator, n_boards: int, n_playout: int = 400, multipv: int = 1, max_len: int = 32, solver: bool = False, search=None,
-                 width: int = 1, early_stop=None, **engine_kw):
+                 width: int = 1, early_stop=None, leaf_history=None, **engine_kw):
         """``width`` > 1: every position gathers up to ``width`` leaves of its tree per step, kept apart by virtual loss
         (``wide.WideSearch``: an engine of ``n_boards * width`` slots) -- for a handful of positions, where the sequential search
         runs at the evaluator's latency; another tree than the sequential one; excludes ``solver`` and ``search``.
@@ -100,7 +100,7 @@ class BatchedAnalysis:
             raise TypeError("BatchedAnalysis: the evaluator must be callable or have evaluate_leaves_logits")
         if not 1 <= int(multipv) <= 128 or int(max_len) < 1 or int(n_playout) < 1:
             raise ValueError("BatchedAnalysis: multipv must be 1..128, max_len and n_playout >= 1")
-        SearchOptions(n_playout, width=width, solver=solver, search=search, early_stop=early_stop)   # (ValueError: width > 1 excludes them)
+        SearchOptions(n_playout, width=width, solver=solver, search=search, early_stop=early_stop, leaf_history=leaf_history)   # (ValueError: width > 1 excludes them)
         if "eval_cache_log2" not in engine_kw:
             engine_kw["eval_cache_log2"] = 22 if (int(n_boards) >= 192 and desc.accepts_plan) else 0
         engine_kw.setdefault("mirror", False)
@@ -120,7 +120,7 @@ class BatchedAnalysis:
             self.engine = self.wide.engine
             self.solver = False
             return
-        self.sp = BatchedSelfPlay(ev, int(n_boards), n_playout=int(n_playout), eps=0.0, search=search, early_stop=early_stop, **engine_kw)   # no GPU: CczError
+        self.sp = BatchedSelfPlay(ev, int(n_boards), n_playout=int(n_playout), eps=0.0, search=search, early_stop=early_stop, leaf_history=leaf_history, **engine_kw)   # no GPU: CczError
         self.engine = self.sp.engine
         opts = SearchOptions(solver=solver)     # (search and early stop: the self-play front end's own, above)
         self.solver = opts.solver               # the MCTS-solver: records gain "mate", bestmove follows the proof (make_record)
@@ -234,7 +234,9 @@ def main(argv=None) -> int:
     ap.add_argument("--solver", action="store_true", help="MCTS-solver: prove decided positions in the tree; every record gains \"mate\": N or null")
     add_search_args(ap)
     add_early_stop_args(ap)
+    add_leaf_history_args(ap)
     args = ap.parse_args(argv)
+    leaf_history = leaf_history_from_args(ap, args)
     search = search_from_args(ap, args)
     early_stop = early_stop_from_args(ap, args)
     with open(args.file, encoding="utf-8") as f:
@@ -250,9 +252,11 @@ def main(argv=None) -> int:
     from .net import PolicyValueNet
     try:
         pvn = PolicyValueNet(model=args.weights, device="cuda:0")
+        if leaf_history is not None:
+            pvn.set_leaf_history(True)
         an = BatchedAnalysis(pvn, max(1, min(args.boards, len(parsed) or 1)), n_playout=args.playout, multipv=args.multipv,
                              max_len=args.max_len, solver=args.solver, search=search, width=args.width,
-                             early_stop=early_stop)
+                             early_stop=early_stop, leaf_history=leaf_history)
         records = an.analyse([b for _, b in parsed])
     except CczError as e:
         print(f"analyse: {e}", file=sys.stderr)

@@ -23,7 +23,7 @@ import numpy as np
 
 from .boundary import WeightsWatch, describe
 from .parameters import C_PUCT
-from .options import SearchOptions, add_resign_args, proven_moves, resign_from_args, search_move
+from .options import SearchOptions, add_leaf_history_args, add_resign_args, leaf_history_from_args, proven_moves, resign_from_args, search_move
 from .searchcfg import add_search_args, search_from_args
 from .stopcfg import StopPoll, add_early_stop_args, early_stop_from_args
 
@@ -180,7 +180,9 @@ class Arena:
 
     def __init__(self, net_a, net_b, n_pairs: int, n_playout: int = 400, opening_plies: int = 6, seed: int = 0,
                  max_plies: int = 0, c_puct: float = C_PUCT, eval_cache_log2: int = 22, device: int = 0,
-                 cache_verify: bool = False, n_playout_b: int | None = None, resign=None, solver: bool = False, search=None, early_stop=None):
+                 cache_verify: bool = False, n_playout_b: int | None = None, resign=None, solver: bool = False, search=None, early_stop=None,
+                 leaf_history=None):
+        from .boundary import need_history
         from .engine import SelfPlayEngine
         self.nets = (net_a, net_b)
         described = (_as_evaluator(net_a, "A"), _as_evaluator(net_b, "B"))
@@ -199,8 +201,8 @@ class Arena:
         if self.n_playout < 1 or (self.n_playout_b is not None and self.n_playout_b < 1):
             raise ValueError("Arena: n_playout and n_playout_b must be >= 1")
         self.n_steps = self.n_playout if self.n_playout_b is None else max(self.n_playout, self.n_playout_b)   # lockstep steps per move
-        self.options = o = SearchOptions(self.n_steps, resign=resign, solver=solver, search=search, early_stop=early_stop)
-        self.resign, self.solver, self.search_cfg, self.early_stop = o.keywords().values()
+        self.options = o = SearchOptions(self.n_steps, resign=resign, solver=solver, search=search, early_stop=early_stop, leaf_history=leaf_history)
+        self.resign, self.solver, self.search_cfg, self.early_stop, self.leaf_history = o.keywords().values()
         if self.resign is not None:          # (the dict ``o.apply`` hands to the engine)
             if self.resign.get("p_playon", 0.0) != 0.0:
                 raise ValueError("Arena: a match plays no game on after the resignation rule fired (p_playon is fixed at 0)")
@@ -212,6 +214,8 @@ class Arena:
         self.max_plies = e.max_plies
         self.proven_moves = 0                # moves played from a proof
         o.apply(e)
+        for name, net in zip("AB", self.nets):   # leaf history: both networks must read the 119 planes the engine then writes
+            need_history(e, net, f"Arena: evaluator {name}: ")
         self._poll = StopPoll(e, self.early_stop)
         self.opening_of, self.a_colour, self.red_net = pair_layout(self.P)
         self.openings = make_openings(self.P, int(opening_plies), seed=seed, device=device)
@@ -366,15 +370,20 @@ def main(argv=None) -> int:
     ap.add_argument("--solver", action="store_true", help="MCTS-solver on both sides: decided positions are proven in the tree and the proven move is played")
     add_search_args(ap)
     add_early_stop_args(ap)
+    add_leaf_history_args(ap)
     a = ap.parse_args(argv)
     search = search_from_args(ap, a)
     early_stop = early_stop_from_args(ap, a)
     resign = resign_from_args(ap, a)
     na = _load(a.a, a.channels, a.blocks, a.device)
     nb = _load(a.b, a.channels, a.blocks, a.device)
+    leaf_history = leaf_history_from_args(ap, a)
+    if leaf_history is not None:
+        na.set_leaf_history(True)
+        nb.set_leaf_history(True)
     arena = Arena(na, nb, a.pairs, n_playout=a.playout, opening_plies=a.opening_plies, seed=a.seed, max_plies=a.max_plies,
                   eval_cache_log2=a.eval_cache_log2, device=a.device, n_playout_b=a.playout_b, resign=resign, solver=a.solver, search=search,
-                  early_stop=early_stop)
+                  early_stop=early_stop, leaf_history=leaf_history)
     r = arena.play()
     r.update({"a": a.a, "b": a.b, "opening_plies": a.opening_plies, "seed": a.seed, "net": f"{a.blocks}x{a.channels}",
               "promote": promote(r, a.threshold), "threshold": a.threshold})

@@ -49,6 +49,26 @@ def need_version(ev: Evaluator, who: str = "", planned: bool = False, consequenc
     log(f"{who}the evaluator exposes no weights_version and no version_fn was given: {consequence}", "WARNING")
 
 
+def reads_history(evaluator) -> bool:
+    """Whether the evaluator reads all 17 plane groups of a leaf row: a true ``leaf_history`` attribute (or a callable of that name
+    returning true) on the callable, on the object it is a bound method of, or on the object passed in. Nothing says so: it does not
+    -- ``InferenceNet`` packs the 21 live channels of groups 7, 15 and 16 and would drop the other 98 planes without a word."""
+    fn = getattr(evaluator, "evaluate_leaves_logits", evaluator)
+    for o in (fn, getattr(fn, "__self__", None), evaluator):
+        v = getattr(o, "leaf_history", None)
+        if v is not None:
+            return bool(v() if callable(v) else v)
+    return False
+
+
+def need_history(engine, evaluator, who: str = ""):
+    """An engine that writes leaf history planes (``SelfPlayEngine.set_leaf_history``) with an evaluator that does not read them is
+    refused: the search would run, on inputs the net never saw and with cache keys that tell apart rows the evaluator cannot."""
+    if getattr(engine, "leaf_history", False) and not reads_history(evaluator):
+        raise ValueError(f"{who}the engine writes leaf history planes (set_leaf_history) but the evaluator does not read them: it packs "
+                         "plane groups 7, 15 and 16 only. Use an evaluator that declares `leaf_history = True`, or turn the option off")
+
+
 class WeightsWatch:
     """The last weights version seen. What follows a change (clear the cache, drop graphs, re-capture, re-salt) is the caller's.
     It holds the value only, never the evaluator or its owner: a front end and its engine die with their last reference."""

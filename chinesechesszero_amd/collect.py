@@ -44,7 +44,7 @@ from .mcts import MCTS_AI
 from .net import PolicyValueNet
 from .parameters import BATCH_SIZE, C_PUCT, DATA_DIR, MODEL_DIR, PLAYOUT
 from .options import (SearchOptions, add_gumbel_args, add_resign_args, add_root_exploration_args, format_exploration, format_gumbel,  # noqa: F401
-                      add_surprise_args, format_search, gumbel_from_args, resign_from_args, root_exploration_from_args, surprise_from_args)
+                      add_leaf_history_args, add_surprise_args, format_search, leaf_history_from_args, gumbel_from_args, resign_from_args, root_exploration_from_args, surprise_from_args)
 from .checkpoint import add_checkpoint_args, checkpoint_from_args
 from .searchcfg import add_search_args, search_from_args
 from .stopcfg import add_early_stop_args, early_stop_from_args
@@ -575,13 +575,14 @@ class CollectPipeline:
                  finalize_every: int = 0, on_playout=None, max_plies: int = 0, eval_cache_log2: int | None = None, gatherer=None,
                  dense_shards: bool = False, replay_plies: int = 0, train_every: int = 0, train_batch: int = BATCH_SIZE,
                  playout_cap_fast: int = 0, playout_cap_prob: float | None = None, resign=None, value_q_weight: float = 0.0,
-                 root_exploration=None, solver: bool = False, gumbel=None, search=None, early_stop=None, surprise=None,
+                 root_exploration=None, solver: bool = False, gumbel=None, search=None, early_stop=None, surprise=None, leaf_history=None,
                  checkpoint_dir: str | None = None, checkpoint_every: int = 0, resume: bool = False):
         # the engine options of the batched path, as BatchedSelfPlay takes them (options.OPTIONS: each None / False = off); only the search
         # parameters also run in the one-game loop (which then runs without scout slots)
         self.options = o = SearchOptions(n_playout, batched=n_boards > 1, resign=resign, root_exploration=root_exploration, gumbel=gumbel,
-                                         solver=solver, search=search, early_stop=early_stop, surprise=surprise)
-        self.resign, self.root_exploration, self.gumbel, self.solver, self.search, self.early_stop, self.surprise = o.keywords().values()
+                                         solver=solver, search=search, early_stop=early_stop, surprise=surprise, leaf_history=leaf_history)
+        (self.resign, self.root_exploration, self.gumbel, self.solver, self.search, self.early_stop, self.surprise,
+         self.leaf_history) = o.keywords().values()   # (leaf_history: search AND network read the rows' eight-position input; part of the signature)
         # policy surprise weighting: the records carry a sampling weight; with a ring the trainer's minibatch is drawn by it, without
         # one the sink writes the weights next to the rows (sample_weights.npy)
         if self.surprise is not None:
@@ -816,6 +817,8 @@ class CollectPipeline:
             rank = torch.distributed.get_rank() if torch.distributed.is_initialized() else 0
             # compact evaluator boundary (logits in, the engine gathers the legal priors) and, on the fused evaluator path (>= 192
             # boards), the evaluation cache: positions evaluated before skip the network (same results)
+            if self.leaf_history is not None:
+                self.policy_value_net.set_leaf_history(True)   # the evaluator's half: its stem reads all 119 planes
             self.selfplay = BatchedSelfPlay(self.policy_value_net.evaluate_leaves_logits, self.n_boards, n_playout=self.n_playout,
                                             eval_cache_log2=(24 if self.n_boards >= 192 else 0) if self.eval_cache_log2 is None else int(self.eval_cache_log2),
                                             c_puct=self.c_puct, temp=self.temp, seed=self.seed, board_id_base=rank * self.n_boards,
@@ -1090,6 +1093,7 @@ def build_parser():
     add_search_args(parser)
     add_early_stop_args(parser)
     add_surprise_args(parser)
+    add_leaf_history_args(parser)
     parser.add_argument("--value-q-weight", type=float, default=0.0, help="with --train-every: weight of the recorded root value q in the value "
                         "target, (1 - w) z + w q on rows that carry one (0 = z alone)")
     add_checkpoint_args(parser)
@@ -1108,8 +1112,9 @@ def parse_args(argv=None):
     args.search = search_from_args(parser, args)
     args.early_stop = early_stop_from_args(parser, args)
     args.surprise = surprise_from_args(parser, args)
+    args.leaf_history_cfg = leaf_history_from_args(parser, args)
     args.options = dict(resign=args.resign, root_exploration=args.root_exploration, gumbel=args.gumbel_cfg, solver=args.solver, search=args.search,
-                        early_stop=args.early_stop, surprise=args.surprise)
+                        early_stop=args.early_stop, surprise=args.surprise, leaf_history=args.leaf_history_cfg)
     try:
         SearchOptions(args.playout, batched=args.boards > 1, **args.options)
     except ValueError as ex:

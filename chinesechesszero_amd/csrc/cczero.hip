@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "cczero_kernels.h"
+#include "cczero_history.h"
 #include "cczero_netops.h"
 #include "cczero_conv.h"
 #include "cczero_conv_small.h"
@@ -93,6 +94,7 @@ struct ccz_engine {
     SurpriseBlock *sp_block = nullptr; // device: the surprise settings and array pointers, behind the resignation settings (BoundaryCfg)
     SurpriseBlock sp_host = {};        // the host's copy of the pointers (cfg stays zero here: the device's is the truth)
     bool surprise_on = false;      // ccz_set_surprise(enabled): the host's shadow of SurpriseCfg.enabled (scouts are refused with it; a snapshot gets its section)
+    bool history_on = false;       // ccz_set_leaf_history(enabled): every select phase is followed by k_leaf_history (scouts and a width above 1 are refused with it)
     // MCTS-solver (ccz_set_solver): the proof bytes [B][2][cap] (allocated by the first call that turns it on), the host's shadow of
     // SolverCfg.enabled, staging of ccz_root_proof (state [B], dist [B], child state [B][128], child dist [B][128])
     uint8_t *proof = nullptr, *st_proof = nullptr;
@@ -523,13 +525,45 @@ int ccz_zero_leaf_input(ccz_engine *e, void *stream, void *leaf_input_f16_dev)
     return 0;
 }
 
+// ccz_set_leaf_history on: the rows and keys of the select phase just launched are rewritten with the boards' histories (off: no launch)
+static int leaf_history(ccz_engine *e, hipStream_t s, void *leaf_input_f16_dev)
+{
+    if (!e->history_on) return 0;
+    if (!leaf_input_f16_dev) return fail(-1, "leaf history is on (ccz_set_leaf_history): the select phase needs a leaf input tensor");
+    hipLaunchKernelGGL(k_leaf_history, dim3(ACTIVE(e)), dim3(64), 0, s, e->d, (uint16_t *)leaf_input_f16_dev);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int ccz_set_leaf_history(ccz_engine *e, void *stream, int32_t enabled)
+{
+    NEED(e);
+    (void)stream; // the setting lives on the host: it decides which launches the next select phase is made of
+    if (enabled) {
+        if (SCOUTS(e)) return fail(-1, "ccz_set_leaf_history: not with scout slots (ccz_set_scouts): a scout's leaf has no path of its own to replay");
+        if (WIDE(e)) return fail(-1, "ccz_set_leaf_history: not while the width is %d (ccz_set_width)", e->width);
+        if (e->d.flags & CCZ_FLAG_REFERENCE_QUIRKS)
+            return fail(-1, "ccz_set_leaf_history: not on a CCZ_FLAG_REFERENCE_QUIRKS engine: its training rows alias the final history, which no search sees");
+    }
+    e->history_on = enabled != 0;
+    return 0;
+}
+
+int ccz_get_leaf_history(ccz_engine *e, int32_t *enabled_host)
+{
+    NEED(e);
+    if (!enabled_host) return fail(-1, "ccz_get_leaf_history: null output");
+    *enabled_host = e->history_on ? 1 : 0;
+    return 0;
+}
+
 int ccz_select_leaves(ccz_engine *e, void *stream, void *leaf_input_f16_dev)
 {
     NEED(e);
     NOT_WIDE(e);
     hipLaunchKernelGGL(k_select, dim3(ACTIVE(e)), dim3(64), 0, (hipStream_t)stream, e->d, (uint16_t *)leaf_input_f16_dev);
     HIP_TRY(hipGetLastError());
-    return 0;
+    return leaf_history(e, (hipStream_t)stream, leaf_input_f16_dev);
 }
 
 int ccz_expand_backup(ccz_engine *e, void *stream, const float *prob_dev, const float *value_dev)
@@ -550,7 +584,7 @@ int ccz_step(ccz_engine *e, void *stream, const float *prob_dev, const float *va
     hipLaunchKernelGGL(k_step<false>, dim3(ACTIVE(e)), dim3(64), 0, (hipStream_t)stream, e->d, prob_dev, value_dev,
                        (uint16_t *)leaf_input_f16_dev);
     HIP_TRY(hipGetLastError());
-    return 0;
+    return leaf_history(e, (hipStream_t)stream, leaf_input_f16_dev);
 }
 
 int ccz_gather_priors(ccz_engine *e, void *stream, const void *logits_dev, int32_t logits_f16)
@@ -588,6 +622,7 @@ int ccz_set_scouts(ccz_engine *e, int32_t n_scouts)
     if (n_scouts && e->budgets_on) return fail(-1, "ccz_set_scouts: not while simulation budgets are on (ccz_set_budgets(NULL) turns them off)");
     if (n_scouts && e->explore_on) return fail(-1, "ccz_set_scouts: not while root exploration is on (ccz_set_root_exploration)");
     if (n_scouts && e->gumbel_on) return fail(-1, "ccz_set_scouts: not while the Gumbel root search is on (ccz_set_gumbel)");
+    if (n_scouts && e->history_on) return fail(-1, "ccz_set_scouts: not while leaf history is on (ccz_set_leaf_history)");
     if (n_scouts && e->surprise_on) return fail(-1, "ccz_set_scouts: not while policy surprise weighting is on (ccz_set_surprise)");
     if (n_scouts && e->stop_on) return fail(-1, "ccz_set_scouts: not while the early stop is on (ccz_set_early_stop)");
     if (n_scouts && e->search_on) return fail(-1, "ccz_set_scouts: not while the search parameters are on (ccz_set_search): scouts rest on children being first visited in legal-move order");
@@ -1234,7 +1269,7 @@ int ccz_step_compact(ccz_engine *e, void *stream, const float *value_dev, void *
     hipLaunchKernelGGL(k_step<true>, dim3(ACTIVE(e)), dim3(64), 0, (hipStream_t)stream, e->d, (const float *)e->d.prior128, value_dev,
                        (uint16_t *)leaf_input_f16_dev);
     HIP_TRY(hipGetLastError());
-    return 0;
+    return leaf_history(e, (hipStream_t)stream, leaf_input_f16_dev);
 }
 
 int ccz_expand_backup_compact(ccz_engine *e, void *stream, const float *value_dev)
@@ -1262,6 +1297,7 @@ int ccz_set_width(ccz_engine *e, void *stream, int32_t width)
         if (e->search_on) return fail(-1, "ccz_set_width: not while the search parameters are on (ccz_set_search)");
         if (e->stop_on) return fail(-1, "ccz_set_width: not while the early stop is on (ccz_set_early_stop)");
         if (e->routed) return fail(-1, "ccz_set_width: not while routing is on (ccz_set_routing)");
+        if (e->history_on) return fail(-1, "ccz_set_width: not while leaf history is on (ccz_set_leaf_history)");
     }
     hipStream_t s = (hipStream_t)stream;
     if (width == 1) {
@@ -2130,7 +2166,7 @@ static int conv3x3_launch(const char *who, void *stream, const void *x_dev, cons
     // Small batches (one game at a time; up to kSmallMaxPixels): the 16-channel x 64-pixel-block kernel spreads them over the chip
     // instead of filling a few 256-pixel tiles. Same operations in the same order: bit-identical results (cczero_conv_small.h).
     // flags bit 4 forces it, bit 5 forces the tile kernel (A/B runs, tests).
-    if (!live_rows_dev && !(relu & 32) && ((relu & 16) || n_pixels <= kSmallMaxPixels)) {
+    if (cin != 128 && !live_rows_dev && !(relu & 32) && ((relu & 16) || n_pixels <= kSmallMaxPixels)) { // (128, the history stem: the tile kernel at any size)
         const dim3 grid((unsigned)((n_pixels + kSmPix - 1) / kSmPix), 16);
         const int rl = relu & 1;
 #define CCZ_SMALL(RES_, CIN_)                                                                                                  \
@@ -2284,7 +2320,7 @@ int ccz_pack_live_planes_rows_f16(void *stream, const void *leaf_dev, void *x64_
 
 int ccz_pack_conv_weights_g16_f16(void *stream, const void *w_dev, void *wp_dev, int32_t cin)
 {
-    if (!w_dev || !wp_dev || w_dev == wp_dev || (cin != 64 && cin != 256)) return fail(-1, "ccz_pack_conv_weights_g16_f16: bad arguments (cin must be 64 or 256, not in place)");
+    if (!w_dev || !wp_dev || w_dev == wp_dev || (cin != 64 && cin != 128 && cin != 256)) return fail(-1, "ccz_pack_conv_weights_g16_f16: bad arguments (cin must be 64, 128 or 256, not in place)");
     if ((((uintptr_t)w_dev) | ((uintptr_t)wp_dev)) & 15) return fail(-1, "ccz_pack_conv_weights_g16_f16: pointers must be 16-byte aligned");
     const int n = 256 * 9 * (cin >> 3);
     hipLaunchKernelGGL(k_pack_conv_weights_g16, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const cv_half8 *)w_dev, (cv_half8 *)wp_dev, (int)cin);
@@ -2301,6 +2337,48 @@ int ccz_pack_live_planes_g16_f16(void *stream, const void *leaf_dev, void *x64_d
                        (const int *)rows_dev, (const int *)n_rows_dev, rows_dev ? 3 : 1); // planned form: as ccz_pack_live_planes_rows_f16
     HIP_TRY(hipGetLastError());
     return 0;
+}
+
+// ---- the 128-channel stem of the leaf history planes (cczero.h "leaf history planes"): the general tile forms at cin = 128
+static int pack_planes128(const char *who, void *stream, const void *leaf_dev, void *x128_dev, int32_t n_boards, const int32_t *rows_dev, const int32_t *n_rows_dev, int flags)
+{
+    if (!leaf_dev || !x128_dev || n_boards < 0 || (!rows_dev) != (!n_rows_dev)) return fail(-1, "%s: bad arguments", who);
+    if ((uintptr_t)x128_dev & 15) return fail(-1, "%s: output must be 16-byte aligned", who);
+    if (n_boards == 0) return 0;
+    hipLaunchKernelGGL(k_pack_planes128, dim3((unsigned)n_boards), dim3(kPackThreads), 0, (hipStream_t)stream, (const _Float16 *)leaf_dev, (half8_t *)x128_dev, (int)n_boards,
+                       (const int *)rows_dev, (const int *)n_rows_dev, flags);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int ccz_pack_planes128_f16(void *stream, const void *leaf_dev, void *x128_dev, int32_t n_boards)
+{
+    return pack_planes128("ccz_pack_planes128_f16", stream, leaf_dev, x128_dev, n_boards, nullptr, nullptr, 0);
+}
+
+int ccz_pack_planes128_g16_f16(void *stream, const void *leaf_dev, void *x128_dev, int32_t n_boards, const int32_t *rows_dev, const int32_t *n_rows_dev)
+{
+    return pack_planes128("ccz_pack_planes128_g16_f16", stream, leaf_dev, x128_dev, n_boards, rows_dev, n_rows_dev, 1);
+}
+
+int ccz_pack_planes128_rows_f16(void *stream, const void *leaf_dev, void *x128_dev, int32_t n_boards, const int32_t *rows_dev, const int32_t *n_rows_dev)
+{
+    if (!rows_dev || !n_rows_dev) return fail(-1, "ccz_pack_planes128_rows_f16: bad arguments");
+    return pack_planes128("ccz_pack_planes128_rows_f16", stream, leaf_dev, x128_dev, n_boards, rows_dev, n_rows_dev, 0);
+}
+
+int ccz_conv3x3_stem128_f16(void *stream, const void *x128_dev, const void *w_dev, const void *bias_f32_dev, void *y_dev, int64_t n_pixels, int32_t relu)
+{
+    if (relu & ~(3 | CCZ_CONV_G16)) return fail(-1, "ccz_conv3x3_stem128_f16: flags are ReLU (1), tile order (2) and CCZ_CONV_G16");
+    return conv3x3_launch("ccz_conv3x3_stem128_f16", stream, x128_dev, w_dev, bias_f32_dev, nullptr, y_dev, n_pixels, relu, 128);
+}
+
+int ccz_conv3x3_stem128_f16_live(void *stream, const void *x128_dev, const void *w_dev, const void *bias_f32_dev, void *y_dev, int64_t n_pixels, int32_t relu,
+                                 const int32_t *live_rows_dev, int32_t part, int32_t n_parts)
+{
+    if (relu & ~(3 | CCZ_CONV_G16)) return fail(-1, "ccz_conv3x3_stem128_f16_live: flags are ReLU (1), tile order (2) and CCZ_CONV_G16");
+    if (!live_rows_dev || g16_bad_part(part, n_parts)) return fail(-1, "ccz_conv3x3_stem128_f16_live: null live-row count or bad part / n_parts");
+    return conv3x3_launch("ccz_conv3x3_stem128_f16_live", stream, x128_dev, w_dev, bias_f32_dev, nullptr, y_dev, n_pixels, relu, 128, live_rows_dev, part | (n_parts << 16));
 }
 
 int ccz_pack_live_planes_f16(void *stream, const void *leaf_dev, void *x64_dev, int32_t n_boards)

@@ -100,6 +100,8 @@ class SelfPlayEngine:
         self.n_miss = torch.zeros((1,), dtype=torch.int32, device=self.device)
         # torch-owned boundary buffers (evaluator input / outputs, move buffers)
         self.leaf_input = torch.zeros((self.B, 17, 7, 10, 9), dtype=torch.float16, device=self.device)
+        self.leaf_history = False   # set_leaf_history: the host's shadow of the engine's setting, and a counter of its changes
+        self.history_version = 0
         self.moves_out = torch.full((self.B,), -1, dtype=torch.int32, device=self.device)
         self._forced = torch.full((self.B,), -1, dtype=torch.int32, device=self.device)
         self.budgets_out = torch.zeros((self.B,), dtype=torch.int32, device=self.device)   # what draw_budgets drew last
@@ -286,6 +288,31 @@ class SelfPlayEngine:
         and their number. No host sync: the evaluator's kernels read the count on the device."""
         check(self.L.ccz_eval_plan(self.h, self._stream(), _ptr(self.miss_rows), _ptr(self.n_miss)))
         return self.miss_rows, self.n_miss
+
+    # ------------------------------------------------------------------ leaf history planes (include/cczero.h ccz_set_leaf_history)
+    def set_leaf_history(self, enabled: bool = True):
+        """The evaluator input of a pending leaf shows the eight positions a training row shows (the game's recorded plies, the root,
+        the selection path; clamped at the game's first position) instead of the leaf alone in groups 7 / 15, and the leaf's cache
+        key becomes its history key, from the next select phase on. Call it between moves or before the first selection: a leaf that
+        is pending keeps the row it has. A change drops what rested on the old setting: the evaluation cache is cleared, the leaf
+        tensor is zeroed when the option goes off (the old path rewrites three groups only) and ``history_version`` moves -- a hipGraph
+        of the step does not hold the new launch, and ``selfplay.GraphedStep`` captures again when it sees that. The evaluator must
+        read all 17 groups (``boundary.need_history``). Not with scout slots, a width above 1 or ``reference_quirks``."""
+        enabled = bool(enabled)
+        if enabled == self.leaf_history:
+            return
+        check(self.L.ccz_set_leaf_history(self.h, self._stream(), int(enabled)))
+        self.leaf_history = enabled
+        self.history_version += 1
+        self.clear_eval_cache()
+        if not enabled:
+            check(self.L.ccz_zero_leaf_input(self.h, self._stream(), _ptr(self.leaf_input)))
+
+    def get_leaf_history(self) -> bool:
+        """The setting as the engine holds it (``ccz_get_leaf_history``)."""
+        v = C.c_int32(0)
+        check(self.L.ccz_get_leaf_history(self.h, C.byref(v)))
+        return bool(v.value)
 
     # ------------------------------------------------------------------ scouts (one game at a time: include/cczero.h ccz_scout)
     def set_scouts(self, n_scouts: int):

@@ -242,9 +242,14 @@ class InferenceNet(nn.Module):
 
     LIVE = list(range(7 * 7, 8 * 7)) + list(range(15 * 7, 17 * 7))  # channel ids of groups 7, 15, 16
 
-    def __init__(self, net: Net, dtype=torch.float16, live_only: bool = True):
+    def __init__(self, net: Net, dtype=torch.float16, live_only: bool = True, history: bool = False):
+        """``history``: the leaf rows hold all 17 plane groups (``SelfPlayEngine.set_leaf_history``): the stem reads the 119 planes --
+        ``stem_w128`` and the 128-channel pack + the general tile forms at cin = 128 next to (not instead of the code of) the 21-channel
+        form; batches below ``FUSED_MIN_BOARDS`` take the torch stem on the full input, with the once-per-shape log line."""
         super().__init__()
         self.dtype = dtype
+        self.history = bool(history)
+        live_only = live_only and not self.history
         self.live_only = live_only
         self.opt = EvalOptions()
         if self.opt.non_default():
@@ -262,6 +267,12 @@ class InferenceNet(nn.Module):
             w64[..., :len(self.LIVE)] = w.permute(0, 2, 3, 1)
             self.stem_w64 = nn.Parameter(w64.to(dtype).contiguous(), requires_grad=False)
             self.stem_b32 = nn.Parameter(b.detach().float().clone(), requires_grad=False)
+        if self.history and w.shape[0] == 256:
+            # the full stem for the fused kernels: [co, ky, kx, 128], the 119 planes in their own order, zeros above
+            w128 = torch.zeros(256, 3, 3, 128, dtype=w.dtype, device=w.device)
+            w128[..., :PLAYS * PIECES] = w.permute(0, 2, 3, 1)
+            self.stem_w128 = nn.Parameter(w128.to(dtype).contiguous(), requires_grad=False)
+            self.stem_b32 = nn.Parameter(b.detach().float().clone(), requires_grad=False)
         ws, bs = [], []
         for blk in net.res_blocks:
             for conv, bn in ((blk.conv1, blk.conv1_bn), (blk.conv2, blk.conv2_bn)):
@@ -275,6 +286,8 @@ class InferenceNet(nn.Module):
             self.ws_g16 = nn.ParameterList([nn.Parameter(pack_conv_weights_g16(w.permute(0, 2, 3, 1)), requires_grad=False) for w in ws])
         if hasattr(self, "stem_w64"):
             self.stem_w64_g16 = nn.Parameter(pack_conv_weights_g16(self.stem_w64), requires_grad=False)
+        if hasattr(self, "stem_w128"):
+            self.stem_w128_g16 = nn.Parameter(pack_conv_weights_g16(self.stem_w128), requires_grad=False)
         # float32 copies of the tower biases for the fused convolution kernel (bias is added to the fp32 accumulator)
         self.bs32 = nn.ParameterList([nn.Parameter(b.detach().float().clone(), requires_grad=False) for b in bs])
         # both 1x1 head convs as ONE plain GEMM on the NHWC rows: [pixels, C] x [C, 17 policy + 7 value channels]. (As an
@@ -380,6 +393,8 @@ class InferenceNet(nn.Module):
             names |= {f"ws_g16.{i}" for i in range(len(self.ws_g16))}
         if hasattr(self, "stem_w64_g16"):
             names.add("stem_w64_g16")
+        if hasattr(self, "stem_w128_g16"):
+            names.add("stem_w128_g16")
         return names
 
     @torch.no_grad()
@@ -394,6 +409,9 @@ class InferenceNet(nn.Module):
         if hasattr(self, "stem_w64_g16"):
             self.stem_w64_g16.copy_(pack_conv_weights_g16(self.stem_w64))
             done.add("stem_w64_g16")
+        if hasattr(self, "stem_w128_g16"):
+            self.stem_w128_g16.copy_(pack_conv_weights_g16(self.stem_w128))
+            done.add("stem_w128_g16")
         if done != self.derived_parameter_names():
             raise RuntimeError(f"repack_derived rebuilt {sorted(done)} but derived_parameter_names() lists {sorted(self.derived_parameter_names())}")
         self.__dict__.pop("_b2", None)
@@ -587,6 +605,8 @@ class InferenceNet(nn.Module):
         s = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         Bp = -(-B // 16) * 16 if g16 else B          # group-of-16 layout: whole groups; the padding boards hold zeros
         lay = _lib.CONV_G16 if g16 else 0   # (the stem is one launch over the whole batch, not chained: the single-kernel form)
+        if self.history:
+            return self._stem128(leaf_input, plan, g16, Bp, lay, s)
         if plan is None:
             x64 = (torch.zeros if Bp != B else torch.empty)((Bp, 90, 64), dtype=torch.float16, device=dev)
             y = torch.empty((Bp, 256, 10, 9), dtype=torch.float16, device=dev, memory_format=torch.channels_last)
@@ -607,6 +627,30 @@ class InferenceNet(nn.Module):
             stem = L.ccz_conv3x3_stem_g16c_f16 if plan is None else L.ccz_conv3x3_stem_g16c_f16_live
         _lib.check(pack(s, _ptr(leaf_input), _ptr(x64), B, *gather))
         _lib.check(stem(s, _ptr(x64), _ptr(self.stem_w64_g16 if g16 else self.stem_w64), _ptr(self.stem_b32), _ptr(y), *tail))
+        return y
+
+    def _stem128(self, leaf_input, plan, g16, Bp, lay, s):
+        """:meth:`_stem_fused` in history mode: every plane packed as NHWC rows of 128 channels (``ccz_pack_planes128_*``), then the
+        general tile form of the tower convolution at cin = 128 (``ccz_conv3x3_stem128_f16[_live]``). Rows, never chunk-major."""
+        from . import _lib
+        L = _lib.lib()
+        B, dev = leaf_input.shape[0], leaf_input.device
+        if plan is None:
+            x = (torch.zeros if Bp != B else torch.empty)((Bp, 90, 128), dtype=torch.float16, device=dev)
+            y = torch.empty((Bp, 256, 10, 9), dtype=torch.float16, device=dev, memory_format=torch.channels_last)
+            pack, gather = (L.ccz_pack_planes128_g16_f16, (None, None)) if g16 else (L.ccz_pack_planes128_f16, ())
+            stem, tail = L.ccz_conv3x3_stem128_f16, (Bp * 90, 1 | lay)
+        else:
+            bufs = self.__dict__.setdefault("_plan_bufs", {})
+            key = (Bp, dev, g16, 128)   # (as in _stem_fused: zeroed once, a dead row holds an old finite result)
+            if key not in bufs:
+                bufs[key] = (torch.zeros((Bp, 90, 128), dtype=torch.float16, device=dev),
+                             torch.empty((Bp, 256, 10, 9), dtype=torch.float16, device=dev, memory_format=torch.channels_last).zero_())
+            x, y = bufs[key]
+            pack, gather = (L.ccz_pack_planes128_g16_f16 if g16 else L.ccz_pack_planes128_rows_f16), (_ptr(plan[0]), _ptr(plan[1]))
+            stem, tail = L.ccz_conv3x3_stem128_f16_live, (Bp * 90 if g16 else -(-B // 8) * 8 * 90, 1 | lay, _ptr(plan[1]), 0, 1)
+        _lib.check(pack(s, _ptr(leaf_input), _ptr(x), B, *gather))
+        _lib.check(stem(s, _ptr(x), _ptr(self.stem_w128_g16 if g16 else self.stem_w128), _ptr(self.stem_b32), _ptr(y), *tail))
         return y
 
     @torch.no_grad()
@@ -632,7 +676,7 @@ class InferenceNet(nn.Module):
         cache = self.__dict__.setdefault("_path_cache", {})
         if key not in cache:
             o = self.opt
-            fused = (hasattr(self, "stem_w64") and leaf_input.is_cuda and leaf_input.dtype == torch.float16 and leaf_input.is_contiguous()
+            fused = ((hasattr(self, "stem_w64") or hasattr(self, "stem_w128")) and leaf_input.is_cuda and leaf_input.dtype == torch.float16 and leaf_input.is_contiguous()
                      and B >= self.FUSED_MIN_BOARDS and self.dtype == torch.float16 and o.fused_conv and o.fused_stem)
             if fused:
                 cache[key] = "g16" if self._g16(B) else "nhwc"
@@ -653,7 +697,7 @@ class InferenceNet(nn.Module):
             plan = None
         g16 = path == "g16"   # True: x holds its rows in the group-of-16 layout (and ceil(B / 16) * 16 boards)
         if path in ("g16", "nhwc"):
-            cm = g16 and self._g16c(-(-B // 16) * 16)
+            cm = g16 and not self.history and self._g16c(-(-B // 16) * 16)   # (no G16C form of the 128-channel stem: history runs on rows)
             x = self._stem_fused(leaf_input, plan, g16, cm)
             probe = self.__dict__.get("tower_probe")   # bench.py: a list that receives one HIP-event pair around the 80 tower launches
             if probe is not None:   # (recorded on the current stream: the chains fork from it and join it)
@@ -674,6 +718,13 @@ class InferenceNet(nn.Module):
             if self.live_only:
                 x = torch.cat([x[:, 49:56], x[:, 105:119]], dim=1)
             x = x.to(self.dtype).contiguous(memory_format=torch.channels_last)
+            if self.history and x.is_cuda:
+                seen = self.__dict__.setdefault("_torch_stem_seen", set())
+                if B not in seen:   # once per shape: a history batch that does not run the 128-channel pack + stem kernels
+                    seen.add(B)
+                    from .tools import log
+                    log(f"evaluator: history batch of {B} boards takes the torch stem on all 119 planes (the 128-channel pack + stem serve "
+                        f"256-wide fp16 towers from {self.FUSED_MIN_BOARDS} boards)")
             x = self._epilogue(F.conv2d(x, self.stem_w, None, padding=1), self.stem_b)
             if path == "torch_stem" and self._use_fused_tower(x):
                 x = self._tower_fused(x, None, False)
@@ -794,12 +845,21 @@ class PolicyValueNet:
         # MIOpen "find" mode for the evaluator's torch convolutions (towers that are not 256 wide): read once; CCZ_MIOPEN_FIND=0 =
         # immediate mode, no per-shape find step (tests, tiny nets)
         self._miopen_find = os.environ.get("CCZ_MIOPEN_FIND", "1") != "0"
+        self.leaf_history = False   # set_leaf_history: the inference copy reads all 119 planes of a row (boundary.reads_history asks this)
         self.weights_version = 0  # bumped whenever the inference copy is rebuilt or invalidated (hipGraphs hold its addresses)
 
     def invalidate_inference_copy(self):
         """The training weights changed: the fp16 inference copy is stale (rebuilt on the next evaluation)."""
         self._infer = None
         self.weights_version += 1
+
+    def set_leaf_history(self, enabled: bool = True):
+        """The evaluator reads all 17 plane groups of a leaf row (an engine with ``set_leaf_history`` on writes them) instead of the 21
+        live channels of groups 7, 15 and 16. A change drops the inference copy and moves ``weights_version``: evaluation caches and
+        captured graphs follow as they follow new weights."""
+        if bool(enabled) != self.leaf_history:
+            self.leaf_history = bool(enabled)
+            self.invalidate_inference_copy()
 
     # ---- batched evaluator for the lockstep engine -------------------------------------------
     def refresh_inference_copy(self):
@@ -808,7 +868,7 @@ class PolicyValueNet:
         # per shape and selects the composable-kernel XDL grouped-conv kernel (0.60 ms) -- profiles/miopen_find_r01.txt
         self._require_current_fp32("refresh_inference_copy")
         self.policy_value_net.eval()
-        self._infer = InferenceNet(self.policy_value_net).to(self.device).eval()
+        self._infer = InferenceNet(self.policy_value_net, history=self.leaf_history).to(self.device).eval()
         self._infer.bind_chain_streams(self.device)   # hardware queues for the tower's launch chains, before anything else asks for streams
         self._graph = None
         self.weights_version += 1

@@ -4,7 +4,8 @@ what, call the setters in one order, report. Also the command line of resign / r
 ``stopcfg`` (which keep the search parameters' and the early stop's), and the move of the arg-max front ends. No GPU here. Adding an
 option: ``ccz_set_x`` on the C side (which refuses what it excludes), the setter in ``engine.py``, ONE entry in ``OPTIONS`` (and a rule
 in ``SearchOptions.__init__`` if it excludes another), the keyword on the front ends that allow it. ``RECORD_OPTIONS`` holds, in the same
-shape, what decides how a recorded game is trained on (policy surprise weighting); ``SearchOptions`` handles both tables alike."""
+shape, what decides how a recorded game is trained on (policy surprise weighting), ``INPUT_OPTIONS`` what decides the evaluator's input (leaf
+history planes); ``SearchOptions`` handles the three tables alike."""
 from __future__ import annotations
 
 from collections import namedtuple
@@ -107,7 +108,27 @@ RECORD_OPTIONS = {
                        report=lambda e: {"surprise": surprise_report(e.surprise_stats())},
                        of_scalar=lambda x: {} if x is True else {"alpha": float(x)}),
 }
-ALL_OPTIONS = {**OPTIONS, **RECORD_OPTIONS}
+
+
+def history_report(stats: dict) -> dict:
+    """``stats`` = ``SelfPlayEngine.stats()``: the setting, and the share of the probed leaves the evaluation cache answered (from the table
+    or from another board's row of the same step; None without a cache) -- with history planes a transposition is another input and misses."""
+    n = stats["cache_probes"]
+    return {"leaf_history": True, "cache_hit_share": (stats["cache_hits"] + stats["cache_shared_rows"]) / n if n else None}
+
+
+def format_history(stats: dict) -> str:
+    share = history_report(stats)["cache_hit_share"]
+    return ", leaf history planes on, cache hit share " + ("n/a" if share is None else f"{share:.4f}")
+
+
+# What decides the evaluator's INPUT: applied and reported after the two tables above. The evaluator of a front end that turns it on must read
+# all 17 plane groups (``boundary.need_history``).
+INPUT_OPTIONS = {
+    "leaf_history": Option("set_leaf_history", "leaf history planes", lambda e: format_history(e.stats()),
+                           report=lambda e: history_report(e.stats()), of_scalar=lambda x: {"enabled": True}),
+}
+ALL_OPTIONS = {**OPTIONS, **RECORD_OPTIONS, **INPUT_OPTIONS}
 
 
 class SearchOptions:
@@ -140,13 +161,16 @@ class SearchOptions:
             raise ValueError("the early stop (--stop-*) and the Gumbel root search (--gumbel) exclude each other: sequential halving plans the whole budget")
         if int(width) > 1 and any(name in on for name in ("solver", "search", "early_stop")):
             raise ValueError("width > 1 (the wide search) excludes scouts, the solver, the search parameters and the early stop")
+        if int(width) > 1 and "leaf_history" in on:
+            raise ValueError("width > 1 (the wide search) excludes leaf history planes: a wide step's leaves are not replayed one path each")
 
     def keywords(self) -> dict:
         """``{keyword: value}`` of every allowed option, on or off, as a front end takes them (and in OPTIONS' order)."""
         return {name: getattr(self, name) for name in ALL_OPTIONS if hasattr(self, name)}
 
     def apply(self, engine):
-        """Call the setters of the options that are on, and no others: resign, root exploration, gumbel, solver, search, early stop, surprise.
+        """Call the setters of the options that are on, and no others: resign, root exploration, gumbel, solver, search, early stop, surprise,
+        leaf history.
         Every setter writes its own settings block only, so the order decides nothing."""
         for name, cfg in self.on.items():
             getattr(engine, ALL_OPTIONS[name].setter)(**cfg)
@@ -278,6 +302,24 @@ def gumbel_from_args(ap, a):
     """(``a.playout``: the simulations of a move.)"""
     return _from_args(ap, a, "--gumbel", "the Gumbel root search is off", ("--gumbel-considered", "--gumbel-c-visit", "--gumbel-c-scale"),
                       make_gumbel, a.gumbel, a.playout, a.gumbel_considered, a.gumbel_c_visit, a.gumbel_c_scale)
+
+
+def make_leaf_history(on):
+    """The value of the ``leaf_history`` keyword of the front ends: ``{"enabled": True}`` (the dict of ``SelfPlayEngine.set_leaf_history``'s
+    arguments) or None."""
+    return {"enabled": True} if on else None
+
+
+def add_leaf_history_args(ap):
+    """--leaf-history."""
+    ap.add_argument("--leaf-history", action="store_true", default=False, help="batched path: the search shows the network the eight-position "
+                    "input a training row holds (the game's recorded plies, the root, the selection path) instead of the leaf alone; the network "
+                    "reads all 119 planes (a 128-channel stem) and the evaluation cache keys on the history, so transpositions miss. For nets "
+                    "trained on this project's rows; absent = off (the reference's search input)")
+
+
+def leaf_history_from_args(ap, a):
+    return _from_args(ap, a, "--leaf-history", "leaf history planes are off", (), make_leaf_history, a.leaf_history)
 
 
 def make_surprise(weight, cap=None):

@@ -11,7 +11,7 @@ import os
 
 import numpy as np
 
-from .boundary import PlayoutTicker, WeightsWatch, capture, deliver, describe, kind_of, may_graph, need_version
+from .boundary import PlayoutTicker, WeightsWatch, capture, deliver, describe, kind_of, may_graph, need_history, need_version
 from .engine import SelfPlayEngine
 from .options import SearchOptions
 from .parameters import ALPHA, C_PUCT, EPS
@@ -43,6 +43,8 @@ class GraphedStep:
 
     def _capture(self):
         engine, ev = self.engine, self._ev
+        need_history(engine, self.evaluator, "GraphedStep: ")
+        self._history = engine.history_version   # (the captured launches are those of this setting: set_leaf_history moves it)
         # warm-up: the pending leaf is only evaluated, never stepped (and a stale inference copy is rebuilt OUTSIDE the capture,
         # which moves the version: it is read after that); capture does not execute: nothing is applied to the trees yet
         self.graph = capture(engine.device, lambda: deliver(engine, kind_of(ev), *ev.fn(engine.leaf_input), False),
@@ -51,8 +53,8 @@ class GraphedStep:
         self.captures += 1
 
     def replay(self):
-        if self._weights.moved(self._ev.version()):
-            self._capture()  # weights changed since the capture (train_step / refresh_inference_copy / broadcast_model)
+        if self._weights.moved(self._ev.version()) or self._history != self.engine.history_version:
+            self._capture()  # weights changed since the capture (train_step / refresh_inference_copy / broadcast_model), or the step's launches did
         self.graph.replay()
 
 
@@ -154,8 +156,12 @@ class BatchedSelfPlay:
     def __init__(self, evaluator, n_boards: int, n_playout: int = 400, c_puct: float = C_PUCT, eps: float = EPS,
                  alpha: float = ALPHA, temp: float = 1.0, seed: int = 0, board_id_base: int = 0, device: int = 0,
                  sampling: str = "device", use_graph: bool = False, version_fn=None, playout_cap=None, resign=None,
-                 root_exploration=None, solver: bool = False, gumbel=None, search=None, early_stop=None, surprise=None, **engine_kw):
-        """``surprise``: True, a weight in [0, 1], or a dict of :meth:`SelfPlayEngine.set_surprise`'s arguments (``alpha``, ``cap``): policy
+                 root_exploration=None, solver: bool = False, gumbel=None, search=None, early_stop=None, surprise=None, leaf_history: bool = False,
+                 **engine_kw):
+        """``leaf_history``: the evaluator input of a leaf shows the eight positions a training row shows (:meth:`SelfPlayEngine.set_leaf_history`):
+        the game's recorded plies, the root and the selection path. The evaluator must read all 17 plane groups and say so (a true
+        ``leaf_history`` attribute, ``boundary.reads_history``); one that does not is refused here. Not with ``reference_quirks``. False: off.
+        ``surprise``: True, a weight in [0, 1], or a dict of :meth:`SelfPlayEngine.set_surprise`'s arguments (``alpha``, ``cap``): policy
         surprise weighting -- the records of harvested games carry a sampling weight (``REC_WEIGHT``) that ``RecordReplayBuffer.sample(weighted=True)``
         draws by. Changes no search and no move; works with every other option and both sampling modes. None (default): off.
         ``early_stop``: a dict of :meth:`SelfPlayEngine.set_early_stop`'s arguments (``single_reply``, ``gap_factor``,
@@ -190,8 +196,10 @@ class BatchedSelfPlay:
         if sampling not in ("device", "numpy"):
             raise ValueError("sampling must be 'device' (Philox on the GPU) or 'numpy' (reference-exact host RNG)")
         self.options = o = SearchOptions(n_playout, sampling, resign=resign, root_exploration=root_exploration, gumbel=gumbel, solver=solver,
-                                         search=search, early_stop=early_stop, surprise=surprise)       # (ValueError: what excludes what)
-        self.resign, self.root_exploration, self.gumbel, self.solver, self.search_cfg, self.early_stop, self.surprise = o.keywords().values()
+                                         search=search, early_stop=early_stop, surprise=surprise, leaf_history=leaf_history)       # (ValueError: what excludes what)
+        (self.resign, self.root_exploration, self.gumbel, self.solver, self.search_cfg, self.early_stop, self.surprise,
+         self.leaf_history) = o.keywords().values()
+        self.leaf_history = self.leaf_history is not None
         self.playout_cap = None
         if playout_cap is not None:
             n_fast, p_full = playout_cap
@@ -204,6 +212,7 @@ class BatchedSelfPlay:
         self.engine = SelfPlayEngine(n_boards, n_playout=n_playout, c_puct=c_puct, eps=eps, alpha=alpha, temp=temp,
                                      seed=seed, board_id_base=board_id_base, device=device, **engine_kw)
         o.apply(self.engine)
+        need_history(self.engine, evaluator, "BatchedSelfPlay: ")   # (at every evaluation too: the evaluator can be swapped, the option set later)
         self.B = n_boards
         self.n_playout = n_playout
         self.sampling = sampling
@@ -248,6 +257,7 @@ class BatchedSelfPlay:
 
     def _evaluate(self, leaf):
         """``(boundary kind, outputs, value)`` of the pending leaf batch from the evaluator that is current."""
+        need_history(self.engine, self.evaluator, "BatchedSelfPlay: ")
         if self.planned:   # cache probe + plan, the network on the planned rows only
             return ("planned", *self._planned_eval(leaf))
         return (kind_of(self.evaluator), *self.evaluator(leaf))
@@ -378,7 +388,7 @@ class BatchedSelfPlay:
         they come from the boards' Philox streams, which the engine's snapshot carries. ``torch.save`` takes the dict as it is."""
         self._need_move_boundary("state_dict")
         return {"engine": self.engine.save_state(), "ticker_acc": int(self._ticker.acc), "sampling": self.sampling,
-                "n_playout": int(self.n_playout), "playout_cap": self.playout_cap,
+                "n_playout": int(self.n_playout), "playout_cap": self.playout_cap, "leaf_history": bool(self.engine.leaf_history),
                 "rngs": None if self.rngs is None else [r.get_state() for r in self.rngs]}
 
     def load_state_dict(self, state: dict, keep_board_id_base: bool = False):
@@ -390,6 +400,9 @@ class BatchedSelfPlay:
             theirs = state[name]
             if (tuple(theirs) if isinstance(theirs, (list, tuple)) else theirs) != mine:
                 raise ValueError(f"load_state_dict: {name} differs: the state has {theirs!r}, this object {mine!r}")
+        if bool(state.get("leaf_history", False)) != bool(self.engine.leaf_history):   # (a state from before the option: off)
+            raise ValueError(f"load_state_dict: leaf_history differs: the state has {bool(state.get('leaf_history', False))}, this object "
+                             f"{bool(self.engine.leaf_history)}: the rows and cache keys of the two settings are not the same search")
         if (state["rngs"] is None) != (self.rngs is None) or (self.rngs is not None and len(state["rngs"]) != len(self.rngs)):
             raise ValueError("load_state_dict: the per-board RandomStates of the state do not match this object's boards")
         self.engine.load_state(state["engine"], keep_board_id_base=keep_board_id_base)

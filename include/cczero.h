@@ -229,7 +229,8 @@ int ccz_reset_tree(ccz_engine *e, void *stream, const uint8_t *mask_host);
  * generation and game-end tests at the leaf, and the evaluator input written to
  * leaf_input_f16_dev [B,17,7,10,9] fp16. Only plane groups 7, 15 and 16 are ever non-zero on this
  * path (net.py:160-173); the engine rewrites those three and assumes the other 14 groups are zero
- * (ccz_zero_leaf_input zeroes the whole tensor once). */
+ * (ccz_zero_leaf_input zeroes the whole tensor once). ccz_set_leaf_history replaces this row by the eight-position row a
+ * training sample holds. */
 int ccz_select_leaves(ccz_engine *e, void *stream, void *leaf_input_f16_dev);
 int ccz_zero_leaf_input(ccz_engine *e, void *stream, void *leaf_input_f16_dev);
 /* Replaces the second half of MCTS.playout (mcts.py:113-129): Node.expand with priors
@@ -285,7 +286,8 @@ int ccz_scouted_run(ccz_engine *e, void *stream, void *leaf_input_f16_dev, int32
                     int32_t *run_dev);
 
 /* Evaluation cache (ccz_config.eval_cache_log2 > 0). On the search path the evaluator sees the leaf POSITION and the side to move
- * only (net.py:160-173: the history planes are zero; mcts.py:214 passes none), i.e. a function of the leaf's Zobrist key. The
+ * only (net.py:160-173: the history planes are zero; mcts.py:214 passes none), i.e. a function of the leaf's Zobrist key (with
+ * ccz_set_leaf_history on: of the leaf's HISTORY KEY, which stands in for the Zobrist key in everything below). The
  * reference evaluates every leaf on its own (mcts.py:114); here a position that was evaluated before -- by this board (a
  * transposition), by another board (every restarted game walks through openings that earlier games searched), or by another
  * board in this very step -- is not sent through the network again. Results are unchanged bit for bit as long as the evaluator is
@@ -307,6 +309,48 @@ int ccz_eval_plan(ccz_engine *e, void *stream, int32_t *miss_rows_dev, int32_t *
 int ccz_gather_priors_planned(ccz_engine *e, void *stream, const void *logits_compact_dev, int32_t logits_f16,
                               const float *value_compact_dev);
 int ccz_eval_cache_clear(ccz_engine *e, void *stream);
+
+/* ---- leaf history planes (additive to ABI 9) -------------------------------------------------------------------------------------
+ * The rows the collector trains on (ccz_harvest, default mode) show eight positions; the search above shows the net one, in the
+ * groups where a row holds the position of seven plies ago. With the option on, every select phase (ccz_select_leaves, ccz_step,
+ * ccz_step_compact) is followed by one more launch that rewrites ALL 17 groups of the row of every board with a pending leaf to
+ * evaluate (CCZ_LEAF_EXPAND; other boards' rows are unspecified, as before):
+ *   p = the plies recorded in the board's current game, S_0 .. S_{p-1} = their root positions, S_p = the root, S_{p+1} .. S_{p+d} = the
+ *   positions along the selection path to the leaf at depth d, te = p + d. History slot i (0..7) shows S_{max(te - i, 0)} -- the clamp
+ *   of the rows (the reference's reset_states_history padding). Groups 0..7 hold the red pieces of slots 0..7, groups 8..15 the black
+ *   ones, group 16 is all ones iff red is to move at the leaf; channels follow plane_of_type. That is, byte for byte, the state
+ *   ccz_harvest writes (pass 0) for ply te of a game played along that path.
+ * Cache key rule: "equal keys = equal evaluator input" must hold, and with history the input is no function of the leaf position. The
+ * same launch therefore replaces the board's key by the HISTORY KEY
+ *   mix64(leaf_key ^ h_7),  h_0 = 0x9E3779B97F4A7C15, h_i = mix64(h_{i-1} ^ P(slot i)),  i = 1..7,
+ * P(S) = the XOR of the Zobrist words of S's pieces (no side to move), mix64 = the splitmix64 finaliser. The hash depends on the
+ * positions shown, not on where they come from: a clamped prefix and a real repeat of the same positions hash alike, as their input
+ * is alike. Every reader of the key (probe, plan, same-step sharing, the routing salts, verify mode, ccz_leaf_keys) sees the history
+ * key and works unchanged; a transposition reached by another move order is now another input and misses.
+ *   ccz_set_leaf_history: host-side, takes effect with the next select phase (`stream` is unused). Enabling fails with scout slots
+ *     (ccz_set_scouts), with a width above 1 (ccz_set_width) and on CCZ_FLAG_REFERENCE_QUIRKS engines (their rows alias the final
+ *     history, which no search sees); ccz_set_scouts(n > 0) and ccz_set_width(width > 1) fail while it is on. The select calls then
+ *     need a non-null leaf input. After turning it OFF the caller must call ccz_zero_leaf_input once: the old path rewrites groups
+ *     7, 15 and 16 only. A hipGraph captured before the call does not hold the new launch: capture again. Flush the evaluation cache
+ *     when the setting changes (ccz_eval_cache_clear): keys of the two modes name different inputs.
+ *   Positions loaded by ccz_set_position(s) start a game at ply 0: the moves that led there are no history, the clamp repeats the
+ *     loaded position. */
+int ccz_set_leaf_history(ccz_engine *e, void *stream, int32_t enabled);
+int ccz_get_leaf_history(ccz_engine *e, int32_t *enabled_host);
+/* The evaluator's side of it: ALL 119 planes of a row, where ccz_pack_live_planes_* keep the 21 of groups 7, 15 and 16.
+ *   ccz_pack_planes128_f16 / _g16_f16 / _rows_f16: dense [B,17,7,10,9] fp16 -> NHWC rows of 128 channels (119 + 9 zeros), board-major /
+ *     group-of-16 / planned rows: the three ccz_pack_live_planes* entry points with x128_dev [rows, 128] for x64_dev, the same rows /
+ *     n_rows conventions; every byte of a written row is written (no pre-zeroed buffer is assumed).
+ *   ccz_conv3x3_stem128_f16[_live]: ccz_conv3x3_stem_f16[_live] at cin = 128 -- the GENERAL tile forms (k_conv3x3_c256 with two 64-channel
+ *     chunks, k_conv3x3_g16 with four 32-channel chunks under CCZ_CONV_G16), not the one-chunk stem form; weights [256, 3, 3, 128]
+ *     (under CCZ_CONV_G16: packed by ccz_pack_conv_weights_g16_f16 with cin = 128). Flags: ReLU, tile order, CCZ_CONV_G16. There is no small-
+ *     batch form and no G16C form at 128 channels: any batch runs the tile kernel, and a tower that follows runs on rows. */
+int ccz_pack_planes128_f16(void *stream, const void *leaf_dev, void *x128_dev, int32_t n_boards);
+int ccz_pack_planes128_g16_f16(void *stream, const void *leaf_dev, void *x128_dev, int32_t n_boards, const int32_t *rows_dev, const int32_t *n_rows_dev);
+int ccz_pack_planes128_rows_f16(void *stream, const void *leaf_dev, void *x128_dev, int32_t n_boards, const int32_t *rows_dev, const int32_t *n_rows_dev);
+int ccz_conv3x3_stem128_f16(void *stream, const void *x128_dev, const void *w_dev, const void *bias_f32_dev, void *y_dev, int64_t n_pixels, int32_t relu);
+int ccz_conv3x3_stem128_f16_live(void *stream, const void *x128_dev, const void *w_dev, const void *bias_f32_dev, void *y_dev, int64_t n_pixels, int32_t relu,
+                                 const int32_t *live_rows_dev, int32_t part, int32_t n_parts);
 
 /* Two evaluators on one engine (an arena between two networks; needs the evaluation cache, no scout slots). The reference's
  * Game.start_play (game.py:77-130) with two MCTS_AI players: the player to move at the ROOT searches with its own network, which
@@ -790,7 +834,8 @@ int ccz_leaf_priors(ccz_engine *e, void *stream, float *prior_host, float *value
 /* Zobrist keys (pieces + side to move: everything the evaluator input of net.py:160-173 depends on) and CCZ_LEAF_* status of
  * the pending leaves, copied device-to-device on `stream` (no sync): keys_dev uint64 [B], status_dev uint8 [B], either may be
  * NULL. Equal keys = equal evaluator input: what a transposition / duplicate-leaf cache would key on (the reference
- * evaluates every leaf separately, mcts.py:114). */
+ * evaluates every leaf separately, mcts.py:114). With ccz_set_leaf_history on these are the HISTORY KEYS (see there): the leaf's
+ * key mixed with a hash of the seven older positions shown, so the sentence above stays true. */
 int ccz_leaf_keys(ccz_engine *e, void *stream, uint64_t *keys_dev, uint8_t *status_dev);
 
 /* ---- training tuples ---------------------------------------------------------------------- */
