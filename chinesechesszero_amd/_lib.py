@@ -177,6 +177,10 @@ PROTOTYPES = {
     "ccz_searching": (C.c_int, [_P, _P, C.POINTER(C.c_int32)]),
     "ccz_set_solver": (C.c_int, [_P, _P, C.c_int32]),
     "ccz_root_proof": (C.c_int, [_P, _P, _P, _P, _P, _P]),
+    "ccz_set_value_stats": (C.c_int, [_P, _P, C.c_int32]),
+    "ccz_get_value_stats": (C.c_int, [_P, _P]),
+    "ccz_root_value_stats": (C.c_int, [_P, _P, _P, _P]),
+    "ccz_lcb_moves": (C.c_int, [_P, _P, C.c_double, C.c_double, C.c_int32, _P, _P, _P]),
     "ccz_get_solver_stats": (C.c_int, [_P, _P, C.POINTER(SolverStats)]),
     "ccz_proof_combine": (C.c_int, [_P, _P, _P, C.c_int32, _P]),
     "ccz_set_width": (C.c_int, [_P, _P, C.c_int32]),

@@ -16,6 +16,7 @@ skipped); one JSON object per position goes to ``--out`` (stdout without it), a 
 from __future__ import annotations
 
 import json
+import math
 import sys
 import time
 
@@ -24,7 +25,7 @@ import numpy as np
 from ._lib import CczError
 from .boundary import describe
 from .game import Board
-from .options import SearchOptions, add_leaf_history_args, leaf_history_from_args
+from .options import SearchOptions, add_lcb_args, add_leaf_history_args, lcb_from_args, leaf_history_from_args
 from .searchcfg import add_search_args, search_from_args
 from .stopcfg import add_early_stop_args, early_stop_from_args
 
@@ -58,15 +59,23 @@ def parse_positions(lines) -> list[tuple[int, Board]]:
     return out
 
 
-def make_record(status: str, root_visits: int = 0, lines=(), solver=None) -> dict:
+def make_record(status: str, root_visits: int = 0, lines=(), solver=None, lcb=None) -> dict:
     """One result record: ``status`` ("ok", "illegal move i", "invalid position", "history too long", "game over: ..."),
     ``bestmove`` (the first move of line 0, or None), ``root_visits``, ``lines`` = [{moves (uci), visits, q, prior}].
     ``solver`` (an analysis with the MCTS-solver; None without): ``{"proven": uci or None, "mates": {uci: N}}`` -- the record and
     every line gain ``"mate"``: N in moves (``engine.mate_score``; negative: the side to move is mated) or None, and ``bestmove``
-    is the proven move where the root is decided."""
+    is the proven move where the root is decided. ``lcb`` (an analysis with the LCB move; None without): ``{"move": uci or None,
+    "stats": {uci: (stdev, lcb)}}`` -- every line gains ``"stdev"`` (the sample standard deviation of the values backed up through its
+    first move; None below two visits) and ``"lcb"`` (its lower confidence bound; None where it has none), and ``bestmove`` is the LCB
+    move unless the root is proven. The lines stay ranked by visits."""
     keep = [dict(moves=list(l["moves"]), visits=[int(v) for v in l["visits"]], q=float(l["q"]), prior=float(l["prior"])) for l in lines]
     rec = {"status": status, "bestmove": keep[0]["moves"][0] if keep and keep[0]["moves"] else None,
            "root_visits": int(root_visits), "lines": keep}
+    if lcb is not None:
+        for l in keep:
+            l["stdev"], l["lcb"] = lcb["stats"].get(l["moves"][0], (None, None)) if l["moves"] else (None, None)
+        if lcb.get("move") is not None and rec["bestmove"] is not None:
+            rec["bestmove"] = lcb["move"]
     if solver is not None:
         for l in keep:
             l["mate"] = solver["mates"].get(l["moves"][0]) if l["moves"] else None
@@ -87,12 +96,13 @@ class BatchedAnalysis:
     across chunks and cleared only when the evaluator's weights version changes."""
 
     def __init__(self, evaluator, n_boards: int, n_playout: int = 400, multipv: int = 1, max_len: int = 32, solver: bool = False, search=None,
-                 width: int = 1, early_stop=None, leaf_history=None, **engine_kw):
+                 width: int = 1, early_stop=None, leaf_history=None, lcb=None, **engine_kw):
         """``width`` > 1: every position gathers up to ``width`` leaves of its tree per step, kept apart by virtual loss
         (``wide.WideSearch``: an engine of ``n_boards * width`` slots) -- for a handful of positions, where the sequential search
         runs at the evaluator's latency; another tree than the sequential one; excludes ``solver`` and ``search``.
         ``solver`` / ``search`` / ``early_stop``: the engine options (``options.OPTIONS``; None / False: off). With the early stop a position
-        stops being searched when its best move can no longer change, and a chunk's loop ends when no board would select any more."""
+        stops being searched when its best move can no longer change, and a chunk's loop ends when no board would select any more.
+        ``lcb``: the LCB move (``options.MOVE_OPTIONS``): ``bestmove`` is it, every line gains ``stdev`` and ``lcb``; not with ``width`` > 1."""
         from .selfplay import BatchedSelfPlay
         desc = describe(evaluator)
         ev = desc.fn
@@ -100,7 +110,7 @@ class BatchedAnalysis:
             raise TypeError("BatchedAnalysis: the evaluator must be callable or have evaluate_leaves_logits")
         if not 1 <= int(multipv) <= 128 or int(max_len) < 1 or int(n_playout) < 1:
             raise ValueError("BatchedAnalysis: multipv must be 1..128, max_len and n_playout >= 1")
-        SearchOptions(n_playout, width=width, solver=solver, search=search, early_stop=early_stop, leaf_history=leaf_history)   # (ValueError: width > 1 excludes them)
+        SearchOptions(n_playout, width=width, solver=solver, search=search, early_stop=early_stop, leaf_history=leaf_history, lcb=lcb)   # (ValueError: width > 1 excludes them)
         if "eval_cache_log2" not in engine_kw:
             engine_kw["eval_cache_log2"] = 22 if (int(n_boards) >= 192 and desc.accepts_plan) else 0
         engine_kw.setdefault("mirror", False)
@@ -118,11 +128,12 @@ class BatchedAnalysis:
             self.wide = WideSearch(ev, int(n_boards), self.width, n_playout=int(n_playout), **engine_kw)   # ValueError: width not in 2..64
             self.sp = None
             self.engine = self.wide.engine
-            self.solver = False
+            self.solver, self.lcb = False, None
             return
         self.sp = BatchedSelfPlay(ev, int(n_boards), n_playout=int(n_playout), eps=0.0, search=search, early_stop=early_stop, leaf_history=leaf_history, **engine_kw)   # no GPU: CczError
         self.engine = self.sp.engine
-        opts = SearchOptions(solver=solver)     # (search and early stop: the self-play front end's own, above)
+        opts = SearchOptions(solver=solver, lcb=lcb)     # (search and early stop: the self-play front end's own, above; it samples from pi and takes no lcb)
+        self.lcb = opts.lcb
         self.solver = opts.solver               # the MCTS-solver: records gain "mate", bestmove follows the proof (make_record)
         opts.apply(self.engine)
 
@@ -169,6 +180,11 @@ class BatchedAnalysis:
             pv = e.principal_variations(self.multipv, self.max_len)
             e.check_healthy()
             rp, rc = (e.root_proof(), e.root_children()) if self.solver else (None, None)
+            lb = None
+            if self.lcb is not None:
+                got = e.lcb_moves(self.lcb["z"], self.lcb["min_visit_ratio"], self.lcb["min_visits"], with_bounds=True)
+                lb = {"moves": got["moves"].cpu().numpy(), "lcb": got["lcb"].cpu().numpy(), "S": e.root_value_stats()["S"]}
+                rc = e.root_children() if rc is None else rc
             for j, bd in enumerate(chunk):
                 s = int(status[j])
                 if s > 0:
@@ -191,8 +207,16 @@ class BatchedAnalysis:
                         pm = proof_move(rp["state"][j], rp["dist"][j], rp["child_state"][j], rp["child_dist"][j], rc["acts"][j])
                         sv = {"proven": None if pm is None else uci_of[pm],
                               "mates": {uci_of[int(rc["acts"][j][i])]: mate_score(rp["child_state"][j][i], rp["child_dist"][j][i]) for i in range(k)}}
+                    lc = None
+                    if lb is not None:
+                        stats = {}
+                        for i in range(int(rc["k"][j])):
+                            n_i, s_i, b_i = int(rc["visits"][j][i]), float(lb["S"][j][i]), float(lb["lcb"][j][i])
+                            stats[uci_of[int(rc["acts"][j][i])]] = (math.sqrt(max(s_i, 0.0) / (n_i - 1)) if n_i >= 2 else None,
+                                                                    b_i if b_i > float("-inf") else None)
+                        lc = {"move": uci_of[int(lb["moves"][j])] if lb["moves"][j] >= 0 else None, "stats": stats}
                     if lines:
-                        out.append(make_record("ok", pv["root_visits"][j], lines, solver=sv))
+                        out.append(make_record("ok", pv["root_visits"][j], lines, solver=sv, lcb=lc))
                     else:   # a position given without moves that is already decided: the root never got children
                         oc = bd.outcome()
                         out.append(make_record("ok" if oc is None else _winner_text(None if oc.winner is None else int(bool(oc.winner))),
@@ -235,8 +259,10 @@ def main(argv=None) -> int:
     add_search_args(ap)
     add_early_stop_args(ap)
     add_leaf_history_args(ap)
+    add_lcb_args(ap)
     args = ap.parse_args(argv)
     leaf_history = leaf_history_from_args(ap, args)
+    lcb = lcb_from_args(ap, args)
     search = search_from_args(ap, args)
     early_stop = early_stop_from_args(ap, args)
     with open(args.file, encoding="utf-8") as f:
@@ -256,7 +282,7 @@ def main(argv=None) -> int:
             pvn.set_leaf_history(True)
         an = BatchedAnalysis(pvn, max(1, min(args.boards, len(parsed) or 1)), n_playout=args.playout, multipv=args.multipv,
                              max_len=args.max_len, solver=args.solver, search=search, width=args.width,
-                             early_stop=early_stop, leaf_history=leaf_history)
+                             early_stop=early_stop, leaf_history=leaf_history, lcb=lcb)
         records = an.analyse([b for _, b in parsed])
     except CczError as e:
         print(f"analyse: {e}", file=sys.stderr)

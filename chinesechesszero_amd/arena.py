@@ -23,7 +23,8 @@ import numpy as np
 
 from .boundary import WeightsWatch, describe
 from .parameters import C_PUCT
-from .options import SearchOptions, add_leaf_history_args, add_resign_args, leaf_history_from_args, proven_moves, resign_from_args, search_move
+from .options import (SearchOptions, add_lcb_args, add_leaf_history_args, add_resign_args, lcb_from_args, lcb_moves, leaf_history_from_args,
+                      proven_moves, resign_from_args, search_move)
 from .searchcfg import add_search_args, search_from_args
 from .stopcfg import StopPoll, add_early_stop_args, early_stop_from_args
 
@@ -176,12 +177,16 @@ class Arena:
     is a win for the other side like any other, counted in ``result()["resigned"]``; no game is played on (``p_playon`` = 0).
     None (default): games end by the rules or the ply cap only. ``solver`` / ``search`` / ``early_stop``: the engine options
     (``options.OPTIONS``; None / False: off), for both sides alike: with the solver the proven move is played where the root is decided
-    (``options.proven_moves``), with the early stop the move's loop ends when no board would select any more (``options.search_move``)."""
+    (``options.proven_moves``), with the early stop the move's loop ends when no board would select any more (``options.search_move``).
+    ``lcb``: the LCB move (``options.MOVE_OPTIONS``: True, a multiple z of the standard error, or a dict) instead of the most visited one,
+    for the side(s) ``lcb_side`` names -- "both", "a" or "b": a board's move is the LCB move only when the owner of the side to move has
+    the option, so ``Arena(X, X, lcb=True, lcb_side="a")`` measures it. A proven move wins over it. ``result()["lcb"]`` then holds, per
+    side, the moves played by the rule and how many of them were not the most visited move."""
 
     def __init__(self, net_a, net_b, n_pairs: int, n_playout: int = 400, opening_plies: int = 6, seed: int = 0,
                  max_plies: int = 0, c_puct: float = C_PUCT, eval_cache_log2: int = 22, device: int = 0,
                  cache_verify: bool = False, n_playout_b: int | None = None, resign=None, solver: bool = False, search=None, early_stop=None,
-                 leaf_history=None):
+                 leaf_history=None, lcb=None, lcb_side: str = "both"):
         from .boundary import need_history
         from .engine import SelfPlayEngine
         self.nets = (net_a, net_b)
@@ -201,8 +206,15 @@ class Arena:
         if self.n_playout < 1 or (self.n_playout_b is not None and self.n_playout_b < 1):
             raise ValueError("Arena: n_playout and n_playout_b must be >= 1")
         self.n_steps = self.n_playout if self.n_playout_b is None else max(self.n_playout, self.n_playout_b)   # lockstep steps per move
-        self.options = o = SearchOptions(self.n_steps, resign=resign, solver=solver, search=search, early_stop=early_stop, leaf_history=leaf_history)
-        self.resign, self.solver, self.search_cfg, self.early_stop, self.leaf_history = o.keywords().values()
+        self.options = o = SearchOptions(self.n_steps, resign=resign, solver=solver, search=search, early_stop=early_stop, lcb=lcb,
+                                         leaf_history=leaf_history)
+        self.resign, self.solver, self.search_cfg, self.early_stop, self.lcb, self.leaf_history = o.keywords().values()
+        if lcb_side not in ("both", "a", "b"):
+            raise ValueError(f"Arena: lcb_side must be 'both', 'a' or 'b' (got {lcb_side!r})")
+        if self.lcb is None and lcb_side != "both":
+            raise ValueError("Arena: lcb_side without lcb: the LCB move is off")
+        self.lcb_side = lcb_side
+        self.lcb_sides = {s: {"moves": 0, "differed": 0} for s in ("a", "b") if self.lcb is not None and lcb_side in ("both", s)}
         if self.resign is not None:          # (the dict ``o.apply`` hands to the engine)
             if self.resign.get("p_playon", 0.0) != 0.0:
                 raise ValueError("Arena: a match plays no game on after the resignation rule fired (p_playon is fixed at 0)")
@@ -277,6 +289,14 @@ class Arena:
         over = e.game_status()["over"]
         forced, proven = proven_moves(e, self.solver, over)
         self.proven_moves += proven
+        a_moves = self._turn == self.a_colour
+        if self.lcb is not None:   # (off: no call is made) one call; the counts are split by the owner of the side to move
+            allow = None if self.lcb_side == "both" else (a_moves if self.lcb_side == "a" else ~a_moves)
+            forced, _, fill, off = lcb_moves(e, self.lcb, forced, over, allow=allow, counts=self.options.lcb_counts, detail=True)
+            for side, c in self.lcb_sides.items():
+                mine = a_moves if side == "a" else ~a_moves
+                c["moves"] += int((fill & mine).sum())
+                c["differed"] += int((off & mine).sum())
         moves = e.finish_move(forced_moves=forced, temps=self._temps, keep_tree=False).cpu().numpy().copy()
         # a game adjudicated at max_plies ends INSTEAD of a move (finish_move plays none on that board); so does a resigned one
         st = e.game_status()
@@ -326,6 +346,8 @@ class Arena:
         out.update(self.options.report(self.engine))
         if self.solver:
             out["solver"]["proven_moves"] = self.proven_moves
+        if self.lcb is not None:
+            out["lcb"] = dict(self.lcb, side=self.lcb_side, **{s: dict(c) for s, c in self.lcb_sides.items()})
         s = self.engine.stats()
         out["cache"] = {k: s[k] for k in ("cache_probes", "cache_hits", "cache_shared_rows", "cache_stores",
                                            "cache_verified", "cache_verify_mismatches")}
@@ -371,19 +393,25 @@ def main(argv=None) -> int:
     add_search_args(ap)
     add_early_stop_args(ap)
     add_leaf_history_args(ap)
+    add_lcb_args(ap)
+    ap.add_argument("--lcb-side", choices=("both", "a", "b"), default=None, help="... which side plays the LCB move (default both); "
+                    "--a X --b X --lcb --lcb-side a measures the option")
     a = ap.parse_args(argv)
     search = search_from_args(ap, a)
     early_stop = early_stop_from_args(ap, a)
     resign = resign_from_args(ap, a)
     na = _load(a.a, a.channels, a.blocks, a.device)
     nb = _load(a.b, a.channels, a.blocks, a.device)
+    lcb = lcb_from_args(ap, a)
+    if lcb is None and a.lcb_side is not None:
+        ap.error("--lcb-side without --lcb: the LCB move is off")
     leaf_history = leaf_history_from_args(ap, a)
     if leaf_history is not None:
         na.set_leaf_history(True)
         nb.set_leaf_history(True)
     arena = Arena(na, nb, a.pairs, n_playout=a.playout, opening_plies=a.opening_plies, seed=a.seed, max_plies=a.max_plies,
                   eval_cache_log2=a.eval_cache_log2, device=a.device, n_playout_b=a.playout_b, resign=resign, solver=a.solver, search=search,
-                  early_stop=early_stop, leaf_history=leaf_history)
+                  early_stop=early_stop, leaf_history=leaf_history, lcb=lcb, lcb_side=a.lcb_side or "both")
     r = arena.play()
     r.update({"a": a.a, "b": a.b, "opening_plies": a.opening_plies, "seed": a.seed, "net": f"{a.blocks}x{a.channels}",
               "promote": promote(r, a.threshold), "threshold": a.threshold})

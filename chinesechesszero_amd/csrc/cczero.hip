@@ -99,6 +99,10 @@ struct ccz_engine {
     // SolverCfg.enabled, staging of ccz_root_proof (state [B], dist [B], child state [B][128], child dist [B][128])
     uint8_t *proof = nullptr, *st_proof = nullptr;
     bool solver_on = false;
+    // value spread (ccz_set_value_stats): S [B][2][cap] floats (allocated by the first call that turns it on), the host's shadow of
+    // SolverCfg.spread, staging of ccz_root_value_stats (children [B][128], root [B])
+    float *spread_S = nullptr, *st_spread = nullptr;
+    bool spread_on = false;
     // wide search (ccz_set_width): slots per board (1: off; above 1 `active` = n_boards / width), the in-flight counts F [B][2][cap] and
     // the per-board counters (both allocated by the first call that turns it on), staging of ccz_get_wide_stats
     int width = 1;
@@ -345,9 +349,9 @@ int ccz_create(const ccz_config *cfg, ccz_engine **out)
     ALLOC(d.ex_dir, B * kMaxLegal);
     ALLOC(d.ex_stamp, B * 2);
     ALLOC(d.ex_stats, B);
-    SolverCfg *sv_cfg = nullptr;
-    ALLOC(sv_cfg, 1); // zeroed: solver off, no proof array
-    d.sv_cfg = sv_cfg;
+    SolverBlock *sv_block = nullptr;
+    ALLOC(sv_block, 1); // zeroed: solver off, no proof array; value spread off, no S array
+    d.sv_cfg = &sv_block->cfg;
     ALLOC(d.sv_stats, B);
     GumbelCfg *gm_cfg = nullptr;
     ALLOC(gm_cfg, 1); // zeroed: Gumbel root search off
@@ -1162,11 +1166,74 @@ int ccz_set_solver(ccz_engine *e, void *stream, int32_t enabled)
     }
     SolverCfg v;
     v.enabled = enabled ? 1 : 0;
-    v.pad = 0;
+    v.spread = e->spread_on ? 1 : 0;
     v.proof = e->proof;
     hipLaunchKernelGGL(k_set_solver, dim3(1), dim3(1), 0, s, const_cast<SolverCfg *>(e->d.sv_cfg), v);
     HIP_TRY(hipGetLastError());
     e->solver_on = enabled != 0;
+    return 0;
+}
+
+// ---- value spread and the LCB move (cczero.h: "Value spread and the LCB move")
+int ccz_set_value_stats(ccz_engine *e, void *stream, int32_t enabled)
+{
+    NEED(e);
+    hipStream_t s = (hipStream_t)stream;
+    if (enabled && WIDE(e)) return fail(-1, "ccz_set_value_stats: not while the width is %d (ccz_set_width): a virtual loss is no value", e->width);
+    if (enabled && (e->d.flags & CCZ_FLAG_VALUE_F16)) return fail(-1, "ccz_set_value_stats: not on a CCZ_FLAG_VALUE_F16 engine: the float16 running mean has no stated S");
+    const size_t n = (size_t)e->d.B * 2 * (size_t)e->d.cap;
+    if (enabled && !e->spread_S) {
+        HIP_TRY(hipSetDevice(e->cfg.device));
+        HIP_TRY(dalloc(&e->spread_S, n, e->owned, e->bytes)); // (zeroed; may sync)
+    } else if (enabled && !e->spread_on) {
+        HIP_TRY(hipMemsetAsync(e->spread_S, 0, n * sizeof(float), s)); // nothing kept the sums up to date while it was off
+    }
+    SolverBlock *blk = reinterpret_cast<SolverBlock *>(const_cast<SolverCfg *>(e->d.sv_cfg));
+    hipLaunchKernelGGL(k_set_value_stats, dim3(1), dim3(1), 0, s, blk, enabled ? 1 : 0, e->spread_S);
+    HIP_TRY(hipGetLastError());
+    e->spread_on = enabled != 0;
+    return 0;
+}
+
+int ccz_get_value_stats(ccz_engine *e, int32_t *enabled_out)
+{
+    NEED(e);
+    if (!enabled_out) return fail(-1, "ccz_get_value_stats: null output");
+    *enabled_out = e->spread_on ? 1 : 0;
+    return 0;
+}
+
+int ccz_root_value_stats(ccz_engine *e, void *stream, float *s_host, float *root_s_host)
+{
+    NEED(e);
+    if (!e->spread_on) return fail(-1, "ccz_root_value_stats: the value spread is off (ccz_set_value_stats)");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t B = (size_t)e->d.B;
+    if (!e->st_spread) {
+        HIP_TRY(hipSetDevice(e->cfg.device));
+        HIP_TRY(dalloc(&e->st_spread, B * (kMaxLegal + 1), e->owned, e->bytes));
+    }
+    float *p = e->st_spread;
+    hipLaunchKernelGGL(k_root_value_stats, dim3(e->d.B), dim3(64), 0, s, e->d, (int)ACTIVE(e), p, p + B * kMaxLegal);
+    HIP_TRY(hipGetLastError());
+    if (s_host) HIP_TRY(hipMemcpyAsync(s_host, p, B * kMaxLegal * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (root_s_host) HIP_TRY(hipMemcpyAsync(root_s_host, p + B * kMaxLegal, B * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return 0;
+}
+
+int ccz_lcb_moves(ccz_engine *e, void *stream, double z, double min_visit_ratio, int32_t min_visits, int32_t *moves_out_dev,
+                  int32_t *child_out_dev, double *lcb_out_dev)
+{
+    NEED(e);
+    if (!e->spread_on) return fail(-1, "ccz_lcb_moves: the value spread is off (ccz_set_value_stats)");
+    if (!moves_out_dev) return fail(-1, "ccz_lcb_moves: null moves_out");
+    if (!(z >= 0.0) || z > 1.7976931348623157e308) return fail(-1, "ccz_lcb_moves: z %g must be finite and >= 0", z);
+    if (!(min_visit_ratio >= 0.0 && min_visit_ratio <= 1.0)) return fail(-1, "ccz_lcb_moves: min_visit_ratio %g must be in [0, 1]", min_visit_ratio);
+    if (min_visits < 0) return fail(-1, "ccz_lcb_moves: min_visits %d must be >= 0", min_visits);
+    hipLaunchKernelGGL(k_lcb_moves, dim3(e->d.B), dim3(64), 0, (hipStream_t)stream, e->d, (int)ACTIVE(e), z, min_visit_ratio, (int)min_visits,
+                       moves_out_dev, child_out_dev, lcb_out_dev);
+    HIP_TRY(hipGetLastError());
     return 0;
 }
 
@@ -1298,6 +1365,7 @@ int ccz_set_width(ccz_engine *e, void *stream, int32_t width)
         if (e->stop_on) return fail(-1, "ccz_set_width: not while the early stop is on (ccz_set_early_stop)");
         if (e->routed) return fail(-1, "ccz_set_width: not while routing is on (ccz_set_routing)");
         if (e->history_on) return fail(-1, "ccz_set_width: not while leaf history is on (ccz_set_leaf_history)");
+        if (e->spread_on) return fail(-1, "ccz_set_width: not while the value spread is on (ccz_set_value_stats): a virtual loss is no value");
     }
     hipStream_t s = (hipStream_t)stream;
     if (width == 1) {
@@ -1855,6 +1923,7 @@ int ccz_snapshot_save(ccz_engine *e, void *stream, void *blob_dev, uint64_t capa
     if (!blob_dev) return fail(-1, "ccz_snapshot_save: null blob");
     if ((uintptr_t)blob_dev & 15) return fail(-1, "ccz_snapshot_save: the blob must be 16-byte aligned");
     if (SCOUTS(e)) return fail(-1, "ccz_snapshot_save: not with scout slots (ccz_set_scouts): a scout slot has no game and no tree");
+    if (e->spread_on) return fail(-1, "ccz_snapshot_save: not while the value spread is on (ccz_set_value_stats): its array is no snapshot section yet");
     hipStream_t s = (hipStream_t)stream;
     uint64_t total = 0;
     if (const int rc = snap_prepare(e, s, "ccz_snapshot_save", &total)) return rc;
@@ -1882,6 +1951,7 @@ int ccz_snapshot_load(ccz_engine *e, void *stream, const void *blob_dev, uint64_
     if (!blob_dev) return fail(-1, "ccz_snapshot_load: null blob");
     if ((uintptr_t)blob_dev & 15) return fail(-1, "ccz_snapshot_load: the blob must be 16-byte aligned");
     if (SCOUTS(e)) return fail(-1, "ccz_snapshot_load: not with scout slots (ccz_set_scouts)");
+    if (e->spread_on) return fail(-1, "ccz_snapshot_load: not while the value spread is on (ccz_set_value_stats): its array is no snapshot section yet");
     hipStream_t s = (hipStream_t)stream;
     const Dev &d = e->d;
     const int B = d.B;

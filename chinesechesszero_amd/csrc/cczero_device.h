@@ -161,8 +161,17 @@ struct SurpriseBlock {
 constexpr uint32_t kProofWin = 1u, kProofLoss = 2u, kProofDraw = 3u;
 struct SolverCfg {
     int32_t enabled;  // 0: no kernel reads or writes a proof byte
-    int32_t pad;
+    int32_t spread;   // value spread (ccz_set_value_stats): 0: no kernel reads or writes an S. It rides in the solver's settings word
+                      // pair, so the kernels that test it load nothing they did not load before
     uint8_t *proof;   // [B][2][cap], indexed like nodeA / nodeB
+};
+// Value spread (ccz_set_value_stats): S, the running sum of squared deviations of the values backed up through a node, float32
+// [B][2][cap] indexed like nodeA / nodeB. The array is allocated by the first ccz_set_value_stats(1) and its pointer lies BEHIND the
+// solver's settings in the same allocation (Dev.sv_cfg points at the first member), as the surprise block lies behind the resignation
+// settings: Dev keeps its size and bytes, SolverCfg keeps its 16, and only code that runs with the option on loads the pointer.
+struct SolverBlock {
+    SolverCfg cfg; // written by k_set_solver (enabled, proof) and k_set_value_stats (spread) in stream order
+    float *S;      // written by k_set_value_stats
 };
 struct SolverBoardStats {
     unsigned long long proven, stops; // nodes whose byte left "unknown"; simulations that ended at a node proven before
@@ -281,6 +290,7 @@ struct BoundaryCfg {
     SurpriseBlock surprise;
 };
 __device__ __forceinline__ const SurpriseBlock *surprise_block(const Dev &D) { return &reinterpret_cast<const BoundaryCfg *>(D.rs_cfg)->surprise; }
+__device__ __forceinline__ float *spread_array(const Dev &D) { return reinterpret_cast<const SolverBlock *>(D.sv_cfg)->S; }
 __device__ __forceinline__ int plane_of(const Dev &D, int type) { return (int)((D.chanpack >> (3 * type)) & 7u); }
 __device__ __forceinline__ int type_in_plane(const Dev &D, int chan) { return (int)((D.typepack >> (3 * chan)) & 7u) + 1; }
 

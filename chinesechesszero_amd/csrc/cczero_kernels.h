@@ -39,6 +39,7 @@ __device__ __forceinline__ void fresh_root(const Dev &D, int b, int half)
     D.nodeB[base] = 0u;
     const SolverCfg sv = *D.sv_cfg;
     if (sv.enabled) sv.proof[base] = 0; // a fresh root is unproven
+    if (sv.spread) spread_array(D)[base] = 0.0f; // ... and has received no value
     D.path_len[b] = 0;
     D.leaf_status[b] = CCZ_LEAF_SKIP;
     D.move_sims[b] = 0; // a move boundary: the board's simulation budget (Dev.budget) starts over
@@ -261,6 +262,7 @@ __device__ __forceinline__ SolverCfg solver_cfg(const Dev &D)
 {
     SolverCfg sv = *D.sv_cfg;
     sv.enabled = __builtin_amdgcn_readfirstlane(sv.enabled);
+    sv.spread = __builtin_amdgcn_readfirstlane(sv.spread);
     return sv;
 }
 
@@ -1094,6 +1096,7 @@ __device__ inline TopPatch expand_backup_phase(const Dev &D, int r, int b, int l
     tp.active = false; tp.root_expanded = false; tp.kid_expanded = false; tp.k = 0; tp.first_id = 0; tp.n0 = 0; tp.rootN = 0;
     tp.rootQ = 0.0f; tp.node1 = -1; tp.N1 = 0; tp.Q1 = 0.0f; tp.has1 = false; tp.hasp1 = false; tp.p1 = 0u;
     const bool solver = sv.enabled != 0;
+    const bool spread = sv.spread != 0; // value spread (ccz_set_value_stats): wave-uniform; off: no S is read or written, nor its pointer
     // everything that does not depend on another load is requested first
     const int status = D.leaf_status[b];
     const int d = D.path_len[b];
@@ -1136,6 +1139,11 @@ __device__ inline TopPatch expand_backup_phase(const Dev &D, int r, int b, int l
                 if (lane < k) proof[CCZ_IDX(D, n0 + lane, D.cap)] = 0;
                 if (64 + lane < k) proof[CCZ_IDX(D, n0 + 64 + lane, D.cap)] = 0;
             }
+            if (spread) { // ... and have received no value
+                float *S = spread_array(D) + base;
+                if (lane < k) S[CCZ_IDX(D, n0 + lane, D.cap)] = 0.0f;
+                if (64 + lane < k) S[CCZ_IDX(D, n0 + 64 + lane, D.cap)] = 0.0f;
+            }
             tp.root_expanded = d == 0;
             tp.kid_expanded = d == 1;
             tp.n0 = n0;
@@ -1170,6 +1178,10 @@ __device__ inline TopPatch expand_backup_phase(const Dev &D, int r, int b, int l
         const float val = ((d - j) & 1) ? v : -v;
         const int n = A[node].N + 1;
         const float q = A[node].Q;
+        // value spread (wave-uniform; off: nothing is read): the node's S is requested in the round of its N and Q
+        float *Sn = nullptr;
+        float s_old = 0.0f;
+        if (spread) { Sn = spread_array(D) + base + node; s_old = *Sn; }
         // visits += 1 ; value += 1.0*(leaf_value - value)/visits   in float32 (mcts.py:68-71)
         float qn;
         if (D.flags & 4u) {
@@ -1181,9 +1193,16 @@ __device__ inline TopPatch expand_backup_phase(const Dev &D, int r, int b, int l
             dh = (float)(_Float16)(dh / (float)(_Float16)(float)n);
             qn = (float)(_Float16)(qh + dh);
         } else {
-            float delta = val - q;
-            delta = delta / (float)n;
+            const float d0 = val - q;
+            const float delta = d0 / (float)n;
             qn = q + delta;
+            // value spread: S <- S + (val - q) * (val - qn), Welford's sum of squared deviations, float32, no contraction; the node's
+            // S is its lane's, like N and Q, and is stored with them (a CCZ_FLAG_VALUE_F16 engine refuses the option)
+            if (spread) {
+                const float d1 = val - qn;
+                const float prod = d0 * d1;
+                *Sn = s_old + prod;
+            }
         }
         A[node].N = n;
         A[node].Q = qn;
@@ -2080,7 +2099,11 @@ __global__ __launch_bounds__(64) void k_finish_move(Dev D, const int32_t *forced
     const SolverCfg sv = *D.sv_cfg;
     const uint8_t *PO = sv.proof + ((size_t)b * 2 + rv.half) * (size_t)D.cap;
     uint8_t *PN = sv.proof + baseNew;
-    if (lane == 0) { D.nodeA[baseNew] = NodeA{0, 0.0f, 1.0f, -1}; D.nodeB[baseNew] = 0u; if (sv.enabled) PN[0] = 0; } // whatever happens below, the new half holds a valid (empty) tree
+    // value spread (off: the word that came with the solver's): a kept node's S moves with its records; a fresh root has S = 0
+    const float *SO = nullptr;
+    float *SN = nullptr;
+    if (sv.spread) { float *S = spread_array(D); SO = S + ((size_t)b * 2 + rv.half) * (size_t)D.cap; SN = S + baseNew; }
+    if (lane == 0) { D.nodeA[baseNew] = NodeA{0, 0.0f, 1.0f, -1}; D.nodeB[baseNew] = 0u; if (sv.enabled) PN[0] = 0; if (sv.spread) SN[0] = 0.0f; } // whatever happens below, the new half holds a valid (empty) tree
     const int want = forced ? forced[b] : -1;
     // A refused board neither records nor moves: position, clocks, history, ply and move counter stay. Its tree is the empty root just
     // written, so its pool accounting restarts with it (the host flips the half word for every board), and its pending leaf is dropped.
@@ -2269,6 +2292,7 @@ __global__ __launch_bounds__(64) void k_finish_move(Dev D, const int32_t *forced
             NA[0] = rv.A[CCZ_IDX(D, rv.root.fc + ci, D.cap)];
             NB[0] = rv.Bn[CCZ_IDX(D, rv.root.fc + ci, D.cap)];
             if (sv.enabled) PN[0] = PO[CCZ_IDX(D, rv.root.fc + ci, D.cap)];
+            if (sv.spread) SN[0] = SO[CCZ_IDX(D, rv.root.fc + ci, D.cap)];
         }
         __syncthreads();
         int head = 0, pruned = 0;
@@ -2304,6 +2328,7 @@ __global__ __launch_bounds__(64) void k_finish_move(Dev D, const int32_t *forced
                     NA[CCZ_IDX(D, dd + j, D.cap)] = rv.A[CCZ_IDX(D, src + j, D.cap)];
                     NB[CCZ_IDX(D, dd + j, D.cap)] = rv.Bn[CCZ_IDX(D, src + j, D.cap)];
                     if (sv.enabled) PN[CCZ_IDX(D, dd + j, D.cap)] = PO[CCZ_IDX(D, src + j, D.cap)];
+                    if (sv.spread) SN[CCZ_IDX(D, dd + j, D.cap)] = SO[CCZ_IDX(D, src + j, D.cap)];
                 }
             }
             const int nbatch = n_new - head < 64 ? n_new - head : 64;
@@ -2317,7 +2342,7 @@ __global__ __launch_bounds__(64) void k_finish_move(Dev D, const int32_t *forced
         }
     }
     if (!keep_tree || n_new == 0) {
-        if (lane == 0) { NA[0] = NodeA{0, 0.0f, 1.0f, -1}; NB[0] = 0u; if (sv.enabled) PN[0] = 0; }
+        if (lane == 0) { NA[0] = NodeA{0, 0.0f, 1.0f, -1}; NB[0] = 0u; if (sv.enabled) PN[0] = 0; if (sv.spread) SN[0] = 0.0f; }
         n_new = 1;
     }
 
@@ -3118,6 +3143,86 @@ __global__ __launch_bounds__(64) void k_root_proof(Dev D, uint8_t *state, uint8_
     }
 }
 
+// ------------------------------------------------------------------ value spread: settings, inspection, the LCB move
+// ccz_set_value_stats: the word and the array's pointer reach the device in stream order (the array is zeroed in front of this launch
+// when the option turns on). The solver's two members of the block are not touched; k_set_solver writes the word back as the host knows it.
+__global__ void k_set_value_stats(SolverBlock *blk, int32_t spread, float *S)
+{
+    if (blockIdx.x == 0 && threadIdx.x == 0) { blk->cfg.spread = spread; blk->S = S; }
+}
+
+// ccz_root_value_stats: S of the root's children, aligned with k_root_children's acts (zero past k), and of the root; zero rows for
+// a finished board and a slot past `active`
+__global__ __launch_bounds__(64) void k_root_value_stats(Dev D, int active, float *s_out, float *root_s)
+{
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const BoardMeta m = D.meta[b];
+    const SolverCfg sv = *D.sv_cfg;
+    const RootView rv = root_view(D, b);
+    int k = root_k(rv) > kMaxLegal ? kMaxLegal : root_k(rv);
+    const bool live = sv.spread && !m.over && b < active;
+    if (!live) k = 0;
+    const float *S = live ? spread_array(D) + ((size_t)b * 2 + rv.half) * (size_t)D.cap : nullptr;
+    if (lane == 0) root_s[b] = live ? S[0] : 0.0f;
+    for (int i = lane; i < kMaxLegal; i += 64) s_out[(size_t)b * kMaxLegal + i] = i < k ? S[CCZ_IDX(D, rv.root.fc + i, D.cap)] : 0.0f;
+}
+
+// ccz_lcb_moves (the rule in full: include/cczero.h, "Value spread and the LCB move"): one wave per board, children `lane` and
+// `64 + lane`; all arithmetic float64. moves / child: -1 for a finished board, a slot past `active`, a root without a visited child.
+__global__ __launch_bounds__(64) void k_lcb_moves(Dev D, int active, double z, double min_ratio, int min_visits, int32_t *moves_out,
+                                                    int32_t *child_out, double *lcb_out)
+{
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const BoardMeta m = D.meta[b];
+    const SolverCfg sv = *D.sv_cfg;
+    const RootView rv = root_view(D, b);
+    int k = root_k(rv) > kMaxLegal ? kMaxLegal : root_k(rv);
+    const bool live = sv.spread && !m.over && b < active;
+    if (!live) k = 0;
+    const float *S = live ? spread_array(D) + ((size_t)b * 2 + rv.half) * (size_t)D.cap : nullptr;
+    const double ninf = -__builtin_huge_val();
+    int N[2];
+    double lcb[2];
+    bool in[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int i = 64 * h + lane;
+        in[h] = i < k;
+        N[h] = 0;
+        lcb[h] = ninf;
+        if (in[h]) {
+            const NodeA c = rv.A[CCZ_IDX(D, rv.root.fc + i, D.cap)];
+            const double s = (double)S[CCZ_IDX(D, rv.root.fc + i, D.cap)];
+            N[h] = c.N;
+            if (c.N >= 2) {
+                const double var = (s > 0.0 ? s : 0.0) / (double)(c.N - 1);
+                const double se = sqrt(var / (double)c.N);
+                const double zs = z * se;
+                lcb[h] = (double)c.Q - zs;
+            }
+        }
+        if (lcb_out) lcb_out[(size_t)b * kMaxLegal + i] = in[h] ? lcb[h] : 0.0;
+    }
+    const int best = gumbel_first_max((double)N[0], in[0], (double)N[1], in[1], lane); // i*: the first index of maximal N
+    const int nmax = wave_max_i32(N[0] > N[1] ? N[0] : N[1]);
+    int choice = -1;
+    if (best >= 0 && nmax > 0) {
+        bool el[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const double need = min_ratio * (double)nmax;
+            el[h] = in[h] && (64 * h + lane == best || (N[h] >= 2 && N[h] >= min_visits && (double)N[h] >= need));
+            el[h] = el[h] && lcb[h] > ninf; // a bound of -inf is never chosen over i*: if nothing is left, i* it is
+        }
+        choice = gumbel_first_max(lcb[0], el[0], lcb[1], el[1], lane);
+        if (choice < 0) choice = best;
+    }
+    if (lane == 0) {
+        moves_out[b] = choice >= 0 ? (int32_t)(rv.Bn[CCZ_IDX(D, rv.root.fc + choice, D.cap)] & 0xffffu) : -1;
+        if (child_out) child_out[b] = choice;
+    }
+}
+
 // ccz_proof_combine: one wave per case, proof_combine on bytes[case][0 .. counts[case])
 __global__ __launch_bounds__(64) void k_proof_combine(const uint8_t *bytes, const int32_t *counts, int n, uint8_t *out)
 {
@@ -3269,7 +3374,7 @@ __global__ __launch_bounds__(64 * NW) void k_wide(Dev D, WideArgs wa, const floa
     if (w == 0) {
         if (lane < 64) { s_depth[lane] = -1; s_undo[lane] = 0; }
         SolverCfg sv;
-        sv.enabled = 0; sv.pad = 0; sv.proof = nullptr;
+        sv.enabled = 0; sv.spread = 0; sv.proof = nullptr; // (both refuse a width above 1)
         int sims = D.move_sims[r];
         // ---- phase A: the pending slots are backed up in slot order
         if (backup) {

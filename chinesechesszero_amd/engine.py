@@ -682,6 +682,47 @@ class SelfPlayEngine:
         check(self.L.ccz_get_solver_stats(self.h, self._stream(), C.byref(s)))
         return {f: int(getattr(s, f)) for f, _ in _lib.SolverStats._fields_}
 
+    # ------------------------------------------------------------------ value spread and the LCB move (include/cczero.h ccz_set_value_stats)
+    def set_value_stats(self, enabled: bool = True):
+        """Every tree node also keeps S, the running sum of squared deviations of the values backed up through it (Welford, float32:
+        ``S += (val - q) * (val - q_new)`` in the backup), which is what :meth:`lcb_moves` needs. S never feeds back into the search:
+        N, Q, P, leaves, moves and records are bit for bit what they are without it. The first call that turns it on allocates four
+        bytes per tree node and may sync; turning it on again starts from zeros. Off (the state of a new engine): every launch is
+        what it is without the feature. Not with a width above 1, not on a ``value_f16`` engine, and no snapshot while it is on."""
+        with torch.cuda.device(self.device):
+            check(self.L.ccz_set_value_stats(self.h, self._stream(), 1 if enabled else 0))
+        self.value_stats = bool(enabled)
+
+    def get_value_stats(self) -> bool:
+        """The setting as the engine holds it (``ccz_get_value_stats``)."""
+        v = C.c_int32(0)
+        check(self.L.ccz_get_value_stats(self.h, C.byref(v)))
+        return bool(v.value)
+
+    def root_value_stats(self) -> dict:
+        """S at the top of every tree (``ccz_root_value_stats``; syncs): ``S`` float32 [B,128] of the root's children, aligned with
+        ``root_children()['acts']`` (zero past k), and ``root_S`` float32 [B]. Zero rows for finished boards and scout slots. The
+        sample variance of child i is ``max(S_i, 0) / (N_i - 1)``. Fails while the option is off."""
+        out = {"S": np.zeros((self.B, MAX_LEGAL), np.float32), "root_S": np.zeros(self.B, np.float32)}
+        check(self.L.ccz_root_value_stats(self.h, self._stream(), _ptr(out["S"]), _ptr(out["root_S"])))
+        return out
+
+    def lcb_moves(self, z: float, min_visit_ratio: float, min_visits: int, with_bounds: bool = False):
+        """The lower-confidence-bound move of every board (``ccz_lcb_moves``; the rule in full is in include/cczero.h): among the
+        root's children searched enough -- ``N >= max(2, min_visits)`` and ``N >= min_visit_ratio * N_max``, and always the most
+        visited one -- the one of largest ``Q - z * sqrt(var / N)``. Returns ``moves`` int32 [B] on the device (-1: finished board,
+        scout slot, nothing visited): what :meth:`finish_move` takes as ``forced_moves``. No host sync. ``with_bounds``: a dict
+        ``moves`` / ``child`` int32 [B] and ``lcb`` float64 [B,128] (-inf: no bound; 0 past k), on the device."""
+        if not hasattr(self, "_lcb_moves"):
+            self._lcb_moves = torch.empty((self.B,), dtype=torch.int32, device=self.device)
+            self._lcb_child = torch.empty((self.B,), dtype=torch.int32, device=self.device)
+        lcb = torch.empty((self.B, MAX_LEGAL), dtype=torch.float64, device=self.device) if with_bounds else None
+        check(self.L.ccz_lcb_moves(self.h, self._stream(), float(z), float(min_visit_ratio), int(min_visits), _ptr(self._lcb_moves),
+                                   _ptr(self._lcb_child), _ptr(lcb)))
+        if with_bounds:
+            return {"moves": self._lcb_moves, "child": self._lcb_child, "lcb": lcb}
+        return self._lcb_moves
+
     def _to_dev(self, x, dtype, name):
         t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x, dtype={torch.int32: np.int32, torch.uint8: np.uint8}[dtype]))
         t = t.to(device=self.device, dtype=dtype).contiguous()

@@ -13,19 +13,20 @@ import numpy as np
 
 from .boundary import deliver, kind_of
 from .engine import SelfPlayEngine
-from .options import SearchOptions, proven_moves, search_move
+from .options import SearchOptions, lcb_moves, proven_moves, search_move
 from .parameters import C_PUCT
 from .stopcfg import StopPoll
 
 
 class BatchedMatch:
     def __init__(self, evaluator_red, evaluator_black, n_boards: int, n_playout: int = 400, c_puct: float = C_PUCT,
-                 seed: int = 0, device: int = 0, max_plies: int = 0, temp: float = 1e-3, solver: bool = False, search=None, early_stop=None):
+                 seed: int = 0, device: int = 0, max_plies: int = 0, temp: float = 1e-3, solver: bool = False, search=None, early_stop=None, lcb=None):
         """``solver`` / ``search`` / ``early_stop``: the engine options (``options.OPTIONS``: what ``engine.set_solver`` / ``set_search`` /
         ``set_early_stop`` take; None / False: off), for both sides alike. With the solver the proven move is played where the root is decided
-        (``options.proven_moves``); with the early stop the move's loop ends when no board would select any more (``options.search_move``)."""
-        self.options = o = SearchOptions(n_playout, solver=solver, search=search, early_stop=early_stop)
-        self.solver, self.search_cfg, self.early_stop = o.keywords().values()
+        (``options.proven_moves``); with the early stop the move's loop ends when no board would select any more (``options.search_move``).
+        ``lcb``: both sides play the LCB move (``options.MOVE_OPTIONS``) instead of the most visited one; a proven move wins over it."""
+        self.options = o = SearchOptions(n_playout, solver=solver, search=search, early_stop=early_stop, lcb=lcb)
+        self.solver, self.search_cfg, self.early_stop, self.lcb = o.keywords().values()
         self.ev = {1: evaluator_red, 0: evaluator_black}
         self.B = n_boards
         self.n_playout = n_playout
@@ -50,6 +51,8 @@ class BatchedMatch:
             self.before_move(self)
         forced, proven = proven_moves(e, self.solver)
         self.proven_moves += proven
+        if self.lcb is not None:
+            forced, _ = lcb_moves(e, self.lcb, forced, counts=self.options.lcb_counts)
         moves = e.finish_move(forced_moves=forced, temps=self._temps, keep_tree=False).cpu().numpy()
         if self.on_move is not None:
             self.on_move(self, moves)

@@ -71,8 +71,10 @@ SCOUTS = 10  # scout slots of a one-game search (ScoutedSearch): 1 + 10 = 11 row
 
 class MCTS:
     def __init__(self, policy_value_fn, c_puct=5, n_playout=10000, device: int = 0, seed: int = 0, scouts: int | None = None,
-                 solver: bool = False, search=None, width: int | None = None):
-        """``width``: None / 1 (default): the sequential search, scouted as below. 2..64: the wide search (``wide.WideSearch``): up to
+                 solver: bool = False, search=None, width: int | None = None, lcb=None):
+        """``lcb``: keep the value spread of every node (``SelfPlayEngine.set_value_stats``) so that :meth:`lcb_move` can name the
+        lower-confidence-bound move (``options.MOVE_OPTIONS``: True, a multiple z of the standard error, or a dict); not with ``width`` > 1.
+        ``width``: None / 1 (default): the sequential search, scouted as below. 2..64: the wide search (``wide.WideSearch``): up to
         ``width`` leaves of the tree per evaluator call, kept apart by virtual loss -- another tree than the reference's; needs a
         batched evaluator that returns logits, and excludes ``scouts`` > 0, ``solver`` and ``search`` (ValueError).
         ``search``: a dict of ``SelfPlayEngine.set_search``'s arguments (first-play urgency, visit-scaled c_puct). Scout slots rest
@@ -86,8 +88,8 @@ class MCTS:
         self.width = 1 if width is None else int(width)
         if not 1 <= self.width <= 64:
             raise ValueError(f"width must be in 1..64 (got {width})")
-        self.options = SearchOptions(n_playout, width=self.width, solver=solver, search=search)
-        self.solver, self.search_cfg = self.options.keywords().values()
+        self.options = SearchOptions(n_playout, width=self.width, solver=solver, search=search, lcb=lcb)
+        self.solver, self.search_cfg, self.lcb = self.options.keywords().values()
         if self.width > 1 and scouts:
             raise ValueError("width > 1 (the wide search) excludes scouts")
         self._wide = None
@@ -297,16 +299,27 @@ class MCTS:
         return proof_move(rp["state"][0], rp["dist"][0], rp["child_state"][0], rp["child_dist"][0], rc["acts"][0])
 
 
+    def lcb_move(self):
+        """The move id the LCB rule plays at the root (``SelfPlayEngine.lcb_moves`` with this search's ``lcb`` settings), or None:
+        the option is off, nothing was searched, or the game is over."""
+        if self.lcb is None or self._engine is None:
+            return None
+        mv = int(self._engine.lcb_moves(self.lcb["z"], self.lcb["min_visit_ratio"], self.lcb["min_visits"])[0].item())
+        return mv if mv >= 0 else None
+
+
 class MCTS_AI:
     """reference mcts.py:181-233"""
 
     def __init__(self, policy_value_fn, c_puct=5, n_playout=2000, is_selfplay=False, device: int = 0, seed: int = 0, scouts: int | None = None,
-                 solver: bool = False, search=None, width: int | None = None):
-        """``width``: as in :class:`MCTS` (None / 1: the scouted sequential search; 2..64: the wide search).
+                 solver: bool = False, search=None, width: int | None = None, lcb=None):
+        """``lcb``: as in :class:`MCTS`; a match player (``is_selfplay`` False) then plays :meth:`MCTS.lcb_move` instead of drawing from
+        the visit counts at temperature ``temp`` (a proven move wins over it; the self-play branch is untouched).
+        ``width``: as in :class:`MCTS` (None / 1: the scouted sequential search; 2..64: the wide search).
         ``search``: as in :class:`MCTS` (with it, ``scouts`` None means 0 and ``scouts`` > 0 raises ValueError).
         ``solver``: search with the MCTS-solver and play the proven move when the root is decided (the fastest mate, the longest
         defence) instead of drawing from the visit counts."""
-        self.mcts = MCTS(policy_value_fn, c_puct, n_playout, device=device, seed=seed, scouts=scouts, solver=solver, search=search, width=width)
+        self.mcts = MCTS(policy_value_fn, c_puct, n_playout, device=device, seed=seed, scouts=scouts, solver=solver, search=search, width=width, lcb=lcb)
         self.is_selfplay = is_selfplay
         self.agent = "AI"
 
@@ -329,7 +342,8 @@ class MCTS_AI:
             move = np.random.choice(acts, p=(1 - EPS) * probs + EPS * np.random.dirichlet(ALPHA * np.ones(len(probs))))
             self.mcts.update_with_move(move)
         else:
-            move = np.random.choice(acts, p=probs)
+            lcb = self.mcts.lcb_move()
+            move = np.random.choice(acts, p=probs) if lcb is None else lcb
             self.mcts.update_with_move(-1)
         if return_prob:
             return move, move_probs

@@ -5,7 +5,7 @@ what, call the setters in one order, report. Also the command line of resign / r
 option: ``ccz_set_x`` on the C side (which refuses what it excludes), the setter in ``engine.py``, ONE entry in ``OPTIONS`` (and a rule
 in ``SearchOptions.__init__`` if it excludes another), the keyword on the front ends that allow it. ``RECORD_OPTIONS`` holds, in the same
 shape, what decides how a recorded game is trained on (policy surprise weighting), ``INPUT_OPTIONS`` what decides the evaluator's input (leaf
-history planes); ``SearchOptions`` handles the three tables alike."""
+history planes), ``MOVE_OPTIONS`` what decides which move is played after the search (the LCB move); ``SearchOptions`` handles the four tables alike."""
 from __future__ import annotations
 
 from collections import namedtuple
@@ -16,6 +16,10 @@ from .stopcfg import stop_report
 RESIGN_MOVES, RESIGN_MIN_PLY, RESIGN_PLAYON, FORCED_PLAYOUTS = 2, 30, 0.1, 2.0
 GUMBEL_CONSIDERED, GUMBEL_C_VISIT, GUMBEL_C_SCALE = 16, 50.0, 1.0
 SURPRISE_WEIGHT, SURPRISE_CAP = 0.5, 8.0
+# The LCB move's defaults are KataGo's published lcbStdevs = 5.0 and minVisitPropForLCB = 0.15, with at least two visits (below that a child
+# has no sample variance). They are conventions taken from that engine, NOT measurements of this one: no trained weights exist here to measure
+# strength with (arena --a X --b X --lcb --lcb-side a is the experiment).
+LCB_STDEVS, LCB_MIN_VISIT_RATIO, LCB_MIN_VISITS = 5.0, 0.15, 2
 
 
 # ---------------------------------------------------------------------- fragments of the collector's periodic log line
@@ -80,7 +84,8 @@ def engine_stop_report(e) -> dict:
 # ``setter``: the SelfPlayEngine method that takes the option's dict; ``what``: its name in messages; ``log(engine)``: its fragment of the log
 # line; ``report(engine)``: its entries in the JSON of Arena.result / BatchedAnalysis.summary (None: none); ``of_scalar``: the dict of a value
 # that is not one; ``device_only``: why it needs sampling='device' (None: it does not); ``one_game``: it also runs in the collector's one-game loop
-Option = namedtuple("Option", "setter what log report of_scalar device_only one_game", defaults=(None, dict, None, False))
+# ``setter_args(cfg)``: the setter's keywords when they are not the option's dict itself (None: they are)
+Option = namedtuple("Option", "setter what log report of_scalar device_only one_game setter_args", defaults=(None, dict, None, False, None))
 SOLVER_LOG = ", nodes proven {nodes_proven}, simulations ended at a proven node {proven_stops}, roots proven {roots_proven}"
 STOP_LOG = ", early stops {single_reply} single reply / {visit_gap} gap / {kld_gain} kld, {mean_sims_per_move} simulations per move"
 
@@ -128,7 +133,27 @@ INPUT_OPTIONS = {
     "leaf_history": Option("set_leaf_history", "leaf history planes", lambda e: format_history(e.stats()),
                            report=lambda e: history_report(e.stats()), of_scalar=lambda x: {"enabled": True}),
 }
-ALL_OPTIONS = {**OPTIONS, **RECORD_OPTIONS, **INPUT_OPTIONS}
+
+
+def format_lcb(c: dict) -> str:
+    share = f"{c['differed'] / c['moves']:.4f}" if c["moves"] else "n/a"
+    return f", lcb moves {c['moves']}, off the most visited move {c['differed']} (share {share})"
+
+
+def _lcb_of_scalar(x):
+    return {"z": LCB_STDEVS if x is True else float(x), "min_visit_ratio": LCB_MIN_VISIT_RATIO, "min_visits": LCB_MIN_VISITS}
+
+
+# What decides which move is PLAYED after the search (the search itself is untouched): applied and reported after the tables above, before the
+# input options. The engine's side of it is the value spread S per node (``set_value_stats``); the rule's numbers stay on the host and go to
+# ``SelfPlayEngine.lcb_moves`` at every move (:func:`lcb_moves`). Its log and report take the front end's own counters
+# (``SearchOptions.lcb_counts``: moves played by the rule, and how many of them were not the most visited move), not the engine.
+MOVE_OPTIONS = {
+    "lcb": Option("set_value_stats", "the LCB move", lambda c: format_lcb(c), report=lambda c: {"lcb": dict(c)},
+                  of_scalar=_lcb_of_scalar, device_only="with host sampling every move is drawn on the host, and the LCB move is a forced one",
+                  one_game=True, setter_args=lambda cfg: {"enabled": True}),
+}
+ALL_OPTIONS = {**OPTIONS, **RECORD_OPTIONS, **MOVE_OPTIONS, **INPUT_OPTIONS}
 
 
 class SearchOptions:
@@ -161,6 +186,14 @@ class SearchOptions:
             raise ValueError("the early stop (--stop-*) and the Gumbel root search (--gumbel) exclude each other: sequential halving plans the whole budget")
         if int(width) > 1 and any(name in on for name in ("solver", "search", "early_stop")):
             raise ValueError("width > 1 (the wide search) excludes scouts, the solver, the search parameters and the early stop")
+        if "lcb" in on:
+            on["lcb"] = make_lcb(**{"z": True, **on["lcb"]})   # (a dict may leave the defaults out; the numbers are checked here)
+            self.lcb = on["lcb"]
+            self.lcb_counts = {"moves": 0, "differed": 0}   # what :func:`lcb_moves` is handed as ``counts``
+        if "lcb" in on and "gumbel" in on:
+            raise ValueError("lcb and gumbel (--lcb, --gumbel) exclude each other: the Gumbel rule plays its own move")
+        if "lcb" in on and int(width) > 1:
+            raise ValueError("width > 1 (the wide search) excludes lcb: a virtual loss is no value, the spread of a wide search is a follow-up")
         if int(width) > 1 and "leaf_history" in on:
             raise ValueError("width > 1 (the wide search) excludes leaf history planes: a wide step's leaves are not replayed one path each")
 
@@ -170,18 +203,20 @@ class SearchOptions:
 
     def apply(self, engine):
         """Call the setters of the options that are on, and no others: resign, root exploration, gumbel, solver, search, early stop, surprise,
-        leaf history.
+        lcb (the value spread), leaf history.
         Every setter writes its own settings block only, so the order decides nothing."""
         for name, cfg in self.on.items():
-            getattr(engine, ALL_OPTIONS[name].setter)(**cfg)
+            o = ALL_OPTIONS[name]
+            getattr(engine, o.setter)(**(cfg if o.setter_args is None else o.setter_args(cfg)))
 
     def report(self, engine) -> dict:
         """The entries of the options that are on in a front end's JSON result (syncs)."""
-        return {k: v for name in self.on if ALL_OPTIONS[name].report for k, v in ALL_OPTIONS[name].report(engine).items()}
+        return {k: v for name in self.on if ALL_OPTIONS[name].report
+                for k, v in ALL_OPTIONS[name].report(self.lcb_counts if name == "lcb" else engine).items()}
 
     def log_line(self, engine) -> str:
         """The fragments of the options that are on, for the collector's periodic log line (empty with none on; syncs)."""
-        return "".join(ALL_OPTIONS[name].log(engine) for name in self.on)
+        return "".join(ALL_OPTIONS[name].log(self.lcb_counts if name == "lcb" else engine) for name in self.on)
 
 
 # ---------------------------------------------------------------------- the move of an arg-max front end
@@ -203,6 +238,34 @@ def proven_moves(engine, solver: bool, over=None):
     forced = engine.proof_moves()
     forced[(engine.game_status()["over"] if over is None else over) != 0] = -1
     return forced, int((forced >= 0).sum())
+
+
+def lcb_moves(engine, cfg, forced, over=None, allow=None, counts=None, detail: bool = False):
+    """The LCB move of every running game whose entry of ``forced`` is still -1 (a proven move wins over it), after a search with the value
+    spread on. ``cfg``: the ``lcb`` dict of :class:`SearchOptions` (None: off, ``forced`` comes back as it is); ``forced``: int32 [B] numpy, or
+    None (all -1); ``allow``: bool [B], the boards whose mover plays the LCB move (None: all); ``counts``: the front end's ``{"moves", "differed"}`` (``SearchOptions.lcb_counts``),
+    moved in place. Returns ``(forced, how many of the moves filled in are not the arg-max move)``; with ``detail`` also the two bool [B] masks (filled,
+    filled and not the arg-max move). One launch, one read of the root children. Syncs."""
+    if cfg is None:
+        return (forced, 0, None, None) if detail else (forced, 0)
+    import numpy as np
+    out = engine.lcb_moves(cfg["z"], cfg["min_visit_ratio"], cfg["min_visits"], with_bounds=True)
+    moves, child = out["moves"].cpu().numpy(), out["child"].cpu().numpy()
+    over = engine.game_status()["over"] if over is None else over
+    if forced is None:
+        forced = np.full(engine.B, -1, np.int32)
+    rc = engine.root_children()
+    fill = (forced < 0) & (np.asarray(over) == 0) & (moves >= 0)
+    if allow is not None:
+        fill &= np.asarray(allow, bool)
+    star = rc["visits"].argmax(axis=1)          # the first index of maximal N: the arg-max player's move
+    off = fill & (child != star)
+    differed = int(off.sum())
+    forced[fill] = moves[fill]
+    if counts is not None:
+        counts["moves"] += int(fill.sum())
+        counts["differed"] += differed
+    return (forced, differed, fill, off) if detail else (forced, differed)
 
 
 # ---------------------------------------------------------------------- command lines: make_x (ValueError), add_x_args, x_from_args (ap.error)
@@ -345,3 +408,34 @@ def add_surprise_args(ap):
 def surprise_from_args(ap, a):
     return _from_args(ap, a, "--surprise-weight", "policy surprise weighting is off", ("--surprise-cap",), make_surprise, a.surprise_weight,
                       a.surprise_cap)
+
+
+def make_lcb(z, min_visit_ratio=None, min_visits=None):
+    """The ``lcb`` dict of the front ends (None when ``z`` is None or False): ``z`` True = the default multiple of the standard error.
+    ValueError: what ``ccz_lcb_moves`` refuses."""
+    if z is None or z is False:
+        return None
+    z = LCB_STDEVS if z is True else float(z)
+    if not 0.0 <= z < float("inf"):
+        raise ValueError(f"--lcb must be finite and >= 0 (got {z})")
+    if min_visit_ratio is not None and not 0.0 <= min_visit_ratio <= 1.0:
+        raise ValueError(f"--lcb-min-visit-ratio must be in [0, 1] (got {min_visit_ratio})")
+    if min_visits is not None and not min_visits >= 0:
+        raise ValueError(f"--lcb-min-visits must be >= 0 (got {min_visits})")
+    return {"z": z, "min_visit_ratio": LCB_MIN_VISIT_RATIO if min_visit_ratio is None else float(min_visit_ratio),
+            "min_visits": LCB_MIN_VISITS if min_visits is None else int(min_visits)}
+
+
+def add_lcb_args(ap):
+    """--lcb [Z] / --lcb-min-visit-ratio / --lcb-min-visits."""
+    ap.add_argument("--lcb", type=float, nargs="?", const=True, default=None, metavar="Z", help="play the lower-confidence-bound move instead of "
+                    "the most visited one: among the root's children searched enough, the one of largest Q - Z * standard error of its backed-up "
+                    f"values (default Z = {LCB_STDEVS:g}, KataGo's lcbStdevs: a convention, not a measurement of this engine); absent = off")
+    ap.add_argument("--lcb-min-visit-ratio", type=float, default=None, metavar="R", help="... a child is considered from this share of the most "
+                    f"visited child's visits, in [0, 1] (default {LCB_MIN_VISIT_RATIO:g}, KataGo's minVisitPropForLCB)")
+    ap.add_argument("--lcb-min-visits", type=int, default=None, metavar="N", help=f"... and from this many visits (default {LCB_MIN_VISITS})")
+
+
+def lcb_from_args(ap, a):
+    return _from_args(ap, a, "--lcb", "the LCB move is off", ("--lcb-min-visit-ratio", "--lcb-min-visits"), make_lcb, a.lcb,
+                      a.lcb_min_visit_ratio, a.lcb_min_visits)

@@ -3,7 +3,8 @@
 The reference's README (README.md:3) advertises "standard UCI protocol" but ships no loop; what it does
 use everywhere are UCI coordinate strings ("a0a1", tools.py:172-269). This is that missing loop:
 ``uci``, ``isready``, ``ucinewgame``, ``position startpos|fen <fen> [moves ...]``, ``go [nodes N]``,
-``setoption name Playouts|MultiPV value N``, ``setoption name Solver value true|false`` (MCTS-solver: ``score mate N``), ``d``, ``quit``. ``go`` reports one ``info depth .. multipv .. score cp .. nodes .. pv ..``
+``setoption name Playouts|MultiPV value N``, ``setoption name Solver value true|false`` (MCTS-solver: ``score mate N``), ``setoption name LCB value true|false`` (``bestmove`` is the
+lower-confidence-bound move; ``LCBStdevs`` / ``LCBMinVisitRatio``: its numbers; the ``info`` lines stay as they are), ``d``, ``quit``. ``go`` reports one ``info depth .. multipv .. score cp .. nodes .. pv ..``
 line per principal variation (``SelfPlayEngine.principal_variations``); ``cp`` is a display mapping of the first move's Q
 (``analyse.cp_of``). The search is ``MCTS_AI`` on the HIP engine (no CPU fallback).
 """
@@ -79,6 +80,8 @@ class UciLoop:
         self.multipv = 1
         self.solver = False
         self.width = 1               # Width: leaves per evaluator call (1: the sequential, scouted search)
+        self.lcb = False             # LCB: bestmove is the lower-confidence-bound move (LCBStdevs / LCBMinVisitRatio: its numbers)
+        self.lcb_opts = {}
         self.search_opts = {}        # FpuReduction / FpuAbsolute / CpuctBase / CpuctFactor as set; empty: the reference's PUCT
 
     def _search(self):
@@ -86,6 +89,11 @@ class UciLoop:
         from .searchcfg import make_search
         o = self.search_opts
         return make_search(o.get("fpureduction"), o.get("fpuabsolute"), None, None, o.get("cpuctbase"), o.get("cpuctfactor"))
+
+    def _lcb(self):
+        """The ``lcb`` dict of ``MCTS_AI`` for the options set so far (None: off)."""
+        from .options import make_lcb
+        return make_lcb(self.lcb_opts.get("lcbstdevs", True), self.lcb_opts.get("lcbminvisitratio")) if self.lcb else None
 
     def _set(self, **new) -> bool:
         """Set ``solver`` / ``width`` / ``search_opts`` if they still go together (``SearchOptions``); else say why not and leave all as it was."""
@@ -95,7 +103,7 @@ class UciLoop:
             self.width = int(self.width)
             if not 1 <= self.width <= 64:
                 raise ValueError(f"Width {self.width} must be in 1..64")
-            SearchOptions(self.n_playout, width=self.width, solver=self.solver, search=self._search())
+            SearchOptions(self.n_playout, width=self.width, solver=self.solver, search=self._search(), lcb=self._lcb())
         except ValueError as e:
             vars(self).update(old)
             self._say(f"info string error {e}")
@@ -110,11 +118,11 @@ class UciLoop:
         if self.policy_value_fn is None:
             from .net import PolicyValueNet
             self.policy_value_fn = PolicyValueNet(device=f"cuda:{self.device}").policy_value_fn
-        search = self._search()
-        if self.ai is None or self.ai.mcts.n_playout != nodes or self.ai.mcts.solver != self.solver or self.ai.mcts.search_cfg != search \
+        search, lcb = self._search(), self._lcb()
+        if self.ai is None or self.ai.mcts.lcb != lcb or self.ai.mcts.n_playout != nodes or self.ai.mcts.solver != self.solver or self.ai.mcts.search_cfg != search \
                 or self.ai.mcts.width != self.width:
             self.ai = MCTS_AI(self.policy_value_fn, c_puct=C_PUCT, n_playout=nodes, is_selfplay=False, device=self.device, solver=self.solver,
-                              search=search, width=self.width)
+                              search=search, width=self.width, lcb=lcb)
         return self.ai
 
     def _say_pvs(self, ai):
@@ -154,6 +162,9 @@ class UciLoop:
             self._say("option name MultiPV type spin default 1 min 1 max 128")
             self._say("option name Solver type check default false")
             self._say("option name Width type spin default 1 min 1 max 64")
+            self._say("option name LCB type check default false")
+            self._say("option name LCBStdevs type string default 5")
+            self._say("option name LCBMinVisitRatio type string default 0.15")
             self._say("option name FpuReduction type string default <empty>")
             self._say("option name FpuAbsolute type string default <empty>")
             self._say("option name CpuctBase type string default <empty>")
@@ -167,6 +178,13 @@ class UciLoop:
             self.multipv = max(1, min(128, int(tok[4])))
         elif cmd == "setoption" and len(tok) >= 5 and tok[1] == "name" and tok[2].lower() == "solver":
             self._set(solver=tok[4].lower() == "true")
+        elif cmd == "setoption" and len(tok) >= 5 and tok[1] == "name" and tok[2].lower() == "lcb":
+            self._set(lcb=tok[4].lower() == "true")
+        elif cmd == "setoption" and len(tok) >= 5 and tok[1] == "name" and tok[2].lower() in ("lcbstdevs", "lcbminvisitratio"):
+            try:
+                self._set(lcb_opts=dict(self.lcb_opts, **{tok[2].lower(): float(tok[4])}))
+            except ValueError as e:
+                self._say(f"info string error {e}")
         elif cmd == "setoption" and len(tok) >= 5 and tok[1] == "name" and tok[2].lower() == "width":
             self._set(width=tok[4])
         elif cmd == "setoption" and len(tok) >= 5 and tok[1] == "name" and tok[2].lower() in ("fpureduction", "fpuabsolute", "cpuctbase", "cpuctfactor"):

@@ -698,6 +698,43 @@ int ccz_root_proof(ccz_engine *e, void *stream, uint8_t *state_host, uint8_t *di
 int ccz_get_solver_stats(ccz_engine *e, void *stream, ccz_solver_stats *out);
 int ccz_proof_combine(void *stream, const uint8_t *bytes_dev, const int32_t *counts_dev, int32_t n_cases, uint8_t *out_dev);
 
+/* ---- Value spread and the LCB move: what decides the move a match player plays (additive to ABI 9) --------------------------------------
+ * A node stores {N, Q, P, first_child}; with this option it also has S, the running sum of squared deviations of the values backed up
+ * through it (Welford), in a device array of its own (float32 [B][2][max_nodes], indexed like the node records; allocated and zeroed
+ * by the first ccz_set_value_stats(enabled = 1), which may sync; never touched while the option is off).
+ *   backup: with val the value applied to a path node, q its Q and n = N + 1 as the backup forms them, all float32, no contraction:
+ *       d0 = val - q;  qn = q + d0 / (float)n;        (the incremental mean, unchanged)
+ *       S  = S + d0 * (val - qn);                     (one multiply, one add)
+ *     in every stepping sequence (ccz_step[_compact], ccz_expand_backup[_compact], ccz_scouted_run with either loop).
+ *   expansion writes S = 0 for the new children; the re-root of ccz_finish_move copies a kept node's S with its records, pruned or
+ *     not (the new root's S is the chosen child's); a fresh root (ccz_reset, ccz_reset_tree, keep_tree = 0, ccz_set_position[s], a
+ *     refused move) has S = 0. ccz_set_value_stats(1) after ccz_set_value_stats(0) starts from an all-zero array.
+ * S never feeds back into the search: with the option on, N, Q, P, leaves, moves and records are bit for bit what they are with it
+ * off. Works with scout slots (a scout slot has no tree) and with the solver.
+ * Refused, in either call order: a width above 1 (a virtual loss is no value), a CCZ_FLAG_VALUE_F16 engine (the float16 running mean
+ * has no stated S), ccz_snapshot_save / _load while the option is on (the array is no snapshot section yet).
+ * ccz_get_value_stats: the host's word; no sync.
+ * ccz_root_value_stats (syncs; fails while the option is off): S of every root's children (float32 [B][128], aligned with
+ * ccz_root_children's acts, zero past k) and of the root (float32 [B]); zero rows for finished boards and scout slots. Either may be NULL.
+ * ccz_lcb_moves (asynchronous; fails while the option is off): the lower-confidence-bound move of every board, one wave per board,
+ * all arithmetic float64 with IEEE / and sqrt. For the root's child i with visits N_i, stored value Q_i (already in the view of the
+ * root's side to move) and S_i:
+ *     N_i >= 2:  var_i = max((double)S_i, 0) / (N_i - 1);   lcb_i = (double)Q_i - z * sqrt(var_i / N_i)
+ *     N_i <  2:  lcb_i = -inf
+ *   i* = the first index of maximal N (the move an arg-max player plays); i* is always eligible; another child is eligible iff
+ *   N_i >= 2 and N_i >= min_visits and (double)N_i >= min_visit_ratio * (double)N_max. The move is the eligible child of maximal lcb,
+ *   ties to the lowest index; if every eligible bound is -inf the move is i*. So z = 0 plays the eligible child of highest Q, and
+ *   min_visit_ratio = 1 plays i* unless another child ties its visits.
+ *   moves_out_dev int32 [B]: the move id; child_out_dev int32 [B] (or NULL): the child index; lcb_out_dev float64 [B][128] (or NULL):
+ *   every child's bound, -inf where it has none, 0 past k. A finished board, a root without a visited child and a scout slot: -1 / -1
+ *   (a finished board's and a scout slot's row of bounds is all zero).
+ *   Arguments refused: z not finite or < 0, min_visit_ratio outside [0, 1], min_visits < 0. */
+int ccz_set_value_stats(ccz_engine *e, void *stream, int32_t enabled);
+int ccz_get_value_stats(ccz_engine *e, int32_t *enabled_out);
+int ccz_root_value_stats(ccz_engine *e, void *stream, float *s_host, float *root_s_host);
+int ccz_lcb_moves(ccz_engine *e, void *stream, double z, double min_visit_ratio, int32_t min_visits, int32_t *moves_out_dev,
+                  int32_t *child_out_dev, double *lcb_out_dev);
+
 /* ---- Wide search: several pending leaves per board and step, with virtual loss (additive to ABI 9) -------------------------------------
  * Every board runs a strictly sequential MCTS by default: one leaf per board and lockstep step. That fills the chip at thousands of
  * boards and leaves it idle where boards are few (one game, a handful of analysed positions): the evaluator call costs the same for
