@@ -25,7 +25,8 @@ import numpy as np
 from ._lib import CczError
 from .boundary import describe
 from .game import Board
-from .options import SearchOptions, add_lcb_args, add_leaf_history_args, lcb_from_args, leaf_history_from_args
+from .options import (SearchOptions, add_fused_narrow_args, add_lcb_args, add_leaf_history_args, fused_narrow_from_args, lcb_from_args,
+                      leaf_history_from_args)
 from .searchcfg import add_search_args, search_from_args
 from .stopcfg import add_early_stop_args, early_stop_from_args
 
@@ -253,6 +254,8 @@ def main(argv=None) -> int:
     ap.add_argument("--multipv", type=int, default=1)
     ap.add_argument("--max-len", type=int, default=32)
     ap.add_argument("--weights", default=None, help="model file (default: random initialisation)")
+    ap.add_argument("--channels", type=int, default=256, help="width of the net's tower")
+    ap.add_argument("--blocks", type=int, default=40, help="residual blocks of the net's tower")
     ap.add_argument("--out", default=None, help="JSON lines file (default: stdout)")
     ap.add_argument("--width", type=int, default=1, help="leaves per position and evaluator call (virtual loss); 1: the sequential search")
     ap.add_argument("--solver", action="store_true", help="MCTS-solver: prove decided positions in the tree; every record gains \"mate\": N or null")
@@ -260,6 +263,7 @@ def main(argv=None) -> int:
     add_early_stop_args(ap)
     add_leaf_history_args(ap)
     add_lcb_args(ap)
+    add_fused_narrow_args(ap)
     args = ap.parse_args(argv)
     leaf_history = leaf_history_from_args(ap, args)
     lcb = lcb_from_args(ap, args)
@@ -277,7 +281,8 @@ def main(argv=None) -> int:
         return 1
     from .net import PolicyValueNet
     try:
-        pvn = PolicyValueNet(model=args.weights, device="cuda:0")
+        pvn = PolicyValueNet(model=args.weights, device="cuda:0", num_channels=args.channels, resblocks_num=args.blocks,
+                             fused_narrow=fused_narrow_from_args(ap, args))
         if leaf_history is not None:
             pvn.set_leaf_history(True)
         an = BatchedAnalysis(pvn, max(1, min(args.boards, len(parsed) or 1)), n_playout=args.playout, multipv=args.multipv,

@@ -23,7 +23,7 @@ import numpy as np
 
 from .boundary import WeightsWatch, describe
 from .parameters import C_PUCT
-from .options import (SearchOptions, add_lcb_args, add_leaf_history_args, add_resign_args, lcb_from_args, lcb_moves, leaf_history_from_args,
+from .options import (SearchOptions, add_fused_narrow_args, fused_narrow_from_args, add_lcb_args, add_leaf_history_args, add_resign_args, lcb_from_args, lcb_moves, leaf_history_from_args,
                       proven_moves, resign_from_args, search_move)
 from .searchcfg import add_search_args, search_from_args
 from .stopcfg import StopPoll, add_early_stop_args, early_stop_from_args
@@ -362,14 +362,14 @@ def policy_evaluate(current, best, **kw) -> float:
 
 
 # ---------------------------------------------------------------------- CLI
-def _load(spec: str, channels: int, blocks: int, device: int):
+def _load(spec: str, channels: int, blocks: int, device: int, fused_narrow: bool = False):
     import torch
     from .net import PolicyValueNet
     dev = f"cuda:{device}"
     if spec.startswith("random:"):
         torch.manual_seed(int(spec.split(":", 1)[1]))
-        return PolicyValueNet(device=dev, num_channels=channels, resblocks_num=blocks)
-    return PolicyValueNet(model=spec, device=dev, num_channels=channels, resblocks_num=blocks)
+        return PolicyValueNet(device=dev, num_channels=channels, resblocks_num=blocks, fused_narrow=fused_narrow)
+    return PolicyValueNet(model=spec, device=dev, num_channels=channels, resblocks_num=blocks, fused_narrow=fused_narrow)
 
 
 def main(argv=None) -> int:
@@ -394,14 +394,16 @@ def main(argv=None) -> int:
     add_early_stop_args(ap)
     add_leaf_history_args(ap)
     add_lcb_args(ap)
+    add_fused_narrow_args(ap)
     ap.add_argument("--lcb-side", choices=("both", "a", "b"), default=None, help="... which side plays the LCB move (default both); "
                     "--a X --b X --lcb --lcb-side a measures the option")
     a = ap.parse_args(argv)
     search = search_from_args(ap, a)
     early_stop = early_stop_from_args(ap, a)
     resign = resign_from_args(ap, a)
-    na = _load(a.a, a.channels, a.blocks, a.device)
-    nb = _load(a.b, a.channels, a.blocks, a.device)
+    narrow = fused_narrow_from_args(ap, a)
+    na = _load(a.a, a.channels, a.blocks, a.device, narrow)
+    nb = _load(a.b, a.channels, a.blocks, a.device, narrow)
     lcb = lcb_from_args(ap, a)
     if lcb is None and a.lcb_side is not None:
         ap.error("--lcb-side without --lcb: the LCB move is off")

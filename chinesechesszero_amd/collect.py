@@ -44,7 +44,7 @@ from .mcts import MCTS_AI
 from .net import PolicyValueNet
 from .parameters import BATCH_SIZE, C_PUCT, DATA_DIR, MODEL_DIR, PLAYOUT
 from .options import (SearchOptions, add_gumbel_args, add_resign_args, add_root_exploration_args, format_exploration, format_gumbel,  # noqa: F401
-                      add_leaf_history_args, add_surprise_args, format_search, leaf_history_from_args, gumbel_from_args, resign_from_args, root_exploration_from_args, surprise_from_args)
+                      add_fused_narrow_args, fused_narrow_from_args, add_leaf_history_args, add_surprise_args, format_search, leaf_history_from_args, gumbel_from_args, resign_from_args, root_exploration_from_args, surprise_from_args)
 from .checkpoint import add_checkpoint_args, checkpoint_from_args
 from .searchcfg import add_search_args, search_from_args
 from .stopcfg import add_early_stop_args, early_stop_from_args
@@ -576,7 +576,7 @@ class CollectPipeline:
                  dense_shards: bool = False, replay_plies: int = 0, train_every: int = 0, train_batch: int = BATCH_SIZE,
                  playout_cap_fast: int = 0, playout_cap_prob: float | None = None, resign=None, value_q_weight: float = 0.0,
                  root_exploration=None, solver: bool = False, gumbel=None, search=None, early_stop=None, surprise=None, leaf_history=None,
-                 checkpoint_dir: str | None = None, checkpoint_every: int = 0, resume: bool = False):
+                 checkpoint_dir: str | None = None, checkpoint_every: int = 0, resume: bool = False, fused_narrow: bool = False):
         # the engine options of the batched path, as BatchedSelfPlay takes them (options.OPTIONS: each None / False = off); only the search
         # parameters also run in the one-game loop (which then runs without scout slots)
         self.options = o = SearchOptions(n_playout, batched=n_boards > 1, resign=resign, root_exploration=root_exploration, gumbel=gumbel,
@@ -635,6 +635,7 @@ class CollectPipeline:
         self.seed = seed
         self.reference_quirks = reference_quirks
         self._net_shape = (num_channels, resblocks_num)
+        self.fused_narrow = bool(fused_narrow)   # nets of 64 / 128 channels: the evaluator on the narrow kernels (PolicyValueNet(fused_narrow=True))
         self.mcts_ai = None
         self.policy_value_net = None
         self.selfplay = None
@@ -734,11 +735,12 @@ class CollectPipeline:
             dev = f"cuda:{self.device}"
             try:
                 self.policy_value_net = PolicyValueNet(model=model_path, device=dev, num_channels=self._net_shape[0],
-                                                       resblocks_num=self._net_shape[1])
+                                                       resblocks_num=self._net_shape[1], fused_narrow=self.fused_narrow)
                 log(f"Loaded model: {model_path}")
             except Exception as e:
                 log(f"Failed to load model {model_path}: {e}", "ERROR")
-                self.policy_value_net = PolicyValueNet(device=dev, num_channels=self._net_shape[0], resblocks_num=self._net_shape[1])
+                self.policy_value_net = PolicyValueNet(device=dev, num_channels=self._net_shape[0], resblocks_num=self._net_shape[1],
+                                                       fused_narrow=self.fused_narrow)
             if self.gatherer is not None and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
                 # one job, one net: every rank plays with rank 0's weights (a model file that is missing on some rank, or the random
                 # fallback above, must not give the ranks different evaluators) -- ONE broadcast of the fp32 state, before any exchange
@@ -1094,6 +1096,7 @@ def build_parser():
     add_early_stop_args(parser)
     add_surprise_args(parser)
     add_leaf_history_args(parser)
+    add_fused_narrow_args(parser)
     parser.add_argument("--value-q-weight", type=float, default=0.0, help="with --train-every: weight of the recorded root value q in the value "
                         "target, (1 - w) z + w q on rows that carry one (0 = z alone)")
     add_checkpoint_args(parser)
@@ -1113,6 +1116,7 @@ def parse_args(argv=None):
     args.early_stop = early_stop_from_args(parser, args)
     args.surprise = surprise_from_args(parser, args)
     args.leaf_history_cfg = leaf_history_from_args(parser, args)
+    args.fused_narrow = fused_narrow_from_args(parser, args)
     args.options = dict(resign=args.resign, root_exploration=args.root_exploration, gumbel=args.gumbel_cfg, solver=args.solver, search=args.search,
                         early_stop=args.early_stop, surprise=args.surprise, leaf_history=args.leaf_history_cfg)
     try:
@@ -1151,7 +1155,8 @@ if __name__ == "__main__":
                            num_channels=args.channels, resblocks_num=args.blocks, max_plies=args.max_plies, device=device,
                            eval_cache_log2=args.eval_cache_log2, gatherer=gatherer, replay_plies=args.replay_plies,
                            train_every=args.train_every, train_batch=args.train_batch, playout_cap_fast=args.playout_cap_fast,
-                           playout_cap_prob=args.playout_cap_prob, value_q_weight=args.value_q_weight, **args.options, **args.checkpoint)
+                           playout_cap_prob=args.playout_cap_prob, value_q_weight=args.value_q_weight, fused_narrow=args.fused_narrow, **args.options,
+                           **args.checkpoint)
     if world > 1:
         from .launch import guarded
 

@@ -20,6 +20,7 @@
 #include "cczero_netops.h"
 #include "cczero_conv.h"
 #include "cczero_conv_small.h"
+#include "cczero_conv_narrow.h"
 #include "cczero_conv_g16.h"
 #include "cczero_conv_g16e.h"
 #include "cczero_heads.h"
@@ -2240,7 +2241,7 @@ static int conv3x3_launch(const char *who, void *stream, const void *x_dev, cons
         const dim3 grid((unsigned)((n_pixels + kSmPix - 1) / kSmPix), 16);
         const int rl = relu & 1;
 #define CCZ_SMALL(RES_, CIN_)                                                                                                  \
-        hipLaunchKernelGGL((k_conv3x3_small<RES_, CIN_>), grid, dim3(256), 0, (hipStream_t)stream, (const _Float16 *)x_dev, (const _Float16 *)w_dev, \
+        hipLaunchKernelGGL((k_conv3x3_small<RES_, CIN_, kCvC>), grid, dim3(256), 0, (hipStream_t)stream, (const _Float16 *)x_dev, (const _Float16 *)w_dev, \
                            (const float *)bias_f32_dev, (const _Float16 *)residual_dev, (_Float16 *)y_dev, (int)n_pixels, rl)
         if (cin == 64) CCZ_SMALL(false, 64);
         else if (residual_dev) CCZ_SMALL(true, 256);
@@ -2497,6 +2498,82 @@ int ccz_heads_conv1x1_f16(void *stream, const void *x_dev, const void *w32_dev, 
                            (const float *)bias32_f32_dev, (_Float16 *)pol_dev, (_Float16 *)val_dev, (int)n_boards, (const int *)live_boards_dev);
     else
         hipLaunchKernelGGL(k_head_conv1x1<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const _Float16 *)x_dev, (const _Float16 *)w32_dev,
+                           (const float *)bias32_f32_dev, (_Float16 *)pol_dev, (_Float16 *)val_dev, (int)n_boards, (const int *)live_boards_dev);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---- narrow towers (64 / 128 channels, board-major rows; cczero_conv_narrow.h): additive to ABI 9 ----
+static int conv3x3_cn_launch(const char *who, void *stream, const void *x_dev, const void *w_dev, const void *bias_f32_dev, const void *residual_dev, void *y_dev,
+                             int64_t n_pixels, int32_t relu, int32_t cin, int32_t cout, const int32_t *live_rows_dev, int32_t row0)
+{
+    if ((cin != 64 && cin != 128) || (cout != 64 && cout != 128))
+        return fail(-1, "%s: unsupported shape %d -> %d channels (cin and cout must be 64 or 128; 256-wide towers: ccz_conv3x3_c256_f16)", who, cin, cout);
+    if (!x_dev || !w_dev || !bias_f32_dev || !y_dev || n_pixels < 0 || n_pixels > (int64_t)INT32_MAX / 256)
+        return fail(-1, "%s: bad arguments (null pointer, or n_pixels outside 0 .. 2^31 / 256)", who);
+    if ((((uintptr_t)x_dev) | ((uintptr_t)w_dev) | ((uintptr_t)bias_f32_dev) | ((uintptr_t)residual_dev) | ((uintptr_t)y_dev)) & 15)
+        return fail(-1, "%s: pointers must be 16-byte aligned", who);
+    if (x_dev == y_dev) return fail(-1, "%s: the output may alias the residual but not the input", who);
+    if (relu & ~(CCZ_CONV_RELU | CCZ_CONV_DESCENDING | CCZ_CONV_FORCE_SMALL | CCZ_CONV_FORCE_TILE))
+        return fail(-1, "%s: flags are ReLU, tile order and the two force bits (board-major rows only)", who);
+    const bool whole = n_pixels % 90 == 0;
+    if (live_rows_dev && !whole) return fail(-1, "%s: the live form takes whole boards (n_pixels = boards * 90)", who);
+    if ((relu & CCZ_CONV_FORCE_SMALL) && (relu & CCZ_CONV_FORCE_TILE)) return fail(-1, "%s: both force bits set", who);
+    if ((relu & CCZ_CONV_FORCE_SMALL) && (live_rows_dev || !whole)) return fail(-1, "%s: the small form takes whole boards and no live count", who);
+    if (n_pixels == 0) return 0;
+    const bool res = residual_dev != nullptr;
+    const bool small = whole && !live_rows_dev && !(relu & CCZ_CONV_FORCE_TILE) && ((relu & CCZ_CONV_FORCE_SMALL) || n_pixels <= kSmallMaxPixels);
+#define CCZ_CN_SMALL(RES_, CIN_, COUT_)                                                                                                         \
+    hipLaunchKernelGGL((k_conv3x3_small<RES_, CIN_, COUT_>), dim3((unsigned)((n_pixels + kSmPix - 1) / kSmPix), COUT_ / 16), dim3(256), 0, (hipStream_t)stream, \
+                       (const _Float16 *)x_dev, (const _Float16 *)w_dev, (const float *)bias_f32_dev, (const _Float16 *)residual_dev, (_Float16 *)y_dev, \
+                       (int)n_pixels, (int)(relu & 1))
+#define CCZ_CN_TILE(RES_, CIN_, COUT_)                                                                                                          \
+    hipLaunchKernelGGL((k_conv3x3_narrow<RES_, CIN_, COUT_>), dim3((unsigned)((n_pixels + kNwBM - 1) / kNwBM)), dim3(512), 0, (hipStream_t)stream, \
+                       (const _Float16 *)x_dev, (const _Float16 *)w_dev, (const float *)bias_f32_dev, (const _Float16 *)residual_dev, (_Float16 *)y_dev, \
+                       (int)n_pixels, (int)(relu & 3), (const int *)live_rows_dev, (int)row0)
+#define CCZ_CN_FORM(RES_, CIN_, COUT_) do { if (small) CCZ_CN_SMALL(RES_, CIN_, COUT_); else CCZ_CN_TILE(RES_, CIN_, COUT_); } while (0)
+#define CCZ_CN_RES(CIN_, COUT_) do { if (res) CCZ_CN_FORM(true, CIN_, COUT_); else CCZ_CN_FORM(false, CIN_, COUT_); } while (0)
+    if (cin == 64 && cout == 64) CCZ_CN_RES(64, 64);
+    else if (cin == 64) CCZ_CN_RES(64, 128);
+    else if (cout == 64) CCZ_CN_RES(128, 64);
+    else CCZ_CN_RES(128, 128);
+#undef CCZ_CN_RES
+#undef CCZ_CN_FORM
+#undef CCZ_CN_TILE
+#undef CCZ_CN_SMALL
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int ccz_conv3x3_cn_f16(void *stream, const void *x_dev, const void *w_dev, const void *bias_f32_dev, const void *residual_dev, void *y_dev,
+                       int64_t n_pixels, int32_t relu, int32_t cin, int32_t cout)
+{
+    return conv3x3_cn_launch("ccz_conv3x3_cn_f16", stream, x_dev, w_dev, bias_f32_dev, residual_dev, y_dev, n_pixels, relu, cin, cout, nullptr, 0);
+}
+
+int ccz_conv3x3_cn_f16_live(void *stream, const void *x_dev, const void *w_dev, const void *bias_f32_dev, const void *residual_dev, void *y_dev,
+                            int64_t n_pixels, int32_t relu, int32_t cin, int32_t cout, const int32_t *live_rows_dev, int32_t part, int32_t n_parts)
+{
+    if (!live_rows_dev || g16_bad_part(part, n_parts)) return fail(-1, "ccz_conv3x3_cn_f16_live: null live-row count or bad part / n_parts");
+    return conv3x3_cn_launch("ccz_conv3x3_cn_f16_live", stream, x_dev, w_dev, bias_f32_dev, residual_dev, y_dev, n_pixels, relu, cin, cout, live_rows_dev,
+                             part | (n_parts << 16));
+}
+
+int ccz_heads_conv1x1_cn_f16(void *stream, const void *x_dev, const void *w32_dev, const void *bias32_f32_dev, void *pol_dev, void *val_dev,
+                             int32_t n_boards, int32_t c_in, const int32_t *live_boards_dev)
+{
+    if (c_in != 64 && c_in != 128) return fail(-1, "ccz_heads_conv1x1_cn_f16: unsupported width %d (64 or 128; 256: ccz_heads_conv1x1_f16)", c_in);
+    if (!x_dev || !w32_dev || !bias32_f32_dev || !pol_dev || !val_dev || n_boards < 0) return fail(-1, "ccz_heads_conv1x1_cn_f16: bad arguments");
+    if ((((uintptr_t)x_dev) | ((uintptr_t)w32_dev) | ((uintptr_t)bias32_f32_dev)) & 15) return fail(-1, "ccz_heads_conv1x1_cn_f16: x, weights and bias must be 16-byte aligned");
+    if ((((uintptr_t)pol_dev) | ((uintptr_t)val_dev)) & 1) return fail(-1, "ccz_heads_conv1x1_cn_f16: outputs must be 2-byte aligned");
+    if (n_boards == 0) return 0;
+    const long cells = ((long)n_boards * 90 + 15) / 16;
+    const unsigned blocks = (unsigned)((cells + 3) / 4 < 768 ? (cells + 3) / 4 : 768); // as ccz_heads_conv1x1_f16
+    if (c_in == 64)
+        hipLaunchKernelGGL((k_head_conv1x1<false, 64>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const _Float16 *)x_dev, (const _Float16 *)w32_dev,
+                           (const float *)bias32_f32_dev, (_Float16 *)pol_dev, (_Float16 *)val_dev, (int)n_boards, (const int *)live_boards_dev);
+    else
+        hipLaunchKernelGGL((k_head_conv1x1<false, 128>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const _Float16 *)x_dev, (const _Float16 *)w32_dev,
                            (const float *)bias32_f32_dev, (_Float16 *)pol_dev, (_Float16 *)val_dev, (int)n_boards, (const int *)live_boards_dev);
     HIP_TRY(hipGetLastError());
     return 0;

@@ -33,7 +33,9 @@ __host__ __device__ constexpr int sm_lds_bytes(int cin) { return (cin >> 6) * 18
 
 // LDS: [weights: n_half fragments of 1 KB, lane-linear | slab rows of CIN fp16, 16-byte chunk c of row r at position
 // (c & ~swz) | ((c ^ r) & swz) | one zero row]
-template <bool RES, int CIN>
+// COUT: channels per row of R and Y (the grid's y dimension is COUT / 16); 256 for the tower and its stems, 64 / 128 for the narrow
+// towers (cczero_conv_narrow.h). Nothing else depends on it: the staging and the K loop are generic in CIN.
+template <bool RES, int CIN, int COUT>
 __global__ __launch_bounds__(256) void k_conv3x3_small(const _Float16 *__restrict__ X, const _Float16 *__restrict__ W,
                                                          const float *__restrict__ bias, const _Float16 *R, _Float16 *Y, int M,
                                                          int relu)
@@ -117,9 +119,9 @@ __global__ __launch_bounds__(256) void k_conv3x3_small(const _Float16 *__restric
         }
     }
     // the residual of this lane's 4 channels, requested behind the operands (it is needed last)
-    const long at = pix * kCvC + co0 + 4 * q4;
+    const long at = pix * COUT + co0 + 4 * q4;
     cv_half4 res = (cv_half4)(_Float16)0;
-    if constexpr (RES) res = *(const cv_half4 *)(R + (pix < M ? at : (long)(M - 1) * kCvC + co0 + 4 * q4)); // (no branch: a pixel past the tensor reads the last row's and stores nothing)
+    if constexpr (RES) res = *(const cv_half4 *)(R + (pix < M ? at : (long)(M - 1) * COUT + co0 + 4 * q4)); // (no branch: a pixel past the tensor reads the last row's and stores nothing)
 
     // ---- K loop from LDS: half-step h = (chunk of 32 input channels, tap); the fragments of h + 1 are requested before the MFMA of h
     auto frag_b = [&](int h) {

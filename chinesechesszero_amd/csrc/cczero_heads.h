@@ -36,7 +36,8 @@ constexpr int kHdValStride = 640;             // ... of the value-head output: 9
 // X: tower rows [n_rows][256] fp16 (NHWC: row = board * 90 + pos; G16: row = (g * 90 + pos) * 16 + j for board 16 g + j).
 // Wh: [32][256] fp16, rows 0..16 policy, 17..23 value, 24..31 zero; bh: float [32]. pol / val: [boards][kHdPolStride / kHdValStride].
 // live: device count of live boards (rows of boards past it are skipped) or nullptr.
-template <bool G16>
+// C: channels per tower row (256; 64 / 128 for the narrow towers, board-major rows): C / 32 k-steps, the same chain otherwise.
+template <bool G16, int C = 256>
 __global__ __launch_bounds__(256) void k_head_conv1x1(const _Float16 *__restrict__ X, const _Float16 *__restrict__ Wh,
                                                         const float *__restrict__ bh, _Float16 *__restrict__ pol,
                                                         _Float16 *__restrict__ val, int n_boards, const int *__restrict__ live)
@@ -49,22 +50,23 @@ __global__ __launch_bounds__(256) void k_head_conv1x1(const _Float16 *__restrict
     const int n_cells = (int)((n_rows + 15) >> 4);
     if (wave >= n_cells) return;
     // weights as A fragments: [row block m][k-step s]: row m * 16 + r, k = s * 32 + q4 * 8 .. + 7
-    cv_half8 a[2][8];
+    constexpr int KS = C / 32;
+    cv_half8 a[2][KS];
 #pragma unroll
     for (int m = 0; m < 2; ++m)
 #pragma unroll
-        for (int s = 0; s < 8; ++s) a[m][s] = *(const cv_half8 *)(Wh + (m * 16 + r) * 256 + s * 32 + q4 * 8);
+        for (int s = 0; s < KS; ++s) a[m][s] = *(const cv_half8 *)(Wh + (m * 16 + r) * C + s * 32 + q4 * 8);
     float4 bias[2];
     bias[0] = *(const float4 *)(bh + 4 * q4);
     bias[1] = *(const float4 *)(bh + 16 + 4 * q4);
-    auto load = [&](int cell, cv_half8 (&b)[8]) {
+    auto load = [&](int cell, cv_half8 (&b)[KS]) {
         long row = (long)cell * 16 + r;
         row = row < n_rows ? row : n_rows - 1; // (a clamped row is computed and not stored)
-        const _Float16 *src = X + row * 256 + q4 * 8;
+        const _Float16 *src = X + row * C + q4 * 8;
 #pragma unroll
-        for (int s = 0; s < 8; ++s) b[s] = *(const cv_half8 *)(src + s * 32);
+        for (int s = 0; s < KS; ++s) b[s] = *(const cv_half8 *)(src + s * 32);
     };
-    cv_half8 b[8], bn[8];
+    cv_half8 b[KS], bn[KS];
     load(wave, b);
     for (int cell = wave; cell < n_cells; cell += n_waves) {
         const int next = cell + n_waves;
@@ -73,7 +75,7 @@ __global__ __launch_bounds__(256) void k_head_conv1x1(const _Float16 *__restrict
         acc0[0] = bias[0].x; acc0[1] = bias[0].y; acc0[2] = bias[0].z; acc0[3] = bias[0].w;
         acc1[0] = bias[1].x; acc1[1] = bias[1].y; acc1[2] = bias[1].z; acc1[3] = bias[1].w;
 #pragma unroll
-        for (int s = 0; s < 8; ++s) {
+        for (int s = 0; s < KS; ++s) {
             acc0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[0][s], b[s], acc0, 0, 0, 0);
             acc1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[1][s], b[s], acc1, 0, 0, 0);
         }
@@ -105,7 +107,7 @@ __global__ __launch_bounds__(256) void k_head_conv1x1(const _Float16 *__restrict
         }
         if (next < n_cells) {
 #pragma unroll
-            for (int s = 0; s < 8; ++s) b[s] = bn[s];
+            for (int s = 0; s < KS; ++s) b[s] = bn[s];
         }
     }
 }

@@ -158,10 +158,14 @@ class EvalOptions:
     128 (g5q_tile, csrc/cczero_conv_g16.h; same bits);
     ``CCZ_CONV_CHUNK_MAJOR=0`` (chunk_major): the tower's activations as group-of-16 ROWS at every size instead of the chunk-major
     G16C layout (csrc/cczero_conv_g16.h g16c_off: a tile's slab DMA moves whole cache lines; same bits) where the quad one-launch
-    form with the heads in the last layer runs (:meth:`InferenceNet._g16c`)."""
+    form with the heads in the last layer runs (:meth:`InferenceNet._g16c`);
+    ``CCZ_FUSED_NARROW=1`` (narrow; default OFF): towers of 64 or 128 channels run stem, tower and heads on the hand-written kernels for
+    narrow towers (csrc/cczero_conv_narrow.h: board-major rows at every batch size, the 256-wide kernels' rounding chain) instead of MIOpen +
+    hipBLASLt: a board's logits and value are then the same bits at every batch size (:attr:`InferenceNet.batch_invariant`). The weights
+    those kernels read are built with the object: ``InferenceNet(net, narrow=True)`` / ``PolicyValueNet(fused_narrow=True)``."""
 
     FIELDS = ("fused_conv", "fused_stem", "fused_heads", "fused_last", "layout", "force", "groups", "chains", "zigzag", "edge_tiles", "one_launch",
-              "quad", "chunk_major")
+              "quad", "chunk_major", "narrow")
 
     def __init__(self, env=None):
         env = os.environ if env is None else env
@@ -179,6 +183,7 @@ class EvalOptions:
         self.one_launch = env.get("CCZ_CONV_ONE_LAUNCH", "1") != "0"
         self.quad = env.get("CCZ_CONV_QUAD", "1") != "0"
         self.chunk_major = env.get("CCZ_CONV_CHUNK_MAJOR", "1") != "0"
+        self.narrow = env.get("CCZ_FUSED_NARROW", "0") == "1"
         if self.layout not in ("auto", "nhwc", "g16"):
             raise ValueError("CCZ_CONV_LAYOUT must be auto, nhwc or g16")
 
@@ -242,8 +247,13 @@ class InferenceNet(nn.Module):
 
     LIVE = list(range(7 * 7, 8 * 7)) + list(range(15 * 7, 17 * 7))  # channel ids of groups 7, 15, 16
 
-    def __init__(self, net: Net, dtype=torch.float16, live_only: bool = True, history: bool = False):
-        """``history``: the leaf rows hold all 17 plane groups (``SelfPlayEngine.set_leaf_history``): the stem reads the 119 planes --
+    NARROW_WIDTHS = (64, 128)   # tower widths served by csrc/cczero_conv_narrow.h (EvalOptions.narrow)
+
+    def __init__(self, net: Net, dtype=torch.float16, live_only: bool = True, history: bool = False, narrow=None):
+        """``narrow``: True / False sets ``EvalOptions.narrow`` of this object (None: as ``CCZ_FUSED_NARROW`` says). With it on, fp16 and a
+        tower of 64 or 128 channels, the weights of the narrow kernels are built (``stem_w64`` / ``stem_w128`` as [C, 3, 3, 64 | 128],
+        ``stem_b32``, ``head_w32`` as [32, C], the padded FC weights) and the whole evaluator runs on hand-written kernels.
+        ``history``: the leaf rows hold all 17 plane groups (``SelfPlayEngine.set_leaf_history``): the stem reads the 119 planes --
         ``stem_w128`` and the 128-channel pack + the general tile forms at cin = 128 next to (not instead of the code of) the 21-channel
         form; batches below ``FUSED_MIN_BOARDS`` take the torch stem on the full input, with the once-per-shape log line."""
         super().__init__()
@@ -252,6 +262,8 @@ class InferenceNet(nn.Module):
         live_only = live_only and not self.history
         self.live_only = live_only
         self.opt = EvalOptions()
+        if narrow is not None:
+            self.opt.narrow = bool(narrow)
         if self.opt.non_default():
             from .tools import log
             log(f"evaluator options from the environment: {self.opt.non_default()}")
@@ -261,15 +273,18 @@ class InferenceNet(nn.Module):
             w = w[:, self.LIVE]
         self.stem_w = nn.Parameter(w.to(dtype).contiguous(memory_format=cl), requires_grad=False)
         self.stem_b = nn.Parameter(b.to(dtype), requires_grad=False)
-        if live_only and w.shape[0] == 256:
+        # (the narrow kernels' weights exist only where the option was on when the object was built)
+        narrow_w = self.opt.narrow and dtype == torch.float16 and w.shape[0] in self.NARROW_WIDTHS
+        fused_w = w.shape[0] if (w.shape[0] == 256 or narrow_w) else 0   # width the hand-written stem kernels get weights for (0: none)
+        if live_only and fused_w:
             # stem weights for the fused kernel: [co, ky, kx, 64] with the 21 live input channels first, zeros above
-            w64 = torch.zeros(256, 3, 3, 64, dtype=w.dtype, device=w.device)
+            w64 = torch.zeros(fused_w, 3, 3, 64, dtype=w.dtype, device=w.device)
             w64[..., :len(self.LIVE)] = w.permute(0, 2, 3, 1)
             self.stem_w64 = nn.Parameter(w64.to(dtype).contiguous(), requires_grad=False)
             self.stem_b32 = nn.Parameter(b.detach().float().clone(), requires_grad=False)
-        if self.history and w.shape[0] == 256:
+        if self.history and fused_w:
             # the full stem for the fused kernels: [co, ky, kx, 128], the 119 planes in their own order, zeros above
-            w128 = torch.zeros(256, 3, 3, 128, dtype=w.dtype, device=w.device)
+            w128 = torch.zeros(fused_w, 3, 3, 128, dtype=w.dtype, device=w.device)
             w128[..., :PLAYS * PIECES] = w.permute(0, 2, 3, 1)
             self.stem_w128 = nn.Parameter(w128.to(dtype).contiguous(), requires_grad=False)
             self.stem_b32 = nn.Parameter(b.detach().float().clone(), requires_grad=False)
@@ -284,9 +299,9 @@ class InferenceNet(nn.Module):
         # the same weights packed for k_conv3x3_g16 (contiguous half-tiles; ccz_pack_conv_weights_g16_f16 is the C-side twin)
         if ws and ws[0].shape[0] == 256 and ws[0].shape[1] == 256:
             self.ws_g16 = nn.ParameterList([nn.Parameter(pack_conv_weights_g16(w.permute(0, 2, 3, 1)), requires_grad=False) for w in ws])
-        if hasattr(self, "stem_w64"):
+        if hasattr(self, "stem_w64") and fused_w == 256:
             self.stem_w64_g16 = nn.Parameter(pack_conv_weights_g16(self.stem_w64), requires_grad=False)
-        if hasattr(self, "stem_w128"):
+        if hasattr(self, "stem_w128") and fused_w == 256:
             self.stem_w128_g16 = nn.Parameter(pack_conv_weights_g16(self.stem_w128), requires_grad=False)
         # float32 copies of the tower biases for the fused convolution kernel (bias is added to the fp32 accumulator)
         self.bs32 = nn.ParameterList([nn.Parameter(b.detach().float().clone(), requires_grad=False) for b in bs])
@@ -311,7 +326,7 @@ class InferenceNet(nn.Module):
         # ccz_fc_f16, ccz_value_out_f32): head convolutions as ONE [32, 256] matrix (17 policy + 7 value rows + 8 zero rows), FC
         # weights with their input columns in (pos, channel) order zero-padded to the kernels' K granule (1530 -> 1536, 630 -> 640)
         # and their rows to whole 128-row tiles, biases in float32 (added to the fp32 accumulator)
-        if C_in == 256 and dtype == torch.float16:
+        if (C_in == 256 or narrow_w) and dtype == torch.float16:
             w32 = torch.zeros(32, C_in, dtype=torch.float64)
             w32[:PLAYS + PIECES] = torch.cat([wp, wv], 0).reshape(PLAYS + PIECES, C_in)
             b32 = torch.zeros(32, dtype=torch.float64)
@@ -332,6 +347,7 @@ class InferenceNet(nn.Module):
             self.policy_fc_b32 = nn.Parameter(padded_bias(net.policy_fc.bias, 2176), requires_grad=False)
             self.value_fc1_wp = nn.Parameter(padded(pc(net.value_fc1.weight, PIECES), 256, 640), requires_grad=False)
             self.value_fc1_b32 = nn.Parameter(padded_bias(net.value_fc1.bias, 256), requires_grad=False)
+        self.narrow_width = C_in if narrow_w else 0   # the tower's width when this object holds the narrow kernels' weights, else 0
 
     def set_options(self, **kw):
         """Change A/B switches of a live object (tests, profile scripts): ``set_options(layout="g16", fused_conv=False)``;
@@ -341,6 +357,8 @@ class InferenceNet(nn.Module):
                 raise KeyError(k)
             if k == "force" and isinstance(v, str):
                 v = {"small": 16, "tile": 32, "": 0}[v]
+            if k == "narrow" and v and not self.narrow_width and self.dtype == torch.float16 and self.stem_w.shape[0] in self.NARROW_WIDTHS:
+                raise ValueError("narrow=True needs the narrow kernels' weights: build the object with InferenceNet(net, narrow=True)")
             setattr(self.opt, k, v)
         if self.opt.layout not in ("auto", "nhwc", "g16"):
             raise ValueError("layout must be auto, nhwc or g16")
@@ -349,6 +367,24 @@ class InferenceNet(nn.Module):
 
     def opt_fused_conv(self) -> bool:
         return self.opt.fused_conv
+
+    def _narrow(self) -> bool:
+        """Does this object run the narrow kernels (``narrow`` on with the three fused switches, a 64- or 128-wide fp16 tower whose
+        derived weights were built)?"""
+        o = self.opt
+        return bool(o.narrow and self.narrow_width and o.fused_conv and o.fused_stem and o.fused_heads)
+
+    @property
+    def batch_invariant(self) -> bool:
+        """True when the WHOLE evaluator of this object runs on hand-written kernels, whose result for a board does not depend on
+        the batch it sits in -- what an evaluation cache, scout slots and planned batches assume: a 256-wide fp16 net on the GPU with
+        the fused switches on, or a 64- / 128-wide one with ``narrow`` on. Everything else runs (partly) on MIOpen / hipBLASLt, which
+        pick a kernel per problem size."""
+        o = self.opt
+        if self.dtype != torch.float16 or not self.stem_w.is_cuda or not (o.fused_conv and o.fused_stem and o.fused_heads):
+            return False
+        wide = hasattr(self, "head_w32") and not self.narrow_width and (hasattr(self, "stem_w64") or hasattr(self, "stem_w128"))
+        return bool(wide or self._narrow())
 
     def tower_groups(self, B: int, g16: bool) -> int:
         """Sequential board groups of the tower for a batch of B boards (Infinity-Cache residency, :meth:`_tower_fused`)."""
@@ -395,7 +431,28 @@ class InferenceNet(nn.Module):
             names.add("stem_w64_g16")
         if hasattr(self, "stem_w128_g16"):
             names.add("stem_w128_g16")
+        if self.narrow_width:   # the narrow kernels' weights that are exact functions of the fp16 primaries
+            names |= {n for n in self.NARROW_DERIVED if hasattr(self, n)}
         return names
+
+    # derived weight of a narrow object -> the primary it is rebuilt from (:meth:`_narrow_derive`); stem_b32 and head_b32 are NOT derived:
+    # they hold the float32 rounding of the folded biases, which the fp16 primaries no longer know
+    NARROW_DERIVED = {"stem_w64": "stem_w", "stem_w128": "stem_w", "head_w32": "head_wT", "policy_fc_wp": "policy_fc_w",
+                      "policy_fc_b32": "policy_fc_b", "value_fc1_wp": "value_fc1_w", "value_fc1_b32": "value_fc1_b"}
+
+    def _narrow_derive(self, name):
+        """The value of one of ``NARROW_DERIVED`` from its primary (what ``__init__`` built from the folded weights: zero padding only)."""
+        dst, src = getattr(self, name), getattr(self, self.NARROW_DERIVED[name])
+        out = torch.zeros_like(dst)
+        if name in ("stem_w64", "stem_w128"):
+            out[..., :src.shape[1]] = src.permute(0, 2, 3, 1)
+        elif name == "head_w32":
+            out[:src.shape[1]] = src.t()
+        elif name.endswith("_b32"):
+            out[:src.shape[0]] = src.float()
+        else:
+            out[:src.shape[0], :src.shape[1]] = src
+        return out
 
     @torch.no_grad()
     def repack_derived(self):
@@ -412,6 +469,11 @@ class InferenceNet(nn.Module):
         if hasattr(self, "stem_w128_g16"):
             self.stem_w128_g16.copy_(pack_conv_weights_g16(self.stem_w128))
             done.add("stem_w128_g16")
+        if self.narrow_width:
+            for name in self.NARROW_DERIVED:
+                if hasattr(self, name):
+                    getattr(self, name).copy_(self._narrow_derive(name))
+                    done.add(name)
         if done != self.derived_parameter_names():
             raise RuntimeError(f"repack_derived rebuilt {sorted(done)} but derived_parameter_names() lists {sorted(self.derived_parameter_names())}")
         self.__dict__.pop("_b2", None)
@@ -453,7 +515,7 @@ class InferenceNet(nn.Module):
 
     def _g16(self, B) -> bool:
         mode = self.opt.layout
-        if mode == "nhwc" or self.opt.force:
+        if mode == "nhwc" or self.opt.force or self.narrow_width:   # (narrow towers: board-major rows at every size)
             return False
         return B >= (65 if mode == "g16" else self.G16_MIN_BOARDS)
 
@@ -537,10 +599,16 @@ class InferenceNet(nn.Module):
         hw, hb = (_ptr(self.head_w32), _ptr(self.head_b32)) if heads is not None else (None, None)
         conv = L.ccz_conv3x3_c256_f16 if plan is None else L.ccz_conv3x3_c256_f16_live
         heads_layer = L.ccz_conv3x3_c256_heads_f16
+        Cw = x.shape[1]
+        if Cw != 256:   # a narrow tower (64 / 128 channels): the same schedule on the narrow entry points, which take the two widths behind the flags
+            if not self._narrow() or Cw != self.narrow_width or heads is not None or chunk_major:
+                raise RuntimeError(f"no hand-written tower kernels for {Cw} channels here (narrow towers: board-major rows, heads as a pass of their own)")
+            cn = L.ccz_conv3x3_cn_f16 if plan is None else L.ccz_conv3x3_cn_f16_live
+            conv = lambda s, xp, w, b, r, yp, n, f, *tail: cn(s, xp, w, b, r, yp, n, f, Cw, Cw, *tail)
         if chunk_major:   # the G16C twins: same arguments (a chain's board range is whole 128-board blocks: the group stride is the rows')
             conv = L.ccz_conv3x3_c256_g16c_f16 if plan is None else L.ccz_conv3x3_c256_g16c_f16_live
             heads_layer = L.ccz_conv3x3_c256_heads_g16c_f16
-        row = 90 * 256 * x.element_size()
+        row = 90 * Cw * x.element_size()
 
         def chain(st, d):
             """One chain's arguments: stream, x, y, head buffers, pixels, the two flag words, and what a convolution / the heads
@@ -605,11 +673,14 @@ class InferenceNet(nn.Module):
         s = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         Bp = -(-B // 16) * 16 if g16 else B          # group-of-16 layout: whole groups; the padding boards hold zeros
         lay = _lib.CONV_G16 if g16 else 0   # (the stem is one launch over the whole batch, not chained: the single-kernel form)
+        Cw = self.narrow_width if self._narrow() else 256   # output channels: the tower's width
+        if Cw != 256 and (g16 or chunk_major):
+            raise RuntimeError("narrow towers run on board-major rows only")
         if self.history:
             return self._stem128(leaf_input, plan, g16, Bp, lay, s)
         if plan is None:
             x64 = (torch.zeros if Bp != B else torch.empty)((Bp, 90, 64), dtype=torch.float16, device=dev)
-            y = torch.empty((Bp, 256, 10, 9), dtype=torch.float16, device=dev, memory_format=torch.channels_last)
+            y = torch.empty((Bp, Cw, 10, 9), dtype=torch.float16, device=dev, memory_format=torch.channels_last)
             pack, gather = (L.ccz_pack_live_planes_g16_f16, (None, None)) if g16 else (L.ccz_pack_live_planes_f16, ())
             stem, tail = L.ccz_conv3x3_stem_f16, (Bp * 90, 1 | self.opt.force | lay)   # (force: CCZ_CONV_FORCE=small|tile, an A/B switch)
         else:
@@ -619,15 +690,27 @@ class InferenceNet(nn.Module):
             key = (Bp, dev, g16)   # (either layout of the group-of-16 rows: a dead row holds an old finite result of some layout, read by nobody)
             if key not in bufs:
                 bufs[key] = (torch.zeros((Bp, 90, 64), dtype=torch.float16, device=dev),
-                             torch.empty((Bp, 256, 10, 9), dtype=torch.float16, device=dev, memory_format=torch.channels_last).zero_())
+                             torch.empty((Bp, Cw, 10, 9), dtype=torch.float16, device=dev, memory_format=torch.channels_last).zero_())
             x64, y = bufs[key]
             pack, gather = (L.ccz_pack_live_planes_g16_f16 if g16 else L.ccz_pack_live_planes_rows_f16), (_ptr(plan[0]), _ptr(plan[1]))
             stem, tail = L.ccz_conv3x3_stem_f16_live, (Bp * 90 if g16 else -(-B // 8) * 8 * 90, 1 | lay, _ptr(plan[1]), 0, 1)
         if chunk_major:
             stem = L.ccz_conv3x3_stem_g16c_f16 if plan is None else L.ccz_conv3x3_stem_g16c_f16_live
         _lib.check(pack(s, _ptr(leaf_input), _ptr(x64), B, *gather))
+        if Cw != 256:
+            self._stem_narrow(s, x64, self.stem_w64, y, tail, 64, Cw)
+            return y
         _lib.check(stem(s, _ptr(x64), _ptr(self.stem_w64_g16 if g16 else self.stem_w64), _ptr(self.stem_b32), _ptr(y), *tail))
         return y
+
+    def _stem_narrow(self, s, x, w, y, tail, cin, cout):
+        """The stem of a narrow tower: ``tail`` = (pixels, flags[, live count, part, n_parts]) as the 256-wide stem calls take it, on
+        ``ccz_conv3x3_cn_f16[_live]`` -- no residual, ``cin`` = 64 (live planes) or 128 (all planes), ``cout`` = the tower's width."""
+        from . import _lib
+        L = _lib.lib()
+        n, flags, live = tail[0], tail[1], tail[2:]
+        call = L.ccz_conv3x3_cn_f16_live if live else L.ccz_conv3x3_cn_f16
+        _lib.check(call(s, _ptr(x), _ptr(w), _ptr(self.stem_b32), None, _ptr(y), n, flags, cin, cout, *live))
 
     def _stem128(self, leaf_input, plan, g16, Bp, lay, s):
         """:meth:`_stem_fused` in history mode: every plane packed as NHWC rows of 128 channels (``ccz_pack_planes128_*``), then the
@@ -635,9 +718,10 @@ class InferenceNet(nn.Module):
         from . import _lib
         L = _lib.lib()
         B, dev = leaf_input.shape[0], leaf_input.device
+        Cw = self.narrow_width if self._narrow() else 256
         if plan is None:
             x = (torch.zeros if Bp != B else torch.empty)((Bp, 90, 128), dtype=torch.float16, device=dev)
-            y = torch.empty((Bp, 256, 10, 9), dtype=torch.float16, device=dev, memory_format=torch.channels_last)
+            y = torch.empty((Bp, Cw, 10, 9), dtype=torch.float16, device=dev, memory_format=torch.channels_last)
             pack, gather = (L.ccz_pack_planes128_g16_f16, (None, None)) if g16 else (L.ccz_pack_planes128_f16, ())
             stem, tail = L.ccz_conv3x3_stem128_f16, (Bp * 90, 1 | lay)
         else:
@@ -645,11 +729,14 @@ class InferenceNet(nn.Module):
             key = (Bp, dev, g16, 128)   # (as in _stem_fused: zeroed once, a dead row holds an old finite result)
             if key not in bufs:
                 bufs[key] = (torch.zeros((Bp, 90, 128), dtype=torch.float16, device=dev),
-                             torch.empty((Bp, 256, 10, 9), dtype=torch.float16, device=dev, memory_format=torch.channels_last).zero_())
+                             torch.empty((Bp, Cw, 10, 9), dtype=torch.float16, device=dev, memory_format=torch.channels_last).zero_())
             x, y = bufs[key]
             pack, gather = (L.ccz_pack_planes128_g16_f16 if g16 else L.ccz_pack_planes128_rows_f16), (_ptr(plan[0]), _ptr(plan[1]))
             stem, tail = L.ccz_conv3x3_stem128_f16_live, (Bp * 90 if g16 else -(-B // 8) * 8 * 90, 1 | lay, _ptr(plan[1]), 0, 1)
         _lib.check(pack(s, _ptr(leaf_input), _ptr(x), B, *gather))
+        if Cw != 256:
+            self._stem_narrow(s, x, self.stem_w128, y, tail, 128, Cw)
+            return y
         _lib.check(stem(s, _ptr(x), _ptr(self.stem_w128_g16 if g16 else self.stem_w128), _ptr(self.stem_b32), _ptr(y), *tail))
         return y
 
@@ -676,7 +763,9 @@ class InferenceNet(nn.Module):
         cache = self.__dict__.setdefault("_path_cache", {})
         if key not in cache:
             o = self.opt
-            fused = ((hasattr(self, "stem_w64") or hasattr(self, "stem_w128")) and leaf_input.is_cuda and leaf_input.dtype == torch.float16 and leaf_input.is_contiguous()
+            # (a narrow tower is on the hand-written kernels as a whole -- stem, tower AND heads -- or not at all: _narrow)
+            fused = ((hasattr(self, "stem_w64") or hasattr(self, "stem_w128")) and (not self.narrow_width or self._narrow())
+                     and leaf_input.is_cuda and leaf_input.dtype == torch.float16 and leaf_input.is_contiguous()
                      and B >= self.FUSED_MIN_BOARDS and self.dtype == torch.float16 and o.fused_conv and o.fused_stem)
             if fused:
                 cache[key] = "g16" if self._g16(B) else "nhwc"
@@ -747,11 +836,12 @@ class InferenceNet(nn.Module):
         batches run -- edge tiles, one launch per layer, quad middle tiles, the heads in the last layer's epilogue; anything else
         stays on rows (``chunk_major=False`` / ``CCZ_CONV_CHUNK_MAJOR=0``: always)."""
         o = self.opt
-        return bool(o.chunk_major and o.one_launch and o.quad and o.fused_last and o.fused_heads and hasattr(self, "head_w32")
+        return bool(o.chunk_major and o.one_launch and o.quad and o.fused_last and o.fused_heads and hasattr(self, "head_w32") and not self.narrow_width
                     and self.dtype == torch.float16 and self._edge(Bp, True))
 
     def _fused_heads_ok(self, x) -> bool:
-        return bool(self.opt.fused_heads and hasattr(self, "head_w32") and x.is_cuda and x.dtype == torch.float16 and x.shape[1] == 256
+        return bool(self.opt.fused_heads and hasattr(self, "head_w32") and x.is_cuda and x.dtype == torch.float16
+                    and (x.shape[1] == 256 if not self.narrow_width else (self._narrow() and x.shape[1] == self.narrow_width))
                     and x.is_contiguous(memory_format=torch.channels_last))
 
     def _head_buffers(self, Bx, dev):
@@ -779,7 +869,9 @@ class InferenceNet(nn.Module):
         v = torch.empty((B,), dtype=torch.float32, device=dev)
         s = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         live = _ptr(plan[1]) if plan is not None else None
-        if not conv_done:   # (conv_done: the last tower layer wrote pol / val from its epilogue, ``x`` is not the tower's output)
+        if x.shape[1] != 256:   # a narrow tower: board-major rows of 64 / 128 channels
+            _lib.check(L.ccz_heads_conv1x1_cn_f16(s, _ptr(x), _ptr(self.head_w32), _ptr(self.head_b32), _ptr(pol), _ptr(val), Bx, x.shape[1], live))
+        elif not conv_done:   # (conv_done: the last tower layer wrote pol / val from its epilogue, ``x`` is not the tower's output)
             _lib.check(L.ccz_heads_conv1x1_f16(s, _ptr(x), _ptr(self.head_w32), _ptr(self.head_b32), _ptr(pol), _ptr(val), Bx, _lib.CONV_G16 if g16 else 0, live))
         _lib.check(L.ccz_fc_f16(s, _ptr(pol), _lib.HEAD_POL_STRIDE, _ptr(self.policy_fc_wp), _ptr(self.policy_fc_b32), _ptr(logits), 2086, B, 2086, 1536, 0, live))
         _lib.check(L.ccz_fc_f16(s, _ptr(val), _lib.HEAD_VAL_STRIDE, _ptr(self.value_fc1_wp), _ptr(self.value_fc1_b32), _ptr(h1), 256, B, 256, 640, 1, live))
@@ -823,8 +915,11 @@ class PolicyValueNet:
     """Mirror of reference net.py:113-247 (same constructor, ``policy_value``, ``policy_value_fn``,
     ``save_model``, ``train_step``) plus the batched evaluator :meth:`evaluate_leaves`."""
 
-    def __init__(self, model=None, use_gpu=True, device=None, num_channels=256, resblocks_num=40):
+    def __init__(self, model=None, use_gpu=True, device=None, num_channels=256, resblocks_num=40, fused_narrow=False):
+        """``fused_narrow``: every inference copy of a 64- or 128-wide net runs on the hand-written kernels for narrow towers
+        (``InferenceNet(narrow=True)``); False leaves it to ``CCZ_FUSED_NARROW``."""
         self.use_gpu = use_gpu
+        self.fused_narrow = bool(fused_narrow)
         self.l2_const = 2e-3
         if device is not None:
             self.device = torch.device(device)
@@ -868,7 +963,7 @@ class PolicyValueNet:
         # per shape and selects the composable-kernel XDL grouped-conv kernel (0.60 ms) -- profiles/miopen_find_r01.txt
         self._require_current_fp32("refresh_inference_copy")
         self.policy_value_net.eval()
-        self._infer = InferenceNet(self.policy_value_net, history=self.leaf_history).to(self.device).eval()
+        self._infer = InferenceNet(self.policy_value_net, history=self.leaf_history, narrow=True if self.fused_narrow else None).to(self.device).eval()
         self._infer.bind_chain_streams(self.device)   # hardware queues for the tower's launch chains, before anything else asks for streams
         self._graph = None
         self.weights_version += 1
@@ -882,6 +977,13 @@ class PolicyValueNet:
             raise RuntimeError(f"{what}: this rank's fp32 net does not hold the weights of the last broadcast_model(what='inference') "
                                "(only the inference copy was sent): call broadcast_model(what='state') before training, saving or "
                                "rebuilding the inference copy here")
+
+    @property
+    def batch_invariant(self) -> bool:
+        """:attr:`InferenceNet.batch_invariant` of the inference copy (built when there is none)."""
+        if self._infer is None:
+            self.refresh_inference_copy()
+        return self._infer.batch_invariant
 
     @torch.no_grad()
     def evaluate_leaves(self, leaf_input: torch.Tensor):

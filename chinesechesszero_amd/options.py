@@ -439,3 +439,17 @@ def add_lcb_args(ap):
 def lcb_from_args(ap, a):
     return _from_args(ap, a, "--lcb", "the LCB move is off", ("--lcb-min-visit-ratio", "--lcb-min-visits"), make_lcb, a.lcb,
                       a.lcb_min_visit_ratio, a.lcb_min_visits)
+
+
+# ---------------------------------------------------------------------- the evaluator's own switch (no engine setter: it goes to PolicyValueNet)
+def add_fused_narrow_args(ap):
+    """--fused-narrow."""
+    ap.add_argument("--fused-narrow", action="store_true", default=False, help="nets of 64 or 128 channels (--channels): run the whole evaluator on "
+                    "the hand-written kernels for narrow towers instead of MIOpen / hipBLASLt, so that a board's logits and value are the same "
+                    "bits at every batch size -- what the evaluation cache, scout slots and planned batches assume (PolicyValueNet(fused_narrow=True), "
+                    "CCZ_FUSED_NARROW=1). No effect on other widths; absent = off")
+
+
+def fused_narrow_from_args(ap, a) -> bool:
+    """The value of the ``fused_narrow`` keyword of ``PolicyValueNet``."""
+    return bool(a.fused_narrow)

@@ -1094,6 +1094,26 @@ int ccz_fc_f16(void *stream, const void *a_dev, int32_t lda, const void *w_dev, 
 int ccz_value_out_f32(void *stream, const void *h_dev, const void *w2_dev, float b2, float *v_dev, int32_t m,
                       const int32_t *live_rows_dev);
 
+/* ---- narrow towers: 64 and 128 channels (additive to ABI 9; csrc/cczero_conv_narrow.h) -------------------------------------------
+ * The same chain as ccz_conv3x3_c256_f16 -- fp32 accumulator started at the bias, K in ascending chunks of 32 input channels x 9
+ * taps, fp16(acc) [+ residual in fp16] [ReLU] -- for board-major rows x [n_pixels, cin] -> y [n_pixels, cout], cin and cout each 64
+ * or 128 (towers 64 -> 64 and 128 -> 128; stems 64 -> 64 / 128 behind ccz_pack_live_planes_*_f16 and 128 -> 64 / 128 behind
+ * ccz_pack_planes128_*). w: [cout, 3, 3, cin] fp16, unpacked; bias: float [cout]; residual: [n_pixels, cout] or NULL (y may alias it,
+ * not x). relu: CCZ_CONV_RELU, CCZ_CONV_DESCENDING, CCZ_CONV_FORCE_SMALL / _TILE as on ccz_conv3x3_c256_f16; no group-of-16 form. Up
+ * to 64 boards run on k_conv3x3_small, larger batches on k_conv3x3_narrow (256-pixel tiles): the same bits from both, so a board's
+ * activations do not depend on its batch. A count that is not whole boards runs the tile form; the rows of its last board past
+ * n_pixels read as zero. Any other (cin, cout), misaligned pointers, a bad part / n_parts or a NULL live count fail the call.
+ * ccz_conv3x3_cn_f16_live: live_rows_dev / part / n_parts / n_pixels (the capacity of a range) as ccz_conv3x3_c256_f16_live on
+ *   board-major rows: ranges of ceil(ceil(L / n_parts) / 8) * 8 boards, rows past the live boards are not written.
+ * ccz_heads_conv1x1_cn_f16: ccz_heads_conv1x1_f16 on board-major rows of c_in = 64 or 128 channels (w32: [32, c_in]). */
+int ccz_conv3x3_cn_f16(void *stream, const void *x_dev, const void *w_dev, const void *bias_f32_dev, const void *residual_dev,
+                       void *y_dev, int64_t n_pixels, int32_t relu, int32_t cin, int32_t cout);
+int ccz_conv3x3_cn_f16_live(void *stream, const void *x_dev, const void *w_dev, const void *bias_f32_dev, const void *residual_dev,
+                            void *y_dev, int64_t n_pixels, int32_t relu, int32_t cin, int32_t cout, const int32_t *live_rows_dev,
+                            int32_t part, int32_t n_parts);
+int ccz_heads_conv1x1_cn_f16(void *stream, const void *x_dev, const void *w32_dev, const void *bias32_f32_dev, void *pol_dev,
+                             void *val_dev, int32_t n_boards, int32_t c_in, const int32_t *live_boards_dev);
+
 /* The LAST residual layer of the tower with both head convolutions in its epilogue (group-of-16 rows only: flags must hold
  * CCZ_CONV_G16; bit 0 ReLU, CCZ_CONV_G16_EDGE_TILES as ccz_conv3x3_c256_f16): computes relu(conv3x3(x) + bias + residual) like
  * ccz_conv3x3_c256_f16 but does NOT store it -- each tile multiplies its finished rows with w32 while they are still in LDS and
