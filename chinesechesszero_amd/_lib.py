@@ -44,6 +44,8 @@ FLAG_STRICT = 16   # parity mode: pruning a kept subtree / adjudicating at max_p
 LEAF_EXPAND, LEAF_DRAW, LEAF_LOSS, LEAF_SKIP = 0, 1, 2, 3
 LEAF_WIN = 4   # CCZ_LEAF_WIN: MCTS-solver only -- the descent ended at a node proven won for its side to move
 PROOF_UNKNOWN, PROOF_WIN, PROOF_LOSS, PROOF_DRAW = 0, 1, 2, 3   # CCZ_PROOF_*: state of a proof byte (side to move's view)
+MATE_MAX_PLIES, MATE_MAX_NODES = 31, 131072   # CCZ_MATE_MAX_PLIES / CCZ_MATE_MAX_NODES: what ccz_mate_search accepts
+MATE_NONE, MATE_FOUND, MATE_NO_MATE, MATE_BUDGET = 0, 1, 2, 3   # CCZ_MATE_*: the state of a board after ccz_mate_search
 
 ERR_BITS = {1: "node pool exhausted (raise max_nodes)", 2: "selection path deeper than max_depth", 64: "history chain overflow (> 128 positions since the last capture)",
             4: "more than 128 legal moves or pseudo-move overflow", 8: "pi record arena overflow",
@@ -181,6 +183,7 @@ PROTOTYPES = {
     "ccz_get_value_stats": (C.c_int, [_P, _P]),
     "ccz_root_value_stats": (C.c_int, [_P, _P, _P, _P]),
     "ccz_lcb_moves": (C.c_int, [_P, _P, C.c_double, C.c_double, C.c_int32, _P, _P, _P]),
+    "ccz_mate_search": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "ccz_get_solver_stats": (C.c_int, [_P, _P, C.POINTER(SolverStats)]),
     "ccz_proof_combine": (C.c_int, [_P, _P, _P, C.c_int32, _P]),
     "ccz_set_width": (C.c_int, [_P, _P, C.c_int32]),

@@ -25,7 +25,7 @@ import numpy as np
 from ._lib import CczError
 from .boundary import describe
 from .game import Board
-from .options import (SearchOptions, add_fused_narrow_args, add_lcb_args, add_leaf_history_args, fused_narrow_from_args, lcb_from_args,
+from .options import (SearchOptions, add_mate_search_args, mate_search_from_args, add_fused_narrow_args, add_lcb_args, add_leaf_history_args, fused_narrow_from_args, lcb_from_args,
                       leaf_history_from_args)
 from .searchcfg import add_search_args, search_from_args
 from .stopcfg import add_early_stop_args, early_stop_from_args
@@ -60,7 +60,7 @@ def parse_positions(lines) -> list[tuple[int, Board]]:
     return out
 
 
-def make_record(status: str, root_visits: int = 0, lines=(), solver=None, lcb=None) -> dict:
+def make_record(status: str, root_visits: int = 0, lines=(), solver=None, lcb=None, mate=None) -> dict:
     """One result record: ``status`` ("ok", "illegal move i", "invalid position", "history too long", "game over: ..."),
     ``bestmove`` (the first move of line 0, or None), ``root_visits``, ``lines`` = [{moves (uci), visits, q, prior}].
     ``solver`` (an analysis with the MCTS-solver; None without): ``{"proven": uci or None, "mates": {uci: N}}`` -- the record and
@@ -68,7 +68,10 @@ def make_record(status: str, root_visits: int = 0, lines=(), solver=None, lcb=No
     is the proven move where the root is decided. ``lcb`` (an analysis with the LCB move; None without): ``{"move": uci or None,
     "stats": {uci: (stdev, lcb)}}`` -- every line gains ``"stdev"`` (the sample standard deviation of the values backed up through its
     first move; None below two visits) and ``"lcb"`` (its lower confidence bound; None where it has none), and ``bestmove`` is the LCB
-    move unless the root is proven. The lines stay ranked by visits."""
+    move unless the root is proven. The lines stay ranked by visits.
+    ``mate`` (an analysis with the mate search; None without): ``{"move": uci or None, "mate": N or None}`` -- the record gains ``"mate"``
+    (with or without the solver), and where a mate by checks was found ``bestmove`` is its first move and ``"mate"`` its length in moves,
+    unless the solver has proven a mate of at most that length."""
     keep = [dict(moves=list(l["moves"]), visits=[int(v) for v in l["visits"]], q=float(l["q"]), prior=float(l["prior"])) for l in lines]
     rec = {"status": status, "bestmove": keep[0]["moves"][0] if keep and keep[0]["moves"] else None,
            "root_visits": int(root_visits), "lines": keep}
@@ -83,6 +86,12 @@ def make_record(status: str, root_visits: int = 0, lines=(), solver=None, lcb=No
         if solver.get("proven") is not None:
             rec["bestmove"] = solver["proven"]
         rec["mate"] = solver["mates"].get(rec["bestmove"]) if rec["bestmove"] is not None else None
+    if mate is not None:
+        # a forced mate by checks: it is the best move and the record's "mate", unless the tree has proven a mate that is no longer
+        quicker = solver is not None and rec.get("mate") is not None and 0 < rec["mate"] <= (mate.get("mate") or 0)
+        rec.setdefault("mate", None)
+        if mate.get("move") is not None and not quicker:
+            rec["bestmove"], rec["mate"] = mate["move"], mate["mate"]
     return rec
 
 
@@ -97,7 +106,7 @@ class BatchedAnalysis:
     across chunks and cleared only when the evaluator's weights version changes."""
 
     def __init__(self, evaluator, n_boards: int, n_playout: int = 400, multipv: int = 1, max_len: int = 32, solver: bool = False, search=None,
-                 width: int = 1, early_stop=None, leaf_history=None, lcb=None, **engine_kw):
+                 width: int = 1, early_stop=None, leaf_history=None, lcb=None, mate_search=None, **engine_kw):
         """``width`` > 1: every position gathers up to ``width`` leaves of its tree per step, kept apart by virtual loss
         (``wide.WideSearch``: an engine of ``n_boards * width`` slots) -- for a handful of positions, where the sequential search
         runs at the evaluator's latency; another tree than the sequential one; excludes ``solver`` and ``search``.
@@ -111,7 +120,11 @@ class BatchedAnalysis:
             raise TypeError("BatchedAnalysis: the evaluator must be callable or have evaluate_leaves_logits")
         if not 1 <= int(multipv) <= 128 or int(max_len) < 1 or int(n_playout) < 1:
             raise ValueError("BatchedAnalysis: multipv must be 1..128, max_len and n_playout >= 1")
-        SearchOptions(n_playout, width=width, solver=solver, search=search, early_stop=early_stop, leaf_history=leaf_history, lcb=lcb)   # (ValueError: width > 1 excludes them)
+        # ``mate_search``: plies or the dict of ``options.make_mate_search``: every position is also searched for a forced mate by checks
+        # (``ccz_mate_search``, no evaluator rows); records gain "mate", and bestmove is the mating move where one is found
+        self.mate_opts = SearchOptions(n_playout, width=width, solver=solver, search=search, early_stop=early_stop, leaf_history=leaf_history,
+                                       lcb=lcb, mate_search=mate_search)   # (ValueError: width > 1 excludes the others)
+        self.mate_search = self.mate_opts.mate_search
         if "eval_cache_log2" not in engine_kw:
             engine_kw["eval_cache_log2"] = 22 if (int(n_boards) >= 192 and desc.accepts_plan) else 0
         engine_kw.setdefault("mirror", False)
@@ -172,6 +185,10 @@ class BatchedAnalysis:
             if sp is not None:
                 sp._sim, sp._leaf, sp._ticker.acc = 0, None, 0      # fresh roots: whatever leaf was pending belongs to the old ones
             st = e.game_status()
+            ms = None
+            if self.mate_search is not None:     # (off: no call is made) the roots as loaded; the search below runs all the same
+                from .options import mate_moves
+                ms = mate_moves(e, self.mate_search, None, st["over"], counts=self.mate_opts.mate_counts, detail=True)[2]
             if self.wide is not None:
                 self.wide.boundary()
                 if not st["over"][:n].all():
@@ -216,8 +233,14 @@ class BatchedAnalysis:
                             stats[uci_of[int(rc["acts"][j][i])]] = (math.sqrt(max(s_i, 0.0) / (n_i - 1)) if n_i >= 2 else None,
                                                                     b_i if b_i > float("-inf") else None)
                         lc = {"move": uci_of[int(lb["moves"][j])] if lb["moves"][j] >= 0 else None, "stats": stats}
+                    mt = None
+                    if ms is not None:
+                        from .engine import mate_score
+                        hit = int(ms["state"][j]) == 1
+                        mt = {"move": uci_of[int(ms["move"][j])] if hit else None,
+                              "mate": mate_score(2, int(ms["dist"][j]) - 1) if hit else None}   # (the child is LOSS in dist - 1 plies)
                     if lines:
-                        out.append(make_record("ok", pv["root_visits"][j], lines, solver=sv, lcb=lc))
+                        out.append(make_record("ok", pv["root_visits"][j], lines, solver=sv, lcb=lc, mate=mt))
                     else:   # a position given without moves that is already decided: the root never got children
                         oc = bd.outcome()
                         out.append(make_record("ok" if oc is None else _winner_text(None if oc.winner is None else int(bool(oc.winner))),
@@ -238,6 +261,9 @@ class BatchedAnalysis:
         out = {"positions": self.positions, "seconds": round(self.seconds, 3), "positions_per_s": round(self.positions / sec, 2),
                "sims_per_s": round(self.sims / sec, 1), "evaluator_rows_per_step": round(rows / max(1, self.steps), 2)}
         out.update(self.sp.options.report(self.engine))   # search: the settings as the kernels read them, and how deep the leaves lay
+        if self.mate_search is not None:
+            from .options import mate_report
+            out["mate_search"] = mate_report(self.mate_search, self.mate_opts.mate_counts)
         if "search" in out:
             out["mean_leaf_depth"] = round(out["mean_leaf_depth"], 3)
         if "early_stop" in out:                 # stops per reason, and what a position cost on average
@@ -264,7 +290,9 @@ def main(argv=None) -> int:
     add_leaf_history_args(ap)
     add_lcb_args(ap)
     add_fused_narrow_args(ap)
+    add_mate_search_args(ap)
     args = ap.parse_args(argv)
+    mate_search = mate_search_from_args(ap, args)
     leaf_history = leaf_history_from_args(ap, args)
     lcb = lcb_from_args(ap, args)
     search = search_from_args(ap, args)
@@ -287,7 +315,7 @@ def main(argv=None) -> int:
             pvn.set_leaf_history(True)
         an = BatchedAnalysis(pvn, max(1, min(args.boards, len(parsed) or 1)), n_playout=args.playout, multipv=args.multipv,
                              max_len=args.max_len, solver=args.solver, search=search, width=args.width,
-                             early_stop=early_stop, leaf_history=leaf_history, lcb=lcb)
+                             early_stop=early_stop, leaf_history=leaf_history, lcb=lcb, mate_search=mate_search)
         records = an.analyse([b for _, b in parsed])
     except CczError as e:
         print(f"analyse: {e}", file=sys.stderr)

@@ -24,6 +24,7 @@ import numpy as np
 from .boundary import WeightsWatch, describe
 from .parameters import C_PUCT
 from .options import (SearchOptions, add_fused_narrow_args, fused_narrow_from_args, add_lcb_args, add_leaf_history_args, add_resign_args, lcb_from_args, lcb_moves, leaf_history_from_args,
+                      add_mate_search_args, mate_moves, mate_search_from_args,
                       proven_moves, resign_from_args, search_move)
 from .searchcfg import add_search_args, search_from_args
 from .stopcfg import StopPoll, add_early_stop_args, early_stop_from_args
@@ -186,7 +187,7 @@ class Arena:
     def __init__(self, net_a, net_b, n_pairs: int, n_playout: int = 400, opening_plies: int = 6, seed: int = 0,
                  max_plies: int = 0, c_puct: float = C_PUCT, eval_cache_log2: int = 22, device: int = 0,
                  cache_verify: bool = False, n_playout_b: int | None = None, resign=None, solver: bool = False, search=None, early_stop=None,
-                 leaf_history=None, lcb=None, lcb_side: str = "both"):
+                 leaf_history=None, lcb=None, lcb_side: str = "both", mate_search=None):
         from .boundary import need_history
         from .engine import SelfPlayEngine
         self.nets = (net_a, net_b)
@@ -207,8 +208,9 @@ class Arena:
             raise ValueError("Arena: n_playout and n_playout_b must be >= 1")
         self.n_steps = self.n_playout if self.n_playout_b is None else max(self.n_playout, self.n_playout_b)   # lockstep steps per move
         self.options = o = SearchOptions(self.n_steps, resign=resign, solver=solver, search=search, early_stop=early_stop, lcb=lcb,
-                                         leaf_history=leaf_history)
-        self.resign, self.solver, self.search_cfg, self.early_stop, self.lcb, self.leaf_history = o.keywords().values()
+                                         leaf_history=leaf_history, mate_search=mate_search)
+        self.mate_search = o.mate_search     # both sides look for a forced mate by checks before the move (options.mate_moves)
+        self.resign,self.solver, self.search_cfg, self.early_stop, self.lcb, self.leaf_history = o.keywords().values()
         if lcb_side not in ("both", "a", "b"):
             raise ValueError(f"Arena: lcb_side must be 'both', 'a' or 'b' (got {lcb_side!r})")
         if self.lcb is None and lcb_side != "both":
@@ -289,6 +291,8 @@ class Arena:
         over = e.game_status()["over"]
         forced, proven = proven_moves(e, self.solver, over)
         self.proven_moves += proven
+        if self.mate_search is not None:   # (off: no call is made) the mating move wins over the LCB move and the most visited one
+            forced, _ = mate_moves(e, self.mate_search, forced, over, counts=self.options.mate_counts)
         a_moves = self._turn == self.a_colour
         if self.lcb is not None:   # (off: no call is made) one call; the counts are split by the owner of the side to move
             allow = None if self.lcb_side == "both" else (a_moves if self.lcb_side == "a" else ~a_moves)
@@ -395,13 +399,15 @@ def main(argv=None) -> int:
     add_leaf_history_args(ap)
     add_lcb_args(ap)
     add_fused_narrow_args(ap)
+    add_mate_search_args(ap)
     ap.add_argument("--lcb-side", choices=("both", "a", "b"), default=None, help="... which side plays the LCB move (default both); "
                     "--a X --b X --lcb --lcb-side a measures the option")
     a = ap.parse_args(argv)
     search = search_from_args(ap, a)
     early_stop = early_stop_from_args(ap, a)
     resign = resign_from_args(ap, a)
-    narrow = fused_narrow_from_args(ap, a)
+    mate_search = mate_search_from_args(ap, a)
+    narrow =fused_narrow_from_args(ap, a)
     na = _load(a.a, a.channels, a.blocks, a.device, narrow)
     nb = _load(a.b, a.channels, a.blocks, a.device, narrow)
     lcb = lcb_from_args(ap, a)
@@ -413,7 +419,7 @@ def main(argv=None) -> int:
         nb.set_leaf_history(True)
     arena = Arena(na, nb, a.pairs, n_playout=a.playout, opening_plies=a.opening_plies, seed=a.seed, max_plies=a.max_plies,
                   eval_cache_log2=a.eval_cache_log2, device=a.device, n_playout_b=a.playout_b, resign=resign, solver=a.solver, search=search,
-                  early_stop=early_stop, leaf_history=leaf_history, lcb=lcb, lcb_side=a.lcb_side or "both")
+                  early_stop=early_stop, leaf_history=leaf_history, lcb=lcb, lcb_side=a.lcb_side or "both", mate_search=mate_search)
     r = arena.play()
     r.update({"a": a.a, "b": a.b, "opening_plies": a.opening_plies, "seed": a.seed, "net": f"{a.blocks}x{a.channels}",
               "promote": promote(r, a.threshold), "threshold": a.threshold})

@@ -17,6 +17,7 @@
 
 #include "cczero_kernels.h"
 #include "cczero_history.h"
+#include "cczero_mate.h"
 #include "cczero_netops.h"
 #include "cczero_conv.h"
 #include "cczero_conv_small.h"
@@ -1234,6 +1235,21 @@ int ccz_lcb_moves(ccz_engine *e, void *stream, double z, double min_visit_ratio,
     if (min_visits < 0) return fail(-1, "ccz_lcb_moves: min_visits %d must be >= 0", min_visits);
     hipLaunchKernelGGL(k_lcb_moves, dim3(e->d.B), dim3(64), 0, (hipStream_t)stream, e->d, (int)ACTIVE(e), z, min_visit_ratio, (int)min_visits,
                        moves_out_dev, child_out_dev, lcb_out_dev);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int ccz_mate_search(ccz_engine *e, void *stream, int32_t max_plies, int32_t node_budget, int32_t *state_dev, int32_t *dist_dev,
+                    int32_t *move_dev, int32_t *nodes_dev)
+{
+    NEED(e);
+    if (!state_dev || !dist_dev || !move_dev || !nodes_dev) return fail(-1, "ccz_mate_search: null output");
+    if (max_plies < 1 || max_plies > CCZ_MATE_MAX_PLIES || !(max_plies & 1))
+        return fail(-1, "ccz_mate_search: max_plies %d must be odd and in 1..%d", max_plies, CCZ_MATE_MAX_PLIES);
+    if (node_budget < 1 || node_budget > CCZ_MATE_MAX_NODES)
+        return fail(-1, "ccz_mate_search: node_budget %d must be in 1..%d", node_budget, CCZ_MATE_MAX_NODES);
+    hipLaunchKernelGGL(k_mate_search, dim3(e->d.B), dim3(64), 0, (hipStream_t)stream, e->d, (int)ACTIVE(e), (int)max_plies, (int)node_budget,
+                       state_dev, dist_dev, move_dev, nodes_dev);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -723,6 +723,26 @@ class SelfPlayEngine:
             return {"moves": self._lcb_moves, "child": self._lcb_child, "lcb": lcb}
         return self._lcb_moves
 
+    def mate_search(self, max_plies: int, node_budget: int, out=None) -> dict:
+        """Forced mates by consecutive checks from every board's root (``ccz_mate_search``; the definition in full is in
+        include/cczero.h): the side to move may only give check, the other side tries every reply, depth-first with iterative
+        deepening 1, 3, ..., ``max_plies`` (odd, at most ``MATE_MAX_PLIES``), at most ``node_budget`` move generations per board
+        (1 .. ``MATE_MAX_NODES``). No evaluator row, nothing of the engine changes. Returns NumPy int32 [B] arrays: ``state``
+        (0 not searched: game over, parked, scout slot; 1 mate found; 2 none within ``max_plies``; 3 budget reached), ``dist`` (plies
+        of the mate, else 0), ``move`` (the first mating move in ``legal_moves`` order, else -1), ``nodes``. ``out``: an int32 device
+        tensor [4,B] to launch into (default: one kept by the engine). Syncs, for the copy."""
+        if out is None:
+            if not hasattr(self, "_mate_out"):
+                self._mate_out = torch.empty((4, self.B), dtype=torch.int32, device=self.device)
+            out = self._mate_out
+        if out.dtype != torch.int32 or tuple(out.shape) != (4, self.B) or not out.is_contiguous() or out.device != self.device:
+            raise ValueError(f"out must be a contiguous int32 tensor [4,{self.B}] on {self.device}")
+        with torch.cuda.device(self.device):
+            check(self.L.ccz_mate_search(self.h, self._stream(), int(max_plies), int(node_budget), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]),
+                                         _ptr(out[3])))
+        host = out.cpu().numpy()
+        return {"state": host[0].copy(), "dist": host[1].copy(), "move": host[2].copy(), "nodes": host[3].copy()}
+
     def _to_dev(self, x, dtype, name):
         t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x, dtype={torch.int32: np.int32, torch.uint8: np.uint8}[dtype]))
         t = t.to(device=self.device, dtype=dtype).contiguous()

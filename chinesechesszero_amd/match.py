@@ -13,19 +13,23 @@ import numpy as np
 
 from .boundary import deliver, kind_of
 from .engine import SelfPlayEngine
-from .options import SearchOptions, lcb_moves, proven_moves, search_move
+from .options import SearchOptions, lcb_moves, mate_moves, proven_moves, search_move
 from .parameters import C_PUCT
 from .stopcfg import StopPoll
 
 
 class BatchedMatch:
     def __init__(self, evaluator_red, evaluator_black, n_boards: int, n_playout: int = 400, c_puct: float = C_PUCT,
-                 seed: int = 0, device: int = 0, max_plies: int = 0, temp: float = 1e-3, solver: bool = False, search=None, early_stop=None, lcb=None):
+                 seed: int = 0, device: int = 0, max_plies: int = 0, temp: float = 1e-3, solver: bool = False, search=None, early_stop=None, lcb=None,
+                 mate_search=None):
         """``solver`` / ``search`` / ``early_stop``: the engine options (``options.OPTIONS``: what ``engine.set_solver`` / ``set_search`` /
         ``set_early_stop`` take; None / False: off), for both sides alike. With the solver the proven move is played where the root is decided
         (``options.proven_moves``); with the early stop the move's loop ends when no board would select any more (``options.search_move``).
-        ``lcb``: both sides play the LCB move (``options.MOVE_OPTIONS``) instead of the most visited one; a proven move wins over it."""
-        self.options = o = SearchOptions(n_playout, solver=solver, search=search, early_stop=early_stop, lcb=lcb)
+        ``lcb``: both sides play the LCB move (``options.MOVE_OPTIONS``) instead of the most visited one; a proven move wins over it.
+        ``mate_search``: plies, or the dict of ``options.make_mate_search``: before every move ``ccz_mate_search`` looks for a forced mate by
+        consecutive checks, and the mating move is played where one is found (``options.mate_moves``); the search runs all the same."""
+        self.options = o = SearchOptions(n_playout, solver=solver, search=search, early_stop=early_stop, lcb=lcb, mate_search=mate_search)
+        self.mate_search = o.mate_search
         self.solver, self.search_cfg, self.early_stop, self.lcb = o.keywords().values()
         self.ev = {1: evaluator_red, 0: evaluator_black}
         self.B = n_boards
@@ -44,13 +48,15 @@ class BatchedMatch:
         """One lockstep move of every unfinished board by the player of colour ``turn`` (1 RED, 0 BLACK): n_playout
         simulations on a fresh tree, move ~ pi at temperature 1e-3, tree discarded (mcts.py:225-229). Returns the moves
         played (host int32 [B], -1 on finished boards)."""
-        e = self.engine
+        e, o = self.engine, self.options
         ev = self.ev[turn]
         search_move(e, self.n_playout, lambda leaf, last: deliver(e, kind_of(ev), *ev(leaf), last), self._poll)
         if self.before_move is not None:
             self.before_move(self)
         forced, proven = proven_moves(e, self.solver)
         self.proven_moves += proven
+        if self.mate_search is not None:
+            forced, _ = mate_moves(e, self.mate_search, forced, counts=o.mate_counts)
         if self.lcb is not None:
             forced, _ = lcb_moves(e, self.lcb, forced, counts=self.options.lcb_counts)
         moves = e.finish_move(forced_moves=forced, temps=self._temps, keep_tree=False).cpu().numpy()

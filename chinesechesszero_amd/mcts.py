@@ -71,8 +71,10 @@ SCOUTS = 10  # scout slots of a one-game search (ScoutedSearch): 1 + 10 = 11 row
 
 class MCTS:
     def __init__(self, policy_value_fn, c_puct=5, n_playout=10000, device: int = 0, seed: int = 0, scouts: int | None = None,
-                 solver: bool = False, search=None, width: int | None = None, lcb=None):
-        """``lcb``: keep the value spread of every node (``SelfPlayEngine.set_value_stats``) so that :meth:`lcb_move` can name the
+                 solver: bool = False, search=None, width: int | None = None, lcb=None, mate_search=None):
+        """``mate_search``: plies, or the dict of ``options.make_mate_search``: :meth:`mate_move` then looks for a forced mate by
+        consecutive checks from a board's position (``SelfPlayEngine.mate_search``: no evaluator call).
+        ``lcb``: keep the value spread of every node (``SelfPlayEngine.set_value_stats``) so that :meth:`lcb_move` can name the
         lower-confidence-bound move (``options.MOVE_OPTIONS``: True, a multiple z of the standard error, or a dict); not with ``width`` > 1.
         ``width``: None / 1 (default): the sequential search, scouted as below. 2..64: the wide search (``wide.WideSearch``): up to
         ``width`` leaves of the tree per evaluator call, kept apart by virtual loss -- another tree than the reference's; needs a
@@ -88,8 +90,9 @@ class MCTS:
         self.width = 1 if width is None else int(width)
         if not 1 <= self.width <= 64:
             raise ValueError(f"width must be in 1..64 (got {width})")
-        self.options = SearchOptions(n_playout, width=self.width, solver=solver, search=search, lcb=lcb)
+        self.options = SearchOptions(n_playout, width=self.width, solver=solver, search=search, lcb=lcb, mate_search=mate_search)
         self.solver, self.search_cfg, self.lcb = self.options.keywords().values()
+        self.mate_search = self.options.mate_search
         if self.width > 1 and scouts:
             raise ValueError("width > 1 (the wide search) excludes scouts")
         self._wide = None
@@ -299,6 +302,24 @@ class MCTS:
         return proof_move(rp["state"][0], rp["dist"][0], rp["child_state"][0], rp["child_dist"][0], rc["acts"][0])
 
 
+    def mate_move(self, board, cfg=None):
+        """``(move id, dist in plies, nodes)`` of the forced mate by consecutive checks from ``board``'s position, or None: the option
+        is off (and no ``cfg`` is given), the game is over, or the search found none. ``cfg``: settings for this one call
+        (``options.make_mate_search``). The engine's root is synced to the board first; no evaluator call is made."""
+        cfg = self.mate_search if cfg is None else cfg
+        if cfg is None:
+            return None
+        self._sync_root(board)
+        res = self._engine.mate_search(cfg["max_plies"], cfg["node_budget"])
+        c = self.options.mate_counts
+        c["boards"] += int(res["state"][0] != 0)
+        c["mates"] += int(res["state"][0] == 1)
+        c["nodes"] += int(res["nodes"][0])
+        self.last_mate_nodes = int(res["nodes"][0])
+        if int(res["state"][0]) != 1:
+            return None
+        return int(res["move"][0]), int(res["dist"][0]), int(res["nodes"][0])
+
     def lcb_move(self):
         """The move id the LCB rule plays at the root (``SelfPlayEngine.lcb_moves`` with this search's ``lcb`` settings), or None:
         the option is off, nothing was searched, or the game is over."""
@@ -312,14 +333,19 @@ class MCTS_AI:
     """reference mcts.py:181-233"""
 
     def __init__(self, policy_value_fn, c_puct=5, n_playout=2000, is_selfplay=False, device: int = 0, seed: int = 0, scouts: int | None = None,
-                 solver: bool = False, search=None, width: int | None = None, lcb=None):
-        """``lcb``: as in :class:`MCTS`; a match player (``is_selfplay`` False) then plays :meth:`MCTS.lcb_move` instead of drawing from
+                 solver: bool = False, search=None, width: int | None = None, lcb=None, mate_search=None):
+        """``mate_search``: as in :class:`MCTS`; :meth:`get_action` then runs the mate search before the playouts and, where it finds a
+        forced mate, returns its first move (``return_prob``: one-hot) without any evaluator call; ``last_mate`` holds (move, dist, nodes)
+        of that move, None after a searched one.
+        ``lcb``: as in :class:`MCTS`; a match player (``is_selfplay`` False) then plays :meth:`MCTS.lcb_move` instead of drawing from
         the visit counts at temperature ``temp`` (a proven move wins over it; the self-play branch is untouched).
         ``width``: as in :class:`MCTS` (None / 1: the scouted sequential search; 2..64: the wide search).
         ``search``: as in :class:`MCTS` (with it, ``scouts`` None means 0 and ``scouts`` > 0 raises ValueError).
         ``solver``: search with the MCTS-solver and play the proven move when the root is decided (the fastest mate, the longest
         defence) instead of drawing from the visit counts."""
-        self.mcts = MCTS(policy_value_fn, c_puct, n_playout, device=device, seed=seed, scouts=scouts, solver=solver, search=search, width=width, lcb=lcb)
+        self.mcts = MCTS(policy_value_fn, c_puct, n_playout, device=device, seed=seed, scouts=scouts, solver=solver, search=search, width=width, lcb=lcb,
+                         mate_search=mate_search)
+        self.last_mate = None
         self.is_selfplay = is_selfplay
         self.agent = "AI"
 
@@ -329,8 +355,15 @@ class MCTS_AI:
     def reset_player(self):
         self.mcts.update_with_move(-1)
 
-    def get_action(self, board, temp=1e-3, return_prob=False, on_playout=None):
+    def get_action(self, board, temp=1e-3, return_prob=False, on_playout=None, mate_search=None):
+        """``mate_search``: the mate search's settings for this one call (``options.make_mate_search``; None: the player's own)."""
         move_probs = np.zeros(2086)
+        self.last_mate = self.mcts.mate_move(board, mate_search)
+        if self.last_mate is not None:       # a forced mate by checks: played as it is, no playout, no evaluator call
+            move = self.last_mate[0]
+            move_probs[move] = 1.0
+            self.mcts.update_with_move(move if self.is_selfplay else -1)
+            return (move, move_probs) if return_prob else move
         acts, probs = self.mcts.get_move_probs(board, temp, on_playout=on_playout)
         move_probs[list(acts)] = probs
         proven = self.mcts.proof_move()

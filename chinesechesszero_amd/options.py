@@ -163,7 +163,11 @@ class SearchOptions:
     Raises ValueError for every combination that is refused before an engine exists (``csrc/cczero.hip`` refuses them again, and more: it stays the
     authority). Then every allowed option is an attribute: its dict, None when off (``solver``: a bool); ``on``: those that are on, in OPTIONS' order."""
 
-    def __init__(self, n_playout=None, sampling: str = "device", batched: bool = True, width: int = 1, **given):
+    def __init__(self, n_playout=None, sampling: str = "device", batched: bool = True, width: int = 1, mate_search=None, **given):
+        # the mate search is a query before the move, not an engine setting: it has no setter and no entry in the tables (``keywords``
+        # and ``on`` are what they are without it); its dict, its counters, its report and its log fragment live next to them
+        self.mate_search = mate_search_of(mate_search)
+        self.mate_counts = {"boards": 0, "mates": 0, "nodes": 0}   # what :func:`mate_moves` is handed as ``counts``
         self.on = on = {}
         for name, o in ALL_OPTIONS.items():
             if name in given:
@@ -211,12 +215,16 @@ class SearchOptions:
 
     def report(self, engine) -> dict:
         """The entries of the options that are on in a front end's JSON result (syncs)."""
-        return {k: v for name in self.on if ALL_OPTIONS[name].report
-                for k, v in ALL_OPTIONS[name].report(self.lcb_counts if name == "lcb" else engine).items()}
+        out = {k: v for name in self.on if ALL_OPTIONS[name].report
+               for k, v in ALL_OPTIONS[name].report(self.lcb_counts if name == "lcb" else engine).items()}
+        if self.mate_search is not None:
+            out["mate_search"] = mate_report(self.mate_search, self.mate_counts)
+        return out
 
     def log_line(self, engine) -> str:
         """The fragments of the options that are on, for the collector's periodic log line (empty with none on; syncs)."""
-        return "".join(ALL_OPTIONS[name].log(self.lcb_counts if name == "lcb" else engine) for name in self.on)
+        return "".join(ALL_OPTIONS[name].log(self.lcb_counts if name == "lcb" else engine) for name in self.on) + (
+            format_mate(self.mate_counts) if self.mate_search is not None else "")
 
 
 # ---------------------------------------------------------------------- the move of an arg-max front end
@@ -266,6 +274,91 @@ def lcb_moves(engine, cfg, forced, over=None, allow=None, counts=None, detail: b
         counts["moves"] += int(fill.sum())
         counts["differed"] += differed
     return (forced, differed, fill, off) if detail else (forced, differed)
+
+
+# ---------------------------------------------------------------------- the mate search (ccz_mate_search): a query before the move
+MATE_MAX_PLIES, MATE_MAX_NODES = 31, 131072   # CCZ_MATE_MAX_PLIES / CCZ_MATE_MAX_NODES (no GPU here: tests compare them with _lib's)
+MATE_NODES = 2048                            # the budget per board when none is given
+_PROOF_WIN = 1                               # CCZ_PROOF_WIN
+
+
+def make_mate_search(plies, nodes=None):
+    """The ``mate_search`` dict of the front ends -- ``{"max_plies", "node_budget"}``, what ``SelfPlayEngine.mate_search`` takes -- or None
+    when ``plies`` is None, False or 0. ValueError: what ``ccz_mate_search`` refuses."""
+    if plies is None or plies is False or plies == 0:
+        if nodes is not None:
+            raise ValueError("--mate-nodes without --mate-search: the mate search is off")
+        return None
+    plies = int(plies)
+    if not 1 <= plies <= MATE_MAX_PLIES or plies % 2 == 0:
+        raise ValueError(f"--mate-search must be odd and in 1..{MATE_MAX_PLIES} plies (got {plies})")
+    nodes = MATE_NODES if nodes is None else int(nodes)
+    if not 1 <= nodes <= MATE_MAX_NODES:
+        raise ValueError(f"--mate-nodes must be in 1..{MATE_MAX_NODES} (got {nodes})")
+    return {"max_plies": plies, "node_budget": nodes}
+
+
+def mate_search_of(value):
+    """The ``mate_search`` keyword of a front end as its dict: None / False / 0 off, a number of plies, or a dict (``max_plies`` /
+    ``plies``, ``node_budget`` / ``nodes``), checked by :func:`make_mate_search`."""
+    if isinstance(value, dict):
+        extra = set(value) - {"max_plies", "plies", "node_budget", "nodes"}
+        if extra:
+            raise ValueError(f"mate_search: no such setting: {', '.join(sorted(extra))}")
+        return make_mate_search(value.get("max_plies", value.get("plies")), value.get("node_budget", value.get("nodes")))
+    return make_mate_search(value)
+
+
+def add_mate_search_args(ap):
+    """--mate-search PLIES / --mate-nodes N."""
+    ap.add_argument("--mate-search", type=int, default=None, metavar="PLIES", help="before every move, look for a forced mate by consecutive "
+                    f"checks of at most PLIES plies (odd, 1..{MATE_MAX_PLIES}) on the device -- no evaluator rows -- and play it where one is "
+                    "found; absent = off")
+    ap.add_argument("--mate-nodes", type=int, default=None, metavar="N", help=f"... at most N positions per board, 1..{MATE_MAX_NODES} "
+                    f"(default {MATE_NODES})")
+
+
+def mate_search_from_args(ap, a):
+    return _from_args(ap, a, "--mate-search", "the mate search is off", ("--mate-nodes",), make_mate_search, a.mate_search, a.mate_nodes)
+
+
+def mate_report(cfg: dict, counts: dict) -> dict:
+    """The settings, the boards searched, the mates found, and the mean nodes per searched board (None before the first)."""
+    n = counts["boards"]
+    return dict(cfg, boards=n, mates=counts["mates"], mean_nodes=counts["nodes"] / n if n else None)
+
+
+def format_mate(counts: dict) -> str:
+    n = counts["boards"]
+    mean = f"{counts['nodes'] / n:.1f}" if n else "n/a"
+    return f", mate search boards {n}, mates {counts['mates']}, mean nodes {mean}"
+
+
+def mate_moves(engine, cfg, forced, over=None, counts=None, detail: bool = False):
+    """The mating move of every running game on which ``SelfPlayEngine.mate_search`` finds one (state 1), written into ``forced``: it
+    wins over the LCB move and the most visited move (call :func:`lcb_moves` after this), and over the tree's proven move unless the
+    tree holds a WIN proof of at most the mate's distance (solver on). ``cfg``: the ``mate_search`` dict of :class:`SearchOptions`
+    (None: off, no call is made, ``forced`` comes back as it is); ``forced``: int32 [B] numpy or None (all -1); ``counts``:
+    ``SearchOptions.mate_counts``, moved in place. Returns ``(forced, mates written)``; with ``detail`` also the result arrays. Syncs."""
+    if cfg is None:
+        return (forced, 0, None) if detail else (forced, 0)
+    import numpy as np
+    res = engine.mate_search(cfg["max_plies"], cfg["node_budget"])
+    over = engine.game_status()["over"] if over is None else over
+    if forced is None:
+        forced = np.full(engine.B, -1, np.int32)
+    found = (res["state"] == 1) & (np.asarray(over) == 0) & (res["move"] >= 0)
+    if getattr(engine, "solver", False) and found.any():
+        rp = engine.root_proof()
+        found &= ~((rp["state"] == _PROOF_WIN) & (rp["dist"].astype(np.int64) <= res["dist"]) & (forced >= 0))
+    forced[found] = res["move"][found]
+    if counts is not None:
+        searched = res["state"] != 0
+        counts["boards"] += int(searched.sum())
+        counts["mates"] += int((res["state"] == 1).sum())
+        counts["nodes"] += int(res["nodes"][searched].sum())
+    n = int(found.sum())
+    return (forced, n, res) if detail else (forced, n)
 
 
 # ---------------------------------------------------------------------- command lines: make_x (ValueError), add_x_args, x_from_args (ap.error)

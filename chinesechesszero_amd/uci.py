@@ -4,7 +4,10 @@ The reference's README (README.md:3) advertises "standard UCI protocol" but ship
 use everywhere are UCI coordinate strings ("a0a1", tools.py:172-269). This is that missing loop:
 ``uci``, ``isready``, ``ucinewgame``, ``position startpos|fen <fen> [moves ...]``, ``go [nodes N]``,
 ``setoption name Playouts|MultiPV value N``, ``setoption name Solver value true|false`` (MCTS-solver: ``score mate N``), ``setoption name LCB value true|false`` (``bestmove`` is the
-lower-confidence-bound move; ``LCBStdevs`` / ``LCBMinVisitRatio``: its numbers; the ``info`` lines stay as they are), ``d``, ``quit``. ``go`` reports one ``info depth .. multipv .. score cp .. nodes .. pv ..``
+lower-confidence-bound move; ``LCBStdevs`` / ``LCBMinVisitRatio``: its numbers; the ``info`` lines stay as they are),
+``setoption name MateSearch value PLIES`` / ``MateNodes value N`` (before the search, look for a forced mate by consecutive checks --
+``ccz_mate_search``, no evaluator call --: ``info depth D score mate N nodes <nodes> pv <move>`` and ``bestmove``; 0 = off), ``go mate N``
+(that search at 2N - 1 plies for this one command, falling back to the normal search), ``d``, ``quit``. ``go`` reports one ``info depth .. multipv .. score cp .. nodes .. pv ..``
 line per principal variation (``SelfPlayEngine.principal_variations``); ``cp`` is a display mapping of the first move's Q
 (``analyse.cp_of``). The search is ``MCTS_AI`` on the HIP engine (no CPU fallback).
 """
@@ -15,7 +18,7 @@ import sys
 import numpy as np
 
 from .game import RED, Board, Move, _SYMBOL
-from .options import SearchOptions
+from .options import MATE_MAX_NODES, MATE_MAX_PLIES, MATE_NODES, SearchOptions
 from .parameters import C_PUCT, PLAYOUT
 
 ENGINE_NAME = "cczero-mi355x"
@@ -69,6 +72,17 @@ def parse_position(tokens: list[str], validate: bool = True) -> Board:
     return board
 
 
+def go_mate_plies(tok):
+    """``go ... mate N``: the plies of the mate search of this one command, 2N - 1 clamped to the cap; None without ``mate``.
+    ValueError: N is missing, no integer, or < 1."""
+    if "mate" not in tok:
+        return None
+    i = tok.index("mate")
+    if i + 1 >= len(tok) or not tok[i + 1].lstrip("-").isdigit() or int(tok[i + 1]) < 1:
+        raise ValueError("go mate needs a number of moves >= 1")
+    return min(2 * int(tok[i + 1]) - 1, MATE_MAX_PLIES)
+
+
 class UciLoop:
     def __init__(self, policy_value_fn=None, n_playout: int = PLAYOUT, device: int = 0, out=sys.stdout):
         self.policy_value_fn = policy_value_fn
@@ -82,6 +96,8 @@ class UciLoop:
         self.width = 1               # Width: leaves per evaluator call (1: the sequential, scouted search)
         self.lcb = False             # LCB: bestmove is the lower-confidence-bound move (LCBStdevs / LCBMinVisitRatio: its numbers)
         self.lcb_opts = {}
+        self.mate_plies = 0          # MateSearch: plies of the mate search before every go (0: off); MateNodes: its budget (None: the default)
+        self.mate_nodes = None
         self.search_opts = {}        # FpuReduction / FpuAbsolute / CpuctBase / CpuctFactor as set; empty: the reference's PUCT
 
     def _search(self):
@@ -95,6 +111,11 @@ class UciLoop:
         from .options import make_lcb
         return make_lcb(self.lcb_opts.get("lcbstdevs", True), self.lcb_opts.get("lcbminvisitratio")) if self.lcb else None
 
+    def _mate(self, plies=None):
+        """The ``mate_search`` dict for the options set so far (None: off); ``plies``: of this one command (``go mate N``)."""
+        from .options import make_mate_search
+        return make_mate_search(self.mate_plies if plies is None else plies, self.mate_nodes if (plies or self.mate_plies) else None)
+
     def _set(self, **new) -> bool:
         """Set ``solver`` / ``width`` / ``search_opts`` if they still go together (``SearchOptions``); else say why not and leave all as it was."""
         old = {k: getattr(self, k) for k in new}
@@ -103,7 +124,7 @@ class UciLoop:
             self.width = int(self.width)
             if not 1 <= self.width <= 64:
                 raise ValueError(f"Width {self.width} must be in 1..64")
-            SearchOptions(self.n_playout, width=self.width, solver=self.solver, search=self._search(), lcb=self._lcb())
+            SearchOptions(self.n_playout, width=self.width, solver=self.solver, search=self._search(), lcb=self._lcb(), mate_search=self._mate())
         except ValueError as e:
             vars(self).update(old)
             self._say(f"info string error {e}")
@@ -165,6 +186,8 @@ class UciLoop:
             self._say("option name LCB type check default false")
             self._say("option name LCBStdevs type string default 5")
             self._say("option name LCBMinVisitRatio type string default 0.15")
+            self._say(f"option name MateSearch type spin default 0 min 0 max {MATE_MAX_PLIES}")
+            self._say(f"option name MateNodes type spin default {MATE_NODES} min 1 max {MATE_MAX_NODES}")
             self._say("option name FpuReduction type string default <empty>")
             self._say("option name FpuAbsolute type string default <empty>")
             self._say("option name CpuctBase type string default <empty>")
@@ -183,6 +206,11 @@ class UciLoop:
         elif cmd == "setoption" and len(tok) >= 5 and tok[1] == "name" and tok[2].lower() in ("lcbstdevs", "lcbminvisitratio"):
             try:
                 self._set(lcb_opts=dict(self.lcb_opts, **{tok[2].lower(): float(tok[4])}))
+            except ValueError as e:
+                self._say(f"info string error {e}")
+        elif cmd == "setoption" and len(tok) >= 5 and tok[1] == "name" and tok[2].lower() in ("matesearch", "matenodes"):
+            try:
+                self._set(**{"mate_plies" if tok[2].lower() == "matesearch" else "mate_nodes": int(tok[4])})
             except ValueError as e:
                 self._say(f"info string error {e}")
         elif cmd == "setoption" and len(tok) >= 5 and tok[1] == "name" and tok[2].lower() == "width":
@@ -217,7 +245,17 @@ class UciLoop:
                 self._say("bestmove (none)")
                 return True
             ai = self._player(nodes)
-            move, probs = ai.get_action(self.board, temp=1e-3, return_prob=True)
+            try:
+                mate = self._mate(go_mate_plies(tok))
+            except ValueError as e:
+                self._say(f"info string error {e}")
+                return True
+            move, probs = ai.get_action(self.board, temp=1e-3, return_prob=True, mate_search=mate)
+            if ai.last_mate is not None:     # a forced mate by checks: no playout ran, the tree holds nothing to report
+                _, dist, mate_nodes = ai.last_mate
+                self._say(f"info depth {dist} score mate {(dist + 1) // 2} nodes {mate_nodes} pv {Move.from_id(move).uci()}")
+                self._say(f"bestmove {Move.from_id(move).uci()}")
+                return True
             self._say_pvs(ai)
             rc = ai.mcts.root_children()
             self._say(f"info nodes {int(rc['root_visits'])} string visits {int(rc['visits'].max())}/{int(rc['visits'].sum())}")

@@ -735,6 +735,43 @@ int ccz_root_value_stats(ccz_engine *e, void *stream, float *s_host, float *root
 int ccz_lcb_moves(ccz_engine *e, void *stream, double z, double min_visit_ratio, int32_t min_visits, int32_t *moves_out_dev,
                   int32_t *child_out_dev, double *lcb_out_dev);
 
+/* ---- Mate search: forced mates by consecutive checks (additive to ABI 9) ---------------------------------------------------------------
+ * A stateless query like ccz_lcb_moves: asynchronous, one wave per board, no evaluator row, no engine state changed (no tree node, no
+ * board field, no counter, no error bit); it writes its four output arrays and nothing else, and keeps nothing for a snapshot.
+ *
+ * The definition. S, the side to move at a board's root position, is the attacker. Iterative deepening n = 1, 3, ..., max_plies:
+ *   attacker node with r plies left (r odd): the legal moves in `legal_moves` order (the configured move rank: the order of the tree's
+ *     children). A move after which the enemy king is not attacked is skipped; every other move leads to a defender node with r - 1
+ *     plies left. The first child that succeeds makes the node succeed; with none it fails.
+ *   defender node (the position after the attacker's move): with no legal move it is a mate and succeeds -- also at halfmove clock 120:
+ *     the sixty-move rule requires a legal move. Otherwise it FAILS if it is blocked, and fails if r - 1 == 0. Else every reply, in
+ *     order, leads to an attacker node with r - 2 left, and the first reply whose node fails makes the defender node fail.
+ *   an attacker node below the root is tested for blocked before it generates: a blocked one fails, and is not counted as a node.
+ *   blocked: the position (64-bit key, side to move included) equals an earlier position of the DFS path or one of the board's history
+ *     chain; or the halfmove clock, kept as ccz_finish_move keeps it (CCZ_RULE_PAWN_MOVE_RESETS_CLOCK included), has reached 120; or
+ *     the material is insufficient. This is stricter than the game's rules on purpose (ANY repeat blocks, not the fourth): a mate found
+ *     is a forced win under the engine's own game-end rules, the perpetual-check rule included. The search may miss mates (it never
+ *     looks at a quiet first move, nor past a repeat) and never invents one.
+ *   A node is one position whose legal moves are generated. Nodes are counted over the whole call, every iteration's root included;
+ *     the search stops the moment the count reaches node_budget.
+ * Per board (all int32 [n_boards], device memory):
+ *   state  0 not searched (the game is over, the board is parked, the slot lies past the active boards, or the history chain is full:
+ *            128 keys since the last zeroing move, where any deeper leaf raises CCZ_ERR_CHAIN -- here no error bit is set),
+ *          1 mate found, 2 no checking mate within max_plies, 3 the budget was reached;
+ *   dist   the plies of the first iteration that succeeded (odd), else 0;
+ *   move   the id of that iteration's succeeding root move -- the first such move in `legal_moves` order --, else -1;
+ *   nodes  the nodes counted; == node_budget exactly in state 3; 0 in state 0.
+ * Refused (an error with a message; no sticky bit): max_plies even or outside 1 .. CCZ_MATE_MAX_PLIES, node_budget outside
+ * 1 .. CCZ_MATE_MAX_NODES, a null output. The budget bounds the kernel's one loop, so a launch always ends. */
+#define CCZ_MATE_MAX_PLIES 31
+#define CCZ_MATE_MAX_NODES 131072
+#define CCZ_MATE_NONE 0
+#define CCZ_MATE_FOUND 1
+#define CCZ_MATE_NO_MATE 2
+#define CCZ_MATE_BUDGET 3
+int ccz_mate_search(ccz_engine *e, void *stream, int32_t max_plies, int32_t node_budget, int32_t *state_dev, int32_t *dist_dev,
+                    int32_t *move_dev, int32_t *nodes_dev);
+
 /* ---- Wide search: several pending leaves per board and step, with virtual loss (additive to ABI 9) -------------------------------------
  * Every board runs a strictly sequential MCTS by default: one leaf per board and lockstep step. That fills the chip at thousands of
  * boards and leaves it idle where boards are few (one game, a handful of analysed positions): the evaluator call costs the same for
