@@ -2487,6 +2487,18 @@ int ccz_debug_conv_stamps(unsigned long long *out_host)
     HIP_TRY(hipMemcpyFromSymbol(out_host, HIP_SYMBOL(g_cv_stamps), sizeof(unsigned long long) * 2048 * 2 * 16));
     return 0;
 }
+// diagnostic build only: wait / barrier cycle sums of the last launch with quad tiles (uint64 [4096][8][8], cczero_conv_g16.h g_g5q_stamps)
+int ccz_debug_g5q_stamps(unsigned long long *out_host, int clear)
+{
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpyFromSymbol(out_host, HIP_SYMBOL(g_g5q_stamps), sizeof(unsigned long long) * 4096 * 8 * 8));
+    if (clear) {
+        void *p = nullptr;
+        HIP_TRY(hipGetSymbolAddress(&p, HIP_SYMBOL(g_g5q_stamps)));
+        HIP_TRY(hipMemset(p, 0, sizeof(unsigned long long) * 4096 * 8 * 8));
+    }
+    return 0;
+}
 // diagnostic build only: per-board s_memtime stamps of the last k_step launch (uint64 [B*16])
 int ccz_debug_stamps(ccz_engine *e, void *stream, unsigned long long *out_host)
 {

@@ -84,13 +84,21 @@ constexpr int kG5QRows = 576;                              // rows per tile (36 
 constexpr int kG5QSlabRows = 864;                          // 54 cells
 constexpr int kG5QSlabBytes = kG5QSlabRows * 64;           // 55,296 B per 32-channel chunk: six staging passes of 8 KB + one of 6 KB
 constexpr int kG5QWBytes = 128 * 64;                       // one half-step of weights: 128 output channels
-constexpr int kG5QAOff = kG5Ring * kG5QWBytes;             // LDS: [weight ring | slab 0 | slab 1 | dump]
-constexpr int kG5QDump = kG5QAOff + 2 * kG5QSlabBytes;     // 8 x 1 KB: where waves 6-7 aim staging pass 6, which has no piece for them
-constexpr int kG5QLds = kG5QDump + 8 * 1024;
+// CCZ_G5Q_PAIR (A/B switch; 1 = what ships): the quad tile meets at ONE workgroup barrier per TWO half-steps -- a ring of six weight
+// slots, four ahead (g5_step, "the two-step ring"). 0 builds the body with a ring of five, three ahead, one barrier per half-step.
+#ifndef CCZ_G5Q_PAIR
+#define CCZ_G5Q_PAIR 1
+#endif
+constexpr bool kG5QPair = CCZ_G5Q_PAIR != 0;
+constexpr int kG5QRing = kG5QPair ? 6 : kG5Ring, kG5QAhead = kG5QPair ? 4 : kG5Ahead;
+constexpr int kG5QAOff = kG5QRing * kG5QWBytes;            // LDS: [weight ring | slab 0 | slab 1 | dump]
+constexpr int kG5QDump = kG5QAOff + 2 * kG5QSlabBytes;     // where waves 6-7 aim staging pass 6, which has no piece for them: 1 KB each
+constexpr int kG5QDumpWave0 = kG5QPair ? 6 : 0;            // (ring of five: a KB for each of the eight waves, six of them unused)
+constexpr int kG5QLds = kG5QDump + (8 - kG5QDumpWave0) * 1024;
 constexpr int kG5QERow = 272;                              // epilogue image: bytes per row (256 + pad)
-static_assert(kG5QLds == 159744 && kG5QLds <= kG5Lds, "quad tile: ring + two slabs + dump must fit the workgroup's LDS");
+static_assert(kG5QLds == (kG5QPair ? 161792 : 159744) && kG5QLds <= kG5Lds, "quad tile: ring + two slabs + dump must fit the workgroup's LDS");
 static_assert(kG5QRows * kG5QERow == 156672 && kG5QRows * kG5QERow <= kG5QLds,
-              "quad tile: the epilogue image covers the operand buffers AND most of the dump area (free once every DMA has landed)");
+              "quad tile: the epilogue image covers the operand buffers (ring of five: and most of the dump area), free once every DMA has landed");
 
 // Layout "G16C" (the CM forms): inside each 16-board group the rows are chunk-major -- [chunk 0..7][row 0..1439][32 channels], row
 // stride 64 B, chunk stride 92,160 B, the group stride (737,280 B) as in G16 -- so that a chunk's slab is one contiguous run of whole
@@ -119,6 +127,9 @@ struct G5Ctx {
     int a_off;               // weight fragment offset inside a ring slot (tile 0; tile i: + 1024 i)
     int vb[2];               // this lane's pixel-fragment base in slab 0 / 1 (cell 0 of the wave's rank at tap offset 0 = + 9 * 1024)
     int cin, cmask;          // input channels; number of 32-channel chunks - 1
+#ifdef CCZ_STAMPS
+    mutable unsigned long long st_vm, st_bar, st_n; // SCALAR, diagnostic build (G5Q_STAMP_ADD): cycles in the vmcnt waits / in the barriers, their count
+#endif
 };
 
 __host__ __device__ constexpr bool g5_slab_tap(int t) { return t >= 1 && t <= 5; }
@@ -144,6 +155,22 @@ static_assert(g5q_vmcnt(0) == 4 && g5q_vmcnt(1) == 5 && g5q_vmcnt(2) == 4 && g5q
 static_assert(g5q_dma(0) == 3 && g5q_dma(1) == 2 && g5q_dma(2) == 2 && g5q_dma(3) == 2 && g5q_dma(4) == 2 && g5q_dma(5) == 2 && g5q_dma(6) == 1 &&
               g5q_dma(7) == 1 && g5q_dma(8) == 1, "16 DMA loads per chunk and thread: 7 slab pieces + 9 weight pieces");
 
+// The two-step ring (kG5QPair): the barrier stands in the ODD half-steps J of the unrolled pair of chunks and publishes the slots of
+// half-steps J + 1 and J + 2; its wait still leaves the loads of half-steps J and J - 1 in flight, and with the weights four ahead
+// those are the pieces of half-steps J + 4 and J + 3. A chunk is nine half-steps, so in the second chunk (J = 9..17) the barrier in
+// front of the first slab read (half-step 8 of the chunk, J = 17) is the one of its half-step 6 (J = 15), not 7: there the seven slab
+// pieces go into half-steps 0..4 -- passes 0, 1 | 2, 3 | 4 | 5 | 6 -- and in the first chunk they stay where the ring of five has them.
+__host__ __device__ constexpr int g5q2_nslab(int j) { return j < 9 ? g5q_nslab(j) : j - 9 <= 1 ? 2 : j - 9 <= 4 ? 1 : 0; }
+__host__ __device__ constexpr int g5q2_pass(int j) { return j % 9 == 0 ? 0 : g5q2_pass(j - 1) + g5q2_nslab(j - 1); } // first staging pass of half-step j
+__host__ __device__ constexpr int g5q2_dma(int j) { return 1 + g5q2_nslab(j); }
+__host__ __device__ constexpr int g5q2_vmcnt(int j) { return g5q2_dma(j) + g5q2_dma((j + 17) % 18); }
+__host__ __device__ constexpr bool g5q2_barrier(int j) { return (j & 1) != 0; }
+static_assert(g5q2_vmcnt(1) == 5 && g5q2_vmcnt(3) == 4 && g5q2_vmcnt(5) == 4 && g5q2_vmcnt(7) == 2 && g5q2_vmcnt(9) == 4 && g5q2_vmcnt(11) == 5 &&
+              g5q2_vmcnt(13) == 4 && g5q2_vmcnt(15) == 2 && g5q2_vmcnt(17) == 2, "g5q2_vmcnt table (the odd half-steps wait)");
+static_assert(g5q2_pass(8) == 7 && g5q2_pass(17) == 7 && g5q2_pass(5) == 6 && g5q2_pass(13) == 6 && g5q2_nslab(6) == 0 && g5q2_nslab(14) == 0,
+              "seven slab pieces per chunk; the last one is issued in J = 5 resp. 13, two half-steps in front of the barriers of J = 7 resp. 15");
+static_assert(18 % kG5QRing == 0 || !kG5QPair, "the slot of a half-step is a compile-time function of J");
+
 template <int T, int N> __host__ __device__ constexpr bool g5_on_board() // is tap T of the cell with file N on the board (dx only)
 {
     return !((T % 3 == 0 && N == 0) || (T % 3 == 2 && N == 8));
@@ -158,6 +185,17 @@ template <bool LDS_DONE = false> __device__ __forceinline__ void g5_barrier()
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
 }
+
+// Diagnostic build (-DCCZ_STAMPS, profiles/conv_quad_stamps.py; the shipped kernels hold no stamp): what the quad tile's meeting point
+// costs a wave -- cycles in the counted vmcnt wait and in the barrier, summed over the tile's half-steps in scalar registers.
+#ifdef CCZ_STAMPS
+__device__ unsigned long long g_g5q_stamps[4096 * 8 * 8]; // [workgroup][wave]: vm wait, barrier, loop, real time of the loop, meetings
+#define G5Q_STAMP(s_) const unsigned long long s_ = cv_stamp();
+#define G5Q_STAMP_ADD(c_, s0_, s1_, s2_) (c_).st_vm += s1_ - s0_; (c_).st_bar += s2_ - s1_; (c_).st_n += 1;
+#else
+#define G5Q_STAMP(s_)
+#define G5Q_STAMP_ADD(c_, s0_, s1_, s2_)
+#endif
 
 // The rank above rank 0 (tiles with k = 0) and the rank below rank 9 (k = 4) do not exist: their slab rows were staged from
 // clamped addresses (the DMA count stays static) and are overwritten with zeros by the thread that staged them, after its DMA has
@@ -214,18 +252,21 @@ __device__ __forceinline__ void g5_step(const G5Ctx &c, cv_f32x4 (&acc)[4][9], i
     // off-board pairs) and is refilled once per dy, during the dx = +1 tap: b[N] is dead as soon as cell N - 1 has issued its
     // MFMAs there, so it is reloaded for the next dy right in front of cell N's MFMAs -- 27 fragment reads per chunk instead of 78.
 #define G5_REFILL(N) (9 + N + 9 * (Tn / 3 - 1))
-    constexpr int T2 = (T + kG5Ahead) % 9;
+    constexpr bool P = Q && kG5QPair;           // the two-step ring: a barrier in the odd half-steps only, slots by J (g5q2_vmcnt)
+    constexpr int kAhead = Q ? kG5QAhead : kG5Ahead;
+    constexpr int T2 = (T + kAhead) % 9;
     // Past the last chunk there is nothing left to prefetch, but every load is still ISSUED (the vmcnt counts stay static): its
     // descriptor then has zero records, the range check fails and nothing is fetched (cv_blds16)
-    const int chunk2 = chunk + (T + kG5Ahead >= 9 ? 1 : 0);
+    const int chunk2 = chunk + (T + kAhead >= 9 ? 1 : 0);
+    constexpr int nslab = !Q ? 0 : P ? g5q2_nslab(J) : g5q_nslab(T);
     G5_CELLS(T, 0, 1)
-    if constexpr (Q && g5q_nslab(T) > 0) { // the next chunk's slab: 7 pieces per thread, passes 0, 1 | 2 | .. | 6 in taps 0 | 1 | .. | 5
-        constexpr int pass = T == 0 ? 0 : T + 1;
+    if constexpr (nslab > 0) { // the next chunk's slab: 7 pieces per thread, passes 0, 1 | 2 | .. | 6 in taps 0 | 1 | .. | 5 (P, second chunk: g5q2_nslab)
+        constexpr int pass = P ? g5q2_pass(J) : T == 0 ? 0 : T + 1;
         const unsigned so = (unsigned)((chunk + 1) * (CM ? kG16CChunk : 64));
         const unsigned live = chunk < c.cmask ? (pass < 6 ? c.xbytes : c.xbytes_part) : 0u;
         cv_blds16(c.X, live, c.xoff[0], so + pass * c.xstep,
                   lds + (pass < 6 ? kAOff + (1 - BUF) * kSlab + pass * 8192 + c.wave_dst : c.wave_dst_part + (1 - BUF) * c.wave_step_part));
-        if constexpr (g5q_nslab(T) > 1) cv_blds16(c.X, live, c.xoff[0], so + (pass + 1) * c.xstep, lds + kAOff + (1 - BUF) * kSlab + ((pass + 1) * 8192 + c.wave_dst));
+        if constexpr (nslab > 1) cv_blds16(c.X, live, c.xoff[0], so + (pass + 1) * c.xstep, lds + kAOff + (1 - BUF) * kSlab + ((pass + 1) * 8192 + c.wave_dst));
         __builtin_amdgcn_sched_barrier(0);
     }
     if constexpr (!Q && g5_dma(T) > 2) { // the next chunk's slab: 5 pieces per thread, in taps 1..5
@@ -237,7 +278,8 @@ __device__ __forceinline__ void g5_step(const G5Ctx &c, cv_f32x4 (&acc)[4][9], i
     }
     G5_CELLS(T, 1, 2)
     if constexpr (Q) { // this tile's half (8 KB: rows 128 h .. 128 h + 127) of half-tile (chunk2, T2): one piece per thread
-        cv_blds16(c.W, chunk2 <= c.cmask ? c.wbytes : 0u, c.woff, (unsigned)((T2 + 9 * chunk2) * (2 * 8192)) + c.whalf, lds + ring_wr * kWB + c.wave_dst);
+        if constexpr (P) cv_blds16(c.W, chunk2 <= c.cmask ? c.wbytes : 0u, c.woff, (unsigned)((T2 + 9 * chunk2) * (2 * 8192)) + c.whalf, lds + ((J + kAhead) % kG5QRing) * kWB + c.wave_dst);
+        else cv_blds16(c.W, chunk2 <= c.cmask ? c.wbytes : 0u, c.woff, (unsigned)((T2 + 9 * chunk2) * (2 * 8192)) + c.whalf, lds + ring_wr * kWB + c.wave_dst);
         __builtin_amdgcn_sched_barrier(0);
         G5_CELLS(T, 2, 3)
     } else {
@@ -252,19 +294,42 @@ __device__ __forceinline__ void g5_step(const G5Ctx &c, cv_f32x4 (&acc)[4][9], i
     }
     G5_CELLS(T, 3, kG5Split)
 
-    ring_rd = ring_rd + 1 == kG5Ring ? 0 : ring_rd + 1;
-    cv_wait_vm<Q ? g5q_vmcnt(T) : g5_vmcnt(T)>();
-    if constexpr (!Q && T == 7) g5_zero_ranks(c, 1 - BUF); // this thread's slab pieces of the next chunk have landed (all but the youngest weight loads)
-    g5_barrier();
-
-    {
-        const unsigned char *wa = lds + (ring_rd * kWB + c.a_off);
+    if constexpr (P) {
+        // The two-step ring. An odd half-step waits for this thread's pieces of the slots of J + 1 and J + 2 (and, J = 7 and 15, of the
+        // next chunk's slab) and meets the other waves; an even one does neither: slot J + 1, which it reads below, was published by the
+        // barrier of J - 1. What a DMA of half-step J overwrites is slot J + 4 = J - 2 (mod 6): its readers loaded their fragments in
+        // J - 3 and spent them in the MFMAs of J - 2, in front of the last barrier this wave has passed (J - 1 or J - 2).
+        if constexpr (g5q2_barrier(J)) {
+            G5Q_STAMP(s0)
+            cv_wait_vm<g5q2_vmcnt(J)>();
+            G5Q_STAMP(s1)
+            g5_barrier();
+            G5Q_STAMP(s2)
+            G5Q_STAMP_ADD(c, s0, s1, s2)
+        } else __builtin_amdgcn_sched_barrier(0);
+        const unsigned char *wa = lds + (((J + 1) % kG5QRing) * kWB + c.a_off);
 #pragma unroll
         for (int i = 0; i < 4; ++i) anxt[i] = *(const cv_half8 *)(wa + i * 1024);
         __builtin_amdgcn_sched_barrier(0);
+        G5_CELLS(T, kG5Split, 9)
+    } else {
+        ring_rd = ring_rd + 1 == kG5Ring ? 0 : ring_rd + 1;
+        if constexpr (Q) { G5Q_STAMP(s0) cv_wait_vm<g5q_vmcnt(T)>(); G5Q_STAMP(s1) g5_barrier(); G5Q_STAMP(s2) G5Q_STAMP_ADD(c, s0, s1, s2) }
+        else {
+            cv_wait_vm<g5_vmcnt(T)>();
+            if constexpr (T == 7) g5_zero_ranks(c, 1 - BUF); // this thread's slab pieces of the next chunk have landed (all but the youngest weight loads)
+            g5_barrier();
+        }
+
+        {
+            const unsigned char *wa = lds + (ring_rd * kWB + c.a_off);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) anxt[i] = *(const cv_half8 *)(wa + i * 1024);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        G5_CELLS(T, kG5Split, 9)
+        ring_wr = ring_wr + 1 == kG5Ring ? 0 : ring_wr + 1;
     }
-    G5_CELLS(T, kG5Split, 9)
-    ring_wr = ring_wr + 1 == kG5Ring ? 0 : ring_wr + 1;
 #undef G5_REFILL
 }
 
@@ -648,7 +713,7 @@ __device__ __forceinline__ void g5q_tile(unsigned char *lds, int blk, int grid, 
 
     G5Ctx c;
     g5_ctx_common(c, lds, X, W, w, (unsigned)M * (unsigned)cin * 2u, cin, cin >> 5);
-    c.wave_dst_part = w < 6 ? kG5QAOff + 6 * 8192 + w * 1024 : kG5QDump + w * 1024;
+    c.wave_dst_part = w < 6 ? kG5QAOff + 6 * 8192 + w * 1024 : kG5QDump + (w - kG5QDumpWave0) * 1024;
     c.wave_step_part = w < 6 ? kG5QSlabBytes : 0;
     c.xbytes_part = w < 6 ? c.xbytes : 0u;
     c.xstep = CM ? 128u * 64u : 128u * (unsigned)cin * 2u;
@@ -662,34 +727,49 @@ __device__ __forceinline__ void g5q_tile(unsigned char *lds, int blk, int grid, 
         else c.xoff[0] = (unsigned)((p0 - 144 + sr) * cin + schunk * 8) * 2u;
         c.woff = (unsigned)(tid * 16);
     }
-    // ---- prologue: slab of chunk 0, this half's weight blocks of taps 0..2
+    // ---- prologue: slab of chunk 0, this half's weight blocks of the first kG5QAhead taps
 #pragma unroll
     for (int it = 0; it < 7; ++it)
         cv_blds16(X, it < 6 ? c.xbytes : c.xbytes_part, c.xoff[0], it * c.xstep, lds + (it < 6 ? kG5QAOff + it * 8192 + c.wave_dst : c.wave_dst_part));
 #pragma unroll
-    for (int u = 0; u < kG5Ahead; ++u) cv_blds16(W, c.wbytes, c.woff, (unsigned)(u * 2 * 8192) + c.whalf, lds + u * kG5QWBytes + c.wave_dst);
+    for (int u = 0; u < kG5QAhead; ++u) cv_blds16(W, c.wbytes, c.woff, (unsigned)(u * 2 * 8192) + c.whalf, lds + u * kG5QWBytes + c.wave_dst);
     g5_ctx_frags(c, r, q4, wm, wn * 9, kG5QAOff, kG5QSlabBytes); // weight rows 128 h + 64 wm + ..; slab cell 9 wn + n + 9 + delta
 
     cv_f32x4 acc[4][9];
 #pragma unroll
     for (int i = 0; i < 4; ++i) g5_acc_row_from_bias(acc[i], bias + h * 128 + wm * 64 + i * 16 + 4 * q4);
 
-    cv_wait_vm<2>(); // all but the weight blocks of taps 1 and 2
+    cv_wait_vm<2>(); // all but the weight blocks of the last two taps (two-step ring: slots 0 AND 1 are published here, half-step 0 has no barrier)
     g5_barrier();
 
-    int ring_rd = 0, ring_wr = kG5Ahead;
+    int ring_rd = 0, ring_wr = kG5QAhead; // (two-step ring: unused, a half-step's slots are functions of J)
     cv_half8 a0[4], a1[4], b[9];
 #pragma unroll
     for (int i = 0; i < 4; ++i) a0[i] = *(const cv_half8 *)(lds + c.a_off + i * 1024);
 #pragma unroll
     for (int n = 0; n < 9; ++n) b[n] = *(const cv_half8 *)(lds + c.vb[0] + n * 1024); // the rank above this wave's: dy = -1
+#ifdef CCZ_STAMPS
+    c.st_vm = c.st_bar = c.st_n = 0;
+    const unsigned long long st_loop0 = cv_stamp(), st_real0 = __builtin_amdgcn_s_memrealtime();
+    __builtin_amdgcn_s_waitcnt(0xC07F);
+#endif
     for (int chunk = 0; chunk <= c.cmask; chunk += 2) {
 #define G5Q_S(j) g5_step<j, true, CM>(c, acc, chunk + (j) / 9, ring_rd, ring_wr, a0, a1, b)
         G5Q_S(0); G5Q_S(1); G5Q_S(2); G5Q_S(3); G5Q_S(4); G5Q_S(5); G5Q_S(6); G5Q_S(7); G5Q_S(8);
         G5Q_S(9); G5Q_S(10); G5Q_S(11); G5Q_S(12); G5Q_S(13); G5Q_S(14); G5Q_S(15); G5Q_S(16); G5Q_S(17);
 #undef G5Q_S
     }
-    cv_wait_vm<0>(); // the out-of-range DMA loads (zeros) must have landed: the image below covers the dump area too
+#ifdef CCZ_STAMPS
+    {
+        const unsigned long long st_loop1 = cv_stamp(), st_real1 = __builtin_amdgcn_s_memrealtime();
+        __builtin_amdgcn_s_waitcnt(0xC07F);
+        if (blk < 4096 && lane == 0) { // a buffer of the stamps' own: nothing in the kernel reads it
+            unsigned long long *o = g_g5q_stamps + ((size_t)blk * 8 + w) * 8;
+            o[0] = c.st_vm; o[1] = c.st_bar; o[2] = st_loop1 - st_loop0; o[3] = st_real1 - st_real0; o[4] = c.st_n;
+        }
+    }
+#endif
+    cv_wait_vm<0>(); // the out-of-range DMA loads (zeros) must have landed before the image below is written over the operand buffers
 
     // ---- epilogue: every wave writes its 64 channels x 144 rows into the [row][channel] image; then wave w owns rows 72 w .. 72 w + 71
     g5_barrier(); // every wave is done reading the slabs and the ring
